@@ -36,6 +36,11 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
     parity        frame 0 rendered by the CPU oracle, compared with the GPU frame (max abs, bit equality, counts)
     cpu_baseline  the oracle timed on the host cores of this box (all cores and one thread, one pixel grid); N = 1 only
     regimes       (C3 only) the four {exact-0 air, noisy air} x {default ramp, zero-prefix TF} numbers, serial leg
+
+--dump-outputs DIR (one GPU): what the serial leg's last timed frame handed its caller, written after the clock stopped --
+DIR/frame.npy (float32 H x W x RGBA) and DIR/counters.npy (float64: composited samples, covered pixels, fetched samples).  A
+frame above DUMP_LIMIT_BYTES is written as a fixed, seeded sample of its pixels (N x RGBA, same sample for the same W x H).
+The inputs are synthetic and seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -87,6 +92,31 @@ PMC_EXTRA = [["TCP_PENDING_STALL_CYCLES_sum"],
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all .npy files together, headers included
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """Writes {name: array} as out_dir/<name>.npy, float32 / float64 only.  When the arrays exceed `limit`, the largest is cut to a
+    fixed, seeded sample of its pixels (rows of its last axis, kept in index order); the rest are written whole."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        if v.dtype not in (np.float32, np.float64):
+            raise TypeError(f"--dump-outputs: {k} is {v.dtype}, not float32 / float64")
+    header = 256  # bytes per .npy file above its data (numpy pads the header to a multiple of 64)
+    total = sum(v.nbytes + header for v in arrays.values())
+    if total > limit:
+        big = max(arrays, key=lambda k: arrays[k].nbytes)
+        rows = arrays[big].reshape(-1, arrays[big].shape[-1])
+        keep = (limit - (total - arrays[big].nbytes)) // rows[0].nbytes
+        idx = np.sort(np.random.default_rng(seed).choice(len(rows), size=int(keep), replace=False))
+        arrays[big] = rows[idx]
+        log(f"[bench] --dump-outputs: {big} cut to a seeded sample of {keep} of {len(rows)} pixels")
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return {k: list(v.shape) for k, v in arrays.items()}
 
 
 class stdout_to_stderr:
@@ -386,9 +416,15 @@ def main():
     ap.add_argument("--settle", type=int, default=24,
                     help="untimed LAUNCHES in front of every leg's warm-up (twice as many with launches in flight): the context measures its "
                          "candidate kernels on live frames (vr.h, flavour 0) and the leg then times the steady state")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the serial leg's last timed frame computed as DIR/<name>.npy (frame, counters; one GPU)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--pmc-identical", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
+    if args.dump_outputs and (args.gpus > 1 or os.environ.get("VR_BENCH_SELF_GATHER")):
+        ap.error("--dump-outputs: one GPU, one process (the frame of the serial leg)")
     if args.pmc_child:
         return pmc_child(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -588,10 +624,11 @@ def main():
             g += 1
         return g
 
-    def timed_leg(nbuf, n_warm, n_steps, min_events=0, fpl=1, present=False):
+    def timed_leg(nbuf, n_warm, n_steps, min_events=0, fpl=1, present=False, capture=None):
         """W warm-up + exactly K timed frames of the turntable (frames 0 .. W+K-1), barrier + synchronise on both sides; the MAX
         over ranks of the wall time.  Returns (seconds, kernel durations of the timed launches [+ extra frames up to
-        min_events], composited samples of the K timed frames, fetched samples of them)."""
+        min_events], composited samples of the K timed frames, fetched samples of them).  `capture` (a dict; one process, one
+        frame per launch) receives the last timed frame and its counters, read after the clock stopped."""
         ctx.hint_frames_in_flight(nbuf)  # what this leg's caller does: steers the default kernel choice (vr.h)
         if mg is not None:
             mg.set_frames_in_flight(1 if nbuf == 1 else 0)
@@ -605,6 +642,9 @@ def main():
         g1 = run_frames(g, n_steps, nbuf, fpl, present)
         sync_all()
         dt = time.perf_counter() - t0
+        if capture is not None:  # (before the extra frames below overwrite the buffer)
+            capture["frame"] = frames[(n_steps - 1) % nbuf].cpu().numpy()
+            capture["counters"] = np.array(ctx.counters(), dtype=np.float64)
         comp = sum(counts[x % n_seq][0] for x in range(g, g1))
         fetched = sum(counts[x % n_seq][2] for x in range(g, g1))
         if n_steps < min_events:  # the median below wants >= 20 event-timed frames (outside the K-step region)
@@ -636,7 +676,10 @@ def main():
                 "kernel_events": int(len(kt))}
 
     # ---- the legs -----------------------------------------------------------------------------------------------------
-    res_serial = timed_leg(1, args.warmup, args.steps, min_events=20)
+    dumped = {} if args.dump_outputs else None
+    res_serial = timed_leg(1, args.warmup, args.steps, min_events=20, capture=dumped)
+    if dumped is not None:
+        log(f"[bench] --dump-outputs: {dump_outputs(args.dump_outputs, dumped)} -> {args.dump_outputs}")
     # The legs' launches are timed from their own per-workgroup records (vr_kernel_times' default: two HIP events around
     # every launch cost the frame's stream 11 us, which the one-frame-at-a-time leg would pay).  The roofline's denominator is
     # measured the contract's way: HIP events on the launch stream around each of 20 more one-at-a-time frames, outside the

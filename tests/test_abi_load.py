@@ -53,8 +53,8 @@ def test_uniform_struct_layout_matches_header(tmp_path):
 
 
 def test_no_silent_cpu_fallback_without_gpu():
-    import torch
-    if torch.cuda.is_available():
+    import vrtest as vt
+    if vt.gpu_present():
         pytest.skip("GPU present")
     with pytest.raises(capi.VrError) as ei:
         capi.Context(64, 64)

@@ -20,9 +20,9 @@ def build(tmp_path):
 
 
 def test_example_builds_and_has_no_cpu_fallback(tmp_path):
-    import torch
+    import vrtest as vt
     exe = build(tmp_path)
-    if torch.cuda.is_available():
+    if vt.gpu_present():
         pytest.skip("GPU present")
     r = subprocess.run([exe], capture_output=True, text=True, cwd=tmp_path)
     assert r.returncode == 2 and "no CPU fallback" in r.stderr

@@ -3,6 +3,8 @@
 Bar: BIT-EXACT f32 frames and identical composited-sample counts (tolerance stated by BASELINE.json is
 <= 1e-4 max-abs per channel; both implementations follow the same normative operation order, so 0 is expected
 and asserted; the 1e-4 bound is asserted separately so a future relaxation is visible)."""
+import os
+
 import numpy as np
 import pytest
 
@@ -771,7 +773,11 @@ def test_context_streams_for_frames_in_flight(ctx):
     u = hr.make_uniforms(W, H, steps_count=count, step_size=step)
     ref, _, n_ref = vt.gpu_render(ctx, capi.LIGHT, u, vols, tfs)
     ss = [ctx.stream(i) for i in range(4)]
-    assert all(ss) and len(set(ss)) >= 2          # at least two distinct streams that overlap
+    # a probed stream shares a hardware queue with no other probed stream and not with the context's sort stream: the HIP
+    # runtime's queues per device (GPU_MAX_HW_QUEUES, 4 by default) less one -- at least two distinct streams that overlap
+    # with the default, exactly one where the runtime is limited to two queues
+    queues = int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))
+    assert all(ss) and min(2, queues - 1) <= len(set(ss)) <= queues - 1
     assert ctx.stream(0) == ss[0]                  # stable handles
     others = [capi.Context(W, H, 0) for _ in range(4)]
     try:

@@ -1,5 +1,8 @@
 """Shared helpers for the parity tests (harness only)."""
 import ctypes as C
+import functools
+import subprocess
+import sys
 
 import numpy as np
 
@@ -8,6 +11,17 @@ import oracle_binding as ob
 from volumerendering_amd import capi
 
 f32 = np.float32
+
+
+@functools.lru_cache(maxsize=None)
+def gpu_present() -> bool:
+    """Whether torch sees a GPU, asked in a child process.  torch ships its own HIP runtime: started in the test process after
+    libvr_hip.so has loaded the system one, it is a second runtime that takes the device, and every later vr_create fails."""
+    r = subprocess.run([sys.executable, *(["-s"] if sys.flags.no_user_site else []), "-c",
+                        "import sys, torch; sys.exit(0 if torch.cuda.is_available() else 3)"],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode in (0, 3), (r.returncode, r.stderr[-2000:])
+    return r.returncode == 0
 
 
 def to_capi_uniforms(u):
