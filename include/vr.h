@@ -309,7 +309,7 @@ int vr_last_block_trace(vr_ctx* ctx, uint64_t* out, int capacity);
 /* Kernel flavour for A/B measurements.  All flavours are bit-identical in output and in the composited / covered counts; the
  * FETCHED count (vr_last_counters out[2]) is the same for all but 1 and 16, which skip nothing and fetch every composited sample
  * -- the default may pick 16 for volumes with next to nothing to skip, so `fetched` can differ between frames of one scene.
- * (2, 3, 4, 5, 9 and 14 exist only in builds with -DVR_EXPERIMENTAL_FLAVOURS=1: vr_experimental_flavours below.)
+ * 2, 3, 4, 5, 9 and 14 were forms that lost every A/B and have been removed (HISTORY.md): VR_ERR_UNSUPPORTED.
  *   0  default: a MEASURED choice.  Every form below gives the same bits, so the context tries the eligible ones on the
  *      caller's own frames -- three launches each (frames in flight + 3 with launches in flight), behind a few launches of the
  *      prior's pick so that a launch order exists -- and keeps the fastest by the launches' own records (no synchronisation: the
@@ -320,12 +320,7 @@ int vr_last_block_trace(vr_ctx* ctx, uint64_t* out, int capacity);
  *      frames in flight and the chain length of an earlier launch), 17 / 16, 6, 18, and 10 / 11 (launches that leave the machine
  *      part empty) or 12.  vr_kernel_choice reports what was measured.  VR_EXP_TUNE=0 in the environment: the prior alone.
  *   1  one lane per ray, no empty-space skipping (every composited sample is fetched)
- *   2 / 3  LDS wave tiles without / with skipping (lit shader only; others fall back to 1 / 6)
- *   4  skipping + closed-form leaping (f32 accumulation as integer arithmetic on the bit patterns)
- *      (launches of several frames exist for the plain, run and depth-parallel loop forms: there 2 runs as 1 and 3 / 4 / 9 as 6)
- *   5  skipping alone, one step per iteration
  *   6  one lane per ray (forced), 7  four lanes per ray (forced), 8  two lanes per ray (forced)
- *   9  one lane per ray with the next step's corner loads software-pipelined behind the shading
  *   10 / 11  four / two lanes per ray with the next round's corner loads software-pipelined (lit shader; what
  *      the default uses for small launches)
  *   12 / 13  persistent wavefronts (csrc/vr_pw.h): one workgroup of 16 wavefronts per CU, the packets come from a queue
@@ -344,9 +339,6 @@ int vr_last_block_trace(vr_ctx* ctx, uint64_t* out, int capacity);
  *      clamp-to-edge texel pair of a coordinate is one ds_read2_b32; filled per workgroup, by the workgroups that can hit the box);
  *      the shaders that sample one volume (lit, unlit, in-shader gradient) on the bricked copy, launches of any number of frames;
  *      else it runs as 6
- *   14  (experimental build) lanes per ray chosen PER PACKET (csrc/vr_mixed.h): packets whose longest ray chain in an earlier
- *      launch of the same shape reached 75 % of that launch's longest are marched as two half packets with two lanes per ray,
- *      the rest with one; one-frame launches of the shaders that have a depth-parallel form
  *   15  the voxels of a packet's next four steps in an LDS tile filled by LDS-DMA (csrc/vr_lt.h): lit shader, launches of
  *       one frame (other launches run 6); never picked by the default -- slower than 17 / 16 wherever measured            */
 int vr_set_kernel_flavour(vr_ctx* ctx, int flavour);
@@ -356,11 +348,6 @@ int vr_set_kernel_flavour(vr_ctx* ctx, int flavour);
  * running: the prior's pick, flavours[0], runs meanwhile).  Returns the number of candidates (0: nothing launched through the
  * default yet, or the shape has a single eligible form).                                                               */
 int vr_kernel_choice(vr_ctx* ctx, int flavours[6], float ms_per_launch[6], int* chosen);
-
-/* 1 if the library was built with -DVR_EXPERIMENTAL_FLAVOURS=1: the kernel forms that lost every A/B -- flavours 2, 3, 4, 5, 9,
- * 14 and volume layout 2 -- are then compiled in; 0 (the shipped build): vr_set_kernel_flavour / vr_set_volume_layout return
- * VR_ERR_UNSUPPORTED for them.                                                                                           */
-int vr_experimental_flavours(void);
 
 /* Arithmetic mode.  WGSL leaves it to the implementation whether `a * b + c` is evaluated with one rounding or two
  * (the reference's Tint -> HLSL -> D3D12 back end emits `mad`).
@@ -383,22 +370,16 @@ int vr_set_arithmetic(vr_ctx* ctx, int mode);
  *      and vr_volume_download returns) stays resident beside it; the copy is rebuilt after every upload / in-place change
  *   3  round 2's default: the reference's x-fastest vec4 voxels + an x-fastest density plane
  *   1  the reference's RGBA32F voxels only (16 B / voxel; what round 1 measured)
- *   2  0 + the lit shader derives the eight corner gradients from the plane on the fly when the slot's .rgb is verified,
- *      at upload, to be VolumeFile::PreComputeGradient(false) of its .a bit for bit (VolumeFile.cpp:196-257): a quarter of
- *      the footprint and 0.69x the fabric traffic, but 1.5x the L1 accesses of the row-major plane -- measured slower
- *      (DESIGN.md section 4.5), kept for A/B
- * vr_volume_layout: *flags bit 0 = density plane present, bit 1 = .rgb verified as the central difference of .a,
- * bit 2 = the last render derived its gradients on the fly, bit 3 = the bricked copy is what the gathers read.  */
+ *   2  (removed: the lit shader's gradients derived from the plane on the fly -- measured slower)
+ *      VR_ERR_UNSUPPORTED
+ * vr_volume_layout: *flags bit 0 = density plane present, bit 1 = .rgb verified, at upload, as the central difference of .a
+ * (VolumeFile::PreComputeGradient(false), VolumeFile.cpp:196-257, bit for bit), bit 2 = no longer set (it said the last
+ * render derived its gradients on the fly: layout 2), bit 3 = the bricked copy is what the gathers read.  */
 int vr_set_volume_layout(vr_ctx* ctx, int mode);
 int vr_volume_layout(vr_ctx* ctx, int slot, int* flags);
 
 /* The flavour the last render actually ran (what 0 resolved to for that launch), or a negative vr_status. */
 int vr_last_kernel_flavour(vr_ctx* ctx);
-
-/* Flavour 14 (lanes per ray chosen per packet): how many 8x8 packets the last launch marched as two half packets with two
- * lanes per ray -- 0 until an item list of an earlier launch of the same shape exists (the fourth launch or so), or when the
- * last launch was of another flavour.  Negative vr_status on error.                                                      */
-int vr_last_split_packets(vr_ctx* ctx);
 
 #ifdef __cplusplus
 }

@@ -170,6 +170,14 @@ def test_error_behaviour(ctx):
         c.render(99)
     with pytest.raises(capi.VrError):
         c.tf_upload(5, np.zeros(4, f32), np.zeros((4, 4), f32))
+    # the kernel forms that lost every A/B were removed: asking for one is refused, not quietly run as another form
+    for flavour in (2, 3, 4, 5, 9, 14):
+        with pytest.raises(capi.VrError) as e:
+            c.set_kernel_flavour(flavour)
+        assert e.value.code == capi.VR_ERR_UNSUPPORTED and "removed" in str(e.value), flavour
+    with pytest.raises(capi.VrError) as e:
+        c.set_volume_layout(2)
+    assert e.value.code == capi.VR_ERR_UNSUPPORTED and "removed" in str(e.value)
     c.close()
 
 
@@ -235,7 +243,7 @@ def test_skipping_with_hostile_values(ctx):
     tf = zero_prefix_tf(32, 3)
     for variant in (capi.BASIC, capi.LIGHT, capi.LIGHT_INSHADER):
         ref, n_ref, _ = ob.render(variant, u, [v], [tf], W, H, nthreads=8)
-        for flavour in vt.flavours(0, 1, 5, 6, 8, 9, 11, 12, 13, 14, 15, 16, 17, 18):  # every loop form and lanes-per-ray layout
+        for flavour in (0, 1, 6, 8, 11, 12, 13, 15, 16, 17, 18):  # every loop form and lanes-per-ray layout
             ctx.set_kernel_flavour(flavour)
             frag, _, ns = vt.gpu_render(ctx, variant, u, [v], [tf])
             assert same(frag, ref) and ns == n_ref, (variant, flavour)
@@ -250,7 +258,7 @@ def test_skipping_with_hostile_values(ctx):
         for variant in (capi.BASIC, capi.LIGHT):
             ref, n_ref, _ = ob.render(variant, u, [lone], [tf], W, H, nthreads=8)
             assert np.isnan(ref).any()
-            for flavour in vt.flavours(0, 6, 11, 12, 13, 15, 16, 17, 18):
+            for flavour in (0, 6, 11, 12, 13, 15, 16, 17, 18):
                 ctx.set_kernel_flavour(flavour)
                 frag, _, ns = vt.gpu_render(ctx, variant, u, [lone], [tf])
                 assert same(frag, ref) and ns == n_ref, (bad, where, variant, flavour)
@@ -317,34 +325,6 @@ def test_volume_mask_skipping_respects_the_mask(ctx):
     assert ctx.counters()[2] == ns
 
 
-@pytest.mark.skipif(not vt.experimental(), reason="flavours 2 / 3 need VR_EXPERIMENTAL_FLAVOURS=1")
-@pytest.mark.parametrize("flavour", [2, 3])
-def test_lds_wave_tile_flavours_are_exact(ctx, flavour):
-    """Flavours 2 / 3 stage the voxels of the lit shader through LDS wave tiles: same frame, same counts."""
-    cases = [
-        (96, 80, 24, dict(yaw=0.6, pitch=0.35)),
-        (130, 70, 40, dict(yaw=2.5, pitch=-1.0, distance=0.8)),
-        (64, 48, 16, dict(yaw=0.0, pitch=0.0, distance=5.0)),
-        (65, 33, 32, dict(yaw=-0.9, pitch=1.2, distance=0.75)),
-    ]
-    try:
-        for (W, H, n, cam) in cases:
-            vols, tfs = vt.scene(capi.LIGHT, n=n)
-            step, count = hr.stepping_params(n, n, n)
-            for extra in (dict(), dict(clip_x=(0.2, 0.1), clip_z=(0.1, 0.0)), dict(toggles=(1, 1, 0, 0))):
-                u = hr.make_uniforms(W, H, steps_count=count, step_size=step, **cam, **extra)
-                ctx.set_kernel_flavour(flavour)
-                check(ctx, capi.LIGHT, u, vols, tfs, W, H)
-        # anisotropic grid + a box too large for the tile at grazing distance (falls back per pair of steps)
-        raw = hr.ct_phantom_raw(24)[:10, :17, :]
-        v = ob.precompute_gradient(ob.normalize_data(hr.raw_to_vec4(raw)))
-        tf = (hr.default_opacity_tf(32), hr.default_color_tf(32))
-        u = hr.make_uniforms(64, 48, steps_count=41, step_size=1 / 24, distance=0.62, yaw=0.1, pitch=0.05)
-        check(ctx, capi.LIGHT, u, [v], [tf], 64, 48)
-    finally:
-        ctx.set_kernel_flavour(0)
-
-
 def test_skipping_on_a_mostly_empty_volume(ctx):
     """A 96^3 volume that is almost entirely exactly-zero air (long inert runs), cameras from many sides, clips and
     variable step: the skipping kernel must equal the oracle and count the same samples."""
@@ -370,7 +350,7 @@ def test_skipping_on_a_mostly_empty_volume(ctx):
                 assert ctx.counters()[2] < 0.5 * ns
 
 
-@pytest.mark.parametrize("flavour", vt.flavours(4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 15, 16, 17, 18))
+@pytest.mark.parametrize("flavour", [6, 7, 8, 10, 11, 12, 13, 15, 16, 17, 18])
 def test_exact_leaping_flavour(ctx, flavour):
     """Every way of getting through empty space and every lanes-per-ray layout must reproduce the step-by-step
     accumulation bit for bit (frames AND sample counts): 5 single steps, 6 wave-uniform runs of plain additions,
@@ -408,7 +388,7 @@ def test_exact_leaping_flavour(ctx, flavour):
         ctx.set_kernel_flavour(0)
 
 
-@pytest.mark.parametrize("flavour", vt.flavours(6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18))
+@pytest.mark.parametrize("flavour", [6, 7, 8, 10, 11, 12, 13, 15, 16, 17, 18])
 @pytest.mark.parametrize("variant", range(8))
 def test_every_variant_every_layout(ctx, variant, flavour):
     """The default picks the lanes per ray from the launch size (small test frames always get four); every layout is
@@ -436,7 +416,7 @@ def test_default_layout_follows_launch_size(ctx):
     ctx.resize(W, H)
     try:
         frames = []
-        for fl in vt.flavours(0, 6, 7, 8, 10, 11, 12, 13, 15, 16, 17, 18):
+        for fl in (0, 6, 7, 8, 10, 11, 12, 13, 15, 16, 17, 18):
             ctx.set_kernel_flavour(fl)
             frag, _, n = vt.gpu_render(ctx, capi.LIGHT, u, vols, tfs)
             frames.append((vt.bits(frag), n))
@@ -534,11 +514,11 @@ def test_two_frames_in_flight_on_two_streams(ctx):
             hip.hipFree(bufs[i])
 
 
-# ---- volume layout in HBM: density plane + gradients on the fly (vr_set_volume_layout) --------------------------------
+# ---- volume layout in HBM: bricked copy, vec4 voxels, density plane (vr_set_volume_layout) -------------------------------
 def test_density_plane_and_on_the_fly_gradients_are_exact(ctx):
-    """Layout 0 (density plane for .a fetches), 1 (the reference's vec4 voxels only) and 2 (0 + the lit shader derives the
-    corner gradients from the plane when the voxels' .rgb is verified to be PreComputeGradient(false) of .a) give the same
-    bits and counts as the oracle, for every shader; the verification recognises derived and foreign gradients."""
+    """Layout 0 (the bricked copy), 1 (the reference's vec4 voxels only) and 3 (x-fastest voxels + density plane) give the
+    same bits and counts as the oracle, for every shader; the upload recognises gradients derived from .a.  (Layout 2, the
+    gradients derived on the fly, was removed: vr_volume_layout's bit 2 stays clear.)"""
     W, H = 88, 60
     step, count = hr.stepping_params(24, 24, 24)
     try:
@@ -548,7 +528,7 @@ def test_density_plane_and_on_the_fly_gradients_are_exact(ctx):
                 args = dict(steps_count=count, step_size=step)
                 args.update(kw)
                 u = hr.make_uniforms(W, H, **args)
-                for mode in vt.layouts(0, 1, 2, 3):
+                for mode in (0, 1, 3):
                     ctx.set_volume_layout(mode)
                     for fl in (0, 6, 1):
                         ctx.set_kernel_flavour(fl)
@@ -556,69 +536,10 @@ def test_density_plane_and_on_the_fly_gradients_are_exact(ctx):
                         if variant == capi.LIGHT:
                             flags = ctx.volume_layout(0)
                             assert flags & 1 and flags & 2            # plane present, gradient recognised as derived
-                            assert bool(flags & 4) == (mode == 2 and ctx.last_kernel_flavour() in (1, 4, 5, 6, 9))
+                            assert not flags & 4                      # nothing derived on the fly
     finally:
         ctx.set_volume_layout(0)
         ctx.set_kernel_flavour(0)
-
-
-@pytest.mark.skipif(not vt.experimental(), reason="volume layout 2 needs VR_EXPERIMENTAL_FLAVOURS=1")
-def test_gradient_verification_and_boundary_cells(ctx):
-    W, H = 72, 56
-    ctx.set_kernel_flavour(6)
-    ctx.set_volume_layout(2)
-    try:
-        # tiny and ragged grids: cells touch the faces everywhere (n < 4: the generic corner path only)
-        for shape in [(3, 3, 3), (2, 5, 9), (4, 4, 4), (5, 4, 7), (1, 8, 8), (9, 1, 6)]:
-            raw = hr.ct_phantom_raw(16)[5: 5 + shape[0], 4: 4 + shape[1], 3: 3 + shape[2]]  # from inside the body
-            v = ob.precompute_gradient(ob.normalize_data(hr.raw_to_vec4(raw)))
-            tf = (hr.default_opacity_tf(32), hr.default_color_tf(32))
-            for cam in (dict(), dict(yaw=1.9, pitch=0.8, distance=0.75)):
-                u = hr.make_uniforms(W, H, steps_count=45, step_size=1 / 24, **cam)
-                check(ctx, capi.LIGHT, u, [v], [tf], W, H)
-                assert ctx.volume_layout(0) & 6 == 6
-        # constant medium: interior gradients are -0.0 (the bits PreComputeGradient produces), recognised and reproduced
-        c = ob.precompute_gradient(np.full((12, 12, 12, 4), 0.4, dtype=f32))
-        assert np.signbit(c[5, 5, 5, 0]) and c[5, 5, 5, 0] == 0
-        u = hr.make_uniforms(W, H, steps_count=30, step_size=1 / 12)
-        check(ctx, capi.LIGHT, u, [c], [(hr.default_opacity_tf(16), hr.default_color_tf(16))], W, H)
-        assert ctx.volume_layout(0) & 6 == 6
-        # foreign gradients: normalised to [0,1], +0.0 instead of -0.0, one voxel off by an ulp, a NaN -> vec4 fetch
-        n = 16
-        base = ob.precompute_gradient(ob.normalize_data(hr.raw_to_vec4(hr.ct_phantom_raw(n))))
-        for spoil in ("norm01", "pluszero", "ulp", "nan"):
-            v = base.copy()
-            if spoil == "norm01":
-                v = ob.precompute_gradient(ob.normalize_data(hr.raw_to_vec4(hr.ct_phantom_raw(n))), True)
-            elif spoil == "pluszero":
-                z = (v[..., :3] == 0) & np.signbit(v[..., :3])
-                assert z.any()
-                v[..., :3][z] = 0.0
-            elif spoil == "ulp":
-                v[7, 8, 9, 1] = np.nextafter(v[7, 8, 9, 1], f32(1))
-            else:
-                v[3, 3, 3, 2] = np.nan
-            u = hr.make_uniforms(W, H, steps_count=27, step_size=1 / 16)
-            frag, _, ns = vt.gpu_render(ctx, capi.LIGHT, u, [v], [(hr.default_opacity_tf(32), hr.default_color_tf(32))])
-            ref, n_ref, _ = ob.render(capi.LIGHT, u, [v], [(hr.default_opacity_tf(32), hr.default_color_tf(32))], W, H, nthreads=8)
-            assert same(frag, ref) and ns == n_ref, spoil
-            assert ctx.volume_layout(0) & 7 == 1, spoil   # plane present, gradient NOT derived, nothing derived on the fly
-        # in-place preparation on the device keeps the plane and the verdict current
-        ctx.volume_upload_raw(0, hr.ct_phantom_raw(n))
-        assert ctx.volume_layout(0) & 2 == 0              # raw value broadcast to all lanes: not a gradient
-        ctx.volume_normalize(0)
-        ctx.volume_precompute_gradient(0)
-        assert ctx.volume_layout(0) & 2
-        ctx.tf_upload(0, hr.default_opacity_tf(32), hr.default_color_tf(32))
-        u = hr.make_uniforms(W, H, steps_count=27, step_size=1 / 16)
-        ctx.set_uniforms(vt.to_capi_uniforms(u))
-        ctx.render(capi.LIGHT)
-        frag, _, ns = ctx.download()
-        ref, n_ref, _ = ob.render(capi.LIGHT, u, [base], [(hr.default_opacity_tf(32), hr.default_color_tf(32))], W, H, nthreads=8)
-        assert np.array_equal(vt.bits(frag), vt.bits(ref)) and ns == n_ref and ctx.volume_layout(0) & 4
-    finally:
-        ctx.set_kernel_flavour(0)
-        ctx.set_volume_layout(0)
 
 
 def test_longest_first_launch_order_changes_nothing(ctx):
@@ -676,7 +597,7 @@ def test_fused_every_variant_every_loop_form(fused, variant):
     W, H = 70, 45
     vols, tfs = vt.scene(variant, n=24)
     step, count = hr.stepping_params(24, 24, 24)
-    for fl in vt.flavours(0, 1, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18):
+    for fl in (0, 1, 6, 7, 8, 10, 11, 12, 13, 15, 16, 17, 18):
         fused.set_kernel_flavour(fl)
         for kw in (dict(), dict(clip_x=(0.2, 0.1), clip_z=(0.0, 0.3)), dict(toggles=(1, 1, 0, 0), yaw=2.0, pitch=-0.4),
                    dict(distance=0.7, yaw=1.0)):
@@ -696,7 +617,7 @@ def test_fused_empty_space_skipping_is_exact(fused, variant, zeros):
     for cam in (dict(yaw=0.9, pitch=-0.3), dict(yaw=-2.1, pitch=0.6, distance=0.85)):
         u = hr.make_uniforms(W, H, steps_count=count, step_size=step, **cam)
         outs = []
-        for fl in vt.flavours(0, 1, 5, 11, 12, 13, 15, 16, 17, 18):
+        for fl in (0, 1, 11, 12, 13, 15, 16, 17, 18):
             fused.set_kernel_flavour(fl)
             frag, n_s = check(fused, variant, u, vols, tfs, W, H)
             outs.append((vt.bits(frag), n_s))
@@ -709,7 +630,7 @@ def test_fused_layouts_hostile_values_and_mode_switching(fused):
     vols, tfs = vt.scene(capi.LIGHT, n=24)
     step, count = hr.stepping_params(24, 24, 24)
     u = hr.make_uniforms(W, H, steps_count=count, step_size=step)
-    for mode in vt.layouts(0, 1, 2, 3):
+    for mode in (0, 1, 3):
         fused.set_volume_layout(mode)
         for fl in (6, 1):
             fused.set_kernel_flavour(fl)
@@ -915,10 +836,10 @@ def test_kernel_times_from_the_launch_records_agree_with_events(ctx):
         warnings.warn(f"HIP events read {excess * 1e3:.0f} us more than the launch records (busy box?): {list(kt)} vs {ev}")
 
 
-@pytest.mark.parametrize("mode", ["fused"] + (["otf"] if vt.experimental() else []))
+@pytest.mark.parametrize("mode", ["fused"])
 def test_batched_launches_in_the_other_kernel_families(ctx, mode):
-    """The batch instantiations of the fused-arithmetic kernels (namespace vrf) and of the gradients-on-the-fly kernel are
-    separate code: each frame of a four-frame launch equals the single-frame render of the same mode bit for bit."""
+    """The batch instantiations of the fused-arithmetic kernels (namespace vrf) are separate code: each frame of a four-frame
+    launch equals the single-frame render of the same mode bit for bit."""
     W, H = 136, 100
     ctx.resize(W, H)
     vols, tfs = vt.scene(capi.LIGHT, n=24)
@@ -926,17 +847,12 @@ def test_batched_launches_in_the_other_kernel_families(ctx, mode):
     us = _batch_uniforms(W, H, count, step)
     others = [capi.Context(W, H, 0) for _ in range(4)]
     try:
-        if mode == "fused":
-            ctx.set_arithmetic(capi.ARITH_FUSED)
-        else:
-            ctx.set_volume_layout(2)
+        ctx.set_arithmetic(capi.ARITH_FUSED)
         refs = [vt.gpu_render(ctx, capi.LIGHT, u, vols, tfs) for u in us]
         for flavour in (0, 6, 11):
             ctx.set_kernel_flavour(flavour)
             ctx.render_batch_async(capi.LIGHT, [vt.to_capi_uniforms(u) for u in us], [o.frame_device_ptr() for o in others], ctx.stream(0))
             assert ctx.counters()[0] == refs[3][2]
-            if mode == "otf" and flavour == 6:   # (the one-lane kernel; small default launches take the depth-parallel ones)
-                assert ctx.volume_layout(0) & 4   # the launch really derived its gradients from the density plane
             ctx.resize(W, H)
             for o, ref in zip(others, refs):
                 got, _, _ = o.download()
@@ -944,7 +860,6 @@ def test_batched_launches_in_the_other_kernel_families(ctx, mode):
     finally:
         ctx.set_kernel_flavour(0)
         ctx.set_arithmetic(capi.ARITH_SEPARATE)
-        ctx.set_volume_layout(0)
         for o in others:
             o.close()
 
@@ -1060,72 +975,6 @@ def test_two_steps_ahead_jumps_idle_rays_and_the_last_steps(ctx, variant):
     finally:
         ctx.set_kernel_flavour(0)
         ctx.resize(96, 80)
-
-
-# ---- lanes per ray chosen per packet (flavour 14, csrc/vr_mixed.h) -----------------------------------------------------------
-@pytest.mark.skipif(not vt.experimental(), reason="flavour 14 needs VR_EXPERIMENTAL_FLAVOURS=1")
-@pytest.mark.parametrize("variant", [capi.BASIC, capi.LIGHT, capi.VOLUME_MASK, capi.THREE_FILES, capi.MULTI_CTRT, capi.TF_CALIB])
-def test_mixed_lanes_per_ray_per_packet(ctx, variant, monkeypatch):
-    """Flavour 14: from the fourth launch or so the packets with the longest chains are marched as two half packets with two
-    lanes per ray (an item list built behind an earlier launch), the others with one: every launch -- before and after the
-    list exists, with a moving camera that makes it stale -- is bit-equal to the oracle, the sample counts included, and the
-    per-packet records (summed over the two halves) equal the one-lane kernel's."""
-    W, H = 200, 150
-    vols, tfs = vt.scene(variant, n=32)
-    step, count = hr.stepping_params(32, 32, 32)
-    cams = [dict(yaw=0.6 + 0.01 * k) for k in range(8)] + [dict(yaw=2.0, pitch=-0.5, distance=0.9)] * 2 + [dict(clip_x=(0.2, 0.1))] * 4
-    monkeypatch.setenv("VR_EXP_SPLIT_MIN", "4")  # (the default floor of 64 samples: a 32^3 volume has no chain that long)
-    ctx = capi.Context(W, H)
-    try:
-        ctx.set_kernel_flavour(14)
-        split_seen = 0
-        for k, cam in enumerate(cams):
-            u = hr.make_uniforms(W, H, steps_count=count, step_size=step, **cam)
-            check(ctx, variant, u, vols, tfs, W, H)
-            assert ctx.last_kernel_flavour() == 14
-            split_seen = max(split_seen, ctx.last_split_packets())
-        assert split_seen > 0  # the list came into use
-        # records: the mixed launch's (halves combined) against the one-lane kernel's, same camera
-        u = hr.make_uniforms(W, H, steps_count=count, step_size=step, **cams[-1])
-        recs = []
-        for fl in (14, 6):
-            ctx.set_kernel_flavour(fl)
-            for _ in range(6):
-                vt.gpu_render(ctx, variant, u, vols, tfs)
-            if fl == 14:
-                assert ctx.last_split_packets() > 0
-            recs.append(ctx.block_trace().astype(np.uint64))
-        a, b = recs
-        assert a.shape == b.shape and np.array_equal(a[:, :3], b[:, :3]) and np.array_equal(a[:, 5] >> 40, b[:, 5] >> 40)
-    finally:
-        ctx.close()
-
-
-@pytest.mark.skipif(not vt.experimental(), reason="flavour 14 needs VR_EXPERIMENTAL_FLAVOURS=1")
-def test_mixed_lanes_per_ray_at_1080p_and_every_threshold(ctx, monkeypatch):
-    """A 1080p frame (32 640 packets), packed tiles of a two-rank partition, and thresholds from 'split everything that samples'
-    to 'split nothing': always the one-lane kernel's frame and counts."""
-    W, H = 1920, 1080
-    vols, tfs = vt.scene(capi.LIGHT, n=24)
-    step, count = hr.stepping_params(24, 24, 24)
-    u = hr.make_uniforms(W, H, steps_count=count, step_size=step, distance=0.9)
-    monkeypatch.setenv("VR_EXP_SPLIT_MIN", "4")
-    for pct in ("1", "50", "100", "1000"):
-        monkeypatch.setenv("VR_EXP_SPLIT_PCT", pct)
-        with capi.Context(W, H) as c2:
-            c2.set_kernel_flavour(6)
-            ref, _, n_ref = vt.gpu_render(c2, capi.LIGHT, u, vols, tfs)
-            c2.render_tiles(capi.LIGHT, 1, 2)
-            tiles_ref, nt_ref = c2.download_tiles(c2.tile_count(1, 2))
-            c2.set_kernel_flavour(14)
-            for k in range(7):
-                frag, _, n = vt.gpu_render(c2, capi.LIGHT, u, vols, tfs)
-                assert n == n_ref and np.array_equal(vt.bits(frag), vt.bits(ref)), (pct, k)
-            assert (c2.last_split_packets() > 0) == (pct != "1000")
-            for k in range(6):
-                c2.render_tiles(capi.LIGHT, 1, 2)
-                t, nt = c2.download_tiles(c2.tile_count(1, 2))
-                assert nt == nt_ref and np.array_equal(vt.bits(t), vt.bits(tiles_ref)), (pct, k)
 
 
 # ---- LDS tiles filled by LDS-DMA (flavour 15, csrc/vr_lt.h) ------------------------------------------------------------------

@@ -18,13 +18,8 @@ $B > $OUT/c3_default.json 2> $OUT/c3_default.err; echo "c3 default rc $?"
 $B --arith fused > $OUT/c3_fused.json 2> $OUT/c3_fused.err; echo "c3 fused rc $?"
 $B --air noisy > $OUT/c3_noisy.json 2> $OUT/c3_noisy.err; echo "c3 noisy rc $?"
 $B --air noisy --layout 1 > $OUT/c3_noisy_vec4.json 2> $OUT/c3_noisy_vec4.err; echo "c3 noisy vec4 rc $?"
-$B --air noisy --layout 2 > $OUT/c3_noisy_otf.json 2> $OUT/c3_noisy_otf.err; echo "c3 noisy otf rc $?"
-$B --layout 2 > $OUT/c3_otf.json 2> $OUT/c3_otf.err; echo "c3 otf rc $?"
 $B --tf thin > $OUT/c3_thin.json 2> $OUT/c3_thin.err; echo "c3 thin rc $?"
 $B --flavour 1 > $OUT/c3_flavour1.json 2> $OUT/c3_flavour1.err; echo "c3 flavour1 rc $?"
-$B --air noisy --flavour 2 > $OUT/c3_noisy_wtb.json 2> $OUT/c3_noisy_wtb.err; echo "c3 noisy wtb rc $?"
-VR_EXP_WAVES_PER_BLOCK=4 $B > $OUT/c3_wpb4.json 2> $OUT/c3_wpb4.err; echo "c3 wpb4 rc $?"
-VR_EXP_ORDER=0 $B > $OUT/c3_noorder.json 2> $OUT/c3_noorder.err; echo "c3 noorder rc $?"
 for W in C1 C2 C4 C5; do
   python3 bench.py --workload $W --steps 50 --warmup 5 --no-regimes > $OUT/${W}_default.json 2> $OUT/${W}_default.err; echo "$W rc $?"
   python3 bench.py --workload $W --tf thin --steps 50 --warmup 5 --no-regimes --no-cpu-baseline --no-live-pmc > $OUT/${W}_thin.json 2> $OUT/${W}_thin.err; echo "$W thin rc $?"

@@ -20,15 +20,12 @@ $B --arith fused > $OUT/c3_fused.json 2> $OUT/c3_fused.err; echo "c3 fused rc $?
 $B --identical-frames > $OUT/c3_identical.json 2> $OUT/c3_identical.err; echo "c3 identical rc $?"
 $B --flavour 12 > $OUT/c3_f12.json 2> $OUT/c3_f12.err; echo "c3 f12 rc $?"
 $B --flavour 13 > $OUT/c3_f13.json 2> $OUT/c3_f13.err; echo "c3 f13 rc $?"
-# (flavours 14 and 15 need the experimental build: VR_EXPERIMENTAL_FLAVOURS=1 python -c "from volumerendering_amd import build; build.build_all()")
-$B --flavour 14 > $OUT/c3_f14.json 2> $OUT/c3_f14.err; echo "c3 f14 rc $?"
 $B --flavour 15 > $OUT/c3_f15.json 2> $OUT/c3_f15.err; echo "c3 f15 rc $?"
 $B --tf thin > $OUT/c3_thin.json 2> $OUT/c3_thin.err; echo "c3 thin rc $?"
 $B --air noisy > $OUT/c3_noisy.json 2> $OUT/c3_noisy.err; echo "c3 noisy rc $?"
 $B --air noisy --flavour 6 > $OUT/c3_noisy_f6.json 2> $OUT/c3_noisy_f6.err; echo "c3 noisy f6 rc $?"
 $B --air noisy --flavour 6 --layout 3 > $OUT/c3_noisy_f6_layout3.json 2> $OUT/c3_noisy_f6_layout3.err; echo "c3 noisy f6 layout3 rc $?"
 $B --air noisy --flavour 15 > $OUT/c3_noisy_f15.json 2> $OUT/c3_noisy_f15.err; echo "c3 noisy f15 rc $?"
-$B --air noisy --flavour 2 > $OUT/c3_noisy_wtb.json 2> $OUT/c3_noisy_wtb.err; echo "c3 noisy wtb rc $?"
 $B --air noisy --arith fused > $OUT/c3_noisy_fused.json 2> $OUT/c3_noisy_fused.err; echo "c3 noisy fused rc $?"
 for W in C1 C2 C4 C5; do
   python3 bench.py --workload $W --steps 30 --warmup 5 --no-regimes --no-cpu-baseline > $OUT/${W}_default.json 2> $OUT/${W}_default.err; echo "$W rc $?"

@@ -37,12 +37,10 @@ def build_hip(force: bool = False) -> str:
     """Two translation units, compiled side by side: vr_api.hip (C ABI + kernels with separately rounded multiply-adds)
     and vr_fused.hip (the march kernels once more with fused multiply-adds), linked into one libvr_hip.so."""
     target = os.path.join(HERE, "libvr_hip.so")
-    hdrs = [os.path.join(CSRC, f) for f in ("vr_kernels.h", "vr_wtb.h", "vr_dp.h", "vr_pw.h", "vr_p2.h", "vr_mixed.h", "vr_lt.h", "vr_device.h", "vr_launch.h")]
+    hdrs = [os.path.join(CSRC, f) for f in ("vr_kernels.h", "vr_dp.h", "vr_pw.h", "vr_p2.h", "vr_lt.h", "vr_device.h", "vr_launch.h")]
     hdrs.append(os.path.join(os.path.dirname(HERE), "include", "vr.h"))
     flags = [f for f in HIP_FLAGS if f != "-shared"] + os.environ.get("VR_EXTRA_HIPCC_FLAGS", "").split()
-    if os.environ.get("VR_EXPERIMENTAL_FLAVOURS", "0") not in ("", "0"):
-        flags.append("-DVR_EXPERIMENTAL_FLAVOURS=1")  # the kernel forms that lost every A/B (vr_launch.h)
-    # the flags the objects were compiled with: a change (VR_EXTRA_HIPCC_FLAGS, VR_EXPERIMENTAL_FLAVOURS) rebuilds them
+    # the flags the objects were compiled with: a change (VR_EXTRA_HIPCC_FLAGS) rebuilds them
     stamp = os.path.join(CSRC, ".build_flags")
     want = " ".join(flags)
     if not os.path.exists(stamp) or open(stamp).read() != want:

@@ -34,7 +34,7 @@ ABI_SYMBOLS = [
     "vr_render_batch_async", "vr_render_tiles_batch_async", "vr_unpack_tiles_strided_async",
     "vr_last_timing", "vr_kernel_times", "vr_reset_kernel_times", "vr_frame_device_ptr", "vr_last_covered_pixels", "vr_last_counters", "vr_set_kernel_flavour", "vr_last_block_trace", "vr_last_kernel_flavour",
     "vr_set_volume_layout", "vr_volume_layout", "vr_viewport", "vr_set_arithmetic", "vr_present_async", "vr_stream", "vr_hint_frames_in_flight",
-    "vr_set_kernel_timing", "vr_present_tiles_async", "vr_last_split_packets", "vr_experimental_flavours", "vr_kernel_choice",
+    "vr_set_kernel_timing", "vr_present_tiles_async", "vr_kernel_choice",
     "vr_present_packed_async", "vr_unpack_tiles_bgra8_async",
 ]
 
@@ -50,11 +50,6 @@ class Uniforms(C.Structure):
         ("toggles", C.c_int32 * 4),
         ("light_pos", C.c_float * 4), ("light_ambient", C.c_float * 4), ("light_diffuse", C.c_float * 4),
     ]
-
-
-def experimental_flavours() -> bool:
-    """True if libvr_hip.so was built with -DVR_EXPERIMENTAL_FLAVOURS=1 (flavours 2, 3, 4, 5, 9 and layout 2 compiled in)."""
-    return bool(load().vr_experimental_flavours())
 
 
 class VrError(RuntimeError):
@@ -118,8 +113,6 @@ def load() -> C.CDLL:
     lib.vr_last_block_trace.argtypes = [vp, C.c_void_p, C.c_int]
     lib.vr_set_kernel_flavour.argtypes = [vp, i32]
     lib.vr_last_kernel_flavour.argtypes = [vp]
-    lib.vr_last_split_packets.argtypes = [vp]
-    lib.vr_experimental_flavours.argtypes = []
     lib.vr_set_volume_layout.argtypes = [vp, i32]
     lib.vr_set_arithmetic.argtypes = [vp, i32]
     lib.vr_present_async.argtypes = [vp, vp, vp, vp]
@@ -317,10 +310,6 @@ class Context:
     def frame_device_ptr(self) -> int:
         return int(self.lib.vr_frame_device_ptr(self.h) or 0)
 
-    def last_split_packets(self) -> int:
-        """Flavour 14: packets the last launch marched as two half packets with two lanes per ray."""
-        return self._chk(self.lib.vr_last_split_packets(self.h))
-
     def last_kernel_flavour(self) -> int:
         return self._chk(self.lib.vr_last_kernel_flavour(self.h))
 
@@ -356,7 +345,7 @@ class Context:
         self._chk(self.lib.vr_set_arithmetic(self.h, mode))
 
     def set_volume_layout(self, mode: int):
-        """0 density plane for .a fetches (default), 1 the reference's vec4 voxels only, 2 = 0 + lit gradients on the fly."""
+        """0 bricked copy (default), 1 the reference's vec4 voxels only, 3 x-fastest voxels + density plane (2 was removed)."""
         self._chk(self.lib.vr_set_volume_layout(self.h, mode))
 
     def volume_layout(self, slot: int) -> int:

@@ -54,8 +54,8 @@ struct vr_ctx {
     size_t vol_bricked_cap[VR_MAX_VOLUMES] = {};  // in slots (bricks x 64)
     bool vol_grad_derived[VR_MAX_VOLUMES] = {};  // .rgb verified to be PreComputeGradient(false) of .a, bit for bit
     int arith = VR_ARITH_SEPARATE;             // vr_set_arithmetic
-    int layout_mode = 0;                       // vr_set_volume_layout: 0 density plane for .a fetches, 1 vec4 voxels only,
-                                               // 2 plane + lit gradients derived on the fly
+    int layout_mode = 0;                       // vr_set_volume_layout: 0 bricked copy + its density plane, 1 vec4 voxels only,
+                                               // 3 x-fastest voxels + density plane (2, gradients on the fly, was removed)
     float2* merged_bricks = nullptr;           // VOLUME_MASK: (CT density max, mask rgb max), rebuilt when stale
     bool merged_stale = true;
     unsigned char* brick_dist = nullptr;       // distance field over the records in use; key below says for what
@@ -96,15 +96,7 @@ struct vr_ctx {
         unsigned long long key = 0, seq = 0;
         unsigned long long scene_key = 0;  // what the launch rendered, whatever kernel form it took (the chain length's key)
         bool valid = false;
-        unsigned* items = nullptr;  // mixed lanes per ray (vr_mixed.h): the item list built behind that launch's sort
-        size_t items_cap = 0;
-        bool has_items = false;
     } order_ring[kOrderRing];
-    unsigned* h_items = nullptr;  // pinned, one word per ring slot: grid of a launch that takes that slot's item list (0 = not built yet)
-    unsigned* h_split = nullptr;  // pinned: how many packets that list splits in two
-    int split_pct = 75;           // a packet is split when its longest chain reaches this share of the launch's longest (VR_EXP_SPLIT_PCT)
-    int split_min = 64;           // ... and at least this many samples (VR_EXP_SPLIT_MIN)
-    unsigned last_split = 0;      // packets the last mixed launch marched with two lanes per ray
     unsigned long long* h_span = nullptr;  // pinned, kRing words: duration of launch q in 100 MHz ticks + 1, from its records (0 = not known)
     bool ring_events[kRing] = {};          // launch q was timed with the events k0 / k1 instead (no sort behind it)
     unsigned long long* h_end = nullptr;   // pinned, kRing words: end of launch q's last workgroup on the 100 MHz device clock, | 1 (0 = not known)
@@ -131,7 +123,6 @@ struct vr_ctx {
     hipStream_t flight[kStreams] = {};  // vr_stream(): streams probed to run side by side (created on first use)
     int n_flight = 0;
     hipStream_t order_stream = nullptr;  // the sorts run here, behind their launch's event: never on a frame's critical path
-    int order_mode = 1;  // 0 = launch the blocks in index order (VR_EXP_ORDER=0)
     // VR_EXP_HOST_ORDER_WAIT=1: one frame at a time, a launch waits for the two sorts it depends on (the launch order it reads, the sort
     // that read its record slot last) on the HOST, before it is enqueued, instead of on its stream (enqueue_render).  Off by default.
     int host_order_wait = 0;
@@ -139,35 +130,25 @@ struct vr_ctx {
     bool cnt_pending = false;                  // block counts of the last launch not summed / copied yet
     int cnt_blocks = 0;
     bool event_timing = false;                 // vr_set_kernel_timing(VR_TIMING_EVENTS): time every launch with HIP events
-    bool zskip = true;                         // per-step zero-opacity vote (VR_EXP_NO_ZSKIP=1 switches it off for A/B)
     size_t cnt_offset = 0;                     // ... and where in that buffer the records of its last frame start (u64 words)
     unsigned long long* h_counters = nullptr;  // pinned [3]
     Timing tm;
     KernelRing ring;
     int flavour = 0;
-    int waves_per_block = 1;  // 1 (default: the launch order of section 4.6 works at wavefront granularity) or 4 (VR_EXP_WAVES_PER_BLOCK)
-    int only_tile = -1;       // experiment knob VR_EXP_ONLY_TILE
-    int prio_mode = 0;        // VR_EXP_PRIO=1: wave priority by remaining ray path (+2-3 % for one frame at a time,
-                              // -2 % with frames in flight, where nothing waits for the long rays)
     int n_cus = 256;          // compute units of the device
     int default_flavour = 0;  // what flavour 0 resolves to (experiment knob VR_EXP_FLAVOUR)
     int last_flavour = 0;     // the flavour the last launch resolved to
-    bool last_otf = false;    // ... and whether it derived the gradients from the density plane
-    int xcd_mode = 2;         // deal a tile's 16x16 sub-blocks over the XCDs (VR_EXP_XCD=1: its packets one by one; 0: one XCD per tile)
-    bool pw_ltf = true;       // persistent wavefronts keep TF slot 0 in LDS (VR_EXP_PW_LTF=0: from L1, for A/B)
-    unsigned p2_threads = 0;  // flavours 16 / 17: threads per workgroup when not 768 (VR_EXP_P2_THREADS: fewer wavefronts per CU)
-    unsigned p2_wgs = 0;      // flavours 16 / 17: workgroups per CU when not chosen by the launch (VR_EXP_P2_WGS)
-    int p2_dynq = 0;          // flavours 16 / 17: every item from the queue heads, the wavefronts' first ones too (VR_EXP_P2_DYNQ=1; measured with
-                              // launches in flight, where workgroups start as others retire: 0.522 against 0.502 ms per C3 frame, so off)
     unsigned p2_window = 0;   // flavours 16 / 17: records per gather window (VR_EXP_P2_WINDOW: the moving window of volumes >= 4 GiB, forced
                               // onto small volumes by the tests; 0 = what the hardware reaches, just below 4 GiB)
     double active_fraction = 1.0;  // share of bricks that are not inert, of the distance field in use
     float abox[6] = {-3.0e38f, -3.0e38f, -3.0e38f, 3.0e38f, 3.0e38f, 3.0e38f};  // uvw box around the active bricks of that field (MarchParams::abox)
-    int pw_policy = 1;        // the default (flavour 0) may pick the persistent kernel (VR_EXP_PW_POLICY=0: never)
     std::string err;
 };
 
 namespace {
+
+// kernel forms that lost every A/B and were removed (HISTORY.md): vr_set_kernel_flavour rejects them, VR_EXP_FLAVOUR ignores them
+bool removed_flavour(int f) { return f == 2 || f == 3 || f == 4 || f == 5 || f == 9 || f == 14; }
 
 int fail(vr_ctx* c, int code, const std::string& msg)
 {
@@ -498,8 +479,7 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
         const size_t lin_bytes = c->vol_bytes[i];
         P.vol[i].data_bytes = lin_bytes > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)lin_bytes;
     }
-    // the bricked copies (layout 0) are what the gathers read; decided below, once the kernel form is known (the LDS wave-tile
-    // flavours and the on-the-fly gradients address the reference's x-fastest order)
+    // the bricked copies (layout 0) are what the gathers read (use_bricked, below)
     auto use_bricked = [&]() {
         for (int i = 0; i < VR_MAX_VOLUMES; ++i) {
             if (!c->vol[i].data || !c->vol_bricked[i] || !c->vol_bdens[i]) continue;
@@ -523,9 +503,6 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
     P.n_tiles = tile_count(c, rank, world);
     P.packed = packed ? 1 : 0;
     P.n_blocks = P.n_tiles * kBlocksPerTile;
-    P.only_tile = c->only_tile;
-    P.prio_mode = c->prio_mode;
-    P.xcd_mode = c->xcd_mode;
     // exact empty-space skipping: only for the shaders whose opacity is the CT table value alone, only when a
     // zero-opacity sample is provably the identity (finite colour table and light), and unless flavour 1 asks
     // for the plain kernel
@@ -578,7 +555,7 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
     // with 32-bit slots, rows and slabs of bricks below 2^24 slots; a volume of 4 GiB or more through a moving window of at least
     // four z-slabs of bricks.  Launches of several frames and launches in flight included.  Else 13 / 12 (one frame) or 6.
     const int p2_vol = variant == VR_VARIANT_VOLUME_MASK ? 2 : 0;
-    bool p2_ok = (variant == VR_VARIANT_LIGHT || variant == VR_VARIANT_BASIC || variant == VR_VARIANT_VOLUME_MASK) && c->pw_ltf &&
+    bool p2_ok = (variant == VR_VARIANT_LIGHT || variant == VR_VARIANT_BASIC || variant == VR_VARIANT_VOLUME_MASK) &&
                  c->tf[0].res_o == c->tf[0].res_c && c->tf[0].res_o + 2 <= 8192 && c->layout_mode == 0 && c->vol_bricked[p2_vol] && c->vol_bdens[p2_vol];
     unsigned p2_lds = 0;
     if (p2_ok) {
@@ -603,14 +580,12 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
     if (fl == 16 && variant == VR_VARIANT_VOLUME_MASK) fl = 17;  // (the composite's form is the skipping one: its mask records)
     // LDS tiles (15; vr_lt.h): the lit shader, launches of one frame
     if (fl == 15 && (n_frames != 1 || variant != VR_VARIANT_LIGHT)) fl = 6;
-    // mixed lanes per ray (14; vr_mixed.h): launches of one frame, shaders that have a depth-parallel form
-    if (fl == 14 && (n_frames != 1 || variant == VR_VARIANT_ILLUSTRATIVE || variant == VR_VARIANT_LIGHT_INSHADER)) fl = 6;
     // the illustrative shader's opacity reads the accumulated alpha: its steps cannot be sampled side by side
     if (variant == VR_VARIANT_ILLUSTRATIVE && (fl == 7 || fl == 8 || fl == 10 || fl == 11)) fl = 6;
     // the in-shader gradient variant (seven density fetches per sample) exists as the one-lane kernel only
-    if (variant == VR_VARIANT_LIGHT_INSHADER && fl != 1 && fl != 4 && fl != 5 && fl != 12 && fl != 13 && fl != 18) fl = 6;
+    if (variant == VR_VARIANT_LIGHT_INSHADER && fl != 1 && fl != 12 && fl != 13 && fl != 18) fl = 6;
     c->last_flavour = fl;
-    bool can_skip = skip_variant && fl != 1 && fl != 2 && c->vol_bricks[sv] && c->tf_zero_prefix[0] >= 0 &&
+    bool can_skip = skip_variant && fl != 1 && c->vol_bricks[sv] && c->tf_zero_prefix[0] >= 0 &&
                     c->tf_color_finite[0];
     for (int f = 0; f < n_frames; ++f) can_skip = can_skip && all_finite(batch_u ? batch_u[f].light_pos : c->u.light_pos, 12);
     // the kernels index bricks with 24-bit multiplies and 32-bit byte offsets
@@ -632,7 +607,6 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
         P.bsy = (float)c->vol[sv].ny * kBrickInv;
         P.bsz = (float)c->vol[sv].nz * kBrickInv;
         P.tf_zero_prefix = c->tf_zero_prefix[0];
-        P.zskip_prefix = c->zskip ? P.tf_zero_prefix : -2;  // (-2: no vote, and mask and dose are always fetched)
         P.bricks = c->vol_bricks[sv];
         P.use_rgb = 0;
         if (variant == VR_VARIANT_VOLUME_MASK) {
@@ -723,7 +697,7 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
     const bool whole_frame = (double)px_all / ((double)c->n_cus * 4.0 * 5.0 * 64.0) >= 4.5;
     const bool nothing_to_skip = !can_skip || c->active_fraction >= 0.9;
     const bool auto_choice = c->flavour == 0 && c->default_flavour == 0;
-    if (auto_choice && c->pw_policy && fl == 6 && whole_frame && p2_ok && p2_variant) {
+    if (auto_choice && fl == 6 && whole_frame && p2_ok && p2_variant) {
         const bool short_chains = chain_known != 0 && chain_known - 1 < 128;
         if (nothing_to_skip && variant != VR_VARIANT_VOLUME_MASK) fl = 16;
         else if (!short_chains) fl = 17;
@@ -731,7 +705,7 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
     // ... and THE MEASURED CHOICE (tune_pick): the eligible forms take turns on the caller's own frames, the fastest by the launches'
     // own records stays.  Candidates: the prior; the two-steps-ahead kernel; the one-lane kernel; the depth-parallel kernel (launches
     // that leave the machine part empty) or the persistent kernel without the pipeline (the longest chains).
-    if (auto_choice && c->tune_mode && c->pw_policy) {
+    if (auto_choice && c->tune_mode) {
         int cand[6], n = 0;
         auto add = [&](int f) {
             for (int i = 0; i < n; ++i)
@@ -750,12 +724,12 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
                                                                  ((unsigned long long)n_frames << 4) ^ (unsigned long long)c->frames_in_flight) | 1ull;
         const unsigned long long key = (shape ^ (c->brick_epoch * 0xD6E8FEB86659FD93ull) ^ (c->tf_epoch << 20) ^ ((unsigned long long)c->arith << 1) ^
                                         ((unsigned long long)c->layout_mode << 2)) | 1ull;
-        const bool measurable = c->order_mode == 1 && c->h_span && c->h_end && !c->event_timing;
+        const bool measurable = c->h_span && c->h_end && !c->event_timing;
         fl = tune_pick(c, key, shape, cand, n, chain_known, measurable);
     }
     c->last_flavour = fl;
 
-    if (c->layout_mode == 0 && fl != 2 && fl != 3) use_bricked();
+    if (c->layout_mode == 0) use_bricked();
     if (fl == 18 && P.vol[0].bricked) P.vol[0].lut = 1;  // (march_kernel fills the tables; every fetch of volume 0 goes through them)
     for (int i = 0; i < nvol; ++i)  // (a bricked copy is padded to whole bricks: a volume just below 4 GiB may cross the line)
         if (P.vol[i].bricked && (size_t)P.vol[i].brick_slab * (((unsigned)P.vol[i].nz + kVbM) >> kVbS) * 16 > 0xFFFFFFFFull) off32 = false;
@@ -778,24 +752,13 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
 
     if (frame_events) VR_HIP(c, hipEventRecord(c->tm.ev_begin, s));
     if (P.n_blocks > 0) {
-        // flavours 2/3: LDS wave tiles (without / with skipping), lit shader only
-        // (launches of several frames exist for the loop forms the default flavours use: plain, runs, depth-parallel)
-        const bool wtb = (fl == 2 || fl == 3) && variant == VR_VARIANT_LIGHT && P.fragment_mode == 0 && c->arith == VR_ARITH_SEPARATE &&
-                         n_frames == 1;
-        const int leap_mode = n_frames > 1 ? (fl == 5 ? 0 : 3) : (fl == 4 ? 1 : (fl == 5 ? 0 : (fl == 9 ? 2 : 3)));
-        const int dp = (fl == 7 || fl == 10) ? 4 : ((fl == 8 || fl == 11) ? 2 : 0);
-        // gradients on the fly (one-lane kernel, lit shader): the volume's .rgb is verified to be the central difference of
-        // its .a, so the eight corners are derived from the density plane -- same bits, a quarter of the footprint
-        const bool otf = variant == VR_VARIANT_LIGHT && c->layout_mode == 2 && c->vol_grad_derived[0] && P.vol[0].dens != nullptr &&
-                         !wtb && dp == 0;
-        c->last_otf = otf;
-        const bool dp_pipe = fl == 10 || fl == 11;  // ... with the next round's corner loads software-pipelined  // lanes per ray (vr_dp.h): 64 / 32 workgroups per tile
+        const int dp = (fl == 7 || fl == 10) ? 4 : ((fl == 8 || fl == 11) ? 2 : 0);  // lanes per ray (vr_dp.h): 64 / 32 workgroups per tile
+        const bool dp_pipe = fl == 10 || fl == 11;  // ... with the next round's corner loads software-pipelined
         // one wavefront per workgroup (launch order at wavefront granularity) -- except for the depth-parallel kernels on
         // large launches, where 4x the workgroups cost more at dispatch than the finer order gains (C2: 32 768 workgroups of
         // a 0.12 ms frame)
         const bool pw = fl == 12 || fl == 13 || fl == 16 || fl == 17;
-        int wpb = wtb ? 4 : ((pw || fl == 15) ? 1 : c->waves_per_block);
-        if (dp && P.n_tiles * (dp == 4 ? 256 : 128) > 16384) wpb = 4;
+        const int wpb = dp && P.n_tiles * (dp == 4 ? 256 : 128) > 16384 ? 4 : 1;
         dim3 block((unsigned)(64 * wpb));
         dim3 grid((unsigned)(dp ? P.n_tiles * (dp == 4 ? 256 : 128) / wpb : (P.n_tiles + 7) / 8 * 8 * (64 / wpb)));  // see map_pixel / map_pixel_dp
         if (n_frames > 1 && grid.x % 8u != 0) return fail(c, VR_ERR_INVALID_ARG, "vr_render: launch shape cannot carry several frames");
@@ -829,9 +792,8 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
             slot_sort = nullptr;
             return e;
         };
-        // every frame of the launch has its own records; twice the space for one frame: a packet marched as two half packets
-        // (vr_mixed.h) leaves its second half's record grid.x records further on
-        const size_t n_records = (size_t)grid.x * (size_t)(n_frames > 1 ? n_frames : 2);
+        // every frame of the launch has its own records
+        const size_t n_records = (size_t)grid.x * (size_t)n_frames;
         if (n_records > c->block_counts_cap[cb]) {
             VR_HIP(c, wait_slot_sort());
             if (c->d_block_counts[cb]) (void)hipFree(c->d_block_counts[cb]);
@@ -851,13 +813,11 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
         // older one's buffer may be recycled under this launch; ordered behind it by its event (long complete by then)
         const unsigned long long okey = ((unsigned long long)grid.x << 32) ^ ((unsigned long long)block.x << 20) ^
                                         ((unsigned long long)variant << 16) ^ ((unsigned long long)world << 8) ^ (unsigned long long)rank ^
-                                        ((unsigned long long)(fl == 14 ? 14 : 0) << 44) ^ (packed ? 1ull << 63 : 0ull);
+                                        (packed ? 1ull << 63 : 0ull);
         // (not the flavour: the kernels that march one packet per wavefront -- 6, 12, 13, 16, 17 -- share the logical blocks, so a
         // launch order sorted behind one of them serves the others: the measured choice below tries them in turn on a live scene)
         P.order = nullptr;
-        const unsigned* mixed_items = nullptr;  // fl 14: the item list of an earlier launch of this shape, once one exists
-        unsigned mixed_grid = 0;
-        const bool ordered = c->order_mode == 1 && !wtb && grid.x <= (unsigned)kOrderMaxBlocks && grid.x % 8u == 0;
+        const bool ordered = grid.x <= (unsigned)kOrderMaxBlocks && grid.x % 8u == 0;
         if (ordered) {
             const vr_ctx::OrderSlot* best = nullptr;
             const unsigned long long age = (unsigned long long)(c->frames_in_flight + 2 > 3 ? c->frames_in_flight + 2 : 3);
@@ -868,19 +828,9 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
                 VR_HIP(c, host_wait ? hipEventSynchronize(best->sorted) : hipStreamWaitEvent(s, best->sorted, 0));
                 if (slot_sort && best->seq >= slot_sort->seq) slot_sort = nullptr;  // (covered: the order stream runs its sorts in order)
                 P.order = best->buf;
-                if (fl == 14 && best->has_items && c->h_items) {
-                    const int bi = (int)(best - c->order_ring);
-                    const unsigned n_pos = *(volatile unsigned*)&c->h_items[bi];
-                    if (n_pos >= grid.x && n_pos <= 2u * grid.x && n_pos % 8u == 0) {
-                        mixed_items = best->items;
-                        mixed_grid = n_pos;
-                        c->last_split = *(volatile unsigned*)&c->h_split[bi];
-                    }
-                }
             }
         }
         VR_HIP(c, wait_slot_sort());
-        if (!mixed_items) c->last_split = 0;
         const int slot = (int)(c->ring.head % kRing);
         if (frame_events) VR_HIP(c, hipEventRecord(c->tm.ev_k0, s));
         // launches with a sort behind them are timed from their own records (order_blocks_kernel); events only otherwise
@@ -893,11 +843,8 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
             LaunchDesc L;
             L.variant = variant;
             L.off32 = off32;
-            L.leap_mode = leap_mode;
             L.dp = dp;
             L.dp_pipe = dp_pipe;
-            L.wtb = wtb;
-            L.otf = otf;
             L.lt = fl == 15;
             L.pw = false;
             L.pw_ltf = false;
@@ -906,9 +853,7 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
             L.pw_p2_skip = false;
             L.pw_p2_win = false;
             L.lds_bytes = (fl == 18 && P.vol[0].lut) ? lut_lds : 0u;
-            L.queue = PwQueue{nullptr, 0u, 0u, 0u};
-            L.mixed_items = nullptr;
-            L.n_logical = 0;
+            L.queue = PwQueue{nullptr, 0u, 0u};
             L.grid = grid;
             L.block = block;
             // frame f of the launch: every n_frames-th group of 8 workgroups (MarchBatch), its own uniforms, output and
@@ -934,15 +879,11 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
                 const bool p2 = fl == 16 || fl == 17;
                 // (the unlit shader's two buffers are 4-byte densities, 101 VGPRs: 4 wavefronts per SIMD -- C2 one frame at a time 0.121 ->
                 // 0.113 ms, thin table 0.255 -> 0.239, four frames per launch 0.070 -> 0.061: tools/experiments/s2h.sh)
-                unsigned pw_threads = fl == 17 ? (variant == VR_VARIANT_BASIC ? 1024u : 768u) : (fl == 16 ? 512u : 1024u);
+                const unsigned pw_threads = fl == 17 ? (variant == VR_VARIANT_BASIC ? 1024u : 768u) : (fl == 16 ? 512u : 1024u);
                 // (launches in flight: the same shape.  Two workgroups of 6 wavefronts do not share a CU -- the second one's wavefronts
                 // would have to go 1-1-2-2 over the SIMDs where the dispatcher deals 2-2-1-1: measured 0.75 ms per C3 frame, what
                 // one such workgroup per CU takes -- and two of 4 run at 8 wavefronts per CU: 0.63 against 0.54; three of 4, the same
                 // 12 wavefronts per CU, take 0.79 ms one frame at a time and 0.62 in flight against 0.55 / 0.51: profiles/r04_p2_launch_shapes.txt)
-                unsigned wg_per_cu = 1;
-                if (p2 && c->p2_threads) pw_threads = c->p2_threads;  // (VR_EXP_P2_THREADS: 64 .. 768; .. 1024 for the unlit shader)
-                if (p2 && variant != VR_VARIANT_BASIC && pw_threads > 768u) pw_threads = 768u;
-                if (p2 && c->p2_wgs) wg_per_cu = c->p2_wgs;           // (VR_EXP_P2_WGS: workgroups per CU the grid is sized for)
                 const unsigned per_wg = pw_threads / 64u;
                 const unsigned items = grid.x * (unsigned)n_frames;
                 const unsigned wgs = (items + per_wg - 1u) / per_wg;
@@ -951,23 +892,16 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
                 L.pw_p2 = p2;
                 L.pw_p2_skip = fl == 17 && P.brick_dist != nullptr;
                 L.pw_p2_win = p2 && (!off32 || c->p2_window != 0);
-                L.pw_ltf = c->pw_ltf && c->tf[0].res_o == c->tf[0].res_c && c->tf[0].res_o + 2 <= 8192;
+                L.pw_ltf = c->tf[0].res_o == c->tf[0].res_c && c->tf[0].res_o + 2 <= 8192;
                 L.lds_bytes = p2 ? p2_lds : (L.pw_ltf ? (unsigned)(c->tf[0].res_o + 2) * 16u : 0u);
                 L.queue.heads = c->d_pw_heads + (size_t)cb * 8 * 64;
                 L.queue.n_items = grid.x;
                 L.queue.p2_window = c->p2_window;
-                L.queue.dynamic = p2 && c->p2_dynq == 1 ? 1u : 0u;
-                const unsigned max_wgs = (unsigned)c->n_cus * wg_per_cu;
+                const unsigned max_wgs = (unsigned)c->n_cus;
                 L.grid = dim3(wgs < max_wgs ? wgs : max_wgs);
                 L.block = dim3(pw_threads);
                 if (c->pw_heads_dirty[cb]) VR_HIP(c, hipMemsetAsync(L.queue.heads, 0, 8 * 64 * sizeof(unsigned), s));
                 c->pw_heads_dirty[cb] = true;  // (until the sort that clears them behind this launch has really been enqueued: below)
-            }
-            if (mixed_items) {
-                L.mixed_items = mixed_items;
-                L.n_logical = (int)grid.x;
-                L.grid = dim3(mixed_grid);
-                L.block = dim3(64);
             }
             if (c->arith == VR_ARITH_FUSED) vrf::launch_march(L, s, B);
             else vr::launch_march(L, s, B);
@@ -1003,25 +937,6 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
                                (c->h_span && c->h_end && !time_with_events) ? c->h_end + slot : (unsigned long long*)nullptr);
             VR_HIP(c, hipGetLastError());
             if (pw) c->pw_heads_dirty[cb] = false;  // (the sort zeroes the heads behind the launch: the slot's next user finds them clean)
-            o.has_items = false;
-#if VR_EXPERIMENTAL_FLAVOURS
-            if (fl == 14 && c->h_items && c->h_split) {
-                const int oi = (int)(c->order_seq % kOrderRing);
-                if (2 * (size_t)grid.x > o.items_cap) {
-                    if (o.items) (void)hipFree(o.items);
-                    o.items = nullptr;
-                    o.items_cap = 0;
-                    VR_HIP(c, hipMalloc(&o.items, 2 * (size_t)grid.x * sizeof(unsigned)));
-                    o.items_cap = 2 * (size_t)grid.x;
-                }
-                c->h_items[oi] = 0;
-                c->h_split[oi] = 0;
-                hipLaunchKernelGGL(build_items_kernel, dim3(1), dim3(1024), 0, c->order_stream, c->d_block_counts[cb], (int)grid.x, o.buf,
-                                   (unsigned)c->split_pct, (unsigned)c->split_min, o.items, c->h_items + oi, c->h_split + oi);
-                VR_HIP(c, hipGetLastError());
-                o.has_items = true;
-            }
-#endif
             VR_HIP(c, hipEventRecord(o.sorted, c->order_stream));
             o.valid = true;
         }
@@ -1083,16 +998,14 @@ int refresh_bricks(vr_ctx* c, int slot)
     hipLaunchKernelGGL(brick_max_kernel, dim3((unsigned)nbricks), dim3(64), 0, c->stream, v.data, v.nx, v.ny, v.nz, bnx, bny,
                        c->vol_bricks[slot]);
     VR_HIP(c, hipGetLastError());
-    // scalar density plane + "is .rgb the central difference of .a?" (decides whether the lit shader may derive gradients)
+    // scalar density plane + "is .rgb the central difference of .a?" (vr_volume_layout bit 2)
     const size_t n = (size_t)v.nx * v.ny * v.nz;
     c->vol_grad_derived[slot] = false;
     if (n > c->vol_dens_cap[slot]) {
         if (c->vol_dens[slot]) (void)hipFree(c->vol_dens[slot]);
         c->vol_dens[slot] = nullptr;
         c->vol_dens_cap[slot] = 0;
-        // (+ 4 floats of slack: the 16-byte row pieces of fetch_rgba_otf never start beyond the last voxel, but may end there)
-        VR_HIP(c, hipMalloc(&c->vol_dens[slot], (n + 4) * sizeof(float)));
-        VR_HIP(c, hipMemsetAsync(c->vol_dens[slot] + n, 0, 4 * sizeof(float), c->stream));
+        VR_HIP(c, hipMalloc(&c->vol_dens[slot], n * sizeof(float)));
         c->vol_dens_cap[slot] = n;
     }
     hipLaunchKernelGGL(extract_density_kernel, dim3(4096), dim3(256), 0, c->stream, v.data, c->vol_dens[slot], n);
@@ -1297,26 +1210,14 @@ int vr_create(vr_ctx** out, uint32_t width, uint32_t height, int device_id)
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_id) == hipSuccess && cus > 0) c->n_cus = cus;
     }
     // experiment knobs (A/B measurements; none changes any result)
-    if (const char* e = getenv("VR_EXP_WAVES_PER_BLOCK")) c->waves_per_block = (atoi(e) == 4) ? 4 : 1;
-    if (const char* e = getenv("VR_EXP_ONLY_TILE")) c->only_tile = atoi(e);
-    if (const char* e = getenv("VR_EXP_PRIO")) c->prio_mode = atoi(e);
     if (const char* e = getenv("VR_EXP_FLAVOUR")) {
         const int f = atoi(e);
-        if (f >= 0 && f <= 18 && (VR_EXPERIMENTAL_FLAVOURS || !(f == 2 || f == 3 || f == 4 || f == 5 || f == 9 || f == 14))) c->default_flavour = f;
+        if (f >= 0 && f <= 18 && !removed_flavour(f)) c->default_flavour = f;
     }
-    if (const char* e = getenv("VR_EXP_XCD")) c->xcd_mode = atoi(e);
-    if (const char* e = getenv("VR_EXP_PW_LTF")) c->pw_ltf = atoi(e) != 0;
-    if (const char* e = getenv("VR_EXP_P2_THREADS")) {
-        const int t = atoi(e);
-        if (t >= 64 && t <= 1024 && t % 64 == 0) c->p2_threads = (unsigned)t;
-    }
-    if (const char* e = getenv("VR_EXP_P2_WGS")) c->p2_wgs = (unsigned)(atoi(e) > 0 && atoi(e) <= 8 ? atoi(e) : 0);
-    if (const char* e = getenv("VR_EXP_P2_DYNQ")) c->p2_dynq = atoi(e);
     if (const char* e = getenv("VR_EXP_P2_WINDOW")) {  // records per gather window of march_p2_kernel (tests: the moving window on small volumes)
         const long long w = atoll(e);
         if (w > 0 && w <= 0x3fffffffll) c->p2_window = (unsigned)w;
     }
-    if (const char* e = getenv("VR_EXP_PW_POLICY")) c->pw_policy = atoi(e);
     if (const char* e = getenv("VR_EXP_TUNE")) c->tune_mode = atoi(e);
     if (!hip_ok(hipMalloc(&c->d_pw_heads, (size_t)kInFlight * 8 * 64 * sizeof(unsigned)), "hipMalloc(queue heads)")) return bail(VR_ERR_HIP);
     if (!hip_ok(hipMemset(c->d_pw_heads, 0, (size_t)kInFlight * 8 * 64 * sizeof(unsigned)), "hipMemset(queue heads)")) return bail(VR_ERR_HIP);
@@ -1343,14 +1244,6 @@ int vr_create(vr_ctx** out, uint32_t width, uint32_t height, int device_id)
         std::memset(c->h_span, 0, kRing * sizeof(unsigned long long));
     else
         c->h_span = nullptr;  // (every launch is then timed with events)
-    if (hipHostMalloc((void**)&c->h_items, 2 * kOrderRing * sizeof(unsigned), hipHostMallocDefault) == hipSuccess) {
-        std::memset(c->h_items, 0, 2 * kOrderRing * sizeof(unsigned));
-        c->h_split = c->h_items + kOrderRing;
-    } else {
-        c->h_items = c->h_split = nullptr;  // (flavour 14 then always marches with one lane per ray)
-    }
-    if (const char* e = getenv("VR_EXP_SPLIT_PCT")) c->split_pct = atoi(e) > 0 ? atoi(e) : 75;
-    if (const char* e = getenv("VR_EXP_SPLIT_MIN")) c->split_min = atoi(e) > 0 ? atoi(e) : 64;
     if (hipHostMalloc((void**)&c->h_end, kRing * sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess)
         std::memset(c->h_end, 0, kRing * sizeof(unsigned long long));
     else
@@ -1359,10 +1252,7 @@ int vr_create(vr_ctx** out, uint32_t width, uint32_t height, int device_id)
         std::memset(c->h_chain, 0, kOrderRing * sizeof(unsigned));
     else
         c->h_chain = nullptr;  // (the choice of lanes per ray then goes by the launch size alone)
-    if (const char* e = getenv("VR_EXP_ORDER")) c->order_mode = atoi(e);
     if (const char* e = getenv("VR_EXP_HOST_ORDER_WAIT")) c->host_order_wait = atoi(e) != 0;
-    if (const char* e = getenv("VR_EXP_NO_ZSKIP")) c->zskip = atoi(e) == 0;
-    if (const char* e = getenv("VR_EXP_EVENT_TIMING")) c->event_timing = atoi(e) != 0;
     if (!hip_ok(hipMalloc(&c->d_counters, 3 * sizeof(unsigned long long)), "hipMalloc(counters)")) return bail(VR_ERR_HIP);
     if (!hip_ok(hipHostMalloc((void**)&c->h_counters, 3 * sizeof(unsigned long long), hipHostMallocDefault),
                 "hipHostMalloc"))
@@ -1423,10 +1313,8 @@ void vr_destroy(vr_ctx* c)
     for (auto& o : c->order_ring) {
         if (o.sorted) (void)hipEventDestroy(o.sorted);
         if (o.buf) (void)hipFree(o.buf);
-        if (o.items) (void)hipFree(o.items);
     }
     if (c->order_stream) (void)hipStreamDestroy(c->order_stream);
-    if (c->h_items) (void)hipHostFree(c->h_items);
     if (c->h_chain) (void)hipHostFree(c->h_chain);
     if (c->h_span) (void)hipHostFree(c->h_span);
     if (c->h_end) (void)hipHostFree(c->h_end);
@@ -1836,26 +1724,6 @@ int vr_last_block_trace(vr_ctx* c, uint64_t* out, int capacity)
     if (n > 0) {
         const unsigned long long* src = c->d_block_counts[c->cnt_buf] + c->cnt_offset;
         VR_HIP(c, hipMemcpy(out, src, (size_t)n * kBlockRecord * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        // packets marched as two half packets (vr_mixed.h): add the second half's record (cnt_offset == 0 for such launches)
-        bool any = false;
-        for (int i = 0; i < n && !any; ++i) any = (out[(size_t)i * kBlockRecord + 5] & kRecSplit) != 0;
-        if (any && c->cnt_offset == 0) {
-            std::vector<unsigned long long> second((size_t)n * kBlockRecord);
-            VR_HIP(c, hipMemcpy(second.data(), src + (size_t)c->cnt_blocks * kBlockRecord, second.size() * sizeof(unsigned long long),
-                                hipMemcpyDeviceToHost));
-            for (int i = 0; i < n; ++i) {
-                uint64_t* a = out + (size_t)i * kBlockRecord;
-                if (!(a[5] & kRecSplit)) continue;
-                const unsigned long long* b = second.data() + (size_t)i * kBlockRecord;
-                a[0] += b[0];
-                a[1] += b[1];
-                a[2] += b[2];
-                a[3] = b[3] < a[3] ? b[3] : a[3];
-                a[4] = b[4] > a[4] ? b[4] : a[4];
-                const unsigned long long ca = a[5] >> 40, cb2 = b[5] >> 40;
-                a[5] = (a[5] & ((1ull << 40) - 1)) | ((ca > cb2 ? ca : cb2) << 40);
-            }
-        }
     }
     return c->cnt_blocks;
 }
@@ -1864,14 +1732,6 @@ int vr_last_kernel_flavour(vr_ctx* c)
 {
     if (!c) return VR_ERR_INVALID_ARG;
     return c->last_flavour;
-}
-
-int vr_experimental_flavours(void) { return VR_EXPERIMENTAL_FLAVOURS ? 1 : 0; }
-
-int vr_last_split_packets(vr_ctx* c)
-{
-    if (!c) return VR_ERR_INVALID_ARG;
-    return (int)c->last_split;
 }
 
 // Event-timed span of one 150 us single-wavefront spin on a and, if b is given, a second one on b right behind it.
@@ -1962,8 +1822,7 @@ int vr_set_volume_layout(vr_ctx* c, int mode)
 {
     if (!c) return VR_ERR_INVALID_ARG;
     if (mode < 0 || mode > 3) return fail(c, VR_ERR_INVALID_ARG, "vr_set_volume_layout: unknown mode");
-    if (!VR_EXPERIMENTAL_FLAVOURS && mode == 2)
-        return fail(c, VR_ERR_UNSUPPORTED, "vr_set_volume_layout: layout 2 is compiled with -DVR_EXPERIMENTAL_FLAVOURS=1 only");
+    if (mode == 2) return fail(c, VR_ERR_UNSUPPORTED, "vr_set_volume_layout: layout 2 (gradients derived on the fly) was removed");
     c->layout_mode = mode;
     return VR_OK;
 }
@@ -1973,8 +1832,7 @@ int vr_volume_layout(vr_ctx* c, int slot, int* flags)
     if (!c || !flags) return VR_ERR_INVALID_ARG;
     if (slot < 0 || slot >= VR_MAX_VOLUMES) return fail(c, VR_ERR_INVALID_ARG, "vr_volume_layout: bad slot");
     if (!c->vol[slot].data) return fail(c, VR_ERR_NOT_READY, "vr_volume_layout: volume slot is empty");
-    *flags = (c->vol_dens[slot] ? 1 : 0) | (c->vol_grad_derived[slot] ? 2 : 0) | (c->last_otf ? 4 : 0) |
-             ((c->vol_bricked[slot] && c->layout_mode == 0) ? 8 : 0);
+    *flags = (c->vol_dens[slot] ? 1 : 0) | (c->vol_grad_derived[slot] ? 2 : 0) | ((c->vol_bricked[slot] && c->layout_mode == 0) ? 8 : 0);
     return VR_OK;
 }
 
@@ -1997,8 +1855,8 @@ int vr_set_kernel_flavour(vr_ctx* c, int flavour)
 {
     if (!c) return VR_ERR_INVALID_ARG;
     if (flavour < 0 || flavour > 18) return fail(c, VR_ERR_INVALID_ARG, "vr_set_kernel_flavour: unknown flavour");
-    if (!VR_EXPERIMENTAL_FLAVOURS && (flavour == 2 || flavour == 3 || flavour == 4 || flavour == 5 || flavour == 9 || flavour == 14))
-        return fail(c, VR_ERR_UNSUPPORTED, "vr_set_kernel_flavour: flavours 2, 3, 4, 5, 9 and 14 are compiled with -DVR_EXPERIMENTAL_FLAVOURS=1 only");
+    if (removed_flavour(flavour))
+        return fail(c, VR_ERR_UNSUPPORTED, "vr_set_kernel_flavour: flavour " + std::to_string(flavour) + " was removed (it lost every A/B)");
     c->flavour = flavour;
     return VR_OK;
 }

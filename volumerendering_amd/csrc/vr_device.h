@@ -10,7 +10,6 @@ constexpr int kTile = 64;        // multi-GPU ownership granule (pixels)
 constexpr int kBlockEdge = 16;   // one 256-thread workgroup = 16x16 pixels = four 8x8 wave packets
 constexpr int kBlockRecord = 6;  // u64 words per block in MarchParams::block_counts
 constexpr int kBlocksPerTile = (kTile / kBlockEdge) * (kTile / kBlockEdge);
-constexpr unsigned long long kRecSplit = 1ull << 39;  // record word 5: the packet was marched as two half packets (vr_mixed.h)
 // Empty-space bricks of 4 x 4 x 4 base cells (a brick's cells touch 5 x 5 x 5 voxels).  Round 1 used 8-cell bricks; 4-cell
 // ones leave 6.5 % fewer samples of C3 (39 % of C2) inside active bricks for a distance field 8 times the size (2 MB for
 // 512^3, 16 MB for 1024^3: one byte per brick) and are faster on every configuration (C3 0.573 -> 0.562 ms one frame at a
@@ -92,9 +91,6 @@ struct MarchParams {
     // work decomposition: the launch walks the 64x64 tiles t = rank + n*world, n = 0..n_tiles-1
     int rank, world, tiles_x, tiles_y, n_tiles;
     int packed;              // 0: write frame[y*W+x]; 1: write packed tiles
-    int prio_mode;           // 1: wavefronts with long remaining ray paths raise their issue priority (s_setprio)
-    int xcd_mode;            // 0: the blocks of a tile share an XCD, 1: they are dealt over the XCDs
-    int only_tile;           // experiment (VR_EXP_ONLY_TILE): >= 0 -> rays of every other tile ordinal do not march
     int rect[4];             // x0, y0, x1, y1 (inclusive): no ray outside this pixel rectangle can hit the box
     int n_blocks;            // logical blocks = n_tiles * kBlocksPerTile (grid is padded to a multiple of 8)
     // exact empty-space skipping (BASIC / LIGHT / THREE_FILES): per-brick maximum density of vol[0] over the
@@ -108,8 +104,7 @@ struct MarchParams {
     float abox[6];           // uvw box (lo xyz, hi xyz) around the ACTIVE bricks of brick_dist, one brick of margin: outside it nothing is sampled
     int bnx, bny, bnz;       // bricks per axis
     float bsx, bsy, bsz;     // n / kBrickCells per axis of vol[skip_vol] (exact in f32)
-    int tf_zero_prefix;      // largest Z with opacity[0..Z] == 0 exactly (-1: none)
-    int zskip_prefix;        // the same for the per-step vote of sample_and_blend (-1 with VR_EXP_NO_ZSKIP: never skips)
+    int tf_zero_prefix;      // largest Z with opacity[0..Z] == 0 exactly (-1: none); also the per-step vote of sample_and_blend
     // Launch order of the logical blocks: workgroup blockIdx.x works on logical block order[blockIdx.x] (nullptr =
     // identity).  The host sorts the blocks of the previous frame by their longest ray chain, longest first, so that the
     // long blocks start at once and the short ones fill the machine at the end (speed only: a permutation of the blocks).
@@ -138,7 +133,6 @@ struct MarchBatch {
 struct PwQueue {
     unsigned* heads;
     unsigned n_items;  // logical blocks of the launch (a multiple of 8)
-    unsigned dynamic;    // march_p2_kernel: 1 = a wavefront's first item comes from the heads as well (no static deal)
     unsigned p2_window;  // march_p2_kernel<.., WIN>: records per gather window when not 0 (tests: a small window on a small volume)
 };
 
@@ -147,11 +141,8 @@ struct PwQueue {
 struct LaunchDesc {
     int variant;      // vr_variant
     bool off32;       // every bound volume < 4 GiB: 32-bit byte offsets
-    int leap_mode;    // LEAP template argument of march_kernel
     int dp;           // lanes per ray of march_dp_kernel (2 / 4), 0 = march_kernel
     bool dp_pipe;     // ... with the next round's corner loads software-pipelined
-    bool wtb;         // LDS wave-tile kernel (lit shader, separate arithmetic only)
-    bool otf;         // lit shader: corner gradients derived from the density plane
     bool lt;          // LDS tiles filled by LDS-DMA (vr_lt.h; lit shader)
     bool pw;          // persistent wavefronts (vr_pw.h): grid = workgroups of 1024 threads, the packets come from `queue`
     bool pw_ltf;      // ... with TF slot 0 in LDS (lds_bytes of dynamic LDS)
@@ -161,8 +152,6 @@ struct LaunchDesc {
     bool pw_p2_win;   // ... ... a bound volume of 4 GiB or more: the gather window moves (march_p2_kernel<.., WIN>)
     unsigned lds_bytes;
     PwQueue queue;
-    const unsigned* mixed_items;  // lanes per ray chosen per packet (vr_mixed.h): the item list, grid = its positions
-    int n_logical;                // ... and the logical blocks of the launch (where the second halves' records start)
     dim3 grid, block;
 };
 

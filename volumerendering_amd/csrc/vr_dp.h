@@ -64,7 +64,7 @@ __device__ __forceinline__ PixelSlot map_pixel_dp(const MarchParams& P)
     s.px = tx * kTile + tpx;
     s.py = ty * kTile + tpy;
     s.in_launch = in_launch;
-    s.active = in_launch && (s.px < P.W) && (s.py < P.H) && (P.only_tile < 0 || P.only_tile == n);
+    s.active = in_launch && (s.px < P.W) && (s.py < P.H);
     s.out_index = P.packed ? (n * (kTile * kTile) + tpy * kTile + tpx) : (s.py * P.W + s.px);
     return s;
 }
@@ -91,9 +91,8 @@ __device__ __forceinline__ void dp_blend_slot(int flags, v2f s_rg, v2f s_ba, v2f
     alive = alive && !cut && !left;
 }
 
-// The whole depth-parallel march of the rays of one wavefront: lane = ray * K + depth slot, `slot` = the ray's pixel.  Shared by
-// march_dp_kernel and the mixed kernel (vr_mixed.h: two lanes per ray for the packets with the longest chains only).  Depth
-// slot 0 of every ray holds (like the others) the ray's result and counts on return.
+// The whole depth-parallel march of the rays of one wavefront (march_dp_kernel): lane = ray * K + depth slot, `slot` = the ray's
+// pixel.  Depth slot 0 of every ray holds (like the others) the ray's result and counts on return.
 template <int V, bool OFF32, bool SKIP, int K, bool PIPE>
 __device__ __forceinline__ void march_dp_body(const MarchParams& P, const PixelSlot& slot, float4& dst, unsigned& blends,
                                               unsigned& covered, unsigned& fetched)

@@ -1,6 +1,6 @@
 // vr_kernels.h -- hand-written HIP kernels for gfx950 (MI355X / CDNA4): the front-to-back compositing loop
 // of the reference's WGSL fragment shaders, one ray per lane, one 8x8 pixel packet per 64-wide wavefront
-// (march_kernel; vr_dp.h holds the two / four lanes per ray form, vr_wtb.h the LDS wave-tile experiment), plus the
+// (march_kernel; vr_dp.h holds the two / four lanes per ray form), plus the
 // auxiliary kernels (brick records and distance field, counters, present, tile unpack, data preparation).
 //
 // What each piece replaces (paths below the reference root):
@@ -31,12 +31,6 @@
 #ifndef VR_FUSED
 #define VR_FUSED 0
 #endif
-// Experiment knob (build with -DVR_LIGHT_WPE=6): ask the compiler for six waves per SIMD for the lit one-lane kernel (80
-// VGPRs instead of 88-90) at the price of a few spilled registers.
-#ifndef VR_LIGHT_WPE
-#define VR_LIGHT_WPE 1
-#endif
-#define VR_LIGHT_WAVES_PER_EU(V, OTF) (((V) == 1 && !(OTF)) ? VR_LIGHT_WPE : 1)
 
 namespace VR_KNS {
 using namespace vr;
@@ -397,28 +391,6 @@ __device__ __forceinline__ float load_a(const DevVolume& v, unsigned idx)
         return *reinterpret_cast<const float*>(v.a_base + ((size_t)idx << v.a_shift));
     }
 }
-// 4 / 2 consecutive densities of the plane starting at voxel idx (dword-aligned, not 16 / 8-byte aligned)
-typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef float f2u __attribute__((ext_vector_type(2), aligned(4)));
-template <bool OFF32>
-__device__ __forceinline__ f4u load_d4(const float* base, unsigned idx)
-{
-    if constexpr (OFF32) return *reinterpret_cast<const f4u*>(reinterpret_cast<const char*>(base) + (idx << 2));
-    else return *reinterpret_cast<const f4u*>(base + (size_t)idx);
-}
-template <bool OFF32>
-__device__ __forceinline__ float load_d1(const float* base, unsigned idx)
-{
-    if constexpr (OFF32) return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + (idx << 2));
-    else return base[(size_t)idx];
-}
-template <bool OFF32>
-__device__ __forceinline__ f2u load_d2(const float* base, unsigned idx)
-{
-    if constexpr (OFF32) return *reinterpret_cast<const f2u*>(reinterpret_cast<const char*>(base) + (idx << 2));
-    else return *reinterpret_cast<const f2u*>(base + (size_t)idx);
-}
-
 __device__ __forceinline__ float tri(float v000, float v100, float v010, float v110, float v001, float v101,
                                      float v011, float v111, float fx, float fy, float fz)
 {
@@ -467,67 +439,6 @@ __device__ __forceinline__ void fetch_a(const DevVolume& v, f3 p, Fetch1& q, flo
     fz = c.fz;
 }
 
-// ---- gradients on the fly (volumes whose .rgb is verifiably PreComputeGradient(false) of their .a) ---------------------
-// VolumeFile::PreComputeGradient (VolumeFile.cpp:196-257): g = (-(p - m)) * 0.5 per axis from the +-1 neighbours' densities,
-// a neighbour outside the grid counting as 0.  The 8 corners of a trilinear cell need 32 distinct densities: the four
-// x-rows of the cell extended by one voxel either side (4 x 16 B) and the 2-voxel pieces of the rows above / below / in
-// front / behind (8 x 8 B) -- 128 B per sample, as many as the eight vec4 voxels, but out of a volume a quarter the size.
-// The same subtraction, negation and halving the preparation pass performs, so the corners come out bit-identical to the
-// stored voxels and everything downstream (interpolation, shading) is unchanged.
-__device__ __forceinline__ float grad_cd(float p, float m) { return (-(p - m)) * 0.5f; }
-// one corner the slow way (cells that touch the volume's faces): clamped texel, out-of-grid neighbours are 0
-template <bool OFF32>
-__device__ __forceinline__ float4 corner_otf(const DevVolume& v, int i, int j, int k)
-{
-    const unsigned row = (unsigned)v.nx, slab = (unsigned)v.nx * (unsigned)v.ny;
-    const unsigned c = ((unsigned)k * (unsigned)v.ny + (unsigned)j) * row + (unsigned)i;
-    const float d = load_d1<OFF32>(v.dens, c);
-    const float mx = i > 0 ? load_d1<OFF32>(v.dens, c - 1u) : 0.0f, px = i + 1 < v.nx ? load_d1<OFF32>(v.dens, c + 1u) : 0.0f;
-    const float my = j > 0 ? load_d1<OFF32>(v.dens, c - row) : 0.0f, py = j + 1 < v.ny ? load_d1<OFF32>(v.dens, c + row) : 0.0f;
-    const float mz = k > 0 ? load_d1<OFF32>(v.dens, c - slab) : 0.0f, pz = k + 1 < v.nz ? load_d1<OFF32>(v.dens, c + slab) : 0.0f;
-    return make_float4(grad_cd(px, mx), grad_cd(py, my), grad_cd(pz, mz), d);
-}
-template <bool OFF32>
-__device__ __forceinline__ void fetch_rgba_otf(const DevVolume& v, f3 p, Fetch4& q, float& fx, float& fy, float& fz)
-{
-    const float x = mad(p.x, (float)v.nx, -0.5f), y = mad(p.y, (float)v.ny, -0.5f), z = mad(p.z, (float)v.nz, -0.5f);
-    const float x0 = floorf(x), y0 = floorf(y), z0 = floorf(z);
-    fx = x - x0;
-    fy = y - y0;
-    fz = z - z0;
-    const int tx = (int)x0, ty = (int)y0, tz = (int)z0;  // saturating conversions, NaN -> 0
-    // the cell and its one-voxel apron strictly inside the grid: 1 <= t <= n - 3 on every axis
-    const bool inner = (unsigned)(tx - 1) < (unsigned)(v.nx - 3) && (unsigned)(ty - 1) < (unsigned)(v.ny - 3) &&
-                       (unsigned)(tz - 1) < (unsigned)(v.nz - 3) && v.nx >= 4 && v.ny >= 4 && v.nz >= 4;
-    if (vr_ballot(!inner) == 0) {
-        const unsigned row = (unsigned)v.nx, slab = (unsigned)v.nx * (unsigned)v.ny;
-        const unsigned b = ((unsigned)tz * (unsigned)v.ny + (unsigned)ty) * row + (unsigned)tx - 1u;  // (x0-1, y0, z0)
-        const f4u r00 = load_d4<OFF32>(v.dens, b), r10 = load_d4<OFF32>(v.dens, b + row);
-        const f4u r01 = load_d4<OFF32>(v.dens, b + slab), r11 = load_d4<OFF32>(v.dens, b + slab + row);
-        const unsigned b1 = b + 1u;
-        const f2u ym0 = load_d2<OFF32>(v.dens, b1 - row), ym1 = load_d2<OFF32>(v.dens, b1 - row + slab);
-        const f2u yp0 = load_d2<OFF32>(v.dens, b1 + 2u * row), yp1 = load_d2<OFF32>(v.dens, b1 + 2u * row + slab);
-        const f2u zm0 = load_d2<OFF32>(v.dens, b1 - slab), zm1 = load_d2<OFF32>(v.dens, b1 - slab + row);
-        const f2u zp0 = load_d2<OFF32>(v.dens, b1 + 2u * slab), zp1 = load_d2<OFF32>(v.dens, b1 + 2u * slab + row);
-        q.a = make_float4(grad_cd(r00.z, r00.x), grad_cd(r10.y, ym0.x), grad_cd(r01.y, zm0.x), r00.y);  // 000
-        q.b = make_float4(grad_cd(r00.w, r00.y), grad_cd(r10.z, ym0.y), grad_cd(r01.z, zm0.y), r00.z);  // 100
-        q.d = make_float4(grad_cd(r10.z, r10.x), grad_cd(yp0.x, r00.y), grad_cd(r11.y, zm1.x), r10.y);  // 010
-        q.e = make_float4(grad_cd(r10.w, r10.y), grad_cd(yp0.y, r00.z), grad_cd(r11.z, zm1.y), r10.z);  // 110
-        q.f = make_float4(grad_cd(r01.z, r01.x), grad_cd(r11.y, ym1.x), grad_cd(zp0.x, r00.y), r01.y);  // 001
-        q.g = make_float4(grad_cd(r01.w, r01.y), grad_cd(r11.z, ym1.y), grad_cd(zp0.y, r00.z), r01.z);  // 101
-        q.h = make_float4(grad_cd(r11.z, r11.x), grad_cd(yp1.x, r01.y), grad_cd(zp1.x, r10.y), r11.y);  // 011
-        q.i = make_float4(grad_cd(r11.w, r11.y), grad_cd(yp1.y, r01.z), grad_cd(zp1.y, r10.z), r11.z);  // 111
-        return;
-    }
-    int i0, i1, j0, j1, k0, k1;
-    texel_pair(x0, v.nx, i0, i1);
-    texel_pair(y0, v.ny, j0, j1);
-    texel_pair(z0, v.nz, k0, k1);
-    q.a = corner_otf<OFF32>(v, i0, j0, k0); q.b = corner_otf<OFF32>(v, i1, j0, k0);
-    q.d = corner_otf<OFF32>(v, i0, j1, k0); q.e = corner_otf<OFF32>(v, i1, j1, k0);
-    q.f = corner_otf<OFF32>(v, i0, j0, k1); q.g = corner_otf<OFF32>(v, i1, j0, k1);
-    q.h = corner_otf<OFF32>(v, i0, j1, k1); q.i = corner_otf<OFF32>(v, i1, j1, k1);
-}
 // Two channels at a time (packed f32 on the register halves the 16-byte loads deliver: no shuffling).  Per lane
 // and per channel the operations and their order are those of tri(): a + (b - a) * t, separately rounded.
 typedef float v2f __attribute__((ext_vector_type(2)));
@@ -597,14 +508,13 @@ __device__ __forceinline__ float interp_a(const Fetch1& q, float fx, float fy, f
     return tri(q.a, q.b, q.d, q.e, q.f, q.g, q.h, q.i, fx, fy, fz);
 }
 
-// textureSample(vol, samplerLin, p) -> all four channels (OTF: the corners' gradients derived from the density plane)
-template <bool OFF32, bool OTF = false>
+// textureSample(vol, samplerLin, p) -> all four channels
+template <bool OFF32>
 __device__ __forceinline__ float4 tex3_rgba(const DevVolume& v, f3 p)
 {
     Fetch4 q;
     float fx, fy, fz;
-    if constexpr (OTF) fetch_rgba_otf<OFF32>(v, p, q, fx, fy, fz);
-    else fetch_rgba<OFF32>(v, p, q, fx, fy, fz);
+    fetch_rgba<OFF32>(v, p, q, fx, fy, fz);
     const v2f zw = interp_zw(q, fx, fy, fz), xy = interp_xy(q, fx, fy, fz);
     return make_float4(xy.x, xy.y, zw.x, zw.y);
 }
@@ -894,7 +804,7 @@ __device__ __forceinline__ void fetch_mask_and_dose(const MarchParams& P, f3 p, 
     mask = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     rt = 0.0f;
     any_masked = true;
-    if (P.bricks != nullptr && P.use_rgb && P.zskip_prefix >= -1)  // (wave-uniform)
+    if (P.bricks != nullptr && P.use_rgb)  // (wave-uniform)
         any_masked = vr_ballot(!(brick_record(P, brick_of<OFF32>(P, p)).y <= 0.0f)) != 0;
     if (any_masked) {
         mask = tex3_rgba<OFF32>(P.vol[0], p);
@@ -904,7 +814,7 @@ __device__ __forceinline__ void fetch_mask_and_dose(const MarchParams& P, f3 p, 
 
 // (start = the ray's first position and dst_a = the opacity accumulated so far are read by the illustrative shader only,
 // ss = the ray's step size after the variable-step override by the in-shader gradient only)
-template <int V, bool OFF32, bool OTF = false, bool LTF = false>
+template <int V, bool OFF32, bool LTF = false>
 __device__ __forceinline__ Src sample_src(const MarchParams& P, f3 p, f3 w, f3 start = f3{0.0f, 0.0f, 0.0f}, float dst_a = 0.0f,
                                           float ss = 0.0f)
 {
@@ -915,7 +825,7 @@ __device__ __forceinline__ Src sample_src(const MarchParams& P, f3 p, f3 w, f3 s
         o.rgb = t.rgb;
         o.a = t.opacity;
     } else if constexpr (V == V_LIGHT) {
-        float4 v = tex3_rgba<OFF32, OTF>(P.vol[0], p);
+        float4 v = tex3_rgba<OFF32>(P.vol[0], p);
         TfSample t = tf_lookup0<LTF>(P, v.w);
         f3 N = normalize3(mk3(v.x, v.y, v.z));
         f3 s = shade(N, w, mk3(P.light_pos[0], P.light_pos[1], P.light_pos[2]),
@@ -991,7 +901,7 @@ __device__ __forceinline__ Src sample_src(const MarchParams& P, f3 p, f3 w, f3 s
 __device__ __forceinline__ bool opacity_is_zero(const MarchParams& P, float d)
 {
     const int jo = padded_texel(floorf(mad(d, (float)P.tf[0].res_o, -0.5f)), P.tf[0].res_o);
-    return (d - d == 0.0f) && jo <= P.zskip_prefix;  // finite: an infinite density has a NaN weight, hence a NaN opacity
+    return (d - d == 0.0f) && jo <= P.tf_zero_prefix;  // finite: an infinite density has a NaN weight, hence a NaN opacity
 }
 
 // The lit shader from the interpolated voxel to the blend (BasicVolLightApp.wgsl:216-223), on (x, y) / (r, g) register pairs
@@ -1054,7 +964,7 @@ __device__ __forceinline__ void light_shade_blend(const MarchParams& P, f3 w, v2
 // when the opacity of EVERY ray of the packet is exactly 0 at this step, the blend is the identity for all of them (rgb
 // finite, rgb * 0 = 0, dst + (1 - dst.a) * 0 = dst) and the table texels, the gradient, the shade and the blend are not
 // computed -- the cells of an active brick that lie in air, before the rays reach the body.  One vote per step.
-template <int V, bool OFF32, bool OTF = false, bool ZSKIP = false, bool LTF = false>
+template <int V, bool OFF32, bool ZSKIP = false, bool LTF = false>
 __device__ __forceinline__ void sample_and_blend(const MarchParams& P, f3 p, f3 w, float4& dst, f3 start, float ss)
 {
     if constexpr (V == V_BASIC && ZSKIP) {
@@ -1068,8 +978,7 @@ __device__ __forceinline__ void sample_and_blend(const MarchParams& P, f3 p, f3 
         // normalize3 / shade / blend.
         Fetch4 q;
         float fx, fy, fz;
-        if constexpr (OTF) fetch_rgba_otf<OFF32>(P.vol[0], p, q, fx, fy, fz);
-        else fetch_rgba<OFF32>(P.vol[0], p, q, fx, fy, fz);
+        fetch_rgba<OFF32>(P.vol[0], p, q, fx, fy, fz);
         const v2f zw = interp_zw(q, fx, fy, fz);  // (gradient z, density)
         if constexpr (ZSKIP) {
             if (vr_ballot(!opacity_is_zero(P, zw.y)) == 0) return;
@@ -1106,7 +1015,7 @@ __device__ __forceinline__ void sample_and_blend(const MarchParams& P, f3 p, f3 
             }
             return;
         }
-        const Src s = sample_src<V, OFF32, OTF, LTF>(P, p, w, start, dst.w, ss);
+        const Src s = sample_src<V, OFF32, LTF>(P, p, w, start, dst.w, ss);
         blend(s.rgb, s.a, dst);
     }
 }
@@ -1153,24 +1062,20 @@ __device__ __forceinline__ PixelSlot map_pixel_at(const MarchParams& P, int lb, 
 {
     PixelSlot s;
     // Workgroups are dealt round-robin over the 8 XCDs (blocks b and b+8 share an XCD; speed only, never
-    // correctness).  The 16 blocks of one 64x64 tile stay on ONE XCD (their rays traverse neighbouring voxels:
-    // shared L2 lines), while consecutive tiles go to different XCDs so that every XCD gets an even share of the
-    // heavy (volume-covered) and the empty parts of the screen.
-    // A block is 1 or 4 wavefronts (blockDim.x 64 / 256); a tile is 64 packets of 8x8 pixels either way, packet
-    // pk = 4 * (16x16 sub-block) + quadrant.
-    const int xcd = lb & 7, q = lb >> 3;
-    const int bpt = 64 / wpb;  // blocks per tile
-    int n = xcd + 8 * (q / bpt);  // ordinal of the owned tile this block works on
-    int pk = (q % bpt) * wpb + wib;
-    if (P.xcd_mode == 2 && wpb == 1) {
-        // an even sample of the screen for every XCD at the grain of 16x16 sub-blocks: an XCD gets two whole sub-blocks (2 x 4
-        // packets) of every tile, so the four packets of a sub-block -- neighbouring rays, neighbouring voxels -- share an L2.
-        // Same frame time as the finest grain below, a fifth to a quarter less fabric traffic (C3 1.43 -> 1.16 GB, noisy air
-        // 5.2 -> 4.3 GB: gpurun_out/r5i); whole tiles per XCD (mode 0) halve the traffic and cost 9 % (the XCDs' work differs).
+    // correctness), and every XCD gets an even sample of the screen: its share of the heavy (volume-covered) and of the
+    // empty parts.  A block is 1 or 4 wavefronts (blockDim.x 64 / 256); a tile is 64 packets of 8x8 pixels either way,
+    // packet pk = 4 * (16x16 sub-block) + quadrant.
+    int n, pk;  // ordinal of the owned tile this block works on, packet in it
+    if (wpb == 1) {
+        // at the grain of 16x16 sub-blocks: an XCD gets two whole sub-blocks (2 x 4 packets) of every tile, so the four packets
+        // of a sub-block -- neighbouring rays, neighbouring voxels -- share an L2.  Same frame time as the finest grain below, a
+        // fifth to a quarter less fabric traffic (C3 1.43 -> 1.16 GB, noisy air 5.2 -> 4.3 GB); whole tiles per XCD halve the
+        // traffic and cost 9 % (the XCDs' work differs).
         n = lb / 64;
         const int l = lb % 64, hi = l >> 3;
         pk = (((l & 7) | ((hi & 1) << 3)) << 2) | (hi >> 1);
-    } else if (P.xcd_mode != 0) {  // consecutive blocks of a tile on consecutive XCDs: every XCD gets an even sample of the screen
+    } else {  // consecutive blocks of a tile on consecutive XCDs
+        const int bpt = 64 / wpb;  // blocks per tile
         n = lb / bpt;
         pk = (lb % bpt) * wpb + wib;
     }
@@ -1185,7 +1090,7 @@ __device__ __forceinline__ PixelSlot map_pixel_at(const MarchParams& P, int lb, 
     s.px = tx * kTile + tpx;
     s.py = ty * kTile + tpy;
     s.in_launch = in_launch;
-    s.active = in_launch && (s.px < P.W) && (s.py < P.H) && (P.only_tile < 0 || P.only_tile == n);
+    s.active = in_launch && (s.px < P.W) && (s.py < P.H);
     s.out_index = P.packed ? (n * (kTile * kTile) + tpy * kTile + tpx) : (s.py * P.W + s.px);
     return s;
 }
@@ -1281,16 +1186,14 @@ __device__ __forceinline__ void store_block_counts(const MarchParams& P, unsigne
         o[4] = wall_clock64();
         // HW_ID | XCC_ID << 32 | longest per-ray sample chain of the workgroup << 40
         o[5] = (unsigned long long)__builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11)) |
-               ((unsigned long long)(__builtin_amdgcn_s_getreg((20) | (0 << 6) | (31 << 11)) & 0x7fu) << 32) | (cr << 40);  // (bit 39: kRecSplit)
+               ((unsigned long long)(__builtin_amdgcn_s_getreg((20) | (0 << 6) | (31 << 11)) & 0x7fu) << 32) | (cr << 40);
     }
 }
 
-// store_block_counts for a block of ONE wavefront that is not a workgroup (persistent wavefronts, vr_pw.h; mixed lanes per
-// ray, vr_mixed.h): no barrier, no LDS.  `rec` = the record's index; split = the packet's rays were marched by two
-// wavefronts (vr_mixed.h): this is the first half's record, the second half's is at rec + (logical blocks of the launch)
-// (kRecSplit in word 5 tells the readers -- sum_block_counts_kernel, order_blocks_kernel, vr_last_block_trace -- to add it).
+// store_block_counts for a block of ONE wavefront that is not a workgroup (persistent wavefronts, vr_pw.h): no barrier, no
+// LDS.  `rec` = the record's index.
 __device__ __forceinline__ void store_wave_counts(const MarchParams& P, int rec, unsigned blends, unsigned covered, unsigned fetched,
-                                                  unsigned long long t_start, bool split = false)
+                                                  unsigned long long t_start)
 {
     unsigned long long packed_cnt = ((unsigned long long)covered << 40) | (unsigned long long)blends;
     unsigned long long fetched_cnt = fetched;
@@ -1310,68 +1213,9 @@ __device__ __forceinline__ void store_wave_counts(const MarchParams& P, int rec,
         o[4] = wall_clock64();
         o[5] = (unsigned long long)__builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11)) |
                ((unsigned long long)(__builtin_amdgcn_s_getreg((20) | (0 << 6) | (31 << 11)) & 0x7fu) << 32) |
-               (split ? kRecSplit : 0ull) | ((unsigned long long)crit << 40);
+               ((unsigned long long)crit << 40);
     }
 }
-
-// ---- exact empty-space leaping -----------------------------------------------------------------------------
-// p advances by one ROUNDED addition of `s` per step.  While p keeps its sign and binary exponent its ulp U is
-// constant, p = n*U and s = (k + f)*U with |f| <= 1/2, so every addition moves p by the same whole number of ulps
-// (k, or from the second addition on k or k+1 in the exact-tie case f = 1/2, where round-to-even makes the result
-// even and the increment constant afterwards).  Hence, with x1 = fl(x + s) and x2 = fl(x1 + s),
-//      bits(x after m additions) = bits(x1) + (m - 1) * (bits(x2) - bits(x1)),        m >= 1,
-// provided x, x1, x2 and the result share sign and exponent (the sequence is monotone, so the end points suffice).
-// That makes a jump over m steps O(1) and bit-identical to m single steps.  Returns false when the condition fails
-// (the caller then takes a single ordinary step).  leap_plan also returns how many steps fit before the binade edge.
-struct LeapCoord {
-    int b0, b1, d;  // bits of x and of x1 = fl(x+s); ulps per step from the second addition on
-    float mmax;     // largest m (as float, conservative) for which the result keeps x's sign and exponent
-};
-__device__ __forceinline__ LeapCoord leap_plan(float x, float s)
-{
-    const float x1 = x + s, x2 = x1 + s;
-    LeapCoord c;
-    c.b0 = __float_as_int(x);
-    c.b1 = __float_as_int(x1);
-    const int b2 = __float_as_int(x2);
-    c.d = b2 - c.b1;
-    // room, in ulps, between x1 and the edge of its binade in the direction the MAGNITUDE moves
-    const int mag1 = c.b1 & 0x7FFFFFFF, mag2 = b2 & 0x7FFFFFFF;
-    const int dm = mag2 - mag1;
-    const int room = dm > 0 ? (0x7FFFFF - (mag1 & 0x7FFFFF)) : (mag1 & 0x7FFFFF);
-    const bool same = (((c.b0 ^ c.b1) | (c.b0 ^ b2)) & (int)0xFF800000) == 0;  // x, x1, x2 in one binade
-    // m - 1 further increments of |dm| ulps must fit into `room`
-    c.mmax = !same ? 0.0f : (dm == 0 ? 1.0e9f : 1.0f + (float)room * (__builtin_amdgcn_rcpf((float)abs(dm)) * 0.999f));
-    return c;
-}
-__device__ __forceinline__ int leap_apply(const LeapCoord& c, int m, float& out)
-{
-    const int r = c.b1 + (m - 1) * c.d;
-    out = __int_as_float(r);
-    return (((c.b0 ^ r) & (int)0xFF800000) == 0) ? 1 : 0;  // final guard: sign and exponent unchanged
-}
-
-// Number of steps (>= 0) a ray at p certainly stays inside the cube of bricks within Chebyshev distance D-1 of its
-// own brick -- all of them inert by construction of the distance field.  Same conservative span arithmetic as the
-// brick definition: base-cell index floor(p*n - 0.5) in [8*lo, 8*(hi+1)), shrunk by 0.01 cell; edge bricks also own
-// the clamped cells beyond the volume (no bound there: the caller keeps the leap inside the clip range).
-__device__ __forceinline__ float leap_axis(float p, float s, float bs, int nb, int k, float inv_n)
-{
-    if (s == 0.0f) return 1.0e9f;
-    const int b = clampi((int)floorf(mad(p, bs, -kBrickHalf)), 0, nb - 1);
-    float room;
-    if (s > 0.0f) {
-        const int hi = b + k;  // last inert brick index in the direction of travel
-        if (hi >= nb - 1) return 1.0e9f;
-        room = ((float)((hi + 1) << kBrickShift) + 0.49f) * inv_n - p;
-    } else {
-        const int lo = b - k;
-        if (lo <= 0) return 1.0e9f;
-        room = p - ((float)(lo << kBrickShift) + 0.51f) * inv_n;
-    }
-    return room * (__builtin_amdgcn_rcpf(fabsf(s)) * 0.999f);  // approximate reciprocal, scaled down: never too large
-}
-
 
 // Number of steps a ray certainly stays inside IsInSampleCoords: positions p_0 .. p_{n-1} of the accumulation
 // p_{k+1} = fl(p_k + step) are inside [b0, b1] on every axis.
@@ -1396,10 +1240,6 @@ __device__ __forceinline__ int steps_inside(f3 p, f3 step, float bx0, float by0,
     return (in0 && f > 0.0f) ? (int)f : 0;
 }
 
-#ifndef VR_APPROACH
-#define VR_APPROACH 1
-#endif
-constexpr bool kApproach = VR_APPROACH != 0;  // the approach loop in front of the march loops (-DVR_APPROACH=0: A/B builds)
 constexpr int kApproachMax = 1024;            // identity steps one iteration of it may take
 // Steps [k0, k1] outside of which the ray's positions certainly lie outside the box [lo, hi] (uvw; the caller's box carries its own
 // margin of a whole brick, far above what the rounded additions of n_steps steps can drift -- 2^-23 per step -- and what this
@@ -1428,12 +1268,12 @@ __device__ __forceinline__ void steps_near_box(f3 p, f3 s, const float* box, int
     k1 = miss ? -1 : (int)fminf(t1 * 1.001f + 3.0f, 2.0e9f);
 }
 
-// OTF (V_LIGHT only): the corners' gradients are derived from the density plane (fetch_rgba_otf) instead of read from
-// the vec4 voxels; the host asks for it when the volume's .rgb is verified to be PreComputeGradient(false) of its .a.
 // The whole march of one ray (ray set-up, per-pixel prologue, the loop): what a lane does for its pixel `slot`.  Shared by
 // march_kernel (one packet per wavefront of the grid) and march_pw_kernel (vr_pw.h: persistent wavefronts that take packet
 // after packet from a queue; LTF = transfer-function slot 0 read from the workgroup's LDS).
-template <int V, bool OFF32, bool SKIP, int LEAP, bool OTF, bool LTF>
+// LEAP: 0 = no skipping; 2 = skipping with the next step's corner loads software-pipelined (kPipe; march_pw_kernel's PIPE form);
+// 3 = skipping with wave-uniform runs of identity steps (march_kernel's skipping form).
+template <int V, bool OFF32, bool SKIP, int LEAP, bool LTF>
 __device__ __forceinline__ void march_packet(const MarchParams& P, const PixelSlot& slot, float4& dst, unsigned& blends,
                                              unsigned& covered, unsigned& fetched)
 {
@@ -1488,7 +1328,7 @@ __device__ __forceinline__ void march_packet(const MarchParams& P, const PixelSl
                 // wavefront whose rays are all inside tissue skips that block, and the eight corner loads it has issued
                 // for the next step (kPipe) stay in flight from the shading of one step to the interpolation of the next.
                 constexpr bool kRun = SKIP && (LEAP >= 2);                              // wave-uniform runs of identity steps
-                constexpr bool kPipe = (V == V_LIGHT || V == V_BASIC) && LEAP != 3 && LEAP != 1 && !OTF;  // corner prefetch
+                constexpr bool kPipe = (V == V_LIGHT || V == V_BASIC) && LEAP != 3;     // corner prefetch
                 unsigned D = 0, Dn = 0, Dq = 0, Dn2 = 0;
                 bool have = false;   // the previous iteration sampled: corners of p requested (F4 / F1), Dn arrived
                 bool stale = false;  // ... and the one before did, this one did not: Dq was not requested
@@ -1497,7 +1337,7 @@ __device__ __forceinline__ void march_packet(const MarchParams& P, const PixelSl
                 float wfx = 0.0f, wfy = 0.0f, wfz = 0.0f;
                 const int lim = min(n_inside, P.steps_count);  // runs stay inside the provably-in-box prefix
                 int i0 = 0;  // the step the loop below starts at
-                if constexpr (kRun && kApproach) {
+                if constexpr (kRun) {
                     // THE APPROACH (march_p2_kernel's, vr_p2.h, with votes instead of a wave minimum: the lanes without a ray are
                     // switched off here): until a ray of the packet stands in an active brick, one byte per ray and the identity
                     // steps it allows -- the largest power of two every ray allows -- as plain rounded additions; rays outside the
@@ -1536,7 +1376,6 @@ __device__ __forceinline__ void march_packet(const MarchParams& P, const PixelSl
                     Dq = dist_at(P, brick_of<OFF32>(P, mk3(p.x + step.x, p.y + step.y, p.z + step.z)));
                     asm volatile("" : "+v"(D));  // wait for D here; Dq stays in flight
                 }
-                const int prio_q1 = P.steps_count >> 2, prio_q2 = P.steps_count >> 1, prio_q3 = prio_q1 + prio_q2;
                 // kRun: steps a ray at distance-field value D can take while it certainly stays within D-1 bricks of
                 // its brick on every axis = (D - 1 - 1/16) / (largest per-step move in brick units), 0.1 % short
                 float leap_c = 0.0f;
@@ -1545,7 +1384,7 @@ __device__ __forceinline__ void march_packet(const MarchParams& P, const PixelSl
                     leap_c = 0.999f / vmax;  // vmax 0 -> inf (capped below), NaN -> n_inside is 0 and nothing leaps
                 }
                 for (int i = i0; i < P.steps_count;) {
-                    f3 pn = mk3(p.x + step.x, p.y + step.y, p.z + step.z);
+                    const f3 pn = mk3(p.x + step.x, p.y + step.y, p.z + step.z);
                     const f3 pq = mk3(pn.x + step.x, pn.y + step.y, pn.z + step.z);
                     if constexpr (SKIP) {
                         if (!have) {
@@ -1598,19 +1437,8 @@ __device__ __forceinline__ void march_packet(const MarchParams& P, const PixelSl
                     bool inb = true;
                     if (i >= n_inside)
                         inb = p.x >= bx0 && p.x <= bx1 && p.y >= by0 && p.y <= by1 && p.z >= bz0 && p.z <= bz1;
-                    int adv = 1;  // steps this iteration advances by
                     if (inb) {
                         if (!SKIP || D == 0) {
-                            if (P.prio_mode == 1 && (__builtin_amdgcn_readfirstlane(i) & 7) == 0) {
-                                // longest-remaining-path-first: the frame is done when its longest ray is, so wavefronts
-                                // whose rays still have far to go get the issue slots first (4 levels, by quarters of
-                                // stepsCount; re-evaluated every 8th step; speed only)
-                                const int r = lim - i;
-                                if (vr_ballot(r > prio_q3) != 0) __builtin_amdgcn_s_setprio(3);
-                                else if (vr_ballot(r > prio_q2) != 0) __builtin_amdgcn_s_setprio(2);
-                                else if (vr_ballot(r > prio_q1) != 0) __builtin_amdgcn_s_setprio(1);
-                                else __builtin_amdgcn_s_setprio(0);
-                            }
                             if constexpr (kPipe) {
                                 // Software pipeline over the steps of a ray: the corners of THIS step were requested one
                                 // iteration ago (or are requested now, on entering tissue).  The next step's corners are
@@ -1656,7 +1484,7 @@ __device__ __forceinline__ void march_packet(const MarchParams& P, const PixelSl
                                     }
                                 }
                             } else {
-                                sample_and_blend<V, OFF32, OTF, SKIP, LTF>(P, p, w, dst, ray.start, step_size);
+                                sample_and_blend<V, OFF32, SKIP, LTF>(P, p, w, dst, ray.start, step_size);
                             }
                             ++fetched;
                             ++blends;
@@ -1667,42 +1495,7 @@ __device__ __forceinline__ void march_packet(const MarchParams& P, const PixelSl
                                 stale = have;  // leaving tissue: back to the loop-head scheme
                                 have = false;
                             }
-                            if constexpr (LEAP == 1) {
-                                if (D >= 2 && i + 3 < lim) {
-                                    const DevVolume& v = P.vol[P.skip_vol];
-                                    const int k = (int)D - 1;
-                                    float mf = fminf(fminf(leap_axis(p.x, step.x, P.bsx, P.bnx, k, 1.0f / (float)v.nx),
-                                                           leap_axis(p.y, step.y, P.bsy, P.bny, k, 1.0f / (float)v.ny)),
-                                                     fminf(leap_axis(p.z, step.z, P.bsz, P.bnz, k, 1.0f / (float)v.nz), 255.0f));
-                                    // every coordinate also bounds the leap by its room to the edge of its binade
-                                    const LeapCoord cx = leap_plan(p.x, step.x), cy = leap_plan(p.y, step.y),
-                                                    cz = leap_plan(p.z, step.z);
-                                    mf = fminf(fminf(mf - 1.0f, cx.mmax), fminf(cy.mmax, cz.mmax));
-                                    LeapCoord wx = cx, wy = cy, wz = cz;
-                                    if constexpr (V != V_BASIC && V != V_TF_CALIB) {
-                                        wx = leap_plan(w.x, wstep.x);
-                                        wy = leap_plan(w.y, wstep.y);
-                                        wz = leap_plan(w.z, wstep.z);
-                                        mf = fminf(fminf(mf, wx.mmax), fminf(wy.mmax, wz.mmax));
-                                    }
-                                    const int m = min((int)mf, lim - i - 1);
-                                    if (m >= 3) {
-                                        f3 q, wq = w;
-                                        int ok = leap_apply(cx, m, q.x) & leap_apply(cy, m, q.y) & leap_apply(cz, m, q.z);
-                                        if constexpr (V != V_BASIC && V != V_TF_CALIB)
-                                            ok = ok & leap_apply(wx, m, wq.x) & leap_apply(wy, m, wq.y) & leap_apply(wz, m, wq.z);
-                                        if (ok) {  // all m steps are in-box identity blends: count them and land
-                                            adv = m;
-                                            pn = q;
-                                            if constexpr (V != V_BASIC && V != V_TF_CALIB) w = wq;
-                                            Dn = dist_at(P, brick_of<OFF32>(P, pn));
-                                            Dq = dist_at(P, brick_of<OFF32>(P, mk3(pn.x + step.x, pn.y + step.y, pn.z + step.z)));
-                                            asm volatile("" : "+v"(Dn));
-                                        }
-                                    }
-                                }
-                            }
-                            blends += (unsigned)adv;
+                            ++blends;
                         }
                     } else {
                         if constexpr (kPipe) {
@@ -1720,18 +1513,16 @@ __device__ __forceinline__ void march_packet(const MarchParams& P, const PixelSl
                     if constexpr (kPipe) {
                         if (have) Dn = Dn2;
                     }
-                    if (adv == 1) {
-                        if constexpr (V != V_BASIC && V != V_TF_CALIB) w = mk3(w.x + wstep.x, w.y + wstep.y, w.z + wstep.z);
-                    }
-                    i += adv;
+                    if constexpr (V != V_BASIC && V != V_TF_CALIB) w = mk3(w.x + wstep.x, w.y + wstep.y, w.z + wstep.z);
+                    ++i;
                 }
             }
         }
     }
 }
 
-template <int V, bool OFF32, bool SKIP, int LEAP, bool OTF = false, bool BATCH = false>
-__global__ __launch_bounds__(256, VR_LIGHT_WAVES_PER_EU(V, OTF)) void march_kernel(const MarchBatch B)
+template <int V, bool OFF32, bool SKIP, int LEAP, bool BATCH = false>
+__global__ __launch_bounds__(256, 1) void march_kernel(const MarchBatch B)
 {
     const MarchParams& P = frame_params<BATCH>(B);
     const unsigned long long t_start = wall_clock64();
@@ -1748,7 +1539,7 @@ __global__ __launch_bounds__(256, VR_LIGHT_WAVES_PER_EU(V, OTF)) void march_kern
         }
     }
 
-    march_packet<V, OFF32, SKIP, LEAP, OTF, false>(P, slot, dst, blends, covered, fetched);
+    march_packet<V, OFF32, SKIP, LEAP, false>(P, slot, dst, blends, covered, fetched);
 
     // packed-tile launches write every slot of an owned tile (pixels outside the viewport = 0)
     if (slot.active || (P.packed && slot.in_launch)) P.out[slot.out_index] = dst;
@@ -1872,12 +1663,6 @@ __global__ __launch_bounds__(256) void sum_block_counts_kernel(const unsigned lo
         a += in[(size_t)i * kBlockRecord];
         b += in[(size_t)i * kBlockRecord + 1];
         f += in[(size_t)i * kBlockRecord + 2];
-        if (in[(size_t)i * kBlockRecord + 5] & kRecSplit) {  // the packet's second half (vr_mixed.h)
-            const size_t h = (size_t)(i + n_blocks) * kBlockRecord;
-            a += in[h];
-            b += in[h + 1];
-            f += in[h + 2];
-        }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -1910,7 +1695,7 @@ __global__ __launch_bounds__(64) void spin_kernel(unsigned long long ticks, unsi
 // One workgroup: order[] = the logical blocks of the launch whose records are `in`, sorted by the longest per-ray sample
 // chain of the block (record word 5, bits 40..), longest first, SEPARATELY within each residue class of the block index
 // modulo 8: position b of the order holds a block lb with lb % 8 == b % 8.  Workgroups are dispatched round-robin over the
-// 8 XCDs, so a block stays on the XCD its index maps to (what map_pixel's xcd_mode relies on) and every XCD runs its own
+// 8 XCDs, so a block stays on the XCD its index maps to (what map_pixel relies on) and every XCD runs its own
 // blocks longest-processing-time-first.  Eight counting sorts over 128 key buckets each (n_blocks % 8 == 0).
 constexpr int kOrderMaxBlocks = 192 * 1024;  // launches with more blocks keep the index order (C5, one wavefront per block: 130 560)
 // It also reports how long the launch took: last workgroup end - first workgroup start of the records it reads (100 MHz
@@ -1944,16 +1729,8 @@ __global__ __launch_bounds__(1024) void order_blocks_kernel(const unsigned long 
     for (int k = 0; k * 1024 < n_blocks; ++k) {
         const int b = t + k * 1024;
         if (b < n_blocks) {
-            const unsigned long long w5 = in[(size_t)b * kBlockRecord + 5];
-            unsigned long long crit = w5 >> 40;
-            unsigned long long b0 = in[(size_t)b * kBlockRecord + 3], b1 = in[(size_t)b * kBlockRecord + 4];
-            if (w5 & kRecSplit) {  // marched by two wavefronts (vr_mixed.h): the second half's record
-                const size_t h = (size_t)(b + n_blocks) * kBlockRecord;
-                const unsigned long long c2 = in[h + 5] >> 40, s2 = in[h + 3], e2 = in[h + 4];
-                crit = c2 > crit ? c2 : crit;
-                b0 = s2 < b0 ? s2 : b0;
-                b1 = e2 > b1 ? e2 : b1;
-            }
+            const unsigned long long crit = in[(size_t)b * kBlockRecord + 5] >> 40;
+            const unsigned long long b0 = in[(size_t)b * kBlockRecord + 3], b1 = in[(size_t)b * kBlockRecord + 4];
             my_first = b0 < my_first ? b0 : my_first;
             my_last = b1 > my_last ? b1 : my_last;
             my_chain = crit > my_chain ? (unsigned)crit : my_chain;
@@ -2117,6 +1894,7 @@ __global__ void extract_density_kernel(const float4* __restrict__ vol, float* __
 }
 // *mismatch != 0 afterwards unless EVERY voxel's .rgb has exactly the bits PreComputeGradient(false) computes from the
 // .a plane ((-(p - m)) * 0.5 per axis, neighbours outside the grid = 0; NaNs never match).
+__device__ __forceinline__ float grad_cd(float p, float m) { return (-(p - m)) * 0.5f; }
 __global__ void verify_gradient_kernel(const float4* __restrict__ vol, const float* __restrict__ dens, int nx, int ny, int nz,
                                        unsigned* __restrict__ mismatch)
 {

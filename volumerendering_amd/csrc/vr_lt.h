@@ -21,10 +21,33 @@
 // Reference loop: BasicVolLightApp.wgsl:207-234.  Flavour 15 (vr_set_kernel_flavour), lit shader, one frame per launch.
 #pragma once
 #include "vr_kernels.h"
-#include "vr_wtb.h"
 
 namespace VR_KNS {
 using namespace vr;
+
+// Wave-wide component-wise minimum of two packed 16-bit values (v_pk_min_u16): the six bounds of the voxel box
+// travel as three such pairs, the upper bounds complemented so that one kind of reduction serves both.
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned pk_min_u16(unsigned a, unsigned b)
+{
+    u16x2 r = __builtin_elementwise_min(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b));
+    return __builtin_bit_cast(unsigned, r);
+}
+__device__ __forceinline__ unsigned wave_pk_min_u16(unsigned v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = pk_min_u16(v, (unsigned)__shfl_xor((int)v, off, 64));
+    return v;
+}
+
+// Orders a wavefront's LDS writes before its following LDS reads of the SAME wave-private region (and the reads of one
+// tile before the next tile load overwrites them).  A wavefront's LDS instructions execute in issue order, so no s_barrier
+// is needed; this only stops the compiler from moving memory operations across it.
+__device__ __forceinline__ void wave_lds_fence()
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
 
 constexpr int kLtCap = 480;   // float4 voxels per tile: 7.5 KiB of LDS per wavefront (one wavefront per workgroup, 20 per CU)
 constexpr int kLtSteps = 4;   // steps a tile is planned for
@@ -269,7 +292,7 @@ __global__ __launch_bounds__(256) void march_lt_kernel(const MarchBatch B)
     }
 
     if (slot.active || (P.packed && slot.in_launch)) P.out[slot.out_index] = dst;
-    store_wave_counts(P, lb, blends, covered, fetched, t_start, false);
+    store_wave_counts(P, lb, blends, covered, fetched, t_start);
 }
 
 }  // namespace VR_KNS

@@ -36,8 +36,7 @@ constexpr int kP2JumpMax = VR_P2_JUMP_MAX;  // identity steps one trip may skip 
 #ifndef VR_P2_EXIT
 #define VR_P2_EXIT 1
 #endif
-constexpr bool kP2Exit = kApproach && VR_P2_EXIT != 0;  // ... and the same knowledge behind the box of the active bricks (A/B: -DVR_P2_EXIT=0)
-constexpr bool kP2Approach = kApproach;  // the approach loop in front of the pipelined loop (-DVR_APPROACH=0: A/B builds)
+constexpr bool kP2Exit = VR_P2_EXIT != 0;  // ... and the same knowledge behind the box of the active bricks (A/B: -DVR_P2_EXIT=0)
 constexpr int kP2Threads = 768;  // at most 12 wavefronts per CU, 3 per SIMD (two corner buffers are 64 of ~168 VGPRs)
 constexpr int kP2ThreadsUnlit = 1024;  // the unlit shader's buffers are 4-byte densities (101 VGPRs): 4 wavefronts per SIMD fit
 
@@ -229,7 +228,7 @@ __device__ __forceinline__ bool p2_vote(const MarchParams& P0, bool sampled, flo
     j = masked ? 0x7fffffff : j;
     j = sampled ? j : (int)0x80000000;             // a ray that does not sample never asks for the shading
     asm volatile("" : "+v"(j));                    // (kept as a value: the compiler would turn the compare back into mask logic)
-    return vr_ballot(j > P0.zskip_prefix) != 0;
+    return vr_ballot(j > P0.tf_zero_prefix) != 0;
 }
 
 // SKIP: empty-space skipping on top of it.  One distance-field byte per ray rides along with each corner buffer: the byte of
@@ -249,12 +248,10 @@ __global__ __launch_bounds__(V == V_BASIC ? kP2ThreadsUnlit : kP2Threads) void m
     // (the one-frame >= 4 GiB kernel is at the register limit: with the approach loop in front its pipelined loop reloads two register
     // pairs from scratch per step -- C5 3.39 -> 3.45 ms, with the exit test 3.59, a rank's half of C5 1.82 -> 2.00; its several-frames
     // form and every other form gain: tools/experiments/r4x.sh, r4z.sh)
-    // BATCH names the launch (several frames / one); kMulti is the code: the several-frames form -- a frame's parameters read where they
-    // are used, through a wave-uniform index -- also for one frame per launch (vr_launch.h: VR_P2_ALL_BATCH / VR_P2_WIN_BATCH; the
-    // one-frame launches keep a kernel name of their own in the profiles)
-    constexpr bool kMulti = BATCH || (WIN ? VR_P2_WIN_BATCH != 0 : VR_P2_ALL_BATCH != 0);
-    constexpr bool kApproachHere = SKIP && kP2Approach && !(WIN && !kMulti);
-    constexpr bool kExit = kApproachHere && kP2Exit;
+    // BATCH names the launch (several frames / one); the code is the several-frames form -- a frame's parameters read where they are
+    // used, through a wave-uniform index -- also for one frame per launch (vr_launch.h; the one-frame launches keep a kernel name of
+    // their own in the profiles)
+    constexpr bool kExit = SKIP && kP2Exit;
     const MarchParams& P0 = B.frame[0];                 // what every frame of the launch shares: volumes, tables, brick records
     const DevVolume& vol = P0.vol[kSrc];
     P2Lds L;
@@ -296,30 +293,20 @@ __global__ __launch_bounds__(V == V_BASIC ? kP2ThreadsUnlit : kP2Threads) void m
     const unsigned groups = (gridDim.x - cls + 7u) >> 3;
     const unsigned wib = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const unsigned wpb = blockDim.x >> 6;
-    const unsigned nf = kMulti ? B.n_frames : 1u;
+    const unsigned nf = B.n_frames;
     const unsigned n_c = (Q.n_items >> 3) * nf;  // items per class: every frame's packets of the class, the frames interleaved
     // first item: static (wavefront k of every workgroup before wavefront k + 1 of any: the longest packets are dealt over the CUs, no
-    // atomic at the start of the launch) -- or, Q.dynamic (launches in flight: workgroups start when others retire, and the
-    // first to start should take the longest packets left), from the class's head like every later one
+    // atomic at the start of the launch); every later one from the class's head
     unsigned idx = wib * groups + (blockIdx.x >> 3);
-    if (Q.dynamic) {
-        unsigned r = 0;
-        if ((threadIdx.x & 63u) == 0) r = atomicAdd(Q.heads + cls * kPwHeadStride, 1u);
-        idx = (unsigned)__builtin_amdgcn_readfirstlane((int)r);
-    }
     typedef typename std::conditional<kLit, vr_f4, float>::type Elem;
     const unsigned cur = cls;
     for (;;) {
         if (idx >= n_c) break;  // (the class's queue has run dry: the wavefront leaves)
         // item idx of the class = packet idx / nf (in the launch order) of frame idx % nf
-        unsigned item = idx, frame = 0;
-        if constexpr (kMulti) {
-            item = batch_group(idx, nf);
-            frame = idx - item * nf;
-        }
+        const unsigned item = batch_group(idx, nf), frame = idx - item * nf;
         // (the frame's parameters through a wave-uniform index, said so explicitly: scalar loads; behind an index the compiler takes
         // for divergent they become vector loads -- in the middle of the pipelined loop, whose wait counts they then drain)
-        const MarchParams& P = B.frame[kMulti ? (unsigned)__builtin_amdgcn_readfirstlane((int)frame) : 0u];
+        const MarchParams& P = B.frame[(unsigned)__builtin_amdgcn_readfirstlane((int)frame)];
         // what the step loop reads of the frame, once per packet
         const f3 light_pos = mk3(P.light_pos[0], P.light_pos[1], P.light_pos[2]), light_dif = mk3(P.light_dif[0], P.light_dif[1], P.light_dif[2]),
                  light_amb = mk3(P.light_amb[0], P.light_amb[1], P.light_amb[2]);
@@ -546,7 +533,7 @@ __global__ __launch_bounds__(V == V_BASIC ? kP2ThreadsUnlit : kP2Threads) void m
                 if constexpr (kLit) w = mk3(w.x + wstep.x, w.y + wstep.y, w.z + wstep.z);
             };
             int k_last = 0x7fffffff;  // no step of the ray behind this one can lie in an active brick (steps_near_box)
-            if constexpr (kApproachHere) {
+            if constexpr (SKIP) {
                 // THE APPROACH: until a ray of the packet stands in an active brick nothing is requested ahead -- a byte per ray, the
                 // identity steps it allows (march_packet's run length, and one for the position itself), the wave's minimum of them
                 // as plain rounded additions.  A packet that never meets an active brick (C3: 7 775 of the 12 214 packets whose rays
@@ -682,7 +669,7 @@ __global__ __launch_bounds__(V == V_BASIC ? kP2ThreadsUnlit : kP2Threads) void m
                         bool sampled = true;
                         if constexpr (SKIP) sampled = i <= k_last && dist_at(P0, brick_of<true>(P0, p)) == 0u;
                         if (sampled) {
-                            sample_and_blend<V, !WIN, false, SKIP, true>(P, p, w, dst, mk3(0.0f, 0.0f, 0.0f), 0.0f);
+                            sample_and_blend<V, !WIN, SKIP, true>(P, p, w, dst, mk3(0.0f, 0.0f, 0.0f), 0.0f);
                             ++fetched;
                         }
                         ++blends;
@@ -720,7 +707,7 @@ __global__ __launch_bounds__(V == V_BASIC ? kP2ThreadsUnlit : kP2Threads) void m
 #endif
         unsigned r = 0;
         if ((threadIdx.x & 63u) == 0) r = atomicAdd(Q.heads + cur * kPwHeadStride, 1u);
-        idx = (Q.dynamic ? 0u : groups * wpb) + (unsigned)__builtin_amdgcn_readfirstlane((int)r);
+        idx = groups * wpb + (unsigned)__builtin_amdgcn_readfirstlane((int)r);
     }
 }
 

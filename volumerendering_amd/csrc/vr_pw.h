@@ -71,7 +71,7 @@ __global__ __launch_bounds__(kPwThreads) void march_pw_kernel(const MarchBatch B
         const PixelSlot slot = map_pixel_at(P, lb, 1, 0);
         float4 dst = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         unsigned blends = 0, covered = 0, fetched = 0;
-        march_packet<V, OFF32, SKIP, PIPE ? 2 : (SKIP ? 3 : 0), false, LTF>(P, slot, dst, blends, covered, fetched);
+        march_packet<V, OFF32, SKIP, PIPE ? 2 : (SKIP ? 3 : 0), LTF>(P, slot, dst, blends, covered, fetched);
         if (slot.active || (P.packed && slot.in_launch)) P.out[slot.out_index] = dst;
         store_wave_counts(P, lb, blends, covered, fetched, t_start);
         unsigned r = 0;
