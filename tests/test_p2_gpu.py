@@ -207,13 +207,11 @@ def test_persistent_launches_in_flight(variant):
                     o.close()
 
 
-@pytest.mark.parametrize("host_wait", ["0", "1"])
-def test_one_frame_at_a_time_on_one_stream_far_ahead_of_the_device(monkeypatch, host_wait):
+def test_one_frame_at_a_time_on_one_stream_far_ahead_of_the_device():
     """The stream-ordered loop of bench.py's serial leg: 40 launches enqueued on one stream without waiting for any, four cameras in
     turn into four buffers -- more launches than record slots (8) and launch-order buffers (16), so every launch takes an earlier
-    launch's order and re-uses a record slot whose sort it must be ordered behind (one wait for the younger of the two sorts; with
-    VR_EXP_HOST_ORDER_WAIT=1 on the host).  Every frame equals its reference, the last launch's counts too; default and forced kernels."""
-    monkeypatch.setenv("VR_EXP_HOST_ORDER_WAIT", host_wait)
+    launch's order and re-uses a record slot whose sort it must be ordered behind (one wait for the younger of the two sorts).
+    Every frame equals its reference, the last launch's counts too; default and forced kernels."""
     n, W, H = 24, 640, 360
     step, count = hr.stepping_params(n, n, n)
     vols, tfs = vt.scene(capi.LIGHT, n=n)

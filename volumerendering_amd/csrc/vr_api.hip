@@ -123,9 +123,6 @@ struct vr_ctx {
     hipStream_t flight[kStreams] = {};  // vr_stream(): streams probed to run side by side (created on first use)
     int n_flight = 0;
     hipStream_t order_stream = nullptr;  // the sorts run here, behind their launch's event: never on a frame's critical path
-    // VR_EXP_HOST_ORDER_WAIT=1: one frame at a time, a launch waits for the two sorts it depends on (the launch order it reads, the sort
-    // that read its record slot last) on the HOST, before it is enqueued, instead of on its stream (enqueue_render).  Off by default.
-    int host_order_wait = 0;
     int cnt_buf = 0;                           // the buffer the last launch wrote
     bool cnt_pending = false;                  // block counts of the last launch not summed / copied yet
     int cnt_blocks = 0;
@@ -427,10 +424,40 @@ int tune_pick(vr_ctx* c, unsigned long long key, unsigned long long shape, const
     return t->cand[best];
 }
 
-// Enqueue one launch on `s`: ONE frame with the context's uniforms into `out` (nullptr -> ctx-owned buffer), or, with
-// batch_u / batch_out, n_frames (2 .. kBatchMax) frames of the same scene, each with its own uniforms and output buffer.
-int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, float4* out, hipStream_t s, bool frame_events,
-                   int n_frames = 1, const vr_uniforms* batch_u = nullptr, void* const* batch_out = nullptr)
+// the bricked copy of a volume (DevVolume::bricked): storage bricks per axis, and their slots (voxels)
+struct BrickedGrid {
+    unsigned nbx, nby, nbz;
+    size_t slots;
+};
+BrickedGrid bricked_grid(const DevVolume& v)
+{
+    const unsigned nbx = ((unsigned)v.nx + kVbM) >> kVbS, nby = ((unsigned)v.ny + kVbM) >> kVbS, nbz = ((unsigned)v.nz + kVbM) >> kVbS;
+    return {nbx, nby, nbz, (size_t)nbx * nby * nbz * kVbN};
+}
+
+// empty-space bricks along an axis of n base cells
+int skip_bricks(int n) { return (n + kBrickCells - 1) >> kBrickShift; }
+
+// rays per hardware lane (n_cus x 4 x 5 x 64) of `frames` launches of this rank's share of the frame: how full they keep the machine
+double rays_per_lane(const vr_ctx* c, int rank, int world, int frames)
+{
+    const long long px = (long long)tile_count(c, rank, world) * kTile * kTile;
+    return (double)px * frames / ((double)c->n_cus * 4.0 * 5.0 * 64.0);
+}
+
+// what a launch rendered, whatever kernel form it took (OrderSlot::scene_key: the key of the longest ray chain its sort reports)
+unsigned long long scene_key(const vr_ctx* c, int variant, int rank, int world, bool packed)
+{
+    return ((unsigned long long)variant << 16) ^ ((unsigned long long)world << 8) ^ (unsigned long long)rank ^ (packed ? 1ull << 63 : 0ull) ^
+           ((unsigned long long)c->W << 40) ^ ((unsigned long long)c->H << 24);
+}
+
+// TF slot 0 fits a workgroup's LDS beside nothing else: one resolution for both tables, R <= 8190 (128 KiB)
+bool tf0_fits_lds(const vr_ctx* c) { return c->tf[0].res_o == c->tf[0].res_c && c->tf[0].res_o + 2 <= 8192; }
+
+// The arguments of a launch and the slots its shader samples (*nvol volumes); *off32: every one of them below 4 GiB.
+int check_render_args(vr_ctx* c, int variant, int rank, int world, int n_frames, const vr_uniforms* batch_u, void* const* batch_out,
+                      int* nvol, bool* off32)
 {
     if (variant < 0 || variant >= VR_VARIANT_COUNT) return fail(c, VR_ERR_INVALID_ARG, "vr_render: bad variant");
     if (world < 1 || rank < 0 || rank >= world) return fail(c, VR_ERR_INVALID_ARG, "vr_render: bad rank/world");
@@ -443,27 +470,28 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
             if (!is_identity(batch_u[f].model))  // (as vr_set_uniforms)
                 return fail(c, VR_ERR_UNSUPPORTED, "vr_render: model matrix must be the identity (App/src/Application.cpp:489-492)");
         }
-        out = (float4*)batch_out[0];
     } else {
         if (n_frames != 1) return fail(c, VR_ERR_INVALID_ARG, "vr_render: several frames per launch need their uniforms");
         if (!c->have_uniforms) return fail(c, VR_ERR_NOT_READY, "vr_render: vr_set_uniforms has not been called");
     }
-    const vr_uniforms& u0 = batch_u ? batch_u[0] : c->u;
-    int nvol, ntf;
-    variant_needs(variant, &nvol, &ntf);
-    bool off32 = true;
-    for (int i = 0; i < nvol; ++i) {
+    int ntf;
+    variant_needs(variant, nvol, &ntf);
+    *off32 = true;
+    for (int i = 0; i < *nvol; ++i) {
         if (!c->vol[i].data) return fail(c, VR_ERR_NOT_READY, "vr_render: volume slot " + std::to_string(i) + " is empty");
-        if (c->vol_bytes[i] > 0xFFFFFFFFull) off32 = false;
+        if (c->vol_bytes[i] > 0xFFFFFFFFull) *off32 = false;
     }
     for (int i = 0; i < ntf; ++i)
         if (!c->tf[i].opacity || !c->tf[i].color)
             return fail(c, VR_ERR_NOT_READY, "vr_render: TF slot " + std::to_string(i) + " is empty");
-    if (u0.steps_count < 0) return fail(c, VR_ERR_INVALID_ARG, "vr_render: negative steps_count");
-    VR_HIP(c, hipSetDevice(c->device));
-    (void)hipGetLastError();  // a stale error of somebody else's call must not be reported as a failed launch below
+    if ((batch_u ? batch_u[0] : c->u).steps_count < 0) return fail(c, VR_ERR_INVALID_ARG, "vr_render: negative steps_count");
+    return VR_OK;
+}
 
-    MarchParams P;
+// The parameters of a launch that no kernel form changes; the volumes as the vec4 voxels and their density plane (the bricked copies
+// replace them in use_bricked_copies).
+void fill_launch_params(const vr_ctx* c, MarchParams& P, const vr_uniforms& u0, int rank, int world, bool packed)
+{
     std::memset(&P, 0, sizeof P);
     P.W = (int)c->W;
     P.H = (int)c->H;
@@ -479,22 +507,6 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
         const size_t lin_bytes = c->vol_bytes[i];
         P.vol[i].data_bytes = lin_bytes > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)lin_bytes;
     }
-    // the bricked copies (layout 0) are what the gathers read (use_bricked, below)
-    auto use_bricked = [&]() {
-        for (int i = 0; i < VR_MAX_VOLUMES; ++i) {
-            if (!c->vol[i].data || !c->vol_bricked[i] || !c->vol_bdens[i]) continue;
-            const unsigned nbx = ((unsigned)c->vol[i].nx + kVbM) >> kVbS, nby = ((unsigned)c->vol[i].ny + kVbM) >> kVbS, nbz = ((unsigned)c->vol[i].nz + kVbM) >> kVbS;
-            const size_t slots = (size_t)nbx * nby * nbz * kVbN;
-            if (slots > 0xFFFFFFFFull) continue;  // (indices are 32 bits)
-            P.vol[i].data = c->vol_bricked[i];
-            P.vol[i].a_base = reinterpret_cast<const char*>(c->vol_bdens[i]);
-            P.vol[i].a_shift = 2;
-            P.vol[i].bricked = 1;
-            P.vol[i].brick_row = nbx * kVbN;
-            P.vol[i].brick_slab = nbx * nby * kVbN;
-            P.vol[i].data_bytes = slots * 16 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)(slots * 16);
-        }
-    };
     for (int i = 0; i < VR_MAX_TFS; ++i) P.tf[i] = c->tf[i];
     P.rank = rank;
     P.world = world;
@@ -503,16 +515,194 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
     P.n_tiles = tile_count(c, rank, world);
     P.packed = packed ? 1 : 0;
     P.n_blocks = P.n_tiles * kBlocksPerTile;
-    // exact empty-space skipping: only for the shaders whose opacity is the CT table value alone, only when a
-    // zero-opacity sample is provably the identity (finite colour table and light), and unless flavour 1 asks
-    // for the plain kernel
-    const bool skip_variant = variant == VR_VARIANT_BASIC || variant == VR_VARIANT_LIGHT ||
-                              variant == VR_VARIANT_THREE_FILES || variant == VR_VARIANT_VOLUME_MASK ||
-                              variant == VR_VARIANT_LIGHT_INSHADER;
-    const int sv = (variant == VR_VARIANT_VOLUME_MASK) ? 2 : 0;  // the volume whose density drives tf[0]'s opacity
-    int fl = c->flavour == 0 ? c->default_flavour : c->flavour;
-    unsigned chain_known = 0;  // longest ray chain + 1 of the most recent launch of this scene shape whose sort has reported (0: none)
-    if (fl == 0) {
+}
+
+// the bricked copies (layout 0) are what the gathers read
+void use_bricked_copies(const vr_ctx* c, MarchParams& P)
+{
+    for (int i = 0; i < VR_MAX_VOLUMES; ++i) {
+        if (!c->vol[i].data || !c->vol_bricked[i] || !c->vol_bdens[i]) continue;
+        const BrickedGrid g = bricked_grid(c->vol[i]);
+        if (g.slots > 0xFFFFFFFFull) continue;  // (indices are 32 bits)
+        P.vol[i].data = c->vol_bricked[i];
+        P.vol[i].a_base = reinterpret_cast<const char*>(c->vol_bdens[i]);
+        P.vol[i].a_shift = 2;
+        P.vol[i].bricked = 1;
+        P.vol[i].brick_row = g.nbx * kVbN;
+        P.vol[i].brick_slab = g.nbx * g.nby * kVbN;
+        P.vol[i].data_bytes = g.slots * 16 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)(g.slots * 16);
+    }
+}
+
+// What a launch could run, worked out once before the kernel choice (choose_flavour).
+struct Eligibility {
+    bool p2_ok;             // two steps ahead (16, 17) can run
+    unsigned p2_lds;        // ... with this much dynamic LDS (TF slot 0 and the three axis tables)
+    bool lut_ok;            // 18 can run
+    unsigned lut_lds;       // ... with this much (the slot tables of volume 0)
+    bool can_skip;          // exact empty-space skipping (prepare_skip)
+    bool whole_frame;       // enough rays to fill the machine in one frame
+    unsigned chain_known;   // longest ray chain + 1 of the most recent launch of this scene shape whose sort has reported (0: none)
+};
+
+// the longest ray chain + 1 of the most recent launch of this scene shape whose sort has reported (written to pinned memory by the
+// launch-order sort; read without synchronising, 0 = not known)
+unsigned last_chain(const vr_ctx* c, unsigned long long skey)
+{
+    unsigned chain = 0;
+    if (!c->h_chain) return chain;
+    unsigned long long best_seq = 0;
+    for (int i = 0; i < kOrderRing; ++i) {
+        const unsigned v = *(volatile unsigned*)&c->h_chain[i];
+        if (v != 0 && c->order_ring[i].scene_key == skey && c->order_ring[i].seq + 1 > best_seq) {
+            best_seq = c->order_ring[i].seq + 1;
+            chain = v;
+        }
+    }
+    return chain;
+}
+
+Eligibility eligibility(const vr_ctx* c, int requested, int variant, int n_frames, int rank, int world, bool packed, const vr_uniforms* batch_u)
+{
+    Eligibility E = {};
+    // two steps ahead (16, 17; march_p2_kernel, vr_p2.h): lit / unlit shader and the three-volume composite (with its brick records:
+    // choose_flavour); TF slot 0 (one resolution for both tables) and the three axis tables in LDS; the bricked copy with 32-bit slots,
+    // rows and slabs of bricks below 2^24 slots; a volume of 4 GiB or more through a moving window of at least four z-slabs of bricks.
+    // Launches of several frames and launches in flight included.
+    const int sv = variant == VR_VARIANT_VOLUME_MASK ? 2 : 0;  // the volume whose density drives tf[0]'s opacity
+    E.p2_ok = (variant == VR_VARIANT_LIGHT || variant == VR_VARIANT_BASIC || variant == VR_VARIANT_VOLUME_MASK) && tf0_fits_lds(c) &&
+              c->layout_mode == 0 && c->vol_bricked[sv] && c->vol_bdens[sv];
+    if (E.p2_ok) {
+        const DevVolume& v = c->vol[sv];
+        const BrickedGrid g = bricked_grid(v);
+        const size_t slab = (size_t)g.nbx * g.nby * kVbN, window = variant == VR_VARIANT_BASIC ? 0x3fffffffull : 0x0fffffffull;
+        const size_t lds = (size_t)(c->tf[0].res_o + 2) * 16 + ((size_t)v.nx + v.ny + v.nz + 3) * 8;
+        E.p2_ok = g.slots <= 0xFFFFFFFFull && slab < (1u << 24) && (c->p2_window ? c->p2_window / slab >= 3 : window / slab >= 4) && lds <= 160u * 1024u;
+        E.p2_lds = (unsigned)lds;
+    }
+    // 18: march_kernel with the slot tables of volume 0 in its workgroup's LDS (make_cell_lut): the shaders that sample ONE volume, the
+    // bricked copy with 32-bit slots
+    E.lut_ok = (variant == VR_VARIANT_LIGHT || variant == VR_VARIANT_BASIC || variant == VR_VARIANT_LIGHT_INSHADER) && c->layout_mode == 0 &&
+               c->vol_bricked[0] && c->vol_bdens[0];
+    if (E.lut_ok) {
+        E.lut_lds = (unsigned)(((size_t)c->vol[0].nx + c->vol[0].ny + c->vol[0].nz + 6) * 4);
+        E.lut_ok = bricked_grid(c->vol[0]).slots <= 0xFFFFFFFFull && E.lut_lds <= 32u * 1024u;
+    }
+    // exact empty-space skipping: only for the shaders whose opacity is the CT table value alone, only when a zero-opacity sample is
+    // provably the identity (finite colour table and light), and unless flavour 1 asks for the plain kernel (no rule of choose_flavour
+    // turns another flavour into 1 or 1 into another)
+    E.can_skip = (variant == VR_VARIANT_BASIC || variant == VR_VARIANT_LIGHT || variant == VR_VARIANT_THREE_FILES ||
+                  variant == VR_VARIANT_VOLUME_MASK || variant == VR_VARIANT_LIGHT_INSHADER) &&
+                 requested != 1 && c->vol_bricks[sv] && c->tf_zero_prefix[0] >= 0 && c->tf_color_finite[0];
+    for (int f = 0; f < n_frames; ++f) E.can_skip = E.can_skip && all_finite(batch_u ? batch_u[f].light_pos : c->u.light_pos, 12);
+    // the kernels index bricks with 24-bit multiplies and 32-bit byte offsets
+    E.can_skip = E.can_skip && skip_bricks(c->vol[sv].nx) * (long long)skip_bricks(c->vol[sv].ny) < (1 << 23);
+    if (variant == VR_VARIANT_THREE_FILES) E.can_skip = E.can_skip && c->tf_color_finite[1] && c->tf_opacity_finite[1];
+    if (variant == VR_VARIANT_VOLUME_MASK)  // mask and CT must share one grid so that one brick index serves both
+        E.can_skip = E.can_skip && c->vol_bricks[0] && c->vol[0].nx == c->vol[2].nx && c->vol[0].ny == c->vol[2].ny &&
+                     c->vol[0].nz == c->vol[2].nz;
+    E.whole_frame = rays_per_lane(c, rank, world, 1) >= 4.5;
+    E.chain_known = requested == 0 ? last_chain(c, scene_key(c, variant, rank, world, packed)) : 0;
+    return E;
+}
+
+// Exact empty-space skipping (E.can_skip): fills P's brick fields from c, and rebuilds what is stale of the merged mask records, the
+// distance field, the share of active bricks (active_fraction, which the kernel choice reads) and the box of the active bricks.
+int prepare_skip(vr_ctx* c, int variant, hipStream_t s, MarchParams& P)
+{
+    const int sv = variant == VR_VARIANT_VOLUME_MASK ? 2 : 0;
+    P.skip_vol = sv;
+    P.bnx = skip_bricks(c->vol[sv].nx);
+    P.bny = skip_bricks(c->vol[sv].ny);
+    P.bnz = skip_bricks(c->vol[sv].nz);
+    P.bsx = (float)c->vol[sv].nx * kBrickInv;
+    P.bsy = (float)c->vol[sv].ny * kBrickInv;
+    P.bsz = (float)c->vol[sv].nz * kBrickInv;
+    P.tf_zero_prefix = c->tf_zero_prefix[0];
+    P.bricks = c->vol_bricks[sv];
+    P.use_rgb = 0;
+    const int nb = P.bnx * P.bny * P.bnz;
+    if (variant == VR_VARIANT_VOLUME_MASK) {
+        if (c->merged_stale || !c->merged_bricks) {
+            if (c->merged_bricks) (void)hipFree(c->merged_bricks);
+            c->merged_bricks = nullptr;
+            VR_HIP(c, hipMalloc(&c->merged_bricks, (size_t)nb * sizeof(float2)));
+            hipLaunchKernelGGL(merge_bricks_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, c->vol_bricks[2],
+                               c->vol_bricks[0], c->merged_bricks, nb);
+            VR_HIP(c, hipGetLastError());
+            c->merged_stale = false;
+        }
+        P.bricks = c->merged_bricks;
+        P.use_rgb = 1;
+    }
+    // distance field over the inert bricks (Chebyshev distance to the nearest active brick), rebuilt when the
+    // records, the zero prefix or the table resolution changed since it was last built
+    if (c->dist_records != (const void*)P.bricks || c->dist_epoch != c->brick_epoch || c->dist_z != P.tf_zero_prefix ||
+        c->dist_res != c->tf[0].res_o || c->dist_rgb != P.use_rgb || !c->brick_dist) {
+        // (rare: an input changed.  Frames may be in flight on other streams and read the field: drain them first,
+        // and finish the rebuild before any other stream's launch can follow)
+        VR_HIP(c, hipDeviceSynchronize());
+        if ((size_t)nb > c->dist_cap) {
+            if (c->brick_dist) (void)hipFree(c->brick_dist);
+            c->brick_dist = nullptr;
+            c->dist_cap = 0;
+            VR_HIP(c, hipMalloc(&c->brick_dist, (size_t)nb));
+            c->dist_cap = (size_t)nb;
+        }
+        const dim3 g((unsigned)((nb + 255) / 256)), b(256);
+        hipLaunchKernelGGL(brick_active_kernel, g, b, 0, s, P.bricks, c->brick_dist, nb, P.use_rgb, P.tf_zero_prefix,
+                           c->tf[0].res_o);
+        for (int k = 1; k < kDistMax; ++k)
+            hipLaunchKernelGGL(brick_dist_pass_kernel, g, b, 0, s, c->brick_dist, P.bnx, P.bny, P.bnz, k);
+        hipLaunchKernelGGL(brick_dist_cap_kernel, g, b, 0, s, c->brick_dist, nb);
+        VR_HIP(c, hipGetLastError());
+        // share of active bricks (steers the default kernel choice)
+        unsigned* d_cnt = reinterpret_cast<unsigned*>(c->d_counters);
+        VR_HIP(c, hipMemsetAsync(d_cnt, 0, sizeof(unsigned), s));
+        hipLaunchKernelGGL(count_active_bricks_kernel, g, b, 0, s, c->brick_dist, nb, d_cnt);
+        VR_HIP(c, hipGetLastError());
+        unsigned cnt = 0;
+        VR_HIP(c, hipMemcpyAsync(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, s));
+        VR_HIP(c, hipStreamSynchronize(s));
+        c->active_fraction = nb > 0 ? (double)cnt / (double)nb : 1.0;
+        // the box of the active bricks, in uvw with one brick of margin (MarchParams::abox): brick b of axis a holds the
+        // positions with p * bs - kBrickHalf in [b, b + 1), the first and the last brick those beyond them as well
+        int* d_box = reinterpret_cast<int*>(c->d_counters);  // (6 ints: the counters' 24 bytes)
+        int box[6] = {0x7fffffff, 0x7fffffff, 0x7fffffff, -1, -1, -1};
+        VR_HIP(c, hipMemcpyAsync(d_box, box, sizeof box, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(active_brick_box_kernel, g, b, 0, s, c->brick_dist, P.bnx, P.bny, P.bnz, d_box);
+        VR_HIP(c, hipGetLastError());
+        VR_HIP(c, hipMemcpyAsync(box, d_box, sizeof box, hipMemcpyDeviceToHost, s));
+        VR_HIP(c, hipStreamSynchronize(s));
+        const double bs[3] = {(double)P.bsx, (double)P.bsy, (double)P.bsz};
+        for (int a = 0; a < 3; ++a) {
+            if (box[3 + a] < 0) {  // (no active brick: every ray misses)
+                c->abox[a] = 3.0e38f;
+                c->abox[3 + a] = -3.0e38f;
+            } else {
+                c->abox[a] = (float)(((double)box[a] - 1.0 + (double)kBrickHalf) / bs[a]);
+                c->abox[3 + a] = (float)(((double)box[3 + a] + 2.0 + (double)kBrickHalf) / bs[a]);
+            }
+        }
+        VR_HIP(c, hipStreamSynchronize(s));
+        c->dist_records = (const void*)P.bricks;
+        c->dist_epoch = c->brick_epoch;
+        c->dist_z = P.tf_zero_prefix;
+        c->dist_res = c->tf[0].res_o;
+        c->dist_rgb = P.use_rgb;
+    }
+    P.brick_dist = c->brick_dist;
+    for (int a = 0; a < 6; ++a) P.abox[a] = c->abox[a];
+    return VR_OK;
+}
+
+// The kernel form ("flavour") a launch runs: `fl` is the one asked for (vr_set_kernel_flavour, else VR_EXP_FLAVOUR), 0 = the default.
+int choose_flavour(vr_ctx* c, int fl, int variant, int n_frames, int rank, int world, bool packed, const Eligibility& E)
+{
+    const bool auto_choice = fl == 0;
+    const double rays = rays_per_lane(c, rank, world, c->frames_in_flight * n_frames);
+    const bool short_chains = E.chain_known != 0 && E.chain_known - 1 < 128;
+    if (auto_choice) {
         // Default: pick the lanes per ray from what will be on the machine.  With many rays per hardware lane the machine is
         // throughput-bound and one lane per ray does the least work; with few (a small frame, or one GPU's share of the
         // tiles) the frame waits for its longest rays, whose chains of dependent samples the depth-parallel kernel cuts to a
@@ -521,62 +711,18 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
         //    vr_hint_frames_in_flight; asking the events instead flushes the runtime's command batches and costs more than it
         //    tells) the other launches fill the machine as well, so the rays per lane count once per frame in flight (a
         //    rank's half of C3, two frames pipelined: 0.34 ms with one lane, 0.42 with two);
-        //  * how long the chains really are: the longest ray chain of an earlier launch of this shape (written to pinned
-        //    memory by the launch-order sort; read here without synchronising, 0 = not known).  Chains too short to matter --
-        //    under 128 samples, 0.2 ms (C2: 102) -- leave nothing for the depth-parallel kernels to cut (C2: 0.133 / 0.091 ms per frame
-        //    with one lane, 0.153 / 0.123 with two), unless the launch is too small to fill the machine at all.
-        const long long px = (long long)tile_count(c, rank, world) * kTile * kTile;
-        const int in_flight = c->frames_in_flight;  // the caller's hint (vr_hint_frames_in_flight)
-        const double rays_per_lane = (double)px * in_flight * n_frames / ((double)c->n_cus * 4.0 * 5.0 * 64.0);
-        unsigned chain = 0;  // longest chain + 1 of the most recent launch of this scene shape whose sort has reported
-        if (c->h_chain) {
-            const unsigned long long skey = ((unsigned long long)variant << 16) ^ ((unsigned long long)world << 8) ^ (unsigned long long)rank ^
-                                            (packed ? 1ull << 63 : 0ull) ^ ((unsigned long long)c->W << 40) ^ ((unsigned long long)c->H << 24);
-            unsigned long long best_seq = 0;
-            for (int i = 0; i < kOrderRing; ++i) {
-                const unsigned v = *(volatile unsigned*)&c->h_chain[i];
-                if (v != 0 && c->order_ring[i].scene_key == skey && c->order_ring[i].seq + 1 > best_seq) {
-                    best_seq = c->order_ring[i].seq + 1;
-                    chain = v;
-                }
-            }
-        }
-        chain_known = chain;
-        const bool short_chains = chain != 0 && chain - 1 < 128;
+        //  * how long the chains really are (E.chain_known).  Chains too short to matter -- under 128 samples, 0.2 ms (C2: 102) --
+        //    leave nothing for the depth-parallel kernels to cut (C2: 0.133 / 0.091 ms per frame with one lane, 0.153 / 0.123 with
+        //    two), unless the launch is too small to fill the machine at all.
         // (two lanes per ray from 2 rays per lane on, four below: re-measured on the bricked layout -- a rank's quarter of C3
         // (1.6 rays per lane), one frame at a time: 0.274 ms with two lanes, 0.203 with four; a rank's half (3.2): 0.362 / 0.377;
         // a quarter with two launches in flight counts 3.2 and keeps two lanes: 0.190 / 0.217 per frame)
-        fl = (rays_per_lane >= 4.5 || (short_chains && rays_per_lane >= 1.2)) ? 6 : (rays_per_lane >= 2.0 ? 11 : 10);
+        fl = (rays >= 4.5 || (short_chains && rays >= 1.2)) ? 6 : (rays >= 2.0 ? 11 : 10);
     }
-    // persistent wavefronts (12, 13; vr_pw.h) exist for launches of one frame
+    // what a form runs as where it cannot run: persistent wavefronts (12, 13; vr_pw.h) exist for launches of one frame
     if ((fl == 12 || fl == 13) && n_frames != 1) fl = 6;
-    // two steps ahead (16, 17; march_p2_kernel, vr_p2.h): lit / unlit shader and the three-volume composite (with its brick records:
-    // checked once can_skip is known); TF slot 0 (one resolution for both tables) and the three axis tables in LDS; the bricked copy
-    // with 32-bit slots, rows and slabs of bricks below 2^24 slots; a volume of 4 GiB or more through a moving window of at least
-    // four z-slabs of bricks.  Launches of several frames and launches in flight included.  Else 13 / 12 (one frame) or 6.
-    const int p2_vol = variant == VR_VARIANT_VOLUME_MASK ? 2 : 0;
-    bool p2_ok = (variant == VR_VARIANT_LIGHT || variant == VR_VARIANT_BASIC || variant == VR_VARIANT_VOLUME_MASK) &&
-                 c->tf[0].res_o == c->tf[0].res_c && c->tf[0].res_o + 2 <= 8192 && c->layout_mode == 0 && c->vol_bricked[p2_vol] && c->vol_bdens[p2_vol];
-    unsigned p2_lds = 0;
-    if (p2_ok) {
-        const size_t nbx = ((unsigned)c->vol[p2_vol].nx + kVbM) >> kVbS, nby = ((unsigned)c->vol[p2_vol].ny + kVbM) >> kVbS, nbz = ((unsigned)c->vol[p2_vol].nz + kVbM) >> kVbS;
-        const size_t slab = nbx * nby * kVbN, window = variant == VR_VARIANT_BASIC ? 0x3fffffffull : 0x0fffffffull;
-        const size_t lds = (size_t)(c->tf[0].res_o + 2) * 16 + ((size_t)c->vol[p2_vol].nx + c->vol[p2_vol].ny + c->vol[p2_vol].nz + 3) * 8;
-        p2_ok = slab * nbz <= 0xFFFFFFFFull && slab < (1u << 24) && (c->p2_window ? c->p2_window / slab >= 3 : window / slab >= 4) && lds <= 160u * 1024u;
-        p2_lds = (unsigned)lds;
-    }
-    if ((fl == 16 || fl == 17) && !p2_ok) fl = n_frames != 1 ? 6 : (fl == 16 ? 13 : 12);
-    // 18: march_kernel with the slot tables of volume 0 in its workgroup's LDS (make_cell_lut): the shaders that sample ONE volume, the
-    // bricked copy with 32-bit slots (bricks of rows and slabs below 2^24 slots as above); else 6
-    bool lut_ok = (variant == VR_VARIANT_LIGHT || variant == VR_VARIANT_BASIC || variant == VR_VARIANT_LIGHT_INSHADER) && c->layout_mode == 0 &&
-                  c->vol_bricked[0] && c->vol_bdens[0];
-    unsigned lut_lds = 0;
-    if (lut_ok) {
-        const size_t nbx = ((unsigned)c->vol[0].nx + kVbM) >> kVbS, nby = ((unsigned)c->vol[0].ny + kVbM) >> kVbS, nbz = ((unsigned)c->vol[0].nz + kVbM) >> kVbS;
-        lut_lds = (unsigned)(((size_t)c->vol[0].nx + c->vol[0].ny + c->vol[0].nz + 6) * 4);
-        lut_ok = nbx * nby * nbz * kVbN <= 0xFFFFFFFFull && lut_lds <= 32u * 1024u;
-    }
-    if (fl == 18 && !lut_ok) fl = 6;
+    if ((fl == 16 || fl == 17) && !E.p2_ok) fl = n_frames != 1 ? 6 : (fl == 16 ? 13 : 12);
+    if (fl == 18 && !E.lut_ok) fl = 6;
     if (fl == 16 && variant == VR_VARIANT_VOLUME_MASK) fl = 17;  // (the composite's form is the skipping one: its mask records)
     // LDS tiles (15; vr_lt.h): the lit shader, launches of one frame
     if (fl == 15 && (n_frames != 1 || variant != VR_VARIANT_LIGHT)) fl = 6;
@@ -584,107 +730,9 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
     if (variant == VR_VARIANT_ILLUSTRATIVE && (fl == 7 || fl == 8 || fl == 10 || fl == 11)) fl = 6;
     // the in-shader gradient variant (seven density fetches per sample) exists as the one-lane kernel only
     if (variant == VR_VARIANT_LIGHT_INSHADER && fl != 1 && fl != 12 && fl != 13 && fl != 18) fl = 6;
-    c->last_flavour = fl;
-    bool can_skip = skip_variant && fl != 1 && c->vol_bricks[sv] && c->tf_zero_prefix[0] >= 0 &&
-                    c->tf_color_finite[0];
-    for (int f = 0; f < n_frames; ++f) can_skip = can_skip && all_finite(batch_u ? batch_u[f].light_pos : c->u.light_pos, 12);
-    // the kernels index bricks with 24-bit multiplies and 32-bit byte offsets
-    can_skip = can_skip && ((c->vol[sv].nx + kBrickCells - 1) >> kBrickShift) * (long long)((c->vol[sv].ny + kBrickCells - 1) >> kBrickShift) < (1 << 23);
-    if (variant == VR_VARIANT_THREE_FILES) can_skip = can_skip && c->tf_color_finite[1] && c->tf_opacity_finite[1];
-    if (variant == VR_VARIANT_VOLUME_MASK)  // mask and CT must share one grid so that one brick index serves both
-        can_skip = can_skip && c->vol_bricks[0] && c->vol[0].nx == c->vol[2].nx && c->vol[0].ny == c->vol[2].ny &&
-                   c->vol[0].nz == c->vol[2].nz;
-    if ((fl == 16 || fl == 17) && variant == VR_VARIANT_VOLUME_MASK && !can_skip) {  // (no brick records: no on-demand mask fetch)
+    if ((fl == 16 || fl == 17) && variant == VR_VARIANT_VOLUME_MASK && !E.can_skip)  // (no brick records: no on-demand mask fetch)
         fl = n_frames != 1 ? 6 : 12;
-        c->last_flavour = fl;
-    }
-    if (can_skip) {
-        P.skip_vol = sv;
-        P.bnx = (c->vol[sv].nx + kBrickCells - 1) >> kBrickShift;
-        P.bny = (c->vol[sv].ny + kBrickCells - 1) >> kBrickShift;
-        P.bnz = (c->vol[sv].nz + kBrickCells - 1) >> kBrickShift;
-        P.bsx = (float)c->vol[sv].nx * kBrickInv;
-        P.bsy = (float)c->vol[sv].ny * kBrickInv;
-        P.bsz = (float)c->vol[sv].nz * kBrickInv;
-        P.tf_zero_prefix = c->tf_zero_prefix[0];
-        P.bricks = c->vol_bricks[sv];
-        P.use_rgb = 0;
-        if (variant == VR_VARIANT_VOLUME_MASK) {
-            const int nb = P.bnx * P.bny * P.bnz;
-            if (c->merged_stale || !c->merged_bricks) {
-                if (c->merged_bricks) (void)hipFree(c->merged_bricks);
-                c->merged_bricks = nullptr;
-                VR_HIP(c, hipMalloc(&c->merged_bricks, (size_t)nb * sizeof(float2)));
-                hipLaunchKernelGGL(merge_bricks_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, c->vol_bricks[2],
-                                   c->vol_bricks[0], c->merged_bricks, nb);
-                VR_HIP(c, hipGetLastError());
-                c->merged_stale = false;
-            }
-            P.bricks = c->merged_bricks;
-            P.use_rgb = 1;
-        }
-        // distance field over the inert bricks (Chebyshev distance to the nearest active brick), rebuilt when the
-        // records, the zero prefix or the table resolution changed since it was last built
-        const int nb = P.bnx * P.bny * P.bnz;
-        if (c->dist_records != (const void*)P.bricks || c->dist_epoch != c->brick_epoch || c->dist_z != P.tf_zero_prefix ||
-            c->dist_res != c->tf[0].res_o || c->dist_rgb != P.use_rgb || !c->brick_dist) {
-            // (rare: an input changed.  Frames may be in flight on other streams and read the field: drain them first,
-            // and finish the rebuild before any other stream's launch can follow)
-            VR_HIP(c, hipDeviceSynchronize());
-            if ((size_t)nb > c->dist_cap) {
-                if (c->brick_dist) (void)hipFree(c->brick_dist);
-                c->brick_dist = nullptr;
-                c->dist_cap = 0;
-                VR_HIP(c, hipMalloc(&c->brick_dist, (size_t)nb));
-                c->dist_cap = (size_t)nb;
-            }
-            const dim3 g((unsigned)((nb + 255) / 256)), b(256);
-            hipLaunchKernelGGL(brick_active_kernel, g, b, 0, s, P.bricks, c->brick_dist, nb, P.use_rgb, P.tf_zero_prefix,
-                               c->tf[0].res_o);
-            for (int k = 1; k < kDistMax; ++k)
-                hipLaunchKernelGGL(brick_dist_pass_kernel, g, b, 0, s, c->brick_dist, P.bnx, P.bny, P.bnz, k);
-            hipLaunchKernelGGL(brick_dist_cap_kernel, g, b, 0, s, c->brick_dist, nb);
-            VR_HIP(c, hipGetLastError());
-            {   // share of active bricks (steers the default kernel choice below)
-                unsigned* d_cnt = reinterpret_cast<unsigned*>(c->d_counters);
-                VR_HIP(c, hipMemsetAsync(d_cnt, 0, sizeof(unsigned), s));
-                hipLaunchKernelGGL(count_active_bricks_kernel, g, b, 0, s, c->brick_dist, nb, d_cnt);
-                VR_HIP(c, hipGetLastError());
-                unsigned cnt = 0;
-                VR_HIP(c, hipMemcpyAsync(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, s));
-                VR_HIP(c, hipStreamSynchronize(s));
-                c->active_fraction = nb > 0 ? (double)cnt / (double)nb : 1.0;
-            }
-            {   // the box of the active bricks, in uvw with one brick of margin (MarchParams::abox): brick b of axis a holds the
-                // positions with p * bs - kBrickHalf in [b, b + 1), the first and the last brick those beyond them as well
-                int* d_box = reinterpret_cast<int*>(c->d_counters);  // (6 ints: the counters' 24 bytes)
-                int box[6] = {0x7fffffff, 0x7fffffff, 0x7fffffff, -1, -1, -1};
-                VR_HIP(c, hipMemcpyAsync(d_box, box, sizeof box, hipMemcpyHostToDevice, s));
-                hipLaunchKernelGGL(active_brick_box_kernel, g, b, 0, s, c->brick_dist, P.bnx, P.bny, P.bnz, d_box);
-                VR_HIP(c, hipGetLastError());
-                VR_HIP(c, hipMemcpyAsync(box, d_box, sizeof box, hipMemcpyDeviceToHost, s));
-                VR_HIP(c, hipStreamSynchronize(s));
-                const double bs[3] = {(double)P.bsx, (double)P.bsy, (double)P.bsz};
-                for (int a = 0; a < 3; ++a) {
-                    if (box[3 + a] < 0) {  // (no active brick: every ray misses)
-                        c->abox[a] = 3.0e38f;
-                        c->abox[3 + a] = -3.0e38f;
-                    } else {
-                        c->abox[a] = (float)(((double)box[a] - 1.0 + (double)kBrickHalf) / bs[a]);
-                        c->abox[3 + a] = (float)(((double)box[3 + a] + 2.0 + (double)kBrickHalf) / bs[a]);
-                    }
-                }
-            }
-            VR_HIP(c, hipStreamSynchronize(s));
-            c->dist_records = (const void*)P.bricks;
-            c->dist_epoch = c->brick_epoch;
-            c->dist_z = P.tf_zero_prefix;
-            c->dist_res = c->tf[0].res_o;
-            c->dist_rgb = P.use_rgb;
-        }
-        P.brick_dist = c->brick_dist;
-        for (int a = 0; a < 6; ++a) P.abox[a] = c->abox[a];
-    }
+    if (!auto_choice) return fl;
 
     // Default choice, second part -- THE PRIOR: what runs before anything has been measured.  Whole frames of the lit / unlit shader
     // and of the composite, one launch at a time: the kernel with the corner loads two steps ahead (vr_p2.h) -- 17, or 16 where next to
@@ -692,47 +740,216 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
     // launch of this shape says its chains are short (C2, longest chain 102: a packet is too short for the pipeline's fill and a
     // dequeue, 0.111 -> 0.161).  The same with launches in flight and several frames per launch since the approach loop (C3 0.417 / 0.382
     // ms per frame against march_kernel's 0.464 / 0.445; C5 level); shares of a frame: the first part's choice.
-    const bool p2_variant = variant == VR_VARIANT_LIGHT || variant == VR_VARIANT_BASIC || (variant == VR_VARIANT_VOLUME_MASK && can_skip);
-    const long long px_all = (long long)tile_count(c, rank, world) * kTile * kTile;
-    const bool whole_frame = (double)px_all / ((double)c->n_cus * 4.0 * 5.0 * 64.0) >= 4.5;
-    const bool nothing_to_skip = !can_skip || c->active_fraction >= 0.9;
-    const bool auto_choice = c->flavour == 0 && c->default_flavour == 0;
-    if (auto_choice && fl == 6 && whole_frame && p2_ok && p2_variant) {
-        const bool short_chains = chain_known != 0 && chain_known - 1 < 128;
+    const bool p2_variant = variant == VR_VARIANT_LIGHT || variant == VR_VARIANT_BASIC || (variant == VR_VARIANT_VOLUME_MASK && E.can_skip);
+    const bool nothing_to_skip = !E.can_skip || c->active_fraction >= 0.9;  // (prepare_skip has measured the share of active bricks)
+    if (fl == 6 && E.whole_frame && E.p2_ok && p2_variant) {
         if (nothing_to_skip && variant != VR_VARIANT_VOLUME_MASK) fl = 16;
         else if (!short_chains) fl = 17;
     }
+    if (!c->tune_mode) return fl;
     // ... and THE MEASURED CHOICE (tune_pick): the eligible forms take turns on the caller's own frames, the fastest by the launches'
     // own records stays.  Candidates: the prior; the two-steps-ahead kernel; the one-lane kernel; the depth-parallel kernel (launches
     // that leave the machine part empty) or the persistent kernel without the pipeline (the longest chains).
-    if (auto_choice && c->tune_mode) {
-        int cand[6], n = 0;
-        auto add = [&](int f) {
-            for (int i = 0; i < n; ++i)
-                if (cand[i] == f) return;
-            if (n < 6) cand[n++] = f;
-        };
-        add(fl);
-        if (p2_ok && p2_variant) add((nothing_to_skip && variant != VR_VARIANT_VOLUME_MASK) || !can_skip ? 16 : 17);
-        add(6);
-        if (lut_ok && lut_lds <= 8u * 1024u) add(18);  // (the one-lane kernel with its slot arithmetic from LDS tables; larger tables cost it wavefronts per CU: C5 4.2 vs 3.4 ms)
-        const bool dp_variant = variant != VR_VARIANT_ILLUSTRATIVE && variant != VR_VARIANT_LIGHT_INSHADER;
-        if (!whole_frame && dp_variant) add((double)px_all * c->frames_in_flight * n_frames / ((double)c->n_cus * 4.0 * 5.0 * 64.0) >= 2.0 ? 11 : 10);
-        else if (n_frames == 1 && (variant == VR_VARIANT_LIGHT || variant == VR_VARIANT_BASIC)) add(12);
-        const unsigned long long shape = 0x9E3779B97F4A7C15ull * (((unsigned long long)variant << 56) ^ ((unsigned long long)world << 48) ^ ((unsigned long long)rank << 40) ^
-                                                                 ((unsigned long long)c->W << 24) ^ ((unsigned long long)c->H << 8) ^ (packed ? 0x80ull : 0ull) ^
-                                                                 ((unsigned long long)n_frames << 4) ^ (unsigned long long)c->frames_in_flight) | 1ull;
-        const unsigned long long key = (shape ^ (c->brick_epoch * 0xD6E8FEB86659FD93ull) ^ (c->tf_epoch << 20) ^ ((unsigned long long)c->arith << 1) ^
-                                        ((unsigned long long)c->layout_mode << 2)) | 1ull;
-        const bool measurable = c->h_span && c->h_end && !c->event_timing;
-        fl = tune_pick(c, key, shape, cand, n, chain_known, measurable);
-    }
-    c->last_flavour = fl;
+    int cand[6], n = 0;
+    auto add = [&](int f) {
+        for (int i = 0; i < n; ++i)
+            if (cand[i] == f) return;
+        if (n < 6) cand[n++] = f;
+    };
+    add(fl);
+    if (E.p2_ok && p2_variant) add((nothing_to_skip && variant != VR_VARIANT_VOLUME_MASK) || !E.can_skip ? 16 : 17);
+    add(6);
+    if (E.lut_ok && E.lut_lds <= 8u * 1024u) add(18);  // (the one-lane kernel with its slot arithmetic from LDS tables; larger tables cost it wavefronts per CU: C5 4.2 vs 3.4 ms)
+    const bool dp_variant = variant != VR_VARIANT_ILLUSTRATIVE && variant != VR_VARIANT_LIGHT_INSHADER;
+    if (!E.whole_frame && dp_variant) add(rays >= 2.0 ? 11 : 10);
+    else if (n_frames == 1 && (variant == VR_VARIANT_LIGHT || variant == VR_VARIANT_BASIC)) add(12);
+    const unsigned long long shape = 0x9E3779B97F4A7C15ull * (((unsigned long long)variant << 56) ^ ((unsigned long long)world << 48) ^ ((unsigned long long)rank << 40) ^
+                                                             ((unsigned long long)c->W << 24) ^ ((unsigned long long)c->H << 8) ^ (packed ? 0x80ull : 0ull) ^
+                                                             ((unsigned long long)n_frames << 4) ^ (unsigned long long)c->frames_in_flight) | 1ull;
+    const unsigned long long key = (shape ^ (c->brick_epoch * 0xD6E8FEB86659FD93ull) ^ (c->tf_epoch << 20) ^ ((unsigned long long)c->arith << 1) ^
+                                    ((unsigned long long)c->layout_mode << 2)) | 1ull;
+    const bool measurable = c->h_span && c->h_end && !c->event_timing;
+    return tune_pick(c, key, shape, cand, n, E.chain_known, measurable);
+}
 
-    if (c->layout_mode == 0) use_bricked();
-    if (fl == 18 && P.vol[0].bricked) P.vol[0].lut = 1;  // (march_kernel fills the tables; every fetch of volume 0 goes through them)
+// What each flavour launches -- the one place a flavour's number is decoded.
+struct KernelForm {
+    LaunchDesc::Family family;
+    int lanes;            // kDp: lanes per ray (vr_dp.h): 64 / 32 workgroups per tile
+    bool pipe;            // kDp / kPw: the next round's / step's corner loads software-pipelined
+    bool p2_skip;         // kP2: the skipping form
+    bool lut;             // kPlain: the slot tables of volume 0 in LDS
+    unsigned pw_threads;  // kPw / kP2: threads per workgroup
+};
+
+KernelForm kernel_form(int fl, int variant)
+{
+    // (march_p2_kernel: two corner buffers, 3 wavefronts per SIMD at most; with every ray sampling all the time two per SIMD are faster
+    // -- the corner data in flight is many times the L1 either way: noisy air 2.13 -> 2.04 ms.  The unlit shader's two buffers are 4-byte
+    // densities, 101 VGPRs: 4 wavefronts per SIMD -- C2 one frame at a time 0.121 -> 0.113 ms, thin table 0.255 -> 0.239, four frames per
+    // launch 0.070 -> 0.061: tools/experiments/s2h.sh.  Launches in flight: the same shape.  Two workgroups of 6 wavefronts do not share
+    // a CU -- the second one's wavefronts would have to go 1-1-2-2 over the SIMDs where the dispatcher deals 2-2-1-1: measured 0.75 ms
+    // per C3 frame, what one such workgroup per CU takes -- and two of 4 run at 8 wavefronts per CU: 0.63 against 0.54; three of 4, the
+    // same 12 wavefronts per CU, take 0.79 ms one frame at a time and 0.62 in flight against 0.55 / 0.51: profiles/r04_p2_launch_shapes.txt)
+    using D = LaunchDesc;
+    switch (fl) {
+    case 7: return {D::kDp, 4, false, false, false, 0u};
+    case 8: return {D::kDp, 2, false, false, false, 0u};
+    case 10: return {D::kDp, 4, true, false, false, 0u};
+    case 11: return {D::kDp, 2, true, false, false, 0u};
+    case 12: return {D::kPw, 0, false, false, false, 1024u};
+    case 13: return {D::kPw, 0, true, false, false, 1024u};
+    case 15: return {D::kLt, 0, false, false, false, 0u};
+    case 16: return {D::kP2, 0, false, false, false, 512u};
+    case 17: return {D::kP2, 0, false, true, false, variant == VR_VARIANT_BASIC ? 1024u : 768u};
+    case 18: return {D::kPlain, 0, false, false, true, 0u};
+    default: return {D::kPlain, 0, false, false, false, 0u};  // 1, 6
+    }
+}
+
+// The record slot of the next launch, *cb = order_seq % kInFlight.  (Record slot and order slot both derive from order_seq, which
+// advances only once a launch has really been enqueued: a failed enqueue cannot shift one against the other.)  The slot's previous
+// launch (kInFlight launches ago, possibly on another stream) must have finished before its record buffer is written again or
+// re-allocated: this is what bounds the launches in flight to kInFlight.  *slot_sort: the sort that read those records, which the
+// launch's stream has yet to wait for (wait_for_order); waited for at once only when the buffer is re-allocated (the memset behind
+// the allocation writes it).
+int take_record_slot(vr_ctx* c, hipStream_t s, size_t n_records, int* cb, const vr_ctx::OrderSlot** slot_sort)
+{
+    const int k = (int)(c->order_seq % (unsigned long long)kInFlight);
+    *cb = k;
+    if (c->slot_used[k]) VR_HIP(c, hipEventSynchronize(c->slot_done[k]));
+    *slot_sort = nullptr;
+    if (c->order_seq >= (unsigned long long)kInFlight) {
+        const vr_ctx::OrderSlot& po = c->order_ring[(c->order_seq - kInFlight) % kOrderRing];
+        if (po.valid && po.seq + kInFlight == c->order_seq) *slot_sort = &po;
+    }
+    if (n_records > c->block_counts_cap[k]) {
+        if (*slot_sort) VR_HIP(c, hipStreamWaitEvent(s, (*slot_sort)->sorted, 0));
+        *slot_sort = nullptr;
+        if (c->d_block_counts[k]) (void)hipFree(c->d_block_counts[k]);
+        c->d_block_counts[k] = nullptr;
+        c->block_counts_cap[k] = 0;
+        VR_HIP(c, hipMalloc(&c->d_block_counts[k], n_records * kBlockRecord * sizeof(unsigned long long)));
+        VR_HIP(c, hipMemsetAsync(c->d_block_counts[k], 0, n_records * kBlockRecord * sizeof(unsigned long long), s));
+        c->block_counts_cap[k] = n_records;
+    }
+    return VR_OK;
+}
+
+// The launch order an ordered launch takes (*order; nullptr = index order) and the one wait for a sort it implies.  The order: the most
+// recent sort of a launch of the same shape (okey) that is three or four launches old (two or three more than the frames the caller
+// says it keeps in flight, if that is more: with short frames -- C2, 0.08 ms -- the sort of the launch that finished one frame time ago
+// is itself only just finishing) -- a younger one may still be waiting for its launch to finish (the sorts run on a side stream behind
+// their launches; waiting for one would put a bubble into this stream, and with four frames in flight it would chain this launch behind
+// the one three before it), an older one's buffer may be recycled under this launch; ordered behind it by its event (long complete by
+// then).  A stream's wait for another stream's event costs the stream 5 us per launch even when the event completed long ago
+// (tools/ubench/stream_gap.hip), so the wait for `slot_sort` is left out when the order's wait covers it: every sort runs on the one
+// order stream, in the order of the launches.
+int wait_for_order(vr_ctx* c, hipStream_t s, bool ordered, unsigned long long okey, const vr_ctx::OrderSlot* slot_sort, const unsigned** order)
+{
+    *order = nullptr;
+    if (ordered) {
+        const vr_ctx::OrderSlot* best = nullptr;
+        const unsigned long long age = (unsigned long long)(c->frames_in_flight + 2 > 3 ? c->frames_in_flight + 2 : 3);
+        for (const auto& o : c->order_ring)
+            if (o.valid && o.key == okey && o.seq + age + 1 >= c->order_seq && o.seq + age <= c->order_seq && (!best || o.seq > best->seq))
+                best = &o;
+        if (best) {
+            VR_HIP(c, hipStreamWaitEvent(s, best->sorted, 0));
+            if (slot_sort && best->seq >= slot_sort->seq) slot_sort = nullptr;  // (covered: the order stream runs its sorts in order)
+            *order = best->buf;
+        }
+    }
+    if (slot_sort) VR_HIP(c, hipStreamWaitEvent(s, slot_sort->sorted, 0));
+    return VR_OK;
+}
+
+// Behind the launch in record slot cb: the slot's event and, for an ordered launch, the sort of its n_blocks records on the order stream
+// into order slot order_seq % kOrderRing -- the launch order of later launches; the longest chain (h_chain), and unless the launch is
+// timed with events its span and end (h_span / h_end, ring slot `ring`); the persistent kernels' queue heads cleared.  Then the next
+// launch takes the next slots.
+int enqueue_sort(vr_ctx* c, hipStream_t s, int cb, bool ordered, unsigned long long okey, unsigned long long skey, unsigned n_blocks, int ring,
+                 bool time_with_events, bool pw)
+{
+    vr_ctx::OrderSlot& o = c->order_ring[c->order_seq % kOrderRing];
+    if (ordered) {
+        o.valid = false;
+        if (n_blocks > o.cap) {
+            if (o.buf) (void)hipFree(o.buf);
+            o.buf = nullptr;
+            o.cap = 0;
+            VR_HIP(c, hipMalloc(&o.buf, (size_t)n_blocks * sizeof(unsigned)));
+            o.cap = n_blocks;
+        }
+        o.stream = s;
+        o.key = okey;
+        o.scene_key = skey;
+        o.seq = c->order_seq;
+        if (c->h_chain) c->h_chain[c->order_seq % kOrderRing] = 0;  // not known until this launch's sort has run
+    }
+    VR_HIP(c, hipEventRecord(c->slot_done[cb], s));
+    c->slot_used[cb] = true;
+    if (ordered) {
+        VR_HIP(c, hipStreamWaitEvent(c->order_stream, c->slot_done[cb], 0));
+        hipLaunchKernelGGL(order_blocks_kernel, dim3(1), dim3(1024), 0, c->order_stream, c->d_block_counts[cb], (int)n_blocks, o.buf,
+                           c->h_chain ? c->h_chain + (c->order_seq % kOrderRing) : (unsigned*)nullptr,
+                           (c->h_span && !time_with_events) ? c->h_span + ring : (unsigned long long*)nullptr,
+                           pw ? c->d_pw_heads + (size_t)cb * 8 * 64 : (unsigned*)nullptr,
+                           (c->h_span && c->h_end && !time_with_events) ? c->h_end + ring : (unsigned long long*)nullptr);
+        VR_HIP(c, hipGetLastError());
+        if (pw) c->pw_heads_dirty[cb] = false;  // (the sort zeroes the heads behind the launch: the slot's next user finds them clean)
+        VR_HIP(c, hipEventRecord(o.sorted, c->order_stream));
+        o.valid = true;
+    }
+    ++c->order_seq;
+    return VR_OK;
+}
+
+// The launch's frames (frame f: every n_frames-th group of 8 workgroups, MarchBatch), each with its own uniforms, output and records;
+// the launch order (a heuristic of the shape) is shared.
+const MarchBatch& fill_batch(MarchParams& P, int n_frames, const vr_uniforms* batch_u, void* const* batch_out, unsigned blocks_per_frame)
+{
+    static thread_local MarchBatch B;
+    P.batch_n = (unsigned)n_frames;
+    B.frame[0] = P;
+    for (int f = 1; f < n_frames; ++f) {
+        MarchParams& Pf = B.frame[f];
+        Pf = P;
+        fill_frame_params(Pf, batch_u[f]);
+        Pf.out = (float4*)batch_out[f];
+        Pf.block_counts = P.block_counts + (size_t)f * blocks_per_frame * kBlockRecord;
+    }
+    B.n_frames = (unsigned)n_frames;
+    return B;
+}
+
+// Enqueue one launch on `s`: ONE frame with the context's uniforms into `out` (nullptr -> ctx-owned buffer), or, with
+// batch_u / batch_out, n_frames (2 .. kBatchMax) frames of the same scene, each with its own uniforms and output buffer.
+int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, float4* out, hipStream_t s, bool frame_events,
+                   int n_frames = 1, const vr_uniforms* batch_u = nullptr, void* const* batch_out = nullptr)
+{
+    int nvol;
+    bool off32;
+    if (const int rc = check_render_args(c, variant, rank, world, n_frames, batch_u, batch_out, &nvol, &off32)) return rc;
+    if (batch_u) out = (float4*)batch_out[0];
+    VR_HIP(c, hipSetDevice(c->device));
+    (void)hipGetLastError();  // a stale error of somebody else's call must not be reported as a failed launch below
+
+    MarchParams P;
+    fill_launch_params(c, P, batch_u ? batch_u[0] : c->u, rank, world, packed);
+    // the kernel choice: what can run, the skipping state (the prior reads its share of active bricks), the flavour
+    const int requested = c->flavour == 0 ? c->default_flavour : c->flavour;
+    const Eligibility E = eligibility(c, requested, variant, n_frames, rank, world, packed, batch_u);
+    if (E.can_skip)
+        if (const int rc = prepare_skip(c, variant, s, P)) return rc;
+    const int fl = choose_flavour(c, requested, variant, n_frames, rank, world, packed, E);
+    c->last_flavour = fl;
+    const KernelForm form = kernel_form(fl, variant);
+
+    if (c->layout_mode == 0) use_bricked_copies(c, P);
+    if (form.lut && P.vol[0].bricked) P.vol[0].lut = 1;  // (march_kernel fills the tables; every fetch of volume 0 goes through them)
     for (int i = 0; i < nvol; ++i)  // (a bricked copy is padded to whole bricks: a volume just below 4 GiB may cross the line)
-        if (P.vol[i].bricked && (size_t)P.vol[i].brick_slab * (((unsigned)P.vol[i].nz + kVbM) >> kVbS) * 16 > 0xFFFFFFFFull) off32 = false;
+        if (P.vol[i].bricked && bricked_grid(P.vol[i]).slots * 16 > 0xFFFFFFFFull) off32 = false;
 
     if (packed && !out) {
         size_t need = (size_t)P.n_tiles * kTile * kTile;
@@ -752,195 +969,68 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
 
     if (frame_events) VR_HIP(c, hipEventRecord(c->tm.ev_begin, s));
     if (P.n_blocks > 0) {
-        const int dp = (fl == 7 || fl == 10) ? 4 : ((fl == 8 || fl == 11) ? 2 : 0);  // lanes per ray (vr_dp.h): 64 / 32 workgroups per tile
-        const bool dp_pipe = fl == 10 || fl == 11;  // ... with the next round's corner loads software-pipelined
-        // one wavefront per workgroup (launch order at wavefront granularity) -- except for the depth-parallel kernels on
-        // large launches, where 4x the workgroups cost more at dispatch than the finer order gains (C2: 32 768 workgroups of
-        // a 0.12 ms frame)
-        const bool pw = fl == 12 || fl == 13 || fl == 16 || fl == 17;
-        const int wpb = dp && P.n_tiles * (dp == 4 ? 256 : 128) > 16384 ? 4 : 1;
-        dim3 block((unsigned)(64 * wpb));
-        dim3 grid((unsigned)(dp ? P.n_tiles * (dp == 4 ? 256 : 128) / wpb : (P.n_tiles + 7) / 8 * 8 * (64 / wpb)));  // see map_pixel / map_pixel_dp
+        // the LOGICAL blocks (records, launch order): one wavefront per workgroup (launch order at wavefront granularity) -- except
+        // for the depth-parallel kernels on large launches, where 4x the workgroups cost more at dispatch than the finer order gains
+        // (C2: 32 768 workgroups of a 0.12 ms frame).  See map_pixel / map_pixel_dp.
+        const int dp = form.family == LaunchDesc::kDp ? form.lanes : 0, wpb = dp && P.n_tiles * dp * 64 > 16384 ? 4 : 1;
+        const dim3 block((unsigned)(64 * wpb));
+        const dim3 grid((unsigned)(dp ? P.n_tiles * dp * 64 / wpb : (P.n_tiles + 7) / 8 * 8 * (64 / wpb)));
         if (n_frames > 1 && grid.x % 8u != 0) return fail(c, VR_ERR_INVALID_ARG, "vr_render: launch shape cannot carry several frames");
-        // (record slot and order slot are both derived from order_seq, which advances only once a launch has really been
-        // enqueued: a failed enqueue cannot shift one against the other)
-        const int cb = (int)(c->order_seq % (unsigned long long)kInFlight);
-        // the slot's previous launch (kInFlight launches ago, possibly on another stream) must have finished before its
-        // record buffer is written again or re-allocated: this is what bounds the launches in flight to kInFlight
-        if (c->slot_used[cb]) VR_HIP(c, hipEventSynchronize(c->slot_done[cb]));
-        // A stream's wait for another stream's event costs the stream 5 us per launch even when the event completed long ago
-        // (tools/ubench/stream_gap.hip): the two waits below are 10 of the 17 us between two march kernels of a one-at-a-time loop.
-        // Waiting on the HOST instead (VR_EXP_HOST_ORDER_WAIT=1, callers with vr_hint_frames_in_flight <= 1) buys them back -- C3 0.4685 ->
-        // 0.461 ms per frame, C2 0.113 -> 0.106, C1 0.042 -> 0.035; with the ONE wait a launch has left (below) 0.467 -> 0.461 -- but
-        // leaves the host two or three launches ahead of the device instead of eight, and a host thread that wakes up a few
-        // milliseconds late then idles the device (two of sixteen legs on a shared box: C1 0.040 -> 0.37 ms, C4 0.51 -> 0.64); taking
-        // the complete order of eight launches ago keeps the queue deep and loses more to the stale order than the waits cost (+17 us
-        // of span per C3 frame).  tools/experiments/s2o.sh, s2p.sh.  Off by default.
-        const bool host_wait = c->host_order_wait != 0 && c->frames_in_flight <= 1;
-        // ... and the sort that read those records.  Every sort runs on the one order stream, in the order of the launches: when this
-        // launch waits for a YOUNGER sort anyway -- the one whose launch order it takes, below -- that wait covers this one, and a wait
-        // for another stream's event less is 5 us less between two march kernels.  Waited for at once only when the record buffer is
-        // re-allocated (the memset behind the allocation writes it).
-        const vr_ctx::OrderSlot* slot_sort = nullptr;
-        if (c->order_seq >= (unsigned long long)kInFlight) {
-            const vr_ctx::OrderSlot& po = c->order_ring[(c->order_seq - kInFlight) % kOrderRing];
-            if (po.valid && po.seq + kInFlight == c->order_seq) slot_sort = &po;
-        }
-        auto wait_slot_sort = [&]() -> hipError_t {
-            if (!slot_sort) return hipSuccess;
-            const hipError_t e = host_wait ? hipEventSynchronize(slot_sort->sorted) : hipStreamWaitEvent(s, slot_sort->sorted, 0);
-            slot_sort = nullptr;
-            return e;
-        };
-        // every frame of the launch has its own records
-        const size_t n_records = (size_t)grid.x * (size_t)n_frames;
-        if (n_records > c->block_counts_cap[cb]) {
-            VR_HIP(c, wait_slot_sort());
-            if (c->d_block_counts[cb]) (void)hipFree(c->d_block_counts[cb]);
-            c->d_block_counts[cb] = nullptr;
-            c->block_counts_cap[cb] = 0;
-            VR_HIP(c, hipMalloc(&c->d_block_counts[cb], n_records * kBlockRecord * sizeof(unsigned long long)));
-            VR_HIP(c, hipMemsetAsync(c->d_block_counts[cb], 0, n_records * kBlockRecord * sizeof(unsigned long long), s));
-            c->block_counts_cap[cb] = n_records;
-        }
+        const bool pw = form.family == LaunchDesc::kPw || form.family == LaunchDesc::kP2;
+        // the ring slots: record buffer, then the launch order and the sort waits (a launch order is kept per launch shape -- not per
+        // flavour: the kernels that march one packet per wavefront -- 6, 12, 13, 16, 17 -- share the logical blocks, so an order sorted
+        // behind one of them serves the others, and the measured choice tries them in turn on a live scene)
+        int cb;
+        const vr_ctx::OrderSlot* slot_sort;
+        if (const int rc = take_record_slot(c, s, (size_t)grid.x * (size_t)n_frames, &cb, &slot_sort)) return rc;
         P.block_counts = c->d_block_counts[cb];
         c->cnt_buf = cb;
-        // launch order: the most recent sort of a launch of the same shape that is three or four launches old (two or three
-        // more than the frames the caller says it keeps in flight, if that is more: with short frames -- C2, 0.08 ms -- the
-        // sort of the launch that finished one frame time ago is itself only just finishing) -- a younger one may still be waiting
-        // for its launch to finish (the sorts run on a side stream behind their launches; waiting for one would put a bubble
-        // into this stream, and with four frames in flight it would chain this launch behind the one three before it), an
-        // older one's buffer may be recycled under this launch; ordered behind it by its event (long complete by then)
         const unsigned long long okey = ((unsigned long long)grid.x << 32) ^ ((unsigned long long)block.x << 20) ^
                                         ((unsigned long long)variant << 16) ^ ((unsigned long long)world << 8) ^ (unsigned long long)rank ^
                                         (packed ? 1ull << 63 : 0ull);
-        // (not the flavour: the kernels that march one packet per wavefront -- 6, 12, 13, 16, 17 -- share the logical blocks, so a
-        // launch order sorted behind one of them serves the others: the measured choice below tries them in turn on a live scene)
-        P.order = nullptr;
         const bool ordered = grid.x <= (unsigned)kOrderMaxBlocks && grid.x % 8u == 0;
-        if (ordered) {
-            const vr_ctx::OrderSlot* best = nullptr;
-            const unsigned long long age = (unsigned long long)(c->frames_in_flight + 2 > 3 ? c->frames_in_flight + 2 : 3);
-            for (const auto& o : c->order_ring)
-                if (o.valid && o.key == okey && o.seq + age + 1 >= c->order_seq && o.seq + age <= c->order_seq && (!best || o.seq > best->seq))
-                    best = &o;
-            if (best) {
-                VR_HIP(c, host_wait ? hipEventSynchronize(best->sorted) : hipStreamWaitEvent(s, best->sorted, 0));
-                if (slot_sort && best->seq >= slot_sort->seq) slot_sort = nullptr;  // (covered: the order stream runs its sorts in order)
-                P.order = best->buf;
-            }
-        }
-        VR_HIP(c, wait_slot_sort());
-        const int slot = (int)(c->ring.head % kRing);
+        if (const int rc = wait_for_order(c, s, ordered, okey, slot_sort, &P.order)) return rc;
+
+        const int ring = (int)(c->ring.head % kRing);
         if (frame_events) VR_HIP(c, hipEventRecord(c->tm.ev_k0, s));
         // launches with a sort behind them are timed from their own records (order_blocks_kernel); events only otherwise
         const bool time_with_events = !(ordered && c->h_span) || c->event_timing;
-        c->ring_events[slot] = time_with_events;
-        if (c->h_span) c->h_span[slot] = 0;
-        if (c->h_end) c->h_end[slot] = 0;
-        if (time_with_events) VR_HIP(c, hipEventRecord(c->ring.k0[slot], s));
-        {
-            LaunchDesc L;
-            L.variant = variant;
-            L.off32 = off32;
-            L.dp = dp;
-            L.dp_pipe = dp_pipe;
-            L.lt = fl == 15;
-            L.pw = false;
-            L.pw_ltf = false;
-            L.pw_pipe = false;
-            L.pw_p2 = false;
-            L.pw_p2_skip = false;
-            L.pw_p2_win = false;
-            L.lds_bytes = (fl == 18 && P.vol[0].lut) ? lut_lds : 0u;
-            L.queue = PwQueue{nullptr, 0u, 0u};
-            L.grid = grid;
-            L.block = block;
-            // frame f of the launch: every n_frames-th group of 8 workgroups (MarchBatch), its own uniforms, output and
-            // records; the launch order (a heuristic of the shape) is shared
-            static thread_local MarchBatch B;
-            P.batch_n = (unsigned)n_frames;
-            B.frame[0] = P;
-            for (int f = 1; f < n_frames; ++f) {
-                MarchParams& Pf = B.frame[f];
-                Pf = P;
-                fill_frame_params(Pf, batch_u[f]);
-                Pf.out = (float4*)batch_out[f];
-                Pf.block_counts = P.block_counts + (size_t)f * grid.x * kBlockRecord;
-            }
-            B.n_frames = (unsigned)n_frames;
-            L.grid = dim3(grid.x * (unsigned)n_frames);
-                if (pw) {
-                // persistent wavefronts: `grid` stays the number of LOGICAL blocks (records, launch order); the launch itself is one
-                // workgroup of 16 wavefronts per CU (fewer when there are fewer packets), TF slot 0 in LDS when its two tables
-                // have one resolution and fit beside nothing else (R <= 8190: 128 KiB)
-                // (march_p2_kernel: two corner buffers, 3 wavefronts per SIMD at most; with every ray sampling all the time two per
-                // SIMD are faster -- the corner data in flight is many times the L1 either way: noisy air 2.13 -> 2.04 ms)
-                const bool p2 = fl == 16 || fl == 17;
-                // (the unlit shader's two buffers are 4-byte densities, 101 VGPRs: 4 wavefronts per SIMD -- C2 one frame at a time 0.121 ->
-                // 0.113 ms, thin table 0.255 -> 0.239, four frames per launch 0.070 -> 0.061: tools/experiments/s2h.sh)
-                const unsigned pw_threads = fl == 17 ? (variant == VR_VARIANT_BASIC ? 1024u : 768u) : (fl == 16 ? 512u : 1024u);
-                // (launches in flight: the same shape.  Two workgroups of 6 wavefronts do not share a CU -- the second one's wavefronts
-                // would have to go 1-1-2-2 over the SIMDs where the dispatcher deals 2-2-1-1: measured 0.75 ms per C3 frame, what
-                // one such workgroup per CU takes -- and two of 4 run at 8 wavefronts per CU: 0.63 against 0.54; three of 4, the same
-                // 12 wavefronts per CU, take 0.79 ms one frame at a time and 0.62 in flight against 0.55 / 0.51: profiles/r04_p2_launch_shapes.txt)
-                const unsigned per_wg = pw_threads / 64u;
-                const unsigned items = grid.x * (unsigned)n_frames;
-                const unsigned wgs = (items + per_wg - 1u) / per_wg;
-                L.pw = true;
-                L.pw_pipe = fl == 13;
-                L.pw_p2 = p2;
-                L.pw_p2_skip = fl == 17 && P.brick_dist != nullptr;
-                L.pw_p2_win = p2 && (!off32 || c->p2_window != 0);
-                L.pw_ltf = c->tf[0].res_o == c->tf[0].res_c && c->tf[0].res_o + 2 <= 8192;
-                L.lds_bytes = p2 ? p2_lds : (L.pw_ltf ? (unsigned)(c->tf[0].res_o + 2) * 16u : 0u);
-                L.queue.heads = c->d_pw_heads + (size_t)cb * 8 * 64;
-                L.queue.n_items = grid.x;
-                L.queue.p2_window = c->p2_window;
-                const unsigned max_wgs = (unsigned)c->n_cus;
-                L.grid = dim3(wgs < max_wgs ? wgs : max_wgs);
-                L.block = dim3(pw_threads);
-                if (c->pw_heads_dirty[cb]) VR_HIP(c, hipMemsetAsync(L.queue.heads, 0, 8 * 64 * sizeof(unsigned), s));
-                c->pw_heads_dirty[cb] = true;  // (until the sort that clears them behind this launch has really been enqueued: below)
-            }
-            if (c->arith == VR_ARITH_FUSED) vrf::launch_march(L, s, B);
-            else vr::launch_march(L, s, B);
+        c->ring_events[ring] = time_with_events;
+        if (c->h_span) c->h_span[ring] = 0;
+        if (c->h_end) c->h_end[ring] = 0;
+        if (time_with_events) VR_HIP(c, hipEventRecord(c->ring.k0[ring], s));
+        const MarchBatch& B = fill_batch(P, n_frames, batch_u, batch_out, grid.x);
+        LaunchDesc L = {};
+        L.variant = variant;
+        L.family = form.family;
+        L.off32 = off32;
+        L.lanes = form.lanes;
+        L.pipe = form.pipe;
+        L.lds_bytes = P.vol[0].lut ? E.lut_lds : 0u;
+        L.grid = dim3(grid.x * (unsigned)n_frames);
+        L.block = block;
+        if (pw) {
+            // persistent wavefronts: `grid` stays the number of LOGICAL blocks (records, launch order); the launch itself is one
+            // workgroup of form.pw_threads per CU (fewer when there are fewer packets), TF slot 0 in LDS when it fits
+            const bool p2 = form.family == LaunchDesc::kP2;
+            const unsigned per_wg = form.pw_threads / 64u, wgs = (grid.x * (unsigned)n_frames + per_wg - 1u) / per_wg;
+            L.ltf = tf0_fits_lds(c);
+            L.p2_skip = form.p2_skip && P.brick_dist != nullptr;
+            L.p2_win = p2 && (!off32 || c->p2_window != 0);
+            L.lds_bytes = p2 ? E.p2_lds : (L.ltf ? (unsigned)(c->tf[0].res_o + 2) * 16u : 0u);
+            L.queue = PwQueue{c->d_pw_heads + (size_t)cb * 8 * 64, grid.x, c->p2_window};
+            L.grid = dim3(wgs < (unsigned)c->n_cus ? wgs : (unsigned)c->n_cus);
+            L.block = dim3(form.pw_threads);
+            if (c->pw_heads_dirty[cb]) VR_HIP(c, hipMemsetAsync(L.queue.heads, 0, 8 * 64 * sizeof(unsigned), s));
+            c->pw_heads_dirty[cb] = true;  // (until the sort that clears them behind this launch has really been enqueued)
         }
+        if (c->arith == VR_ARITH_FUSED) vrf::launch_march(L, s, B);
+        else vr::launch_march(L, s, B);
         VR_HIP(c, hipGetLastError());
-        if (time_with_events) VR_HIP(c, hipEventRecord(c->ring.k1[slot], s));
-        if (ordered) {
-            vr_ctx::OrderSlot& o = c->order_ring[c->order_seq % kOrderRing];
-            o.valid = false;
-            if (grid.x > o.cap) {
-                if (o.buf) (void)hipFree(o.buf);
-                o.buf = nullptr;
-                o.cap = 0;
-                VR_HIP(c, hipMalloc(&o.buf, (size_t)grid.x * sizeof(unsigned)));
-                o.cap = grid.x;
-            }
-            o.stream = s;
-            o.key = okey;
-            o.scene_key = ((unsigned long long)variant << 16) ^ ((unsigned long long)world << 8) ^ (unsigned long long)rank ^
-                          (packed ? 1ull << 63 : 0ull) ^ ((unsigned long long)c->W << 40) ^ ((unsigned long long)c->H << 24);
-            o.seq = c->order_seq;
-            if (c->h_chain) c->h_chain[c->order_seq % kOrderRing] = 0;  // not known until this launch's sort has run
-        }
-        VR_HIP(c, hipEventRecord(c->slot_done[cb], s));
-        c->slot_used[cb] = true;
-        if (ordered) {
-            vr_ctx::OrderSlot& o = c->order_ring[c->order_seq % kOrderRing];
-            VR_HIP(c, hipStreamWaitEvent(c->order_stream, c->slot_done[cb], 0));
-            hipLaunchKernelGGL(order_blocks_kernel, dim3(1), dim3(1024), 0, c->order_stream, c->d_block_counts[cb], (int)grid.x, o.buf,
-                               c->h_chain ? c->h_chain + (c->order_seq % kOrderRing) : (unsigned*)nullptr,
-                               (c->h_span && !time_with_events) ? c->h_span + slot : (unsigned long long*)nullptr,
-                               pw ? c->d_pw_heads + (size_t)cb * 8 * 64 : (unsigned*)nullptr,
-                               (c->h_span && c->h_end && !time_with_events) ? c->h_end + slot : (unsigned long long*)nullptr);
-            VR_HIP(c, hipGetLastError());
-            if (pw) c->pw_heads_dirty[cb] = false;  // (the sort zeroes the heads behind the launch: the slot's next user finds them clean)
-            VR_HIP(c, hipEventRecord(o.sorted, c->order_stream));
-            o.valid = true;
-        }
-        ++c->order_seq;
+        if (time_with_events) VR_HIP(c, hipEventRecord(c->ring.k1[ring], s));
+
+        if (const int rc = enqueue_sort(c, s, cb, ordered, okey, scene_key(c, variant, rank, world, packed), grid.x, ring, time_with_events, pw))
+            return rc;
         if (frame_events) VR_HIP(c, hipEventRecord(c->tm.ev_k1, s));
         ++c->ring.head;
         c->cnt_blocks = (int)grid.x;
@@ -992,7 +1082,7 @@ int refresh_bricks(vr_ctx* c, int slot)
     c->vol_bricks[slot] = nullptr;
     c->merged_stale = true;
     ++c->brick_epoch;
-    const int bnx = (v.nx + kBrickCells - 1) >> kBrickShift, bny = (v.ny + kBrickCells - 1) >> kBrickShift, bnz = (v.nz + kBrickCells - 1) >> kBrickShift;
+    const int bnx = skip_bricks(v.nx), bny = skip_bricks(v.ny), bnz = skip_bricks(v.nz);
     const size_t nbricks = (size_t)bnx * bny * bnz;
     VR_HIP(c, hipMalloc(&c->vol_bricks[slot], nbricks * sizeof(float2)));
     hipLaunchKernelGGL(brick_max_kernel, dim3((unsigned)nbricks), dim3(64), 0, c->stream, v.data, v.nx, v.ny, v.nz, bnx, bny,
@@ -1021,8 +1111,8 @@ int refresh_bricks(vr_ctx* c, int slot)
     c->vol_grad_derived[slot] = flag == 0;
     c->vol[slot].dens = c->vol_dens[slot];
     {   // the bricked copy the march kernels gather from (DevVolume::bricked)
-        const unsigned nbx = ((unsigned)v.nx + kVbM) >> kVbS, nby = ((unsigned)v.ny + kVbM) >> kVbS, nbz = ((unsigned)v.nz + kVbM) >> kVbS;
-        const size_t slots = (size_t)nbx * nby * nbz * kVbN;
+        const BrickedGrid g = bricked_grid(v);
+        const size_t slots = g.slots;
         if (slots > c->vol_bricked_cap[slot]) {
             if (c->vol_bricked[slot]) (void)hipFree(c->vol_bricked[slot]);
             if (c->vol_bdens[slot]) (void)hipFree(c->vol_bdens[slot]);
@@ -1045,7 +1135,7 @@ int refresh_bricks(vr_ctx* c, int slot)
             return VR_OK;
         }
         hipLaunchKernelGGL(rebrick_kernel, dim3(8192), dim3(256), 0, c->stream, v.data, c->vol_bricked[slot], c->vol_bdens[slot], v.nx,
-                           v.ny, v.nz, nbx, nby, slots);
+                           v.ny, v.nz, g.nbx, g.nby, slots);
         VR_HIP(c, hipGetLastError());
         VR_HIP(c, hipStreamSynchronize(c->stream));
     }
@@ -1252,7 +1342,6 @@ int vr_create(vr_ctx** out, uint32_t width, uint32_t height, int device_id)
         std::memset(c->h_chain, 0, kOrderRing * sizeof(unsigned));
     else
         c->h_chain = nullptr;  // (the choice of lanes per ray then goes by the launch size alone)
-    if (const char* e = getenv("VR_EXP_HOST_ORDER_WAIT")) c->host_order_wait = atoi(e) != 0;
     if (!hip_ok(hipMalloc(&c->d_counters, 3 * sizeof(unsigned long long)), "hipMalloc(counters)")) return bail(VR_ERR_HIP);
     if (!hip_ok(hipHostMalloc((void**)&c->h_counters, 3 * sizeof(unsigned long long), hipHostMallocDefault),
                 "hipHostMalloc"))

@@ -137,19 +137,18 @@ struct PwQueue {
 };
 
 // What enqueue_render decided about one march launch; handed to launch_march of the arithmetic mode's translation unit
-// (vr_launch.h: namespace vr = separately rounded multiply-adds, namespace vrf = fused).
+// (vr_launch.h: namespace vr = separately rounded multiply-adds, namespace vrf = fused).  Host only.
 struct LaunchDesc {
+    enum Family { kPlain, kDp, kPw, kP2, kLt };
     int variant;      // vr_variant
+    Family family;    // march_kernel, march_dp_kernel, march_pw_kernel (persistent wavefronts: grid = workgroups, the packets come
+                      // from `queue`), march_p2_kernel (the same, corner loads two steps ahead), march_lt_kernel (LDS tiles, lit shader)
     bool off32;       // every bound volume < 4 GiB: 32-bit byte offsets
-    int dp;           // lanes per ray of march_dp_kernel (2 / 4), 0 = march_kernel
-    bool dp_pipe;     // ... with the next round's corner loads software-pipelined
-    bool lt;          // LDS tiles filled by LDS-DMA (vr_lt.h; lit shader)
-    bool pw;          // persistent wavefronts (vr_pw.h): grid = workgroups of 1024 threads, the packets come from `queue`
-    bool pw_ltf;      // ... with TF slot 0 in LDS (lds_bytes of dynamic LDS)
-    bool pw_pipe;     // ... with the next step's corner loads software-pipelined (lit / unlit shader)
-    bool pw_p2;       // ... the no-skip form with the corner loads two steps ahead (march_p2_kernel; TF slot 0 in LDS, bricked copy)
-    bool pw_p2_skip;  // ... ... with skipping by whole wavefronts (march_p2_kernel<V, true>)
-    bool pw_p2_win;   // ... ... a bound volume of 4 GiB or more: the gather window moves (march_p2_kernel<.., WIN>)
+    int lanes;        // kDp: lanes per ray (2 / 4)
+    bool pipe;        // kDp / kPw: the next round's / step's corner loads software-pipelined
+    bool ltf;         // kPw: TF slot 0 in LDS (lds_bytes of dynamic LDS)
+    bool p2_skip;     // kP2: skipping by whole wavefronts (march_p2_kernel<V, true>)
+    bool p2_win;      // kP2: a bound volume of 4 GiB or more: the gather window moves (march_p2_kernel<.., WIN>)
     unsigned lds_bytes;
     PwQueue queue;
     dim3 grid, block;

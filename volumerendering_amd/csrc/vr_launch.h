@@ -19,200 +19,109 @@
 // vr_set_kernel_flavour(15) and tested on every box, not a candidate of the measured choice.
 #include "vr_lt.h"
 
+#include <type_traits>
+
 namespace VR_KNS {
 
-template <int V>
-void launch_variant(bool off32, dim3 grid, dim3 block, hipStream_t s, const MarchBatch& B, unsigned lds_bytes = 0)
+// the shaders with exact empty-space skipping (brick records), with a pipelined loop, with a two-steps-ahead kernel
+template <int V> constexpr bool kCanSkip = V == V_BASIC || V == V_LIGHT || V == V_THREE_FILES || V == V_VOLUME_MASK || V == V_LIGHT_INSHADER;
+template <int V> constexpr bool kCanPipe = V == V_BASIC || V == V_LIGHT;
+template <int V> constexpr bool kCanP2 = kCanPipe<V> || V == V_VOLUME_MASK;
+
+// f(std::bool_constant<b>{}...): run-time flags as template arguments.  f is instantiated for every combination; it skips the ones
+// that have no kernel with `if constexpr`.
+template <class F>
+void with_flags(F&& f) { f(); }
+template <class F, class... R>
+void with_flags(F&& f, bool b, R... rest)
 {
-    constexpr bool kCanSkip = (V == V_BASIC || V == V_LIGHT || V == V_THREE_FILES || V == V_VOLUME_MASK || V == V_LIGHT_INSHADER);
-    // launches that carry several frames (MarchBatch) exist for both loop forms: plain (0) and, skipping, runs (3)
-#define VR_LAUNCH(O, S, L)                                                                                             \
-    do {                                                                                                               \
-        if (B.n_frames > 1) hipLaunchKernelGGL((march_kernel<V, O, S, L, true>), grid, block, lds_bytes, s, B);        \
-        else hipLaunchKernelGGL((march_kernel<V, O, S, L, false>), grid, block, lds_bytes, s, B);                      \
-    } while (0)
-    if constexpr (kCanSkip) {
-        if (B.frame[0].brick_dist) {
-            if (off32) VR_LAUNCH(true, true, 3);
-            else VR_LAUNCH(false, true, 3);
-            return;
-        }
-    }
-    if (off32) VR_LAUNCH(true, false, 0);
-    else VR_LAUNCH(false, false, 0);
-#undef VR_LAUNCH
+    if (b) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
 
-template <int V, int K, bool PIPE>
-void launch_dp(bool off32, dim3 grid, dim3 block, hipStream_t s, const MarchBatch& B)
+// march_pw_kernel / march_p2_kernel: more than 48 KiB of dynamic LDS must be allowed per kernel first.  Keyed on the kernel itself: every
+// instantiation of one kernel template has the same function type, and `raised` must be one per kernel (the attribute sticks to it).
+template <auto K>
+void launch_queued(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
 {
-    constexpr bool kCanSkip = (V == V_BASIC || V == V_LIGHT || V == V_THREE_FILES || V == V_VOLUME_MASK);
-#define VR_LAUNCH_DP(O, S)                                                                                             \
-    do {                                                                                                               \
-        if (B.n_frames > 1) hipLaunchKernelGGL((march_dp_kernel<V, O, S, K, PIPE, true>), grid, block, 0, s, B);       \
-        else hipLaunchKernelGGL((march_dp_kernel<V, O, S, K, PIPE, false>), grid, block, 0, s, B);                     \
-    } while (0)
-    if constexpr (kCanSkip) {
-        if (B.frame[0].brick_dist) {
-            if (off32) VR_LAUNCH_DP(true, true);
-            else VR_LAUNCH_DP(false, true);
-            return;
+    if (L.lds_bytes > 48u * 1024u) {
+        static unsigned raised = 0;
+        if (L.lds_bytes > raised) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes);
+            raised = L.lds_bytes;
         }
     }
-    if (off32) VR_LAUNCH_DP(true, false);
-    else VR_LAUNCH_DP(false, false);
-#undef VR_LAUNCH_DP
+    hipLaunchKernelGGL(K, L.grid, L.block, L.lds_bytes, s, B, L.queue);
+}
+
+// march_kernel; launches that carry several frames (MarchBatch) exist for both loop forms: plain (0) and, skipping, runs (3)
+template <int V>
+void launch_plain(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
+{
+    with_flags([&](auto O, auto S, auto BT) {
+        if constexpr (!S || kCanSkip<V>)
+            hipLaunchKernelGGL((march_kernel<V, O, S, (S ? 3 : 0), BT>), L.grid, L.block, L.lds_bytes, s, B);
+    }, L.off32, kCanSkip<V> && B.frame[0].brick_dist, B.n_frames > 1);
+}
+
+// march_dp_kernel, 4 or 2 lanes per ray (the pipelined form exists for the lit shader)
+template <int V>
+void launch_dp(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
+{
+    with_flags([&](auto O, auto S, auto K4, auto PIPE, auto BT) {
+        if constexpr ((!S || kCanSkip<V>) && (!PIPE || V == V_LIGHT))
+            hipLaunchKernelGGL((march_dp_kernel<V, O, S, (K4 ? 4 : 2), PIPE, BT>), L.grid, L.block, 0, s, B);
+    }, L.off32, kCanSkip<V> && B.frame[0].brick_dist, L.lanes == 4, V == V_LIGHT && L.pipe, B.n_frames > 1);
 }
 
 // persistent wavefronts (vr_pw.h); the loop form is march_kernel's default (runs through inert bricks when skipping)
 template <int V>
 void launch_pw(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
 {
-    constexpr bool kCanSkip = (V == V_BASIC || V == V_LIGHT || V == V_THREE_FILES || V == V_VOLUME_MASK || V == V_LIGHT_INSHADER);
-    const bool skip = kCanSkip && B.frame[0].brick_dist != nullptr;
-#define VR_LAUNCH_PW(O, S, T, PP)                                                                                      \
-    do {                                                                                                               \
-        auto k = march_pw_kernel<V, O, S, T, PP>;                                                                      \
-        if (L.lds_bytes > 48u * 1024u) {                                                                               \
-            static unsigned raised = 0;  /* per instantiation: the attribute sticks to the function */                 \
-            if (L.lds_bytes > raised) {                                                                                \
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,\
-                                          (int)L.lds_bytes);                                                           \
-                raised = L.lds_bytes;                                                                                  \
-            }                                                                                                          \
-        }                                                                                                              \
-        hipLaunchKernelGGL(k, L.grid, L.block, L.lds_bytes, s, B, L.queue);                                            \
-    } while (0)
-#define VR_LAUNCH_PW_T(O, S)                                                                                           \
-    do {                                                                                                               \
-        if constexpr (kCanPipe) {                                                                                      \
-            if (L.pw_pipe) {                                                                                           \
-                if (L.pw_ltf) VR_LAUNCH_PW(O, S, true, true);                                                          \
-                else VR_LAUNCH_PW(O, S, false, true);                                                                  \
-                break;                                                                                                 \
-            }                                                                                                          \
-        }                                                                                                              \
-        if (L.pw_ltf) VR_LAUNCH_PW(O, S, true, false);                                                                 \
-        else VR_LAUNCH_PW(O, S, false, false);                                                                         \
-    } while (0)
-    constexpr bool kCanPipe = (V == V_BASIC || V == V_LIGHT);
-    constexpr bool kCanP2 = kCanPipe || V == V_VOLUME_MASK;
-    if constexpr (kCanP2) {
-        if (L.pw_p2) {  // two steps ahead (vr_p2.h; the host: TF slot 0 and the axis tables fit LDS, the bricked copy is in use)
-#define VR_LAUNCH_P2(S, WN, BT)                                                                                        \
-    do {                                                                                                               \
-        auto k = march_p2_kernel<V, S, WN, BT>;                                                                        \
-        if (L.lds_bytes > 48u * 1024u) {                                                                               \
-            static unsigned raised = 0;                                                                                \
-            if (L.lds_bytes > raised) {                                                                                \
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,\
-                                          (int)L.lds_bytes);                                                           \
-                raised = L.lds_bytes;                                                                                  \
-            }                                                                                                          \
-        }                                                                                                              \
-        hipLaunchKernelGGL(k, L.grid, L.block, L.lds_bytes, s, B, L.queue);                                            \
-    } while (0)
-#define VR_LAUNCH_P2_W(S)                                                                                              \
-    do {                                                                                                               \
-        if (L.pw_p2_win) {                                                                                             \
-            if (B.n_frames > 1) VR_LAUNCH_P2(S, true, true);                                                           \
-            else VR_LAUNCH_P2(S, true, false);                                                                         \
-        } else {                                                                                                       \
-            if (B.n_frames > 1) VR_LAUNCH_P2(S, false, true);                                                          \
-            else VR_LAUNCH_P2(S, false, false);                                                                        \
-        }                                                                                                              \
-    } while (0)
-            if constexpr (V == V_VOLUME_MASK) {
-                VR_LAUNCH_P2_W(true);  // (the host asks for it only with the brick records in place)
-            } else {
-                if (skip && L.pw_p2_skip) VR_LAUNCH_P2_W(true);
-                else VR_LAUNCH_P2_W(false);
-            }
-#undef VR_LAUNCH_P2_W
-#undef VR_LAUNCH_P2
-            return;
-        }
-    }
-    if constexpr (kCanSkip) {
-        if (skip) {
-            if (L.off32) VR_LAUNCH_PW_T(true, true);
-            else VR_LAUNCH_PW_T(false, true);
-            return;
-        }
-    }
-    if (L.off32) VR_LAUNCH_PW_T(true, false);
-    else VR_LAUNCH_PW_T(false, false);
-#undef VR_LAUNCH_PW_T
-#undef VR_LAUNCH_PW
+    with_flags([&](auto O, auto S, auto T, auto PP) {
+        if constexpr ((!S || kCanSkip<V>) && (!PP || kCanPipe<V>)) launch_queued<march_pw_kernel<V, O, S, T, PP>>(L, s, B);
+    }, L.off32, kCanSkip<V> && B.frame[0].brick_dist, L.ltf, kCanPipe<V> && L.pipe);
+}
+
+// two steps ahead (vr_p2.h; the host: TF slot 0 and the axis tables fit LDS, the bricked copy is in use).  The composite's form is the
+// skipping one (the host asks for it only with the brick records in place).
+template <int V>
+void launch_p2(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
+{
+    with_flags([&](auto S, auto WN, auto BT) {
+        if constexpr (S || V != V_VOLUME_MASK) launch_queued<march_p2_kernel<V, S, WN, BT>>(L, s, B);
+    }, V == V_VOLUME_MASK || (B.frame[0].brick_dist && L.p2_skip), L.p2_win, B.n_frames > 1);
 }
 
 void launch_march(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
 {
-    const int variant = L.variant;
-    if (L.lt) {  // LDS tiles (vr_lt.h): lit shader
-        const bool skip = B.frame[0].brick_dist != nullptr;
-        if (L.off32) {
-            if (skip) hipLaunchKernelGGL((march_lt_kernel<true, true>), L.grid, L.block, 0, s, B);
-            else hipLaunchKernelGGL((march_lt_kernel<true, false>), L.grid, L.block, 0, s, B);
-        } else {
-            if (skip) hipLaunchKernelGGL((march_lt_kernel<false, true>), L.grid, L.block, 0, s, B);
-            else hipLaunchKernelGGL((march_lt_kernel<false, false>), L.grid, L.block, 0, s, B);
-        }
+    if (L.family == LaunchDesc::kLt) {  // LDS tiles (vr_lt.h): lit shader
+        with_flags([&](auto O, auto S) { hipLaunchKernelGGL((march_lt_kernel<O, S>), L.grid, L.block, 0, s, B); },
+                   L.off32, B.frame[0].brick_dist != nullptr);
         return;
     }
-    if (L.pw) {
-        switch (variant) {
-        case VR_VARIANT_BASIC: launch_pw<V_BASIC>(L, s, B); break;
-        case VR_VARIANT_LIGHT: launch_pw<V_LIGHT>(L, s, B); break;
-        case VR_VARIANT_VOLUME_MASK: launch_pw<V_VOLUME_MASK>(L, s, B); break;
-        case VR_VARIANT_THREE_FILES: launch_pw<V_THREE_FILES>(L, s, B); break;
-        case VR_VARIANT_MULTI_CTRT: launch_pw<V_MULTI_CTRT>(L, s, B); break;
-        case VR_VARIANT_ILLUSTRATIVE: launch_pw<V_ILLUSTRATIVE>(L, s, B); break;
-        case VR_VARIANT_LIGHT_INSHADER: launch_pw<V_LIGHT_INSHADER>(L, s, B); break;
-        default: launch_pw<V_TF_CALIB>(L, s, B); break;
-        }
-        return;
-    }
-    const bool off32 = L.off32, dp_pipe = L.dp_pipe;
-    const int dp = L.dp;
-    const dim3 grid = L.grid, block = L.block;
-    if (dp == 4) {
-        switch (variant) {
-        case VR_VARIANT_BASIC: launch_dp<V_BASIC, 4, false>(off32, grid, block, s, B); break;
-        case VR_VARIANT_LIGHT:
-            if (dp_pipe) launch_dp<V_LIGHT, 4, true>(off32, grid, block, s, B);
-            else launch_dp<V_LIGHT, 4, false>(off32, grid, block, s, B);
+    auto launch = [&](auto v) {
+        constexpr int V = decltype(v)::value;
+        switch (L.family) {
+        case LaunchDesc::kDp:  // (no depth-parallel form of the illustrative and in-shader gradient shaders: enqueue_render never asks for one)
+            if constexpr (V != V_ILLUSTRATIVE && V != V_LIGHT_INSHADER) launch_dp<V>(L, s, B);
             break;
-        case VR_VARIANT_VOLUME_MASK: launch_dp<V_VOLUME_MASK, 4, false>(off32, grid, block, s, B); break;
-        case VR_VARIANT_THREE_FILES: launch_dp<V_THREE_FILES, 4, false>(off32, grid, block, s, B); break;
-        case VR_VARIANT_MULTI_CTRT: launch_dp<V_MULTI_CTRT, 4, false>(off32, grid, block, s, B); break;
-        case VR_VARIANT_TF_CALIB: launch_dp<V_TF_CALIB, 4, false>(off32, grid, block, s, B); break;
-        default: break;  // (no depth-parallel form of this shader: enqueue_render never asks for one)
-        }
-    } else if (dp == 2) {
-        switch (variant) {
-        case VR_VARIANT_BASIC: launch_dp<V_BASIC, 2, false>(off32, grid, block, s, B); break;
-        case VR_VARIANT_LIGHT:
-            if (dp_pipe) launch_dp<V_LIGHT, 2, true>(off32, grid, block, s, B);
-            else launch_dp<V_LIGHT, 2, false>(off32, grid, block, s, B);
+        case LaunchDesc::kPw: launch_pw<V>(L, s, B); break;
+        case LaunchDesc::kP2:
+            if constexpr (kCanP2<V>) launch_p2<V>(L, s, B);
             break;
-        case VR_VARIANT_VOLUME_MASK: launch_dp<V_VOLUME_MASK, 2, false>(off32, grid, block, s, B); break;
-        case VR_VARIANT_THREE_FILES: launch_dp<V_THREE_FILES, 2, false>(off32, grid, block, s, B); break;
-        case VR_VARIANT_MULTI_CTRT: launch_dp<V_MULTI_CTRT, 2, false>(off32, grid, block, s, B); break;
-        case VR_VARIANT_TF_CALIB: launch_dp<V_TF_CALIB, 2, false>(off32, grid, block, s, B); break;
-        default: break;  // (no depth-parallel form of this shader: enqueue_render never asks for one)
+        default: launch_plain<V>(L, s, B); break;
         }
-    } else {
-        switch (variant) {
-        case VR_VARIANT_BASIC: launch_variant<V_BASIC>(off32, grid, block, s, B, L.lds_bytes); break;
-        case VR_VARIANT_LIGHT: launch_variant<V_LIGHT>(off32, grid, block, s, B, L.lds_bytes); break;
-        case VR_VARIANT_VOLUME_MASK: launch_variant<V_VOLUME_MASK>(off32, grid, block, s, B); break;
-        case VR_VARIANT_THREE_FILES: launch_variant<V_THREE_FILES>(off32, grid, block, s, B); break;
-        case VR_VARIANT_MULTI_CTRT: launch_variant<V_MULTI_CTRT>(off32, grid, block, s, B); break;
-        case VR_VARIANT_ILLUSTRATIVE: launch_variant<V_ILLUSTRATIVE>(off32, grid, block, s, B); break;
-        case VR_VARIANT_LIGHT_INSHADER: launch_variant<V_LIGHT_INSHADER>(off32, grid, block, s, B, L.lds_bytes); break;
-        default: launch_variant<V_TF_CALIB>(off32, grid, block, s, B); break;
-        }
+    };
+    switch (L.variant) {
+    case VR_VARIANT_BASIC: launch(std::integral_constant<int, V_BASIC>{}); break;
+    case VR_VARIANT_LIGHT: launch(std::integral_constant<int, V_LIGHT>{}); break;
+    case VR_VARIANT_VOLUME_MASK: launch(std::integral_constant<int, V_VOLUME_MASK>{}); break;
+    case VR_VARIANT_THREE_FILES: launch(std::integral_constant<int, V_THREE_FILES>{}); break;
+    case VR_VARIANT_MULTI_CTRT: launch(std::integral_constant<int, V_MULTI_CTRT>{}); break;
+    case VR_VARIANT_ILLUSTRATIVE: launch(std::integral_constant<int, V_ILLUSTRATIVE>{}); break;
+    case VR_VARIANT_LIGHT_INSHADER: launch(std::integral_constant<int, V_LIGHT_INSHADER>{}); break;
+    default: launch(std::integral_constant<int, V_TF_CALIB>{}); break;
     }
 }
 
