@@ -26,6 +26,7 @@
 #define VR_H_
 
 #include <stdint.h>
+#include <stddef.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -161,6 +162,26 @@ int vr_tf_upload(vr_ctx* ctx, int slot, const float* opacity, const float* color
 int vr_tf_upload_opacity(vr_ctx* ctx, int slot, const float* opacity, uint32_t resolution);
 int vr_tf_upload_color(vr_ctx* ctx, int slot, const float* color_rgba, uint32_t resolution);
 
+/* Stream-ordered table edits (the reference's wgpuQueueWriteTexture, App/src/renderer/Texture.cpp:87-95): what an editor
+ * calls every frame.  Arguments and validation as vr_tf_upload_opacity / _color; `stream` is a hipStream_t, NULL = the
+ * context's own stream.
+ *  - Copied on call: the table has been copied when the call returns; the caller may reuse or free its array at once.
+ *  - Ordered: every render entry point enqueued after the call returns uses the new table, on any stream, and so do its
+ *    empty-space skipping state and its counters.  Everything enqueued before the call keeps the old table, whatever its
+ *    stream.  A launch on another stream than the edit's waits for the edit once (a device-side wait, one per stream
+ *    per edit).
+ *  - Non-blocking: neither the call nor the next render that picks the edit up waits for the device, with one
+ *    exception: a call blocks the host while EIGHT earlier asynchronous edits are still being copied (the context stages
+ *    edits in eight pinned buffers, used in turn).  Each table keeps FOUR device generations; a generation is rewritten
+ *    on the device behind the last launch that read it, never by a host wait.  An opacity edit of slot 0 that moves the
+ *    table's zero prefix or changes its resolution rebuilds the empty-space distance field on `stream` as well; until its
+ *    active-brick box has reached the host, launches prune with no box (same bits, vr_unbounded_box_launches).  A
+ *    resolution change may allocate; what it replaces is freed by the next call that drains the device.
+ *  - The synchronous uploads, the volume uploads, vr_resize and vr_destroy still drain the device first, and with it
+ *    every asynchronous edit made before them.                                                                      */
+int vr_tf_upload_opacity_async(vr_ctx* ctx, int slot, const float* opacity, uint32_t resolution, void* stream);
+int vr_tf_upload_color_async(vr_ctx* ctx, int slot, const float* color_rgba, uint32_t resolution, void* stream);
+
 /* Replaces: the 12 wgpuQueueWriteBuffer calls of Application::OnUpdate (Application.cpp:96-119)
  * plus the scene's Light uniform (BasicVolLightApp.cpp:42).  Returns VR_ERR_UNSUPPORTED when
  * `model` is not the identity (the reference never uploads anything else).                       */
@@ -189,8 +210,9 @@ int vr_tile_count(const vr_ctx* ctx, int rank, int world);
  * ninth enqueue blocks the calling thread until the oldest of the eight has finished (each launch owns
  * one of eight record buffers, guarded by an event), so a caller that keeps four frames in flight never
  * waits for its oldest launch inside an enqueue.  vr_volume_upload*, vr_volume_normalize / _gradient,
- * vr_tf_upload*, vr_resize and vr_destroy drain the whole device first, so they are safe to call
- * while asynchronous renders are still in flight on the caller's streams.                          */
+ * vr_tf_upload, vr_tf_upload_opacity / _color, vr_resize and vr_destroy drain the whole device first, so they are
+ * safe to call while asynchronous renders are still in flight on the caller's streams; the asynchronous table edits
+ * (vr_tf_upload_opacity_async / _color_async) are ordered on a stream instead and drain nothing.                */
 int vr_render_async(vr_ctx* ctx, int variant, void* d_frame, void* stream);
 
 /* Streams for frames in flight.  HIP maps streams onto a few hardware queues, and two streams that share a queue run
@@ -380,6 +402,17 @@ int vr_volume_layout(vr_ctx* ctx, int slot, int* flags);
 
 /* The flavour the last render actually ran (what 0 resolved to for that launch), or a negative vr_status. */
 int vr_last_kernel_flavour(vr_ctx* ctx);
+
+/* The brick distance field a launch of `variant` would use now: built / refreshed synchronously, copied to `dist`
+ * (min(capacity, n) bytes, x fastest), the brick grid in dims[3], the active-brick box (brick coordinates, inclusive;
+ * hi < 0 if none) in box[6], the number of active bricks in *active.  Each byte is min(Chebyshev distance in bricks to
+ * the nearest active brick, 128): 0 for an active brick, 128 everywhere when none is active.  Drains the device.
+ * Returns n, or a negative vr_status (VR_ERR_NOT_READY when such a launch would not skip empty space).             */
+int vr_skip_field(vr_ctx* ctx, int variant, uint8_t* dist, size_t capacity, int dims[3], int box[6], uint64_t* active);
+
+/* How many skipping launches ran with no active-brick box because an asynchronous rebuild's box had not reached the
+ * host yet (vr_tf_upload_opacity_async), since the context was created. */
+int64_t vr_unbounded_box_launches(vr_ctx* ctx);
 
 #ifdef __cplusplus
 }

@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "vr_set_volume_layout", "vr_volume_layout", "vr_viewport", "vr_set_arithmetic", "vr_present_async", "vr_stream", "vr_hint_frames_in_flight",
     "vr_set_kernel_timing", "vr_present_tiles_async", "vr_kernel_choice",
     "vr_present_packed_async", "vr_unpack_tiles_bgra8_async",
+    "vr_tf_upload_opacity_async", "vr_tf_upload_color_async", "vr_skip_field", "vr_unbounded_box_launches",
 ]
 
 
@@ -90,6 +91,11 @@ def load() -> C.CDLL:
     lib.vr_tf_upload.argtypes = [vp, i32, vp, vp, u32]
     lib.vr_tf_upload_opacity.argtypes = [vp, i32, vp, u32]
     lib.vr_tf_upload_color.argtypes = [vp, i32, vp, u32]
+    lib.vr_tf_upload_opacity_async.argtypes = [vp, i32, vp, u32, vp]
+    lib.vr_tf_upload_color_async.argtypes = [vp, i32, vp, u32, vp]
+    lib.vr_skip_field.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_int * 3), C.POINTER(C.c_int * 6), C.POINTER(C.c_uint64)]
+    lib.vr_unbounded_box_launches.argtypes = [vp]
+    lib.vr_unbounded_box_launches.restype = C.c_int64
     lib.vr_set_uniforms.argtypes = [vp, C.POINTER(Uniforms)]
     lib.vr_render.argtypes = [vp, i32]
     lib.vr_render_tiles.argtypes = [vp, i32, i32, i32]
@@ -209,6 +215,29 @@ class Context:
         else:  # the two textures of a pair may differ in resolution
             self._chk(self.lib.vr_tf_upload_opacity(self.h, slot, o.ctypes.data, o.size))
             self._chk(self.lib.vr_tf_upload_color(self.h, slot, c.ctypes.data, c.size // 4))
+
+    def tf_upload_async(self, slot: int, opacity: np.ndarray | None = None, color: np.ndarray | None = None, stream: int = 0):
+        """Stream-ordered table edit (vr_tf_upload_opacity_async / _color_async): copied on call, used by every render enqueued
+        after it on any stream, drains nothing.  Either table may be left out."""
+        if opacity is not None:
+            o = _f32(opacity)
+            self._chk(self.lib.vr_tf_upload_opacity_async(self.h, slot, o.ctypes.data, o.size, stream))
+        if color is not None:
+            c = _f32(color)
+            self._chk(self.lib.vr_tf_upload_color_async(self.h, slot, c.ctypes.data, c.size // 4, stream))
+
+    def skip_field(self, variant: int):
+        """(field uint8[bnz, bny, bnx], box (lo xyz, hi xyz) in bricks, active bricks) a launch of `variant` would use now
+        (vr_skip_field: built synchronously)."""
+        dims, box, active = (C.c_int * 3)(), (C.c_int * 6)(), C.c_uint64(0)
+        n = self._chk(self.lib.vr_skip_field(self.h, variant, None, 0, C.byref(dims), C.byref(box), C.byref(active)))
+        out = np.zeros(n, dtype=np.uint8)
+        self._chk(self.lib.vr_skip_field(self.h, variant, out.ctypes.data, n, C.byref(dims), C.byref(box), C.byref(active)))
+        return out.reshape(dims[2], dims[1], dims[0]), tuple(int(x) for x in box), int(active.value)
+
+    def unbounded_box_launches(self) -> int:
+        """Skipping launches that ran without an active-brick box (an asynchronous rebuild's box still on its way)."""
+        return self._chk(self.lib.vr_unbounded_box_launches(self.h))
 
     def set_uniforms(self, u: Uniforms):
         self._chk(self.lib.vr_set_uniforms(self.h, C.byref(u)))

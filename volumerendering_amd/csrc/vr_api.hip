@@ -39,6 +39,23 @@ constexpr int kInFlight = 8;  // launches that may be in flight at a time (recor
                                // a caller with four frames in flight never blocks on its oldest launch)
 constexpr int kStreams = 4;   // vr_stream(): streams for frames in flight
 constexpr int kOrderRing = 16;  // launch-order buffers: written behind launch k, read by launches k+3 .. k+6 only (see enqueue_render)
+constexpr int kGen = 4;         // generations of each table and of the distance field (vr_tf_upload_*_async)
+constexpr int kStage = 8;       // pinned staging buffers of the asynchronous table edits
+constexpr int kEditSeen = 8;    // streams remembered to have waited for the latest asynchronous edit
+
+// A device buffer of one generation: written by an edit, read by the launches that captured it while it was current, on any
+// streams.  Rewritten only behind every one of them (reuse_wait): reader[k] is the order_seq of the latest launch in record slot k
+// (seq % kInFlight) that read it, -1 if none since it was last written.
+struct GenBuf {
+    void* d = nullptr;
+    size_t cap = 0;  // bytes
+    long long reader[kInFlight];
+    GenBuf() { written(); }
+    void written()
+    {
+        for (auto& r : reader) r = -1;
+    }
+};
 
 struct vr_ctx {
     int device = 0;
@@ -58,8 +75,12 @@ struct vr_ctx {
                                                // 3 x-fastest voxels + density plane (2, gradients on the fly, was removed)
     float2* merged_bricks = nullptr;           // VOLUME_MASK: (CT density max, mask rgb max), rebuilt when stale
     bool merged_stale = true;
-    unsigned char* brick_dist = nullptr;       // distance field over the records in use; key below says for what
-    size_t dist_cap = 0;
+    unsigned char* brick_dist = nullptr;       // distance field over the records in use (field[field_cur]); key below says for what
+    GenBuf field[kGen];                        // its generations (an asynchronous opacity edit builds the next one)
+    int field_cur = 0;
+    unsigned char* dist_tmp = nullptr;         // the y pass's output, the z pass's input
+    size_t tmp_cap = 0;
+    int dist_bn[3] = {0, 0, 0};                // bricks per axis of the field
     const void* dist_records = nullptr;
     unsigned long long dist_epoch = ~0ull;     // volume-change counter the field was built at
     int dist_z = -2, dist_res = 0, dist_rgb = -1;
@@ -68,8 +89,35 @@ struct vr_ctx {
     bool tf_color_finite[VR_MAX_TFS] = {false, false};
     bool tf_opacity_finite[VR_MAX_TFS] = {false, false};
     DevTF tf[VR_MAX_TFS] = {};
-    float* tf_opacity[VR_MAX_TFS] = {};
-    float4* tf_color[VR_MAX_TFS] = {};
+    GenBuf tf_buf[VR_MAX_TFS][2][kGen];        // [slot][opacity, colour]: the table's generations, tf_cur the one in use (DevTF layout)
+    int tf_cur[VR_MAX_TFS][2] = {};
+    // Asynchronous edits (vr_tf_upload_*_async): each records edit_ev on its stream, behind the one before it; a launch on
+    // another stream waits for it once (edit_seen), nothing once a draining call has seen it (drained_gen).
+    hipEvent_t edit_ev = nullptr;
+    hipStream_t edit_stream = nullptr;
+    unsigned long long edit_gen = 0, drained_gen = 0;
+    struct EditSeen {
+        hipStream_t s = nullptr;
+        unsigned long long gen = 0;
+    } edit_seen[kEditSeen];
+    int seen_next = 0;
+    struct Stage {  // pinned copy of an edited table, in the DevTF layout; reused behind its copy's event
+        void* h = nullptr;
+        size_t cap = 0;
+        hipEvent_t done = nullptr;
+        bool used = false;
+    } stage[kStage];
+    unsigned stage_next = 0;
+    std::vector<void*> retired_dev, retired_host;  // replaced on a non-blocking path: freed by the next draining call
+    // What each field build reports (SkipSummary, pinned, one per field generation) and the device words it accumulates in.
+    // skip_pending: a build's count and box have not reached the host yet -- launches use the unbounded box meanwhile.
+    SkipSummary* h_skip = nullptr;
+    SkipSumDev* d_skip_sum = nullptr;
+    unsigned long long skip_gen = 0;
+    bool skip_pending = false;
+    int skip_box[6] = {0x7fffffff, 0x7fffffff, 0x7fffffff, -1, -1, -1};  // of the field in use, once known (vr_skip_field)
+    unsigned long long skip_active = 0;
+    long long unbounded_launches = 0;
     vr_uniforms u = {};
     bool have_uniforms = false;
     float4* d_frame = nullptr;
@@ -606,6 +654,113 @@ Eligibility eligibility(const vr_ctx* c, int requested, int variant, int n_frame
     return E;
 }
 
+// After a hipDeviceSynchronize: every asynchronous edit has completed, and what they replaced can be freed.
+void drained(vr_ctx* c)
+{
+    for (void* p : c->retired_dev) (void)hipFree(p);
+    for (void* p : c->retired_host) (void)hipHostFree(p);
+    c->retired_dev.clear();
+    c->retired_host.clear();
+    c->drained_gen = c->edit_gen;
+}
+
+// Before `s` rewrites generation b: every launch that read it must have finished, whatever its stream (launches on different
+// streams finish in any order).  A reader fewer than kInFlight launches old still owns its record slot's event: s waits for it on
+// the device, one wait per such slot.  An older one was waited for on the host by the take_record_slot that reused its slot.
+int reuse_wait(vr_ctx* c, hipStream_t s, const GenBuf& b)
+{
+    for (int k = 0; k < kInFlight; ++k)
+        if (b.reader[k] >= 0 && (unsigned long long)b.reader[k] + kInFlight >= c->order_seq)
+            VR_HIP(c, hipStreamWaitEvent(s, c->slot_done[k], 0));
+    return VR_OK;
+}
+
+// A launch on `s` comes after every asynchronous edit made so far: once per stream per edit, a wait for the latest edit's event
+// (each edit is ordered behind the one before it).
+int wait_for_edits(vr_ctx* c, hipStream_t s)
+{
+    if (c->edit_gen <= c->drained_gen) return VR_OK;
+    vr_ctx::EditSeen* e = nullptr;
+    for (auto& x : c->edit_seen)
+        if (x.s == s) e = &x;
+    if (e && e->gen >= c->edit_gen) return VR_OK;
+    if (s != c->edit_stream) VR_HIP(c, hipStreamWaitEvent(s, c->edit_ev, 0));
+    if (!e) e = &c->edit_seen[c->seen_next++ % kEditSeen];
+    e->s = s;
+    e->gen = c->edit_gen;
+    return VR_OK;
+}
+
+// The launches' reads of the current generations (enqueued as launch order_seq, whose slot event is recorded behind it).
+void mark_reads(vr_ctx* c, const MarchParams& P)
+{
+    for (int i = 0; i < VR_MAX_TFS; ++i)
+        for (int k = 0; k < 2; ++k) {
+            GenBuf& b = c->tf_buf[i][k][c->tf_cur[i][k]];
+            if (b.d) b.reader[c->order_seq % kInFlight] = (long long)c->order_seq;
+        }
+    if (P.brick_dist) c->field[c->field_cur].reader[c->order_seq % kInFlight] = (long long)c->order_seq;
+}
+
+// The distance field of records `rec` (bricks bn) into `field` on `s`: the active bricks, the x, y and z passes (vr_kernels.h), the
+// count and box of build `gen` into h_skip[slot].  dist_tmp holds at least bn[0] * bn[1] * bn[2] bytes.
+int build_field(vr_ctx* c, hipStream_t s, const float2* rec, const int bn[3], int use_rgb, int zero_prefix, int res_o, unsigned char* field,
+                int slot, unsigned long long gen)
+{
+    const int nb = bn[0] * bn[1] * bn[2];
+    hipLaunchKernelGGL(brick_active_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, rec, field, nb, use_rgb, zero_prefix, res_o);
+    const long long waves = (long long)((bn[0] + 63) >> 6) * bn[1] * bn[2];
+    hipLaunchKernelGGL(brick_dist_x_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, field, bn[0], bn[1] * bn[2]);
+    const unsigned tx = (unsigned)((bn[0] + kDistCols - 1) / kDistCols);
+    hipLaunchKernelGGL((brick_dist_axis_kernel<false>), dim3(tx, (unsigned)((bn[1] + kDistRows - 1) / kDistRows), (unsigned)bn[2]), dim3(256),
+                       0, s, field, c->dist_tmp, bn[0], bn[1], (size_t)bn[0], (size_t)bn[0] * bn[1], (SkipSumDev*)nullptr,
+                       (SkipSummary*)nullptr, 0ull);
+    hipLaunchKernelGGL((brick_dist_axis_kernel<true>), dim3(tx, (unsigned)((bn[2] + kDistRows - 1) / kDistRows), (unsigned)bn[1]), dim3(256),
+                       0, s, c->dist_tmp, field, bn[0], bn[2], (size_t)bn[0] * bn[1], (size_t)bn[0], c->d_skip_sum + slot, c->h_skip + slot, gen);
+    VR_HIP(c, hipGetLastError());
+    return VR_OK;
+}
+
+// The count and box of the field in use, once its build has reported them (pinned h_skip, generation first): the share of active bricks
+// (which the kernel choice reads) and the box of the active bricks in uvw with one brick of margin (MarchParams::abox): brick b of axis
+// a holds the positions with p * bs - kBrickHalf in [b, b + 1), the first and the last brick those beyond them as well.
+void adopt_skip(vr_ctx* c, const float bs[3])
+{
+    if (!c->skip_pending) return;
+    const volatile SkipSummary& h = c->h_skip[c->field_cur];
+    if (h.gen != c->skip_gen) return;
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    const long long nb = (long long)c->dist_bn[0] * c->dist_bn[1] * c->dist_bn[2];
+    c->skip_active = h.count;
+    c->active_fraction = nb > 0 ? (double)h.count / (double)nb : 1.0;
+    for (int a = 0; a < 6; ++a) c->skip_box[a] = h.box[a];
+    for (int a = 0; a < 3; ++a) {
+        if (c->skip_box[3 + a] < 0) {  // (no active brick: every ray misses)
+            c->abox[a] = 3.0e38f;
+            c->abox[3 + a] = -3.0e38f;
+        } else {
+            c->abox[a] = (float)(((double)c->skip_box[a] - 1.0 + (double)kBrickHalf) / (double)bs[a]);
+            c->abox[3 + a] = (float)(((double)c->skip_box[3 + a] + 2.0 + (double)kBrickHalf) / (double)bs[a]);
+        }
+    }
+    c->skip_pending = false;
+}
+
+// Grows a generation to `bytes`.  `drain`: nothing is in flight, the old buffer is freed; otherwise it waits for the next draining call.
+int grow(vr_ctx* c, void** d, size_t* cap, size_t bytes, bool drain)
+{
+    if (bytes <= *cap) return VR_OK;
+    if (*d) {
+        if (drain) (void)hipFree(*d);
+        else c->retired_dev.push_back(*d);
+    }
+    *d = nullptr;
+    *cap = 0;
+    VR_HIP(c, hipMalloc(d, bytes));
+    *cap = bytes;
+    return VR_OK;
+}
+
 // Exact empty-space skipping (E.can_skip): fills P's brick fields from c, and rebuilds what is stale of the merged mask records, the
 // distance field, the share of active bricks (active_fraction, which the kernel choice reads) and the box of the active bricks.
 int prepare_skip(vr_ctx* c, int variant, hipStream_t s, MarchParams& P)
@@ -636,63 +791,44 @@ int prepare_skip(vr_ctx* c, int variant, hipStream_t s, MarchParams& P)
         P.use_rgb = 1;
     }
     // distance field over the inert bricks (Chebyshev distance to the nearest active brick), rebuilt when the
-    // records, the zero prefix or the table resolution changed since it was last built
+    // records, the zero prefix or the table resolution changed since it was last built (an asynchronous opacity edit rebuilds it
+    // on its own stream for the records it was built from: vr_tf_upload_opacity_async)
+    const float bs[3] = {P.bsx, P.bsy, P.bsz};
     if (c->dist_records != (const void*)P.bricks || c->dist_epoch != c->brick_epoch || c->dist_z != P.tf_zero_prefix ||
         c->dist_res != c->tf[0].res_o || c->dist_rgb != P.use_rgb || !c->brick_dist) {
         // (rare: an input changed.  Frames may be in flight on other streams and read the field: drain them first,
         // and finish the rebuild before any other stream's launch can follow)
         VR_HIP(c, hipDeviceSynchronize());
-        if ((size_t)nb > c->dist_cap) {
-            if (c->brick_dist) (void)hipFree(c->brick_dist);
-            c->brick_dist = nullptr;
-            c->dist_cap = 0;
-            VR_HIP(c, hipMalloc(&c->brick_dist, (size_t)nb));
-            c->dist_cap = (size_t)nb;
-        }
-        const dim3 g((unsigned)((nb + 255) / 256)), b(256);
-        hipLaunchKernelGGL(brick_active_kernel, g, b, 0, s, P.bricks, c->brick_dist, nb, P.use_rgb, P.tf_zero_prefix,
-                           c->tf[0].res_o);
-        for (int k = 1; k < kDistMax; ++k)
-            hipLaunchKernelGGL(brick_dist_pass_kernel, g, b, 0, s, c->brick_dist, P.bnx, P.bny, P.bnz, k);
-        hipLaunchKernelGGL(brick_dist_cap_kernel, g, b, 0, s, c->brick_dist, nb);
-        VR_HIP(c, hipGetLastError());
-        // share of active bricks (steers the default kernel choice)
-        unsigned* d_cnt = reinterpret_cast<unsigned*>(c->d_counters);
-        VR_HIP(c, hipMemsetAsync(d_cnt, 0, sizeof(unsigned), s));
-        hipLaunchKernelGGL(count_active_bricks_kernel, g, b, 0, s, c->brick_dist, nb, d_cnt);
-        VR_HIP(c, hipGetLastError());
-        unsigned cnt = 0;
-        VR_HIP(c, hipMemcpyAsync(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, s));
+        drained(c);
+        GenBuf& g = c->field[c->field_cur];
+        c->brick_dist = nullptr;
+        if (const int rc = grow(c, &g.d, &g.cap, (size_t)nb, true)) return rc;
+        if (const int rc = grow(c, (void**)&c->dist_tmp, &c->tmp_cap, (size_t)nb, true)) return rc;
+        const int bn[3] = {P.bnx, P.bny, P.bnz};
+        if (const int rc = build_field(c, s, P.bricks, bn, P.use_rgb, P.tf_zero_prefix, c->tf[0].res_o, (unsigned char*)g.d, c->field_cur,
+                                       ++c->skip_gen))
+            return rc;
         VR_HIP(c, hipStreamSynchronize(s));
-        c->active_fraction = nb > 0 ? (double)cnt / (double)nb : 1.0;
-        // the box of the active bricks, in uvw with one brick of margin (MarchParams::abox): brick b of axis a holds the
-        // positions with p * bs - kBrickHalf in [b, b + 1), the first and the last brick those beyond them as well
-        int* d_box = reinterpret_cast<int*>(c->d_counters);  // (6 ints: the counters' 24 bytes)
-        int box[6] = {0x7fffffff, 0x7fffffff, 0x7fffffff, -1, -1, -1};
-        VR_HIP(c, hipMemcpyAsync(d_box, box, sizeof box, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(active_brick_box_kernel, g, b, 0, s, c->brick_dist, P.bnx, P.bny, P.bnz, d_box);
-        VR_HIP(c, hipGetLastError());
-        VR_HIP(c, hipMemcpyAsync(box, d_box, sizeof box, hipMemcpyDeviceToHost, s));
-        VR_HIP(c, hipStreamSynchronize(s));
-        const double bs[3] = {(double)P.bsx, (double)P.bsy, (double)P.bsz};
-        for (int a = 0; a < 3; ++a) {
-            if (box[3 + a] < 0) {  // (no active brick: every ray misses)
-                c->abox[a] = 3.0e38f;
-                c->abox[3 + a] = -3.0e38f;
-            } else {
-                c->abox[a] = (float)(((double)box[a] - 1.0 + (double)kBrickHalf) / bs[a]);
-                c->abox[3 + a] = (float)(((double)box[3 + a] + 2.0 + (double)kBrickHalf) / bs[a]);
-            }
-        }
-        VR_HIP(c, hipStreamSynchronize(s));
+        g.written();
+        c->brick_dist = (unsigned char*)g.d;
+        c->skip_pending = true;
+        for (int a = 0; a < 3; ++a) c->dist_bn[a] = bn[a];
         c->dist_records = (const void*)P.bricks;
         c->dist_epoch = c->brick_epoch;
         c->dist_z = P.tf_zero_prefix;
         c->dist_res = c->tf[0].res_o;
         c->dist_rgb = P.use_rgb;
     }
+    adopt_skip(c, bs);
     P.brick_dist = c->brick_dist;
-    for (int a = 0; a < 6; ++a) P.abox[a] = c->abox[a];
+    if (c->skip_pending) {
+        // (the count and box of an asynchronous rebuild are on their way: the unbounded box -- the kernels only prune with it -- and
+        // the last share of active bricks)
+        const float unbounded[6] = {-3.0e38f, -3.0e38f, -3.0e38f, 3.0e38f, 3.0e38f, 3.0e38f};
+        for (int a = 0; a < 6; ++a) P.abox[a] = unbounded[a];
+    } else {
+        for (int a = 0; a < 6; ++a) P.abox[a] = c->abox[a];
+    }
     return VR_OK;
 }
 
@@ -934,14 +1070,17 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
     if (batch_u) out = (float4*)batch_out[0];
     VR_HIP(c, hipSetDevice(c->device));
     (void)hipGetLastError();  // a stale error of somebody else's call must not be reported as a failed launch below
+    if (const int rc = wait_for_edits(c, s)) return rc;
 
     MarchParams P;
     fill_launch_params(c, P, batch_u ? batch_u[0] : c->u, rank, world, packed);
     // the kernel choice: what can run, the skipping state (the prior reads its share of active bricks), the flavour
     const int requested = c->flavour == 0 ? c->default_flavour : c->flavour;
     const Eligibility E = eligibility(c, requested, variant, n_frames, rank, world, packed, batch_u);
-    if (E.can_skip)
+    if (E.can_skip) {
         if (const int rc = prepare_skip(c, variant, s, P)) return rc;
+        if (c->skip_pending) ++c->unbounded_launches;
+    }
     const int fl = choose_flavour(c, requested, variant, n_frames, rank, world, packed, E);
     c->last_flavour = fl;
     const KernelForm form = kernel_form(fl, variant);
@@ -1027,6 +1166,7 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
         if (c->arith == VR_ARITH_FUSED) vrf::launch_march(L, s, B);
         else vr::launch_march(L, s, B);
         VR_HIP(c, hipGetLastError());
+        mark_reads(c, P);
         if (time_with_events) VR_HIP(c, hipEventRecord(c->ring.k1[ring], s));
 
         if (const int rc = enqueue_sort(c, s, cb, ordered, okey, scene_key(c, variant, rank, world, packed), grid.x, ring, time_with_events, pw))
@@ -1149,6 +1289,7 @@ int check_slot(vr_ctx* c, int slot, const char* who)
     if (!c->vol[slot].data) return fail(c, VR_ERR_NOT_READY, std::string(who) + ": volume slot is empty");
     VR_HIP(c, hipSetDevice(c->device));
     VR_HIP(c, hipDeviceSynchronize());  // asynchronous renders on the caller's streams may still read the slot
+    drained(c);
     (void)hipGetLastError();
     return VR_OK;
 }
@@ -1164,6 +1305,7 @@ int upload_raw(vr_ctx* c, int slot, const T* raw, uint16_t nx, uint16_t ny, uint
     if (n > 0xFFFFFFFFull) return fail(c, VR_ERR_INVALID_ARG, "vr_volume_upload_raw: more than 2^32 voxels");
     VR_HIP(c, hipSetDevice(c->device));
     VR_HIP(c, hipDeviceSynchronize());  // asynchronous renders on the caller's streams may still read the slot
+    drained(c);
     (void)hipGetLastError();
     const size_t bytes = n * sizeof(float4);
     if (c->vol[slot].data && c->vol_bytes[slot] != bytes) {
@@ -1330,6 +1472,13 @@ int vr_create(vr_ctx** out, uint32_t width, uint32_t height, int device_id)
     // the sorts' barriers), and the full C3 frame gains nothing from a third frame in flight either way (tools/exp_tiles.py,
     // tools/exp_queues).
     if (!hip_ok(hipStreamCreateWithFlags(&c->order_stream, hipStreamNonBlocking), "hipStreamCreate")) return bail(VR_ERR_HIP);
+    if (!hip_ok(hipEventCreateWithFlags(&c->edit_ev, hipEventDisableTiming), "hipEventCreate")) return bail(VR_ERR_HIP);
+    for (auto& st : c->stage)
+        if (!hip_ok(hipEventCreateWithFlags(&st.done, hipEventDisableTiming), "hipEventCreate")) return bail(VR_ERR_HIP);
+    if (!hip_ok(hipHostMalloc((void**)&c->h_skip, kGen * sizeof(SkipSummary), hipHostMallocDefault), "hipHostMalloc")) return bail(VR_ERR_HIP);
+    std::memset(c->h_skip, 0, kGen * sizeof(SkipSummary));
+    if (!hip_ok(hipMalloc(&c->d_skip_sum, kGen * sizeof(SkipSumDev)), "hipMalloc(skip summary)")) return bail(VR_ERR_HIP);
+    if (!hip_ok(hipMemset(c->d_skip_sum, 0, kGen * sizeof(SkipSumDev)), "hipMemset(skip summary)")) return bail(VR_ERR_HIP);
     if (hipHostMalloc((void**)&c->h_span, kRing * sizeof(unsigned long long), hipHostMallocDefault) == hipSuccess)
         std::memset(c->h_span, 0, kRing * sizeof(unsigned long long));
     else
@@ -1360,6 +1509,7 @@ int vr_resize(vr_ctx* c, uint32_t width, uint32_t height)
         return fail(c, VR_ERR_INVALID_ARG, "vr_resize: bad viewport size");
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();  // frames may be in flight on the caller's streams
+    drained(c);
     c->W = width;
     c->H = height;
     return alloc_frame(c);
@@ -1370,6 +1520,7 @@ void vr_destroy(vr_ctx* c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();  // renders may be in flight on streams of the caller's
+    drained(c);
     for (int i = 0; i < VR_MAX_VOLUMES; ++i)
         if (c->vol[i].data) (void)hipFree(const_cast<float4*>(c->vol[i].data));
     for (int i = 0; i < VR_MAX_VOLUMES; ++i)
@@ -1380,11 +1531,20 @@ void vr_destroy(vr_ctx* c)
         if (c->vol_bdens[i]) (void)hipFree(c->vol_bdens[i]);
     }
     if (c->merged_bricks) (void)hipFree(c->merged_bricks);
-    if (c->brick_dist) (void)hipFree(c->brick_dist);
-    for (int i = 0; i < VR_MAX_TFS; ++i) {
-        if (c->tf_opacity[i]) (void)hipFree(c->tf_opacity[i]);
-        if (c->tf_color[i]) (void)hipFree(c->tf_color[i]);
+    for (auto& g : c->field)
+        if (g.d) (void)hipFree(g.d);
+    if (c->dist_tmp) (void)hipFree(c->dist_tmp);
+    for (auto& slot : c->tf_buf)
+        for (auto& kind : slot)
+            for (auto& g : kind)
+                if (g.d) (void)hipFree(g.d);
+    for (auto& st : c->stage) {
+        if (st.h) (void)hipHostFree(st.h);
+        if (st.done) (void)hipEventDestroy(st.done);
     }
+    if (c->edit_ev) (void)hipEventDestroy(c->edit_ev);
+    if (c->h_skip) (void)hipHostFree(c->h_skip);
+    if (c->d_skip_sum) (void)hipFree(c->d_skip_sum);
     if (c->d_frame) (void)hipFree(c->d_frame);
     if (c->d_tiles) (void)hipFree(c->d_tiles);
     if (c->d_present) (void)hipFree(c->d_present);
@@ -1428,6 +1588,7 @@ static int volume_upload_common(vr_ctx* c, int slot, const void* src, bool src_i
     size_t bytes = (size_t)voxels * sizeof(float4);
     VR_HIP(c, hipSetDevice(c->device));
     VR_HIP(c, hipDeviceSynchronize());  // asynchronous renders on the caller's streams may still read the slot
+    drained(c);
     if (c->vol[slot].data && c->vol_bytes[slot] != bytes) {
         (void)hipFree(const_cast<float4*>(c->vol[slot].data));
         c->vol[slot] = DevVolume{};
@@ -1459,46 +1620,25 @@ int vr_volume_upload_device(vr_ctx* c, int slot, const void* d_vec4_voxels, uint
     return volume_upload_common(c, slot, d_vec4_voxels, true, nx, ny, nz);
 }
 
-static int tf_upload_one(vr_ctx* c, int slot, const float* table, uint32_t R, bool is_color)
+static int tf_check(vr_ctx* c, int slot, const float* table, uint32_t R, const char* who)
 {
-    if (!c) return VR_ERR_INVALID_ARG;
-    if (slot < 0 || slot >= VR_MAX_TFS) return fail(c, VR_ERR_INVALID_ARG, "vr_tf_upload: bad slot");
-    if (!table) return fail(c, VR_ERR_INVALID_ARG, "vr_tf_upload: table is NULL");
-    if (R == 0 || R > (1u << 24)) return fail(c, VR_ERR_INVALID_ARG, "vr_tf_upload: bad resolution");
-    VR_HIP(c, hipSetDevice(c->device));
-    VR_HIP(c, hipDeviceSynchronize());  // asynchronous renders on the caller's streams may still read the table
+    if (slot < 0 || slot >= VR_MAX_TFS) return fail(c, VR_ERR_INVALID_ARG, std::string(who) + ": bad slot");
+    if (!table) return fail(c, VR_ERR_INVALID_ARG, std::string(who) + ": table is NULL");
+    if (R == 0 || R > (1u << 24)) return fail(c, VR_ERR_INVALID_ARG, std::string(who) + ": bad resolution");
+    return VR_OK;
+}
+
+// the host state of a table as the launches after an upload see it: the current generation, its resolution, its flags
+static void tf_set_current(vr_ctx* c, int slot, const float* table, uint32_t R, bool is_color)
+{
     ++c->tf_epoch;
+    const GenBuf& g = c->tf_buf[slot][is_color ? 1 : 0][c->tf_cur[slot][is_color ? 1 : 0]];
     if (is_color) {
-        if (c->tf[slot].res_c != (int)R) {
-            if (c->tf_color[slot]) (void)hipFree(c->tf_color[slot]);
-            c->tf_color[slot] = nullptr;
-            c->tf[slot].color = nullptr;
-            c->tf[slot].res_c = 0;
-            VR_HIP(c, hipMalloc(&c->tf_color[slot], ((size_t)R + 2) * sizeof(float4)));
-        }
-        // device layout (DevTF): the first and the last texel once more at either end
-        VR_HIP(c, hipMemcpyAsync(c->tf_color[slot] + 1, table, R * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-        VR_HIP(c, hipMemcpyAsync(c->tf_color[slot], table, sizeof(float4), hipMemcpyHostToDevice, c->stream));
-        VR_HIP(c, hipMemcpyAsync(c->tf_color[slot] + R + 1, table + 4 * ((size_t)R - 1), sizeof(float4), hipMemcpyHostToDevice,
-                                 c->stream));
-        VR_HIP(c, hipStreamSynchronize(c->stream));
-        c->tf[slot].color = c->tf_color[slot];
+        c->tf[slot].color = (const float4*)g.d;
         c->tf[slot].res_c = (int)R;
         c->tf_color_finite[slot] = all_finite(table, (int)(4 * R));
     } else {
-        if (c->tf[slot].res_o != (int)R) {
-            if (c->tf_opacity[slot]) (void)hipFree(c->tf_opacity[slot]);
-            c->tf_opacity[slot] = nullptr;
-            c->tf[slot].opacity = nullptr;
-            c->tf[slot].res_o = 0;
-            VR_HIP(c, hipMalloc(&c->tf_opacity[slot], ((size_t)R + 2) * sizeof(float)));
-        }
-        VR_HIP(c, hipMemcpyAsync(c->tf_opacity[slot] + 1, table, R * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        VR_HIP(c, hipMemcpyAsync(c->tf_opacity[slot], table, sizeof(float), hipMemcpyHostToDevice, c->stream));
-        VR_HIP(c, hipMemcpyAsync(c->tf_opacity[slot] + R + 1, table + ((size_t)R - 1), sizeof(float), hipMemcpyHostToDevice,
-                                 c->stream));
-        VR_HIP(c, hipStreamSynchronize(c->stream));
-        c->tf[slot].opacity = c->tf_opacity[slot];
+        c->tf[slot].opacity = (const float*)g.d;
         c->tf[slot].res_o = (int)R;
         int z = -1;
         c->tf_opacity_finite[slot] = all_finite(table, (int)R);
@@ -1506,11 +1646,123 @@ static int tf_upload_one(vr_ctx* c, int slot, const float* table, uint32_t R, bo
             while (z + 1 < (int)R && table[z + 1] == 0.0f) ++z;
         c->tf_zero_prefix[slot] = z;
     }
+}
+
+static int tf_upload_one(vr_ctx* c, int slot, const float* table, uint32_t R, bool is_color)
+{
+    if (!c) return VR_ERR_INVALID_ARG;
+    if (const int rc = tf_check(c, slot, table, R, "vr_tf_upload")) return rc;
+    VR_HIP(c, hipSetDevice(c->device));
+    VR_HIP(c, hipDeviceSynchronize());  // asynchronous renders on the caller's streams may still read the table
+    drained(c);
+    const int comps = is_color ? 4 : 1;
+    GenBuf& g = c->tf_buf[slot][is_color ? 1 : 0][c->tf_cur[slot][is_color ? 1 : 0]];
+    if (is_color) {
+        c->tf[slot].color = nullptr;
+        c->tf[slot].res_c = 0;
+    } else {
+        c->tf[slot].opacity = nullptr;
+        c->tf[slot].res_o = 0;
+    }
+    if (const int rc = grow(c, &g.d, &g.cap, ((size_t)R + 2) * comps * sizeof(float), true)) return rc;
+    // device layout (DevTF): the first and the last texel once more at either end
+    float* d = (float*)g.d;
+    const size_t texel = comps * sizeof(float);
+    VR_HIP(c, hipMemcpyAsync(d + comps, table, R * texel, hipMemcpyHostToDevice, c->stream));
+    VR_HIP(c, hipMemcpyAsync(d, table, texel, hipMemcpyHostToDevice, c->stream));
+    VR_HIP(c, hipMemcpyAsync(d + ((size_t)R + 1) * comps, table + comps * ((size_t)R - 1), texel, hipMemcpyHostToDevice, c->stream));
+    VR_HIP(c, hipStreamSynchronize(c->stream));
+    g.written();
+    tf_set_current(c, slot, table, R, is_color);
+    return VR_OK;
+}
+
+// An asynchronous opacity edit of slot 0 that moves the zero prefix or changes the resolution: the field in use is rebuilt on the edit's
+// stream into its next generation, for the records it was built from -- unless it is stale anyway (a volume changed, no field yet): then
+// the next skipping launch rebuilds it as before.  A failure here leaves it to that launch as well.
+static void rebuild_field_async(vr_ctx* c, hipStream_t s)
+{
+    const int z = c->tf_zero_prefix[0], res = c->tf[0].res_o;
+    if (!c->brick_dist || (c->dist_z == z && c->dist_res == res) || c->dist_epoch != c->brick_epoch) return;
+    if (c->dist_rgb ? (c->merged_stale || c->dist_records != (const void*)c->merged_bricks) : c->dist_records != (const void*)c->vol_bricks[0])
+        return;
+    const int b = (c->field_cur + 1) % kGen;
+    GenBuf& g = c->field[b];
+    const size_t nb = (size_t)c->dist_bn[0] * c->dist_bn[1] * c->dist_bn[2];
+    const bool fresh = nb > g.cap;
+    if (grow(c, &g.d, &g.cap, nb, false) != VR_OK || grow(c, (void**)&c->dist_tmp, &c->tmp_cap, nb, false) != VR_OK ||
+        (!fresh && reuse_wait(c, s, g) != VR_OK) ||
+        build_field(c, s, (const float2*)c->dist_records, c->dist_bn, c->dist_rgb, z, res, (unsigned char*)g.d, b, c->skip_gen + 1) != VR_OK) {
+        (void)hipGetLastError();
+        return;
+    }
+    ++c->skip_gen;
+    g.written();
+    c->field_cur = b;
+    c->brick_dist = (unsigned char*)g.d;
+    c->skip_pending = true;
+    c->dist_z = z;
+    c->dist_res = res;
+}
+
+// vr_tf_upload_opacity_async / _color_async: the table into pinned staging (DevTF layout), one copy on `s` into the next generation
+// behind the last launch that read it, the host state as the synchronous upload sets it; then edit_ev behind it all.
+static int tf_upload_async(vr_ctx* c, int slot, const float* table, uint32_t R, bool is_color, void* stream)
+{
+    if (!c) return VR_ERR_INVALID_ARG;
+    if (const int rc = tf_check(c, slot, table, R, is_color ? "vr_tf_upload_color_async" : "vr_tf_upload_opacity_async")) return rc;
+    VR_HIP(c, hipSetDevice(c->device));
+    (void)hipGetLastError();
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const int comps = is_color ? 4 : 1, kind = is_color ? 1 : 0;
+    const size_t texel = comps * sizeof(float), bytes = ((size_t)R + 2) * texel;
+    vr_ctx::Stage& st = c->stage[c->stage_next % kStage];
+    if (st.used) VR_HIP(c, hipEventSynchronize(st.done));  // (the one host wait: kStage edits are still being copied)
+    st.used = false;
+    if (bytes > st.cap) {
+        if (st.h) c->retired_host.push_back(st.h);
+        st.h = nullptr;
+        st.cap = 0;
+        VR_HIP(c, hipHostMalloc(&st.h, bytes, hipHostMallocDefault));
+        st.cap = bytes;
+    }
+    float* h = (float*)st.h;
+    std::memcpy(h + comps, table, R * texel);
+    std::memcpy(h, table, texel);
+    std::memcpy(h + ((size_t)R + 1) * comps, table + comps * ((size_t)R - 1), texel);
+    // behind the edit before it, whatever its stream
+    if (c->edit_gen > c->drained_gen && s != c->edit_stream) VR_HIP(c, hipStreamWaitEvent(s, c->edit_ev, 0));
+    const int b = (c->tf_cur[slot][kind] + 1) % kGen;
+    GenBuf& g = c->tf_buf[slot][kind][b];
+    if (bytes > g.cap) {
+        if (const int rc = grow(c, &g.d, &g.cap, bytes, false)) return rc;
+    } else if (const int rc = reuse_wait(c, s, g)) {
+        return rc;
+    }
+    VR_HIP(c, hipMemcpyAsync(g.d, h, bytes, hipMemcpyHostToDevice, s));
+    VR_HIP(c, hipEventRecord(st.done, s));
+    st.used = true;
+    ++c->stage_next;
+    g.written();
+    c->tf_cur[slot][kind] = b;
+    tf_set_current(c, slot, table, R, is_color);
+    if (!is_color && slot == 0) rebuild_field_async(c, s);
+    VR_HIP(c, hipEventRecord(c->edit_ev, s));
+    c->edit_stream = s;
+    ++c->edit_gen;
     return VR_OK;
 }
 
 int vr_tf_upload_opacity(vr_ctx* c, int slot, const float* opacity, uint32_t R) { return tf_upload_one(c, slot, opacity, R, false); }
 int vr_tf_upload_color(vr_ctx* c, int slot, const float* color_rgba, uint32_t R) { return tf_upload_one(c, slot, color_rgba, R, true); }
+int vr_tf_upload_opacity_async(vr_ctx* c, int slot, const float* opacity, uint32_t R, void* stream)
+{
+    return tf_upload_async(c, slot, opacity, R, false, stream);
+}
+int vr_tf_upload_color_async(vr_ctx* c, int slot, const float* color_rgba, uint32_t R, void* stream)
+{
+    return tf_upload_async(c, slot, color_rgba, R, true, stream);
+}
 
 int vr_tf_upload(vr_ctx* c, int slot, const float* opacity, const float* color_rgba, uint32_t R)
 {
@@ -1821,6 +2073,46 @@ int vr_last_kernel_flavour(vr_ctx* c)
 {
     if (!c) return VR_ERR_INVALID_ARG;
     return c->last_flavour;
+}
+
+int vr_skip_field(vr_ctx* c, int variant, uint8_t* dist, size_t capacity, int dims[3], int box[6], uint64_t* active)
+{
+    if (!c) return VR_ERR_INVALID_ARG;
+    if (variant < 0 || variant >= VR_VARIANT_COUNT) return fail(c, VR_ERR_INVALID_ARG, "vr_skip_field: bad variant");
+    if (capacity > 0 && !dist) return fail(c, VR_ERR_INVALID_ARG, "vr_skip_field: dist is NULL");
+    int nvol, ntf;
+    variant_needs(variant, &nvol, &ntf);
+    for (int i = 0; i < nvol; ++i)
+        if (!c->vol[i].data) return fail(c, VR_ERR_NOT_READY, "vr_skip_field: volume slot " + std::to_string(i) + " is empty");
+    for (int i = 0; i < ntf; ++i)
+        if (!c->tf[i].opacity || !c->tf[i].color) return fail(c, VR_ERR_NOT_READY, "vr_skip_field: TF slot " + std::to_string(i) + " is empty");
+    VR_HIP(c, hipSetDevice(c->device));
+    VR_HIP(c, hipDeviceSynchronize());
+    drained(c);
+    (void)hipGetLastError();
+    const Eligibility E = eligibility(c, 0, variant, 1, 0, 1, false, nullptr);
+    if (!E.can_skip) return fail(c, VR_ERR_NOT_READY, "vr_skip_field: launches of this variant do not skip empty space now");
+    MarchParams P;
+    std::memset(&P, 0, sizeof P);
+    if (const int rc = prepare_skip(c, variant, c->stream, P)) return rc;
+    VR_HIP(c, hipStreamSynchronize(c->stream));
+    const float bs[3] = {P.bsx, P.bsy, P.bsz};
+    adopt_skip(c, bs);
+    if (c->skip_pending) return fail(c, VR_ERR_HIP, "vr_skip_field: the field's count and box did not arrive");
+    const size_t n = (size_t)c->dist_bn[0] * c->dist_bn[1] * c->dist_bn[2];
+    if (capacity > 0) VR_HIP(c, hipMemcpy(dist, c->brick_dist, capacity < n ? capacity : n, hipMemcpyDeviceToHost));
+    if (dims)
+        for (int a = 0; a < 3; ++a) dims[a] = c->dist_bn[a];
+    if (box)
+        for (int a = 0; a < 6; ++a) box[a] = c->skip_box[a];
+    if (active) *active = c->skip_active;
+    return (int)n;
+}
+
+int64_t vr_unbounded_box_launches(vr_ctx* c)
+{
+    if (!c) return VR_ERR_INVALID_ARG;
+    return c->unbounded_launches;
 }
 
 // Event-timed span of one 150 us single-wavefront spin on a and, if b is given, a second one on b right behind it.

@@ -25,7 +25,17 @@ constexpr float kBrickHalf = 0.5f / (float)kBrickCells;   // half a cell in bric
 #ifndef VR_DIST_MAX
 #define VR_DIST_MAX 128
 #endif
-constexpr int kDistMax = VR_DIST_MAX;  // cap of the brick distance field (one dilation pass per value when the field is rebuilt; < 255)
+constexpr int kDistMax = VR_DIST_MAX;  // cap of the brick distance field
+// (the builder's x pass sees 128 bricks to either side of a wavefront's 64, and its y / z tiles take 2 x (kDistMax - 1) rows of halo)
+static_assert(kDistMax >= 2 && kDistMax <= 128, "the distance-field builder (vr_kernels.h) is exact for caps up to 128");
+
+// What a distance-field build reports to the host (pinned memory, written by its last workgroup): the active bricks and their box
+// (brick coordinates, inclusive; hi < 0 if none).  `gen` is written last: the values belong to build `gen` once it reads so.
+struct SkipSummary {
+    unsigned long long gen;
+    unsigned long long count;
+    int box[6];
+};
 // Storage bricks of the bricked volume copy (DevVolume::bricked): 2^S voxels per axis, S = 2 (4 x 4 x 4 = 1 KiB of vec4 voxels)
 // by default; -DVR_VOX_BRICK_SHIFT=1 / 3 rebuilds with 2^3- / 8^3-voxel bricks for A/B (tools/run_r3l.sh).
 #ifndef VR_VOX_BRICK_SHIFT
