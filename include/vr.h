@@ -60,7 +60,22 @@ typedef enum vr_variant {
      * trilinear density samples at +-stepSize along the uvw axes, negated and normalised (zero length -> 0), instead of
      * the pre-computed .rgb of the voxels.  Slots and light as LIGHT; only the density plane of the volume is read.  */
     VR_VARIANT_LIGHT_INSHADER = 7,
-    VR_VARIANT_COUNT = 8
+    /* Intensity projections of volume slot 0 through TF slot 0 (no shader of the reference; csrc/vr_proj.h).  Sample
+     * positions are exactly BASIC's march (BasicVolumeApp.wgsl fs_main): the same start, direction, stepsCount, step size,
+     * variable-step toggle, jitter and repeated rounded additions p += step; fragmentMode 1-4 return what BASIC returns.
+     * Only the n samples that pass IsInSampleCoords (the clip box) count, each d = textureSample(vol0, linear, p).a with
+     * BASIC's arithmetic in either vr_set_arithmetic mode; no opacity cut-off.
+     *   MIP:     m = -inf, then if (d > m) m = d          (NaN samples are ignored)
+     *   MINIP:   m = +inf, then if (d < m) m = d          (NaN samples are ignored)
+     *   AVERAGE: s = +0.0f, then s = s + d in step order (f32), v = s / (float)n   (NaN propagates)
+     * n == 0: the pixel is (0,0,0,0).  Otherwise v goes through TF slot 0 with BASIC's lookup (linear, clamp-to-edge) and the
+     * fragment is FrontToBackBlend((c.rgb, o), dst = 0) in the blend's own arithmetic: (c.r o, c.g o, c.b o, o), a -0 made +0.
+     * Counters: composited = sum of n, covered = pixels with n > 0, fetched = samples whose corners were loaded.  The output
+     * is bit-identical across kernel forms, layouts, launch shapes and skipping on / off.                              */
+    VR_VARIANT_MIP = 8,
+    VR_VARIANT_MINIP = 9,
+    VR_VARIANT_AVERAGE = 10,
+    VR_VARIANT_COUNT = 11
 } vr_variant;
 
 #define VR_MAX_VOLUMES 3
@@ -73,8 +88,9 @@ typedef enum vr_variant {
  *   THREE_FILES   : 0 = CT, 1 = RT, 2 = mask (bound, never sampled) (ThreeFilesApp.wgsl:50-52)
  *   MULTI_CTRT    : 0 = CT, 1 = RT                  (MultiCTRTApp.wgsl:50-51)
  *   TF_CALIB      : 0 = CT, 1 = mask                (TFCalibrationApp.wgsl:40-41)
+ *   MIP / MINIP / AVERAGE : 0 = volume (as BASIC)
  * TF slots = the order of the (opacity, colour) texture_1d pairs:
- *   single-TF scenes: 0;  two-TF scenes: 0 = CT pair, 1 = RT pair (VolumeMaskApp.wgsl:43-46).
+ *   single-TF scenes (and the projections): 0;  two-TF scenes: 0 = CT pair, 1 = RT pair (VolumeMaskApp.wgsl:43-46).
  */
 
 /*
@@ -362,7 +378,13 @@ int vr_last_block_trace(vr_ctx* ctx, uint64_t* out, int capacity);
  *      the shaders that sample one volume (lit, unlit, in-shader gradient) on the bricked copy, launches of any number of frames;
  *      else it runs as 6
  *   15  the voxels of a packet's next four steps in an LDS tile filled by LDS-DMA (csrc/vr_lt.h): lit shader, launches of
- *       one frame (other launches run 6); never picked by the default -- slower than 17 / 16 wherever measured            */
+ *       one frame (other launches run 6); never picked by the default -- slower than 17 / 16 wherever measured
+ * The projections (MIP / MINIP / AVERAGE) have forms of their own, reported by vr_last_kernel_flavour and never measured against
+ * each other (vr_kernel_choice reports 0 candidates after a projection launch):
+ *   19  march_proj_kernel with exact skipping (csrc/vr_proj.h): a step whose brick cannot change the result loads nothing
+ *       (MIP: brick max <= m, MINIP: brick min >= m, AVERAGE: every voxel of the brick +-0), and MIP / MINIP stop loading once
+ *       m has reached the volume's maximum / minimum.  Flavour 0 runs as 19, and so does every other flavour but 1.
+ *   20  march_proj_kernel without skipping: every counted sample is fetched.  Flavour 1 runs as 20.                    */
 int vr_set_kernel_flavour(vr_ctx* ctx, int flavour);
 
 /* What the default's measured choice (flavour 0) knows about the launch shape it was asked for last: the candidates' flavours, the

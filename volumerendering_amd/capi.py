@@ -21,7 +21,9 @@ VR_ERR_UNSUPPORTED = -4
 VR_ERR_OOM = -5
 
 BASIC, LIGHT, VOLUME_MASK, THREE_FILES, MULTI_CTRT, TF_CALIB, ILLUSTRATIVE, LIGHT_INSHADER = range(8)
-VARIANT_NAMES = ["BASIC", "LIGHT", "VOLUME_MASK", "THREE_FILES", "MULTI_CTRT", "TF_CALIB", "ILLUSTRATIVE", "LIGHT_INSHADER"]
+MIP, MINIP, AVERAGE = 8, 9, 10  # intensity projections of volume slot 0 (include/vr.h)
+VARIANT_NAMES = ["BASIC", "LIGHT", "VOLUME_MASK", "THREE_FILES", "MULTI_CTRT", "TF_CALIB", "ILLUSTRATIVE", "LIGHT_INSHADER",
+                 "MIP", "MINIP", "AVERAGE"]
 TILE = 64
 ARITH_SEPARATE, ARITH_FUSED = 0, 1
 

@@ -79,6 +79,16 @@ private:
     int m_TfRes;
 };
 
+// Intensity projections (VR_VARIANT_MIP / MINIP / AVERAGE; no scene of the reference): BasicVolumeApp's volume, preparation and
+// tables, drawn with the projection `mode` instead of the unlit shader.
+class ProjectionApp : public BasicVolumeApp {
+public:
+    ProjectionApp(VolumePtr ct, int mode, int tfResolution = 256) : BasicVolumeApp(std::move(ct), tfResolution), m_Mode(mode) {}
+    int Variant() const override { return m_Mode; }
+private:
+    int m_Mode;
+};
+
 // App/src/miniapps/BasicVolLightApp.cpp:12-51: normalise -> gradient -> AverageGradient(5) (no-op), TF 4096,
 // light (0,5,0) / ambient .1 / diffuse 1 (BasicVolLightApp.h:32-37).
 class BasicVolLightApp : public MiniApp {

@@ -315,6 +315,9 @@ int vrh_app_start(void* a, int variant, void* v0, void* v1, void* v2, int tf_res
             break;
         }
         case VR_VARIANT_TF_CALIB: scene = std::make_unique<TFCalibrationApp>(vol(v0), vol(v1), vol(v2)); break;
+        case VR_VARIANT_MIP:
+        case VR_VARIANT_MINIP:
+        case VR_VARIANT_AVERAGE: scene = std::make_unique<ProjectionApp>(vol(v0), variant, tf_res > 0 ? tf_res : 256); break;
         default: return VR_ERR_INVALID_ARG;
         }
         return app->OnStart(std::move(scene));

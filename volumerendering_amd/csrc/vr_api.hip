@@ -187,6 +187,19 @@ struct vr_ctx {
                               // onto small volumes by the tests; 0 = what the hardware reaches, just below 4 GiB)
     double active_fraction = 1.0;  // share of bricks that are not inert, of the distance field in use
     float abox[6] = {-3.0e38f, -3.0e38f, -3.0e38f, 3.0e38f, 3.0e38f, 3.0e38f};  // uvw box around the active bricks of that field (MarchParams::abox)
+    // Intensity projections (vr_proj.h): (min, max) of volume 0 per empty-space brick and over the whole volume, rebuilt on the launch's
+    // stream by the first skipping projection launch after a volume change (proj_epoch = the brick_epoch they were built at).  Launches on
+    // other streams wait once for the event behind the build (proj_seen), none after a draining call (proj_pending).
+    float2* proj_rec = nullptr;
+    size_t proj_rec_cap = 0;  // bytes
+    float2* proj_range = nullptr;
+    unsigned long long proj_epoch = ~0ull;
+    hipEvent_t proj_ev = nullptr;
+    hipStream_t proj_stream = nullptr;
+    bool proj_pending = false;
+    hipStream_t proj_seen[kEditSeen] = {};
+    int proj_seen_next = 0;
+    bool last_proj = false;  // the last launch was a projection (vr_kernel_choice reports no candidates)
     std::string err;
 };
 
@@ -229,13 +242,18 @@ bool is_identity(const float* m)
     return true;
 }
 
+bool is_projection(int variant) { return variant == VR_VARIANT_MIP || variant == VR_VARIANT_MINIP || variant == VR_VARIANT_AVERAGE; }
+
 // volumes / TF pairs each variant samples (vr.h slot tables)
 void variant_needs(int variant, int* nvol, int* ntf)
 {
     switch (variant) {
     case VR_VARIANT_BASIC:
     case VR_VARIANT_LIGHT:
-    case VR_VARIANT_LIGHT_INSHADER: *nvol = 1; *ntf = 1; break;
+    case VR_VARIANT_LIGHT_INSHADER:
+    case VR_VARIANT_MIP:
+    case VR_VARIANT_MINIP:
+    case VR_VARIANT_AVERAGE: *nvol = 1; *ntf = 1; break;
     case VR_VARIANT_VOLUME_MASK: *nvol = 3; *ntf = 2; break;
     case VR_VARIANT_THREE_FILES: *nvol = 2; *ntf = 2; break;  // the mask (slot 2) is bound but never sampled
     case VR_VARIANT_MULTI_CTRT: *nvol = 2; *ntf = 2; break;
@@ -662,6 +680,7 @@ void drained(vr_ctx* c)
     c->retired_dev.clear();
     c->retired_host.clear();
     c->drained_gen = c->edit_gen;
+    c->proj_pending = false;
 }
 
 // Before `s` rewrites generation b: every launch that read it must have finished, whatever its stream (launches on different
@@ -832,9 +851,63 @@ int prepare_skip(vr_ctx* c, int variant, hipStream_t s, MarchParams& P)
     return VR_OK;
 }
 
+// The skipping projection (flavour 19): fills P's brick fields with volume 0's range records, (re)builds them and the whole volume's range
+// on `s` when a volume changed since they were built (no host wait), and orders a launch on another stream behind that build once.
+// Returns the whole volume's range (device), or nullptr after a failure (c->err says why).
+const float2* prepare_proj(vr_ctx* c, hipStream_t s, MarchParams& P)
+{
+    const DevVolume& v = c->vol[0];
+    P.skip_vol = 0;
+    P.bnx = skip_bricks(v.nx);
+    P.bny = skip_bricks(v.ny);
+    P.bnz = skip_bricks(v.nz);
+    P.bsx = (float)v.nx * kBrickInv;
+    P.bsy = (float)v.ny * kBrickInv;
+    P.bsz = (float)v.nz * kBrickInv;
+    const size_t nb = (size_t)P.bnx * P.bny * P.bnz;
+    if (c->proj_epoch != c->brick_epoch || !c->proj_rec || !c->proj_range) {
+        // (a volume change drained the device: nothing in flight reads the records; a smaller buffer is retired all the same)
+        if (grow(c, (void**)&c->proj_rec, &c->proj_rec_cap, nb * sizeof(float2), false)) return nullptr;
+        if (!c->proj_range && hipMalloc(&c->proj_range, sizeof(float2)) != hipSuccess) {
+            c->proj_range = nullptr;
+            fail(c, VR_ERR_OOM, "vr_render: no memory for the projection's volume range");
+            return nullptr;
+        }
+        if (!c->proj_ev && hipEventCreateWithFlags(&c->proj_ev, hipEventDisableTiming) != hipSuccess) {
+            c->proj_ev = nullptr;
+            fail(c, VR_ERR_HIP, "vr_render: hipEventCreateWithFlags failed");
+            return nullptr;
+        }
+        hipLaunchKernelGGL(brick_range_kernel, dim3((unsigned)nb), dim3(64), 0, s, v.data, v.nx, v.ny, v.nz, P.bnx, P.bny, c->proj_rec);
+        hipLaunchKernelGGL(range_reduce_kernel, dim3(1), dim3(1024), 0, s, (const float2*)c->proj_rec, (int)nb, c->proj_range);
+        if (hipGetLastError() != hipSuccess || hipEventRecord(c->proj_ev, s) != hipSuccess) {
+            fail(c, VR_ERR_HIP, "vr_render: the projection's brick ranges could not be enqueued");
+            return nullptr;
+        }
+        c->proj_epoch = c->brick_epoch;
+        c->proj_stream = s;
+        c->proj_pending = true;
+        for (auto& x : c->proj_seen) x = nullptr;
+    } else if (c->proj_pending && s != c->proj_stream) {
+        bool seen = false;
+        for (auto x : c->proj_seen) seen = seen || x == s;
+        if (!seen) {
+            if (hipStreamWaitEvent(s, c->proj_ev, 0) != hipSuccess) {
+                fail(c, VR_ERR_HIP, "vr_render: hipStreamWaitEvent failed");
+                return nullptr;
+            }
+            c->proj_seen[c->proj_seen_next++ % kEditSeen] = s;
+        }
+    }
+    P.bricks = c->proj_rec;
+    return c->proj_range;
+}
+
 // The kernel form ("flavour") a launch runs: `fl` is the one asked for (vr_set_kernel_flavour, else VR_EXP_FLAVOUR), 0 = the default.
 int choose_flavour(vr_ctx* c, int fl, int variant, int n_frames, int rank, int world, bool packed, const Eligibility& E)
 {
+    // the projections: 1 asks for the form without skipping (20), everything else runs as the skipping one (19); nothing is measured
+    if (is_projection(variant)) return fl == 1 ? 20 : 19;
     const bool auto_choice = fl == 0;
     const double rays = rays_per_lane(c, rank, world, c->frames_in_flight * n_frames);
     const bool short_chains = E.chain_known != 0 && E.chain_known - 1 < 128;
@@ -939,6 +1012,8 @@ KernelForm kernel_form(int fl, int variant)
     case 16: return {D::kP2, 0, false, false, false, 512u};
     case 17: return {D::kP2, 0, false, true, false, variant == VR_VARIANT_BASIC ? 1024u : 768u};
     case 18: return {D::kPlain, 0, false, false, true, 0u};
+    case 19:
+    case 20: return {D::kProj, 0, false, false, false, 0u};
     default: return {D::kPlain, 0, false, false, false, 0u};  // 1, 6
     }
 }
@@ -1084,6 +1159,12 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
     const int fl = choose_flavour(c, requested, variant, n_frames, rank, world, packed, E);
     c->last_flavour = fl;
     const KernelForm form = kernel_form(fl, variant);
+    c->last_proj = form.family == LaunchDesc::kProj;
+    const float2* vrange = nullptr;
+    if (fl == 19) {
+        vrange = prepare_proj(c, s, P);
+        if (!vrange) return VR_ERR_HIP;
+    }
 
     if (c->layout_mode == 0) use_bricked_copies(c, P);
     if (form.lut && P.vol[0].bricked) P.vol[0].lut = 1;  // (march_kernel fills the tables; every fetch of volume 0 goes through them)
@@ -1148,6 +1229,8 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
         L.lds_bytes = P.vol[0].lut ? E.lut_lds : 0u;
         L.grid = dim3(grid.x * (unsigned)n_frames);
         L.block = block;
+        L.vrange = vrange;
+        L.proj_skip = vrange != nullptr;
         if (pw) {
             // persistent wavefronts: `grid` stays the number of LOGICAL blocks (records, launch order); the launch itself is one
             // workgroup of form.pw_threads per CU (fewer when there are fewer packets), TF slot 0 in LDS when it fits
@@ -1531,6 +1614,9 @@ void vr_destroy(vr_ctx* c)
         if (c->vol_bdens[i]) (void)hipFree(c->vol_bdens[i]);
     }
     if (c->merged_bricks) (void)hipFree(c->merged_bricks);
+    if (c->proj_rec) (void)hipFree(c->proj_rec);
+    if (c->proj_range) (void)hipFree(c->proj_range);
+    if (c->proj_ev) (void)hipEventDestroy(c->proj_ev);
     for (auto& g : c->field)
         if (g.d) (void)hipFree(g.d);
     if (c->dist_tmp) (void)hipFree(c->dist_tmp);
@@ -2220,6 +2306,10 @@ int vr_volume_layout(vr_ctx* c, int slot, int* flags)
 int vr_kernel_choice(vr_ctx* c, int flavours[6], float ms_per_launch[6], int* chosen)
 {
     if (!c) return VR_ERR_INVALID_ARG;
+    if (c->last_proj) {  // (the projections' forms are never measured)
+        if (chosen) *chosen = -1;
+        return 0;
+    }
     const vr_ctx::Tune* t = nullptr;
     for (const auto& e : c->tune)
         if (e.key != 0 && e.used != 0 && (!t || e.used > t->used)) t = &e;

@@ -149,10 +149,11 @@ struct PwQueue {
 // What enqueue_render decided about one march launch; handed to launch_march of the arithmetic mode's translation unit
 // (vr_launch.h: namespace vr = separately rounded multiply-adds, namespace vrf = fused).  Host only.
 struct LaunchDesc {
-    enum Family { kPlain, kDp, kPw, kP2, kLt };
+    enum Family { kPlain, kDp, kPw, kP2, kLt, kProj };
     int variant;      // vr_variant
     Family family;    // march_kernel, march_dp_kernel, march_pw_kernel (persistent wavefronts: grid = workgroups, the packets come
-                      // from `queue`), march_p2_kernel (the same, corner loads two steps ahead), march_lt_kernel (LDS tiles, lit shader)
+                      // from `queue`), march_p2_kernel (the same, corner loads two steps ahead), march_lt_kernel (LDS tiles, lit shader),
+                      // march_proj_kernel (vr_proj.h: the intensity projections)
     bool off32;       // every bound volume < 4 GiB: 32-bit byte offsets
     int lanes;        // kDp: lanes per ray (2 / 4)
     bool pipe;        // kDp / kPw: the next round's / step's corner loads software-pipelined
@@ -162,6 +163,8 @@ struct LaunchDesc {
     unsigned lds_bytes;
     PwQueue queue;
     dim3 grid, block;
+    const float2* vrange;  // kProj: (min, max) of volume 0 (vr_proj.h); with `proj_skip` the brick records are MarchParams::bricks
+    bool proj_skip;        // kProj: the skipping form (march_proj_kernel<.., SKIP = true, ..>)
 };
 
 }  // namespace vr

@@ -18,6 +18,8 @@
 // is part of the shipped library: slower than the two-steps-ahead kernel everywhere measured, selectable with
 // vr_set_kernel_flavour(15) and tested on every box, not a candidate of the measured choice.
 #include "vr_lt.h"
+// Intensity projections (MIP / MinIP / AIP of volume slot 0; flavours 19 and 20)
+#include "vr_proj.h"
 
 #include <type_traits>
 
@@ -93,8 +95,27 @@ void launch_p2(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
     }, V == V_VOLUME_MASK || (B.frame[0].brick_dist && L.p2_skip), L.p2_win, B.n_frames > 1);
 }
 
+// the projections: mode x skipping x addressing x frames per launch
+void launch_proj(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
+{
+    const int mode = L.variant == VR_VARIANT_MIP ? kProjMax : (L.variant == VR_VARIANT_MINIP ? kProjMin : kProjAvg);
+    auto launch = [&](auto md) {
+        constexpr int M = decltype(md)::value;
+        with_flags([&](auto S, auto O, auto BT) {
+            hipLaunchKernelGGL((march_proj_kernel<M, O, S, BT>), L.grid, L.block, 0, s, B, L.vrange);
+        }, L.proj_skip, L.off32, B.n_frames > 1);
+    };
+    if (mode == kProjMax) launch(std::integral_constant<int, kProjMax>{});
+    else if (mode == kProjMin) launch(std::integral_constant<int, kProjMin>{});
+    else launch(std::integral_constant<int, kProjAvg>{});
+}
+
 void launch_march(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
 {
+    if (L.family == LaunchDesc::kProj) {
+        launch_proj(L, s, B);
+        return;
+    }
     if (L.family == LaunchDesc::kLt) {  // LDS tiles (vr_lt.h): lit shader
         with_flags([&](auto O, auto S) { hipLaunchKernelGGL((march_lt_kernel<O, S>), L.grid, L.block, 0, s, B); },
                    L.off32, B.frame[0].brick_dist != nullptr);
