@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Gsamples/s + fps of the volume ray-march compositing loop (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 N = 1: this process.  N > 1: one process per GPU -- under torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE in the
 environment) or, when those are absent, spawned by this script itself BEFORE anything touches a GPU (`launch_ranks`).
@@ -18,9 +18,14 @@ rotated g times by Camera::Rotate(2 px, 0) -- yaw + g * 0.01 rad, what the refer
 frames (App/src/Application.cpp:381-457 -> App/src/Camera.cpp:146-152): no two frames of a leg, and no two frames of one
 batched launch, share uniforms.  Every leg starts at g = 0, so the legs render the same sequence.
 
+A plain run does what the headline needs and nothing more: the scene, the untimed count of what every camera composites, the
+`serial` leg below, --dump-outputs, and the JSON line (contract fields, `config`, `serial`).  --full runs everything else this
+docstring names as well, in the same process after the serial leg: the other legs, sync_8d, full_turn, arith_ab, the roofline's
+counter passes, the regime table, the oracle's parity and cpu_baseline (tens of seconds; the multi-rank stage timeline too).
+
 Legs, W warm-up + exactly K timed frames each, bracketed by barrier + device synchronise:
     serial      one frame at a time (the reference's interactive loop, Application.cpp:332-379) -- SURVEY 8d's t_frame.
-                `value` / `ms_per_step` / `fps` ARE THIS LEG'S.
+                `value` / `ms_per_step` / `fps` ARE THIS LEG'S.  The only leg of a plain run; the others need --full.
     serial_with_present
                 the same + the output merge into BGRA8 (vr_present_async, PipelineBuilder.cpp:142-154) behind every frame
     pipelined_one_frame_per_launch
@@ -29,7 +34,7 @@ Legs, W warm-up + exactly K timed frames each, bracketed by barrier + device syn
                 different cameras per launch: throughput at eight frames of delay, reported beside the headline
 value = composited samples of the K timed frames (counted per camera in an untimed pass) / wall time of the leg.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  Besides the contract fields, with --full it carries
     roofline      HBM roofline of the march kernel from MEASURED fabric bytes (rocprofv3 PMC passes run by this script
                   on the same turntable: FETCH_SIZE x 2 + WRITE_SIZE, MI355X_MICROARCH.md) over the median HIP-event kernel
                   time of the serial leg; `turntable_vs_identical` has the same counters for identical frames
@@ -392,6 +397,9 @@ def main():
     ap.add_argument("--workload", default="C3", choices=["C1", "C2", "C3", "C4", "C5"])
     ap.add_argument("--tf", default="default", choices=["default", "thin", "prefix", "zero"])
     ap.add_argument("--air", default="exact0", choices=["exact0", "noisy"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's serial leg, everything else: the other legs, sync_8d, full_turn, arith_ab, counter "
+                         "passes / roofline, regimes, oracle parity and cpu_baseline (the --no-* switches below trim it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-live-pmc", action="store_true", help="skip the rocprofv3 counter passes (roofline.traffic = null)")
     ap.add_argument("--no-regimes", action="store_true", help="skip the air x TF regime table (C3)")
@@ -520,9 +528,9 @@ def main():
     if multi and mg is None:
         fpl = 1  # (the gloo rehearsal renders frame by frame)
     batch_frames = [[torch.zeros((H, W, 4), dtype=torch.float32, device="cuda") for _ in range(fpl)] for _ in range(max_flight)] \
-        if (fpl > 1 and not multi) else []
+        if (fpl > 1 and not multi and args.full) else []
 
-    if mg is not None and fpl > 1:  # size the loop's buffer sets for fpl frames per launch outside every timed region
+    if mg is not None and fpl > 1 and args.full:  # size the loop's buffer sets for fpl frames per launch outside every timed region
         with stdout_to_stderr():
             for _ in range(max_flight):  # (every buffer set: the final comparison reads all of their frames)
                 mg.frames_async(variant, us[:fpl])
@@ -675,11 +683,79 @@ def main():
                 "kernel_ms_p10_p90": [round(float(np.percentile(kt, 10)), 4), round(float(np.percentile(kt, 90)), 4)] if len(kt) else None,
                 "kernel_events": int(len(kt))}
 
+    part_world = max(world, share)
+    part = "single GPU" if not multi else f"64x64 image tiles interleaved over {part_world} GPUs + " + \
+        ((mg.backend() + " (C++ frame loop, libvr_mgpu.so)") if mg is not None else "gloo gather through host memory (rehearsal)")
+
+    def run_config(ran, layout_flags, value_is):
+        """The line's `config`: what was rendered, how it was partitioned, which kernel ran."""
+        total_samples, covered, total_fetched = counts[0]
+        return {
+            "workload": f"{args.workload}: ct-phantom-{n} RGBA32F voxels, {W}x{H}, {vname} shader, TF {args.tf}, air {args.air}, "
+                        f"step 1/{round(1 / step_size)} x {steps_count}, camera d=1.2 yaw=.6 pitch=.35 + turntable",
+            "camera": ("every frame with frame 0's camera (--identical-frames)" if args.identical_frames else
+                       "turntable: frame g = the BASELINE camera after g x Camera::Rotate(2 px, 0), yaw + 0.01 rad per frame "
+                       "(App/src/Application.cpp:410-416, App/src/Camera.cpp:146-152); every leg renders frames 0 .. W+K-1; frames of "
+                       "one batched launch have different uniforms"),
+            "partition": part,
+            "value_is": value_is,
+            "composited_samples_frame0": total_samples, "fetched_samples_frame0": total_fetched, "covered_pixels_frame0": covered,
+            "composited_samples_per_frame_min_max": [min(c[0] for c in counts), max(c[0] for c in counts)],
+            "kernel_flavour": args.flavour, "kernel_flavour_resolved": ran,
+            "volume_layout": {0: "bricked copy (4 x 4 x 4 voxel bricks, brick-linear) of the vec4 voxels + density plane",
+                              1: "reference vec4 voxels only, x fastest",
+                              2: "x-fastest density plane, corner gradients derived on the fly" if layout_flags & 4 else "x-fastest vec4 voxels + density plane",
+                              3: "x-fastest vec4 voxels + density plane (round 2's default)"}[args.layout],
+            "arithmetic": args.arith,
+        }
+
+    def contract_fields(serial):
+        return {"metric": "Gsamples/s", "value": serial["value"], "unit": "Gsamples/s", "n_gpus": world,
+                "steps": args.steps, "warmup": args.warmup, "ms_per_step": serial["ms_per_step"], "fps": serial["fps"],
+                "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic"}
+
+    def describe_ranks(cfg):
+        """What a multi-rank run really was: ranks RCCL saw, the device of every rank (collective)."""
+        devs = [None] * world
+        if dist is not None:
+            dist.all_gather_object(devs, {"rank": rank, "device": device_index,
+                                          "name": torch.cuda.get_device_name(device_index), "pid": os.getpid()})
+        cfg["ranks"] = devs
+        cfg["launched_by"] = launched_by
+        if mg is not None:
+            cfg["rccl_nranks"] = mg.comm_count()
+
+    def finish(out):
+        """Closes the multi-rank loop and the process group, prints rank 0's line, closes the scene."""
+        if mg is not None:
+            mg.close()
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        app.close()
+
     # ---- the legs -----------------------------------------------------------------------------------------------------
     dumped = {} if args.dump_outputs else None
     res_serial = timed_leg(1, args.warmup, args.steps, min_events=20, capture=dumped)
     if dumped is not None:
         log(f"[bench] --dump-outputs: {dump_outputs(args.dump_outputs, dumped)} -> {args.dump_outputs}")
+    serial = leg(res_serial, 1, args.steps)
+    serial["kernel_ms_source"] = "first workgroup start .. last workgroup end of each timed launch (100 MHz device clock, from the launch's records)"
+    if not args.full:
+        # the headline alone: the serial leg's line, no further launches (the kernel that ran last is the serial leg's)
+        out = {**contract_fields(serial),
+               "config": run_config(res_serial[4]["ran_last"], ctx.volume_layout(2 if vname == "VOLUME_MASK" else 0),
+                                    "the `serial` leg: ONE FRAME AT A TIME, stream-ordered on one stream (the host enqueues ahead and never "
+                                    "waits inside the timed region), composited samples of the K timed turntable frames / wall time between "
+                                    "barrier + synchronise.  The other legs, sync_8d, full_turn, roofline, regimes, parity and cpu_baseline: "
+                                    "bench.py --full"),
+               "serial": serial}
+        if multi:
+            describe_ranks(out["config"])
+        finish(out)
+        return
     # The legs' launches are timed from their own per-workgroup records (vr_kernel_times' default: two HIP events around
     # every launch cost the frame's stream 11 us, which the one-frame-at-a-time leg would pay).  The roofline's denominator is
     # measured the contract's way: HIP events on the launch stream around each of 20 more one-at-a-time frames, outside the
@@ -774,8 +850,7 @@ def main():
                 gpu_frames.append(frames[b].cpu().numpy())
                 frames_g.append(g)
 
-    serial, over = leg(res_serial, 1, args.steps), leg(res_over, nbuf_over, args.steps)
-    serial["kernel_ms_source"] = "first workgroup start .. last workgroup end of each timed launch (100 MHz device clock, from the launch's records)"
+    over = leg(res_over, nbuf_over, args.steps)
     serial["kernel_ms_hip_events_median"] = round(float(np.median(kt_events)), 4) if len(kt_events) else None
     serial["kernel_ms_hip_events_note"] = "HIP events on the launch stream around 20 further one-at-a-time launches; the roofline's denominator"
     with_present = None
@@ -830,7 +905,6 @@ def main():
         torch.cuda.synchronize()
     kernel_ms = serial["kernel_ms_hip_events_median"] or serial["kernel_ms_median"]
     bs = wl.BYTES_PER_SAMPLE[vname]
-    part_world = max(world, share)
     owned_px = W * H if not multi else ctx.tile_count(rank, part_world) * capi.TILE * capi.TILE
     alg_fetched = my_fetched * bs + 16 * owned_px   # what the kernel's loads ask for (mostly served by L1 / L2)
     alg_composited = my_samples * bs + 16 * owned_px  # SURVEY 8d's figure: every composited sample priced as a fetch
@@ -970,36 +1044,16 @@ def main():
         except Exception:  # noqa: BLE001
             pass
 
-    part = "single GPU" if not multi else f"64x64 image tiles interleaved over {part_world} GPUs + " + \
-        ((mg.backend() + " (C++ frame loop, libvr_mgpu.so)") if mg is not None else "gloo gather through host memory (rehearsal)")
     out = {
-        "metric": "Gsamples/s", "value": serial["value"], "unit": "Gsamples/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": serial["ms_per_step"], "fps": serial["fps"],
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {
-            "workload": f"{args.workload}: ct-phantom-{n} RGBA32F voxels, {W}x{H}, {vname} shader, TF {args.tf}, air {args.air}, "
-                        f"step 1/{round(1 / step_size)} x {steps_count}, camera d=1.2 yaw=.6 pitch=.35 + turntable",
-            "camera": ("every frame with frame 0's camera (--identical-frames)" if args.identical_frames else
-                       "turntable: frame g = the BASELINE camera after g x Camera::Rotate(2 px, 0), yaw + 0.01 rad per frame "
-                       "(App/src/Application.cpp:410-416, App/src/Camera.cpp:146-152); every leg renders frames 0 .. W+K-1; frames of "
-                       "one batched launch have different uniforms"),
-            "partition": part,
-            "value_is": "the `serial` leg: ONE FRAME AT A TIME, stream-ordered on one stream (the host enqueues ahead and never waits inside "
-                        "the timed region), composited samples of the K timed turntable frames / wall time between barrier + synchronise.  "
-                        "SURVEY 8d's t_frame to the letter (median of hipEvent-timed synchronous vr_render calls) is `sync_8d`; every camera "
-                        f"of a 2 pi turn is `full_turn`; the pipelined ({nbuf_over} launches x 1 frame) and batched ({nbuf_over} launches x "
-                        f"{fpl} frames) legs are extras, in `pipelined_one_frame_per_launch` / `overlapped`",
-            "composited_samples_frame0": total_samples, "fetched_samples_frame0": total_fetched, "covered_pixels_frame0": covered,
-            "composited_samples_per_frame_min_max": [min(c[0] for c in counts), max(c[0] for c in counts)],
-            "kernel_flavour": args.flavour, "kernel_flavour_resolved": ran,
-            "volume_layout": {0: "bricked copy (4 x 4 x 4 voxel bricks, brick-linear) of the vec4 voxels + density plane",
-                              1: "reference vec4 voxels only, x fastest",
-                              2: "x-fastest density plane, corner gradients derived on the fly" if layout_flags & 4 else "x-fastest vec4 voxels + density plane",
-                              3: "x-fastest vec4 voxels + density plane (round 2's default)"}[args.layout],
-        },
+        **contract_fields(serial),
+        "config": run_config(ran, layout_flags,
+                             "the `serial` leg: ONE FRAME AT A TIME, stream-ordered on one stream (the host enqueues ahead and never waits inside "
+                             "the timed region), composited samples of the K timed turntable frames / wall time between barrier + synchronise.  "
+                             "SURVEY 8d's t_frame to the letter (median of hipEvent-timed synchronous vr_render calls) is `sync_8d`; every camera "
+                             f"of a 2 pi turn is `full_turn`; the pipelined ({nbuf_over} launches x 1 frame) and batched ({nbuf_over} launches x "
+                             f"{fpl} frames) legs are extras, in `pipelined_one_frame_per_launch` / `overlapped`"),
         "serial": serial, "overlapped": over, "roofline": roofline,
     }
-    out["config"]["arithmetic"] = args.arith
     if sync_8d:
         out["sync_8d"] = sync_8d
     if full_turn:
@@ -1015,14 +1069,8 @@ def main():
                       **{k: v for k, v in pmc.items() if not k.startswith("_")}}
     if multi:
         # what the run really was: ranks RCCL saw, the device of every rank, the stage timeline of rank 0
-        devs = [None] * world
-        if dist is not None:
-            dist.all_gather_object(devs, {"rank": rank, "device": device_index,
-                                          "name": torch.cuda.get_device_name(device_index), "pid": os.getpid()})
-        out["config"]["ranks"] = devs
-        out["config"]["launched_by"] = launched_by
+        describe_ranks(out["config"])
         if mg is not None:
-            out["config"]["rccl_nranks"] = mg.comm_count()
             # stage timeline of this rank (rank 0 prints its own): 20 one-at-a-time frames and 20 batched launches, events on
             out["rank0_stage_timeline"] = stage_timeline(mg, ctx, variant, us, fpl, dist)
 
@@ -1103,14 +1151,7 @@ def main():
         ctx.set_uniforms(u0)
         mg.frame_async(variant)  # (collective: the root's comparison frame above)
         mg.wait()
-    if mg is not None:
-        mg.close()
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    app.close()
+    finish(out)
 
 
 def stage_timeline(mg, ctx, variant, us, fpl, dist):

@@ -4,7 +4,7 @@
 O=gpurun_out/r4a
 mkdir -p $O
 timeout -k 10 120 ./tools/ubench/struct_buffer > $O/struct_buffer.txt 2>&1; echo "struct_buffer rc $?"; cat $O/struct_buffer.txt
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_c3.json 2> $O/bench_c3.err || { tail -5 $O/bench_c3.err; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_c3.json 2> $O/bench_c3.err || { tail -5 $O/bench_c3.err; exit 1; }
 python - <<'PY'
 import json
 d=json.load(open('gpurun_out/r4a/bench_c3.json'))

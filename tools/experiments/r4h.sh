@@ -2,7 +2,7 @@
 # the default (measured choice) on every configuration and leg, and the rank-share rehearsals
 O=gpurun_out/r4h
 mkdir -p $O
-B="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-regimes --no-live-pmc --turn-frames 0"
+B="python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-regimes --no-live-pmc --turn-frames 0"
 for w in C1 C2 C3 C4 C5; do
   timeout -k 10 400 $B --workload $w > $O/bench_$w.json 2> $O/bench_$w.err || { echo "bench $w failed"; tail -5 $O/bench_$w.err; exit 1; }
 done

@@ -3,8 +3,8 @@
 # real RCCL loop with a world of one
 O=gpurun_out/r4o
 mkdir -p $O
-VR_BENCH_DEVICE=0 VR_BENCH_BACKEND=gloo timeout -k 10 400 python bench.py --gpus 2 --steps 6 --warmup 2 --no-cpu-baseline > $O/gloo2.json 2> $O/gloo2.err || { tail -8 $O/gloo2.err; exit 1; }
-VR_BENCH_SELF_GATHER=1 timeout -k 10 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-regimes --no-live-pmc > $O/selfgather.json 2> $O/selfgather.err || { tail -8 $O/selfgather.err; exit 1; }
+VR_BENCH_DEVICE=0 VR_BENCH_BACKEND=gloo timeout -k 10 400 python bench.py --full --gpus 2 --steps 6 --warmup 2 --no-cpu-baseline > $O/gloo2.json 2> $O/gloo2.err || { tail -8 $O/gloo2.err; exit 1; }
+VR_BENCH_SELF_GATHER=1 timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-regimes --no-live-pmc > $O/selfgather.json 2> $O/selfgather.err || { tail -8 $O/selfgather.err; exit 1; }
 python - <<'PY'
 import json
 for n in ('gloo2','selfgather'):

@@ -4,7 +4,7 @@ O=gpurun_out/r4y
 mkdir -p $O
 timeout -k 10 900 python -m pytest tests -x -q -m gpu > $O/tests.txt 2>&1 || { tail -30 $O/tests.txt; exit 1; }
 tail -2 $O/tests.txt
-B="python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-regimes --no-live-pmc --turn-frames 0 --settle 0"
+B="python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-regimes --no-live-pmc --turn-frames 0 --settle 0"
 run() {  # tag
   timeout -k 10 300 $B --flavour 6 > $O/c3_f6_$1.json 2> $O/c3_f6_$1.err || exit 1
   timeout -k 10 300 $B --flavour 18 > $O/c3_f18_$1.json 2> $O/c3_f18_$1.err || exit 1

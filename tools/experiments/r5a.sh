@@ -4,7 +4,7 @@ O=gpurun_out/r5a
 mkdir -p $O
 timeout -k 10 600 python -m pytest tests/test_p2_gpu.py -x -q -m gpu > $O/tests.txt 2>&1 || { tail -30 $O/tests.txt; exit 1; }
 tail -2 $O/tests.txt
-B="python bench.py --workload C5 --steps 20 --warmup 4 --no-cpu-baseline --no-regimes --no-live-pmc --turn-frames 0 --settle 0"
+B="python bench.py --full --workload C5 --steps 20 --warmup 4 --no-cpu-baseline --no-regimes --no-live-pmc --turn-frames 0 --settle 0"
 run() {  # tag
   timeout -k 10 400 $B --flavour 17 > $O/c5_f17_$1.json 2> $O/c5_f17_$1.err || exit 1
   for N in 2 8; do

@@ -2,7 +2,7 @@
 # round 4: the several-frames form of march_p2_kernel for one frame per launch below 4 GiB too?  A/B (-DVR_P2_ALL_BATCH=1)
 O=gpurun_out/r5b
 mkdir -p $O
-B="python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-regimes --no-live-pmc --turn-frames 0 --settle 0"
+B="python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-regimes --no-live-pmc --turn-frames 0 --settle 0"
 run() {  # tag
   timeout -k 10 300 $B --flavour 17 > $O/c3_f17_$1.json 2> $O/c3_f17_$1.err || exit 1
   timeout -k 10 300 $B --flavour 17 --workload C4 > $O/c4_f17_$1.json 2> $O/c4_f17_$1.err || exit 1

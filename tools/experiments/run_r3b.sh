@@ -8,11 +8,11 @@ rc=$?
 tail -3 $O/pytest_pw.txt
 [ $rc -eq 0 ] || exit $rc
 for fl in 6 12; do
-  timeout -k 10 300 python bench.py --steps 50 --warmup 10 --flavour $fl --no-cpu-baseline --no-regimes > $O/bench_c3_f$fl.json 2> $O/bench_c3_f$fl.err || exit 1
-  timeout -k 10 300 python bench.py --steps 30 --warmup 5 --flavour $fl --air noisy --no-cpu-baseline --no-regimes > $O/bench_c3noisy_f$fl.json 2> $O/bench_c3noisy_f$fl.err || exit 1
-  timeout -k 10 300 python bench.py --steps 30 --warmup 5 --flavour $fl --tf thin --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_c3thin_f$fl.json 2> $O/bench_c3thin_f$fl.err || exit 1
-  timeout -k 10 300 python bench.py --workload C2 --steps 50 --warmup 10 --flavour $fl --no-cpu-baseline --no-live-pmc > $O/bench_c2_f$fl.json 2> $O/bench_c2_f$fl.err || exit 1
-  timeout -k 10 300 python bench.py --workload C4 --steps 30 --warmup 5 --flavour $fl --no-cpu-baseline --no-live-pmc > $O/bench_c4_f$fl.json 2> $O/bench_c4_f$fl.err || exit 1
+  timeout -k 10 300 python bench.py --full --steps 50 --warmup 10 --flavour $fl --no-cpu-baseline --no-regimes > $O/bench_c3_f$fl.json 2> $O/bench_c3_f$fl.err || exit 1
+  timeout -k 10 300 python bench.py --full --steps 30 --warmup 5 --flavour $fl --air noisy --no-cpu-baseline --no-regimes > $O/bench_c3noisy_f$fl.json 2> $O/bench_c3noisy_f$fl.err || exit 1
+  timeout -k 10 300 python bench.py --full --steps 30 --warmup 5 --flavour $fl --tf thin --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_c3thin_f$fl.json 2> $O/bench_c3thin_f$fl.err || exit 1
+  timeout -k 10 300 python bench.py --full --workload C2 --steps 50 --warmup 10 --flavour $fl --no-cpu-baseline --no-live-pmc > $O/bench_c2_f$fl.json 2> $O/bench_c2_f$fl.err || exit 1
+  timeout -k 10 300 python bench.py --full --workload C4 --steps 30 --warmup 5 --flavour $fl --no-cpu-baseline --no-live-pmc > $O/bench_c4_f$fl.json 2> $O/bench_c4_f$fl.err || exit 1
 done
 python - <<'PY'
 import json,glob

@@ -8,15 +8,15 @@ rc=$?
 tail -3 $O/pytest_pw.txt
 [ $rc -eq 0 ] || exit $rc
 for fl in 13 12 6; do
-  timeout -k 10 300 python bench.py --steps 50 --warmup 10 --flavour $fl --no-cpu-baseline --no-regimes > $O/bench_c3_f$fl.json 2> $O/bench_c3_f$fl.err || exit 1
+  timeout -k 10 300 python bench.py --full --steps 50 --warmup 10 --flavour $fl --no-cpu-baseline --no-regimes > $O/bench_c3_f$fl.json 2> $O/bench_c3_f$fl.err || exit 1
 done
 for fl in 13; do
-  timeout -k 10 300 python bench.py --steps 30 --warmup 5 --flavour $fl --air noisy --no-cpu-baseline --no-regimes > $O/bench_c3noisy_f$fl.json 2> $O/bench_c3noisy_f$fl.err || exit 1
-  timeout -k 10 300 python bench.py --steps 30 --warmup 5 --flavour $fl --tf thin --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_c3thin_f$fl.json 2> $O/bench_c3thin_f$fl.err || exit 1
-  timeout -k 10 300 python bench.py --workload C2 --steps 50 --warmup 10 --flavour $fl --no-cpu-baseline --no-live-pmc > $O/bench_c2_f$fl.json 2> $O/bench_c2_f$fl.err || exit 1
-  timeout -k 10 300 python bench.py --workload C5 --steps 10 --warmup 3 --flavour $fl --no-cpu-baseline --no-live-pmc > $O/bench_c5_f$fl.json 2> $O/bench_c5_f$fl.err || exit 1
+  timeout -k 10 300 python bench.py --full --steps 30 --warmup 5 --flavour $fl --air noisy --no-cpu-baseline --no-regimes > $O/bench_c3noisy_f$fl.json 2> $O/bench_c3noisy_f$fl.err || exit 1
+  timeout -k 10 300 python bench.py --full --steps 30 --warmup 5 --flavour $fl --tf thin --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_c3thin_f$fl.json 2> $O/bench_c3thin_f$fl.err || exit 1
+  timeout -k 10 300 python bench.py --full --workload C2 --steps 50 --warmup 10 --flavour $fl --no-cpu-baseline --no-live-pmc > $O/bench_c2_f$fl.json 2> $O/bench_c2_f$fl.err || exit 1
+  timeout -k 10 300 python bench.py --full --workload C5 --steps 10 --warmup 3 --flavour $fl --no-cpu-baseline --no-live-pmc > $O/bench_c5_f$fl.json 2> $O/bench_c5_f$fl.err || exit 1
 done
-timeout -k 10 300 python bench.py --workload C5 --steps 10 --warmup 3 --flavour 6 --no-cpu-baseline --no-live-pmc > $O/bench_c5_f6.json 2> $O/bench_c5_f6.err || exit 1
+timeout -k 10 300 python bench.py --full --workload C5 --steps 10 --warmup 3 --flavour 6 --no-cpu-baseline --no-live-pmc > $O/bench_c5_f6.json 2> $O/bench_c5_f6.err || exit 1
 timeout -k 10 300 python tools/block_trace.py --flavour 13 > $O/trace_c3_f13.txt 2>&1
 python - <<'PY'
 import json,glob

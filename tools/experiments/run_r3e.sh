@@ -7,10 +7,10 @@ timeout -k 10 600 python -m pytest tests/test_mgpu_loopback_gpu.py tests/test_mg
 rc=$?
 tail -5 $O/pytest_mgpu.txt
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
-VR_BENCH_SELF_GATHER=1 timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_selfgather.json 2> $O/bench_selfgather.err || { tail -20 $O/bench_selfgather.err; exit 1; }
-VR_BENCH_SELF_GATHER=1 VR_MGPU_EXP_SHARE=8 timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_share8.json 2> $O/bench_share8.err || { tail -20 $O/bench_share8.err; exit 1; }
-VR_BENCH_DEVICE=0 VR_BENCH_BACKEND=gloo timeout -k 10 300 python bench.py --gpus 2 --steps 6 --warmup 2 --no-cpu-baseline > $O/bench_gloo2.json 2> $O/bench_gloo2.err || { tail -20 $O/bench_gloo2.err; exit 1; }
+timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
+VR_BENCH_SELF_GATHER=1 timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_selfgather.json 2> $O/bench_selfgather.err || { tail -20 $O/bench_selfgather.err; exit 1; }
+VR_BENCH_SELF_GATHER=1 VR_MGPU_EXP_SHARE=8 timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_share8.json 2> $O/bench_share8.err || { tail -20 $O/bench_share8.err; exit 1; }
+VR_BENCH_DEVICE=0 VR_BENCH_BACKEND=gloo timeout -k 10 300 python bench.py --full --gpus 2 --steps 6 --warmup 2 --no-cpu-baseline > $O/bench_gloo2.json 2> $O/bench_gloo2.err || { tail -20 $O/bench_gloo2.err; exit 1; }
 python - <<'PY'
 import json,glob
 for f in sorted(glob.glob('gpurun_out/r3e/bench_*.json')):

@@ -4,7 +4,7 @@ set -x
 O=gpurun_out/r3g
 mkdir -p $O
 for n in 32 64 128 256; do for fl in 6 13; do
-  timeout -k 10 300 python bench.py --steps 30 --warmup 8 --flavour $fl --vol-n $n --identical-frames --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_c3_n${n}_f$fl.json 2> $O/bench_c3_n${n}_f$fl.err || { tail -5 $O/bench_c3_n${n}_f$fl.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 30 --warmup 8 --flavour $fl --vol-n $n --identical-frames --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_c3_n${n}_f$fl.json 2> $O/bench_c3_n${n}_f$fl.err || { tail -5 $O/bench_c3_n${n}_f$fl.err; exit 1; }
 done; done
 python - <<'PY'
 import json,glob

@@ -7,9 +7,9 @@ timeout -k 10 1100 python -m pytest tests -x -q -m gpu > $O/pytest_all.txt 2>&1
 rc=$?
 tail -5 $O/pytest_all.txt
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py --steps 30 --warmup 8 --air noisy --no-cpu-baseline --no-regimes > $O/bench_noisy.json 2> $O/bench_noisy.err || { tail -5 $O/bench_noisy.err; exit 1; }
-timeout -k 10 300 python bench.py --workload C4 --steps 30 --warmup 8 --no-cpu-baseline > $O/bench_C4.json 2> $O/bench_C4.err || { tail -5 $O/bench_C4.err; exit 1; }
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-live-pmc > $O/bench_c3.json 2> $O/bench_c3.err || { tail -5 $O/bench_c3.err; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 30 --warmup 8 --air noisy --no-cpu-baseline --no-regimes > $O/bench_noisy.json 2> $O/bench_noisy.err || { tail -5 $O/bench_noisy.err; exit 1; }
+timeout -k 10 300 python bench.py --full --workload C4 --steps 30 --warmup 8 --no-cpu-baseline > $O/bench_C4.json 2> $O/bench_C4.err || { tail -5 $O/bench_C4.err; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-live-pmc > $O/bench_c3.json 2> $O/bench_c3.err || { tail -5 $O/bench_c3.err; exit 1; }
 python - <<'PY'
 import json,glob
 for f in sorted(glob.glob('gpurun_out/r3i/bench_*.json')):

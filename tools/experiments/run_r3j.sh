@@ -8,11 +8,11 @@ rc=$?
 tail -5 $O/pytest_all.txt
 [ $rc -eq 0 ] || exit $rc
 for lay in 0 3; do
-  timeout -k 10 300 python bench.py --steps 40 --warmup 8 --layout $lay --no-cpu-baseline --no-regimes > $O/bench_c3_l$lay.json 2> $O/bench_c3_l$lay.err || { tail -5 $O/bench_c3_l$lay.err; exit 1; }
-  timeout -k 10 300 python bench.py --steps 30 --warmup 8 --layout $lay --air noisy --no-cpu-baseline --no-regimes > $O/bench_noisy_l$lay.json 2> $O/bench_noisy_l$lay.err || { tail -5 $O/bench_noisy_l$lay.err; exit 1; }
-  timeout -k 10 300 python bench.py --steps 30 --warmup 8 --layout $lay --tf thin --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_thin_l$lay.json 2> $O/bench_thin_l$lay.err || { tail -5 $O/bench_thin_l$lay.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 40 --warmup 8 --layout $lay --no-cpu-baseline --no-regimes > $O/bench_c3_l$lay.json 2> $O/bench_c3_l$lay.err || { tail -5 $O/bench_c3_l$lay.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 30 --warmup 8 --layout $lay --air noisy --no-cpu-baseline --no-regimes > $O/bench_noisy_l$lay.json 2> $O/bench_noisy_l$lay.err || { tail -5 $O/bench_noisy_l$lay.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 30 --warmup 8 --layout $lay --tf thin --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_thin_l$lay.json 2> $O/bench_thin_l$lay.err || { tail -5 $O/bench_thin_l$lay.err; exit 1; }
   for wk in C2 C4 C5; do
-    timeout -k 10 400 python bench.py --workload $wk --steps 20 --warmup 5 --layout $lay --no-cpu-baseline --no-live-pmc > $O/bench_${wk}_l$lay.json 2> $O/bench_${wk}_l$lay.err || { tail -5 $O/bench_${wk}_l$lay.err; exit 1; }
+    timeout -k 10 400 python bench.py --full --workload $wk --steps 20 --warmup 5 --layout $lay --no-cpu-baseline --no-live-pmc > $O/bench_${wk}_l$lay.json 2> $O/bench_${wk}_l$lay.err || { tail -5 $O/bench_${wk}_l$lay.err; exit 1; }
   done
 done
 python - <<'PY'

@@ -8,11 +8,11 @@ rc=$?
 tail -6 $O/pytest.txt
 [ $rc -eq 0 ] || exit $rc
 for fl in 16 13; do
-  timeout -k 10 300 python bench.py --steps 30 --warmup 8 --flavour $fl --air noisy --no-cpu-baseline --no-regimes > $O/bench_noisy_f$fl.json 2> $O/bench_noisy_f$fl.err || { tail -5 $O/bench_noisy_f$fl.err; exit 1; }
-  timeout -k 10 300 python bench.py --steps 30 --warmup 8 --flavour $fl --tf thin --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_thin_f$fl.json 2> $O/bench_thin_f$fl.err || { tail -5 $O/bench_thin_f$fl.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 30 --warmup 8 --flavour $fl --air noisy --no-cpu-baseline --no-regimes > $O/bench_noisy_f$fl.json 2> $O/bench_noisy_f$fl.err || { tail -5 $O/bench_noisy_f$fl.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 30 --warmup 8 --flavour $fl --tf thin --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_thin_f$fl.json 2> $O/bench_thin_f$fl.err || { tail -5 $O/bench_thin_f$fl.err; exit 1; }
 done
-timeout -k 10 300 python bench.py --steps 30 --warmup 8 --flavour 16 --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_c3_f16.json 2> $O/bench_c3_f16.err || { tail -5 $O/bench_c3_f16.err; exit 1; }
-timeout -k 10 300 python bench.py --steps 30 --warmup 8 --flavour 16 --air noisy --arith fused --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_noisy_fused_f16.json 2> $O/bench_noisy_fused_f16.err || { tail -5 $O/bench_noisy_fused_f16.err; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 30 --warmup 8 --flavour 16 --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_c3_f16.json 2> $O/bench_c3_f16.err || { tail -5 $O/bench_c3_f16.err; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 30 --warmup 8 --flavour 16 --air noisy --arith fused --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_noisy_fused_f16.json 2> $O/bench_noisy_fused_f16.err || { tail -5 $O/bench_noisy_fused_f16.err; exit 1; }
 python - <<'PY'
 import json,glob
 for f in sorted(glob.glob('gpurun_out/r3r/bench_*.json')):

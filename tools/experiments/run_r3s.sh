@@ -8,12 +8,12 @@ rc=$?
 tail -6 $O/pytest.txt
 [ $rc -eq 0 ] || exit $rc
 for fl in 17 0; do
-  timeout -k 10 300 python bench.py --steps 30 --warmup 8 --flavour $fl --no-cpu-baseline --no-regimes > $O/bench_c3_f$fl.json 2> $O/bench_c3_f$fl.err || { tail -5 $O/bench_c3_f$fl.err; exit 1; }
-  timeout -k 10 300 python bench.py --steps 30 --warmup 8 --flavour $fl --tf thin --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_thin_f$fl.json 2> $O/bench_thin_f$fl.err || { tail -5 $O/bench_thin_f$fl.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 30 --warmup 8 --flavour $fl --no-cpu-baseline --no-regimes > $O/bench_c3_f$fl.json 2> $O/bench_c3_f$fl.err || { tail -5 $O/bench_c3_f$fl.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 30 --warmup 8 --flavour $fl --tf thin --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_thin_f$fl.json 2> $O/bench_thin_f$fl.err || { tail -5 $O/bench_thin_f$fl.err; exit 1; }
 done
-timeout -k 10 300 python bench.py --steps 30 --warmup 8 --flavour 17 --identical-frames --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_c3ident_f17.json 2> $O/bench_c3ident_f17.err || { tail -5 $O/bench_c3ident_f17.err; exit 1; }
-timeout -k 10 300 python bench.py --steps 30 --warmup 8 --flavour 17 --air noisy --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_noisy_f17.json 2> $O/bench_noisy_f17.err || { tail -5 $O/bench_noisy_f17.err; exit 1; }
-timeout -k 10 300 python bench.py --steps 30 --warmup 8 --flavour 17 --arith fused --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_c3_fused_f17.json 2> $O/bench_c3_fused_f17.err || { tail -5 $O/bench_c3_fused_f17.err; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 30 --warmup 8 --flavour 17 --identical-frames --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_c3ident_f17.json 2> $O/bench_c3ident_f17.err || { tail -5 $O/bench_c3ident_f17.err; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 30 --warmup 8 --flavour 17 --air noisy --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_noisy_f17.json 2> $O/bench_noisy_f17.err || { tail -5 $O/bench_noisy_f17.err; exit 1; }
+timeout -k 10 300 python bench.py --full --steps 30 --warmup 8 --flavour 17 --arith fused --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_c3_fused_f17.json 2> $O/bench_c3_fused_f17.err || { tail -5 $O/bench_c3_fused_f17.err; exit 1; }
 python - <<'PY'
 import json,glob
 for f in sorted(glob.glob('gpurun_out/r3s/bench_*.json')):

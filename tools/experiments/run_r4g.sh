@@ -9,11 +9,11 @@ tail -4 $O/pytest.txt
 [ $rc -eq 0 ] || exit $rc
 for wl in C1 C2 C3; do
  for fl in 17 0; do
-  timeout -k 10 300 python bench.py --steps 30 --warmup 8 --workload $wl --flavour $fl --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_${wl}_f$fl.json 2> $O/bench_${wl}_f$fl.err || { tail -5 $O/bench_${wl}_f$fl.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 30 --warmup 8 --workload $wl --flavour $fl --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_${wl}_f$fl.json 2> $O/bench_${wl}_f$fl.err || { tail -5 $O/bench_${wl}_f$fl.err; exit 1; }
  done
 done
-timeout -k 10 300 python bench.py --steps 30 --warmup 8 --flavour 17 --tf thin --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_thin_f17.json 2> $O/bench_thin_f17.err
-timeout -k 10 300 python bench.py --steps 30 --warmup 8 --flavour 0 --air noisy --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_noisy_f0.json 2> $O/bench_noisy_f0.err
+timeout -k 10 300 python bench.py --full --steps 30 --warmup 8 --flavour 17 --tf thin --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_thin_f17.json 2> $O/bench_thin_f17.err
+timeout -k 10 300 python bench.py --full --steps 30 --warmup 8 --flavour 0 --air noisy --no-cpu-baseline --no-regimes --no-live-pmc > $O/bench_noisy_f0.json 2> $O/bench_noisy_f0.err
 python - <<'PY'
 import json,glob
 for f in sorted(glob.glob('gpurun_out/r4g/bench_*.json')):

@@ -7,7 +7,7 @@ timeout -k 10 1100 python -m pytest tests -x -q -m gpu > $O/pytest.txt 2>&1
 rc=$?
 tail -5 $O/pytest.txt
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }
+timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }
 python - <<'PY'
 import json
 d=json.load(open('gpurun_out/r4h/bench_default.json'))

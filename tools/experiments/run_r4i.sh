@@ -5,7 +5,7 @@ O=gpurun_out/r4t
 mkdir -p $O
 for N in 2 4 8; do
  for fl in 0 17; do
-  VR_BENCH_SELF_GATHER=1 VR_MGPU_EXP_SHARE=$N timeout -k 10 300 python bench.py --steps 60 --warmup 10 --flavour $fl --no-cpu-baseline --no-regimes --no-live-pmc > $O/c3_share${N}_f$fl.json 2> $O/c3_share${N}_f$fl.err || { tail -5 $O/c3_share${N}_f$fl.err; exit 1; }
+  VR_BENCH_SELF_GATHER=1 VR_MGPU_EXP_SHARE=$N timeout -k 10 300 python bench.py --full --steps 60 --warmup 10 --flavour $fl --no-cpu-baseline --no-regimes --no-live-pmc > $O/c3_share${N}_f$fl.json 2> $O/c3_share${N}_f$fl.err || { tail -5 $O/c3_share${N}_f$fl.err; exit 1; }
  done
 done
 python - <<'PY'

@@ -7,7 +7,7 @@ timeout -k 10 1100 python -m pytest tests -x -q -m gpu > $O/pytest.txt 2>&1
 rc=$?
 tail -3 $O/pytest.txt
 [ $rc -eq 0 ] || exit $rc
-run() { name=$1; shift; timeout -k 10 300 python bench.py --steps 30 --warmup 8 --no-cpu-baseline --no-regimes --no-live-pmc "$@" > $O/bench_$name.json 2> $O/bench_$name.err || { tail -5 $O/bench_$name.err; exit 1; }; }
+run() { name=$1; shift; timeout -k 10 300 python bench.py --full --steps 30 --warmup 8 --no-cpu-baseline --no-regimes --no-live-pmc "$@" > $O/bench_$name.json 2> $O/bench_$name.err || { tail -5 $O/bench_$name.err; exit 1; }; }
 run c3_default
 run c3_f6 --flavour 6
 run thin --tf thin

@@ -7,7 +7,7 @@ timeout -k 10 1000 python -m pytest tests/test_parity_gpu.py tests/test_random_g
 rc=$?
 tail -3 $O/pytest.txt
 [ $rc -eq 0 ] || exit $rc
-run() { name=$1; shift; timeout -k 10 300 python bench.py --steps 30 --warmup 8 --no-cpu-baseline --no-regimes --no-live-pmc "$@" > $O/bench_$name.json 2> $O/bench_$name.err || { tail -5 $O/bench_$name.err; exit 1; }; }
+run() { name=$1; shift; timeout -k 10 300 python bench.py --full --steps 30 --warmup 8 --no-cpu-baseline --no-regimes --no-live-pmc "$@" > $O/bench_$name.json 2> $O/bench_$name.err || { tail -5 $O/bench_$name.err; exit 1; }; }
 run c3_default
 run thin_f17 --tf thin --flavour 17
 run noisy --air noisy

@@ -7,11 +7,11 @@ timeout -k 10 900 python -m pytest tests -x -q -m gpu > $O/pytest.txt 2>&1
 rc=$?
 tail -4 $O/pytest.txt
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }
+timeout -k 10 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }
 for N in 2 4 8; do
-  VR_BENCH_SELF_GATHER=1 VR_MGPU_EXP_SHARE=$N timeout -k 10 300 python bench.py --workload C5 --steps 20 --warmup 4 --no-cpu-baseline --no-regimes --no-live-pmc > $O/C5_share$N.json 2> $O/C5_share$N.err || { tail -5 $O/C5_share$N.err; exit 1; }
+  VR_BENCH_SELF_GATHER=1 VR_MGPU_EXP_SHARE=$N timeout -k 10 300 python bench.py --full --workload C5 --steps 20 --warmup 4 --no-cpu-baseline --no-regimes --no-live-pmc > $O/C5_share$N.json 2> $O/C5_share$N.err || { tail -5 $O/C5_share$N.err; exit 1; }
 done
-VR_BENCH_SELF_GATHER=1 timeout -k 10 300 python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-regimes --no-live-pmc > $O/c3_selfgather.json 2> $O/c3_selfgather.err
+VR_BENCH_SELF_GATHER=1 timeout -k 10 300 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-regimes --no-live-pmc > $O/c3_selfgather.json 2> $O/c3_selfgather.err
 python - <<'PY'
 import json,glob
 d=json.load(open('gpurun_out/r5g/bench_default.json'))

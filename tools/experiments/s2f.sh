@@ -7,7 +7,7 @@ mkdir -p $O
 cd $R
 timeout -k 10 600 python3 -m pytest tests -m gpu -x -q > $O/pytest.txt 2>&1 || { tail -30 $O/pytest.txt; exit 1; }
 tail -3 $O/pytest.txt
-B="python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-regimes --turn-frames 0"
+B="python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-regimes --turn-frames 0"
 $B --flavour 15 > $O/c3_f15.json 2> $O/c3_f15.err; echo "c3 f15 rc $?"
 $B --flavour 15 --air noisy > $O/c3_noisy_f15.json 2> $O/c3_noisy_f15.err; echo "c3 noisy f15 rc $?"
 $B --air noisy > $O/c3_noisy.json 2> $O/c3_noisy.err; echo "c3 noisy rc $?"

@@ -11,7 +11,7 @@ python3 $R/tools/launch_gap.py --read $O/kt > $O/gap.txt 2>&1; cat $O/gap.txt; r
 cd $R
 timeout -k 10 300 python3 -m pytest tests/test_parity_gpu.py -x -q -k "order or persistent or records" > $O/pytest_order.txt 2>&1; tail -2 $O/pytest_order.txt
 for i in 1 2; do
-  python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-regimes --no-live-pmc --turn-frames 0 > $O/bench$i.json 2> $O/bench$i.err
+  python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-regimes --no-live-pmc --turn-frames 0 > $O/bench$i.json 2> $O/bench$i.err
   python3 - <<P
 import json
 t=open('$O/bench$i.json').read(); d=json.loads(t[t.find('{"metric'):].splitlines()[0])

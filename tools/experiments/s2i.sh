@@ -7,8 +7,8 @@ cd $R
 timeout -k 10 600 python3 -m pytest tests -m gpu -x -q > $O/pytest.txt 2>&1 || { tail -30 $O/pytest.txt; exit 1; }
 tail -2 $O/pytest.txt
 for W in C1 C2; do
-  python3 bench.py --workload $W --steps 30 --warmup 5 --no-regimes --no-cpu-baseline > $O/${W}_default.json 2> $O/${W}_default.err; echo "$W rc $?"
-  python3 bench.py --workload $W --tf thin --steps 30 --warmup 5 --no-regimes --no-cpu-baseline --no-live-pmc --turn-frames 0 > $O/${W}_thin.json 2> $O/${W}_thin.err; echo "$W thin rc $?"
+  python3 bench.py --full --workload $W --steps 30 --warmup 5 --no-regimes --no-cpu-baseline > $O/${W}_default.json 2> $O/${W}_default.err; echo "$W rc $?"
+  python3 bench.py --full --workload $W --tf thin --steps 30 --warmup 5 --no-regimes --no-cpu-baseline --no-live-pmc --turn-frames 0 > $O/${W}_thin.json 2> $O/${W}_thin.err; echo "$W thin rc $?"
 done
 python3 - <<'P'
 import json,glob

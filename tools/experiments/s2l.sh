@@ -6,7 +6,7 @@ mkdir -p $O
 cd $R
 timeout -k 10 600 python3 -m pytest tests -m gpu -x -q > $O/pytest.txt 2>&1 || { tail -30 $O/pytest.txt; exit 1; }
 tail -2 $O/pytest.txt
-B="python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-regimes --turn-frames 0"
+B="python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-regimes --turn-frames 0"
 $B --air noisy > $O/c3_noisy.json 2> $O/c3_noisy.err; echo "c3 noisy rc $?"
 $B --air noisy --arith fused --no-live-pmc > $O/c3_noisy_fused.json 2> $O/c3_noisy_fused.err; echo "c3 noisy fused rc $?"
 $B --tf thin --flavour 16 --no-live-pmc > $O/c3_thin_f16.json 2> $O/c3_thin_f16.err; echo "c3 thin f16 rc $?"

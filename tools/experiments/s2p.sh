@@ -7,11 +7,11 @@ cd $R
 timeout -k 10 600 python3 -m pytest tests -m gpu -x -q > $O/pytest.txt 2>&1 || { tail -30 $O/pytest.txt; exit 1; }
 tail -2 $O/pytest.txt
 python3 -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids
-python3 bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $?"
+python3 bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $?"
 for W in C1 C2 C4; do
-  python3 bench.py --workload $W --steps 30 --warmup 5 --no-regimes --no-cpu-baseline --no-live-pmc --turn-frames 0 > $O/$W.json 2> $O/$W.err; echo "$W rc $?"
+  python3 bench.py --full --workload $W --steps 30 --warmup 5 --no-regimes --no-cpu-baseline --no-live-pmc --turn-frames 0 > $O/$W.json 2> $O/$W.err; echo "$W rc $?"
 done
-python3 bench.py --air noisy --steps 20 --warmup 5 --no-regimes --no-cpu-baseline --no-live-pmc --turn-frames 0 > $O/c3_noisy.json 2> $O/c3_noisy.err
+python3 bench.py --full --air noisy --steps 20 --warmup 5 --no-regimes --no-cpu-baseline --no-live-pmc --turn-frames 0 > $O/c3_noisy.json 2> $O/c3_noisy.err
 python3 - <<'P'
 import json,glob
 for f in sorted(glob.glob('gpurun_out/s2p/*.json')):
