@@ -75,7 +75,29 @@ typedef enum vr_variant {
     VR_VARIANT_MIP = 8,
     VR_VARIANT_MINIP = 9,
     VR_VARIANT_AVERAGE = 10,
-    VR_VARIANT_COUNT = 11
+    /* Shaded isosurface of volume slot 0 at the level set by vr_set_iso_value (no shader of the reference; csrc/vr_iso.h).
+     * Volume slot 0 holds the pre-computed gradient in .rgb (as LIGHT); TF slot 0; the light of vr_uniforms (as LIGHT).
+     *   Positions: exactly BASIC's march (start, direction, stepsCount, step size, variable-step toggle, jitter, repeated rounded
+     *     additions p_{k+1} = p_k + step); fragmentMode 1-4 return what BASIC returns.  The world position w is LIGHT's: w_0 = the
+     *     ray's worldCoord, w_{k+1} = w_k + wstep (rounded additions), wstep = CalculateWorldStep (BasicVolLightApp.wgsl:78-84,
+     *     before the variable-step override, z negated).
+     *   Hit: only the steps that pass IsInSampleCoords count (they are contiguous: positions are monotone per component and the
+     *     box is convex).  The hit is the first of them, k, whose d_k = textureSample(vol0, linear, p_k).a satisfies d_k >= iso
+     *     (NaN samples never hit).
+     *   Refinement: if k is the ray's first in-box step, q = p_k and w_q = w_k.  Otherwise d_prev = the density at p_{k-1},
+     *     t = (iso - d_prev) / (d_k - d_prev) (correctly rounded f32 division); if !(t >= 0 && t <= 1) then q = p_k, w_q = w_k,
+     *     else q = mad(step, t, p_{k-1}) and w_q = mad(wstep, t, w_{k-1}) per component, in the vr_set_arithmetic mode's mad
+     *     (two roundings with VR_ARITH_SEPARATE, one with VR_ARITH_FUSED).
+     *   Shading: s = textureSample(vol0, linear, q) (all four channels), N = normalize(s.rgb) (a zero gradient gives NaN and
+     *     max(NaN, 0) leaves the ambient term only, as in LIGHT), c = the TF slot 0 colour at iso with BASIC's lookup (linear,
+     *     clamp-to-edge), rgb = c * BlinnPhong(N, w_q, light, kD = 2.5, kA = 0.5) as in LIGHT, and the fragment is
+     *     FrontToBackBlend((rgb, 1), dst = 0) in the blend's own arithmetic (a -0 made +0): opaque; the opacity table is not read.
+     *   No hit: the pixel is (0,0,0,0).
+     *   Counters: composited = the in-box steps up to and including the hit (all of them without a hit), covered = pixels whose ray
+     *     hit, fetched = march-loop samples whose corners were loaded (the refinement's fetches are not counted).
+     * The output, composited and covered are bit-identical across kernel forms, layouts, launch shapes and skipping on / off. */
+    VR_VARIANT_ISO = 11,
+    VR_VARIANT_COUNT = 12
 } vr_variant;
 
 #define VR_MAX_VOLUMES 3
@@ -89,8 +111,9 @@ typedef enum vr_variant {
  *   MULTI_CTRT    : 0 = CT, 1 = RT                  (MultiCTRTApp.wgsl:50-51)
  *   TF_CALIB      : 0 = CT, 1 = mask                (TFCalibrationApp.wgsl:40-41)
  *   MIP / MINIP / AVERAGE : 0 = volume (as BASIC)
+ *   ISO           : 0 = volume with its gradient in .rgb (as LIGHT)
  * TF slots = the order of the (opacity, colour) texture_1d pairs:
- *   single-TF scenes (and the projections): 0;  two-TF scenes: 0 = CT pair, 1 = RT pair (VolumeMaskApp.wgsl:43-46).
+ *   single-TF scenes (and the projections, the isosurface): 0;  two-TF scenes: 0 = CT pair, 1 = RT pair (VolumeMaskApp.wgsl:43-46).
  */
 
 /*
@@ -384,7 +407,11 @@ int vr_last_block_trace(vr_ctx* ctx, uint64_t* out, int capacity);
  *   19  march_proj_kernel with exact skipping (csrc/vr_proj.h): a step whose brick cannot change the result loads nothing
  *       (MIP: brick max <= m, MINIP: brick min >= m, AVERAGE: every voxel of the brick +-0), and MIP / MINIP stop loading once
  *       m has reached the volume's maximum / minimum.  Flavour 0 runs as 19, and so does every other flavour but 1.
- *   20  march_proj_kernel without skipping: every counted sample is fetched.  Flavour 1 runs as 20.                    */
+ *   20  march_proj_kernel without skipping: every counted sample is fetched.  Flavour 1 runs as 20.
+ * The isosurface (ISO) likewise (0 candidates after an ISO launch):
+ *   21  march_iso_kernel with exact skipping (csrc/vr_iso.h): a step whose brick's maximum density is below the level loads
+ *       nothing.  Flavour 0 runs as 21, and so does every other flavour but 1.
+ *   22  march_iso_kernel without skipping: every in-box step up to the hit is fetched.  Flavour 1 runs as 22.            */
 int vr_set_kernel_flavour(vr_ctx* ctx, int flavour);
 
 /* What the default's measured choice (flavour 0) knows about the launch shape it was asked for last: the candidates' flavours, the
@@ -404,6 +431,10 @@ int vr_kernel_choice(vr_ctx* ctx, int flavours[6], float ms_per_launch[6], int* 
 #define VR_ARITH_SEPARATE 0
 #define VR_ARITH_FUSED 1
 int vr_set_arithmetic(vr_ctx* ctx, int mode);
+
+/* Threshold of VR_VARIANT_ISO for launches enqueued after this call (default 0.5f).  Finite values only:
+ * NaN / +-inf -> VR_ERR_INVALID_ARG, the previous value stays. */
+int vr_set_iso_value(vr_ctx* ctx, float iso);
 
 /* Volume layout in HBM (A/B measurements; frames and counts are bit-identical in every mode).
  *   0  default: the march kernels gather from a BRICKED copy of every slot -- the vec4 voxels and a scalar f32 density plane

@@ -1,0 +1,146 @@
+"""float32 numpy restatement of the shaded isosurface of include/vr.h (VR_VARIANT_ISO) in separately rounded arithmetic: BASIC's
+sample positions as proj_ref.march places them (rays from oracle_binding.setup_ray, jitter from oracle_binding.jitter), LIGHT's
+world position beside them, the first in-box sample at or above the level, the secant refinement, and the shading in the oracle's
+operation order (normalize3 = v * (1 / sqrt(dot)), BlinnPhong, the texel pairs and lerps of the samplers, FrontToBackBlend).
+Harness only."""
+import numpy as np
+
+import oracle_binding as ob
+import proj_ref as pr
+
+f32 = np.float32
+ISO = 11
+
+
+def sample_rgba(vec4, p):
+    """textureSample(vol, linear, p) for points p (N, 3): all four channels, the texel pairs and lerp order of proj_ref.sample_a."""
+    nz, ny, nx = vec4.shape[:3]
+    with np.errstate(all="ignore"):
+        x = p[:, 0] * f32(nx) + f32(-0.5)
+        y = p[:, 1] * f32(ny) + f32(-0.5)
+        z = p[:, 2] * f32(nz) + f32(-0.5)
+        x0, y0, z0 = np.floor(x), np.floor(y), np.floor(z)
+        fx, fy, fz = (x - x0)[:, None], (y - y0)[:, None], (z - z0)[:, None]
+        i0, i1 = pr._texel_pair(x0, nx)
+        j0, j1 = pr._texel_pair(y0, ny)
+        k0, k1 = pr._texel_pair(z0, nz)
+        c00 = pr._lerp(vec4[k0, j0, i0], vec4[k0, j0, i1], fx)
+        c10 = pr._lerp(vec4[k0, j1, i0], vec4[k0, j1, i1], fx)
+        c01 = pr._lerp(vec4[k1, j0, i0], vec4[k1, j0, i1], fx)
+        c11 = pr._lerp(vec4[k1, j1, i0], vec4[k1, j1, i1], fx)
+        return pr._lerp(pr._lerp(c00, c10, fy), pr._lerp(c01, c11, fy), fz)
+
+
+def dot3(a, b):
+    return (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
+
+
+def normalize3(a):
+    with np.errstate(all="ignore"):
+        inv = f32(1.0) / np.sqrt(dot3(a, a))
+        return a * inv[:, None]
+
+
+def shade(N, w, lpos, dif, amb, kD, kA):
+    """light.diffuse * max(dot(N, L), 0) * kD + light.ambient * kA, L = normalize(lightPos - w) (NaN -> 0)."""
+    with np.errstate(all="ignore"):
+        L = normalize3(lpos[None, :] - w)
+        d = dot3(N, L)
+        m = np.where(d > f32(0.0), d, f32(0.0)).astype(f32)
+        return (dif[None, :] * m[:, None]) * f32(kD) + amb[None, :] * f32(kA)
+
+
+def march(u, W, H, vec4, tf, iso, pixels=None):
+    """ISO of `pixels` (px, py) (default: the whole frame, row by row).  Returns a dict: frag (N, 4), composited (N,), covered (N,),
+    fetched_all (N,) = what the form without skipping fetches (= composited), hit (N,), q / pk (N, 3) = the refined / unrefined
+    hit positions (NaN where no hit), pixels."""
+    if pixels is None:
+        pixels = np.stack(np.meshgrid(np.arange(W), np.arange(H)), -1).reshape(-1, 2)
+    pixels = np.asarray(pixels, dtype=np.int64).reshape(-1, 2)
+    vec4 = np.ascontiguousarray(np.asarray(vec4, dtype=f32))
+    dens = np.ascontiguousarray(vec4[..., 3])
+    opacity, color = (np.asarray(t, dtype=f32) for t in tf)
+    iso = f32(iso)
+    N = len(pixels)
+    out = dict(frag=np.zeros((N, 4), f32), composited=np.zeros(N, np.int64), covered=np.zeros(N, bool), hit=np.zeros(N, bool),
+               q=np.full((N, 3), np.nan, f32), pk=np.full((N, 3), np.nan, f32), pixels=pixels)
+    start, end, world0 = (np.zeros((N, 3), f32) for _ in range(3))
+    rayhit = np.zeros(N, bool)
+    for k, (px, py) in enumerate(pixels):
+        h, s, e, w = ob.setup_ray(u, W, H, int(px), int(py))
+        rayhit[k], start[k], end[k], world0[k] = h, s, e, w
+    assert u.fragment_mode == 0
+    idx = np.nonzero(rayhit)[0]
+    out["fetched_all"] = out["composited"]
+    if idx.size == 0 or u.steps_count <= 0:
+        return out
+    M = idx.size
+    with np.errstate(all="ignore"):
+        diff = end[idx] - start[idx]
+        ln = np.sqrt((diff[:, 0] * diff[:, 0] + diff[:, 1] * diff[:, 1]) + diff[:, 2] * diff[:, 2])
+        dr = diff * (f32(1.0) / ln)[:, None]
+        ss = np.full(M, f32(u.step_size), f32)
+        wstep = np.stack([dr[:, 0] * (ss * f32(1.0)), dr[:, 1] * (ss * f32(1.0)), dr[:, 2] * (ss * f32(0.5))], 1)
+        wstep[:, 2] = wstep[:, 2] * f32(-1.0)
+        if u.toggles[0] == 1:
+            ss = ln / f32(u.steps_count)
+        p = start[idx].copy()
+        if u.toggles[1] == 1:
+            j = np.array([ob.jitter(float(f32(px) + f32(0.5)), float(f32(py) + f32(0.5))) for px, py in pixels[idx]], f32)
+            p = p + (dr * ss[:, None]) * j[:, None]
+        step = dr * ss[:, None]
+    w = world0[idx].copy()
+    lo = np.array([f32(0.0) + f32(u.clip_x[0]), f32(0.0) + f32(u.clip_y[0]), f32(0.0) + f32(u.clip_z[0])], f32)
+    hi = np.array([f32(1.0) - f32(u.clip_x[1]), f32(1.0) - f32(u.clip_y[1]), f32(1.0) - f32(u.clip_z[1])], f32)
+    n = np.zeros(M, np.int64)
+    hit = np.zeros(M, bool)
+    pk, wk, pp, wp = (np.zeros((M, 3), f32) for _ in range(4))
+    dk, dprev = np.zeros(M, f32), np.zeros(M, f32)
+    prev_inb, hit_prev_inb = np.zeros(M, bool), np.zeros(M, bool)
+    for _ in range(u.steps_count):
+        alive = ~hit
+        inb = alive & np.all((p >= lo) & (p <= hi), axis=1)
+        d = pr.sample_a(dens, p)
+        n += inb
+        now = inb & (d >= iso)
+        pk[now], wk[now], dk[now] = p[now], w[now], d[now]
+        hit_prev_inb[now] = prev_inb[now]
+        hit |= now
+        go = alive & ~now
+        pp[go], wp[go], dprev[go], prev_inb[go] = p[go], w[go], d[go], inb[go]
+        with np.errstate(all="ignore"):
+            p = p + step
+            w = w + wstep
+    q, wq = pk.copy(), wk.copy()
+    with np.errstate(all="ignore"):
+        t = (iso - dprev) / (dk - dprev)
+        ok = hit & hit_prev_inb & (t >= f32(0.0)) & (t <= f32(1.0))
+        q[ok] = step[ok] * t[ok][:, None] + pp[ok]
+        wq[ok] = wstep[ok] * t[ok][:, None] + wp[ok]
+    h = np.nonzero(hit)[0]
+    frag = np.zeros((M, 4), f32)
+    if h.size:
+        s = sample_rgba(vec4, q[h])
+        Nn = normalize3(np.ascontiguousarray(s[:, :3]))
+        lpos, dif, amb = (np.asarray(a[:3], f32) for a in (u.light_pos, u.light_diffuse, u.light_ambient))
+        sh = shade(Nn, wq[h], lpos, dif, amb, 2.5, 0.5)
+        _, c = pr.tf_lookup(opacity, color, np.array([iso], f32))
+        with np.errstate(all="ignore"):
+            rgb = c * sh
+            dst = np.zeros((h.size, 4), f32)
+            pr._blend(rgb, np.ones(h.size, f32), dst, np.ones(h.size, bool))
+        frag[h] = dst
+    out["frag"][idx] = frag
+    out["composited"][idx] = n
+    out["fetched_all"] = out["composited"]
+    out["covered"][idx] = hit
+    out["hit"][idx] = hit
+    out["q"][idx[h]] = q[h]
+    out["pk"][idx[h]] = pk[h]
+    return out
+
+
+def frame(u, W, H, vec4, tf, iso):
+    """(frag [H, W, 4], composited, covered) of the whole frame."""
+    r = march(u, W, H, vec4, tf, iso)
+    return r["frag"].reshape(H, W, 4), int(r["composited"].sum()), int(r["covered"].sum())

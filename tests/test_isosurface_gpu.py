@@ -1,0 +1,319 @@
+"""GPU side of the shaded isosurface (VR_VARIANT_ISO, csrc/vr_iso.h): frames and counters bit-exact against the float32 restatement
+(iso_ref.py, itself pinned to the oracle's LIGHT march by tests/test_isosurface.py); at a level below every sample the same bits as
+the GPU's and the oracle's LIGHT frames in both arithmetic modes; the same bits from every kernel form, layout and launch shape;
+hostile volumes and levels, volume and table edits in stream order, and no interference with the compositing shaders."""
+import numpy as np
+import pytest
+
+import host_ref as hr
+import iso_ref as ir
+import oracle_binding as ob
+import vrtest as vt
+from volumerendering_amd import capi
+
+pytestmark = pytest.mark.gpu
+f32 = np.float32
+W, H = 72, 56
+ISO = 0.3
+
+
+def phantom(n=16):
+    return vt.make_volume("phantom", n, gradient=True)
+
+
+def tf_pair(res=64):
+    return hr.default_opacity_tf(res), hr.default_color_tf(res)
+
+
+def flat_tf(res=64, rgb=(0.8, 0.55, 0.3)):
+    return np.ones(res, f32), np.tile(np.array([*rgb, 1.0], f32), (res, 1))
+
+
+def uniforms(shape, **over):
+    step, count = hr.stepping_params(*shape)
+    kw = dict(steps_count=count, step_size=step)
+    kw.update(over)
+    return hr.make_uniforms(W, H, **kw)
+
+
+def render(ctx, iso, u, v, tf, variant=capi.ISO):
+    ctx.set_iso_value(iso)
+    frag, _, _ = vt.gpu_render(ctx, variant, u, [v], [tf])
+    return frag, ctx.counters()
+
+
+def air_and_core(n=24):
+    """Exact-zero air around a bright core (gradient in .rgb): most bricks lie below any positive level."""
+    v = np.zeros((n, n, n, 4), f32)
+    c = n // 2
+    v[c - 3:c + 3, c - 3:c + 3, c - 3:c + 3, 3] = f32(0.9)
+    v[c - 1:c + 1, c - 1:c + 1, c - 1:c + 1, 3] = f32(1.0)
+    return ob.precompute_gradient(v)
+
+
+def shape_of(v):
+    return v.shape[2], v.shape[1], v.shape[0]
+
+
+CASES = [
+    # (id, volume, tf res, level, uniform overrides)
+    ("sphere", lambda: vt.make_volume("sphere", 16, gradient=True), 64, ISO, {}),
+    ("phantom", phantom, 16, ISO, {}),
+    ("aniso", lambda: ob.precompute_gradient(ob.normalize_data(hr.raw_to_vec4(
+        np.random.default_rng(7).integers(0, 4096, size=(7, 20, 13)).astype(np.uint16)))), 257, 0.6, {}),
+    ("clip", phantom, 64, ISO, dict(clip_x=(0.1, 0.2), clip_y=(0.05, 0.0), clip_z=(0.0, 0.3))),
+    ("varstep", phantom, 64, ISO, dict(toggles=(1, 0, 0, 0))),
+    ("jitter", lambda: vt.make_volume("sphere", 16, gradient=True), 64, ISO, dict(toggles=(0, 1, 0, 0))),
+    ("steps0", phantom, 64, ISO, dict(steps_count=0)),
+    ("steps1", phantom, 64, -1.0, dict(steps_count=1)),
+    ("steps7", phantom, 64, ISO, dict(steps_count=7, step_size=0.05)),
+    ("core", air_and_core, 64, 0.5, {}),
+    ("refined", air_and_core, 64, 0.45, {}),      # between two voxel values (0 and 0.9): every hit is refined
+    ("plateau", air_and_core, 64, 0.9, {}),       # equal to a voxel value
+    ("above_max", air_and_core, 64, 1.5, {}),     # above the volume's maximum: no hit
+]
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = capi.Context(W, H, 0)
+    yield c
+    c.close()
+
+
+@pytest.mark.parametrize("cid,make,res,iso,over", CASES, ids=[c[0] for c in CASES])
+def test_matches_restatement(ctx, cid, make, res, iso, over):
+    v, tf = make(), tf_pair(res)
+    u = uniforms(shape_of(v), **over)
+    ref, n_ref, cov_ref = ir.frame(u, W, H, v, tf, iso)
+    fetched = {}
+    for fl in (0, 1):
+        ctx.set_kernel_flavour(fl)
+        frag, (n, cov, f) = render(ctx, iso, u, v, tf)
+        assert ctx.last_kernel_flavour() == (21 if fl == 0 else 22)
+        assert np.array_equal(vt.bits(frag), vt.bits(ref)), (fl, float(np.nanmax(np.abs(frag - ref))))
+        assert (n, cov) == (n_ref, cov_ref)
+        assert f <= n and (fl == 0 or f == n)
+        fetched[fl] = f
+    ctx.set_kernel_flavour(0)
+    if cid == "above_max":
+        assert cov_ref == 0 and not np.any(ref) and n_ref > 0 and fetched[0] == 0
+    if cid in ("refined", "plateau", "core"):
+        assert cov_ref > 0
+
+
+@pytest.mark.parametrize("mode", [capi.ARITH_SEPARATE, capi.ARITH_FUSED])
+@pytest.mark.parametrize("kind", ["sphere", "phantom"])
+def test_light_cross_check(ctx, mode, kind):
+    """iso = -1 with a constant colour table of opacity 1: the ISO frame is the GPU's LIGHT frame and the oracle's LIGHT frame, bit
+    for bit, with the same composited count, in either arithmetic mode."""
+    v, tf = vt.make_volume(kind, 16, gradient=True), flat_tf()
+    u = uniforms((16, 16, 16))
+    ctx.set_arithmetic(mode)
+    try:
+        iso_frag, (n_iso, _, _) = render(ctx, -1.0, u, v, tf)
+        light_frag, (n_light, _, _) = render(ctx, -1.0, u, v, tf, variant=capi.LIGHT)
+    finally:
+        ctx.set_arithmetic(capi.ARITH_SEPARATE)
+    with ob.arithmetic(ob.FUSED if mode == capi.ARITH_FUSED else ob.SEPARATE):
+        ref, n_ref, _ = ob.render(ob.LIGHT, u, [v], [tf], W, H, nthreads=4)
+    assert n_iso == n_light == n_ref > 0
+    assert np.array_equal(vt.bits(iso_frag), vt.bits(light_frag))
+    assert np.array_equal(vt.bits(iso_frag), vt.bits(ref))
+
+
+def test_forms_layouts_and_arithmetic(ctx):
+    """Requested flavours 0 / 1 / 6 / 17 (they run as 21 / 22 / 21 / 21) x layouts 0 / 1 / 3 give the restatement's bits; fused
+    arithmetic gives one frame for all of them, close to the separate one; skipping fetches far less on exact-zero air."""
+    v, tf = air_and_core(), tf_pair()
+    u = uniforms((24, 24, 24))
+    ref, n_ref, cov_ref = ir.frame(u, W, H, v, tf, 0.5)
+    fetched = {}
+    for mode in (capi.ARITH_SEPARATE, capi.ARITH_FUSED):
+        ctx.set_arithmetic(mode)
+        frames = []
+        for layout in (0, 1, 3):
+            ctx.set_volume_layout(layout)
+            for fl in (0, 1, 6, 17):
+                ctx.set_kernel_flavour(fl)
+                frag, (n, cov, f) = render(ctx, 0.5, u, v, tf)
+                assert ctx.last_kernel_flavour() == (22 if fl == 1 else 21)
+                assert (n, cov) == (n_ref, cov_ref), (mode, layout, fl)
+                frames.append(frag)
+                fetched[mode, layout, fl] = f
+        for f in frames[1:]:
+            assert np.array_equal(vt.bits(f), vt.bits(frames[0])), mode
+        if mode == capi.ARITH_SEPARATE:
+            assert np.array_equal(vt.bits(frames[0]), vt.bits(ref))
+        else:
+            assert float(np.max(np.abs(frames[0] - ref))) <= 1e-3
+    ctx.set_arithmetic(capi.ARITH_SEPARATE)
+    ctx.set_volume_layout(0)
+    ctx.set_kernel_flavour(0)
+    for key, f in fetched.items():
+        if key[2] != 1:
+            assert f <= fetched[key[0], key[1], 1]
+    assert fetched[capi.ARITH_SEPARATE, 0, 0] < fetched[capi.ARITH_SEPARATE, 0, 1] // 4
+
+
+def test_hostile_inputs(ctx):
+    """NaN and +-inf voxels and an all-zero volume agree with the restatement (NaN where it is NaN); a NaN voxel's brick is never
+    skipped; vr_set_iso_value refuses NaN / +-inf and keeps the level it had."""
+    tf = tf_pair()
+    u = uniforms((16, 16, 16))
+    v = phantom()
+    nan = v.copy()
+    nan[5, 7, 8, 3] = np.nan
+    inf = v.copy()
+    inf[8, 8, 8, 3] = np.inf
+    inf[3, 9, 4, 3] = -np.inf
+    for name, vol in (("nan", nan), ("inf", inf), ("zero", np.zeros_like(v))):
+        ref, n_ref, cov_ref = ir.frame(u, W, H, vol, tf, ISO)
+        for fl in (0, 1):
+            ctx.set_kernel_flavour(fl)
+            frag, (n, cov, _) = render(ctx, ISO, u, vol, tf)
+            assert np.array_equal(np.isnan(frag), np.isnan(ref)), (name, fl)
+            fin = ~np.isnan(ref)
+            assert np.array_equal(vt.bits(frag)[fin], vt.bits(ref)[fin]), (name, fl)
+            assert (n, cov) == (n_ref, cov_ref), (name, fl)
+    ctx.set_kernel_flavour(0)
+    # exact-zero air with one NaN voxel: nothing hits, and only the NaN voxel's brick(s) are loaded
+    z = np.zeros((24, 24, 24, 4), f32)
+    _, (n0, cov0, f0) = render(ctx, 0.5, uniforms((24, 24, 24)), z, tf)
+    z[12, 12, 12, 3] = np.nan
+    _, (n1, cov1, f1) = render(ctx, 0.5, uniforms((24, 24, 24)), z, tf)
+    assert cov0 == cov1 == 0 and n0 == n1 > 0 and f0 == 0 and 0 < f1 < n1
+    # refused levels
+    want, _ = render(ctx, ISO, u, v, tf)
+    for bad in (float("nan"), float("inf"), float("-inf")):
+        with pytest.raises(capi.VrError) as e:
+            ctx.set_iso_value(bad)
+        assert e.value.code == capi.VR_ERR_INVALID_ARG
+        ctx.render(capi.ISO)
+        got, _, _ = ctx.download()
+        assert np.array_equal(vt.bits(got), vt.bits(want))
+
+
+def test_tiles_batches_and_streams(ctx):
+    """Tiles of world 2 / 3 (unpacked) equal the frame; a batch of four frames with different uniforms equals the single renders;
+    launches on two streams with the level changed between enqueues each show the level of their own enqueue."""
+    v, tf = phantom(), tf_pair()
+    us = [uniforms((16, 16, 16), yaw=0.6 + 0.4 * k, clip_z=(0.0, 0.1 * k)) for k in range(4)]
+    refs = [render(ctx, ISO, u, v, tf)[0] for u in us]
+    ctx.set_uniforms(vt.to_capi_uniforms(us[0]))
+    for world in (2, 3):
+        full = np.zeros((H, W, 4), f32)
+        for rank in range(world):
+            cnt = ctx.tile_count(rank, world)
+            ctx.render_tiles(capi.ISO, rank, world)
+            if cnt == 0:
+                continue
+            tl, _ = ctx.download_tiles(cnt)
+            tl = tl.reshape(cnt, capi.TILE, capi.TILE, 4)
+            tiles_x = (W + capi.TILE - 1) // capi.TILE
+            for k in range(cnt):
+                t = rank + k * world
+                ty, tx = divmod(t, tiles_x)
+                y0, x0 = ty * capi.TILE, tx * capi.TILE
+                h, w = min(capi.TILE, H - y0), min(capi.TILE, W - x0)
+                full[y0:y0 + h, x0:x0 + w] = tl[k, :h, :w]
+        assert np.array_equal(vt.bits(full), vt.bits(refs[0])), world
+    others = [capi.Context(W, H, 0) for _ in range(4)]
+    try:
+        ctx.render_batch_async(capi.ISO, [vt.to_capi_uniforms(u) for u in us], [o.frame_device_ptr() for o in others], ctx.stream(0))
+        ctx.counters()
+        for o, r in zip(others, refs):
+            assert np.array_equal(vt.bits(o.download()[0]), vt.bits(r))
+        # the level is taken at enqueue: a frame at 0.3 on stream 0, one at 0.6 on stream 1, then 0.3 again on stream 1
+        ref_hi = render(ctx, 0.6, us[0], v, tf)[0]
+        assert not np.array_equal(vt.bits(ref_hi), vt.bits(refs[0]))
+        ctx.set_uniforms(vt.to_capi_uniforms(us[0]))
+        levels = [(ISO, 0), (0.6, 1), (ISO, 2)]
+        for lvl, k in levels:
+            ctx.set_iso_value(lvl)
+            ctx.render_async(capi.ISO, others[k].frame_device_ptr(), ctx.stream(min(k, 1)))
+        ctx.set_iso_value(0.9)
+        ctx.counters()
+        ctx.render_async(capi.ISO, others[3].frame_device_ptr(), ctx.stream(0))  # (stream 0's frames have finished behind this one)
+        ctx.counters()
+        for lvl, k in levels:
+            assert np.array_equal(vt.bits(others[k].download()[0]), vt.bits(refs[0] if lvl == ISO else ref_hi)), (lvl, k)
+    finally:
+        for o in others:
+            o.close()
+
+
+def test_volume_edit_and_async_colour_edit():
+    """After vr_volume_upload of another volume the brick records are rebuilt and the next frame matches the restatement; an
+    asynchronous colour-table edit followed by an ISO launch on the same stream shows the new surface colour."""
+    tf = tf_pair()
+    u = uniforms((24, 24, 24))
+    a = air_and_core()
+    b = air_and_core()
+    b[..., 3] *= f32(0.5)
+    b[2:5, 3:6, 18:21, 3] = f32(1.0)
+    with capi.Context(W, H, 0) as ctx, capi.Context(W, H, 0) as out:
+        for v in (a, b, a):
+            frag, (n, cov, _) = render(ctx, 0.5, u, v, tf)
+            ref, n_ref, cov_ref = ir.frame(u, W, H, v, tf, 0.5)
+            assert np.array_equal(vt.bits(frag), vt.bits(ref))
+            assert (n, cov) == (n_ref, cov_ref)
+        before, _ = render(ctx, 0.5, u, a, tf)
+        edited = hr.default_color_tf(64).copy()
+        edited[:, 0] = f32(0.2)
+        ctx.tf_upload_async(0, color=edited, stream=ctx.stream(1))
+        ctx.render_async(capi.ISO, out.frame_device_ptr(), ctx.stream(1))
+        ctx.counters()
+        got = out.download()[0]
+        want = ir.frame(u, W, H, a, (tf[0], edited), 0.5)[0]
+        assert np.array_equal(vt.bits(got), vt.bits(want))
+        assert not np.array_equal(vt.bits(got), vt.bits(before))
+
+
+def test_no_interference_and_choice():
+    """LIGHT frames, the measured choice and vr_skip_field are unchanged by ISO launches; an ISO launch has no measured choice and
+    no distance field."""
+    vl, tfl = vt.scene(capi.LIGHT, n=16)
+    u = uniforms((16, 16, 16))
+    with capi.Context(W, H, 0) as ctx:
+        before = vt.gpu_render(ctx, capi.LIGHT, u, vl, tfl)
+        choice0 = ctx.kernel_choice()
+        field0 = ctx.skip_field(capi.LIGHT)
+        for fl in (0, 1):
+            ctx.set_kernel_flavour(fl)
+            ctx.render(capi.ISO)
+            assert ctx.kernel_choice()[0] == [] and ctx.last_kernel_flavour() == (22 if fl else 21)
+        ctx.set_kernel_flavour(0)
+        with pytest.raises(capi.VrError) as e:
+            ctx.skip_field(capi.ISO)
+        assert e.value.code == capi.VR_ERR_NOT_READY
+        after = vt.gpu_render(ctx, capi.LIGHT, u, vl, tfl)
+        assert ctx.kernel_choice()[0] == choice0[0]
+        field1 = ctx.skip_field(capi.LIGHT)
+        assert np.array_equal(vt.bits(before[0]), vt.bits(after[0])) and before[2] == after[2]
+        assert all(np.array_equal(np.asarray(x), np.asarray(y)) for x, y in zip(field0, field1))
+
+
+def test_c3_seeded_pixels():
+    """Full size, through the host surface: C3's 512^3 phantom at 1920 x 1080 started as an IsoSurfaceApp at level 0.3 (host
+    Application.OnStart(ISO, ...), set_iso_value, OnUpdate), 2 048 seeded pixels of the frame exact against the restatement."""
+    from volumerendering_amd import host, synth, workloads as wl
+    n, W3, H3, _ = wl.WORKLOADS["C3"]
+    with host.Application(W3, H3, 0) as app:
+        vol = host.VolumeFile.from_raw(synth.ct_phantom_raw_fast(n))
+        app.OnStart(capi.ISO, [vol])
+        app.set_iso_value(0.3)
+        app.camera().SetOrbit(*wl.CAMERA)
+        app.OnUpdate()
+        app.OnRender()
+        frag, _, samples = app.ReadFrame()
+        ub, volumes, tfs = wl.oracle_inputs(app, [vol])
+        assert app.context().last_kernel_flavour() == 21
+        cov_all = app.context().counters()[1]
+    u = hr.Uniforms.from_buffer_copy(ub)
+    rng = np.random.default_rng(2048)
+    pix = np.stack([rng.integers(0, W3, 2048), rng.integers(0, H3, 2048)], 1)
+    r = ir.march(u, W3, H3, volumes[0], tfs[0], 0.3, pix)
+    got = frag[pix[:, 1], pix[:, 0]]
+    assert r["covered"].sum() > 100 and samples > 0 and cov_all > 0
+    assert np.array_equal(vt.bits(got), vt.bits(r["frag"])), float(np.nanmax(np.abs(got - r["frag"])))

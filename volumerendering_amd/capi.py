@@ -22,8 +22,9 @@ VR_ERR_OOM = -5
 
 BASIC, LIGHT, VOLUME_MASK, THREE_FILES, MULTI_CTRT, TF_CALIB, ILLUSTRATIVE, LIGHT_INSHADER = range(8)
 MIP, MINIP, AVERAGE = 8, 9, 10  # intensity projections of volume slot 0 (include/vr.h)
+ISO = 11  # shaded isosurface of volume slot 0 at the level of Context.set_iso_value (include/vr.h)
 VARIANT_NAMES = ["BASIC", "LIGHT", "VOLUME_MASK", "THREE_FILES", "MULTI_CTRT", "TF_CALIB", "ILLUSTRATIVE", "LIGHT_INSHADER",
-                 "MIP", "MINIP", "AVERAGE"]
+                 "MIP", "MINIP", "AVERAGE", "ISO"]
 TILE = 64
 ARITH_SEPARATE, ARITH_FUSED = 0, 1
 
@@ -39,6 +40,7 @@ ABI_SYMBOLS = [
     "vr_set_kernel_timing", "vr_present_tiles_async", "vr_kernel_choice",
     "vr_present_packed_async", "vr_unpack_tiles_bgra8_async",
     "vr_tf_upload_opacity_async", "vr_tf_upload_color_async", "vr_skip_field", "vr_unbounded_box_launches",
+    "vr_set_iso_value",
 ]
 
 
@@ -123,6 +125,7 @@ def load() -> C.CDLL:
     lib.vr_last_kernel_flavour.argtypes = [vp]
     lib.vr_set_volume_layout.argtypes = [vp, i32]
     lib.vr_set_arithmetic.argtypes = [vp, i32]
+    lib.vr_set_iso_value.argtypes = [vp, C.c_float]
     lib.vr_present_async.argtypes = [vp, vp, vp, vp]
     lib.vr_present_tiles_async.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
     lib.vr_hint_frames_in_flight.argtypes = [vp, i32]
@@ -374,6 +377,10 @@ class Context:
     def set_arithmetic(self, mode: int):
         """ARITH_SEPARATE (0, default) or ARITH_FUSED (1): per-sample a * b + c with two roundings or one (include/vr.h)."""
         self._chk(self.lib.vr_set_arithmetic(self.h, mode))
+
+    def set_iso_value(self, iso: float):
+        """The level of ISO launches enqueued after this call (default 0.5; finite values only, include/vr.h)."""
+        self._chk(self.lib.vr_set_iso_value(self.h, iso))
 
     def set_volume_layout(self, mode: int):
         """0 bricked copy (default), 1 the reference's vec4 voxels only, 3 x-fastest voxels + density plane (2 was removed)."""

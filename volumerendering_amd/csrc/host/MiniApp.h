@@ -110,6 +110,29 @@ private:
     Light m_Light1{vrm::vec4(0.0f, 5.0f, 0.0f, 1.0f), vrm::vec4(0.1f), vrm::vec4(1.0f)};
 };
 
+// Shaded isosurface (VR_VARIANT_ISO; no scene of the reference): BasicVolLightApp's preparation, light and tables, drawn at the level
+// SetIsoValue sets (default 0.5), handed to the ray-marcher in OnStart and in every OnUpdate.
+class IsoSurfaceApp : public BasicVolLightApp {
+public:
+    explicit IsoSurfaceApp(VolumePtr ct, int tfResolution = 4096) : BasicVolLightApp(std::move(ct), tfResolution) {}
+    void OnStart(vr_ctx* ctx) override
+    {
+        m_Ctx = ctx;
+        BasicVolLightApp::OnStart(ctx);  // (calls OnUpdate)
+    }
+    void OnUpdate() override
+    {
+        BasicVolLightApp::OnUpdate();
+        if (m_Ctx) Check(vr_set_iso_value(m_Ctx, m_Iso));
+    }
+    int Variant() const override { return VR_VARIANT_ISO; }
+    void SetIsoValue(float iso) { m_Iso = iso; }
+    float GetIsoValue() const { return m_Iso; }
+private:
+    vr_ctx* m_Ctx = nullptr;
+    float m_Iso = 0.5f;
+};
+
 // App/src/miniapps/VolumeMaskApp.cpp:12-65: CT gradient(true) BEFORE normalisation, TF 256 (CT) / 4096 (RT),
 // bind order mask, RT, CT.
 class VolumeMaskApp : public MiniApp {

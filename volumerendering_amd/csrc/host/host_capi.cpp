@@ -1,6 +1,7 @@
 // host_capi.cpp -- flat C wrapper over the C++ host surface (VolumeFile / OpacityTF / ColorTF / Camera /
 // MiniApp scenes / Application) so that the pytest harness and bench.py can drive the same objects a C++
 // application would.  Handles are opaque pointers; every function is exception-safe at the boundary.
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -318,12 +319,22 @@ int vrh_app_start(void* a, int variant, void* v0, void* v1, void* v2, int tf_res
         case VR_VARIANT_MIP:
         case VR_VARIANT_MINIP:
         case VR_VARIANT_AVERAGE: scene = std::make_unique<ProjectionApp>(vol(v0), variant, tf_res > 0 ? tf_res : 256); break;
+        case VR_VARIANT_ISO: scene = std::make_unique<IsoSurfaceApp>(vol(v0), tf_res > 0 ? tf_res : 4096); break;
         default: return VR_ERR_INVALID_ARG;
         }
         return app->OnStart(std::move(scene));
     } catch (...) {
         return VR_ERR_INVALID_ARG;
     }
+}
+// IsoSurfaceApp::SetIsoValue of the running scene (taken over by the next OnUpdate); VR_ERR_NOT_READY when the scene is no isosurface
+int vrh_app_set_iso_value(void* a, float iso)
+{
+    auto* p = dynamic_cast<IsoSurfaceApp*>(static_cast<Application*>(a)->GetApp());
+    if (!p) return VR_ERR_NOT_READY;
+    if (!std::isfinite(iso)) return VR_ERR_INVALID_ARG;
+    p->SetIsoValue(iso);
+    return VR_OK;
 }
 void vrh_app_set_prepare_on_device(void* a, int on) { static_cast<Application*>(a)->m_PrepareOnDevice = on != 0; }
 int vrh_app_update(void* a) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->OnUpdate(); }) }

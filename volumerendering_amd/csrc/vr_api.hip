@@ -9,6 +9,7 @@ namespace vrf {
 void launch_march(const vr::LaunchDesc& L, hipStream_t s, const vr::MarchBatch& B);
 }
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -187,9 +188,10 @@ struct vr_ctx {
                               // onto small volumes by the tests; 0 = what the hardware reaches, just below 4 GiB)
     double active_fraction = 1.0;  // share of bricks that are not inert, of the distance field in use
     float abox[6] = {-3.0e38f, -3.0e38f, -3.0e38f, 3.0e38f, 3.0e38f, 3.0e38f};  // uvw box around the active bricks of that field (MarchParams::abox)
-    // Intensity projections (vr_proj.h): (min, max) of volume 0 per empty-space brick and over the whole volume, rebuilt on the launch's
-    // stream by the first skipping projection launch after a volume change (proj_epoch = the brick_epoch they were built at).  Launches on
-    // other streams wait once for the event behind the build (proj_seen), none after a draining call (proj_pending).
+    // Intensity projections (vr_proj.h) and the isosurface (vr_iso.h): (min, max) of volume 0 per empty-space brick and over the whole
+    // volume, rebuilt on the launch's stream by the first skipping projection or isosurface launch after a volume change (proj_epoch = the
+    // brick_epoch they were built at).  Launches on other streams wait once for the event behind the build (proj_seen), none after a
+    // draining call (proj_pending).
     float2* proj_rec = nullptr;
     size_t proj_rec_cap = 0;  // bytes
     float2* proj_range = nullptr;
@@ -199,7 +201,8 @@ struct vr_ctx {
     bool proj_pending = false;
     hipStream_t proj_seen[kEditSeen] = {};
     int proj_seen_next = 0;
-    bool last_proj = false;  // the last launch was a projection (vr_kernel_choice reports no candidates)
+    bool last_proj = false;  // the last launch was a projection or an isosurface (vr_kernel_choice reports no candidates)
+    float iso = 0.5f;        // VR_VARIANT_ISO's level (vr_set_iso_value), copied into MarchParams::iso at enqueue
     std::string err;
 };
 
@@ -253,7 +256,8 @@ void variant_needs(int variant, int* nvol, int* ntf)
     case VR_VARIANT_LIGHT_INSHADER:
     case VR_VARIANT_MIP:
     case VR_VARIANT_MINIP:
-    case VR_VARIANT_AVERAGE: *nvol = 1; *ntf = 1; break;
+    case VR_VARIANT_AVERAGE:
+    case VR_VARIANT_ISO: *nvol = 1; *ntf = 1; break;
     case VR_VARIANT_VOLUME_MASK: *nvol = 3; *ntf = 2; break;
     case VR_VARIANT_THREE_FILES: *nvol = 2; *ntf = 2; break;  // the mask (slot 2) is bound but never sampled
     case VR_VARIANT_MULTI_CTRT: *nvol = 2; *ntf = 2; break;
@@ -581,6 +585,7 @@ void fill_launch_params(const vr_ctx* c, MarchParams& P, const vr_uniforms& u0, 
     P.n_tiles = tile_count(c, rank, world);
     P.packed = packed ? 1 : 0;
     P.n_blocks = P.n_tiles * kBlocksPerTile;
+    P.iso = c->iso;  // (every frame of a batch: fill_batch copies P)
 }
 
 // the bricked copies (layout 0) are what the gathers read
@@ -851,7 +856,7 @@ int prepare_skip(vr_ctx* c, int variant, hipStream_t s, MarchParams& P)
     return VR_OK;
 }
 
-// The skipping projection (flavour 19): fills P's brick fields with volume 0's range records, (re)builds them and the whole volume's range
+// The skipping projection (flavour 19) and isosurface (21): fills P's brick fields with volume 0's range records, (re)builds them and the whole volume's range
 // on `s` when a volume changed since they were built (no host wait), and orders a launch on another stream behind that build once.
 // Returns the whole volume's range (device), or nullptr after a failure (c->err says why).
 const float2* prepare_proj(vr_ctx* c, hipStream_t s, MarchParams& P)
@@ -908,6 +913,8 @@ int choose_flavour(vr_ctx* c, int fl, int variant, int n_frames, int rank, int w
 {
     // the projections: 1 asks for the form without skipping (20), everything else runs as the skipping one (19); nothing is measured
     if (is_projection(variant)) return fl == 1 ? 20 : 19;
+    // the isosurface: the same rule, 22 without skipping, 21 with it
+    if (variant == VR_VARIANT_ISO) return fl == 1 ? 22 : 21;
     const bool auto_choice = fl == 0;
     const double rays = rays_per_lane(c, rank, world, c->frames_in_flight * n_frames);
     const bool short_chains = E.chain_known != 0 && E.chain_known - 1 < 128;
@@ -1014,6 +1021,8 @@ KernelForm kernel_form(int fl, int variant)
     case 18: return {D::kPlain, 0, false, false, true, 0u};
     case 19:
     case 20: return {D::kProj, 0, false, false, false, 0u};
+    case 21:
+    case 22: return {D::kIso, 0, false, false, false, 0u};
     default: return {D::kPlain, 0, false, false, false, 0u};  // 1, 6
     }
 }
@@ -1159,9 +1168,9 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
     const int fl = choose_flavour(c, requested, variant, n_frames, rank, world, packed, E);
     c->last_flavour = fl;
     const KernelForm form = kernel_form(fl, variant);
-    c->last_proj = form.family == LaunchDesc::kProj;
+    c->last_proj = form.family == LaunchDesc::kProj || form.family == LaunchDesc::kIso;
     const float2* vrange = nullptr;
-    if (fl == 19) {
+    if (fl == 19 || fl == 21) {
         vrange = prepare_proj(c, s, P);
         if (!vrange) return VR_ERR_HIP;
     }
@@ -2285,6 +2294,14 @@ int vr_set_arithmetic(vr_ctx* c, int mode)
     return VR_OK;
 }
 
+int vr_set_iso_value(vr_ctx* c, float iso)
+{
+    if (!c) return VR_ERR_INVALID_ARG;
+    if (!std::isfinite(iso)) return fail(c, VR_ERR_INVALID_ARG, "vr_set_iso_value: the level must be finite");
+    c->iso = iso;
+    return VR_OK;
+}
+
 int vr_set_volume_layout(vr_ctx* c, int mode)
 {
     if (!c) return VR_ERR_INVALID_ARG;
@@ -2306,7 +2323,7 @@ int vr_volume_layout(vr_ctx* c, int slot, int* flags)
 int vr_kernel_choice(vr_ctx* c, int flavours[6], float ms_per_launch[6], int* chosen)
 {
     if (!c) return VR_ERR_INVALID_ARG;
-    if (c->last_proj) {  // (the projections' forms are never measured)
+    if (c->last_proj) {  // (the projections' and the isosurface's forms are never measured)
         if (chosen) *chosen = -1;
         return 0;
     }

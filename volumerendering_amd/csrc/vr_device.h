@@ -122,6 +122,8 @@ struct MarchParams {
     float4* out;
     unsigned long long* block_counts;  // [blocks of this frame][kBlockRecord]: composited, covered, fetched, t0, t1, hw id
     unsigned batch_n;        // frames the launch carries (1 .. kBatchMax): see MarchBatch
+    float iso;               // VR_VARIANT_ISO: the level (vr_set_iso_value) when the launch was enqueued (in the tail padding after
+                             // batch_n: the size and every other offset of the struct are what they were without it)
 };
 
 // One launch may carry up to kBatchMax frames of the same scene and shape (different uniforms, output and record buffers).
@@ -149,11 +151,11 @@ struct PwQueue {
 // What enqueue_render decided about one march launch; handed to launch_march of the arithmetic mode's translation unit
 // (vr_launch.h: namespace vr = separately rounded multiply-adds, namespace vrf = fused).  Host only.
 struct LaunchDesc {
-    enum Family { kPlain, kDp, kPw, kP2, kLt, kProj };
+    enum Family { kPlain, kDp, kPw, kP2, kLt, kProj, kIso };
     int variant;      // vr_variant
     Family family;    // march_kernel, march_dp_kernel, march_pw_kernel (persistent wavefronts: grid = workgroups, the packets come
                       // from `queue`), march_p2_kernel (the same, corner loads two steps ahead), march_lt_kernel (LDS tiles, lit shader),
-                      // march_proj_kernel (vr_proj.h: the intensity projections)
+                      // march_proj_kernel (vr_proj.h: the intensity projections), march_iso_kernel (vr_iso.h: the isosurface)
     bool off32;       // every bound volume < 4 GiB: 32-bit byte offsets
     int lanes;        // kDp: lanes per ray (2 / 4)
     bool pipe;        // kDp / kPw: the next round's / step's corner loads software-pipelined
@@ -164,7 +166,7 @@ struct LaunchDesc {
     PwQueue queue;
     dim3 grid, block;
     const float2* vrange;  // kProj: (min, max) of volume 0 (vr_proj.h); with `proj_skip` the brick records are MarchParams::bricks
-    bool proj_skip;        // kProj: the skipping form (march_proj_kernel<.., SKIP = true, ..>)
+    bool proj_skip;        // kProj / kIso: the skipping form (march_proj_kernel<.., SKIP = true, ..>, march_iso_kernel<.., true, ..>)
 };
 
 }  // namespace vr

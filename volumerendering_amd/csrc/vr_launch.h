@@ -20,6 +20,8 @@
 #include "vr_lt.h"
 // Intensity projections (MIP / MinIP / AIP of volume slot 0; flavours 19 and 20)
 #include "vr_proj.h"
+// The shaded isosurface of volume slot 0 (flavours 21 and 22; it reads the projections' brick records)
+#include "vr_iso.h"
 
 #include <type_traits>
 
@@ -110,8 +112,19 @@ void launch_proj(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
     else launch(std::integral_constant<int, kProjAvg>{});
 }
 
+// the isosurface: skipping x addressing x frames per launch
+void launch_iso(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
+{
+    with_flags([&](auto S, auto O, auto BT) { hipLaunchKernelGGL((march_iso_kernel<O, S, BT>), L.grid, L.block, 0, s, B); },
+               L.proj_skip, L.off32, B.n_frames > 1);
+}
+
 void launch_march(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
 {
+    if (L.family == LaunchDesc::kIso) {
+        launch_iso(L, s, B);
+        return;
+    }
     if (L.family == LaunchDesc::kProj) {
         launch_proj(L, s, B);
         return;
