@@ -411,7 +411,13 @@ int vr_last_block_trace(vr_ctx* ctx, uint64_t* out, int capacity);
  * The isosurface (ISO) likewise (0 candidates after an ISO launch):
  *   21  march_iso_kernel with exact skipping (csrc/vr_iso.h): a step whose brick's maximum density is below the level loads
  *       nothing.  Flavour 0 runs as 21, and so does every other flavour but 1.
- *   22  march_iso_kernel without skipping: every in-box step up to the hit is fetched.  Flavour 1 runs as 22.            */
+ *   22  march_iso_kernel without skipping: every in-box step up to the hit is fetched.  Flavour 1 runs as 22.
+ * LIGHT with shadows on (vr_set_shadows) likewise (0 candidates after such a launch; nothing is measured against LIGHT's forms):
+ *   23  march_shadow_kernel and shadow_build_kernel with exact skipping by LIGHT's distance field (csrc/vr_shadow.h): a step in
+ *       an inert brick loads nothing, in the march and in the light volume's build, and a blended sample of opacity exactly 0
+ *       is not shaded.  Flavour 0 runs as 23, and so does every other flavour but 1.  (When LIGHT would not skip -- a
+ *       non-finite colour table or light, no zero prefix of the opacity table -- 23 runs 24's kernels.)
+ *   24  both without skipping: every in-box step up to the cut-off is fetched and shaded.  Flavour 1 runs as 24.          */
 int vr_set_kernel_flavour(vr_ctx* ctx, int flavour);
 
 /* What the default's measured choice (flavour 0) knows about the launch shape it was asked for last: the candidates' flavours, the
@@ -435,6 +441,40 @@ int vr_set_arithmetic(vr_ctx* ctx, int mode);
 /* Threshold of VR_VARIANT_ISO for launches enqueued after this call (default 0.5f).  Finite values only:
  * NaN / +-inf -> VR_ERR_INVALID_ARG, the previous value stays. */
 int vr_set_iso_value(vr_ctx* ctx, float iso);
+
+/* Shadows of the lit shader (VR_VARIANT_LIGHT only; every other variant ignores the setting).  grid_divisor 0 = off (default):
+ * LIGHT is exactly what it was.  1, 2, 4 or 8 = one light-volume texel per divisor^3 voxels.  opacity_scale: finite and >= 0.
+ * Otherwise VR_ERR_INVALID_ARG, and the previous setting stays.  Applies to launches enqueued after the call (captured at enqueue,
+ * as vr_set_iso_value is).
+ *
+ * Light volume.  Inputs: volume slot 0 (nx, ny, nz), divisor r and scale s = opacity_scale, the launch's light_pos L and its clip
+ * bounds bmin / bmax (IsInSampleCoords), TF slot 0's opacity table as the launch captured it, the context's arithmetic mode.
+ *   Grid G = (ceil(nx/r), ceil(ny/r), ceil(nz/r)), x fastest.  Light in texture space l = (L.x + 0.5f, L.y + 0.5f, 0.5f - 2.0f * L.z)
+ *   (setup_ray's world-to-uvw map of the box).  Step length h = 1.0f / (float)max(Gx, Gy, Gz).  Texel centre
+ *   c = (((float)i + 0.5f) / (float)Gx, ...).  D = l - c, len = length3s(D), dir = normalize3s(D), step = dir * h (ray-placement
+ *   forms: separately rounded in both arithmetic modes).  lim = len / h, K = lim < 65536.0f ? (int)lim : 65536 (NaN: 65536).
+ *   T = 1.0f, q = c; for k = 1..K: q = q + step (a rounded addition per component); stop if any component of q is < 0, > 1 or
+ *   NaN; if q is inside the clip box: d = BASIC's trilinear .a fetch at q, a = BASIC's opacity look-up of d, a' = s * a,
+ *   a' = a' > 1 ? 1 : a', a' = a' > 0 ? a' : 0 (NaN -> 0), T = T * (1.0f - a'); stop if T < 0x1p-10f (T is kept as it is).
+ *   The texel stores T.  The texture-coordinate and lerp expressions follow the arithmetic mode, as every per-sample expression.
+ * Shadowed march: exactly LIGHT -- positions, world positions, variable step, jitter, the cut-off dst.a < 1.0, fragment modes
+ *   1-4, the blend and the counters -- except in each blended sample's shading: S = the light volume sampled at the sample's uvw
+ *   position p with the density sampler's texel pairs and lerps (linear, clamp-to-edge; the arithmetic mode's form), and the
+ *   diffuse term dif_c * m of the shading becomes dif_c * (m * S), m * S rounded first.  `fetched` counts volume samples only.
+ *   Consequences: s = 0 gives T == 1 everywhere, lerps of a constant grid are exact, m * 1 = m: a shadowed frame at s = 0 is
+ *   bit-identical to LIGHT's in both arithmetic modes.  A build step in an inert brick of LIGHT's distance field has opacity
+ *   exactly 0 and leaves T as it is: the skipping build (flavour 23) loads nothing there and stores the same texels.
+ * The context keeps the light volumes of the last 4 keys (volume, opacity table, light, clip box, divisor, scale, arithmetic
+ * mode); a launch whose key has none builds it on its own stream first, behind the launches still reading the entry it reuses.
+ * Every frame of a batched launch must have the same key (VR_ERR_UNSUPPORTED otherwise); a light volume of 4 GiB or more is
+ * VR_ERR_UNSUPPORTED, a failed allocation VR_ERR_OOM: nothing is enqueued in either case.  vr_last_timing's total_ms includes a
+ * build the render enqueued, its kernel_ms and vr_kernel_times do not (the march alone). */
+int vr_set_shadows(vr_ctx* ctx, int grid_divisor, float opacity_scale);
+
+/* The light volume that a LIGHT launch enqueued now would read (the context's uniforms).  It is built if needed, synchronously, and
+ * the call drains the device, like vr_skip_field.  Copies min(capacity, n) floats in x-fastest order, writes the grid to dims[3]
+ * and returns n.  VR_ERR_NOT_READY when shadows are off, volume 0 / TF 0 are missing or no uniforms were set. */
+int vr_shadow_volume(vr_ctx* ctx, float* out, size_t capacity, int dims[3]);
 
 /* Volume layout in HBM (A/B measurements; frames and counts are bit-identical in every mode).
  *   0  default: the march kernels gather from a BRICKED copy of every slot -- the vec4 voxels and a scalar f32 density plane

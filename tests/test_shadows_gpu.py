@@ -1,0 +1,404 @@
+"""GPU side of the lit shader's shadows (vr_set_shadows, csrc/vr_shadow.h): at opacity scale 0 the frames are LIGHT's, bit for bit, in
+every form, layout, arithmetic mode and launch shape; the light volume equals the float32 restatement's build (shadow_ref.py) on
+hostile inputs; shadowed frames equal the restated march fed the GPU's light volume; the ring of light volumes follows edits, moving
+lights and launches in flight; argument checks, C3 at full size, and the host scene."""
+import math
+
+import numpy as np
+import pytest
+
+import host_ref as hr
+import oracle_binding as ob
+import shadow_ref as sr
+import vrtest as vt
+from volumerendering_amd import capi
+
+pytestmark = pytest.mark.gpu
+f32 = np.float32
+W, H = 128, 64  # two 64 x 64 tiles: a frame buffer holds a rank's packed tiles at world 1 and 2
+
+
+def phantom(n=16):
+    return vt.make_volume("phantom", n, gradient=True)
+
+
+def tf_pair(res=64):
+    return hr.default_opacity_tf(res), hr.default_color_tf(res)
+
+
+def shape_of(v):
+    return v.shape[2], v.shape[1], v.shape[0]
+
+
+def uniforms(shape=(16, 16, 16), **over):
+    step, count = hr.stepping_params(*shape)
+    kw = dict(steps_count=count, step_size=step)
+    kw.update(over)
+    return hr.make_uniforms(W, H, **kw)
+
+
+def setup(ctx, u, v, tf):
+    ctx.volume_upload(0, v)
+    ctx.tf_upload(0, tf[0], tf[1])
+    ctx.set_uniforms(vt.to_capi_uniforms(u))
+
+
+def render(ctx):
+    ctx.render(capi.LIGHT)
+    frag, _, _ = ctx.download()
+    return frag, ctx.counters()
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = capi.Context(W, H, 0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def others():
+    cs = [capi.Context(W, H, 0) for _ in range(6)]
+    yield cs
+    for c in cs:
+        c.close()
+
+
+def shapes(ctx, others, us):
+    """The frame (or raw packed tiles) of every launch shape of LIGHT: sync, async on stream 1, a batch of two, sync tiles of world 2,
+    async tiles, a tiles batch of two (us: two uniforms of one light and clip box)."""
+    out = {}
+    ctx.set_uniforms(vt.to_capi_uniforms(us[0]))
+    out["sync"] = render(ctx)[0]
+    ctx.render_async(capi.LIGHT, others[0].frame_device_ptr(), ctx.stream(1))
+    ctx.counters()
+    out["async"] = others[0].download()[0]
+    cu = [vt.to_capi_uniforms(u) for u in us]
+    ctx.render_batch_async(capi.LIGHT, cu, [others[1].frame_device_ptr(), others[2].frame_device_ptr()], ctx.stream(0))
+    ctx.counters()
+    out["batch0"], out["batch1"] = others[1].download()[0], others[2].download()[0]
+    for rank in range(2):
+        ctx.render_tiles(capi.LIGHT, rank, 2)
+        out[f"tiles{rank}"] = ctx.download_tiles(ctx.tile_count(rank, 2))[0]
+    ctx.render_tiles_async(capi.LIGHT, 0, 1, others[3].frame_device_ptr(), ctx.stream(2))
+    ctx.counters()
+    out["tiles_async"] = others[3].download()[0]
+    ctx.render_tiles_batch_async(capi.LIGHT, 0, 1, cu, [others[4].frame_device_ptr(), others[5].frame_device_ptr()], ctx.stream(3))
+    ctx.counters()
+    out["tiles_batch0"], out["tiles_batch1"] = others[4].download()[0], others[5].download()[0]
+    ctx.set_uniforms(vt.to_capi_uniforms(us[0]))
+    return out
+
+
+def test_scale_zero_is_light(ctx, others):
+    """Opacity scale 0: frames of flavours 23 and 24 x layouts 0 / 1 / 3 x every launch shape equal unshadowed LIGHT's (and the
+    oracle's LIGHT frame), in both arithmetic modes, with LIGHT's composited and covered counts."""
+    v, tf = phantom(), tf_pair()
+    us = [uniforms(yaw=0.6, toggles=(0, 1, 0, 0)), uniforms(yaw=1.4, pitch=-0.3, toggles=(0, 1, 0, 0))]
+    setup(ctx, us[0], v, tf)
+    try:
+        for mode in (capi.ARITH_SEPARATE, capi.ARITH_FUSED):
+            ctx.set_arithmetic(mode)
+            with ob.arithmetic(ob.FUSED if mode == capi.ARITH_FUSED else ob.SEPARATE):
+                ref, n_ref, _ = ob.render(ob.LIGHT, us[0], [v], [tf], W, H, nthreads=4)
+            for layout in (0, 1, 3):
+                ctx.set_volume_layout(layout)
+                ctx.set_shadows(0)
+                ctx.set_kernel_flavour(0)
+                plain = shapes(ctx, others, us)
+                _, (n_plain, cov_plain, _) = render(ctx)
+                assert np.array_equal(vt.bits(plain["sync"]), vt.bits(ref)) and n_plain == n_ref
+                for fl in (0, 1):
+                    ctx.set_kernel_flavour(fl)
+                    ctx.set_shadows(2, 0.0)
+                    got = shapes(ctx, others, us)
+                    frag, (n, cov, _) = render(ctx)
+                    assert ctx.last_kernel_flavour() == (24 if fl == 1 else 23)
+                    assert ctx.kernel_choice()[0] == []
+                    assert (n, cov) == (n_plain, cov_plain), (mode, layout, fl)
+                    for k in plain:
+                        assert np.array_equal(vt.bits(got[k]), vt.bits(plain[k])), (mode, layout, fl, k)
+    finally:
+        ctx.set_shadows(0)
+        ctx.set_kernel_flavour(0)
+        ctx.set_volume_layout(0)
+        ctx.set_arithmetic(capi.ARITH_SEPARATE)
+
+
+def hostile_opacity(res=64):
+    o = np.linspace(-0.5, 1.6, res).astype(f32)
+    o[::7] = f32(-0.25)
+    return o
+
+
+def nan_phantom():
+    v = phantom()
+    v[4:6, 7, 2:9, 3] = np.nan
+    return v
+
+
+def center_light(n, r):
+    """A world light position exactly on the centre of texel (3, G/2, G - 3) of a cube of n voxels at divisor r."""
+    g = (n + r - 1) // r
+    c = [(i + 0.5) / g for i in (3, g // 2, g - 3)]
+    return (c[0] - 0.5, c[1] - 0.5, (0.5 - c[2]) / 2.0), (3, g // 2, g - 3)
+
+
+BUILD_CASES = [
+    # (id, volume, opacity table, scale, uniform overrides)
+    ("phantom", phantom, None, 1.0, {}),
+    ("nan", lambda: nan_phantom(), None, 1.0, {}),
+    ("opacity_range", phantom, hostile_opacity(), 1.0, {}),
+    ("light_inside", phantom, None, 2.0, dict(light_pos=(0.1, -0.05, 0.02, 1.0))),
+    ("light_far", phantom, None, 1.0, dict(light_pos=(1.0e30, 0.0, 0.0, 1.0))),
+    ("scale_huge", phantom, None, 1.0e30, {}),
+    ("clip_all", phantom, None, 1.0, dict(clip_x=(0.6, 0.6))),
+    ("clip_some", phantom, None, 1.0, dict(clip_y=(0.2, 0.1), clip_z=(0.0, 0.3))),
+    ("thin_z", lambda: ob.precompute_gradient(ob.normalize_data(hr.raw_to_vec4(
+        np.random.default_rng(5).integers(0, 4096, size=(3, 16, 20)).astype(np.uint16)))), None, 1.0, {}),
+]
+
+
+@pytest.mark.parametrize("cid,make,opacity,scale,over", BUILD_CASES, ids=[c[0] for c in BUILD_CASES])
+def test_build_matches_restatement(ctx, cid, make, opacity, scale, over):
+    """vr_shadow_volume at divisors 1, 2, 4 equals shadow_ref.build (separate arithmetic); the skipping build (flavour 23) and the
+    plain one (24) store the same texels; the fused mode's texels are within 2e-3 of the separate mode's."""
+    v = make()
+    tf = tf_pair()
+    if opacity is not None:
+        tf = (opacity, tf[1])
+    u = uniforms(shape_of(v), **over)
+    setup(ctx, u, v, tf)
+    lo, hi = sr.clip_box(u)
+    try:
+        for r in (1, 2, 4):
+            ctx.set_shadows(r, scale)
+            ctx.set_kernel_flavour(0)
+            got, dims = ctx.shadow_volume()
+            assert dims == sr.grid_of(v.shape, r)
+            ref = sr.build(v, tf[0], r, scale, u.light_pos[:3], lo, hi)
+            assert np.array_equal(vt.bits(got), vt.bits(ref)), (cid, r, float(np.max(np.abs(got - ref))))
+            ctx.set_kernel_flavour(1)
+            ctx.volume_upload(0, v)  # (a volume change empties the ring: the plain form builds anew)
+            plain, _ = ctx.shadow_volume()
+            assert np.array_equal(vt.bits(plain), vt.bits(got)), (cid, r)
+            ctx.set_arithmetic(capi.ARITH_FUSED)
+            fused, _ = ctx.shadow_volume()
+            ctx.set_arithmetic(capi.ARITH_SEPARATE)
+            assert float(np.max(np.abs(fused - got))) <= 2e-3, (cid, r)
+            if cid == "clip_all":
+                assert np.all(got == f32(1.0))
+            if cid == "scale_huge":
+                assert np.all((got == f32(1.0)) | (got == f32(0.0))) and np.any(got == f32(0.0))
+    finally:
+        ctx.set_shadows(0)
+        ctx.set_kernel_flavour(0)
+        ctx.set_arithmetic(capi.ARITH_SEPARATE)
+
+
+def test_light_on_a_texel_centre(ctx):
+    v, tf = phantom(), tf_pair()
+    L, (i, j, k) = center_light(16, 2)
+    u = uniforms(light_pos=(*L, 1.0))
+    setup(ctx, u, v, tf)
+    ctx.set_shadows(2, 4.0)
+    try:
+        got, _ = ctx.shadow_volume()
+        lo, hi = sr.clip_box(u)
+        assert got[k, j, i] == f32(1.0)
+        assert np.array_equal(vt.bits(got), vt.bits(sr.build(v, tf[0], 2, 4.0, L, lo, hi)))
+        assert np.any(got < f32(1.0))
+    finally:
+        ctx.set_shadows(0)
+
+
+@pytest.mark.parametrize("scale", [1.0, 4.0])
+def test_frames_match_restatement(ctx, scale):
+    """Shadowed frames of flavours 23 and 24 equal the restated march fed the GPU's light volume, with the same composited and covered
+    counts; 23 fetches no more than 24; a shadowed frame's colour is nowhere above LIGHT's (alpha is LIGHT's, bit for bit) and visibly
+    darker behind the phantom's dense parts."""
+    v, tf = phantom(), tf_pair()
+    u = uniforms(toggles=(1, 1, 0, 0), light_pos=(0.3, 2.0, -0.4, 1.0))
+    setup(ctx, u, v, tf)
+    light, _ = render(ctx)
+    try:
+        ctx.set_shadows(2, scale)
+        grid, _ = ctx.shadow_volume()
+        assert np.any(grid < f32(0.5))
+        ref, n_ref, cov_ref = sr.frame(u, W, H, v, tf, grid)
+        fetched = {}
+        for fl in (0, 1):
+            ctx.set_kernel_flavour(fl)
+            frag, (n, cov, f) = render(ctx)
+            assert np.array_equal(vt.bits(frag), vt.bits(ref)), (fl, float(np.max(np.abs(frag - ref))))
+            assert (n, cov) == (n_ref, cov_ref)
+            fetched[fl] = f
+        assert fetched[0] <= fetched[1] == n_ref
+        assert np.array_equal(vt.bits(ref[..., 3]), vt.bits(light[..., 3]))
+        assert np.all(ref[..., :3] <= light[..., :3])
+        assert ref[..., :3].sum() < 0.9 * light[..., :3].sum()
+    finally:
+        ctx.set_shadows(0)
+        ctx.set_kernel_flavour(0)
+
+
+def test_async_edit_moving_light_and_launches_in_flight(ctx, others):
+    """An asynchronous opacity edit on stream 0, then a shadowed launch on stream 1, sees the edited table; moving the light between
+    launches rebuilds; six launches in flight on four streams, each with its own light, all right (the ring's reuse waits for
+    readers); shadows off again gives the untouched LIGHT frame and flavour."""
+    v, tf = phantom(), tf_pair()
+    u = uniforms()
+    setup(ctx, u, v, tf)
+    ctx.set_kernel_flavour(0)
+    light0, _ = render(ctx)
+    fl0 = ctx.last_kernel_flavour()
+    edited = (tf[0] * f32(2.5)).astype(f32)
+    lights = [(0.0, 5.0, 0.0), (3.0, 0.5, 0.0), (-2.0, -2.0, 1.0), (0.0, 0.2, 4.0), (0.4, 0.6, -0.3), (-4.0, 1.0, -1.0)]
+
+    def expect(tfs, lp):
+        with capi.Context(W, H, 0) as fresh:
+            uu = uniforms(light_pos=(*lp, 1.0))
+            setup(fresh, uu, v, tfs)
+            fresh.set_shadows(2, 1.0)
+            return render(fresh)[0]
+
+    try:
+        ctx.set_shadows(2, 1.0)
+        render(ctx)  # (a light volume of the unedited table in the ring)
+        ctx.tf_upload_async(0, opacity=edited, stream=ctx.stream(0))
+        ctx.render_async(capi.LIGHT, others[0].frame_device_ptr(), ctx.stream(1))
+        ctx.counters()
+        assert np.array_equal(vt.bits(others[0].download()[0]), vt.bits(expect((edited, tf[1]), lights[0])))
+        ctx.tf_upload(0, tf[0], tf[1])
+        # moving the light
+        frames = []
+        for lp in lights[:2]:
+            ctx.set_uniforms(vt.to_capi_uniforms(uniforms(light_pos=(*lp, 1.0))))
+            frames.append(render(ctx)[0])
+        assert not np.array_equal(vt.bits(frames[0]), vt.bits(frames[1]))
+        want = [expect(tf, lp) for lp in lights]
+        assert np.array_equal(vt.bits(frames[1]), vt.bits(want[1]))
+        # launches in flight, a light each
+        ctx.hint_frames_in_flight(4)
+        for k, lp in enumerate(lights):
+            ctx.set_uniforms(vt.to_capi_uniforms(uniforms(light_pos=(*lp, 1.0))))
+            ctx.render_async(capi.LIGHT, others[k].frame_device_ptr(), ctx.stream(k % 4))
+        ctx.counters()
+        for k in range(len(lights)):
+            assert np.array_equal(vt.bits(others[k].download()[0]), vt.bits(want[k])), k
+        # shadows off
+        ctx.hint_frames_in_flight(1)
+        ctx.set_shadows(0)
+        ctx.set_uniforms(vt.to_capi_uniforms(u))
+        again, _ = render(ctx)
+        assert np.array_equal(vt.bits(again), vt.bits(light0)) and ctx.last_kernel_flavour() == fl0
+    finally:
+        ctx.hint_frames_in_flight(1)
+        ctx.set_shadows(0)
+        ctx.set_uniforms(vt.to_capi_uniforms(u))
+
+
+def test_batch_of_two_lights_is_refused(ctx, others):
+    v, tf = phantom(), tf_pair()
+    setup(ctx, uniforms(), v, tf)
+    ctx.set_shadows(2, 1.0)
+    try:
+        # (known contents first: a plain LIGHT frame in both buffers)
+        ctx.set_shadows(0)
+        ctx.render_async(capi.LIGHT, others[0].frame_device_ptr(), ctx.stream(0))
+        ctx.render_async(capi.LIGHT, others[1].frame_device_ptr(), ctx.stream(0))
+        ctx.counters()
+        before = [others[k].download()[0] for k in (0, 1)]
+        ctx.set_shadows(2, 1.0)
+        us = [vt.to_capi_uniforms(uniforms()), vt.to_capi_uniforms(uniforms(light_pos=(1.0, 5.0, 0.0, 1.0)))]
+        for call in (lambda: ctx.render_batch_async(capi.LIGHT, us, [others[0].frame_device_ptr(), others[1].frame_device_ptr()], ctx.stream(0)),
+                     lambda: ctx.render_tiles_batch_async(capi.LIGHT, 0, 1, us, [others[0].frame_device_ptr(), others[1].frame_device_ptr()],
+                                                          ctx.stream(0))):
+            with pytest.raises(capi.VrError) as e:
+                call()
+            assert e.value.code == capi.VR_ERR_UNSUPPORTED
+        ctx.counters()
+        for k in (0, 1):
+            assert np.array_equal(vt.bits(others[k].download()[0]), vt.bits(before[k]))
+    finally:
+        ctx.set_shadows(0)
+
+
+def test_argument_checks(ctx):
+    v, tf = phantom(), tf_pair()
+    setup(ctx, uniforms(), v, tf)
+    with pytest.raises(capi.VrError) as e:
+        ctx.shadow_volume()
+    assert e.value.code == capi.VR_ERR_NOT_READY
+    ctx.set_shadows(4, 1.5)
+    try:
+        want, dims = ctx.shadow_volume()
+        frame_want, _ = render(ctx)
+        for div, scale in ((3, 1.0), (-1, 1.0), (16, 1.0), (2, math.nan), (2, -1.0), (2, math.inf)):
+            with pytest.raises(capi.VrError) as e:
+                ctx.set_shadows(div, scale)
+            assert e.value.code == capi.VR_ERR_INVALID_ARG, (div, scale)
+            got, d = ctx.shadow_volume()
+            assert d == dims and np.array_equal(vt.bits(got), vt.bits(want))
+        assert np.array_equal(vt.bits(render(ctx)[0]), vt.bits(frame_want))
+    finally:
+        ctx.set_shadows(0)
+
+
+def test_c3_texels_and_pixels():
+    """Full size, through the host surface: C3's 512^3 phantom at 1920 x 1080 as a BasicVolLightApp with SetShadows(4, 1): about 2 000
+    seeded light-volume texels against shadow_ref.build, and 1 024 seeded pixels of the frame against shadow_ref.march fed the GPU's
+    light volume."""
+    from volumerendering_amd import host, synth, workloads as wl
+    n, W3, H3, _ = wl.WORKLOADS["C3"]
+    with host.Application(W3, H3, 0) as app:
+        vol = host.VolumeFile.from_raw(synth.ct_phantom_raw_fast(n))
+        app.OnStart(capi.LIGHT, [vol])
+        app.set_shadows(4, 1.0)
+        app.camera().SetOrbit(*wl.CAMERA)
+        app.OnUpdate()
+        app.OnRender()
+        frag, _, samples = app.ReadFrame()
+        assert app.context().last_kernel_flavour() == 23
+        grid, dims = app.context().shadow_volume()
+        ub, volumes, tfs = wl.oracle_inputs(app, [vol])
+    u = hr.Uniforms.from_buffer_copy(ub)
+    assert dims == (128, 128, 128) and np.any(grid < f32(0.5)) and samples > 0
+    rng = np.random.default_rng(2000)
+    tex = rng.integers(0, 128, size=(2000, 3))
+    lo, hi = sr.clip_box(u)
+    dens = np.ascontiguousarray(volumes[0][..., 3])
+    T = sr.build(dens, tfs[0][0], 4, 1.0, u.light_pos[:3], lo, hi, texels=tex)
+    got_t = grid[tex[:, 2], tex[:, 1], tex[:, 0]]
+    assert np.array_equal(vt.bits(got_t), vt.bits(T)), float(np.max(np.abs(got_t - T)))
+    pix = np.stack([rng.integers(0, W3, 1024), rng.integers(0, H3, 1024)], 1)
+    ref, _, cov, _ = sr.march(u, W3, H3, volumes[0], tfs[0], grid, pix)
+    got = frag[pix[:, 1], pix[:, 0]]
+    assert cov.sum() > 50
+    assert np.array_equal(vt.bits(got), vt.bits(ref)), float(np.nanmax(np.abs(got - ref)))
+
+
+def test_host_scene_renders_the_c_abi_frame():
+    """A BasicVolLightApp with SetShadows(2, 1.5) renders the frame the C ABI renders from the scene's own inputs."""
+    from volumerendering_amd import host, synth, workloads as wl
+    with host.Application(W, H, 0) as app:
+        vol = host.VolumeFile.from_raw(synth.ct_phantom_raw_fast(32))
+        app.OnStart(capi.LIGHT, [vol])
+        app.set_shadows(2, 1.5)
+        app.OnUpdate()
+        app.OnRender()
+        frag, _, _ = app.ReadFrame()
+        assert app.context().last_kernel_flavour() == 23
+        ub, volumes, tfs = wl.oracle_inputs(app, [vol])
+    with capi.Context(W, H, 0) as c:
+        c.volume_upload(0, volumes[0])
+        c.tf_upload(0, *tfs[0])
+        c.set_uniforms(capi.Uniforms.from_buffer_copy(ub))
+        c.set_shadows(2, 1.5)
+        c.render(capi.LIGHT)
+        want, _, _ = c.download()
+        c.set_shadows(0)
+        c.render(capi.LIGHT)
+        unshadowed, _, _ = c.download()
+    assert np.array_equal(vt.bits(frag), vt.bits(want))
+    assert not np.array_equal(vt.bits(frag), vt.bits(unshadowed))

@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     "vr_set_kernel_timing", "vr_present_tiles_async", "vr_kernel_choice",
     "vr_present_packed_async", "vr_unpack_tiles_bgra8_async",
     "vr_tf_upload_opacity_async", "vr_tf_upload_color_async", "vr_skip_field", "vr_unbounded_box_launches",
-    "vr_set_iso_value",
+    "vr_set_iso_value", "vr_set_shadows", "vr_shadow_volume",
 ]
 
 
@@ -126,6 +126,8 @@ def load() -> C.CDLL:
     lib.vr_set_volume_layout.argtypes = [vp, i32]
     lib.vr_set_arithmetic.argtypes = [vp, i32]
     lib.vr_set_iso_value.argtypes = [vp, C.c_float]
+    lib.vr_set_shadows.argtypes = [vp, i32, C.c_float]
+    lib.vr_shadow_volume.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_int * 3)]
     lib.vr_present_async.argtypes = [vp, vp, vp, vp]
     lib.vr_present_tiles_async.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
     lib.vr_hint_frames_in_flight.argtypes = [vp, i32]
@@ -381,6 +383,20 @@ class Context:
     def set_iso_value(self, iso: float):
         """The level of ISO launches enqueued after this call (default 0.5; finite values only, include/vr.h)."""
         self._chk(self.lib.vr_set_iso_value(self.h, iso))
+
+    def set_shadows(self, divisor: int, scale: float = 1.0):
+        """Shadows of LIGHT launches enqueued after this call: divisor 0 = off (default), 1 / 2 / 4 / 8 = voxels per light-volume
+        texel and axis; scale = the opacity scale (finite, >= 0).  include/vr.h vr_set_shadows."""
+        self._chk(self.lib.vr_set_shadows(self.h, divisor, scale))
+
+    def shadow_volume(self):
+        """(transmittance float32[Gz, Gy, Gx], (Gx, Gy, Gz)): the light volume a LIGHT launch enqueued now would read
+        (vr_shadow_volume: built synchronously, drains the device)."""
+        dims = (C.c_int * 3)()
+        n = self._chk(self.lib.vr_shadow_volume(self.h, None, 0, C.byref(dims)))
+        out = np.zeros(n, dtype=np.float32)
+        self._chk(self.lib.vr_shadow_volume(self.h, out.ctypes.data, n, C.byref(dims)))
+        return out.reshape(dims[2], dims[1], dims[0]), (int(dims[0]), int(dims[1]), int(dims[2]))
 
     def set_volume_layout(self, mode: int):
         """0 bricked copy (default), 1 the reference's vec4 voxels only, 3 x-fastest voxels + density plane (2 was removed)."""

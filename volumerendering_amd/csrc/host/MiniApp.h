@@ -100,6 +100,11 @@ public:
     // renders with the shader's own ComputeGradient (BasicVolLightApp.wgsl:239-253), the call the reference keeps
     // commented out at :212, instead of the voxels' pre-computed .rgb
     void SetInShaderGradient(bool on) { m_InShaderGradient = on; }
+    // shadows through a light volume (vr_set_shadows: divisor 0 = off, the default), handed to the ray-marcher in OnStart and in
+    // every OnUpdate
+    void SetShadows(int divisor, float scale) { m_ShadowDivisor = divisor; m_ShadowScale = scale; }
+    int GetShadowDivisor() const { return m_ShadowDivisor; }
+    float GetShadowScale() const { return m_ShadowScale; }
     const Light* GetLight() const override { return &m_Light1; }
     std::unique_ptr<OpacityTF> p_OpacityTf;
     std::unique_ptr<ColorTF> p_ColorTf;
@@ -107,6 +112,9 @@ private:
     VolumePtr p_Ct;
     int m_TfRes;
     bool m_InShaderGradient = false;
+    vr_ctx* m_ShadowCtx = nullptr;
+    int m_ShadowDivisor = 0;
+    float m_ShadowScale = 1.0f;
     Light m_Light1{vrm::vec4(0.0f, 5.0f, 0.0f, 1.0f), vrm::vec4(0.1f), vrm::vec4(1.0f)};
 };
 

@@ -34,6 +34,7 @@ void BasicVolumeApp::OnUpdate()
 // ---- BasicVolLightApp (App/src/miniapps/BasicVolLightApp.cpp:12-51) ---------------------------------------------
 void BasicVolLightApp::OnStart(vr_ctx* ctx)
 {
+    m_ShadowCtx = ctx;
     const bool onDevice = m_PrepareOnDevice && !p_Ct->IsNormalized() && !p_Ct->HasGradient();
     if (onDevice) {
         Upload(ctx, 0, *p_Ct);
@@ -58,6 +59,7 @@ void BasicVolLightApp::OnUpdate()
 {
     p_OpacityTf->UpdateTexture();
     p_ColorTf->UpdateTexture();
+    if (m_ShadowCtx) Check(vr_set_shadows(m_ShadowCtx, m_ShadowDivisor, m_ShadowScale));
 }
 
 // ---- VolumeMaskApp (App/src/miniapps/VolumeMaskApp.cpp:12-65) ---------------------------------------------------

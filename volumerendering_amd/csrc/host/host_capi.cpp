@@ -336,6 +336,16 @@ int vrh_app_set_iso_value(void* a, float iso)
     p->SetIsoValue(iso);
     return VR_OK;
 }
+// BasicVolLightApp::SetShadows of the running scene (taken over by the next OnUpdate); VR_ERR_NOT_READY when the scene is not lit
+int vrh_app_set_shadows(void* a, int divisor, float scale)
+{
+    auto* p = dynamic_cast<BasicVolLightApp*>(static_cast<Application*>(a)->GetApp());
+    if (!p) return VR_ERR_NOT_READY;
+    if ((divisor != 0 && divisor != 1 && divisor != 2 && divisor != 4 && divisor != 8) || !std::isfinite(scale) || !(scale >= 0.0f))
+        return VR_ERR_INVALID_ARG;
+    p->SetShadows(divisor, scale);
+    return VR_OK;
+}
 void vrh_app_set_prepare_on_device(void* a, int on) { static_cast<Application*>(a)->m_PrepareOnDevice = on != 0; }
 int vrh_app_update(void* a) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->OnUpdate(); }) }
 int vrh_app_render(void* a) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->OnRender(); }) }

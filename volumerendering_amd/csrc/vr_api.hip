@@ -7,6 +7,7 @@
 // the same dispatch over the kernels compiled with fused multiply-adds (vr_fused.hip)
 namespace vrf {
 void launch_march(const vr::LaunchDesc& L, hipStream_t s, const vr::MarchBatch& B);
+void launch_shadow_build(const vr::MarchParams& P, float* out, float sigma, bool skip, bool off32, hipStream_t s);
 }
 
 #include <cmath>
@@ -43,6 +44,7 @@ constexpr int kOrderRing = 16;  // launch-order buffers: written behind launch k
 constexpr int kGen = 4;         // generations of each table and of the distance field (vr_tf_upload_*_async)
 constexpr int kStage = 8;       // pinned staging buffers of the asynchronous table edits
 constexpr int kEditSeen = 8;    // streams remembered to have waited for the latest asynchronous edit
+constexpr int kShadowRing = 4;  // light volumes kept (vr_set_shadows): one per key, the least recently used one rebuilt
 
 // A device buffer of one generation: written by an edit, read by the launches that captured it while it was current, on any
 // streams.  Rewritten only behind every one of them (reuse_wait): reader[k] is the order_seq of the latest launch in record slot k
@@ -201,8 +203,38 @@ struct vr_ctx {
     bool proj_pending = false;
     hipStream_t proj_seen[kEditSeen] = {};
     int proj_seen_next = 0;
-    bool last_proj = false;  // the last launch was a projection or an isosurface (vr_kernel_choice reports no candidates)
+    bool last_proj = false;  // the last launch was a projection, an isosurface or shadowed (vr_kernel_choice reports no candidates)
     float iso = 0.5f;        // VR_VARIANT_ISO's level (vr_set_iso_value), copied into MarchParams::iso at enqueue
+    // Shadows of the lit shader (vr_set_shadows, vr_shadow.h): the setting, and a ring of light volumes, one per key.  A launch whose key
+    // matches an entry reads it (waiting once per stream for its build); otherwise it builds the least recently used entry on its own
+    // stream, behind every launch still reading it (buf.reader, as the table generations).  A volume change drains the device and
+    // empties the ring.
+    int shadow_div = 0;                     // 0 = off; 1, 2, 4, 8 = voxels per light-volume texel and axis
+    float shadow_sigma = 1.0f;              // opacity scale
+    unsigned long long opacity_edits = 0;   // bumped by every upload of TF slot 0's opacity table, synchronous or not (the key's content)
+    struct ShadowKey {
+        unsigned long long epoch = 0, opacity = 0;  // brick_epoch, opacity_edits
+        uint32_t light[3] = {}, box[6] = {}, sigma = 0;
+        int div = 0, arith = 0;
+        bool operator==(const ShadowKey& o) const
+        {
+            return epoch == o.epoch && opacity == o.opacity && std::memcmp(light, o.light, sizeof light) == 0 &&
+                   std::memcmp(box, o.box, sizeof box) == 0 && sigma == o.sigma && div == o.div && arith == o.arith;
+        }
+    };
+    struct ShadowVol {
+        GenBuf buf;
+        ShadowKey key;
+        bool valid = false;
+        hipEvent_t built = nullptr;   // behind the build, on `stream`
+        hipStream_t stream = nullptr;
+        bool pending = false;         // the build may still run: other streams wait for `built` once (seen), none after a draining call
+        hipStream_t seen[kEditSeen] = {};
+        int seen_next = 0;
+        unsigned long long used = 0;  // (least recently used entry is rebuilt)
+    } shadow[kShadowRing];
+    unsigned long long shadow_clock = 0;
+    int shadow_cur = -1;  // the entry the launch being enqueued reads (mark_reads)
     std::string err;
 };
 
@@ -686,6 +718,7 @@ void drained(vr_ctx* c)
     c->retired_host.clear();
     c->drained_gen = c->edit_gen;
     c->proj_pending = false;
+    for (auto& e : c->shadow) e.pending = false;
 }
 
 // Before `s` rewrites generation b: every launch that read it must have finished, whatever its stream (launches on different
@@ -724,6 +757,7 @@ void mark_reads(vr_ctx* c, const MarchParams& P)
             if (b.d) b.reader[c->order_seq % kInFlight] = (long long)c->order_seq;
         }
     if (P.brick_dist) c->field[c->field_cur].reader[c->order_seq % kInFlight] = (long long)c->order_seq;
+    if (c->shadow_cur >= 0) c->shadow[c->shadow_cur].buf.reader[c->order_seq % kInFlight] = (long long)c->order_seq;
 }
 
 // The distance field of records `rec` (bricks bn) into `field` on `s`: the active bricks, the x, y and z passes (vr_kernels.h), the
@@ -908,6 +942,95 @@ const float2* prepare_proj(vr_ctx* c, hipStream_t s, MarchParams& P)
     return c->proj_range;
 }
 
+// Shadows (vr_set_shadows): the key of the light volume a LIGHT frame with uniforms u reads, and the light volume's grid (texels per axis).
+vr_ctx::ShadowKey shadow_key(const vr_ctx* c, const vr_uniforms& u)
+{
+    vr_ctx::ShadowKey k;
+    k.epoch = c->brick_epoch;
+    k.opacity = c->opacity_edits;
+    // (the clip bounds as fill_frame_params computes them)
+    const float box[6] = {0.0f + u.clip_x[0], 0.0f + u.clip_y[0], 0.0f + u.clip_z[0], 1.0f - u.clip_x[1], 1.0f - u.clip_y[1], 1.0f - u.clip_z[1]};
+    std::memcpy(k.light, u.light_pos, sizeof k.light);
+    std::memcpy(k.box, box, sizeof k.box);
+    std::memcpy(&k.sigma, &c->shadow_sigma, sizeof k.sigma);
+    k.div = c->shadow_div;
+    k.arith = c->arith;
+    return k;
+}
+
+size_t shadow_grid(const vr_ctx* c, int g[3])
+{
+    const int n[3] = {c->vol[0].nx, c->vol[0].ny, c->vol[0].nz};
+    for (int a = 0; a < 3; ++a) g[a] = (n[a] + c->shadow_div - 1) / c->shadow_div;
+    return (size_t)g[0] * g[1] * g[2];
+}
+
+// The light volume of a shadowed LIGHT launch on `s` whose parameters are P (volume 0, TF slot 0, the clip box and the light of its first
+// frame; with `skip` LIGHT's distance field in P.brick_dist): the ring's entry of that key, built on `s` into the least recently used
+// entry if there is none -- behind every launch that still reads that entry and behind its own last build -- or waited for once on a
+// stream other than its build's.  Binds it as P.vol[1] and makes it the entry the launch reads (shadow_cur).  An allocation failure
+// returns before anything is enqueued.
+int prepare_shadow(vr_ctx* c, hipStream_t s, MarchParams& P, const vr_ctx::ShadowKey& key, bool skip, bool off32)
+{
+    int g[3];
+    const size_t texels = shadow_grid(c, g);
+    int e = -1;
+    for (int i = 0; i < kShadowRing; ++i)
+        if (c->shadow[i].valid && c->shadow[i].key == key) e = i;
+    bool build = e < 0;
+    if (build) {
+        e = 0;
+        for (int i = 1; i < kShadowRing; ++i)
+            if (c->shadow[i].used < c->shadow[e].used) e = i;
+    }
+    vr_ctx::ShadowVol& v = c->shadow[e];
+    if (build) {
+        v.valid = false;
+        const bool fresh = texels * sizeof(float) > v.buf.cap;
+        // (a smaller buffer may still be read by launches in flight: it is retired, freed by the next draining call)
+        if (const int rc = grow(c, &v.buf.d, &v.buf.cap, texels * sizeof(float), false)) return rc;
+        if (!v.built) VR_HIP(c, hipEventCreateWithFlags(&v.built, hipEventDisableTiming));
+        if (!fresh) {
+            if (const int rc = reuse_wait(c, s, v.buf)) return rc;
+            if (v.pending && v.stream != s) VR_HIP(c, hipStreamWaitEvent(s, v.built, 0));
+        }
+    }
+    DevVolume& lv = P.vol[1];
+    lv = DevVolume{};
+    lv.data = nullptr;
+    lv.dens = (const float*)v.buf.d;
+    lv.a_base = (const char*)v.buf.d;
+    lv.a_shift = 2;
+    lv.nx = g[0];
+    lv.ny = g[1];
+    lv.nz = g[2];
+    lv.bricked = 0;
+    lv.lut = 0;
+    lv.data_bytes = (unsigned)(texels * sizeof(float));
+    if (build) {
+        if (c->arith == VR_ARITH_FUSED) vrf::launch_shadow_build(P, (float*)v.buf.d, c->shadow_sigma, skip, off32, s);
+        else vr::launch_shadow_build(P, (float*)v.buf.d, c->shadow_sigma, skip, off32, s);
+        VR_HIP(c, hipGetLastError());
+        VR_HIP(c, hipEventRecord(v.built, s));
+        v.buf.written();
+        v.key = key;
+        v.valid = true;
+        v.stream = s;
+        v.pending = true;
+        for (auto& x : v.seen) x = nullptr;
+    } else if (v.pending && s != v.stream) {
+        bool seen = false;
+        for (auto x : v.seen) seen = seen || x == s;
+        if (!seen) {
+            VR_HIP(c, hipStreamWaitEvent(s, v.built, 0));
+            v.seen[v.seen_next++ % kEditSeen] = s;
+        }
+    }
+    v.used = ++c->shadow_clock;
+    c->shadow_cur = e;
+    return VR_OK;
+}
+
 // The kernel form ("flavour") a launch runs: `fl` is the one asked for (vr_set_kernel_flavour, else VR_EXP_FLAVOUR), 0 = the default.
 int choose_flavour(vr_ctx* c, int fl, int variant, int n_frames, int rank, int world, bool packed, const Eligibility& E)
 {
@@ -915,6 +1038,8 @@ int choose_flavour(vr_ctx* c, int fl, int variant, int n_frames, int rank, int w
     if (is_projection(variant)) return fl == 1 ? 20 : 19;
     // the isosurface: the same rule, 22 without skipping, 21 with it
     if (variant == VR_VARIANT_ISO) return fl == 1 ? 22 : 21;
+    // the shadowed lit shader: 24 without skipping, 23 with it
+    if (variant == VR_VARIANT_LIGHT && c->shadow_div != 0) return fl == 1 ? 24 : 23;
     const bool auto_choice = fl == 0;
     const double rays = rays_per_lane(c, rank, world, c->frames_in_flight * n_frames);
     const bool short_chains = E.chain_known != 0 && E.chain_known - 1 < 128;
@@ -1023,6 +1148,8 @@ KernelForm kernel_form(int fl, int variant)
     case 20: return {D::kProj, 0, false, false, false, 0u};
     case 21:
     case 22: return {D::kIso, 0, false, false, false, 0u};
+    case 23:
+    case 24: return {D::kShadow, 0, false, false, false, 0u};
     default: return {D::kPlain, 0, false, false, false, 0u};  // 1, 6
     }
 }
@@ -1151,6 +1278,19 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
     int nvol;
     bool off32;
     if (const int rc = check_render_args(c, variant, rank, world, n_frames, batch_u, batch_out, &nvol, &off32)) return rc;
+    // shadows: every frame of the launch reads one light volume, of less than 4 GiB
+    const bool shadowed = variant == VR_VARIANT_LIGHT && c->shadow_div != 0;
+    vr_ctx::ShadowKey shadow_k;
+    if (shadowed) {
+        shadow_k = shadow_key(c, batch_u ? batch_u[0] : c->u);
+        for (int f = 1; f < n_frames; ++f)
+            if (!(shadow_key(c, batch_u[f]) == shadow_k))
+                return fail(c, VR_ERR_UNSUPPORTED, "vr_render: the frames of a shadowed batch must share the light and the clip box");
+        int g[3];
+        if (shadow_grid(c, g) * sizeof(float) >= (1ull << 32))
+            return fail(c, VR_ERR_UNSUPPORTED, "vr_render: the light volume would take 4 GiB or more (a larger divisor)");
+    }
+    c->shadow_cur = -1;
     if (batch_u) out = (float4*)batch_out[0];
     VR_HIP(c, hipSetDevice(c->device));
     (void)hipGetLastError();  // a stale error of somebody else's call must not be reported as a failed launch below
@@ -1168,7 +1308,7 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
     const int fl = choose_flavour(c, requested, variant, n_frames, rank, world, packed, E);
     c->last_flavour = fl;
     const KernelForm form = kernel_form(fl, variant);
-    c->last_proj = form.family == LaunchDesc::kProj || form.family == LaunchDesc::kIso;
+    c->last_proj = form.family == LaunchDesc::kProj || form.family == LaunchDesc::kIso || form.family == LaunchDesc::kShadow;
     const float2* vrange = nullptr;
     if (fl == 19 || fl == 21) {
         vrange = prepare_proj(c, s, P);
@@ -1197,7 +1337,12 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
     c->last_tiles = packed ? P.n_tiles : 0;
 
     if (frame_events) VR_HIP(c, hipEventRecord(c->tm.ev_begin, s));
+    // the shadowed form (23 with LIGHT's distance field in place, else 24's kernels)
+    const bool shadow_skip = form.family == LaunchDesc::kShadow && fl == 23 && P.brick_dist != nullptr;
     if (P.n_blocks > 0) {
+        // the light volume it reads: built here when its key has none (inside vr_last_timing's total, outside its kernel time)
+        if (shadowed)
+            if (const int rc = prepare_shadow(c, s, P, shadow_k, shadow_skip, off32)) return rc;
         // the LOGICAL blocks (records, launch order): one wavefront per workgroup (launch order at wavefront granularity) -- except
         // for the depth-parallel kernels on large launches, where 4x the workgroups cost more at dispatch than the finer order gains
         // (C2: 32 768 workgroups of a 0.12 ms frame).  See map_pixel / map_pixel_dp.
@@ -1239,7 +1384,7 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
         L.grid = dim3(grid.x * (unsigned)n_frames);
         L.block = block;
         L.vrange = vrange;
-        L.proj_skip = vrange != nullptr;
+        L.proj_skip = vrange != nullptr || shadow_skip;
         if (pw) {
             // persistent wavefronts: `grid` stays the number of LOGICAL blocks (records, launch order); the launch itself is one
             // workgroup of form.pw_threads per CU (fewer when there are fewer packets), TF slot 0 in LDS when it fits
@@ -1314,6 +1459,7 @@ int refresh_bricks(vr_ctx* c, int slot)
     c->vol_bricks[slot] = nullptr;
     c->merged_stale = true;
     ++c->brick_epoch;
+    for (auto& e : c->shadow) e.valid = false;  // (the caller drained the device)
     const int bnx = skip_bricks(v.nx), bny = skip_bricks(v.ny), bnz = skip_bricks(v.nz);
     const size_t nbricks = (size_t)bnx * bny * bnz;
     VR_HIP(c, hipMalloc(&c->vol_bricks[slot], nbricks * sizeof(float2)));
@@ -1626,6 +1772,10 @@ void vr_destroy(vr_ctx* c)
     if (c->proj_rec) (void)hipFree(c->proj_rec);
     if (c->proj_range) (void)hipFree(c->proj_range);
     if (c->proj_ev) (void)hipEventDestroy(c->proj_ev);
+    for (auto& e : c->shadow) {
+        if (e.buf.d) (void)hipFree(e.buf.d);
+        if (e.built) (void)hipEventDestroy(e.built);
+    }
     for (auto& g : c->field)
         if (g.d) (void)hipFree(g.d);
     if (c->dist_tmp) (void)hipFree(c->dist_tmp);
@@ -1733,6 +1883,7 @@ static void tf_set_current(vr_ctx* c, int slot, const float* table, uint32_t R, 
         c->tf[slot].res_c = (int)R;
         c->tf_color_finite[slot] = all_finite(table, (int)(4 * R));
     } else {
+        if (slot == 0) ++c->opacity_edits;  // (the light volumes' key)
         c->tf[slot].opacity = (const float*)g.d;
         c->tf[slot].res_o = (int)R;
         int z = -1;
@@ -2302,6 +2453,53 @@ int vr_set_iso_value(vr_ctx* c, float iso)
     return VR_OK;
 }
 
+int vr_set_shadows(vr_ctx* c, int grid_divisor, float opacity_scale)
+{
+    if (!c) return VR_ERR_INVALID_ARG;
+    if (grid_divisor != 0 && grid_divisor != 1 && grid_divisor != 2 && grid_divisor != 4 && grid_divisor != 8)
+        return fail(c, VR_ERR_INVALID_ARG, "vr_set_shadows: the divisor must be 0 (off), 1, 2, 4 or 8");
+    if (!std::isfinite(opacity_scale) || !(opacity_scale >= 0.0f))
+        return fail(c, VR_ERR_INVALID_ARG, "vr_set_shadows: the opacity scale must be finite and >= 0");
+    c->shadow_div = grid_divisor;
+    c->shadow_sigma = opacity_scale;
+    return VR_OK;
+}
+
+int vr_shadow_volume(vr_ctx* c, float* out, size_t capacity, int dims[3])
+{
+    if (!c) return VR_ERR_INVALID_ARG;
+    if (capacity > 0 && !out) return fail(c, VR_ERR_INVALID_ARG, "vr_shadow_volume: out is NULL");
+    if (c->shadow_div == 0) return fail(c, VR_ERR_NOT_READY, "vr_shadow_volume: shadows are off");
+    if (!c->vol[0].data) return fail(c, VR_ERR_NOT_READY, "vr_shadow_volume: volume slot 0 is empty");
+    if (!c->tf[0].opacity || !c->tf[0].color) return fail(c, VR_ERR_NOT_READY, "vr_shadow_volume: TF slot 0 is empty");
+    if (!c->have_uniforms) return fail(c, VR_ERR_NOT_READY, "vr_shadow_volume: vr_set_uniforms has not been called");
+    int g[3];
+    const size_t n = shadow_grid(c, g);
+    if (n * sizeof(float) >= (1ull << 32)) return fail(c, VR_ERR_UNSUPPORTED, "vr_shadow_volume: the light volume would take 4 GiB or more");
+    VR_HIP(c, hipSetDevice(c->device));
+    VR_HIP(c, hipDeviceSynchronize());
+    drained(c);
+    (void)hipGetLastError();
+    // the parameters a LIGHT launch of the context's uniforms would have (the flavour asked for decides the build's form; both give the
+    // same texels)
+    MarchParams P;
+    fill_launch_params(c, P, c->u, 0, 1, false);
+    const int requested = c->flavour == 0 ? c->default_flavour : c->flavour;
+    const Eligibility E = eligibility(c, requested, VR_VARIANT_LIGHT, 1, 0, 1, false, nullptr);
+    if (E.can_skip)
+        if (const int rc = prepare_skip(c, VR_VARIANT_LIGHT, c->stream, P)) return rc;
+    if (c->layout_mode == 0) use_bricked_copies(c, P);
+    const bool off32 = c->vol_bytes[0] <= 0xFFFFFFFFull && !(P.vol[0].bricked && bricked_grid(P.vol[0]).slots * 16 > 0xFFFFFFFFull);
+    const int rc = prepare_shadow(c, c->stream, P, shadow_key(c, c->u), P.brick_dist != nullptr && requested != 1, off32);
+    c->shadow_cur = -1;  // (no launch reads it)
+    if (rc) return rc;
+    VR_HIP(c, hipStreamSynchronize(c->stream));
+    if (capacity > 0) VR_HIP(c, hipMemcpy(out, P.vol[1].dens, (capacity < n ? capacity : n) * sizeof(float), hipMemcpyDeviceToHost));
+    if (dims)
+        for (int a = 0; a < 3; ++a) dims[a] = g[a];
+    return (int)n;
+}
+
 int vr_set_volume_layout(vr_ctx* c, int mode)
 {
     if (!c) return VR_ERR_INVALID_ARG;
@@ -2323,7 +2521,7 @@ int vr_volume_layout(vr_ctx* c, int slot, int* flags)
 int vr_kernel_choice(vr_ctx* c, int flavours[6], float ms_per_launch[6], int* chosen)
 {
     if (!c) return VR_ERR_INVALID_ARG;
-    if (c->last_proj) {  // (the projections' and the isosurface's forms are never measured)
+    if (c->last_proj) {  // (the projections', the isosurface's and the shadowed forms are never measured)
         if (chosen) *chosen = -1;
         return 0;
     }

@@ -151,11 +151,12 @@ struct PwQueue {
 // What enqueue_render decided about one march launch; handed to launch_march of the arithmetic mode's translation unit
 // (vr_launch.h: namespace vr = separately rounded multiply-adds, namespace vrf = fused).  Host only.
 struct LaunchDesc {
-    enum Family { kPlain, kDp, kPw, kP2, kLt, kProj, kIso };
+    enum Family { kPlain, kDp, kPw, kP2, kLt, kProj, kIso, kShadow };
     int variant;      // vr_variant
     Family family;    // march_kernel, march_dp_kernel, march_pw_kernel (persistent wavefronts: grid = workgroups, the packets come
                       // from `queue`), march_p2_kernel (the same, corner loads two steps ahead), march_lt_kernel (LDS tiles, lit shader),
-                      // march_proj_kernel (vr_proj.h: the intensity projections), march_iso_kernel (vr_iso.h: the isosurface)
+                      // march_proj_kernel (vr_proj.h: the intensity projections), march_iso_kernel (vr_iso.h: the isosurface),
+                      // march_shadow_kernel (vr_shadow.h: the lit shader with shadows; MarchParams::vol[1] = the light volume)
     bool off32;       // every bound volume < 4 GiB: 32-bit byte offsets
     int lanes;        // kDp: lanes per ray (2 / 4)
     bool pipe;        // kDp / kPw: the next round's / step's corner loads software-pipelined
@@ -166,7 +167,8 @@ struct LaunchDesc {
     PwQueue queue;
     dim3 grid, block;
     const float2* vrange;  // kProj: (min, max) of volume 0 (vr_proj.h); with `proj_skip` the brick records are MarchParams::bricks
-    bool proj_skip;        // kProj / kIso: the skipping form (march_proj_kernel<.., SKIP = true, ..>, march_iso_kernel<.., true, ..>)
+    bool proj_skip;        // kProj / kIso / kShadow: the skipping form (march_proj_kernel<.., SKIP = true, ..>, march_iso_kernel<.., true, ..>,
+                           // march_shadow_kernel<.., true, ..>)
 };
 
 }  // namespace vr

@@ -908,10 +908,11 @@ __device__ __forceinline__ bool opacity_is_zero(const MarchParams& P, float d)
 // so that the packed instructions need no shuffling; per component the operations and their order are those of
 // normalize3 / shade / blend.  zw = (gradient z, density), gxy = (gradient x, gradient y), tq = the table texels of `density`.
 // (lpos / dif / amb, kD / kA: the scene's light -- the uniforms of BasicVolLightApp, the constants of VolumeMaskApp.wgsl:116-123;
-// MASKED: a lane whose mask sample says so takes the dose table's sample `trt` unshaded instead, VolumeMaskApp.wgsl:201-205)
-template <bool UNI = false, bool MASKED = false>
+// MASKED: a lane whose mask sample says so takes the dose table's sample `trt` unshaded instead, VolumeMaskApp.wgsl:201-205;
+// SHADOW: the diffuse term dif * m becomes dif * (m * S), S = the light volume's transmittance at the sample, vr_shadow.h)
+template <bool UNI = false, bool MASKED = false, bool SHADOW = false>
 __device__ __forceinline__ void shade_blend_packed(f3 lpos, f3 dif, f3 amb, float kD, float kA, f3 w, v2f zw, v2f gxy, const TfFetch& tq, float4& dst,
-                                                   bool masked = false, f3 trt_rgb = f3{0.0f, 0.0f, 0.0f}, float trt_a = 0.0f)
+                                                   bool masked = false, f3 trt_rgb = f3{0.0f, 0.0f, 0.0f}, float trt_a = 0.0f, float S = 1.0f)
 {
     v2f Lxy = v2f{lpos.x - w.x, lpos.y - w.y};
     float Lz = lpos.z - w.z;
@@ -927,11 +928,12 @@ __device__ __forceinline__ void shade_blend_packed(f3 lpos, f3 dif, f3 amb, floa
     Lxy = Lxy * inv_l;
     Lz = Lz * inv_l;
 #if VR_FUSED
-    const float m = max0(mad(Nz, Lz, mad(Nxy.y, Lxy.y, Nxy.x * Lxy.x)));
+    float m = max0(mad(Nz, Lz, mad(Nxy.y, Lxy.y, Nxy.x * Lxy.x)));
 #else
     const v2f nl = Nxy * Lxy;
-    const float m = max0((nl.x + nl.y) + Nz * Lz);
+    float m = max0((nl.x + nl.y) + Nz * Lz);
 #endif
+    if constexpr (SHADOW) m = m * S;
     const v2f sh_rg = mad2(v2f{dif.x, dif.y} * m, v2f{kD, kD}, v2f{amb.x, amb.y} * kA);
     const float sh_b = mad(dif.z * m, kD, amb.z * kA);
     float opacity = lerpf(tq.o0, tq.o1, tq.fo);

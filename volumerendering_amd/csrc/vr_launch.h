@@ -22,6 +22,8 @@
 #include "vr_proj.h"
 // The shaded isosurface of volume slot 0 (flavours 21 and 22; it reads the projections' brick records)
 #include "vr_iso.h"
+// Shadows of the lit shader through a light volume (flavours 23 and 24; the build and the shadowed march)
+#include "vr_shadow.h"
 
 #include <type_traits>
 
@@ -119,8 +121,27 @@ void launch_iso(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
                L.proj_skip, L.off32, B.n_frames > 1);
 }
 
+// the shadowed lit shader: skipping x addressing x frames per launch
+void launch_shadow(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
+{
+    with_flags([&](auto S, auto O, auto BT) { hipLaunchKernelGGL((march_shadow_kernel<O, S, BT>), L.grid, L.block, 0, s, B); },
+               L.proj_skip, L.off32, B.n_frames > 1);
+}
+
+// the light volume of a shadowed launch (P: its parameters, vol[1] = the grid, whose storage is `out`); skip: by LIGHT's distance field
+void launch_shadow_build(const MarchParams& P, float* out, float sigma, bool skip, bool off32, hipStream_t s)
+{
+    const unsigned blocks = (((unsigned)P.vol[1].nx + 3u) >> 2) * (((unsigned)P.vol[1].ny + 3u) >> 2) * (((unsigned)P.vol[1].nz + 3u) >> 2);
+    with_flags([&](auto S, auto O) { hipLaunchKernelGGL((shadow_build_kernel<O, S>), dim3(blocks), dim3(64), 0, s, P, out, sigma); }, skip,
+               off32);
+}
+
 void launch_march(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
 {
+    if (L.family == LaunchDesc::kShadow) {
+        launch_shadow(L, s, B);
+        return;
+    }
     if (L.family == LaunchDesc::kIso) {
         launch_iso(L, s, B);
         return;
