@@ -417,7 +417,12 @@ int vr_last_block_trace(vr_ctx* ctx, uint64_t* out, int capacity);
  *       an inert brick loads nothing, in the march and in the light volume's build, and a blended sample of opacity exactly 0
  *       is not shaded.  Flavour 0 runs as 23, and so does every other flavour but 1.  (When LIGHT would not skip -- a
  *       non-finite colour table or light, no zero prefix of the opacity table -- 23 runs 24's kernels.)
- *   24  both without skipping: every in-box step up to the cut-off is fetched and shaded.  Flavour 1 runs as 24.          */
+ *   24  both without skipping: every in-box step up to the cut-off is fetched and shaded.  Flavour 1 runs as 24.
+ * BASIC / LIGHT with surface output (vr_set_output) likewise (0 candidates after such a launch; ISO's surface launches keep 21 / 22):
+ *   25  march_surf_kernel with exact skipping by BASIC's distance field (csrc/vr_surf.h): a step in an inert brick loads nothing
+ *       and leaves the accumulated alpha as it is.  Flavour 0 runs as 25, and so does every other flavour but 1.  (Without a zero
+ *       prefix of the opacity table 25 runs 26's kernels; the colour table and the light play no part.)
+ *   26  march_surf_kernel without skipping: every in-box step up to the hit is fetched.  Flavour 1 runs as 26.               */
 int vr_set_kernel_flavour(vr_ctx* ctx, int flavour);
 
 /* What the default's measured choice (flavour 0) knows about the launch shape it was asked for last: the candidates' flavours, the
@@ -475,6 +480,67 @@ int vr_set_shadows(vr_ctx* ctx, int grid_divisor, float opacity_scale);
  * the call drains the device, like vr_skip_field.  Copies min(capacity, n) floats in x-fastest order, writes the grid to dims[3]
  * and returns n.  VR_ERR_NOT_READY when shadows are off, volume 0 / TF 0 are missing or no uniforms were set. */
 int vr_shadow_volume(vr_ctx* ctx, float* out, size_t capacity, int dims[3]);
+
+/* ---- surface positions: first-hit position, depth, picking --------------------------------------------------------------
+ * What a launch writes.  VR_OUTPUT_COLOR (default): every launch is exactly what it is without this setting.  VR_OUTPUT_SURFACE:
+ * the launches of VR_VARIANT_BASIC, VR_VARIANT_LIGHT and VR_VARIANT_ISO write surface positions instead of colour, through every
+ * launch shape (synchronous, asynchronous, tiles, several frames per launch); every other variant returns VR_ERR_UNSUPPORTED and
+ * enqueues nothing.  Applies to launches enqueued after the call (captured at enqueue, as vr_set_iso_value is).  The frame is
+ * W*H*4 floats as ever.
+ *
+ * Surface output of BASIC and LIGHT (volume slot 0, TF slot 0's opacity table alone; both variants give the same bits: they share
+ * their sample positions).  tau = the threshold of vr_set_surface_threshold when the launch was enqueued.
+ *   Positions: exactly BASIC's march (start, direction, stepsCount, step size, variable-step toggle, jitter, repeated rounded
+ *     additions p_{k+1} = p_k + step); fragmentMode 1-4 return what BASIC returns.
+ *   Accumulation: a = +0.  For each step that passes IsInSampleCoords, while a <= tau: d = BASIC's trilinear .a fetch at the step,
+ *     o = BASIC's opacity look-up of d (linear, clamp-to-edge), a_prev = a, a = mad(1 - a, o, a) -- the alpha line of
+ *     FrontToBackBlend, in the vr_set_arithmetic mode's mad.  The variant's own cut-off (0.95 / 1.0) plays no part.
+ *   Hit: the first in-box step k after whose blend a > tau.  A NaN a ends the loop and is no hit.
+ *   Refinement (the isosurface's rule, on alpha): if k is the ray's first in-box step, q = p_k.  Otherwise
+ *     t = (tau - a_prev) / (a - a_prev) (correctly rounded f32 division); if !(t >= 0 && t <= 1) then q = p_k, else
+ *     q = mad(step, t, p_{k-1}) per component in the arithmetic mode's mad.
+ *   Pixel: hit -> (q.x, q.y, q.z, a); ray through the box without a hit -> (0, 0, 0, a) with the final a; no ray -> (0, 0, 0, 0).
+ *     So a pixel is a hit exactly when .w > tau; at tau = 0.95f the .w plane is BASIC's alpha plane bit for bit, at
+ *     tau = 0x1.fffffep-1f LIGHT's.
+ *   Counters: composited = the in-box steps up to and including the hit (all of them without one; a NaN a ends the count at its
+ *     step), covered = pixels with a hit, fetched = samples whose corners were loaded.  In fragmentMode 1-4 all three are 0.
+ *   Shadows (vr_set_shadows) are ignored: no light volume is built or read.
+ * Surface output of ISO: hit -> (q.x, q.y, q.z, 1.0f) with q the refined point of VR_VARIANT_ISO's definition above; no hit -> zeros.
+ *   Counters as ISO's.
+ * The output, composited and covered are bit-identical across layouts, launch shapes and skipping on / off (flavours 25 / 26). */
+#define VR_OUTPUT_COLOR 0
+#define VR_OUTPUT_SURFACE 1
+int vr_set_output(vr_ctx* ctx, int mode);
+
+/* The alpha threshold of BASIC / LIGHT surface launches enqueued after this call (default 0.5f).  Finite, 0 <= tau < 1; otherwise
+ * VR_ERR_INVALID_ARG and the previous value stays. */
+int vr_set_surface_threshold(vr_ctx* ctx, float tau);
+
+/* The depth a rasteriser drawing at the surface points would write: d_surface = a surface frame (W*H*4 floats, device), d_depth =
+ * W*H floats (device), on `stream` (NULL = the ctx's own); nothing is synchronised.  Uses the view and proj matrices of the context's
+ * uniforms and the threshold of vr_set_surface_threshold AT THIS CALL (not those of the launch that wrote the frame).  Per pixel s:
+ * !(s.w > tau) -> 1.0f (an ISO frame's .w is 1 or 0).  Otherwise w = (s.x - 0.5f, s.y - 0.5f, (0.5f - s.z) * 0.5f) -- the inverse
+ * of the ray set-up's world-to-uvw map --, e = view * (w, 1), c = proj * e, both with the column-major, left-to-right-summed product
+ * of the ray set-up (separately rounded in both arithmetic modes), depth = c.z / c.w.  VR_ERR_NOT_READY before vr_set_uniforms. */
+int vr_surface_depth_async(vr_ctx* ctx, const void* d_surface, void* d_depth, void* stream);
+
+/* What is under a pixel.  hit = 0: every other field but alpha is 0 and depth is 1.0f. */
+typedef struct vr_pick_result {
+    int32_t hit;       /* the pixel's .w > tau                                                              */
+    float uvw[3];      /* the surface point q in texture space                                              */
+    float world[3];    /* (q.x - 0.5f, q.y - 0.5f, (0.5f - q.z) * 0.5f)                                     */
+    float depth;       /* as vr_surface_depth_async                                                         */
+    float alpha;       /* the pixel's .w                                                                    */
+    int32_t voxel[3];  /* clamp((int)floor(uvw * n), 0, n - 1) of volume slot 0                             */
+    float value[VR_MAX_VOLUMES][4]; /* the vec4 voxel there of every uploaded slot whose size equals slot 0's; else zeros */
+} vr_pick_result;
+
+/* Renders the surface pixel (x, y) of `variant` (BASIC, LIGHT or ISO; others VR_ERR_UNSUPPORTED) with the context's uniforms and
+ * threshold into a buffer of its own -- whatever vr_set_output says --, drains the device (as vr_skip_field does) and fills *out.
+ * The context's frame (vr_download), vr_last_counters, vr_last_kernel_flavour, vr_last_timing, vr_kernel_times and the measured
+ * kernel choice stay what the render before the pick left: a pick between a render and its download is the normal use.
+ * A pixel outside the viewport is VR_ERR_INVALID_ARG. */
+int vr_pick(vr_ctx* ctx, int variant, uint32_t x, uint32_t y, vr_pick_result* out);
 
 /* Volume layout in HBM (A/B measurements; frames and counts are bit-identical in every mode).
  *   0  default: the march kernels gather from a BRICKED copy of every slot -- the vec4 voxels and a scalar f32 density plane

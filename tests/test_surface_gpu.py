@@ -1,0 +1,441 @@
+"""GPU side of the surface-position output (vr_set_output, csrc/vr_surf.h): frames and counters bit-exact against the float32
+restatement (surf_ref.py, itself pinned to the oracle's BASIC and LIGHT marches by tests/test_surface.py) for flavours 25 and 26; the
+.w plane against the GPU's and the oracle's own colour frames in both arithmetic modes; the same bits from every layout and launch
+shape; hostile inputs; the isosurface's points; depth and picking; and no interference with the colour launches."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import host_ref as hr
+import iso_ref as ir
+import oracle_binding as ob
+import surf_ref as sr
+import vrtest as vt
+from volumerendering_amd import capi
+
+pytestmark = pytest.mark.gpu
+f32 = np.float32
+W, H = 72, 56
+TAUS = [0.0, 0.5, float(sr.TAU_BASIC), float(sr.TAU_LIGHT)]
+
+
+def phantom(n=16):
+    return vt.make_volume("phantom", n, gradient=True)
+
+
+def steep_tf(res=64, gain=4.0):
+    """Opacity min(1, gain * ramp), exactly 0 at density 0 (tests/test_surface.py checks on the CPU that it gives hits)."""
+    return np.minimum(hr.default_opacity_tf(res) * f32(gain), f32(1.0)).astype(f32), hr.default_color_tf(res)
+
+
+def uniforms(shape, **over):
+    step, count = hr.stepping_params(*shape)
+    kw = dict(steps_count=count, step_size=step)
+    kw.update(over)
+    return hr.make_uniforms(W, H, **kw)
+
+
+def air_and_core(n=24):
+    """Exact-zero air around a bright core (gradient in .rgb): most bricks are inert under any table with opacity[0] == 0."""
+    v = np.zeros((n, n, n, 4), f32)
+    c = n // 2
+    v[c - 3:c + 3, c - 3:c + 3, c - 3:c + 3, 3] = f32(0.9)
+    v[c - 1:c + 1, c - 1:c + 1, c - 1:c + 1, 3] = f32(1.0)
+    return ob.precompute_gradient(v)
+
+
+def shape_of(v):
+    return v.shape[2], v.shape[1], v.shape[0]
+
+
+def surface(ctx, variant, tau, u, v, tf):
+    """A surface frame and its counters; the output setting is put back."""
+    ctx.set_output(capi.OUTPUT_SURFACE)
+    ctx.set_surface_threshold(tau)
+    try:
+        frag, _, _ = vt.gpu_render(ctx, variant, u, [v], [tf])
+        return frag, ctx.counters()
+    finally:
+        ctx.set_output(capi.OUTPUT_COLOR)
+
+
+def same(a, b):
+    """Bit-equal, NaN where the other is NaN."""
+    a, b = np.asarray(a, f32), np.asarray(b, f32)
+    fin = ~np.isnan(b)
+    return np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(vt.bits(a)[fin], vt.bits(b)[fin])
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = capi.Context(W, H, 0)
+    yield c
+    c.close()
+
+
+CASES = [
+    # (id, volume, tf res, uniform overrides): the isosurface GPU test's list
+    ("sphere", lambda: vt.make_volume("sphere", 16, gradient=True), 64, {}),
+    ("phantom", phantom, 16, {}),
+    ("aniso", lambda: ob.precompute_gradient(ob.normalize_data(hr.raw_to_vec4(
+        np.random.default_rng(7).integers(0, 4096, size=(7, 20, 13)).astype(np.uint16)))), 257, {}),
+    ("clip", phantom, 64, dict(clip_x=(0.1, 0.2), clip_y=(0.05, 0.0), clip_z=(0.0, 0.3))),
+    ("varstep", phantom, 64, dict(toggles=(1, 0, 0, 0))),
+    ("jitter", lambda: vt.make_volume("sphere", 16, gradient=True), 64, dict(toggles=(0, 1, 0, 0))),
+    ("steps0", phantom, 64, dict(steps_count=0)),
+    ("steps1", phantom, 64, dict(steps_count=1)),
+    ("steps7", phantom, 64, dict(steps_count=7, step_size=0.05)),
+    ("core", air_and_core, 64, {}),
+]
+
+
+@pytest.mark.parametrize("cid,make,res,over", CASES, ids=[c[0] for c in CASES])
+def test_matches_restatement(ctx, cid, make, res, over):
+    """Frames and counters of flavours 25 and 26 at four thresholds, LIGHT and BASIC alike, against the restatement."""
+    v, tf = make(), steep_tf(res)
+    u = uniforms(shape_of(v), **over)
+    for tau in TAUS:
+        ref, n_ref, cov_ref = sr.frame(u, W, H, v, tf[0], tau)
+        for fl in (0, 1):
+            ctx.set_kernel_flavour(fl)
+            try:
+                frag, (n, cov, f) = surface(ctx, capi.LIGHT if fl == 0 else capi.BASIC, tau, u, v, tf)
+                assert ctx.last_kernel_flavour() == (25 if fl == 0 else 26)
+                assert ctx.kernel_choice()[0] == []
+            finally:
+                ctx.set_kernel_flavour(0)
+            assert np.array_equal(vt.bits(frag), vt.bits(ref)), (tau, fl, float(np.nanmax(np.abs(frag - ref))))
+            assert (n, cov) == (n_ref, cov_ref), (tau, fl)
+            assert f <= n and (fl == 0 or f == n)
+        if cid not in ("steps0", "steps1") and tau <= 0.5:
+            assert cov_ref > 0
+
+
+def test_skipping_and_its_weakest_condition(ctx):
+    """Exact-zero air: 25 fetches far fewer samples than it counts, 26 all of them.  A non-finite colour table and light switch
+    LIGHT's own skipping off but not the surface march's (it reads neither).  A table without a zero prefix: 25 runs 26's kernels."""
+    v, tf = air_and_core(), steep_tf()
+    u = uniforms((24, 24, 24))
+    ref, n_ref, cov_ref = sr.frame(u, W, H, v, tf[0], 0.5)
+    assert cov_ref > 0
+    frag, (n, cov, f25) = surface(ctx, capi.LIGHT, 0.5, u, v, tf)
+    assert np.array_equal(vt.bits(frag), vt.bits(ref)) and (n, cov) == (n_ref, cov_ref) and f25 < n // 4
+    ctx.set_kernel_flavour(1)
+    try:
+        frag, (n, cov, f26) = surface(ctx, capi.LIGHT, 0.5, u, v, tf)
+    finally:
+        ctx.set_kernel_flavour(0)
+    assert np.array_equal(vt.bits(frag), vt.bits(ref)) and f26 == n == n_ref
+    bad_colour = tf[1].copy()
+    bad_colour[5, 1] = np.nan
+    ub = uniforms((24, 24, 24), light_pos=(np.inf, 5.0, 0.0, 1.0))
+    frag, (n, cov, f) = surface(ctx, capi.LIGHT, 0.5, ub, v, (tf[0], bad_colour))
+    assert np.array_equal(vt.bits(frag), vt.bits(ref)) and (n, cov, f) == (n_ref, cov_ref, f25)
+    no_prefix = (np.maximum(tf[0], f32(0.01)), tf[1])
+    ref2, n2, cov2 = sr.frame(u, W, H, v, no_prefix[0], 0.5)
+    frag, (n, cov, f) = surface(ctx, capi.LIGHT, 0.5, u, v, no_prefix)
+    assert ctx.last_kernel_flavour() == 25
+    assert np.array_equal(vt.bits(frag), vt.bits(ref2)) and (n, cov) == (n2, cov2) and f == n
+
+
+def test_hostile_inputs(ctx):
+    """NaN / +-inf voxels and NaN / inf table entries agree with the restatement (NaN where it is NaN), both flavours; the threshold
+    refuses NaN, +-inf, negatives and 1.0 and keeps the value it had; the output refuses unknown modes."""
+    u = uniforms((16, 16, 16))
+    v, tf = phantom(), steep_tf()
+    nan, inf = v.copy(), v.copy()
+    nan[5, 7, 8, 3] = np.nan
+    inf[8, 8, 8, 3] = np.inf
+    inf[3, 9, 4, 3] = -np.inf
+    o_nan, o_inf = tf[0].copy(), tf[0].copy()
+    o_nan[20] = np.nan
+    o_inf[30] = np.inf
+    for name, vol, o in (("nan", nan, tf[0]), ("inf", inf, tf[0]), ("zero", np.zeros_like(v), tf[0]), ("tf nan", v, o_nan), ("tf inf", v, o_inf)):
+        ref, n_ref, cov_ref = sr.frame(u, W, H, vol, o, 0.5)
+        for fl in (0, 1):
+            ctx.set_kernel_flavour(fl)
+            try:
+                frag, (n, cov, _) = surface(ctx, capi.BASIC, 0.5, u, vol, (o, tf[1]))
+            finally:
+                ctx.set_kernel_flavour(0)
+            assert same(frag, ref), (name, fl)
+            assert (n, cov) == (n_ref, cov_ref), (name, fl)
+    want, _ = surface(ctx, capi.BASIC, 0.25, u, v, tf)
+    for bad in (float("nan"), float("inf"), float("-inf"), -0.25, 1.0, 1.5):
+        with pytest.raises(capi.VrError) as e:
+            ctx.set_surface_threshold(bad)
+        assert e.value.code == capi.VR_ERR_INVALID_ARG
+        ctx.set_output(capi.OUTPUT_SURFACE)
+        ctx.render(capi.BASIC)
+        ctx.set_output(capi.OUTPUT_COLOR)
+        assert np.array_equal(vt.bits(ctx.download()[0]), vt.bits(want))
+    with pytest.raises(capi.VrError) as e:
+        ctx.set_output(2)
+    assert e.value.code == capi.VR_ERR_INVALID_ARG
+
+
+@pytest.mark.parametrize("mode", [capi.ARITH_SEPARATE, capi.ARITH_FUSED])
+@pytest.mark.parametrize("variant,tau", [(capi.BASIC, float(sr.TAU_BASIC)), (capi.LIGHT, float(sr.TAU_LIGHT))], ids=["basic", "light"])
+def test_alpha_plane_is_the_colour_frames(ctx, mode, variant, tau):
+    """At the shader's own cut-off .w is the .a plane of the GPU's colour frame of the same context and of the oracle's, with equal
+    composited counts, in both arithmetic modes; every hit's xyz lies between two consecutive positions of its ray (the positions are
+    the same in both modes; the restatement does not model the fused mad, so WHICH pair is not asserted there)."""
+    v, tf = phantom(), steep_tf()
+    u = uniforms((16, 16, 16))
+    ctx.set_arithmetic(mode)
+    try:
+        colour, _, _ = vt.gpu_render(ctx, variant, u, [v], [tf])
+        n_colour = ctx.counters()[0]
+        surf, (n, cov, _) = surface(ctx, variant, tau, u, v, tf)
+    finally:
+        ctx.set_arithmetic(capi.ARITH_SEPARATE)
+    with ob.arithmetic(ob.FUSED if mode == capi.ARITH_FUSED else ob.SEPARATE):
+        ref, n_ref, _ = ob.render(variant, u, [v], [tf], W, H, nthreads=4)
+    assert n == n_colour == n_ref > 0 and cov > 0
+    assert np.array_equal(vt.bits(surf[..., 3]), vt.bits(colour[..., 3]))
+    assert np.array_equal(vt.bits(surf[..., 3]), vt.bits(ref[..., 3]))
+    assert cov == int((ref[..., 3] > f32(tau)).sum())
+    r = sr.march(u, W, H, v, tf[0], tau, positions=True)
+    flat = surf.reshape(-1, 4)
+    if mode == capi.ARITH_SEPARATE:
+        assert np.array_equal(vt.bits(flat), vt.bits(r["frag"]))
+    hit = flat[:, 3] > f32(tau)
+    P = r["positions"][:, hit]  # (steps, hits, 3)
+    q = flat[hit, :3][None]
+    lo, hi = np.minimum(P[:-1], P[1:]), np.maximum(P[:-1], P[1:])
+    between = np.all((q >= lo) & (q <= hi), axis=2).any(axis=0) | np.all(q == P, axis=2).any(axis=0)
+    assert hit.sum() > 50 and np.all(between)
+
+
+def test_layouts_shapes_and_arithmetic(ctx):
+    """Layouts 0 / 3 / 1 x flavours 0 / 1 / 6 / 17, synchronous, asynchronous, tiles of a world of 3 and a batch of four cameras give
+    one frame per arithmetic mode -- the restatement's in the separately rounded one."""
+    v, tf = air_and_core(), steep_tf()
+    us = [uniforms((24, 24, 24), yaw=0.6 + 0.4 * k, clip_z=(0.0, 0.1 * k)) for k in range(4)]
+    refs = [sr.frame(u, W, H, v, tf[0], 0.5) for u in us]
+    others = [capi.Context(W, H, 0) for _ in range(4)]
+    try:
+        for mode in (capi.ARITH_SEPARATE, capi.ARITH_FUSED):
+            ctx.set_arithmetic(mode)
+            frames = []
+            for layout in (0, 3, 1):
+                ctx.set_volume_layout(layout)
+                for fl in (0, 1, 6, 17):
+                    ctx.set_kernel_flavour(fl)
+                    frag, (n, cov, _) = surface(ctx, capi.LIGHT, 0.5, us[0], v, tf)
+                    assert ctx.last_kernel_flavour() == (26 if fl == 1 else 25)
+                    if mode == capi.ARITH_SEPARATE:
+                        assert (n, cov) == refs[0][1:]
+                    frames.append(frag)
+            ctx.set_volume_layout(0)
+            ctx.set_kernel_flavour(0)
+            ctx.set_output(capi.OUTPUT_SURFACE)
+            # asynchronous, into another context's frame
+            ctx.render_async(capi.LIGHT, others[0].frame_device_ptr(), ctx.stream(0))
+            ctx.counters()
+            frames.append(others[0].download()[0])
+            # tiles of each rank of a world of 3, unpacked into a frame
+            full = np.zeros((H, W, 4), f32)
+            for rank in range(3):
+                cnt = ctx.tile_count(rank, 3)
+                ctx.render_tiles(capi.LIGHT, rank, 3)
+                if cnt == 0:
+                    continue
+                tl = ctx.download_tiles(cnt)[0].reshape(cnt, capi.TILE, capi.TILE, 4)
+                tiles_x = (W + capi.TILE - 1) // capi.TILE
+                for k in range(cnt):
+                    ty, tx = divmod(rank + k * 3, tiles_x)
+                    y0, x0 = ty * capi.TILE, tx * capi.TILE
+                    h, w = min(capi.TILE, H - y0), min(capi.TILE, W - x0)
+                    full[y0:y0 + h, x0:x0 + w] = tl[k, :h, :w]
+            frames.append(full)
+            # four cameras in one launch
+            ctx.render_batch_async(capi.LIGHT, [vt.to_capi_uniforms(u) for u in us], [o.frame_device_ptr() for o in others], ctx.stream(1))
+            ctx.counters()
+            batch = [o.download()[0] for o in others]
+            ctx.set_output(capi.OUTPUT_COLOR)
+            frames.append(batch[0])
+            for f in frames[1:]:
+                assert np.array_equal(vt.bits(f), vt.bits(frames[0])), mode
+            if mode == capi.ARITH_SEPARATE:
+                for b, r in zip(batch, refs):
+                    assert np.array_equal(vt.bits(b), vt.bits(r[0]))
+    finally:
+        ctx.set_output(capi.OUTPUT_COLOR)
+        ctx.set_arithmetic(capi.ARITH_SEPARATE)
+        ctx.set_volume_layout(0)
+        ctx.set_kernel_flavour(0)
+        for o in others:
+            o.close()
+
+
+def test_iso_points_and_unsupported_variants(ctx):
+    """ISO in surface mode is iso_ref's refined point, both flavours, with ISO's counters; a colour ISO frame right after is what it
+    was; the other variants return VR_ERR_UNSUPPORTED and enqueue nothing (flavour, counters and frame stay)."""
+    v, tf = air_and_core(), (hr.default_opacity_tf(64), hr.default_color_tf(64))
+    u = uniforms((24, 24, 24))
+    ctx.set_iso_value(0.45)
+    colour0, _, _ = vt.gpu_render(ctx, capi.ISO, u, [v], [tf])
+    ref, n_ref, cov_ref = sr.iso_frame(u, W, H, v, tf, 0.45)
+    assert cov_ref > 0
+    for fl in (0, 1):
+        ctx.set_kernel_flavour(fl)
+        try:
+            frag, (n, cov, _) = surface(ctx, capi.ISO, 0.5, u, v, tf)
+            assert ctx.last_kernel_flavour() == (22 if fl else 21)
+        finally:
+            ctx.set_kernel_flavour(0)
+        assert np.array_equal(vt.bits(frag), vt.bits(ref)) and (n, cov) == (n_ref, cov_ref)
+    colour1, _, _ = vt.gpu_render(ctx, capi.ISO, u, [v], [tf])
+    assert np.array_equal(vt.bits(colour0), vt.bits(colour1)) and np.any(colour1[..., :3] != frag[..., :3])
+    counters, flavour = ctx.counters(), ctx.last_kernel_flavour()
+    ctx.set_output(capi.OUTPUT_SURFACE)
+    try:
+        for variant in (capi.VOLUME_MASK, capi.THREE_FILES, capi.MULTI_CTRT, capi.TF_CALIB, capi.ILLUSTRATIVE, capi.LIGHT_INSHADER,
+                        capi.MIP, capi.MINIP, capi.AVERAGE):
+            with pytest.raises(capi.VrError) as e:
+                ctx.render(variant)
+            assert e.value.code == capi.VR_ERR_UNSUPPORTED, variant
+    finally:
+        ctx.set_output(capi.OUTPUT_COLOR)
+    assert ctx.counters() == counters and ctx.last_kernel_flavour() == flavour
+    assert np.array_equal(vt.bits(ctx.download()[0]), vt.bits(colour1))
+    ctx.set_iso_value(0.5)
+
+
+def test_no_interference():
+    """With the output back at colour, BASIC / LIGHT / ISO / MIP / shadowed LIGHT give the bits they gave before the surface launches,
+    LIGHT's measured choice keeps its candidates, and a surface launch with shadows on runs the surface form (25, not the shadowed
+    23: no light volume is bound) and gives the bits it gives with shadows off."""
+    vl, tfl = vt.scene(capi.LIGHT, n=16)
+    u = uniforms((16, 16, 16))
+
+    def colour_frames(ctx):
+        out = []
+        for variant in (capi.BASIC, capi.LIGHT, capi.ISO, capi.MIP):
+            out.append(vt.gpu_render(ctx, variant, u, vl, tfl)[0])
+        ctx.set_shadows(2, 1.0)
+        out.append(vt.gpu_render(ctx, capi.LIGHT, u, vl, tfl)[0])
+        ctx.set_shadows(0, 1.0)
+        return out
+
+    with capi.Context(W, H, 0) as ctx:
+        before = colour_frames(ctx)
+        vt.gpu_render(ctx, capi.LIGHT, u, vl, tfl)
+        choice0 = ctx.kernel_choice()[0]
+        ctx.set_shadows(2, 1.0)
+        plain, _ = surface(ctx, capi.LIGHT, 0.5, u, vl[0], tfl[0])
+        assert ctx.last_kernel_flavour() == 25
+        ctx.set_shadows(0, 1.0)
+        unshadowed, _ = surface(ctx, capi.LIGHT, 0.5, u, vl[0], tfl[0])
+        assert np.array_equal(vt.bits(plain), vt.bits(unshadowed))
+        for fl in (0, 1):
+            ctx.set_kernel_flavour(fl)
+            surface(ctx, capi.BASIC, 0.95, u, vl[0], tfl[0])
+        ctx.set_kernel_flavour(0)
+        vt.gpu_render(ctx, capi.LIGHT, u, vl, tfl)
+        assert ctx.kernel_choice()[0] == choice0
+        after = colour_frames(ctx)
+        for a, b in zip(before, after):
+            assert np.array_equal(vt.bits(a), vt.bits(b))
+
+
+def test_depth(ctx):
+    """vr_surface_depth_async against the restatement, bit for bit; 1.0 where there is no hit; the threshold is the one at the call."""
+    v, tf = phantom(), steep_tf()
+    u = uniforms((16, 16, 16))
+    frag, (_, cov, _) = surface(ctx, capi.LIGHT, 0.5, u, v, tf)
+    assert cov > 0
+    with capi.Context(W, H, 0) as out:  # (its frame serves as device memory for the depth plane: W*H of its W*H*4 floats)
+        for tau in (0.5, 0.9):
+            ctx.set_surface_threshold(tau)
+            ctx.surface_depth(ctx.frame_device_ptr(), out.frame_device_ptr())
+            ctx.counters()
+            got = out.download()[0].reshape(-1)[:W * H].reshape(H, W)
+            want = sr.depth(frag, u, tau)
+            assert np.array_equal(vt.bits(got), vt.bits(want)), tau
+            assert np.all(got[~(frag[..., 3] > f32(tau))] == f32(1.0)) and np.any(got < 1.0)
+    ctx.set_surface_threshold(0.5)
+
+
+def test_pick(ctx):
+    """vr_pick against the restatement's record for hit, missed and uncovered pixels of LIGHT and ISO scenes; value[] is the uploaded
+    voxel of every slot of slot 0's size; after a pick the frame, the counters and the last flavour still describe the render before
+    it; a pixel outside the viewport is refused."""
+    v, tf = phantom(), steep_tf()
+    dose = vt.make_volume("sphere", 16)
+    u = uniforms((16, 16, 16))
+    ctx.volume_upload(1, dose)
+    try:
+        ref = sr.march(u, W, H, v, tf[0], 0.5)
+        flat_hit = ref["hit"].reshape(H, W)
+        covered = ref["rayhit"].reshape(H, W)
+        ys, xs = np.nonzero(flat_hit)
+        my, mx = np.nonzero(covered & ~flat_hit)
+        pixels = [(int(xs[0]), int(ys[0])), (int(xs[len(xs) // 2]), int(ys[len(ys) // 2])), (int(xs[-1]), int(ys[-1])), (0, 0)]
+        if len(mx):
+            pixels.append((int(mx[0]), int(my[0])))
+        colour, _, _ = vt.gpu_render(ctx, capi.LIGHT, u, [v], [tf])
+        counters, flavour = ctx.counters(), ctx.last_kernel_flavour()
+        ctx.set_surface_threshold(0.5)
+        for variant, iso in ((capi.LIGHT, 0.5), (capi.BASIC, 0.5), (capi.ISO, 0.3)):
+            ctx.set_iso_value(iso)
+            for x, y in pixels:
+                got = ctx.pick(variant, x, y).as_dict()
+                want = sr.pick(variant, u, W, H, [v, dose, None], tf, 0.5, x, y, iso=iso)
+                assert got["hit"] == want["hit"], (variant, x, y)
+                for key in ("uvw", "world", "depth", "alpha", "value"):
+                    assert np.array_equal(vt.bits(got[key]), vt.bits(want[key])), (variant, x, y, key)
+                assert np.array_equal(got["voxel"], want["voxel"]), (variant, x, y)
+            assert ctx.counters() == counters and ctx.last_kernel_flavour() == flavour
+            assert np.array_equal(vt.bits(ctx.download()[0]), vt.bits(colour))
+        assert ctx.pick(capi.LIGHT, *pixels[0]).hit == 1
+        for x, y in ((W, 0), (0, H)):
+            with pytest.raises(capi.VrError) as e:
+                ctx.pick(capi.LIGHT, x, y)
+            assert e.value.code == capi.VR_ERR_INVALID_ARG
+        with pytest.raises(capi.VrError) as e:
+            ctx.pick(capi.MIP, 1, 1)
+        assert e.value.code == capi.VR_ERR_UNSUPPORTED
+    finally:
+        ctx.set_iso_value(0.5)
+
+
+def test_stream_ordered_opacity_edit():
+    """An asynchronous opacity edit followed by a surface launch on the same stream shows the new table."""
+    v, tf = air_and_core(), steep_tf()
+    u = uniforms((24, 24, 24))
+    with capi.Context(W, H, 0) as ctx, capi.Context(W, H, 0) as out:
+        before, _ = surface(ctx, capi.LIGHT, 0.5, u, v, tf)
+        edited = steep_tf(gain=0.6)[0]
+        ctx.set_output(capi.OUTPUT_SURFACE)
+        ctx.tf_upload_async(0, opacity=edited, stream=ctx.stream(1))
+        ctx.render_async(capi.LIGHT, out.frame_device_ptr(), ctx.stream(1))
+        ctx.counters()
+        got = out.download()[0]
+        want = sr.frame(u, W, H, v, edited, 0.5)[0]
+        assert np.array_equal(vt.bits(got), vt.bits(want))
+        assert not np.array_equal(vt.bits(got), vt.bits(before))
+
+
+def test_host_surface_pick():
+    """Through the host surface: App.pick on a LIGHT and an ISO scene equals Context.pick with the same inputs."""
+    from volumerendering_amd import host, synth
+    for variant in (capi.LIGHT, capi.ISO):
+        with host.Application(W, H, 0) as app:
+            vol = host.VolumeFile.from_raw(synth.ct_phantom_raw_fast(32))
+            app.OnStart(variant, [vol])
+            if variant == capi.ISO:
+                app.set_iso_value(0.3)
+            app.set_surface_threshold(0.05)
+            app.OnUpdate()
+            app.OnRender()
+            hits = 0
+            for x, y in ((W // 2, H // 2), (W // 3, H // 2), (0, 0)):
+                a = app.pick(x, y).as_dict()
+                b = app.context().pick(variant, x, y).as_dict()
+                hits += a["hit"]
+                for key in a:
+                    assert np.array_equal(np.asarray(a[key]), np.asarray(b[key])), (variant, x, y, key)
+            assert hits > 0

@@ -27,6 +27,8 @@ VARIANT_NAMES = ["BASIC", "LIGHT", "VOLUME_MASK", "THREE_FILES", "MULTI_CTRT", "
                  "MIP", "MINIP", "AVERAGE", "ISO"]
 TILE = 64
 ARITH_SEPARATE, ARITH_FUSED = 0, 1
+OUTPUT_COLOR, OUTPUT_SURFACE = 0, 1  # Context.set_output (include/vr.h)
+MAX_VOLUMES = 3
 
 # every symbol include/vr.h declares (tests check that the library exports each of them)
 ABI_SYMBOLS = [
@@ -41,6 +43,7 @@ ABI_SYMBOLS = [
     "vr_present_packed_async", "vr_unpack_tiles_bgra8_async",
     "vr_tf_upload_opacity_async", "vr_tf_upload_color_async", "vr_skip_field", "vr_unbounded_box_launches",
     "vr_set_iso_value", "vr_set_shadows", "vr_shadow_volume",
+    "vr_set_output", "vr_set_surface_threshold", "vr_surface_depth_async", "vr_pick",
 ]
 
 
@@ -55,6 +58,20 @@ class Uniforms(C.Structure):
         ("toggles", C.c_int32 * 4),
         ("light_pos", C.c_float * 4), ("light_ambient", C.c_float * 4), ("light_diffuse", C.c_float * 4),
     ]
+
+
+class PickResult(C.Structure):
+    """struct vr_pick_result (include/vr.h)."""
+    _fields_ = [
+        ("hit", C.c_int32), ("uvw", C.c_float * 3), ("world", C.c_float * 3), ("depth", C.c_float), ("alpha", C.c_float),
+        ("voxel", C.c_int32 * 3), ("value", (C.c_float * 4) * MAX_VOLUMES),
+    ]
+
+    def as_dict(self) -> dict:
+        """The record as plain numpy values (float32 / int32), for comparisons."""
+        return dict(hit=int(self.hit), uvw=np.array(self.uvw, np.float32), world=np.array(self.world, np.float32),
+                    depth=np.float32(self.depth), alpha=np.float32(self.alpha), voxel=np.array(self.voxel, np.int32),
+                    value=np.array([list(v) for v in self.value], np.float32))
 
 
 class VrError(RuntimeError):
@@ -128,6 +145,10 @@ def load() -> C.CDLL:
     lib.vr_set_iso_value.argtypes = [vp, C.c_float]
     lib.vr_set_shadows.argtypes = [vp, i32, C.c_float]
     lib.vr_shadow_volume.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_int * 3)]
+    lib.vr_set_output.argtypes = [vp, i32]
+    lib.vr_set_surface_threshold.argtypes = [vp, C.c_float]
+    lib.vr_surface_depth_async.argtypes = [vp, vp, vp, vp]
+    lib.vr_pick.argtypes = [vp, i32, u32, u32, C.POINTER(PickResult)]
     lib.vr_present_async.argtypes = [vp, vp, vp, vp]
     lib.vr_present_tiles_async.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
     lib.vr_hint_frames_in_flight.argtypes = [vp, i32]
@@ -397,6 +418,27 @@ class Context:
         out = np.zeros(n, dtype=np.float32)
         self._chk(self.lib.vr_shadow_volume(self.h, out.ctypes.data, n, C.byref(dims)))
         return out.reshape(dims[2], dims[1], dims[0]), (int(dims[0]), int(dims[1]), int(dims[2]))
+
+    def set_output(self, mode: int):
+        """OUTPUT_COLOR (0, default) or OUTPUT_SURFACE (1): launches of BASIC / LIGHT / ISO enqueued after this call write surface
+        positions (q.x, q.y, q.z, alpha) instead of colour (include/vr.h vr_set_output)."""
+        self._chk(self.lib.vr_set_output(self.h, mode))
+
+    def set_surface_threshold(self, tau: float):
+        """The alpha threshold of BASIC / LIGHT surface launches enqueued after this call (default 0.5; finite, 0 <= tau < 1)."""
+        self._chk(self.lib.vr_set_surface_threshold(self.h, tau))
+
+    def surface_depth(self, d_surface: int, d_depth: int, stream: int = 0):
+        """vr_surface_depth_async: the depth (W*H floats, device) a rasteriser drawing at the points of the surface frame `d_surface`
+        (device) would write, with the context's uniforms and threshold at this call; 1.0 where there is no hit."""
+        self._chk(self.lib.vr_surface_depth_async(self.h, d_surface, d_depth, stream))
+
+    def pick(self, variant: int, x: int, y: int) -> PickResult:
+        """vr_pick: what is under pixel (x, y) of a BASIC / LIGHT / ISO frame with the context's uniforms (synchronous; the context's
+        frame, counters and last flavour stay those of the render before it)."""
+        out = PickResult()
+        self._chk(self.lib.vr_pick(self.h, variant, x, y, C.byref(out)))
+        return out
 
     def set_volume_layout(self, mode: int):
         """0 bricked copy (default), 1 the reference's vec4 voxels only, 3 x-fastest voxels + density plane (2 was removed)."""

@@ -89,6 +89,22 @@ int Application::OnResize(uint32_t width, uint32_t height)
     return rc;
 }
 
+int Application::Pick(uint32_t x, uint32_t y, vr_pick_result* out)
+{
+    if (!p_Ctx || !p_App) return VR_ERR_NOT_READY;
+    int rc = vr_pick(p_Ctx, p_App->Variant(), x, y, out);
+    if (rc != VR_OK) m_Error = vr_last_error(p_Ctx);
+    return rc;
+}
+
+int Application::SetSurfaceThreshold(float tau)
+{
+    if (!p_Ctx) return VR_ERR_HIP;
+    int rc = vr_set_surface_threshold(p_Ctx, tau);
+    if (rc != VR_OK) m_Error = vr_last_error(p_Ctx);
+    return rc;
+}
+
 int Application::ReadFrame(float* frag_rgba, uint8_t* present_bgra8, uint64_t* samples)
 {
     int rc = vr_download(p_Ctx, frag_rgba, present_bgra8, samples);

@@ -43,6 +43,13 @@ public:
     bool m_BToggles[4] = {false, false, false, false};  // (variable step size, jitter, -, -)
     bool m_PrepareOnDevice = false;  // forwarded to the scene in OnStart (MiniApp::SetPrepareOnDevice)
 
+    // What is under pixel (x, y) of the running scene's frame with the uniforms of the last OnUpdate (vr_pick: the surface position,
+    // its depth, the voxel and the values of every volume there).  Scenes drawn as BASIC, LIGHT or ISO; any other returns
+    // VR_ERR_UNSUPPORTED.  The frame of the last OnRender and its counters stay what they were.
+    int Pick(uint32_t x, uint32_t y, vr_pick_result* out);
+    // the accumulated opacity at which the unlit / lit scene's surface lies (vr_set_surface_threshold: finite, 0 <= tau < 1)
+    int SetSurfaceThreshold(float tau);
+
     // read back the fragment output / the presented BGRA8 frame of the last OnRender
     int ReadFrame(float* frag_rgba, uint8_t* present_bgra8 = nullptr, uint64_t* samples = nullptr);
 

@@ -346,6 +346,9 @@ int vrh_app_set_shadows(void* a, int divisor, float scale)
     p->SetShadows(divisor, scale);
     return VR_OK;
 }
+// Application::Pick / SetSurfaceThreshold (vr_pick, vr_set_surface_threshold of the application's context)
+int vrh_app_pick(void* a, uint32_t x, uint32_t y, vr_pick_result* out) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->Pick(x, y, out); }) }
+int vrh_app_set_surface_threshold(void* a, float tau) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->SetSurfaceThreshold(tau); }) }
 void vrh_app_set_prepare_on_device(void* a, int on) { static_cast<Application*>(a)->m_PrepareOnDevice = on != 0; }
 int vrh_app_update(void* a) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->OnUpdate(); }) }
 int vrh_app_render(void* a) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->OnRender(); }) }

@@ -235,6 +235,13 @@ struct vr_ctx {
     } shadow[kShadowRing];
     unsigned long long shadow_clock = 0;
     int shadow_cur = -1;  // the entry the launch being enqueued reads (mark_reads)
+    // Surface-position output (vr_set_output, vr_surf.h): the setting and the threshold, both captured at enqueue; vr_pick's frame
+    // (allocated on first use, freed with the viewport's buffers), and the pixel a pick launch is confined to (pick_px[0] < 0: none).
+    int output = VR_OUTPUT_COLOR;
+    float surf_tau = 0.5f;
+    float4* d_pick = nullptr;
+    float* d_pick_depth = nullptr;
+    int pick_px[2] = {-1, -1};
     std::string err;
 };
 
@@ -303,8 +310,10 @@ int alloc_frame(vr_ctx* c)
     VR_HIP(c, hipSetDevice(c->device));
     if (c->d_frame) (void)hipFree(c->d_frame);
     if (c->d_present) (void)hipFree(c->d_present);
+    if (c->d_pick) (void)hipFree(c->d_pick);
     c->d_frame = nullptr;
     c->d_present = nullptr;
+    c->d_pick = nullptr;
     size_t n = (size_t)c->W * c->H;
     VR_HIP(c, hipMalloc(&c->d_frame, n * sizeof(float4)));
     VR_HIP(c, hipMalloc(&c->d_present, n * sizeof(uint32_t)));
@@ -548,9 +557,10 @@ double rays_per_lane(const vr_ctx* c, int rank, int world, int frames)
 }
 
 // what a launch rendered, whatever kernel form it took (OrderSlot::scene_key: the key of the longest ray chain its sort reports)
-unsigned long long scene_key(const vr_ctx* c, int variant, int rank, int world, bool packed)
+// (a surface launch -- vr_set_output -- is a scene of its own: its chains say nothing about the colour launch's)
+unsigned long long scene_key(const vr_ctx* c, int variant, int rank, int world, bool packed, bool surface = false)
 {
-    return ((unsigned long long)variant << 16) ^ ((unsigned long long)world << 8) ^ (unsigned long long)rank ^ (packed ? 1ull << 63 : 0ull) ^
+    return ((unsigned long long)(variant | (surface ? 0x80 : 0)) << 16) ^ ((unsigned long long)world << 8) ^ (unsigned long long)rank ^ (packed ? 1ull << 63 : 0ull) ^
            ((unsigned long long)c->W << 40) ^ ((unsigned long long)c->H << 24);
 }
 
@@ -1032,8 +1042,10 @@ int prepare_shadow(vr_ctx* c, hipStream_t s, MarchParams& P, const vr_ctx::Shado
 }
 
 // The kernel form ("flavour") a launch runs: `fl` is the one asked for (vr_set_kernel_flavour, else VR_EXP_FLAVOUR), 0 = the default.
-int choose_flavour(vr_ctx* c, int fl, int variant, int n_frames, int rank, int world, bool packed, const Eligibility& E)
+int choose_flavour(vr_ctx* c, int fl, int variant, int n_frames, int rank, int world, bool packed, const Eligibility& E, bool surface)
 {
+    // the surface-position output of the unlit / lit shader: 26 without skipping, 25 with it (the isosurface's keeps 21 / 22)
+    if (surface && variant != VR_VARIANT_ISO) return fl == 1 ? 26 : 25;
     // the projections: 1 asks for the form without skipping (20), everything else runs as the skipping one (19); nothing is measured
     if (is_projection(variant)) return fl == 1 ? 20 : 19;
     // the isosurface: the same rule, 22 without skipping, 21 with it
@@ -1150,6 +1162,8 @@ KernelForm kernel_form(int fl, int variant)
     case 22: return {D::kIso, 0, false, false, false, 0u};
     case 23:
     case 24: return {D::kShadow, 0, false, false, false, 0u};
+    case 25:
+    case 26: return {D::kSurf, 0, false, false, false, 0u};
     default: return {D::kPlain, 0, false, false, false, 0u};  // 1, 6
     }
 }
@@ -1277,9 +1291,15 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
 {
     int nvol;
     bool off32;
+    // surface-position output (vr_set_output; a pick launch whatever the setting): the unlit / lit shader and the isosurface -- any
+    // other variant is refused whatever the scene holds
+    const bool surface = c->output == VR_OUTPUT_SURFACE || c->pick_px[0] >= 0;
+    if (surface && variant >= 0 && variant < VR_VARIANT_COUNT && variant != VR_VARIANT_BASIC && variant != VR_VARIANT_LIGHT &&
+        variant != VR_VARIANT_ISO)
+        return fail(c, VR_ERR_UNSUPPORTED, "vr_render: surface output exists for BASIC, LIGHT and ISO only");
     if (const int rc = check_render_args(c, variant, rank, world, n_frames, batch_u, batch_out, &nvol, &off32)) return rc;
-    // shadows: every frame of the launch reads one light volume, of less than 4 GiB
-    const bool shadowed = variant == VR_VARIANT_LIGHT && c->shadow_div != 0;
+    // shadows: every frame of the launch reads one light volume, of less than 4 GiB (a surface launch reads none)
+    const bool shadowed = variant == VR_VARIANT_LIGHT && c->shadow_div != 0 && !surface;
     vr_ctx::ShadowKey shadow_k;
     if (shadowed) {
         shadow_k = shadow_key(c, batch_u ? batch_u[0] : c->u);
@@ -1298,17 +1318,32 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
 
     MarchParams P;
     fill_launch_params(c, P, batch_u ? batch_u[0] : c->u, rank, world, packed);
+    if (surface && variant != VR_VARIANT_ISO) P.iso = c->surf_tau;  // (these launches read no level)
+    if (c->pick_px[0] >= 0)  // vr_pick: the one pixel's ray (a rectangle no larger than the one the box can be hit in)
+        for (int a = 0; a < 2; ++a) {
+            P.rect[a] = P.rect[a] > c->pick_px[a] ? P.rect[a] : c->pick_px[a];
+            P.rect[2 + a] = P.rect[2 + a] < c->pick_px[a] ? P.rect[2 + a] : c->pick_px[a];
+        }
     // the kernel choice: what can run, the skipping state (the prior reads its share of active bricks), the flavour
     const int requested = c->flavour == 0 ? c->default_flavour : c->flavour;
-    const Eligibility E = eligibility(c, requested, variant, n_frames, rank, world, packed, batch_u);
+    Eligibility E = eligibility(c, requested, variant, n_frames, rank, world, packed, batch_u);
+    if (surface && variant != VR_VARIANT_ISO) {
+        // The surface march skips by the distance field of BASIC / LIGHT under the weakest condition that is still exact: an inert
+        // brick's samples have opacity exactly 0, which leaves the accumulated alpha as it is whatever the colour table and the
+        // light hold -- neither is read.  So: the brick records, a zero prefix of the opacity table, the kernels' index range.
+        E.can_skip = requested != 1 && c->vol_bricks[0] && c->tf_zero_prefix[0] >= 0 &&
+                     skip_bricks(c->vol[0].nx) * (long long)skip_bricks(c->vol[0].ny) < (1 << 23);
+        E.chain_known = 0;
+    }
     if (E.can_skip) {
         if (const int rc = prepare_skip(c, variant, s, P)) return rc;
         if (c->skip_pending) ++c->unbounded_launches;
     }
-    const int fl = choose_flavour(c, requested, variant, n_frames, rank, world, packed, E);
+    const int fl = choose_flavour(c, requested, variant, n_frames, rank, world, packed, E, surface);
     c->last_flavour = fl;
     const KernelForm form = kernel_form(fl, variant);
-    c->last_proj = form.family == LaunchDesc::kProj || form.family == LaunchDesc::kIso || form.family == LaunchDesc::kShadow;
+    c->last_proj = form.family == LaunchDesc::kProj || form.family == LaunchDesc::kIso || form.family == LaunchDesc::kShadow ||
+                   form.family == LaunchDesc::kSurf;
     const float2* vrange = nullptr;
     if (fl == 19 || fl == 21) {
         vrange = prepare_proj(c, s, P);
@@ -1339,6 +1374,8 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
     if (frame_events) VR_HIP(c, hipEventRecord(c->tm.ev_begin, s));
     // the shadowed form (23 with LIGHT's distance field in place, else 24's kernels)
     const bool shadow_skip = form.family == LaunchDesc::kShadow && fl == 23 && P.brick_dist != nullptr;
+    // the surface form likewise (25 with the distance field in place, else 26's kernels)
+    const bool surf_skip = form.family == LaunchDesc::kSurf && fl == 25 && P.brick_dist != nullptr;
     if (P.n_blocks > 0) {
         // the light volume it reads: built here when its key has none (inside vr_last_timing's total, outside its kernel time)
         if (shadowed)
@@ -1360,7 +1397,7 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
         P.block_counts = c->d_block_counts[cb];
         c->cnt_buf = cb;
         const unsigned long long okey = ((unsigned long long)grid.x << 32) ^ ((unsigned long long)block.x << 20) ^
-                                        ((unsigned long long)variant << 16) ^ ((unsigned long long)world << 8) ^ (unsigned long long)rank ^
+                                        ((unsigned long long)(variant | (surface ? 0x10 : 0)) << 16) ^ ((unsigned long long)world << 8) ^ (unsigned long long)rank ^
                                         (packed ? 1ull << 63 : 0ull);
         const bool ordered = grid.x <= (unsigned)kOrderMaxBlocks && grid.x % 8u == 0;
         if (const int rc = wait_for_order(c, s, ordered, okey, slot_sort, &P.order)) return rc;
@@ -1384,7 +1421,8 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
         L.grid = dim3(grid.x * (unsigned)n_frames);
         L.block = block;
         L.vrange = vrange;
-        L.proj_skip = vrange != nullptr || shadow_skip;
+        L.proj_skip = vrange != nullptr || shadow_skip || surf_skip;
+        L.surface = surface;
         if (pw) {
             // persistent wavefronts: `grid` stays the number of LOGICAL blocks (records, launch order); the launch itself is one
             // workgroup of form.pw_threads per CU (fewer when there are fewer packets), TF slot 0 in LDS when it fits
@@ -1406,7 +1444,7 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
         mark_reads(c, P);
         if (time_with_events) VR_HIP(c, hipEventRecord(c->ring.k1[ring], s));
 
-        if (const int rc = enqueue_sort(c, s, cb, ordered, okey, scene_key(c, variant, rank, world, packed), grid.x, ring, time_with_events, pw))
+        if (const int rc = enqueue_sort(c, s, cb, ordered, okey, scene_key(c, variant, rank, world, packed, surface), grid.x, ring, time_with_events, pw))
             return rc;
         if (frame_events) VR_HIP(c, hipEventRecord(c->tm.ev_k1, s));
         ++c->ring.head;
@@ -1793,6 +1831,8 @@ void vr_destroy(vr_ctx* c)
     if (c->d_frame) (void)hipFree(c->d_frame);
     if (c->d_tiles) (void)hipFree(c->d_tiles);
     if (c->d_present) (void)hipFree(c->d_present);
+    if (c->d_pick) (void)hipFree(c->d_pick);
+    if (c->d_pick_depth) (void)hipFree(c->d_pick_depth);
     if (c->d_counters) (void)hipFree(c->d_counters);
     if (c->d_pw_heads) (void)hipFree(c->d_pw_heads);
     for (auto* b : c->d_block_counts)
@@ -2498,6 +2538,118 @@ int vr_shadow_volume(vr_ctx* c, float* out, size_t capacity, int dims[3])
     if (dims)
         for (int a = 0; a < 3; ++a) dims[a] = g[a];
     return (int)n;
+}
+
+int vr_set_output(vr_ctx* c, int mode)
+{
+    if (!c) return VR_ERR_INVALID_ARG;
+    if (mode != VR_OUTPUT_COLOR && mode != VR_OUTPUT_SURFACE) return fail(c, VR_ERR_INVALID_ARG, "vr_set_output: unknown mode");
+    c->output = mode;
+    return VR_OK;
+}
+
+int vr_set_surface_threshold(vr_ctx* c, float tau)
+{
+    if (!c) return VR_ERR_INVALID_ARG;
+    if (!std::isfinite(tau) || !(tau >= 0.0f) || !(tau < 1.0f))
+        return fail(c, VR_ERR_INVALID_ARG, "vr_set_surface_threshold: the threshold must be finite, >= 0 and < 1");
+    c->surf_tau = tau;
+    return VR_OK;
+}
+
+namespace {
+
+// the uniforms a depth pass needs, and the threshold of the context now
+DepthParams depth_params(const vr_ctx* c)
+{
+    DepthParams D;
+    std::memcpy(D.view, c->u.view, sizeof D.view);
+    std::memcpy(D.proj, c->u.proj, sizeof D.proj);
+    D.tau = c->surf_tau;
+    return D;
+}
+
+}  // namespace
+
+int vr_surface_depth_async(vr_ctx* c, const void* d_surface, void* d_depth, void* stream)
+{
+    if (!c) return VR_ERR_INVALID_ARG;
+    if (!d_surface || !d_depth) return fail(c, VR_ERR_INVALID_ARG, "vr_surface_depth_async: a buffer is NULL");
+    if (!c->have_uniforms) return fail(c, VR_ERR_NOT_READY, "vr_surface_depth_async: vr_set_uniforms has not been called");
+    VR_HIP(c, hipSetDevice(c->device));
+    (void)hipGetLastError();
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const size_t n = (size_t)c->W * c->H;
+    hipLaunchKernelGGL(surface_depth_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float4*)d_surface, (float*)d_depth,
+                       (int)n, depth_params(c));
+    VR_HIP(c, hipGetLastError());
+    return VR_OK;
+}
+
+int vr_pick(vr_ctx* c, int variant, uint32_t x, uint32_t y, vr_pick_result* out)
+{
+    if (!c) return VR_ERR_INVALID_ARG;
+    if (!out) return fail(c, VR_ERR_INVALID_ARG, "vr_pick: out is NULL");
+    if (x >= c->W || y >= c->H) return fail(c, VR_ERR_INVALID_ARG, "vr_pick: the pixel lies outside the viewport");
+    VR_HIP(c, hipSetDevice(c->device));
+    // what the render before the pick left behind stays what the context reports: its counters are summed now ...
+    if (const int rc = fetch_counters(c)) return rc;
+    if (!c->d_pick) VR_HIP(c, hipMalloc(&c->d_pick, (size_t)c->W * c->H * sizeof(float4)));
+    if (!c->d_pick_depth) VR_HIP(c, hipMalloc(&c->d_pick_depth, sizeof(float)));
+    // ... and the launch's bookkeeping is put back behind the pick's own launch (which takes the next record slot, not the last one's)
+    const int last_flavour = c->last_flavour, last_tiles = c->last_tiles, cnt_buf = c->cnt_buf, cnt_blocks = c->cnt_blocks;
+    const bool last_proj = c->last_proj, tm_valid = c->tm.valid;
+    const size_t cnt_offset = c->cnt_offset;
+    const long long ring_head = c->ring.head;
+    const unsigned long long counters[3] = {c->h_counters[0], c->h_counters[1], c->h_counters[2]};
+    c->pick_px[0] = (int)x;
+    c->pick_px[1] = (int)y;
+    const int rc = enqueue_render(c, variant, 0, 1, false, c->d_pick, c->stream, false);
+    c->pick_px[0] = c->pick_px[1] = -1;
+    const hipError_t sync = hipDeviceSynchronize();
+    if (sync == hipSuccess) drained(c);
+    c->last_flavour = last_flavour;
+    c->last_tiles = last_tiles;
+    c->cnt_buf = cnt_buf;
+    c->cnt_blocks = cnt_blocks;
+    c->cnt_offset = cnt_offset;
+    c->cnt_pending = false;
+    c->last_proj = last_proj;
+    c->tm.valid = tm_valid;
+    c->ring.head = ring_head;
+    for (int i = 0; i < 3; ++i) c->h_counters[i] = counters[i];
+    if (rc != VR_OK) return rc;
+    VR_HIP(c, sync);
+
+    const size_t idx = (size_t)y * c->W + x;
+    float4 px;
+    VR_HIP(c, hipMemcpy(&px, c->d_pick + idx, sizeof px, hipMemcpyDeviceToHost));
+    std::memset(out, 0, sizeof *out);
+    out->alpha = px.w;
+    out->depth = 1.0f;
+    out->hit = px.w > c->surf_tau ? 1 : 0;  // (an ISO frame's .w is 1 or 0)
+    if (!out->hit) return VR_OK;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(surface_depth_kernel, dim3(1), dim3(256), 0, c->stream, (const float4*)(c->d_pick + idx), c->d_pick_depth, 1,
+                       depth_params(c));
+    VR_HIP(c, hipGetLastError());
+    VR_HIP(c, hipStreamSynchronize(c->stream));
+    VR_HIP(c, hipMemcpy(&out->depth, c->d_pick_depth, sizeof(float), hipMemcpyDeviceToHost));
+    const float q[3] = {px.x, px.y, px.z};
+    out->world[0] = q[0] - 0.5f;
+    out->world[1] = q[1] - 0.5f;
+    out->world[2] = (0.5f - q[2]) * 0.5f;
+    const int n0[3] = {c->vol[0].nx, c->vol[0].ny, c->vol[0].nz};
+    for (int a = 0; a < 3; ++a) {
+        out->uvw[a] = q[a];
+        const float f = std::floor(q[a] * (float)n0[a]);
+        out->voxel[a] = f >= (float)(n0[a] - 1) ? n0[a] - 1 : (f > 0.0f ? (int)f : 0);  // (NaN -> 0)
+    }
+    const size_t v = ((size_t)out->voxel[2] * (size_t)n0[1] + (size_t)out->voxel[1]) * (size_t)n0[0] + (size_t)out->voxel[0];
+    for (int i = 0; i < VR_MAX_VOLUMES; ++i)
+        if (c->vol[i].data && c->vol[i].nx == n0[0] && c->vol[i].ny == n0[1] && c->vol[i].nz == n0[2])
+            VR_HIP(c, hipMemcpy(out->value[i], c->vol[i].data + v, sizeof(float4), hipMemcpyDeviceToHost));
+    return VR_OK;
 }
 
 int vr_set_volume_layout(vr_ctx* c, int mode)

@@ -123,7 +123,8 @@ struct MarchParams {
     unsigned long long* block_counts;  // [blocks of this frame][kBlockRecord]: composited, covered, fetched, t0, t1, hw id
     unsigned batch_n;        // frames the launch carries (1 .. kBatchMax): see MarchBatch
     float iso;               // VR_VARIANT_ISO: the level (vr_set_iso_value) when the launch was enqueued (in the tail padding after
-                             // batch_n: the size and every other offset of the struct are what they were without it)
+                             // batch_n: the size and every other offset of the struct are what they were without it).  Surface
+                             // launches of the unlit / lit shader (vr_surf.h), which read no level: the alpha threshold
 };
 
 // One launch may carry up to kBatchMax frames of the same scene and shape (different uniforms, output and record buffers).
@@ -151,12 +152,13 @@ struct PwQueue {
 // What enqueue_render decided about one march launch; handed to launch_march of the arithmetic mode's translation unit
 // (vr_launch.h: namespace vr = separately rounded multiply-adds, namespace vrf = fused).  Host only.
 struct LaunchDesc {
-    enum Family { kPlain, kDp, kPw, kP2, kLt, kProj, kIso, kShadow };
+    enum Family { kPlain, kDp, kPw, kP2, kLt, kProj, kIso, kShadow, kSurf };
     int variant;      // vr_variant
     Family family;    // march_kernel, march_dp_kernel, march_pw_kernel (persistent wavefronts: grid = workgroups, the packets come
                       // from `queue`), march_p2_kernel (the same, corner loads two steps ahead), march_lt_kernel (LDS tiles, lit shader),
                       // march_proj_kernel (vr_proj.h: the intensity projections), march_iso_kernel (vr_iso.h: the isosurface),
-                      // march_shadow_kernel (vr_shadow.h: the lit shader with shadows; MarchParams::vol[1] = the light volume)
+                      // march_shadow_kernel (vr_shadow.h: the lit shader with shadows; MarchParams::vol[1] = the light volume),
+                      // march_surf_kernel (vr_surf.h: the surface-position output of the unlit / lit shader; MarchParams::iso = the threshold)
     bool off32;       // every bound volume < 4 GiB: 32-bit byte offsets
     int lanes;        // kDp: lanes per ray (2 / 4)
     bool pipe;        // kDp / kPw: the next round's / step's corner loads software-pipelined
@@ -167,8 +169,9 @@ struct LaunchDesc {
     PwQueue queue;
     dim3 grid, block;
     const float2* vrange;  // kProj: (min, max) of volume 0 (vr_proj.h); with `proj_skip` the brick records are MarchParams::bricks
-    bool proj_skip;        // kProj / kIso / kShadow: the skipping form (march_proj_kernel<.., SKIP = true, ..>, march_iso_kernel<.., true, ..>,
-                           // march_shadow_kernel<.., true, ..>)
+    bool proj_skip;        // kProj / kIso / kShadow / kSurf: the skipping form (march_proj_kernel<.., SKIP = true, ..>,
+                           // march_iso_kernel<.., true, ..>, march_shadow_kernel<.., true, ..>, march_surf_kernel<.., true, ..>)
+    bool surface;          // kIso: the refined point instead of the shaded fragment (iso_point_kernel, vr_surf.h)
 };
 
 }  // namespace vr

@@ -20,7 +20,8 @@
 namespace VR_KNS {
 
 // One ray: what a lane does for its pixel `slot`.
-template <bool OFF32, bool SKIP>
+// SURF (vr_set_output(VR_OUTPUT_SURFACE)): the refined point is the pixel, (q, 1); nothing is shaded.
+template <bool OFF32, bool SKIP, bool SURF = false>
 __device__ __forceinline__ void iso_packet(const MarchParams& P, const PixelSlot& slot, float4& dst, unsigned& samples, unsigned& covered,
                                            unsigned& fetched)
 {
@@ -141,6 +142,10 @@ __device__ __forceinline__ void iso_packet(const MarchParams& P, const PixelSlot
             q = mk3(mad(step.x, t, pp.x), mad(step.y, t, pp.y), mad(step.z, t, pp.z));
             wq = mk3(mad(wstep.x, t, wp.x), mad(wstep.y, t, wp.y), mad(wstep.z, t, wp.z));
         }
+    }
+    if constexpr (SURF) {
+        dst = make_float4(q.x, q.y, q.z, 1.0f);
+        return;
     }
     const float4 s = tex3_rgba<OFF32>(P.vol[0], q);
     const f3 N = normalize3(mk3(s.x, s.y, s.z));  // (zero gradient: NaN -> max(NaN, 0) = 0, ambient only, as LIGHT)

@@ -24,6 +24,8 @@
 #include "vr_iso.h"
 // Shadows of the lit shader through a light volume (flavours 23 and 24; the build and the shadowed march)
 #include "vr_shadow.h"
+// The surface-position output of the unlit / lit shader (flavours 25 and 26) and of the isosurface; the depth of a surface frame
+#include "vr_surf.h"
 
 #include <type_traits>
 
@@ -121,6 +123,20 @@ void launch_iso(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
                L.proj_skip, L.off32, B.n_frames > 1);
 }
 
+// the isosurface's refined points (surface output): the same
+void launch_iso_point(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
+{
+    with_flags([&](auto S, auto O, auto BT) { hipLaunchKernelGGL((iso_point_kernel<O, S, BT>), L.grid, L.block, 0, s, B); },
+               L.proj_skip, L.off32, B.n_frames > 1);
+}
+
+// the surface-position output of the unlit / lit shader: skipping x addressing x frames per launch
+void launch_surf(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
+{
+    with_flags([&](auto S, auto O, auto BT) { hipLaunchKernelGGL((march_surf_kernel<O, S, BT>), L.grid, L.block, 0, s, B); },
+               L.proj_skip, L.off32, B.n_frames > 1);
+}
+
 // the shadowed lit shader: skipping x addressing x frames per launch
 void launch_shadow(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
 {
@@ -142,8 +158,13 @@ void launch_march(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
         launch_shadow(L, s, B);
         return;
     }
+    if (L.family == LaunchDesc::kSurf) {
+        launch_surf(L, s, B);
+        return;
+    }
     if (L.family == LaunchDesc::kIso) {
-        launch_iso(L, s, B);
+        if (L.surface) launch_iso_point(L, s, B);
+        else launch_iso(L, s, B);
         return;
     }
     if (L.family == LaunchDesc::kProj) {

@@ -59,7 +59,8 @@ def load() -> C.CDLL:
         "vrh_camera_key": (None, [vp, i32]), "vrh_camera_get": (None, [vp, vp]),
         "vrh_app_create": (vp, [u32, u32, i32]), "vrh_app_free": (None, [vp]), "vrh_app_ok": (i32, [vp]),
         "vrh_app_error": (C.c_char_p, [vp]), "vrh_app_context": (vp, [vp]), "vrh_app_camera": (vp, [vp]),
-        "vrh_app_start": (i32, [vp, i32, vp, vp, vp, i32]), "vrh_app_set_prepare_on_device": (None, [vp, i32]), "vrh_app_set_iso_value": (i32, [vp, f32]), "vrh_app_set_shadows": (i32, [vp, i32, f32]), "vrh_app_update": (i32, [vp]), "vrh_app_render": (i32, [vp]),
+        "vrh_app_start": (i32, [vp, i32, vp, vp, vp, i32]), "vrh_app_set_prepare_on_device": (None, [vp, i32]), "vrh_app_set_iso_value": (i32, [vp, f32]), "vrh_app_set_shadows": (i32, [vp, i32, f32]),
+        "vrh_app_pick": (i32, [vp, u32, u32, C.POINTER(capi.PickResult)]), "vrh_app_set_surface_threshold": (i32, [vp, f32]), "vrh_app_update": (i32, [vp]), "vrh_app_render": (i32, [vp]),
         "vrh_app_resize": (i32, [vp, u32, u32]), "vrh_app_read_frame": (i32, [vp, vp, vp, C.POINTER(u64)]),
         "vrh_app_set_params": (None, [vp, i32, i32, f32, vp, vp]),
         "vrh_app_get_stepping": (None, [vp, C.POINTER(i32), C.POINTER(f32)]),
@@ -447,6 +448,17 @@ class Application:
         if rc < 0:
             raise capi.VrError(rc, "vrh_app_set_shadows: " + ("the scene is not lit" if rc == capi.VR_ERR_NOT_READY else
                                                               "divisor 0, 1, 2, 4 or 8 and a finite scale >= 0"))
+
+    def pick(self, x: int, y: int) -> capi.PickResult:
+        """Application::Pick: what is under pixel (x, y) of the running BASIC / LIGHT / ISO scene with the uniforms of the last
+        OnUpdate (include/vr.h vr_pick); the frame of the last OnRender stays."""
+        out = capi.PickResult()
+        self._chk(self.lib.vrh_app_pick(self.h, x, y, C.byref(out)))
+        return out
+
+    def set_surface_threshold(self, tau: float):
+        """Application::SetSurfaceThreshold: the accumulated opacity at which the surface of an unlit / lit scene lies."""
+        self._chk(self.lib.vrh_app_set_surface_threshold(self.h, tau))
 
     def set_params(self, fragment_mode=0, steps_count=-1, step_size=-1.0, clips=None, toggles=None):
         c = (C.c_float * 6)(*clips) if clips is not None else None
