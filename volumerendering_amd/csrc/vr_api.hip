@@ -60,6 +60,31 @@ struct GenBuf {
     }
 };
 
+// Something built on `stream` with `ev` recorded behind the build: a launch on another stream waits for the event once (seen), none
+// after a draining call (pending = false).
+struct BuiltOn {
+    hipEvent_t ev = nullptr;
+    hipStream_t stream = nullptr;
+    bool pending = false;
+    hipStream_t seen[kEditSeen] = {};
+    int seen_next = 0;
+    void built(hipStream_t s)  // (ev has been recorded on s)
+    {
+        stream = s;
+        pending = true;
+        for (auto& x : seen) x = nullptr;
+    }
+    hipError_t order_behind(hipStream_t s)  // a launch on s comes after the build
+    {
+        if (!pending || s == stream) return hipSuccess;
+        for (auto x : seen)
+            if (x == s) return hipSuccess;
+        const hipError_t e = hipStreamWaitEvent(s, ev, 0);
+        if (e == hipSuccess) seen[seen_next++ % kEditSeen] = s;
+        return e;
+    }
+};
+
 struct vr_ctx {
     int device = 0;
     uint32_t W = 0, H = 0;
@@ -192,18 +217,13 @@ struct vr_ctx {
     float abox[6] = {-3.0e38f, -3.0e38f, -3.0e38f, 3.0e38f, 3.0e38f, 3.0e38f};  // uvw box around the active bricks of that field (MarchParams::abox)
     // Intensity projections (vr_proj.h) and the isosurface (vr_iso.h): (min, max) of volume 0 per empty-space brick and over the whole
     // volume, rebuilt on the launch's stream by the first skipping projection or isosurface launch after a volume change (proj_epoch = the
-    // brick_epoch they were built at).  Launches on other streams wait once for the event behind the build (proj_seen), none after a
-    // draining call (proj_pending).
+    // brick_epoch they were built at).  Launches on other streams wait once for the event behind the build (proj_built).
     float2* proj_rec = nullptr;
     size_t proj_rec_cap = 0;  // bytes
     float2* proj_range = nullptr;
     unsigned long long proj_epoch = ~0ull;
-    hipEvent_t proj_ev = nullptr;
-    hipStream_t proj_stream = nullptr;
-    bool proj_pending = false;
-    hipStream_t proj_seen[kEditSeen] = {};
-    int proj_seen_next = 0;
-    bool last_proj = false;  // the last launch was a projection, an isosurface or shadowed (vr_kernel_choice reports no candidates)
+    BuiltOn proj_built;
+    bool last_unmeasured = false;  // the last launch's family is never measured (KernelForm::measured): vr_kernel_choice reports no candidates
     float iso = 0.5f;        // VR_VARIANT_ISO's level (vr_set_iso_value), copied into MarchParams::iso at enqueue
     // Shadows of the lit shader (vr_set_shadows, vr_shadow.h): the setting, and a ring of light volumes, one per key.  A launch whose key
     // matches an entry reads it (waiting once per stream for its build); otherwise it builds the least recently used entry on its own
@@ -226,11 +246,7 @@ struct vr_ctx {
         GenBuf buf;
         ShadowKey key;
         bool valid = false;
-        hipEvent_t built = nullptr;   // behind the build, on `stream`
-        hipStream_t stream = nullptr;
-        bool pending = false;         // the build may still run: other streams wait for `built` once (seen), none after a draining call
-        hipStream_t seen[kEditSeen] = {};
-        int seen_next = 0;
+        BuiltOn built;                // the build may still run: other streams wait for it once
         unsigned long long used = 0;  // (least recently used entry is rebuilt)
     } shadow[kShadowRing];
     unsigned long long shadow_clock = 0;
@@ -727,8 +743,8 @@ void drained(vr_ctx* c)
     c->retired_dev.clear();
     c->retired_host.clear();
     c->drained_gen = c->edit_gen;
-    c->proj_pending = false;
-    for (auto& e : c->shadow) e.pending = false;
+    c->proj_built.pending = false;
+    for (auto& e : c->shadow) e.built.pending = false;
 }
 
 // Before `s` rewrites generation b: every launch that read it must have finished, whatever its stream (launches on different
@@ -829,18 +845,24 @@ int grow(vr_ctx* c, void** d, size_t* cap, size_t bytes, bool drain)
     return VR_OK;
 }
 
+// The empty-space brick grid of volume slot sv in P: bricks per axis and voxels per brick edge (exact in f32).
+void fill_brick_grid(MarchParams& P, int sv, const DevVolume& v)
+{
+    P.skip_vol = sv;
+    P.bnx = skip_bricks(v.nx);
+    P.bny = skip_bricks(v.ny);
+    P.bnz = skip_bricks(v.nz);
+    P.bsx = (float)v.nx * kBrickInv;
+    P.bsy = (float)v.ny * kBrickInv;
+    P.bsz = (float)v.nz * kBrickInv;
+}
+
 // Exact empty-space skipping (E.can_skip): fills P's brick fields from c, and rebuilds what is stale of the merged mask records, the
 // distance field, the share of active bricks (active_fraction, which the kernel choice reads) and the box of the active bricks.
 int prepare_skip(vr_ctx* c, int variant, hipStream_t s, MarchParams& P)
 {
     const int sv = variant == VR_VARIANT_VOLUME_MASK ? 2 : 0;
-    P.skip_vol = sv;
-    P.bnx = skip_bricks(c->vol[sv].nx);
-    P.bny = skip_bricks(c->vol[sv].ny);
-    P.bnz = skip_bricks(c->vol[sv].nz);
-    P.bsx = (float)c->vol[sv].nx * kBrickInv;
-    P.bsy = (float)c->vol[sv].ny * kBrickInv;
-    P.bsz = (float)c->vol[sv].nz * kBrickInv;
+    fill_brick_grid(P, sv, c->vol[sv]);
     P.tf_zero_prefix = c->tf_zero_prefix[0];
     P.bricks = c->vol_bricks[sv];
     P.use_rgb = 0;
@@ -906,13 +928,7 @@ int prepare_skip(vr_ctx* c, int variant, hipStream_t s, MarchParams& P)
 const float2* prepare_proj(vr_ctx* c, hipStream_t s, MarchParams& P)
 {
     const DevVolume& v = c->vol[0];
-    P.skip_vol = 0;
-    P.bnx = skip_bricks(v.nx);
-    P.bny = skip_bricks(v.ny);
-    P.bnz = skip_bricks(v.nz);
-    P.bsx = (float)v.nx * kBrickInv;
-    P.bsy = (float)v.ny * kBrickInv;
-    P.bsz = (float)v.nz * kBrickInv;
+    fill_brick_grid(P, 0, v);
     const size_t nb = (size_t)P.bnx * P.bny * P.bnz;
     if (c->proj_epoch != c->brick_epoch || !c->proj_rec || !c->proj_range) {
         // (a volume change drained the device: nothing in flight reads the records; a smaller buffer is retired all the same)
@@ -922,31 +938,22 @@ const float2* prepare_proj(vr_ctx* c, hipStream_t s, MarchParams& P)
             fail(c, VR_ERR_OOM, "vr_render: no memory for the projection's volume range");
             return nullptr;
         }
-        if (!c->proj_ev && hipEventCreateWithFlags(&c->proj_ev, hipEventDisableTiming) != hipSuccess) {
-            c->proj_ev = nullptr;
+        if (!c->proj_built.ev && hipEventCreateWithFlags(&c->proj_built.ev, hipEventDisableTiming) != hipSuccess) {
+            c->proj_built.ev = nullptr;
             fail(c, VR_ERR_HIP, "vr_render: hipEventCreateWithFlags failed");
             return nullptr;
         }
         hipLaunchKernelGGL(brick_range_kernel, dim3((unsigned)nb), dim3(64), 0, s, v.data, v.nx, v.ny, v.nz, P.bnx, P.bny, c->proj_rec);
         hipLaunchKernelGGL(range_reduce_kernel, dim3(1), dim3(1024), 0, s, (const float2*)c->proj_rec, (int)nb, c->proj_range);
-        if (hipGetLastError() != hipSuccess || hipEventRecord(c->proj_ev, s) != hipSuccess) {
+        if (hipGetLastError() != hipSuccess || hipEventRecord(c->proj_built.ev, s) != hipSuccess) {
             fail(c, VR_ERR_HIP, "vr_render: the projection's brick ranges could not be enqueued");
             return nullptr;
         }
         c->proj_epoch = c->brick_epoch;
-        c->proj_stream = s;
-        c->proj_pending = true;
-        for (auto& x : c->proj_seen) x = nullptr;
-    } else if (c->proj_pending && s != c->proj_stream) {
-        bool seen = false;
-        for (auto x : c->proj_seen) seen = seen || x == s;
-        if (!seen) {
-            if (hipStreamWaitEvent(s, c->proj_ev, 0) != hipSuccess) {
-                fail(c, VR_ERR_HIP, "vr_render: hipStreamWaitEvent failed");
-                return nullptr;
-            }
-            c->proj_seen[c->proj_seen_next++ % kEditSeen] = s;
-        }
+        c->proj_built.built(s);
+    } else if (c->proj_built.order_behind(s) != hipSuccess) {
+        fail(c, VR_ERR_HIP, "vr_render: hipStreamWaitEvent failed");
+        return nullptr;
     }
     P.bricks = c->proj_rec;
     return c->proj_range;
@@ -999,10 +1006,10 @@ int prepare_shadow(vr_ctx* c, hipStream_t s, MarchParams& P, const vr_ctx::Shado
         const bool fresh = texels * sizeof(float) > v.buf.cap;
         // (a smaller buffer may still be read by launches in flight: it is retired, freed by the next draining call)
         if (const int rc = grow(c, &v.buf.d, &v.buf.cap, texels * sizeof(float), false)) return rc;
-        if (!v.built) VR_HIP(c, hipEventCreateWithFlags(&v.built, hipEventDisableTiming));
+        if (!v.built.ev) VR_HIP(c, hipEventCreateWithFlags(&v.built.ev, hipEventDisableTiming));
         if (!fresh) {
             if (const int rc = reuse_wait(c, s, v.buf)) return rc;
-            if (v.pending && v.stream != s) VR_HIP(c, hipStreamWaitEvent(s, v.built, 0));
+            if (v.built.pending && v.built.stream != s) VR_HIP(c, hipStreamWaitEvent(s, v.built.ev, 0));
         }
     }
     DevVolume& lv = P.vol[1];
@@ -1021,20 +1028,13 @@ int prepare_shadow(vr_ctx* c, hipStream_t s, MarchParams& P, const vr_ctx::Shado
         if (c->arith == VR_ARITH_FUSED) vrf::launch_shadow_build(P, (float*)v.buf.d, c->shadow_sigma, skip, off32, s);
         else vr::launch_shadow_build(P, (float*)v.buf.d, c->shadow_sigma, skip, off32, s);
         VR_HIP(c, hipGetLastError());
-        VR_HIP(c, hipEventRecord(v.built, s));
+        VR_HIP(c, hipEventRecord(v.built.ev, s));
         v.buf.written();
         v.key = key;
         v.valid = true;
-        v.stream = s;
-        v.pending = true;
-        for (auto& x : v.seen) x = nullptr;
-    } else if (v.pending && s != v.stream) {
-        bool seen = false;
-        for (auto x : v.seen) seen = seen || x == s;
-        if (!seen) {
-            VR_HIP(c, hipStreamWaitEvent(s, v.built, 0));
-            v.seen[v.seen_next++ % kEditSeen] = s;
-        }
+        v.built.built(s);
+    } else {
+        VR_HIP(c, v.built.order_behind(s));
     }
     v.used = ++c->shadow_clock;
     c->shadow_cur = e;
@@ -1044,14 +1044,19 @@ int prepare_shadow(vr_ctx* c, hipStream_t s, MarchParams& P, const vr_ctx::Shado
 // The kernel form ("flavour") a launch runs: `fl` is the one asked for (vr_set_kernel_flavour, else VR_EXP_FLAVOUR), 0 = the default.
 int choose_flavour(vr_ctx* c, int fl, int variant, int n_frames, int rank, int world, bool packed, const Eligibility& E, bool surface)
 {
-    // the surface-position output of the unlit / lit shader: 26 without skipping, 25 with it (the isosurface's keeps 21 / 22)
-    if (surface && variant != VR_VARIANT_ISO) return fl == 1 ? 26 : 25;
-    // the projections: 1 asks for the form without skipping (20), everything else runs as the skipping one (19); nothing is measured
-    if (is_projection(variant)) return fl == 1 ? 20 : 19;
-    // the isosurface: the same rule, 22 without skipping, 21 with it
-    if (variant == VR_VARIANT_ISO) return fl == 1 ? 22 : 21;
-    // the shadowed lit shader: 24 without skipping, 23 with it
-    if (variant == VR_VARIANT_LIGHT && c->shadow_div != 0) return fl == 1 ? 24 : 23;
+    // The one-lane families come in pairs: 1 asks for the form without skipping (the odd flavour + 1), everything else runs as the
+    // skipping one; nothing is measured.  The first row that applies decides (the isosurface's surface output keeps 21 / 22).
+    const struct {
+        bool applies;
+        int skipping;
+    } pairs[] = {
+        {surface && variant != VR_VARIANT_ISO, 25},               // the surface-position output of the unlit / lit shader
+        {is_projection(variant), 19},                             // the projections
+        {variant == VR_VARIANT_ISO, 21},                          // the isosurface
+        {variant == VR_VARIANT_LIGHT && c->shadow_div != 0, 23},  // the shadowed lit shader
+    };
+    for (const auto& pr : pairs)
+        if (pr.applies) return fl == 1 ? pr.skipping + 1 : pr.skipping;
     const bool auto_choice = fl == 0;
     const double rays = rays_per_lane(c, rank, world, c->frames_in_flight * n_frames);
     const bool short_chains = E.chain_known != 0 && E.chain_known - 1 < 128;
@@ -1130,9 +1135,16 @@ struct KernelForm {
     LaunchDesc::Family family;
     int lanes;            // kDp: lanes per ray (vr_dp.h): 64 / 32 workgroups per tile
     bool pipe;            // kDp / kPw: the next round's / step's corner loads software-pipelined
-    bool p2_skip;         // kP2: the skipping form
+    bool skip;            // the skipping flavour of a pair (17 of 16 / 17; 19, 21, 23, 25 of the one-lane families): LaunchDesc::skip once
+                          // its records are in place
     bool lut;             // kPlain: the slot tables of volume 0 in LDS
     unsigned pw_threads;  // kPw / kP2: threads per workgroup
+    // what follows from the family
+    bool range_records() const { return family == LaunchDesc::kProj || family == LaunchDesc::kIso; }  // skips by prepare_proj's records
+    bool measured() const  // a candidate of the measured choice (the one-lane families never are)
+    {
+        return !(range_records() || family == LaunchDesc::kShadow || family == LaunchDesc::kSurf);
+    }
 };
 
 KernelForm kernel_form(int fl, int variant)
@@ -1157,13 +1169,13 @@ KernelForm kernel_form(int fl, int variant)
     case 17: return {D::kP2, 0, false, true, false, variant == VR_VARIANT_BASIC ? 1024u : 768u};
     case 18: return {D::kPlain, 0, false, false, true, 0u};
     case 19:
-    case 20: return {D::kProj, 0, false, false, false, 0u};
+    case 20: return {D::kProj, 0, false, fl == 19, false, 0u};
     case 21:
-    case 22: return {D::kIso, 0, false, false, false, 0u};
+    case 22: return {D::kIso, 0, false, fl == 21, false, 0u};
     case 23:
-    case 24: return {D::kShadow, 0, false, false, false, 0u};
+    case 24: return {D::kShadow, 0, false, fl == 23, false, 0u};
     case 25:
-    case 26: return {D::kSurf, 0, false, false, false, 0u};
+    case 26: return {D::kSurf, 0, false, fl == 25, false, 0u};
     default: return {D::kPlain, 0, false, false, false, 0u};  // 1, 6
     }
 }
@@ -1342,10 +1354,9 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
     const int fl = choose_flavour(c, requested, variant, n_frames, rank, world, packed, E, surface);
     c->last_flavour = fl;
     const KernelForm form = kernel_form(fl, variant);
-    c->last_proj = form.family == LaunchDesc::kProj || form.family == LaunchDesc::kIso || form.family == LaunchDesc::kShadow ||
-                   form.family == LaunchDesc::kSurf;
+    c->last_unmeasured = !form.measured();
     const float2* vrange = nullptr;
-    if (fl == 19 || fl == 21) {
+    if (form.skip && form.range_records()) {
         vrange = prepare_proj(c, s, P);
         if (!vrange) return VR_ERR_HIP;
     }
@@ -1372,14 +1383,13 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
     c->last_tiles = packed ? P.n_tiles : 0;
 
     if (frame_events) VR_HIP(c, hipEventRecord(c->tm.ev_begin, s));
-    // the shadowed form (23 with LIGHT's distance field in place, else 24's kernels)
-    const bool shadow_skip = form.family == LaunchDesc::kShadow && fl == 23 && P.brick_dist != nullptr;
-    // the surface form likewise (25 with the distance field in place, else 26's kernels)
-    const bool surf_skip = form.family == LaunchDesc::kSurf && fl == 25 && P.brick_dist != nullptr;
+    // the skipping form of a pair runs with its records in place -- the projections' range records, else the distance field -- and
+    // as the pair's other kernels without them
+    const bool skip = form.skip && (form.range_records() ? vrange != nullptr : P.brick_dist != nullptr);
     if (P.n_blocks > 0) {
         // the light volume it reads: built here when its key has none (inside vr_last_timing's total, outside its kernel time)
         if (shadowed)
-            if (const int rc = prepare_shadow(c, s, P, shadow_k, shadow_skip, off32)) return rc;
+            if (const int rc = prepare_shadow(c, s, P, shadow_k, skip, off32)) return rc;
         // the LOGICAL blocks (records, launch order): one wavefront per workgroup (launch order at wavefront granularity) -- except
         // for the depth-parallel kernels on large launches, where 4x the workgroups cost more at dispatch than the finer order gains
         // (C2: 32 768 workgroups of a 0.12 ms frame).  See map_pixel / map_pixel_dp.
@@ -1421,7 +1431,7 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
         L.grid = dim3(grid.x * (unsigned)n_frames);
         L.block = block;
         L.vrange = vrange;
-        L.proj_skip = vrange != nullptr || shadow_skip || surf_skip;
+        L.skip = skip;
         L.surface = surface;
         if (pw) {
             // persistent wavefronts: `grid` stays the number of LOGICAL blocks (records, launch order); the launch itself is one
@@ -1429,7 +1439,6 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
             const bool p2 = form.family == LaunchDesc::kP2;
             const unsigned per_wg = form.pw_threads / 64u, wgs = (grid.x * (unsigned)n_frames + per_wg - 1u) / per_wg;
             L.ltf = tf0_fits_lds(c);
-            L.p2_skip = form.p2_skip && P.brick_dist != nullptr;
             L.p2_win = p2 && (!off32 || c->p2_window != 0);
             L.lds_bytes = p2 ? E.p2_lds : (L.ltf ? (unsigned)(c->tf[0].res_o + 2) * 16u : 0u);
             L.queue = PwQueue{c->d_pw_heads + (size_t)cb * 8 * 64, grid.x, c->p2_window};
@@ -1809,10 +1818,10 @@ void vr_destroy(vr_ctx* c)
     if (c->merged_bricks) (void)hipFree(c->merged_bricks);
     if (c->proj_rec) (void)hipFree(c->proj_rec);
     if (c->proj_range) (void)hipFree(c->proj_range);
-    if (c->proj_ev) (void)hipEventDestroy(c->proj_ev);
+    if (c->proj_built.ev) (void)hipEventDestroy(c->proj_built.ev);
     for (auto& e : c->shadow) {
         if (e.buf.d) (void)hipFree(e.buf.d);
-        if (e.built) (void)hipEventDestroy(e.built);
+        if (e.built.ev) (void)hipEventDestroy(e.built.ev);
     }
     for (auto& g : c->field)
         if (g.d) (void)hipFree(g.d);
@@ -2598,7 +2607,7 @@ int vr_pick(vr_ctx* c, int variant, uint32_t x, uint32_t y, vr_pick_result* out)
     if (!c->d_pick_depth) VR_HIP(c, hipMalloc(&c->d_pick_depth, sizeof(float)));
     // ... and the launch's bookkeeping is put back behind the pick's own launch (which takes the next record slot, not the last one's)
     const int last_flavour = c->last_flavour, last_tiles = c->last_tiles, cnt_buf = c->cnt_buf, cnt_blocks = c->cnt_blocks;
-    const bool last_proj = c->last_proj, tm_valid = c->tm.valid;
+    const bool last_unmeasured = c->last_unmeasured, tm_valid = c->tm.valid;
     const size_t cnt_offset = c->cnt_offset;
     const long long ring_head = c->ring.head;
     const unsigned long long counters[3] = {c->h_counters[0], c->h_counters[1], c->h_counters[2]};
@@ -2614,7 +2623,7 @@ int vr_pick(vr_ctx* c, int variant, uint32_t x, uint32_t y, vr_pick_result* out)
     c->cnt_blocks = cnt_blocks;
     c->cnt_offset = cnt_offset;
     c->cnt_pending = false;
-    c->last_proj = last_proj;
+    c->last_unmeasured = last_unmeasured;
     c->tm.valid = tm_valid;
     c->ring.head = ring_head;
     for (int i = 0; i < 3; ++i) c->h_counters[i] = counters[i];
@@ -2673,7 +2682,7 @@ int vr_volume_layout(vr_ctx* c, int slot, int* flags)
 int vr_kernel_choice(vr_ctx* c, int flavours[6], float ms_per_launch[6], int* chosen)
 {
     if (!c) return VR_ERR_INVALID_ARG;
-    if (c->last_proj) {  // (the projections', the isosurface's and the shadowed forms are never measured)
+    if (c->last_unmeasured) {  // (the projections', the isosurface's, the shadowed and the surface forms)
         if (chosen) *chosen = -1;
         return 0;
     }

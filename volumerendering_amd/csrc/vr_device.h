@@ -156,6 +156,7 @@ struct LaunchDesc {
     int variant;      // vr_variant
     Family family;    // march_kernel, march_dp_kernel, march_pw_kernel (persistent wavefronts: grid = workgroups, the packets come
                       // from `queue`), march_p2_kernel (the same, corner loads two steps ahead), march_lt_kernel (LDS tiles, lit shader),
+                      // the one-lane marches on vr_ray.h's prologue and shell:
                       // march_proj_kernel (vr_proj.h: the intensity projections), march_iso_kernel (vr_iso.h: the isosurface),
                       // march_shadow_kernel (vr_shadow.h: the lit shader with shadows; MarchParams::vol[1] = the light volume),
                       // march_surf_kernel (vr_surf.h: the surface-position output of the unlit / lit shader; MarchParams::iso = the threshold)
@@ -163,15 +164,17 @@ struct LaunchDesc {
     int lanes;        // kDp: lanes per ray (2 / 4)
     bool pipe;        // kDp / kPw: the next round's / step's corner loads software-pipelined
     bool ltf;         // kPw: TF slot 0 in LDS (lds_bytes of dynamic LDS)
-    bool p2_skip;     // kP2: skipping by whole wavefronts (march_p2_kernel<V, true>)
     bool p2_win;      // kP2: a bound volume of 4 GiB or more: the gather window moves (march_p2_kernel<.., WIN>)
     unsigned lds_bytes;
     PwQueue queue;
     dim3 grid, block;
-    const float2* vrange;  // kProj: (min, max) of volume 0 (vr_proj.h); with `proj_skip` the brick records are MarchParams::bricks
-    bool proj_skip;        // kProj / kIso / kShadow / kSurf: the skipping form (march_proj_kernel<.., SKIP = true, ..>,
-                           // march_iso_kernel<.., true, ..>, march_shadow_kernel<.., true, ..>, march_surf_kernel<.., true, ..>)
-    bool surface;          // kIso: the refined point instead of the shaded fragment (iso_point_kernel, vr_surf.h)
+    bool skip;        // the skipping form of a flavour pair, asked for only with its records in place (KernelForm::skip, vr_api.hip).
+                      // kP2: skipping by whole wavefronts on the distance field (march_p2_kernel<V, true>); kProj / kIso: by volume
+                      // 0's range records in MarchParams::bricks (march_proj_kernel / march_iso_kernel / iso_point_kernel<.., SKIP = true,
+                      // ..>); kShadow / kSurf: by the distance field (march_shadow_kernel / march_surf_kernel<.., true, ..>).  The other
+                      // families read MarchParams::brick_dist alone.
+    const float2* vrange;  // kProj: (min, max) of volume 0 (vr_proj.h)
+    bool surface;          // kIso: the refined point instead of the shaded fragment (iso_point_kernel, vr_iso.h)
 };
 
 }  // namespace vr

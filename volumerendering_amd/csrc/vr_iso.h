@@ -25,147 +25,112 @@ template <bool OFF32, bool SKIP, bool SURF = false>
 __device__ __forceinline__ void iso_packet(const MarchParams& P, const PixelSlot& slot, float4& dst, unsigned& samples, unsigned& covered,
                                            unsigned& fetched)
 {
-    if (!(slot.active && slot.px >= P.rect[0] && slot.px <= P.rect[2] && slot.py >= P.rect[1] && slot.py <= P.rect[3])) return;
-    const Ray ray = setup_ray(P, slot.px, slot.py);
-    if (!ray.hit) return;
-    const f3 diff = mk3(ray.end.x - ray.start.x, ray.end.y - ray.start.y, ray.end.z - ray.start.z);
-    const f3 dir = normalize3s(diff);
-    const float ray_len = length3s(diff);
-    if (P.fragment_mode == 1) {
-        dst = make_float4(fabsf(dir.x), fabsf(dir.y), fabsf(dir.z), 1.0f);
-        return;
-    } else if (P.fragment_mode == 2) {
-        dst = make_float4(ray.start.x, ray.start.y, ray.start.z, 1.0f);
-        return;
-    } else if (P.fragment_mode == 3) {
-        dst = make_float4(ray.end.x, ray.end.y, ray.end.z, 1.0f);
-        return;
-    } else if (P.fragment_mode == 4) {
-        dst = make_float4(0.5f * (ray.world0.x / 1.0f) + 0.5f, -0.5f * (ray.world0.y / 1.0f) + 0.5f, 0.0f, 1.0f);
-        return;
-    }
-    float step_size = P.step_size;
-    // LIGHT's CalculateWorldStep, before the variable-step override
-    f3 wstep = mk3(dir.x * (step_size * 1.0f), dir.y * (step_size * 1.0f), dir.z * (step_size * 0.5f));
-    wstep.z = wstep.z * (-1.0f);
-    if (P.toggle_varstep == 1) step_size = ray_len / (float)P.steps_count;
-    f3 p = ray.start;
-    if (P.toggle_jitter == 1) {
-        const float j = jitter((float)slot.px + 0.5f, (float)slot.py + 0.5f);
-        p = mk3(p.x + (dir.x * step_size) * j, p.y + (dir.y * step_size) * j, p.z + (dir.z * step_size) * j);
-    }
-    const f3 step = mk3(dir.x * step_size, dir.y * step_size, dir.z * step_size);
-    f3 w = ray.world0;
-    const float iso = P.iso;
-    const float bx0 = P.bmin[0], by0 = P.bmin[1], bz0 = P.bmin[2];
-    const float bx1 = P.bmax[0], by1 = P.bmax[1], bz1 = P.bmax[2];
-    const int n_steps = P.steps_count;
-    const int n_inside = steps_inside(p, step, bx0, by0, bz0, bx1, by1, bz1);
-    auto in_box = [&](int i, f3 q) {
-        return i < n_inside || (q.x >= bx0 && q.x <= bx1 && q.y >= by0 && q.y <= by1 && q.z >= bz0 && q.z <= bz1);
-    };
-    unsigned n = 0;
-    // the step before the current one: its position, world position, density (when loaded) and whether it was in the box
-    f3 pp = p, wp = w;
-    float dprev = 0.0f;
-    bool prev_loaded = false, prev_inb = false;
-    bool hit = false;
-    float dk = 0.0f;
+    RayStart r;
+    with_ray(P, slot, dst, r, [&]() __attribute__((always_inline)) {
+        f3 p = r.p, w = r.world0;
+        const f3 step = r.step, wstep = world_step(P, r.dir);
+        const float iso = P.iso;
+        const int n_steps = P.steps_count;
+        const ClipBox box = clip_box(P);  // (read once, in front of the loop: vr_ray.h says why)
+        unsigned n = 0;
+        // the step before the current one: its position, world position, density (when loaded) and whether it was in the box
+        f3 pp = p, wp = w;
+        float dprev = 0.0f;
+        bool prev_loaded = false, prev_inb = false;
+        bool hit = false;
+        float dk = 0.0f;
 
-    // step i: corners of p in F (requested one iteration ago) when `have`; R = record of p + step (requested one iteration ago)
-    Fetch1 F;
-    float fx = 0.0f, fy = 0.0f, fz = 0.0f;
-    bool have = false;
-    float2 R = make_float2(0.0f, 0.0f);
-    if (n_steps > 0 && in_box(0, p)) {
-        have = !SKIP || !(proj_record(P, p).y < iso);
-        if (have) fetch_a<OFF32>(P.vol[0], p, F, fx, fy, fz);
-    }
-    if constexpr (SKIP) R = proj_record(P, mk3(p.x + step.x, p.y + step.y, p.z + step.z));
-    for (int i = 0; i < n_steps; ++i) {
-        const bool inb = in_box(i, p);
-        if (!inb) {
-            // p moves monotonically per component: once past the far bound it never returns
-            const bool gone = (step.x >= 0.0f && p.x > bx1) || (step.x <= 0.0f && p.x < bx0) || (step.y >= 0.0f && p.y > by1) ||
-                              (step.y <= 0.0f && p.y < by0) || (step.z >= 0.0f && p.z > bz1) || (step.z <= 0.0f && p.z < bz0);
-            if (gone) break;
+        // step i: corners of p in F (requested one iteration ago) when `have`; R = record of p + step (requested one iteration ago)
+        Fetch1 F;
+        float fx = 0.0f, fy = 0.0f, fz = 0.0f;
+        bool have = false;
+        float2 R = make_float2(0.0f, 0.0f);
+        if (n_steps > 0 && in_box(box, r, 0, p)) {
+            have = !SKIP || !(proj_record(P, p).y < iso);
+            if (have) fetch_a<OFF32>(P.vol[0], p, F, fx, fy, fz);
         }
-        const f3 pn = mk3(p.x + step.x, p.y + step.y, p.z + step.z);
-        // the next step: loaded unless it is outside the box or its brick lies below the level
-        bool next = i + 1 < n_steps && in_box(i + 1, pn);
-        if constexpr (SKIP) {
-            next = next && !(R.y < iso);
-            R = proj_record(P, mk3(pn.x + step.x, pn.y + step.y, pn.z + step.z));  // (issued before the corners below)
-        }
-        Fetch1 G;
-        float gx = 0.0f, gy = 0.0f, gz = 0.0f;
-        __builtin_amdgcn_sched_barrier(0);
-        if (next) fetch_a<OFF32>(P.vol[0], pn, G, gx, gy, gz);
-        __builtin_amdgcn_sched_barrier(0);
-        bool loaded = false;
-        float d = 0.0f;
-        if (inb) {
-            ++n;
-            if (have) {
-                d = interp_a(F, fx, fy, fz);
-                loaded = true;
-                ++fetched;
-                if (d >= iso) {  // (NaN never hits)
-                    hit = true;
-                    dk = d;
-                    break;
+        if constexpr (SKIP) R = proj_record(P, mk3(p.x + step.x, p.y + step.y, p.z + step.z));
+        for (int i = 0; i < n_steps; ++i) {
+            const bool inb = in_box(box, r, i, p);
+            if (!inb && gone(box, step, p)) break;
+            const f3 pn = mk3(p.x + step.x, p.y + step.y, p.z + step.z);
+            // the next step: loaded unless it is outside the box or its brick lies below the level
+            bool next = i + 1 < n_steps && in_box(box, r, i + 1, pn);
+            if constexpr (SKIP) {
+                next = next && !(R.y < iso);
+                R = proj_record(P, mk3(pn.x + step.x, pn.y + step.y, pn.z + step.z));  // (issued before the corners below)
+            }
+            Fetch1 G;
+            float gx = 0.0f, gy = 0.0f, gz = 0.0f;
+            __builtin_amdgcn_sched_barrier(0);
+            if (next) fetch_a<OFF32>(P.vol[0], pn, G, gx, gy, gz);
+            __builtin_amdgcn_sched_barrier(0);
+            bool loaded = false;
+            float d = 0.0f;
+            if (inb) {
+                ++n;
+                if (have) {
+                    d = interp_a(F, fx, fy, fz);
+                    loaded = true;
+                    ++fetched;
+                    if (d >= iso) {  // (NaN never hits)
+                        hit = true;
+                        dk = d;
+                        break;
+                    }
                 }
             }
+            pp = p;
+            wp = w;
+            dprev = d;
+            prev_loaded = loaded;
+            prev_inb = inb;
+            F = G;
+            fx = gx;
+            fy = gy;
+            fz = gz;
+            have = next;
+            p = pn;
+            w = mk3(w.x + wstep.x, w.y + wstep.y, w.z + wstep.z);
         }
-        pp = p;
-        wp = w;
-        dprev = d;
-        prev_loaded = loaded;
-        prev_inb = inb;
-        F = G;
-        fx = gx;
-        fy = gy;
-        fz = gz;
-        have = next;
-        p = pn;
-        w = mk3(w.x + wstep.x, w.y + wstep.y, w.z + wstep.z);
-    }
-    samples = n;
-    if (!hit) return;
-    covered = 1;
-    // the surface point: p_k, or the secant step from the previous in-box step
-    f3 q = p, wq = w;
-    if (prev_inb) {
-        const float d0 = prev_loaded ? dprev : tex3_a<OFF32>(P.vol[0], pp);
-        const float t = (iso - d0) / (dk - d0);
-        if (t >= 0.0f && t <= 1.0f) {
-            q = mk3(mad(step.x, t, pp.x), mad(step.y, t, pp.y), mad(step.z, t, pp.z));
-            wq = mk3(mad(wstep.x, t, wp.x), mad(wstep.y, t, wp.y), mad(wstep.z, t, wp.z));
+        samples = n;
+        if (!hit) return;
+        covered = 1;
+        // the surface point: p_k, or the secant step from the previous in-box step
+        f3 q = p, wq = w;
+        if (prev_inb) {
+            const float d0 = prev_loaded ? dprev : tex3_a<OFF32>(P.vol[0], pp);
+            const float t = (iso - d0) / (dk - d0);
+            if (t >= 0.0f && t <= 1.0f) {
+                q = mk3(mad(step.x, t, pp.x), mad(step.y, t, pp.y), mad(step.z, t, pp.z));
+                wq = mk3(mad(wstep.x, t, wp.x), mad(wstep.y, t, wp.y), mad(wstep.z, t, wp.z));
+            }
         }
-    }
-    if constexpr (SURF) {
-        dst = make_float4(q.x, q.y, q.z, 1.0f);
-        return;
-    }
-    const float4 s = tex3_rgba<OFF32>(P.vol[0], q);
-    const f3 N = normalize3(mk3(s.x, s.y, s.z));  // (zero gradient: NaN -> max(NaN, 0) = 0, ambient only, as LIGHT)
-    const f3 sh = shade(N, wq, mk3(P.light_pos[0], P.light_pos[1], P.light_pos[2]), mk3(P.light_dif[0], P.light_dif[1], P.light_dif[2]),
-                        mk3(P.light_amb[0], P.light_amb[1], P.light_amb[2]), 2.5f, 0.5f);
-    const TfSample c = tf_lookup(P.tf[0], iso);
-    blend(mk3(c.rgb.x * sh.x, c.rgb.y * sh.y, c.rgb.z * sh.z), 1.0f, dst);
+        if constexpr (SURF) {
+            dst = make_float4(q.x, q.y, q.z, 1.0f);
+            return;
+        }
+        const float4 s = tex3_rgba<OFF32>(P.vol[0], q);
+        const f3 N = normalize3(mk3(s.x, s.y, s.z));  // (zero gradient: NaN -> max(NaN, 0) = 0, ambient only, as LIGHT)
+        const f3 sh = shade(N, wq, mk3(P.light_pos[0], P.light_pos[1], P.light_pos[2]), mk3(P.light_dif[0], P.light_dif[1], P.light_dif[2]),
+                            mk3(P.light_amb[0], P.light_amb[1], P.light_amb[2]), 2.5f, 0.5f);
+        const TfSample c = tf_lookup(P.tf[0], iso);
+        blend(mk3(c.rgb.x * sh.x, c.rgb.y * sh.y, c.rgb.z * sh.z), 1.0f, dst);
+    });
 }
 
 template <bool OFF32, bool SKIP, bool BATCH = false>
 __global__ __launch_bounds__(64) void march_iso_kernel(const MarchBatch B)
 {
-    const MarchParams& P = frame_params<BATCH>(B);
-    const unsigned long long t_start = wall_clock64();
-    const PixelSlot slot = map_pixel(P);
-    float4 dst = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    unsigned samples = 0, covered = 0, fetched = 0;
-    iso_packet<OFF32, SKIP>(P, slot, dst, samples, covered, fetched);
-    if (slot.active || (P.packed && slot.in_launch)) P.out[slot.out_index] = dst;
-    store_block_counts(P, samples, covered, fetched, t_start);
+    march_shell<BATCH>(B, [](auto&... a) { iso_packet<OFF32, SKIP>(a...); });
+}
+
+// The picking read-back: march_iso_kernel's march with the refined point stored in place of the shading tail
+// (iso_packet<.., SURF = true>).  A kernel name of its own: march_iso_kernel keeps exactly the instances it had.
+template <bool OFF32, bool SKIP, bool BATCH = false>
+__global__ __launch_bounds__(64) void iso_point_kernel(const MarchBatch B)
+{
+    march_shell<BATCH>(B, [](auto&... a) { iso_packet<OFF32, SKIP, true>(a...); });
 }
 
 }  // namespace VR_KNS

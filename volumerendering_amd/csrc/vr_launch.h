@@ -18,13 +18,15 @@
 // is part of the shipped library: slower than the two-steps-ahead kernel everywhere measured, selectable with
 // vr_set_kernel_flavour(15) and tested on every box, not a candidate of the measured choice.
 #include "vr_lt.h"
+// The ray prologue, the in-box tests and the kernel shell of the four one-lane families below
+#include "vr_ray.h"
 // Intensity projections (MIP / MinIP / AIP of volume slot 0; flavours 19 and 20)
 #include "vr_proj.h"
-// The shaded isosurface of volume slot 0 (flavours 21 and 22; it reads the projections' brick records)
+// The shaded isosurface of volume slot 0 (flavours 21 and 22; it reads the projections' brick records) and its refined points
 #include "vr_iso.h"
 // Shadows of the lit shader through a light volume (flavours 23 and 24; the build and the shadowed march)
 #include "vr_shadow.h"
-// The surface-position output of the unlit / lit shader (flavours 25 and 26) and of the isosurface; the depth of a surface frame
+// The surface-position output of the unlit / lit shader (flavours 25 and 26); the depth of a surface frame
 #include "vr_surf.h"
 
 #include <type_traits>
@@ -98,50 +100,23 @@ void launch_p2(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
 {
     with_flags([&](auto S, auto WN, auto BT) {
         if constexpr (S || V != V_VOLUME_MASK) launch_queued<march_p2_kernel<V, S, WN, BT>>(L, s, B);
-    }, V == V_VOLUME_MASK || (B.frame[0].brick_dist && L.p2_skip), L.p2_win, B.n_frames > 1);
+    }, V == V_VOLUME_MASK || (B.frame[0].brick_dist && L.skip), L.p2_win, B.n_frames > 1);
 }
 
-// the projections: mode x skipping x addressing x frames per launch
+// The one-lane kernels of vr_proj.h, vr_iso.h, vr_shadow.h and vr_surf.h: skipping x addressing x frames per launch.
+// kernel(S, O, BT) returns the instantiation; args follow the batch.
+template <class K, class... A>
+void launch_one_lane(const LaunchDesc& L, hipStream_t s, const MarchBatch& B, K kernel, A... args)
+{
+    with_flags([&](auto S, auto O, auto BT) { hipLaunchKernelGGL(kernel(S, O, BT), L.grid, L.block, 0, s, B, args...); }, L.skip, L.off32,
+               B.n_frames > 1);
+}
+
+// the projections: one mode each
+template <int M>
 void launch_proj(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
 {
-    const int mode = L.variant == VR_VARIANT_MIP ? kProjMax : (L.variant == VR_VARIANT_MINIP ? kProjMin : kProjAvg);
-    auto launch = [&](auto md) {
-        constexpr int M = decltype(md)::value;
-        with_flags([&](auto S, auto O, auto BT) {
-            hipLaunchKernelGGL((march_proj_kernel<M, O, S, BT>), L.grid, L.block, 0, s, B, L.vrange);
-        }, L.proj_skip, L.off32, B.n_frames > 1);
-    };
-    if (mode == kProjMax) launch(std::integral_constant<int, kProjMax>{});
-    else if (mode == kProjMin) launch(std::integral_constant<int, kProjMin>{});
-    else launch(std::integral_constant<int, kProjAvg>{});
-}
-
-// the isosurface: skipping x addressing x frames per launch
-void launch_iso(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
-{
-    with_flags([&](auto S, auto O, auto BT) { hipLaunchKernelGGL((march_iso_kernel<O, S, BT>), L.grid, L.block, 0, s, B); },
-               L.proj_skip, L.off32, B.n_frames > 1);
-}
-
-// the isosurface's refined points (surface output): the same
-void launch_iso_point(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
-{
-    with_flags([&](auto S, auto O, auto BT) { hipLaunchKernelGGL((iso_point_kernel<O, S, BT>), L.grid, L.block, 0, s, B); },
-               L.proj_skip, L.off32, B.n_frames > 1);
-}
-
-// the surface-position output of the unlit / lit shader: skipping x addressing x frames per launch
-void launch_surf(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
-{
-    with_flags([&](auto S, auto O, auto BT) { hipLaunchKernelGGL((march_surf_kernel<O, S, BT>), L.grid, L.block, 0, s, B); },
-               L.proj_skip, L.off32, B.n_frames > 1);
-}
-
-// the shadowed lit shader: skipping x addressing x frames per launch
-void launch_shadow(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
-{
-    with_flags([&](auto S, auto O, auto BT) { hipLaunchKernelGGL((march_shadow_kernel<O, S, BT>), L.grid, L.block, 0, s, B); },
-               L.proj_skip, L.off32, B.n_frames > 1);
+    launch_one_lane(L, s, B, [](auto S, auto O, auto BT) { return march_proj_kernel<M, O, S, BT>; }, L.vrange);
 }
 
 // the light volume of a shadowed launch (P: its parameters, vol[1] = the grid, whose storage is `out`); skip: by LIGHT's distance field
@@ -154,27 +129,23 @@ void launch_shadow_build(const MarchParams& P, float* out, float sigma, bool ski
 
 void launch_march(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
 {
-    if (L.family == LaunchDesc::kShadow) {
-        launch_shadow(L, s, B);
+    switch (L.family) {
+    case LaunchDesc::kShadow: launch_one_lane(L, s, B, [](auto S, auto O, auto BT) { return march_shadow_kernel<O, S, BT>; }); return;
+    case LaunchDesc::kSurf: launch_one_lane(L, s, B, [](auto S, auto O, auto BT) { return march_surf_kernel<O, S, BT>; }); return;
+    case LaunchDesc::kIso:  // (surface output: the refined points)
+        if (L.surface) launch_one_lane(L, s, B, [](auto S, auto O, auto BT) { return iso_point_kernel<O, S, BT>; });
+        else launch_one_lane(L, s, B, [](auto S, auto O, auto BT) { return march_iso_kernel<O, S, BT>; });
         return;
-    }
-    if (L.family == LaunchDesc::kSurf) {
-        launch_surf(L, s, B);
+    case LaunchDesc::kProj:
+        if (L.variant == VR_VARIANT_MIP) launch_proj<kProjMax>(L, s, B);
+        else if (L.variant == VR_VARIANT_MINIP) launch_proj<kProjMin>(L, s, B);
+        else launch_proj<kProjAvg>(L, s, B);
         return;
-    }
-    if (L.family == LaunchDesc::kIso) {
-        if (L.surface) launch_iso_point(L, s, B);
-        else launch_iso(L, s, B);
-        return;
-    }
-    if (L.family == LaunchDesc::kProj) {
-        launch_proj(L, s, B);
-        return;
-    }
-    if (L.family == LaunchDesc::kLt) {  // LDS tiles (vr_lt.h): lit shader
+    case LaunchDesc::kLt:  // LDS tiles (vr_lt.h): lit shader
         with_flags([&](auto O, auto S) { hipLaunchKernelGGL((march_lt_kernel<O, S>), L.grid, L.block, 0, s, B); },
                    L.off32, B.frame[0].brick_dist != nullptr);
         return;
+    default: break;  // the families that exist per shader variant
     }
     auto launch = [&](auto v) {
         constexpr int V = decltype(v)::value;

@@ -59,113 +59,73 @@ template <int MODE, bool OFF32, bool SKIP>
 __device__ __forceinline__ void proj_packet(const MarchParams& P, const float2* __restrict__ vrange, const PixelSlot& slot, float4& dst,
                                             unsigned& samples, unsigned& covered, unsigned& fetched)
 {
-    if (!(slot.active && slot.px >= P.rect[0] && slot.px <= P.rect[2] && slot.py >= P.rect[1] && slot.py <= P.rect[3])) return;
-    const Ray ray = setup_ray(P, slot.px, slot.py);
-    if (!ray.hit) return;
-    const f3 diff = mk3(ray.end.x - ray.start.x, ray.end.y - ray.start.y, ray.end.z - ray.start.z);
-    const f3 dir = normalize3s(diff);
-    const float ray_len = length3s(diff);
-    if (P.fragment_mode == 1) {
-        dst = make_float4(fabsf(dir.x), fabsf(dir.y), fabsf(dir.z), 1.0f);
-        return;
-    } else if (P.fragment_mode == 2) {
-        dst = make_float4(ray.start.x, ray.start.y, ray.start.z, 1.0f);
-        return;
-    } else if (P.fragment_mode == 3) {
-        dst = make_float4(ray.end.x, ray.end.y, ray.end.z, 1.0f);
-        return;
-    } else if (P.fragment_mode == 4) {
-        dst = make_float4(0.5f * (ray.world0.x / 1.0f) + 0.5f, -0.5f * (ray.world0.y / 1.0f) + 0.5f, 0.0f, 1.0f);
-        return;
-    }
-    float step_size = P.step_size;
-    if (P.toggle_varstep == 1) step_size = ray_len / (float)P.steps_count;
-    f3 p = ray.start;
-    if (P.toggle_jitter == 1) {
-        const float j = jitter((float)slot.px + 0.5f, (float)slot.py + 0.5f);
-        p = mk3(p.x + (dir.x * step_size) * j, p.y + (dir.y * step_size) * j, p.z + (dir.z * step_size) * j);
-    }
-    const f3 step = mk3(dir.x * step_size, dir.y * step_size, dir.z * step_size);
-    const float bx0 = P.bmin[0], by0 = P.bmin[1], bz0 = P.bmin[2];
-    const float bx1 = P.bmax[0], by1 = P.bmax[1], bz1 = P.bmax[2];
-    const int n_steps = P.steps_count;
-    const int n_inside = steps_inside(p, step, bx0, by0, bz0, bx1, by1, bz1);
-    auto in_box = [&](int i, f3 q) {
-        return i < n_inside || (q.x >= bx0 && q.x <= bx1 && q.y >= by0 && q.y <= by1 && q.z >= bz0 && q.z <= bz1);
-    };
-    float m = MODE == kProjMax ? -INFINITY : (MODE == kProjMin ? INFINITY : 0.0f);
-    float lim = 0.0f;  // early exit: MIP m >= lim, MinIP m <= lim (NaN: never)
-    if constexpr (SKIP && MODE != kProjAvg) lim = MODE == kProjMax ? vrange->y : vrange->x;
-    bool done = false;
-    unsigned n = 0;
+    RayStart r;
+    with_ray(P, slot, dst, r, [&]() __attribute__((always_inline)) {
+        f3 p = r.p;
+        const f3 step = r.step;
+        const int n_steps = P.steps_count;
+        float m = MODE == kProjMax ? -INFINITY : (MODE == kProjMin ? INFINITY : 0.0f);
+        float lim = 0.0f;  // early exit: MIP m >= lim, MinIP m <= lim (NaN: never)
+        if constexpr (SKIP && MODE != kProjAvg) lim = MODE == kProjMax ? vrange->y : vrange->x;
+        bool done = false;
+        unsigned n = 0;
 
-    // step i: corners of p in F (requested one iteration ago) when `have`; R = record of p + step (requested one iteration ago)
-    Fetch1 F;
-    float fx = 0.0f, fy = 0.0f, fz = 0.0f;
-    bool have = false;
-    float2 R = make_float2(0.0f, 0.0f);
-    if (n_steps > 0 && in_box(0, p)) {
-        have = !SKIP || !proj_inert<MODE>(proj_record(P, p), m);
-        if (have) fetch_a<OFF32>(P.vol[0], p, F, fx, fy, fz);
-    }
-    if constexpr (SKIP) R = proj_record(P, mk3(p.x + step.x, p.y + step.y, p.z + step.z));
-    for (int i = 0; i < n_steps; ++i) {
-        const bool inb = in_box(i, p);
-        if (!inb) {
-            // p moves monotonically per component: once past the far bound it never returns
-            const bool gone = (step.x >= 0.0f && p.x > bx1) || (step.x <= 0.0f && p.x < bx0) || (step.y >= 0.0f && p.y > by1) ||
-                              (step.y <= 0.0f && p.y < by0) || (step.z >= 0.0f && p.z > bz1) || (step.z <= 0.0f && p.z < bz0);
-            if (gone) break;
+        // step i: corners of p in F (requested one iteration ago) when `have`; R = record of p + step (requested one iteration ago)
+        Fetch1 F;
+        float fx = 0.0f, fy = 0.0f, fz = 0.0f;
+        bool have = false;
+        float2 R = make_float2(0.0f, 0.0f);
+        if (n_steps > 0 && in_box(P, r, 0, p)) {
+            have = !SKIP || !proj_inert<MODE>(proj_record(P, p), m);
+            if (have) fetch_a<OFF32>(P.vol[0], p, F, fx, fy, fz);
         }
-        const f3 pn = mk3(p.x + step.x, p.y + step.y, p.z + step.z);
-        // the next step: loaded unless it is outside the box or its brick cannot change m as m stands now (m only ever moves
-        // towards the side that makes more bricks inert, so the test stays true when it is applied one step early)
-        bool next = i + 1 < n_steps && !done && in_box(i + 1, pn);
-        if constexpr (SKIP) {
-            next = next && !proj_inert<MODE>(R, m);
-            R = proj_record(P, mk3(pn.x + step.x, pn.y + step.y, pn.z + step.z));  // (issued before the corners below)
-        }
-        Fetch1 G;
-        float gx = 0.0f, gy = 0.0f, gz = 0.0f;
-        __builtin_amdgcn_sched_barrier(0);
-        if (next) fetch_a<OFF32>(P.vol[0], pn, G, gx, gy, gz);
-        __builtin_amdgcn_sched_barrier(0);
-        if (inb) {
-            ++n;
-            if (have) {
-                proj_update<MODE>(m, interp_a(F, fx, fy, fz));
-                ++fetched;
-                if constexpr (SKIP && MODE == kProjMax) done = m >= lim;
-                if constexpr (SKIP && MODE == kProjMin) done = m <= lim;
+        if constexpr (SKIP) R = proj_record(P, mk3(p.x + step.x, p.y + step.y, p.z + step.z));
+        for (int i = 0; i < n_steps; ++i) {
+            const bool inb = in_box(P, r, i, p);
+            if (!inb && gone(P, step, p)) break;
+            const f3 pn = mk3(p.x + step.x, p.y + step.y, p.z + step.z);
+            // the next step: loaded unless it is outside the box or its brick cannot change m as m stands now (m only ever moves
+            // towards the side that makes more bricks inert, so the test stays true when it is applied one step early)
+            bool next = i + 1 < n_steps && !done && in_box(P, r, i + 1, pn);
+            if constexpr (SKIP) {
+                next = next && !proj_inert<MODE>(R, m);
+                R = proj_record(P, mk3(pn.x + step.x, pn.y + step.y, pn.z + step.z));  // (issued before the corners below)
             }
+            Fetch1 G;
+            float gx = 0.0f, gy = 0.0f, gz = 0.0f;
+            __builtin_amdgcn_sched_barrier(0);
+            if (next) fetch_a<OFF32>(P.vol[0], pn, G, gx, gy, gz);
+            __builtin_amdgcn_sched_barrier(0);
+            if (inb) {
+                ++n;
+                if (have) {
+                    proj_update<MODE>(m, interp_a(F, fx, fy, fz));
+                    ++fetched;
+                    if constexpr (SKIP && MODE == kProjMax) done = m >= lim;
+                    if constexpr (SKIP && MODE == kProjMin) done = m <= lim;
+                }
+            }
+            F = G;
+            fx = gx;
+            fy = gy;
+            fz = gz;
+            have = next;
+            p = pn;
         }
-        F = G;
-        fx = gx;
-        fy = gy;
-        fz = gz;
-        have = next;
-        p = pn;
-    }
-    samples = n;
-    if (n == 0) return;
-    covered = 1;
-    float v = m;
-    if constexpr (MODE == kProjAvg) v = m / (float)n;
-    const TfSample t = tf_lookup(P.tf[0], v);
-    blend(t.rgb, t.opacity, dst);
+        samples = n;
+        if (n == 0) return;
+        covered = 1;
+        float v = m;
+        if constexpr (MODE == kProjAvg) v = m / (float)n;
+        const TfSample t = tf_lookup(P.tf[0], v);
+        blend(t.rgb, t.opacity, dst);
+    });
 }
 
 template <int MODE, bool OFF32, bool SKIP, bool BATCH = false>
 __global__ __launch_bounds__(64) void march_proj_kernel(const MarchBatch B, const float2* __restrict__ vrange)
 {
-    const MarchParams& P = frame_params<BATCH>(B);
-    const unsigned long long t_start = wall_clock64();
-    const PixelSlot slot = map_pixel(P);
-    float4 dst = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    unsigned samples = 0, covered = 0, fetched = 0;
-    proj_packet<MODE, OFF32, SKIP>(P, vrange, slot, dst, samples, covered, fetched);
-    if (slot.active || (P.packed && slot.in_launch)) P.out[slot.out_index] = dst;
-    store_block_counts(P, samples, covered, fetched, t_start);
+    march_shell<BATCH>(B, [&](const MarchParams& P, auto&... a) { proj_packet<MODE, OFF32, SKIP>(P, vrange, a...); });
 }
 
 #if !VR_FUSED  // auxiliary kernels: compiled once, in namespace vr

@@ -79,132 +79,88 @@ template <bool OFF32, bool SKIP>
 __device__ __forceinline__ void shadow_packet(const MarchParams& P, const PixelSlot& slot, float4& dst, unsigned& blends, unsigned& covered,
                                               unsigned& fetched)
 {
-    if (!(slot.active && slot.px >= P.rect[0] && slot.px <= P.rect[2] && slot.py >= P.rect[1] && slot.py <= P.rect[3])) return;
-    const Ray ray = setup_ray(P, slot.px, slot.py);
-    if (!ray.hit) return;
-    covered = 1;
-    const f3 diff = mk3(ray.end.x - ray.start.x, ray.end.y - ray.start.y, ray.end.z - ray.start.z);
-    const f3 dir = normalize3s(diff);
-    const float ray_len = length3s(diff);
-    if (P.fragment_mode == 1) {
-        dst = make_float4(fabsf(dir.x), fabsf(dir.y), fabsf(dir.z), 1.0f);
-        return;
-    } else if (P.fragment_mode == 2) {
-        dst = make_float4(ray.start.x, ray.start.y, ray.start.z, 1.0f);
-        return;
-    } else if (P.fragment_mode == 3) {
-        dst = make_float4(ray.end.x, ray.end.y, ray.end.z, 1.0f);
-        return;
-    } else if (P.fragment_mode == 4) {
-        dst = make_float4(0.5f * (ray.world0.x / 1.0f) + 0.5f, -0.5f * (ray.world0.y / 1.0f) + 0.5f, 0.0f, 1.0f);
-        return;
-    }
-    float step_size = P.step_size;
-    // CalculateWorldStep, before the variable-step override
-    f3 wstep = mk3(dir.x * (step_size * 1.0f), dir.y * (step_size * 1.0f), dir.z * (step_size * 0.5f));
-    wstep.z = wstep.z * (-1.0f);
-    if (P.toggle_varstep == 1) step_size = ray_len / (float)P.steps_count;
-    f3 p = ray.start;
-    if (P.toggle_jitter == 1) {
-        const float j = jitter((float)slot.px + 0.5f, (float)slot.py + 0.5f);
-        p = mk3(p.x + (dir.x * step_size) * j, p.y + (dir.y * step_size) * j, p.z + (dir.z * step_size) * j);
-    }
-    const f3 step = mk3(dir.x * step_size, dir.y * step_size, dir.z * step_size);
-    f3 w = ray.world0;
-    const float bx0 = P.bmin[0], by0 = P.bmin[1], bz0 = P.bmin[2];
-    const float bx1 = P.bmax[0], by1 = P.bmax[1], bz1 = P.bmax[2];
-    const int n_steps = P.steps_count;
-    const int n_inside = steps_inside(p, step, bx0, by0, bz0, bx1, by1, bz1);
-    auto in_box = [&](int i, f3 q) {
-        return i < n_inside || (q.x >= bx0 && q.x <= bx1 && q.y >= by0 && q.y <= by1 && q.z >= bz0 && q.z <= bz1);
-    };
-    const f3 lpos = mk3(P.light_pos[0], P.light_pos[1], P.light_pos[2]);
-    const f3 dif = mk3(P.light_dif[0], P.light_dif[1], P.light_dif[2]);
-    const f3 amb = mk3(P.light_amb[0], P.light_amb[1], P.light_amb[2]);
-    unsigned n = 0;
+    RayStart r;
+    // (covered: every pixel whose ray hits the box, as LIGHT's march_packet)
+    covered = with_ray(P, slot, dst, r, [&]() __attribute__((always_inline)) {
+        f3 p = r.p, w = r.world0;
+        const f3 step = r.step, wstep = world_step(P, r.dir);
+        const int n_steps = P.steps_count;
+        const f3 lpos = mk3(P.light_pos[0], P.light_pos[1], P.light_pos[2]);
+        const f3 dif = mk3(P.light_dif[0], P.light_dif[1], P.light_dif[2]);
+        const f3 amb = mk3(P.light_amb[0], P.light_amb[1], P.light_amb[2]);
+        unsigned n = 0;
 
-    // step i: corners of p in F (requested one iteration ago) when `have`; R = distance-field byte of p + step (requested one
-    // iteration ago)
-    Fetch4 F;
-    float fx = 0.0f, fy = 0.0f, fz = 0.0f;
-    bool have = false;
-    unsigned R = 0;
-    if (n_steps > 0 && in_box(0, p)) {
-        have = !SKIP || dist_at(P, brick_of<OFF32>(P, p)) == 0u;
-        if (have) fetch_rgba<OFF32>(P.vol[0], p, F, fx, fy, fz);
-    }
-    if constexpr (SKIP) R = dist_at(P, brick_of<OFF32>(P, mk3(p.x + step.x, p.y + step.y, p.z + step.z)));
-    for (int i = 0; i < n_steps; ++i) {
-        const bool inb = in_box(i, p);
-        if (!inb) {
-            // p moves monotonically per component: once past the far bound it never returns
-            const bool gone = (step.x >= 0.0f && p.x > bx1) || (step.x <= 0.0f && p.x < bx0) || (step.y >= 0.0f && p.y > by1) ||
-                              (step.y <= 0.0f && p.y < by0) || (step.z >= 0.0f && p.z > bz1) || (step.z <= 0.0f && p.z < bz0);
-            if (gone) break;
+        // step i: corners of p in F (requested one iteration ago) when `have`; R = distance-field byte of p + step (requested one
+        // iteration ago)
+        Fetch4 F;
+        float fx = 0.0f, fy = 0.0f, fz = 0.0f;
+        bool have = false;
+        unsigned R = 0;
+        if (n_steps > 0 && in_box(P, r, 0, p)) {
+            have = !SKIP || dist_at(P, brick_of<OFF32>(P, p)) == 0u;
+            if (have) fetch_rgba<OFF32>(P.vol[0], p, F, fx, fy, fz);
         }
-        const f3 pn = mk3(p.x + step.x, p.y + step.y, p.z + step.z);
-        // the next step: loaded unless it is outside the box or in an inert brick
-        bool next = i + 1 < n_steps && in_box(i + 1, pn);
-        if constexpr (SKIP) {
-            next = next && R == 0u;
-            R = dist_at(P, brick_of<OFF32>(P, mk3(pn.x + step.x, pn.y + step.y, pn.z + step.z)));  // (issued before the corners below)
-        }
-        // this step's sample: its table texels and its light-volume corners are requested before the next step's corners, so that
-        // waiting for them leaves those eight loads in flight
-        const bool sample = inb && have;
-        bool shaded = false;
-        v2f zw = v2f{0.0f, 0.0f}, gxy = zw;
-        TfFetch tq = {};
-        Fetch1 Sq = {};
-        float sx = 0.0f, sy = 0.0f, sz = 0.0f;
-        if (sample) {
-            zw = interp_zw(F, fx, fy, fz);  // (gradient z, density)
-            shaded = !SKIP || !opacity_is_zero(P, zw.y);
-            if (shaded) {
-                tq = tf_fetch(P.tf[0], zw.y);
-                gxy = interp_xy(F, fx, fy, fz);
-                fetch_a<OFF32>(P.vol[1], p, Sq, sx, sy, sz);
+        if constexpr (SKIP) R = dist_at(P, brick_of<OFF32>(P, mk3(p.x + step.x, p.y + step.y, p.z + step.z)));
+        for (int i = 0; i < n_steps; ++i) {
+            const bool inb = in_box(P, r, i, p);
+            if (!inb && gone(P, step, p)) break;
+            const f3 pn = mk3(p.x + step.x, p.y + step.y, p.z + step.z);
+            // the next step: loaded unless it is outside the box or in an inert brick
+            bool next = i + 1 < n_steps && in_box(P, r, i + 1, pn);
+            if constexpr (SKIP) {
+                next = next && R == 0u;
+                R = dist_at(P, brick_of<OFF32>(P, mk3(pn.x + step.x, pn.y + step.y, pn.z + step.z)));  // (issued before the corners below)
             }
-        }
-        Fetch4 G;
-        float gx = 0.0f, gy = 0.0f, gz = 0.0f;
-        __builtin_amdgcn_sched_barrier(0);
-        if (next) fetch_rgba<OFF32>(P.vol[0], pn, G, gx, gy, gz);
-        __builtin_amdgcn_sched_barrier(0);
-        if (inb) {
-            ++n;
+            // this step's sample: its table texels and its light-volume corners are requested before the next step's corners, so that
+            // waiting for them leaves those eight loads in flight
+            const bool sample = inb && have;
+            bool shaded = false;
+            v2f zw = v2f{0.0f, 0.0f}, gxy = zw;
+            TfFetch tq = {};
+            Fetch1 Sq = {};
+            float sx = 0.0f, sy = 0.0f, sz = 0.0f;
             if (sample) {
-                ++fetched;
+                zw = interp_zw(F, fx, fy, fz);  // (gradient z, density)
+                shaded = !SKIP || !opacity_is_zero(P, zw.y);
                 if (shaded) {
-                    const float S = interp_a(Sq, sx, sy, sz);
-                    shade_blend_packed<false, false, true>(lpos, dif, amb, 2.5f, 0.5f, w, zw, gxy, tq, dst, false, f3{0.0f, 0.0f, 0.0f},
-                                                           0.0f, S);
+                    tq = tf_fetch(P.tf[0], zw.y);
+                    gxy = interp_xy(F, fx, fy, fz);
+                    fetch_a<OFF32>(P.vol[1], p, Sq, sx, sy, sz);
                 }
-                if (!(dst.w < 1.0f)) break;  // LIGHT's cut-off: no later iteration can blend
             }
+            Fetch4 G;
+            float gx = 0.0f, gy = 0.0f, gz = 0.0f;
+            __builtin_amdgcn_sched_barrier(0);
+            if (next) fetch_rgba<OFF32>(P.vol[0], pn, G, gx, gy, gz);
+            __builtin_amdgcn_sched_barrier(0);
+            if (inb) {
+                ++n;
+                if (sample) {
+                    ++fetched;
+                    if (shaded) {
+                        const float S = interp_a(Sq, sx, sy, sz);
+                        shade_blend_packed<false, false, true>(lpos, dif, amb, 2.5f, 0.5f, w, zw, gxy, tq, dst, false, f3{0.0f, 0.0f, 0.0f},
+                                                               0.0f, S);
+                    }
+                    if (!(dst.w < 1.0f)) break;  // LIGHT's cut-off: no later iteration can blend
+                }
+            }
+            F = G;
+            fx = gx;
+            fy = gy;
+            fz = gz;
+            have = next;
+            p = pn;
+            w = mk3(w.x + wstep.x, w.y + wstep.y, w.z + wstep.z);
         }
-        F = G;
-        fx = gx;
-        fy = gy;
-        fz = gz;
-        have = next;
-        p = pn;
-        w = mk3(w.x + wstep.x, w.y + wstep.y, w.z + wstep.z);
-    }
-    blends = n;
+        blends = n;
+    });
 }
 
 template <bool OFF32, bool SKIP, bool BATCH = false>
 __global__ __launch_bounds__(64) void march_shadow_kernel(const MarchBatch B)
 {
-    const MarchParams& P = frame_params<BATCH>(B);
-    const unsigned long long t_start = wall_clock64();
-    const PixelSlot slot = map_pixel(P);
-    float4 dst = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    unsigned blends = 0, covered = 0, fetched = 0;
-    shadow_packet<OFF32, SKIP>(P, slot, dst, blends, covered, fetched);
-    if (slot.active || (P.packed && slot.in_launch)) P.out[slot.out_index] = dst;
-    store_block_counts(P, blends, covered, fetched, t_start);
+    march_shell<BATCH>(B, [](auto&... a) { shadow_packet<OFF32, SKIP>(a...); });
 }
 
 }  // namespace VR_KNS

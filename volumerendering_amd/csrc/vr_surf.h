@@ -27,155 +27,100 @@ template <bool OFF32, bool SKIP>
 __device__ __forceinline__ void surf_packet(const MarchParams& P, const PixelSlot& slot, float4& dst, unsigned& samples, unsigned& covered,
                                             unsigned& fetched)
 {
-    if (!(slot.active && slot.px >= P.rect[0] && slot.px <= P.rect[2] && slot.py >= P.rect[1] && slot.py <= P.rect[3])) return;
-    const Ray ray = setup_ray(P, slot.px, slot.py);
-    if (!ray.hit) return;
-    const f3 diff = mk3(ray.end.x - ray.start.x, ray.end.y - ray.start.y, ray.end.z - ray.start.z);
-    const f3 dir = normalize3s(diff);
-    const float ray_len = length3s(diff);
-    if (P.fragment_mode == 1) {
-        dst = make_float4(fabsf(dir.x), fabsf(dir.y), fabsf(dir.z), 1.0f);
-        return;
-    } else if (P.fragment_mode == 2) {
-        dst = make_float4(ray.start.x, ray.start.y, ray.start.z, 1.0f);
-        return;
-    } else if (P.fragment_mode == 3) {
-        dst = make_float4(ray.end.x, ray.end.y, ray.end.z, 1.0f);
-        return;
-    } else if (P.fragment_mode == 4) {
-        dst = make_float4(0.5f * (ray.world0.x / 1.0f) + 0.5f, -0.5f * (ray.world0.y / 1.0f) + 0.5f, 0.0f, 1.0f);
-        return;
-    }
-    float step_size = P.step_size;
-    if (P.toggle_varstep == 1) step_size = ray_len / (float)P.steps_count;
-    f3 p = ray.start;
-    if (P.toggle_jitter == 1) {
-        const float j = jitter((float)slot.px + 0.5f, (float)slot.py + 0.5f);
-        p = mk3(p.x + (dir.x * step_size) * j, p.y + (dir.y * step_size) * j, p.z + (dir.z * step_size) * j);
-    }
-    const f3 step = mk3(dir.x * step_size, dir.y * step_size, dir.z * step_size);
-    const float tau = P.iso;
-    const float bx0 = P.bmin[0], by0 = P.bmin[1], bz0 = P.bmin[2];
-    const float bx1 = P.bmax[0], by1 = P.bmax[1], bz1 = P.bmax[2];
-    const int n_steps = P.steps_count;
-    const int n_inside = steps_inside(p, step, bx0, by0, bz0, bx1, by1, bz1);
-    auto in_box = [&](int i, f3 q) {
-        return i < n_inside || (q.x >= bx0 && q.x <= bx1 && q.y >= by0 && q.y <= by1 && q.z >= bz0 && q.z <= bz1);
-    };
-    unsigned n = 0;
-    float a = 0.0f, a_prev = 0.0f;
-    f3 pp = p;  // the step before the current one, and whether it was in the box
-    bool prev_inb = false;
-    bool hit = false;
+    RayStart r;
+    with_ray(P, slot, dst, r, [&]() __attribute__((always_inline)) {
+        f3 p = r.p;
+        const f3 step = r.step;
+        const float tau = P.iso;
+        const int n_steps = P.steps_count;
+        unsigned n = 0;
+        float a = 0.0f, a_prev = 0.0f;
+        f3 pp = p;  // the step before the current one, and whether it was in the box
+        bool prev_inb = false;
+        bool hit = false;
 
-    // step i: corners of p in F (requested one iteration ago) when `have`; R = distance-field byte of p + step (requested one
-    // iteration ago)
-    Fetch1 F;
-    float fx = 0.0f, fy = 0.0f, fz = 0.0f;
-    bool have = false;
-    unsigned R = 0;
-    if (n_steps > 0 && in_box(0, p)) {
-        have = !SKIP || dist_at(P, brick_of<OFF32>(P, p)) == 0u;
-        if (have) fetch_a<OFF32>(P.vol[0], p, F, fx, fy, fz);
-    }
-    if constexpr (SKIP) R = dist_at(P, brick_of<OFF32>(P, mk3(p.x + step.x, p.y + step.y, p.z + step.z)));
-    for (int i = 0; i < n_steps; ++i) {
-        const bool inb = in_box(i, p);
-        if (!inb) {
-            // p moves monotonically per component: once past the far bound it never returns
-            const bool gone = (step.x >= 0.0f && p.x > bx1) || (step.x <= 0.0f && p.x < bx0) || (step.y >= 0.0f && p.y > by1) ||
-                              (step.y <= 0.0f && p.y < by0) || (step.z >= 0.0f && p.z > bz1) || (step.z <= 0.0f && p.z < bz0);
-            if (gone) break;
+        // step i: corners of p in F (requested one iteration ago) when `have`; R = distance-field byte of p + step (requested one
+        // iteration ago)
+        Fetch1 F;
+        float fx = 0.0f, fy = 0.0f, fz = 0.0f;
+        bool have = false;
+        unsigned R = 0;
+        if (n_steps > 0 && in_box(P, r, 0, p)) {
+            have = !SKIP || dist_at(P, brick_of<OFF32>(P, p)) == 0u;
+            if (have) fetch_a<OFF32>(P.vol[0], p, F, fx, fy, fz);
         }
-        const f3 pn = mk3(p.x + step.x, p.y + step.y, p.z + step.z);
-        // the next step: loaded unless it is outside the box or in an inert brick
-        bool next = i + 1 < n_steps && in_box(i + 1, pn);
-        if constexpr (SKIP) {
-            next = next && R == 0u;
-            R = dist_at(P, brick_of<OFF32>(P, mk3(pn.x + step.x, pn.y + step.y, pn.z + step.z)));  // (issued before the corners below)
-        }
-        // this step's opacity texels are requested before the next step's corners, so that waiting for them leaves those eight
-        // loads in flight
-        const bool sample = inb && have;
-        float o0 = 0.0f, o1 = 0.0f, fo = 0.0f;
-        if (sample) {
-            const float d = interp_a(F, fx, fy, fz);
-            const float xo = mad(d, (float)P.tf[0].res_o, -0.5f);
-            const float xo0 = floorf(xo);
-            fo = xo - xo0;
-            const int jo = padded_texel(xo0, P.tf[0].res_o);
-            const float* po = reinterpret_cast<const float*>(reinterpret_cast<const char*>(P.tf[0].opacity) + ((unsigned)jo << 2));
-            o0 = po[0];
-            o1 = po[1];
-        }
-        Fetch1 G;
-        float gx = 0.0f, gy = 0.0f, gz = 0.0f;
-        __builtin_amdgcn_sched_barrier(0);
-        if (next) fetch_a<OFF32>(P.vol[0], pn, G, gx, gy, gz);
-        __builtin_amdgcn_sched_barrier(0);
-        if (inb) {
-            ++n;
-            if (sample) {
-                ++fetched;
-                a_prev = a;
-                a = mad(1.0f - a, lerpf(o0, o1, fo), a);  // the alpha line of FrontToBackBlend
-                if (a > tau) {
-                    hit = true;
-                    break;
-                }
-                if (!(a <= tau)) break;  // (a NaN alpha ends the loop and is no hit)
+        if constexpr (SKIP) R = dist_at(P, brick_of<OFF32>(P, mk3(p.x + step.x, p.y + step.y, p.z + step.z)));
+        for (int i = 0; i < n_steps; ++i) {
+            const bool inb = in_box(P, r, i, p);
+            if (!inb && gone(P, step, p)) break;
+            const f3 pn = mk3(p.x + step.x, p.y + step.y, p.z + step.z);
+            // the next step: loaded unless it is outside the box or in an inert brick
+            bool next = i + 1 < n_steps && in_box(P, r, i + 1, pn);
+            if constexpr (SKIP) {
+                next = next && R == 0u;
+                R = dist_at(P, brick_of<OFF32>(P, mk3(pn.x + step.x, pn.y + step.y, pn.z + step.z)));  // (issued before the corners below)
             }
+            // this step's opacity texels are requested before the next step's corners, so that waiting for them leaves those eight
+            // loads in flight
+            const bool sample = inb && have;
+            float o0 = 0.0f, o1 = 0.0f, fo = 0.0f;
+            if (sample) {
+                const float d = interp_a(F, fx, fy, fz);
+                const float xo = mad(d, (float)P.tf[0].res_o, -0.5f);
+                const float xo0 = floorf(xo);
+                fo = xo - xo0;
+                const int jo = padded_texel(xo0, P.tf[0].res_o);
+                const float* po = reinterpret_cast<const float*>(reinterpret_cast<const char*>(P.tf[0].opacity) + ((unsigned)jo << 2));
+                o0 = po[0];
+                o1 = po[1];
+            }
+            Fetch1 G;
+            float gx = 0.0f, gy = 0.0f, gz = 0.0f;
+            __builtin_amdgcn_sched_barrier(0);
+            if (next) fetch_a<OFF32>(P.vol[0], pn, G, gx, gy, gz);
+            __builtin_amdgcn_sched_barrier(0);
+            if (inb) {
+                ++n;
+                if (sample) {
+                    ++fetched;
+                    a_prev = a;
+                    a = mad(1.0f - a, lerpf(o0, o1, fo), a);  // the alpha line of FrontToBackBlend
+                    if (a > tau) {
+                        hit = true;
+                        break;
+                    }
+                    if (!(a <= tau)) break;  // (a NaN alpha ends the loop and is no hit)
+                }
+            }
+            pp = p;
+            prev_inb = inb;
+            F = G;
+            fx = gx;
+            fy = gy;
+            fz = gz;
+            have = next;
+            p = pn;
         }
-        pp = p;
-        prev_inb = inb;
-        F = G;
-        fx = gx;
-        fy = gy;
-        fz = gz;
-        have = next;
-        p = pn;
-    }
-    samples = n;
-    if (!hit) {
-        dst = make_float4(0.0f, 0.0f, 0.0f, a);
-        return;
-    }
-    covered = 1;
-    // the surface point: p_k, or the isosurface's secant step on alpha from the previous in-box step
-    f3 q = p;
-    if (prev_inb) {
-        const float t = (tau - a_prev) / (a - a_prev);
-        if (t >= 0.0f && t <= 1.0f) q = mk3(mad(step.x, t, pp.x), mad(step.y, t, pp.y), mad(step.z, t, pp.z));
-    }
-    dst = make_float4(q.x, q.y, q.z, a);
+        samples = n;
+        if (!hit) {
+            dst = make_float4(0.0f, 0.0f, 0.0f, a);
+            return;
+        }
+        covered = 1;
+        // the surface point: p_k, or the isosurface's secant step on alpha from the previous in-box step
+        f3 q = p;
+        if (prev_inb) {
+            const float t = (tau - a_prev) / (a - a_prev);
+            if (t >= 0.0f && t <= 1.0f) q = mk3(mad(step.x, t, pp.x), mad(step.y, t, pp.y), mad(step.z, t, pp.z));
+        }
+        dst = make_float4(q.x, q.y, q.z, a);
+    });
 }
 
 template <bool OFF32, bool SKIP, bool BATCH = false>
 __global__ __launch_bounds__(64) void march_surf_kernel(const MarchBatch B)
 {
-    const MarchParams& P = frame_params<BATCH>(B);
-    const unsigned long long t_start = wall_clock64();
-    const PixelSlot slot = map_pixel(P);
-    float4 dst = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    unsigned samples = 0, covered = 0, fetched = 0;
-    surf_packet<OFF32, SKIP>(P, slot, dst, samples, covered, fetched);
-    if (slot.active || (P.packed && slot.in_launch)) P.out[slot.out_index] = dst;
-    store_block_counts(P, samples, covered, fetched, t_start);
-}
-
-// The isosurface's picking read-back: march_iso_kernel's march with the refined point stored in place of the shading tail
-// (iso_packet<.., SURF = true>).  A kernel name of its own: march_iso_kernel keeps exactly the instances it had.
-template <bool OFF32, bool SKIP, bool BATCH = false>
-__global__ __launch_bounds__(64) void iso_point_kernel(const MarchBatch B)
-{
-    const MarchParams& P = frame_params<BATCH>(B);
-    const unsigned long long t_start = wall_clock64();
-    const PixelSlot slot = map_pixel(P);
-    float4 dst = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    unsigned samples = 0, covered = 0, fetched = 0;
-    iso_packet<OFF32, SKIP, true>(P, slot, dst, samples, covered, fetched);
-    if (slot.active || (P.packed && slot.in_launch)) P.out[slot.out_index] = dst;
-    store_block_counts(P, samples, covered, fetched, t_start);
+    march_shell<BATCH>(B, [](auto&... a) { surf_packet<OFF32, SKIP>(a...); });
 }
 
 #if !VR_FUSED
