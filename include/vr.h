@@ -422,7 +422,14 @@ int vr_last_block_trace(vr_ctx* ctx, uint64_t* out, int capacity);
  *   25  march_surf_kernel with exact skipping by BASIC's distance field (csrc/vr_surf.h): a step in an inert brick loads nothing
  *       and leaves the accumulated alpha as it is.  Flavour 0 runs as 25, and so does every other flavour but 1.  (Without a zero
  *       prefix of the opacity table 25 runs 26's kernels; the colour table and the light play no part.)
- *   26  march_surf_kernel without skipping: every in-box step up to the hit is fetched.  Flavour 1 runs as 26.               */
+ *   26  march_surf_kernel without skipping: every in-box step up to the hit is fetched.  Flavour 1 runs as 26.
+ * BASIC / LIGHT between ray bounds (vr_set_ray_bounds) likewise (0 candidates after such a launch):
+ *   27  march_bound_kernel with exact skipping by the variant's distance field (csrc/vr_bound.h): a step in an inert brick loads
+ *       nothing and a sample of opacity exactly 0 is not shaded, whether the step counts or not.  Flavour 0 runs as 27, and so does
+ *       every other flavour but 1.  (When the variant would not skip -- a non-finite colour table or light, no zero prefix of the
+ *       opacity table -- 27 runs 28's kernels.)
+ *   28  march_bound_kernel without skipping: every counted step up to the cut-off is fetched and shaded.  Flavour 1 runs as 28.
+ *       Both are one-lane kernels: on a whole unbounded frame they are slower than 17.                                       */
 int vr_set_kernel_flavour(vr_ctx* ctx, int flavour);
 
 /* What the default's measured choice (flavour 0) knows about the launch shape it was asked for last: the candidates' flavours, the
@@ -541,6 +548,36 @@ typedef struct vr_pick_result {
  * kernel choice stay what the render before the pick left: a pick between a render and its download is the normal use.
  * A pixel outside the viewport is VR_ERR_INVALID_ARG. */
 int vr_pick(vr_ctx* ctx, int variant, uint32_t x, uint32_t y, vr_pick_result* out);
+
+/* ---- per-pixel ray bounds: the colour march between two caller depth buffers ----------------------------------------------
+ * d_near and d_far are device pointers to W*H floats each, row-major, pixel (px, py) at py*W + px.  NULL = no bound on that side;
+ * both NULL = off (default): every launch is exactly what it is without this setting.  The buffers stay the caller's, as the d_frame
+ * of vr_render_async does.  The pointers are captured when a launch is enqueued (as vr_set_iso_value is); the kernel reads the
+ * contents in stream order: the caller writes the buffers on the launch's stream, or orders them before it.  vr_resize turns the
+ * bounds off (the buffers no longer fit); nothing else changes them.  A depth value means exactly what vr_surface_depth_async
+ * writes: clip.z / clip.w of proj * view * (world, 1) with the context's matrices -- a rasteriser's depth attachment under the same
+ * matrices, or the depth of a surface frame of this library.
+ *
+ * Applies to the colour launches of VR_VARIANT_BASIC and VR_VARIANT_LIGHT (shadows off) through the synchronous, asynchronous and
+ * tile launch shapes.  Everything is the variant's own march -- positions, world positions, variable step, jitter, the clip box, the
+ * cut-off 0.95 / 1.0, fragment modes 1-4 (which return what they return without bounds), the blend and every per-sample expression
+ * in the vr_set_arithmetic mode -- except which in-box steps count:
+ *   g(d) = unproject(ndcx, ndcy, d) of the ray set-up -- the function it calls for d = 0 and d = 1, with the same pixel-centre ndcx,
+ *     ndcy -- mapped to texture space with the ray set-up's map (x + 0.5f, y + 0.5f, 0.5f - 2.0f * z).
+ *   sigma(x) = (x.x*dir.x + x.y*dir.y) + x.z*dir.z, dir = the ray's normalised texture-space direction: separately rounded and summed
+ *     left to right in both arithmetic modes (ray placement, like length3s).
+ *   S_near = sigma(g(near[pixel])), S_far = sigma(g(far[pixel])), once per ray.
+ *   Step k at p_k counts iff it passes IsInSampleCoords and, near bound present, sigma(p_k) >= S_near and, far bound present,
+ *     sigma(p_k) < S_far.  A step that does not count is treated exactly like a step outside the clip box: not fetched, not blended,
+ *     not counted; p and w still advance by their rounded additions.
+ *   A NaN bound makes both comparisons false: no step of that pixel counts and the fragment is what a fully clipped ray gives.  No
+ *     value of a bound is an error: near > far, infinities and negatives included.
+ *   Counters as the variant's: composited = blends executed, covered as without bounds, fetched = counted samples whose corners were
+ *     loaded.
+ * With bounds on, every other variant, VR_OUTPUT_SURFACE, LIGHT with shadows on and the two *_batch_async entry points return
+ * VR_ERR_UNSUPPORTED and enqueue nothing (a silently ignored occluder is a wrong picture).  vr_pick ignores the bounds as it ignores
+ * the output setting.  Frames and counters are bit-identical across layouts, launch shapes and skipping on / off (flavours 27 / 28). */
+int vr_set_ray_bounds(vr_ctx* ctx, const void* d_near, const void* d_far);
 
 /* Volume layout in HBM (A/B measurements; frames and counts are bit-identical in every mode).
  *   0  default: the march kernels gather from a BRICKED copy of every slot -- the vec4 voxels and a scalar f32 density plane

@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "vr_tf_upload_opacity_async", "vr_tf_upload_color_async", "vr_skip_field", "vr_unbounded_box_launches",
     "vr_set_iso_value", "vr_set_shadows", "vr_shadow_volume",
     "vr_set_output", "vr_set_surface_threshold", "vr_surface_depth_async", "vr_pick",
+    "vr_set_ray_bounds",
 ]
 
 
@@ -149,6 +150,7 @@ def load() -> C.CDLL:
     lib.vr_set_surface_threshold.argtypes = [vp, C.c_float]
     lib.vr_surface_depth_async.argtypes = [vp, vp, vp, vp]
     lib.vr_pick.argtypes = [vp, i32, u32, u32, C.POINTER(PickResult)]
+    lib.vr_set_ray_bounds.argtypes = [vp, vp, vp]
     lib.vr_present_async.argtypes = [vp, vp, vp, vp]
     lib.vr_present_tiles_async.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
     lib.vr_hint_frames_in_flight.argtypes = [vp, i32]
@@ -439,6 +441,11 @@ class Context:
         out = PickResult()
         self._chk(self.lib.vr_pick(self.h, variant, x, y, C.byref(out)))
         return out
+
+    def set_ray_bounds(self, d_near: int | None = None, d_far: int | None = None):
+        """vr_set_ray_bounds: BASIC / LIGHT colour launches enqueued after this call march only between the two depth buffers (device
+        pointers to W*H floats each, the depth convention of surface_depth; None = no bound on that side, both None = off)."""
+        self._chk(self.lib.vr_set_ray_bounds(self.h, d_near or None, d_far or None))
 
     def set_volume_layout(self, mode: int):
         """0 bricked copy (default), 1 the reference's vec4 voxels only, 3 x-fastest voxels + density plane (2 was removed)."""

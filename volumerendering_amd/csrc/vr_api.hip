@@ -258,6 +258,10 @@ struct vr_ctx {
     float4* d_pick = nullptr;
     float* d_pick_depth = nullptr;
     int pick_px[2] = {-1, -1};
+    // Per-pixel ray bounds (vr_set_ray_bounds, vr_bound.h): the caller's depth buffers, W*H floats each (nullptr: no bound on that side);
+    // captured at enqueue, dropped by vr_resize
+    const float* d_near = nullptr;
+    const float* d_far = nullptr;
     std::string err;
 };
 
@@ -574,9 +578,10 @@ double rays_per_lane(const vr_ctx* c, int rank, int world, int frames)
 
 // what a launch rendered, whatever kernel form it took (OrderSlot::scene_key: the key of the longest ray chain its sort reports)
 // (a surface launch -- vr_set_output -- is a scene of its own: its chains say nothing about the colour launch's)
-unsigned long long scene_key(const vr_ctx* c, int variant, int rank, int world, bool packed, bool surface = false)
+// (so is a launch between ray bounds -- vr_set_ray_bounds)
+unsigned long long scene_key(const vr_ctx* c, int variant, int rank, int world, bool packed, bool surface = false, bool bounded = false)
 {
-    return ((unsigned long long)(variant | (surface ? 0x80 : 0)) << 16) ^ ((unsigned long long)world << 8) ^ (unsigned long long)rank ^ (packed ? 1ull << 63 : 0ull) ^
+    return ((unsigned long long)(variant | (surface ? 0x80 : 0) | (bounded ? 0x40 : 0)) << 16) ^ ((unsigned long long)world << 8) ^ (unsigned long long)rank ^ (packed ? 1ull << 63 : 0ull) ^
            ((unsigned long long)c->W << 40) ^ ((unsigned long long)c->H << 24);
 }
 
@@ -1042,7 +1047,8 @@ int prepare_shadow(vr_ctx* c, hipStream_t s, MarchParams& P, const vr_ctx::Shado
 }
 
 // The kernel form ("flavour") a launch runs: `fl` is the one asked for (vr_set_kernel_flavour, else VR_EXP_FLAVOUR), 0 = the default.
-int choose_flavour(vr_ctx* c, int fl, int variant, int n_frames, int rank, int world, bool packed, const Eligibility& E, bool surface)
+int choose_flavour(vr_ctx* c, int fl, int variant, int n_frames, int rank, int world, bool packed, const Eligibility& E, bool surface,
+                   bool bounded)
 {
     // The one-lane families come in pairs: 1 asks for the form without skipping (the odd flavour + 1), everything else runs as the
     // skipping one; nothing is measured.  The first row that applies decides (the isosurface's surface output keeps 21 / 22).
@@ -1050,6 +1056,7 @@ int choose_flavour(vr_ctx* c, int fl, int variant, int n_frames, int rank, int w
         bool applies;
         int skipping;
     } pairs[] = {
+        {bounded, 27},                                            // the unlit / lit shader between ray bounds
         {surface && variant != VR_VARIANT_ISO, 25},               // the surface-position output of the unlit / lit shader
         {is_projection(variant), 19},                             // the projections
         {variant == VR_VARIANT_ISO, 21},                          // the isosurface
@@ -1135,7 +1142,7 @@ struct KernelForm {
     LaunchDesc::Family family;
     int lanes;            // kDp: lanes per ray (vr_dp.h): 64 / 32 workgroups per tile
     bool pipe;            // kDp / kPw: the next round's / step's corner loads software-pipelined
-    bool skip;            // the skipping flavour of a pair (17 of 16 / 17; 19, 21, 23, 25 of the one-lane families): LaunchDesc::skip once
+    bool skip;            // the skipping flavour of a pair (17 of 16 / 17; 19, 21, 23, 25, 27 of the one-lane families): LaunchDesc::skip once
                           // its records are in place
     bool lut;             // kPlain: the slot tables of volume 0 in LDS
     unsigned pw_threads;  // kPw / kP2: threads per workgroup
@@ -1143,7 +1150,7 @@ struct KernelForm {
     bool range_records() const { return family == LaunchDesc::kProj || family == LaunchDesc::kIso; }  // skips by prepare_proj's records
     bool measured() const  // a candidate of the measured choice (the one-lane families never are)
     {
-        return !(range_records() || family == LaunchDesc::kShadow || family == LaunchDesc::kSurf);
+        return !(range_records() || family == LaunchDesc::kShadow || family == LaunchDesc::kSurf || family == LaunchDesc::kBound);
     }
 };
 
@@ -1176,6 +1183,8 @@ KernelForm kernel_form(int fl, int variant)
     case 24: return {D::kShadow, 0, false, fl == 23, false, 0u};
     case 25:
     case 26: return {D::kSurf, 0, false, fl == 25, false, 0u};
+    case 27:
+    case 28: return {D::kBound, 0, false, fl == 27, false, 0u};
     default: return {D::kPlain, 0, false, false, false, 0u};  // 1, 6
     }
 }
@@ -1309,6 +1318,17 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
     if (surface && variant >= 0 && variant < VR_VARIANT_COUNT && variant != VR_VARIANT_BASIC && variant != VR_VARIANT_LIGHT &&
         variant != VR_VARIANT_ISO)
         return fail(c, VR_ERR_UNSUPPORTED, "vr_render: surface output exists for BASIC, LIGHT and ISO only");
+    // ray bounds (vr_set_ray_bounds; a pick launch ignores them): colour launches of one frame of the unlit shader and of the lit one
+    // without shadows -- anything else is refused, never rendered with the occluder ignored
+    const bool bounded = (c->d_near || c->d_far) && c->pick_px[0] < 0;
+    if (bounded && variant >= 0 && variant < VR_VARIANT_COUNT) {
+        if (variant != VR_VARIANT_BASIC && variant != VR_VARIANT_LIGHT)
+            return fail(c, VR_ERR_UNSUPPORTED, "vr_render: ray bounds exist for BASIC and LIGHT only");
+        if (surface) return fail(c, VR_ERR_UNSUPPORTED, "vr_render: ray bounds do not apply to surface output");
+        if (variant == VR_VARIANT_LIGHT && c->shadow_div != 0)
+            return fail(c, VR_ERR_UNSUPPORTED, "vr_render: ray bounds do not apply to LIGHT with shadows on");
+        if (batch_u) return fail(c, VR_ERR_UNSUPPORTED, "vr_render: ray bounds do not apply to launches of several frames");
+    }
     if (const int rc = check_render_args(c, variant, rank, world, n_frames, batch_u, batch_out, &nvol, &off32)) return rc;
     // shadows: every frame of the launch reads one light volume, of less than 4 GiB (a surface launch reads none)
     const bool shadowed = variant == VR_VARIANT_LIGHT && c->shadow_div != 0 && !surface;
@@ -1351,7 +1371,7 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
         if (const int rc = prepare_skip(c, variant, s, P)) return rc;
         if (c->skip_pending) ++c->unbounded_launches;
     }
-    const int fl = choose_flavour(c, requested, variant, n_frames, rank, world, packed, E, surface);
+    const int fl = choose_flavour(c, requested, variant, n_frames, rank, world, packed, E, surface, bounded);
     c->last_flavour = fl;
     const KernelForm form = kernel_form(fl, variant);
     c->last_unmeasured = !form.measured();
@@ -1363,6 +1383,10 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
 
     if (c->layout_mode == 0) use_bricked_copies(c, P);
     if (form.lut && P.vol[0].bricked) P.vol[0].lut = 1;  // (march_kernel fills the tables; every fetch of volume 0 goes through them)
+    if (form.family == LaunchDesc::kBound) {  // the depth buffers, in the slots these shaders do not sample (vr_bound.h)
+        P.vol[1].data = reinterpret_cast<const float4*>(c->d_near);
+        P.vol[2].data = reinterpret_cast<const float4*>(c->d_far);
+    }
     for (int i = 0; i < nvol; ++i)  // (a bricked copy is padded to whole bricks: a volume just below 4 GiB may cross the line)
         if (P.vol[i].bricked && bricked_grid(P.vol[i]).slots * 16 > 0xFFFFFFFFull) off32 = false;
 
@@ -1407,8 +1431,8 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
         P.block_counts = c->d_block_counts[cb];
         c->cnt_buf = cb;
         const unsigned long long okey = ((unsigned long long)grid.x << 32) ^ ((unsigned long long)block.x << 20) ^
-                                        ((unsigned long long)(variant | (surface ? 0x10 : 0)) << 16) ^ ((unsigned long long)world << 8) ^ (unsigned long long)rank ^
-                                        (packed ? 1ull << 63 : 0ull);
+                                        ((unsigned long long)(variant | (surface ? 0x10 : 0) | (bounded ? 0x20 : 0)) << 16) ^ ((unsigned long long)world << 8) ^
+                                        (unsigned long long)rank ^ (packed ? 1ull << 63 : 0ull);
         const bool ordered = grid.x <= (unsigned)kOrderMaxBlocks && grid.x % 8u == 0;
         if (const int rc = wait_for_order(c, s, ordered, okey, slot_sort, &P.order)) return rc;
 
@@ -1453,7 +1477,7 @@ int enqueue_render(vr_ctx* c, int variant, int rank, int world, bool packed, flo
         mark_reads(c, P);
         if (time_with_events) VR_HIP(c, hipEventRecord(c->ring.k1[ring], s));
 
-        if (const int rc = enqueue_sort(c, s, cb, ordered, okey, scene_key(c, variant, rank, world, packed, surface), grid.x, ring, time_with_events, pw))
+        if (const int rc = enqueue_sort(c, s, cb, ordered, okey, scene_key(c, variant, rank, world, packed, surface, bounded), grid.x, ring, time_with_events, pw))
             return rc;
         if (frame_events) VR_HIP(c, hipEventRecord(c->tm.ev_k1, s));
         ++c->ring.head;
@@ -1797,6 +1821,7 @@ int vr_resize(vr_ctx* c, uint32_t width, uint32_t height)
     drained(c);
     c->W = width;
     c->H = height;
+    c->d_near = c->d_far = nullptr;  // (the caller's depth buffers no longer fit)
     return alloc_frame(c);
 }
 
@@ -2557,6 +2582,14 @@ int vr_set_output(vr_ctx* c, int mode)
     return VR_OK;
 }
 
+int vr_set_ray_bounds(vr_ctx* c, const void* d_near, const void* d_far)
+{
+    if (!c) return VR_ERR_INVALID_ARG;
+    c->d_near = static_cast<const float*>(d_near);
+    c->d_far = static_cast<const float*>(d_far);
+    return VR_OK;
+}
+
 int vr_set_surface_threshold(vr_ctx* c, float tau)
 {
     if (!c) return VR_ERR_INVALID_ARG;
@@ -2682,7 +2715,7 @@ int vr_volume_layout(vr_ctx* c, int slot, int* flags)
 int vr_kernel_choice(vr_ctx* c, int flavours[6], float ms_per_launch[6], int* chosen)
 {
     if (!c) return VR_ERR_INVALID_ARG;
-    if (c->last_unmeasured) {  // (the projections', the isosurface's, the shadowed and the surface forms)
+    if (c->last_unmeasured) {  // (the projections', the isosurface's, the shadowed, the surface and the bounded forms)
         if (chosen) *chosen = -1;
         return 0;
     }

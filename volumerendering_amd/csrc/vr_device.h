@@ -152,14 +152,16 @@ struct PwQueue {
 // What enqueue_render decided about one march launch; handed to launch_march of the arithmetic mode's translation unit
 // (vr_launch.h: namespace vr = separately rounded multiply-adds, namespace vrf = fused).  Host only.
 struct LaunchDesc {
-    enum Family { kPlain, kDp, kPw, kP2, kLt, kProj, kIso, kShadow, kSurf };
+    enum Family { kPlain, kDp, kPw, kP2, kLt, kProj, kIso, kShadow, kSurf, kBound };
     int variant;      // vr_variant
     Family family;    // march_kernel, march_dp_kernel, march_pw_kernel (persistent wavefronts: grid = workgroups, the packets come
                       // from `queue`), march_p2_kernel (the same, corner loads two steps ahead), march_lt_kernel (LDS tiles, lit shader),
                       // the one-lane marches on vr_ray.h's prologue and shell:
                       // march_proj_kernel (vr_proj.h: the intensity projections), march_iso_kernel (vr_iso.h: the isosurface),
                       // march_shadow_kernel (vr_shadow.h: the lit shader with shadows; MarchParams::vol[1] = the light volume),
-                      // march_surf_kernel (vr_surf.h: the surface-position output of the unlit / lit shader; MarchParams::iso = the threshold)
+                      // march_surf_kernel (vr_surf.h: the surface-position output of the unlit / lit shader; MarchParams::iso = the threshold),
+                      // march_bound_kernel (vr_bound.h: the unlit / lit shader between per-pixel ray bounds; MarchParams::vol[1].data /
+                      // vol[2].data = the near / far depth buffers, W*H floats each or nullptr)
     bool off32;       // every bound volume < 4 GiB: 32-bit byte offsets
     int lanes;        // kDp: lanes per ray (2 / 4)
     bool pipe;        // kDp / kPw: the next round's / step's corner loads software-pipelined
@@ -171,7 +173,7 @@ struct LaunchDesc {
     bool skip;        // the skipping form of a flavour pair, asked for only with its records in place (KernelForm::skip, vr_api.hip).
                       // kP2: skipping by whole wavefronts on the distance field (march_p2_kernel<V, true>); kProj / kIso: by volume
                       // 0's range records in MarchParams::bricks (march_proj_kernel / march_iso_kernel / iso_point_kernel<.., SKIP = true,
-                      // ..>); kShadow / kSurf: by the distance field (march_shadow_kernel / march_surf_kernel<.., true, ..>).  The other
+                      // ..>); kShadow / kSurf / kBound: by the distance field (march_shadow_kernel / march_surf_kernel / march_bound_kernel<.., true, ..>).  The other
                       // families read MarchParams::brick_dist alone.
     const float2* vrange;  // kProj: (min, max) of volume 0 (vr_proj.h)
     bool surface;          // kIso: the refined point instead of the shaded fragment (iso_point_kernel, vr_iso.h)

@@ -18,7 +18,7 @@
 // is part of the shipped library: slower than the two-steps-ahead kernel everywhere measured, selectable with
 // vr_set_kernel_flavour(15) and tested on every box, not a candidate of the measured choice.
 #include "vr_lt.h"
-// The ray prologue, the in-box tests and the kernel shell of the four one-lane families below
+// The ray prologue, the in-box tests and the kernel shell of the five one-lane families below
 #include "vr_ray.h"
 // Intensity projections (MIP / MinIP / AIP of volume slot 0; flavours 19 and 20)
 #include "vr_proj.h"
@@ -28,6 +28,8 @@
 #include "vr_shadow.h"
 // The surface-position output of the unlit / lit shader (flavours 25 and 26); the depth of a surface frame
 #include "vr_surf.h"
+// Per-pixel ray bounds of the unlit / lit shader (flavours 27 and 28; MarchParams::vol[1].data / vol[2].data = the depth buffers)
+#include "vr_bound.h"
 
 #include <type_traits>
 
@@ -103,7 +105,7 @@ void launch_p2(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
     }, V == V_VOLUME_MASK || (B.frame[0].brick_dist && L.skip), L.p2_win, B.n_frames > 1);
 }
 
-// The one-lane kernels of vr_proj.h, vr_iso.h, vr_shadow.h and vr_surf.h: skipping x addressing x frames per launch.
+// The one-lane kernels of vr_proj.h, vr_iso.h, vr_shadow.h, vr_surf.h and vr_bound.h: skipping x addressing x frames per launch.
 // kernel(S, O, BT) returns the instantiation; args follow the batch.
 template <class K, class... A>
 void launch_one_lane(const LaunchDesc& L, hipStream_t s, const MarchBatch& B, K kernel, A... args)
@@ -132,6 +134,10 @@ void launch_march(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
     switch (L.family) {
     case LaunchDesc::kShadow: launch_one_lane(L, s, B, [](auto S, auto O, auto BT) { return march_shadow_kernel<O, S, BT>; }); return;
     case LaunchDesc::kSurf: launch_one_lane(L, s, B, [](auto S, auto O, auto BT) { return march_surf_kernel<O, S, BT>; }); return;
+    case LaunchDesc::kBound:  // (launches of one frame: BT is not an argument)
+        if (L.variant == VR_VARIANT_LIGHT) launch_one_lane(L, s, B, [](auto S, auto O, auto) { return march_bound_kernel<V_LIGHT, O, S>; });
+        else launch_one_lane(L, s, B, [](auto S, auto O, auto) { return march_bound_kernel<V_BASIC, O, S>; });
+        return;
     case LaunchDesc::kIso:  // (surface output: the refined points)
         if (L.surface) launch_one_lane(L, s, B, [](auto S, auto O, auto BT) { return iso_point_kernel<O, S, BT>; });
         else launch_one_lane(L, s, B, [](auto S, auto O, auto BT) { return march_iso_kernel<O, S, BT>; });

@@ -1,7 +1,7 @@
-// vr_ray.h -- what the one-lane marches of vr_proj.h, vr_iso.h, vr_shadow.h and vr_surf.h share: the ray prologue (with_ray: BASIC's start,
+// vr_ray.h -- what the one-lane marches of vr_proj.h, vr_iso.h, vr_shadow.h, vr_surf.h and vr_bound.h share: the ray prologue (with_ray: BASIC's start,
 // direction, step and the reference's quirks around them), the in-box and past-the-box tests of their step loops, and the kernel
 // shell around a packet.  Each file keeps its own step loop: the loops differ in what is requested before the next step's corners.
-// Included by vr_launch.h once per arithmetic mode, ahead of the four.
+// Included by vr_launch.h once per arithmetic mode, ahead of the five.
 //
 // Wave-uniform values (the clip bounds, steps_count, step_size) are read from MarchParams where they are used and never copied into
 // RayStart: a copy in a per-lane struct moves them from SGPRs to VGPRs (march_proj_kernel: 59 -> 68 VGPRs, 8 -> 7 wavefronts per SIMD).
