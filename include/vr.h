@@ -579,6 +579,76 @@ int vr_pick(vr_ctx* ctx, int variant, uint32_t x, uint32_t y, vr_pick_result* ou
  * the output setting.  Frames and counters are bit-identical across layouts, launch shapes and skipping on / off (flavours 27 / 28). */
 int vr_set_ray_bounds(vr_ctx* ctx, const void* d_near, const void* d_far);
 
+/* ---- slice views: oblique reformats and slab projections of one volume slot ------------------------------------------------
+ * A plane through a volume instead of a camera's view of it (no shader of the reference; csrc/vr_slice.h): parallel sample lines
+ * on a caller-defined plane in texture space, any output size, any uploaded volume slot through any TF slot.  The context's
+ * uniforms, clip box, viewport, output setting, ray bounds and shadows play no part.
+ *   Positions: for pixel (px, py) and each component c, b.c = (origin.c + (float)px * du.c) + (float)py * dv.c -- product and sums
+ *     rounded separately in both vr_set_arithmetic modes (placement, like the ray set-up).  p_0 = b, p_{k+1} = p_k + dn (a rounded
+ *     addition per component), k = 0 .. slab_steps - 1.  Step k counts iff every component of p_k is >= 0 and <= 1 (NaN fails).
+ *   Sample: VR_SLICE_LINEAR -- d = BASIC's trilinear .a fetch of the slot at p_k in the arithmetic mode (texture coordinates
+ *     p * N - 0.5 and the seven lerps follow the mode, clamp-to-edge texel pairs).  VR_SLICE_NEAREST -- d = .a of the voxel
+ *     clamp((int)floor(p_k * N), 0, N - 1) per axis, the product rounded once (TFCalibrationApp.wgsl:172).
+ *   Reduction over the n counted samples, in step order, as MIP / MINIP / AVERAGE above:
+ *     VR_SLICE_MAX:     m = -inf, then if (d > m) m = d          (NaN samples are ignored)
+ *     VR_SLICE_MIN:     m = +inf, then if (d < m) m = d          (NaN samples are ignored)
+ *     VR_SLICE_AVERAGE: s = +0.0f, then s = s + d (f32), v = s / (float)n   (NaN propagates)
+ *   Pixel: n == 0 -> (0,0,0,0).  Otherwise v goes through the TF slot with BASIC's lookup (linear, clamp-to-edge, each table at its
+ *     own resolution) and the fragment is FrontToBackBlend((c.rgb, o), dst = 0) in the blend's own arithmetic:
+ *     (c.r o, c.g o, c.b o, o), a -0 made +0.  VR_SLICE_RGBA32F stores that float4; VR_SLICE_BGRA8 stores the four bytes
+ *     vr_present_async gives for it (one 32-bit word per pixel; the n == 0 pixel is the white background, 0xFFFFFFFF).
+ *     The output is row-major, pixel (px, py) at py * width + px: width * height * 16 or * 4 bytes.
+ *   Counters (vr_slice_counters): out[0] = counted samples (the sum of n), out[1] = pixels with n > 0, out[2] = samples whose
+ *     voxels were loaded.
+ * Kernel forms: every flavour of vr_set_kernel_flavour but 1 runs slice_kernel with exact skipping by the slot's per-brick range
+ * records (MAX: brick max <= m, MIN: brick min >= m, AVERAGE: every voxel the brick can touch +-0; MAX / MIN stop loading once m
+ * has reached the slot's extreme), flavour 1 the form that loads every counted sample (out[2] == out[0]).  The output, out[0] and
+ * out[1] are bit-identical across the two forms and the volume layouts.  vr_last_kernel_flavour does not report slices. */
+#define VR_SLICE_MAX 0
+#define VR_SLICE_MIN 1
+#define VR_SLICE_AVERAGE 2
+#define VR_SLICE_LINEAR 0
+#define VR_SLICE_NEAREST 1
+#define VR_SLICE_RGBA32F 0
+#define VR_SLICE_BGRA8 1
+typedef struct vr_slice_desc {
+    int32_t volume_slot;    /* an uploaded slot, 0 .. VR_MAX_VOLUMES-1                         */
+    int32_t tf_slot;        /* a slot with both tables uploaded                                */
+    uint32_t width, height; /* of the output, 1 .. 16384 each; independent of the viewport     */
+    float origin[3];        /* texture-space position of pixel (0,0)'s centre at slab step 0   */
+    float du[3], dv[3];     /* texture-space displacement per output pixel in x / in y         */
+    float dn[3];            /* ... per slab step                                               */
+    int32_t slab_steps;     /* 1 .. 65536; 1 = the thin slice                                  */
+    int32_t reduce, filter, format;
+} vr_slice_desc;
+
+/* Enqueues the slice on `stream` (a hipStream_t, NULL = the ctx's own) into DEVICE memory `d_out`; nothing is synchronised.
+ * VR_ERR_INVALID_ARG, before anything is enqueued: a NULL pointer, a slot out of range, a zero or oversized output, slab_steps out of
+ * range, an unknown reduce / filter / format.  VR_ERR_NOT_READY: the volume slot or one of the TF slot's tables is missing.  No value
+ * of origin, du, dv or dn is an error: NaN and infinities simply count nothing.
+ * A slice is a launch like any other for the stream-ordered machinery: it comes after every vr_tf_upload_*_async made before it and
+ * keeps the tables it read from being rewritten under it; it is one of the eight launches that may be in flight; the range records it
+ * skips by are built on its stream when a volume changed since they were built (no host wait), and slices on other streams wait for
+ * that build once.  It changes nothing else the caller can read: the frame of vr_download, vr_last_counters, vr_last_kernel_flavour,
+ * vr_last_timing, vr_kernel_times and vr_kernel_choice stay what the render before it left -- a slice between a render and its
+ * download is the normal use -- and vr_resize does not concern it.                                                          */
+int vr_slice_async(vr_ctx* ctx, const vr_slice_desc* desc, void* d_out, void* stream);
+
+/* The same into HOST memory `out_host` (width * height * 16 or * 4 bytes), on the ctx's own stream; synchronous on return. */
+int vr_slice_render(vr_ctx* ctx, const vr_slice_desc* desc, void* out_host);
+
+/* Fills *out for the axis-aligned plane `axis` (0 = x, 1 = y, 2 = z) at voxel `index` of volume slot `slot`: one output pixel per
+ * voxel, pixel centres at voxel centres ((float)i + 0.5f) / (float)n.  The output's x / y run along (y, z) for axis 0, (x, z) for
+ * axis 1 and (x, y) for axis 2.  A slab of `thickness` >= 1 voxels is centred on `index`: step 0 lies at voxel index - (thickness - 1) / 2
+ * (integer division) and dn is one voxel, 1.0f / (float)n, along the axis; where the slab runs past a face its steps simply do not
+ * count (it is not moved).  Sets volume_slot = slot, tf_slot = 0, reduce = VR_SLICE_MAX, filter = VR_SLICE_LINEAR, format =
+ * VR_SLICE_RGBA32F; the caller edits them.  Pure host arithmetic; VR_ERR_INVALID_ARG for a NULL pointer, a bad slot, axis, index or
+ * thickness (1 .. 65536), VR_ERR_NOT_READY for an empty slot.                                                               */
+int vr_slice_orthogonal(const vr_ctx* ctx, int slot, int axis, int index, int thickness, vr_slice_desc* out);
+
+/* Counters of the last slice launch (as described above); waits for that launch.  Zeros before the first slice. */
+int vr_slice_counters(vr_ctx* ctx, uint64_t out[3]);
+
 /* Volume layout in HBM (A/B measurements; frames and counts are bit-identical in every mode).
  *   0  default: the march kernels gather from a BRICKED copy of every slot -- the vec4 voxels and a scalar f32 density plane
  *      (what fetches that consume .a alone read: BasicVolumeApp.wgsl:171, the density / dose fetches of the other shaders)

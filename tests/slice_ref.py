@@ -1,0 +1,179 @@
+"""float32 numpy restatement of the slice views of include/vr.h (vr_slice_desc): positions b = (origin + px * du) + py * dv and
+p += dn by rounded additions, the samples inside the unit cube, their maximum / minimum / mean, one TF look-up and one
+FrontToBackBlend onto 0, and vr_present_async's bytes.  Built on proj_ref's sampler, TF look-up and blend (pinned to the oracle by
+tests/test_projection.py); adds the nearest fetch and, for VR_ARITH_FUSED, the same expressions with their multiply-adds fused
+(texture coordinates, the seven lerps, the TF coordinates and lerps).  Harness only."""
+import numpy as np
+
+import proj_ref as pr
+from volumerendering_amd import capi
+
+f32 = np.float32
+MAX, MIN, AVERAGE = 0, 1, 2
+LINEAR, NEAREST = 0, 1
+RGBA32F, BGRA8 = 0, 1
+
+
+def fma32(a, b, c):
+    """Correctly rounded f32 a * b + c: the product is exact in f64, the f64 sum is rounded to odd (TwoSum tells whether it was
+    inexact and to which side), and rounding that to f32 is then the single rounding of the exact value."""
+    a, b, c = (np.asarray(x, f32).astype(np.float64) for x in np.broadcast_arrays(a, b, c))
+    with np.errstate(all="ignore"):
+        p = a * b
+        s = p + c
+        bb = s - p
+        e = (p - (s - bb)) + (c - bb)
+        fix = np.isfinite(s) & np.isfinite(e) & (e != 0.0) & ((s.view(np.int64) & 1) == 0)
+        toward = np.where(e > 0.0, np.inf, -np.inf)
+        s = np.where(fix, np.nextafter(s, toward), s)
+        return s.astype(f32)
+
+
+def _lerp_f(a, b, t):
+    with np.errstate(all="ignore"):
+        return fma32(b - a, t, a)
+
+
+def sample_a(dens, p, fused=False):
+    """textureSample(vol, linear, p).a in either arithmetic mode."""
+    if not fused:
+        return pr.sample_a(dens, p)
+    nz, ny, nx = dens.shape
+    x = fma32(p[:, 0], f32(nx), f32(-0.5))
+    y = fma32(p[:, 1], f32(ny), f32(-0.5))
+    z = fma32(p[:, 2], f32(nz), f32(-0.5))
+    with np.errstate(all="ignore"):
+        x0, y0, z0 = np.floor(x), np.floor(y), np.floor(z)
+        fx, fy, fz = x - x0, y - y0, z - z0
+    i0, i1 = pr._texel_pair(x0, nx)
+    j0, j1 = pr._texel_pair(y0, ny)
+    k0, k1 = pr._texel_pair(z0, nz)
+    c00 = _lerp_f(dens[k0, j0, i0], dens[k0, j0, i1], fx)
+    c10 = _lerp_f(dens[k0, j1, i0], dens[k0, j1, i1], fx)
+    c01 = _lerp_f(dens[k1, j0, i0], dens[k1, j0, i1], fx)
+    c11 = _lerp_f(dens[k1, j1, i0], dens[k1, j1, i1], fx)
+    return _lerp_f(_lerp_f(c00, c10, fy), _lerp_f(c01, c11, fy), fz)
+
+
+def nearest_index(p, shape):
+    """(k, j, i) of the voxel textureSample(vol, nearest, p) addresses: clamp((int)floor(p * n), 0, n - 1), the product rounded once."""
+    nz, ny, nx = shape
+    with np.errstate(all="ignore"):
+        i = np.clip(pr._i32_sat(np.floor(p[:, 0] * f32(nx))), 0, nx - 1)
+        j = np.clip(pr._i32_sat(np.floor(p[:, 1] * f32(ny))), 0, ny - 1)
+        k = np.clip(pr._i32_sat(np.floor(p[:, 2] * f32(nz))), 0, nz - 1)
+    return k, j, i
+
+
+def sample_nearest(dens, p):
+    k, j, i = nearest_index(p, dens.shape)
+    return dens[k, j, i]
+
+
+def tf_lookup(opacity, color, d, fused=False):
+    if not fused:
+        return pr.tf_lookup(opacity, color, d)
+    x = fma32(d, f32(opacity.size), f32(-0.5))
+    xc = fma32(d, f32(color.shape[0]), f32(-0.5))
+    with np.errstate(all="ignore"):
+        x0, xc0 = np.floor(x), np.floor(xc)
+        fo, fc = x - x0, xc - xc0
+    i0, i1 = pr._texel_pair(x0, opacity.size)
+    c0, c1 = pr._texel_pair(xc0, color.shape[0])
+    o = _lerp_f(opacity[i0], opacity[i1], fo)
+    rgb = _lerp_f(color[c0, :3], color[c1, :3], fc[:, None])
+    return o, rgb
+
+
+def orthogonal_desc(shape, axis, index, thickness=1, slot=0):
+    """vr_slice_orthogonal's descriptor for a volume of shape (nx, ny, nz), restated: one pixel per voxel, centres
+    ((float)i + 0.5f) / (float)n, the slab centred on `index`, one voxel per step."""
+    n = [int(x) for x in shape]
+    ua, va = (1 if axis == 0 else 0), (1 if axis == 2 else 2)
+    d = capi.SliceDesc()
+    d.volume_slot, d.tf_slot, d.width, d.height, d.slab_steps = slot, 0, n[ua], n[va], thickness
+    d.reduce, d.filter, d.format = MAX, LINEAR, RGBA32F
+    d.origin[ua] = f32(0.5) / f32(n[ua])
+    d.origin[va] = f32(0.5) / f32(n[va])
+    d.origin[axis] = (f32(index - (thickness - 1) // 2) + f32(0.5)) / f32(n[axis])
+    d.du[ua] = f32(1.0) / f32(n[ua])
+    d.dv[va] = f32(1.0) / f32(n[va])
+    d.dn[axis] = f32(1.0) / f32(n[axis])
+    return d
+
+
+def positions(desc, pixels):
+    """b of the pixels (N, 2) = (px, py): (origin + px * du) + py * dv, each operation rounded."""
+    o, du, dv = (np.array(list(v), f32) for v in (desc.origin, desc.du, desc.dv))
+    px = pixels[:, 0].astype(f32)[:, None]
+    py = pixels[:, 1].astype(f32)[:, None]
+    with np.errstate(all="ignore"):
+        return ((o[None, :] + px * du[None, :]) + py * dv[None, :]).astype(f32)
+
+
+def in_cube(p):
+    with np.errstate(all="ignore"):
+        return np.all((p >= f32(0.0)) & (p <= f32(1.0)), axis=1)
+
+
+def reduce_slab(desc, vec4, pixels=None, fused=False, max_steps=None):
+    """(value (N,), n (N,), pixels) of the slab reduction, before the TF.  Steps beyond the last one at which any pixel can still
+    count are not walked (positions are monotone per component; a NaN stays a NaN)."""
+    W, H = int(desc.width), int(desc.height)
+    if pixels is None:
+        pixels = np.stack(np.meshgrid(np.arange(W), np.arange(H)), -1).reshape(-1, 2)
+    pixels = np.asarray(pixels, np.int64).reshape(-1, 2)
+    dens = np.ascontiguousarray(np.asarray(vec4, f32)[..., 3])
+    dn = np.array(list(desc.dn), f32)
+    p = positions(desc, pixels)
+    N = len(pixels)
+    n = np.zeros(N, np.int64)
+    m = np.full(N, {MAX: -np.inf, MIN: np.inf}.get(int(desc.reduce), 0.0), f32)
+    steps = int(desc.slab_steps) if max_steps is None else min(int(desc.slab_steps), max_steps)
+    for _ in range(steps):
+        inb = in_cube(p)
+        with np.errstate(all="ignore"):
+            gone = np.any(((dn >= 0) & (p > f32(1.0))) | ((dn <= 0) & (p < f32(0.0))) | np.isnan(p), axis=1)
+        if not inb.any() and gone.all():
+            break
+        d = sample_nearest(dens, p) if int(desc.filter) == NEAREST else sample_a(dens, p, fused)
+        n += inb
+        with np.errstate(all="ignore"):
+            if desc.reduce == MAX:
+                m = np.where(inb & (d > m), d, m)
+            elif desc.reduce == MIN:
+                m = np.where(inb & (d < m), d, m)
+            else:
+                m = np.where(inb, m + d, m)
+            p = p + dn[None, :]
+    v = m
+    if desc.reduce == AVERAGE:
+        with np.errstate(all="ignore"):
+            v = m / np.maximum(n, 1).astype(f32)
+    return v, n, pixels
+
+
+def present(frag):
+    """vr_present_async's bytes (B, G, R, A) of fragments (..., 4): SrcAlpha / OneMinusSrcAlpha over white, unorm8."""
+    frag = np.asarray(frag, f32)
+    with np.errstate(all="ignore"):
+        a = frag[..., 3:4]
+        c = frag * a + f32(1.0) * (f32(1.0) - a)  # (r, g, b, alpha)
+        c = np.where(c > f32(0.0), c, f32(0.0))  # (NaN -> 0)
+        c = np.where(c > f32(1.0), f32(1.0), c)
+        q = np.floor(c * f32(255.0) + f32(0.5)).astype(np.uint8)
+    return np.stack([q[..., 2], q[..., 1], q[..., 0], q[..., 3]], -1)
+
+
+def slice_frame(desc, vec4, tf, fused=False):
+    """(image, counted samples, pixels with n > 0): float32 [H, W, 4] fragments, or uint8 [H, W, 4] for BGRA8."""
+    W, H = int(desc.width), int(desc.height)
+    opacity, color = (np.asarray(t, f32) for t in tf)
+    v, n, _ = reduce_slab(desc, vec4, fused=fused)
+    o, rgb = tf_lookup(opacity, color.reshape(-1, 4), v, fused)
+    dst = np.zeros((W * H, 4), f32)
+    pr._blend(rgb, o, dst, n > 0)
+    img = dst.reshape(H, W, 4)
+    if desc.format == BGRA8:
+        img = present(img)
+    return img, int(n.sum()), int((n > 0).sum())

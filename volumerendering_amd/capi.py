@@ -29,6 +29,9 @@ TILE = 64
 ARITH_SEPARATE, ARITH_FUSED = 0, 1
 OUTPUT_COLOR, OUTPUT_SURFACE = 0, 1  # Context.set_output (include/vr.h)
 MAX_VOLUMES = 3
+SLICE_MAX, SLICE_MIN, SLICE_AVERAGE = 0, 1, 2  # vr_slice_desc.reduce (include/vr.h)
+SLICE_LINEAR, SLICE_NEAREST = 0, 1              # vr_slice_desc.filter
+SLICE_RGBA32F, SLICE_BGRA8 = 0, 1               # vr_slice_desc.format
 
 # every symbol include/vr.h declares (tests check that the library exports each of them)
 ABI_SYMBOLS = [
@@ -45,6 +48,7 @@ ABI_SYMBOLS = [
     "vr_set_iso_value", "vr_set_shadows", "vr_shadow_volume",
     "vr_set_output", "vr_set_surface_threshold", "vr_surface_depth_async", "vr_pick",
     "vr_set_ray_bounds",
+    "vr_slice_async", "vr_slice_render", "vr_slice_orthogonal", "vr_slice_counters",
 ]
 
 
@@ -73,6 +77,24 @@ class PickResult(C.Structure):
         return dict(hit=int(self.hit), uvw=np.array(self.uvw, np.float32), world=np.array(self.world, np.float32),
                     depth=np.float32(self.depth), alpha=np.float32(self.alpha), voxel=np.array(self.voxel, np.int32),
                     value=np.array([list(v) for v in self.value], np.float32))
+
+
+class SliceDesc(C.Structure):
+    """struct vr_slice_desc (include/vr.h): a plane in texture space, its output size, slab, reduction, filter and format."""
+    _fields_ = [
+        ("volume_slot", C.c_int32), ("tf_slot", C.c_int32), ("width", C.c_uint32), ("height", C.c_uint32),
+        ("origin", C.c_float * 3), ("du", C.c_float * 3), ("dv", C.c_float * 3), ("dn", C.c_float * 3),
+        ("slab_steps", C.c_int32), ("reduce", C.c_int32), ("filter", C.c_int32), ("format", C.c_int32),
+    ]
+
+    def copy(self, **over) -> "SliceDesc":
+        """A copy with the given fields replaced (vectors from any sequence of three floats)."""
+        d = SliceDesc.from_buffer_copy(bytes(self))
+        for k, v in over.items():
+            if k in ("origin", "du", "dv", "dn"):
+                v = (C.c_float * 3)(*[float(x) for x in v])
+            setattr(d, k, v)
+        return d
 
 
 class VrError(RuntimeError):
@@ -151,6 +173,10 @@ def load() -> C.CDLL:
     lib.vr_surface_depth_async.argtypes = [vp, vp, vp, vp]
     lib.vr_pick.argtypes = [vp, i32, u32, u32, C.POINTER(PickResult)]
     lib.vr_set_ray_bounds.argtypes = [vp, vp, vp]
+    lib.vr_slice_async.argtypes = [vp, C.POINTER(SliceDesc), vp, vp]
+    lib.vr_slice_render.argtypes = [vp, C.POINTER(SliceDesc), vp]
+    lib.vr_slice_orthogonal.argtypes = [vp, i32, i32, i32, i32, C.POINTER(SliceDesc)]
+    lib.vr_slice_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
     lib.vr_present_async.argtypes = [vp, vp, vp, vp]
     lib.vr_present_tiles_async.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
     lib.vr_hint_frames_in_flight.argtypes = [vp, i32]
@@ -446,6 +472,31 @@ class Context:
         """vr_set_ray_bounds: BASIC / LIGHT colour launches enqueued after this call march only between the two depth buffers (device
         pointers to W*H floats each, the depth convention of surface_depth; None = no bound on that side, both None = off)."""
         self._chk(self.lib.vr_set_ray_bounds(self.h, d_near or None, d_far or None))
+
+    def slice_async(self, desc: SliceDesc, d_out: int, stream: int = 0):
+        """vr_slice_async: the slice `desc` into device memory d_out (width * height float4, or 32-bit words for SLICE_BGRA8) on
+        `stream`; nothing is synchronised."""
+        self._chk(self.lib.vr_slice_async(self.h, C.byref(desc), d_out, stream))
+
+    def slice(self, desc: SliceDesc) -> np.ndarray:
+        """vr_slice_render: the slice as float32[height, width, 4], or uint8[height, width, 4] (B, G, R, A) for SLICE_BGRA8."""
+        shape = (int(desc.height), int(desc.width), 4)
+        out = np.empty(shape, dtype=np.uint8 if desc.format == SLICE_BGRA8 else np.float32)
+        self._chk(self.lib.vr_slice_render(self.h, C.byref(desc), out.ctypes.data))
+        return out
+
+    def slice_orthogonal(self, slot: int, axis: int, index: int, thickness: int = 1) -> SliceDesc:
+        """vr_slice_orthogonal: the descriptor of the axis-aligned plane `axis` (0 x, 1 y, 2 z) at voxel `index` of volume `slot`,
+        one pixel per voxel, `thickness` voxels of slab centred on it (MAX, LINEAR, RGBA32F, TF slot 0: edit as needed)."""
+        d = SliceDesc()
+        self._chk(self.lib.vr_slice_orthogonal(self.h, slot, axis, index, thickness, C.byref(d)))
+        return d
+
+    def slice_counters(self):
+        """(counted samples, pixels with a counted sample, samples whose voxels were loaded) of the last slice launch."""
+        out = (C.c_uint64 * 3)()
+        self._chk(self.lib.vr_slice_counters(self.h, C.byref(out)))
+        return int(out[0]), int(out[1]), int(out[2])
 
     def set_volume_layout(self, mode: int):
         """0 bricked copy (default), 1 the reference's vec4 voxels only, 3 x-fastest voxels + density plane (2 was removed)."""

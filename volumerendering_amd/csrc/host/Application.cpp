@@ -89,6 +89,29 @@ int Application::OnResize(uint32_t width, uint32_t height)
     return rc;
 }
 
+int Application::Slice(const vr_slice_desc& desc, void* out_host)
+{
+    if (!p_Ctx) return VR_ERR_NOT_READY;
+    int rc = vr_slice_render(p_Ctx, &desc, out_host);
+    if (rc != VR_OK) m_Error = vr_last_error(p_Ctx);
+    return rc;
+}
+
+int Application::SliceThroughPick(const vr_pick_result& pick, int axis, int thickness, std::vector<float>& rgba, uint32_t* w, uint32_t* h)
+{
+    if (!p_Ctx) return VR_ERR_NOT_READY;
+    if (!pick.hit || axis < 0 || axis > 2) return VR_ERR_INVALID_ARG;
+    vr_slice_desc d;
+    int rc = vr_slice_orthogonal(p_Ctx, 0, axis, pick.voxel[axis], thickness, &d);
+    if (rc != VR_OK) return rc;
+    rgba.resize((size_t)d.width * d.height * 4);
+    rc = Slice(d, rgba.data());
+    if (rc != VR_OK) return rc;
+    if (w) *w = d.width;
+    if (h) *h = d.height;
+    return VR_OK;
+}
+
 int Application::Pick(uint32_t x, uint32_t y, vr_pick_result* out)
 {
     if (!p_Ctx || !p_App) return VR_ERR_NOT_READY;

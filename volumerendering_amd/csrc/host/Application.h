@@ -47,6 +47,13 @@ public:
     // its depth, the voxel and the values of every volume there).  Scenes drawn as BASIC, LIGHT or ISO; any other returns
     // VR_ERR_UNSUPPORTED.  The frame of the last OnRender and its counters stay what they were.
     int Pick(uint32_t x, uint32_t y, vr_pick_result* out);
+    // A slice view of one of the scene's volumes (vr_slice_render: a plane in texture space, any output size, any slot) into host
+    // memory: desc.width * desc.height float4, or 32-bit words for VR_SLICE_BGRA8.  The frame of the last OnRender and its counters stay.
+    int Slice(const vr_slice_desc& desc, void* out_host);
+    // The axis-aligned plane `axis` (0 x, 1 y, 2 z) through the voxel under a picked pixel (pick.voxel of volume slot 0), `thickness`
+    // voxels of maximum-intensity slab around it, through TF slot 0: rgba = *w x *h float4, one pixel per voxel.  A pick without a
+    // hit returns VR_ERR_INVALID_ARG.
+    int SliceThroughPick(const vr_pick_result& pick, int axis, int thickness, std::vector<float>& rgba, uint32_t* w, uint32_t* h);
     // the accumulated opacity at which the unlit / lit scene's surface lies (vr_set_surface_threshold: finite, 0 <= tau < 1)
     int SetSurfaceThreshold(float tau);
 

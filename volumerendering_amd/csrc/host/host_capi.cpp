@@ -348,6 +348,25 @@ int vrh_app_set_shadows(void* a, int divisor, float scale)
 }
 // Application::Pick / SetSurfaceThreshold (vr_pick, vr_set_surface_threshold of the application's context)
 int vrh_app_pick(void* a, uint32_t x, uint32_t y, vr_pick_result* out) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->Pick(x, y, out); }) }
+// Application::Slice / SliceThroughPick (vr_slice_render of the application's context); the latter into rgba[capacity] floats:
+// returns the number of floats the slice has (w * h * 4; nothing is copied when capacity is smaller) or a negative vr_status
+int vrh_app_slice(void* a, const vr_slice_desc* d, void* out_host)
+{
+    if (!d || !out_host) return VR_ERR_INVALID_ARG;
+    VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->Slice(*d, out_host); })
+}
+long long vrh_app_slice_through_pick(void* a, const vr_pick_result* pick, int axis, int thickness, float* rgba, size_t capacity, uint32_t* w,
+                                     uint32_t* h)
+{
+    if (!pick) return VR_ERR_INVALID_ARG;
+    VRH_TRY(VR_ERR_HIP, {
+        std::vector<float> px;
+        const int rc = static_cast<Application*>(a)->SliceThroughPick(*pick, axis, thickness, px, w, h);
+        if (rc != VR_OK) return rc;
+        if (rgba && capacity >= px.size()) std::memcpy(rgba, px.data(), px.size() * sizeof(float));
+        return (long long)px.size();
+    })
+}
 int vrh_app_set_surface_threshold(void* a, float tau) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->SetSurfaceThreshold(tau); }) }
 void vrh_app_set_prepare_on_device(void* a, int on) { static_cast<Application*>(a)->m_PrepareOnDevice = on != 0; }
 int vrh_app_update(void* a) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->OnUpdate(); }) }

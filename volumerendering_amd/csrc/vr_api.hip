@@ -8,6 +8,7 @@
 namespace vrf {
 void launch_march(const vr::LaunchDesc& L, hipStream_t s, const vr::MarchBatch& B);
 void launch_shadow_build(const vr::MarchParams& P, float* out, float sigma, bool skip, bool off32, hipStream_t s);
+void launch_slice(const vr::SliceParams& S, int reduce, bool nearest, bool off32, bool skip, unsigned tiles, hipStream_t s);
 }
 
 #include <cmath>
@@ -215,14 +216,24 @@ struct vr_ctx {
                               // onto small volumes by the tests; 0 = what the hardware reaches, just below 4 GiB)
     double active_fraction = 1.0;  // share of bricks that are not inert, of the distance field in use
     float abox[6] = {-3.0e38f, -3.0e38f, -3.0e38f, 3.0e38f, 3.0e38f, 3.0e38f};  // uvw box around the active bricks of that field (MarchParams::abox)
-    // Intensity projections (vr_proj.h) and the isosurface (vr_iso.h): (min, max) of volume 0 per empty-space brick and over the whole
-    // volume, rebuilt on the launch's stream by the first skipping projection or isosurface launch after a volume change (proj_epoch = the
-    // brick_epoch they were built at).  Launches on other streams wait once for the event behind the build (proj_built).
-    float2* proj_rec = nullptr;
-    size_t proj_rec_cap = 0;  // bytes
-    float2* proj_range = nullptr;
-    unsigned long long proj_epoch = ~0ull;
-    BuiltOn proj_built;
+    // Intensity projections (vr_proj.h), the isosurface (vr_iso.h) and slice views (vr_slice.h): (min, max) of a volume slot per
+    // empty-space brick and over the whole volume, kept per slot ([0]: what the projections and the isosurface read), rebuilt on the
+    // launch's stream by the first skipping launch that reads them after a volume change (proj_epoch = the brick_epoch they were built
+    // at).  Launches on other streams wait once for the event behind the build (proj_built).
+    float2* proj_rec[VR_MAX_VOLUMES] = {};
+    size_t proj_rec_cap[VR_MAX_VOLUMES] = {};  // bytes
+    float2* proj_range[VR_MAX_VOLUMES] = {};
+    unsigned long long proj_epoch[VR_MAX_VOLUMES] = {~0ull, ~0ull, ~0ull};
+    BuiltOn proj_built[VR_MAX_VOLUMES];
+    // Slice views (vr_slice_async): the wavefront records of the slice launches, one buffer per record slot (a slice takes a record
+    // slot like every launch, and leaves the march launches' records, counters and timings alone), and which of them the last
+    // slice wrote (vr_slice_counters)
+    unsigned long long* d_slice_counts[kInFlight] = {};
+    size_t slice_counts_cap[kInFlight] = {};  // in workgroups
+    int slice_buf = -1;
+    unsigned slice_tiles = 0;
+    void* d_slice_out = nullptr;  // vr_slice_render's device output (grown on demand)
+    size_t slice_out_cap = 0;     // bytes
     bool last_unmeasured = false;  // the last launch's family is never measured (KernelForm::measured): vr_kernel_choice reports no candidates
     float iso = 0.5f;        // VR_VARIANT_ISO's level (vr_set_iso_value), copied into MarchParams::iso at enqueue
     // Shadows of the lit shader (vr_set_shadows, vr_shadow.h): the setting, and a ring of light volumes, one per key.  A launch whose key
@@ -623,23 +634,28 @@ int check_render_args(vr_ctx* c, int variant, int rank, int world, int n_frames,
 
 // The parameters of a launch that no kernel form changes; the volumes as the vec4 voxels and their density plane (the bricked copies
 // replace them in use_bricked_copies).
+// volume slot i as the vec4 voxels and their density plane
+DevVolume linear_volume(const vr_ctx* c, int i)
+{
+    DevVolume v = c->vol[i];
+    const bool plane = c->layout_mode != 1 && c->vol_dens[i] && c->vol[i].data;
+    v.dens = plane ? c->vol_dens[i] : nullptr;
+    v.a_base = plane ? reinterpret_cast<const char*>(c->vol_dens[i]) : reinterpret_cast<const char*>(c->vol[i].data) + 12;
+    v.a_shift = plane ? 2 : 4;
+    v.bricked = 0;
+    v.brick_row = v.brick_slab = 0;
+    const size_t lin_bytes = c->vol_bytes[i];
+    v.data_bytes = lin_bytes > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)lin_bytes;
+    return v;
+}
+
 void fill_launch_params(const vr_ctx* c, MarchParams& P, const vr_uniforms& u0, int rank, int world, bool packed)
 {
     std::memset(&P, 0, sizeof P);
     P.W = (int)c->W;
     P.H = (int)c->H;
     fill_frame_params(P, u0);
-    for (int i = 0; i < VR_MAX_VOLUMES; ++i) {
-        P.vol[i] = c->vol[i];
-        const bool plane = c->layout_mode != 1 && c->vol_dens[i] && c->vol[i].data;
-        P.vol[i].dens = plane ? c->vol_dens[i] : nullptr;
-        P.vol[i].a_base = plane ? reinterpret_cast<const char*>(c->vol_dens[i]) : reinterpret_cast<const char*>(c->vol[i].data) + 12;
-        P.vol[i].a_shift = plane ? 2 : 4;
-        P.vol[i].bricked = 0;
-        P.vol[i].brick_row = P.vol[i].brick_slab = 0;
-        const size_t lin_bytes = c->vol_bytes[i];
-        P.vol[i].data_bytes = lin_bytes > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)lin_bytes;
-    }
+    for (int i = 0; i < VR_MAX_VOLUMES; ++i) P.vol[i] = linear_volume(c, i);
     for (int i = 0; i < VR_MAX_TFS; ++i) P.tf[i] = c->tf[i];
     P.rank = rank;
     P.world = world;
@@ -652,20 +668,22 @@ void fill_launch_params(const vr_ctx* c, MarchParams& P, const vr_uniforms& u0, 
 }
 
 // the bricked copies (layout 0) are what the gathers read
+void use_bricked_copy(const vr_ctx* c, int i, DevVolume& v)
+{
+    if (!c->vol[i].data || !c->vol_bricked[i] || !c->vol_bdens[i]) return;
+    const BrickedGrid g = bricked_grid(c->vol[i]);
+    if (g.slots > 0xFFFFFFFFull) return;  // (indices are 32 bits)
+    v.data = c->vol_bricked[i];
+    v.a_base = reinterpret_cast<const char*>(c->vol_bdens[i]);
+    v.a_shift = 2;
+    v.bricked = 1;
+    v.brick_row = g.nbx * kVbN;
+    v.brick_slab = g.nbx * g.nby * kVbN;
+    v.data_bytes = g.slots * 16 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)(g.slots * 16);
+}
 void use_bricked_copies(const vr_ctx* c, MarchParams& P)
 {
-    for (int i = 0; i < VR_MAX_VOLUMES; ++i) {
-        if (!c->vol[i].data || !c->vol_bricked[i] || !c->vol_bdens[i]) continue;
-        const BrickedGrid g = bricked_grid(c->vol[i]);
-        if (g.slots > 0xFFFFFFFFull) continue;  // (indices are 32 bits)
-        P.vol[i].data = c->vol_bricked[i];
-        P.vol[i].a_base = reinterpret_cast<const char*>(c->vol_bdens[i]);
-        P.vol[i].a_shift = 2;
-        P.vol[i].bricked = 1;
-        P.vol[i].brick_row = g.nbx * kVbN;
-        P.vol[i].brick_slab = g.nbx * g.nby * kVbN;
-        P.vol[i].data_bytes = g.slots * 16 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)(g.slots * 16);
-    }
+    for (int i = 0; i < VR_MAX_VOLUMES; ++i) use_bricked_copy(c, i, P.vol[i]);
 }
 
 // What a launch could run, worked out once before the kernel choice (choose_flavour).
@@ -748,7 +766,7 @@ void drained(vr_ctx* c)
     c->retired_dev.clear();
     c->retired_host.clear();
     c->drained_gen = c->edit_gen;
-    c->proj_built.pending = false;
+    for (auto& b : c->proj_built) b.pending = false;
     for (auto& e : c->shadow) e.built.pending = false;
 }
 
@@ -780,13 +798,17 @@ int wait_for_edits(vr_ctx* c, hipStream_t s)
 }
 
 // The launches' reads of the current generations (enqueued as launch order_seq, whose slot event is recorded behind it).
+void mark_table_reads(vr_ctx* c, int slot)
+{
+    for (int k = 0; k < 2; ++k) {
+        GenBuf& b = c->tf_buf[slot][k][c->tf_cur[slot][k]];
+        if (b.d) b.reader[c->order_seq % kInFlight] = (long long)c->order_seq;
+    }
+}
+
 void mark_reads(vr_ctx* c, const MarchParams& P)
 {
-    for (int i = 0; i < VR_MAX_TFS; ++i)
-        for (int k = 0; k < 2; ++k) {
-            GenBuf& b = c->tf_buf[i][k][c->tf_cur[i][k]];
-            if (b.d) b.reader[c->order_seq % kInFlight] = (long long)c->order_seq;
-        }
+    for (int i = 0; i < VR_MAX_TFS; ++i) mark_table_reads(c, i);
     if (P.brick_dist) c->field[c->field_cur].reader[c->order_seq % kInFlight] = (long long)c->order_seq;
     if (c->shadow_cur >= 0) c->shadow[c->shadow_cur].buf.reader[c->order_seq % kInFlight] = (long long)c->order_seq;
 }
@@ -927,41 +949,48 @@ int prepare_skip(vr_ctx* c, int variant, hipStream_t s, MarchParams& P)
     return VR_OK;
 }
 
-// The skipping projection (flavour 19) and isosurface (21): fills P's brick fields with volume 0's range records, (re)builds them and the whole volume's range
-// on `s` when a volume changed since they were built (no host wait), and orders a launch on another stream behind that build once.
-// Returns the whole volume's range (device), or nullptr after a failure (c->err says why).
-const float2* prepare_proj(vr_ctx* c, hipStream_t s, MarchParams& P)
+// The range records of volume slot `slot` (bn bricks per axis): (re)builds them and the whole volume's range on `s` when a volume
+// changed since they were built (no host wait), and orders a launch on another stream behind that build once.  *rec = the records,
+// the return value the whole volume's range (both device), or nullptr after a failure (c->err says why).
+const float2* prepare_range(vr_ctx* c, hipStream_t s, int slot, int bnx, int bny, int bnz, const float2** rec)
 {
-    const DevVolume& v = c->vol[0];
-    fill_brick_grid(P, 0, v);
-    const size_t nb = (size_t)P.bnx * P.bny * P.bnz;
-    if (c->proj_epoch != c->brick_epoch || !c->proj_rec || !c->proj_range) {
+    const DevVolume& v = c->vol[slot];
+    const size_t nb = (size_t)bnx * bny * bnz;
+    BuiltOn& built = c->proj_built[slot];
+    if (c->proj_epoch[slot] != c->brick_epoch || !c->proj_rec[slot] || !c->proj_range[slot]) {
         // (a volume change drained the device: nothing in flight reads the records; a smaller buffer is retired all the same)
-        if (grow(c, (void**)&c->proj_rec, &c->proj_rec_cap, nb * sizeof(float2), false)) return nullptr;
-        if (!c->proj_range && hipMalloc(&c->proj_range, sizeof(float2)) != hipSuccess) {
-            c->proj_range = nullptr;
+        if (grow(c, (void**)&c->proj_rec[slot], &c->proj_rec_cap[slot], nb * sizeof(float2), false)) return nullptr;
+        if (!c->proj_range[slot] && hipMalloc(&c->proj_range[slot], sizeof(float2)) != hipSuccess) {
+            c->proj_range[slot] = nullptr;
             fail(c, VR_ERR_OOM, "vr_render: no memory for the projection's volume range");
             return nullptr;
         }
-        if (!c->proj_built.ev && hipEventCreateWithFlags(&c->proj_built.ev, hipEventDisableTiming) != hipSuccess) {
-            c->proj_built.ev = nullptr;
+        if (!built.ev && hipEventCreateWithFlags(&built.ev, hipEventDisableTiming) != hipSuccess) {
+            built.ev = nullptr;
             fail(c, VR_ERR_HIP, "vr_render: hipEventCreateWithFlags failed");
             return nullptr;
         }
-        hipLaunchKernelGGL(brick_range_kernel, dim3((unsigned)nb), dim3(64), 0, s, v.data, v.nx, v.ny, v.nz, P.bnx, P.bny, c->proj_rec);
-        hipLaunchKernelGGL(range_reduce_kernel, dim3(1), dim3(1024), 0, s, (const float2*)c->proj_rec, (int)nb, c->proj_range);
-        if (hipGetLastError() != hipSuccess || hipEventRecord(c->proj_built.ev, s) != hipSuccess) {
+        hipLaunchKernelGGL(brick_range_kernel, dim3((unsigned)nb), dim3(64), 0, s, v.data, v.nx, v.ny, v.nz, bnx, bny, c->proj_rec[slot]);
+        hipLaunchKernelGGL(range_reduce_kernel, dim3(1), dim3(1024), 0, s, (const float2*)c->proj_rec[slot], (int)nb, c->proj_range[slot]);
+        if (hipGetLastError() != hipSuccess || hipEventRecord(built.ev, s) != hipSuccess) {
             fail(c, VR_ERR_HIP, "vr_render: the projection's brick ranges could not be enqueued");
             return nullptr;
         }
-        c->proj_epoch = c->brick_epoch;
-        c->proj_built.built(s);
-    } else if (c->proj_built.order_behind(s) != hipSuccess) {
+        c->proj_epoch[slot] = c->brick_epoch;
+        built.built(s);
+    } else if (built.order_behind(s) != hipSuccess) {
         fail(c, VR_ERR_HIP, "vr_render: hipStreamWaitEvent failed");
         return nullptr;
     }
-    P.bricks = c->proj_rec;
-    return c->proj_range;
+    *rec = c->proj_rec[slot];
+    return c->proj_range[slot];
+}
+
+// The skipping projection (flavour 19) and isosurface (21): fills P's brick fields with volume 0's range records (prepare_range).
+const float2* prepare_proj(vr_ctx* c, hipStream_t s, MarchParams& P)
+{
+    fill_brick_grid(P, 0, c->vol[0]);
+    return prepare_range(c, s, 0, P.bnx, P.bny, P.bnz, &P.bricks);
 }
 
 // Shadows (vr_set_shadows): the key of the light volume a LIGHT frame with uniforms u reads, and the light volume's grid (texels per axis).
@@ -1841,9 +1870,14 @@ void vr_destroy(vr_ctx* c)
         if (c->vol_bdens[i]) (void)hipFree(c->vol_bdens[i]);
     }
     if (c->merged_bricks) (void)hipFree(c->merged_bricks);
-    if (c->proj_rec) (void)hipFree(c->proj_rec);
-    if (c->proj_range) (void)hipFree(c->proj_range);
-    if (c->proj_built.ev) (void)hipEventDestroy(c->proj_built.ev);
+    for (int i = 0; i < VR_MAX_VOLUMES; ++i) {
+        if (c->proj_rec[i]) (void)hipFree(c->proj_rec[i]);
+        if (c->proj_range[i]) (void)hipFree(c->proj_range[i]);
+        if (c->proj_built[i].ev) (void)hipEventDestroy(c->proj_built[i].ev);
+    }
+    for (auto* b : c->d_slice_counts)
+        if (b) (void)hipFree(b);
+    if (c->d_slice_out) (void)hipFree(c->d_slice_out);
     for (auto& e : c->shadow) {
         if (e.buf.d) (void)hipFree(e.buf.d);
         if (e.built.ev) (void)hipEventDestroy(e.built.ev);
@@ -2691,6 +2725,168 @@ int vr_pick(vr_ctx* c, int variant, uint32_t x, uint32_t y, vr_pick_result* out)
     for (int i = 0; i < VR_MAX_VOLUMES; ++i)
         if (c->vol[i].data && c->vol[i].nx == n0[0] && c->vol[i].ny == n0[1] && c->vol[i].nz == n0[2])
             VR_HIP(c, hipMemcpy(out->value[i], c->vol[i].data + v, sizeof(float4), hipMemcpyDeviceToHost));
+    return VR_OK;
+}
+
+namespace {
+
+// the descriptor's own fields (VR_ERR_INVALID_ARG), then what the context must hold (VR_ERR_NOT_READY)
+int check_slice(vr_ctx* c, const vr_slice_desc* d, const void* out, const char* who)
+{
+    const std::string w(who);
+    if (!d || !out) return fail(c, VR_ERR_INVALID_ARG, w + ": the descriptor or the output is NULL");
+    if (d->volume_slot < 0 || d->volume_slot >= VR_MAX_VOLUMES) return fail(c, VR_ERR_INVALID_ARG, w + ": bad volume slot");
+    if (d->tf_slot < 0 || d->tf_slot >= VR_MAX_TFS) return fail(c, VR_ERR_INVALID_ARG, w + ": bad TF slot");
+    if (d->width < 1 || d->width > 16384 || d->height < 1 || d->height > 16384)
+        return fail(c, VR_ERR_INVALID_ARG, w + ": the output must be 1 .. 16384 pixels each way");
+    if (d->slab_steps < 1 || d->slab_steps > 65536) return fail(c, VR_ERR_INVALID_ARG, w + ": slab_steps must be 1 .. 65536");
+    if (d->reduce != VR_SLICE_MAX && d->reduce != VR_SLICE_MIN && d->reduce != VR_SLICE_AVERAGE)
+        return fail(c, VR_ERR_INVALID_ARG, w + ": unknown reduction");
+    if (d->filter != VR_SLICE_LINEAR && d->filter != VR_SLICE_NEAREST) return fail(c, VR_ERR_INVALID_ARG, w + ": unknown filter");
+    if (d->format != VR_SLICE_RGBA32F && d->format != VR_SLICE_BGRA8) return fail(c, VR_ERR_INVALID_ARG, w + ": unknown format");
+    if (!c->vol[d->volume_slot].data) return fail(c, VR_ERR_NOT_READY, w + ": volume slot " + std::to_string(d->volume_slot) + " is empty");
+    if (!c->tf[d->tf_slot].opacity || !c->tf[d->tf_slot].color)
+        return fail(c, VR_ERR_NOT_READY, w + ": TF slot " + std::to_string(d->tf_slot) + " is empty");
+    return VR_OK;
+}
+
+// One slice launch on `s` (the descriptor has been checked).  It takes the next record slot -- so it is one of the kInFlight launches
+// in flight, and its slot's event is what reuse_wait orders a later table edit behind -- but writes records of its own
+// (d_slice_counts) and touches none of the march launches' bookkeeping: counters, last flavour, timings, kernel choice, launch order.
+int enqueue_slice(vr_ctx* c, const vr_slice_desc& d, void* d_out, hipStream_t s)
+{
+    VR_HIP(c, hipSetDevice(c->device));
+    (void)hipGetLastError();
+    if (const int rc = wait_for_edits(c, s)) return rc;
+    const int vs = d.volume_slot;
+    SliceParams S;
+    std::memset(&S, 0, sizeof S);
+    S.vol = linear_volume(c, vs);
+    if (c->layout_mode == 0) use_bricked_copy(c, vs, S.vol);
+    bool off32 = c->vol_bytes[vs] <= 0xFFFFFFFFull;
+    if (S.vol.bricked && bricked_grid(S.vol).slots * 16 > 0xFFFFFFFFull) off32 = false;
+    S.tf = c->tf[d.tf_slot];
+    for (int a = 0; a < 3; ++a) {
+        S.origin[a] = d.origin[a];
+        S.du[a] = d.du[a];
+        S.dv[a] = d.dv[a];
+        S.dn[a] = d.dn[a];
+    }
+    S.width = (int)d.width;
+    S.height = (int)d.height;
+    S.tiles_x = (int)((d.width + 7u) / 8u);
+    S.slab_steps = d.slab_steps;
+    S.format = d.format;
+    S.out = d_out;
+    const unsigned tiles = (unsigned)S.tiles_x * ((d.height + 7u) / 8u);
+    // exact skipping by the slot's range records, unless flavour 1 asks for the plain form (the kernels index bricks with 24-bit
+    // multiplies and 32-bit byte offsets, as every skipping kernel)
+    const DevVolume& v = c->vol[vs];
+    S.bnx = skip_bricks(v.nx);
+    S.bny = skip_bricks(v.ny);
+    S.bnz = skip_bricks(v.nz);
+    S.bsx = (float)v.nx * kBrickInv;
+    S.bsy = (float)v.ny * kBrickInv;
+    S.bsz = (float)v.nz * kBrickInv;
+    const int requested = c->flavour == 0 ? c->default_flavour : c->flavour;
+    const bool skip = requested != 1 && (long long)S.bnx * S.bny < (1 << 23);
+    if (skip) {
+        S.vrange = prepare_range(c, s, vs, S.bnx, S.bny, S.bnz, &S.bricks);
+        if (!S.vrange) return VR_ERR_HIP;
+    }
+    // the record slot: the launch that used it last has finished (host wait: the bound on launches in flight); the sort that read that
+    // launch's records is waited for on the stream, so that whoever takes the slot next may write them behind this launch's event
+    int cb;
+    const vr_ctx::OrderSlot* slot_sort;
+    if (const int rc = take_record_slot(c, s, 0, &cb, &slot_sort)) return rc;
+    if (slot_sort) VR_HIP(c, hipStreamWaitEvent(s, slot_sort->sorted, 0));
+    if (tiles > c->slice_counts_cap[cb]) {
+        if (c->d_slice_counts[cb]) (void)hipFree(c->d_slice_counts[cb]);  // (its last slice has finished: the slot's event, above)
+        c->d_slice_counts[cb] = nullptr;
+        c->slice_counts_cap[cb] = 0;
+        VR_HIP(c, hipMalloc(&c->d_slice_counts[cb], (size_t)tiles * 3 * sizeof(unsigned long long)));
+        c->slice_counts_cap[cb] = tiles;
+    }
+    S.counts = c->d_slice_counts[cb];
+    if (c->arith == VR_ARITH_FUSED) vrf::launch_slice(S, d.reduce, d.filter == VR_SLICE_NEAREST, off32, skip, tiles, s);
+    else vr::launch_slice(S, d.reduce, d.filter == VR_SLICE_NEAREST, off32, skip, tiles, s);
+    VR_HIP(c, hipGetLastError());
+    mark_table_reads(c, d.tf_slot);
+    VR_HIP(c, hipEventRecord(c->slot_done[cb], s));
+    c->slot_used[cb] = true;
+    ++c->order_seq;
+    c->slice_buf = cb;
+    c->slice_tiles = tiles;
+    return VR_OK;
+}
+
+}  // namespace
+
+int vr_slice_async(vr_ctx* c, const vr_slice_desc* desc, void* d_out, void* stream)
+{
+    if (!c) return VR_ERR_INVALID_ARG;
+    if (const int rc = check_slice(c, desc, d_out, "vr_slice_async")) return rc;
+    return enqueue_slice(c, *desc, d_out, stream ? (hipStream_t)stream : c->stream);
+}
+
+int vr_slice_render(vr_ctx* c, const vr_slice_desc* desc, void* out_host)
+{
+    if (!c) return VR_ERR_INVALID_ARG;
+    if (const int rc = check_slice(c, desc, out_host, "vr_slice_render")) return rc;
+    VR_HIP(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)desc->width * desc->height * (desc->format == VR_SLICE_BGRA8 ? 4u : 16u);
+    // (the buffer's earlier uses were synchronous on this stream; a smaller one is freed by the next draining call)
+    if (const int rc = grow(c, &c->d_slice_out, &c->slice_out_cap, bytes, false)) return rc;
+    if (const int rc = enqueue_slice(c, *desc, c->d_slice_out, c->stream)) return rc;
+    VR_HIP(c, hipMemcpyAsync(out_host, c->d_slice_out, bytes, hipMemcpyDeviceToHost, c->stream));
+    VR_HIP(c, hipStreamSynchronize(c->stream));
+    return VR_OK;
+}
+
+int vr_slice_orthogonal(const vr_ctx* c, int slot, int axis, int index, int thickness, vr_slice_desc* out)
+{
+    if (!c || !out) return VR_ERR_INVALID_ARG;
+    if (slot < 0 || slot >= VR_MAX_VOLUMES || axis < 0 || axis > 2 || thickness < 1 || thickness > 65536) return VR_ERR_INVALID_ARG;
+    if (!c->vol[slot].data) return VR_ERR_NOT_READY;
+    const int n[3] = {c->vol[slot].nx, c->vol[slot].ny, c->vol[slot].nz};
+    if (index < 0 || index >= n[axis]) return VR_ERR_INVALID_ARG;
+    const int ua = axis == 0 ? 1 : 0, va = axis == 2 ? 1 : 2;  // the output's x / y axes: (y, z), (x, z), (x, y)
+    std::memset(out, 0, sizeof *out);
+    out->volume_slot = slot;
+    out->tf_slot = 0;
+    out->width = (uint32_t)n[ua];
+    out->height = (uint32_t)n[va];
+    out->origin[ua] = 0.5f / (float)n[ua];
+    out->origin[va] = 0.5f / (float)n[va];
+    out->origin[axis] = ((float)(index - (thickness - 1) / 2) + 0.5f) / (float)n[axis];
+    out->du[ua] = 1.0f / (float)n[ua];
+    out->dv[va] = 1.0f / (float)n[va];
+    out->dn[axis] = 1.0f / (float)n[axis];
+    out->slab_steps = thickness;
+    out->reduce = VR_SLICE_MAX;
+    out->filter = VR_SLICE_LINEAR;
+    out->format = VR_SLICE_RGBA32F;
+    return VR_OK;
+}
+
+int vr_slice_counters(vr_ctx* c, uint64_t out[3])
+{
+    if (!c) return VR_ERR_INVALID_ARG;
+    if (!out) return fail(c, VR_ERR_INVALID_ARG, "vr_slice_counters: out is NULL");
+    out[0] = out[1] = out[2] = 0;
+    if (c->slice_buf < 0) return VR_OK;
+    VR_HIP(c, hipSetDevice(c->device));
+    (void)hipGetLastError();
+    // the event behind the slice (or behind a later launch in its record slot), then the context's own stream: the caller's may be gone
+    VR_HIP(c, hipEventSynchronize(c->slot_done[c->slice_buf]));
+    // (d_counters: every use of it is synchronous on the context's stream, as this one)
+    hipLaunchKernelGGL(slice_sum_kernel, dim3(1), dim3(1024), 0, c->stream, (const unsigned long long*)c->d_slice_counts[c->slice_buf],
+                       c->slice_tiles, c->d_counters);
+    VR_HIP(c, hipGetLastError());
+    unsigned long long h[3] = {0, 0, 0};
+    VR_HIP(c, hipMemcpyAsync(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    VR_HIP(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < 3; ++i) out[i] = h[i];
     return VR_OK;
 }
 

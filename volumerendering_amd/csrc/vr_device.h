@@ -141,6 +141,24 @@ struct MarchBatch {
     unsigned n_frames;
 };
 
+// Kernel argument block of a slice view (slice_kernel, vr_slice.h; vr_slice_desc of include/vr.h): passed by value.  A slice has
+// a geometry of its own -- a plane in texture space, any output size, any volume and TF slot -- and reads nothing of MarchParams.
+struct SliceParams {
+    DevVolume vol;           // the sliced slot, in the layout in use
+    DevTF tf;                // the TF slot
+    float origin[3], du[3], dv[3], dn[3];
+    int width, height;       // of the output
+    int tiles_x;             // 8x8 pixel tiles per row: workgroup t works on tile (t % tiles_x, t / tiles_x)
+    int slab_steps;
+    int format;              // VR_SLICE_RGBA32F: float4 per pixel, VR_SLICE_BGRA8: the presented 32-bit word
+    const float2* bricks;    // SKIP: (min, max) of the slot's .a per empty-space brick ...
+    const float2* vrange;    // ... and over the whole volume (vr_proj.h)
+    int bnx, bny, bnz;       // bricks per axis
+    float bsx, bsy, bsz;     // n / kBrickCells per axis (exact in f32)
+    void* out;               // width * height pixels, row-major
+    unsigned long long* counts;  // [workgroups][3]: counted samples, pixels with a sample, samples loaded
+};
+
 // Work queue of the persistent-wavefront kernel (vr_pw.h): eight heads, one per class of the workgroup index modulo 8,
 // zero at launch; heads[c * 64] counts the items of class c handed out beyond every wavefront's first.
 struct PwQueue {

@@ -30,6 +30,8 @@
 #include "vr_surf.h"
 // Per-pixel ray bounds of the unlit / lit shader (flavours 27 and 28; MarchParams::vol[1].data / vol[2].data = the depth buffers)
 #include "vr_bound.h"
+// Slice views of any volume slot (vr_slice_async): a kernel with a parameter struct of its own, outside launch_march
+#include "vr_slice.h"
 
 #include <type_traits>
 
@@ -127,6 +129,19 @@ void launch_shadow_build(const MarchParams& P, float* out, float sigma, bool ski
     const unsigned blocks = (((unsigned)P.vol[1].nx + 3u) >> 2) * (((unsigned)P.vol[1].ny + 3u) >> 2) * (((unsigned)P.vol[1].nz + 3u) >> 2);
     with_flags([&](auto S, auto O) { hipLaunchKernelGGL((shadow_build_kernel<O, S>), dim3(blocks), dim3(64), 0, s, P, out, sigma); }, skip,
                off32);
+}
+
+// a slice view (vr_slice.h): reduction x filter x addressing x skipping; one workgroup of one wavefront per 8x8 pixel tile
+void launch_slice(const SliceParams& S, int reduce, bool nearest, bool off32, bool skip, unsigned tiles, hipStream_t s)
+{
+    auto launch = [&](auto r) {
+        constexpr int R = decltype(r)::value;
+        with_flags([&](auto N, auto O, auto K) { hipLaunchKernelGGL((slice_kernel<R, N, O, K>), dim3(tiles), dim3(64), 0, s, S); }, nearest, off32,
+                   skip);
+    };
+    if (reduce == VR_SLICE_MAX) launch(std::integral_constant<int, kProjMax>{});
+    else if (reduce == VR_SLICE_MIN) launch(std::integral_constant<int, kProjMin>{});
+    else launch(std::integral_constant<int, kProjAvg>{});
 }
 
 void launch_march(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)

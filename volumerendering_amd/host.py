@@ -60,7 +60,9 @@ def load() -> C.CDLL:
         "vrh_app_create": (vp, [u32, u32, i32]), "vrh_app_free": (None, [vp]), "vrh_app_ok": (i32, [vp]),
         "vrh_app_error": (C.c_char_p, [vp]), "vrh_app_context": (vp, [vp]), "vrh_app_camera": (vp, [vp]),
         "vrh_app_start": (i32, [vp, i32, vp, vp, vp, i32]), "vrh_app_set_prepare_on_device": (None, [vp, i32]), "vrh_app_set_iso_value": (i32, [vp, f32]), "vrh_app_set_shadows": (i32, [vp, i32, f32]),
-        "vrh_app_pick": (i32, [vp, u32, u32, C.POINTER(capi.PickResult)]), "vrh_app_set_surface_threshold": (i32, [vp, f32]), "vrh_app_update": (i32, [vp]), "vrh_app_render": (i32, [vp]),
+        "vrh_app_pick": (i32, [vp, u32, u32, C.POINTER(capi.PickResult)]),
+        "vrh_app_slice": (i32, [vp, C.POINTER(capi.SliceDesc), vp]),
+        "vrh_app_slice_through_pick": (C.c_longlong, [vp, C.POINTER(capi.PickResult), i32, i32, vp, C.c_size_t, C.POINTER(u32), C.POINTER(u32)]), "vrh_app_set_surface_threshold": (i32, [vp, f32]), "vrh_app_update": (i32, [vp]), "vrh_app_render": (i32, [vp]),
         "vrh_app_resize": (i32, [vp, u32, u32]), "vrh_app_read_frame": (i32, [vp, vp, vp, C.POINTER(u64)]),
         "vrh_app_set_params": (None, [vp, i32, i32, f32, vp, vp]),
         "vrh_app_get_stepping": (None, [vp, C.POINTER(i32), C.POINTER(f32)]),
@@ -455,6 +457,23 @@ class Application:
         out = capi.PickResult()
         self._chk(self.lib.vrh_app_pick(self.h, x, y, C.byref(out)))
         return out
+
+    def slice(self, desc: capi.SliceDesc) -> np.ndarray:
+        """Application::Slice: a slice view of one of the scene's volumes (include/vr.h vr_slice_render) as float32[h, w, 4], or
+        uint8[h, w, 4] for SLICE_BGRA8; the frame of the last OnRender stays."""
+        out = np.empty((int(desc.height), int(desc.width), 4), dtype=np.uint8 if desc.format == capi.SLICE_BGRA8 else np.float32)
+        self._chk(self.lib.vrh_app_slice(self.h, C.byref(desc), out.ctypes.data))
+        return out
+
+    def slice_through_pick(self, pick: capi.PickResult, axis: int, thickness: int = 1) -> np.ndarray:
+        """Application::SliceThroughPick: the axis-aligned plane (0 x, 1 y, 2 z) through the picked voxel of volume slot 0, a
+        maximum-intensity slab of `thickness` voxels through TF slot 0, as float32[h, w, 4] (one pixel per voxel)."""
+        w, h = C.c_uint32(0), C.c_uint32(0)
+        n = self.lib.vrh_app_slice_through_pick(self.h, C.byref(pick), axis, thickness, None, 0, C.byref(w), C.byref(h))
+        self._chk(n)
+        out = np.empty(n, dtype=np.float32)
+        self._chk(self.lib.vrh_app_slice_through_pick(self.h, C.byref(pick), axis, thickness, out.ctypes.data, n, C.byref(w), C.byref(h)))
+        return out.reshape(int(h.value), int(w.value), 4)
 
     def set_surface_threshold(self, tau: float):
         """Application::SetSurfaceThreshold: the accumulated opacity at which the surface of an unlit / lit scene lies."""
