@@ -649,6 +649,68 @@ int vr_slice_orthogonal(const vr_ctx* ctx, int slot, int axis, int index, int th
 /* Counters of the last slice launch (as described above); waits for that launch.  Zeros before the first slice. */
 int vr_slice_counters(vr_ctx* ctx, uint64_t out[3]);
 
+/* ---- histograms: how the values of a volume slot are distributed, overall and inside each contour of a mask -------------------
+ * Integer counts of one channel of an uploaded slot over a voxel box, on the device (csrc/vr_hist.h; the host surface's
+ * OpacityTF::ActivateHistogram / CalibrateOnMask restated for volumes that live in HBM).  Row 0 counts every voxel of the box; row
+ * 1 + c the voxels of the box that lie inside contour c of the mask slot.  The uniforms, tables, viewport and vr_set_arithmetic play
+ * no part.
+ *   Binning of a value v: t = v * scale, one f32 multiply; i = (int32)t by the normative conversion -- truncation toward zero,
+ *     saturating, NaN -> 0.  VR_HIST_CLAMP: bin = min(max(i, 0), bins - 1), and every voxel is counted.  VR_HIST_DROP: the voxel is
+ *     counted iff 0 <= i < bins; otherwise it adds one to the row's `dropped`.  (static_cast<int>(a * resolution) then clamp is
+ *     ActivateHistogram; static_cast<int>(a) then value < bin.size() is CalibrateOnMask.)
+ *   Mask: component c of the mask voxel at the same index selects iff m.c != 0.0f -- NaN selects, -0 does not.  A voxel inside two
+ *     contours is counted in both rows.
+ *   Outputs: counts = uint64[VR_HIST_ROWS][bins], rows = vr_hist_row[VR_HIST_ROWS] with voxels = counted + dropped, so that for every
+ *     computed row the sum of its counts + dropped == voxels.  Rows that are not requested are all zero in both; the call zeroes
+ *     its own outputs on the stream.  An empty box (lo == hi on an axis) is valid and gives zeros.
+ *   Counters (vr_hist_counters): out[0] = voxels of the box, out[1] = voxels whose value was loaded, out[2] = voxels accounted for
+ *     from a brick range record without being loaded.
+ * Kernel forms: every flavour of vr_set_kernel_flavour but 1 runs the default form -- lanes of a wavefront that hold the same
+ * (row, bin) are combined before they add, and an unmasked channel-3 launch settles every 4 x 4 x 4 brick of the box whose range
+ * record pins all its voxels to one bin without loading it (exact: csrc/vr_hist.h), out[1] + out[2] == out[0].  Flavour 1 runs the plain
+ * form: out[1] == out[0], out[2] == 0.  With a mask the value is loaded only where a requested row needs it: out[1] < out[0] when
+ * row 0 is off and voxels lie outside every requested contour.  Counts, rows and out[0] are identical across the forms and the
+ * volume layouts. */
+#define VR_HIST_ROWS 5          /* row 0: every voxel of the box; row 1+c: voxels whose mask component c != 0 */
+#define VR_HIST_MAX_BINS 65536
+#define VR_HIST_CLAMP 0
+#define VR_HIST_DROP 1
+typedef struct vr_hist_desc {
+    int32_t  volume_slot;   /* the values: an uploaded slot                                   */
+    int32_t  channel;       /* 0..3 = .r .g .b .a of its voxels                               */
+    int32_t  mask_slot;     /* -1 = none; else an uploaded slot of the same nx, ny, nz        */
+    uint32_t rows;          /* bit r set = compute row r; bits 1..4 need a mask_slot          */
+    uint32_t bins;          /* 1 .. VR_HIST_MAX_BINS                                          */
+    float    scale;
+    int32_t  out_of_range;  /* VR_HIST_CLAMP / VR_HIST_DROP                                   */
+    int32_t  lo[3], hi[3];  /* voxel box, half open, 0 <= lo <= hi <= n per axis; lo == hi: empty, valid */
+} vr_hist_desc;
+typedef struct vr_hist_row { uint64_t voxels, dropped; } vr_hist_row;   /* voxels = counted + dropped */
+
+/* Fills *out for the whole volume of `slot`: the box (0,0,0) .. (nx,ny,nz), channel 3, no mask, rows = 1, VR_HIST_CLAMP, the given
+ * bins and scale.  Pure host arithmetic; VR_ERR_INVALID_ARG for a NULL pointer, a bad slot or bin count, VR_ERR_NOT_READY for an
+ * empty slot. */
+int vr_hist_whole(const vr_ctx* ctx, int slot, uint32_t bins, float scale, vr_hist_desc* out);
+
+/* Enqueues the histogram on `stream` (a hipStream_t, NULL = the ctx's own) into DEVICE memory: d_counts = uint64[VR_HIST_ROWS][bins],
+ * d_rows = vr_hist_row[VR_HIST_ROWS]; nothing is synchronised on the host.
+ * Checked before anything is enqueued (the outputs stay untouched).  VR_ERR_INVALID_ARG: a NULL pointer; a volume or mask slot out of
+ * range; a channel outside 0 .. 3; bins outside 1 .. VR_HIST_MAX_BINS; an unknown out_of_range; a box that is not 0 <= lo <= hi <= n
+ * on every axis; rows == 0, a bit of rows above bit 4, or bits 1 .. 4 without a mask_slot; a mask whose nx, ny, nz differ from the
+ * value volume's.  VR_ERR_NOT_READY: the volume slot or the mask slot is empty.  No value of scale is an error.
+ * A histogram is a stream-ordered launch like a slice: it is one of the eight launches that may be in flight, and the range records the
+ * default form settles by are built on its stream when a volume changed since they were built (no host wait).  It changes nothing
+ * else the caller can read: the frame of vr_download, vr_last_counters, vr_last_kernel_flavour, vr_last_timing, vr_kernel_times,
+ * vr_kernel_choice and vr_slice_counters stay what they were. */
+int vr_histogram_async(vr_ctx* ctx, const vr_hist_desc* desc, void* d_counts, void* d_rows, void* stream);
+
+/* The same into HOST memory (counts = uint64[VR_HIST_ROWS * bins], rows = vr_hist_row[VR_HIST_ROWS]), on the ctx's own stream;
+ * synchronous on return. */
+int vr_histogram(vr_ctx* ctx, const vr_hist_desc* desc, uint64_t* counts, vr_hist_row* rows);
+
+/* Counters of the last histogram launch (as described above); waits for that launch.  Zeros before the first histogram. */
+int vr_hist_counters(vr_ctx* ctx, uint64_t out[3]);
+
 /* Volume layout in HBM (A/B measurements; frames and counts are bit-identical in every mode).
  *   0  default: the march kernels gather from a BRICKED copy of every slot -- the vec4 voxels and a scalar f32 density plane
  *      (what fetches that consume .a alone read: BasicVolumeApp.wgsl:171, the density / dose fetches of the other shaders)

@@ -32,6 +32,8 @@ MAX_VOLUMES = 3
 SLICE_MAX, SLICE_MIN, SLICE_AVERAGE = 0, 1, 2  # vr_slice_desc.reduce (include/vr.h)
 SLICE_LINEAR, SLICE_NEAREST = 0, 1              # vr_slice_desc.filter
 SLICE_RGBA32F, SLICE_BGRA8 = 0, 1               # vr_slice_desc.format
+HIST_ROWS, HIST_MAX_BINS = 5, 65536              # vr_histogram (include/vr.h)
+HIST_CLAMP, HIST_DROP = 0, 1                     # vr_hist_desc.out_of_range
 
 # every symbol include/vr.h declares (tests check that the library exports each of them)
 ABI_SYMBOLS = [
@@ -49,6 +51,7 @@ ABI_SYMBOLS = [
     "vr_set_output", "vr_set_surface_threshold", "vr_surface_depth_async", "vr_pick",
     "vr_set_ray_bounds",
     "vr_slice_async", "vr_slice_render", "vr_slice_orthogonal", "vr_slice_counters",
+    "vr_hist_whole", "vr_histogram_async", "vr_histogram", "vr_hist_counters",
 ]
 
 
@@ -95,6 +98,28 @@ class SliceDesc(C.Structure):
                 v = (C.c_float * 3)(*[float(x) for x in v])
             setattr(d, k, v)
         return d
+
+
+class HistDesc(C.Structure):
+    """struct vr_hist_desc (include/vr.h): the value slot and channel, the mask, the rows, the binning and the voxel box."""
+    _fields_ = [
+        ("volume_slot", C.c_int32), ("channel", C.c_int32), ("mask_slot", C.c_int32), ("rows", C.c_uint32), ("bins", C.c_uint32),
+        ("scale", C.c_float), ("out_of_range", C.c_int32), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3),
+    ]
+
+    def copy(self, **over) -> "HistDesc":
+        """A copy with the given fields replaced (lo / hi from any sequence of three integers)."""
+        d = HistDesc.from_buffer_copy(bytes(self))
+        for k, v in over.items():
+            if k in ("lo", "hi"):
+                v = (C.c_int32 * 3)(*[int(x) for x in v])
+            setattr(d, k, v)
+        return d
+
+
+class HistRow(C.Structure):
+    """struct vr_hist_row: voxels = counted + dropped."""
+    _fields_ = [("voxels", C.c_uint64), ("dropped", C.c_uint64)]
 
 
 class VrError(RuntimeError):
@@ -177,6 +202,10 @@ def load() -> C.CDLL:
     lib.vr_slice_render.argtypes = [vp, C.POINTER(SliceDesc), vp]
     lib.vr_slice_orthogonal.argtypes = [vp, i32, i32, i32, i32, C.POINTER(SliceDesc)]
     lib.vr_slice_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
+    lib.vr_hist_whole.argtypes = [vp, i32, u32, C.c_float, C.POINTER(HistDesc)]
+    lib.vr_histogram_async.argtypes = [vp, C.POINTER(HistDesc), vp, vp, vp]
+    lib.vr_histogram.argtypes = [vp, C.POINTER(HistDesc), vp, vp]
+    lib.vr_hist_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
     lib.vr_present_async.argtypes = [vp, vp, vp, vp]
     lib.vr_present_tiles_async.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
     lib.vr_hint_frames_in_flight.argtypes = [vp, i32]
@@ -496,6 +525,30 @@ class Context:
         """(counted samples, pixels with a counted sample, samples whose voxels were loaded) of the last slice launch."""
         out = (C.c_uint64 * 3)()
         self._chk(self.lib.vr_slice_counters(self.h, C.byref(out)))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def hist_whole(self, slot: int, bins: int, scale: float) -> HistDesc:
+        """vr_hist_whole: the descriptor of the whole volume `slot` (channel 3, no mask, row 0, CLAMP: edit as needed)."""
+        d = HistDesc()
+        self._chk(self.lib.vr_hist_whole(self.h, slot, bins, scale, C.byref(d)))
+        return d
+
+    def histogram_async(self, desc: HistDesc, d_counts: int, d_rows: int, stream: int = 0):
+        """vr_histogram_async: into device memory d_counts (uint64[5][bins]) and d_rows (5 x (voxels, dropped) uint64) on `stream`;
+        nothing is synchronised."""
+        self._chk(self.lib.vr_histogram_async(self.h, C.byref(desc), d_counts, d_rows, stream))
+
+    def histogram(self, desc: HistDesc):
+        """vr_histogram: (counts uint64[5, bins], rows = [(voxels, dropped)] * 5); rows that were not requested are zero."""
+        counts = np.zeros((HIST_ROWS, int(desc.bins)), dtype=np.uint64)
+        rows = (HistRow * HIST_ROWS)()
+        self._chk(self.lib.vr_histogram(self.h, C.byref(desc), counts.ctypes.data, C.addressof(rows)))
+        return counts, [(int(r.voxels), int(r.dropped)) for r in rows]
+
+    def hist_counters(self):
+        """(voxels of the box, voxels whose value was loaded, voxels settled from a brick record) of the last histogram launch."""
+        out = (C.c_uint64 * 3)()
+        self._chk(self.lib.vr_hist_counters(self.h, C.byref(out)))
         return int(out[0]), int(out[1]), int(out[2])
 
     def set_volume_layout(self, mode: int):

@@ -112,6 +112,36 @@ int Application::SliceThroughPick(const vr_pick_result& pick, int axis, int thic
     return VR_OK;
 }
 
+int Application::Histogram(const vr_hist_desc& desc, uint64_t* counts, vr_hist_row* rows)
+{
+    if (!p_Ctx) return VR_ERR_NOT_READY;
+    int rc = vr_histogram(p_Ctx, &desc, counts, rows);
+    if (rc != VR_OK) m_Error = vr_last_error(p_Ctx);
+    return rc;
+}
+
+int Application::DoseVolumeHistogram(int doseSlot, int maskSlot, int contour, uint32_t bins, float scale, std::vector<uint64_t>& atLeast)
+{
+    if (!p_Ctx) return VR_ERR_NOT_READY;
+    if (contour < 0 || contour > 3) return VR_ERR_INVALID_ARG;
+    vr_hist_desc d;
+    int rc = vr_hist_whole(p_Ctx, doseSlot, bins, scale, &d);
+    if (rc != VR_OK) return rc;
+    d.mask_slot = maskSlot;
+    d.rows = 2u << contour;
+    std::vector<uint64_t> counts((size_t)VR_HIST_ROWS * bins);
+    vr_hist_row rows[VR_HIST_ROWS];
+    rc = Histogram(d, counts.data(), rows);
+    if (rc != VR_OK) return rc;
+    atLeast.assign(bins, 0);
+    uint64_t sum = 0;
+    for (size_t b = bins; b-- > 0;) {
+        sum += counts[(size_t)(1 + contour) * bins + b];
+        atLeast[b] = sum;
+    }
+    return VR_OK;
+}
+
 int Application::Pick(uint32_t x, uint32_t y, vr_pick_result* out)
 {
     if (!p_Ctx || !p_App) return VR_ERR_NOT_READY;

@@ -54,6 +54,13 @@ public:
     // voxels of maximum-intensity slab around it, through TF slot 0: rgba = *w x *h float4, one pixel per voxel.  A pick without a
     // hit returns VR_ERR_INVALID_ARG.
     int SliceThroughPick(const vr_pick_result& pick, int axis, int thickness, std::vector<float>& rgba, uint32_t* w, uint32_t* h);
+    // A histogram of one of the scene's volumes (vr_histogram): counts = uint64[VR_HIST_ROWS * desc.bins], rows = vr_hist_row[VR_HIST_ROWS],
+    // host memory.  The frame of the last OnRender and its counters stay.
+    int Histogram(const vr_hist_desc& desc, uint64_t* counts, vr_hist_row* rows);
+    // The cumulative dose-volume histogram of contour `contour` (0 .. 3) of volume maskSlot: .a of volume doseSlot binned as
+    // (int)(dose * scale) into `bins` bins (CLAMP), then atLeast[b] = the sum of counts[k] over k >= b -- the voxels of the structure
+    // that receive at least the dose of bin b; atLeast[0] is the structure's voxel count.
+    int DoseVolumeHistogram(int doseSlot, int maskSlot, int contour, uint32_t bins, float scale, std::vector<uint64_t>& atLeast);
     // the accumulated opacity at which the unlit / lit scene's surface lies (vr_set_surface_threshold: finite, 0 <= tau < 1)
     int SetSurfaceThreshold(float tau);
 

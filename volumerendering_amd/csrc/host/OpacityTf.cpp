@@ -59,6 +59,27 @@ void OpacityTF::ActivateHistogram(const VolumeFile& file)
         if (h != 0.0f) h = std::log10(h) / maxVal;
 }
 
+int OpacityTF::ActivateHistogram(vr_ctx* ctx, int slot, bool normalized, size_t dataRange)
+{
+    if (!ctx) return VR_ERR_INVALID_ARG;
+    // the CPU overload's two scale factors (the second with its integer division)
+    const float scale = normalized ? static_cast<float>(m_TextureResolution) : static_cast<float>(m_TextureResolution / std::max<size_t>(dataRange, 1));
+    vr_hist_desc d;
+    int rc = vr_hist_whole(ctx, slot, static_cast<uint32_t>(m_TextureResolution), scale, &d);
+    if (rc != VR_OK) return rc;
+    std::vector<uint64_t> counts(static_cast<size_t>(VR_HIST_ROWS) * d.bins);
+    vr_hist_row rows[VR_HIST_ROWS];
+    rc = vr_histogram(ctx, &d, counts.data(), rows);
+    if (rc != VR_OK) return rc;
+    m_Histogram.assign(m_TextureResolution, 0.0f);
+    const float maxVal = std::log10(static_cast<float>(rows[0].voxels));
+    for (int i = 0; i < m_TextureResolution; ++i) {
+        const float h = static_cast<float>(counts[i]);  // one correct rounding of the exact count
+        if (h != 0.0f) m_Histogram[i] = std::log10(h) / maxVal;
+    }
+    return VR_OK;
+}
+
 bool OpacityTF::Save(const std::string& name)
 {
     std::ofstream file(name);
@@ -142,6 +163,40 @@ void OpacityTF::CalibrateOnMask(std::shared_ptr<const VolumeFile> mask, std::sha
                 size_t value = static_cast<size_t>(static_cast<int>(fileData[i].a));
                 if (value < bin.size()) ++bin[value];
             }
+    CalibrateFromBins(bin, file->GetMaxNumber());
+}
+
+int OpacityTF::CalibrateOnMask(vr_ctx* ctx, int fileSlot, int maskSlot, int channel, size_t maxValue, std::array<int, 4> activeContours)
+{
+    if (!ctx || maxValue == 0 || maxValue > VR_HIST_MAX_BINS) return VR_ERR_INVALID_ARG;
+    uint32_t rowBits = 0;
+    for (int i = 0; i < 4; ++i)
+        if (activeContours[i] == 1) rowBits |= 2u << i;
+    if (rowBits == 0) return VR_ERR_INVALID_ARG;
+    vr_hist_desc d;
+    int rc = vr_hist_whole(ctx, fileSlot, static_cast<uint32_t>(maxValue), 1.0f, &d);
+    if (rc != VR_OK) return rc;
+    d.channel = channel;
+    d.mask_slot = maskSlot;
+    d.rows = rowBits;
+    d.out_of_range = VR_HIST_DROP;
+    std::vector<uint64_t> counts(static_cast<size_t>(VR_HIST_ROWS) * d.bins);
+    vr_hist_row rows[VR_HIST_ROWS];
+    rc = vr_histogram(ctx, &d, counts.data(), rows);
+    if (rc != VR_OK) return rc;
+    // a voxel inside two active contours counts twice, as in the CPU loop
+    std::vector<double> bin(maxValue, 0.0);
+    for (int r = 1; r < VR_HIST_ROWS; ++r)
+        if ((rowBits >> r) & 1u)
+            for (size_t b = 0; b < maxValue; ++b) bin[b] += static_cast<double>(counts[static_cast<size_t>(r) * d.bins + b]);
+    CalibrateFromBins(bin, maxValue);
+    return VR_OK;
+}
+
+// the control points and the table of a calibration histogram (bin.size() = the number of raw values; maxNumber scales a bin to the table)
+void OpacityTF::CalibrateFromBins(const std::vector<double>& bin, size_t maxNumber)
+{
+    const size_t maxValue = bin.size();
     const int maxElem = static_cast<int>(*std::max_element(bin.begin(), bin.end()));
     if (maxElem == 0) return;
 
@@ -156,8 +211,8 @@ void OpacityTF::CalibrateOnMask(std::shared_ptr<const VolumeFile> mask, std::sha
             if (first == -1) first = i;
             last = i;
         } else if (first != -1) {
-            const int cpFirst = static_cast<int>((static_cast<double>(first) / file->GetMaxNumber()) * GetTextureResolution());
-            const int cpLast = static_cast<int>((static_cast<double>(last) / file->GetMaxNumber()) * GetTextureResolution());
+            const int cpFirst = static_cast<int>((static_cast<double>(first) / maxNumber) * GetTextureResolution());
+            const int cpLast = static_cast<int>((static_cast<double>(last) / maxNumber) * GetTextureResolution());
             if (!exists(cpFirst)) cps.push_back({static_cast<double>(cpFirst), bin[first] / maxElem});
             if (cpFirst != cpLast) cps.push_back({static_cast<double>(cpLast), bin[last] / maxElem});
             first = -1;

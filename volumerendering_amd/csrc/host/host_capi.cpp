@@ -236,6 +236,24 @@ void vrh_otf_histogram(void* t, void* file, float* out)
     tf->ActivateHistogram(*static_cast<VolumeHandle*>(file)->v);
     std::memcpy(out, tf->GetHistogram().data(), tf->GetHistogram().size() * sizeof(float));
 }
+// the device overloads (vr_histogram of ctx); a vr_status
+int vrh_otf_histogram_device(void* t, void* ctx, int slot, int normalized, size_t data_range, float* out)
+{
+    VRH_TRY(VR_ERR_HIP, {
+        auto* tf = static_cast<OpacityTF*>(t);
+        const int rc = tf->ActivateHistogram(static_cast<vr_ctx*>(ctx), slot, normalized != 0, data_range);
+        if (rc != VR_OK) return rc;
+        std::memcpy(out, tf->GetHistogram().data(), tf->GetHistogram().size() * sizeof(float));
+        return VR_OK;
+    })
+}
+int vrh_otf_calibrate_device(void* t, void* ctx, int file_slot, int mask_slot, int channel, size_t max_value, const int active[4])
+{
+    VRH_TRY(VR_ERR_HIP, {
+        return static_cast<OpacityTF*>(t)->CalibrateOnMask(static_cast<vr_ctx*>(ctx), file_slot, mask_slot, channel, max_value,
+                                                           {active[0], active[1], active[2], active[3]});
+    })
+}
 void vrh_otf_remap_cp(void* t, double x, double y, int data_range, int tf_res, double out[2])
 {
     auto r = static_cast<OpacityTF*>(t)->RemapCP({x, y}, data_range, tf_res);
@@ -365,6 +383,23 @@ long long vrh_app_slice_through_pick(void* a, const vr_pick_result* pick, int ax
         if (rc != VR_OK) return rc;
         if (rgba && capacity >= px.size()) std::memcpy(rgba, px.data(), px.size() * sizeof(float));
         return (long long)px.size();
+    })
+}
+// Application::Histogram / DoseVolumeHistogram (vr_histogram of the application's context); the latter into at_least[bins]
+int vrh_app_histogram(void* a, const vr_hist_desc* d, uint64_t* counts, vr_hist_row* rows)
+{
+    if (!d || !counts || !rows) return VR_ERR_INVALID_ARG;
+    VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->Histogram(*d, counts, rows); })
+}
+int vrh_app_dvh(void* a, int dose_slot, int mask_slot, int contour, uint32_t bins, float scale, uint64_t* at_least)
+{
+    if (!at_least) return VR_ERR_INVALID_ARG;
+    VRH_TRY(VR_ERR_HIP, {
+        std::vector<uint64_t> v;
+        const int rc = static_cast<Application*>(a)->DoseVolumeHistogram(dose_slot, mask_slot, contour, bins, scale, v);
+        if (rc != VR_OK) return rc;
+        std::memcpy(at_least, v.data(), v.size() * sizeof(uint64_t));
+        return VR_OK;
     })
 }
 int vrh_app_set_surface_threshold(void* a, float tau) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->SetSurfaceThreshold(tau); }) }

@@ -3,6 +3,8 @@
 // device vr_create fails with VR_ERR_HIP.
 #include "../../include/vr.h"
 #include "vr_launch.h"
+// Histograms (vr_histogram_async): nothing to fuse, so this kernel exists once, here
+#include "vr_hist.h"
 
 // the same dispatch over the kernels compiled with fused multiply-adds (vr_fused.hip)
 namespace vrf {
@@ -234,6 +236,13 @@ struct vr_ctx {
     unsigned slice_tiles = 0;
     void* d_slice_out = nullptr;  // vr_slice_render's device output (grown on demand)
     size_t slice_out_cap = 0;     // bytes
+    // Histograms (vr_histogram_async): the three counters of the histogram launches, one buffer per record slot (a histogram takes
+    // a record slot like a slice, and leaves every other launch's bookkeeping alone), which of them the last histogram wrote
+    // (vr_hist_counters), and vr_histogram's device outputs (grown on demand)
+    unsigned long long* d_hist_stats[kInFlight] = {};
+    int hist_buf = -1;
+    void* d_hist_out = nullptr;
+    size_t hist_out_cap = 0;  // bytes
     bool last_unmeasured = false;  // the last launch's family is never measured (KernelForm::measured): vr_kernel_choice reports no candidates
     float iso = 0.5f;        // VR_VARIANT_ISO's level (vr_set_iso_value), copied into MarchParams::iso at enqueue
     // Shadows of the lit shader (vr_set_shadows, vr_shadow.h): the setting, and a ring of light volumes, one per key.  A launch whose key
@@ -1878,6 +1887,9 @@ void vr_destroy(vr_ctx* c)
     for (auto* b : c->d_slice_counts)
         if (b) (void)hipFree(b);
     if (c->d_slice_out) (void)hipFree(c->d_slice_out);
+    for (auto* b : c->d_hist_stats)
+        if (b) (void)hipFree(b);
+    if (c->d_hist_out) (void)hipFree(c->d_hist_out);
     for (auto& e : c->shadow) {
         if (e.buf.d) (void)hipFree(e.buf.d);
         if (e.built.ev) (void)hipEventDestroy(e.built.ev);
@@ -2885,6 +2897,166 @@ int vr_slice_counters(vr_ctx* c, uint64_t out[3])
     VR_HIP(c, hipGetLastError());
     unsigned long long h[3] = {0, 0, 0};
     VR_HIP(c, hipMemcpyAsync(h, c->d_counters, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    VR_HIP(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < 3; ++i) out[i] = h[i];
+    return VR_OK;
+}
+
+namespace {
+
+// the descriptor's own fields (VR_ERR_INVALID_ARG), then what the context must hold (VR_ERR_NOT_READY, mismatched mask)
+int check_hist(vr_ctx* c, const vr_hist_desc* d, const void* counts, const void* rows, const char* who)
+{
+    const std::string w(who);
+    if (!d || !counts || !rows) return fail(c, VR_ERR_INVALID_ARG, w + ": the descriptor or an output is NULL");
+    if (d->volume_slot < 0 || d->volume_slot >= VR_MAX_VOLUMES) return fail(c, VR_ERR_INVALID_ARG, w + ": bad volume slot");
+    if (d->mask_slot < -1 || d->mask_slot >= VR_MAX_VOLUMES) return fail(c, VR_ERR_INVALID_ARG, w + ": bad mask slot");
+    if (d->channel < 0 || d->channel > 3) return fail(c, VR_ERR_INVALID_ARG, w + ": the channel must be 0 .. 3");
+    if (d->bins < 1 || d->bins > VR_HIST_MAX_BINS) return fail(c, VR_ERR_INVALID_ARG, w + ": bins must be 1 .. 65536");
+    if (d->out_of_range != VR_HIST_CLAMP && d->out_of_range != VR_HIST_DROP) return fail(c, VR_ERR_INVALID_ARG, w + ": unknown out_of_range policy");
+    if (d->rows == 0 || (d->rows >> VR_HIST_ROWS) != 0) return fail(c, VR_ERR_INVALID_ARG, w + ": rows must have a bit of 0 .. 4 set and none above");
+    if ((d->rows & ~1u) != 0 && d->mask_slot < 0) return fail(c, VR_ERR_INVALID_ARG, w + ": contour rows need a mask slot");
+    const DevVolume& v = c->vol[d->volume_slot];
+    if (!v.data) return fail(c, VR_ERR_NOT_READY, w + ": volume slot " + std::to_string(d->volume_slot) + " is empty");
+    const int n[3] = {v.nx, v.ny, v.nz};
+    for (int a = 0; a < 3; ++a)
+        if (d->lo[a] < 0 || d->lo[a] > d->hi[a] || d->hi[a] > n[a]) return fail(c, VR_ERR_INVALID_ARG, w + ": the box must be 0 <= lo <= hi <= n on every axis");
+    if (d->mask_slot >= 0) {
+        const DevVolume& m = c->vol[d->mask_slot];
+        if (!m.data) return fail(c, VR_ERR_NOT_READY, w + ": mask slot " + std::to_string(d->mask_slot) + " is empty");
+        if (m.nx != v.nx || m.ny != v.ny || m.nz != v.nz) return fail(c, VR_ERR_INVALID_ARG, w + ": the mask's dimensions differ from the volume's");
+    }
+    return VR_OK;
+}
+
+// One histogram launch on `s` (the descriptor has been checked).  Like a slice it takes the next record slot -- it is one of the
+// kInFlight launches in flight -- and touches none of the other launches' bookkeeping.
+int enqueue_hist(vr_ctx* c, const vr_hist_desc& d, void* d_counts, void* d_rows, hipStream_t s)
+{
+    VR_HIP(c, hipSetDevice(c->device));
+    (void)hipGetLastError();
+    const int vs = d.volume_slot;
+    const DevVolume v = linear_volume(c, vs);
+    HistParams H;
+    std::memset(&H, 0, sizeof H);
+    const bool plane = d.channel == 3 && d.mask_slot < 0 && v.dens;
+    H.val = plane ? v.dens : reinterpret_cast<const float*>(v.data) + d.channel;
+    H.val_stride = plane ? 1 : 4;
+    H.mask = d.mask_slot >= 0 ? c->vol[d.mask_slot].data : nullptr;
+    H.nx = v.nx;
+    H.ny = v.ny;
+    H.nz = v.nz;
+    unsigned long long units = 1, box = 1;
+    for (int a = 0; a < 3; ++a) {
+        H.lo[a] = d.lo[a];
+        H.hi[a] = d.hi[a];
+        H.u0[a] = d.lo[a] >> 2;
+        H.un[a] = d.hi[a] > d.lo[a] ? ((d.hi[a] + 3) >> 2) - H.u0[a] : 0;
+        units *= (unsigned long long)H.un[a];
+        box *= (unsigned long long)(d.hi[a] - d.lo[a]);
+    }
+    if (box == 0) units = 0;
+    if (units > 0xFFFFFFFFull) return fail(c, VR_ERR_UNSUPPORTED, "vr_histogram: the box has 2^32 brick units or more");
+    H.units = (unsigned)units;
+    H.rows = d.rows;
+    H.bins = d.bins;
+    H.scale = d.scale;
+    H.drop = d.out_of_range == VR_HIST_DROP;
+    unsigned n_rows = 0;
+    for (int r = 0; r < VR_HIST_ROWS; ++r) n_rows += (d.rows >> r) & 1u;
+    const unsigned blocks = units < 4 ? 1u : (units / 4 < kHistBlocks ? (unsigned)(units / 4) : kHistBlocks);
+    // the private LDS copy: within the budget, and a workgroup's share of the voxels (its four wavefronts' units) below 2^32 so that
+    // no u32 count can wrap; otherwise the kernel adds into the u64 outputs directly
+    const unsigned long long per_block = (units + blocks * 4ull - 1) / (blocks * 4ull) * 4ull * 64ull;
+    H.lds = (size_t)n_rows * d.bins * sizeof(unsigned) <= kHistLdsBytes && per_block < (1ull << 32);
+    const int requested = c->flavour == 0 ? c->default_flavour : c->flavour;
+    const bool plain = requested == 1;
+    // exact settling by the slot's range records (of .a: channel 3), for the unmasked launch
+    if (!plain && d.channel == 3 && d.mask_slot < 0 && units != 0) {
+        H.bnx = skip_bricks(v.nx);
+        H.bny = skip_bricks(v.ny);
+        if (!prepare_range(c, s, vs, H.bnx, H.bny, skip_bricks(v.nz), &H.bricks)) return VR_ERR_HIP;
+    }
+    int cb;
+    const vr_ctx::OrderSlot* slot_sort;
+    if (const int rc = take_record_slot(c, s, 0, &cb, &slot_sort)) return rc;
+    if (slot_sort) VR_HIP(c, hipStreamWaitEvent(s, slot_sort->sorted, 0));
+    if (!c->d_hist_stats[cb]) {
+        VR_HIP(c, hipMalloc(&c->d_hist_stats[cb], 3 * sizeof(unsigned long long)));
+    }
+    VR_HIP(c, hipMemsetAsync(c->d_hist_stats[cb], 0, 3 * sizeof(unsigned long long), s));
+    VR_HIP(c, hipMemsetAsync(d_counts, 0, (size_t)VR_HIST_ROWS * d.bins * sizeof(unsigned long long), s));
+    VR_HIP(c, hipMemsetAsync(d_rows, 0, VR_HIST_ROWS * sizeof(vr_hist_row), s));
+    H.counts = static_cast<unsigned long long*>(d_counts);
+    H.row_sums = static_cast<unsigned long long*>(d_rows);
+    H.stats = c->d_hist_stats[cb];
+    const size_t lds_bytes = H.lds ? (size_t)n_rows * d.bins * sizeof(unsigned) : 0;
+    if (plain) hipLaunchKernelGGL(hist_kernel<true>, dim3(blocks), dim3(256), lds_bytes, s, H);
+    else hipLaunchKernelGGL(hist_kernel<false>, dim3(blocks), dim3(256), lds_bytes, s, H);
+    VR_HIP(c, hipGetLastError());
+    VR_HIP(c, hipEventRecord(c->slot_done[cb], s));
+    c->slot_used[cb] = true;
+    ++c->order_seq;
+    c->hist_buf = cb;
+    return VR_OK;
+}
+
+}  // namespace
+
+int vr_hist_whole(const vr_ctx* c, int slot, uint32_t bins, float scale, vr_hist_desc* out)
+{
+    if (!c || !out) return VR_ERR_INVALID_ARG;
+    if (slot < 0 || slot >= VR_MAX_VOLUMES || bins < 1 || bins > VR_HIST_MAX_BINS) return VR_ERR_INVALID_ARG;
+    if (!c->vol[slot].data) return VR_ERR_NOT_READY;
+    std::memset(out, 0, sizeof *out);
+    out->volume_slot = slot;
+    out->channel = 3;
+    out->mask_slot = -1;
+    out->rows = 1;
+    out->bins = bins;
+    out->scale = scale;
+    out->out_of_range = VR_HIST_CLAMP;
+    out->hi[0] = c->vol[slot].nx;
+    out->hi[1] = c->vol[slot].ny;
+    out->hi[2] = c->vol[slot].nz;
+    return VR_OK;
+}
+
+int vr_histogram_async(vr_ctx* c, const vr_hist_desc* desc, void* d_counts, void* d_rows, void* stream)
+{
+    if (!c) return VR_ERR_INVALID_ARG;
+    if (const int rc = check_hist(c, desc, d_counts, d_rows, "vr_histogram_async")) return rc;
+    return enqueue_hist(c, *desc, d_counts, d_rows, stream ? (hipStream_t)stream : c->stream);
+}
+
+int vr_histogram(vr_ctx* c, const vr_hist_desc* desc, uint64_t* counts, vr_hist_row* rows)
+{
+    if (!c) return VR_ERR_INVALID_ARG;
+    if (const int rc = check_hist(c, desc, counts, rows, "vr_histogram")) return rc;
+    VR_HIP(c, hipSetDevice(c->device));
+    const size_t cbytes = (size_t)VR_HIST_ROWS * desc->bins * sizeof(uint64_t), rbytes = VR_HIST_ROWS * sizeof(vr_hist_row);
+    // (the buffer's earlier uses were synchronous on this stream; a smaller one is freed by the next draining call)
+    if (const int rc = grow(c, &c->d_hist_out, &c->hist_out_cap, cbytes + rbytes, false)) return rc;
+    char* d = static_cast<char*>(c->d_hist_out);
+    if (const int rc = enqueue_hist(c, *desc, d, d + cbytes, c->stream)) return rc;
+    VR_HIP(c, hipMemcpyAsync(counts, d, cbytes, hipMemcpyDeviceToHost, c->stream));
+    VR_HIP(c, hipMemcpyAsync(rows, d + cbytes, rbytes, hipMemcpyDeviceToHost, c->stream));
+    VR_HIP(c, hipStreamSynchronize(c->stream));
+    return VR_OK;
+}
+
+int vr_hist_counters(vr_ctx* c, uint64_t out[3])
+{
+    if (!c) return VR_ERR_INVALID_ARG;
+    if (!out) return fail(c, VR_ERR_INVALID_ARG, "vr_hist_counters: out is NULL");
+    out[0] = out[1] = out[2] = 0;
+    if (c->hist_buf < 0) return VR_OK;
+    VR_HIP(c, hipSetDevice(c->device));
+    (void)hipGetLastError();
+    // the event behind the histogram (or behind a later launch in its record slot), then the context's own stream
+    VR_HIP(c, hipEventSynchronize(c->slot_done[c->hist_buf]));
+    unsigned long long h[3] = {0, 0, 0};
+    VR_HIP(c, hipMemcpyAsync(h, c->d_hist_stats[c->hist_buf], sizeof h, hipMemcpyDeviceToHost, c->stream));
     VR_HIP(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < 3; ++i) out[i] = h[i];
     return VR_OK;

@@ -159,6 +159,27 @@ struct SliceParams {
     unsigned long long* counts;  // [workgroups][3]: counted samples, pixels with a sample, samples loaded
 };
 
+// Kernel argument block of a histogram (hist_kernel, vr_hist.h; vr_hist_desc of include/vr.h): passed by value.
+struct HistParams {
+    const float* val;        // the value of voxel idx is val[idx * val_stride]: the channel of the x-fastest vec4 voxels (stride 4),
+    int val_stride;          // or the density plane (stride 1: channel 3 of an unmasked launch, when the layout has one)
+    const float4* mask;      // the mask slot's x-fastest vec4 voxels; nullptr = no mask
+    int nx, ny, nz;          // of the value volume (and of the mask)
+    int lo[3], hi[3];        // the voxel box, half open
+    int u0[3], un[3];        // the 4 x 4 x 4 brick units that meet the box: first unit and units per axis ...
+    unsigned units;          // ... and their number
+    unsigned rows;           // bit r: row r is computed
+    unsigned bins;
+    float scale;
+    int drop;                // VR_HIST_DROP
+    int lds;                 // the counts go through a private u32 copy in LDS (dynamic, rows computed * bins words)
+    const float2* bricks;    // exact settling: the slot's range records (vr_proj.h), bnx x bny x ... bricks; nullptr = off
+    int bnx, bny;
+    unsigned long long* counts;    // [VR_HIST_ROWS][bins]
+    unsigned long long* row_sums;  // [VR_HIST_ROWS][2]: voxels, dropped (vr_hist_row)
+    unsigned long long* stats;     // [3]: voxels of the box, voxels loaded, voxels settled from a record
+};
+
 // Work queue of the persistent-wavefront kernel (vr_pw.h): eight heads, one per class of the workgroup index modulo 8,
 // zero at launch; heads[c * 64] counts the items of class c handed out beyond every wavefront's first.
 struct PwQueue {

@@ -48,6 +48,10 @@ def load() -> C.CDLL:
         "vrh_otf_set_data_range": (None, [vp, i32]), "vrh_otf_data_range": (i32, [vp]),
         "vrh_otf_save": (i32, [vp, C.c_char_p]), "vrh_otf_load": (None, [vp, C.c_char_p, i32]),
         "vrh_otf_calibrate": (None, [vp, vp, vp, vp]), "vrh_otf_histogram": (None, [vp, vp, vp]),
+        "vrh_otf_histogram_device": (i32, [vp, vp, i32, i32, C.c_size_t, vp]),
+        "vrh_otf_calibrate_device": (i32, [vp, vp, i32, i32, i32, C.c_size_t, vp]),
+        "vrh_app_histogram": (i32, [vp, C.POINTER(capi.HistDesc), vp, vp]),
+        "vrh_app_dvh": (i32, [vp, i32, i32, i32, u32, f32, vp]),
         "vrh_otf_remap_cp": (None, [vp, f64, f64, i32, i32, vp]),
         "vrh_ctf_create": (vp, [i32]), "vrh_ctf_free": (None, [vp]), "vrh_ctf_resolution": (i32, [vp]),
         "vrh_ctf_data": (vp, [vp]), "vrh_ctf_reset": (None, [vp]), "vrh_ctf_add_cp": (i32, [vp, f64, vp]),
@@ -333,6 +337,22 @@ class OpacityTF(_TF):
         self.lib.vrh_otf_histogram(self.h, file.h, out.ctypes.data)
         return out
 
+    def ActivateHistogramDevice(self, ctx, slot: int, normalized: bool, data_range: int) -> np.ndarray:
+        """OpacityTF::ActivateHistogram(vr_ctx*, ...): the same from the device histogram of volume `slot` of ctx (a capi.Context or
+        a raw handle); raises capi.VrError on a failed call."""
+        out = np.zeros(self.GetTextureResolution(), dtype=np.float32)
+        rc = self.lib.vrh_otf_histogram_device(self.h, getattr(ctx, "h", ctx), slot, int(normalized), data_range, out.ctypes.data)
+        if rc != 0:
+            raise capi.VrError(rc, "OpacityTF::ActivateHistogram on the device failed")
+        return out
+
+    def CalibrateOnMaskDevice(self, ctx, file_slot: int, mask_slot: int, channel: int, max_value: int, active=(1, 0, 0, 0)):
+        """OpacityTF::CalibrateOnMask(vr_ctx*, ...): calibration from the device histogram of `channel` of volume file_slot inside
+        the active contours of volume mask_slot (channel 0 after vr_volume_normalize)."""
+        rc = self.lib.vrh_otf_calibrate_device(self.h, getattr(ctx, "h", ctx), file_slot, mask_slot, channel, max_value, (C.c_int * 4)(*active))
+        if rc != 0:
+            raise capi.VrError(rc, "OpacityTF::CalibrateOnMask on the device failed")
+
     def RemapCP(self, x, y, data_range, tf_res):
         out = (C.c_double * 2)()
         self.lib.vrh_otf_remap_cp(self.h, x, y, data_range, tf_res, out)
@@ -474,6 +494,19 @@ class Application:
         out = np.empty(n, dtype=np.float32)
         self._chk(self.lib.vrh_app_slice_through_pick(self.h, C.byref(pick), axis, thickness, out.ctypes.data, n, C.byref(w), C.byref(h)))
         return out.reshape(int(h.value), int(w.value), 4)
+
+    def histogram(self, desc: capi.HistDesc):
+        """Application::Histogram: (counts uint64[5, bins], rows [(voxels, dropped)] * 5) of one of the scene's volumes."""
+        counts = np.zeros((capi.HIST_ROWS, int(desc.bins)), dtype=np.uint64)
+        rows = (capi.HistRow * capi.HIST_ROWS)()
+        self._chk(self.lib.vrh_app_histogram(self.h, C.byref(desc), counts.ctypes.data, C.addressof(rows)))
+        return counts, [(int(r.voxels), int(r.dropped)) for r in rows]
+
+    def dose_volume_histogram(self, dose_slot: int, mask_slot: int, contour: int, bins: int, scale: float) -> np.ndarray:
+        """Application::DoseVolumeHistogram: uint64[bins], element b = the voxels of contour `contour` whose dose bin is >= b."""
+        out = np.zeros(bins, dtype=np.uint64)
+        self._chk(self.lib.vrh_app_dvh(self.h, dose_slot, mask_slot, contour, bins, scale, out.ctypes.data))
+        return out
 
     def set_surface_threshold(self, tau: float):
         """Application::SetSurfaceThreshold: the accumulated opacity at which the surface of an unlit / lit scene lies."""
