@@ -445,7 +445,15 @@ int vr_kernel_choice(vr_ctx* ctx, int flavours[6], float ms_per_launch[6], int* 
  *                                linear-filter lerp a + (b - a) * t, dot products, light.diffuse * m * kD + light.ambient * kA,
  *                                the CT / RT colour mix and FrontToBackBlend -- are single fused multiply-adds: bit-exact with
  *                                the oracle's fused mode, about a fifth fewer vector instructions per sample.  Ray placement
- *                                (matrices, slab test, step vectors, p += step) is identical in both modes.             */
+ *                                (matrices, slab test, step vectors, p += step) is identical in both modes.
+ * In full: a table look-up's coordinate d * R - 0.5 is a texture coordinate; a dot product is mad(a.z, b.z, mad(a.y, b.y, a.x * b.x)),
+ * and the sum of squares under a per-sample normalize (the gradient, lightPos - w) is that dot product; the shading sum is
+ * mad(dif_c * m, kD, amb_c * kA) and the blend mad(1 - dst.a, c * a, dst.c), their inner products dif_c * m, amb_c * kA, c.rgb * a
+ * rounded on their own in both modes, like rgb * shade, 1 - dst.a, the scale 1 / sqrt and the coordinate's fraction x - floor(x).
+ * The feature marches follow the same rule -- a per-sample expression of the shape a * b + c is fused, placement is not -- and
+ * their sections name the expressions: ISO's and the surface's refinement mads and the surface's alpha line are fused; w += wstep,
+ * sigma and g(d) of the ray bounds, the light volume's walk (D, len, dir, step, lim, q += step), s * a, T * (1 - a'), m * S, the t
+ * divisions and AVERAGE's s + d and s / n are not.                                                                       */
 #define VR_ARITH_SEPARATE 0
 #define VR_ARITH_FUSED 1
 int vr_set_arithmetic(vr_ctx* ctx, int mode);

@@ -1,8 +1,9 @@
-"""float32 numpy restatement of the per-pixel ray bounds of include/vr.h (vr_set_ray_bounds) in separately rounded arithmetic: BASIC's
+"""float32 numpy restatement of the per-pixel ray bounds of include/vr.h (vr_set_ray_bounds) in either arithmetic mode: BASIC's
 and LIGHT's march as proj_ref.march / shadow_ref.march restate them (rays from oracle_binding.setup_ray, jitter from
 oracle_binding.jitter, proj_ref's and iso_ref's samplers, look-ups and blend), with the one exception of the definition: an in-box step
 at p counts iff S_near <= sigma(p) < S_far, S = sigma of the bound's depth unprojected with the ray set-up's own unproject, pixel
-centre and world-to-uvw map.  Harness only."""
+centre and world-to-uvw map.  With fused=True the per-sample expressions are the fused ones of proj_ref.march / shadow_ref.march;
+sigma, g(d) and with them S_near / S_far are separately rounded in both modes (ray placement).  Harness only."""
 import numpy as np
 
 import iso_ref as ir
@@ -47,7 +48,7 @@ def box_corner_depths(u):
     return min(ds), max(ds)
 
 
-def march(variant, u, W, H, vec4, tf, near=None, far=None, pixels=None):
+def march(variant, u, W, H, vec4, tf, near=None, far=None, pixels=None, fused=False):
     """BASIC or LIGHT between the bounds near / far (float32 [H, W] depth buffers, None = no bound on that side) for `pixels` (px, py)
     (default: the whole frame, row by row).  Returns a dict: frag (N, 4), composited (N,), covered (N,) = the ray goes through the
     box, pixels, and per pixel what the tests' pins need: before_far (N,) = steps of 0 .. steps_count-1 with sigma(p_k) < S_far,
@@ -120,16 +121,17 @@ def march(variant, u, W, H, vec4, tf, near=None, far=None, pixels=None):
         if mask.any():
             mi = np.nonzero(mask)[0]
             if variant == BASIC:
-                o, rgb = pr.tf_lookup(opacity, color, pr.sample_a(dens, p[mi]))
+                o, rgb = pr.tf_lookup(opacity, color, pr.sample_a(dens, p[mi], fused), fused)
                 col = rgb.astype(f32)
             else:
-                v = ir.sample_rgba(vec4, p[mi])
-                o, rgb = pr.tf_lookup(opacity, color, np.ascontiguousarray(v[:, 3]))
-                sh = shr.shade_s(ir.normalize3(np.ascontiguousarray(v[:, :3])), w[mi], lpos, dif, amb, 2.5, 0.5, np.ones(mi.size, f32))
+                v = ir.sample_rgba(vec4, p[mi], fused)
+                o, rgb = pr.tf_lookup(opacity, color, np.ascontiguousarray(v[:, 3]), fused)
+                sh = shr.shade_s(ir.normalize3(np.ascontiguousarray(v[:, :3]), fused), w[mi], lpos, dif, amb, 2.5, 0.5,
+                                 np.ones(mi.size, f32), fused)
                 with np.errstate(all="ignore"):
                     col = (rgb * sh).astype(f32)
             sub = dst[mi]
-            pr._blend(col, o.astype(f32), sub, np.ones(mi.size, bool))
+            pr._blend(col, o.astype(f32), sub, np.ones(mi.size, bool), fused)
             dst[mi] = sub
             n[mi] += 1
         with np.errstate(all="ignore"):
@@ -141,7 +143,7 @@ def march(variant, u, W, H, vec4, tf, near=None, far=None, pixels=None):
     return out
 
 
-def frame(variant, u, W, H, vec4, tf, near=None, far=None):
+def frame(variant, u, W, H, vec4, tf, near=None, far=None, fused=False):
     """(frag [H, W, 4], composited, covered) of the whole frame."""
-    r = march(variant, u, W, H, vec4, tf, near, far)
+    r = march(variant, u, W, H, vec4, tf, near, far, fused=fused)
     return r["frag"].reshape(H, W, 4), int(r["composited"].sum()), int(r["covered"].sum())

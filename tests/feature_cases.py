@@ -45,6 +45,22 @@ def flat_tf(res, rgb=(0.8, 0.55, 0.3)):
     return np.ones(res, f32), np.tile(np.array([*rgb, 1.0], f32), (res, 1))
 
 
+def edge_volume():
+    """20 x 13 x 16 voxels for the refinement's edges (ISO and the surface output): exact-zero air around a block of density 0.9, a
+    plate of NaN voxels on the block's -x face (a ray that comes through it hits the block with d_prev = NaN: t is NaN, outside
+    [0, 1], and q = p_k), the gradient of all that in .rgb but exactly zero in the upper half z >= 8 (a hit there has a NaN normal:
+    the ambient term only).  With edge_clip the clip box begins inside the block: rays from -y hit on their first in-box step."""
+    v = np.zeros((16, 13, 20, 4), f32)
+    v[4:12, 3:10, 6:14, 3] = f32(0.9)
+    v[4:12, 3:10, 5, 3] = np.nan
+    v = ob.precompute_gradient(v)
+    v[8:, :, :, :3] = f32(0.0)
+    return v
+
+
+edge_clip = dict(clip_y=(0.5, 0.0))
+
+
 def depth_planes(rng, u, W, H):
     """(mode, hostile, near, far): planes drawn between the depths of the box's corners, a few hostile values mixed into a quarter
     of the cases (NaN, +-inf, -1, 2: tests/test_ray_bounds_gpu.hostile's values)."""
@@ -166,30 +182,30 @@ def cases(seed):
     return out
 
 
-def light_volume(case, u, scale=None):
-    """The restated light volume of the case's divisor under uniforms u."""
+def light_volume(case, u, scale=None, fused=False):
+    """The restated light volume of the case's divisor under uniforms u, in either arithmetic mode."""
     lo, hi = shr.clip_box(u)
     return shr.build(case.vec4, case.tf[0], case.shadow_divisor, case.shadow_scale if scale is None else scale, list(u.light_pos)[:3],
-                     lo, hi)
+                     lo, hi, fused=fused)
 
 
-def reference(case, family, u=None):
+def reference(case, family, u=None, fused=False):
     """(frag [H, W, 4], composited, covered) of the family's restatement with the case's parameters under uniforms u (default: the
-    case's own; a batch passes its other cameras)."""
+    case's own; a batch passes its other cameras), in separately rounded or fused arithmetic."""
     u = case.uniforms() if u is None else u
     W, H = case.W, case.H
     if family == "proj":
-        return pr.frame(case.proj_variant, u, W, H, case.vec4, case.tf)
+        return pr.frame(case.proj_variant, u, W, H, case.vec4, case.tf, fused=fused)
     if family == "iso":
-        return ir.frame(u, W, H, case.vec4, case.tf, case.iso)
+        return ir.frame(u, W, H, case.vec4, case.tf, case.iso, fused=fused)
     if family == "shadow":
-        return shr.frame(u, W, H, case.vec4, case.tf, light_volume(case, u))
+        return shr.frame(u, W, H, case.vec4, case.tf, light_volume(case, u, fused=fused), fused=fused)
     if family == "surf":
         if case.surf_variant == ISO:
-            return sr.iso_frame(u, W, H, case.vec4, case.tf, case.iso)
-        return sr.frame(u, W, H, case.vec4, case.tf[0], case.tau)
+            return sr.iso_frame(u, W, H, case.vec4, case.tf, case.iso, fused=fused)
+        return sr.frame(u, W, H, case.vec4, case.tf[0], case.tau, fused=fused)
     if family == "bound":
-        return br.frame(case.bound_variant, u, W, H, case.vec4, case.tf, case.near, case.far)
+        return br.frame(case.bound_variant, u, W, H, case.vec4, case.tf, case.near, case.far, fused=fused)
     raise ValueError(family)
 
 

@@ -2,10 +2,13 @@
 BasicVolumeApp.wgsl fs_main) and, on the same sample positions, the intensity projections of include/vr.h
 (MIP / MINIP / AVERAGE).  Rays come from oracle_binding.setup_ray and the jitter from oracle_binding.jitter; every
 other operation follows the oracle's order: normalize3s, the step, texel pairs, the seven lerps, the TF look-ups and
-FrontToBackBlend.  Harness only."""
+FrontToBackBlend.  With fused=True the expressions include/vr.h names under VR_ARITH_FUSED -- the texture and table coordinates,
+every lerp, the blend -- are single fused multiply-adds (fma_ref.fma32), as the oracle's fused mode evaluates them; ray placement
+(the direction, the step, p += step) and AVERAGE's s + d and s / n are separately rounded in both modes.  Harness only."""
 import numpy as np
 
 import oracle_binding as ob
+from fma_ref import mad
 
 f32 = np.float32
 BASIC, MIP, MINIP, AVERAGE = 0, 8, 9, 10
@@ -23,56 +26,72 @@ def _texel_pair(x0, n):
     return np.clip(t, 0, n - 1), np.clip(t + 1, 0, n - 1)
 
 
-def _lerp(a, b, t):
-    return (b - a) * t + a
-
-
-def sample_a(dens, p):
-    """textureSample(vol, linear, p).a for points p (N, 3); dens is the .a plane [nz, ny, nx] (float32)."""
-    nz, ny, nx = dens.shape
+def _lerp(a, b, t, fused=False):
     with np.errstate(all="ignore"):
-        x = p[:, 0] * f32(nx) + f32(-0.5)
-        y = p[:, 1] * f32(ny) + f32(-0.5)
-        z = p[:, 2] * f32(nz) + f32(-0.5)
+        return mad(b - a, t, a, fused)
+
+
+def sample(vol, p, fused=False):
+    """textureSample(vol, linear, p) for points p (N, 3) in either arithmetic mode: vol is a plane [nz, ny, nx] (the result is (N,))
+    or the voxels [nz, ny, nx, C] (the result is (N, C)); clamp-to-edge texel pairs, the seven lerps x, then y, then z."""
+    nz, ny, nx = vol.shape[:3]
+    with np.errstate(all="ignore"):
+        x = mad(p[:, 0], f32(nx), f32(-0.5), fused)
+        y = mad(p[:, 1], f32(ny), f32(-0.5), fused)
+        z = mad(p[:, 2], f32(nz), f32(-0.5), fused)
         x0, y0, z0 = np.floor(x), np.floor(y), np.floor(z)
         fx, fy, fz = x - x0, y - y0, z - z0
+        if vol.ndim == 4:
+            fx, fy, fz = fx[:, None], fy[:, None], fz[:, None]
         i0, i1 = _texel_pair(x0, nx)
         j0, j1 = _texel_pair(y0, ny)
         k0, k1 = _texel_pair(z0, nz)
-        c00 = _lerp(dens[k0, j0, i0], dens[k0, j0, i1], fx)
-        c10 = _lerp(dens[k0, j1, i0], dens[k0, j1, i1], fx)
-        c01 = _lerp(dens[k1, j0, i0], dens[k1, j0, i1], fx)
-        c11 = _lerp(dens[k1, j1, i0], dens[k1, j1, i1], fx)
-        return _lerp(_lerp(c00, c10, fy), _lerp(c01, c11, fy), fz)
+        c00 = _lerp(vol[k0, j0, i0], vol[k0, j0, i1], fx, fused)
+        c10 = _lerp(vol[k0, j1, i0], vol[k0, j1, i1], fx, fused)
+        c01 = _lerp(vol[k1, j0, i0], vol[k1, j0, i1], fx, fused)
+        c11 = _lerp(vol[k1, j1, i0], vol[k1, j1, i1], fx, fused)
+        return _lerp(_lerp(c00, c10, fy, fused), _lerp(c01, c11, fy, fused), fz, fused)
 
 
-def tf_lookup(opacity, color, d):
-    """(opacity, rgb) of densities d: textureSample(tfOpacity / tfColor, linear, d) with clamp-to-edge."""
+def sample_a(dens, p, fused=False):
+    """textureSample(vol, linear, p).a for points p (N, 3); dens is the .a plane [nz, ny, nx] (float32)."""
+    return sample(dens, p, fused)
+
+
+def opacity_lookup(opacity, d, fused=False):
+    """textureSample(tfOpacity, linear, d) with clamp-to-edge: BASIC's opacity look-up of densities d."""
     with np.errstate(all="ignore"):
-        x = d * f32(opacity.size) + f32(-0.5)
+        x = mad(d, f32(opacity.size), f32(-0.5), fused)
         x0 = np.floor(x)
         i0, i1 = _texel_pair(x0, opacity.size)
-        o = _lerp(opacity[i0], opacity[i1], x - x0)
-        xc = d * f32(color.shape[0]) + f32(-0.5)
+        return _lerp(opacity[i0], opacity[i1], x - x0, fused)
+
+
+def tf_lookup(opacity, color, d, fused=False):
+    """(opacity, rgb) of densities d: textureSample(tfOpacity / tfColor, linear, d) with clamp-to-edge."""
+    o = opacity_lookup(opacity, d, fused)
+    with np.errstate(all="ignore"):
+        xc = mad(d, f32(color.shape[0]), f32(-0.5), fused)
         xc0 = np.floor(xc)
         c0, c1 = _texel_pair(xc0, color.shape[0])
-        rgb = _lerp(color[c0, :3], color[c1, :3], (xc - xc0)[:, None])
+        rgb = _lerp(color[c0, :3], color[c1, :3], (xc - xc0)[:, None], fused)
     return o, rgb
 
 
-def _blend(rgb, a, dst, mask):
+def _blend(rgb, a, dst, mask, fused=False):
+    """FrontToBackBlend: mad(1 - dst.a, src, dst) per channel, src = (rgb * a, a) (the products rgb * a rounded on their own)."""
     with np.errstate(all="ignore"):
         s = rgb * a[:, None]
         om = f32(1.0) - dst[:, 3]
         new = np.empty_like(dst)
-        new[:, :3] = om[:, None] * s + dst[:, :3]
-        new[:, 3] = om * a + dst[:, 3]
+        new[:, :3] = mad(om[:, None], s, dst[:, :3], fused)
+        new[:, 3] = mad(om, a, dst[:, 3], fused)
     dst[mask] = new[mask]
 
 
-def march(variant, u, W, H, vec4, tf, pixels=None):
+def march(variant, u, W, H, vec4, tf, pixels=None, fused=False):
     """Returns (frag (N, 4), composited (N,), covered (N,), pixels (N, 2)) of BASIC or of a projection, for `pixels` (px, py)
-    (default: the whole frame, row by row)."""
+    (default: the whole frame, row by row), in separately rounded or fused arithmetic."""
     if pixels is None:
         pixels = np.stack(np.meshgrid(np.arange(W), np.arange(H)), -1).reshape(-1, 2)
     pixels = np.asarray(pixels, dtype=np.int64).reshape(-1, 2)
@@ -114,11 +133,11 @@ def march(variant, u, W, H, vec4, tf, pixels=None):
     m = np.full(idx.size, {MIP: -np.inf, MINIP: np.inf}.get(variant, 0.0), f32)
     for _ in range(u.steps_count):
         inb = np.all((p >= lo) & (p <= hi), axis=1)
-        d = sample_a(dens, p)
+        d = sample_a(dens, p, fused)
         if variant == BASIC:
-            o, rgb = tf_lookup(opacity, color, d)
+            o, rgb = tf_lookup(opacity, color, d, fused)
             mask = inb & (dst[:, 3] <= f32(0.95))
-            _blend(rgb, o, dst, mask)
+            _blend(rgb, o, dst, mask, fused)
             n += mask
         else:
             n += inb
@@ -136,15 +155,15 @@ def march(variant, u, W, H, vec4, tf, pixels=None):
         if variant == AVERAGE:
             with np.errstate(all="ignore"):
                 v = m / np.maximum(n, 1).astype(f32)
-        o, rgb = tf_lookup(opacity, color, v)
-        _blend(rgb, o, dst, n > 0)
+        o, rgb = tf_lookup(opacity, color, v, fused)
+        _blend(rgb, o, dst, n > 0, fused)
         cov[idx] = n > 0
     frag[idx] = dst
     comp[idx] = n
     return frag, comp, cov, pixels
 
 
-def frame(variant, u, W, H, vec4, tf):
+def frame(variant, u, W, H, vec4, tf, fused=False):
     """(frag [H, W, 4], composited, covered) of the whole frame."""
-    frag, comp, cov, _ = march(variant, u, W, H, vec4, tf)
+    frag, comp, cov, _ = march(variant, u, W, H, vec4, tf, fused=fused)
     return frag.reshape(H, W, 4), int(comp.sum()), int(cov.sum())

@@ -1,8 +1,11 @@
-"""float32 numpy restatement of the shadows of include/vr.h (vr_set_shadows) in separately rounded arithmetic: the light volume's build
+"""float32 numpy restatement of the shadows of include/vr.h (vr_set_shadows) in either arithmetic mode: the light volume's build
 (texel centres, the walk toward the light by repeated rounded additions, BASIC's trilinear density and opacity look-up, the scale and
 clamps, the early stop) and LIGHT's march with every blended sample's diffuse term scaled by the light volume's trilinear sample S.
 Rays come from oracle_binding.setup_ray and the jitter from oracle_binding.jitter; the samplers, the look-ups and the blend are
-proj_ref's and iso_ref's.  Harness only."""
+proj_ref's and iso_ref's.  With fused=True the samplers' and look-ups' coordinates and lerps (of the volume, the tables and the light
+volume), the dot products, the shading sum and the blend are single fused multiply-adds, as in the oracle's fused LIGHT; the light
+volume's walk (l, c, D, len, dir, step, lim, q += step), s * a, T * (1 - a') and m * S are separately rounded in both modes.
+Harness only."""
 import numpy as np
 
 import iso_ref as ir
@@ -27,16 +30,12 @@ def clip_box(u):
     return lo, hi
 
 
-def opacity_lookup(opacity, d):
+def opacity_lookup(opacity, d, fused=False):
     """BASIC's opacity look-up (textureSample(tfOpacity, linear, d), clamp-to-edge)."""
-    with np.errstate(all="ignore"):
-        x = d * f32(opacity.size) + f32(-0.5)
-        x0 = np.floor(x)
-        i0, i1 = pr._texel_pair(x0, opacity.size)
-        return pr._lerp(opacity[i0], opacity[i1], x - x0)
+    return pr.opacity_lookup(opacity, d, fused)
 
 
-def build(vec4, opacity, divisor, sigma, light_pos, lo, hi, texels=None):
+def build(vec4, opacity, divisor, sigma, light_pos, lo, hi, texels=None, fused=False):
     """The light volume: T per texel.  vec4 [nz, ny, nx, 4] (or the density plane [nz, ny, nx]); light_pos = the uniforms' world
     light position (x, y, z); lo / hi = the clip box (clip_box).  texels: (N, 3) integer (i, j, k) to compute (default: every texel;
     then the result is float32[Gz, Gy, Gx], else float32[N])."""
@@ -78,9 +77,9 @@ def build(vec4, opacity, divisor, sigma, light_pos, lo, hi, texels=None):
         inclip = inside & np.all((qi >= lo) & (qi <= hi), axis=1)
         a = np.zeros(idx.size, f32)
         if inclip.any():
-            d = pr.sample_a(dens, qi[inclip])
+            d = pr.sample_a(dens, qi[inclip], fused)
             with np.errstate(all="ignore"):
-                ai = sigma * opacity_lookup(opacity, d)
+                ai = sigma * opacity_lookup(opacity, d, fused)
                 ai = np.where(ai > f32(1.0), f32(1.0), ai)
                 ai = np.where(ai > f32(0.0), ai, f32(0.0)).astype(f32)
             a[inclip] = ai
@@ -93,17 +92,12 @@ def build(vec4, opacity, divisor, sigma, light_pos, lo, hi, texels=None):
     return T.reshape(gz, gy, gx) if full else T
 
 
-def shade_s(N, w, lpos, dif, amb, kD, kA, S):
+def shade_s(N, w, lpos, dif, amb, kD, kA, S, fused=False):
     """iso_ref.shade with the diffuse term dif * (m * S), m * S rounded first."""
-    with np.errstate(all="ignore"):
-        L = ir.normalize3(lpos[None, :] - w)
-        d = ir.dot3(N, L)
-        m = np.where(d > f32(0.0), d, f32(0.0)).astype(f32)
-        m = (m * S).astype(f32)
-        return (dif[None, :] * m[:, None]) * f32(kD) + amb[None, :] * f32(kA)
+    return ir.shade(N, w, lpos, dif, amb, kD, kA, fused, S=S)
 
 
-def march(u, W, H, vec4, tf, shadow, pixels=None):
+def march(u, W, H, vec4, tf, shadow, pixels=None, fused=False):
     """LIGHT with shadows of `pixels` (px, py) (default: the whole frame, row by row), the light volume `shadow` float32[Gz, Gy, Gx]
     (None: S = 1, which is LIGHT).  Returns (frag (N, 4), composited (N,), covered (N,), pixels)."""
     if pixels is None:
@@ -150,15 +144,15 @@ def march(u, W, H, vec4, tf, shadow, pixels=None):
         mask = inb & (dst[:, 3] < f32(1.0))
         if mask.any():
             mi = np.nonzero(mask)[0]
-            v = ir.sample_rgba(vec4, p[mi])
-            o, rgb = pr.tf_lookup(opacity, color, np.ascontiguousarray(v[:, 3]))
-            Nn = ir.normalize3(np.ascontiguousarray(v[:, :3]))
-            S = np.ones(mi.size, f32) if grid is None else pr.sample_a(grid, p[mi])
-            sh = shade_s(Nn, w[mi], lpos, dif, amb, 2.5, 0.5, S)
+            v = ir.sample_rgba(vec4, p[mi], fused)
+            o, rgb = pr.tf_lookup(opacity, color, np.ascontiguousarray(v[:, 3]), fused)
+            Nn = ir.normalize3(np.ascontiguousarray(v[:, :3]), fused)
+            S = np.ones(mi.size, f32) if grid is None else pr.sample_a(grid, p[mi], fused)
+            sh = shade_s(Nn, w[mi], lpos, dif, amb, 2.5, 0.5, S, fused)
             with np.errstate(all="ignore"):
                 col = (rgb * sh).astype(f32)
             sub = dst[mi]
-            pr._blend(col, o.astype(f32), sub, np.ones(mi.size, bool))
+            pr._blend(col, o.astype(f32), sub, np.ones(mi.size, bool), fused)
             dst[mi] = sub
             n[mi] += 1
         with np.errstate(all="ignore"):
@@ -169,7 +163,7 @@ def march(u, W, H, vec4, tf, shadow, pixels=None):
     return frag, comp, cov, pixels
 
 
-def frame(u, W, H, vec4, tf, shadow):
+def frame(u, W, H, vec4, tf, shadow, fused=False):
     """(frag [H, W, 4], composited, covered) of the whole frame."""
-    frag, comp, cov, _ = march(u, W, H, vec4, tf, shadow)
+    frag, comp, cov, _ = march(u, W, H, vec4, tf, shadow, fused=fused)
     return frag.reshape(H, W, 4), int(comp.sum()), int(cov.sum())

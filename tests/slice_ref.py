@@ -1,11 +1,13 @@
 """float32 numpy restatement of the slice views of include/vr.h (vr_slice_desc): positions b = (origin + px * du) + py * dv and
 p += dn by rounded additions, the samples inside the unit cube, their maximum / minimum / mean, one TF look-up and one
 FrontToBackBlend onto 0, and vr_present_async's bytes.  Built on proj_ref's sampler, TF look-up and blend (pinned to the oracle by
-tests/test_projection.py); adds the nearest fetch and, for VR_ARITH_FUSED, the same expressions with their multiply-adds fused
-(texture coordinates, the seven lerps, the TF coordinates and lerps).  Harness only."""
+tests/test_projection.py) in either arithmetic mode -- for VR_ARITH_FUSED the same expressions with their multiply-adds fused
+(texture coordinates, the seven lerps, the TF coordinates and lerps) through fma_ref.fma32 --; adds the nearest fetch.
+Harness only."""
 import numpy as np
 
 import proj_ref as pr
+from fma_ref import fma32  # noqa: F401  (the correctly rounded f32 a * b + c of the fused forms)
 from volumerendering_amd import capi
 
 f32 = np.float32
@@ -14,45 +16,9 @@ LINEAR, NEAREST = 0, 1
 RGBA32F, BGRA8 = 0, 1
 
 
-def fma32(a, b, c):
-    """Correctly rounded f32 a * b + c: the product is exact in f64, the f64 sum is rounded to odd (TwoSum tells whether it was
-    inexact and to which side), and rounding that to f32 is then the single rounding of the exact value."""
-    a, b, c = (np.asarray(x, f32).astype(np.float64) for x in np.broadcast_arrays(a, b, c))
-    with np.errstate(all="ignore"):
-        p = a * b
-        s = p + c
-        bb = s - p
-        e = (p - (s - bb)) + (c - bb)
-        fix = np.isfinite(s) & np.isfinite(e) & (e != 0.0) & ((s.view(np.int64) & 1) == 0)
-        toward = np.where(e > 0.0, np.inf, -np.inf)
-        s = np.where(fix, np.nextafter(s, toward), s)
-        return s.astype(f32)
-
-
-def _lerp_f(a, b, t):
-    with np.errstate(all="ignore"):
-        return fma32(b - a, t, a)
-
-
 def sample_a(dens, p, fused=False):
     """textureSample(vol, linear, p).a in either arithmetic mode."""
-    if not fused:
-        return pr.sample_a(dens, p)
-    nz, ny, nx = dens.shape
-    x = fma32(p[:, 0], f32(nx), f32(-0.5))
-    y = fma32(p[:, 1], f32(ny), f32(-0.5))
-    z = fma32(p[:, 2], f32(nz), f32(-0.5))
-    with np.errstate(all="ignore"):
-        x0, y0, z0 = np.floor(x), np.floor(y), np.floor(z)
-        fx, fy, fz = x - x0, y - y0, z - z0
-    i0, i1 = pr._texel_pair(x0, nx)
-    j0, j1 = pr._texel_pair(y0, ny)
-    k0, k1 = pr._texel_pair(z0, nz)
-    c00 = _lerp_f(dens[k0, j0, i0], dens[k0, j0, i1], fx)
-    c10 = _lerp_f(dens[k0, j1, i0], dens[k0, j1, i1], fx)
-    c01 = _lerp_f(dens[k1, j0, i0], dens[k1, j0, i1], fx)
-    c11 = _lerp_f(dens[k1, j1, i0], dens[k1, j1, i1], fx)
-    return _lerp_f(_lerp_f(c00, c10, fy), _lerp_f(c01, c11, fy), fz)
+    return pr.sample_a(dens, p, fused)
 
 
 def nearest_index(p, shape):
@@ -71,18 +37,7 @@ def sample_nearest(dens, p):
 
 
 def tf_lookup(opacity, color, d, fused=False):
-    if not fused:
-        return pr.tf_lookup(opacity, color, d)
-    x = fma32(d, f32(opacity.size), f32(-0.5))
-    xc = fma32(d, f32(color.shape[0]), f32(-0.5))
-    with np.errstate(all="ignore"):
-        x0, xc0 = np.floor(x), np.floor(xc)
-        fo, fc = x - x0, xc - xc0
-    i0, i1 = pr._texel_pair(x0, opacity.size)
-    c0, c1 = pr._texel_pair(xc0, color.shape[0])
-    o = _lerp_f(opacity[i0], opacity[i1], fo)
-    rgb = _lerp_f(color[c0, :3], color[c1, :3], fc[:, None])
-    return o, rgb
+    return pr.tf_lookup(opacity, color, d, fused)
 
 
 def orthogonal_desc(shape, axis, index, thickness=1, slot=0):

@@ -1,13 +1,16 @@
-"""float32 numpy restatement of the surface-position output of include/vr.h (vr_set_output(VR_OUTPUT_SURFACE)) in separately rounded
-arithmetic: BASIC's sample positions as proj_ref.march places them (rays from oracle_binding.setup_ray, jitter from
+"""float32 numpy restatement of the surface-position output of include/vr.h (vr_set_output(VR_OUTPUT_SURFACE)) in either
+arithmetic mode: BASIC's sample positions as proj_ref.march places them (rays from oracle_binding.setup_ray, jitter from
 oracle_binding.jitter), the alpha line of FrontToBackBlend accumulated through proj_ref's sampler and opacity look-up, the first
 in-box step after whose blend a > tau, the secant refinement on alpha, the depth formula of vr_surface_depth_async and the record of
-vr_pick.  The isosurface's surface output is iso_ref.march's refined point.  Harness only."""
+vr_pick.  The isosurface's surface output is iso_ref.march's refined point.  With fused=True the sampler's and the look-up's
+coordinates and lerps, the alpha line a = mad(1 - a, o, a) and the refinement q = mad(step, t, p_{k-1}) are single fused multiply-adds;
+the positions, the division t and the depth's matrix products are separately rounded in both modes.  Harness only."""
 import numpy as np
 
 import iso_ref as ir
 import oracle_binding as ob
 import proj_ref as pr
+from fma_ref import mad
 
 f32 = np.float32
 BASIC, LIGHT, ISO = 0, 1, 11
@@ -15,16 +18,12 @@ TAU_BASIC = f32(0.95)                          # BASIC's cut-off dst.a <= 0.95
 TAU_LIGHT = f32(np.nextafter(f32(1.0), f32(0.0)))  # 0x1.fffffep-1f: a > tau <=> !(a < 1.0), LIGHT's cut-off
 
 
-def opacity_lookup(opacity, d):
+def opacity_lookup(opacity, d, fused=False):
     """BASIC's opacity look-up of densities d (linear, clamp-to-edge): proj_ref.tf_lookup's opacity half."""
-    with np.errstate(all="ignore"):
-        x = d * f32(opacity.size) + f32(-0.5)
-        x0 = np.floor(x)
-        i0, i1 = pr._texel_pair(x0, opacity.size)
-        return pr._lerp(opacity[i0], opacity[i1], x - x0)
+    return pr.opacity_lookup(opacity, d, fused)
 
 
-def march(u, W, H, vec4, opacity, tau, pixels=None, positions=False):
+def march(u, W, H, vec4, opacity, tau, pixels=None, positions=False, fused=False):
     """Surface output of BASIC / LIGHT for `pixels` (px, py) (default: the whole frame, row by row).  Returns a dict: frag (N, 4),
     composited (N,), hit (N,), rayhit (N,) = the ray goes through the box, k (N,) = the hit's step index (-1 without one), first (N,)
     = the hit is the ray's first in-box step, q / pk / pp (N, 3) = the refined point, the hit step's position and the position of the
@@ -76,8 +75,8 @@ def march(u, W, H, vec4, opacity, tau, pixels=None, positions=False):
         with np.errstate(all="ignore"):
             run = a <= tau  # (false once a ray has hit, and for a NaN alpha)
             inb = run & np.all((p >= lo) & (p <= hi), axis=1)
-            o = opacity_lookup(opacity, pr.sample_a(dens, p))
-            new = (f32(1.0) - a) * o + a
+            o = opacity_lookup(opacity, pr.sample_a(dens, p, fused), fused)
+            new = mad(f32(1.0) - a, o, a, fused)
         n += inb
         a_prev[inb] = a[inb]
         a[inb] = new[inb]
@@ -93,7 +92,7 @@ def march(u, W, H, vec4, opacity, tau, pixels=None, positions=False):
     with np.errstate(all="ignore"):
         t = (tau - a_prev) / (a - a_prev)
         ok = hit & ~first & (t >= f32(0.0)) & (t <= f32(1.0))
-        q[ok] = step[ok] * t[ok][:, None] + pp[ok]
+        q[ok] = mad(step[ok], t[ok][:, None], pp[ok], fused)
     frag = np.zeros((M, 4), f32)
     frag[:, 3] = a
     frag[hit, :3] = q[hit]
@@ -109,15 +108,15 @@ def march(u, W, H, vec4, opacity, tau, pixels=None, positions=False):
     return out
 
 
-def frame(u, W, H, vec4, opacity, tau):
+def frame(u, W, H, vec4, opacity, tau, fused=False):
     """(frag [H, W, 4], composited, covered = pixels with a hit) of the whole frame."""
-    r = march(u, W, H, vec4, opacity, tau)
+    r = march(u, W, H, vec4, opacity, tau, fused=fused)
     return r["frag"].reshape(H, W, 4), int(r["composited"].sum()), int(r["hit"].sum())
 
 
-def iso_frame(u, W, H, vec4, tf, iso):
+def iso_frame(u, W, H, vec4, tf, iso, fused=False):
     """Surface output of ISO: (q, 1) on the hit pixels of iso_ref.march, zeros elsewhere; (frag, composited, covered)."""
-    r = ir.march(u, W, H, vec4, tf, iso)
+    r = ir.march(u, W, H, vec4, tf, iso, fused=fused)
     frag = np.zeros((W * H, 4), f32)
     frag[r["hit"], :3] = r["q"][r["hit"]]
     frag[r["hit"], 3] = f32(1.0)
@@ -148,15 +147,15 @@ def depth(frag, u, tau):
         return np.where(frag[..., 3] > f32(tau), d, f32(1.0)).astype(f32)
 
 
-def pick(variant, u, W, H, vols, tf, tau, x, y, iso=0.5):
+def pick(variant, u, W, H, vols, tf, tau, x, y, iso=0.5, fused=False):
     """The vr_pick_result of pixel (x, y) as a dict of numpy values.  vols: the uploaded slots (None = empty), tf = (opacity, colour)."""
     if variant == ISO:
-        r = ir.march(u, W, H, vols[0], tf, iso, pixels=[(x, y)])
+        r = ir.march(u, W, H, vols[0], tf, iso, pixels=[(x, y)], fused=fused)
         px = np.zeros(4, f32)
         if r["hit"][0]:
             px[:3], px[3] = r["q"][0], f32(1.0)
     else:
-        px = march(u, W, H, vols[0], tf[0], tau, pixels=[(x, y)])["frag"][0]
+        px = march(u, W, H, vols[0], tf[0], tau, pixels=[(x, y)], fused=fused)["frag"][0]
     out = dict(hit=int(px[3] > f32(tau)), uvw=np.zeros(3, f32), world=np.zeros(3, f32), depth=f32(1.0), alpha=f32(px[3]),
                voxel=np.zeros(3, np.int32), value=np.zeros((3, 4), f32))
     if not out["hit"]:

@@ -5,6 +5,7 @@ hostile volumes and levels, volume and table edits in stream order, and no inter
 import numpy as np
 import pytest
 
+import feature_cases as fc
 import host_ref as hr
 import iso_ref as ir
 import oracle_binding as ob
@@ -124,10 +125,13 @@ def test_light_cross_check(ctx, mode, kind):
 
 def test_forms_layouts_and_arithmetic(ctx):
     """Requested flavours 0 / 1 / 6 / 17 (they run as 21 / 22 / 21 / 21) x layouts 0 / 1 / 3 give the restatement's bits; fused
-    arithmetic gives one frame for all of them, close to the separate one; skipping fetches far less on exact-zero air."""
+    arithmetic gives one frame for all of them, close to the separate one and bit for bit the fused restatement's
+    (iso_ref.frame(fused=True)); skipping fetches far less on exact-zero air."""
     v, tf = air_and_core(), tf_pair()
     u = uniforms((24, 24, 24))
     ref, n_ref, cov_ref = ir.frame(u, W, H, v, tf, 0.5)
+    fref, n_fref, cov_fref = ir.frame(u, W, H, v, tf, 0.5, fused=True)
+    assert not np.array_equal(vt.bits(fref), vt.bits(ref))  # (the two modes part company on this frame)
     fetched = {}
     for mode in (capi.ARITH_SEPARATE, capi.ARITH_FUSED):
         ctx.set_arithmetic(mode)
@@ -147,6 +151,8 @@ def test_forms_layouts_and_arithmetic(ctx):
             assert np.array_equal(vt.bits(frames[0]), vt.bits(ref))
         else:
             assert float(np.max(np.abs(frames[0] - ref))) <= 1e-3
+            assert np.array_equal(vt.bits(frames[0]), vt.bits(fref)), float(np.max(np.abs(frames[0] - fref)))
+            assert (n, cov) == (n_fref, cov_fref)
     ctx.set_arithmetic(capi.ARITH_SEPARATE)
     ctx.set_volume_layout(0)
     ctx.set_kernel_flavour(0)
@@ -154,6 +160,39 @@ def test_forms_layouts_and_arithmetic(ctx):
         if key[2] != 1:
             assert f <= fetched[key[0], key[1], 1]
     assert fetched[capi.ARITH_SEPARATE, 0, 0] < fetched[capi.ARITH_SEPARATE, 0, 1] // 4
+
+
+@pytest.mark.parametrize("mode", [capi.ARITH_SEPARATE, capi.ARITH_FUSED], ids=["separate", "fused"])
+def test_refinement_edges_in_both_modes(ctx, mode):
+    """The refinement's edges in one frame (feature_cases.edge_volume, 20 x 13 x 16, under a clip box that begins inside the block):
+    hits on the ray's first in-box step (q = p_k, no refinement), refined hits (q = mad(step, t, p_{k-1}) and w_q in the mode's mad),
+    hits behind NaN samples whose t is outside [0, 1] (q = p_k), and hits where the gradient is exactly zero (a NaN normal: the
+    ambient term only).  Frames and counters of flavours 21 and 22 equal the restatement of the mode bit for bit."""
+    fused = mode == capi.ARITH_FUSED
+    v, tf = fc.edge_volume(), tf_pair()
+    u = uniforms(shape_of(v), yaw=-2.4, pitch=0.3, **fc.edge_clip)
+    r = ir.march(u, W, H, v, tf, 0.45, fused=fused)
+    hit, later = r["hit"], r["hit"] & ~r["first"]
+    with np.errstate(all="ignore"):
+        outside = later & ~((r["t"] >= f32(0.0)) & (r["t"] <= f32(1.0)))
+    refined = later & ~outside
+    zero_gradient = np.all(ir.sample_rgba(v, r["q"][hit], fused)[:, :3] == f32(0.0), axis=1)
+    print("hits", int(hit.sum()), "first step", int((hit & r["first"]).sum()), "t outside", int(outside.sum()), "refined", int(refined.sum()),
+          "zero gradient", int(zero_gradient.sum()))
+    assert (hit & r["first"]).sum() >= 20 and outside.sum() >= 20 and refined.sum() >= 20 and zero_gradient.sum() >= 20
+    assert np.array_equal(vt.bits(r["q"][outside]), vt.bits(r["pk"][outside])) and not np.array_equal(r["q"][refined], r["pk"][refined])
+    ref, n_ref, cov_ref = r["frag"].reshape(H, W, 4), int(r["composited"].sum()), int(r["covered"].sum())
+    ctx.set_arithmetic(mode)
+    try:
+        for fl in (0, 1):
+            ctx.set_kernel_flavour(fl)
+            frag, (n, cov, _) = render(ctx, 0.45, u, v, tf)
+            assert ctx.last_kernel_flavour() == (21 if fl == 0 else 22)
+            assert np.array_equal(vt.bits(frag), vt.bits(ref)), (fl, float(np.nanmax(np.abs(frag - ref))))
+            assert (n, cov) == (n_ref, cov_ref)
+    finally:
+        ctx.set_arithmetic(capi.ARITH_SEPARATE)
+        ctx.set_kernel_flavour(0)
 
 
 def test_hostile_inputs(ctx):

@@ -111,10 +111,15 @@ def test_forms_layouts_and_skipping(ctx, variant):
 
 @pytest.mark.parametrize("variant", MODES)
 def test_fused_arithmetic(ctx, variant):
-    """VR_ARITH_FUSED: every form and layout gives the same bits, within the float64 tolerance of the separate frame."""
+    """VR_ARITH_FUSED: every form and layout gives the same bits, within the float64 tolerance of the separate frame -- and they are
+    the bits of the fused restatement (proj_ref.frame(fused=True): the sampler's and look-up's coordinates and lerps and the blend
+    fused, positions and AVERAGE's sum and mean not), with its counters."""
     v, tf = phantom(), tf_pair()
     u = uniforms((16, 16, 16))
     ref, n_ref, _ = pr.frame(variant, u, W, H, v, tf)
+    fref, n_fref, cov_fref = pr.frame(variant, u, W, H, v, tf, fused=True)
+    # (the two modes part company on this frame; MINIP's minimum is the air's exact 0 in both)
+    assert variant == capi.MINIP or not np.array_equal(vt.bits(fref), vt.bits(ref))
     ctx.set_arithmetic(capi.ARITH_FUSED)
     try:
         frames = []
@@ -128,6 +133,8 @@ def test_fused_arithmetic(ctx, variant):
         for f in frames[1:]:
             assert np.array_equal(vt.bits(f), vt.bits(frames[0]))
         assert float(np.max(np.abs(frames[0] - ref))) <= 1e-3
+        assert np.array_equal(vt.bits(frames[0]), vt.bits(fref)), float(np.nanmax(np.abs(frames[0] - fref)))
+        assert ctx.counters()[:2] == (n_fref, cov_fref)
     finally:
         ctx.set_arithmetic(capi.ARITH_SEPARATE)
         ctx.set_volume_layout(0)

@@ -2,10 +2,13 @@
 prologue, kernel shell and launcher they share, csrc/vr_ray.h): the cases of feature_cases.py -- non-cubic volumes, ragged viewports,
 random cameras, clips, stepping, tables -- x family x arithmetic mode x layout x forced flavour x launch shape (synchronous,
 asynchronous into another context's frame, tiles of a world of 1 / 2 / 3, a batch of 2 - 4 cameras), one context per seed resized per
-case.  Separately rounded arithmetic: frame and counters equal the family's float32 restatement bit for bit (the restatements are
-pinned to the oracle on the same cases by tests/test_random_features.py).  Fused arithmetic: every form, layout and shape gives one
-frame, and the fused oracle's where it can speak (bounds that cut nothing, the surface alpha plane at the shader's cut-off, shadows
-at scale 0, a far bound that leaves the steps 0 .. m-1).  Fragment modes 1-4 give the oracle's BASIC frame; the flavour, candidate
+case.  In both arithmetic modes the drawn launch's frame(s) and counters equal the family's float32 restatement bit for bit: the
+separately rounded one, or with fused=True the one whose multiply-adds are the ones include/vr.h names under VR_ARITH_FUSED (both are
+pinned to the oracle of their mode on the same cases by tests/test_random_features.py, the fused multiply-add itself to exact
+arithmetic by tests/test_fma_ref.py).  Fused arithmetic in addition: every form and layout gives one frame -- which is compared with
+the restatement too -- and the fused oracle's where it can speak (bounds that cut nothing, the surface alpha plane at the shader's
+cut-off, shadows at scale 0, a far bound that leaves the steps 0 .. m-1).  Every case restates its whole frame(s); none is
+subsampled.  Fragment modes 1-4 give the oracle's BASIC frame; the flavour, candidate
 and fetched invariants of include/vr.h hold; and a plain BASIC / LIGHT frame after a feature launch is the oracle's.  Every message
 carries the seed, the case index and the whole draw: feature_cases.cases(seed)[index] replays the case."""
 import ctypes as C
@@ -178,16 +181,14 @@ def run_case(s, c, d, oracle_mode):
             if family in ("shadow", "bound"):  # (the counters are LIGHT's / the variant's: the oracle's in a fragment mode)
                 return frag, oracle(capi.LIGHT if family == "shadow" else c.bound_variant, uu)[1:]
             return frag, None
-        if not d["fused"]:
-            frag, n, cov = fc.reference(c, family, uu)
-            return frag, (n, cov)
-        return None
+        frag, n, cov = fc.reference(c, family, uu, fused=d["fused"])
+        return frag, (n, cov)
 
-    # ---- the fused mode has no restatement: all forms and layouts give one frame, which the drawn shape must give too
     # (a bounded batch is refused: only the first camera is ever rendered)
     rendered = us[:1] if family == "bound" else us
-    expect = [want(uu) for uu in rendered] if (fm or not d["fused"]) else None
-    if expect is None:
+    expect = [want(uu) for uu in rendered]
+    # ---- the fused mode: all forms and layouts give one frame, the restatement's, and the fused oracle's where it can speak
+    if d["fused"] and not fm:
         variant = s.feature_on(c, family)
         forms = []
         for layout in (0, 3, 1):
@@ -199,12 +200,13 @@ def run_case(s, c, d, oracle_mode):
                 forms.append((frag, counters[:2]))
         for frag, nc in forms[1:]:
             assert same(frag, forms[0][0]) and nc == forms[0][1], ("fused forms differ", what)
+        assert same(forms[0][0], expect[0][0]), ("fused forms against the fused restatement", forms[0][1], expect[0][1], what)
+        assert forms[0][1] == tuple(expect[0][1]), ("fused forms' counters against the fused restatement", forms[0][1], expect[0][1], what)
         ctx.set_volume_layout(0)
         ctx.set_kernel_flavour(0)
-        expect = [forms[0]]
-        for uu in rendered[1:]:
+        for uu, e in zip(rendered[1:], expect[1:]):
             frag, counters, _, _ = s.sync(variant, uu)
-            expect.append((frag, counters[:2]))
+            assert same(frag, e[0]) and counters[:2] == tuple(e[1]), ("fused frame of a batch's camera", counters, e[1], what)
         fused_pins(s, c, d, u, oracle, what)
 
     # ---- the drawn launch

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import bound_ref as br
+import feature_cases as fc
 import host_ref as hr
 import iso_ref as ir
 import oracle_binding as ob
@@ -185,10 +186,24 @@ def test_matches_restatement(ctx, bufs, cid, make, res, over):
 @pytest.mark.parametrize("variant", [capi.BASIC, capi.LIGHT], ids=["basic", "light"])
 def test_pins_to_the_oracle_in_both_arithmetic_modes(ctx, bufs, mode, variant):
     """near = 0, far = 1 is the oracle's frame; a far bound that leaves the steps 0 .. m-1 is the pixel of the oracle's frame with
-    steps_count = m (m from the restatement: ray placement, the same in both modes)."""
+    steps_count = m (m from the restatement: ray placement, the same in both modes).  And the restatement of the mode
+    (bound_ref.frame(fused=...)): the far-bounded frame and one between a near and a far plane that hold exact ties
+    (feature_cases.tie_depths: S == sigma(p_k) of an early in-box step, where >= / < part company from > / <= and a fused sigma
+    would flip the step), frames and counters bit for bit."""
+    fused = mode == capi.ARITH_FUSED
     v, tf = phantom(), steep_tf()
     u = uniforms((16, 16, 16))
     far = seeded_depth(u, 2)
+    tied, ties = [seeded_depth(u, 8), seeded_depth(u, 9)], 0
+    case = fc.Case(W=W, H=H, vec4=v, tf=tf)
+    for k, p in enumerate(tied):
+        pix, d = fc.tie_depths(case, u, np.random.default_rng(70 + k), count=8000)
+        p[pix[:, 1], pix[:, 0]] = d
+        ties += len(d)
+    assert ties >= 20
+    restated = {"far": br.frame(variant, u, W, H, v, tf, None, far, fused=fused),
+                "ties": br.frame(variant, u, W, H, v, tf, tied[0], tied[1], fused=fused)}
+    assert 0 < restated["ties"][1] < br.frame(variant, u, W, H, v, tf, fused=fused)[1]
     m = br.march(variant, u, W, H, v, tf, None, far)
     ray = m["covered"]
     assert np.all(m["prefix"]) and (m["before_far"][ray] < u.steps_count).sum() * 4 >= ray.sum()
@@ -207,6 +222,11 @@ def test_pins_to_the_oracle_in_both_arithmetic_modes(ctx, bufs, mode, variant):
                     total += k
             assert np.array_equal(vt.bits(trivial), vt.bits(ref)) and (n, cov) == (n_ref, cov_ref)
             assert np.array_equal(vt.bits(cut.reshape(-1, 4)), vt.bits(want)) and n_cut == total
+            assert np.array_equal(vt.bits(cut), vt.bits(restated["far"][0])) and (n_cut, cov) == restated["far"][1:]
+            both, (n_both, cov_both, _), _, _ = bounded(ctx, bufs, variant, u, v, tf, tied[0], tied[1], fl)
+            print("mode", mode, "variant", variant, "flavour", fl, "ties", ties, "composited", n_both, "restated", restated["ties"][1])
+            assert np.array_equal(vt.bits(both), vt.bits(restated["ties"][0])), float(np.nanmax(np.abs(both - restated["ties"][0])))
+            assert (n_both, cov_both) == restated["ties"][1:]
     finally:
         ctx.set_arithmetic(capi.ARITH_SEPARATE)
 

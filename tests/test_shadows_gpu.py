@@ -1,6 +1,7 @@
 """GPU side of the lit shader's shadows (vr_set_shadows, csrc/vr_shadow.h): at opacity scale 0 the frames are LIGHT's, bit for bit, in
 every form, layout, arithmetic mode and launch shape; the light volume equals the float32 restatement's build (shadow_ref.py) on
-hostile inputs; shadowed frames equal the restated march fed the GPU's light volume; the ring of light volumes follows edits, moving
+hostile inputs, in separately rounded and in fused arithmetic; shadowed frames equal the restated march fed the GPU's light volume,
+in both modes; the ring of light volumes follows edits, moving
 lights and launches in flight; argument checks, C3 at full size, and the host scene."""
 import math
 
@@ -162,7 +163,8 @@ BUILD_CASES = [
 @pytest.mark.parametrize("cid,make,opacity,scale,over", BUILD_CASES, ids=[c[0] for c in BUILD_CASES])
 def test_build_matches_restatement(ctx, cid, make, opacity, scale, over):
     """vr_shadow_volume at divisors 1, 2, 4 equals shadow_ref.build (separate arithmetic); the skipping build (flavour 23) and the
-    plain one (24) store the same texels; the fused mode's texels are within 2e-3 of the separate mode's."""
+    plain one (24) store the same texels; the fused mode's texels are within 2e-3 of the separate mode's, and bit for bit those of
+    shadow_ref.build(fused=True)."""
     v = make()
     tf = tf_pair()
     if opacity is not None:
@@ -186,6 +188,8 @@ def test_build_matches_restatement(ctx, cid, make, opacity, scale, over):
             fused, _ = ctx.shadow_volume()
             ctx.set_arithmetic(capi.ARITH_SEPARATE)
             assert float(np.max(np.abs(fused - got))) <= 2e-3, (cid, r)
+            fref = sr.build(v, tf[0], r, scale, u.light_pos[:3], lo, hi, fused=True)
+            assert np.array_equal(vt.bits(fused), vt.bits(fref)), (cid, r, "fused", float(np.max(np.abs(fused - fref))))
             if cid == "clip_all":
                 assert np.all(got == f32(1.0))
             if cid == "scale_huge":
@@ -194,6 +198,48 @@ def test_build_matches_restatement(ctx, cid, make, opacity, scale, over):
         ctx.set_shadows(0)
         ctx.set_kernel_flavour(0)
         ctx.set_arithmetic(capi.ARITH_SEPARATE)
+
+
+def ragged_noise():
+    """13 x 20 x 7 voxels of noise with exact-zero air: no side is a multiple of the divisors or of the brick edge 4."""
+    raw = np.random.default_rng(23).integers(0, 4096, size=(7, 20, 13)).astype(np.uint16)
+    raw[raw < 1800] = 0
+    return ob.precompute_gradient(ob.normalize_data(hr.raw_to_vec4(raw)))
+
+
+@pytest.mark.parametrize("where,light", [("outside", (0.9, 1.7, -0.6, 1.0)), ("inside", (0.11, -0.07, 0.03, 1.0))])
+def test_fused_build_matches_fused_restatement(ctx, where, light):
+    """VR_ARITH_FUSED: the texels of vr_shadow_volume equal shadow_ref.build(fused=True) bit for bit -- the sampler's and the opacity
+    look-up's coordinates and lerps fused, the walk (D, len, dir, step, lim, q += step), s * a and T * (1 - a') not -- at divisors 1
+    and 4 of a 13 x 20 x 7 volume, from the skipping build (23) and the plain one (24), with the light outside the box and inside
+    it, under a clip box that cuts the light rays; and the two modes' texels differ, so the comparison can tell them apart."""
+    v, tf = ragged_noise(), fc_steep_tf()
+    u = uniforms(shape_of(v), light_pos=light, clip_x=(0.15, 0.1), clip_y=(0.2, 0.0), clip_z=(0.0, 0.25))
+    setup(ctx, u, v, tf)
+    lo, hi = sr.clip_box(u)
+    ctx.set_arithmetic(capi.ARITH_FUSED)
+    try:
+        for r in (1, 4):
+            ref = sr.build(v, tf[0], r, 1.0, u.light_pos[:3], lo, hi, fused=True)
+            assert np.any(ref < f32(1.0)) and (where == "inside" or np.any(ref == f32(1.0)))
+            if r == 1:
+                assert not np.array_equal(vt.bits(ref), vt.bits(sr.build(v, tf[0], r, 1.0, u.light_pos[:3], lo, hi)))
+            for fl in (0, 1):
+                ctx.set_kernel_flavour(fl)
+                ctx.volume_upload(0, v)  # (a volume change empties the ring: every form builds anew)
+                ctx.set_shadows(r, 1.0)
+                got, dims = ctx.shadow_volume()
+                assert dims == sr.grid_of(v.shape, r)
+                assert np.array_equal(vt.bits(got), vt.bits(ref)), (where, r, fl, float(np.max(np.abs(got - ref))))
+    finally:
+        ctx.set_shadows(0)
+        ctx.set_kernel_flavour(0)
+        ctx.set_arithmetic(capi.ARITH_SEPARATE)
+
+
+def fc_steep_tf(res=64):
+    """The steep ramp of the random sweep: opacity min(1, 4 * ramp), exactly 0 at density 0 (something for flavour 23 to skip)."""
+    return np.minimum(hr.default_opacity_tf(res) * f32(4.0), f32(1.0)).astype(f32), hr.default_color_tf(res)
 
 
 def test_light_on_a_texel_centre(ctx):
@@ -240,6 +286,31 @@ def test_frames_match_restatement(ctx, scale):
     finally:
         ctx.set_shadows(0)
         ctx.set_kernel_flavour(0)
+
+
+def test_fused_frames_match_fused_restatement(ctx):
+    """VR_ARITH_FUSED: shadowed frames of flavours 23 and 24 equal shadow_ref.march(fused=True) fed the GPU's fused light volume, bit
+    for bit and with the counters: the light volume's lerps fused, m * S rounded before dif_c * (m * S), the shading sum and the
+    blend fused as in the oracle's fused LIGHT."""
+    v, tf = phantom(), tf_pair()
+    u = uniforms(toggles=(1, 1, 0, 0), light_pos=(0.3, 2.0, -0.4, 1.0))
+    setup(ctx, u, v, tf)
+    ctx.set_arithmetic(capi.ARITH_FUSED)
+    try:
+        ctx.set_shadows(2, 1.0)
+        grid, _ = ctx.shadow_volume()
+        assert np.any(grid < f32(0.5))
+        ref, n_ref, cov_ref = sr.frame(u, W, H, v, tf, grid, fused=True)
+        assert not np.array_equal(vt.bits(ref), vt.bits(sr.frame(u, W, H, v, tf, grid)[0]))
+        for fl in (0, 1):
+            ctx.set_kernel_flavour(fl)
+            frag, (n, cov, f) = render(ctx)
+            assert np.array_equal(vt.bits(frag), vt.bits(ref)), (fl, float(np.max(np.abs(frag - ref))))
+            assert (n, cov) == (n_ref, cov_ref)
+    finally:
+        ctx.set_shadows(0)
+        ctx.set_kernel_flavour(0)
+        ctx.set_arithmetic(capi.ARITH_SEPARATE)
 
 
 def test_async_edit_moving_light_and_launches_in_flight(ctx, others):

@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import feature_cases as fc
 import host_ref as hr
 import iso_ref as ir
 import oracle_binding as ob
@@ -179,8 +180,9 @@ def test_hostile_inputs(ctx):
 @pytest.mark.parametrize("variant,tau", [(capi.BASIC, float(sr.TAU_BASIC)), (capi.LIGHT, float(sr.TAU_LIGHT))], ids=["basic", "light"])
 def test_alpha_plane_is_the_colour_frames(ctx, mode, variant, tau):
     """At the shader's own cut-off .w is the .a plane of the GPU's colour frame of the same context and of the oracle's, with equal
-    composited counts, in both arithmetic modes; every hit's xyz lies between two consecutive positions of its ray (the positions are
-    the same in both modes; the restatement does not model the fused mad, so WHICH pair is not asserted there)."""
+    composited counts, in both arithmetic modes; the whole frame -- the refined q included -- is the restatement's of the mode
+    (surf_ref.march(fused=...): the alpha line and q = mad(step, t, p_{k-1}) in the mode's mad); every hit's xyz lies between two
+    consecutive positions of its ray (the positions are the same in both modes)."""
     v, tf = phantom(), steep_tf()
     u = uniforms((16, 16, 16))
     ctx.set_arithmetic(mode)
@@ -196,10 +198,10 @@ def test_alpha_plane_is_the_colour_frames(ctx, mode, variant, tau):
     assert np.array_equal(vt.bits(surf[..., 3]), vt.bits(colour[..., 3]))
     assert np.array_equal(vt.bits(surf[..., 3]), vt.bits(ref[..., 3]))
     assert cov == int((ref[..., 3] > f32(tau)).sum())
-    r = sr.march(u, W, H, v, tf[0], tau, positions=True)
+    r = sr.march(u, W, H, v, tf[0], tau, positions=True, fused=mode == capi.ARITH_FUSED)
     flat = surf.reshape(-1, 4)
-    if mode == capi.ARITH_SEPARATE:
-        assert np.array_equal(vt.bits(flat), vt.bits(r["frag"]))
+    assert np.array_equal(vt.bits(flat), vt.bits(r["frag"]))
+    assert (n, cov) == (int(r["composited"].sum()), int(r["hit"].sum()))
     hit = flat[:, 3] > f32(tau)
     P = r["positions"][:, hit]  # (steps, hits, 3)
     q = flat[hit, :3][None]
@@ -210,14 +212,16 @@ def test_alpha_plane_is_the_colour_frames(ctx, mode, variant, tau):
 
 def test_layouts_shapes_and_arithmetic(ctx):
     """Layouts 0 / 3 / 1 x flavours 0 / 1 / 6 / 17, synchronous, asynchronous, tiles of a world of 3 and a batch of four cameras give
-    one frame per arithmetic mode -- the restatement's in the separately rounded one."""
+    one frame per arithmetic mode -- the restatement's of that mode, counters included."""
     v, tf = air_and_core(), steep_tf()
     us = [uniforms((24, 24, 24), yaw=0.6 + 0.4 * k, clip_z=(0.0, 0.1 * k)) for k in range(4)]
-    refs = [sr.frame(u, W, H, v, tf[0], 0.5) for u in us]
+    all_refs = {mode: [sr.frame(u, W, H, v, tf[0], 0.5, fused=mode == capi.ARITH_FUSED) for u in us]
+                for mode in (capi.ARITH_SEPARATE, capi.ARITH_FUSED)}
     others = [capi.Context(W, H, 0) for _ in range(4)]
     try:
         for mode in (capi.ARITH_SEPARATE, capi.ARITH_FUSED):
             ctx.set_arithmetic(mode)
+            refs = all_refs[mode]
             frames = []
             for layout in (0, 3, 1):
                 ctx.set_volume_layout(layout)
@@ -225,8 +229,7 @@ def test_layouts_shapes_and_arithmetic(ctx):
                     ctx.set_kernel_flavour(fl)
                     frag, (n, cov, _) = surface(ctx, capi.LIGHT, 0.5, us[0], v, tf)
                     assert ctx.last_kernel_flavour() == (26 if fl == 1 else 25)
-                    if mode == capi.ARITH_SEPARATE:
-                        assert (n, cov) == refs[0][1:]
+                    assert (n, cov) == refs[0][1:], (mode, layout, fl)
                     frames.append(frag)
             ctx.set_volume_layout(0)
             ctx.set_kernel_flavour(0)
@@ -258,9 +261,8 @@ def test_layouts_shapes_and_arithmetic(ctx):
             frames.append(batch[0])
             for f in frames[1:]:
                 assert np.array_equal(vt.bits(f), vt.bits(frames[0])), mode
-            if mode == capi.ARITH_SEPARATE:
-                for b, r in zip(batch, refs):
-                    assert np.array_equal(vt.bits(b), vt.bits(r[0]))
+            for b, r in zip(batch, refs):
+                assert np.array_equal(vt.bits(b), vt.bits(r[0])), mode
     finally:
         ctx.set_output(capi.OUTPUT_COLOR)
         ctx.set_arithmetic(capi.ARITH_SEPARATE)
@@ -268,6 +270,39 @@ def test_layouts_shapes_and_arithmetic(ctx):
         ctx.set_kernel_flavour(0)
         for o in others:
             o.close()
+
+
+@pytest.mark.parametrize("mode", [capi.ARITH_SEPARATE, capi.ARITH_FUSED], ids=["separate", "fused"])
+def test_refinement_edges_in_both_modes(ctx, mode):
+    """The refinement's edges (feature_cases.edge_volume under a clip box that begins inside the block), frames and counters against
+    the restatement of the mode, both flavours.  BASIC's surface at tau 0.5: hits on the ray's first in-box step (q = p_k) beside
+    refined ones (q = mad(step, t, p_{k-1})); its t = (tau - a_prev) / (a - a_prev) cannot leave [0, 1] (a_prev <= tau < a).  ISO's
+    surface at level 0.45: first-step hits, refined hits and hits behind NaN samples, whose t is NaN and q = p_k; a zero gradient at
+    the hit plays no part in a position."""
+    fused = mode == capi.ARITH_FUSED
+    v, tf = fc.edge_volume(), steep_tf()
+    u = uniforms(shape_of(v), yaw=-2.4, pitch=0.3, **fc.edge_clip)
+    a = sr.march(u, W, H, v, tf[0], 0.5, fused=fused)
+    assert (a["hit"] & a["first"]).sum() >= 20 and (a["hit"] & ~a["first"]).sum() >= 20
+    i = ir.march(u, W, H, v, tf, 0.45, fused=fused)
+    later = i["hit"] & ~i["first"]
+    with np.errstate(all="ignore"):
+        outside = later & ~((i["t"] >= f32(0.0)) & (i["t"] <= f32(1.0)))
+    assert (i["hit"] & i["first"]).sum() >= 20 and outside.sum() >= 20 and (later & ~outside).sum() >= 20
+    want = {capi.BASIC: sr.frame(u, W, H, v, tf[0], 0.5, fused=fused), capi.ISO: sr.iso_frame(u, W, H, v, tf, 0.45, fused=fused)}
+    ctx.set_arithmetic(mode)
+    ctx.set_iso_value(0.45)
+    try:
+        for variant, (ref, n_ref, cov_ref) in want.items():
+            for fl in (0, 1):
+                ctx.set_kernel_flavour(fl)
+                frag, (n, cov, _) = surface(ctx, variant, 0.5, u, v, tf)
+                assert same(frag, ref), (variant, fl, float(np.nanmax(np.abs(frag - ref))))
+                assert (n, cov) == (n_ref, cov_ref), (variant, fl)
+    finally:
+        ctx.set_arithmetic(capi.ARITH_SEPARATE)
+        ctx.set_kernel_flavour(0)
+        ctx.set_iso_value(0.5)
 
 
 def test_iso_points_and_unsupported_variants(ctx):
