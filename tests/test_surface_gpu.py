@@ -396,8 +396,9 @@ def test_depth(ctx):
 
 def test_pick(ctx):
     """vr_pick against the restatement's record for hit, missed and uncovered pixels of LIGHT and ISO scenes; value[] is the uploaded
-    voxel of every slot of slot 0's size; after a pick the frame, the counters and the last flavour still describe the render before
-    it; a pixel outside the viewport is refused."""
+    voxel of every slot of slot 0's size; after a pick the frame and everything the context reports about the last launch (counters,
+    flavour, covered pixels, whether vr_last_timing has a frame, the number of kernel times recorded, the kernel choice) still describe
+    the render before it; a pixel outside the viewport is refused."""
     v, tf = phantom(), steep_tf()
     dose = vt.make_volume("sphere", 16)
     u = uniforms((16, 16, 16))
@@ -413,6 +414,15 @@ def test_pick(ctx):
             pixels.append((int(mx[0]), int(my[0])))
         colour, _, _ = vt.gpu_render(ctx, capi.LIGHT, u, [v], [tf])
         counters, flavour = ctx.counters(), ctx.last_kernel_flavour()
+
+        # Timing validity has no getter of its own: ctx.last_timing() RAISING (VR_ERR_NOT_READY) after a pick is the check that it was
+        # restored.  The counters have been fetched just above, so the picks below restore them fetched, never pending.
+        def last_launch():
+            timing = ctx.last_timing()
+            return (ctx.counters(), ctx.last_kernel_flavour(), ctx.covered_pixels(), len(timing), len(ctx.kernel_times()),
+                    ctx.kernel_choice(), ctx.block_trace().shape)
+
+        before = last_launch()
         ctx.set_surface_threshold(0.5)
         for variant, iso in ((capi.LIGHT, 0.5), (capi.BASIC, 0.5), (capi.ISO, 0.3)):
             ctx.set_iso_value(iso)
@@ -424,6 +434,7 @@ def test_pick(ctx):
                     assert np.array_equal(vt.bits(got[key]), vt.bits(want[key])), (variant, x, y, key)
                 assert np.array_equal(got["voxel"], want["voxel"]), (variant, x, y)
             assert ctx.counters() == counters and ctx.last_kernel_flavour() == flavour
+            assert last_launch() == before, variant
             assert np.array_equal(vt.bits(ctx.download()[0]), vt.bits(colour))
         assert ctx.pick(capi.LIGHT, *pixels[0]).hit == 1
         for x, y in ((W, 0), (0, H)):

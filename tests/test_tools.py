@@ -1,4 +1,5 @@
-"""CPU tests of the analysis tools that read files (no GPU): tools/launch_gap.py --read on a synthetic kernel trace."""
+"""CPU tests of the analysis tools that read files (no GPU): tools/launch_gap.py --read on a synthetic kernel trace,
+tools/device_code_diff.py's comparison on literal listings."""
 import os
 import subprocess
 import sys
@@ -27,3 +28,34 @@ def test_launch_gap_reads_a_kernel_trace(tmp_path):
     assert "end -> next start: median 17.0 us" in out
     assert "vr::order_blocks_kernel: 11 launches, 60.0 us each, queues ['3']" in out
     assert "queues of the march launches: ['4']" in out
+
+
+def test_device_code_diff_compares_listings():
+    """tools/device_code_diff.py on two literal listings: the same instructions at other addresses are equal; a changed
+    instruction, a missing and a new symbol are each reported under their mangled names."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import device_code_diff as dcd
+    finally:
+        sys.path.pop(0)
+    a = """
+Disassembly of section .text:
+
+0000000000001900 <_ZN2vr12march_kernelILi0EEEvNS_10MarchBatchE>:
+\ts_load_dwordx2 s[0:1], s[4:5], 0x0                         // 000000001900: C0060002 00000000
+\tv_add_f32_e32 v1, v0, v2                                   // 000000001908: 02020500
+\ts_endpgm                                                   // 00000000190C: BF810000
+
+0000000000001a00 <_ZN2vr14present_kernelEPK15HIP_vector_typeIfLj4EEPji>:
+\tv_mov_b32_e32 v0, 0                                        // 000000001A00: 7E000280
+\ts_endpgm                                                   // 000000001A04: BF810000
+"""
+    moved = a.replace("0000000000001900", "0000000000002900").replace("// 00000000190", "// 00000000290")
+    assert dcd.compare(a, moved) == ([], [], [])
+    assert len(dcd.functions(a)["_ZN2vr12march_kernelILi0EEEvNS_10MarchBatchE"]) == 3
+    changed = a.replace("v_add_f32_e32 v1, v0, v2", "v_fma_f32 v1, v0, v2, v3")
+    assert dcd.compare(a, changed) == (["_ZN2vr12march_kernelILi0EEEvNS_10MarchBatchE"], [], [])
+    renamed = a.replace("_ZN2vr14present_kernelE", "_ZN2vr15present2_kernelE")
+    differ, missing, new = dcd.compare(a, renamed)
+    assert differ == [] and missing == ["_ZN2vr14present_kernelEPK15HIP_vector_typeIfLj4EEPji"]
+    assert new == ["_ZN2vr15present2_kernelEPK15HIP_vector_typeIfLj4EEPji"]

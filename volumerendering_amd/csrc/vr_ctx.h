@@ -1,0 +1,392 @@
+// vr_ctx.h -- the context behind the C ABI (struct vr_ctx), the owners of its HIP resources, its error reporting.
+// Part of vr_api.hip's translation unit: included there once, behind vr_launch.h and `using namespace vr`.
+#pragma once
+
+// ---- owners: move-only, released by their destructors (vr_destroy drains the device, then deletes the context) ---------------------
+
+// Memory that knows its capacity, in elements of T (bytes for void): device memory (DevBuf) or pinned host memory (PinnedBuf).
+template <typename T, bool kPinned>
+struct Buf {
+    T* p = nullptr;
+    size_t cap = 0;
+    Buf() = default;
+    Buf(Buf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    Buf& operator=(Buf&& o) noexcept { return std::swap(p, o.p), std::swap(cap, o.cap), *this; }
+    ~Buf() { release(); }
+    operator T*() const { return p; }
+    void release()
+    {
+        if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        cap = 0;
+    }
+    // n elements, the old contents gone; empty (capacity 0) if the allocation fails.  zeroed: pinned memory that the device reports into
+    // and the host reads before the first report
+    hipError_t reserve(size_t n, bool zeroed = false)
+    {
+        release();
+        const size_t bytes = n * sizeof(std::conditional_t<std::is_void<T>::value, char, T>);
+        const hipError_t e = kPinned ? hipHostMalloc((void**)&p, bytes, hipHostMallocDefault) : hipMalloc((void**)&p, bytes);
+        if (e != hipSuccess) p = nullptr;
+        else if (kPinned && zeroed) std::memset(p, 0, bytes);
+        cap = p ? n : 0;
+        return e;
+    }
+    T* detach() { return cap = 0, std::exchange(p, nullptr); }  // hands the memory over (the retire lists)
+};
+template <typename T> using DevBuf = Buf<T, false>;
+template <typename T> using PinnedBuf = Buf<T, true>;
+
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+    Event& operator=(Event&& o) noexcept { return std::swap(e, o.e), *this; }
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+    hipError_t create(unsigned flags = hipEventDefault)
+    {
+        const hipError_t rc = hipEventCreateWithFlags(&e, flags);
+        if (rc != hipSuccess) e = nullptr;
+        return rc;
+    }
+};
+
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(Stream&& o) noexcept : s(o.s) { o.s = nullptr; }
+    Stream& operator=(Stream&& o) noexcept { return std::swap(s, o.s), *this; }
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+    hipError_t create()
+    {
+        const hipError_t rc = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+        if (rc != hipSuccess) s = nullptr;
+        return rc;
+    }
+};
+
+// ---- the context's parts -------------------------------------------------------------------------------------------------------------
+
+constexpr int kRing = 256;    // vr_kernel_times: launches remembered
+constexpr int kInFlight = 8;  // launches that may be in flight at a time (record buffers used in turn; twice the streams, so that
+                               // a caller with four frames in flight never blocks on its oldest launch)
+constexpr int kStreams = 4;   // vr_stream(): streams for frames in flight
+constexpr int kOrderRing = 16;  // launch-order buffers: written behind launch k, read by launches k+3 .. k+6 only (see enqueue_render)
+constexpr int kGen = 4;         // generations of each table and of the distance field (vr_tf_upload_*_async)
+constexpr int kStage = 8;       // pinned staging buffers of the asynchronous table edits
+constexpr int kEditSeen = 8;    // streams remembered to have waited for the latest asynchronous edit
+constexpr int kShadowRing = 4;  // light volumes kept (vr_set_shadows): one per key, the least recently used one rebuilt
+
+// A device buffer of one generation (capacity in bytes): written by an edit, read by the launches that captured it while it was
+// current, on any streams.  Rewritten only behind every one of them (reuse_wait): reader[k] is the order_seq of the latest launch in
+// record slot k (seq % kInFlight) that read it, -1 if none since it was last written.
+struct GenBuf : DevBuf<void> {
+    long long reader[kInFlight];
+    GenBuf() { written(); }
+    void written()
+    {
+        for (auto& r : reader) r = -1;
+    }
+};
+
+// Something built on `stream` with `ev` recorded behind the build: a launch on another stream waits for the event once (seen), none
+// after a draining call (pending = false).
+struct BuiltOn {
+    Event ev;
+    hipStream_t stream = nullptr;
+    bool pending = false;
+    hipStream_t seen[kEditSeen] = {};
+    int seen_next = 0;
+    void built(hipStream_t s)  // (ev has been recorded on s)
+    {
+        stream = s;
+        pending = true;
+        for (auto& x : seen) x = nullptr;
+    }
+    hipError_t order_behind(hipStream_t s)  // a launch on s comes after the build
+    {
+        if (!pending || s == stream) return hipSuccess;
+        for (auto x : seen)
+            if (x == s) return hipSuccess;
+        const hipError_t e = hipStreamWaitEvent(s, ev, 0);
+        if (e == hipSuccess) seen[seen_next++ % kEditSeen] = s;
+        return e;
+    }
+};
+
+// A record slot: what launch order_seq takes for itself, k = order_seq % kInFlight (claim_slot), and gives back behind its kernel
+// (finish_slot).  Several frames can be in flight on different streams (the next ones fill the machine while the first one's long rays
+// drain); a march, a slice and a histogram each keep records of their own in the slot and leave the others' alone.
+struct RecordSlot {
+    Event done;                               // recorded behind the launch that last used the slot (any stream)
+    bool used = false;
+    DevBuf<unsigned long long> block_counts;  // march: per-workgroup records (store_block_counts), kBlockRecord words per block
+    bool pw_heads_dirty = false;              // the slot's last persistent launch had no sort behind it to clear its heads (d_pw_heads)
+    DevBuf<unsigned long long> slice_counts;  // slice views: the wavefront records, three words per workgroup
+    DevBuf<unsigned long long> hist_stats;    // histograms: the three counters
+};
+
+// A volume slot: the vec4 voxels as uploaded and what refresh_bricks derives from them.
+struct VolumeSlot {
+    DevVolume vol = {};        // the kernels' view (vol.data = voxels, once an upload has succeeded)
+    DevBuf<float4> voxels;
+    size_t bytes() const { return voxels.cap * sizeof(float4); }
+    DevBuf<float2> bricks;     // per brick: (max density, max(r,g,b)) -- empty-space skipping
+    DevBuf<float> dens;        // scalar density plane (DevVolume::dens)
+    DevBuf<float4> bricked;    // the voxels again in 4 x 4 x 4 bricks (DevVolume::bricked), what the march kernels gather from (in slots:
+                               // bricks x 64)
+    DevBuf<float> bdens;       // ... and their density plane in the same order
+    bool grad_derived = false;  // .rgb verified to be PreComputeGradient(false) of .a, bit for bit
+    // Intensity projections (vr_proj.h), the isosurface (vr_iso.h) and slice views (vr_slice.h): (min, max) of the slot per
+    // empty-space brick and over the whole volume ([0]: what the projections and the isosurface read), rebuilt on the launch's stream
+    // by the first skipping launch that reads them after a volume change (proj_epoch = the brick_epoch they were built at).  Launches
+    // on other streams wait once for the event behind the build (proj_built).
+    DevBuf<float2> proj_rec;
+    DevBuf<float2> proj_range;
+    unsigned long long proj_epoch = ~0ull;
+    BuiltOn proj_built;
+};
+
+// What the reporting calls (vr_last_counters, vr_last_kernel_flavour, vr_last_timing, vr_kernel_times, vr_kernel_choice,
+// vr_download_tiles, vr_last_block_trace) read about the most recent march launch.  vr_pick copies it out and back as one value.
+struct LastLaunch {
+    int flavour = 0;           // the flavour the launch resolved to
+    bool unmeasured = false;   // its family is never measured (KernelForm::measured): vr_kernel_choice reports no candidates
+    int tiles = 0;             // tiles rendered by the last vr_render_tiles
+    int cnt_buf = 0;           // the record slot the launch wrote
+    int cnt_blocks = 0;
+    size_t cnt_offset = 0;     // ... and where in that buffer the records of its last frame start (u64 words)
+    bool cnt_pending = false;  // its block counts are not summed / copied to h_counters yet
+    bool timed = false;        // it recorded Timing's events (vr_last_timing)
+    long long ring_head = 0;   // total launches recorded in the KernelRing since the last reset
+};
+
+// One march launch as its caller asks for it: ONE frame with the context's uniforms into `out` (nullptr -> ctx-owned buffer), or, with
+// batch_u / batch_out, n_frames (2 .. kBatchMax) frames of the same scene, each with its own uniforms and output buffer.
+struct RenderRequest {
+    int variant = 0, rank = 0, world = 1;
+    bool packed = false, frame_events = false;
+    float4* out = nullptr;
+    hipStream_t stream = nullptr;
+    int n_frames = 1;
+    const vr_uniforms* batch_u = nullptr;
+    void* const* batch_out = nullptr;
+    int pick_px[2] = {-1, -1};  // vr_pick: the pixel the launch is confined to (pick_px[0] < 0: none)
+    // derived once from the request and the context's settings (check_render_args)
+    bool surface = false;  // surface-position output (vr_set_output; a pick launch whatever the setting)
+    bool bounded = false;  // between ray bounds (vr_set_ray_bounds; a pick launch ignores them)
+};
+
+struct vr_ctx {
+    int device = 0;
+    uint32_t W = 0, H = 0;
+    Stream stream;
+    VolumeSlot vols[VR_MAX_VOLUMES];
+    int arith = VR_ARITH_SEPARATE;             // vr_set_arithmetic
+    int layout_mode = 0;                       // vr_set_volume_layout: 0 bricked copy + its density plane, 1 vec4 voxels only,
+                                               // 3 x-fastest voxels + density plane (2, gradients on the fly, was removed)
+    DevBuf<float2> merged_bricks;              // VOLUME_MASK: (CT density max, mask rgb max), rebuilt when stale
+    bool merged_stale = true;
+    unsigned char* brick_dist = nullptr;       // distance field over the records in use (field[field_cur]); key below says for what
+    GenBuf field[kGen];                        // its generations (an asynchronous opacity edit builds the next one)
+    int field_cur = 0;
+    DevBuf<unsigned char> dist_tmp;            // the y pass's output, the z pass's input
+    int dist_bn[3] = {0, 0, 0};                // bricks per axis of the field
+    const void* dist_records = nullptr;
+    unsigned long long dist_epoch = ~0ull;     // volume-change counter the field was built at
+    int dist_z = -2, dist_res = 0, dist_rgb = -1;
+    unsigned long long brick_epoch = 0;        // bumped whenever any brick table changes
+    int tf_zero_prefix[VR_MAX_TFS] = {-1, -1};  // zero prefix of each opacity table, -1 if none / not finite
+    bool tf_color_finite[VR_MAX_TFS] = {false, false};
+    bool tf_opacity_finite[VR_MAX_TFS] = {false, false};
+    DevTF tf[VR_MAX_TFS] = {};
+    GenBuf tf_buf[VR_MAX_TFS][2][kGen];        // [slot][opacity, colour]: the table's generations, tf_cur the one in use (DevTF layout)
+    int tf_cur[VR_MAX_TFS][2] = {};
+    // Asynchronous edits (vr_tf_upload_*_async): each records edit_ev on its stream, behind the one before it; a launch on
+    // another stream waits for it once (edit_seen), nothing once a draining call has seen it (drained_gen).
+    Event edit_ev;
+    hipStream_t edit_stream = nullptr;
+    unsigned long long edit_gen = 0, drained_gen = 0;
+    struct EditSeen {
+        hipStream_t s = nullptr;
+        unsigned long long gen = 0;
+    } edit_seen[kEditSeen];
+    int seen_next = 0;
+    struct Stage {  // pinned copy of an edited table, in the DevTF layout (capacity in bytes); reused behind its copy's event
+        PinnedBuf<void> h;
+        Event done;
+        bool used = false;
+    } stage[kStage];
+    unsigned stage_next = 0;
+    std::vector<void*> retired_dev, retired_host;  // replaced on a non-blocking path: freed by the next draining call (drained)
+    // What each field build reports (SkipSummary, pinned, one per field generation) and the device words it accumulates in.
+    // skip_pending: a build's count and box have not reached the host yet -- launches use the unbounded box meanwhile.
+    PinnedBuf<SkipSummary> h_skip;
+    DevBuf<SkipSumDev> d_skip_sum;
+    unsigned long long skip_gen = 0;
+    bool skip_pending = false;
+    int skip_box[6] = {0x7fffffff, 0x7fffffff, 0x7fffffff, -1, -1, -1};  // of the field in use, once known (vr_skip_field)
+    unsigned long long skip_active = 0;
+    long long unbounded_launches = 0;
+    vr_uniforms u = {};
+    bool have_uniforms = false;
+    DevBuf<float4> d_frame;
+    DevBuf<float4> d_tiles;
+    DevBuf<uint32_t> d_present;
+    DevBuf<unsigned long long> d_counters;  // [3] composited, covered, fetched
+    RecordSlot slot[kInFlight];
+    DevBuf<unsigned> d_pw_heads;  // queue heads of the persistent-wavefront kernel: kInFlight x 8 heads, 256 B apart
+    // Longest-first launch order (MarchParams::order): behind every march launch one small kernel sorts that launch's
+    // blocks by their longest ray chain; a later launch of the same shape takes its blocks in that order.
+    struct OrderSlot {
+        DevBuf<unsigned> buf;
+        hipStream_t stream = nullptr;
+        Event sorted;
+        unsigned long long key = 0, seq = 0;
+        unsigned long long scene_key = 0;  // what the launch rendered, whatever kernel form it took (the chain length's key)
+        bool valid = false;
+    } order_ring[kOrderRing];
+    PinnedBuf<unsigned long long> h_span;  // kRing words: duration of launch q in 100 MHz ticks + 1, from its records (0 = not known)
+    bool ring_events[kRing] = {};          // launch q was timed with the events k0 / k1 instead (no sort behind it)
+    PinnedBuf<unsigned long long> h_end;   // kRing words: end of launch q's last workgroup on the 100 MHz device clock, | 1 (0 = not known)
+    PinnedBuf<unsigned> h_chain;  // one word per ring slot: longest ray chain + 1 of that launch (0 = not known yet)
+    // Measured kernel choice (flavour 0): every kernel form is bit-identical, so the context tries the eligible ones on
+    // the caller's own frames and keeps the fastest by the launches' own records -- per "what is launched of what".
+    struct Tune {
+        unsigned long long key = 0;   // shader, share, viewport, frames per launch, frames in flight, scene epoch, arithmetic, layout (0 = free)
+        unsigned long long shape = 0; // ... the same without the scene's epochs: a new scene starts from what the last one of this shape kept
+        int n = 0, cand[6] = {};      // the eligible flavours; cand[0] = the prior's pick (what runs while nothing is known)
+        int cur = 0, issued = 0;      // candidate on trial, launches it has had
+        int per = 3, settle = 4;      // launches per candidate; launches before the trial starts (no launch order exists yet)
+        long long launch[6][16] = {}; // ring_head of every trial launch of every candidate (other shapes' launches may lie in between)
+        int choice = -1;              // index into cand of the kernel kept (-1 = trial running)
+        unsigned chain_ref = 0;       // longest ray chain + 1 when it was chosen: the trial re-opens when that has moved by a quarter
+        float cost[6] = {};           // ms per launch measured (0 = no data)
+        unsigned long long used = 0;  // (least recently used slot is recycled)
+    } tune[8];
+    unsigned long long tune_clock = 0;
+    unsigned long long tf_epoch = 0;  // bumped by every table upload
+    int tune_mode = 1;                // VR_EXP_TUNE=0: the prior alone (round 3's thresholds)
+    int frames_in_flight = 1;                 // vr_hint_frames_in_flight: frames the caller keeps in flight on different streams
+    unsigned long long order_seq = 0;
+    Stream flight[kStreams];  // vr_stream(): streams probed to run side by side (created on first use)
+    int n_flight = 0;
+    Stream order_stream;  // the sorts run here, behind their launch's event: never on a frame's critical path
+    LastLaunch last;
+    bool event_timing = false;                 // vr_set_kernel_timing(VR_TIMING_EVENTS): time every launch with HIP events
+    PinnedBuf<unsigned long long> h_counters;  // [3]: the last launch's block counts summed (fetch_counters)
+    struct {  // vr_last_timing's events (last.timed: whether the last launch recorded them)
+        Event ev_begin, ev_k0, ev_k1, ev_end;
+    } tm;
+    struct {  // one (start, stop) event pair per render call, reused round-robin (last.ring_head counts the launches)
+        Event k0[kRing], k1[kRing];
+    } ring;
+    int flavour = 0;
+    int n_cus = 256;          // compute units of the device
+    int default_flavour = 0;  // what flavour 0 resolves to (experiment knob VR_EXP_FLAVOUR)
+    unsigned p2_window = 0;   // flavours 16 / 17: records per gather window (VR_EXP_P2_WINDOW: the moving window of volumes >= 4 GiB, forced
+                              // onto small volumes by the tests; 0 = what the hardware reaches, just below 4 GiB)
+    double active_fraction = 1.0;  // share of bricks that are not inert, of the distance field in use
+    float abox[6] = {-3.0e38f, -3.0e38f, -3.0e38f, 3.0e38f, 3.0e38f, 3.0e38f};  // uvw box around the active bricks of that field (MarchParams::abox)
+    // Slice views (vr_slice_async): a slice takes a record slot like every launch and leaves the march launches' records, counters
+    // and timings alone; which slot the last slice wrote (vr_slice_counters)
+    int slice_buf = -1;
+    unsigned slice_tiles = 0;
+    DevBuf<void> d_slice_out;  // vr_slice_render's device output (grown on demand, bytes)
+    // Histograms (vr_histogram_async): a histogram takes a record slot like a slice, and leaves every other launch's bookkeeping
+    // alone; which slot the last histogram wrote (vr_hist_counters), and vr_histogram's device outputs (grown on demand, bytes)
+    int hist_buf = -1;
+    DevBuf<void> d_hist_out;
+    float iso = 0.5f;        // VR_VARIANT_ISO's level (vr_set_iso_value), copied into MarchParams::iso at enqueue
+    // Shadows of the lit shader (vr_set_shadows, vr_shadow.h): the setting, and a ring of light volumes, one per key.  A launch whose key
+    // matches an entry reads it (waiting once per stream for its build); otherwise it builds the least recently used entry on its own
+    // stream, behind every launch still reading it (buf.reader, as the table generations).  A volume change drains the device and
+    // empties the ring.
+    int shadow_div = 0;                     // 0 = off; 1, 2, 4, 8 = voxels per light-volume texel and axis
+    float shadow_sigma = 1.0f;              // opacity scale
+    unsigned long long opacity_edits = 0;   // bumped by every upload of TF slot 0's opacity table, synchronous or not (the key's content)
+    struct ShadowKey {
+        unsigned long long epoch = 0, opacity = 0;  // brick_epoch, opacity_edits
+        uint32_t light[3] = {}, box[6] = {}, sigma = 0;
+        int div = 0, arith = 0;
+        bool operator==(const ShadowKey& o) const
+        {
+            return epoch == o.epoch && opacity == o.opacity && std::memcmp(light, o.light, sizeof light) == 0 &&
+                   std::memcmp(box, o.box, sizeof box) == 0 && sigma == o.sigma && div == o.div && arith == o.arith;
+        }
+    };
+    struct ShadowVol {
+        GenBuf buf;
+        ShadowKey key;
+        bool valid = false;
+        BuiltOn built;                // the build may still run: other streams wait for it once
+        unsigned long long used = 0;  // (least recently used entry is rebuilt)
+    } shadow[kShadowRing];
+    unsigned long long shadow_clock = 0;
+    int shadow_cur = -1;  // the entry the launch being enqueued reads (mark_reads)
+    // Surface-position output (vr_set_output, vr_surf.h): the setting and the threshold, both captured at enqueue; vr_pick's frame
+    // (allocated on first use, freed with the viewport's buffers)
+    int output = VR_OUTPUT_COLOR;
+    float surf_tau = 0.5f;
+    DevBuf<float4> d_pick;
+    DevBuf<float> d_pick_depth;
+    // Per-pixel ray bounds (vr_set_ray_bounds, vr_bound.h): the caller's depth buffers, W*H floats each (nullptr: no bound on that side);
+    // captured at enqueue, dropped by vr_resize
+    const float* d_near = nullptr;
+    const float* d_far = nullptr;
+    std::string err;
+};
+
+namespace {
+
+thread_local std::string g_create_error;
+
+int fail(vr_ctx* c, int code, const std::string& msg)
+{
+    if (c) c->err = msg;
+    else g_create_error = msg;
+    return code;
+}
+
+#define VR_HIP(c, call)                                                                               \
+    do {                                                                                              \
+        hipError_t e__ = (call);                                                                      \
+        if (e__ != hipSuccess)                                                                        \
+            return fail((c), e__ == hipErrorOutOfMemory ? VR_ERR_OOM : VR_ERR_HIP,                    \
+                        std::string(#call) + " (" __FILE_NAME__ ":" + std::to_string(__LINE__) + "): " + hipGetErrorString(e__));            \
+    } while (0)
+
+// After a hipDeviceSynchronize: every asynchronous edit has completed, and what they replaced can be freed.
+void drained(vr_ctx* c)
+{
+    for (void* p : c->retired_dev) (void)hipFree(p);
+    for (void* p : c->retired_host) (void)hipHostFree(p);
+    c->retired_dev.clear();
+    c->retired_host.clear();
+    c->drained_gen = c->edit_gen;
+    for (auto& v : c->vols) v.proj_built.pending = false;
+    for (auto& e : c->shadow) e.built.pending = false;
+}
+
+// Waits for everything on the device, the launches on the caller's streams included; nothing is in flight after it.
+int drain(vr_ctx* c)
+{
+    VR_HIP(c, hipSetDevice(c->device));
+    VR_HIP(c, hipDeviceSynchronize());
+    drained(c);
+    return VR_OK;
+}
+
+// Grows a buffer to n elements.  `drain`: nothing is in flight, the old memory is freed; otherwise it waits for the next draining call.
+template <typename T>
+int grow(vr_ctx* c, DevBuf<T>& b, size_t n, bool drain)
+{
+    if (n <= b.cap) return VR_OK;
+    if (b.p && !drain) c->retired_dev.push_back(b.detach());
+    VR_HIP(c, b.reserve(n));
+    return VR_OK;
+}
+
+}  // namespace
