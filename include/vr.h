@@ -719,6 +719,74 @@ int vr_histogram(vr_ctx* ctx, const vr_hist_desc* desc, uint64_t* counts, vr_his
 /* Counters of the last histogram launch (as described above); waits for that launch.  Zeros before the first histogram. */
 int vr_hist_counters(vr_ctx* ctx, uint64_t out[3]);
 
+/* ---- region growing: the structure under a voxel, as a contour of a mask volume ---------------------------------------------------
+ * Every consumer of a mask (VOLUME_MASK, TF_CALIB, rows 1 .. 4 of vr_histogram, vr_pick's value[]) runs on the device; this call
+ * produces one there too (csrc/vr_grow.h): the threshold-connected region around seed voxels -- a vr_pick_result's `voxel`, say --
+ * written into one component of a mask slot.  The result is a uniquely defined set of voxels; nothing about it is approximate.
+ *   Sets: Q = the voxels of the box whose value v (channel `channel` of volume_slot) qualifies: v >= lo && v <= hi in f32, so NaN never
+ *     does.  Two voxels are neighbours if they differ by at most 1 on every axis and are not equal; with VR_GROW_FACES only if they
+ *     differ on exactly one axis.  R = the union of the connected components of Q -- adjacency restricted to the box: a path never
+ *     leaves it -- that contain at least one seed.
+ *   Seeds: a seed outside the box or not in Q contributes nothing (no error); duplicates are fine.
+ *   Effect on component `contour` of the mask slot's voxels: VR_GROW_REPLACE: 1.0f in R and +0.0f everywhere else, outside the box
+ *     too.  VR_GROW_ADD: 1.0f in R, every other voxel keeps its bits.  The other three components keep their bits in both modes (NaN
+ *     payloads and -0 included).
+ *   Bounds: no value of lo / hi is an error.  lo > hi or a NaN bound gives an empty Q; -inf / +inf admit every value that is not NaN.
+ *   Mask slot: an empty mask_slot is created with the value volume's nx, ny, nz and every component +0.0f; one that holds a volume of
+ *     other dimensions is VR_ERR_INVALID_ARG.
+ *   Result: voxels = |R|; lo / hi = the half-open bounding box of R, all zero when R is empty; rounds = the propagation rounds that had
+ *     something to do (>= 1; it depends on the kernel form, nothing else does).
+ *   Counters (vr_grow_counters): out[0] = voxels of the box, out[1] = voxels whose value was loaded, out[2] = voxels classified from a
+ *     brick range record without a load.
+ * Kernel forms: every flavour of vr_set_kernel_flavour but 1 classifies whole 4 x 4 x 4 bricks of channel 3 from their range records
+ * where those decide (out[1] + out[2] == out[0]) and propagates along a frontier of bricks; flavour 1 loads every voxel of the box
+ * (out[1] == out[0], out[2] == 0) and sweeps every brick in every round.  The mask, the result but `rounds` and out[0] are identical
+ * across the forms and the volume layouts.  The host enqueues VR_GROW_BATCH rounds at a time and looks at the outcome in between. */
+#define VR_GROW_FACES 6          /* neighbours share a face                    */
+#define VR_GROW_ALL   26         /* ... a face, an edge or a corner            */
+#define VR_GROW_REPLACE 0
+#define VR_GROW_ADD     1
+#define VR_GROW_MAX_SEEDS 64
+#define VR_GROW_BATCH 8          /* propagation rounds enqueued between two looks at the outcome */
+typedef struct vr_grow_desc {
+    int32_t volume_slot, channel;   /* the values: an uploaded slot, 0..3 = .r .g .b .a          */
+    int32_t mask_slot, contour;     /* the result: a slot != volume_slot, component 0..3          */
+    float   lo, hi;                 /* a voxel qualifies iff v >= lo && v <= hi (NaN never does)  */
+    int32_t connectivity, mode;
+    int32_t box_lo[3], box_hi[3];   /* voxel box, half open, 0 <= lo <= hi <= n per axis          */
+    uint32_t n_seeds;               /* 1 .. VR_GROW_MAX_SEEDS                                     */
+    int32_t seeds[VR_GROW_MAX_SEEDS][3];   /* x, y, z; each inside the volume                     */
+} vr_grow_desc;
+typedef struct vr_grow_result {
+    uint64_t voxels;                /* |R|                                                        */
+    int32_t  lo[3], hi[3];          /* half-open bounding box of R; all zero when R is empty      */
+    uint32_t rounds;                /* propagation rounds executed (form-dependent, >= 1)         */
+} vr_grow_result;
+
+/* Fills *out for the whole volume of volume_slot: channel 3, VR_GROW_FACES, VR_GROW_REPLACE, the box (0,0,0) .. (nx,ny,nz), the given
+ * mask slot, contour and bounds, n_seeds = 0: the caller adds the seeds.  Pure host arithmetic; VR_ERR_INVALID_ARG for a NULL pointer,
+ * a slot out of range, mask_slot == volume_slot or a contour outside 0 .. 3, VR_ERR_NOT_READY for an empty volume slot. */
+int vr_grow_whole(const vr_ctx* ctx, int volume_slot, int mask_slot, int contour, float lo, float hi, vr_grow_desc* out);
+
+/* Grows the region and writes the contour; `result` may be NULL.  A data-preparation call like vr_volume_normalize: it waits for
+ * everything in flight, runs on the ctx's own stream, rebuilds what is derived from the mask slot's voxels exactly as an upload does
+ * (brick records, the bricked copy, the mask's part in VOLUME_MASK's records, the distance field, range records, light volumes) and is
+ * synchronous on return.  What the reporting calls say about the last march, slice or histogram stays as it was.
+ * Checked before anything is enqueued or the mask slot is touched.  VR_ERR_INVALID_ARG: a NULL ctx or descriptor; a slot out of range;
+ * mask_slot == volume_slot; a channel or contour outside 0 .. 3; an unknown connectivity or mode; a box that is not
+ * 0 <= lo <= hi <= n on every axis; n_seeds outside 1 .. VR_GROW_MAX_SEEDS; a seed outside the volume; a mask slot of other
+ * dimensions.  VR_ERR_NOT_READY: the volume slot is empty.  VR_ERR_HIP "did not converge": more than voxels-of-the-box + 1 rounds
+ * (a defect, never the data: R grows in every round but the first and the last). */
+int vr_segment_grow(vr_ctx* ctx, const vr_grow_desc* desc, vr_grow_result* result);
+
+/* Counters of the last vr_segment_grow (as described above).  Zeros before the first. */
+int vr_grow_counters(vr_ctx* ctx, uint64_t out[3]);
+
+/* Device time of the last vr_segment_grow in milliseconds, from events on the ctx's stream: ms[0] classify and seed, ms[1] the
+ * propagation rounds (the host's looks in between included), ms[2] the write and the result, ms[3] the rebuild of what is derived
+ * from the mask slot.  Zeros before the first and after one that failed. */
+int vr_grow_timing(vr_ctx* ctx, float ms[4]);
+
 /* Volume layout in HBM (A/B measurements; frames and counts are bit-identical in every mode).
  *   0  default: the march kernels gather from a BRICKED copy of every slot -- the vec4 voxels and a scalar f32 density plane
  *      (what fetches that consume .a alone read: BasicVolumeApp.wgsl:171, the density / dose fetches of the other shaders)

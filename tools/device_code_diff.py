@@ -4,7 +4,7 @@
 A change that is meant to touch host code only (the C ABI, the context, the launch path) must leave every gfx950 code object as
 it was: then no kernel can be slower or compute anything else.  This script disassembles the code objects of both libraries
 (tools/check_exec_regions.py: code_objects, disassemble), keys every function on its mangled symbol and compares the
-instruction text, addresses and encodings stripped.  It prints the symbols that differ or exist on one side only.
+instruction text, addresses, encodings and the padding behind a function's last instruction stripped.  It prints the symbols that differ or exist on one side only.
 
     python tools/device_code_diff.py before/libvr_hip.so after/libvr_hip.so      exit status 0 = no difference
 """
@@ -27,6 +27,11 @@ def functions(listing):
         ins = " ".join(line.split("//")[0].split())  # (the comment holds the address and the encoding)
         if cur is not None and ins:
             cur.append(ins)
+    # what follows a function's last instruction up to the next symbol is the assembler's padding (s_nop 0, or zeros shown as "..."):
+    # it depends on what is linked behind the function, not on the function
+    for ins in out.values():
+        while ins and ins[-1] in ("s_nop 0", "..."):
+            ins.pop()
     return out
 
 

@@ -34,6 +34,10 @@ SLICE_LINEAR, SLICE_NEAREST = 0, 1              # vr_slice_desc.filter
 SLICE_RGBA32F, SLICE_BGRA8 = 0, 1               # vr_slice_desc.format
 HIST_ROWS, HIST_MAX_BINS = 5, 65536              # vr_histogram (include/vr.h)
 HIST_CLAMP, HIST_DROP = 0, 1                     # vr_hist_desc.out_of_range
+GROW_FACES, GROW_ALL = 6, 26                     # vr_grow_desc.connectivity (include/vr.h)
+GROW_REPLACE, GROW_ADD = 0, 1                    # vr_grow_desc.mode
+GROW_MAX_SEEDS = 64
+GROW_BATCH = 8                                   # propagation rounds enqueued between two looks at the outcome (VR_GROW_BATCH)
 
 # every symbol include/vr.h declares (tests check that the library exports each of them)
 ABI_SYMBOLS = [
@@ -52,6 +56,7 @@ ABI_SYMBOLS = [
     "vr_set_ray_bounds",
     "vr_slice_async", "vr_slice_render", "vr_slice_orthogonal", "vr_slice_counters",
     "vr_hist_whole", "vr_histogram_async", "vr_histogram", "vr_hist_counters",
+    "vr_grow_whole", "vr_segment_grow", "vr_grow_counters", "vr_grow_timing",
 ]
 
 
@@ -120,6 +125,40 @@ class HistDesc(C.Structure):
 class HistRow(C.Structure):
     """struct vr_hist_row: voxels = counted + dropped."""
     _fields_ = [("voxels", C.c_uint64), ("dropped", C.c_uint64)]
+
+
+class GrowDesc(C.Structure):
+    """struct vr_grow_desc (include/vr.h): the value slot and channel, the mask slot and contour, the bounds, the connectivity, the
+    mode, the voxel box and the seeds."""
+    _fields_ = [
+        ("volume_slot", C.c_int32), ("channel", C.c_int32), ("mask_slot", C.c_int32), ("contour", C.c_int32),
+        ("lo", C.c_float), ("hi", C.c_float), ("connectivity", C.c_int32), ("mode", C.c_int32),
+        ("box_lo", C.c_int32 * 3), ("box_hi", C.c_int32 * 3), ("n_seeds", C.c_uint32), ("seeds", (C.c_int32 * 3) * GROW_MAX_SEEDS),
+    ]
+
+    def copy(self, **over) -> "GrowDesc":
+        """A copy with the given fields replaced (box_lo / box_hi from any sequence of three integers; seeds from a sequence of at
+        most 64 (x, y, z), which sets n_seeds too unless that is given as well)."""
+        d = GrowDesc.from_buffer_copy(bytes(self))
+        for k, v in over.items():
+            if k in ("box_lo", "box_hi"):
+                v = (C.c_int32 * 3)(*[int(x) for x in v])
+            if k == "seeds":
+                v = [tuple(int(x) for x in p) for p in v]
+                assert len(v) <= GROW_MAX_SEEDS
+                if "n_seeds" not in over:
+                    d.n_seeds = len(v)
+                v = ((C.c_int32 * 3) * GROW_MAX_SEEDS)(*[(C.c_int32 * 3)(*p) for p in v])
+            setattr(d, k, v)
+        return d
+
+
+class GrowResult(C.Structure):
+    """struct vr_grow_result: |R|, its half-open bounding box (zeros when empty) and the propagation rounds."""
+    _fields_ = [("voxels", C.c_uint64), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("rounds", C.c_uint32)]
+
+    def as_tuple(self):
+        return int(self.voxels), tuple(int(x) for x in self.lo), tuple(int(x) for x in self.hi)
 
 
 class VrError(RuntimeError):
@@ -206,6 +245,10 @@ def load() -> C.CDLL:
     lib.vr_histogram_async.argtypes = [vp, C.POINTER(HistDesc), vp, vp, vp]
     lib.vr_histogram.argtypes = [vp, C.POINTER(HistDesc), vp, vp]
     lib.vr_hist_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
+    lib.vr_grow_whole.argtypes = [vp, i32, i32, i32, C.c_float, C.c_float, C.POINTER(GrowDesc)]
+    lib.vr_segment_grow.argtypes = [vp, C.POINTER(GrowDesc), C.POINTER(GrowResult)]
+    lib.vr_grow_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
+    lib.vr_grow_timing.argtypes = [vp, C.POINTER(C.c_float * 4)]
     lib.vr_present_async.argtypes = [vp, vp, vp, vp]
     lib.vr_present_tiles_async.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
     lib.vr_hint_frames_in_flight.argtypes = [vp, i32]
@@ -550,6 +593,30 @@ class Context:
         out = (C.c_uint64 * 3)()
         self._chk(self.lib.vr_hist_counters(self.h, C.byref(out)))
         return int(out[0]), int(out[1]), int(out[2])
+
+    def grow_whole(self, volume_slot: int, mask_slot: int, contour: int, lo: float, hi: float) -> GrowDesc:
+        """vr_grow_whole: the descriptor of a grow over the whole volume (channel 3, FACES, REPLACE, no seeds: add them with copy)."""
+        d = GrowDesc()
+        self._chk(self.lib.vr_grow_whole(self.h, volume_slot, mask_slot, contour, lo, hi, C.byref(d)))
+        return d
+
+    def segment_grow(self, desc: GrowDesc) -> GrowResult:
+        """vr_segment_grow: grows the region from desc's seeds and writes the contour into the mask slot (synchronous)."""
+        out = GrowResult()
+        self._chk(self.lib.vr_segment_grow(self.h, C.byref(desc), C.byref(out)))
+        return out
+
+    def grow_counters(self):
+        """(voxels of the box, voxels whose value was loaded, voxels classified from a brick record) of the last segment_grow."""
+        out = (C.c_uint64 * 3)()
+        self._chk(self.lib.vr_grow_counters(self.h, C.byref(out)))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def grow_timing(self):
+        """(classify, propagate, write, refresh) of the last segment_grow in ms of device time (vr_grow_timing)."""
+        out = (C.c_float * 4)()
+        self._chk(self.lib.vr_grow_timing(self.h, C.byref(out)))
+        return tuple(float(x) for x in out)
 
     def set_volume_layout(self, mode: int):
         """0 bricked copy (default), 1 the reference's vec4 voxels only, 3 x-fastest voxels + density plane (2 was removed)."""

@@ -142,6 +142,22 @@ int Application::DoseVolumeHistogram(int doseSlot, int maskSlot, int contour, ui
     return VR_OK;
 }
 
+int Application::GrowFromPick(const vr_pick_result& pick, int valueSlot, int maskSlot, int contour, float lo, float hi, int connectivity,
+                              vr_grow_result* out)
+{
+    if (!p_Ctx) return VR_ERR_NOT_READY;
+    if (!pick.hit) return VR_ERR_INVALID_ARG;
+    vr_grow_desc d;
+    int rc = vr_grow_whole(p_Ctx, valueSlot, maskSlot, contour, lo, hi, &d);
+    if (rc != VR_OK) return rc;
+    d.connectivity = connectivity;
+    d.n_seeds = 1;
+    for (int a = 0; a < 3; ++a) d.seeds[0][a] = pick.voxel[a];
+    rc = vr_segment_grow(p_Ctx, &d, out);
+    if (rc != VR_OK) m_Error = vr_last_error(p_Ctx);
+    return rc;
+}
+
 int Application::Pick(uint32_t x, uint32_t y, vr_pick_result* out)
 {
     if (!p_Ctx || !p_App) return VR_ERR_NOT_READY;

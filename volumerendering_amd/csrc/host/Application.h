@@ -61,6 +61,10 @@ public:
     // (int)(dose * scale) into `bins` bins (CLAMP), then atLeast[b] = the sum of counts[k] over k >= b -- the voxels of the structure
     // that receive at least the dose of bin b; atLeast[0] is the structure's voxel count.
     int DoseVolumeHistogram(int doseSlot, int maskSlot, int contour, uint32_t bins, float scale, std::vector<uint64_t>& atLeast);
+    // The structure under a picked pixel as contour `contour` (0 .. 3) of volume maskSlot: the voxels of volume valueSlot whose .a lies
+    // in [lo, hi] and that are connected to pick.voxel (vr_segment_grow over the whole volume, VR_GROW_REPLACE; connectivity =
+    // VR_GROW_FACES / VR_GROW_ALL).  `out` may be nullptr.  A pick without a hit returns VR_ERR_INVALID_ARG.
+    int GrowFromPick(const vr_pick_result& pick, int valueSlot, int maskSlot, int contour, float lo, float hi, int connectivity, vr_grow_result* out);
     // the accumulated opacity at which the unlit / lit scene's surface lies (vr_set_surface_threshold: finite, 0 <= tau < 1)
     int SetSurfaceThreshold(float tau);
 

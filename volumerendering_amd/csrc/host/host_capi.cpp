@@ -402,6 +402,13 @@ int vrh_app_dvh(void* a, int dose_slot, int mask_slot, int contour, uint32_t bin
         return VR_OK;
     })
 }
+// Application::GrowFromPick (vr_segment_grow of the application's context)
+int vrh_app_grow_from_pick(void* a, const vr_pick_result* pick, int value_slot, int mask_slot, int contour, float lo, float hi, int connectivity,
+                           vr_grow_result* out)
+{
+    if (!pick) return VR_ERR_INVALID_ARG;
+    VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->GrowFromPick(*pick, value_slot, mask_slot, contour, lo, hi, connectivity, out); })
+}
 int vrh_app_set_surface_threshold(void* a, float tau) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->SetSurfaceThreshold(tau); }) }
 void vrh_app_set_prepare_on_device(void* a, int on) { static_cast<Application*>(a)->m_PrepareOnDevice = on != 0; }
 int vrh_app_update(void* a) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->OnUpdate(); }) }

@@ -6,6 +6,8 @@
 #include "vr_launch.h"
 // Histograms (vr_histogram_async): nothing to fuse, so this kernel exists once, here
 #include "vr_hist.h"
+// Region growing (vr_segment_grow): integer work on bit-bricks, compiled once as well
+#include "vr_grow.h"
 
 // the same dispatch over the kernels compiled with fused multiply-adds (vr_fused.hip)
 namespace vrf {
@@ -31,6 +33,7 @@ using namespace vr;
 #include "vr_api_tf.h"
 #include "vr_api_render.h"
 #include "vr_api_views.h"
+#include "vr_api_segment.h"
 
 namespace {
 

@@ -149,6 +149,18 @@ struct VolumeSlot {
     BuiltOn proj_built;
 };
 
+// Region growing (vr_segment_grow, vr_grow.h): the working buffers of the last grow, grown on demand; what vr_grow_counters and
+// vr_grow_timing report.
+struct GrowState {
+    DevBuf<unsigned long long> words;  // the bit-bricks: Q of every brick, then R of every brick
+    DevBuf<unsigned> lists;            // per brick: the round stamp, then the frontier's two lists
+    DevBuf<GrowWords> d_words;         // counters, result and the rounds' words ...
+    PinnedBuf<GrowWords> h_words;      // ... and where the host sets and reads them
+    Event ev[5];                       // around classify + seed, propagate, write, refresh_bricks
+    unsigned long long counters[3] = {0, 0, 0};
+    float ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+};
+
 // What the reporting calls (vr_last_counters, vr_last_kernel_flavour, vr_last_timing, vr_kernel_times, vr_kernel_choice,
 // vr_download_tiles, vr_last_block_trace) read about the most recent march launch.  vr_pick copies it out and back as one value.
 struct LastLaunch {
@@ -336,6 +348,7 @@ struct vr_ctx {
     // captured at enqueue, dropped by vr_resize
     const float* d_near = nullptr;
     const float* d_far = nullptr;
+    GrowState grow;  // region growing (vr_segment_grow)
     std::string err;
 };
 

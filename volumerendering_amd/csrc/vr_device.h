@@ -180,6 +180,44 @@ struct HistParams {
     unsigned long long* stats;     // [3]: voxels of the box, voxels loaded, voxels settled from a record
 };
 
+// The device words of one region grow (vr_grow.h): what the host sets before the first kernel and reads behind a batch of rounds.
+struct GrowWords {
+    unsigned long long stats[3];  // voxels of the box, voxels loaded, voxels classified from a range record
+    unsigned long long voxels;    // |R| ...
+    int lo[3], hi[3];             // ... and its half-open bounding box (lo starts at INT_MAX, hi at 0)
+    unsigned cnt[3];              // round k reads cnt[k % 3] (frontier: the length of its list; sweep: the round before it changed
+                                  // something), adds to cnt[(k + 1) % 3] and zeroes cnt[(k + 2) % 3]
+    unsigned rounds;              // the last round that had something to do
+};
+
+// Kernel argument block of a region grow (vr_grow.h; vr_grow_desc of include/vr.h): passed by value.
+struct GrowParams {
+    const float* val;        // the value of voxel idx is val[idx * val_stride]: as HistParams
+    int val_stride;
+    int nx, ny, nz;          // of the value volume (and of the mask)
+    int lo[3], hi[3];        // the voxel box, half open
+    int u0[3], un[3];        // the 4 x 4 x 4 brick units that meet the box: first unit and units per axis ...
+    unsigned units;          // ... and their number
+    float vlo, vhi;          // a voxel qualifies iff v >= vlo && v <= vhi
+    const float2* bricks;    // exact settling: the slot's range records (vr_proj.h); nullptr = off
+    int bnx, bny, bnz;       // the volume's brick grid: brick (bx, by, bz) has index (bz * bny + by) * bnx + bx
+    unsigned n_bricks;
+    int all;                 // VR_GROW_ALL: 26 neighbours instead of 6
+    unsigned long long* q;   // per brick: bit x + 4 y + 16 z = the voxel qualifies (and lies in the box)
+    unsigned long long* r;   // ... = the voxel is reached
+    unsigned* stamp;         // frontier: per brick, the last round it was queued for
+    unsigned* list[2];       // frontier: round k reads list[k & 1] and fills list[(k + 1) & 1] (n_bricks words each)
+    GrowWords* w;
+    unsigned round;          // 1, 2, ...
+    float4* mask;            // the mask slot's x-fastest vec4 voxels
+    int contour;             // the component written
+    int write_zeros;         // VR_GROW_REPLACE into a slot that held a mask: voxels outside R are stored +0.0f
+};
+struct GrowSeeds {
+    unsigned n;
+    int xyz[64][3];
+};
+
 // Work queue of the persistent-wavefront kernel (vr_pw.h): eight heads, one per class of the workgroup index modulo 8,
 // zero at launch; heads[c * 64] counts the items of class c handed out beyond every wavefront's first.
 struct PwQueue {

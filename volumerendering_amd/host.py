@@ -65,6 +65,7 @@ def load() -> C.CDLL:
         "vrh_app_error": (C.c_char_p, [vp]), "vrh_app_context": (vp, [vp]), "vrh_app_camera": (vp, [vp]),
         "vrh_app_start": (i32, [vp, i32, vp, vp, vp, i32]), "vrh_app_set_prepare_on_device": (None, [vp, i32]), "vrh_app_set_iso_value": (i32, [vp, f32]), "vrh_app_set_shadows": (i32, [vp, i32, f32]),
         "vrh_app_pick": (i32, [vp, u32, u32, C.POINTER(capi.PickResult)]),
+        "vrh_app_grow_from_pick": (i32, [vp, C.POINTER(capi.PickResult), i32, i32, i32, f32, f32, i32, C.POINTER(capi.GrowResult)]),
         "vrh_app_slice": (i32, [vp, C.POINTER(capi.SliceDesc), vp]),
         "vrh_app_slice_through_pick": (C.c_longlong, [vp, C.POINTER(capi.PickResult), i32, i32, vp, C.c_size_t, C.POINTER(u32), C.POINTER(u32)]), "vrh_app_set_surface_threshold": (i32, [vp, f32]), "vrh_app_update": (i32, [vp]), "vrh_app_render": (i32, [vp]),
         "vrh_app_resize": (i32, [vp, u32, u32]), "vrh_app_read_frame": (i32, [vp, vp, vp, C.POINTER(u64)]),
@@ -506,6 +507,14 @@ class Application:
         """Application::DoseVolumeHistogram: uint64[bins], element b = the voxels of contour `contour` whose dose bin is >= b."""
         out = np.zeros(bins, dtype=np.uint64)
         self._chk(self.lib.vrh_app_dvh(self.h, dose_slot, mask_slot, contour, bins, scale, out.ctypes.data))
+        return out
+
+    def grow_from_pick(self, pick: capi.PickResult, value_slot: int, mask_slot: int, contour: int, lo: float, hi: float,
+                       connectivity: int = capi.GROW_FACES) -> capi.GrowResult:
+        """Application::GrowFromPick: the structure under a picked pixel -- the voxels of volume value_slot with .a in [lo, hi] connected
+        to pick.voxel -- as contour `contour` of volume mask_slot (include/vr.h vr_segment_grow); a miss is VR_ERR_INVALID_ARG."""
+        out = capi.GrowResult()
+        self._chk(self.lib.vrh_app_grow_from_pick(self.h, C.byref(pick), value_slot, mask_slot, contour, lo, hi, connectivity, C.byref(out)))
         return out
 
     def set_surface_threshold(self, tau: float):
