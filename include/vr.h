@@ -395,13 +395,27 @@ int vr_last_block_trace(vr_ctx* ctx, uint64_t* out, int capacity);
  *      Lit / unlit shader and (17; 16 runs as 17) the three-volume composite, whose mask and dose are fetched on demand behind the
  *      per-brick mask record; volumes of 4 GiB and more through a window of z-slabs of bricks that follows the packet; launches of
  *      several frames take (frame, packet) items from the one queue.  Needs one table resolution <= 8190 and the bricked copy
- *      (vr_set_volume_layout(0)); else 13 / 12, or 6 for launches of several frames
+ *      (vr_set_volume_layout(0)), and a volume whose axis tables fit the workgroup's LDS beside TF slot 0:
+ *          (opacity resolution + 2) * 16 + (nx + ny + nz + 3) * 8  <=  160 KiB
+ *      (a 64-entry table: nx + ny + nz <= 20345), a z-slab of storage bricks below 2^24 voxels and a bricked copy below 2^32
+ *      voxels; else 13 / 12, or 6 for launches of several frames
  *   18  the one-lane kernel (6) with the slot arithmetic of volume 0's cells from per-axis tables in its workgroup's LDS (the
  *      clamp-to-edge texel pair of a coordinate is one ds_read2_b32; filled per workgroup, by the workgroups that can hit the box);
- *      the shaders that sample one volume (lit, unlit, in-shader gradient) on the bricked copy, launches of any number of frames;
- *      else it runs as 6
+ *      the shaders that sample one volume (lit, unlit, in-shader gradient) on the bricked copy, launches of any number of frames,
+ *      a volume whose tables fit 32 KiB of LDS:
+ *          (nx + ny + nz + 6) * 4  <=  32 KiB            (nx + ny + nz <= 8186)
+ *      and a bricked copy below 2^32 voxels; else it runs as 6
  *   15  the voxels of a packet's next four steps in an LDS tile filled by LDS-DMA (csrc/vr_lt.h): lit shader, launches of
  *       one frame (other launches run 6); never picked by the default -- slower than 17 / 16 wherever measured
+ * THE BRICK-INDEX LIMIT.  Every skipping form finds the record of a step's brick (4^3 cells) with 24-bit multiplies and a 32-bit
+ * byte offset.  With bn = ceil(n / 4) bricks per axis that is exact for
+ *          bny * bnz <= 2^23,   bnx < 2^23   and   bnx * bny * bnz <= 2^29
+ * (vr_skip_indexable).  Every cube up to 3248 voxels an axis is inside -- more than a device holds --; thin, long volumes are
+ * what leaves it: (1, 8192, 16384) is the last shape of its kind inside, (1, 8196, 16384) the first outside.  A volume beyond
+ * the limit is rendered all the same: its launches do not skip -- the skipping flavour of a pair (17; 19, 21, 23, 25, 27; the
+ * slices) runs as the pair's other form, every counted sample is fetched, the outputs are the same bits -- and vr_skip_field
+ * returns VR_ERR_NOT_READY.  The histogram and the region growing index their records with 64 bits and keep settling units
+ * from them.
  * The projections (MIP / MINIP / AVERAGE) have forms of their own, reported by vr_last_kernel_flavour and never measured against
  * each other (vr_kernel_choice reports 0 candidates after a projection launch):
  *   19  march_proj_kernel with exact skipping (csrc/vr_proj.h): a step whose brick cannot change the result loads nothing
@@ -813,6 +827,10 @@ int vr_last_kernel_flavour(vr_ctx* ctx);
  * the nearest active brick, 128): 0 for an active brick, 128 everywhere when none is active.  Drains the device.
  * Returns n, or a negative vr_status (VR_ERR_NOT_READY when such a launch would not skip empty space).             */
 int vr_skip_field(vr_ctx* ctx, int variant, uint8_t* dist, size_t capacity, int dims[3], int box[6], uint64_t* active);
+
+/* 1 when the skipping kernels can index the bricks of an nx x ny x nz volume (THE BRICK-INDEX LIMIT at vr_set_kernel_flavour),
+ * 0 when launches on such a volume run without skipping.  Needs no context and no device.                              */
+int vr_skip_indexable(uint16_t nx, uint16_t ny, uint16_t nz);
 
 /* How many skipping launches ran with no active-brick box because an asynchronous rebuild's box had not reached the
  * host yet (vr_tf_upload_opacity_async), since the context was created. */

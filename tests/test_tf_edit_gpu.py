@@ -10,11 +10,11 @@ import pytest
 
 import host_ref as hr
 import vrtest as vt
+from skip_ref import CAP, check_field, numpy_active  # (the numpy field, records and active bricks: tests/skip_ref.py)
 from volumerendering_amd import capi
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-CAP = 128  # the field's cap (vr_skip_field)
 
 
 def prefix_tf(res, zeros, top=0.6):
@@ -288,63 +288,6 @@ def test_a_generation_outlives_readers_on_other_streams():
         for o in outs:
             o.close()
         cold.close()
-
-
-def linf_field(active):
-    """min(L-infinity distance to the nearest active brick, CAP), by the separable form (numpy, brute force per axis)."""
-    big = 1 << 20
-    d = np.where(active, 0, big).astype(np.int64)
-    for axis in (2, 1, 0):
-        m = d.shape[axis]
-        idx = np.arange(m)
-        dist = np.abs(idx[:, None] - idx[None, :])  # |i - j|
-        moved = np.moveaxis(d, axis, -1)
-        out = np.min(np.maximum(dist[None, :, :], moved[..., None, :]), axis=-1)
-        d = np.moveaxis(out, -1, axis)
-    return np.minimum(d, CAP).astype(np.uint8)
-
-
-def brick_records(vol):
-    """Per brick of 4^3 cells (vr_kernels.h brick_max_kernel): the maxima of .a and of max(r, g, b) over the voxels
-    [4 b, min(4 b + 4, n - 1)] of each axis (finite volumes)."""
-    nz, ny, nx = vol.shape[:3]
-    bn = [(n + 3) // 4 for n in (nx, ny, nz)]
-    dens = np.empty((bn[2], bn[1], bn[0]), dtype=f32)
-    rgb = np.empty_like(dens)
-    for bz in range(bn[2]):
-        for by in range(bn[1]):
-            for bx in range(bn[0]):
-                v = vol[4 * bz:min(4 * bz + 5, nz), 4 * by:min(4 * by + 5, ny), 4 * bx:min(4 * bx + 5, nx)]
-                dens[bz, by, bx] = v[..., 3].max()
-                rgb[bz, by, bx] = v[..., :3].max()
-    return dens, rgb
-
-
-def numpy_active(density_vol, opacity, mask_vol=None):
-    """The active bricks (brick_active_kernel's rule) from the volume and the opacity table, independently of the field."""
-    z = int(np.argmax(opacity != 0.0)) - 1 if (opacity != 0.0).any() else opacity.size - 1
-    dens, _ = brick_records(density_vol)
-    res = f32(opacity.size)
-    inert = np.where(dens <= 0.0, z >= 0, np.floor(dens * res - f32(0.5)) + f32(2.0) <= f32(z))
-    if mask_vol is not None:
-        _, rgb = brick_records(mask_vol)
-        inert &= rgb <= 0.0
-    return ~inert
-
-
-def check_field(ctx, variant, expect_active=None):
-    field, box, active = ctx.skip_field(variant)
-    act = field == 0
-    if expect_active is not None:
-        assert np.array_equal(act, expect_active)
-    assert np.array_equal(field, linf_field(act))
-    assert active == int(act.sum())
-    if active:
-        zz, yy, xx = np.nonzero(act)
-        assert box == (xx.min(), yy.min(), zz.min(), xx.max(), yy.max(), zz.max())
-    else:
-        assert box[3] < 0 and box[4] < 0 and box[5] < 0
-    return field, box, active
 
 
 def spot_volume(shape, spots):

@@ -50,7 +50,7 @@ ABI_SYMBOLS = [
     "vr_set_volume_layout", "vr_volume_layout", "vr_viewport", "vr_set_arithmetic", "vr_present_async", "vr_stream", "vr_hint_frames_in_flight",
     "vr_set_kernel_timing", "vr_present_tiles_async", "vr_kernel_choice",
     "vr_present_packed_async", "vr_unpack_tiles_bgra8_async",
-    "vr_tf_upload_opacity_async", "vr_tf_upload_color_async", "vr_skip_field", "vr_unbounded_box_launches",
+    "vr_tf_upload_opacity_async", "vr_tf_upload_color_async", "vr_skip_field", "vr_skip_indexable", "vr_unbounded_box_launches",
     "vr_set_iso_value", "vr_set_shadows", "vr_shadow_volume",
     "vr_set_output", "vr_set_surface_threshold", "vr_surface_depth_async", "vr_pick",
     "vr_set_ray_bounds",
@@ -202,6 +202,7 @@ def load() -> C.CDLL:
     lib.vr_tf_upload_opacity_async.argtypes = [vp, i32, vp, u32, vp]
     lib.vr_tf_upload_color_async.argtypes = [vp, i32, vp, u32, vp]
     lib.vr_skip_field.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_int * 3), C.POINTER(C.c_int * 6), C.POINTER(C.c_uint64)]
+    lib.vr_skip_indexable.argtypes = [u16, u16, u16]
     lib.vr_unbounded_box_launches.argtypes = [vp]
     lib.vr_unbounded_box_launches.restype = C.c_int64
     lib.vr_set_uniforms.argtypes = [vp, C.POINTER(Uniforms)]
@@ -362,6 +363,11 @@ class Context:
         out = np.zeros(n, dtype=np.uint8)
         self._chk(self.lib.vr_skip_field(self.h, variant, out.ctypes.data, n, C.byref(dims), C.byref(box), C.byref(active)))
         return out.reshape(dims[2], dims[1], dims[0]), tuple(int(x) for x in box), int(active.value)
+
+    @staticmethod
+    def skip_indexable(nx: int, ny: int, nz: int) -> bool:
+        """Whether launches on a volume of these dimensions may skip empty space (vr_skip_indexable; no device needed)."""
+        return bool(load().vr_skip_indexable(nx, ny, nz))
 
     def unbounded_box_launches(self) -> int:
         """Skipping launches that ran without an active-brick box (an asynchronous rebuild's box still on its way)."""

@@ -345,6 +345,7 @@ struct Eligibility {
     unsigned p2_lds;        // ... with this much dynamic LDS (TF slot 0 and the three axis tables)
     bool lut_ok;            // 18 can run
     unsigned lut_lds;       // ... with this much (the slot tables of volume 0)
+    bool indexable;         // the skipping kernels can index volume 0's bricks (bricks_indexable): every skipping form needs it
     bool can_skip;          // exact empty-space skipping (prepare_skip)
     bool whole_frame;       // enough rays to fill the machine in one frame
     unsigned chain_known;   // longest ray chain + 1 of the most recent launch of this scene shape whose sort has reported (0: none)
@@ -396,12 +397,13 @@ Eligibility eligibility(const vr_ctx* c, int requested, const RenderRequest& R)
     // exact empty-space skipping: only for the shaders whose opacity is the CT table value alone, only when a zero-opacity sample is
     // provably the identity (finite colour table and light), and unless flavour 1 asks for the plain kernel (no rule of choose_flavour
     // turns another flavour into 1 or 1 into another)
+    E.indexable = volume_bricks_indexable(c->vols[0].vol);
     E.can_skip = (R.variant == VR_VARIANT_BASIC || R.variant == VR_VARIANT_LIGHT || R.variant == VR_VARIANT_THREE_FILES ||
                   R.variant == VR_VARIANT_VOLUME_MASK || R.variant == VR_VARIANT_LIGHT_INSHADER) &&
                  requested != 1 && c->vols[sv].bricks && c->tf_zero_prefix[0] >= 0 && c->tf_color_finite[0];
     for (int f = 0; f < R.n_frames; ++f) E.can_skip = E.can_skip && all_finite(R.batch_u ? R.batch_u[f].light_pos : c->u.light_pos, 12);
     // the kernels index bricks with 24-bit multiplies and 32-bit byte offsets
-    E.can_skip = E.can_skip && skip_bricks(c->vols[sv].vol.nx) * (long long)skip_bricks(c->vols[sv].vol.ny) < (1 << 23);
+    E.can_skip = E.can_skip && volume_bricks_indexable(c->vols[sv].vol);
     if (R.variant == VR_VARIANT_THREE_FILES) E.can_skip = E.can_skip && c->tf_color_finite[1] && c->tf_opacity_finite[1];
     if (R.variant == VR_VARIANT_VOLUME_MASK)  // mask and CT must share one grid so that one brick index serves both
         E.can_skip = E.can_skip && c->vols[0].bricks && c->vols[0].vol.nx == c->vols[2].vol.nx && c->vols[0].vol.ny == c->vols[2].vol.ny &&
@@ -730,8 +732,7 @@ int enqueue_render(vr_ctx* c, RenderRequest R)
         // The surface march skips by the distance field of BASIC / LIGHT under the weakest condition that is still exact: an inert
         // brick's samples have opacity exactly 0, which leaves the accumulated alpha as it is whatever the colour table and the
         // light hold -- neither is read.  So: the brick records, a zero prefix of the opacity table, the kernels' index range.
-        E.can_skip = requested != 1 && c->vols[0].bricks && c->tf_zero_prefix[0] >= 0 &&
-                     skip_bricks(c->vols[0].vol.nx) * (long long)skip_bricks(c->vols[0].vol.ny) < (1 << 23);
+        E.can_skip = requested != 1 && c->vols[0].bricks && c->tf_zero_prefix[0] >= 0 && E.indexable;
         E.chain_known = 0;
     }
     if (E.can_skip) {
@@ -743,7 +744,7 @@ int enqueue_render(vr_ctx* c, RenderRequest R)
     const KernelForm form = kernel_form(fl, R.variant);
     c->last.unmeasured = !form.measured();
     const float2* vrange = nullptr;
-    if (form.skip && form.range_records()) {
+    if (form.skip && form.range_records() && E.indexable) {  // (else: the pair's form without skipping)
         vrange = prepare_proj(c, s, P);
         if (!vrange) return VR_ERR_HIP;
     }
@@ -1062,6 +1063,11 @@ int vr_skip_field(vr_ctx* c, int variant, uint8_t* dist, size_t capacity, int di
         for (int a = 0; a < 6; ++a) box[a] = c->skip_box[a];
     if (active) *active = c->skip_active;
     return (int)n;
+}
+
+int vr_skip_indexable(uint16_t nx, uint16_t ny, uint16_t nz)
+{
+    return bricks_indexable(skip_bricks(nx), skip_bricks(ny), skip_bricks(nz)) ? 1 : 0;
 }
 
 int64_t vr_unbounded_box_launches(vr_ctx* c)

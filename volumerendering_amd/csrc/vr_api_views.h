@@ -155,7 +155,7 @@ int enqueue_slice(vr_ctx* c, const vr_slice_desc& d, void* d_out, hipStream_t s)
     S.bsy = (float)v.ny * kBrickInv;
     S.bsz = (float)v.nz * kBrickInv;
     const int requested = c->flavour == 0 ? c->default_flavour : c->flavour;
-    const bool skip = requested != 1 && (long long)S.bnx * S.bny < (1 << 23);
+    const bool skip = requested != 1 && bricks_indexable(S.bnx, S.bny, S.bnz);
     if (skip) {
         S.vrange = prepare_range(c, s, vs, S.bnx, S.bny, S.bnz, &S.bricks);
         if (!S.vrange) return VR_ERR_HIP;

@@ -1128,7 +1128,7 @@ __device__ __forceinline__ int brick_of(const MarchParams& P, f3 p)
         by = clampi((int)floorf(mad(p.y, P.bsy, -kBrickHalf)), 0, P.bny - 1);
         bz = clampi((int)floorf(mad(p.z, P.bsz, -kBrickHalf)), 0, P.bnz - 1);
     }
-    return __mul24(__mul24(bz, P.bny) + by, P.bnx) + bx;  // < 2^24 bricks per axis pair: 24-bit multiplies are exact
+    return __mul24(__mul24(bz, P.bny) + by, P.bnx) + bx;  // (signed 24-bit multiplies: exact for the grids bricks_indexable() admits)
 }
 // distance-field byte of brick `bid` (SGPR base + 32-bit offset addressing)
 __device__ __forceinline__ unsigned dist_at(const MarchParams& P, int bid)
