@@ -801,6 +801,98 @@ int vr_grow_counters(vr_ctx* ctx, uint64_t out[3]);
  * from the mask slot.  Zeros before the first and after one that failed. */
 int vr_grow_timing(vr_ctx* ctx, float ms[4]);
 
+/* ---- mask morphology and contour algebra: margins, shells, unions and closings of contours ---------------------------------------
+ * A contour of a mask slot, restricted to a box, is dilated, eroded, closed or opened by a structuring element, or taken as it is, and
+ * the result is combined into a contour of a mask slot -- on the device (csrc/vr_morph.h), so that a grown region can be smoothed and
+ * a structure given a margin in millimetres without a download.  The result is exact set arithmetic on voxels.
+ *   Membership: voxel p of a slot is IN contour k iff component k of its vec4 is != 0.0f (the rule of vr_histogram's rows 1 .. 4): NaN is
+ *     in, -0.0f is out.
+ *   Element E: a set of integer offsets, symmetric under reflection of each axis, given by its radii (rx, ry, rz) and a table of
+ *     half-chords along x: half[dz + rz][dy + ry] = h >= 0 says that the offsets (-h .. h, dy, dz) belong to E, -1 that none with this
+ *     (dy, dz) does.  Valid: every radius in 0 .. VR_MORPH_MAX_RADIUS; every entry of the (2 rz + 1) x (2 ry + 1) window in -1 .. rx;
+ *     half[rz][ry] >= 0 (the origin is in E); half[rz + dz][ry + dy] == half[rz - dz][ry + dy] == half[rz + dz][ry - dy].  Entries outside
+ *     the window are ignored.  Convexity is not required.
+ *   Operand: A' = the voxels of the box that are in contour src_contour of src_slot.  Nothing outside the box is read as set or written.
+ *   Operators (op), with E ignored by the first:
+ *     VR_MORPH_NONE    R = A' (the pure contour algebra)
+ *     VR_MORPH_DILATE  R = { p in the box : p - e in A' for some e in E }
+ *     VR_MORPH_ERODE   R = box \ dilate(box \ A'): p survives iff every p + e THAT LIES IN THE BOX is in A' (the outside does not erode)
+ *     VR_MORPH_CLOSE   R = erode(dilate(A'))
+ *     VR_MORPH_OPEN    R = dilate(erode(A'))
+ *     With these border rules closing is extensive, opening anti-extensive, and both are idempotent.
+ *   Writing (combine), into component dst_contour of dst_slot, voxels of the box only:
+ *     VR_MORPH_REPLACE  1.0f in R, +0.0f elsewhere          VR_MORPH_OR      1.0f in R, the rest keep their bits
+ *     VR_MORPH_AND      +0.0f outside R, the rest keep theirs  VR_MORPH_ANDNOT  +0.0f in R, the rest keep their bits
+ *     The other three components keep their bits (NaN payloads and -0 included), and so does every voxel outside the box.  A' is packed
+ *     before anything is written: src == dst, in slot and in contour, is legal and means "in place".
+ *   Destination: an empty dst_slot is created with the source's nx, ny, nz and every component +0.0f; one that holds a volume of other
+ *     dimensions is VR_ERR_INVALID_ARG.  dst_slot == src_slot is allowed.
+ *   Result: voxels = |R|, src_voxels = |A'|, lo / hi = the half-open bounding box of R, all zero when R is empty.
+ *   Counters (vr_morph_counters), out[1] + out[2] == out[0] always: out[0] = voxels of the box; out[1] = voxels of the box in the words
+ *     the last dilation launch of the call computed; out[2] = voxels of the box that were settled without computing them.  VR_MORPH_NONE
+ *     launches no dilation: out[1] = 0 in both kernel forms.
+ * Kernel forms: every flavour of vr_set_kernel_flavour but 1 computes only where the result can be set -- for a dilation the bounding box
+ * of its source bits grown by the radii, for an erosion that bounding box itself, both within the box -- and zero-fills the rest; flavour
+ * 1 computes every word of the box (out[1] == out[0] for the four operators with an element).  The mask and the result are identical
+ * across the forms and the volume layouts. */
+#define VR_MORPH_MAX_RADIUS 31
+#define VR_MORPH_NONE   0
+#define VR_MORPH_DILATE 1
+#define VR_MORPH_ERODE  2
+#define VR_MORPH_CLOSE  3
+#define VR_MORPH_OPEN   4
+#define VR_MORPH_REPLACE 0
+#define VR_MORPH_OR      1
+#define VR_MORPH_AND     2
+#define VR_MORPH_ANDNOT  3
+typedef struct vr_morph_element {
+    int32_t radius[3];                /* rx, ry, rz: 0 .. VR_MORPH_MAX_RADIUS                                  */
+    int8_t  half[2 * VR_MORPH_MAX_RADIUS + 1][2 * VR_MORPH_MAX_RADIUS + 1];
+                                      /* half[dz + rz][dy + ry] = h >= 0: offsets (-h .. h, dy, dz) are in E; -1: none is */
+} vr_morph_element;
+typedef struct vr_morph_desc {
+    int32_t src_slot, src_contour;    /* operand A: an uploaded slot, component 0 .. 3                         */
+    int32_t dst_slot, dst_contour;    /* where the result goes; may equal the source (in place)                */
+    int32_t op, combine;
+    int32_t box_lo[3], box_hi[3];     /* voxel box, half open, 0 <= lo <= hi <= n per axis                     */
+    vr_morph_element element;         /* checked and used only when op != VR_MORPH_NONE                        */
+} vr_morph_desc;
+typedef struct vr_morph_result {
+    uint64_t voxels, src_voxels;      /* |R|, |A'|                                                             */
+    int32_t  lo[3], hi[3];            /* half-open bounding box of R; all zero when R is empty                 */
+} vr_morph_result;
+
+/* The ball of `radius` on a grid of the given voxel spacing, both in one unit of the caller's choice (micrometres, say):
+ * (dx, dy, dz) is in E iff (dx sx)^2 + (dy sy)^2 + (dz sz)^2 <= radius^2, evaluated in uint64_t; the radii are radius / spacing by
+ * integer division; entries outside the window are -1.  Pure host integer arithmetic, no context and no device.  VR_ERR_INVALID_ARG for a
+ * NULL pointer, a spacing of zero or above 2^20, or a radius above VR_MORPH_MAX_RADIUS voxels on some axis. */
+int vr_morph_ball(const uint32_t spacing[3], uint32_t radius, vr_morph_element* out);
+
+/* The full box of radii rx, ry, rz (each 0 .. VR_MORPH_MAX_RADIUS, else VR_ERR_INVALID_ARG): every half-chord of the window is rx.
+ * (1, 1, 0) is a per-slice 3 x 3 element. */
+int vr_morph_box(int rx, int ry, int rz, vr_morph_element* out);
+
+/* Fills *out for the whole volume of src_slot: the given slots, contours and operator, VR_MORPH_REPLACE, the box (0,0,0) .. (nx,ny,nz)
+ * and the radius-1 ball of unit spacing (the 6-neighbour cross).  Pure host arithmetic; VR_ERR_INVALID_ARG for a NULL pointer, a slot
+ * or contour out of range or an unknown operator, VR_ERR_NOT_READY for an empty source slot. */
+int vr_morph_whole(const vr_ctx* ctx, int src_slot, int src_contour, int dst_slot, int dst_contour, int op, vr_morph_desc* out);
+
+/* Does the work; `result` may be NULL.  A data-preparation call exactly like vr_segment_grow: it waits for everything in flight, runs
+ * on the ctx's own stream, rebuilds what is derived from the destination slot's voxels as an upload does and is synchronous on return.
+ * What the reporting calls say about the last march, slice, histogram or grow stays as it was.
+ * Checked before anything is enqueued or a slot is touched.  VR_ERR_INVALID_ARG: a NULL ctx or descriptor; a slot out of range; a
+ * contour outside 0 .. 3; an unknown op or combine; a box that is not 0 <= lo <= hi <= n on every axis; an invalid element when
+ * op != VR_MORPH_NONE; a destination slot of other dimensions.  VR_ERR_NOT_READY: the source slot is empty. */
+int vr_mask_morph(vr_ctx* ctx, const vr_morph_desc* desc, vr_morph_result* result);
+
+/* Counters of the last vr_mask_morph (as described above).  Zeros before the first. */
+int vr_morph_counters(vr_ctx* ctx, uint64_t out[3]);
+
+/* Device time of the last vr_mask_morph in milliseconds, from events on the ctx's stream: ms[0] the pack of the operand (the host's
+ * look at its bounding box included), ms[1] the dilation launches, ms[2] the write and the result, ms[3] the rebuild of what is derived
+ * from the destination slot.  Zeros before the first and after one that failed. */
+int vr_morph_timing(vr_ctx* ctx, float ms[4]);
+
 /* Volume layout in HBM (A/B measurements; frames and counts are bit-identical in every mode).
  *   0  default: the march kernels gather from a BRICKED copy of every slot -- the vec4 voxels and a scalar f32 density plane
  *      (what fetches that consume .a alone read: BasicVolumeApp.wgsl:171, the density / dose fetches of the other shaders)

@@ -38,6 +38,9 @@ GROW_FACES, GROW_ALL = 6, 26                     # vr_grow_desc.connectivity (in
 GROW_REPLACE, GROW_ADD = 0, 1                    # vr_grow_desc.mode
 GROW_MAX_SEEDS = 64
 GROW_BATCH = 8                                   # propagation rounds enqueued between two looks at the outcome (VR_GROW_BATCH)
+MORPH_MAX_RADIUS = 31                            # vr_morph_element (include/vr.h)
+MORPH_NONE, MORPH_DILATE, MORPH_ERODE, MORPH_CLOSE, MORPH_OPEN = range(5)   # vr_morph_desc.op
+MORPH_REPLACE, MORPH_OR, MORPH_AND, MORPH_ANDNOT = range(4)                 # vr_morph_desc.combine
 
 # every symbol include/vr.h declares (tests check that the library exports each of them)
 ABI_SYMBOLS = [
@@ -57,6 +60,7 @@ ABI_SYMBOLS = [
     "vr_slice_async", "vr_slice_render", "vr_slice_orthogonal", "vr_slice_counters",
     "vr_hist_whole", "vr_histogram_async", "vr_histogram", "vr_hist_counters",
     "vr_grow_whole", "vr_segment_grow", "vr_grow_counters", "vr_grow_timing",
+    "vr_morph_ball", "vr_morph_box", "vr_morph_whole", "vr_mask_morph", "vr_morph_counters", "vr_morph_timing",
 ]
 
 
@@ -161,6 +165,45 @@ class GrowResult(C.Structure):
         return int(self.voxels), tuple(int(x) for x in self.lo), tuple(int(x) for x in self.hi)
 
 
+class MorphElement(C.Structure):
+    """struct vr_morph_element (include/vr.h): the radii (rx, ry, rz) and the half-chords along x, half[dz + rz][dy + ry]."""
+    _fields_ = [("radius", C.c_int32 * 3), ("half", (C.c_int8 * (2 * MORPH_MAX_RADIUS + 1)) * (2 * MORPH_MAX_RADIUS + 1))]
+
+    def table(self) -> np.ndarray:
+        """The used window of the half-chords as an int8 array [2 rz + 1][2 ry + 1]."""
+        rx, ry, rz = (int(r) for r in self.radius)
+        return np.ctypeslib.as_array(self.half)[:2 * rz + 1, :2 * ry + 1].copy()
+
+
+class MorphDesc(C.Structure):
+    """struct vr_morph_desc (include/vr.h): the source slot and contour, the destination slot and contour, the operator, the way the
+    result is stored, the voxel box and the structuring element."""
+    _fields_ = [
+        ("src_slot", C.c_int32), ("src_contour", C.c_int32), ("dst_slot", C.c_int32), ("dst_contour", C.c_int32),
+        ("op", C.c_int32), ("combine", C.c_int32), ("box_lo", C.c_int32 * 3), ("box_hi", C.c_int32 * 3), ("element", MorphElement),
+    ]
+
+    def copy(self, **over) -> "MorphDesc":
+        """A copy with the given fields replaced (box_lo / box_hi from any sequence of three integers; element from a MorphElement,
+        which is copied)."""
+        d = MorphDesc.from_buffer_copy(bytes(self))
+        for k, v in over.items():
+            if k in ("box_lo", "box_hi"):
+                v = (C.c_int32 * 3)(*[int(x) for x in v])
+            if k == "element":
+                v = MorphElement.from_buffer_copy(bytes(v))
+            setattr(d, k, v)
+        return d
+
+
+class MorphResult(C.Structure):
+    """struct vr_morph_result: |R|, |A'| and the half-open bounding box of R (zeros when empty)."""
+    _fields_ = [("voxels", C.c_uint64), ("src_voxels", C.c_uint64), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3)]
+
+    def as_tuple(self):
+        return int(self.voxels), int(self.src_voxels), tuple(int(x) for x in self.lo), tuple(int(x) for x in self.hi)
+
+
 class VrError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"vr error {code}: {msg}")
@@ -250,6 +293,12 @@ def load() -> C.CDLL:
     lib.vr_segment_grow.argtypes = [vp, C.POINTER(GrowDesc), C.POINTER(GrowResult)]
     lib.vr_grow_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
     lib.vr_grow_timing.argtypes = [vp, C.POINTER(C.c_float * 4)]
+    lib.vr_morph_ball.argtypes = [C.POINTER(C.c_uint32 * 3), C.c_uint32, C.POINTER(MorphElement)]
+    lib.vr_morph_box.argtypes = [i32, i32, i32, C.POINTER(MorphElement)]
+    lib.vr_morph_whole.argtypes = [vp, i32, i32, i32, i32, i32, C.POINTER(MorphDesc)]
+    lib.vr_mask_morph.argtypes = [vp, C.POINTER(MorphDesc), C.POINTER(MorphResult)]
+    lib.vr_morph_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
+    lib.vr_morph_timing.argtypes = [vp, C.POINTER(C.c_float * 4)]
     lib.vr_present_async.argtypes = [vp, vp, vp, vp]
     lib.vr_present_tiles_async.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
     lib.vr_hint_frames_in_flight.argtypes = [vp, i32]
@@ -624,6 +673,30 @@ class Context:
         self._chk(self.lib.vr_grow_timing(self.h, C.byref(out)))
         return tuple(float(x) for x in out)
 
+    def morph_whole(self, src_slot: int, src_contour: int, dst_slot: int, dst_contour: int, op: int) -> MorphDesc:
+        """vr_morph_whole: the descriptor of an operator over the whole volume (REPLACE, the radius-1 ball of unit spacing)."""
+        d = MorphDesc()
+        self._chk(self.lib.vr_morph_whole(self.h, src_slot, src_contour, dst_slot, dst_contour, op, C.byref(d)))
+        return d
+
+    def mask_morph(self, desc: MorphDesc) -> MorphResult:
+        """vr_mask_morph: dilates, erodes, closes, opens or takes a contour and combines the result into a contour (synchronous)."""
+        out = MorphResult()
+        self._chk(self.lib.vr_mask_morph(self.h, C.byref(desc), C.byref(out)))
+        return out
+
+    def morph_counters(self):
+        """(voxels of the box, voxels the last dilation launch computed, voxels settled without computing) of the last mask_morph."""
+        out = (C.c_uint64 * 3)()
+        self._chk(self.lib.vr_morph_counters(self.h, C.byref(out)))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def morph_timing(self):
+        """(pack, morphology, write, refresh) of the last mask_morph in ms of device time (vr_morph_timing)."""
+        out = (C.c_float * 4)()
+        self._chk(self.lib.vr_morph_timing(self.h, C.byref(out)))
+        return tuple(float(x) for x in out)
+
     def set_volume_layout(self, mode: int):
         """0 bricked copy (default), 1 the reference's vec4 voxels only, 3 x-fastest voxels + density plane (2 was removed)."""
         self._chk(self.lib.vr_set_volume_layout(self.h, mode))
@@ -636,3 +709,23 @@ class Context:
 
     def set_kernel_flavour(self, flavour: int):
         self._chk(self.lib.vr_set_kernel_flavour(self.h, flavour))
+
+
+def morph_ball(spacing, radius: int) -> MorphElement:
+    """vr_morph_ball: the ball of `radius` on a grid of voxel spacing (sx, sy, sz), all in one integer unit (micrometres, say).  Host
+    arithmetic: needs no context and no device."""
+    e = MorphElement()
+    sp = (C.c_uint32 * 3)(*[int(x) for x in spacing])
+    rc = load().vr_morph_ball(C.byref(sp), int(radius), C.byref(e))
+    if rc != VR_OK:
+        raise VrError(rc, f"vr_morph_ball: spacing {tuple(spacing)}, radius {radius}")
+    return e
+
+
+def morph_box(rx: int, ry: int, rz: int) -> MorphElement:
+    """vr_morph_box: the full box of radii (rx, ry, rz).  Host arithmetic: needs no context and no device."""
+    e = MorphElement()
+    rc = load().vr_morph_box(int(rx), int(ry), int(rz), C.byref(e))
+    if rc != VR_OK:
+        raise VrError(rc, f"vr_morph_box: radii {(rx, ry, rz)}")
+    return e

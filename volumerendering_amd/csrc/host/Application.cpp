@@ -1,5 +1,6 @@
 #include "Application.h"
 
+#include <cmath>
 #include <cstring>
 
 namespace med {
@@ -156,6 +157,32 @@ int Application::GrowFromPick(const vr_pick_result& pick, int valueSlot, int mas
     rc = vr_segment_grow(p_Ctx, &d, out);
     if (rc != VR_OK) m_Error = vr_last_error(p_Ctx);
     return rc;
+}
+
+int Application::MorphContour(const vr_morph_desc& desc, vr_morph_result* out)
+{
+    if (!p_Ctx) return VR_ERR_NOT_READY;
+    const int rc = vr_mask_morph(p_Ctx, &desc, out);
+    if (rc != VR_OK) m_Error = vr_last_error(p_Ctx);
+    return rc;
+}
+
+int Application::MarginMm(int srcSlot, int srcContour, int dstSlot, int dstContour, float mm, const VolumeFileDcm& grid, vr_morph_result* out)
+{
+    if (!p_Ctx) return VR_ERR_NOT_READY;
+    const DicomVolumeParams p = grid.GetVolumeParams();
+    const double mmOf[4] = {p.PixelSpacing[0], p.PixelSpacing[1], p.SliceThickness, (double)mm};
+    uint32_t um[4];
+    for (int i = 0; i < 4; ++i) {
+        if (!std::isfinite(mmOf[i]) || mmOf[i] < 0.0 || mmOf[i] > 4.0e6) return VR_ERR_INVALID_ARG;  // (micrometres fit 32 bits)
+        um[i] = (uint32_t)std::lround(mmOf[i] * 1000.0);
+    }
+    vr_morph_desc d;
+    int rc = vr_morph_whole(p_Ctx, srcSlot, srcContour, dstSlot, dstContour, VR_MORPH_DILATE, &d);
+    if (rc != VR_OK) return rc;
+    rc = vr_morph_ball(um, um[3], &d.element);
+    if (rc != VR_OK) return rc;
+    return MorphContour(d, out);
 }
 
 int Application::Pick(uint32_t x, uint32_t y, vr_pick_result* out)

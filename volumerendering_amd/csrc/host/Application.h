@@ -10,6 +10,7 @@
 
 #include "Camera.h"
 #include "MiniApp.h"
+#include "dicom/VolumeFileDcm.h"
 #include "vr.h"
 
 namespace med {
@@ -65,6 +66,14 @@ public:
     // in [lo, hi] and that are connected to pick.voxel (vr_segment_grow over the whole volume, VR_GROW_REPLACE; connectivity =
     // VR_GROW_FACES / VR_GROW_ALL).  `out` may be nullptr.  A pick without a hit returns VR_ERR_INVALID_ARG.
     int GrowFromPick(const vr_pick_result& pick, int valueSlot, int maskSlot, int contour, float lo, float hi, int connectivity, vr_grow_result* out);
+    // Morphology and algebra of mask contours on the device (vr_mask_morph of include/vr.h): dilate, erode, close or open a contour by a
+    // structuring element, or take it as it is, and combine the result into a contour.  `out` may be nullptr.
+    int MorphContour(const vr_morph_desc& desc, vr_morph_result* out);
+    // Contour srcContour of volume srcSlot grown by a margin of `mm` millimetres on the voxel grid of `grid` (its PixelSpacing and
+    // SliceThickness), into contour dstContour of volume dstSlot: VR_MORPH_DILATE with VR_MORPH_REPLACE over the whole volume by
+    // vr_morph_ball, the spacings and the radius each rounded to whole micrometres with lround.  VR_ERR_INVALID_ARG for a margin that
+    // is negative or not finite, a spacing that is not positive, or a margin beyond VR_MORPH_MAX_RADIUS voxels on some axis.
+    int MarginMm(int srcSlot, int srcContour, int dstSlot, int dstContour, float mm, const VolumeFileDcm& grid, vr_morph_result* out);
     // the accumulated opacity at which the unlit / lit scene's surface lies (vr_set_surface_threshold: finite, 0 <= tau < 1)
     int SetSurfaceThreshold(float tau);
 

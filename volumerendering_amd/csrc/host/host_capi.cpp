@@ -409,6 +409,18 @@ int vrh_app_grow_from_pick(void* a, const vr_pick_result* pick, int value_slot, 
     if (!pick) return VR_ERR_INVALID_ARG;
     VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->GrowFromPick(*pick, value_slot, mask_slot, contour, lo, hi, connectivity, out); })
 }
+// Application::MorphContour and Application::MarginMm (vr_mask_morph of the application's context); grid: a volume read by DicomReader
+int vrh_app_morph_contour(void* a, const vr_morph_desc* desc, vr_morph_result* out)
+{
+    if (!desc) return VR_ERR_INVALID_ARG;
+    VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->MorphContour(*desc, out); })
+}
+int vrh_app_margin_mm(void* a, int src_slot, int src_contour, int dst_slot, int dst_contour, float mm, void* grid, vr_morph_result* out)
+{
+    auto* vh = static_cast<VolumeHandle*>(grid);
+    if (!vh || !vh->dcm) return VR_ERR_INVALID_ARG;
+    VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->MarginMm(src_slot, src_contour, dst_slot, dst_contour, mm, *vh->dcm, out); })
+}
 int vrh_app_set_surface_threshold(void* a, float tau) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->SetSurfaceThreshold(tau); }) }
 void vrh_app_set_prepare_on_device(void* a, int on) { static_cast<Application*>(a)->m_PrepareOnDevice = on != 0; }
 int vrh_app_update(void* a) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->OnUpdate(); }) }

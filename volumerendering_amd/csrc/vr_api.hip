@@ -8,6 +8,8 @@
 #include "vr_hist.h"
 // Region growing (vr_segment_grow): integer work on bit-bricks, compiled once as well
 #include "vr_grow.h"
+// Mask morphology (vr_mask_morph): integer work on bit-rows, compiled once as well
+#include "vr_morph.h"
 
 // the same dispatch over the kernels compiled with fused multiply-adds (vr_fused.hip)
 namespace vrf {
@@ -34,6 +36,7 @@ using namespace vr;
 #include "vr_api_render.h"
 #include "vr_api_views.h"
 #include "vr_api_segment.h"
+#include "vr_api_morph.h"
 
 namespace {
 

@@ -1,0 +1,357 @@
+// vr_api_morph.h -- mask morphology and contour algebra on the device (vr_mask_morph; the kernels are vr_morph.h's) and the two host
+// fillers of a structuring element.  vr_mask_morph is a data-preparation call like vr_segment_grow: it drains the device, runs on the
+// context's stream, ends with bind_voxels for a slot it created and with refresh_bricks otherwise, and is synchronous on return.
+// Part of vr_api.hip's translation unit.
+#pragma once
+
+namespace {
+
+constexpr int kMorphSide = 2 * VR_MORPH_MAX_RADIUS + 1;
+
+// the rules of include/vr.h for an element; nullptr if it meets them, else what is wrong
+const char* check_element(const vr_morph_element& e)
+{
+    for (int a = 0; a < 3; ++a)
+        if (e.radius[a] < 0 || e.radius[a] > VR_MORPH_MAX_RADIUS) return "a radius of the element is outside 0 .. 31";
+    const int rx = e.radius[0], ry = e.radius[1], rz = e.radius[2];
+    if (e.half[rz][ry] < 0) return "the element does not hold the origin";
+    for (int dz = 0; dz <= rz; ++dz)
+        for (int dy = 0; dy <= ry; ++dy) {
+            const int h = e.half[rz + dz][ry + dy];
+            if (h < -1 || h > rx) return "a half-chord of the element is outside -1 .. rx";
+            if (e.half[rz - dz][ry + dy] != h || e.half[rz + dz][ry - dy] != h || e.half[rz - dz][ry - dy] != h)
+                return "the element is not symmetric under reflection of y or z";
+        }
+    return nullptr;
+}
+
+// the descriptor's own fields (VR_ERR_INVALID_ARG), then what the context must hold (VR_ERR_NOT_READY, the box, the destination)
+int check_morph(vr_ctx* c, const vr_morph_desc* d)
+{
+    const std::string w("vr_mask_morph");
+    if (!d) return fail(c, VR_ERR_INVALID_ARG, w + ": the descriptor is NULL");
+    if (d->src_slot < 0 || d->src_slot >= VR_MAX_VOLUMES) return fail(c, VR_ERR_INVALID_ARG, w + ": bad source slot");
+    if (d->dst_slot < 0 || d->dst_slot >= VR_MAX_VOLUMES) return fail(c, VR_ERR_INVALID_ARG, w + ": bad destination slot");
+    if (d->src_contour < 0 || d->src_contour > 3) return fail(c, VR_ERR_INVALID_ARG, w + ": the source contour must be 0 .. 3");
+    if (d->dst_contour < 0 || d->dst_contour > 3) return fail(c, VR_ERR_INVALID_ARG, w + ": the destination contour must be 0 .. 3");
+    if (d->op < VR_MORPH_NONE || d->op > VR_MORPH_OPEN) return fail(c, VR_ERR_INVALID_ARG, w + ": unknown op");
+    if (d->combine < VR_MORPH_REPLACE || d->combine > VR_MORPH_ANDNOT) return fail(c, VR_ERR_INVALID_ARG, w + ": unknown combine");
+    if (d->op != VR_MORPH_NONE)
+        if (const char* what = check_element(d->element)) return fail(c, VR_ERR_INVALID_ARG, w + ": " + what);
+    const DevVolume& v = c->vols[d->src_slot].vol;
+    if (!v.data) return fail(c, VR_ERR_NOT_READY, w + ": source slot " + std::to_string(d->src_slot) + " is empty");
+    const int n[3] = {v.nx, v.ny, v.nz};
+    for (int a = 0; a < 3; ++a)
+        if (d->box_lo[a] < 0 || d->box_lo[a] > d->box_hi[a] || d->box_hi[a] > n[a])
+            return fail(c, VR_ERR_INVALID_ARG, w + ": the box must be 0 <= lo <= hi <= n on every axis");
+    const DevVolume& m = c->vols[d->dst_slot].vol;
+    if (m.data && (m.nx != v.nx || m.ny != v.ny || m.nz != v.nz)) return fail(c, VR_ERR_INVALID_ARG, w + ": the destination's dimensions differ from the source's");
+    return VR_OK;
+}
+
+// the working buffers of a call over nw words per bit-row buffer, and its events (first use)
+int prepare_morph_state(vr_ctx* c, size_t nw)
+{
+    MorphState& M = c->morph;
+    // (the device is drained and every earlier use was synchronous: a smaller buffer is freed at once)
+    if (const int rc = grow(c, M.words, 3 * nw, true)) return rc;
+    if (!M.rows) VR_HIP(c, M.rows.reserve((size_t)kMorphSide * kMorphSide));
+    if (!M.h_rows) VR_HIP(c, M.h_rows.reserve((size_t)kMorphSide * kMorphSide, true));
+    if (!M.d_words) VR_HIP(c, M.d_words.reserve(1));
+    if (!M.h_words) VR_HIP(c, M.h_words.reserve(1, true));
+    for (Event& e : M.ev)
+        if (!e) VR_HIP(c, e.create());
+    return VR_OK;
+}
+
+// a half-open voxel region; empty when some hi <= lo
+struct MorphRegion {
+    int lo[3], hi[3];
+    bool empty() const { return hi[0] <= lo[0] || hi[1] <= lo[1] || hi[2] <= lo[2]; }
+};
+
+// One dilation launch over the words that meet `reg` (a part of the box): dst is zeroed first and keeps zeros outside them.
+// *computed = the voxels of the box in those words.
+int morph_pass(vr_ctx* c, const MorphParams& P, const unsigned long long* src, unsigned long long* dst, size_t nw, bool comp,
+               const MorphRegion& reg, unsigned long long* computed)
+{
+    hipStream_t s = c->stream;
+    VR_HIP(c, hipMemsetAsync(dst, 0, nw * sizeof(unsigned long long), s));
+    *computed = 0;
+    if (reg.empty()) return VR_OK;
+    MorphPass S;
+    S.src = src;
+    S.dst = dst;
+    S.rw0 = reg.lo[0] >> 6;
+    S.rw = ((reg.hi[0] + 63) >> 6) - S.rw0;
+    S.ry0 = reg.lo[1];
+    S.ry = reg.hi[1] - reg.lo[1];
+    S.rz0 = reg.lo[2];
+    S.rz = reg.hi[2] - reg.lo[2];
+    S.words = (unsigned long long)S.rw * (unsigned long long)S.ry * (unsigned long long)S.rz;
+    const int x0 = S.rw0 << 6 > P.lo[0] ? S.rw0 << 6 : P.lo[0], x1 = (S.rw0 + S.rw) << 6 < P.hi[0] ? (S.rw0 + S.rw) << 6 : P.hi[0];
+    *computed = (unsigned long long)(x1 - x0) * (unsigned long long)S.ry * (unsigned long long)S.rz;
+    const unsigned blocks = (unsigned)((S.words + 255ull) / 256ull);  // (at most 2^32 / 64 words: below 2^18 blocks)
+    if (comp) hipLaunchKernelGGL(morph_dilate_kernel<true>, dim3(blocks), dim3(256), 0, s, P, S);
+    else hipLaunchKernelGGL(morph_dilate_kernel<false>, dim3(blocks), dim3(256), 0, s, P, S);
+    VR_HIP(c, hipGetLastError());
+    return VR_OK;
+}
+
+// The call itself, every argument checked and the device drained.  `fresh`: the destination slot's voxels were allocated and zeroed by
+// this call.
+int run_morph(vr_ctx* c, const vr_morph_desc& d, float4* dst, bool fresh, vr_morph_result* result)
+{
+    MorphState& M = c->morph;
+    hipStream_t s = c->stream;
+    const DevVolume& v = c->vols[d.src_slot].vol;
+    MorphParams P;
+    std::memset(&P, 0, sizeof P);
+    P.src = v.data;
+    P.dst = dst;
+    P.src_contour = d.src_contour;
+    P.dst_contour = d.dst_contour;
+    P.nx = v.nx;
+    P.ny = v.ny;
+    P.nz = v.nz;
+    P.wx = (v.nx + 63) >> 6;
+    unsigned long long box = 1;
+    for (int a = 0; a < 3; ++a) {
+        P.lo[a] = d.box_lo[a];
+        P.hi[a] = d.box_hi[a];
+        box *= (unsigned long long)(d.box_hi[a] - d.box_lo[a]);
+    }
+    P.bw0 = P.lo[0] >> 6;
+    P.bw = ((P.hi[0] + 63) >> 6) - P.bw0;
+    P.box_words = box == 0 ? 0ull : (unsigned long long)P.bw * (unsigned long long)(P.hi[1] - P.lo[1]) * (unsigned long long)(P.hi[2] - P.lo[2]);
+    P.combine = d.combine;
+    P.fresh = fresh ? 1 : 0;
+    const size_t nw = (size_t)P.wx * (size_t)v.ny * (size_t)v.nz;
+    if (const int rc = prepare_morph_state(c, nw)) return rc;
+    unsigned long long* const A = M.words.p;
+    unsigned long long* const B = M.words.p + nw;
+    unsigned long long* const C = M.words.p + 2 * nw;
+    P.a = A;
+    P.w = M.d_words;
+    const int requested = c->flavour == 0 ? c->default_flavour : c->flavour;
+    const bool plain = requested == 1;
+    const bool morph = d.op != VR_MORPH_NONE;
+    const int rad[3] = {morph ? d.element.radius[0] : 0, morph ? d.element.radius[1] : 0, morph ? d.element.radius[2] : 0};
+    if (morph) {  // the element's rows, sorted by half-chord, largest first (a counting sort over h = rx .. 0)
+        unsigned* rows = M.h_rows;
+        int n = 0;
+        for (int h = rad[0]; h >= 0; --h)
+            for (int dz = -rad[2]; dz <= rad[2]; ++dz)
+                for (int dy = -rad[1]; dy <= rad[1]; ++dy)
+                    if (d.element.half[dz + rad[2]][dy + rad[1]] == h) rows[n++] = (unsigned)h | (unsigned)(dy + 32) << 8 | (unsigned)(dz + 32) << 16;
+        P.n_rows = n;
+        P.hmax = (int)(rows[0] & 0xFFu);  // (n >= 1: the origin's row)
+        VR_HIP(c, hipMemcpyAsync(M.rows, M.h_rows, (size_t)n * sizeof(unsigned), hipMemcpyHostToDevice, s));
+        P.rows = M.rows;
+    }
+    const unsigned blocks = P.box_words < 4 ? 1u : (P.box_words / 4 < kMorphBlocks ? (unsigned)(P.box_words / 4) : kMorphBlocks);
+
+    VR_HIP(c, hipEventRecord(M.ev[0], s));
+    MorphWords init;
+    std::memset(&init, 0, sizeof init);
+    for (int a = 0; a < 3; ++a) init.src_lo[a] = init.lo[a] = 0x7fffffff;
+    *M.h_words.p = init;
+    VR_HIP(c, hipMemcpyAsync(M.d_words, M.h_words, sizeof(MorphWords), hipMemcpyHostToDevice, s));
+    VR_HIP(c, hipMemsetAsync(A, 0, nw * sizeof(unsigned long long), s));
+    if (P.box_words != 0) {
+        hipLaunchKernelGGL(morph_pack_kernel, dim3(blocks), dim3(256), 0, s, P);
+        VR_HIP(c, hipGetLastError());
+    }
+    VR_HIP(c, hipMemcpyAsync(M.h_words, M.d_words, sizeof(MorphWords), hipMemcpyDeviceToHost, s));
+    VR_HIP(c, hipStreamSynchronize(s));
+    const MorphWords packed = *M.h_words.p;
+    VR_HIP(c, hipEventRecord(M.ev[1], s));
+
+    // Where the result of a pass can be set: a dilation's within the bounding box of its source bits grown by the radii, an erosion's
+    // within that bounding box itself (the origin is in E), both within the box.  The plain form takes the whole box.
+    MorphRegion bb, grown, whole;
+    for (int a = 0; a < 3; ++a) {
+        whole.lo[a] = P.lo[a];
+        whole.hi[a] = box == 0 ? P.lo[a] : P.hi[a];
+        bb.lo[a] = packed.src_voxels ? packed.src_lo[a] : 0;
+        bb.hi[a] = packed.src_voxels ? packed.src_hi[a] : 0;
+        grown.lo[a] = bb.lo[a] - rad[a] > P.lo[a] ? bb.lo[a] - rad[a] : P.lo[a];
+        grown.hi[a] = bb.hi[a] + rad[a] < P.hi[a] ? bb.hi[a] + rad[a] : P.hi[a];
+        if (!packed.src_voxels) grown.hi[a] = grown.lo[a] = P.lo[a];
+    }
+    if (plain) bb = grown = whole;
+    unsigned long long computed = 0;
+    const unsigned long long* R = A;
+    switch (d.op) {
+    case VR_MORPH_DILATE:
+        if (const int rc = morph_pass(c, P, A, B, nw, false, grown, &computed)) return rc;
+        R = B;
+        break;
+    case VR_MORPH_ERODE:
+        if (const int rc = morph_pass(c, P, A, B, nw, true, bb, &computed)) return rc;
+        R = B;
+        break;
+    case VR_MORPH_CLOSE:  // (the dilation is empty outside `grown`, and the erosion of it is a part of it)
+        if (const int rc = morph_pass(c, P, A, B, nw, false, grown, &computed)) return rc;
+        if (const int rc = morph_pass(c, P, B, C, nw, true, grown, &computed)) return rc;
+        R = C;
+        break;
+    case VR_MORPH_OPEN:  // (the erosion is a part of A': its bounding box lies within A''s)
+        if (const int rc = morph_pass(c, P, A, B, nw, true, bb, &computed)) return rc;
+        if (const int rc = morph_pass(c, P, B, C, nw, false, grown, &computed)) return rc;
+        R = C;
+        break;
+    default: break;
+    }
+    P.r = R;
+    VR_HIP(c, hipEventRecord(M.ev[2], s));
+
+    if (P.box_words != 0) {
+        hipLaunchKernelGGL(morph_write_kernel, dim3(blocks), dim3(256), 0, s, P);
+        VR_HIP(c, hipGetLastError());
+    }
+    VR_HIP(c, hipMemcpyAsync(M.h_words, M.d_words, sizeof(MorphWords), hipMemcpyDeviceToHost, s));
+    VR_HIP(c, hipEventRecord(M.ev[3], s));
+    VR_HIP(c, hipStreamSynchronize(s));
+    const MorphWords& w = *M.h_words.p;
+    M.counters[0] = box;
+    M.counters[1] = computed;
+    M.counters[2] = box - computed;
+    if (result) {
+        std::memset(result, 0, sizeof *result);
+        result->voxels = w.voxels;
+        result->src_voxels = w.src_voxels;
+        for (int a = 0; a < 3 && w.voxels != 0; ++a) {
+            result->lo[a] = w.lo[a];
+            result->hi[a] = w.hi[a];
+        }
+    }
+    return VR_OK;
+}
+
+void fill_element(vr_morph_element* e, int rx, int ry, int rz)
+{
+    std::memset(e->half, -1, sizeof e->half);
+    e->radius[0] = rx;
+    e->radius[1] = ry;
+    e->radius[2] = rz;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vr_morph_ball(const uint32_t spacing[3], uint32_t radius, vr_morph_element* out)
+{
+    if (!spacing || !out) return VR_ERR_INVALID_ARG;
+    int r[3];
+    for (int a = 0; a < 3; ++a) {
+        if (spacing[a] == 0 || spacing[a] > (1u << 20)) return VR_ERR_INVALID_ARG;
+        if (radius / spacing[a] > VR_MORPH_MAX_RADIUS) return VR_ERR_INVALID_ARG;
+        r[a] = (int)(radius / spacing[a]);
+    }
+    fill_element(out, r[0], r[1], r[2]);
+    // (|d| <= 31 and a spacing <= 2^20: a term is below 2^50, the sum of three below 2^52)
+    const uint64_t rr = (uint64_t)radius * radius, sx = spacing[0], sy = spacing[1], sz = spacing[2];
+    for (int dz = -r[2]; dz <= r[2]; ++dz)
+        for (int dy = -r[1]; dy <= r[1]; ++dy) {
+            const uint64_t ay = (uint64_t)(dy < 0 ? -dy : dy) * sy, az = (uint64_t)(dz < 0 ? -dz : dz) * sz;
+            const uint64_t yz = ay * ay + az * az;
+            int h = -1;
+            for (int dx = 0; dx <= r[0]; ++dx) {
+                const uint64_t ax = (uint64_t)dx * sx;
+                if (ax * ax + yz <= rr) h = dx;
+                else break;
+            }
+            out->half[dz + r[2]][dy + r[1]] = (int8_t)h;
+        }
+    return VR_OK;
+}
+
+int vr_morph_box(int rx, int ry, int rz, vr_morph_element* out)
+{
+    if (!out) return VR_ERR_INVALID_ARG;
+    if (rx < 0 || rx > VR_MORPH_MAX_RADIUS || ry < 0 || ry > VR_MORPH_MAX_RADIUS || rz < 0 || rz > VR_MORPH_MAX_RADIUS) return VR_ERR_INVALID_ARG;
+    fill_element(out, rx, ry, rz);
+    for (int z = 0; z <= 2 * rz; ++z)
+        for (int y = 0; y <= 2 * ry; ++y) out->half[z][y] = (int8_t)rx;
+    return VR_OK;
+}
+
+int vr_morph_whole(const vr_ctx* c, int src_slot, int src_contour, int dst_slot, int dst_contour, int op, vr_morph_desc* out)
+{
+    if (!c || !out) return VR_ERR_INVALID_ARG;
+    if (src_slot < 0 || src_slot >= VR_MAX_VOLUMES || dst_slot < 0 || dst_slot >= VR_MAX_VOLUMES || src_contour < 0 || src_contour > 3 ||
+        dst_contour < 0 || dst_contour > 3 || op < VR_MORPH_NONE || op > VR_MORPH_OPEN)
+        return VR_ERR_INVALID_ARG;
+    if (!c->vols[src_slot].vol.data) return VR_ERR_NOT_READY;
+    std::memset(out, 0, sizeof *out);
+    out->src_slot = src_slot;
+    out->src_contour = src_contour;
+    out->dst_slot = dst_slot;
+    out->dst_contour = dst_contour;
+    out->op = op;
+    out->combine = VR_MORPH_REPLACE;
+    out->box_hi[0] = c->vols[src_slot].vol.nx;
+    out->box_hi[1] = c->vols[src_slot].vol.ny;
+    out->box_hi[2] = c->vols[src_slot].vol.nz;
+    const uint32_t unit[3] = {1, 1, 1};
+    return vr_morph_ball(unit, 1, &out->element);
+}
+
+int vr_mask_morph(vr_ctx* c, const vr_morph_desc* desc, vr_morph_result* result)
+{
+    if (!c) return VR_ERR_INVALID_ARG;
+    if (const int rc = check_morph(c, desc)) return rc;
+    if (const int rc = drain(c)) return rc;  // asynchronous renders on the caller's streams may still read the destination slot
+    (void)hipGetLastError();
+    const int ds = desc->dst_slot;
+    VolumeSlot& D = c->vols[ds];
+    const DevVolume& v = c->vols[desc->src_slot].vol;
+    const uint16_t nx = (uint16_t)v.nx, ny = (uint16_t)v.ny, nz = (uint16_t)v.nz;
+    const bool fresh = !D.vol.data;
+    if (fresh) {  // an empty destination slot: the source's dimensions, every component +0.0f
+        const size_t n = (size_t)nx * ny * nz;
+        float4* dst;
+        if (D.voxels && D.voxels.cap != n) D.voxels.release();
+        if (const int rc = voxels_for_upload(c, ds, n, &dst)) return rc;
+        const hipError_t e = hipMemsetAsync(dst, 0, n * sizeof(float4), c->stream);
+        if (e != hipSuccess) {
+            D.voxels.release();
+            return fail(c, VR_ERR_HIP, std::string("vr_mask_morph: hipMemsetAsync failed: ") + hipGetErrorString(e));
+        }
+    }
+    for (float& t : c->morph.ms) t = 0.0f;
+    int rc = run_morph(c, *desc, D.voxels, fresh, result);
+    if (rc != VR_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        if (fresh) D.voxels.release();  // (the slot stays empty)
+        return rc;
+    }
+    rc = fresh ? bind_voxels(c, ds, nx, ny, nz) : refresh_bricks(c, ds);
+    if (rc != VR_OK) return rc;
+    MorphState& M = c->morph;
+    VR_HIP(c, hipEventRecord(M.ev[4], c->stream));
+    VR_HIP(c, hipEventSynchronize(M.ev[4]));
+    for (int i = 0; i < 4; ++i)
+        if (hipEventElapsedTime(&M.ms[i], M.ev[i], M.ev[i + 1]) != hipSuccess) M.ms[i] = 0.0f;
+    return VR_OK;
+}
+
+int vr_morph_counters(vr_ctx* c, uint64_t out[3])
+{
+    if (!c) return VR_ERR_INVALID_ARG;
+    if (!out) return fail(c, VR_ERR_INVALID_ARG, "vr_morph_counters: out is NULL");
+    for (int i = 0; i < 3; ++i) out[i] = c->morph.counters[i];
+    return VR_OK;
+}
+
+int vr_morph_timing(vr_ctx* c, float ms[4])
+{
+    if (!c) return VR_ERR_INVALID_ARG;
+    if (!ms) return fail(c, VR_ERR_INVALID_ARG, "vr_morph_timing: ms is NULL");
+    for (int i = 0; i < 4; ++i) ms[i] = c->morph.ms[i];
+    return VR_OK;
+}
+
+}  // extern "C"

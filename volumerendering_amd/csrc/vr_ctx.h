@@ -161,6 +161,19 @@ struct GrowState {
     float ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 };
 
+// Mask morphology (vr_mask_morph, vr_morph.h): the bit-row buffers of the last call, grown on demand; what vr_morph_counters and
+// vr_morph_timing report.
+struct MorphState {
+    DevBuf<unsigned long long> words;  // three bit-row buffers: the packed operand and the two a dilation pass writes in turn
+    DevBuf<unsigned> rows;             // the element's rows ...
+    PinnedBuf<unsigned> h_rows;        // ... and where the host sorts them
+    DevBuf<MorphWords> d_words;        // the counts and bounding boxes ...
+    PinnedBuf<MorphWords> h_words;     // ... and where the host sets and reads them
+    Event ev[5];                       // around pack, morphology, write, refresh_bricks
+    unsigned long long counters[3] = {0, 0, 0};
+    float ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+};
+
 // What the reporting calls (vr_last_counters, vr_last_kernel_flavour, vr_last_timing, vr_kernel_times, vr_kernel_choice,
 // vr_download_tiles, vr_last_block_trace) read about the most recent march launch.  vr_pick copies it out and back as one value.
 struct LastLaunch {
@@ -349,6 +362,7 @@ struct vr_ctx {
     const float* d_near = nullptr;
     const float* d_far = nullptr;
     GrowState grow;  // region growing (vr_segment_grow)
+    MorphState morph;  // mask morphology (vr_mask_morph)
     std::string err;
 };
 

@@ -218,6 +218,40 @@ struct GrowSeeds {
     int xyz[64][3];
 };
 
+// The device words of one vr_mask_morph (vr_morph.h): set by the host before the first kernel, read behind the pack and the write.
+struct MorphWords {
+    unsigned long long src_voxels;  // |A'| ...
+    int src_lo[3], src_hi[3];       // ... and its half-open bounding box (lo starts at INT_MAX, hi at 0)
+    unsigned long long voxels;      // |R| ...
+    int lo[3], hi[3];               // ... and its box
+};
+
+// Kernel argument block of a vr_mask_morph (vr_morph.h; vr_morph_desc of include/vr.h): passed by value.
+struct MorphParams {
+    const float4* src;            // the source slot's x-fastest vec4 voxels
+    float4* dst;                  // the destination slot's
+    int src_contour, dst_contour;
+    int nx, ny, nz;               // of both slots
+    int wx;                       // words per row: ceil(nx / 64)
+    int lo[3], hi[3];             // the voxel box, half open
+    int bw0, bw;                  // the words of a row that meet the box: the first and their number ...
+    unsigned long long box_words; // ... and bw * rows * slices of the box (0 for an empty box)
+    unsigned long long* a;        // the packed operand A' (wx * ny * nz words, as every bit-row buffer)
+    const unsigned long long* r;  // the result R
+    const unsigned* rows;         // the element's rows: h | (dy + 32) << 8 | (dz + 32) << 16, sorted by h, largest first
+    int n_rows, hmax;
+    int combine;                  // VR_MORPH_REPLACE ..
+    int fresh;                    // the destination slot was created zeroed by this call: REPLACE stores R alone
+    MorphWords* w;
+};
+// One dilation launch: from src into the words of a region of dst (rw words from word rw0, ry rows from ry0, rz slices from rz0).
+struct MorphPass {
+    const unsigned long long* src;
+    unsigned long long* dst;
+    int rw0, rw, ry0, ry, rz0, rz;
+    unsigned long long words;     // rw * ry * rz
+};
+
 // Work queue of the persistent-wavefront kernel (vr_pw.h): eight heads, one per class of the workgroup index modulo 8,
 // zero at launch; heads[c * 64] counts the items of class c handed out beyond every wavefront's first.
 struct PwQueue {

@@ -66,6 +66,8 @@ def load() -> C.CDLL:
         "vrh_app_start": (i32, [vp, i32, vp, vp, vp, i32]), "vrh_app_set_prepare_on_device": (None, [vp, i32]), "vrh_app_set_iso_value": (i32, [vp, f32]), "vrh_app_set_shadows": (i32, [vp, i32, f32]),
         "vrh_app_pick": (i32, [vp, u32, u32, C.POINTER(capi.PickResult)]),
         "vrh_app_grow_from_pick": (i32, [vp, C.POINTER(capi.PickResult), i32, i32, i32, f32, f32, i32, C.POINTER(capi.GrowResult)]),
+        "vrh_app_morph_contour": (i32, [vp, C.POINTER(capi.MorphDesc), C.POINTER(capi.MorphResult)]),
+        "vrh_app_margin_mm": (i32, [vp, i32, i32, i32, i32, f32, vp, C.POINTER(capi.MorphResult)]),
         "vrh_app_slice": (i32, [vp, C.POINTER(capi.SliceDesc), vp]),
         "vrh_app_slice_through_pick": (C.c_longlong, [vp, C.POINTER(capi.PickResult), i32, i32, vp, C.c_size_t, C.POINTER(u32), C.POINTER(u32)]), "vrh_app_set_surface_threshold": (i32, [vp, f32]), "vrh_app_update": (i32, [vp]), "vrh_app_render": (i32, [vp]),
         "vrh_app_resize": (i32, [vp, u32, u32]), "vrh_app_read_frame": (i32, [vp, vp, vp, C.POINTER(u64)]),
@@ -515,6 +517,19 @@ class Application:
         to pick.voxel -- as contour `contour` of volume mask_slot (include/vr.h vr_segment_grow); a miss is VR_ERR_INVALID_ARG."""
         out = capi.GrowResult()
         self._chk(self.lib.vrh_app_grow_from_pick(self.h, C.byref(pick), value_slot, mask_slot, contour, lo, hi, connectivity, C.byref(out)))
+        return out
+
+    def morph_contour(self, desc: capi.MorphDesc) -> capi.MorphResult:
+        """Application::MorphContour: vr_mask_morph (include/vr.h) on the application's context."""
+        out = capi.MorphResult()
+        self._chk(self.lib.vrh_app_morph_contour(self.h, C.byref(desc), C.byref(out)))
+        return out
+
+    def margin_mm(self, src_slot: int, src_contour: int, dst_slot: int, dst_contour: int, mm: float, grid: "VolumeFile") -> capi.MorphResult:
+        """Application::MarginMm: contour src_contour of volume src_slot grown by `mm` millimetres on the voxel grid of `grid` (a
+        volume read from DICOM: its PixelSpacing and SliceThickness), stored as contour dst_contour of volume dst_slot."""
+        out = capi.MorphResult()
+        self._chk(self.lib.vrh_app_margin_mm(self.h, src_slot, src_contour, dst_slot, dst_contour, mm, grid.h, C.byref(out)))
         return out
 
     def set_surface_threshold(self, tau: float):
