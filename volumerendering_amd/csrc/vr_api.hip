@@ -4,6 +4,7 @@
 // device vr_create fails with VR_ERR_HIP.
 #include "../../include/vr.h"
 #include "vr_launch.h"
+#include "vr_units.h"  // what the three voxel tools below share
 // Histograms (vr_histogram_async): nothing to fuse, so this kernel exists once, here
 #include "vr_hist.h"
 // Region growing (vr_segment_grow): integer work on bit-bricks, compiled once as well
@@ -32,6 +33,7 @@ using namespace vr;
 
 #include "vr_ctx.h"
 #include "vr_api_volume.h"
+#include "vr_api_tools.h"
 #include "vr_api_tf.h"
 #include "vr_api_render.h"
 #include "vr_api_views.h"

@@ -40,16 +40,12 @@ int check_morph(vr_ctx* c, const vr_morph_desc* d)
         if (const char* what = check_element(d->element)) return fail(c, VR_ERR_INVALID_ARG, w + ": " + what);
     const DevVolume& v = c->vols[d->src_slot].vol;
     if (!v.data) return fail(c, VR_ERR_NOT_READY, w + ": source slot " + std::to_string(d->src_slot) + " is empty");
-    const int n[3] = {v.nx, v.ny, v.nz};
-    for (int a = 0; a < 3; ++a)
-        if (d->box_lo[a] < 0 || d->box_lo[a] > d->box_hi[a] || d->box_hi[a] > n[a])
-            return fail(c, VR_ERR_INVALID_ARG, w + ": the box must be 0 <= lo <= hi <= n on every axis");
+    if (const int rc = check_box(c, w, d->box_lo, d->box_hi, v)) return rc;
     const DevVolume& m = c->vols[d->dst_slot].vol;
-    if (m.data && (m.nx != v.nx || m.ny != v.ny || m.nz != v.nz)) return fail(c, VR_ERR_INVALID_ARG, w + ": the destination's dimensions differ from the source's");
-    return VR_OK;
+    return m.data ? check_same_dims(c, w, "destination", m, "source", v) : VR_OK;
 }
 
-// the working buffers of a call over nw words per bit-row buffer, and its events (first use)
+// the working buffers of a call over nw words per bit-row buffer (first use)
 int prepare_morph_state(vr_ctx* c, size_t nw)
 {
     MorphState& M = c->morph;
@@ -59,8 +55,6 @@ int prepare_morph_state(vr_ctx* c, size_t nw)
     if (!M.h_rows) VR_HIP(c, M.h_rows.reserve((size_t)kMorphSide * kMorphSide, true));
     if (!M.d_words) VR_HIP(c, M.d_words.reserve(1));
     if (!M.h_words) VR_HIP(c, M.h_words.reserve(1, true));
-    for (Event& e : M.ev)
-        if (!e) VR_HIP(c, e.create());
     return VR_OK;
 }
 
@@ -133,8 +127,7 @@ int run_morph(vr_ctx* c, const vr_morph_desc& d, float4* dst, bool fresh, vr_mor
     unsigned long long* const C = M.words.p + 2 * nw;
     P.a = A;
     P.w = M.d_words;
-    const int requested = c->flavour == 0 ? c->default_flavour : c->flavour;
-    const bool plain = requested == 1;
+    const bool plain = plain_form(c);
     const bool morph = d.op != VR_MORPH_NONE;
     const int rad[3] = {morph ? d.element.radius[0] : 0, morph ? d.element.radius[1] : 0, morph ? d.element.radius[2] : 0};
     if (morph) {  // the element's rows, sorted by half-chord, largest first (a counting sort over h = rx .. 0)
@@ -149,13 +142,10 @@ int run_morph(vr_ctx* c, const vr_morph_desc& d, float4* dst, bool fresh, vr_mor
         VR_HIP(c, hipMemcpyAsync(M.rows, M.h_rows, (size_t)n * sizeof(unsigned), hipMemcpyHostToDevice, s));
         P.rows = M.rows;
     }
-    const unsigned blocks = P.box_words < 4 ? 1u : (P.box_words / 4 < kMorphBlocks ? (unsigned)(P.box_words / 4) : kMorphBlocks);
+    const unsigned blocks = tool_blocks(P.box_words);
 
-    VR_HIP(c, hipEventRecord(M.ev[0], s));
-    MorphWords init;
-    std::memset(&init, 0, sizeof init);
-    for (int a = 0; a < 3; ++a) init.src_lo[a] = init.lo[a] = 0x7fffffff;
-    *M.h_words.p = init;
+    VR_HIP(c, hipEventRecord(M.report.ev[0], s));
+    *M.h_words.p = MorphWords{CountBox::empty(), CountBox::empty()};
     VR_HIP(c, hipMemcpyAsync(M.d_words, M.h_words, sizeof(MorphWords), hipMemcpyHostToDevice, s));
     VR_HIP(c, hipMemsetAsync(A, 0, nw * sizeof(unsigned long long), s));
     if (P.box_words != 0) {
@@ -165,7 +155,7 @@ int run_morph(vr_ctx* c, const vr_morph_desc& d, float4* dst, bool fresh, vr_mor
     VR_HIP(c, hipMemcpyAsync(M.h_words, M.d_words, sizeof(MorphWords), hipMemcpyDeviceToHost, s));
     VR_HIP(c, hipStreamSynchronize(s));
     const MorphWords packed = *M.h_words.p;
-    VR_HIP(c, hipEventRecord(M.ev[1], s));
+    VR_HIP(c, hipEventRecord(M.report.ev[1], s));
 
     // Where the result of a pass can be set: a dilation's within the bounding box of its source bits grown by the radii, an erosion's
     // within that bounding box itself (the origin is in E), both within the box.  The plain form takes the whole box.
@@ -173,11 +163,11 @@ int run_morph(vr_ctx* c, const vr_morph_desc& d, float4* dst, bool fresh, vr_mor
     for (int a = 0; a < 3; ++a) {
         whole.lo[a] = P.lo[a];
         whole.hi[a] = box == 0 ? P.lo[a] : P.hi[a];
-        bb.lo[a] = packed.src_voxels ? packed.src_lo[a] : 0;
-        bb.hi[a] = packed.src_voxels ? packed.src_hi[a] : 0;
+        bb.lo[a] = packed.src.voxels ? packed.src.lo[a] : 0;
+        bb.hi[a] = packed.src.voxels ? packed.src.hi[a] : 0;
         grown.lo[a] = bb.lo[a] - rad[a] > P.lo[a] ? bb.lo[a] - rad[a] : P.lo[a];
         grown.hi[a] = bb.hi[a] + rad[a] < P.hi[a] ? bb.hi[a] + rad[a] : P.hi[a];
-        if (!packed.src_voxels) grown.hi[a] = grown.lo[a] = P.lo[a];
+        if (!packed.src.voxels) grown.hi[a] = grown.lo[a] = P.lo[a];
     }
     if (plain) bb = grown = whole;
     unsigned long long computed = 0;
@@ -204,27 +194,23 @@ int run_morph(vr_ctx* c, const vr_morph_desc& d, float4* dst, bool fresh, vr_mor
     default: break;
     }
     P.r = R;
-    VR_HIP(c, hipEventRecord(M.ev[2], s));
+    VR_HIP(c, hipEventRecord(M.report.ev[2], s));
 
     if (P.box_words != 0) {
         hipLaunchKernelGGL(morph_write_kernel, dim3(blocks), dim3(256), 0, s, P);
         VR_HIP(c, hipGetLastError());
     }
     VR_HIP(c, hipMemcpyAsync(M.h_words, M.d_words, sizeof(MorphWords), hipMemcpyDeviceToHost, s));
-    VR_HIP(c, hipEventRecord(M.ev[3], s));
+    VR_HIP(c, hipEventRecord(M.report.ev[3], s));
     VR_HIP(c, hipStreamSynchronize(s));
     const MorphWords& w = *M.h_words.p;
-    M.counters[0] = box;
-    M.counters[1] = computed;
-    M.counters[2] = box - computed;
+    M.report.counters[0] = box;
+    M.report.counters[1] = computed;
+    M.report.counters[2] = box - computed;
     if (result) {
         std::memset(result, 0, sizeof *result);
-        result->voxels = w.voxels;
-        result->src_voxels = w.src_voxels;
-        for (int a = 0; a < 3 && w.voxels != 0; ++a) {
-            result->lo[a] = w.lo[a];
-            result->hi[a] = w.hi[a];
-        }
+        copy_count_box(w.result, result);
+        result->src_voxels = w.src.voxels;
     }
     return VR_OK;
 }
@@ -292,9 +278,7 @@ int vr_morph_whole(const vr_ctx* c, int src_slot, int src_contour, int dst_slot,
     out->dst_contour = dst_contour;
     out->op = op;
     out->combine = VR_MORPH_REPLACE;
-    out->box_hi[0] = c->vols[src_slot].vol.nx;
-    out->box_hi[1] = c->vols[src_slot].vol.ny;
-    out->box_hi[2] = c->vols[src_slot].vol.nz;
+    whole_box(c->vols[src_slot].vol, out->box_hi);
     const uint32_t unit[3] = {1, 1, 1};
     return vr_morph_ball(unit, 1, &out->element);
 }
@@ -303,55 +287,12 @@ int vr_mask_morph(vr_ctx* c, const vr_morph_desc* desc, vr_morph_result* result)
 {
     if (!c) return VR_ERR_INVALID_ARG;
     if (const int rc = check_morph(c, desc)) return rc;
-    if (const int rc = drain(c)) return rc;  // asynchronous renders on the caller's streams may still read the destination slot
-    (void)hipGetLastError();
-    const int ds = desc->dst_slot;
-    VolumeSlot& D = c->vols[ds];
-    const DevVolume& v = c->vols[desc->src_slot].vol;
-    const uint16_t nx = (uint16_t)v.nx, ny = (uint16_t)v.ny, nz = (uint16_t)v.nz;
-    const bool fresh = !D.vol.data;
-    if (fresh) {  // an empty destination slot: the source's dimensions, every component +0.0f
-        const size_t n = (size_t)nx * ny * nz;
-        float4* dst;
-        if (D.voxels && D.voxels.cap != n) D.voxels.release();
-        if (const int rc = voxels_for_upload(c, ds, n, &dst)) return rc;
-        const hipError_t e = hipMemsetAsync(dst, 0, n * sizeof(float4), c->stream);
-        if (e != hipSuccess) {
-            D.voxels.release();
-            return fail(c, VR_ERR_HIP, std::string("vr_mask_morph: hipMemsetAsync failed: ") + hipGetErrorString(e));
-        }
-    }
-    for (float& t : c->morph.ms) t = 0.0f;
-    int rc = run_morph(c, *desc, D.voxels, fresh, result);
-    if (rc != VR_OK) {
-        (void)hipStreamSynchronize(c->stream);
-        if (fresh) D.voxels.release();  // (the slot stays empty)
-        return rc;
-    }
-    rc = fresh ? bind_voxels(c, ds, nx, ny, nz) : refresh_bricks(c, ds);
-    if (rc != VR_OK) return rc;
-    MorphState& M = c->morph;
-    VR_HIP(c, hipEventRecord(M.ev[4], c->stream));
-    VR_HIP(c, hipEventSynchronize(M.ev[4]));
-    for (int i = 0; i < 4; ++i)
-        if (hipEventElapsedTime(&M.ms[i], M.ev[i], M.ev[i + 1]) != hipSuccess) M.ms[i] = 0.0f;
-    return VR_OK;
+    return mask_tool_call(c, "vr_mask_morph", desc->src_slot, desc->dst_slot, c->morph.report,
+                          [&](float4* dst, bool fresh) { return run_morph(c, *desc, dst, fresh, result); });
 }
 
-int vr_morph_counters(vr_ctx* c, uint64_t out[3])
-{
-    if (!c) return VR_ERR_INVALID_ARG;
-    if (!out) return fail(c, VR_ERR_INVALID_ARG, "vr_morph_counters: out is NULL");
-    for (int i = 0; i < 3; ++i) out[i] = c->morph.counters[i];
-    return VR_OK;
-}
+int vr_morph_counters(vr_ctx* c, uint64_t out[3]) { return tool_counters(c, &vr_ctx::morph, out, "vr_morph_counters"); }
 
-int vr_morph_timing(vr_ctx* c, float ms[4])
-{
-    if (!c) return VR_ERR_INVALID_ARG;
-    if (!ms) return fail(c, VR_ERR_INVALID_ARG, "vr_morph_timing: ms is NULL");
-    for (int i = 0; i < 4; ++i) ms[i] = c->morph.ms[i];
-    return VR_OK;
-}
+int vr_morph_timing(vr_ctx* c, float ms[4]) { return tool_timing(c, &vr_ctx::morph, ms, "vr_morph_timing"); }
 
 }  // extern "C"

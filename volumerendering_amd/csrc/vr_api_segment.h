@@ -20,19 +20,16 @@ int check_grow(vr_ctx* c, const vr_grow_desc* d)
     if (d->n_seeds < 1 || d->n_seeds > VR_GROW_MAX_SEEDS) return fail(c, VR_ERR_INVALID_ARG, w + ": n_seeds must be 1 .. 64");
     const DevVolume& v = c->vols[d->volume_slot].vol;
     if (!v.data) return fail(c, VR_ERR_NOT_READY, w + ": volume slot " + std::to_string(d->volume_slot) + " is empty");
+    if (const int rc = check_box(c, w, d->box_lo, d->box_hi, v)) return rc;
     const int n[3] = {v.nx, v.ny, v.nz};
-    for (int a = 0; a < 3; ++a)
-        if (d->box_lo[a] < 0 || d->box_lo[a] > d->box_hi[a] || d->box_hi[a] > n[a])
-            return fail(c, VR_ERR_INVALID_ARG, w + ": the box must be 0 <= lo <= hi <= n on every axis");
     for (uint32_t i = 0; i < d->n_seeds; ++i)
         for (int a = 0; a < 3; ++a)
             if (d->seeds[i][a] < 0 || d->seeds[i][a] >= n[a]) return fail(c, VR_ERR_INVALID_ARG, w + ": seed " + std::to_string(i) + " lies outside the volume");
     const DevVolume& m = c->vols[d->mask_slot].vol;
-    if (m.data && (m.nx != v.nx || m.ny != v.ny || m.nz != v.nz)) return fail(c, VR_ERR_INVALID_ARG, w + ": the mask's dimensions differ from the volume's");
-    return VR_OK;
+    return m.data ? check_same_dims(c, w, "mask", m, "volume", v) : VR_OK;
 }
 
-// the working buffers of a grow over nb bricks, and its events (first use)
+// the working buffers of a grow over nb bricks (first use)
 int prepare_grow_state(vr_ctx* c, size_t nb)
 {
     GrowState& G = c->grow;
@@ -41,8 +38,6 @@ int prepare_grow_state(vr_ctx* c, size_t nb)
     if (const int rc = grow(c, G.lists, 3 * nb, true)) return rc;
     if (!G.d_words) VR_HIP(c, G.d_words.reserve(1));
     if (!G.h_words) VR_HIP(c, G.h_words.reserve(1, true));
-    for (Event& e : G.ev)
-        if (!e) VR_HIP(c, e.create());
     return VR_OK;
 }
 
@@ -61,17 +56,8 @@ int run_grow(vr_ctx* c, const vr_grow_desc& d, float4* mask, bool fresh, vr_grow
     P.nx = v.nx;
     P.ny = v.ny;
     P.nz = v.nz;
-    unsigned long long units = 1, box = 1;
-    for (int a = 0; a < 3; ++a) {
-        P.lo[a] = d.box_lo[a];
-        P.hi[a] = d.box_hi[a];
-        P.u0[a] = d.box_lo[a] >> 2;
-        P.un[a] = d.box_hi[a] > d.box_lo[a] ? ((d.box_hi[a] + 3) >> 2) - P.u0[a] : 0;
-        units *= (unsigned long long)P.un[a];
-        box *= (unsigned long long)(d.box_hi[a] - d.box_lo[a]);
-    }
-    if (box == 0) units = 0;
-    P.units = (unsigned)units;  // (at most the volume's bricks, below 2^26)
+    unsigned long long box;
+    P.box = box_units(d.box_lo, d.box_hi, &box);  // (units: at most the volume's bricks, below 2^26)
     P.vlo = d.lo;
     P.vhi = d.hi;
     P.bnx = skip_bricks(v.nx);
@@ -80,8 +66,7 @@ int run_grow(vr_ctx* c, const vr_grow_desc& d, float4* mask, bool fresh, vr_grow
     const size_t nb = (size_t)P.bnx * P.bny * P.bnz;
     P.n_bricks = (unsigned)nb;
     P.all = d.connectivity == VR_GROW_ALL;
-    const int requested = c->flavour == 0 ? c->default_flavour : c->flavour;
-    const bool plain = requested == 1;
+    const bool plain = plain_form(c);
     if (const int rc = prepare_grow_state(c, nb)) return rc;
     P.q = G.words;
     P.r = G.words.p + nb;
@@ -97,18 +82,15 @@ int run_grow(vr_ctx* c, const vr_grow_desc& d, float4* mask, bool fresh, vr_grow
     S.n = d.n_seeds;
     std::memcpy(S.xyz, d.seeds, sizeof(int32_t) * 3 * d.n_seeds);
 
-    VR_HIP(c, hipEventRecord(G.ev[0], s));
+    VR_HIP(c, hipEventRecord(G.report.ev[0], s));
     // exact settling by the slot's range records (of .a: channel 3)
-    if (!plain && d.channel == 3 && units != 0 && !prepare_range(c, s, vs, P.bnx, P.bny, P.bnz, &P.bricks)) return VR_ERR_HIP;
-    GrowWords init;
-    std::memset(&init, 0, sizeof init);
-    init.lo[0] = init.lo[1] = init.lo[2] = 0x7fffffff;
-    *G.h_words.p = init;
+    if (!plain && d.channel == 3 && P.box.units != 0 && !prepare_range(c, s, vs, P.bnx, P.bny, P.bnz, &P.bricks)) return VR_ERR_HIP;
+    *G.h_words.p = GrowWords{{0, 0, 0}, CountBox::empty(), {0, 0, 0}, 0};
     VR_HIP(c, hipMemcpyAsync(G.d_words, G.h_words, sizeof(GrowWords), hipMemcpyHostToDevice, s));
     VR_HIP(c, hipMemsetAsync(G.words, 0, 2 * nb * sizeof(unsigned long long), s));
     VR_HIP(c, hipMemsetAsync(G.lists, 0, nb * sizeof(unsigned), s));  // (the stamps; the lists are written before they are read)
-    if (units != 0) {
-        const unsigned blocks = units < 4 ? 1u : (units / 4 < kGrowBlocks ? (unsigned)(units / 4) : kGrowBlocks);
+    if (P.box.units != 0) {
+        const unsigned blocks = tool_blocks(P.box.units);
         if (plain) hipLaunchKernelGGL(grow_classify_kernel<true>, dim3(blocks), dim3(256), 0, s, P);
         else hipLaunchKernelGGL(grow_classify_kernel<false>, dim3(blocks), dim3(256), 0, s, P);
         VR_HIP(c, hipGetLastError());
@@ -116,11 +98,11 @@ int run_grow(vr_ctx* c, const vr_grow_desc& d, float4* mask, bool fresh, vr_grow
     if (plain) hipLaunchKernelGGL(grow_seed_kernel<true>, dim3(1), dim3(64), 0, s, P, S);
     else hipLaunchKernelGGL(grow_seed_kernel<false>, dim3(1), dim3(64), 0, s, P, S);
     VR_HIP(c, hipGetLastError());
-    VR_HIP(c, hipEventRecord(G.ev[1], s));
+    VR_HIP(c, hipEventRecord(G.report.ev[1], s));
 
     // Rounds in batches of VR_GROW_BATCH, the words read behind each batch: done when the next round's input word is zero.  R grows
     // strictly in every round but the first and the last that have anything to do, so voxels + 1 rounds bound them all.
-    const unsigned blocks = nb < 4 ? 1u : (nb / 4 < kGrowBlocks ? (unsigned)(nb / 4) : kGrowBlocks);
+    const unsigned blocks = tool_blocks(nb);
     const unsigned long long limit = box + 1 < 0xFFFFFFF0ull ? box + 1 : 0xFFFFFFF0ull;
     unsigned long long k = 0;
     for (;;) {
@@ -135,22 +117,18 @@ int run_grow(vr_ctx* c, const vr_grow_desc& d, float4* mask, bool fresh, vr_grow
         VR_HIP(c, hipStreamSynchronize(s));
         if (G.h_words.p->cnt[(k + 1) % 3] == 0) break;
     }
-    VR_HIP(c, hipEventRecord(G.ev[2], s));
+    VR_HIP(c, hipEventRecord(G.report.ev[2], s));
 
     hipLaunchKernelGGL(grow_write_kernel, dim3(blocks), dim3(256), 0, s, P);
     VR_HIP(c, hipGetLastError());
     VR_HIP(c, hipMemcpyAsync(G.h_words, G.d_words, sizeof(GrowWords), hipMemcpyDeviceToHost, s));
-    VR_HIP(c, hipEventRecord(G.ev[3], s));
+    VR_HIP(c, hipEventRecord(G.report.ev[3], s));
     VR_HIP(c, hipStreamSynchronize(s));
     const GrowWords& w = *G.h_words.p;
-    for (int i = 0; i < 3; ++i) G.counters[i] = w.stats[i];
+    for (int i = 0; i < 3; ++i) G.report.counters[i] = w.stats[i];
     if (result) {
         std::memset(result, 0, sizeof *result);
-        result->voxels = w.voxels;
-        for (int a = 0; a < 3 && w.voxels != 0; ++a) {
-            result->lo[a] = w.lo[a];
-            result->hi[a] = w.hi[a];
-        }
+        copy_count_box(w.reached, result);
         result->rounds = w.rounds > 0 ? w.rounds : 1u;
     }
     return VR_OK;
@@ -176,9 +154,7 @@ int vr_grow_whole(const vr_ctx* c, int volume_slot, int mask_slot, int contour, 
     out->hi = hi;
     out->connectivity = VR_GROW_FACES;
     out->mode = VR_GROW_REPLACE;
-    out->box_hi[0] = c->vols[volume_slot].vol.nx;
-    out->box_hi[1] = c->vols[volume_slot].vol.ny;
-    out->box_hi[2] = c->vols[volume_slot].vol.nz;
+    whole_box(c->vols[volume_slot].vol, out->box_hi);
     return VR_OK;
 }
 
@@ -186,55 +162,12 @@ int vr_segment_grow(vr_ctx* c, const vr_grow_desc* desc, vr_grow_result* result)
 {
     if (!c) return VR_ERR_INVALID_ARG;
     if (const int rc = check_grow(c, desc)) return rc;
-    if (const int rc = drain(c)) return rc;  // asynchronous renders on the caller's streams may still read the mask slot
-    (void)hipGetLastError();
-    const int ms = desc->mask_slot;
-    VolumeSlot& M = c->vols[ms];
-    const DevVolume& v = c->vols[desc->volume_slot].vol;
-    const uint16_t nx = (uint16_t)v.nx, ny = (uint16_t)v.ny, nz = (uint16_t)v.nz;
-    const bool fresh = !M.vol.data;
-    if (fresh) {  // an empty mask slot: the value volume's dimensions, every component +0.0f
-        const size_t n = (size_t)nx * ny * nz;
-        float4* dst;
-        if (M.voxels && M.voxels.cap != n) M.voxels.release();
-        if (const int rc = voxels_for_upload(c, ms, n, &dst)) return rc;
-        const hipError_t e = hipMemsetAsync(dst, 0, n * sizeof(float4), c->stream);
-        if (e != hipSuccess) {
-            M.voxels.release();
-            return fail(c, VR_ERR_HIP, std::string("vr_segment_grow: hipMemsetAsync failed: ") + hipGetErrorString(e));
-        }
-    }
-    for (float& t : c->grow.ms) t = 0.0f;
-    int rc = run_grow(c, *desc, M.voxels, fresh, result);
-    if (rc != VR_OK) {
-        (void)hipStreamSynchronize(c->stream);
-        if (fresh) M.voxels.release();  // (the slot stays empty)
-        return rc;
-    }
-    rc = fresh ? bind_voxels(c, ms, nx, ny, nz) : refresh_bricks(c, ms);
-    if (rc != VR_OK) return rc;
-    GrowState& G = c->grow;
-    VR_HIP(c, hipEventRecord(G.ev[4], c->stream));
-    VR_HIP(c, hipEventSynchronize(G.ev[4]));
-    for (int i = 0; i < 4; ++i)
-        if (hipEventElapsedTime(&G.ms[i], G.ev[i], G.ev[i + 1]) != hipSuccess) G.ms[i] = 0.0f;
-    return VR_OK;
+    return mask_tool_call(c, "vr_segment_grow", desc->volume_slot, desc->mask_slot, c->grow.report,
+                          [&](float4* mask, bool fresh) { return run_grow(c, *desc, mask, fresh, result); });
 }
 
-int vr_grow_counters(vr_ctx* c, uint64_t out[3])
-{
-    if (!c) return VR_ERR_INVALID_ARG;
-    if (!out) return fail(c, VR_ERR_INVALID_ARG, "vr_grow_counters: out is NULL");
-    for (int i = 0; i < 3; ++i) out[i] = c->grow.counters[i];
-    return VR_OK;
-}
+int vr_grow_counters(vr_ctx* c, uint64_t out[3]) { return tool_counters(c, &vr_ctx::grow, out, "vr_grow_counters"); }
 
-int vr_grow_timing(vr_ctx* c, float ms[4])
-{
-    if (!c) return VR_ERR_INVALID_ARG;
-    if (!ms) return fail(c, VR_ERR_INVALID_ARG, "vr_grow_timing: ms is NULL");
-    for (int i = 0; i < 4; ++i) ms[i] = c->grow.ms[i];
-    return VR_OK;
-}
+int vr_grow_timing(vr_ctx* c, float ms[4]) { return tool_timing(c, &vr_ctx::grow, ms, "vr_grow_timing"); }
 
 }  // extern "C"

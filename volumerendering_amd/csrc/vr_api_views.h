@@ -154,8 +154,7 @@ int enqueue_slice(vr_ctx* c, const vr_slice_desc& d, void* d_out, hipStream_t s)
     S.bsx = (float)v.nx * kBrickInv;
     S.bsy = (float)v.ny * kBrickInv;
     S.bsz = (float)v.nz * kBrickInv;
-    const int requested = c->flavour == 0 ? c->default_flavour : c->flavour;
-    const bool skip = requested != 1 && bricks_indexable(S.bnx, S.bny, S.bnz);
+    const bool skip = !plain_form(c) && bricks_indexable(S.bnx, S.bny, S.bnz);
     if (skip) {
         S.vrange = prepare_range(c, s, vs, S.bnx, S.bny, S.bnz, &S.bricks);
         if (!S.vrange) return VR_ERR_HIP;
@@ -191,13 +190,11 @@ int check_hist(vr_ctx* c, const vr_hist_desc* d, const void* counts, const void*
     if ((d->rows & ~1u) != 0 && d->mask_slot < 0) return fail(c, VR_ERR_INVALID_ARG, w + ": contour rows need a mask slot");
     const DevVolume& v = c->vols[d->volume_slot].vol;
     if (!v.data) return fail(c, VR_ERR_NOT_READY, w + ": volume slot " + std::to_string(d->volume_slot) + " is empty");
-    const int n[3] = {v.nx, v.ny, v.nz};
-    for (int a = 0; a < 3; ++a)
-        if (d->lo[a] < 0 || d->lo[a] > d->hi[a] || d->hi[a] > n[a]) return fail(c, VR_ERR_INVALID_ARG, w + ": the box must be 0 <= lo <= hi <= n on every axis");
+    if (const int rc = check_box(c, w, d->lo, d->hi, v)) return rc;
     if (d->mask_slot >= 0) {
         const DevVolume& m = c->vols[d->mask_slot].vol;
         if (!m.data) return fail(c, VR_ERR_NOT_READY, w + ": mask slot " + std::to_string(d->mask_slot) + " is empty");
-        if (m.nx != v.nx || m.ny != v.ny || m.nz != v.nz) return fail(c, VR_ERR_INVALID_ARG, w + ": the mask's dimensions differ from the volume's");
+        return check_same_dims(c, w, "mask", m, "volume", v);
     }
     return VR_OK;
 }
@@ -219,33 +216,23 @@ int enqueue_hist(vr_ctx* c, const vr_hist_desc& d, void* d_counts, void* d_rows,
     H.nx = v.nx;
     H.ny = v.ny;
     H.nz = v.nz;
-    unsigned long long units = 1, box = 1;
-    for (int a = 0; a < 3; ++a) {
-        H.lo[a] = d.lo[a];
-        H.hi[a] = d.hi[a];
-        H.u0[a] = d.lo[a] >> 2;
-        H.un[a] = d.hi[a] > d.lo[a] ? ((d.hi[a] + 3) >> 2) - H.u0[a] : 0;
-        units *= (unsigned long long)H.un[a];
-        box *= (unsigned long long)(d.hi[a] - d.lo[a]);
-    }
-    if (box == 0) units = 0;
-    if (units > 0xFFFFFFFFull) return fail(c, VR_ERR_UNSUPPORTED, "vr_histogram: the box has 2^32 brick units or more");
-    H.units = (unsigned)units;
+    unsigned long long box;
+    H.box = box_units(d.lo, d.hi, &box);
+    if ((unsigned long long)H.box.un[0] * H.box.un[1] * H.box.un[2] > 0xFFFFFFFFull) return fail(c, VR_ERR_UNSUPPORTED, "vr_histogram: the box has 2^32 brick units or more");
     H.rows = d.rows;
     H.bins = d.bins;
     H.scale = d.scale;
     H.drop = d.out_of_range == VR_HIST_DROP;
     unsigned n_rows = 0;
     for (int r = 0; r < VR_HIST_ROWS; ++r) n_rows += (d.rows >> r) & 1u;
-    const unsigned blocks = units < 4 ? 1u : (units / 4 < kHistBlocks ? (unsigned)(units / 4) : kHistBlocks);
+    const unsigned blocks = tool_blocks(H.box.units);
     // the private LDS copy: within the budget, and a workgroup's share of the voxels (its four wavefronts' units) below 2^32 so that
     // no u32 count can wrap; otherwise the kernel adds into the u64 outputs directly
-    const unsigned long long per_block = (units + blocks * 4ull - 1) / (blocks * 4ull) * 4ull * 64ull;
+    const unsigned long long per_block = (H.box.units + blocks * 4ull - 1) / (blocks * 4ull) * 4ull * 64ull;
     H.lds = (size_t)n_rows * d.bins * sizeof(unsigned) <= kHistLdsBytes && per_block < (1ull << 32);
-    const int requested = c->flavour == 0 ? c->default_flavour : c->flavour;
-    const bool plain = requested == 1;
+    const bool plain = plain_form(c);
     // exact settling by the slot's range records (of .a: channel 3), for the unmasked launch
-    if (!plain && d.channel == 3 && d.mask_slot < 0 && units != 0) {
+    if (!plain && d.channel == 3 && d.mask_slot < 0 && H.box.units != 0) {
         H.bnx = skip_bricks(v.nx);
         H.bny = skip_bricks(v.ny);
         if (!prepare_range(c, s, vs, H.bnx, H.bny, skip_bricks(v.nz), &H.bricks)) return VR_ERR_HIP;
@@ -585,9 +572,7 @@ int vr_hist_whole(const vr_ctx* c, int slot, uint32_t bins, float scale, vr_hist
     out->bins = bins;
     out->scale = scale;
     out->out_of_range = VR_HIST_CLAMP;
-    out->hi[0] = c->vols[slot].vol.nx;
-    out->hi[1] = c->vols[slot].vol.ny;
-    out->hi[2] = c->vols[slot].vol.nz;
+    whole_box(c->vols[slot].vol, out->hi);
     return VR_OK;
 }
 

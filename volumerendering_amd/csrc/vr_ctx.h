@@ -149,6 +149,13 @@ struct VolumeSlot {
     BuiltOn proj_built;
 };
 
+// A mask tool's report on its last call: three counters, and its three phases and refresh_bricks timed between five events (vr_api_tools.h).
+struct ToolReport {
+    Event ev[5];
+    unsigned long long counters[3] = {0, 0, 0};
+    float ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+};
+
 // Region growing (vr_segment_grow, vr_grow.h): the working buffers of the last grow, grown on demand; what vr_grow_counters and
 // vr_grow_timing report.
 struct GrowState {
@@ -156,9 +163,7 @@ struct GrowState {
     DevBuf<unsigned> lists;            // per brick: the round stamp, then the frontier's two lists
     DevBuf<GrowWords> d_words;         // counters, result and the rounds' words ...
     PinnedBuf<GrowWords> h_words;      // ... and where the host sets and reads them
-    Event ev[5];                       // around classify + seed, propagate, write, refresh_bricks
-    unsigned long long counters[3] = {0, 0, 0};
-    float ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    ToolReport report;                 // phases: classify + seed, propagate, write, refresh_bricks
 };
 
 // Mask morphology (vr_mask_morph, vr_morph.h): the bit-row buffers of the last call, grown on demand; what vr_morph_counters and
@@ -169,9 +174,7 @@ struct MorphState {
     PinnedBuf<unsigned> h_rows;        // ... and where the host sorts them
     DevBuf<MorphWords> d_words;        // the counts and bounding boxes ...
     PinnedBuf<MorphWords> h_words;     // ... and where the host sets and reads them
-    Event ev[5];                       // around pack, morphology, write, refresh_bricks
-    unsigned long long counters[3] = {0, 0, 0};
-    float ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    ToolReport report;                 // phases: pack, morphology, write, refresh_bricks
 };
 
 // What the reporting calls (vr_last_counters, vr_last_kernel_flavour, vr_last_timing, vr_kernel_times, vr_kernel_choice,

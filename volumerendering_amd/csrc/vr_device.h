@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "vr_units.h"
 
 namespace vr {
 
@@ -165,9 +166,7 @@ struct HistParams {
     int val_stride;          // or the density plane (stride 1: channel 3 of an unmasked launch, when the layout has one)
     const float4* mask;      // the mask slot's x-fastest vec4 voxels; nullptr = no mask
     int nx, ny, nz;          // of the value volume (and of the mask)
-    int lo[3], hi[3];        // the voxel box, half open
-    int u0[3], un[3];        // the 4 x 4 x 4 brick units that meet the box: first unit and units per axis ...
-    unsigned units;          // ... and their number
+    BoxUnits box;            // the voxel box and the 4 x 4 x 4 brick units that meet it (vr_units.h)
     unsigned rows;           // bit r: row r is computed
     unsigned bins;
     float scale;
@@ -183,8 +182,7 @@ struct HistParams {
 // The device words of one region grow (vr_grow.h): what the host sets before the first kernel and reads behind a batch of rounds.
 struct GrowWords {
     unsigned long long stats[3];  // voxels of the box, voxels loaded, voxels classified from a range record
-    unsigned long long voxels;    // |R| ...
-    int lo[3], hi[3];             // ... and its half-open bounding box (lo starts at INT_MAX, hi at 0)
+    CountBox reached;             // |R| and its bounding box (starts as CountBox::empty())
     unsigned cnt[3];              // round k reads cnt[k % 3] (frontier: the length of its list; sweep: the round before it changed
                                   // something), adds to cnt[(k + 1) % 3] and zeroes cnt[(k + 2) % 3]
     unsigned rounds;              // the last round that had something to do
@@ -195,9 +193,7 @@ struct GrowParams {
     const float* val;        // the value of voxel idx is val[idx * val_stride]: as HistParams
     int val_stride;
     int nx, ny, nz;          // of the value volume (and of the mask)
-    int lo[3], hi[3];        // the voxel box, half open
-    int u0[3], un[3];        // the 4 x 4 x 4 brick units that meet the box: first unit and units per axis ...
-    unsigned units;          // ... and their number
+    BoxUnits box;            // the voxel box and the brick units that meet it
     float vlo, vhi;          // a voxel qualifies iff v >= vlo && v <= vhi
     const float2* bricks;    // exact settling: the slot's range records (vr_proj.h); nullptr = off
     int bnx, bny, bnz;       // the volume's brick grid: brick (bx, by, bz) has index (bz * bny + by) * bnx + bx
@@ -220,10 +216,8 @@ struct GrowSeeds {
 
 // The device words of one vr_mask_morph (vr_morph.h): set by the host before the first kernel, read behind the pack and the write.
 struct MorphWords {
-    unsigned long long src_voxels;  // |A'| ...
-    int src_lo[3], src_hi[3];       // ... and its half-open bounding box (lo starts at INT_MAX, hi at 0)
-    unsigned long long voxels;      // |R| ...
-    int lo[3], hi[3];               // ... and its box
+    CountBox src;     // |A'| and its bounding box (both start as CountBox::empty())
+    CountBox result;  // |R| and its
 };
 
 // Kernel argument block of a vr_mask_morph (vr_morph.h; vr_morph_desc of include/vr.h): passed by value.

@@ -6,7 +6,7 @@
 // box) and R (the voxel is reached), bit x + 4 y + 16 z: 16 B per 64 voxels, 32 MiB for a 512^3 volume beside its 2 GiB of voxels.  Bits
 // of voxels outside the volume or the box are never set in Q, and R is a subset of Q throughout: adjacency cannot leave the box.
 //
-// Classify (grow_classify_kernel): the launch shape of hist_kernel -- persistent workgroups of four wavefronts, one wavefront per brick
+// Classify (grow_classify_kernel): the walk of vr_units.h -- persistent workgroups of four wavefronts, one wavefront per brick
 // unit that meets the box, one lane per voxel -- and Q is one 64-bit ballot of in_box && v >= lo && v <= hi.  Exact settling (channel
 // 3, a unit wholly inside the box, a range record (min .a, max .a) of brick_range_kernel that is not the flagged (NaN, NaN) one):
 //     max < lo || min > hi    ->  Q = 0         min >= lo && max <= hi  ->  Q = all ones
@@ -39,8 +39,6 @@
 #pragma once
 
 namespace vr {
-
-constexpr unsigned kGrowBlocks = 512;  // persistent workgroups of four wavefronts (as kHistBlocks)
 
 constexpr unsigned long long kGrowX0 = 0x1111111111111111ull, kGrowX3 = 0x8888888888888888ull;  // the x = 0 / x = 3 columns
 constexpr unsigned long long kGrowY0 = 0x000F000F000F000Full, kGrowY3 = 0xF000F000F000F000ull;  // the y = 0 / y = 3 rows
@@ -88,14 +86,12 @@ __global__ __launch_bounds__(256) void grow_classify_kernel(const GrowParams P)
     const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lx = (int)(lane & 3u), ly = (int)((lane >> 2) & 3u), lz = (int)(lane >> 4);
     unsigned long long n_box = 0, n_load = 0, n_settled = 0;  // per lane
-    const unsigned W = gridDim.x * 4u, uxy = (unsigned)P.un[0] * (unsigned)P.un[1];
-    for (unsigned u = blockIdx.x * 4u + wave; u < P.units; u += W) {
-        const unsigned uz = u / uxy, ur = u - uz * uxy, uy = ur / (unsigned)P.un[0], ux = ur - uy * (unsigned)P.un[0];
-        const int bx = P.u0[0] + (int)ux, by = P.u0[1] + (int)uy, bz = P.u0[2] + (int)uz;
-        const int x0 = bx << 2, y0 = by << 2, z0 = bz << 2;
-        const size_t b = ((size_t)bz * (size_t)P.bny + (size_t)by) * (size_t)P.bnx + (size_t)bx;  // (< n_bricks: the unit meets the volume)
+    const unsigned W = gridDim.x * 4u, uxy = (unsigned)P.box.un[0] * (unsigned)P.box.un[1];
+    for (unsigned u = blockIdx.x * 4u + wave; u < P.box.units; u += W) {
+        const BrickUnit U = brick_unit(P.box, u, uxy);
+        const size_t b = ((size_t)U.bz * (size_t)P.bny + (size_t)U.by) * (size_t)P.bnx + (size_t)U.bx;  // (< n_bricks: the unit meets the volume)
         if constexpr (!PLAIN) {
-            const bool whole = x0 >= P.lo[0] && x0 + 4 <= P.hi[0] && y0 >= P.lo[1] && y0 + 4 <= P.hi[1] && z0 >= P.lo[2] && z0 + 4 <= P.hi[2];
+            const bool whole = whole_unit<BoxUnits>(P.box, U);
             if (P.bricks && whole) {
                 const float2 rec = P.bricks[b];
                 const bool none = rec.y < P.vlo || rec.x > P.vhi, every = rec.x >= P.vlo && rec.y <= P.vhi;  // (the flagged record fails both)
@@ -109,8 +105,8 @@ __global__ __launch_bounds__(256) void grow_classify_kernel(const GrowParams P)
                 }
             }
         }
-        const int x = x0 + lx, y = y0 + ly, z = z0 + lz;
-        const bool in = x >= P.lo[0] && x < P.hi[0] && y >= P.lo[1] && y < P.hi[1] && z >= P.lo[2] && z < P.hi[2];  // (hi <= n)
+        const int x = U.x0 + lx, y = U.y0 + ly, z = U.z0 + lz;
+        const bool in = in_box(P.box, x, y, z);  // (hi <= n)
         bool ok = false;
         if (in) {
             const size_t idx = ((size_t)z * (size_t)P.ny + (size_t)y) * (size_t)P.nx + (size_t)x;
@@ -122,9 +118,9 @@ __global__ __launch_bounds__(256) void grow_classify_kernel(const GrowParams P)
         n_box += in ? 1u : 0u;
         n_load += in ? 1u : 0u;
     }
-    n_box = hist_wave_sum(n_box);
-    n_load = hist_wave_sum(n_load);
-    n_settled = hist_wave_sum(n_settled);
+    n_box = wave_sum_u64(n_box);
+    n_load = wave_sum_u64(n_load);
+    n_settled = wave_sum_u64(n_settled);
     if (lane == 0u) {
         if (n_box != 0ull) atomicAdd(&P.w->stats[0], n_box);
         if (n_load != 0ull) atomicAdd(&P.w->stats[1], n_load);
@@ -140,7 +136,7 @@ __global__ __launch_bounds__(64) void grow_seed_kernel(const GrowParams P, const
     const unsigned i = threadIdx.x;
     if (i >= S.n) return;
     const int x = S.xyz[i][0], y = S.xyz[i][1], z = S.xyz[i][2];
-    if (x < P.lo[0] || x >= P.hi[0] || y < P.lo[1] || y >= P.hi[1] || z < P.lo[2] || z >= P.hi[2]) return;
+    if (!in_box(P.box, x, y, z)) return;
     const unsigned b = ((unsigned)(z >> 2) * (unsigned)P.bny + (unsigned)(y >> 2)) * (unsigned)P.bnx + (unsigned)(x >> 2);
     const unsigned long long bit = 1ull << ((x & 3) + 4 * (y & 3) + 16 * (z & 3));
     if (b >= P.n_bricks || !(P.q[b] & bit)) return;
@@ -231,8 +227,7 @@ __global__ __launch_bounds__(256) void grow_write_kernel(const GrowParams P)
     const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lx = (int)(lane & 3u), ly = (int)((lane >> 2) & 3u), lz = (int)(lane >> 4);
     float* const out = reinterpret_cast<float*>(P.mask) + P.contour;
-    unsigned long long voxels = 0;  // (wave-uniform)
-    int lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {0, 0, 0};
+    CountBox n = CountBox::empty();  // (wave-uniform)
     const unsigned W = gridDim.x * 4u, bxy = (unsigned)P.bnx * (unsigned)P.bny;
     for (unsigned b = blockIdx.x * 4u + wave; b < P.n_bricks; b += W) {
         const unsigned long long rw = P.r[b];
@@ -245,23 +240,17 @@ __global__ __launch_bounds__(256) void grow_write_kernel(const GrowParams P)
             out[idx * 4u] = set ? 1.0f : 0.0f;
         }
         if (rw != 0ull) {
-            voxels += (unsigned long long)__popcll(rw);
+            n.voxels += (unsigned long long)__popcll(rw);
             const unsigned ox = grow_occ_x(rw), oy = grow_occ_y(rw), oz = grow_occ_z(rw);
-            lo[0] = min(lo[0], (bx << 2) + __ffs((int)ox) - 1);
-            lo[1] = min(lo[1], (by << 2) + __ffs((int)oy) - 1);
-            lo[2] = min(lo[2], (bz << 2) + __ffs((int)oz) - 1);
-            hi[0] = max(hi[0], (bx << 2) + 32 - __clz((int)ox));
-            hi[1] = max(hi[1], (by << 2) + 32 - __clz((int)oy));
-            hi[2] = max(hi[2], (bz << 2) + 32 - __clz((int)oz));
+            n.lo[0] = min(n.lo[0], (bx << 2) + __ffs((int)ox) - 1);
+            n.lo[1] = min(n.lo[1], (by << 2) + __ffs((int)oy) - 1);
+            n.lo[2] = min(n.lo[2], (bz << 2) + __ffs((int)oz) - 1);
+            n.hi[0] = max(n.hi[0], (bx << 2) + 32 - __clz((int)ox));
+            n.hi[1] = max(n.hi[1], (by << 2) + 32 - __clz((int)oy));
+            n.hi[2] = max(n.hi[2], (bz << 2) + 32 - __clz((int)oz));
         }
     }
-    if (lane == 0u && voxels != 0ull) {
-        atomicAdd(&P.w->voxels, voxels);
-        for (int a = 0; a < 3; ++a) {
-            atomicMin(&P.w->lo[a], lo[a]);
-            atomicMax(&P.w->hi[a], hi[a]);
-        }
-    }
+    if (lane == 0u) report_count_box(&P.w->reached, n.voxels, n.lo, n.hi);
 }
 
 }  // namespace vr

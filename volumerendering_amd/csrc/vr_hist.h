@@ -4,7 +4,7 @@
 //  -- then CLAMP: bin = min(max(i, 0), bins - 1), or DROP: counted iff 0 <= i < bins, else one more in the row's `dropped`.
 // Nothing can be fused, so vr_set_arithmetic plays no part: the kernel is compiled once, included by vr_api.hip alone.
 //
-// Launch shape: a fixed grid of kHistBlocks persistent workgroups of four wavefronts.  The work is cut into BRICK UNITS, the 4 x 4 x 4
+// Launch shape: a fixed grid of kToolBlocks (vr_api_tools.h) persistent workgroups of four wavefronts.  The work is cut into BRICK UNITS, the 4 x 4 x 4
 // voxel cubes of the volume's own brick grid that meet the box (so that units and range records line up); wavefront w of W takes the
 // units w, w + W, ... with one lane per voxel of the unit (x fastest).  Lanes whose voxel lies outside the box -- a unit the box cuts,
 // a side that is no multiple of 4 -- take no part: that is the whole partial path.
@@ -34,7 +34,6 @@
 
 namespace vr {
 
-constexpr unsigned kHistBlocks = 512;        // two workgroups per CU of the 256
 constexpr unsigned kHistLdsBytes = 65536;    // budget of the private copy (what a launch may ask for without opting in to more; two
                                              // workgroups' copies still share a CU's 160 KiB): rows computed * bins <= 16384
 
@@ -56,13 +55,6 @@ __device__ __forceinline__ void hist_add(const HistParams& H, unsigned* s_hist, 
     else atomicAdd(&H.counts[(size_t)row * H.bins + (unsigned)bin], (unsigned long long)n);
 }
 
-__device__ __forceinline__ unsigned long long hist_wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);  // (every lane takes part)
-    return v;
-}
-
 template <bool PLAIN>
 __global__ __launch_bounds__(256) void hist_kernel(const HistParams H)
 {
@@ -77,15 +69,13 @@ __global__ __launch_bounds__(256) void hist_kernel(const HistParams H)
     const int lx = (int)(lane & 3u), ly = (int)((lane >> 2) & 3u), lz = (int)(lane >> 4);
     unsigned long long vox[VR_HIST_ROWS] = {}, dropped[VR_HIST_ROWS] = {};  // per lane
     unsigned long long n_box = 0, n_load = 0, n_settled = 0;
-    const unsigned W = gridDim.x * 4u, uxy = (unsigned)H.un[0] * (unsigned)H.un[1];
-    for (unsigned u = blockIdx.x * 4u + wave; u < H.units; u += W) {
-        const unsigned uz = u / uxy, ur = u - uz * uxy, uy = ur / (unsigned)H.un[0], ux = ur - uy * (unsigned)H.un[0];
-        const int bx = H.u0[0] + (int)ux, by = H.u0[1] + (int)uy, bz = H.u0[2] + (int)uz;
-        const int x0 = bx << 2, y0 = by << 2, z0 = bz << 2;
+    const unsigned W = gridDim.x * 4u, uxy = (unsigned)H.box.un[0] * (unsigned)H.box.un[1];
+    for (unsigned u = blockIdx.x * 4u + wave; u < H.box.units; u += W) {
+        const BrickUnit U = brick_unit(H.box, u, uxy);
         if constexpr (!PLAIN) {
-            const bool whole = x0 >= H.lo[0] && x0 + 4 <= H.hi[0] && y0 >= H.lo[1] && y0 + 4 <= H.hi[1] && z0 >= H.lo[2] && z0 + 4 <= H.hi[2];
+            const bool whole = whole_unit<const BoxUnits&>(H.box, U);
             if (H.bricks && whole) {
-                const float2 rec = H.bricks[((size_t)bz * (size_t)H.bny + (size_t)by) * (size_t)H.bnx + (size_t)bx];
+                const float2 rec = H.bricks[((size_t)U.bz * (size_t)H.bny + (size_t)U.by) * (size_t)H.bnx + (size_t)U.bx];
                 const int i0 = hist_index(rec.x, H.scale), i1 = hist_index(rec.y, H.scale);
                 if (rec.x == rec.x && rec.y == rec.y && i0 == i1) {
                     const int k = hist_key(i0, (int)H.bins, H.drop);
@@ -100,8 +90,8 @@ __global__ __launch_bounds__(256) void hist_kernel(const HistParams H)
                 }
             }
         }
-        const int x = x0 + lx, y = y0 + ly, z = z0 + lz;
-        const bool in = x >= H.lo[0] && x < H.hi[0] && y >= H.lo[1] && y < H.hi[1] && z >= H.lo[2] && z < H.hi[2];  // (hi <= n)
+        const int x = U.x0 + lx, y = U.y0 + ly, z = U.z0 + lz;
+        const bool in = in_box(H.box, x, y, z);  // (hi <= n)
         const size_t idx = ((size_t)z * (size_t)H.ny + (size_t)y) * (size_t)H.nx + (size_t)x;
         unsigned sel = 0u;  // the rows this voxel belongs to
         if (in) {
@@ -153,15 +143,15 @@ __global__ __launch_bounds__(256) void hist_kernel(const HistParams H)
 #pragma unroll
     for (unsigned r = 0; r < VR_HIST_ROWS; ++r) {
         if (!((H.rows >> r) & 1u)) continue;
-        const unsigned long long v = hist_wave_sum(vox[r]), d = hist_wave_sum(dropped[r]);
+        const unsigned long long v = wave_sum_u64(vox[r]), d = wave_sum_u64(dropped[r]);
         if (lane == 0u) {
             if (v != 0ull) atomicAdd(&H.row_sums[2u * r], v);
             if (d != 0ull) atomicAdd(&H.row_sums[2u * r + 1u], d);
         }
     }
-    n_box = hist_wave_sum(n_box);
-    n_load = hist_wave_sum(n_load);
-    n_settled = hist_wave_sum(n_settled);
+    n_box = wave_sum_u64(n_box);
+    n_load = wave_sum_u64(n_load);
+    n_settled = wave_sum_u64(n_settled);
     if (lane == 0u) {
         if (n_box != 0ull) atomicAdd(&H.stats[0], n_box);
         if (n_load != 0ull) atomicAdd(&H.stats[1], n_load);

@@ -30,8 +30,6 @@
 
 namespace vr {
 
-constexpr unsigned kMorphBlocks = 512;  // persistent workgroups of four wavefronts (as kGrowBlocks)
-
 // the bits of word xw whose voxels lie in [lo, hi) along x
 __device__ __forceinline__ unsigned long long morph_xmask(int xw, int lo, int hi)
 {
@@ -42,26 +40,16 @@ __device__ __forceinline__ unsigned long long morph_xmask(int xw, int lo, int hi
 }
 
 // folds one wavefront's word (its popcount, first and last bit, row and slice) into the words' count and bounding box; lane 0 alone
-__device__ __forceinline__ void morph_fold(unsigned long long w, int xw, int y, int z, unsigned long long& n, int lo[3], int hi[3])
+__device__ __forceinline__ void morph_fold(unsigned long long w, int xw, int y, int z, CountBox& n)
 {
     if (w == 0ull) return;
-    n += (unsigned long long)__popcll(w);
-    lo[0] = min(lo[0], (xw << 6) + __ffsll((long long)w) - 1);
-    hi[0] = max(hi[0], (xw << 6) + 64 - __clzll((long long)w));
-    lo[1] = min(lo[1], y);
-    hi[1] = max(hi[1], y + 1);
-    lo[2] = min(lo[2], z);
-    hi[2] = max(hi[2], z + 1);
-}
-
-__device__ __forceinline__ void morph_report(unsigned long long n, const int lo[3], const int hi[3], unsigned long long* count, int* blo, int* bhi)
-{
-    if (n == 0ull) return;
-    atomicAdd(count, n);
-    for (int a = 0; a < 3; ++a) {
-        atomicMin(&blo[a], lo[a]);
-        atomicMax(&bhi[a], hi[a]);
-    }
+    n.voxels += (unsigned long long)__popcll(w);
+    n.lo[0] = min(n.lo[0], (xw << 6) + __ffsll((long long)w) - 1);
+    n.hi[0] = max(n.hi[0], (xw << 6) + 64 - __clzll((long long)w));
+    n.lo[1] = min(n.lo[1], y);
+    n.hi[1] = max(n.hi[1], y + 1);
+    n.lo[2] = min(n.lo[2], z);
+    n.hi[2] = max(n.hi[2], z + 1);
 }
 
 // word u of the box's words -> (xw, y, z): P.bw words per row from word P.bw0, rows and slices of the box
@@ -80,8 +68,7 @@ __global__ __launch_bounds__(256) void morph_pack_kernel(const MorphParams P)
     const unsigned lane = threadIdx.x & 63u;
     const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const float* const src = reinterpret_cast<const float*>(P.src) + P.src_contour;
-    unsigned long long n = 0;  // (wave-uniform)
-    int lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {0, 0, 0};
+    CountBox n = CountBox::empty();  // (wave-uniform)
     const unsigned long long W = (unsigned long long)gridDim.x * 4ull;
     for (unsigned long long u = (unsigned long long)blockIdx.x * 4ull + wave; u < P.box_words; u += W) {
         int xw, y, z;
@@ -94,9 +81,9 @@ __global__ __launch_bounds__(256) void morph_pack_kernel(const MorphParams P)
         }
         const unsigned long long w = vr_ballot(in);
         if (lane == 0u) P.a[((size_t)z * (size_t)P.ny + (size_t)y) * (size_t)P.wx + (size_t)xw] = w;
-        morph_fold(w, xw, y, z, n, lo, hi);
+        morph_fold(w, xw, y, z, n);
     }
-    if (lane == 0u) morph_report(n, lo, hi, &P.w->src_voxels, P.w->src_lo, P.w->src_hi);
+    if (lane == 0u) report_count_box(&P.w->src, n.voxels, n.lo, n.hi);
 }
 
 // the source word (xw, y, z) of a dilation; COMP: of the box's complement
@@ -152,8 +139,7 @@ __global__ __launch_bounds__(256) void morph_write_kernel(const MorphParams P)
     const unsigned lane = threadIdx.x & 63u;
     const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     float* const out = reinterpret_cast<float*>(P.dst) + P.dst_contour;
-    unsigned long long n = 0;  // (wave-uniform)
-    int lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {0, 0, 0};
+    CountBox n = CountBox::empty();  // (wave-uniform)
     const unsigned long long W = (unsigned long long)gridDim.x * 4ull;
     for (unsigned long long u = (unsigned long long)blockIdx.x * 4ull + wave; u < P.box_words; u += W) {
         int xw, y, z;
@@ -171,9 +157,9 @@ __global__ __launch_bounds__(256) void morph_write_kernel(const MorphParams P)
                 out[idx * 4u] = (set && P.combine <= VR_MORPH_OR) ? 1.0f : 0.0f;
             }
         }
-        morph_fold(rw, xw, y, z, n, lo, hi);
+        morph_fold(rw, xw, y, z, n);
     }
-    if (lane == 0u) morph_report(n, lo, hi, &P.w->voxels, P.w->lo, P.w->hi);
+    if (lane == 0u) report_count_box(&P.w->result, n.voxels, n.lo, n.hi);
 }
 
 }  // namespace vr
