@@ -893,6 +893,87 @@ int vr_morph_counters(vr_ctx* ctx, uint64_t out[3]);
  * from the destination slot.  Zeros before the first and after one that failed. */
 int vr_morph_timing(vr_ctx* ctx, float ms[4]);
 
+/* ---- signed distance maps of a mask contour: how far every voxel is from a structure ------------------------------------------------
+ * The exact Euclidean distance transform of a contour of a mask slot, restricted to a box, on an anisotropic grid, written as f32 into
+ * one component of a volume slot -- on the device (csrc/vr_dist.h).  A distance channel composes with everything downstream: slices,
+ * histograms (dose against distance), VR_VARIANT_ISO (the smooth surface of a structure, or of the structure plus 7 mm).
+ *   Membership, operand, box: exactly those of the morphology above.  A' = the voxels of the half-open box that are in contour src_contour
+ *     of src_slot (!= 0.0f: NaN is in, -0.0f is out); B' = box \ A'.  Nothing outside the box is read as set or written: the outside of
+ *     the box is neither foreground nor background (the border rule of VR_MORPH_ERODE).
+ *   Spacing: spacing[3] (x, y, z) in an integer unit of the caller's choice (micrometres, say), each 1 .. 2^20, and on every axis
+ *     (uint64_t)(box_hi[a] - box_lo[a]) * spacing[a] <= 1 << 30, else VR_ERR_INVALID_ARG: every squared distance stays below 2^62 and
+ *     the differences an exact lower-envelope computation forms fit int64_t.
+ *   Fields: for a voxel p of the box D2out(p) = min over q in A' of sum_a ((p_a - q_a) * spacing[a])^2, and D2in(p) the same over B',
+ *     both exact in uint64_t.  An empty set gives BEYOND.
+ *   Limit: limit (same unit), at most 2^31; 0 = none.  With a limit L a value greater than L^2 becomes BEYOND.
+ *   Stored value: the magnitude of a finite D2 is m = sqrt_rn((float)D2) * scale -- the uint64_t -> f32 conversion rounded to nearest,
+ *     the correctly rounded f32 square root, one f32 multiply; BEYOND gives (float)L * scale with a limit and +inf without one.  scale
+ *     must be finite and > 0, else VR_ERR_INVALID_ARG (0.001f turns micrometres into millimetres).  mode:
+ *       VR_DIST_OUTSIDE  +m(D2out): +0 inside A'
+ *       VR_DIST_INSIDE   +m(D2in): +0 outside A'
+ *       VR_DIST_SIGNED   +m(D2out) for p not in A', -m(D2in) for p in A': no voxel is 0, the zero level lies between voxel centres
+ *     into component dst_channel of dst_slot, voxels of the box only.  The other three components keep their bits, and so does every
+ *     voxel outside the box.  A' (and the probe) are packed before anything is written: source and destination may coincide in slot and
+ *     component.  An empty dst_slot is created with the source's nx, ny, nz and every component +0.0f; one of other dimensions is
+ *     VR_ERR_INVALID_ARG.
+ *   Probe (optional): probe_slot / probe_contour name a second contour of the same dimensions, probe_slot = -1 none; it may be the
+ *     destination.  Over the probe's voxels in the box the result holds probe_voxels and probe_min_sq / probe_max_sq of D2out (the limit
+ *     applied; BEYOND is UINT64_MAX), both 0 when probe_voxels == 0: the minimum distance between two structures and the directed
+ *     Hausdorff distance as exact integers.  A probe with VR_DIST_INSIDE is VR_ERR_INVALID_ARG.
+ *   Result: src_voxels = |A'|, lo / hi = its half-open bounding box (all zero when it is empty), beyond = the voxels of the box whose
+ *     stored value is BEYOND's, then the three probe fields.
+ *   Counters (vr_dist_counters), out[1] + out[2] == out[0] always: out[0] = voxels of the box; out[1] = voxels of the box inside the region
+ *     for which the envelope passes computed the call's field (the OUTSIDE field; the INSIDE field in VR_DIST_INSIDE); out[2] = the rest.
+ * Kernel forms: flavour 1 of vr_set_kernel_flavour computes every voxel of the box (out[1] == out[0]).  Every other flavour computes a
+ * field only inside a region outside of which it is known, and fills the rest: with a limit the OUTSIDE field is BEYOND outside the
+ * bounding box of A' grown by limit / spacing[a] voxels per axis (without one the region is the box, and empty for an empty A'); the INSIDE
+ * field is 0 outside A' and exact when computed on the bounding box of A' grown by one voxel, within the box.  The slot, the result and
+ * out[0] are identical across the forms and the volume layouts.
+ * Two laws tie this to the morphology: with E = the ball of vr_morph_ball for (spacing, r), { p : D2out(p) <= r^2 } is VR_MORPH_DILATE by E
+ * and { p in the box : D2in(p) > r^2 } is VR_MORPH_ERODE by E. */
+#define VR_DIST_OUTSIDE 0
+#define VR_DIST_INSIDE  1
+#define VR_DIST_SIGNED  2
+typedef struct vr_dist_desc {
+    int32_t  src_slot, src_contour;     /* the contour: an uploaded slot, component 0 .. 3                       */
+    int32_t  dst_slot, dst_channel;     /* where the distances go; may equal the source (in place)               */
+    int32_t  mode;                      /* VR_DIST_OUTSIDE / VR_DIST_INSIDE / VR_DIST_SIGNED                     */
+    int32_t  probe_slot, probe_contour; /* a second contour whose D2out range is reported; probe_slot = -1: none */
+    uint32_t limit;                     /* 0 = none; at most 2^31                                                */
+    uint32_t spacing[3];                /* x, y, z: 1 .. 2^20 each                                               */
+    float    scale;                     /* stored value = distance * scale                                       */
+    int32_t  box_lo[3], box_hi[3];      /* voxel box, half open, 0 <= lo <= hi <= n per axis                     */
+} vr_dist_desc;
+typedef struct vr_dist_result {
+    uint64_t src_voxels;                /* |A'|                                                                  */
+    int32_t  lo[3], hi[3];              /* half-open bounding box of A'; all zero when it is empty               */
+    uint64_t beyond;                    /* voxels of the box that store BEYOND's value                           */
+    uint64_t probe_voxels, probe_min_sq, probe_max_sq;
+} vr_dist_result;
+
+/* Fills *out for the whole volume of src_slot: the given slots, components and mode, unit spacing, no limit, scale 1.0f, no probe, the
+ * box (0,0,0) .. (nx,ny,nz).  Pure host arithmetic; VR_ERR_INVALID_ARG for a NULL pointer, a slot or component out of range or an
+ * unknown mode, VR_ERR_NOT_READY for an empty source slot. */
+int vr_dist_whole(const vr_ctx* ctx, int src_slot, int src_contour, int dst_slot, int dst_channel, int mode, vr_dist_desc* out);
+
+/* Does the work; `result` may be NULL.  A data-preparation call exactly like vr_mask_morph: it waits for everything in flight, runs on
+ * the ctx's own stream, rebuilds what is derived from the destination slot's voxels as an upload does and is synchronous on return.
+ * What the reporting calls say about the last march, slice, histogram, grow or morph stays as it was.
+ * Checked before anything is enqueued or a slot is touched.  VR_ERR_INVALID_ARG: a NULL ctx or descriptor; a slot out of range (the
+ * probe's: other than -1); a contour or channel outside 0 .. 3; an unknown mode; a probe with VR_DIST_INSIDE; a spacing of 0 or above
+ * 2^20; a limit above 2^31; a scale that is not finite or not > 0; a box that is not 0 <= lo <= hi <= n on every axis or whose extent
+ * times the spacing exceeds 2^30 on some axis; a destination or probe slot of other dimensions.  VR_ERR_NOT_READY: the source slot, or
+ * the probe slot, is empty.  VR_ERR_OOM: the working buffers could not be allocated; nothing has been written. */
+int vr_mask_distance(vr_ctx* ctx, const vr_dist_desc* desc, vr_dist_result* result);
+
+/* Counters of the last vr_mask_distance (as described above).  Zeros before the first. */
+int vr_dist_counters(vr_ctx* ctx, uint64_t out[3]);
+
+/* Device time of the last vr_mask_distance in milliseconds, from events on the ctx's stream: ms[0] the pack of the contour and the probe
+ * (the host's look at the bounding box included), ms[1] the distance passes, ms[2] the write and the result, ms[3] the rebuild of what
+ * is derived from the destination slot.  Zeros before the first and after one that failed. */
+int vr_dist_timing(vr_ctx* ctx, float ms[4]);
+
 /* Volume layout in HBM (A/B measurements; frames and counts are bit-identical in every mode).
  *   0  default: the march kernels gather from a BRICKED copy of every slot -- the vec4 voxels and a scalar f32 density plane
  *      (what fetches that consume .a alone read: BasicVolumeApp.wgsl:171, the density / dose fetches of the other shaders)

@@ -41,6 +41,8 @@ GROW_BATCH = 8                                   # propagation rounds enqueued b
 MORPH_MAX_RADIUS = 31                            # vr_morph_element (include/vr.h)
 MORPH_NONE, MORPH_DILATE, MORPH_ERODE, MORPH_CLOSE, MORPH_OPEN = range(5)   # vr_morph_desc.op
 MORPH_REPLACE, MORPH_OR, MORPH_AND, MORPH_ANDNOT = range(4)                 # vr_morph_desc.combine
+DIST_OUTSIDE, DIST_INSIDE, DIST_SIGNED = range(3)                           # vr_dist_desc.mode (include/vr.h)
+DIST_MAX_SPACING, DIST_MAX_LIMIT, DIST_MAX_EXTENT = 1 << 20, 1 << 31, 1 << 30  # of a spacing, the limit, (hi - lo) * spacing per axis
 
 # every symbol include/vr.h declares (tests check that the library exports each of them)
 ABI_SYMBOLS = [
@@ -61,6 +63,7 @@ ABI_SYMBOLS = [
     "vr_hist_whole", "vr_histogram_async", "vr_histogram", "vr_hist_counters",
     "vr_grow_whole", "vr_segment_grow", "vr_grow_counters", "vr_grow_timing",
     "vr_morph_ball", "vr_morph_box", "vr_morph_whole", "vr_mask_morph", "vr_morph_counters", "vr_morph_timing",
+    "vr_dist_whole", "vr_mask_distance", "vr_dist_counters", "vr_dist_timing",
 ]
 
 
@@ -204,6 +207,38 @@ class MorphResult(C.Structure):
         return int(self.voxels), int(self.src_voxels), tuple(int(x) for x in self.lo), tuple(int(x) for x in self.hi)
 
 
+class DistDesc(C.Structure):
+    """struct vr_dist_desc (include/vr.h): the source slot and contour, the destination slot and channel, the mode, the probe, the limit,
+    the voxel spacing, the scale and the voxel box."""
+    _fields_ = [
+        ("src_slot", C.c_int32), ("src_contour", C.c_int32), ("dst_slot", C.c_int32), ("dst_channel", C.c_int32), ("mode", C.c_int32),
+        ("probe_slot", C.c_int32), ("probe_contour", C.c_int32), ("limit", C.c_uint32), ("spacing", C.c_uint32 * 3), ("scale", C.c_float),
+        ("box_lo", C.c_int32 * 3), ("box_hi", C.c_int32 * 3),
+    ]
+
+    def copy(self, **over) -> "DistDesc":
+        """A copy with the given fields replaced (box_lo / box_hi / spacing from any sequence of three integers)."""
+        d = DistDesc.from_buffer_copy(bytes(self))
+        for k, v in over.items():
+            if k in ("box_lo", "box_hi"):
+                v = (C.c_int32 * 3)(*[int(x) for x in v])
+            if k == "spacing":
+                v = (C.c_uint32 * 3)(*[int(x) for x in v])
+            setattr(d, k, v)
+        return d
+
+
+class DistResult(C.Structure):
+    """struct vr_dist_result: |A'|, its half-open bounding box (zeros when empty), the voxels that store BEYOND's value, and the probe's
+    voxel count and exact minimum / maximum of D2out (BEYOND = 2^64 - 1; zeros without a probe voxel)."""
+    _fields_ = [("src_voxels", C.c_uint64), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("beyond", C.c_uint64),
+                ("probe_voxels", C.c_uint64), ("probe_min_sq", C.c_uint64), ("probe_max_sq", C.c_uint64)]
+
+    def as_tuple(self):
+        return (int(self.src_voxels), tuple(int(x) for x in self.lo), tuple(int(x) for x in self.hi), int(self.beyond),
+                int(self.probe_voxels), int(self.probe_min_sq), int(self.probe_max_sq))
+
+
 class VrError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"vr error {code}: {msg}")
@@ -299,6 +334,10 @@ def load() -> C.CDLL:
     lib.vr_mask_morph.argtypes = [vp, C.POINTER(MorphDesc), C.POINTER(MorphResult)]
     lib.vr_morph_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
     lib.vr_morph_timing.argtypes = [vp, C.POINTER(C.c_float * 4)]
+    lib.vr_dist_whole.argtypes = [vp, i32, i32, i32, i32, i32, C.POINTER(DistDesc)]
+    lib.vr_mask_distance.argtypes = [vp, C.POINTER(DistDesc), C.POINTER(DistResult)]
+    lib.vr_dist_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
+    lib.vr_dist_timing.argtypes = [vp, C.POINTER(C.c_float * 4)]
     lib.vr_present_async.argtypes = [vp, vp, vp, vp]
     lib.vr_present_tiles_async.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
     lib.vr_hint_frames_in_flight.argtypes = [vp, i32]
@@ -697,6 +736,28 @@ class Context:
         self._chk(self.lib.vr_morph_timing(self.h, C.byref(out)))
         return tuple(float(x) for x in out)
 
+    def dist_whole(self, src_slot: int, src_contour: int, dst_slot: int, dst_channel: int, mode: int) -> DistDesc:
+        """vr_dist_whole: the descriptor of a distance map over the whole volume (unit spacing, no limit, scale 1, no probe)."""
+        return dist_whole(self, src_slot, src_contour, dst_slot, dst_channel, mode)
+
+    def mask_distance(self, desc: DistDesc) -> DistResult:
+        """vr_mask_distance: the exact Euclidean distance transform of a contour into one component of a volume slot (synchronous)."""
+        out = DistResult()
+        self._chk(self.lib.vr_mask_distance(self.h, C.byref(desc), C.byref(out)))
+        return out
+
+    def dist_counters(self):
+        """(voxels of the box, voxels inside the region the envelope passes computed, the rest) of the last mask_distance."""
+        out = (C.c_uint64 * 3)()
+        self._chk(self.lib.vr_dist_counters(self.h, C.byref(out)))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def dist_timing(self):
+        """(pack, distance passes, write, refresh) of the last mask_distance in ms of device time (vr_dist_timing)."""
+        out = (C.c_float * 4)()
+        self._chk(self.lib.vr_dist_timing(self.h, C.byref(out)))
+        return tuple(float(x) for x in out)
+
     def set_volume_layout(self, mode: int):
         """0 bricked copy (default), 1 the reference's vec4 voxels only, 3 x-fastest voxels + density plane (2 was removed)."""
         self._chk(self.lib.vr_set_volume_layout(self.h, mode))
@@ -729,3 +790,11 @@ def morph_box(rx: int, ry: int, rz: int) -> MorphElement:
     if rc != VR_OK:
         raise VrError(rc, f"vr_morph_box: radii {(rx, ry, rz)}")
     return e
+
+
+def dist_whole(ctx: "Context", src_slot: int, src_contour: int, dst_slot: int, dst_channel: int, mode: int) -> DistDesc:
+    """vr_dist_whole: the descriptor of a distance map of contour src_contour of volume src_slot over its whole volume into component
+    dst_channel of volume dst_slot: unit spacing, no limit, scale 1.0, no probe (edit with copy)."""
+    d = DistDesc()
+    ctx._chk(ctx.lib.vr_dist_whole(ctx.h, src_slot, src_contour, dst_slot, dst_channel, mode, C.byref(d)))
+    return d

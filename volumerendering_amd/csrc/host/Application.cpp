@@ -185,6 +185,34 @@ int Application::MarginMm(int srcSlot, int srcContour, int dstSlot, int dstConto
     return MorphContour(d, out);
 }
 
+int Application::DistanceMap(const vr_dist_desc& desc, vr_dist_result* out)
+{
+    if (!p_Ctx) return VR_ERR_NOT_READY;
+    const int rc = vr_mask_distance(p_Ctx, &desc, out);
+    if (rc != VR_OK) m_Error = vr_last_error(p_Ctx);
+    return rc;
+}
+
+int Application::DistanceMm(int srcSlot, int srcContour, int dstSlot, int dstChannel, int mode, float limitMm, const VolumeFileDcm& grid,
+                            vr_dist_result* out)
+{
+    if (!p_Ctx) return VR_ERR_NOT_READY;
+    const DicomVolumeParams p = grid.GetVolumeParams();
+    const double mmOf[4] = {p.PixelSpacing[0], p.PixelSpacing[1], p.SliceThickness, (double)limitMm};
+    uint32_t um[4];
+    for (int i = 0; i < 4; ++i) {
+        if (!std::isfinite(mmOf[i]) || mmOf[i] < 0.0 || mmOf[i] > 4.0e6) return VR_ERR_INVALID_ARG;  // (micrometres fit 32 bits)
+        um[i] = (uint32_t)std::lround(mmOf[i] * 1000.0);
+    }
+    vr_dist_desc d;
+    const int rc = vr_dist_whole(p_Ctx, srcSlot, srcContour, dstSlot, dstChannel, mode, &d);
+    if (rc != VR_OK) return rc;
+    for (int a = 0; a < 3; ++a) d.spacing[a] = um[a];
+    d.limit = um[3];
+    d.scale = 0.001f;
+    return DistanceMap(d, out);
+}
+
 int Application::Pick(uint32_t x, uint32_t y, vr_pick_result* out)
 {
     if (!p_Ctx || !p_App) return VR_ERR_NOT_READY;

@@ -74,6 +74,16 @@ public:
     // vr_morph_ball, the spacings and the radius each rounded to whole micrometres with lround.  VR_ERR_INVALID_ARG for a margin that
     // is negative or not finite, a spacing that is not positive, or a margin beyond VR_MORPH_MAX_RADIUS voxels on some axis.
     int MarginMm(int srcSlot, int srcContour, int dstSlot, int dstContour, float mm, const VolumeFileDcm& grid, vr_morph_result* out);
+    // Exact distance maps of a mask contour on the device (vr_mask_distance of include/vr.h): a descriptor passed through.  `out` may be
+    // nullptr.
+    int DistanceMap(const vr_dist_desc& desc, vr_dist_result* out);
+    // The distance in millimetres from contour srcContour of volume srcSlot, over the whole volume on the voxel grid of `grid` (its
+    // PixelSpacing and SliceThickness), into component dstChannel of volume dstSlot: mode = VR_DIST_OUTSIDE / VR_DIST_INSIDE /
+    // VR_DIST_SIGNED, limitMm = where the map saturates (0: nowhere).  The spacings and the limit are each rounded to whole micrometres
+    // with lround, as MarginMm does, and scale = 0.001f.  VR_ERR_INVALID_ARG for a limit that is negative or not finite, a spacing that
+    // is not positive, or a volume longer than 2^30 micrometres on some axis.
+    int DistanceMm(int srcSlot, int srcContour, int dstSlot, int dstChannel, int mode, float limitMm, const VolumeFileDcm& grid,
+                   vr_dist_result* out);
     // the accumulated opacity at which the unlit / lit scene's surface lies (vr_set_surface_threshold: finite, 0 <= tau < 1)
     int SetSurfaceThreshold(float tau);
 

@@ -421,6 +421,19 @@ int vrh_app_margin_mm(void* a, int src_slot, int src_contour, int dst_slot, int 
     if (!vh || !vh->dcm) return VR_ERR_INVALID_ARG;
     VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->MarginMm(src_slot, src_contour, dst_slot, dst_contour, mm, *vh->dcm, out); })
 }
+// Application::DistanceMap and Application::DistanceMm (vr_mask_distance of the application's context); grid: as vrh_app_margin_mm's
+int vrh_app_distance_map(void* a, const vr_dist_desc* desc, vr_dist_result* out)
+{
+    if (!desc) return VR_ERR_INVALID_ARG;
+    VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->DistanceMap(*desc, out); })
+}
+int vrh_app_distance_mm(void* a, int src_slot, int src_contour, int dst_slot, int dst_channel, int mode, float limit_mm, void* grid,
+                        vr_dist_result* out)
+{
+    auto* vh = static_cast<VolumeHandle*>(grid);
+    if (!vh || !vh->dcm) return VR_ERR_INVALID_ARG;
+    VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->DistanceMm(src_slot, src_contour, dst_slot, dst_channel, mode, limit_mm, *vh->dcm, out); })
+}
 int vrh_app_set_surface_threshold(void* a, float tau) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->SetSurfaceThreshold(tau); }) }
 void vrh_app_set_prepare_on_device(void* a, int on) { static_cast<Application*>(a)->m_PrepareOnDevice = on != 0; }
 int vrh_app_update(void* a) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->OnUpdate(); }) }

@@ -11,6 +11,8 @@
 #include "vr_grow.h"
 // Mask morphology (vr_mask_morph): integer work on bit-rows, compiled once as well
 #include "vr_morph.h"
+// Distance maps (vr_mask_distance): exact integer work on the same bit-rows, compiled once as well
+#include "vr_dist.h"
 
 // the same dispatch over the kernels compiled with fused multiply-adds (vr_fused.hip)
 namespace vrf {
@@ -19,6 +21,7 @@ void launch_shadow_build(const vr::MarchParams& P, float* out, float sigma, bool
 void launch_slice(const vr::SliceParams& S, int reduce, bool nearest, bool off32, bool skip, unsigned tiles, hipStream_t s);
 }
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -39,6 +42,7 @@ using namespace vr;
 #include "vr_api_views.h"
 #include "vr_api_segment.h"
 #include "vr_api_morph.h"
+#include "vr_api_dist.h"
 
 namespace {
 

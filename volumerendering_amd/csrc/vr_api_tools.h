@@ -1,4 +1,4 @@
-// vr_api_tools.h -- what the voxel tools (the histograms of vr_api_views.h, vr_api_segment.h, vr_api_morph.h) share on the host: the
+// vr_api_tools.h -- what the voxel tools (the histograms of vr_api_views.h, vr_api_segment.h, vr_api_morph.h, vr_api_dist.h) share on the host: the
 // rules for a box and a second slot, a walk's units and grid (vr_units.h), the shell and the report of a call into a mask slot.
 #pragma once
 

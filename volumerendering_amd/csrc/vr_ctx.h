@@ -177,6 +177,18 @@ struct MorphState {
     ToolReport report;                 // phases: pack, morphology, write, refresh_bricks
 };
 
+// Distance maps (vr_mask_distance, vr_dist.h): the working buffers of the last call, grown on demand; what vr_dist_counters and
+// vr_dist_timing report.
+struct DistState {
+    DevBuf<unsigned long long> words;    // two bit-row buffers: the packed contour and the packed probe
+    DevBuf<unsigned long long> d2[2];    // the OUTSIDE and the INSIDE field: one word per voxel of the field's region
+    DevBuf<unsigned long long> stack_g;  // the envelope stacks of a line pass, one entry per voxel of the larger region ...
+    DevBuf<unsigned> stack_st;           // ... (vr_device.h: DistLine)
+    DevBuf<DistWords> d_words;           // the counts, the bounding box and the probe's range ...
+    PinnedBuf<DistWords> h_words;        // ... and where the host sets and reads them
+    ToolReport report;                   // phases: pack, distance passes, write, refresh_bricks
+};
+
 // What the reporting calls (vr_last_counters, vr_last_kernel_flavour, vr_last_timing, vr_kernel_times, vr_kernel_choice,
 // vr_download_tiles, vr_last_block_trace) read about the most recent march launch.  vr_pick copies it out and back as one value.
 struct LastLaunch {
@@ -366,6 +378,7 @@ struct vr_ctx {
     const float* d_far = nullptr;
     GrowState grow;  // region growing (vr_segment_grow)
     MorphState morph;  // mask morphology (vr_mask_morph)
+    DistState dist;    // distance maps (vr_mask_distance)
     std::string err;
 };
 

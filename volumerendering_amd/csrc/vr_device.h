@@ -246,6 +246,48 @@ struct MorphPass {
     unsigned long long words;     // rw * ry * rz
 };
 
+// The device words of one vr_mask_distance (vr_dist.h): set by the host before the first kernel, read behind the packs and the write.
+struct DistWords {
+    MorphWords src;    // .src = |A'| and its bounding box, from morph_pack_kernel (.result is not used)
+    MorphWords probe;  // the same of the probe's pack (only the packed bits are used)
+    unsigned long long beyond;                           // voxels of the box that store BEYOND's value
+    unsigned long long probe_voxels, probe_min, probe_max;  // of D2out over the probe (min starts as ~0, max as 0)
+};
+
+// One squared-distance field of a vr_mask_distance: uint64_t per voxel of a REGION of the box, x fastest, kDistNone = no source.
+struct DistField {
+    unsigned long long* d2;
+    int lo[3], n[3];  // the region: first voxel and extent per axis (some n == 0: empty, nothing was computed)
+};
+// The x pass over the words of a field's region (vr_dist.h): from the bit-rows `bits` into F.d2.
+struct DistXPass {
+    const unsigned long long* bits;  // the packed operand A' (MorphParams::a)
+    DistField F;
+    int ny, wx;                      // rows per slice and words per row of the bit-rows
+    int rw0, rw;                     // the words of a row that meet the region: the first and their number ...
+    unsigned long long words;        // ... and rw * rows * slices of the region
+    unsigned long long spacing;      // of x
+};
+// One envelope pass along y or z: lane t works the line d2[(t / inner) * outer + t % inner + i * stride], i < n.
+struct DistLine {
+    unsigned long long* d2;
+    unsigned long long lanes, inner, outer, stride;
+    int n;
+    unsigned long long spacing;      // of the line's axis
+    unsigned long long* stack_g;     // the envelope's stacks, entry q of lane t at [q * lanes + t]: a parabola's g ...
+    unsigned* stack_st;              // ... and its apex s | the first index t where it is the lowest << 16
+};
+// Kernel argument block of the write of a vr_mask_distance (vr_dist.h; vr_dist_desc of include/vr.h): passed by value.
+struct DistParams {
+    MorphParams m;                    // the box walk and the packed operand (m.a); m.dst / m.dst_contour = where the distances go
+    const unsigned long long* probe;  // the packed probe, nullptr = none
+    DistField out, in;                // D2out and D2in (a field the mode does not need is empty and not read)
+    int mode;                         // VR_DIST_OUTSIDE ..
+    unsigned long long limit_sq;      // 0 = no limit
+    float scale, beyond_value;        // (float)L * scale, or +inf
+    DistWords* w;
+};
+
 // Work queue of the persistent-wavefront kernel (vr_pw.h): eight heads, one per class of the workgroup index modulo 8,
 // zero at launch; heads[c * 64] counts the items of class c handed out beyond every wavefront's first.
 struct PwQueue {

@@ -68,6 +68,8 @@ def load() -> C.CDLL:
         "vrh_app_grow_from_pick": (i32, [vp, C.POINTER(capi.PickResult), i32, i32, i32, f32, f32, i32, C.POINTER(capi.GrowResult)]),
         "vrh_app_morph_contour": (i32, [vp, C.POINTER(capi.MorphDesc), C.POINTER(capi.MorphResult)]),
         "vrh_app_margin_mm": (i32, [vp, i32, i32, i32, i32, f32, vp, C.POINTER(capi.MorphResult)]),
+        "vrh_app_distance_map": (i32, [vp, C.POINTER(capi.DistDesc), C.POINTER(capi.DistResult)]),
+        "vrh_app_distance_mm": (i32, [vp, i32, i32, i32, i32, i32, f32, vp, C.POINTER(capi.DistResult)]),
         "vrh_app_slice": (i32, [vp, C.POINTER(capi.SliceDesc), vp]),
         "vrh_app_slice_through_pick": (C.c_longlong, [vp, C.POINTER(capi.PickResult), i32, i32, vp, C.c_size_t, C.POINTER(u32), C.POINTER(u32)]), "vrh_app_set_surface_threshold": (i32, [vp, f32]), "vrh_app_update": (i32, [vp]), "vrh_app_render": (i32, [vp]),
         "vrh_app_resize": (i32, [vp, u32, u32]), "vrh_app_read_frame": (i32, [vp, vp, vp, C.POINTER(u64)]),
@@ -530,6 +532,21 @@ class Application:
         volume read from DICOM: its PixelSpacing and SliceThickness), stored as contour dst_contour of volume dst_slot."""
         out = capi.MorphResult()
         self._chk(self.lib.vrh_app_margin_mm(self.h, src_slot, src_contour, dst_slot, dst_contour, mm, grid.h, C.byref(out)))
+        return out
+
+    def distance_map(self, desc: capi.DistDesc) -> capi.DistResult:
+        """Application::DistanceMap: vr_mask_distance (include/vr.h) on the application's context."""
+        out = capi.DistResult()
+        self._chk(self.lib.vrh_app_distance_map(self.h, C.byref(desc), C.byref(out)))
+        return out
+
+    def distance_mm(self, src_slot: int, src_contour: int, dst_slot: int, dst_channel: int, mode: int, limit_mm: float,
+                    grid: "VolumeFile") -> capi.DistResult:
+        """Application::DistanceMm: the distance in millimetres from contour src_contour of volume src_slot on the voxel grid of `grid` (a
+        volume read from DICOM: its PixelSpacing and SliceThickness) into component dst_channel of volume dst_slot; mode = capi.DIST_*,
+        limit_mm = where the map saturates (0: nowhere)."""
+        out = capi.DistResult()
+        self._chk(self.lib.vrh_app_distance_mm(self.h, src_slot, src_contour, dst_slot, dst_channel, mode, limit_mm, grid.h, C.byref(out)))
         return out
 
     def set_surface_threshold(self, tau: float):
