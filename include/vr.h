@@ -974,6 +974,91 @@ int vr_dist_counters(vr_ctx* ctx, uint64_t out[3]);
  * is derived from the destination slot.  Zeros before the first and after one that failed. */
 int vr_dist_timing(vr_ctx* ctx, float ms[4]);
 
+/* ---- polygon rasterisation: closed planar outlines scan-converted into contours of a mask slot ------------------------------------
+ * The closed polygons of a structure set, or what a user draws on a slice view, become contours of a mask slot -- on the device
+ * (csrc/vr_raster.h), so that an outline can be added to a contour, cut out of it or replace it without a volume passing through the
+ * host.  Everything is integer arithmetic; the result is exact and does not depend on scheduling.
+ *   Grid: the voxels of grid_slot (nx, ny, nz).  The centre of voxel (i, j) of a slice is (xc, yc) = (origin[0] + i * spacing[0],
+ *     origin[1] + j * spacing[1]) in an integer unit of the caller's choice (micrometres, say).  spacing: 1 .. 2^20 each.
+ *   Polygons: polygon p is the points[first .. first + count) (pairs x, y in the same unit) on slice `slice`, for contour `contour`.  Its
+ *     edges join consecutive points, and the last point joins the first.  Each edge is oriented from a to b so that by > ay; horizontal
+ *     edges never count.
+ *   Coverage: an edge COUNTS for voxel (i, j) iff ay <= yc < by and (xc - ax) * (by - ay) < (yc - ay) * (bx - ax): the row is half open
+ *     and the centre lies strictly left of the crossing.  A polygon COVERS the voxel iff an odd number of its edges count.  Hence
+ *       - a centre on a left or lower boundary is in, one on a right or upper boundary is out;
+ *       - two polygons that share an edge partition the voxels between them: none is covered twice, none is left out;
+ *       - a polygon of 1 or 2 points, or of zero area, covers nothing;
+ *       - a self-intersecting polygon follows the even-odd rule.
+ *   Range: every point coordinate and both origin values lie within -2^29 .. 2^29, else VR_ERR_INVALID_ARG.  Then on the rows where an
+ *     edge can count yc - ay < by - ay <= 2^30, each product is below 2^60, N = (yc - ay) * (bx - ax) + (ax - origin[0]) * (by - ay) is
+ *     below 2^61 in magnitude and D = spacing[0] * (by - ay) is at most 2^50: an edge on row j toggles exactly the voxels [0, k) of the
+ *     row, k = clamp(ceil(N / D), 0, nx), in int64_t.
+ *   Sets: for each contour k, R_k is a part of the box, built from the polygons of the call with contour == k and box_lo[2] <= slice <
+ *     box_hi[2], each on its own slice, rows and columns cut to the box.  rule:
+ *       VR_POLY_EVEN_ODD  a voxel is in R_k iff an odd number of those polygons cover it (a polygon inside another one is a hole)
+ *       VR_POLY_UNION     ... iff at least one of them, taken even-odd on its own, covers it
+ *     A polygon whose slice lies outside the box covers nothing.  A polygon whose contour is not in `contours` is VR_ERR_INVALID_ARG.
+ *   Writing: for each k in `contours` (bit k set), component k of the voxels of the box is written by `combine`, with R_k for R, exactly
+ *     as the morphology above writes: VR_MORPH_REPLACE 1.0f in R and +0.0f elsewhere, VR_MORPH_OR 1.0f in R, VR_MORPH_AND +0.0f
+ *     outside R, VR_MORPH_ANDNOT +0.0f in R; the rest of the box, the components not in `contours` and every voxel outside the box keep
+ *     their bits (NaN payloads and -0 included).  A contour in `contours` without polygons has an empty R_k: REPLACE clears the box.
+ *   Destination: an empty dst_slot is created with the grid's nx, ny, nz and every component +0.0f; one that holds a volume of other
+ *     dimensions is VR_ERR_INVALID_ARG.  dst_slot == grid_slot is allowed.
+ *   Result: per contour k in `contours`, voxels[k] = |R_k| and lo[k] / hi[k] = its half-open bounding box; zeros for an empty set and
+ *     for a contour that is not in `contours`.
+ *   Counters (vr_polygons_counters), out[1] + out[2] == out[0] always: out[0] = polygons given; out[1] = polygons rasterised; out[2] =
+ *     polygons skipped: those whose slice is outside the box and, in the default kernel form, those whose bounding rows or columns miss
+ *     the box.
+ * Kernel forms: every flavour of vr_set_kernel_flavour but 1 visits, for each polygon, only the rows of the box that its y span reaches
+ * and skips a polygon that misses the box; flavour 1 visits every row of the box for every polygon of a slice inside the box.  The
+ * slot, the result and out[0] are identical across the forms and the volume layouts. */
+#define VR_POLY_EVEN_ODD 0
+#define VR_POLY_UNION    1
+typedef struct vr_polygon {
+    uint32_t first, count;             /* points[first .. first + count)                                         */
+    int32_t  slice;                    /* z of the slice the polygon lies on                                     */
+    int32_t  contour;                  /* 0 .. 3, and in the descriptor's `contours`                             */
+} vr_polygon;
+typedef struct vr_polygons_desc {
+    int32_t  grid_slot;                /* an uploaded slot: its nx, ny, nz are the grid (and a fresh destination's dimensions) */
+    int32_t  dst_slot;                 /* may equal grid_slot                                                    */
+    int32_t  contours;                 /* bit k set: contour k of dst_slot is written by this call (1 .. 15)     */
+    int32_t  rule, combine;            /* VR_POLY_EVEN_ODD / VR_POLY_UNION; VR_MORPH_REPLACE / OR / AND / ANDNOT */
+    int32_t  box_lo[3], box_hi[3];     /* voxel box, half open; nothing outside it is written                    */
+    int32_t  origin[2];                /* x, y of the CENTRE of voxel (0, 0), in the caller's unit               */
+    uint32_t spacing[2];               /* voxel pitch along x, y in the same unit: 1 .. 2^20                     */
+    uint32_t n_points, n_polygons;
+    const int32_t*    points;          /* n_points pairs (x, y) in that unit, host memory                        */
+    const vr_polygon* polygons;        /* host memory                                                            */
+} vr_polygons_desc;
+typedef struct vr_polygons_result {
+    uint64_t voxels[4];                /* |R_k|                                                                  */
+    int32_t  lo[4][3], hi[4][3];       /* half-open bounding box of R_k; all zero when it is empty               */
+} vr_polygons_result;
+
+/* Fills *out for the whole grid of grid_slot: the given slots, contour 0 alone (contours = 1), VR_POLY_EVEN_ODD, VR_MORPH_REPLACE, the box
+ * (0,0,0) .. (nx,ny,nz), origin (0, 0), unit spacing and no polygons.  Pure host arithmetic; VR_ERR_INVALID_ARG for a NULL pointer or a
+ * slot out of range, VR_ERR_NOT_READY for an empty grid slot. */
+int vr_polygons_whole(const vr_ctx* ctx, int grid_slot, int dst_slot, vr_polygons_desc* out);
+
+/* Does the work; `result` may be NULL.  A data-preparation call exactly like vr_mask_morph: it waits for everything in flight, runs on
+ * the ctx's own stream, rebuilds what is derived from the destination slot's voxels as an upload does and is synchronous on return: the
+ * points and polygons may be freed then.  What the reporting calls say about earlier launches and tools stays as it was.
+ * Checked before anything is enqueued or a slot is touched.  VR_ERR_INVALID_ARG: a NULL ctx or descriptor; a slot out of range; a NULL
+ * points or polygons pointer with a non-zero count; a polygon with first + count > n_points, a contour outside 0 .. 3 or one that is
+ * not in `contours`; `contours` outside 1 .. 15; an unknown rule or combine; a box that is not 0 <= lo <= hi <= n on every axis; a
+ * spacing of 0 or above 2^20; a coordinate or origin value outside the range; a destination slot of other dimensions.
+ * VR_ERR_NOT_READY: the grid slot is empty.  n_polygons == 0 is legal. */
+int vr_mask_polygons(vr_ctx* ctx, const vr_polygons_desc* desc, vr_polygons_result* result);
+
+/* Counters of the last vr_mask_polygons (as described above).  Zeros before the first. */
+int vr_polygons_counters(vr_ctx* ctx, uint64_t out[3]);
+
+/* Device time of the last vr_mask_polygons in milliseconds, from events on the ctx's stream: ms[0] the upload of the points and the
+ * work list, ms[1] the raster, ms[2] the write and the result, ms[3] the rebuild of what is derived from the destination slot.  Zeros
+ * before the first and after one that failed. */
+int vr_polygons_timing(vr_ctx* ctx, float ms[4]);
+
 /* Volume layout in HBM (A/B measurements; frames and counts are bit-identical in every mode).
  *   0  default: the march kernels gather from a BRICKED copy of every slot -- the vec4 voxels and a scalar f32 density plane
  *      (what fetches that consume .a alone read: BasicVolumeApp.wgsl:171, the density / dose fetches of the other shaders)

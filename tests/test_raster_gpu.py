@@ -1,0 +1,492 @@
+"""GPU side of polygon rasterisation (vr_mask_polygons, csrc/vr_raster.h): the downloaded destination slot EQUAL, bit for bit, to the
+numpy restatement (raster_ref.py, pinned on the CPU by tests/test_raster.py), and the result equal too -- word and box edges, the tie
+rules on four grids, more edges than lanes, many polygons on one slice under both rules, a 65535-voxel axis, polygons outside the
+volume and at the ends of the coordinate range, every way of storing and every placement, both kernel forms and the volume layouts,
+the freshness of everything downstream of the mask, the errors, a random sweep, and the host surface."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import host_ref as hr
+import morph_cases as mc
+import raster_cases as rc
+import raster_ref as rr
+import test_histogram_gpu as thg
+import vrtest as vt
+from volumerendering_amd import capi
+
+pytestmark = pytest.mark.gpu
+f32 = np.float32
+W, H = 64, 48
+COMBINES = [capi.MORPH_REPLACE, capi.MORPH_OR, capi.MORPH_AND, capi.MORPH_ANDNOT]
+CT = rc.GRIDS[1]  # 977 x 977 off a negative origin
+
+
+def desc(shape, grid=rc.GRIDS[0], box=None, **over):
+    """A descriptor on the grid of slot 0 into slot 1, contour 0, EVEN_ODD, REPLACE, the whole volume unless a box is given."""
+    d = capi.PolygonsDesc()
+    d.grid_slot, d.dst_slot, d.contours, d.rule, d.combine = 0, 1, 1, capi.POLY_EVEN_ODD, capi.MORPH_REPLACE
+    lo, hi = box if box else mc.whole(shape)
+    return d.copy(box_lo=lo, box_hi=hi, spacing=grid[0], origin=grid[1], **over)
+
+
+def check(ctx, d, points, polygons, shape, before, what=None):
+    """One vr_mask_polygons against the restatement: the destination slot bit for bit, the result, out[0] and out[1] + out[2] == out[0].
+    `before`: the destination slot's voxels before the call (None: an empty slot).  Returns (result, counters, the downloaded
+    destination, R as (4, nz, ny, nx))."""
+    res = ctx.mask_polygons(d, points, polygons)
+    cnt = ctx.polygons_counters()
+    got = ctx.volume_download(d.dst_slot, shape)
+    want, result, r = rr.raster(shape, before, points, polygons, tuple(d.origin), tuple(d.spacing), d.contours, d.rule, d.combine,
+                                tuple(d.box_lo), tuple(d.box_hi))
+    bad = np.argwhere(vt.bits(got) != vt.bits(want))
+    assert bad.size == 0, (what, len(bad), bad[:4])
+    assert res.as_tuple() == result, (what, res.as_tuple(), result)
+    assert cnt[0] == len(polygons) and cnt[1] + cnt[2] == cnt[0], (what, cnt, len(polygons))
+    return res, cnt, got, r
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = capi.Context(W, H, 0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(autouse=True)
+def defaults(ctx):
+    yield
+    ctx.set_kernel_flavour(0)
+    ctx.set_volume_layout(0)
+
+
+def edge_polygons(shape, grid):
+    """On every slice: a 17-gon over most of it (contour 0), a rectangle that straddles x = 63 / 64 between centres and one whose sides
+    lie on the centres of columns 63 and 64 (contour 1), and a strip that sticks out of the volume on three sides (contour 0)."""
+    nz, ny, nx = shape
+    F = rc.F
+    polys = []
+    for z in range(nz):
+        polys.append((rc.place(rc.ngon(17, nx / 2 + z % 3, ny / 2, nx * 0.47, ny * 0.45, phase=0.1 * z), grid[1], grid[0]), z, 0))
+        polys.append((rc.place(rc.rect(F(125, 2), F(1, 2), F(129, 2), ny - F(3, 2)), grid[1], grid[0]), z, 1))
+        polys.append((rc.place(rc.rect(63, 1, 64, ny), grid[1], grid[0]), z, 1))
+        polys.append((rc.place(rc.rect(-5, -5, nx + 5, F(5, 2)), grid[1], grid[0]), z, 0))
+    return rc.flatten(polys)
+
+
+@pytest.mark.parametrize("shape", [(6, 9, 70), (21, 37, 130), (4, 4, 64)], ids=["70x9x6", "130x37x21", "64x4x4"])
+def test_word_and_box_edges(ctx, shape):
+    """x crossing one word, three words, exactly one word; the boxes of the morphology's test of the same name; polygons that straddle
+    x = 63 / 64 and the faces of every box; both kernel forms and both rules."""
+    nz, ny, nx = shape
+    points, polygons = edge_polygons(shape, CT)
+    state = mc.arbitrary_bits(shape, seed=23)
+    ctx.volume_upload(0, np.zeros(shape + (4,), f32))
+    ctx.volume_upload(1, state)
+    boxes = [mc.whole(shape), ((1, 1, 1), (nx - 1, ny - 1, nz - 1)), ((nx // 2, 1, 0), (nx // 2 + 1, 2, 1)), ((3, 2, 1), (3, ny, nz)),
+             ((nx - 3, 0, 0), (nx, ny, 2)), ((0, 0, nz - 1), (min(nx, 64), ny - 1, nz))]
+    if nx > 64:
+        boxes += [((61, 2, 1), (67, ny - 2, nz - 1)), ((64, 0, 0), (nx, ny, nz)), ((63, 1, 0), (65, 3, nz))]
+    seen = 0
+    for n, box in enumerate(boxes):
+        for flavour in (0, 1):
+            ctx.set_kernel_flavour(flavour)
+            d = desc(shape, CT, box, contours=0b0011, rule=n % 2, combine=COMBINES[n % 4])
+            res, cnt, state, _ = check(ctx, d, points, polygons, shape, state, what=(box, flavour))
+            seen = max(seen, res.voxels[0] + res.voxels[1])
+            if flavour == 1:
+                assert cnt[2] == sum(1 for _, _, z, _ in polygons if not box[0][2] <= z < box[1][2])
+    assert seen > 16  # (not vacuous)
+
+
+@pytest.mark.parametrize("grid", rc.GRIDS, ids=["unit", "ct_negative", "aniso_negative", "unit_negative"])
+def test_tie_rules(ctx, grid):
+    """Vertices on voxel centres, edges through centres, horizontal edges on centre rows, polygons between two rows or columns of
+    centres, of 1 and 2 points and of zero area, bow-ties: one shape per slice, then all of them on one slice under both rules."""
+    shapes = rc.tie_shapes()
+    shape = (len(shapes) + 1, 12, 14)
+    polys = [(rc.place(p, grid[1], grid[0]), z, z % 4) for z, (_, p) in enumerate(shapes)]
+    polys += [(rc.place(p, grid[1], grid[0]), len(shapes), 2) for _, p in shapes]
+    points, polygons = rc.flatten(polys)
+    ctx.volume_upload(0, np.zeros(shape + (4,), f32))
+    state = mc.arbitrary_bits(shape, seed=31)
+    ctx.volume_upload(1, state)
+    for rule in (capi.POLY_EVEN_ODD, capi.POLY_UNION):
+        for flavour in (0, 1):
+            ctx.set_kernel_flavour(flavour)
+            res, cnt, state, r = check(ctx, desc(shape, grid, contours=15, rule=rule), points, polygons, shape, state, what=(rule, flavour))
+            for z, (name, _) in enumerate(shapes):
+                if name in ("one_point", "two_points", "zero_area") or (name.startswith("between") and min(grid[0]) >= 4):
+                    assert not r[:, z].any(), name
+            assert r[0, 0].sum() == 7 * 5 and r[0, 0, 1:6, 2:9].all()  # rect_on_centres: left / lower sides in, right / upper out
+            assert sum(res.voxels) > 200
+
+
+def test_more_edges_than_lanes(ctx):
+    """A 200-gon and a comb of 1002 points whose 250 teeth are one voxel wide: the lanes stride over the edges, and a row of the comb has
+    500 crossings."""
+    shape = (2, 12, 520)
+    grid = ((500, 700), (-1234, 77))
+    comb = rc.comb(3, 2, 250, 6)
+    assert len(comb) == 1002
+    points, polygons = rc.flatten([(rc.place(rc.ngon(200, 260, 5.6, 255, 5.2), grid[1], grid[0]), 0, 0), (rc.place(comb, grid[1], grid[0]), 1, 0)])
+    ctx.volume_upload(0, np.zeros(shape + (4,), f32))
+    state = np.zeros(shape + (4,), f32)
+    ctx.volume_upload(1, state)
+    for flavour in (0, 1):
+        ctx.set_kernel_flavour(flavour)
+        res, _, state, r = check(ctx, desc(shape, grid), points, polygons, shape, state, what=flavour)
+        assert r[0, 1, 5, 3:503:2].all() and not r[0, 1, 5, 4:503:2].any() and r[0, 1, 2, 3:502].all()
+        assert r[0, 1].sum() == 250 * 6 + 499 and r[0, 0].sum() > 3000
+
+
+def test_many_polygons_on_one_slice(ctx):
+    """300 small overlapping polygons on one slice: the global atomics of many wavefronts meet in the same words.  EVEN_ODD and UNION
+    must differ."""
+    shape = (2, 37, 130)
+    polys = [(rc.place(p, CT[1], CT[0]), 1, 0) for p in rc.cloud(300, (130, 37), seed=41)]
+    points, polygons = rc.flatten(polys)
+    ctx.volume_upload(0, np.zeros(shape + (4,), f32))
+    state = mc.arbitrary_bits(shape, seed=42)
+    ctx.volume_upload(1, state)
+    sets = {}
+    for rule in (capi.POLY_EVEN_ODD, capi.POLY_UNION):
+        for flavour in (0, 1):
+            ctx.set_kernel_flavour(flavour)
+            res, cnt, state, r = check(ctx, desc(shape, CT, rule=rule), points, polygons, shape, state, what=(rule, flavour))
+            sets[rule] = r[0]
+            assert cnt[0] == 300 and (cnt[1] == 300 if flavour == 1 else cnt[1] > 250)
+    assert not (sets[capi.POLY_EVEN_ODD] & ~sets[capi.POLY_UNION]).any()
+    assert sets[capi.POLY_UNION].sum() > sets[capi.POLY_EVEN_ODD].sum() + 200  # (not vacuous: overlaps exist)
+
+
+def test_long_axis(ctx):
+    """65535 x 4 x 2: a polygon over x = 0 .. 65534 (1024 words in 16 chunks of 64, the last word partial) and one around x = 4095 / 4096."""
+    shape = (2, 4, 65535)
+    grid = ((2, 2), (0, 0))
+    F = rc.F
+    points, polygons = rc.flatten([(rc.place(rc.rect(-F(1, 2), F(1, 2), 65534 + F(1, 2), F(5, 2)), grid[1], grid[0]), 0, 0),
+                                   (rc.place(rc.rect(4094 + F(1, 2), -F(1, 2), 4096 + F(1, 2), 3 + F(1, 2)), grid[1], grid[0]), 1, 0)])
+    ctx.volume_upload(0, np.zeros(shape + (4,), f32))
+    state = np.zeros(shape + (4,), f32)
+    ctx.volume_upload(1, state)
+    for flavour in (0, 1):
+        ctx.set_kernel_flavour(flavour)
+        res, _, state, r = check(ctx, desc(shape, grid), points, polygons, shape, state, what=flavour)
+        assert res.as_tuple()[0] == (2 * 65535 + 2 * 4, (0, 0, 0), (65535, 4, 2))
+        assert r[0, 0, 1:3].all() and not r[0, 0, [0, 3]].any() and r[0, 1, :, 4095:4097].all() and r[0, 1].sum() == 8
+
+
+def test_outside_the_volume_and_the_ends_of_the_range(ctx):
+    """Polygons partly and wholly outside the volume, on slices -1 and nz, and coordinates at +-2^29 on a grid of spacing 2^20."""
+    shape = (5, 30, 70)
+    nz, ny, nx = shape
+    top = 1 << 29
+    grid = ((1 << 20, 1 << 20), (-top, top - 29 * (1 << 20)))  # (the centres reach x = -2^29 + 69 * 2^20 and y = 2^29)
+    far = [[(-top, -top), (top, -top), (top, top), (-top, top)],               # the whole range: covers every voxel but the top row
+           [(-top, top), (top, -top), (top, top)],                             # the range's diagonal
+           [(-top, -top), (-top + 7 * (1 << 20) + 3, top), (-top, top)]]        # a sliver along the left face
+    points, polygons = rc.flatten([(np.asarray(p, np.int64), z, 0) for z, p in enumerate(far)])
+    assert np.abs(points).max() == top
+    near = [(rc.rect(-9, -9, -2, 40), 3), (rc.rect(75, 2, 90, 9), 3), (rc.rect(2, 33, 9, 50), 3), (rc.rect(2, -50, 9, -1), 3),  # wholly outside
+            (rc.ngon(11, 68, 28, 9, 9), 3), (rc.ngon(7, 0, 0, 4, 4), 4),                                                     # partly
+            (rc.rect(1, 1, 9, 9), -1), (rc.rect(1, 1, 9, 9), nz)]
+    near_points, near_polygons = rc.flatten([(rc.place(p, CT[1], CT[0]), z, 0) for p, z in near])
+    ctx.volume_upload(0, np.zeros(shape + (4,), f32))
+    state = mc.arbitrary_bits(shape, seed=51)
+    ctx.volume_upload(1, state)
+    for flavour in (0, 1):
+        ctx.set_kernel_flavour(flavour)
+        res, cnt, state, r = check(ctx, desc(shape, grid), points, polygons, shape, state, what=("far", flavour))
+        assert r[0, 0, :ny - 1].all() and not r[0, 0, ny - 1].any() and 0 < r[0, 1].sum() < nx * ny and 0 < r[0, 2].sum() < 8 * ny
+        assert cnt == (3, 3, 0)
+        res, cnt, state, r = check(ctx, desc(shape, CT, combine=capi.MORPH_OR), near_points, near_polygons, shape, state, what=("near", flavour))
+        assert r[0, 3].any() and r[0, 4].any() and not r[0, 3, :19, :59].any() and not r[0, :3].any()
+        assert cnt[2] == (2 if flavour == 1 else 6)  # the two slices outside; the default form also skips the four that miss the box
+
+
+def test_combine_modes_and_placements(ctx):
+    """All four ways of storing on a destination of arbitrary bits, contours 0 and 2 written in one call while 1 and 3 keep their bits;
+    the destination another slot, the grid's own slot, and a fresh slot."""
+    shape = (21, 37, 70)
+    init = mc.arbitrary_bits(shape, seed=61)
+    points, polygons = edge_polygons(shape, CT)
+    polygons = [(f, n, z, 2 * k) for f, n, z, k in polygons]  # contours 0 and 2
+    box = ((5, 0, 2), (66, 37, 21))
+    for combine in COMBINES:
+        ctx.volume_upload(0, init)
+        ctx.volume_upload(1, init)
+        d = desc(shape, CT, box, contours=0b0101, combine=combine)
+        res, _, after, r = check(ctx, d, points, polygons, shape, init, what=("other slot", combine))
+        assert res.voxels[0] > 0 and res.voxels[2] > 0 and res.voxels[1] == res.voxels[3] == 0
+        assert np.array_equal(vt.bits(after[..., [1, 3]]), vt.bits(init[..., [1, 3]]))
+        if combine in (capi.MORPH_OR, capi.MORPH_ANDNOT):
+            assert np.array_equal(vt.bits(after[..., 0][~r[0]]), vt.bits(init[..., 0][~r[0]]))
+        _, _, same, _ = check(ctx, d.copy(dst_slot=0), points, polygons, shape, init, what=("the grid's slot", combine))
+        assert np.array_equal(vt.bits(same), vt.bits(after))
+        assert np.array_equal(vt.bits(ctx.volume_download(1, shape)), vt.bits(after))  # (slot 1 was not touched by the second call)
+        for flavour in (0, 1):
+            with capi.Context(W, H, 0) as fresh:
+                fresh.set_kernel_flavour(flavour)
+                fresh.volume_upload(0, init)
+                _, _, made, _ = check(fresh, d.copy(dst_slot=2), points, polygons, shape, None, what=("fresh", combine, flavour))
+                check(fresh, d.copy(dst_slot=2, rule=capi.POLY_UNION), points, polygons[:7], shape, made,
+                      what=("no longer fresh", combine, flavour))  # (REPLACE now stores zeros)
+
+
+def test_forms_and_layouts(ctx):
+    shape = (21, 37, 130)
+    init = mc.arbitrary_bits(shape, seed=71)
+    points, polygons = edge_polygons(shape, CT)
+    box = ((2, 1, 0), (128, 37, 20))
+    first = {}
+    for layout in (0, 3, 1):
+        ctx.set_volume_layout(layout)
+        ctx.volume_upload(0, init)
+        for rule in (capi.POLY_EVEN_ODD, capi.POLY_UNION):
+            for flavour in (0, 1):
+                ctx.set_kernel_flavour(flavour)
+                ctx.volume_upload(1, init)
+                res, cnt, after, _ = check(ctx, desc(shape, CT, box, contours=3, rule=rule, combine=capi.MORPH_OR), points, polygons, shape, init,
+                                           what=(layout, rule, flavour))
+                want = first.setdefault(rule, (res.as_tuple(), after, cnt[0]))
+                assert res.as_tuple() == want[0] and np.array_equal(vt.bits(after), vt.bits(want[1])) and cnt[0] == want[2]
+                assert cnt[2] == 4 if flavour == 1 else cnt[2] >= 4  # (the four polygons of slice 20)
+
+
+def test_everything_downstream_of_the_mask_is_fresh():
+    """After a raster into the mask slot of a VOLUME_MASK scene, a render and rows 1 .. 4 of a histogram equal what the same context
+    gives after vr_volume_upload of the expected mask; what the reporting calls say about earlier launches and tools stays."""
+    n = 16
+    variant = capi.VOLUME_MASK
+    vols, tfs = vt.scene(variant, n)
+    shape = vols[0].shape[:3]
+    step, count = hr.stepping_params(n, n, n)
+    u = hr.make_uniforms(W, H, steps_count=count, step_size=step)
+    hd = thg.desc(shape, volume_slot=2, mask_slot=0, rows=0b11110, bins=16, scale=16.0)
+    grid = rc.GRIDS[2]
+    points, polygons = rc.flatten([(rc.place(rc.ngon(13, 7.5, 7.5, 6.3, 5.1, phase=z), grid[1], grid[0]), z, 0) for z in range(2, 14)])
+    with capi.Context(W, H, 0) as ctx:
+        before_frame, _, _ = vt.gpu_render(ctx, variant, u, vols, tfs)
+        img = ctx.slice(ctx.slice_orthogonal(2, 2, n // 2, 3))
+        ctx.histogram(thg.desc(shape, volume_slot=2, bins=64, scale=64.0))
+
+        def reports():
+            return (ctx.counters(), ctx.last_kernel_flavour(), ctx.slice_counters(), ctx.hist_counters(), len(ctx.kernel_times()),
+                    ctx.grow_counters(), ctx.grow_timing(), ctx.morph_counters(), ctx.morph_timing(), ctx.dist_counters(), ctx.dist_timing())
+
+        earlier = reports()
+        d = ctx.polygons_whole(0, 0).copy(spacing=grid[0], origin=grid[1])
+        res, _, mask, r = check(ctx, d, points, polygons, shape, vols[0])
+        assert res.voxels[0] > 500 and not np.array_equal(r[0], mr_member(vols[0][..., 0]))
+        assert reports() == earlier
+        assert np.array_equal(vt.bits(ctx.download()[0]), vt.bits(before_frame))
+        assert np.array_equal(vt.bits(ctx.slice(ctx.slice_orthogonal(2, 2, n // 2, 3))), vt.bits(img))
+        ctx.render(variant)
+        frame = ctx.download()[0]
+        counts, rows = ctx.histogram(hd)
+        timing = ctx.polygons_timing()
+        assert len(timing) == 4 and all(t >= 0.0 for t in timing) and timing[3] > 0.0
+        # the same context after an upload of the expected mask
+        ctx.volume_upload(0, mask)
+        ctx.render(variant)
+        want = ctx.download()[0]
+        want_counts, want_rows = ctx.histogram(hd)
+    assert np.array_equal(vt.bits(frame), vt.bits(want))
+    assert not np.array_equal(vt.bits(frame), vt.bits(before_frame))  # (the new contour shows)
+    assert np.array_equal(counts, want_counts) and rows == want_rows and rows[1][0] == res.voxels[0]
+
+
+def mr_member(component):
+    return component != f32(0.0)
+
+
+def raw_desc(d, points, polygons, /, **over):
+    """The descriptor as mask_polygons would pass it, with fields replaced; the arrays are returned to keep them alive."""
+    pts, polys = capi.polygon_arrays(points, polygons)
+    full = d.copy(n_points=len(pts), n_polygons=len(polys), points=pts.ctypes.data, polygons=C.cast(polys, C.c_void_p).value)
+    return full.copy(**over), (pts, polys)
+
+
+def test_errors_leave_the_destination_untouched(ctx):
+    shape = thg.SMALL
+    nz, ny, nx = shape
+    grid_vol = mc.arbitrary_bits(shape, seed=81)
+    m = mc.arbitrary_bits(shape, seed=83)
+    ctx.volume_upload(0, grid_vol)
+    ctx.volume_upload(1, m)
+    ctx.volume_upload(2, np.zeros((4, 4, 4, 4), f32))
+    points, polygons = rc.flatten([(rc.place(rc.ngon(9, 11, 9, 8, 7), CT[1], CT[0]), 5, 0), (rc.place(rc.rect(2, 2, 20, 15), CT[1], CT[0]), 6, 3)])
+    good = desc(shape, CT, contours=0b1001)
+    _, _, m, _ = check(ctx, good, points, polygons, shape, m)
+    counters = ctx.polygons_counters()
+    assert counters == (2, 2, 0)
+    top = 1 << 29
+
+    def with_polygon(i, **edit):
+        p = [list(q) for q in polygons]
+        for k, v in edit.items():
+            p[i][dict(first=0, count=1, slice=2, contour=3)[k]] = v
+        return capi.polygon_arrays(points, p)[1]
+
+    def with_point(i, a, v):
+        p = points.copy()
+        p[i, a] = v
+        return p
+
+    keep = []
+    invalid = [dict(grid_slot=-1), dict(grid_slot=3), dict(dst_slot=-1), dict(dst_slot=3), dict(contours=0), dict(contours=16), dict(contours=-1),
+               dict(contours=0b0001),  # polygon 1's contour is not in it
+               dict(rule=-1), dict(rule=2), dict(combine=-1), dict(combine=4),
+               dict(box_lo=(-1, 0, 0)), dict(box_hi=(nx + 1, ny, nz)), dict(box_hi=(nx, ny, nz + 1)), dict(box_lo=(5, 0, 0), box_hi=(4, ny, nz)),
+               dict(spacing=(0, 977)), dict(spacing=(977, 0)), dict(spacing=((1 << 20) + 1, 977)), dict(spacing=(977, (1 << 20) + 1)),
+               dict(origin=(top + 1, 0)), dict(origin=(0, -top - 1)),
+               dict(dst_slot=2), dict(grid_slot=2, dst_slot=1),
+               dict(points=None), dict(polygons=None), dict(n_points=len(points) - 1),
+               dict(polygons=with_polygon(1, first=len(points) - 3)), dict(polygons=with_polygon(0, count=len(points) + 1)),
+               dict(polygons=with_polygon(0, first=0xFFFFFFFF, count=2)),
+               dict(polygons=with_polygon(0, contour=-1)), dict(polygons=with_polygon(0, contour=4)), dict(polygons=with_polygon(0, contour=1)),
+               dict(points=with_point(3, 0, top + 1)), dict(points=with_point(0, 1, -top - 1))]
+    for over in invalid:
+        for k in ("points", "polygons"):
+            if over.get(k) is not None:
+                keep.append(over[k])
+                over = {**over, k: over[k].ctypes.data if k == "points" else C.cast(over[k], C.c_void_p).value}
+        d, alive = raw_desc(good, points, polygons, **over)
+        assert ctx.lib.vr_mask_polygons(ctx.h, C.byref(d), C.byref(capi.PolygonsResult())) == capi.VR_ERR_INVALID_ARG, over
+        assert (ctx.lib.vr_last_error(ctx.h) or b"").decode().startswith("vr_mask_polygons"), over
+    d, alive = raw_desc(good, points, polygons)
+    assert ctx.lib.vr_mask_polygons(ctx.h, None, None) == capi.VR_ERR_INVALID_ARG
+    assert (ctx.lib.vr_last_error(ctx.h) or b"").decode().startswith("vr_mask_polygons")
+    assert ctx.lib.vr_mask_polygons(None, C.byref(d), None) == capi.VR_ERR_INVALID_ARG
+    assert ctx.lib.vr_polygons_counters(ctx.h, None) == capi.VR_ERR_INVALID_ARG
+    assert ctx.lib.vr_polygons_timing(ctx.h, None) == capi.VR_ERR_INVALID_ARG
+    assert ctx.polygons_counters() == counters
+    assert np.array_equal(vt.bits(ctx.volume_download(1, shape)), vt.bits(m))
+    assert np.array_equal(vt.bits(ctx.volume_download(0, shape)), vt.bits(grid_vol))
+    assert np.array_equal(vt.bits(ctx.volume_download(2, (4, 4, 4))), np.zeros((4, 4, 4, 4), np.uint32))
+    with capi.Context(W, H, 0) as empty:
+        assert empty.polygons_counters() == (0, 0, 0) and empty.polygons_timing() == (0.0, 0.0, 0.0, 0.0)
+        assert empty.lib.vr_mask_polygons(empty.h, C.byref(d), None) == capi.VR_ERR_NOT_READY
+        err = empty.lib.vr_last_error(empty.h)
+        assert err.startswith(b"vr_mask_polygons") and b"empty" in err
+        assert empty.lib.vr_polygons_whole(empty.h, 0, 1, C.byref(capi.PolygonsDesc())) == capi.VR_ERR_NOT_READY
+        with pytest.raises(capi.VrError):  # the destination slot was not created by the failed call
+            empty.volume_download(1, shape)
+    # vr_polygons_whole
+    w = ctx.polygons_whole(0, 1)
+    assert bytes(w) == bytes(desc(shape))
+    for bad in ((3, 0), (-1, 0), (0, 3), (0, -1)):
+        assert ctx.lib.vr_polygons_whole(ctx.h, *bad, C.byref(capi.PolygonsDesc())) == capi.VR_ERR_INVALID_ARG, bad
+    assert ctx.lib.vr_polygons_whole(ctx.h, 0, 1, None) == capi.VR_ERR_INVALID_ARG
+    # a NULL result is fine; no polygons is legal, and REPLACE then clears the box
+    assert ctx.lib.vr_mask_polygons(ctx.h, C.byref(d), None) == capi.VR_OK
+    assert ctx.polygons_counters() == counters
+    box = ((3, 2, 1), (20, 17, 9))
+    res, cnt, after, _ = check(ctx, desc(shape, CT, box, contours=0b1001), [], [], shape, m, what="no polygons")
+    assert cnt == (0, 0, 0) and res.as_tuple() == ((0, (0, 0, 0), (0, 0, 0)),) * 4
+    assert not after[1:9, 2:17, 3:20][..., [0, 3]].any() and after[..., [0, 3]].any()
+    # NULL pointers are fine where the counts are zero
+    d0 = desc(shape, CT, box)
+    assert ctx.lib.vr_mask_polygons(ctx.h, C.byref(d0), None) == capi.VR_OK
+
+
+SWEEP = rc.sweep(40)
+
+
+@pytest.mark.parametrize("i", range(40))
+def test_random_sweep(i):
+    case = SWEEP[i]
+    shape = case["shape"]
+    grid_vol = mc.arbitrary_bits(shape, seed=case["seed"])
+    other = mc.arbitrary_bits(shape, seed=case["seed"] + 1)
+    with capi.Context(W, H, 0) as c:
+        c.set_kernel_flavour(i % 2)
+        c.volume_upload(case["grid_slot"], grid_vol)
+        before = grid_vol
+        if case["dst_slot"] != case["grid_slot"]:
+            before = None if case["fresh"] else other
+            if not case["fresh"]:
+                c.volume_upload(case["dst_slot"], other)
+        d = capi.PolygonsDesc().copy(grid_slot=case["grid_slot"], dst_slot=case["dst_slot"], contours=case["contours"], rule=case["rule"],
+                                     combine=case["combine"], box_lo=case["box_lo"], box_hi=case["box_hi"], origin=case["origin"],
+                                     spacing=case["spacing"])
+        check(c, d, case["points"], case["polygons"], shape, before, what=i)
+
+
+def test_application_contours_to_mask(tmp_path):
+    """ContoursToMask on a grid of 0.977 x 0.977 x 2.5 mm read from (synthetic) DICOM, the structures read from a (synthetic) RTSTRUCT
+    in patient millimetres: the restatement on the micrometre conversion, all structures in one call."""
+    import dicom_writer as dw
+    from volumerendering_amd import host, synth
+    n, nz = 40, 12
+    raw = synth.ct_phantom_raw(n)[:nz]
+    d = tmp_path / "ct"
+    d.mkdir()
+    x0, y0, z0 = -19.5, -12.25, 10.0
+    for k in range(nz):
+        dw.write_slice(str(d / f"{k:03d}.dcm"), raw[k], rows=n, cols=n, instance=k + 1, position=(x0, y0, z0 + 2.5 * k), spacing=(0.977, 0.977),
+                       thickness=2.5, largest=int(raw.max()), frame_uid="1.2.840.7")
+    grid = host.VolumeFile.from_dicom(str(d))
+    p = grid.dicom_params()
+    assert tuple(p["PixelSpacing"]) == (0.977, 0.977) and p["SliceThickness"] == 2.5 and tuple(p["ImagePositionPatient"]) == (x0, y0, z0)
+    shape = (nz, n, n)
+
+    def mm(voxel_points, k):  # a polygon in patient millimetres on slice k, flat x y z ...
+        return [v for vx, vy in voxel_points for v in (x0 + 0.977 * float(vx), y0 + 0.977 * float(vy), z0 + 2.5 * k)]
+
+    body = [mm(rc.ngon(40, 20, 19, 16.3, 14.2, phase=0.3 * k), k) for k in range(1, 11)]
+    ring = [mm(rc.rect(5.4, 6.2, 33.3, 30.9), k) for k in (3, 4, 5)] + [mm(rc.ngon(12, 19, 18, 7.7, 6.1), k) for k in (3, 4, 5)]
+    cord = [mm(rc.ngon(8, 30, 30, 3.2, 3.2), k) for k in range(0, 12)] + [[1.0, 2.0, z0]]  # (a single point: covers nothing)
+    contours = [body, ring, cord, [mm(rc.rect(0, 0, 1, 1), 0)]]  # (the last structure of a file cannot be selected: Create3DMask's rule)
+    path = str(tmp_path / "rs.dcm")
+    dw.write_rtstruct(path, contours, frame_uid="1.2.840.7")
+    structures = host.StructureFile.read(path)
+    assert structures is not None
+
+    # the restatement's inputs: float32 millimetres (what the file reader keeps) to micrometres in double, slices from the first point
+    ids = [2, 0, 3, 1]  # channel 0 = ring, 1 = cord, 2 = body
+    polys = []
+    for channel, i in enumerate(j for j in ids if j):
+        for poly in structures.contours()[i - 1]:
+            if len(poly) < 3:
+                continue
+            q = np.asarray(poly[:len(poly) // 3 * 3], f32).reshape(-1, 3)
+            t = q[:, :2].astype(np.float64) * 1000.0
+            um = (np.sign(t) * np.floor(np.abs(t) + 0.5)).astype(np.int64)  # (llround: halves away from zero)
+            k = int(np.round(np.abs((q[0, 2] - f32(z0)) / f32(2.5))))
+            polys.append((um, k, channel))
+    points, polygons = rc.flatten(polys)
+    origin = (int(round(x0 * 1000.0)), int(round(y0 * 1000.0)))
+    with host.Application(W, H, 0) as app:
+        app.OnStart(capi.BASIC, [grid])
+        c = app.context()
+        results = {}
+        for rule in (capi.POLY_EVEN_ODD, capi.POLY_UNION):
+            res = app.contours_to_mask(structures, ids, grid, 1, rule)
+            got = c.volume_download(1, shape)
+            want, result, r = rr.raster(shape, None, points, polygons, origin, (977, 977), 0b0111, rule, rr.REPLACE, *mc.whole(shape))
+            assert np.array_equal(vt.bits(got), vt.bits(want)) and res.as_tuple() == result
+            cnt = c.polygons_counters()
+            assert cnt[0] == len(polygons) == 29 and cnt[1] + cnt[2] == cnt[0]
+            results[rule] = res.as_tuple()
+        assert all(results[0][k][0] > 0 for k in range(3)) and results[0][3][0] == 0
+        assert results[0][0][0] < results[1][0][0] and results[0][1:] == results[1][1:]  # (the ring's hole is filled under UNION)
+        # RasterPolygons is vr_mask_polygons on the application's context
+        dsc = c.polygons_whole(0, 2).copy(origin=origin, spacing=(977, 977), contours=0b0111, rule=capi.POLY_UNION)
+        res2 = app.raster_polygons(dsc, points, polygons)
+        assert np.array_equal(vt.bits(c.volume_download(2, shape)), vt.bits(c.volume_download(1, shape))) and res2.as_tuple() == results[1]
+        res3 = c.mask_polygons(dsc.copy(rule=capi.POLY_EVEN_ODD), points, polygons)
+        assert res3.as_tuple() == results[0]
+        # no selectable structure, another frame of reference, a grid without DICOM parameters
+        with pytest.raises(capi.VrError) as e:
+            app.contours_to_mask(structures, [0, 4, 9, 0], grid, 1)
+        assert e.value.code == capi.VR_ERR_INVALID_ARG
+        other = host.StructureFile.from_contours(contours, frame_of_reference="9.9.9")
+        with pytest.raises(capi.VrError) as e:
+            app.contours_to_mask(other, ids, grid, 1)
+        assert e.value.code == capi.VR_ERR_INVALID_ARG
+        raw_grid = host.VolumeFile.from_raw(raw)  # (not read from DICOM: no spacing)
+        with pytest.raises(capi.VrError):
+            app.contours_to_mask(structures, ids, raw_grid, 1)

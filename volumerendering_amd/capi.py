@@ -42,6 +42,8 @@ MORPH_MAX_RADIUS = 31                            # vr_morph_element (include/vr.
 MORPH_NONE, MORPH_DILATE, MORPH_ERODE, MORPH_CLOSE, MORPH_OPEN = range(5)   # vr_morph_desc.op
 MORPH_REPLACE, MORPH_OR, MORPH_AND, MORPH_ANDNOT = range(4)                 # vr_morph_desc.combine
 DIST_OUTSIDE, DIST_INSIDE, DIST_SIGNED = range(3)                           # vr_dist_desc.mode (include/vr.h)
+POLY_EVEN_ODD, POLY_UNION = 0, 1                                            # vr_polygons_desc.rule (include/vr.h)
+POLY_MAX_COORD, POLY_MAX_SPACING = 1 << 29, 1 << 20                         # of a point coordinate or origin value (magnitude), a spacing
 DIST_MAX_SPACING, DIST_MAX_LIMIT, DIST_MAX_EXTENT = 1 << 20, 1 << 31, 1 << 30  # of a spacing, the limit, (hi - lo) * spacing per axis
 
 # every symbol include/vr.h declares (tests check that the library exports each of them)
@@ -64,6 +66,7 @@ ABI_SYMBOLS = [
     "vr_grow_whole", "vr_segment_grow", "vr_grow_counters", "vr_grow_timing",
     "vr_morph_ball", "vr_morph_box", "vr_morph_whole", "vr_mask_morph", "vr_morph_counters", "vr_morph_timing",
     "vr_dist_whole", "vr_mask_distance", "vr_dist_counters", "vr_dist_timing",
+    "vr_polygons_whole", "vr_mask_polygons", "vr_polygons_counters", "vr_polygons_timing",
 ]
 
 
@@ -239,6 +242,43 @@ class DistResult(C.Structure):
                 int(self.probe_voxels), int(self.probe_min_sq), int(self.probe_max_sq))
 
 
+class Polygon(C.Structure):
+    """struct vr_polygon (include/vr.h): points[first .. first + count) on slice `slice`, for contour `contour`."""
+    _fields_ = [("first", C.c_uint32), ("count", C.c_uint32), ("slice", C.c_int32), ("contour", C.c_int32)]
+
+
+class PolygonsDesc(C.Structure):
+    """struct vr_polygons_desc (include/vr.h): the grid and destination slots, the contours written, the rule, the way the result is
+    stored, the voxel box, the grid's origin and spacing, and the points and polygons (set by Context.mask_polygons)."""
+    _fields_ = [
+        ("grid_slot", C.c_int32), ("dst_slot", C.c_int32), ("contours", C.c_int32), ("rule", C.c_int32), ("combine", C.c_int32),
+        ("box_lo", C.c_int32 * 3), ("box_hi", C.c_int32 * 3), ("origin", C.c_int32 * 2), ("spacing", C.c_uint32 * 2),
+        ("n_points", C.c_uint32), ("n_polygons", C.c_uint32), ("points", C.c_void_p), ("polygons", C.c_void_p),
+    ]
+
+    def copy(self, **over) -> "PolygonsDesc":
+        """A copy with the given fields replaced (box_lo / box_hi from any sequence of three integers, origin / spacing of two)."""
+        d = PolygonsDesc.from_buffer_copy(bytes(self))
+        for k, v in over.items():
+            if k in ("box_lo", "box_hi"):
+                v = (C.c_int32 * 3)(*[int(x) for x in v])
+            if k == "origin":
+                v = (C.c_int32 * 2)(*[int(x) for x in v])
+            if k == "spacing":
+                v = (C.c_uint32 * 2)(*[int(x) for x in v])
+            setattr(d, k, v)
+        return d
+
+
+class PolygonsResult(C.Structure):
+    """struct vr_polygons_result: per contour |R_k| and its half-open bounding box (zeros when empty or not written)."""
+    _fields_ = [("voxels", C.c_uint64 * 4), ("lo", (C.c_int32 * 3) * 4), ("hi", (C.c_int32 * 3) * 4)]
+
+    def as_tuple(self):
+        """((voxels, lo, hi) of contour 0, ... of contour 3)"""
+        return tuple((int(self.voxels[k]), tuple(int(x) for x in self.lo[k]), tuple(int(x) for x in self.hi[k])) for k in range(4))
+
+
 class VrError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"vr error {code}: {msg}")
@@ -338,6 +378,10 @@ def load() -> C.CDLL:
     lib.vr_mask_distance.argtypes = [vp, C.POINTER(DistDesc), C.POINTER(DistResult)]
     lib.vr_dist_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
     lib.vr_dist_timing.argtypes = [vp, C.POINTER(C.c_float * 4)]
+    lib.vr_polygons_whole.argtypes = [vp, i32, i32, C.POINTER(PolygonsDesc)]
+    lib.vr_mask_polygons.argtypes = [vp, C.POINTER(PolygonsDesc), C.POINTER(PolygonsResult)]
+    lib.vr_polygons_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
+    lib.vr_polygons_timing.argtypes = [vp, C.POINTER(C.c_float * 4)]
     lib.vr_present_async.argtypes = [vp, vp, vp, vp]
     lib.vr_present_tiles_async.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
     lib.vr_hint_frames_in_flight.argtypes = [vp, i32]
@@ -758,6 +802,35 @@ class Context:
         self._chk(self.lib.vr_dist_timing(self.h, C.byref(out)))
         return tuple(float(x) for x in out)
 
+    def polygons_whole(self, grid_slot: int, dst_slot: int) -> PolygonsDesc:
+        """vr_polygons_whole: the descriptor of a raster over the whole grid (contour 0, EVEN_ODD, REPLACE, origin 0, unit spacing)."""
+        d = PolygonsDesc()
+        self._chk(self.lib.vr_polygons_whole(self.h, grid_slot, dst_slot, C.byref(d)))
+        return d
+
+    def mask_polygons(self, desc: PolygonsDesc, points, polygons) -> PolygonsResult:
+        """vr_mask_polygons: rasterises closed polygons into contours of a mask slot (synchronous).  points: int32 (n, 2) pairs x, y in
+        the descriptor's unit; polygons: a sequence of (first, count, slice, contour).  The descriptor's own points / polygons fields
+        are ignored."""
+        pts, polys = polygon_arrays(points, polygons)
+        d = desc.copy(n_points=len(pts), n_polygons=len(polys), points=pts.ctypes.data if len(pts) else None,
+                      polygons=C.cast(polys, C.c_void_p).value if len(polys) else None)
+        out = PolygonsResult()
+        self._chk(self.lib.vr_mask_polygons(self.h, C.byref(d), C.byref(out)))  # (pts and polys live until here)
+        return out
+
+    def polygons_counters(self):
+        """(polygons given, polygons rasterised, polygons skipped) of the last mask_polygons."""
+        out = (C.c_uint64 * 3)()
+        self._chk(self.lib.vr_polygons_counters(self.h, C.byref(out)))
+        return tuple(int(x) for x in out)
+
+    def polygons_timing(self):
+        """(upload, raster, write, refresh) of the last mask_polygons in ms of device time (vr_polygons_timing)."""
+        out = (C.c_float * 4)()
+        self._chk(self.lib.vr_polygons_timing(self.h, C.byref(out)))
+        return tuple(float(x) for x in out)
+
     def set_volume_layout(self, mode: int):
         """0 bricked copy (default), 1 the reference's vec4 voxels only, 3 x-fastest voxels + density plane (2 was removed)."""
         self._chk(self.lib.vr_set_volume_layout(self.h, mode))
@@ -770,6 +843,13 @@ class Context:
 
     def set_kernel_flavour(self, flavour: int):
         self._chk(self.lib.vr_set_kernel_flavour(self.h, flavour))
+
+
+def polygon_arrays(points, polygons):
+    """(a contiguous int32 (n, 2) array, a ctypes array of Polygon) for vr_polygons_desc.points / .polygons."""
+    pts = np.ascontiguousarray(np.asarray(points, dtype=np.int32).reshape(-1, 2))
+    polys = (Polygon * len(polygons))(*[Polygon(int(f), int(n), int(z), int(k)) for f, n, z, k in polygons])
+    return pts, polys
 
 
 def morph_ball(spacing, radius: int) -> MorphElement:

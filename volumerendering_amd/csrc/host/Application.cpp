@@ -213,6 +213,69 @@ int Application::DistanceMm(int srcSlot, int srcContour, int dstSlot, int dstCha
     return DistanceMap(d, out);
 }
 
+int Application::RasterPolygons(const vr_polygons_desc& desc, vr_polygons_result* out)
+{
+    if (!p_Ctx) return VR_ERR_NOT_READY;
+    const int rc = vr_mask_polygons(p_Ctx, &desc, out);
+    if (rc != VR_OK) m_Error = vr_last_error(p_Ctx);
+    return rc;
+}
+
+int Application::ContoursToMask(const StructureFileDcm& structures, std::array<int, 4> contourIDs, const VolumeFileDcm& grid, int dstSlot,
+                                int rule, vr_polygons_result* out)
+{
+    if (!p_Ctx) return VR_ERR_NOT_READY;
+    if (!structures.CompareFrameOfReference(grid)) return VR_ERR_INVALID_ARG;
+    const DicomVolumeParams p = grid.GetVolumeParams();
+    // whole micrometres within the range of vr_mask_polygons, or false
+    auto um = [](double mm, int32_t* v) {
+        if (!std::isfinite(mm) || std::fabs(mm) * 1000.0 > (double)(1 << 29)) return false;
+        *v = (int32_t)std::llround(mm * 1000.0);
+        return true;
+    };
+    vr_polygons_desc d;
+    int rc = vr_polygons_whole(p_Ctx, 0, dstSlot, &d);
+    if (rc != VR_OK) return rc;
+    const auto [xSize, ySize, zSize] = grid.GetSize();
+    if ((int)xSize != d.box_hi[0] || (int)ySize != d.box_hi[1] || (int)zSize != d.box_hi[2]) return VR_ERR_INVALID_ARG;
+    int32_t pitch[2];
+    for (int a = 0; a < 2; ++a) {
+        if (!um(p.ImagePositionPatient[a], &d.origin[a]) || !um(p.PixelSpacing[a], &pitch[a]) || pitch[a] <= 0) return VR_ERR_INVALID_ARG;
+        d.spacing[a] = (uint32_t)pitch[a];
+    }
+    const auto& data = structures.GetContourData();
+    std::vector<int32_t> points;
+    std::vector<vr_polygon> polygons;
+    int channels = 0;
+    for (int id : contourIDs) {
+        if (!(id > 0 && static_cast<size_t>(id) < data.size())) continue;
+        for (const std::vector<float>& polygon : data[static_cast<size_t>(id - 1)]) {
+            if (polygon.size() < 3) continue;
+            vr_polygon g;
+            g.first = (uint32_t)(points.size() / 2);
+            g.count = (uint32_t)(polygon.size() / 3);
+            g.slice = (int32_t)ContourSliceNumber(polygon[2], static_cast<float>(p.ImagePositionPatient[2]), static_cast<float>(p.SliceThickness));
+            g.contour = channels;
+            for (size_t j = 0; j + 3 <= polygon.size(); j += 3) {
+                int32_t xy[2];
+                if (!um((double)polygon[j], &xy[0]) || !um((double)polygon[j + 1], &xy[1])) return VR_ERR_INVALID_ARG;
+                points.push_back(xy[0]);
+                points.push_back(xy[1]);
+            }
+            polygons.push_back(g);
+        }
+        ++channels;
+    }
+    if (channels == 0) return VR_ERR_INVALID_ARG;
+    d.contours = (1 << channels) - 1;
+    d.rule = rule;
+    d.n_points = (uint32_t)(points.size() / 2);
+    d.n_polygons = (uint32_t)polygons.size();
+    d.points = points.data();
+    d.polygons = polygons.data();
+    return RasterPolygons(d, out);
+}
+
 int Application::Pick(uint32_t x, uint32_t y, vr_pick_result* out)
 {
     if (!p_Ctx || !p_App) return VR_ERR_NOT_READY;

@@ -3,6 +3,7 @@
 // (App/src/Application.h / Application.cpp: OnStart :58-94, OnUpdate :96-119, OnRender :121-239,
 // OnResize :299-323) without the window, the event queue and the ImGui layer.
 #pragma once
+#include <array>
 #include <cstdint>
 #include <memory>
 #include <string>
@@ -10,6 +11,7 @@
 
 #include "Camera.h"
 #include "MiniApp.h"
+#include "dicom/StructureFileDcm.h"
 #include "dicom/VolumeFileDcm.h"
 #include "vr.h"
 
@@ -84,6 +86,18 @@ public:
     // is not positive, or a volume longer than 2^30 micrometres on some axis.
     int DistanceMm(int srcSlot, int srcContour, int dstSlot, int dstChannel, int mode, float limitMm, const VolumeFileDcm& grid,
                    vr_dist_result* out);
+    // Closed planar polygons rasterised into contours of a mask volume on the device (vr_mask_polygons of include/vr.h): a descriptor
+    // passed through.  `out` may be nullptr.
+    int RasterPolygons(const vr_polygons_desc& desc, vr_polygons_result* out);
+    // The structures contourIDs of an RTSTRUCT file as the contours of volume dstSlot, on the voxel grid of `grid` (a volume read from
+    // DICOM in the same frame of reference; volume slot 0, the scene's first volume, holds it or one of its size): ONE vr_mask_polygons
+    // with VR_MORPH_REPLACE over the whole grid, so one rebuild.  Channel l comes from the l-th accepted id as in StructureFileDcm::Create3DMask (ids are 1-based;
+    // 0 and anything >= the number of structures are ignored).  Patient millimetres become whole micrometres by llround(v * 1000.0) in
+    // double -- the points' x and y, ImagePositionPatient x / y and PixelSpacing -- and a polygon lies on the slice ContourSliceNumber gives
+    // for its first point.  rule = VR_POLY_EVEN_ODD / VR_POLY_UNION.  VR_ERR_INVALID_ARG for another frame of reference, no accepted id,
+    // a spacing that is not positive, a coordinate beyond 2^29 micrometres or a volume 0 of another size than `grid`.
+    int ContoursToMask(const StructureFileDcm& structures, std::array<int, 4> contourIDs, const VolumeFileDcm& grid, int dstSlot, int rule,
+                       vr_polygons_result* out);
     // the accumulated opacity at which the unlit / lit scene's surface lies (vr_set_surface_threshold: finite, 0 <= tau < 1)
     int SetSurfaceThreshold(float tau);
 

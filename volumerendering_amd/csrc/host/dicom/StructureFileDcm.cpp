@@ -183,7 +183,7 @@ std::shared_ptr<VolumeFileDcm> StructureFileDcm::Create3DMask(const IDicomFile& 
             for (size_t j = 0; j + 3 <= polygon.size(); j += 3) {
                 const vrm::vec3 point{polygon[j], polygon[j + 1], polygon[j + 2]};
                 vrm::vec3 voxel = toVoxel(point);
-                voxel.z = std::fabs(voxel.z);
+                voxel.z = ContourSliceNumber(point.z, origin.z, spacing.z);
                 voxel = RoundHalfAway(voxel);
                 const int vx = static_cast<int>(voxel.x), vy = static_cast<int>(voxel.y), vz = static_cast<int>(voxel.z);
                 sliceNumber = vz;

@@ -4,6 +4,7 @@
 // (mark / line / morphology / seed / fill) instead of the reference's one long loop.
 #pragma once
 #include <array>
+#include <cmath>
 #include <filesystem>
 #include <memory>
 #include <vector>
@@ -26,6 +27,10 @@ inline ContourPostProcess operator|(ContourPostProcess a, ContourPostProcess b)
 {
     return static_cast<ContourPostProcess>(static_cast<unsigned>(a) | static_cast<unsigned>(b));
 }
+
+// The slice a contour point lies on: its z against the first slice's, in slice thicknesses, the sign dropped and rounded half away from
+// zero, all in float (StructureFileDcm.cpp:105-125).  What Create3DMask marks and what Application::ContoursToMask rasterises into.
+inline float ContourSliceNumber(float z, float firstSliceZ, float sliceThickness) { return std::round(std::fabs((z - firstSliceZ) / sliceThickness)); }
 
 class StructureFileDcm : public IDicomFile {
 public:

@@ -421,6 +421,23 @@ int vrh_app_margin_mm(void* a, int src_slot, int src_contour, int dst_slot, int 
     if (!vh || !vh->dcm) return VR_ERR_INVALID_ARG;
     VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->MarginMm(src_slot, src_contour, dst_slot, dst_contour, mm, *vh->dcm, out); })
 }
+// Application::RasterPolygons and Application::ContoursToMask (vr_mask_polygons of the application's context); structures: from
+// vrh_struct_read / vrh_struct_from_contours, grid: as vrh_app_margin_mm's
+int vrh_app_raster_polygons(void* a, const vr_polygons_desc* desc, vr_polygons_result* out)
+{
+    if (!desc) return VR_ERR_INVALID_ARG;
+    VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->RasterPolygons(*desc, out); })
+}
+int vrh_app_contours_to_mask(void* a, void* structures, const int ids[4], void* grid, int dst_slot, int rule, vr_polygons_result* out)
+{
+    auto* vh = static_cast<VolumeHandle*>(grid);
+    if (!structures || !ids || !vh || !vh->dcm) return VR_ERR_INVALID_ARG;
+    const std::array<int, 4> four{ids[0], ids[1], ids[2], ids[3]};
+    VRH_TRY(VR_ERR_HIP, {
+        return static_cast<Application*>(a)->ContoursToMask(**static_cast<std::shared_ptr<StructureFileDcm>*>(structures), four, *vh->dcm, dst_slot,
+                                                            rule, out);
+    })
+}
 // Application::DistanceMap and Application::DistanceMm (vr_mask_distance of the application's context); grid: as vrh_app_margin_mm's
 int vrh_app_distance_map(void* a, const vr_dist_desc* desc, vr_dist_result* out)
 {

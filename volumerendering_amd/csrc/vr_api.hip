@@ -13,6 +13,8 @@
 #include "vr_morph.h"
 // Distance maps (vr_mask_distance): exact integer work on the same bit-rows, compiled once as well
 #include "vr_dist.h"
+// Polygon rasterisation (vr_mask_polygons): exact integer work on the same bit-rows, compiled once as well
+#include "vr_raster.h"
 
 // the same dispatch over the kernels compiled with fused multiply-adds (vr_fused.hip)
 namespace vrf {
@@ -43,6 +45,7 @@ using namespace vr;
 #include "vr_api_segment.h"
 #include "vr_api_morph.h"
 #include "vr_api_dist.h"
+#include "vr_api_raster.h"
 
 namespace {
 

@@ -189,6 +189,17 @@ struct DistState {
     ToolReport report;                   // phases: pack, distance passes, write, refresh_bricks
 };
 
+// Polygon rasterisation (vr_mask_polygons, vr_raster.h): the working buffers of the last call, grown on demand; what
+// vr_polygons_counters and vr_polygons_timing report.
+struct RasterState {
+    DevBuf<unsigned long long> words;    // four bit-row buffers: R_k of every contour
+    DevBuf<unsigned char> d_stage;       // the points, the polygons that are rasterised and the work items, one behind the other ...
+    PinnedBuf<unsigned char> h_stage;    // ... and where the host puts them together
+    DevBuf<RasterWords> d_words;         // the counts and bounding boxes ...
+    PinnedBuf<RasterWords> h_words;      // ... and where the host sets and reads them
+    ToolReport report;                   // phases: upload, raster, write, refresh_bricks
+};
+
 // What the reporting calls (vr_last_counters, vr_last_kernel_flavour, vr_last_timing, vr_kernel_times, vr_kernel_choice,
 // vr_download_tiles, vr_last_block_trace) read about the most recent march launch.  vr_pick copies it out and back as one value.
 struct LastLaunch {
@@ -379,6 +390,7 @@ struct vr_ctx {
     GrowState grow;  // region growing (vr_segment_grow)
     MorphState morph;  // mask morphology (vr_mask_morph)
     DistState dist;    // distance maps (vr_mask_distance)
+    RasterState raster;  // polygon rasterisation (vr_mask_polygons)
     std::string err;
 };
 

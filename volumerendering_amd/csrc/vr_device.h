@@ -288,6 +288,35 @@ struct DistParams {
     DistWords* w;
 };
 
+// One polygon of a vr_mask_polygons as the raster kernel reads it (vr_raster.h).
+struct RasterPoly {
+    unsigned first, count;  // its points: pts[first .. first + count)
+    int slice, contour;
+    int s0, s1;             // the voxels of a row it can set, within the box along x: [s0, s1), s0 < s1
+};
+// One work item of the raster kernel: `rows` rows from row j0 of polygon `poly`.
+struct RasterItem {
+    unsigned poly;
+    unsigned short j0, rows;
+};
+// The device words of one vr_mask_polygons: |R_k| and its bounding box per contour (each starts as CountBox::empty()).
+struct RasterWords {
+    CountBox r[4];
+};
+// Kernel argument block of a vr_mask_polygons (vr_raster.h; vr_polygons_desc of include/vr.h): passed by value.
+struct RasterParams {
+    MorphParams m;                 // the box walk of the write: dst, nx, ny, nz, wx, lo, hi, bw0, bw, box_words, combine, fresh
+    unsigned long long* bits[4];   // the bit-rows R_k (wx * ny * nz words each, zeroed before the raster)
+    int contours;                  // bit k: contour k is written
+    long long ox, oy;              // the centre of voxel (0, 0)
+    long long sx, sy;              // the voxel pitch
+    const int2* pts;
+    const RasterPoly* polys;
+    const RasterItem* items;
+    unsigned n_items;
+    RasterWords* w;
+};
+
 // Work queue of the persistent-wavefront kernel (vr_pw.h): eight heads, one per class of the workgroup index modulo 8,
 // zero at launch; heads[c * 64] counts the items of class c handed out beyond every wavefront's first.
 struct PwQueue {

@@ -68,6 +68,8 @@ def load() -> C.CDLL:
         "vrh_app_grow_from_pick": (i32, [vp, C.POINTER(capi.PickResult), i32, i32, i32, f32, f32, i32, C.POINTER(capi.GrowResult)]),
         "vrh_app_morph_contour": (i32, [vp, C.POINTER(capi.MorphDesc), C.POINTER(capi.MorphResult)]),
         "vrh_app_margin_mm": (i32, [vp, i32, i32, i32, i32, f32, vp, C.POINTER(capi.MorphResult)]),
+        "vrh_app_raster_polygons": (i32, [vp, C.POINTER(capi.PolygonsDesc), C.POINTER(capi.PolygonsResult)]),
+        "vrh_app_contours_to_mask": (i32, [vp, vp, C.POINTER(C.c_int * 4), vp, i32, i32, C.POINTER(capi.PolygonsResult)]),
         "vrh_app_distance_map": (i32, [vp, C.POINTER(capi.DistDesc), C.POINTER(capi.DistResult)]),
         "vrh_app_distance_mm": (i32, [vp, i32, i32, i32, i32, i32, f32, vp, C.POINTER(capi.DistResult)]),
         "vrh_app_slice": (i32, [vp, C.POINTER(capi.SliceDesc), vp]),
@@ -532,6 +534,26 @@ class Application:
         volume read from DICOM: its PixelSpacing and SliceThickness), stored as contour dst_contour of volume dst_slot."""
         out = capi.MorphResult()
         self._chk(self.lib.vrh_app_margin_mm(self.h, src_slot, src_contour, dst_slot, dst_contour, mm, grid.h, C.byref(out)))
+        return out
+
+    def raster_polygons(self, desc: capi.PolygonsDesc, points, polygons) -> capi.PolygonsResult:
+        """Application::RasterPolygons: vr_mask_polygons (include/vr.h) on the application's context; points and polygons as
+        capi.Context.mask_polygons takes them."""
+        pts, polys = capi.polygon_arrays(points, polygons)
+        d = desc.copy(n_points=len(pts), n_polygons=len(polys), points=pts.ctypes.data if len(pts) else None,
+                      polygons=C.cast(polys, C.c_void_p).value if len(polys) else None)
+        out = capi.PolygonsResult()
+        self._chk(self.lib.vrh_app_raster_polygons(self.h, C.byref(d), C.byref(out)))  # (pts and polys live until here)
+        return out
+
+    def contours_to_mask(self, structures: "StructureFile", contour_ids, grid: "VolumeFile", dst_slot: int,
+                         rule: int = capi.POLY_EVEN_ODD) -> capi.PolygonsResult:
+        """Application::ContoursToMask: the structures contour_ids (1-based, as create_3d_mask takes them) of an RTSTRUCT file rasterised
+        in one call into the contours of volume dst_slot, on the voxel grid of `grid` (a volume read from DICOM in the same frame of
+        reference; volume 0 holds it), REPLACE over the whole grid."""
+        ids = (C.c_int * 4)(*(list(contour_ids) + [0, 0, 0, 0])[:4])
+        out = capi.PolygonsResult()
+        self._chk(self.lib.vrh_app_contours_to_mask(self.h, structures.h, C.byref(ids), grid.h, dst_slot, rule, C.byref(out)))
         return out
 
     def distance_map(self, desc: capi.DistDesc) -> capi.DistResult:
