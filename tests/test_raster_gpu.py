@@ -490,3 +490,89 @@ def test_application_contours_to_mask(tmp_path):
         raw_grid = host.VolumeFile.from_raw(raw)  # (not read from DICOM: no spacing)
         with pytest.raises(capi.VrError):
             app.contours_to_mask(structures, ids, raw_grid, 1)
+
+
+def scratch_sequence_inputs():
+    """The three calls of test_shared_bit_row_scratch_keeps_no_stale_words and what the restatements say of them: per tool (call, the
+    uploads by slot, the shape of the destination, the destination after the call, the result, out[0], the bit-row buffers the call
+    leaves as boolean (nz, ny, nx) sets).  Slot 0 is the grid or the source, slot 1 the destination, slot 2 the probe."""
+    import dist_cases as dc
+    import dist_ref as dr
+    import morph_ref as mr
+    big, small = dc.WIDE, (6, 9, 70)  # 130 x 37 x 21: three words per row, the last partial; 70 x 9 x 6: two
+    out = {}
+    # all four contours on every slice of the big grid
+    polys = []
+    for z in range(big[0]):
+        polys.append((rc.place(rc.ngon(17, 65 + z % 3, 18.5, 61, 16.6, phase=0.1 * z), CT[1], CT[0]), z, 0))
+        polys.append((rc.place(rc.rect(rc.F(5, 2), rc.F(1, 2), rc.F(257, 2), 35), CT[1], CT[0]), z, 1))
+        polys.append((rc.place(rc.ngon(5, 60, 20, 58, 17, phase=0.7), CT[1], CT[0]), z, 2))
+        polys.append((rc.place(rc.rect(-5, 3, 135, 30), CT[1], CT[0]), z, 3))
+    points, polygons = rc.flatten(polys)
+    before = mc.arbitrary_bits(big, seed=41)
+    d = desc(big, CT, contours=15, rule=capi.POLY_UNION, combine=capi.MORPH_OR)
+    want, result, r = rr.raster(big, before, points, polygons, tuple(d.origin), tuple(d.spacing), d.contours, d.rule, d.combine, *mc.whole(big))
+    out["polygons"] = (lambda c: (c.mask_polygons(d, points, polygons), c.polygons_counters()), {0: np.zeros(big + (4,), f32), 1: before},
+                       big, want, result, len(polygons), [r[0], r[1], r[2], r[3]])
+    # CLOSE by the radius-2 ball on the small volume: the packed operand, the dilation (which holds the operand) and the closing
+    src = mc.hostile(mc.dense(small, seed=43), 0, seed=44)
+    before = mc.arbitrary_bits(small, seed=45)
+    dm = capi.MorphDesc()
+    dm.src_slot, dm.src_contour, dm.dst_slot, dm.dst_contour, dm.op, dm.combine = 0, 0, 1, 0, capi.MORPH_CLOSE, capi.MORPH_REPLACE
+    dm = dm.copy(box_lo=(0, 0, 0), box_hi=small[::-1], element=mc.to_capi(mr.ball((1, 1, 1), 2)))
+    want, voxels, src_voxels, (lo, hi), box, r = mr.morph(src, before, 0, 0, dm.op, dm.combine, *mc.whole(small), mc.from_capi(dm.element))
+    a = mr.member(src[..., 0])
+    out["morph"] = (lambda c: (c.mask_morph(dm), c.morph_counters()), {0: src, 1: before}, small, want, (voxels, src_voxels, lo, hi), box, [a, a, r])
+    # SIGNED with a probe on the big volume at 1 x 1 x 3 mm: the packed operand and the packed probe
+    src = mc.hostile(mc.dense(big, seed=46), 0, seed=47)
+    probe = mc.hostile(mc.sparse(big, seed=48, p=0.02), 1, seed=49)
+    before = mc.arbitrary_bits(big, seed=50)
+    dd = capi.DistDesc()
+    dd.src_slot, dd.src_contour, dd.dst_slot, dd.dst_channel, dd.mode, dd.scale = 0, 0, 1, 0, capi.DIST_SIGNED, 1.0
+    dd = dd.copy(box_lo=(0, 0, 0), box_hi=big[::-1], spacing=dc.MM, probe_slot=2, probe_contour=1)
+    want, result, box = dr.distance(src, before, 0, 0, dd.mode, *dc.whole(big), dc.MM, 0, f32(1.0), probe, 1)
+    out["distance"] = (lambda c: (c.mask_distance(dd), c.dist_counters()), {0: src, 1: before, 2: probe}, big, want, result, box,
+                       [mr.member(src[..., 0]), mr.member(probe[..., 1])])
+    return out
+
+
+def test_shared_bit_row_scratch_keeps_no_stale_words():
+    """The three bit-row tools take their buffers from ONE scratch of the context and each zeroes what it takes: polygons with all four
+    contours on 130 x 37 x 21, CLOSE on 70 x 9 x 6 and a SIGNED distance map with a probe on 130 x 37 x 21 again, one after the other on
+    one context of their own, then in reverse order, in both kernel forms.  Every call equals its restatement bit for bit (destination,
+    result, counters).  Not vacuous: `stale` follows, from the restatements' sets, which words of the scratch hold set bits, and every
+    buffer a call takes holds some when the call starts (the first call of all apart)."""
+    tools = scratch_sequence_inputs()
+
+    def word_flags(r):  # per word of the bit-rows of a (nz, ny, nx) set: it has a set bit
+        nz, ny, nx = r.shape
+        padded = np.zeros((nz, ny, (nx + 63) // 64 * 64), bool)
+        padded[..., :nx] = r
+        return padded.reshape(nz, ny, -1, 64).any(-1).ravel()
+
+    stale = np.zeros(0, bool)
+    calls = 0
+    with capi.Context(W, H, 0) as c:
+        for flavour in (0, 1):
+            c.set_kernel_flavour(flavour)
+            for name in ("polygons", "morph", "distance", "distance", "morph", "polygons"):
+                call, uploads, shape, want, result, out0, buffers = tools[name]
+                flags = [word_flags(r) for r in buffers]
+                nw = len(flags[0])
+                if calls:
+                    for k in range(len(flags)):
+                        assert stale[k * nw:(k + 1) * nw].any(), (flavour, name, k)
+                for slot, v in uploads.items():
+                    c.volume_upload(slot, v)
+                res, cnt = call(c)
+                got = c.volume_download(1, shape)
+                bad = np.argwhere(vt.bits(got) != vt.bits(want))
+                assert bad.size == 0, (flavour, name, calls, len(bad), bad[:4])
+                assert res.as_tuple() == result, (flavour, name, calls, res.as_tuple(), result)
+                assert cnt[0] == out0 and cnt[1] + cnt[2] == cnt[0], (flavour, name, calls, cnt, out0)
+                if flavour == 1:
+                    assert cnt[2] == 0, (name, cnt)  # the plain form computes the whole box / takes every polygon of a slice in it
+                after = np.concatenate(flags)
+                stale = np.concatenate([after, stale[len(after):]])
+                calls += 1
+    assert calls == 12 and len(stale) == 4 * 3 * 37 * 21

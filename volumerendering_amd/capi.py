@@ -732,6 +732,18 @@ class Context:
         self._chk(self.lib.vr_hist_counters(self.h, C.byref(out)))
         return int(out[0]), int(out[1]), int(out[2])
 
+    def _tool_counters(self, call):
+        """The three counters of a mask tool's last call, as ints."""
+        out = (C.c_uint64 * 3)()
+        self._chk(call(self.h, C.byref(out)))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def _tool_timing(self, call):
+        """The four phases of a mask tool's last call in ms of device time."""
+        out = (C.c_float * 4)()
+        self._chk(call(self.h, C.byref(out)))
+        return tuple(float(x) for x in out)
+
     def grow_whole(self, volume_slot: int, mask_slot: int, contour: int, lo: float, hi: float) -> GrowDesc:
         """vr_grow_whole: the descriptor of a grow over the whole volume (channel 3, FACES, REPLACE, no seeds: add them with copy)."""
         d = GrowDesc()
@@ -746,15 +758,11 @@ class Context:
 
     def grow_counters(self):
         """(voxels of the box, voxels whose value was loaded, voxels classified from a brick record) of the last segment_grow."""
-        out = (C.c_uint64 * 3)()
-        self._chk(self.lib.vr_grow_counters(self.h, C.byref(out)))
-        return int(out[0]), int(out[1]), int(out[2])
+        return self._tool_counters(self.lib.vr_grow_counters)
 
     def grow_timing(self):
         """(classify, propagate, write, refresh) of the last segment_grow in ms of device time (vr_grow_timing)."""
-        out = (C.c_float * 4)()
-        self._chk(self.lib.vr_grow_timing(self.h, C.byref(out)))
-        return tuple(float(x) for x in out)
+        return self._tool_timing(self.lib.vr_grow_timing)
 
     def morph_whole(self, src_slot: int, src_contour: int, dst_slot: int, dst_contour: int, op: int) -> MorphDesc:
         """vr_morph_whole: the descriptor of an operator over the whole volume (REPLACE, the radius-1 ball of unit spacing)."""
@@ -770,15 +778,11 @@ class Context:
 
     def morph_counters(self):
         """(voxels of the box, voxels the last dilation launch computed, voxels settled without computing) of the last mask_morph."""
-        out = (C.c_uint64 * 3)()
-        self._chk(self.lib.vr_morph_counters(self.h, C.byref(out)))
-        return int(out[0]), int(out[1]), int(out[2])
+        return self._tool_counters(self.lib.vr_morph_counters)
 
     def morph_timing(self):
         """(pack, morphology, write, refresh) of the last mask_morph in ms of device time (vr_morph_timing)."""
-        out = (C.c_float * 4)()
-        self._chk(self.lib.vr_morph_timing(self.h, C.byref(out)))
-        return tuple(float(x) for x in out)
+        return self._tool_timing(self.lib.vr_morph_timing)
 
     def dist_whole(self, src_slot: int, src_contour: int, dst_slot: int, dst_channel: int, mode: int) -> DistDesc:
         """vr_dist_whole: the descriptor of a distance map over the whole volume (unit spacing, no limit, scale 1, no probe)."""
@@ -792,15 +796,11 @@ class Context:
 
     def dist_counters(self):
         """(voxels of the box, voxels inside the region the envelope passes computed, the rest) of the last mask_distance."""
-        out = (C.c_uint64 * 3)()
-        self._chk(self.lib.vr_dist_counters(self.h, C.byref(out)))
-        return int(out[0]), int(out[1]), int(out[2])
+        return self._tool_counters(self.lib.vr_dist_counters)
 
     def dist_timing(self):
         """(pack, distance passes, write, refresh) of the last mask_distance in ms of device time (vr_dist_timing)."""
-        out = (C.c_float * 4)()
-        self._chk(self.lib.vr_dist_timing(self.h, C.byref(out)))
-        return tuple(float(x) for x in out)
+        return self._tool_timing(self.lib.vr_dist_timing)
 
     def polygons_whole(self, grid_slot: int, dst_slot: int) -> PolygonsDesc:
         """vr_polygons_whole: the descriptor of a raster over the whole grid (contour 0, EVEN_ODD, REPLACE, origin 0, unit spacing)."""
@@ -821,15 +821,11 @@ class Context:
 
     def polygons_counters(self):
         """(polygons given, polygons rasterised, polygons skipped) of the last mask_polygons."""
-        out = (C.c_uint64 * 3)()
-        self._chk(self.lib.vr_polygons_counters(self.h, C.byref(out)))
-        return tuple(int(x) for x in out)
+        return self._tool_counters(self.lib.vr_polygons_counters)
 
     def polygons_timing(self):
         """(upload, raster, write, refresh) of the last mask_polygons in ms of device time (vr_polygons_timing)."""
-        out = (C.c_float * 4)()
-        self._chk(self.lib.vr_polygons_timing(self.h, C.byref(out)))
-        return tuple(float(x) for x in out)
+        return self._tool_timing(self.lib.vr_polygons_timing)
 
     def set_volume_layout(self, mode: int):
         """0 bricked copy (default), 1 the reference's vec4 voxels only, 3 x-fastest voxels + density plane (2 was removed)."""

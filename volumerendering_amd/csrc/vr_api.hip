@@ -4,12 +4,12 @@
 // device vr_create fails with VR_ERR_HIP.
 #include "../../include/vr.h"
 #include "vr_launch.h"
-#include "vr_units.h"  // what the three voxel tools below share
+#include "vr_units.h"  // what the voxel tools below share
 // Histograms (vr_histogram_async): nothing to fuse, so this kernel exists once, here
 #include "vr_hist.h"
 // Region growing (vr_segment_grow): integer work on bit-bricks, compiled once as well
 #include "vr_grow.h"
-// Mask morphology (vr_mask_morph): integer work on bit-rows, compiled once as well
+// Mask morphology (vr_mask_morph): integer work on bit-rows (vr_bitrows.h: their box walk, pack and combine rule), compiled once as well
 #include "vr_morph.h"
 // Distance maps (vr_mask_distance): exact integer work on the same bit-rows, compiled once as well
 #include "vr_dist.h"

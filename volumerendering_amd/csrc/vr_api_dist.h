@@ -1,5 +1,5 @@
 // vr_api_dist.h -- exact signed distance maps of a mask contour on the device (vr_mask_distance; the kernels are vr_dist.h's, the pack is
-// vr_morph.h's) and the host filler of its descriptor.  vr_mask_distance is a data-preparation call like vr_mask_morph: it drains the
+// vr_bitrows.h's) and the host filler of its descriptor.  vr_mask_distance is a data-preparation call like vr_mask_morph: it drains the
 // device, runs on the context's stream, ends with bind_voxels for a slot it created and with refresh_bricks otherwise, and is
 // synchronous on return.  Part of vr_api.hip's translation unit.
 #pragma once
@@ -14,30 +14,29 @@ int check_dist(vr_ctx* c, const vr_dist_desc* d)
 {
     const std::string w("vr_mask_distance");
     if (!d) return fail(c, VR_ERR_INVALID_ARG, w + ": the descriptor is NULL");
-    if (d->src_slot < 0 || d->src_slot >= VR_MAX_VOLUMES) return fail(c, VR_ERR_INVALID_ARG, w + ": bad source slot");
-    if (d->dst_slot < 0 || d->dst_slot >= VR_MAX_VOLUMES) return fail(c, VR_ERR_INVALID_ARG, w + ": bad destination slot");
-    if (d->src_contour < 0 || d->src_contour > 3) return fail(c, VR_ERR_INVALID_ARG, w + ": the source contour must be 0 .. 3");
-    if (d->dst_channel < 0 || d->dst_channel > 3) return fail(c, VR_ERR_INVALID_ARG, w + ": the destination channel must be 0 .. 3");
+    if (const int rc = check_slot(c, w, "source", d->src_slot)) return rc;
+    if (const int rc = check_slot(c, w, "destination", d->dst_slot)) return rc;
+    if (const int rc = check_component(c, w, "source contour", d->src_contour)) return rc;
+    if (const int rc = check_component(c, w, "destination channel", d->dst_channel)) return rc;
     if (d->mode < VR_DIST_OUTSIDE || d->mode > VR_DIST_SIGNED) return fail(c, VR_ERR_INVALID_ARG, w + ": unknown mode");
     if (d->probe_slot != -1) {
-        if (d->probe_slot < 0 || d->probe_slot >= VR_MAX_VOLUMES) return fail(c, VR_ERR_INVALID_ARG, w + ": bad probe slot");
-        if (d->probe_contour < 0 || d->probe_contour > 3) return fail(c, VR_ERR_INVALID_ARG, w + ": the probe contour must be 0 .. 3");
+        if (const int rc = check_slot(c, w, "probe", d->probe_slot)) return rc;
+        if (const int rc = check_component(c, w, "probe contour", d->probe_contour)) return rc;
         if (d->mode == VR_DIST_INSIDE) return fail(c, VR_ERR_INVALID_ARG, w + ": a probe reports the OUTSIDE field, which VR_DIST_INSIDE does not compute");
     }
     for (int a = 0; a < 3; ++a)
         if (d->spacing[a] == 0 || d->spacing[a] > kDistMaxSpacing) return fail(c, VR_ERR_INVALID_ARG, w + ": a spacing is outside 1 .. 2^20");
     if (d->limit > kDistMaxLimit) return fail(c, VR_ERR_INVALID_ARG, w + ": the limit is above 2^31");
     if (!std::isfinite(d->scale) || !(d->scale > 0.0f)) return fail(c, VR_ERR_INVALID_ARG, w + ": the scale must be finite and > 0");
+    if (const int rc = check_filled(c, w, "source", d->src_slot)) return rc;
     const DevVolume& v = c->vols[d->src_slot].vol;
-    if (!v.data) return fail(c, VR_ERR_NOT_READY, w + ": source slot " + std::to_string(d->src_slot) + " is empty");
     if (const int rc = check_box(c, w, d->box_lo, d->box_hi, v)) return rc;
     for (int a = 0; a < 3; ++a)
         if ((uint64_t)(d->box_hi[a] - d->box_lo[a]) * d->spacing[a] > kDistMaxExtent)
             return fail(c, VR_ERR_INVALID_ARG, w + ": the box's extent times the spacing exceeds 2^30 on some axis");
     if (d->probe_slot != -1) {
-        const DevVolume& p = c->vols[d->probe_slot].vol;
-        if (!p.data) return fail(c, VR_ERR_NOT_READY, w + ": probe slot " + std::to_string(d->probe_slot) + " is empty");
-        if (const int rc = check_same_dims(c, w, "probe", p, "source", v)) return rc;
+        if (const int rc = check_filled(c, w, "probe", d->probe_slot)) return rc;
+        if (const int rc = check_same_dims(c, w, "probe", c->vols[d->probe_slot].vol, "source", v)) return rc;
     }
     const DevVolume& m = c->vols[d->dst_slot].vol;
     return m.data ? check_same_dims(c, w, "destination", m, "source", v) : VR_OK;
@@ -47,16 +46,16 @@ unsigned long long field_voxels(const DistField& F) { return (unsigned long long
 
 // One field over its region: the x pass from the bit-rows, then the envelope passes along y and z in place (a line of one voxel is
 // what it was).  COMP: the INSIDE field.
-int dist_field(vr_ctx* c, const MorphParams& m, const vr_dist_desc& d, const DistField& F, bool comp)
+int dist_field(vr_ctx* c, const DistParams& P, const vr_dist_desc& d, const DistField& F, bool comp)
 {
     if (field_voxels(F) == 0) return VR_OK;
     DistState& S = c->dist;
     hipStream_t s = c->stream;
     DistXPass X;
-    X.bits = m.a;
+    X.bits = P.a;
     X.F = F;
-    X.ny = m.ny;
-    X.wx = m.wx;
+    X.ny = P.b.ny;
+    X.wx = P.b.wx;
     X.rw0 = F.lo[0] >> 6;
     X.rw = ((F.lo[0] + F.n[0] + 63) >> 6) - X.rw0;
     X.words = (unsigned long long)X.rw * (unsigned long long)F.n[1] * (unsigned long long)F.n[2];
@@ -101,53 +100,35 @@ int run_dist(vr_ctx* c, const vr_dist_desc& d, float4* dst, vr_dist_result* resu
     const bool probe = d.probe_slot != -1;
     DistParams P;
     std::memset(&P, 0, sizeof P);
-    MorphParams& m = P.m;
-    m.src = v.data;
-    m.dst = dst;
-    m.src_contour = d.src_contour;
-    m.dst_contour = d.dst_channel;
-    m.nx = v.nx;
-    m.ny = v.ny;
-    m.nz = v.nz;
-    m.wx = (v.nx + 63) >> 6;
-    unsigned long long box = 1;
-    for (int a = 0; a < 3; ++a) {
-        m.lo[a] = d.box_lo[a];
-        m.hi[a] = d.box_hi[a];
-        box *= (unsigned long long)(d.box_hi[a] - d.box_lo[a]);
-    }
-    m.bw0 = m.lo[0] >> 6;
-    m.bw = ((m.hi[0] + 63) >> 6) - m.bw0;
-    m.box_words = box == 0 ? 0ull : (unsigned long long)m.bw * (unsigned long long)(m.hi[1] - m.lo[1]) * (unsigned long long)(m.hi[2] - m.lo[2]);
-    const size_t nw = (size_t)m.wx * (size_t)v.ny * (size_t)v.nz;
-    // (the device is drained and every earlier use was synchronous: a smaller buffer is freed at once)
-    if (const int rc = grow(c, S.words, 2 * nw, true)) return rc;
-    if (!S.d_words) VR_HIP(c, S.d_words.reserve(1));
-    if (!S.h_words) VR_HIP(c, S.h_words.reserve(1, true));
-    m.a = S.words.p;
-    m.w = &S.d_words.p->src;
-    MorphParams mp = m;  // the probe's pack
-    if (probe) {
-        mp.src = c->vols[d.probe_slot].vol.data;
-        mp.src_contour = d.probe_contour;
-        mp.a = S.words.p + nw;
-        mp.w = &S.d_words.p->probe;
-    }
-    const unsigned blocks = tool_blocks(m.box_words);
+    unsigned long long box;
+    const BitRows W = P.b = bit_rows(v, d.box_lo, d.box_hi, &box);
+    P.dst = dst;
+    P.dst_channel = d.dst_channel;
+    const size_t nw = W.words();
+    if (const int rc = grow(c, c->bit_row_scratch, 2 * nw, true)) return rc;  // (drained: a smaller scratch is freed at once)
+    unsigned long long* const words = c->bit_row_scratch.p;  // the packed operand A', and the packed probe
+    VR_HIP(c, S.io.first_use());
+    P.a = words;
+    P.probe = probe ? words + nw : nullptr;
+    P.w = S.io.d;
+    const BitPack pack = {v.data, d.src_contour, W, words, &S.io.d.p->src};
+    const unsigned blocks = tool_blocks(W.box_words);
 
     VR_HIP(c, hipEventRecord(S.report.ev[0], s));
-    const MorphWords none = {CountBox::empty(), CountBox::empty()};
-    *S.h_words.p = DistWords{none, none, 0ull, 0ull, kDistNone, 0ull};
-    VR_HIP(c, hipMemcpyAsync(S.d_words, S.h_words, sizeof(DistWords), hipMemcpyHostToDevice, s));
-    VR_HIP(c, hipMemsetAsync(S.words.p, 0, (probe ? 2 : 1) * nw * sizeof(unsigned long long), s));
-    if (m.box_words != 0) {
-        hipLaunchKernelGGL(morph_pack_kernel, dim3(blocks), dim3(256), 0, s, m);
-        if (probe) hipLaunchKernelGGL(morph_pack_kernel, dim3(blocks), dim3(256), 0, s, mp);
+    *S.io.h.p = DistWords{CountBox::empty(), CountBox::empty(), 0ull, 0ull, kDistNone, 0ull};
+    VR_HIP(c, S.io.push(s));
+    VR_HIP(c, hipMemsetAsync(words, 0, (probe ? 2 : 1) * nw * sizeof(unsigned long long), s));
+    if (W.box_words != 0) {
+        hipLaunchKernelGGL(bit_pack_kernel, dim3(blocks), dim3(256), 0, s, pack);
+        if (probe) {
+            const BitPack probe_pack = {c->vols[d.probe_slot].vol.data, d.probe_contour, W, words + nw, &S.io.d.p->probe};
+            hipLaunchKernelGGL(bit_pack_kernel, dim3(blocks), dim3(256), 0, s, probe_pack);
+        }
         VR_HIP(c, hipGetLastError());
     }
-    VR_HIP(c, hipMemcpyAsync(S.h_words, S.d_words, sizeof(DistWords), hipMemcpyDeviceToHost, s));
+    VR_HIP(c, S.io.pull(s));
     VR_HIP(c, hipStreamSynchronize(s));
-    const CountBox packed = S.h_words.p->src.src;
+    const CountBox packed = S.io.h.p->src;
     VR_HIP(c, hipEventRecord(S.report.ev[1], s));
 
     // Where a field is computed; outside it is known.  OUTSIDE: with a limit BEYOND outside the bounding box of A' grown by
@@ -161,7 +142,7 @@ int run_dist(vr_ctx* c, const vr_dist_desc& d, float4* dst, vr_dist_result* resu
     for (int f = 0; f < 2; ++f) {
         if (!need[f] || box == 0 || (!plain && packed.voxels == 0)) continue;
         for (int a = 0; a < 3; ++a) {
-            long long lo = m.lo[a], hi = m.hi[a];
+            long long lo = W.lo[a], hi = W.hi[a];
             if (!plain && (f == 1 || d.limit != 0)) {
                 const long long g = f == 1 ? 1 : (long long)(d.limit / d.spacing[a]);
                 lo = std::max(lo, (long long)packed.lo[a] - g);
@@ -179,36 +160,27 @@ int run_dist(vr_ctx* c, const vr_dist_desc& d, float4* dst, vr_dist_result* resu
     if (const int rc = grow(c, S.stack_g, (size_t)std::max(fv[0], fv[1]), true)) return rc;
     if (const int rc = grow(c, S.stack_st, (size_t)std::max(fv[0], fv[1]), true)) return rc;
     for (int f = 0; f < 2; ++f)
-        if (const int rc = dist_field(c, m, d, F[f], f == 1)) return rc;
+        if (const int rc = dist_field(c, P, d, F[f], f == 1)) return rc;
     VR_HIP(c, hipEventRecord(S.report.ev[2], s));
 
-    P.probe = probe ? mp.a : nullptr;
     P.out = F[0];
     P.in = F[1];
     P.mode = d.mode;
     P.limit_sq = (unsigned long long)d.limit * d.limit;
     P.scale = d.scale;
     P.beyond_value = d.limit != 0 ? (float)d.limit * d.scale : INFINITY;
-    P.w = S.d_words;
-    if (m.box_words != 0) {
+    if (W.box_words != 0) {
         hipLaunchKernelGGL(dist_write_kernel, dim3(blocks), dim3(256), 0, s, P);
         VR_HIP(c, hipGetLastError());
     }
-    VR_HIP(c, hipMemcpyAsync(S.h_words, S.d_words, sizeof(DistWords), hipMemcpyDeviceToHost, s));
+    VR_HIP(c, S.io.pull(s));
     VR_HIP(c, hipEventRecord(S.report.ev[3], s));
     VR_HIP(c, hipStreamSynchronize(s));
-    const DistWords& w = *S.h_words.p;
-    const unsigned long long computed = fv[d.mode == VR_DIST_INSIDE ? 1 : 0];
-    S.report.counters[0] = box;
-    S.report.counters[1] = computed;
-    S.report.counters[2] = box - computed;
+    const DistWords& w = *S.io.h.p;
+    S.report.computed_of_box(box, fv[d.mode == VR_DIST_INSIDE ? 1 : 0]);
     if (result) {
         std::memset(result, 0, sizeof *result);
-        result->src_voxels = w.src.src.voxels;
-        for (int a = 0; a < 3 && w.src.src.voxels != 0; ++a) {
-            result->lo[a] = w.src.src.lo[a];
-            result->hi[a] = w.src.src.hi[a];
-        }
+        copy_count_box(w.src, &result->src_voxels, result->lo, result->hi);
         result->beyond = w.beyond;
         result->probe_voxels = w.probe_voxels;
         result->probe_min_sq = w.probe_voxels ? w.probe_min : 0;
@@ -224,9 +196,8 @@ extern "C" {
 int vr_dist_whole(const vr_ctx* c, int src_slot, int src_contour, int dst_slot, int dst_channel, int mode, vr_dist_desc* out)
 {
     if (!c || !out) return VR_ERR_INVALID_ARG;
-    if (src_slot < 0 || src_slot >= VR_MAX_VOLUMES || dst_slot < 0 || dst_slot >= VR_MAX_VOLUMES || src_contour < 0 || src_contour > 3 ||
-        dst_channel < 0 || dst_channel > 3 || mode < VR_DIST_OUTSIDE || mode > VR_DIST_SIGNED)
-        return VR_ERR_INVALID_ARG;
+    if (!is_slot(src_slot) || !is_slot(dst_slot) || !is_component(src_contour) || !is_component(dst_channel)) return VR_ERR_INVALID_ARG;
+    if (mode < VR_DIST_OUTSIDE || mode > VR_DIST_SIGNED) return VR_ERR_INVALID_ARG;
     if (!c->vols[src_slot].vol.data) return VR_ERR_NOT_READY;
     std::memset(out, 0, sizeof *out);
     out->src_slot = src_slot;

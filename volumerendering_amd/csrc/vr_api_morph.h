@@ -30,32 +30,19 @@ int check_morph(vr_ctx* c, const vr_morph_desc* d)
 {
     const std::string w("vr_mask_morph");
     if (!d) return fail(c, VR_ERR_INVALID_ARG, w + ": the descriptor is NULL");
-    if (d->src_slot < 0 || d->src_slot >= VR_MAX_VOLUMES) return fail(c, VR_ERR_INVALID_ARG, w + ": bad source slot");
-    if (d->dst_slot < 0 || d->dst_slot >= VR_MAX_VOLUMES) return fail(c, VR_ERR_INVALID_ARG, w + ": bad destination slot");
-    if (d->src_contour < 0 || d->src_contour > 3) return fail(c, VR_ERR_INVALID_ARG, w + ": the source contour must be 0 .. 3");
-    if (d->dst_contour < 0 || d->dst_contour > 3) return fail(c, VR_ERR_INVALID_ARG, w + ": the destination contour must be 0 .. 3");
+    if (const int rc = check_slot(c, w, "source", d->src_slot)) return rc;
+    if (const int rc = check_slot(c, w, "destination", d->dst_slot)) return rc;
+    if (const int rc = check_component(c, w, "source contour", d->src_contour)) return rc;
+    if (const int rc = check_component(c, w, "destination contour", d->dst_contour)) return rc;
     if (d->op < VR_MORPH_NONE || d->op > VR_MORPH_OPEN) return fail(c, VR_ERR_INVALID_ARG, w + ": unknown op");
     if (d->combine < VR_MORPH_REPLACE || d->combine > VR_MORPH_ANDNOT) return fail(c, VR_ERR_INVALID_ARG, w + ": unknown combine");
     if (d->op != VR_MORPH_NONE)
         if (const char* what = check_element(d->element)) return fail(c, VR_ERR_INVALID_ARG, w + ": " + what);
+    if (const int rc = check_filled(c, w, "source", d->src_slot)) return rc;
     const DevVolume& v = c->vols[d->src_slot].vol;
-    if (!v.data) return fail(c, VR_ERR_NOT_READY, w + ": source slot " + std::to_string(d->src_slot) + " is empty");
     if (const int rc = check_box(c, w, d->box_lo, d->box_hi, v)) return rc;
     const DevVolume& m = c->vols[d->dst_slot].vol;
     return m.data ? check_same_dims(c, w, "destination", m, "source", v) : VR_OK;
-}
-
-// the working buffers of a call over nw words per bit-row buffer (first use)
-int prepare_morph_state(vr_ctx* c, size_t nw)
-{
-    MorphState& M = c->morph;
-    // (the device is drained and every earlier use was synchronous: a smaller buffer is freed at once)
-    if (const int rc = grow(c, M.words, 3 * nw, true)) return rc;
-    if (!M.rows) VR_HIP(c, M.rows.reserve((size_t)kMorphSide * kMorphSide));
-    if (!M.h_rows) VR_HIP(c, M.h_rows.reserve((size_t)kMorphSide * kMorphSide, true));
-    if (!M.d_words) VR_HIP(c, M.d_words.reserve(1));
-    if (!M.h_words) VR_HIP(c, M.h_words.reserve(1, true));
-    return VR_OK;
 }
 
 // a half-open voxel region; empty when some hi <= lo
@@ -83,7 +70,7 @@ int morph_pass(vr_ctx* c, const MorphParams& P, const unsigned long long* src, u
     S.rz0 = reg.lo[2];
     S.rz = reg.hi[2] - reg.lo[2];
     S.words = (unsigned long long)S.rw * (unsigned long long)S.ry * (unsigned long long)S.rz;
-    const int x0 = S.rw0 << 6 > P.lo[0] ? S.rw0 << 6 : P.lo[0], x1 = (S.rw0 + S.rw) << 6 < P.hi[0] ? (S.rw0 + S.rw) << 6 : P.hi[0];
+    const int x0 = S.rw0 << 6 > P.b.lo[0] ? S.rw0 << 6 : P.b.lo[0], x1 = (S.rw0 + S.rw) << 6 < P.b.hi[0] ? (S.rw0 + S.rw) << 6 : P.b.hi[0];
     *computed = (unsigned long long)(x1 - x0) * (unsigned long long)S.ry * (unsigned long long)S.rz;
     const unsigned blocks = (unsigned)((S.words + 255ull) / 256ull);  // (at most 2^32 / 64 words: below 2^18 blocks)
     if (comp) hipLaunchKernelGGL(morph_dilate_kernel<true>, dim3(blocks), dim3(256), 0, s, P, S);
@@ -101,32 +88,21 @@ int run_morph(vr_ctx* c, const vr_morph_desc& d, float4* dst, bool fresh, vr_mor
     const DevVolume& v = c->vols[d.src_slot].vol;
     MorphParams P;
     std::memset(&P, 0, sizeof P);
-    P.src = v.data;
+    unsigned long long box;
+    const BitRows W = P.b = bit_rows(v, d.box_lo, d.box_hi, &box);
     P.dst = dst;
-    P.src_contour = d.src_contour;
     P.dst_contour = d.dst_contour;
-    P.nx = v.nx;
-    P.ny = v.ny;
-    P.nz = v.nz;
-    P.wx = (v.nx + 63) >> 6;
-    unsigned long long box = 1;
-    for (int a = 0; a < 3; ++a) {
-        P.lo[a] = d.box_lo[a];
-        P.hi[a] = d.box_hi[a];
-        box *= (unsigned long long)(d.box_hi[a] - d.box_lo[a]);
-    }
-    P.bw0 = P.lo[0] >> 6;
-    P.bw = ((P.hi[0] + 63) >> 6) - P.bw0;
-    P.box_words = box == 0 ? 0ull : (unsigned long long)P.bw * (unsigned long long)(P.hi[1] - P.lo[1]) * (unsigned long long)(P.hi[2] - P.lo[2]);
-    P.combine = d.combine;
-    P.fresh = fresh ? 1 : 0;
-    const size_t nw = (size_t)P.wx * (size_t)v.ny * (size_t)v.nz;
-    if (const int rc = prepare_morph_state(c, nw)) return rc;
-    unsigned long long* const A = M.words.p;
-    unsigned long long* const B = M.words.p + nw;
-    unsigned long long* const C = M.words.p + 2 * nw;
-    P.a = A;
-    P.w = M.d_words;
+    P.c = {d.combine, fresh ? 1 : 0};
+    const size_t nw = W.words();
+    if (const int rc = grow(c, c->bit_row_scratch, 3 * nw, true)) return rc;  // (drained: a smaller scratch is freed at once)
+    unsigned long long* const A = c->bit_row_scratch.p;  // the packed operand A', and the two buffers a dilation pass writes in turn
+    unsigned long long* const B = A + nw;
+    unsigned long long* const C = A + 2 * nw;
+    if (!M.rows) VR_HIP(c, M.rows.reserve((size_t)kMorphSide * kMorphSide));
+    if (!M.h_rows) VR_HIP(c, M.h_rows.reserve((size_t)kMorphSide * kMorphSide, true));
+    VR_HIP(c, M.io.first_use());
+    P.w = M.io.d;
+    const BitPack pack = {v.data, d.src_contour, W, A, &M.io.d.p->src};
     const bool plain = plain_form(c);
     const bool morph = d.op != VR_MORPH_NONE;
     const int rad[3] = {morph ? d.element.radius[0] : 0, morph ? d.element.radius[1] : 0, morph ? d.element.radius[2] : 0};
@@ -142,32 +118,32 @@ int run_morph(vr_ctx* c, const vr_morph_desc& d, float4* dst, bool fresh, vr_mor
         VR_HIP(c, hipMemcpyAsync(M.rows, M.h_rows, (size_t)n * sizeof(unsigned), hipMemcpyHostToDevice, s));
         P.rows = M.rows;
     }
-    const unsigned blocks = tool_blocks(P.box_words);
+    const unsigned blocks = tool_blocks(W.box_words);
 
     VR_HIP(c, hipEventRecord(M.report.ev[0], s));
-    *M.h_words.p = MorphWords{CountBox::empty(), CountBox::empty()};
-    VR_HIP(c, hipMemcpyAsync(M.d_words, M.h_words, sizeof(MorphWords), hipMemcpyHostToDevice, s));
+    *M.io.h.p = MorphWords{CountBox::empty(), CountBox::empty()};
+    VR_HIP(c, M.io.push(s));
     VR_HIP(c, hipMemsetAsync(A, 0, nw * sizeof(unsigned long long), s));
-    if (P.box_words != 0) {
-        hipLaunchKernelGGL(morph_pack_kernel, dim3(blocks), dim3(256), 0, s, P);
+    if (W.box_words != 0) {
+        hipLaunchKernelGGL(bit_pack_kernel, dim3(blocks), dim3(256), 0, s, pack);
         VR_HIP(c, hipGetLastError());
     }
-    VR_HIP(c, hipMemcpyAsync(M.h_words, M.d_words, sizeof(MorphWords), hipMemcpyDeviceToHost, s));
+    VR_HIP(c, M.io.pull(s));
     VR_HIP(c, hipStreamSynchronize(s));
-    const MorphWords packed = *M.h_words.p;
+    const MorphWords packed = *M.io.h.p;
     VR_HIP(c, hipEventRecord(M.report.ev[1], s));
 
     // Where the result of a pass can be set: a dilation's within the bounding box of its source bits grown by the radii, an erosion's
     // within that bounding box itself (the origin is in E), both within the box.  The plain form takes the whole box.
     MorphRegion bb, grown, whole;
     for (int a = 0; a < 3; ++a) {
-        whole.lo[a] = P.lo[a];
-        whole.hi[a] = box == 0 ? P.lo[a] : P.hi[a];
+        whole.lo[a] = W.lo[a];
+        whole.hi[a] = box == 0 ? W.lo[a] : W.hi[a];
         bb.lo[a] = packed.src.voxels ? packed.src.lo[a] : 0;
         bb.hi[a] = packed.src.voxels ? packed.src.hi[a] : 0;
-        grown.lo[a] = bb.lo[a] - rad[a] > P.lo[a] ? bb.lo[a] - rad[a] : P.lo[a];
-        grown.hi[a] = bb.hi[a] + rad[a] < P.hi[a] ? bb.hi[a] + rad[a] : P.hi[a];
-        if (!packed.src.voxels) grown.hi[a] = grown.lo[a] = P.lo[a];
+        grown.lo[a] = bb.lo[a] - rad[a] > W.lo[a] ? bb.lo[a] - rad[a] : W.lo[a];
+        grown.hi[a] = bb.hi[a] + rad[a] < W.hi[a] ? bb.hi[a] + rad[a] : W.hi[a];
+        if (!packed.src.voxels) grown.hi[a] = grown.lo[a] = W.lo[a];
     }
     if (plain) bb = grown = whole;
     unsigned long long computed = 0;
@@ -196,20 +172,18 @@ int run_morph(vr_ctx* c, const vr_morph_desc& d, float4* dst, bool fresh, vr_mor
     P.r = R;
     VR_HIP(c, hipEventRecord(M.report.ev[2], s));
 
-    if (P.box_words != 0) {
+    if (W.box_words != 0) {
         hipLaunchKernelGGL(morph_write_kernel, dim3(blocks), dim3(256), 0, s, P);
         VR_HIP(c, hipGetLastError());
     }
-    VR_HIP(c, hipMemcpyAsync(M.h_words, M.d_words, sizeof(MorphWords), hipMemcpyDeviceToHost, s));
+    VR_HIP(c, M.io.pull(s));
     VR_HIP(c, hipEventRecord(M.report.ev[3], s));
     VR_HIP(c, hipStreamSynchronize(s));
-    const MorphWords& w = *M.h_words.p;
-    M.report.counters[0] = box;
-    M.report.counters[1] = computed;
-    M.report.counters[2] = box - computed;
+    const MorphWords& w = *M.io.h.p;
+    M.report.computed_of_box(box, computed);
     if (result) {
         std::memset(result, 0, sizeof *result);
-        copy_count_box(w.result, result);
+        copy_count_box(w.result, &result->voxels, result->lo, result->hi);
         result->src_voxels = w.src.voxels;
     }
     return VR_OK;
@@ -267,9 +241,8 @@ int vr_morph_box(int rx, int ry, int rz, vr_morph_element* out)
 int vr_morph_whole(const vr_ctx* c, int src_slot, int src_contour, int dst_slot, int dst_contour, int op, vr_morph_desc* out)
 {
     if (!c || !out) return VR_ERR_INVALID_ARG;
-    if (src_slot < 0 || src_slot >= VR_MAX_VOLUMES || dst_slot < 0 || dst_slot >= VR_MAX_VOLUMES || src_contour < 0 || src_contour > 3 ||
-        dst_contour < 0 || dst_contour > 3 || op < VR_MORPH_NONE || op > VR_MORPH_OPEN)
-        return VR_ERR_INVALID_ARG;
+    if (!is_slot(src_slot) || !is_slot(dst_slot) || !is_component(src_contour) || !is_component(dst_contour)) return VR_ERR_INVALID_ARG;
+    if (op < VR_MORPH_NONE || op > VR_MORPH_OPEN) return VR_ERR_INVALID_ARG;
     if (!c->vols[src_slot].vol.data) return VR_ERR_NOT_READY;
     std::memset(out, 0, sizeof *out);
     out->src_slot = src_slot;

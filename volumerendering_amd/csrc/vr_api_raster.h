@@ -18,8 +18,8 @@ int check_polygons(vr_ctx* c, const vr_polygons_desc* d)
 {
     const std::string w("vr_mask_polygons");
     if (!d) return fail(c, VR_ERR_INVALID_ARG, w + ": the descriptor is NULL");
-    if (d->grid_slot < 0 || d->grid_slot >= VR_MAX_VOLUMES) return fail(c, VR_ERR_INVALID_ARG, w + ": bad grid slot");
-    if (d->dst_slot < 0 || d->dst_slot >= VR_MAX_VOLUMES) return fail(c, VR_ERR_INVALID_ARG, w + ": bad destination slot");
+    if (const int rc = check_slot(c, w, "grid", d->grid_slot)) return rc;
+    if (const int rc = check_slot(c, w, "destination", d->dst_slot)) return rc;
     if (d->contours < 1 || d->contours > 15) return fail(c, VR_ERR_INVALID_ARG, w + ": contours must be 1 .. 15");
     if (d->rule != VR_POLY_EVEN_ODD && d->rule != VR_POLY_UNION) return fail(c, VR_ERR_INVALID_ARG, w + ": unknown rule");
     if (d->combine < VR_MORPH_REPLACE || d->combine > VR_MORPH_ANDNOT) return fail(c, VR_ERR_INVALID_ARG, w + ": unknown combine");
@@ -32,13 +32,14 @@ int check_polygons(vr_ctx* c, const vr_polygons_desc* d)
     for (uint32_t i = 0; i < d->n_polygons; ++i) {
         const vr_polygon& p = d->polygons[i];
         if ((uint64_t)p.first + p.count > d->n_points) return fail(c, VR_ERR_INVALID_ARG, w + ": polygon " + std::to_string(i) + " reads beyond the points");
-        if (p.contour < 0 || p.contour > 3) return fail(c, VR_ERR_INVALID_ARG, w + ": the contour of polygon " + std::to_string(i) + " must be 0 .. 3");
+        if (!is_component(p.contour))  // (asked here first: the message's name is put together only for a polygon that fails)
+            return check_component(c, w, "contour of polygon " + std::to_string(i), p.contour);
         if (!((d->contours >> p.contour) & 1)) return fail(c, VR_ERR_INVALID_ARG, w + ": the contour of polygon " + std::to_string(i) + " is not in contours");
     }
     for (size_t i = 0; i < (size_t)d->n_points * 2; ++i)
         if (d->points[i] < -kPolyCoordMax || d->points[i] > kPolyCoordMax) return fail(c, VR_ERR_INVALID_ARG, w + ": a point coordinate lies outside +-2^29");
+    if (const int rc = check_filled(c, w, "grid", d->grid_slot)) return rc;
     const DevVolume& v = c->vols[d->grid_slot].vol;
-    if (!v.data) return fail(c, VR_ERR_NOT_READY, w + ": grid slot " + std::to_string(d->grid_slot) + " is empty");
     if (const int rc = check_box(c, w, d->box_lo, d->box_hi, v)) return rc;
     const DevVolume& m = c->vols[d->dst_slot].vol;
     return m.data ? check_same_dims(c, w, "destination", m, "grid", v) : VR_OK;
@@ -99,23 +100,10 @@ int run_polygons(vr_ctx* c, const vr_polygons_desc& d, float4* dst, bool fresh, 
     const DevVolume& v = c->vols[d.grid_slot].vol;
     RasterParams P;
     std::memset(&P, 0, sizeof P);
-    MorphParams& M = P.m;
-    M.dst = dst;
-    M.nx = v.nx;
-    M.ny = v.ny;
-    M.nz = v.nz;
-    M.wx = (v.nx + 63) >> 6;
-    unsigned long long box = 1;
-    for (int a = 0; a < 3; ++a) {
-        M.lo[a] = d.box_lo[a];
-        M.hi[a] = d.box_hi[a];
-        box *= (unsigned long long)(d.box_hi[a] - d.box_lo[a]);
-    }
-    M.bw0 = M.lo[0] >> 6;
-    M.bw = ((M.hi[0] + 63) >> 6) - M.bw0;
-    M.box_words = box == 0 ? 0ull : (unsigned long long)M.bw * (unsigned long long)(M.hi[1] - M.lo[1]) * (unsigned long long)(M.hi[2] - M.lo[2]);
-    M.combine = d.combine;
-    M.fresh = fresh ? 1 : 0;
+    unsigned long long box;
+    const BitRows W = P.b = bit_rows(v, d.box_lo, d.box_hi, &box);
+    P.dst = dst;
+    P.c = {d.combine, fresh ? 1 : 0};
     P.contours = d.contours;
     P.ox = d.origin[0];
     P.oy = d.origin[1];
@@ -129,10 +117,10 @@ int run_polygons(vr_ctx* c, const vr_polygons_desc& d, float4* dst, bool fresh, 
     if (items.size() > 0x7fffffffull) return fail(c, VR_ERR_INVALID_ARG, "vr_mask_polygons: more than 2^31 work items");
 
     // the working buffers (first use; the device is drained and every earlier use was synchronous: a smaller buffer is freed at once)
-    const size_t nw = (size_t)M.wx * (size_t)v.ny * (size_t)v.nz;
-    if (const int rc = grow(c, R.words, 4 * nw, true)) return rc;
-    if (!R.d_words) VR_HIP(c, R.d_words.reserve(1));
-    if (!R.h_words) VR_HIP(c, R.h_words.reserve(1, true));
+    const size_t nw = W.words();
+    if (const int rc = grow(c, c->bit_row_scratch, 4 * nw, true)) return rc;
+    unsigned long long* const words = c->bit_row_scratch.p;  // R_k of every contour
+    VR_HIP(c, R.io.first_use());
     const size_t b_points = (size_t)d.n_points * sizeof(int2), b_polys = polys.size() * sizeof(RasterPoly), b_items = items.size() * sizeof(RasterItem);
     const size_t bytes = b_points + b_polys + b_items;
     if (R.h_stage.cap < bytes) VR_HIP(c, R.h_stage.reserve(bytes));
@@ -144,14 +132,14 @@ int run_polygons(vr_ctx* c, const vr_polygons_desc& d, float4* dst, bool fresh, 
     P.polys = reinterpret_cast<const RasterPoly*>(R.d_stage.p + b_points);
     P.items = reinterpret_cast<const RasterItem*>(R.d_stage.p + b_points + b_polys);
     P.n_items = (unsigned)items.size();
-    for (int k = 0; k < 4; ++k) P.bits[k] = R.words.p + (size_t)k * nw;
-    P.w = R.d_words;
+    for (int k = 0; k < 4; ++k) P.bits[k] = words + (size_t)k * nw;
+    P.w = R.io.d;
 
     VR_HIP(c, hipEventRecord(R.report.ev[0], s));
     if (bytes) VR_HIP(c, hipMemcpyAsync(R.d_stage, R.h_stage, bytes, hipMemcpyHostToDevice, s));
-    for (CountBox& b : R.h_words.p->r) b = CountBox::empty();
-    VR_HIP(c, hipMemcpyAsync(R.d_words, R.h_words, sizeof(RasterWords), hipMemcpyHostToDevice, s));
-    VR_HIP(c, hipMemsetAsync(R.words, 0, 4 * nw * sizeof(unsigned long long), s));
+    for (CountBox& b : R.io.h.p->r) b = CountBox::empty();
+    VR_HIP(c, R.io.push(s));
+    VR_HIP(c, hipMemsetAsync(words, 0, 4 * nw * sizeof(unsigned long long), s));
     VR_HIP(c, hipEventRecord(R.report.ev[1], s));
 
     if (P.n_items != 0) {
@@ -162,11 +150,11 @@ int run_polygons(vr_ctx* c, const vr_polygons_desc& d, float4* dst, bool fresh, 
     }
     VR_HIP(c, hipEventRecord(R.report.ev[2], s));
 
-    if (M.box_words != 0) {
-        hipLaunchKernelGGL(raster_write_kernel, dim3(tool_blocks(M.box_words)), dim3(256), 0, s, P);
+    if (W.box_words != 0) {
+        hipLaunchKernelGGL(raster_write_kernel, dim3(tool_blocks(W.box_words)), dim3(256), 0, s, P);
         VR_HIP(c, hipGetLastError());
     }
-    VR_HIP(c, hipMemcpyAsync(R.h_words, R.d_words, sizeof(RasterWords), hipMemcpyDeviceToHost, s));
+    VR_HIP(c, R.io.pull(s));
     VR_HIP(c, hipEventRecord(R.report.ev[3], s));
     VR_HIP(c, hipStreamSynchronize(s));
     R.report.counters[0] = d.n_polygons;
@@ -174,14 +162,7 @@ int run_polygons(vr_ctx* c, const vr_polygons_desc& d, float4* dst, bool fresh, 
     R.report.counters[2] = skipped;
     if (result) {
         std::memset(result, 0, sizeof *result);
-        for (int k = 0; k < 4; ++k) {
-            const CountBox& b = R.h_words.p->r[k];
-            result->voxels[k] = b.voxels;
-            for (int a = 0; a < 3 && b.voxels != 0; ++a) {
-                result->lo[k][a] = b.lo[a];
-                result->hi[k][a] = b.hi[a];
-            }
-        }
+        for (int k = 0; k < 4; ++k) copy_count_box(R.io.h.p->r[k], &result->voxels[k], result->lo[k], result->hi[k]);
     }
     return VR_OK;
 }
@@ -193,7 +174,7 @@ extern "C" {
 int vr_polygons_whole(const vr_ctx* c, int grid_slot, int dst_slot, vr_polygons_desc* out)
 {
     if (!c || !out) return VR_ERR_INVALID_ARG;
-    if (grid_slot < 0 || grid_slot >= VR_MAX_VOLUMES || dst_slot < 0 || dst_slot >= VR_MAX_VOLUMES) return VR_ERR_INVALID_ARG;
+    if (!is_slot(grid_slot) || !is_slot(dst_slot)) return VR_ERR_INVALID_ARG;
     if (!c->vols[grid_slot].vol.data) return VR_ERR_NOT_READY;
     std::memset(out, 0, sizeof *out);
     out->grid_slot = grid_slot;

@@ -10,16 +10,16 @@ int check_grow(vr_ctx* c, const vr_grow_desc* d)
 {
     const std::string w("vr_segment_grow");
     if (!d) return fail(c, VR_ERR_INVALID_ARG, w + ": the descriptor is NULL");
-    if (d->volume_slot < 0 || d->volume_slot >= VR_MAX_VOLUMES) return fail(c, VR_ERR_INVALID_ARG, w + ": bad volume slot");
-    if (d->mask_slot < 0 || d->mask_slot >= VR_MAX_VOLUMES) return fail(c, VR_ERR_INVALID_ARG, w + ": bad mask slot");
+    if (const int rc = check_slot(c, w, "volume", d->volume_slot)) return rc;
+    if (const int rc = check_slot(c, w, "mask", d->mask_slot)) return rc;
     if (d->mask_slot == d->volume_slot) return fail(c, VR_ERR_INVALID_ARG, w + ": the mask slot is the volume slot");
-    if (d->channel < 0 || d->channel > 3) return fail(c, VR_ERR_INVALID_ARG, w + ": the channel must be 0 .. 3");
-    if (d->contour < 0 || d->contour > 3) return fail(c, VR_ERR_INVALID_ARG, w + ": the contour must be 0 .. 3");
+    if (const int rc = check_component(c, w, "channel", d->channel)) return rc;
+    if (const int rc = check_component(c, w, "contour", d->contour)) return rc;
     if (d->connectivity != VR_GROW_FACES && d->connectivity != VR_GROW_ALL) return fail(c, VR_ERR_INVALID_ARG, w + ": unknown connectivity");
     if (d->mode != VR_GROW_REPLACE && d->mode != VR_GROW_ADD) return fail(c, VR_ERR_INVALID_ARG, w + ": unknown mode");
     if (d->n_seeds < 1 || d->n_seeds > VR_GROW_MAX_SEEDS) return fail(c, VR_ERR_INVALID_ARG, w + ": n_seeds must be 1 .. 64");
+    if (const int rc = check_filled(c, w, "volume", d->volume_slot)) return rc;
     const DevVolume& v = c->vols[d->volume_slot].vol;
-    if (!v.data) return fail(c, VR_ERR_NOT_READY, w + ": volume slot " + std::to_string(d->volume_slot) + " is empty");
     if (const int rc = check_box(c, w, d->box_lo, d->box_hi, v)) return rc;
     const int n[3] = {v.nx, v.ny, v.nz};
     for (uint32_t i = 0; i < d->n_seeds; ++i)
@@ -36,8 +36,7 @@ int prepare_grow_state(vr_ctx* c, size_t nb)
     // (the device is drained and every earlier use was synchronous: a smaller buffer is freed at once)
     if (const int rc = grow(c, G.words, 2 * nb, true)) return rc;
     if (const int rc = grow(c, G.lists, 3 * nb, true)) return rc;
-    if (!G.d_words) VR_HIP(c, G.d_words.reserve(1));
-    if (!G.h_words) VR_HIP(c, G.h_words.reserve(1, true));
+    VR_HIP(c, G.io.first_use());
     return VR_OK;
 }
 
@@ -73,7 +72,7 @@ int run_grow(vr_ctx* c, const vr_grow_desc& d, float4* mask, bool fresh, vr_grow
     P.stamp = G.lists;
     P.list[0] = G.lists.p + nb;
     P.list[1] = G.lists.p + 2 * nb;
-    P.w = G.d_words;
+    P.w = G.io.d;
     P.mask = mask;
     P.contour = d.contour;
     P.write_zeros = d.mode == VR_GROW_REPLACE && !fresh;
@@ -85,8 +84,8 @@ int run_grow(vr_ctx* c, const vr_grow_desc& d, float4* mask, bool fresh, vr_grow
     VR_HIP(c, hipEventRecord(G.report.ev[0], s));
     // exact settling by the slot's range records (of .a: channel 3)
     if (!plain && d.channel == 3 && P.box.units != 0 && !prepare_range(c, s, vs, P.bnx, P.bny, P.bnz, &P.bricks)) return VR_ERR_HIP;
-    *G.h_words.p = GrowWords{{0, 0, 0}, CountBox::empty(), {0, 0, 0}, 0};
-    VR_HIP(c, hipMemcpyAsync(G.d_words, G.h_words, sizeof(GrowWords), hipMemcpyHostToDevice, s));
+    *G.io.h.p = GrowWords{{0, 0, 0}, CountBox::empty(), {0, 0, 0}, 0};
+    VR_HIP(c, G.io.push(s));
     VR_HIP(c, hipMemsetAsync(G.words, 0, 2 * nb * sizeof(unsigned long long), s));
     VR_HIP(c, hipMemsetAsync(G.lists, 0, nb * sizeof(unsigned), s));  // (the stamps; the lists are written before they are read)
     if (P.box.units != 0) {
@@ -113,22 +112,22 @@ int run_grow(vr_ctx* c, const vr_grow_desc& d, float4* mask, bool fresh, vr_grow
             else hipLaunchKernelGGL(grow_round_kernel<false>, dim3(blocks), dim3(256), 0, s, P);
         }
         VR_HIP(c, hipGetLastError());
-        VR_HIP(c, hipMemcpyAsync(G.h_words, G.d_words, sizeof(GrowWords), hipMemcpyDeviceToHost, s));
+        VR_HIP(c, G.io.pull(s));
         VR_HIP(c, hipStreamSynchronize(s));
-        if (G.h_words.p->cnt[(k + 1) % 3] == 0) break;
+        if (G.io.h.p->cnt[(k + 1) % 3] == 0) break;
     }
     VR_HIP(c, hipEventRecord(G.report.ev[2], s));
 
     hipLaunchKernelGGL(grow_write_kernel, dim3(blocks), dim3(256), 0, s, P);
     VR_HIP(c, hipGetLastError());
-    VR_HIP(c, hipMemcpyAsync(G.h_words, G.d_words, sizeof(GrowWords), hipMemcpyDeviceToHost, s));
+    VR_HIP(c, G.io.pull(s));
     VR_HIP(c, hipEventRecord(G.report.ev[3], s));
     VR_HIP(c, hipStreamSynchronize(s));
-    const GrowWords& w = *G.h_words.p;
+    const GrowWords& w = *G.io.h.p;
     for (int i = 0; i < 3; ++i) G.report.counters[i] = w.stats[i];
     if (result) {
         std::memset(result, 0, sizeof *result);
-        copy_count_box(w.reached, result);
+        copy_count_box(w.reached, &result->voxels, result->lo, result->hi);
         result->rounds = w.rounds > 0 ? w.rounds : 1u;
     }
     return VR_OK;
@@ -141,9 +140,7 @@ extern "C" {
 int vr_grow_whole(const vr_ctx* c, int volume_slot, int mask_slot, int contour, float lo, float hi, vr_grow_desc* out)
 {
     if (!c || !out) return VR_ERR_INVALID_ARG;
-    if (volume_slot < 0 || volume_slot >= VR_MAX_VOLUMES || mask_slot < 0 || mask_slot >= VR_MAX_VOLUMES || mask_slot == volume_slot ||
-        contour < 0 || contour > 3)
-        return VR_ERR_INVALID_ARG;
+    if (!is_slot(volume_slot) || !is_slot(mask_slot) || mask_slot == volume_slot || !is_component(contour)) return VR_ERR_INVALID_ARG;
     if (!c->vols[volume_slot].vol.data) return VR_ERR_NOT_READY;
     std::memset(out, 0, sizeof *out);
     out->volume_slot = volume_slot;

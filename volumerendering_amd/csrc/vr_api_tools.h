@@ -1,5 +1,6 @@
-// vr_api_tools.h -- what the voxel tools (the histograms of vr_api_views.h, vr_api_segment.h, vr_api_morph.h, vr_api_dist.h) share on the host: the
-// rules for a box and a second slot, a walk's units and grid (vr_units.h), the shell and the report of a call into a mask slot.
+// vr_api_tools.h -- what the voxel tools (the histograms of vr_api_views.h, vr_api_segment.h, vr_api_morph.h, vr_api_dist.h,
+// vr_api_raster.h) share on the host: the rules for a slot, a component, a box and a second slot, a walk's units (vr_units.h) or word
+// rows (vr_bitrows.h) and its grid, the shell and the report of a call into a mask slot.
 #pragma once
 
 namespace {
@@ -8,6 +9,23 @@ constexpr unsigned kToolBlocks = 512;  // persistent workgroups of four wavefron
 
 // vr_set_kernel_flavour(1) asks for the plain form of a tool: no settling, no skipping, everything loaded
 bool plain_form(const vr_ctx* c) { return (c->flavour == 0 ? c->default_flavour : c->flavour) == 1; }
+
+bool is_slot(int slot) { return slot >= 0 && slot < VR_MAX_VOLUMES; }
+bool is_component(int k) { return k >= 0 && k <= 3; }  // a contour of a mask, a channel of a volume
+
+// `what`: which slot or component of the descriptor, as the message names it ("source", "destination channel")
+int check_slot(vr_ctx* c, const std::string& who, const char* what, int slot)
+{
+    return is_slot(slot) ? VR_OK : fail(c, VR_ERR_INVALID_ARG, who + ": bad " + what + " slot");
+}
+int check_component(vr_ctx* c, const std::string& who, const std::string& what, int k)
+{
+    return is_component(k) ? VR_OK : fail(c, VR_ERR_INVALID_ARG, who + ": the " + what + " must be 0 .. 3");
+}
+int check_filled(vr_ctx* c, const std::string& who, const char* what, int slot)
+{
+    return c->vols[slot].vol.data ? VR_OK : fail(c, VR_ERR_NOT_READY, who + ": " + what + " slot " + std::to_string(slot) + " is empty");
+}
 
 int check_box(vr_ctx* c, const std::string& who, const int32_t lo[3], const int32_t hi[3], const DevVolume& vol)
 {
@@ -41,18 +59,33 @@ BoxUnits box_units(const int32_t lo[3], const int32_t hi[3], unsigned long long*
     return B;
 }
 
+// The word rows of a volume's bit-rows that meet a (checked) box; *voxels = the voxels of the box.  An empty box has no words.
+BitRows bit_rows(const DevVolume& v, const int32_t lo[3], const int32_t hi[3], unsigned long long* voxels)
+{
+    BitRows B = {v.nx, v.ny, v.nz, (v.nx + 63) >> 6};  // (wx = ceil(nx / 64))
+    *voxels = 1;
+    for (int a = 0; a < 3; ++a) {
+        B.lo[a] = lo[a];
+        B.hi[a] = hi[a];
+        *voxels *= (unsigned long long)(hi[a] - lo[a]);
+    }
+    B.bw0 = B.lo[0] >> 6;
+    B.bw = ((B.hi[0] + 63) >> 6) - B.bw0;
+    B.box_words = *voxels == 0 ? 0ull : (unsigned long long)B.bw * (unsigned long long)(B.hi[1] - B.lo[1]) * (unsigned long long)(B.hi[2] - B.lo[2]);
+    return B;
+}
+
 void whole_box(const DevVolume& v, int32_t hi[3]) { hi[0] = v.nx, hi[1] = v.ny, hi[2] = v.nz; }  // (a descriptor's lo stays 0)
 
 unsigned tool_blocks(unsigned long long n) { return n < 4 ? 1u : (n / 4 < kToolBlocks ? (unsigned)(n / 4) : kToolBlocks); }
 
-// a device count and box into a result's voxels / lo / hi (zeroed before): the box only if anything was counted
-template <typename Result>
-void copy_count_box(const CountBox& b, Result* r)
+// a device count and box into a result's count / lo / hi (zeroed before): the box only if anything was counted
+void copy_count_box(const CountBox& b, uint64_t* voxels, int32_t lo[3], int32_t hi[3])
 {
-    r->voxels = b.voxels;
+    *voxels = b.voxels;
     for (int a = 0; a < 3 && b.voxels != 0; ++a) {
-        r->lo[a] = b.lo[a];
-        r->hi[a] = b.hi[a];
+        lo[a] = b.lo[a];
+        hi[a] = b.hi[a];
     }
 }
 

@@ -181,20 +181,20 @@ int check_hist(vr_ctx* c, const vr_hist_desc* d, const void* counts, const void*
 {
     const std::string w(who);
     if (!d || !counts || !rows) return fail(c, VR_ERR_INVALID_ARG, w + ": the descriptor or an output is NULL");
-    if (d->volume_slot < 0 || d->volume_slot >= VR_MAX_VOLUMES) return fail(c, VR_ERR_INVALID_ARG, w + ": bad volume slot");
-    if (d->mask_slot < -1 || d->mask_slot >= VR_MAX_VOLUMES) return fail(c, VR_ERR_INVALID_ARG, w + ": bad mask slot");
-    if (d->channel < 0 || d->channel > 3) return fail(c, VR_ERR_INVALID_ARG, w + ": the channel must be 0 .. 3");
+    if (const int rc = check_slot(c, w, "volume", d->volume_slot)) return rc;
+    if (d->mask_slot != -1)
+        if (const int rc = check_slot(c, w, "mask", d->mask_slot)) return rc;
+    if (const int rc = check_component(c, w, "channel", d->channel)) return rc;
     if (d->bins < 1 || d->bins > VR_HIST_MAX_BINS) return fail(c, VR_ERR_INVALID_ARG, w + ": bins must be 1 .. 65536");
     if (d->out_of_range != VR_HIST_CLAMP && d->out_of_range != VR_HIST_DROP) return fail(c, VR_ERR_INVALID_ARG, w + ": unknown out_of_range policy");
     if (d->rows == 0 || (d->rows >> VR_HIST_ROWS) != 0) return fail(c, VR_ERR_INVALID_ARG, w + ": rows must have a bit of 0 .. 4 set and none above");
     if ((d->rows & ~1u) != 0 && d->mask_slot < 0) return fail(c, VR_ERR_INVALID_ARG, w + ": contour rows need a mask slot");
+    if (const int rc = check_filled(c, w, "volume", d->volume_slot)) return rc;
     const DevVolume& v = c->vols[d->volume_slot].vol;
-    if (!v.data) return fail(c, VR_ERR_NOT_READY, w + ": volume slot " + std::to_string(d->volume_slot) + " is empty");
     if (const int rc = check_box(c, w, d->lo, d->hi, v)) return rc;
     if (d->mask_slot >= 0) {
-        const DevVolume& m = c->vols[d->mask_slot].vol;
-        if (!m.data) return fail(c, VR_ERR_NOT_READY, w + ": mask slot " + std::to_string(d->mask_slot) + " is empty");
-        return check_same_dims(c, w, "mask", m, "volume", v);
+        if (const int rc = check_filled(c, w, "mask", d->mask_slot)) return rc;
+        return check_same_dims(c, w, "mask", c->vols[d->mask_slot].vol, "volume", v);
     }
     return VR_OK;
 }
@@ -562,7 +562,7 @@ int vr_slice_counters(vr_ctx* c, uint64_t out[3])
 int vr_hist_whole(const vr_ctx* c, int slot, uint32_t bins, float scale, vr_hist_desc* out)
 {
     if (!c || !out) return VR_ERR_INVALID_ARG;
-    if (slot < 0 || slot >= VR_MAX_VOLUMES || bins < 1 || bins > VR_HIST_MAX_BINS) return VR_ERR_INVALID_ARG;
+    if (!is_slot(slot) || bins < 1 || bins > VR_HIST_MAX_BINS) return VR_ERR_INVALID_ARG;
     if (!c->vols[slot].vol.data) return VR_ERR_NOT_READY;
     std::memset(out, 0, sizeof *out);
     out->volume_slot = slot;

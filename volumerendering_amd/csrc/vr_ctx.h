@@ -37,6 +37,21 @@ struct Buf {
 template <typename T> using DevBuf = Buf<T, false>;
 template <typename T> using PinnedBuf = Buf<T, true>;
 
+// The device words of a tool and the pinned copy where the host sets them before a call's first kernel and reads them behind its last.
+template <typename T>
+struct WordsPair {
+    DevBuf<T> d;
+    PinnedBuf<T> h;
+    hipError_t first_use()
+    {
+        if (!d)
+            if (const hipError_t e = d.reserve(1)) return e;
+        return h ? hipSuccess : h.reserve(1, true);
+    }
+    hipError_t push(hipStream_t s) const { return hipMemcpyAsync(d.p, h.p, sizeof(T), hipMemcpyHostToDevice, s); }
+    hipError_t pull(hipStream_t s) const { return hipMemcpyAsync(h.p, d.p, sizeof(T), hipMemcpyDeviceToHost, s); }
+};
+
 struct Event {
     hipEvent_t e = nullptr;
     Event() = default;
@@ -154,6 +169,11 @@ struct ToolReport {
     Event ev[5];
     unsigned long long counters[3] = {0, 0, 0};
     float ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    // the counters of a tool that computes a part of its box and settles the rest
+    void computed_of_box(unsigned long long box, unsigned long long computed)
+    {
+        counters[0] = box, counters[1] = computed, counters[2] = box - computed;
+    }
 };
 
 // Region growing (vr_segment_grow, vr_grow.h): the working buffers of the last grow, grown on demand; what vr_grow_counters and
@@ -161,42 +181,35 @@ struct ToolReport {
 struct GrowState {
     DevBuf<unsigned long long> words;  // the bit-bricks: Q of every brick, then R of every brick
     DevBuf<unsigned> lists;            // per brick: the round stamp, then the frontier's two lists
-    DevBuf<GrowWords> d_words;         // counters, result and the rounds' words ...
-    PinnedBuf<GrowWords> h_words;      // ... and where the host sets and reads them
+    WordsPair<GrowWords> io;           // counters, result and the rounds' words
     ToolReport report;                 // phases: classify + seed, propagate, write, refresh_bricks
 };
 
-// Mask morphology (vr_mask_morph, vr_morph.h): the bit-row buffers of the last call, grown on demand; what vr_morph_counters and
-// vr_morph_timing report.
+// Mask morphology (vr_mask_morph, vr_morph.h): what vr_morph_counters and vr_morph_timing report.  Of vr_ctx::bit_row_scratch it takes three
+// buffers: the packed operand and the two a dilation pass writes in turn.
 struct MorphState {
-    DevBuf<unsigned long long> words;  // three bit-row buffers: the packed operand and the two a dilation pass writes in turn
     DevBuf<unsigned> rows;             // the element's rows ...
     PinnedBuf<unsigned> h_rows;        // ... and where the host sorts them
-    DevBuf<MorphWords> d_words;        // the counts and bounding boxes ...
-    PinnedBuf<MorphWords> h_words;     // ... and where the host sets and reads them
+    WordsPair<MorphWords> io;          // the counts and bounding boxes
     ToolReport report;                 // phases: pack, morphology, write, refresh_bricks
 };
 
 // Distance maps (vr_mask_distance, vr_dist.h): the working buffers of the last call, grown on demand; what vr_dist_counters and
-// vr_dist_timing report.
+// vr_dist_timing report.  Of vr_ctx::bit_row_scratch it takes two buffers: the packed contour and the packed probe.
 struct DistState {
-    DevBuf<unsigned long long> words;    // two bit-row buffers: the packed contour and the packed probe
     DevBuf<unsigned long long> d2[2];    // the OUTSIDE and the INSIDE field: one word per voxel of the field's region
     DevBuf<unsigned long long> stack_g;  // the envelope stacks of a line pass, one entry per voxel of the larger region ...
-    DevBuf<unsigned> stack_st;           // ... (vr_device.h: DistLine)
-    DevBuf<DistWords> d_words;           // the counts, the bounding box and the probe's range ...
-    PinnedBuf<DistWords> h_words;        // ... and where the host sets and reads them
+    DevBuf<unsigned> stack_st;           // ... (vr_dist.h: DistLine)
+    WordsPair<DistWords> io;             // the counts, the bounding box and the probe's range
     ToolReport report;                   // phases: pack, distance passes, write, refresh_bricks
 };
 
 // Polygon rasterisation (vr_mask_polygons, vr_raster.h): the working buffers of the last call, grown on demand; what
-// vr_polygons_counters and vr_polygons_timing report.
+// vr_polygons_counters and vr_polygons_timing report.  Of vr_ctx::bit_row_scratch it takes four buffers: R_k of every contour.
 struct RasterState {
-    DevBuf<unsigned long long> words;    // four bit-row buffers: R_k of every contour
     DevBuf<unsigned char> d_stage;       // the points, the polygons that are rasterised and the work items, one behind the other ...
     PinnedBuf<unsigned char> h_stage;    // ... and where the host puts them together
-    DevBuf<RasterWords> d_words;         // the counts and bounding boxes ...
-    PinnedBuf<RasterWords> h_words;      // ... and where the host sets and reads them
+    WordsPair<RasterWords> io;           // the counts and bounding boxes
     ToolReport report;                   // phases: upload, raster, write, refresh_bricks
 };
 
@@ -388,6 +401,9 @@ struct vr_ctx {
     const float* d_near = nullptr;
     const float* d_far = nullptr;
     GrowState grow;  // region growing (vr_segment_grow)
+    // The bit-row scratch of the three mask tools below (vr_bitrows.h), grown to the most words a call has asked for.  Each call drains
+    // the device, zeroes the buffers it takes before it reads them and is synchronous on return: no two uses are ever live.
+    DevBuf<unsigned long long> bit_row_scratch;
     MorphState morph;  // mask morphology (vr_mask_morph)
     DistState dist;    // distance maps (vr_mask_distance)
     RasterState raster;  // polygon rasterisation (vr_mask_polygons)

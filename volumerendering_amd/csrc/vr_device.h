@@ -214,109 +214,7 @@ struct GrowSeeds {
     int xyz[64][3];
 };
 
-// The device words of one vr_mask_morph (vr_morph.h): set by the host before the first kernel, read behind the pack and the write.
-struct MorphWords {
-    CountBox src;     // |A'| and its bounding box (both start as CountBox::empty())
-    CountBox result;  // |R| and its
-};
-
-// Kernel argument block of a vr_mask_morph (vr_morph.h; vr_morph_desc of include/vr.h): passed by value.
-struct MorphParams {
-    const float4* src;            // the source slot's x-fastest vec4 voxels
-    float4* dst;                  // the destination slot's
-    int src_contour, dst_contour;
-    int nx, ny, nz;               // of both slots
-    int wx;                       // words per row: ceil(nx / 64)
-    int lo[3], hi[3];             // the voxel box, half open
-    int bw0, bw;                  // the words of a row that meet the box: the first and their number ...
-    unsigned long long box_words; // ... and bw * rows * slices of the box (0 for an empty box)
-    unsigned long long* a;        // the packed operand A' (wx * ny * nz words, as every bit-row buffer)
-    const unsigned long long* r;  // the result R
-    const unsigned* rows;         // the element's rows: h | (dy + 32) << 8 | (dz + 32) << 16, sorted by h, largest first
-    int n_rows, hmax;
-    int combine;                  // VR_MORPH_REPLACE ..
-    int fresh;                    // the destination slot was created zeroed by this call: REPLACE stores R alone
-    MorphWords* w;
-};
-// One dilation launch: from src into the words of a region of dst (rw words from word rw0, ry rows from ry0, rz slices from rz0).
-struct MorphPass {
-    const unsigned long long* src;
-    unsigned long long* dst;
-    int rw0, rw, ry0, ry, rz0, rz;
-    unsigned long long words;     // rw * ry * rz
-};
-
-// The device words of one vr_mask_distance (vr_dist.h): set by the host before the first kernel, read behind the packs and the write.
-struct DistWords {
-    MorphWords src;    // .src = |A'| and its bounding box, from morph_pack_kernel (.result is not used)
-    MorphWords probe;  // the same of the probe's pack (only the packed bits are used)
-    unsigned long long beyond;                           // voxels of the box that store BEYOND's value
-    unsigned long long probe_voxels, probe_min, probe_max;  // of D2out over the probe (min starts as ~0, max as 0)
-};
-
-// One squared-distance field of a vr_mask_distance: uint64_t per voxel of a REGION of the box, x fastest, kDistNone = no source.
-struct DistField {
-    unsigned long long* d2;
-    int lo[3], n[3];  // the region: first voxel and extent per axis (some n == 0: empty, nothing was computed)
-};
-// The x pass over the words of a field's region (vr_dist.h): from the bit-rows `bits` into F.d2.
-struct DistXPass {
-    const unsigned long long* bits;  // the packed operand A' (MorphParams::a)
-    DistField F;
-    int ny, wx;                      // rows per slice and words per row of the bit-rows
-    int rw0, rw;                     // the words of a row that meet the region: the first and their number ...
-    unsigned long long words;        // ... and rw * rows * slices of the region
-    unsigned long long spacing;      // of x
-};
-// One envelope pass along y or z: lane t works the line d2[(t / inner) * outer + t % inner + i * stride], i < n.
-struct DistLine {
-    unsigned long long* d2;
-    unsigned long long lanes, inner, outer, stride;
-    int n;
-    unsigned long long spacing;      // of the line's axis
-    unsigned long long* stack_g;     // the envelope's stacks, entry q of lane t at [q * lanes + t]: a parabola's g ...
-    unsigned* stack_st;              // ... and its apex s | the first index t where it is the lowest << 16
-};
-// Kernel argument block of the write of a vr_mask_distance (vr_dist.h; vr_dist_desc of include/vr.h): passed by value.
-struct DistParams {
-    MorphParams m;                    // the box walk and the packed operand (m.a); m.dst / m.dst_contour = where the distances go
-    const unsigned long long* probe;  // the packed probe, nullptr = none
-    DistField out, in;                // D2out and D2in (a field the mode does not need is empty and not read)
-    int mode;                         // VR_DIST_OUTSIDE ..
-    unsigned long long limit_sq;      // 0 = no limit
-    float scale, beyond_value;        // (float)L * scale, or +inf
-    DistWords* w;
-};
-
-// One polygon of a vr_mask_polygons as the raster kernel reads it (vr_raster.h).
-struct RasterPoly {
-    unsigned first, count;  // its points: pts[first .. first + count)
-    int slice, contour;
-    int s0, s1;             // the voxels of a row it can set, within the box along x: [s0, s1), s0 < s1
-};
-// One work item of the raster kernel: `rows` rows from row j0 of polygon `poly`.
-struct RasterItem {
-    unsigned poly;
-    unsigned short j0, rows;
-};
-// The device words of one vr_mask_polygons: |R_k| and its bounding box per contour (each starts as CountBox::empty()).
-struct RasterWords {
-    CountBox r[4];
-};
-// Kernel argument block of a vr_mask_polygons (vr_raster.h; vr_polygons_desc of include/vr.h): passed by value.
-struct RasterParams {
-    MorphParams m;                 // the box walk of the write: dst, nx, ny, nz, wx, lo, hi, bw0, bw, box_words, combine, fresh
-    unsigned long long* bits[4];   // the bit-rows R_k (wx * ny * nz words each, zeroed before the raster)
-    int contours;                  // bit k: contour k is written
-    long long ox, oy;              // the centre of voxel (0, 0)
-    long long sx, sy;              // the voxel pitch
-    const int2* pts;
-    const RasterPoly* polys;
-    const RasterItem* items;
-    unsigned n_items;
-    RasterWords* w;
-};
-
+// (The argument blocks of the bit-row mask tools live with their kernels: vr_bitrows.h, vr_morph.h, vr_dist.h, vr_raster.h.)
 // Work queue of the persistent-wavefront kernel (vr_pw.h): eight heads, one per class of the workgroup index modulo 8,
 // zero at launch; heads[c * 64] counts the items of class c handed out beyond every wavefront's first.
 struct PwQueue {

@@ -1,12 +1,12 @@
 // vr_dist.h -- exact signed distance maps of a mask contour on the device (vr_mask_distance, include/vr.h): the Euclidean distance
 // transform of one contour of a mask slot, restricted to a box, on an anisotropic grid with integer spacings, written as f32 into one
 // component of a volume slot.  Exact integer arithmetic up to the final square root: nothing can be fused, so vr_set_arithmetic plays no
-// part and the kernels are compiled once, included by vr_api.hip alone, behind vr_morph.h whose bit-rows, pack and box walk they use.
+// part and the kernels are compiled once, included by vr_api.hip alone.  The bit-rows, their pack and the box walk are vr_bitrows.h's.
 //
 // The transform is separable: D2(p) = min over y' of ((y - y') sy)^2 + [min over x' of ((x - x') sx)^2 in row y'], and the same once
 // more along z.  A FIELD is one uint64_t per voxel of a region of the box (DistField), kDistNone where no source voxel has been met.
 //
-// x pass (dist_x_kernel): from the bit-rows morph_pack_kernel packed.  Persistent workgroups of four wavefronts, one wavefront per word
+// x pass (dist_x_kernel): from the bit-rows bit_pack_kernel packed.  Persistent workgroups of four wavefronts, one wavefront per word
 // of the region, one lane per voxel.  The nearest set bit at or left of a lane and at or right of it come from clz / ffs on the lane's
 // own word; where the word has none on that side, from the nearest non-empty word of the row, which the wavefront looks for once for
 // all its lanes (uniform loads).  The lane stores ((distance in voxels) * sx)^2, or kDistNone for a row without a set bit.  COMP: the
@@ -27,8 +27,54 @@
 //
 // No kernel waits for another workgroup and nothing spins: the launch boundaries are the visibility points.
 #pragma once
+#include "vr_bitrows.h"
 
 namespace vr {
+
+// The device words of one vr_mask_distance: set by the host before the first kernel, read behind the packs and the write.
+struct DistWords {
+    CountBox src;    // |A'| and its bounding box, from the pack (starts as CountBox::empty())
+    CountBox probe;  // where the probe's pack reports (only its packed bits are used)
+    unsigned long long beyond;                           // voxels of the box that store BEYOND's value
+    unsigned long long probe_voxels, probe_min, probe_max;  // of D2out over the probe (min starts as ~0, max as 0)
+};
+
+// One squared-distance field of a vr_mask_distance: uint64_t per voxel of a REGION of the box, x fastest, kDistNone = no source.
+struct DistField {
+    unsigned long long* d2;
+    int lo[3], n[3];  // the region: first voxel and extent per axis (some n == 0: empty, nothing was computed)
+};
+// The x pass over the words of a field's region: from the bit-rows `bits` into F.d2.
+struct DistXPass {
+    const unsigned long long* bits;  // the packed operand A'
+    DistField F;
+    int ny, wx;                      // rows per slice and words per row of the bit-rows
+    int rw0, rw;                     // the words of a row that meet the region: the first and their number ...
+    unsigned long long words;        // ... and rw * rows * slices of the region
+    unsigned long long spacing;      // of x
+};
+// One envelope pass along y or z: lane t works the line d2[(t / inner) * outer + t % inner + i * stride], i < n.
+struct DistLine {
+    unsigned long long* d2;
+    unsigned long long lanes, inner, outer, stride;
+    int n;
+    unsigned long long spacing;      // of the line's axis
+    unsigned long long* stack_g;     // the envelope's stacks, entry q of lane t at [q * lanes + t]: a parabola's g ...
+    unsigned* stack_st;              // ... and its apex s | the first index t where it is the lowest << 16
+};
+// Kernel argument block of the write of a vr_mask_distance (vr_dist_desc of include/vr.h): passed by value.
+struct DistParams {
+    BitRows b;                        // the volume, the box and its words
+    const unsigned long long* a;      // the packed operand A'
+    const unsigned long long* probe;  // the packed probe, nullptr = none
+    float4* dst;                      // the destination slot's x-fastest vec4 voxels ...
+    int dst_channel;                  // ... and the component the distances go into
+    DistField out, in;                // D2out and D2in (a field the mode does not need is empty and not read)
+    int mode;                         // VR_DIST_OUTSIDE ..
+    unsigned long long limit_sq;      // 0 = no limit
+    float scale, beyond_value;        // (float)L * scale, or +inf
+    DistWords* w;
+};
 
 constexpr unsigned long long kDistNone = ~0ull;  // no source voxel: BEYOND
 
@@ -58,7 +104,7 @@ template <bool COMP>
 __device__ __forceinline__ unsigned long long dist_src_word(const DistXPass& X, const unsigned long long* row, int xw)
 {
     const unsigned long long w = row[xw];
-    return (COMP ? ~w : w) & morph_xmask(xw, X.F.lo[0], X.F.lo[0] + X.F.n[0]);
+    return (COMP ? ~w : w) & bit_xmask(xw, X.F.lo[0], X.F.lo[0] + X.F.n[0]);
 }
 
 template <bool COMP>
@@ -171,17 +217,17 @@ __global__ __launch_bounds__(256) void dist_write_kernel(const DistParams P)
 {
     const unsigned lane = threadIdx.x & 63u;
     const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    float* const out = reinterpret_cast<float*>(P.m.dst) + P.m.dst_contour;
+    float* const out = reinterpret_cast<float*>(P.dst) + P.dst_channel;
     unsigned long long n_beyond = 0ull, n_probe = 0ull;     // (wave-uniform)
     unsigned long long p_min = kDistNone, p_max = 0ull;     // (per lane)
     const unsigned long long W = (unsigned long long)gridDim.x * 4ull;
-    for (unsigned long long u = (unsigned long long)blockIdx.x * 4ull + wave; u < P.m.box_words; u += W) {
+    for (unsigned long long u = (unsigned long long)blockIdx.x * 4ull + wave; u < P.b.box_words; u += W) {
         int xw, y, z;
-        morph_box_word(P.m, u, xw, y, z);
-        const size_t word = ((size_t)z * (size_t)P.m.ny + (size_t)y) * (size_t)P.m.wx + (size_t)xw;
-        const unsigned long long aw = P.m.a[word];
+        bit_box_word(P.b, u, xw, y, z);
+        const size_t word = ((size_t)z * (size_t)P.b.ny + (size_t)y) * (size_t)P.b.wx + (size_t)xw;
+        const unsigned long long aw = P.a[word];
         const unsigned long long pw = P.probe ? P.probe[word] : 0ull;  // (zero outside the box)
-        const unsigned long long box = morph_xmask(xw, P.m.lo[0], P.m.hi[0]);
+        const unsigned long long box = bit_xmask(xw, P.b.lo[0], P.b.hi[0]);
         const bool in_box = (box >> lane) & 1ull, in_a = (aw >> lane) & 1ull;
         const int x = (xw << 6) + (int)lane;
         bool beyond = false;
@@ -193,7 +239,7 @@ __global__ __launch_bounds__(256) void dist_write_kernel(const DistParams P)
             if (P.limit_sq != 0ull && d2 != kDistNone && d2 > P.limit_sq) d2 = kDistNone;
             beyond = d2 == kDistNone;
             const float m = beyond ? P.beyond_value : sqrtf((float)d2) * P.scale;
-            const size_t idx = ((size_t)z * (size_t)P.m.ny + (size_t)y) * (size_t)P.m.nx + (size_t)x;
+            const size_t idx = ((size_t)z * (size_t)P.b.ny + (size_t)y) * (size_t)P.b.nx + (size_t)x;
             out[idx * 4u] = (P.mode == VR_DIST_SIGNED && in_a) ? -m : m;
             if ((pw >> lane) & 1ull) {  // (a probe comes with OUTSIDE or SIGNED only: d2 is D2out unless the voxel is in A', where that is 0)
                 const unsigned long long d2out = in_a ? 0ull : d2;

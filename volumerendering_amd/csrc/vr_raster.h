@@ -2,7 +2,7 @@
 // are scan-converted into the contours of a mask slot.  Exact integer arithmetic: nothing can be fused, so vr_set_arithmetic plays no
 // part and the kernels are compiled once, included by vr_api.hip alone.
 //
-// State: BIT-ROWS as in vr_morph.h, one buffer R_k per contour, zeroed by a memset before the raster.
+// State: BIT-ROWS (vr_bitrows.h: their layout, the box walk, the write's combine rule), one buffer R_k per contour, zeroed before the raster.
 //
 // Raster (raster_rows_kernel<UNION>): persistent workgroups of four wavefronts; a wavefront takes one work item at a time, a short run
 // of rows of ONE polygon (the host derives the items from each polygon's y span cut to the box, vr_api_raster.h).  For a row j with
@@ -19,11 +19,44 @@
 // is the visibility point.
 //
 // Write (raster_write_kernel): one wavefront per word of the box, one lane per voxel; for each contour of `contours` one 4-byte vector
-// store into its component and only where `combine` stores something (the rule of morph_write_kernel); words that store nothing are
+// store into its component and only where `combine` stores something (BitCombine, the rule of vr_mask_morph); words that store nothing are
 // skipped.  |R_k| and the boxes from the R_k words.
 #pragma once
+#include "vr_bitrows.h"
+#include "vr_lt.h"  // wave_lds_fence
 
 namespace vr {
+
+// One polygon of a vr_mask_polygons as the raster kernel reads it.
+struct RasterPoly {
+    unsigned first, count;  // its points: pts[first .. first + count)
+    int slice, contour;
+    int s0, s1;             // the voxels of a row it can set, within the box along x: [s0, s1), s0 < s1
+};
+// One work item of the raster kernel: `rows` rows from row j0 of polygon `poly`.
+struct RasterItem {
+    unsigned poly;
+    unsigned short j0, rows;
+};
+// The device words of one vr_mask_polygons: |R_k| and its bounding box per contour (each starts as CountBox::empty()).
+struct RasterWords {
+    CountBox r[4];
+};
+// Kernel argument block of a vr_mask_polygons (vr_polygons_desc of include/vr.h): passed by value.
+struct RasterParams {
+    float4* dst;                   // the destination slot's x-fastest vec4 voxels
+    BitRows b;                     // the volume, the box and its words
+    BitCombine c;                  // how every R_k is stored
+    unsigned long long* bits[4];   // the bit-rows R_k (wx * ny * nz words each, zeroed before the raster)
+    int contours;                  // bit k: contour k is written
+    long long ox, oy;              // the centre of voxel (0, 0)
+    long long sx, sy;              // the voxel pitch
+    const int2* pts;
+    const RasterPoly* polys;
+    const RasterItem* items;
+    unsigned n_items;
+    RasterWords* w;
+};
 
 constexpr int kRasterRowWords = 1024;  // the words of the longest row: 65535 voxels
 
@@ -81,9 +114,9 @@ __global__ __launch_bounds__(256) void raster_rows_kernel(const RasterParams P)
                 if ((((unsigned)__popcll(above)) + carry) & 1u) s = ~s;
                 carry ^= (unsigned)__popcll(par) & 1u;
                 if (w < nw) {
-                    s &= morph_xmask(w0 + w, G.s0, G.s1);
+                    s &= bit_xmask(w0 + w, G.s0, G.s1);
                     if (s != 0ull) {
-                        unsigned long long* const dst = bits + ((size_t)G.slice * (size_t)P.m.ny + (size_t)j) * (size_t)P.m.wx + (size_t)(w0 + w);
+                        unsigned long long* const dst = bits + ((size_t)G.slice * (size_t)P.b.ny + (size_t)j) * (size_t)P.b.wx + (size_t)(w0 + w);
                         if constexpr (UNION) atomicOr(dst, s);
                         else atomicXor(dst, s);
                     }
@@ -98,28 +131,25 @@ __global__ __launch_bounds__(256) void raster_write_kernel(const RasterParams P)
 {
     const unsigned lane = threadIdx.x & 63u;
     const unsigned wave = (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    float* const out = reinterpret_cast<float*>(P.m.dst);
+    float* const out = reinterpret_cast<float*>(P.dst);
     CountBox n[4] = {CountBox::empty(), CountBox::empty(), CountBox::empty(), CountBox::empty()};  // (wave-uniform)
     const unsigned long long W = (unsigned long long)gridDim.x * 4ull;
-    for (unsigned long long u = (unsigned long long)blockIdx.x * 4ull + wave; u < P.m.box_words; u += W) {
+    for (unsigned long long u = (unsigned long long)blockIdx.x * 4ull + wave; u < P.b.box_words; u += W) {
         int xw, y, z;
-        morph_box_word(P.m, u, xw, y, z);
-        const size_t wi = ((size_t)z * (size_t)P.m.ny + (size_t)y) * (size_t)P.m.wx + (size_t)xw;
-        const size_t idx = ((size_t)z * (size_t)P.m.ny + (size_t)y) * (size_t)P.m.nx + (size_t)(xw << 6) + (size_t)lane;
-        const unsigned long long box = morph_xmask(xw, P.m.lo[0], P.m.hi[0]);
+        bit_box_word(P.b, u, xw, y, z);
+        const size_t wi = ((size_t)z * (size_t)P.b.ny + (size_t)y) * (size_t)P.b.wx + (size_t)xw;
+        const size_t idx = ((size_t)z * (size_t)P.b.ny + (size_t)y) * (size_t)P.b.nx + (size_t)(xw << 6) + (size_t)lane;
+        const unsigned long long box = bit_xmask(xw, P.b.lo[0], P.b.hi[0]);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if (!((P.contours >> k) & 1)) continue;
             const unsigned long long rw = P.bits[k][wi];  // (zero outside the box)
-            // the voxels that are stored: REPLACE all of the box (only R where the slot was created zeroed), OR and ANDNOT R, AND the rest
-            unsigned long long st = rw;
-            if (P.m.combine == VR_MORPH_REPLACE) st = P.m.fresh ? rw : box;
-            else if (P.m.combine == VR_MORPH_AND) st = box & ~rw;
+            const unsigned long long st = P.c.stores(rw, box);
             if (st != 0ull) {
                 const bool set = (rw >> lane) & 1ull;
-                if ((st >> lane) & 1ull) out[idx * 4u + (size_t)k] = (set && P.m.combine <= VR_MORPH_OR) ? 1.0f : 0.0f;
+                if ((st >> lane) & 1ull) out[idx * 4u + (size_t)k] = P.c.value(set);
             }
-            morph_fold(rw, xw, y, z, n[k]);
+            bit_fold(rw, xw, y, z, n[k]);
         }
     }
     if (lane == 0u) {

@@ -1,7 +1,7 @@
-// vr_units.h -- what the voxel tools share on the device (histograms vr_hist.h, region growing vr_grow.h, mask morphology vr_morph.h,
-// distance maps vr_dist.h):
-// a voxel box and the 4 x 4 x 4 BRICK UNITS of the volume's own brick grid that meet it, one step of the walk over them (the launch
-// shape is described in vr_hist.h), and how a kernel reports.  vr_device.h includes it: the structs are members of its argument blocks.
+// vr_units.h -- what the voxel tools share on the device.  Histograms (vr_hist.h) and region growing (vr_grow.h): a voxel box and the
+// 4 x 4 x 4 BRICK UNITS of the volume's own brick grid that meet it, one step of the walk over them (the launch shape is described in
+// vr_hist.h).  They and the bit-row tools (vr_bitrows.h, which has the walk over word rows; vr_morph.h, vr_dist.h, vr_raster.h): how a
+// kernel reports (CountBox).  vr_device.h includes it: the structs are members of its argument blocks.
 // (The two walks keep their own n_box / n_load / n_settled tail: a shared helper moved hist_kernel's row loop, masked histograms lost 1 %.)
 #pragma once
 
