@@ -1059,6 +1059,82 @@ int vr_polygons_counters(vr_ctx* ctx, uint64_t out[3]);
  * before the first and after one that failed. */
 int vr_polygons_timing(vr_ctx* ctx, float ms[4]);
 
+/* ---- contour tracing: the contours of a mask slot as closed planar polygons --------------------------------------------------------
+ * The inverse of vr_mask_polygons: the contours of a mask slot, slice by slice, become closed rectilinear polygons in the points /
+ * vr_polygon layout that vr_mask_polygons reads -- on the device (csrc/vr_outline.h), so that a structure that was grown, given a margin
+ * or cut can be stored as outlines, or drawn over a slice view, without its volume passing through the host.  Everything is integer
+ * arithmetic; the output is exact and does not depend on scheduling.  The call reads slots and writes none.
+ *   Set: for contour k and slice z of the box, S holds the voxels (i, j) of the box whose component k is != 0.0f (the membership rule of
+ *     the other mask tools: NaN is in, -0 is out).  Everything outside the box is out.
+ *   Cracks: lattice vertex (i, j), 0 <= i <= nx, 0 <= j <= ny, is the lower-left corner of voxel (i, j).  For every voxel of S and each
+ *     of its four sides whose neighbour is not in S there is one directed unit edge with the voxel on its LEFT: with x to the right and
+ *     y up, outer boundaries run counter-clockwise and holes clockwise.  Directions: 0 = +x, 1 = +y, 2 = -x, 3 = -y.  An edge's key is
+ *     (j * (nx + 1) + i) * 4 + direction, of its tail vertex (i, j).
+ *   Successor: an edge's successor is an edge that leaves its head vertex.  At a vertex where two edges leave (two diagonal voxels in,
+ *     the other two out) VR_OUTLINE_SPLIT takes the left turn, which separates the two voxels, and VR_OUTLINE_JOIN the right turn, which
+ *     connects them.  Every edge has exactly one successor and one predecessor: the edges fall into disjoint loops.
+ *   Polygons: one per loop.  Its points are the tails of the loop's edges whose predecessor has another direction (the corners), in
+ *     loop order, the first point the tail of the loop's edge with the smallest key: always a corner, and the lowest-then-leftmost
+ *     vertex of the loop.  A polygon has an even number of points, at least 4, and no three consecutive collinear ones.
+ *   Order: polygons are sorted by contour, then slice, then the key of their first edge; their points follow in the same order, `first`
+ *     running.  vr_polygon.slice = z, .contour = k.
+ *   Coordinates: vertex (i, j) is written as (origin[0] + i * spacing[0] - offset[0], origin[1] + j * spacing[1] - offset[1]), with
+ *     0 <= offset[a] < spacing[a]; origin is the CENTRE of voxel (0, 0) as in vr_polygons_desc.  With offset = spacing / 2 (an even
+ *     spacing) the points lie on the geometric voxel faces.  For ANY offset in that range and either connect rule, vr_mask_polygons of
+ *     the output with the same origin and spacing, VR_POLY_EVEN_ODD and VR_MORPH_REPLACE over the same box reproduces S exactly: a
+ *     face at centre - d, 0 <= d < spacing, cuts between the same two centres under the raster's half-open tie rule.  The origin lies
+ *     within +-2^29 and so does every vertex of the box (0 <= lo <= i <= hi), else VR_ERR_INVALID_ARG.
+ *   Capacity: max_points == max_polygons == 0 is the counting call: VR_OK, the result filled.  If either buffer is too small both
+ *     arrays are left untouched, the result is filled all the same, the call returns VR_ERR_INVALID_ARG and vr_last_error names both
+ *     needed counts.  More than 2^31 - 1 corners in one call: VR_ERR_UNSUPPORTED.
+ *   Result: n_points, n_polygons = what the mask needs; per contour k its polygons, its points and area2[k] = twice the signed area of
+ *     its polygons in lattice units = 2 * the voxels of the contour in the box.  Zeros for a contour that is not traced.
+ *   Counters (vr_outlines_counters): out[0] = corner nodes (= n_points), out[1] = polygons, out[2] = doubling rounds launched.
+ * Kernel forms: every flavour of vr_set_kernel_flavour but 1 stops the rounds that rank the corners along their loops after the first
+ * round that changes nothing; flavour 1 runs ceil(log2(corners)) rounds.  Everything but out[2] is identical across the forms and the
+ * volume layouts. */
+#define VR_OUTLINE_SPLIT 0   /* voxels that touch only at a corner are separated */
+#define VR_OUTLINE_JOIN  1   /* ... are connected                                 */
+typedef struct vr_outlines_desc {
+    int32_t  src_slot;                 /* an uploaded slot                                                       */
+    int32_t  contours;                 /* bit k set: contour k is traced (1 .. 15)                               */
+    int32_t  connect;                  /* VR_OUTLINE_SPLIT / VR_OUTLINE_JOIN                                     */
+    int32_t  box_lo[3], box_hi[3];     /* voxel box, half open; voxels outside it count as not in                */
+    int32_t  origin[2];                /* x, y of the CENTRE of voxel (0, 0), as in vr_polygons_desc             */
+    uint32_t spacing[2];               /* voxel pitch along x, y in the same unit: 1 .. 2^20                     */
+    uint32_t offset[2];                /* 0 <= offset[a] < spacing[a]: see Coordinates                           */
+    uint32_t max_points, max_polygons; /* what the two arrays hold                                               */
+    int32_t*    points;                /* host memory, max_points pairs (x, y); NULL iff max_points == 0         */
+    vr_polygon* polygons;              /* host memory; NULL iff max_polygons == 0                                */
+} vr_outlines_desc;
+typedef struct vr_outlines_result {
+    uint32_t n_points, n_polygons;     /* what the mask needs, whether or not it was stored                      */
+    uint32_t polygons_of[4], points_of[4];
+    int64_t  area2[4];                 /* twice the signed area in lattice units: 2 * voxels of the contour in the box */
+} vr_outlines_result;
+
+/* Fills *out for the whole volume of src_slot: contour 0 alone (contours = 1), VR_OUTLINE_SPLIT, the box (0,0,0) .. (nx,ny,nz), origin
+ * (0, 0), unit spacing, offset 0 and no buffers.  Pure host arithmetic; VR_ERR_INVALID_ARG for a NULL pointer or a slot out of range,
+ * VR_ERR_NOT_READY for an empty slot. */
+int vr_outlines_whole(const vr_ctx* ctx, int src_slot, vr_outlines_desc* out);
+
+/* Does the work; `result` may be NULL.  A synchronous data call on the ctx's own stream: it waits for everything in flight, writes no
+ * slot, rebuilds nothing that is derived from one, and leaves what the reporting calls say about earlier launches and tools as it was.
+ * An empty box or an empty contour gives zero polygons and VR_OK.
+ * Checked before anything is enqueued.  VR_ERR_INVALID_ARG: a NULL ctx or descriptor; a slot out of range; `contours` outside 1 .. 15;
+ * an unknown connect; a box that is not 0 <= lo <= hi <= n on every axis; a spacing of 0 or above 2^20; an offset that is not below its
+ * spacing; an origin value or a vertex of the box outside +-2^29; points or polygons NULL with a capacity, or given with none.
+ * VR_ERR_NOT_READY: the slot is empty.  VR_ERR_OOM: the working buffers could not be allocated. */
+int vr_mask_outlines(vr_ctx* ctx, const vr_outlines_desc* desc, vr_outlines_result* result);
+
+/* Counters of the last vr_mask_outlines that got as far as counting (as described above).  Zeros before the first. */
+int vr_outlines_counters(vr_ctx* ctx, uint64_t out[3]);
+
+/* Device time of the last vr_mask_outlines in milliseconds, from events on the ctx's stream: ms[0] the pack of the contours, ms[1] the
+ * corners, their scan and the links, ms[2] the doubling rounds (the host's looks at their outcome included), ms[3] the polygons' scans,
+ * the emit and the copy back.  Zeros before the first, after one that failed, and for the phases a call did not reach. */
+int vr_outlines_timing(vr_ctx* ctx, float ms[4]);
+
 /* Volume layout in HBM (A/B measurements; frames and counts are bit-identical in every mode).
  *   0  default: the march kernels gather from a BRICKED copy of every slot -- the vec4 voxels and a scalar f32 density plane
  *      (what fetches that consume .a alone read: BasicVolumeApp.wgsl:171, the density / dose fetches of the other shaders)

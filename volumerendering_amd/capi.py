@@ -44,6 +44,7 @@ MORPH_REPLACE, MORPH_OR, MORPH_AND, MORPH_ANDNOT = range(4)                 # vr
 DIST_OUTSIDE, DIST_INSIDE, DIST_SIGNED = range(3)                           # vr_dist_desc.mode (include/vr.h)
 POLY_EVEN_ODD, POLY_UNION = 0, 1                                            # vr_polygons_desc.rule (include/vr.h)
 POLY_MAX_COORD, POLY_MAX_SPACING = 1 << 29, 1 << 20                         # of a point coordinate or origin value (magnitude), a spacing
+OUTLINE_SPLIT, OUTLINE_JOIN = 0, 1                                          # vr_outlines_desc.connect (include/vr.h)
 DIST_MAX_SPACING, DIST_MAX_LIMIT, DIST_MAX_EXTENT = 1 << 20, 1 << 31, 1 << 30  # of a spacing, the limit, (hi - lo) * spacing per axis
 
 # every symbol include/vr.h declares (tests check that the library exports each of them)
@@ -67,6 +68,7 @@ ABI_SYMBOLS = [
     "vr_morph_ball", "vr_morph_box", "vr_morph_whole", "vr_mask_morph", "vr_morph_counters", "vr_morph_timing",
     "vr_dist_whole", "vr_mask_distance", "vr_dist_counters", "vr_dist_timing",
     "vr_polygons_whole", "vr_mask_polygons", "vr_polygons_counters", "vr_polygons_timing",
+    "vr_outlines_whole", "vr_mask_outlines", "vr_outlines_counters", "vr_outlines_timing",
 ]
 
 
@@ -279,6 +281,40 @@ class PolygonsResult(C.Structure):
         return tuple((int(self.voxels[k]), tuple(int(x) for x in self.lo[k]), tuple(int(x) for x in self.hi[k])) for k in range(4))
 
 
+class OutlinesDesc(C.Structure):
+    """struct vr_outlines_desc (include/vr.h): the source slot, the contours traced, the connect rule, the voxel box, the grid's origin,
+    spacing and offset, and the capacities and arrays of the output (set by Context.mask_outlines)."""
+    _fields_ = [
+        ("src_slot", C.c_int32), ("contours", C.c_int32), ("connect", C.c_int32),
+        ("box_lo", C.c_int32 * 3), ("box_hi", C.c_int32 * 3), ("origin", C.c_int32 * 2), ("spacing", C.c_uint32 * 2), ("offset", C.c_uint32 * 2),
+        ("max_points", C.c_uint32), ("max_polygons", C.c_uint32), ("points", C.c_void_p), ("polygons", C.c_void_p),
+    ]
+
+    def copy(self, **over) -> "OutlinesDesc":
+        """A copy with the given fields replaced (box_lo / box_hi from any sequence of three integers, origin / spacing / offset of two)."""
+        d = OutlinesDesc.from_buffer_copy(bytes(self))
+        for k, v in over.items():
+            if k in ("box_lo", "box_hi"):
+                v = (C.c_int32 * 3)(*[int(x) for x in v])
+            if k == "origin":
+                v = (C.c_int32 * 2)(*[int(x) for x in v])
+            if k in ("spacing", "offset"):
+                v = (C.c_uint32 * 2)(*[int(x) for x in v])
+            setattr(d, k, v)
+        return d
+
+
+class OutlinesResult(C.Structure):
+    """struct vr_outlines_result: the points and polygons the mask needs, and per contour its polygons, points and twice its area."""
+    _fields_ = [("n_points", C.c_uint32), ("n_polygons", C.c_uint32), ("polygons_of", C.c_uint32 * 4), ("points_of", C.c_uint32 * 4),
+                ("area2", C.c_int64 * 4)]
+
+    def as_tuple(self):
+        """(n_points, n_polygons, polygons_of, points_of, area2)"""
+        return (int(self.n_points), int(self.n_polygons), tuple(int(x) for x in self.polygons_of), tuple(int(x) for x in self.points_of),
+                tuple(int(x) for x in self.area2))
+
+
 class VrError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"vr error {code}: {msg}")
@@ -382,6 +418,10 @@ def load() -> C.CDLL:
     lib.vr_mask_polygons.argtypes = [vp, C.POINTER(PolygonsDesc), C.POINTER(PolygonsResult)]
     lib.vr_polygons_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
     lib.vr_polygons_timing.argtypes = [vp, C.POINTER(C.c_float * 4)]
+    lib.vr_outlines_whole.argtypes = [vp, i32, C.POINTER(OutlinesDesc)]
+    lib.vr_mask_outlines.argtypes = [vp, C.POINTER(OutlinesDesc), C.POINTER(OutlinesResult)]
+    lib.vr_outlines_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
+    lib.vr_outlines_timing.argtypes = [vp, C.POINTER(C.c_float * 4)]
     lib.vr_present_async.argtypes = [vp, vp, vp, vp]
     lib.vr_present_tiles_async.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
     lib.vr_hint_frames_in_flight.argtypes = [vp, i32]
@@ -826,6 +866,33 @@ class Context:
     def polygons_timing(self):
         """(upload, raster, write, refresh) of the last mask_polygons in ms of device time (vr_polygons_timing)."""
         return self._tool_timing(self.lib.vr_polygons_timing)
+
+    def outlines_whole(self, src_slot: int) -> OutlinesDesc:
+        """vr_outlines_whole: the descriptor of a trace over the whole volume (contour 0, SPLIT, origin 0, unit spacing, offset 0)."""
+        d = OutlinesDesc()
+        self._chk(self.lib.vr_outlines_whole(self.h, src_slot, C.byref(d)))
+        return d
+
+    def mask_outlines(self, desc: OutlinesDesc):
+        """vr_mask_outlines: traces contours of a mask slot into closed polygons (synchronous): the counting call, then the call that
+        stores.  Returns (points int32 (N, 2), polygons [(first, count, slice, contour)], OutlinesResult); the first two can be passed
+        straight to mask_polygons.  The descriptor's own capacities and arrays are ignored."""
+        out = OutlinesResult()
+        self._chk(self.lib.vr_mask_outlines(self.h, C.byref(desc.copy(max_points=0, max_polygons=0, points=None, polygons=None)), C.byref(out)))
+        pts = np.zeros((int(out.n_points), 2), np.int32)
+        polys = (Polygon * int(out.n_polygons))()
+        if out.n_points:
+            d = desc.copy(max_points=len(pts), max_polygons=len(polys), points=pts.ctypes.data, polygons=C.cast(polys, C.c_void_p).value)
+            self._chk(self.lib.vr_mask_outlines(self.h, C.byref(d), C.byref(out)))  # (pts and polys live until here)
+        return pts, [(int(q.first), int(q.count), int(q.slice), int(q.contour)) for q in polys], out
+
+    def outlines_counters(self):
+        """(corner nodes, polygons, doubling rounds launched) of the last mask_outlines."""
+        return self._tool_counters(self.lib.vr_outlines_counters)
+
+    def outlines_timing(self):
+        """(pack, corners + scan + link, doubling rounds, emit + copy back) of the last mask_outlines in ms of device time."""
+        return self._tool_timing(self.lib.vr_outlines_timing)
 
     def set_volume_layout(self, mode: int):
         """0 bricked copy (default), 1 the reference's vec4 voxels only, 3 x-fastest voxels + density plane (2 was removed)."""

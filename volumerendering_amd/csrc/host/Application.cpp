@@ -276,6 +276,69 @@ int Application::ContoursToMask(const StructureFileDcm& structures, std::array<i
     return RasterPolygons(d, out);
 }
 
+int Application::MaskOutlines(const vr_outlines_desc& desc, vr_outlines_result* out)
+{
+    if (!p_Ctx) return VR_ERR_NOT_READY;
+    const int rc = vr_mask_outlines(p_Ctx, &desc, out);
+    if (rc != VR_OK) m_Error = vr_last_error(p_Ctx);
+    return rc;
+}
+
+int Application::MaskToContours(int srcSlot, int contours, int connect, const VolumeFileDcm& grid, std::vector<std::vector<std::vector<float>>>& out)
+{
+    if (!p_Ctx) return VR_ERR_NOT_READY;
+    const DicomVolumeParams p = grid.GetVolumeParams();
+    // whole micrometres within the range of vr_mask_outlines, or false
+    auto um = [](double mm, int32_t* v) {
+        if (!std::isfinite(mm) || std::fabs(mm) * 1000.0 > (double)(1 << 29)) return false;
+        *v = (int32_t)std::llround(mm * 1000.0);
+        return true;
+    };
+    vr_outlines_desc d;
+    int rc = vr_outlines_whole(p_Ctx, srcSlot, &d);
+    if (rc != VR_OK) return rc;
+    const auto [xSize, ySize, zSize] = grid.GetSize();
+    if ((int)xSize != d.box_hi[0] || (int)ySize != d.box_hi[1] || (int)zSize != d.box_hi[2]) return VR_ERR_INVALID_ARG;
+    for (int a = 0; a < 2; ++a) {
+        int32_t pitch;
+        if (!um(p.ImagePositionPatient[a], &d.origin[a]) || !um(p.PixelSpacing[a], &pitch) || pitch <= 0) return VR_ERR_INVALID_ARG;
+        d.spacing[a] = (uint32_t)pitch;
+        d.offset[a] = (uint32_t)pitch / 2u;
+    }
+    d.contours = contours;
+    d.connect = connect;
+    vr_outlines_result r;
+    rc = MaskOutlines(d, &r);  // the counting call
+    if (rc != VR_OK) return rc;
+    std::vector<int32_t> points((size_t)r.n_points * 2);
+    std::vector<vr_polygon> polygons(r.n_polygons);
+    if (r.n_points != 0) {
+        d.max_points = r.n_points;
+        d.max_polygons = r.n_polygons;
+        d.points = points.data();
+        d.polygons = polygons.data();
+        rc = MaskOutlines(d, &r);
+        if (rc != VR_OK) return rc;
+    }
+    int place[4] = {-1, -1, -1, -1}, traced = 0;
+    for (int k = 0; k < 4; ++k)
+        if ((contours >> k) & 1) place[k] = traced++;
+    out.assign((size_t)traced, {});
+    const float z0 = static_cast<float>(p.ImagePositionPatient[2]), dz = static_cast<float>(p.SliceThickness);
+    for (const vr_polygon& g : polygons) {
+        std::vector<float> flat;
+        flat.reserve((size_t)g.count * 3);
+        const float z = z0 + static_cast<float>(g.slice) * dz;
+        for (uint32_t e = g.first; e < g.first + g.count; ++e) {
+            flat.push_back(static_cast<float>(points[(size_t)e * 2] / 1000.0));
+            flat.push_back(static_cast<float>(points[(size_t)e * 2 + 1] / 1000.0));
+            flat.push_back(z);
+        }
+        out[(size_t)place[g.contour]].push_back(std::move(flat));
+    }
+    return VR_OK;
+}
+
 int Application::Pick(uint32_t x, uint32_t y, vr_pick_result* out)
 {
     if (!p_Ctx || !p_App) return VR_ERR_NOT_READY;

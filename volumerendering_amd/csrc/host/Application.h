@@ -98,6 +98,16 @@ public:
     // a spacing that is not positive, a coordinate beyond 2^29 micrometres or a volume 0 of another size than `grid`.
     int ContoursToMask(const StructureFileDcm& structures, std::array<int, 4> contourIDs, const VolumeFileDcm& grid, int dstSlot, int rule,
                        vr_polygons_result* out);
+    // The contours of a mask volume traced into closed planar polygons on the device (vr_mask_outlines of include/vr.h): a descriptor
+    // passed through.  `out` may be nullptr.
+    int MaskOutlines(const vr_outlines_desc& desc, vr_outlines_result* out);
+    // The inverse of ContoursToMask: the contours `contours` (bit k: contour k) of volume srcSlot as structures in patient millimetres
+    // on the voxel grid of `grid` (a volume read from DICOM, of srcSlot's size), the whole volume, connect = VR_OUTLINE_SPLIT /
+    // VR_OUTLINE_JOIN.  The grid is taken in whole micrometres by the same llround(v * 1000.0) of ImagePositionPatient x / y and
+    // PixelSpacing, the offset is half a spacing rounded down.  out[l] = the polygons of the l-th traced contour, each flat x y z floats
+    // (the layout StructureFileDcm holds), z = that of the polygon's slice, the inverse of ContourSliceNumber.  VR_ERR_INVALID_ARG for a
+    // spacing that is not positive, a coordinate beyond 2^29 micrometres or a volume of another size than `grid`.
+    int MaskToContours(int srcSlot, int contours, int connect, const VolumeFileDcm& grid, std::vector<std::vector<std::vector<float>>>& out);
     // the accumulated opacity at which the unlit / lit scene's surface lies (vr_set_surface_threshold: finite, 0 <= tau < 1)
     int SetSurfaceThreshold(float tau);
 

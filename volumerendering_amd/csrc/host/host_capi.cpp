@@ -438,6 +438,35 @@ int vrh_app_contours_to_mask(void* a, void* structures, const int ids[4], void* 
                                                             rule, out);
     })
 }
+// Application::MaskOutlines and Application::MaskToContours (vr_mask_outlines of the application's context); grid: as
+// vrh_app_margin_mm's.  vrh_app_mask_to_contours returns the contours as structures in the grid's frame of reference (vrh_struct_free),
+// nullptr with *rc set on failure
+int vrh_app_mask_outlines(void* a, const vr_outlines_desc* desc, vr_outlines_result* out)
+{
+    if (!desc) return VR_ERR_INVALID_ARG;
+    VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->MaskOutlines(*desc, out); })
+}
+void* vrh_app_mask_to_contours(void* a, int src_slot, int contours, int connect, void* grid, int* rc)
+{
+    auto* vh = static_cast<VolumeHandle*>(grid);
+    int code = VR_ERR_INVALID_ARG;
+    void* made = nullptr;
+    if (vh && vh->dcm) {
+        try {
+            std::vector<std::vector<std::vector<float>>> data;
+            code = static_cast<Application*>(a)->MaskToContours(src_slot, contours, connect, *vh->dcm, data);
+            if (code == VR_OK) {
+                DicomStructParams p;
+                p.FrameOfReference = vh->dcm->GetVolumeParams().FrameOfReference;
+                made = new std::shared_ptr<StructureFileDcm>(std::make_shared<StructureFileDcm>("", p, data));
+            }
+        } catch (...) {
+            code = VR_ERR_HIP;
+        }
+    }
+    if (rc) *rc = code;
+    return made;
+}
 // Application::DistanceMap and Application::DistanceMm (vr_mask_distance of the application's context); grid: as vrh_app_margin_mm's
 int vrh_app_distance_map(void* a, const vr_dist_desc* desc, vr_dist_result* out)
 {

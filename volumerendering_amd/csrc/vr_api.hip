@@ -15,6 +15,8 @@
 #include "vr_dist.h"
 // Polygon rasterisation (vr_mask_polygons): exact integer work on the same bit-rows, compiled once as well
 #include "vr_raster.h"
+// Contour tracing (vr_mask_outlines): the inverse of the raster, exact integer work on the same bit-rows, compiled once as well
+#include "vr_outline.h"
 
 // the same dispatch over the kernels compiled with fused multiply-adds (vr_fused.hip)
 namespace vrf {
@@ -46,6 +48,7 @@ using namespace vr;
 #include "vr_api_morph.h"
 #include "vr_api_dist.h"
 #include "vr_api_raster.h"
+#include "vr_api_outline.h"
 
 namespace {
 

@@ -213,6 +213,20 @@ struct RasterState {
     ToolReport report;                   // phases: upload, raster, write, refresh_bricks
 };
 
+// Contour tracing (vr_mask_outlines, vr_outline.h): the working buffers of the last call, grown on demand; what vr_outlines_counters
+// and vr_outlines_timing report.  Of vr_ctx::bit_row_scratch it takes one buffer per contour traced.
+struct OutlineState {
+    DevBuf<ulonglong2> masks;            // per vertex word: the vertices with one corner, with two
+    DevBuf<unsigned> base;               // per vertex word: its corners, then the corners before it
+    DevBuf<unsigned long long> sums;     // the scans' tile sums
+    DevBuf<unsigned> pred, meta;         // per corner node: the node before it on its loop; its slice and contour
+    DevBuf<int2> pt;                     // ... its point
+    DevBuf<uint4> st[2];                 // ... (leader, rank, jump) of the doubling rounds, written in turn; the idle one takes the output
+    DevBuf<unsigned> pidx, pcount;       // per node: the polygons led by smaller nodes; per polygon: its points, then its first point
+    WordsPair<OutlineWords> io;          // the totals, the areas, the rounds' outcomes
+    ToolReport report;                   // phases: pack, corners + scan + link, doubling rounds, emit + copy back
+};
+
 // What the reporting calls (vr_last_counters, vr_last_kernel_flavour, vr_last_timing, vr_kernel_times, vr_kernel_choice,
 // vr_download_tiles, vr_last_block_trace) read about the most recent march launch.  vr_pick copies it out and back as one value.
 struct LastLaunch {
@@ -401,12 +415,13 @@ struct vr_ctx {
     const float* d_near = nullptr;
     const float* d_far = nullptr;
     GrowState grow;  // region growing (vr_segment_grow)
-    // The bit-row scratch of the three mask tools below (vr_bitrows.h), grown to the most words a call has asked for.  Each call drains
+    // The bit-row scratch of the four mask tools below (vr_bitrows.h), grown to the most words a call has asked for.  Each call drains
     // the device, zeroes the buffers it takes before it reads them and is synchronous on return: no two uses are ever live.
     DevBuf<unsigned long long> bit_row_scratch;
     MorphState morph;  // mask morphology (vr_mask_morph)
     DistState dist;    // distance maps (vr_mask_distance)
     RasterState raster;  // polygon rasterisation (vr_mask_polygons)
+    OutlineState outline;  // contour tracing (vr_mask_outlines)
     std::string err;
 };
 

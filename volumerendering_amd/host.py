@@ -70,6 +70,8 @@ def load() -> C.CDLL:
         "vrh_app_margin_mm": (i32, [vp, i32, i32, i32, i32, f32, vp, C.POINTER(capi.MorphResult)]),
         "vrh_app_raster_polygons": (i32, [vp, C.POINTER(capi.PolygonsDesc), C.POINTER(capi.PolygonsResult)]),
         "vrh_app_contours_to_mask": (i32, [vp, vp, C.POINTER(C.c_int * 4), vp, i32, i32, C.POINTER(capi.PolygonsResult)]),
+        "vrh_app_mask_outlines": (i32, [vp, C.POINTER(capi.OutlinesDesc), C.POINTER(capi.OutlinesResult)]),
+        "vrh_app_mask_to_contours": (vp, [vp, i32, i32, i32, vp, C.POINTER(C.c_int)]),
         "vrh_app_distance_map": (i32, [vp, C.POINTER(capi.DistDesc), C.POINTER(capi.DistResult)]),
         "vrh_app_distance_mm": (i32, [vp, i32, i32, i32, i32, i32, f32, vp, C.POINTER(capi.DistResult)]),
         "vrh_app_slice": (i32, [vp, C.POINTER(capi.SliceDesc), vp]),
@@ -555,6 +557,27 @@ class Application:
         out = capi.PolygonsResult()
         self._chk(self.lib.vrh_app_contours_to_mask(self.h, structures.h, C.byref(ids), grid.h, dst_slot, rule, C.byref(out)))
         return out
+
+    def mask_outlines(self, desc: capi.OutlinesDesc):
+        """Application::MaskOutlines: vr_mask_outlines (include/vr.h) on the application's context, the counting call and the call that
+        stores; returns what capi.Context.mask_outlines returns."""
+        out = capi.OutlinesResult()
+        self._chk(self.lib.vrh_app_mask_outlines(self.h, C.byref(desc.copy(max_points=0, max_polygons=0, points=None, polygons=None)), C.byref(out)))
+        pts = np.zeros((int(out.n_points), 2), np.int32)
+        polys = (capi.Polygon * int(out.n_polygons))()
+        if out.n_points:
+            d = desc.copy(max_points=len(pts), max_polygons=len(polys), points=pts.ctypes.data, polygons=C.cast(polys, C.c_void_p).value)
+            self._chk(self.lib.vrh_app_mask_outlines(self.h, C.byref(d), C.byref(out)))  # (pts and polys live until here)
+        return pts, [(int(q.first), int(q.count), int(q.slice), int(q.contour)) for q in polys], out
+
+    def mask_to_contours(self, src_slot: int, contours: int, connect: int, grid: "VolumeFile") -> "StructureFile":
+        """Application::MaskToContours: the contours `contours` (bit k: contour k) of volume src_slot traced over the whole volume into
+        structures in patient millimetres on the voxel grid of `grid` (a volume read from DICOM): a StructureFile in the grid's frame of
+        reference whose contours() are the traced contours in ascending order, each polygon flat x y z."""
+        rc = C.c_int(0)
+        h = self.lib.vrh_app_mask_to_contours(self.h, src_slot, contours, connect, grid.h, C.byref(rc))
+        self._chk(rc.value)
+        return StructureFile(h)
 
     def distance_map(self, desc: capi.DistDesc) -> capi.DistResult:
         """Application::DistanceMap: vr_mask_distance (include/vr.h) on the application's context."""
