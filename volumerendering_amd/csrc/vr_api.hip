@@ -119,7 +119,7 @@ int vr_create(vr_ctx** out, uint32_t width, uint32_t height, int device_id)
         const long long w = atoll(e);
         if (w > 0 && w <= 0x3fffffffll) c->p2_window = (unsigned)w;
     }
-    if (const char* e = getenv("VR_EXP_TUNE")) c->tune_mode = atoi(e);
+    if (const char* e = getenv("VR_EXP_TUNE")) c->tuner.mode = atoi(e);
     if (!hip_ok(c->d_pw_heads.reserve((size_t)kInFlight * 8 * 64), "hipMalloc(queue heads)")) return bail(VR_ERR_HIP);
     if (!hip_ok(hipMemset(c->d_pw_heads, 0, (size_t)kInFlight * 8 * 64 * sizeof(unsigned)), "hipMemset(queue heads)")) return bail(VR_ERR_HIP);
     for (Event* e : {&c->tm.ev_begin, &c->tm.ev_k0, &c->tm.ev_k1, &c->tm.ev_end})
@@ -129,7 +129,7 @@ int vr_create(vr_ctx** out, uint32_t width, uint32_t height, int device_id)
             return bail(VR_ERR_HIP);
     for (auto& r : c->slot)
         if (!hip_ok(r.done.create(hipEventDisableTiming), "hipEventCreate")) return bail(VR_ERR_HIP);
-    for (auto& o : c->order_ring)
+    for (auto& o : c->order.ring)
         if (!hip_ok(o.sorted.create(hipEventDisableTiming), "hipEventCreate")) return bail(VR_ERR_HIP);
     // The sorts run on a stream of their own, default priority.  The runtime deals streams onto a handful of hardware queues
     // per priority level, and a sort waits (a barrier in its queue) for a launch that is still running, so WHICH streams end up
@@ -138,17 +138,17 @@ int vr_create(vr_ctx** out, uint32_t width, uint32_t height, int device_id)
     // frame (0.24 -> 0.29 ms one frame at a time; with a high-priority sort stream its gather stream, high priority too, meets
     // the sorts' barriers), and the full C3 frame gains nothing from a third frame in flight either way (tools/exp_tiles.py,
     // tools/exp_queues).
-    if (!hip_ok(c->order_stream.create(), "hipStreamCreate")) return bail(VR_ERR_HIP);
-    if (!hip_ok(c->edit_ev.create(hipEventDisableTiming), "hipEventCreate")) return bail(VR_ERR_HIP);
-    for (auto& st : c->stage)
+    if (!hip_ok(c->order.stream.create(), "hipStreamCreate")) return bail(VR_ERR_HIP);
+    if (!hip_ok(c->edits.order.ev.create(hipEventDisableTiming), "hipEventCreate")) return bail(VR_ERR_HIP);
+    for (auto& st : c->edits.stage)
         if (!hip_ok(st.done.create(hipEventDisableTiming), "hipEventCreate")) return bail(VR_ERR_HIP);
-    if (!hip_ok(c->h_skip.reserve(kGen, true), "hipHostMalloc")) return bail(VR_ERR_HIP);
-    if (!hip_ok(c->d_skip_sum.reserve(kGen), "hipMalloc(skip summary)")) return bail(VR_ERR_HIP);
-    if (!hip_ok(hipMemset(c->d_skip_sum, 0, kGen * sizeof(SkipSumDev)), "hipMemset(skip summary)")) return bail(VR_ERR_HIP);
+    if (!hip_ok(c->skip.h_sum.reserve(kGen, true), "hipHostMalloc")) return bail(VR_ERR_HIP);
+    if (!hip_ok(c->skip.d_sum.reserve(kGen), "hipMalloc(skip summary)")) return bail(VR_ERR_HIP);
+    if (!hip_ok(hipMemset(c->skip.d_sum, 0, kGen * sizeof(SkipSumDev)), "hipMemset(skip summary)")) return bail(VR_ERR_HIP);
     // (these three may fail: the buffer stays empty)
-    (void)c->h_span.reserve(kRing, true);        // (else every launch is timed with events)
-    (void)c->h_end.reserve(kRing, true);         // (else no measured kernel choice with launches in flight: the prior's pick stays)
-    (void)c->h_chain.reserve(kOrderRing, true);  // (else the choice of lanes per ray goes by the launch size alone)
+    (void)c->ring.h_span.reserve(kRing, true);         // (else every launch is timed with events)
+    (void)c->ring.h_end.reserve(kRing, true);          // (else no measured kernel choice with launches in flight: the prior's pick stays)
+    (void)c->order.h_chain.reserve(kOrderRing, true);  // (else the choice of lanes per ray goes by the launch size alone)
     if (!hip_ok(c->d_counters.reserve(3), "hipMalloc(counters)")) return bail(VR_ERR_HIP);
     if (!hip_ok(c->h_counters.reserve(3, true), "hipHostMalloc")) return bail(VR_ERR_HIP);
     if (const int rc = alloc_frame(c)) return bail(rc);
@@ -259,7 +259,7 @@ void* vr_stream(vr_ctx* c, int index)
             for (int k = 0; k < c->n_flight && ok; ++k) ok = streams_overlap(c->flight[k], s, e0, e1, one_ms);
             // ... and with the stream of the launch-order sorts, whose barriers (a sort waits for its launch) would hold back
             // the launches of a render stream that shares its queue
-            if (ok && c->order_stream) ok = streams_overlap(c->order_stream, s, e0, e1, one_ms);
+            if (ok && c->order.stream) ok = streams_overlap(c->order.stream, s, e0, e1, one_ms);
             (ok ? c->flight[c->n_flight++] : rejected[n_rejected++]) = std::move(cand);  // (rejected: shares a hardware queue with a kept one)
         }
         (void)hipGetLastError();
@@ -299,8 +299,8 @@ int vr_set_shadows(vr_ctx* c, int grid_divisor, float opacity_scale)
         return fail(c, VR_ERR_INVALID_ARG, "vr_set_shadows: the divisor must be 0 (off), 1, 2, 4 or 8");
     if (!std::isfinite(opacity_scale) || !(opacity_scale >= 0.0f))
         return fail(c, VR_ERR_INVALID_ARG, "vr_set_shadows: the opacity scale must be finite and >= 0");
-    c->shadow_div = grid_divisor;
-    c->shadow_sigma = opacity_scale;
+    c->shadows.div = grid_divisor;
+    c->shadows.sigma = opacity_scale;
     return VR_OK;
 }
 

@@ -5,9 +5,9 @@
 namespace {
 
 // (defined in vr_api_views.h)
-vr_ctx::ShadowKey shadow_key(const vr_ctx* c, const vr_uniforms& u);
+ShadowKey shadow_key(const vr_ctx* c, const vr_uniforms& u);
 size_t shadow_grid(const vr_ctx* c, int g[3]);
-int prepare_shadow(vr_ctx* c, hipStream_t s, MarchParams& P, const vr_ctx::ShadowKey& key, bool skip, bool off32);
+int prepare_shadow(vr_ctx* c, hipStream_t s, MarchParams& P, const ShadowKey& key, bool skip, bool off32);
 
 int tiles_x_of(const vr_ctx* c) { return (int)((c->W + kTile - 1) / kTile); }
 int tiles_y_of(const vr_ctx* c) { return (int)((c->H + kTile - 1) / kTile); }
@@ -143,44 +143,28 @@ void fill_frame_params(MarchParams& P, const vr_uniforms& u)
 int tune_pick(vr_ctx* c, unsigned long long key, unsigned long long shape, const int* cand, int n, unsigned chain_now, bool measurable)
 {
     if (n <= 1) return cand[0];
-    vr_ctx::Tune* t = nullptr;
-    for (auto& e : c->tune)
+    Tuner& T = c->tuner;
+    const KernelRing& ring = c->ring;
+    Trial* t = nullptr;
+    for (auto& e : T.trials)
         if (e.key == key) t = &e;
     const int in_flight = c->frames_in_flight;
-    auto reset = [&](vr_ctx::Tune& e, int first) {
-        e.key = key;
-        e.shape = shape;
-        e.n = 0;
-        e.cand[e.n++] = first;
-        for (int i = 0; i < n; ++i)
-            if (cand[i] != first && e.n < 6) e.cand[e.n++] = cand[i];
-        e.cur = 0;
-        e.issued = 0;
-        e.per = in_flight > 1 ? 3 * in_flight + 2 : 3;  // (<= 14: kStreams is 4)
-        e.settle = in_flight + 3;
-        e.choice = -1;
-        e.chain_ref = 0;
-        for (int i = 0; i < 6; ++i) {
-            e.cost[i] = 0.0f;
-            for (int q = 0; q < 16; ++q) e.launch[i][q] = -1;
-        }
-    };
     if (!t) {
         // a new scene (or table, or arithmetic) of a shape that has been measured before: what that trial kept runs first, if it is
         // still eligible -- a host that edits a table frame after frame keeps its kernel while every new trial settles
         int first = cand[0];
         unsigned long long newest = 0;
-        for (const auto& e : c->tune)
+        for (const auto& e : T.trials)
             if (e.key != 0 && e.shape == shape && e.choice >= 0 && e.used > newest)
                 for (int i = 0; i < n; ++i)
                     if (cand[i] == e.cand[e.choice]) {
                         first = cand[i];
                         newest = e.used;
                     }
-        t = &c->tune[0];
-        for (auto& e : c->tune)
+        t = &T.trials[0];
+        for (auto& e : T.trials)
             if (e.used < t->used) t = &e;
-        reset(*t, first);
+        t->reset(key, shape, first, cand, n, in_flight);
     } else {
         // the eligible set may have changed under the same key (a flavour knob, a table that fits LDS no more)
         bool same = t->n == n;
@@ -189,13 +173,13 @@ int tune_pick(vr_ctx* c, unsigned long long key, unsigned long long shape, const
             for (int j = 0; j < t->n; ++j) found = found || t->cand[j] == cand[i];
             same = found;
         }
-        if (!same) reset(*t, cand[0]);
+        if (!same) t->reset(key, shape, cand[0], cand, n, in_flight);
     }
-    t->used = ++c->tune_clock;
+    t->used = ++T.clock;
     if (t->choice >= 0) {
         if (chain_now != 0 && t->chain_ref != 0) {
             const unsigned lo = t->chain_ref - t->chain_ref / 4, hi = t->chain_ref + t->chain_ref / 4;
-            if (chain_now < lo || chain_now > hi) reset(*t, t->cand[t->choice]);  // (the kernel kept so far runs while the new trial settles)
+            if (chain_now < lo || chain_now > hi) t->reset(key, shape, t->cand[t->choice], cand, n, in_flight);  // (the kernel kept so far runs while the new trial settles)
         }
         if (t->choice >= 0) return t->cand[t->choice];
     }
@@ -224,20 +208,20 @@ int tune_pick(vr_ctx* c, unsigned long long key, unsigned long long shape, const
     }
     for (int i = 0; i < t->n; ++i)
         for (int q = 0; q < t->per; ++q)
-            if (*(volatile unsigned long long*)&c->h_span[t->launch[i][q] % kRing] == 0) return t->cand[0];
+            if (ring.span_ticks(ring.slot(t->launch[i][q])) == 0) return t->cand[0];
     int best = 0;
     for (int i = 0; i < t->n; ++i) {
         double ticks;
         if (in_flight > 1) {
             // (its first `in_flight` launches ran beside the candidate before it, its last ones beside the next: the ends of the
             // launches in between are `in_flight + 2` intervals apart that are this candidate's alone)
-            const unsigned long long e0 = *(volatile unsigned long long*)&c->h_end[t->launch[i][in_flight] % kRing];
-            const unsigned long long e1 = *(volatile unsigned long long*)&c->h_end[t->launch[i][t->per - in_flight] % kRing];
+            const unsigned long long e0 = ring.end_ticks(ring.slot(t->launch[i][in_flight]));
+            const unsigned long long e1 = ring.end_ticks(ring.slot(t->launch[i][t->per - in_flight]));
             ticks = e1 > e0 ? (double)(e1 - e0) / (double)(t->per - 2 * in_flight) : 1.0e18;
         } else {
             ticks = 1.0e18;
             for (int q = 1; q < t->per; ++q) {
-                const double v = (double)*(volatile unsigned long long*)&c->h_span[t->launch[i][q] % kRing];
+                const double v = (double)ring.span_ticks(ring.slot(t->launch[i][q]));
                 ticks = v < ticks ? v : ticks;
             }
         }
@@ -269,7 +253,7 @@ unsigned long long scene_key(const vr_ctx* c, const RenderRequest& R, bool surfa
 }
 
 // TF slot 0 fits a workgroup's LDS beside nothing else: one resolution for both tables, R <= 8190 (128 KiB)
-bool tf0_fits_lds(const vr_ctx* c) { return c->tf[0].res_o == c->tf[0].res_c && c->tf[0].res_o + 2 <= 8192; }
+bool tf0_fits_lds(const vr_ctx* c) { return c->tf[0].dev.res_o == c->tf[0].dev.res_c && c->tf[0].dev.res_o + 2 <= 8192; }
 
 // The arguments of a launch and the slots its shader samples (*nvol volumes); *off32: every one of them below 4 GiB.  Derives what the
 // request does not say itself (R.surface, R.bounded) and refuses what these cannot do.
@@ -288,7 +272,7 @@ int check_render_args(vr_ctx* c, RenderRequest& R, int* nvol, bool* off32)
         if (R.variant != VR_VARIANT_BASIC && R.variant != VR_VARIANT_LIGHT)
             return fail(c, VR_ERR_UNSUPPORTED, "vr_render: ray bounds exist for BASIC and LIGHT only");
         if (R.surface) return fail(c, VR_ERR_UNSUPPORTED, "vr_render: ray bounds do not apply to surface output");
-        if (R.variant == VR_VARIANT_LIGHT && c->shadow_div != 0)
+        if (R.variant == VR_VARIANT_LIGHT && c->shadows.div != 0)
             return fail(c, VR_ERR_UNSUPPORTED, "vr_render: ray bounds do not apply to LIGHT with shadows on");
         if (R.batch_u) return fail(c, VR_ERR_UNSUPPORTED, "vr_render: ray bounds do not apply to launches of several frames");
     }
@@ -315,7 +299,7 @@ int check_render_args(vr_ctx* c, RenderRequest& R, int* nvol, bool* off32)
         if (c->vols[i].bytes() > 0xFFFFFFFFull) *off32 = false;
     }
     for (int i = 0; i < ntf; ++i)
-        if (!c->tf[i].opacity || !c->tf[i].color)
+        if (!c->tf[i].dev.opacity || !c->tf[i].dev.color)
             return fail(c, VR_ERR_NOT_READY, "vr_render: TF slot " + std::to_string(i) + " is empty");
     if ((R.batch_u ? R.batch_u[0] : c->u).steps_count < 0) return fail(c, VR_ERR_INVALID_ARG, "vr_render: negative steps_count");
     return VR_OK;
@@ -328,7 +312,7 @@ void fill_launch_params(const vr_ctx* c, MarchParams& P, const vr_uniforms& u0, 
     P.H = (int)c->H;
     fill_frame_params(P, u0);
     for (int i = 0; i < VR_MAX_VOLUMES; ++i) P.vol[i] = linear_volume(c, i);
-    for (int i = 0; i < VR_MAX_TFS; ++i) P.tf[i] = c->tf[i];
+    for (int i = 0; i < VR_MAX_TFS; ++i) P.tf[i] = c->tf[i].dev;
     P.rank = rank;
     P.world = world;
     P.tiles_x = tiles_x_of(c);
@@ -351,23 +335,6 @@ struct Eligibility {
     unsigned chain_known;   // longest ray chain + 1 of the most recent launch of this scene shape whose sort has reported (0: none)
 };
 
-// the longest ray chain + 1 of the most recent launch of this scene shape whose sort has reported (written to pinned memory by the
-// launch-order sort; read without synchronising, 0 = not known)
-unsigned last_chain(const vr_ctx* c, unsigned long long skey)
-{
-    unsigned chain = 0;
-    if (!c->h_chain) return chain;
-    unsigned long long best_seq = 0;
-    for (int i = 0; i < kOrderRing; ++i) {
-        const unsigned v = *(volatile unsigned*)&c->h_chain[i];
-        if (v != 0 && c->order_ring[i].scene_key == skey && c->order_ring[i].seq + 1 > best_seq) {
-            best_seq = c->order_ring[i].seq + 1;
-            chain = v;
-        }
-    }
-    return chain;
-}
-
 Eligibility eligibility(const vr_ctx* c, int requested, const RenderRequest& R)
 {
     Eligibility E = {};
@@ -382,7 +349,7 @@ Eligibility eligibility(const vr_ctx* c, int requested, const RenderRequest& R)
         const DevVolume& v = c->vols[sv].vol;
         const BrickedGrid g = bricked_grid(v);
         const size_t slab = (size_t)g.nbx * g.nby * kVbN, window = R.variant == VR_VARIANT_BASIC ? 0x3fffffffull : 0x0fffffffull;
-        const size_t lds = (size_t)(c->tf[0].res_o + 2) * 16 + ((size_t)v.nx + v.ny + v.nz + 3) * 8;
+        const size_t lds = (size_t)(c->tf[0].dev.res_o + 2) * 16 + ((size_t)v.nx + v.ny + v.nz + 3) * 8;
         E.p2_ok = g.slots <= 0xFFFFFFFFull && slab < (1u << 24) && (c->p2_window ? c->p2_window / slab >= 3 : window / slab >= 4) && lds <= 160u * 1024u;
         E.p2_lds = (unsigned)lds;
     }
@@ -400,16 +367,16 @@ Eligibility eligibility(const vr_ctx* c, int requested, const RenderRequest& R)
     E.indexable = volume_bricks_indexable(c->vols[0].vol);
     E.can_skip = (R.variant == VR_VARIANT_BASIC || R.variant == VR_VARIANT_LIGHT || R.variant == VR_VARIANT_THREE_FILES ||
                   R.variant == VR_VARIANT_VOLUME_MASK || R.variant == VR_VARIANT_LIGHT_INSHADER) &&
-                 requested != 1 && c->vols[sv].bricks && c->tf_zero_prefix[0] >= 0 && c->tf_color_finite[0];
+                 requested != 1 && c->vols[sv].bricks && c->tf[0].zero_prefix >= 0 && c->tf[0].color_finite;
     for (int f = 0; f < R.n_frames; ++f) E.can_skip = E.can_skip && all_finite(R.batch_u ? R.batch_u[f].light_pos : c->u.light_pos, 12);
     // the kernels index bricks with 24-bit multiplies and 32-bit byte offsets
     E.can_skip = E.can_skip && volume_bricks_indexable(c->vols[sv].vol);
-    if (R.variant == VR_VARIANT_THREE_FILES) E.can_skip = E.can_skip && c->tf_color_finite[1] && c->tf_opacity_finite[1];
+    if (R.variant == VR_VARIANT_THREE_FILES) E.can_skip = E.can_skip && c->tf[1].color_finite && c->tf[1].opacity_finite;
     if (R.variant == VR_VARIANT_VOLUME_MASK)  // mask and CT must share one grid so that one brick index serves both
         E.can_skip = E.can_skip && c->vols[0].bricks && c->vols[0].vol.nx == c->vols[2].vol.nx && c->vols[0].vol.ny == c->vols[2].vol.ny &&
                      c->vols[0].vol.nz == c->vols[2].vol.nz;
     E.whole_frame = rays_per_lane(c, R.rank, R.world, 1) >= 4.5;
-    E.chain_known = requested == 0 ? last_chain(c, scene_key(c, R, false, false)) : 0;  // (the plain colour launch's key, always)
+    E.chain_known = requested == 0 ? c->order.last_chain(scene_key(c, R, false, false)) : 0;  // (the plain colour launch's key, always)
     return E;
 }
 
@@ -426,7 +393,7 @@ int choose_flavour(vr_ctx* c, int fl, const RenderRequest& R, const Eligibility&
         {R.surface && R.variant != VR_VARIANT_ISO, 25},               // the surface-position output of the unlit / lit shader
         {is_projection(R.variant), 19},                               // the projections
         {R.variant == VR_VARIANT_ISO, 21},                            // the isosurface
-        {R.variant == VR_VARIANT_LIGHT && c->shadow_div != 0, 23},    // the shadowed lit shader
+        {R.variant == VR_VARIANT_LIGHT && c->shadows.div != 0, 23},    // the shadowed lit shader
     };
     for (const auto& pr : pairs)
         if (pr.applies) return fl == 1 ? pr.skipping + 1 : pr.skipping;
@@ -472,12 +439,12 @@ int choose_flavour(vr_ctx* c, int fl, const RenderRequest& R, const Eligibility&
     // dequeue, 0.111 -> 0.161).  The same with launches in flight and several frames per launch since the approach loop (C3 0.417 / 0.382
     // ms per frame against march_kernel's 0.464 / 0.445; C5 level); shares of a frame: the first part's choice.
     const bool p2_variant = R.variant == VR_VARIANT_LIGHT || R.variant == VR_VARIANT_BASIC || (R.variant == VR_VARIANT_VOLUME_MASK && E.can_skip);
-    const bool nothing_to_skip = !E.can_skip || c->active_fraction >= 0.9;  // (prepare_skip has measured the share of active bricks)
+    const bool nothing_to_skip = !E.can_skip || c->skip.active_fraction >= 0.9;  // (prepare_skip has measured the share of active bricks)
     if (fl == 6 && E.whole_frame && E.p2_ok && p2_variant) {
         if (nothing_to_skip && R.variant != VR_VARIANT_VOLUME_MASK) fl = 16;
         else if (!short_chains) fl = 17;
     }
-    if (!c->tune_mode) return fl;
+    if (!c->tuner.mode) return fl;
     // ... and THE MEASURED CHOICE (tune_pick): the eligible forms take turns on the caller's own frames, the fastest by the launches'
     // own records stays.  Candidates: the prior; the two-steps-ahead kernel; the one-lane kernel; the depth-parallel kernel (launches
     // that leave the machine part empty) or the persistent kernel without the pipeline (the longest chains).
@@ -499,7 +466,7 @@ int choose_flavour(vr_ctx* c, int fl, const RenderRequest& R, const Eligibility&
                                                              ((unsigned long long)R.n_frames << 4) ^ (unsigned long long)c->frames_in_flight) | 1ull;
     const unsigned long long key = (shape ^ (c->brick_epoch * 0xD6E8FEB86659FD93ull) ^ (c->tf_epoch << 20) ^ ((unsigned long long)c->arith << 1) ^
                                     ((unsigned long long)c->layout_mode << 2)) | 1ull;
-    const bool measurable = c->h_span && c->h_end && !c->event_timing;
+    const bool measurable = c->ring.h_span && c->ring.h_end && !c->event_timing;
     return tune_pick(c, key, shape, cand, n, E.chain_known, measurable);
 }
 
@@ -561,14 +528,14 @@ KernelForm kernel_form(int fl, int variant)
 // re-allocated: this host wait is what bounds the launches in flight to kInFlight.  The sort that read those records is waited for on
 // `s`, so that whoever takes the slot next may write them behind this launch's event -- at once, or, with `stale_sort`, by the caller
 // (the march launch: reserve_block_counts, wait_for_order).
-int claim_slot(vr_ctx* c, hipStream_t s, int* cb, const vr_ctx::OrderSlot** stale_sort = nullptr)
+int claim_slot(vr_ctx* c, hipStream_t s, int* cb, const OrderSlot** stale_sort = nullptr)
 {
     const int k = (int)(c->order_seq % (unsigned long long)kInFlight);
     *cb = k;
     if (c->slot[k].used) VR_HIP(c, hipEventSynchronize(c->slot[k].done));
-    const vr_ctx::OrderSlot* sort = nullptr;
+    const OrderSlot* sort = nullptr;
     if (c->order_seq >= (unsigned long long)kInFlight) {
-        const vr_ctx::OrderSlot& po = c->order_ring[(c->order_seq - kInFlight) % kOrderRing];
+        const OrderSlot& po = c->order.ring[(c->order_seq - kInFlight) % kOrderRing];
         if (po.valid && po.seq + kInFlight == c->order_seq) sort = &po;
     }
     if (stale_sort) *stale_sort = sort;
@@ -578,7 +545,7 @@ int claim_slot(vr_ctx* c, hipStream_t s, int* cb, const vr_ctx::OrderSlot** stal
 
 // The march launch's records in its slot, n_records blocks.  *slot_sort (claim_slot) is waited for at once only when the buffer is
 // re-allocated (the memset behind the allocation writes it).
-int reserve_block_counts(vr_ctx* c, hipStream_t s, int k, size_t n_records, const vr_ctx::OrderSlot** slot_sort)
+int reserve_block_counts(vr_ctx* c, hipStream_t s, int k, size_t n_records, const OrderSlot** slot_sort)
 {
     DevBuf<unsigned long long>& b = c->slot[k].block_counts;
     if (n_records * kBlockRecord > b.cap) {
@@ -599,16 +566,12 @@ int reserve_block_counts(vr_ctx* c, hipStream_t s, int k, size_t n_records, cons
 // then).  A stream's wait for another stream's event costs the stream 5 us per launch even when the event completed long ago
 // (tools/ubench/stream_gap.hip), so the wait for `slot_sort` is left out when the order's wait covers it: every sort runs on the one
 // order stream, in the order of the launches.
-int wait_for_order(vr_ctx* c, hipStream_t s, bool ordered, unsigned long long okey, const vr_ctx::OrderSlot* slot_sort, const unsigned** order)
+int wait_for_order(vr_ctx* c, hipStream_t s, bool ordered, unsigned long long okey, const OrderSlot* slot_sort, const unsigned** order)
 {
     *order = nullptr;
     if (ordered) {
-        const vr_ctx::OrderSlot* best = nullptr;
         const unsigned long long age = (unsigned long long)(c->frames_in_flight + 2 > 3 ? c->frames_in_flight + 2 : 3);
-        for (const auto& o : c->order_ring)
-            if (o.valid && o.key == okey && o.seq + age + 1 >= c->order_seq && o.seq + age <= c->order_seq && (!best || o.seq > best->seq))
-                best = &o;
-        if (best) {
+        if (const OrderSlot* best = c->order.best(okey, c->order_seq, age)) {
             VR_HIP(c, hipStreamWaitEvent(s, best->sorted, 0));
             if (slot_sort && best->seq >= slot_sort->seq) slot_sort = nullptr;  // (covered: the order stream runs its sorts in order)
             *order = best->buf;
@@ -622,17 +585,18 @@ int wait_for_order(vr_ctx* c, hipStream_t s, bool ordered, unsigned long long ok
 struct SortJob {
     unsigned long long okey, skey;  // OrderSlot::key, ::scene_key
     unsigned n_blocks;
-    int ring;                       // the launch's KernelRing slot
+    int ring;                       // the launch's KernelRing::slot
     bool time_with_events, pw;
 };
 
 // Gives record slot cb back behind the launch on `s` that claimed it: the slot's event, and then the next launch takes the next slots.
 // For an ordered march launch (`sort`), in between: the sort of its n_blocks records on the order stream into order slot
 // order_seq % kOrderRing -- the launch order of later launches; the longest chain (h_chain), and unless the launch is timed with events
-// its span and end (h_span / h_end, ring slot `ring`); the persistent kernels' queue heads cleared.
+// its span and end (KernelRing's h_span / h_end, slot `ring`); the persistent kernels' queue heads cleared.
 int finish_slot(vr_ctx* c, hipStream_t s, int cb, const SortJob* sort = nullptr)
 {
-    vr_ctx::OrderSlot& o = c->order_ring[c->order_seq % kOrderRing];
+    LaunchOrder& O = c->order;
+    OrderSlot& o = O.ring[c->order_seq % kOrderRing];
     if (sort) {
         o.valid = false;
         if (sort->n_blocks > o.buf.cap) VR_HIP(c, o.buf.reserve(sort->n_blocks));
@@ -640,21 +604,21 @@ int finish_slot(vr_ctx* c, hipStream_t s, int cb, const SortJob* sort = nullptr)
         o.key = sort->okey;
         o.scene_key = sort->skey;
         o.seq = c->order_seq;
-        if (c->h_chain) c->h_chain[c->order_seq % kOrderRing] = 0;  // not known until this launch's sort has run
+        if (O.h_chain) O.h_chain[c->order_seq % kOrderRing] = 0;  // not known until this launch's sort has run
     }
     VR_HIP(c, hipEventRecord(c->slot[cb].done, s));
     c->slot[cb].used = true;
     if (sort) {
         const bool time_with_events = sort->time_with_events;
-        VR_HIP(c, hipStreamWaitEvent(c->order_stream, c->slot[cb].done, 0));
-        hipLaunchKernelGGL(order_blocks_kernel, dim3(1), dim3(1024), 0, c->order_stream, c->slot[cb].block_counts, (int)sort->n_blocks, o.buf,
-                           c->h_chain ? c->h_chain + (c->order_seq % kOrderRing) : (unsigned*)nullptr,
-                           (c->h_span && !time_with_events) ? c->h_span + sort->ring : (unsigned long long*)nullptr,
+        VR_HIP(c, hipStreamWaitEvent(O.stream, c->slot[cb].done, 0));
+        hipLaunchKernelGGL(order_blocks_kernel, dim3(1), dim3(1024), 0, O.stream, c->slot[cb].block_counts, (int)sort->n_blocks, o.buf,
+                           O.h_chain ? O.h_chain + (c->order_seq % kOrderRing) : (unsigned*)nullptr,
+                           (c->ring.h_span && !time_with_events) ? c->ring.h_span + sort->ring : (unsigned long long*)nullptr,
                            sort->pw ? c->d_pw_heads + (size_t)cb * 8 * 64 : (unsigned*)nullptr,
-                           (c->h_span && c->h_end && !time_with_events) ? c->h_end + sort->ring : (unsigned long long*)nullptr);
+                           (c->ring.h_span && c->ring.h_end && !time_with_events) ? c->ring.h_end + sort->ring : (unsigned long long*)nullptr);
         VR_HIP(c, hipGetLastError());
         if (sort->pw) c->slot[cb].pw_heads_dirty = false;  // (the sort zeroes the heads behind the launch: the slot's next user finds them clean)
-        VR_HIP(c, hipEventRecord(o.sorted, c->order_stream));
+        VR_HIP(c, hipEventRecord(o.sorted, O.stream));
         o.valid = true;
     }
     ++c->order_seq;
@@ -700,8 +664,8 @@ int enqueue_render(vr_ctx* c, RenderRequest R)
     float4* out = R.out;
     hipStream_t s = R.stream;
     // shadows: every frame of the launch reads one light volume, of less than 4 GiB (a surface launch reads none)
-    const bool shadowed = R.variant == VR_VARIANT_LIGHT && c->shadow_div != 0 && !R.surface;
-    vr_ctx::ShadowKey shadow_k;
+    const bool shadowed = R.variant == VR_VARIANT_LIGHT && c->shadows.div != 0 && !R.surface;
+    ShadowKey shadow_k;
     if (shadowed) {
         shadow_k = shadow_key(c, R.batch_u ? R.batch_u[0] : c->u);
         for (int f = 1; f < R.n_frames; ++f)
@@ -711,11 +675,11 @@ int enqueue_render(vr_ctx* c, RenderRequest R)
         if (shadow_grid(c, g) * sizeof(float) >= (1ull << 32))
             return fail(c, VR_ERR_UNSUPPORTED, "vr_render: the light volume would take 4 GiB or more (a larger divisor)");
     }
-    c->shadow_cur = -1;
+    c->shadows.cur = -1;
     if (R.batch_u) out = (float4*)R.batch_out[0];
     VR_HIP(c, hipSetDevice(c->device));
     (void)hipGetLastError();  // a stale error of somebody else's call must not be reported as a failed launch below
-    if (const int rc = wait_for_edits(c, s)) return rc;
+    VR_HIP(c, c->edits.order.order_behind(s));  // the launch comes after every asynchronous edit made so far
 
     MarchParams P;
     fill_launch_params(c, P, R.batch_u ? R.batch_u[0] : c->u, R.rank, R.world, R.packed);
@@ -732,12 +696,12 @@ int enqueue_render(vr_ctx* c, RenderRequest R)
         // The surface march skips by the distance field of BASIC / LIGHT under the weakest condition that is still exact: an inert
         // brick's samples have opacity exactly 0, which leaves the accumulated alpha as it is whatever the colour table and the
         // light hold -- neither is read.  So: the brick records, a zero prefix of the opacity table, the kernels' index range.
-        E.can_skip = requested != 1 && c->vols[0].bricks && c->tf_zero_prefix[0] >= 0 && E.indexable;
+        E.can_skip = requested != 1 && c->vols[0].bricks && c->tf[0].zero_prefix >= 0 && E.indexable;
         E.chain_known = 0;
     }
     if (E.can_skip) {
         if (const int rc = prepare_skip(c, R.variant, s, P)) return rc;
-        if (c->skip_pending) ++c->unbounded_launches;
+        if (c->skip.pending) ++c->skip.unbounded_launches;
     }
     const int fl = choose_flavour(c, requested, R, E);
     c->last.flavour = fl;
@@ -788,7 +752,7 @@ int enqueue_render(vr_ctx* c, RenderRequest R)
         // flavour: the kernels that march one packet per wavefront -- 6, 12, 13, 16, 17 -- share the logical blocks, so an order sorted
         // behind one of them serves the others, and the measured choice tries them in turn on a live scene)
         int cb;
-        const vr_ctx::OrderSlot* slot_sort;
+        const OrderSlot* slot_sort;
         if (const int rc = claim_slot(c, s, &cb, &slot_sort)) return rc;
         if (const int rc = reserve_block_counts(c, s, cb, (size_t)grid.x * (size_t)R.n_frames, &slot_sort)) return rc;
         P.block_counts = c->slot[cb].block_counts;
@@ -799,13 +763,11 @@ int enqueue_render(vr_ctx* c, RenderRequest R)
         const bool ordered = grid.x <= (unsigned)kOrderMaxBlocks && grid.x % 8u == 0;
         if (const int rc = wait_for_order(c, s, ordered, okey, slot_sort, &P.order)) return rc;
 
-        const int ring = (int)(c->last.ring_head % kRing);
+        const int ring = KernelRing::slot(c->last.ring_head);
         if (R.frame_events) VR_HIP(c, hipEventRecord(c->tm.ev_k0, s));
         // launches with a sort behind them are timed from their own records (order_blocks_kernel); events only otherwise
-        const bool time_with_events = !(ordered && c->h_span) || c->event_timing;
-        c->ring_events[ring] = time_with_events;
-        if (c->h_span) c->h_span[ring] = 0;
-        if (c->h_end) c->h_end[ring] = 0;
+        const bool time_with_events = !(ordered && c->ring.h_span) || c->event_timing;
+        c->ring.begin(ring, time_with_events);
         if (time_with_events) VR_HIP(c, hipEventRecord(c->ring.k0[ring], s));
         const MarchBatch& B = fill_batch(P, R.n_frames, R.batch_u, R.batch_out, grid.x);
         LaunchDesc L = {};
@@ -827,7 +789,7 @@ int enqueue_render(vr_ctx* c, RenderRequest R)
             const unsigned per_wg = form.pw_threads / 64u, wgs = (grid.x * (unsigned)R.n_frames + per_wg - 1u) / per_wg;
             L.ltf = tf0_fits_lds(c);
             L.p2_win = p2 && (!off32 || c->p2_window != 0);
-            L.lds_bytes = p2 ? E.p2_lds : (L.ltf ? (unsigned)(c->tf[0].res_o + 2) * 16u : 0u);
+            L.lds_bytes = p2 ? E.p2_lds : (L.ltf ? (unsigned)(c->tf[0].dev.res_o + 2) * 16u : 0u);
             L.queue = PwQueue{c->d_pw_heads + (size_t)cb * 8 * 64, grid.x, c->p2_window};
             L.grid = dim3(wgs < (unsigned)c->n_cus ? wgs : (unsigned)c->n_cus);
             L.block = dim3(form.pw_threads);
@@ -960,11 +922,11 @@ int vr_kernel_times(vr_ctx* c, float* out_ms, int capacity)
     int n = (int)(have < capacity ? have : capacity);
     bool synced = false;
     for (int i = 0; i < n; ++i) {
-        int slot = (int)((c->last.ring_head - n + i) % kRing);
-        if (!c->ring_events[slot]) {  // from the launch's records, written by the sort that runs behind it
-            if (!synced) VR_HIP(c, hipStreamSynchronize(c->order_stream));
+        const int slot = KernelRing::slot(c->last.ring_head - n + i);
+        if (!c->ring.by_events[slot]) {  // from the launch's records, written by the sort that runs behind it
+            if (!synced) VR_HIP(c, hipStreamSynchronize(c->order.stream));
             synced = true;
-            const unsigned long long ticks = *(volatile unsigned long long*)&c->h_span[slot];
+            const unsigned long long ticks = c->ring.span_ticks(slot);
             out_ms[i] = ticks ? (float)((double)(ticks - 1) * 1.0e-5) : 0.0f;
             continue;
         }
@@ -987,7 +949,7 @@ int vr_reset_kernel_times(vr_ctx* c)
     if (!c) return VR_ERR_INVALID_ARG;
     // (sorts of earlier launches still report their launch's duration into the ring: let them finish first)
     VR_HIP(c, hipSetDevice(c->device));
-    VR_HIP(c, hipStreamSynchronize(c->order_stream));
+    VR_HIP(c, hipStreamSynchronize(c->order.stream));
     c->last.ring_head = 0;
     return VR_OK;
 }
@@ -1043,7 +1005,7 @@ int vr_skip_field(vr_ctx* c, int variant, uint8_t* dist, size_t capacity, int di
     for (int i = 0; i < nvol; ++i)
         if (!c->vols[i].vol.data) return fail(c, VR_ERR_NOT_READY, "vr_skip_field: volume slot " + std::to_string(i) + " is empty");
     for (int i = 0; i < ntf; ++i)
-        if (!c->tf[i].opacity || !c->tf[i].color) return fail(c, VR_ERR_NOT_READY, "vr_skip_field: TF slot " + std::to_string(i) + " is empty");
+        if (!c->tf[i].dev.opacity || !c->tf[i].dev.color) return fail(c, VR_ERR_NOT_READY, "vr_skip_field: TF slot " + std::to_string(i) + " is empty");
     if (const int rc = drain(c)) return rc;
     (void)hipGetLastError();
     const Eligibility E = eligibility(c, 0, render_request(c, variant, 0, 1, false, nullptr, nullptr));
@@ -1052,16 +1014,17 @@ int vr_skip_field(vr_ctx* c, int variant, uint8_t* dist, size_t capacity, int di
     std::memset(&P, 0, sizeof P);
     if (const int rc = prepare_skip(c, variant, c->stream, P)) return rc;
     VR_HIP(c, hipStreamSynchronize(c->stream));
+    const SkipField& F = c->skip;
     const float bs[3] = {P.bsx, P.bsy, P.bsz};
-    adopt_skip(c, bs);
-    if (c->skip_pending) return fail(c, VR_ERR_HIP, "vr_skip_field: the field's count and box did not arrive");
-    const size_t n = (size_t)c->dist_bn[0] * c->dist_bn[1] * c->dist_bn[2];
-    if (capacity > 0) VR_HIP(c, hipMemcpy(dist, c->brick_dist, capacity < n ? capacity : n, hipMemcpyDeviceToHost));
+    c->skip.adopt(bs);
+    if (F.pending) return fail(c, VR_ERR_HIP, "vr_skip_field: the field's count and box did not arrive");
+    const size_t n = (size_t)F.bn[0] * F.bn[1] * F.bn[2];
+    if (capacity > 0) VR_HIP(c, hipMemcpy(dist, F.brick_dist, capacity < n ? capacity : n, hipMemcpyDeviceToHost));
     if (dims)
-        for (int a = 0; a < 3; ++a) dims[a] = c->dist_bn[a];
+        for (int a = 0; a < 3; ++a) dims[a] = F.bn[a];
     if (box)
-        for (int a = 0; a < 6; ++a) box[a] = c->skip_box[a];
-    if (active) *active = c->skip_active;
+        for (int a = 0; a < 6; ++a) box[a] = F.box[a];
+    if (active) *active = F.active;
     return (int)n;
 }
 
@@ -1073,7 +1036,7 @@ int vr_skip_indexable(uint16_t nx, uint16_t ny, uint16_t nz)
 int64_t vr_unbounded_box_launches(vr_ctx* c)
 {
     if (!c) return VR_ERR_INVALID_ARG;
-    return c->unbounded_launches;
+    return c->skip.unbounded_launches;
 }
 
 int vr_kernel_choice(vr_ctx* c, int flavours[6], float ms_per_launch[6], int* chosen)
@@ -1083,9 +1046,7 @@ int vr_kernel_choice(vr_ctx* c, int flavours[6], float ms_per_launch[6], int* ch
         if (chosen) *chosen = -1;
         return 0;
     }
-    const vr_ctx::Tune* t = nullptr;
-    for (const auto& e : c->tune)
-        if (e.key != 0 && e.used != 0 && (!t || e.used > t->used)) t = &e;
+    const Trial* t = c->tuner.latest();
     if (chosen) *chosen = t ? t->choice : -1;
     if (!t) return 0;
     for (int i = 0; i < 6; ++i) {

@@ -5,17 +5,17 @@
 namespace {
 
 // Shadows (vr_set_shadows): the key of the light volume a LIGHT frame with uniforms u reads, and the light volume's grid (texels per axis).
-vr_ctx::ShadowKey shadow_key(const vr_ctx* c, const vr_uniforms& u)
+ShadowKey shadow_key(const vr_ctx* c, const vr_uniforms& u)
 {
-    vr_ctx::ShadowKey k;
+    ShadowKey k;
     k.epoch = c->brick_epoch;
     k.opacity = c->opacity_edits;
     // (the clip bounds as fill_frame_params computes them)
     const float box[6] = {0.0f + u.clip_x[0], 0.0f + u.clip_y[0], 0.0f + u.clip_z[0], 1.0f - u.clip_x[1], 1.0f - u.clip_y[1], 1.0f - u.clip_z[1]};
     std::memcpy(k.light, u.light_pos, sizeof k.light);
     std::memcpy(k.box, box, sizeof k.box);
-    std::memcpy(&k.sigma, &c->shadow_sigma, sizeof k.sigma);
-    k.div = c->shadow_div;
+    std::memcpy(&k.sigma, &c->shadows.sigma, sizeof k.sigma);
+    k.div = c->shadows.div;
     k.arith = c->arith;
     return k;
 }
@@ -23,29 +23,23 @@ vr_ctx::ShadowKey shadow_key(const vr_ctx* c, const vr_uniforms& u)
 size_t shadow_grid(const vr_ctx* c, int g[3])
 {
     const int n[3] = {c->vols[0].vol.nx, c->vols[0].vol.ny, c->vols[0].vol.nz};
-    for (int a = 0; a < 3; ++a) g[a] = (n[a] + c->shadow_div - 1) / c->shadow_div;
+    for (int a = 0; a < 3; ++a) g[a] = (n[a] + c->shadows.div - 1) / c->shadows.div;
     return (size_t)g[0] * g[1] * g[2];
 }
 
 // The light volume of a shadowed LIGHT launch on `s` whose parameters are P (volume 0, TF slot 0, the clip box and the light of its first
 // frame; with `skip` LIGHT's distance field in P.brick_dist): the ring's entry of that key, built on `s` into the least recently used
 // entry if there is none -- behind every launch that still reads that entry and behind its own last build -- or waited for once on a
-// stream other than its build's.  Binds it as P.vol[1] and makes it the entry the launch reads (shadow_cur).  An allocation failure
+// stream other than its build's.  Binds it as P.vol[1] and makes it the entry the launch reads (Shadows::cur).  An allocation failure
 // returns before anything is enqueued.
-int prepare_shadow(vr_ctx* c, hipStream_t s, MarchParams& P, const vr_ctx::ShadowKey& key, bool skip, bool off32)
+int prepare_shadow(vr_ctx* c, hipStream_t s, MarchParams& P, const ShadowKey& key, bool skip, bool off32)
 {
+    Shadows& S = c->shadows;
     int g[3];
     const size_t texels = shadow_grid(c, g);
-    int e = -1;
-    for (int i = 0; i < kShadowRing; ++i)
-        if (c->shadow[i].valid && c->shadow[i].key == key) e = i;
-    bool build = e < 0;
-    if (build) {
-        e = 0;
-        for (int i = 1; i < kShadowRing; ++i)
-            if (c->shadow[i].used < c->shadow[e].used) e = i;
-    }
-    vr_ctx::ShadowVol& v = c->shadow[e];
+    bool build;
+    const int e = S.entry(key, &build);
+    ShadowVol& v = S.ring[e];
     if (build) {
         v.valid = false;
         const bool fresh = texels * sizeof(float) > v.buf.cap;
@@ -54,7 +48,7 @@ int prepare_shadow(vr_ctx* c, hipStream_t s, MarchParams& P, const vr_ctx::Shado
         if (!v.built.ev) VR_HIP(c, v.built.ev.create(hipEventDisableTiming));
         if (!fresh) {
             if (const int rc = reuse_wait(c, s, v.buf)) return rc;
-            if (v.built.pending && v.built.stream != s) VR_HIP(c, hipStreamWaitEvent(s, v.built.ev, 0));
+            VR_HIP(c, v.built.rebuild_behind(s));
         }
     }
     DevVolume& lv = P.vol[1];
@@ -70,8 +64,8 @@ int prepare_shadow(vr_ctx* c, hipStream_t s, MarchParams& P, const vr_ctx::Shado
     lv.lut = 0;
     lv.data_bytes = (unsigned)(texels * sizeof(float));
     if (build) {
-        if (c->arith == VR_ARITH_FUSED) vrf::launch_shadow_build(P, (float*)v.buf.p, c->shadow_sigma, skip, off32, s);
-        else vr::launch_shadow_build(P, (float*)v.buf.p, c->shadow_sigma, skip, off32, s);
+        if (c->arith == VR_ARITH_FUSED) vrf::launch_shadow_build(P, (float*)v.buf.p, S.sigma, skip, off32, s);
+        else vr::launch_shadow_build(P, (float*)v.buf.p, S.sigma, skip, off32, s);
         VR_HIP(c, hipGetLastError());
         VR_HIP(c, hipEventRecord(v.built.ev, s));
         v.buf.written();
@@ -81,8 +75,8 @@ int prepare_shadow(vr_ctx* c, hipStream_t s, MarchParams& P, const vr_ctx::Shado
     } else {
         VR_HIP(c, v.built.order_behind(s));
     }
-    v.used = ++c->shadow_clock;
-    c->shadow_cur = e;
+    v.used = ++S.clock;
+    S.cur = e;
     return VR_OK;
 }
 
@@ -111,7 +105,7 @@ int check_slice(vr_ctx* c, const vr_slice_desc* d, const void* out, const char* 
     if (d->filter != VR_SLICE_LINEAR && d->filter != VR_SLICE_NEAREST) return fail(c, VR_ERR_INVALID_ARG, w + ": unknown filter");
     if (d->format != VR_SLICE_RGBA32F && d->format != VR_SLICE_BGRA8) return fail(c, VR_ERR_INVALID_ARG, w + ": unknown format");
     if (!c->vols[d->volume_slot].vol.data) return fail(c, VR_ERR_NOT_READY, w + ": volume slot " + std::to_string(d->volume_slot) + " is empty");
-    if (!c->tf[d->tf_slot].opacity || !c->tf[d->tf_slot].color)
+    if (!c->tf[d->tf_slot].dev.opacity || !c->tf[d->tf_slot].dev.color)
         return fail(c, VR_ERR_NOT_READY, w + ": TF slot " + std::to_string(d->tf_slot) + " is empty");
     return VR_OK;
 }
@@ -123,7 +117,7 @@ int enqueue_slice(vr_ctx* c, const vr_slice_desc& d, void* d_out, hipStream_t s)
 {
     VR_HIP(c, hipSetDevice(c->device));
     (void)hipGetLastError();
-    if (const int rc = wait_for_edits(c, s)) return rc;
+    VR_HIP(c, c->edits.order.order_behind(s));  // the launch comes after every asynchronous edit made so far
     const int vs = d.volume_slot;
     SliceParams S;
     std::memset(&S, 0, sizeof S);
@@ -131,7 +125,7 @@ int enqueue_slice(vr_ctx* c, const vr_slice_desc& d, void* d_out, hipStream_t s)
     if (c->layout_mode == 0) use_bricked_copy(c, vs, S.vol);
     bool off32 = c->vols[vs].bytes() <= 0xFFFFFFFFull;
     if (S.vol.bricked && bricked_grid(S.vol).slots * 16 > 0xFFFFFFFFull) off32 = false;
-    S.tf = c->tf[d.tf_slot];
+    S.tf = c->tf[d.tf_slot].dev;
     for (int a = 0; a < 3; ++a) {
         S.origin[a] = d.origin[a];
         S.du[a] = d.du[a];
@@ -169,7 +163,7 @@ int enqueue_slice(vr_ctx* c, const vr_slice_desc& d, void* d_out, hipStream_t s)
     if (c->arith == VR_ARITH_FUSED) vrf::launch_slice(S, d.reduce, d.filter == VR_SLICE_NEAREST, off32, skip, tiles, s);
     else vr::launch_slice(S, d.reduce, d.filter == VR_SLICE_NEAREST, off32, skip, tiles, s);
     VR_HIP(c, hipGetLastError());
-    mark_table_reads(c, d.tf_slot);
+    c->tf[d.tf_slot].mark_reads(c->order_seq);
     if (const int rc = finish_slot(c, s, cb)) return rc;
     c->slice_buf = cb;
     c->slice_tiles = tiles;
@@ -389,9 +383,9 @@ int vr_shadow_volume(vr_ctx* c, float* out, size_t capacity, int dims[3])
 {
     if (!c) return VR_ERR_INVALID_ARG;
     if (capacity > 0 && !out) return fail(c, VR_ERR_INVALID_ARG, "vr_shadow_volume: out is NULL");
-    if (c->shadow_div == 0) return fail(c, VR_ERR_NOT_READY, "vr_shadow_volume: shadows are off");
+    if (c->shadows.div == 0) return fail(c, VR_ERR_NOT_READY, "vr_shadow_volume: shadows are off");
     if (!c->vols[0].vol.data) return fail(c, VR_ERR_NOT_READY, "vr_shadow_volume: volume slot 0 is empty");
-    if (!c->tf[0].opacity || !c->tf[0].color) return fail(c, VR_ERR_NOT_READY, "vr_shadow_volume: TF slot 0 is empty");
+    if (!c->tf[0].dev.opacity || !c->tf[0].dev.color) return fail(c, VR_ERR_NOT_READY, "vr_shadow_volume: TF slot 0 is empty");
     if (!c->have_uniforms) return fail(c, VR_ERR_NOT_READY, "vr_shadow_volume: vr_set_uniforms has not been called");
     int g[3];
     const size_t n = shadow_grid(c, g);
@@ -409,7 +403,7 @@ int vr_shadow_volume(vr_ctx* c, float* out, size_t capacity, int dims[3])
     if (c->layout_mode == 0) use_bricked_copies(c, P);
     const bool off32 = c->vols[0].bytes() <= 0xFFFFFFFFull && !(P.vol[0].bricked && bricked_grid(P.vol[0]).slots * 16 > 0xFFFFFFFFull);
     const int rc = prepare_shadow(c, c->stream, P, shadow_key(c, c->u), P.brick_dist != nullptr && requested != 1, off32);
-    c->shadow_cur = -1;  // (no launch reads it)
+    c->shadows.cur = -1;  // (no launch reads it)
     if (rc) return rc;
     VR_HIP(c, hipStreamSynchronize(c->stream));
     if (capacity > 0) VR_HIP(c, hipMemcpy(out, P.vol[1].dens, (capacity < n ? capacity : n) * sizeof(float), hipMemcpyDeviceToHost));

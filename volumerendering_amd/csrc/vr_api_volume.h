@@ -126,9 +126,9 @@ int refresh_bricks(vr_ctx* c, int slot)
     (void)hipGetLastError();  // (see enqueue_render)
     VolumeSlot& V = c->vols[slot];
     const DevVolume& v = V.vol;
-    c->merged_stale = true;
+    c->skip.merged_stale = true;
     ++c->brick_epoch;
-    for (auto& e : c->shadow) e.valid = false;  // (the caller drained the device)
+    for (auto& e : c->shadows.ring) e.valid = false;  // (the caller drained the device)
     const int bnx = skip_bricks(v.nx), bny = skip_bricks(v.ny), bnz = skip_bricks(v.nz);
     const size_t nbricks = (size_t)bnx * bny * bnz;
     VR_HIP(c, V.bricks.reserve(nbricks));

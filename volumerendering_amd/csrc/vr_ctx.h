@@ -91,7 +91,7 @@ constexpr int kStreams = 4;   // vr_stream(): streams for frames in flight
 constexpr int kOrderRing = 16;  // launch-order buffers: written behind launch k, read by launches k+3 .. k+6 only (see enqueue_render)
 constexpr int kGen = 4;         // generations of each table and of the distance field (vr_tf_upload_*_async)
 constexpr int kStage = 8;       // pinned staging buffers of the asynchronous table edits
-constexpr int kEditSeen = 8;    // streams remembered to have waited for the latest asynchronous edit
+constexpr int kEditSeen = 8;    // streams remembered to have waited for something built on another stream (BuiltOn)
 constexpr int kShadowRing = 4;  // light volumes kept (vr_set_shadows): one per key, the least recently used one rebuilt
 
 // A device buffer of one generation (capacity in bytes): written by an edit, read by the launches that captured it while it was
@@ -128,6 +128,263 @@ struct BuiltOn {
         const hipError_t e = hipStreamWaitEvent(s, ev, 0);
         if (e == hipSuccess) seen[seen_next++ % kEditSeen] = s;
         return e;
+    }
+    // the next build, on s, comes after this one: a wait of its own, whether or not a launch on s has waited already
+    hipError_t rebuild_behind(hipStream_t s) { return pending && s != stream ? hipStreamWaitEvent(s, ev, 0) : hipSuccess; }
+};
+
+// The transfer-function tables of one slot, [kind]: 0 opacity, 1 colour.  dev is what the launches after an upload see (DevTF layout:
+// the first and the last texel once more at either end); the flags are what skipping derives from the tables.
+struct TfSlot {
+    DevTF dev = {};
+    GenBuf buf[2][kGen];  // the table's generations, cur[kind] the one in use
+    int cur[2] = {};
+    int zero_prefix = -1;  // of the opacity table, -1 if none / not finite
+    bool opacity_finite = false, color_finite = false;
+    GenBuf& current(int kind) { return buf[kind][cur[kind]]; }
+    GenBuf& next(int kind) { return buf[kind][(cur[kind] + 1) % kGen]; }
+    void advance(int kind) { cur[kind] = (cur[kind] + 1) % kGen; }
+    // the host state as the launches after an upload of `table` into current(kind) see it: its resolution, its flags (vr_api_tf.h)
+    void set_current(const float* table, uint32_t R, bool is_color);
+    // launch `seq` (whose slot event is recorded behind it) reads the current generations
+    void mark_reads(unsigned long long seq)
+    {
+        for (int k = 0; k < 2; ++k)
+            if (current(k).p) current(k).reader[seq % kInFlight] = (long long)seq;
+    }
+};
+
+// Asynchronous table edits (vr_tf_upload_*_async): each records order.ev on its stream, behind the one before it; a launch on another
+// stream waits for it once, nothing once a draining call has seen it.  stage: pinned copies of the edited tables, used in turn.
+struct TfEdits {
+    BuiltOn order;
+    struct Stage {  // in the DevTF layout (capacity in bytes); reused behind its copy's event
+        PinnedBuf<void> h;
+        Event done;
+        bool used = false;
+    } stage[kStage];
+    unsigned stage_next = 0;
+};
+
+// What a distance field was built for.
+struct FieldKey {
+    const void* records = nullptr;
+    unsigned long long epoch = ~0ull;  // vr_ctx::brick_epoch
+    int zero_prefix = -2, res = 0, use_rgb = -1;
+    bool operator==(const FieldKey& o) const
+    {
+        return records == o.records && epoch == o.epoch && zero_prefix == o.zero_prefix && res == o.res && use_rgb == o.use_rgb;
+    }
+};
+
+// Exact empty-space skipping (prepare_skip, vr_api_tf.h): VOLUME_MASK's merged records, the distance field over the records in use with
+// its generations, and what each build reports about it.
+struct SkipField {
+    DevBuf<float2> merged_bricks;         // VOLUME_MASK: (CT density max, mask rgb max), rebuilt when stale
+    bool merged_stale = true;
+    unsigned char* brick_dist = nullptr;  // the field in use (field[cur]), built for `key`
+    GenBuf field[kGen];                   // its generations (an asynchronous opacity edit builds the next one)
+    int cur = 0;
+    DevBuf<unsigned char> tmp;            // the y pass's output, the z pass's input
+    int bn[3] = {0, 0, 0};                // bricks per axis of the field
+    FieldKey key;
+    // What each build reports (SkipSummary, pinned, one per generation) and the device words it accumulates in.  pending: the count and
+    // box of build `gen` have not reached the host yet -- launches use the unbounded box meanwhile.
+    PinnedBuf<SkipSummary> h_sum;
+    DevBuf<SkipSumDev> d_sum;
+    unsigned long long gen = 0;
+    bool pending = false;
+    int box[6] = {0x7fffffff, 0x7fffffff, 0x7fffffff, -1, -1, -1};  // of the field in use, once known (vr_skip_field)
+    unsigned long long active = 0;
+    long long unbounded_launches = 0;
+    double active_fraction = 1.0;  // share of bricks that are not inert
+    float abox[6] = {-3.0e38f, -3.0e38f, -3.0e38f, 3.0e38f, 3.0e38f, 3.0e38f};  // uvw box around the active bricks (MarchParams::abox)
+    // generation b holds a field of bn_ bricks freshly built for k: it is the one in use, its count and box on their way
+    void publish(int b, const FieldKey& k, const int bn_[3])
+    {
+        field[b].written();
+        cur = b;
+        brick_dist = (unsigned char*)field[b].p;
+        pending = true;
+        key = k;
+        for (int a = 0; a < 3; ++a) bn[a] = bn_[a];
+    }
+    // The count and box of the field in use, once its build has reported them (pinned, generation first): the share of active bricks
+    // (which the kernel choice reads) and the box of the active bricks in uvw with one brick of margin: brick b of axis a holds the
+    // positions with p * bs - kBrickHalf in [b, b + 1), the first and the last brick those beyond them as well.
+    void adopt(const float bs[3])
+    {
+        if (!pending) return;
+        const volatile SkipSummary& h = h_sum[cur];
+        if (h.gen != gen) return;
+        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        const long long nb = (long long)bn[0] * bn[1] * bn[2];
+        active = h.count;
+        active_fraction = nb > 0 ? (double)h.count / (double)nb : 1.0;
+        for (int a = 0; a < 6; ++a) box[a] = h.box[a];
+        for (int a = 0; a < 3; ++a) {
+            if (box[3 + a] < 0) {
+                // (no active brick: an inverted box.  steps_near_box reports a miss for it only where a step component is zero; every
+                // other ray counts all its steps as near and skips by the field, which says inert everywhere)
+                abox[a] = 3.0e38f;
+                abox[3 + a] = -3.0e38f;
+            } else {
+                abox[a] = (float)(((double)box[a] - 1.0 + (double)kBrickHalf) / (double)bs[a]);
+                abox[3 + a] = (float)(((double)box[3 + a] + 2.0 + (double)kBrickHalf) / (double)bs[a]);
+            }
+        }
+        pending = false;
+    }
+    // the box a launch gets: unbounded (the kernels only prune with it) while the count and box of a rebuild are on their way
+    const float* launch_box() const
+    {
+        static const float unbounded[6] = {-3.0e38f, -3.0e38f, -3.0e38f, 3.0e38f, 3.0e38f, 3.0e38f};
+        return pending ? unbounded : abox;
+    }
+};
+
+// The kernel-time ring (vr_kernel_times): launch number `head` (LastLaunch::ring_head) records itself in slot(head) -- with the events
+// k0 / k1 around it, or, a launch with a sort behind it, from its own records in the pinned words that sort fills.
+struct KernelRing {
+    Event k0[kRing], k1[kRing];
+    bool by_events[kRing] = {};            // launch q was timed with the events (no sort behind it)
+    PinnedBuf<unsigned long long> h_span;  // duration of launch q in 100 MHz ticks + 1, from its records (0 = not known)
+    PinnedBuf<unsigned long long> h_end;   // end of launch q's last workgroup on the 100 MHz device clock, | 1 (0 = not known)
+    static int slot(long long head) { return (int)(head % kRing); }
+    void begin(int q, bool events)  // a launch takes slot q: nothing is known about it yet
+    {
+        by_events[q] = events;
+        if (h_span) h_span[q] = 0;
+        if (h_end) h_end[q] = 0;
+    }
+    unsigned long long span_ticks(int q) const { return *(volatile unsigned long long*)&h_span[q]; }
+    unsigned long long end_ticks(int q) const { return *(volatile unsigned long long*)&h_end[q]; }
+};
+
+// Measured kernel choice (flavour 0): every kernel form is bit-identical, so the context tries the eligible ones on the
+// caller's own frames and keeps the fastest by the launches' own records -- per "what is launched of what" (tune_pick).
+struct Trial {
+    unsigned long long key = 0;   // shader, share, viewport, frames per launch, frames in flight, scene epoch, arithmetic, layout (0 = free)
+    unsigned long long shape = 0; // ... the same without the scene's epochs: a new scene starts from what the last one of this shape kept
+    int n = 0, cand[6] = {};      // the eligible flavours; cand[0] = the prior's pick (what runs while nothing is known)
+    int cur = 0, issued = 0;      // candidate on trial, launches it has had
+    int per = 3, settle = 4;      // launches per candidate; launches before the trial starts (no launch order exists yet)
+    long long launch[6][16] = {}; // ring_head of every trial launch of every candidate (other shapes' launches may lie in between)
+    int choice = -1;              // index into cand of the kernel kept (-1 = trial running)
+    unsigned chain_ref = 0;       // longest ray chain + 1 when it was chosen: the trial re-opens when that has moved by a quarter
+    float cost[6] = {};           // ms per launch measured (0 = no data)
+    unsigned long long used = 0;  // (least recently used slot is recycled)
+    // a new trial of key_ over the n_ flavours of cand_, `first` first, with in_flight frames in flight
+    void reset(unsigned long long key_, unsigned long long shape_, int first, const int* cand_, int n_, int in_flight)
+    {
+        key = key_;
+        shape = shape_;
+        n = 0;
+        cand[n++] = first;
+        for (int i = 0; i < n_; ++i)
+            if (cand_[i] != first && n < 6) cand[n++] = cand_[i];
+        cur = 0;
+        issued = 0;
+        per = in_flight > 1 ? 3 * in_flight + 2 : 3;  // (<= 14: kStreams is 4)
+        settle = in_flight + 3;
+        choice = -1;
+        chain_ref = 0;
+        for (int i = 0; i < 6; ++i) {
+            cost[i] = 0.0f;
+            for (int q = 0; q < 16; ++q) launch[i][q] = -1;
+        }
+    }
+};
+struct Tuner {
+    Trial trials[8];
+    unsigned long long clock = 0;
+    int mode = 1;  // VR_EXP_TUNE=0: the prior alone (round 3's thresholds)
+    const Trial* latest() const  // the trial used most recently (vr_kernel_choice), nullptr if none
+    {
+        const Trial* t = nullptr;
+        for (const auto& e : trials)
+            if (e.key != 0 && e.used != 0 && (!t || e.used > t->used)) t = &e;
+        return t;
+    }
+};
+
+// Longest-first launch order (MarchParams::order): behind every march launch one small kernel sorts that launch's blocks by their
+// longest ray chain; a later launch of the same shape takes its blocks in that order.
+struct OrderSlot {
+    DevBuf<unsigned> buf;
+    hipStream_t stream = nullptr;
+    Event sorted;
+    unsigned long long key = 0, seq = 0;
+    unsigned long long scene_key = 0;  // what the launch rendered, whatever kernel form it took (the chain length's key)
+    bool valid = false;
+};
+struct LaunchOrder {
+    OrderSlot ring[kOrderRing];    // launch seq sorts into ring[seq % kOrderRing]
+    Stream stream;                 // the sorts run here, behind their launch's event: never on a frame's critical path
+    PinnedBuf<unsigned> h_chain;   // one word per ring slot: longest ray chain + 1 of that launch (0 = not known yet)
+    // the longest ray chain + 1 of the most recent launch of scene shape skey whose sort has reported (written to pinned memory by the
+    // launch-order sort; read without synchronising, 0 = not known)
+    unsigned last_chain(unsigned long long skey) const
+    {
+        unsigned chain = 0;
+        if (!h_chain) return chain;
+        unsigned long long best_seq = 0;
+        for (int i = 0; i < kOrderRing; ++i) {
+            const unsigned v = *(volatile unsigned*)&h_chain[i];
+            if (v != 0 && ring[i].scene_key == skey && ring[i].seq + 1 > best_seq) {
+                best_seq = ring[i].seq + 1;
+                chain = v;
+            }
+        }
+        return chain;
+    }
+    // the most recent sort of shape okey that is `age` or `age` + 1 launches old when launch `seq` is enqueued (wait_for_order)
+    const OrderSlot* best(unsigned long long okey, unsigned long long seq, unsigned long long age) const
+    {
+        const OrderSlot* b = nullptr;
+        for (const auto& o : ring)
+            if (o.valid && o.key == okey && o.seq + age + 1 >= seq && o.seq + age <= seq && (!b || o.seq > b->seq)) b = &o;
+        return b;
+    }
+};
+
+// Shadows of the lit shader (vr_set_shadows, vr_shadow.h): the setting, and a ring of light volumes, one per key.  A launch whose key
+// matches an entry reads it (waiting once per stream for its build); otherwise it builds the least recently used entry on its own
+// stream, behind every launch still reading it (buf.reader, as the table generations).  A volume change drains the device and
+// empties the ring.
+struct ShadowKey {
+    unsigned long long epoch = 0, opacity = 0;  // brick_epoch, opacity_edits
+    uint32_t light[3] = {}, box[6] = {}, sigma = 0;
+    int div = 0, arith = 0;
+    bool operator==(const ShadowKey& o) const
+    {
+        return epoch == o.epoch && opacity == o.opacity && std::memcmp(light, o.light, sizeof light) == 0 &&
+               std::memcmp(box, o.box, sizeof box) == 0 && sigma == o.sigma && div == o.div && arith == o.arith;
+    }
+};
+struct ShadowVol {
+    GenBuf buf;
+    ShadowKey key;
+    bool valid = false;
+    BuiltOn built;                // the build may still run: other streams wait for it once
+    unsigned long long used = 0;  // (least recently used entry is rebuilt)
+};
+struct Shadows {
+    int div = 0;         // 0 = off; 1, 2, 4, 8 = voxels per light-volume texel and axis
+    float sigma = 1.0f;  // opacity scale
+    ShadowVol ring[kShadowRing];
+    unsigned long long clock = 0;
+    int cur = -1;  // the entry the launch being enqueued reads (mark_reads)
+    // the entry of `key` (*build = false), else the least recently used one, to be built (*build = true)
+    int entry(const ShadowKey& key, bool* build) const
+    {
+        int e = -1, lru = 0;
+        for (int i = 0; i < kShadowRing; ++i) {
+            if (ring[i].valid && ring[i].key == key) e = i;
+            if (ring[i].used < ring[lru].used) lru = i;
+        }
+        *build = e < 0;
+        return *build ? lru : e;
     }
 };
 
@@ -265,49 +522,13 @@ struct vr_ctx {
     int arith = VR_ARITH_SEPARATE;             // vr_set_arithmetic
     int layout_mode = 0;                       // vr_set_volume_layout: 0 bricked copy + its density plane, 1 vec4 voxels only,
                                                // 3 x-fastest voxels + density plane (2, gradients on the fly, was removed)
-    DevBuf<float2> merged_bricks;              // VOLUME_MASK: (CT density max, mask rgb max), rebuilt when stale
-    bool merged_stale = true;
-    unsigned char* brick_dist = nullptr;       // distance field over the records in use (field[field_cur]); key below says for what
-    GenBuf field[kGen];                        // its generations (an asynchronous opacity edit builds the next one)
-    int field_cur = 0;
-    DevBuf<unsigned char> dist_tmp;            // the y pass's output, the z pass's input
-    int dist_bn[3] = {0, 0, 0};                // bricks per axis of the field
-    const void* dist_records = nullptr;
-    unsigned long long dist_epoch = ~0ull;     // volume-change counter the field was built at
-    int dist_z = -2, dist_res = 0, dist_rgb = -1;
     unsigned long long brick_epoch = 0;        // bumped whenever any brick table changes
-    int tf_zero_prefix[VR_MAX_TFS] = {-1, -1};  // zero prefix of each opacity table, -1 if none / not finite
-    bool tf_color_finite[VR_MAX_TFS] = {false, false};
-    bool tf_opacity_finite[VR_MAX_TFS] = {false, false};
-    DevTF tf[VR_MAX_TFS] = {};
-    GenBuf tf_buf[VR_MAX_TFS][2][kGen];        // [slot][opacity, colour]: the table's generations, tf_cur the one in use (DevTF layout)
-    int tf_cur[VR_MAX_TFS][2] = {};
-    // Asynchronous edits (vr_tf_upload_*_async): each records edit_ev on its stream, behind the one before it; a launch on
-    // another stream waits for it once (edit_seen), nothing once a draining call has seen it (drained_gen).
-    Event edit_ev;
-    hipStream_t edit_stream = nullptr;
-    unsigned long long edit_gen = 0, drained_gen = 0;
-    struct EditSeen {
-        hipStream_t s = nullptr;
-        unsigned long long gen = 0;
-    } edit_seen[kEditSeen];
-    int seen_next = 0;
-    struct Stage {  // pinned copy of an edited table, in the DevTF layout (capacity in bytes); reused behind its copy's event
-        PinnedBuf<void> h;
-        Event done;
-        bool used = false;
-    } stage[kStage];
-    unsigned stage_next = 0;
+    SkipField skip;                            // exact empty-space skipping: the distance field, its count and box
+    TfSlot tf[VR_MAX_TFS];
+    unsigned long long tf_epoch = 0;           // bumped by every table upload
+    unsigned long long opacity_edits = 0;      // bumped by every upload of TF slot 0's opacity table, synchronous or not (ShadowKey's content)
+    TfEdits edits;                             // the asynchronous ones: their order and staging
     std::vector<void*> retired_dev, retired_host;  // replaced on a non-blocking path: freed by the next draining call (drained)
-    // What each field build reports (SkipSummary, pinned, one per field generation) and the device words it accumulates in.
-    // skip_pending: a build's count and box have not reached the host yet -- launches use the unbounded box meanwhile.
-    PinnedBuf<SkipSummary> h_skip;
-    DevBuf<SkipSumDev> d_skip_sum;
-    unsigned long long skip_gen = 0;
-    bool skip_pending = false;
-    int skip_box[6] = {0x7fffffff, 0x7fffffff, 0x7fffffff, -1, -1, -1};  // of the field in use, once known (vr_skip_field)
-    unsigned long long skip_active = 0;
-    long long unbounded_launches = 0;
     vr_uniforms u = {};
     bool have_uniforms = false;
     DevBuf<float4> d_frame;
@@ -316,58 +537,24 @@ struct vr_ctx {
     DevBuf<unsigned long long> d_counters;  // [3] composited, covered, fetched
     RecordSlot slot[kInFlight];
     DevBuf<unsigned> d_pw_heads;  // queue heads of the persistent-wavefront kernel: kInFlight x 8 heads, 256 B apart
-    // Longest-first launch order (MarchParams::order): behind every march launch one small kernel sorts that launch's
-    // blocks by their longest ray chain; a later launch of the same shape takes its blocks in that order.
-    struct OrderSlot {
-        DevBuf<unsigned> buf;
-        hipStream_t stream = nullptr;
-        Event sorted;
-        unsigned long long key = 0, seq = 0;
-        unsigned long long scene_key = 0;  // what the launch rendered, whatever kernel form it took (the chain length's key)
-        bool valid = false;
-    } order_ring[kOrderRing];
-    PinnedBuf<unsigned long long> h_span;  // kRing words: duration of launch q in 100 MHz ticks + 1, from its records (0 = not known)
-    bool ring_events[kRing] = {};          // launch q was timed with the events k0 / k1 instead (no sort behind it)
-    PinnedBuf<unsigned long long> h_end;   // kRing words: end of launch q's last workgroup on the 100 MHz device clock, | 1 (0 = not known)
-    PinnedBuf<unsigned> h_chain;  // one word per ring slot: longest ray chain + 1 of that launch (0 = not known yet)
-    // Measured kernel choice (flavour 0): every kernel form is bit-identical, so the context tries the eligible ones on
-    // the caller's own frames and keeps the fastest by the launches' own records -- per "what is launched of what".
-    struct Tune {
-        unsigned long long key = 0;   // shader, share, viewport, frames per launch, frames in flight, scene epoch, arithmetic, layout (0 = free)
-        unsigned long long shape = 0; // ... the same without the scene's epochs: a new scene starts from what the last one of this shape kept
-        int n = 0, cand[6] = {};      // the eligible flavours; cand[0] = the prior's pick (what runs while nothing is known)
-        int cur = 0, issued = 0;      // candidate on trial, launches it has had
-        int per = 3, settle = 4;      // launches per candidate; launches before the trial starts (no launch order exists yet)
-        long long launch[6][16] = {}; // ring_head of every trial launch of every candidate (other shapes' launches may lie in between)
-        int choice = -1;              // index into cand of the kernel kept (-1 = trial running)
-        unsigned chain_ref = 0;       // longest ray chain + 1 when it was chosen: the trial re-opens when that has moved by a quarter
-        float cost[6] = {};           // ms per launch measured (0 = no data)
-        unsigned long long used = 0;  // (least recently used slot is recycled)
-    } tune[8];
-    unsigned long long tune_clock = 0;
-    unsigned long long tf_epoch = 0;  // bumped by every table upload
-    int tune_mode = 1;                // VR_EXP_TUNE=0: the prior alone (round 3's thresholds)
+    unsigned long long order_seq = 0;  // launches enqueued: record slot order_seq % kInFlight, order slot order_seq % kOrderRing
+    LaunchOrder order;
+    KernelRing ring;
+    Tuner tuner;
     int frames_in_flight = 1;                 // vr_hint_frames_in_flight: frames the caller keeps in flight on different streams
-    unsigned long long order_seq = 0;
     Stream flight[kStreams];  // vr_stream(): streams probed to run side by side (created on first use)
     int n_flight = 0;
-    Stream order_stream;  // the sorts run here, behind their launch's event: never on a frame's critical path
     LastLaunch last;
     bool event_timing = false;                 // vr_set_kernel_timing(VR_TIMING_EVENTS): time every launch with HIP events
     PinnedBuf<unsigned long long> h_counters;  // [3]: the last launch's block counts summed (fetch_counters)
     struct {  // vr_last_timing's events (last.timed: whether the last launch recorded them)
         Event ev_begin, ev_k0, ev_k1, ev_end;
     } tm;
-    struct {  // one (start, stop) event pair per render call, reused round-robin (last.ring_head counts the launches)
-        Event k0[kRing], k1[kRing];
-    } ring;
     int flavour = 0;
     int n_cus = 256;          // compute units of the device
     int default_flavour = 0;  // what flavour 0 resolves to (experiment knob VR_EXP_FLAVOUR)
     unsigned p2_window = 0;   // flavours 16 / 17: records per gather window (VR_EXP_P2_WINDOW: the moving window of volumes >= 4 GiB, forced
                               // onto small volumes by the tests; 0 = what the hardware reaches, just below 4 GiB)
-    double active_fraction = 1.0;  // share of bricks that are not inert, of the distance field in use
-    float abox[6] = {-3.0e38f, -3.0e38f, -3.0e38f, 3.0e38f, 3.0e38f, 3.0e38f};  // uvw box around the active bricks of that field (MarchParams::abox)
     // Slice views (vr_slice_async): a slice takes a record slot like every launch and leaves the march launches' records, counters
     // and timings alone; which slot the last slice wrote (vr_slice_counters)
     int slice_buf = -1;
@@ -378,32 +565,7 @@ struct vr_ctx {
     int hist_buf = -1;
     DevBuf<void> d_hist_out;
     float iso = 0.5f;        // VR_VARIANT_ISO's level (vr_set_iso_value), copied into MarchParams::iso at enqueue
-    // Shadows of the lit shader (vr_set_shadows, vr_shadow.h): the setting, and a ring of light volumes, one per key.  A launch whose key
-    // matches an entry reads it (waiting once per stream for its build); otherwise it builds the least recently used entry on its own
-    // stream, behind every launch still reading it (buf.reader, as the table generations).  A volume change drains the device and
-    // empties the ring.
-    int shadow_div = 0;                     // 0 = off; 1, 2, 4, 8 = voxels per light-volume texel and axis
-    float shadow_sigma = 1.0f;              // opacity scale
-    unsigned long long opacity_edits = 0;   // bumped by every upload of TF slot 0's opacity table, synchronous or not (the key's content)
-    struct ShadowKey {
-        unsigned long long epoch = 0, opacity = 0;  // brick_epoch, opacity_edits
-        uint32_t light[3] = {}, box[6] = {}, sigma = 0;
-        int div = 0, arith = 0;
-        bool operator==(const ShadowKey& o) const
-        {
-            return epoch == o.epoch && opacity == o.opacity && std::memcmp(light, o.light, sizeof light) == 0 &&
-                   std::memcmp(box, o.box, sizeof box) == 0 && sigma == o.sigma && div == o.div && arith == o.arith;
-        }
-    };
-    struct ShadowVol {
-        GenBuf buf;
-        ShadowKey key;
-        bool valid = false;
-        BuiltOn built;                // the build may still run: other streams wait for it once
-        unsigned long long used = 0;  // (least recently used entry is rebuilt)
-    } shadow[kShadowRing];
-    unsigned long long shadow_clock = 0;
-    int shadow_cur = -1;  // the entry the launch being enqueued reads (mark_reads)
+    Shadows shadows;         // vr_set_shadows: the setting and the light volumes
     // Surface-position output (vr_set_output, vr_surf.h): the setting and the threshold, both captured at enqueue; vr_pick's frame
     // (allocated on first use, freed with the viewport's buffers)
     int output = VR_OUTPUT_COLOR;
@@ -451,9 +613,9 @@ void drained(vr_ctx* c)
     for (void* p : c->retired_host) (void)hipHostFree(p);
     c->retired_dev.clear();
     c->retired_host.clear();
-    c->drained_gen = c->edit_gen;
+    c->edits.order.pending = false;
     for (auto& v : c->vols) v.proj_built.pending = false;
-    for (auto& e : c->shadow) e.built.pending = false;
+    for (auto& e : c->shadows.ring) e.built.pending = false;
 }
 
 // Waits for everything on the device, the launches on the caller's streams included; nothing is in flight after it.
