@@ -338,7 +338,8 @@ int vr_last_timing(vr_ctx* ctx, float* kernel_ms, float* total_ms);
  * sorts them (two timing events around every launch cost the frame's stream 11 us: 2 % of a 1080p frame, 8 % of a
  * 1024^2 unlit one); launches without a sort behind them (LDS-tile flavours, > 192 K workgroups) are timed with HIP events
  * on their stream.  At most `capacity` (<= 256) values are written, the number written is returned (negative = error).
- * Waits for the launches concerned.  vr_reset_kernel_times() empties the ring.                                       */
+ * Waits for the launches concerned.  vr_reset_kernel_times() empties the ring: the launches before it are reported no more
+ * (the measured kernel choice keeps reading their records: a reset does not disturb a running trial).                  */
 int vr_kernel_times(vr_ctx* ctx, float* out_ms, int capacity);
 
 /* How vr_kernel_times measures: VR_TIMING_RECORDS (default, as described above) or VR_TIMING_EVENTS -- a pair of HIP events
@@ -372,11 +373,31 @@ int vr_last_block_trace(vr_ctx* ctx, uint64_t* out, int capacity);
  * -- the default may pick 16 for volumes with next to nothing to skip, so `fetched` can differ between frames of one scene.
  * 2, 3, 4, 5, 9 and 14 were forms that lost every A/B and have been removed (HISTORY.md): VR_ERR_UNSUPPORTED.
  *   0  default: a MEASURED choice.  Every form below gives the same bits, so the context tries the eligible ones on the
- *      caller's own frames -- three launches each (frames in flight + 3 with launches in flight), behind a few launches of the
- *      prior's pick so that a launch order exists -- and keeps the fastest by the launches' own records (no synchronisation: the
- *      sort behind a launch writes its duration to pinned memory).  Per "what is launched of what": shader, rank share, viewport,
- *      frames per launch, vr_hint_frames_in_flight, volume / table uploads, arithmetic, layout; the trial re-opens when the
- *      longest ray chain has moved by a quarter.  Candidates: the prior's pick (exact skipping; whole one-at-a-time frames of
+ *      caller's own frames and keeps the fastest by the launches' own records (no synchronisation: the sort behind a launch
+ *      writes its duration and its end to pinned memory).  Per "what is launched of what": shader, rank share, viewport, frames
+ *      per launch, vr_hint_frames_in_flight, volume / table uploads, arithmetic, layout.  The rules (csrc/vr_tuner.h, pinned by
+ *      tests/test_tuner.py), with f = the frames-in-flight hint:
+ *        - a shape with one eligible form runs it and is not measured; launches that cannot be measured (VR_TIMING_EVENTS) run
+ *          the first candidate and count for nothing;
+ *        - f + 3 launches of the first candidate (the prior's pick) come first, so that a launch order exists; then every
+ *          candidate in turn gets 3 launches (f = 1) or 3 f + 2 (f > 1); then the first candidate runs until the last of those
+ *          launches has reported, and the choice is made once;
+ *        - a candidate's cost, f = 1: the shortest span (first workgroup start to last workgroup end) of its launches but the
+ *          first; f > 1: the mean interval between the ends of its launch number f and its launch number 3 f + 2 - f (counted
+ *          from 0), f + 2 intervals that are its alone -- ends that do not advance make the candidate unusable;
+ *        - another kernel replaces the first candidate only below 0.98 times its cost (0.95 with f > 1); between the others
+ *          the strictly smaller cost wins;
+ *        - a trial one of whose launches has not reported 64 launches after its last, or whose launches spread over 256 launches
+ *          or more (vr_kernel_times' ring), keeps the first candidate and reports no costs;
+ *        - the trial re-opens when the longest ray chain + 1 of the scene (c now, r when the choice was made, both known) has left
+ *          [r - r / 4, r + r / 4] in integers; the kernel kept runs first in the new trial, and while it settles;
+ *        - a changed set of eligible forms under the same key starts a fresh trial from the prior's pick; a new key of a shape
+ *          (the key without uploads, arithmetic, layout) starts from what the most recently used decided trial of that shape
+ *          kept, if that is still eligible;
+ *        - eight trials are remembered, the least recently used one makes room.
+ *      A trial names its launches by the context's count of march launches, which nothing rewinds: vr_reset_kernel_times in the
+ *      middle of a trial changes neither the choice nor the costs.  A rank's share without a tile launches nothing and is no part
+ *      of any trial.  Candidates: the prior's pick (exact skipping; whole one-at-a-time frames of
  *      the lit / unlit shader and the composite: 17, or 16 with nothing to skip; else lanes per ray from the launch size, the
  *      frames in flight and the chain length of an earlier launch), 17 / 16, 6, 18, and 10 / 11 (launches that leave the machine
  *      part empty) or 12.  vr_kernel_choice reports what was measured.  VR_EXP_TUNE=0 in the environment: the prior alone.

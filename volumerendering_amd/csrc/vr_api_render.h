@@ -132,109 +132,12 @@ void fill_frame_params(MarchParams& P, const vr_uniforms& u)
     }
 }
 
-// The measured kernel choice (flavour 0).  `cand[0 .. n)` are the flavours that may run this launch (cand[0] = the prior's pick); returns
-// the one to launch now.  A trial gives every candidate `per` launches in turn -- after `settle` launches of the prior, so that a
-// launch order exists (the trial then measures what the steady state runs) -- and reads the launches' durations from
-// the pinned words their sorts fill (no synchronisation: a trial is evaluated when its last word has arrived; until then the
-// prior runs).  One launch at a time: the shortest first-start-to-last-end span of a candidate's launches but its first.  Launches
-// in flight: the mean interval between the ends of its consecutive launches that ran beside launches of the same candidate only
-// (3 x in_flight + 2 launches per turn, the first and the last in_flight of them not used).  The trial re-opens when the scene, the tables,
-// the launch shape or the frames-in-flight hint change (the key) and when the longest ray chain has moved by a quarter.
-int tune_pick(vr_ctx* c, unsigned long long key, unsigned long long shape, const int* cand, int n, unsigned chain_now, bool measurable)
-{
-    if (n <= 1) return cand[0];
-    Tuner& T = c->tuner;
-    const KernelRing& ring = c->ring;
-    Trial* t = nullptr;
-    for (auto& e : T.trials)
-        if (e.key == key) t = &e;
-    const int in_flight = c->frames_in_flight;
-    if (!t) {
-        // a new scene (or table, or arithmetic) of a shape that has been measured before: what that trial kept runs first, if it is
-        // still eligible -- a host that edits a table frame after frame keeps its kernel while every new trial settles
-        int first = cand[0];
-        unsigned long long newest = 0;
-        for (const auto& e : T.trials)
-            if (e.key != 0 && e.shape == shape && e.choice >= 0 && e.used > newest)
-                for (int i = 0; i < n; ++i)
-                    if (cand[i] == e.cand[e.choice]) {
-                        first = cand[i];
-                        newest = e.used;
-                    }
-        t = &T.trials[0];
-        for (auto& e : T.trials)
-            if (e.used < t->used) t = &e;
-        t->reset(key, shape, first, cand, n, in_flight);
-    } else {
-        // the eligible set may have changed under the same key (a flavour knob, a table that fits LDS no more)
-        bool same = t->n == n;
-        for (int i = 0; i < n && same; ++i) {
-            bool found = false;
-            for (int j = 0; j < t->n; ++j) found = found || t->cand[j] == cand[i];
-            same = found;
-        }
-        if (!same) t->reset(key, shape, cand[0], cand, n, in_flight);
-    }
-    t->used = ++T.clock;
-    if (t->choice >= 0) {
-        if (chain_now != 0 && t->chain_ref != 0) {
-            const unsigned lo = t->chain_ref - t->chain_ref / 4, hi = t->chain_ref + t->chain_ref / 4;
-            if (chain_now < lo || chain_now > hi) t->reset(key, shape, t->cand[t->choice], cand, n, in_flight);  // (the kernel kept so far runs while the new trial settles)
-        }
-        if (t->choice >= 0) return t->cand[t->choice];
-    }
-    if (!measurable) return t->cand[0];
-    if (t->settle > 0) {
-        --t->settle;
-        return t->cand[0];
-    }
-    if (t->cur < t->n) {
-        const int f = t->cand[t->cur];
-        t->launch[t->cur][t->issued] = c->last.ring_head;  // (the ring slot this launch will record itself in)
-        if (++t->issued == t->per) {
-            ++t->cur;
-            t->issued = 0;
-        }
-        return f;
-    }
-    // every candidate has had its turn: are the records in?
-    const long long last = t->launch[t->n - 1][t->per - 1];
-    // (a launch of the trial was never measured -- timed with events, or not ordered -- or so many launches of other shapes ran in
-    // between that the trial's first ring slots are about to be written again: keep the prior)
-    if (c->last.ring_head > last + 64 || c->last.ring_head - t->launch[0][0] >= kRing) {
-        t->choice = 0;
-        t->chain_ref = chain_now;
-        return t->cand[0];
-    }
-    for (int i = 0; i < t->n; ++i)
-        for (int q = 0; q < t->per; ++q)
-            if (ring.span_ticks(ring.slot(t->launch[i][q])) == 0) return t->cand[0];
-    int best = 0;
-    for (int i = 0; i < t->n; ++i) {
-        double ticks;
-        if (in_flight > 1) {
-            // (its first `in_flight` launches ran beside the candidate before it, its last ones beside the next: the ends of the
-            // launches in between are `in_flight + 2` intervals apart that are this candidate's alone)
-            const unsigned long long e0 = ring.end_ticks(ring.slot(t->launch[i][in_flight]));
-            const unsigned long long e1 = ring.end_ticks(ring.slot(t->launch[i][t->per - in_flight]));
-            ticks = e1 > e0 ? (double)(e1 - e0) / (double)(t->per - 2 * in_flight) : 1.0e18;
-        } else {
-            ticks = 1.0e18;
-            for (int q = 1; q < t->per; ++q) {
-                const double v = (double)ring.span_ticks(ring.slot(t->launch[i][q]));
-                ticks = v < ticks ? v : ticks;
-            }
-        }
-        t->cost[i] = (float)(ticks * 1.0e-5);  // 100 MHz ticks -> ms
-        // (another kernel must be 2 % faster than the prior's to replace it: the spans of equal kernels differ by about that much)
-        // (... with launches in flight by 5 %: a candidate's interior launches still run beside its neighbours' tails -- a trial that
-        // measured march_kernel at 0.407 ms per C3 frame pipelined against 0.418 kept it, and it then ran at 0.467: gpurun_out/s2p)
-        if (i > 0 && t->cost[i] < t->cost[best] * (best == 0 ? (in_flight > 1 ? 0.95f : 0.98f) : 1.0f)) best = i;
-    }
-    t->choice = best;
-    t->chain_ref = chain_now;
-    return t->cand[best];
-}
+// The kernel-time ring as tune_pick (vr_tuner.h) reads it: the span and the end of launch number L, 0 while its sort has not reported.
+struct RingRecords {
+    const KernelRing& ring;
+    unsigned long long span_ticks(long long launch) const { return ring.span_ticks(KernelRing::slot(launch)); }
+    unsigned long long end_ticks(long long launch) const { return ring.end_ticks(KernelRing::slot(launch)); }
+};
 
 // rays per hardware lane (n_cus x 4 x 5 x 64) of `frames` launches of this rank's share of the frame: how full they keep the machine
 double rays_per_lane(const vr_ctx* c, int rank, int world, int frames)
@@ -332,6 +235,7 @@ struct Eligibility {
     bool indexable;         // the skipping kernels can index volume 0's bricks (bricks_indexable): every skipping form needs it
     bool can_skip;          // exact empty-space skipping (prepare_skip)
     bool whole_frame;       // enough rays to fill the machine in one frame
+    bool empty;             // the share holds no tile: nothing is launched
     unsigned chain_known;   // longest ray chain + 1 of the most recent launch of this scene shape whose sort has reported (0: none)
 };
 
@@ -376,6 +280,7 @@ Eligibility eligibility(const vr_ctx* c, int requested, const RenderRequest& R)
         E.can_skip = E.can_skip && c->vols[0].bricks && c->vols[0].vol.nx == c->vols[2].vol.nx && c->vols[0].vol.ny == c->vols[2].vol.ny &&
                      c->vols[0].vol.nz == c->vols[2].vol.nz;
     E.whole_frame = rays_per_lane(c, R.rank, R.world, 1) >= 4.5;
+    E.empty = tile_count(c, R.rank, R.world) == 0;
     E.chain_known = requested == 0 ? c->order.last_chain(scene_key(c, R, false, false)) : 0;  // (the plain colour launch's key, always)
     return E;
 }
@@ -444,7 +349,8 @@ int choose_flavour(vr_ctx* c, int fl, const RenderRequest& R, const Eligibility&
         if (nothing_to_skip && R.variant != VR_VARIANT_VOLUME_MASK) fl = 16;
         else if (!short_chains) fl = 17;
     }
-    if (!c->tuner.mode) return fl;
+    // (a share without a tile launches nothing and takes no launch number: a trial that counted it would name the next launch twice)
+    if (!c->tuner.mode || E.empty) return fl;
     // ... and THE MEASURED CHOICE (tune_pick): the eligible forms take turns on the caller's own frames, the fastest by the launches'
     // own records stays.  Candidates: the prior; the two-steps-ahead kernel; the one-lane kernel; the depth-parallel kernel (launches
     // that leave the machine part empty) or the persistent kernel without the pipeline (the longest chains).
@@ -467,7 +373,7 @@ int choose_flavour(vr_ctx* c, int fl, const RenderRequest& R, const Eligibility&
     const unsigned long long key = (shape ^ (c->brick_epoch * 0xD6E8FEB86659FD93ull) ^ (c->tf_epoch << 20) ^ ((unsigned long long)c->arith << 1) ^
                                     ((unsigned long long)c->layout_mode << 2)) | 1ull;
     const bool measurable = c->ring.h_span && c->ring.h_end && !c->event_timing;
-    return tune_pick(c, key, shape, cand, n, E.chain_known, measurable);
+    return tune_pick(c->tuner, RingRecords{c->ring}, c->last.ring_head, c->frames_in_flight, key, shape, cand, n, E.chain_known, measurable);
 }
 
 // What each flavour launches -- the one place a flavour's number is decoded.
@@ -918,7 +824,8 @@ int vr_kernel_times(vr_ctx* c, float* out_ms, int capacity)
     if (!c) return VR_ERR_INVALID_ARG;
     if (!out_ms || capacity < 0) return fail(c, VR_ERR_INVALID_ARG, "vr_kernel_times: bad arguments");
     VR_HIP(c, hipSetDevice(c->device));
-    long long have = c->last.ring_head < kRing ? c->last.ring_head : kRing;
+    const long long since = c->last.ring_head - c->ring.reported_from;  // launches since the last vr_reset_kernel_times
+    long long have = since < kRing ? since : kRing;
     int n = (int)(have < capacity ? have : capacity);
     bool synced = false;
     for (int i = 0; i < n; ++i) {
@@ -950,7 +857,8 @@ int vr_reset_kernel_times(vr_ctx* c)
     // (sorts of earlier launches still report their launch's duration into the ring: let them finish first)
     VR_HIP(c, hipSetDevice(c->device));
     VR_HIP(c, hipStreamSynchronize(c->order.stream));
-    c->last.ring_head = 0;
+    // (the launch numbers go on: a running trial of the measured choice names its launches by them)
+    c->ring.reported_from = c->last.ring_head;
     return VR_OK;
 }
 

@@ -84,7 +84,8 @@ struct Stream {
 
 // ---- the context's parts -------------------------------------------------------------------------------------------------------------
 
-constexpr int kRing = 256;    // vr_kernel_times: launches remembered
+#include "vr_tuner.h"  // kRing; the measured kernel choice (Trial, Tuner, tune_pick)
+
 constexpr int kInFlight = 8;  // launches that may be in flight at a time (record buffers used in turn; twice the streams, so that
                                // a caller with four frames in flight never blocks on its oldest launch)
 constexpr int kStreams = 4;   // vr_stream(): streams for frames in flight
@@ -244,8 +245,11 @@ struct SkipField {
 };
 
 // The kernel-time ring (vr_kernel_times): launch number `head` (LastLaunch::ring_head) records itself in slot(head) -- with the events
-// k0 / k1 around it, or, a launch with a sort behind it, from its own records in the pinned words that sort fills.
+// k0 / k1 around it, or, a launch with a sort behind it, from its own records in the pinned words that sort fills.  Launch numbers only
+// grow: vr_reset_kernel_times moves `reported_from` up to the head, so that vr_kernel_times reports nothing older, and leaves the slots
+// and the numbers of the trials' launches (Trial::launch) alone.
 struct KernelRing {
+    long long reported_from = 0;           // vr_kernel_times reports launches reported_from .. head - 1 (the last kRing of them)
     Event k0[kRing], k1[kRing];
     bool by_events[kRing] = {};            // launch q was timed with the events (no sort behind it)
     PinnedBuf<unsigned long long> h_span;  // duration of launch q in 100 MHz ticks + 1, from its records (0 = not known)
@@ -259,53 +263,6 @@ struct KernelRing {
     }
     unsigned long long span_ticks(int q) const { return *(volatile unsigned long long*)&h_span[q]; }
     unsigned long long end_ticks(int q) const { return *(volatile unsigned long long*)&h_end[q]; }
-};
-
-// Measured kernel choice (flavour 0): every kernel form is bit-identical, so the context tries the eligible ones on the
-// caller's own frames and keeps the fastest by the launches' own records -- per "what is launched of what" (tune_pick).
-struct Trial {
-    unsigned long long key = 0;   // shader, share, viewport, frames per launch, frames in flight, scene epoch, arithmetic, layout (0 = free)
-    unsigned long long shape = 0; // ... the same without the scene's epochs: a new scene starts from what the last one of this shape kept
-    int n = 0, cand[6] = {};      // the eligible flavours; cand[0] = the prior's pick (what runs while nothing is known)
-    int cur = 0, issued = 0;      // candidate on trial, launches it has had
-    int per = 3, settle = 4;      // launches per candidate; launches before the trial starts (no launch order exists yet)
-    long long launch[6][16] = {}; // ring_head of every trial launch of every candidate (other shapes' launches may lie in between)
-    int choice = -1;              // index into cand of the kernel kept (-1 = trial running)
-    unsigned chain_ref = 0;       // longest ray chain + 1 when it was chosen: the trial re-opens when that has moved by a quarter
-    float cost[6] = {};           // ms per launch measured (0 = no data)
-    unsigned long long used = 0;  // (least recently used slot is recycled)
-    // a new trial of key_ over the n_ flavours of cand_, `first` first, with in_flight frames in flight
-    void reset(unsigned long long key_, unsigned long long shape_, int first, const int* cand_, int n_, int in_flight)
-    {
-        key = key_;
-        shape = shape_;
-        n = 0;
-        cand[n++] = first;
-        for (int i = 0; i < n_; ++i)
-            if (cand_[i] != first && n < 6) cand[n++] = cand_[i];
-        cur = 0;
-        issued = 0;
-        per = in_flight > 1 ? 3 * in_flight + 2 : 3;  // (<= 14: kStreams is 4)
-        settle = in_flight + 3;
-        choice = -1;
-        chain_ref = 0;
-        for (int i = 0; i < 6; ++i) {
-            cost[i] = 0.0f;
-            for (int q = 0; q < 16; ++q) launch[i][q] = -1;
-        }
-    }
-};
-struct Tuner {
-    Trial trials[8];
-    unsigned long long clock = 0;
-    int mode = 1;  // VR_EXP_TUNE=0: the prior alone (round 3's thresholds)
-    const Trial* latest() const  // the trial used most recently (vr_kernel_choice), nullptr if none
-    {
-        const Trial* t = nullptr;
-        for (const auto& e : trials)
-            if (e.key != 0 && e.used != 0 && (!t || e.used > t->used)) t = &e;
-        return t;
-    }
 };
 
 // Longest-first launch order (MarchParams::order): behind every march launch one small kernel sorts that launch's blocks by their
@@ -495,7 +452,8 @@ struct LastLaunch {
     size_t cnt_offset = 0;     // ... and where in that buffer the records of its last frame start (u64 words)
     bool cnt_pending = false;  // its block counts are not summed / copied to h_counters yet
     bool timed = false;        // it recorded Timing's events (vr_last_timing)
-    long long ring_head = 0;   // total launches recorded in the KernelRing since the last reset
+    long long ring_head = 0;   // march launches recorded in the KernelRing since the context was created: the number the next one takes
+                               // (never rewound by vr_reset_kernel_times -- KernelRing::reported_from; the tuner's trials name launches by it)
 };
 
 // One march launch as its caller asks for it: ONE frame with the context's uniforms into `out` (nullptr -> ctx-owned buffer), or, with
