@@ -40,7 +40,8 @@ typedef enum vr_status {
     VR_ERR_HIP = -2,          /* a HIP runtime call failed (message has hipGetErrorString)   */
     VR_ERR_NOT_READY = -3,    /* render called before the volumes / TFs the variant needs    */
     VR_ERR_UNSUPPORTED = -4,  /* e.g. non-identity model matrix (see vr_set_uniforms)        */
-    VR_ERR_OOM = -5
+    VR_ERR_OOM = -5,
+    VR_ERR_INTERNAL = -6      /* a fault of the library itself: the message names it        */
 } vr_status;
 
 /* One value per fragment shader of the reference. */

@@ -19,6 +19,7 @@ VR_ERR_HIP = -2
 VR_ERR_NOT_READY = -3
 VR_ERR_UNSUPPORTED = -4
 VR_ERR_OOM = -5
+VR_ERR_INTERNAL = -6
 
 BASIC, LIGHT, VOLUME_MASK, THREE_FILES, MULTI_CTRT, TF_CALIB, ILLUSTRATIVE, LIGHT_INSHADER = range(8)
 MIP, MINIP, AVERAGE = 8, 9, 10  # intensity projections of volume slot 0 (include/vr.h)

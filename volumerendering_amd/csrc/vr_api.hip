@@ -20,7 +20,7 @@
 
 // the same dispatch over the kernels compiled with fused multiply-adds (vr_fused.hip)
 namespace vrf {
-void launch_march(const vr::LaunchDesc& L, hipStream_t s, const vr::MarchBatch& B);
+bool launch_march(const vr::LaunchDesc& L, hipStream_t s, const vr::MarchBatch& B);
 void launch_shadow_build(const vr::MarchParams& P, float* out, float sigma, bool skip, bool off32, hipStream_t s);
 void launch_slice(const vr::SliceParams& S, int reduce, bool nearest, bool off32, bool skip, unsigned tiles, hipStream_t s);
 }
@@ -51,9 +51,6 @@ using namespace vr;
 #include "vr_api_outline.h"
 
 namespace {
-
-// kernel forms that lost every A/B and were removed (HISTORY.md): vr_set_kernel_flavour rejects them, VR_EXP_FLAVOUR ignores them
-bool removed_flavour(int f) { return f == 2 || f == 3 || f == 4 || f == 5 || f == 9 || f == 14; }
 
 int alloc_frame(vr_ctx* c)
 {
@@ -113,7 +110,7 @@ int vr_create(vr_ctx** out, uint32_t width, uint32_t height, int device_id)
     // experiment knobs (A/B measurements; none changes any result)
     if (const char* e = getenv("VR_EXP_FLAVOUR")) {
         const int f = atoi(e);
-        if (f >= 0 && f <= 18 && !removed_flavour(f)) c->default_flavour = f;
+        if (flavour_in_range(f) && !removed_flavour(f)) c->default_flavour = f;
     }
     if (const char* e = getenv("VR_EXP_P2_WINDOW")) {  // records per gather window of march_p2_kernel (tests: the moving window on small volumes)
         const long long w = atoll(e);
@@ -332,7 +329,7 @@ int vr_set_surface_threshold(vr_ctx* c, float tau)
 int vr_set_kernel_flavour(vr_ctx* c, int flavour)
 {
     if (!c) return VR_ERR_INVALID_ARG;
-    if (flavour < 0 || flavour > 18) return fail(c, VR_ERR_INVALID_ARG, "vr_set_kernel_flavour: unknown flavour");
+    if (!flavour_in_range(flavour)) return fail(c, VR_ERR_INVALID_ARG, "vr_set_kernel_flavour: unknown flavour");
     if (removed_flavour(flavour))
         return fail(c, VR_ERR_UNSUPPORTED, "vr_set_kernel_flavour: flavour " + std::to_string(flavour) + " was removed (it lost every A/B)");
     c->flavour = flavour;

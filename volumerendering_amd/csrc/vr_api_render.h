@@ -1,4 +1,5 @@
-// vr_api_render.h -- a march launch: its arguments, what may run (eligibility), the kernel choice, the record slots (claim_slot /
+// vr_api_render.h -- a march launch: its arguments, the facts the kernel choice reads (choice_facts; the choice itself -- what may run,
+// the prior, the candidates, what a flavour means, the launch shape -- is vr_choice.h, plain C++), the record slots (claim_slot /
 // finish_slot), the launch itself, the launch-order sort behind it, counters and timing.  Part of vr_api.hip's translation unit.
 #pragma once
 
@@ -9,42 +10,15 @@ ShadowKey shadow_key(const vr_ctx* c, const vr_uniforms& u);
 size_t shadow_grid(const vr_ctx* c, int g[3]);
 int prepare_shadow(vr_ctx* c, hipStream_t s, MarchParams& P, const ShadowKey& key, bool skip, bool off32);
 
-int tiles_x_of(const vr_ctx* c) { return (int)((c->W + kTile - 1) / kTile); }
-int tiles_y_of(const vr_ctx* c) { return (int)((c->H + kTile - 1) / kTile); }
-
-int tile_count(const vr_ctx* c, int rank, int world)
-{
-    int total = tiles_x_of(c) * tiles_y_of(c);
-    if (rank >= total) return 0;
-    return (total - rank + world - 1) / world;
-}
+int tiles_x_of(const vr_ctx* c) { return tiles_across(c->W); }
+int tiles_y_of(const vr_ctx* c) { return tiles_across(c->H); }
+int tile_count(const vr_ctx* c, int rank, int world) { return vr::tile_count(c->W, c->H, rank, world); }
 
 bool is_identity(const float* m)
 {
     for (int i = 0; i < 16; ++i)
         if (m[i] != ((i % 5 == 0) ? 1.0f : 0.0f)) return false;
     return true;
-}
-
-bool is_projection(int variant) { return variant == VR_VARIANT_MIP || variant == VR_VARIANT_MINIP || variant == VR_VARIANT_AVERAGE; }
-
-// volumes / TF pairs each variant samples (vr.h slot tables)
-void variant_needs(int variant, int* nvol, int* ntf)
-{
-    switch (variant) {
-    case VR_VARIANT_BASIC:
-    case VR_VARIANT_LIGHT:
-    case VR_VARIANT_LIGHT_INSHADER:
-    case VR_VARIANT_MIP:
-    case VR_VARIANT_MINIP:
-    case VR_VARIANT_AVERAGE:
-    case VR_VARIANT_ISO: *nvol = 1; *ntf = 1; break;
-    case VR_VARIANT_VOLUME_MASK: *nvol = 3; *ntf = 2; break;
-    case VR_VARIANT_THREE_FILES: *nvol = 2; *ntf = 2; break;  // the mask (slot 2) is bound but never sampled
-    case VR_VARIANT_MULTI_CTRT: *nvol = 2; *ntf = 2; break;
-    case VR_VARIANT_ILLUSTRATIVE: *nvol = 2; *ntf = 2; break;
-    default: *nvol = 2; *ntf = 1; break;  // TF_CALIB
-    }
 }
 
 // Inverse of a column-major 4x4 in double precision (cofactors); false if singular / not finite.
@@ -139,13 +113,6 @@ struct RingRecords {
     unsigned long long end_ticks(long long launch) const { return ring.end_ticks(KernelRing::slot(launch)); }
 };
 
-// rays per hardware lane (n_cus x 4 x 5 x 64) of `frames` launches of this rank's share of the frame: how full they keep the machine
-double rays_per_lane(const vr_ctx* c, int rank, int world, int frames)
-{
-    const long long px = (long long)tile_count(c, rank, world) * kTile * kTile;
-    return (double)px * frames / ((double)c->n_cus * 4.0 * 5.0 * 64.0);
-}
-
 // what a launch rendered, whatever kernel form it took (OrderSlot::scene_key: the key of the longest ray chain its sort reports)
 // (a surface launch -- vr_set_output -- is a scene of its own: its chains say nothing about the colour launch's)
 // (so is a launch between ray bounds -- vr_set_ray_bounds)
@@ -155,9 +122,6 @@ unsigned long long scene_key(const vr_ctx* c, const RenderRequest& R, bool surfa
            ((unsigned long long)c->W << 40) ^ ((unsigned long long)c->H << 24);
 }
 
-// TF slot 0 fits a workgroup's LDS beside nothing else: one resolution for both tables, R <= 8190 (128 KiB)
-bool tf0_fits_lds(const vr_ctx* c) { return c->tf[0].dev.res_o == c->tf[0].dev.res_c && c->tf[0].dev.res_o + 2 <= 8192; }
-
 // The arguments of a launch and the slots its shader samples (*nvol volumes); *off32: every one of them below 4 GiB.  Derives what the
 // request does not say itself (R.surface, R.bounded) and refuses what these cannot do.
 int check_render_args(vr_ctx* c, RenderRequest& R, int* nvol, bool* off32)
@@ -165,15 +129,13 @@ int check_render_args(vr_ctx* c, RenderRequest& R, int* nvol, bool* off32)
     // surface-position output (vr_set_output; a pick launch whatever the setting): the unlit / lit shader and the isosurface -- any
     // other variant is refused whatever the scene holds
     R.surface = c->output == VR_OUTPUT_SURFACE || R.pick_px[0] >= 0;
-    if (R.surface && R.variant >= 0 && R.variant < VR_VARIANT_COUNT && R.variant != VR_VARIANT_BASIC && R.variant != VR_VARIANT_LIGHT &&
-        R.variant != VR_VARIANT_ISO)
+    if (R.surface && R.variant >= 0 && R.variant < VR_VARIANT_COUNT && !kShader[R.variant].surface)
         return fail(c, VR_ERR_UNSUPPORTED, "vr_render: surface output exists for BASIC, LIGHT and ISO only");
     // ray bounds (vr_set_ray_bounds; a pick launch ignores them): colour launches of one frame of the unlit shader and of the lit one
     // without shadows -- anything else is refused, never rendered with the occluder ignored
     R.bounded = (c->d_near || c->d_far) && R.pick_px[0] < 0;
     if (R.bounded && R.variant >= 0 && R.variant < VR_VARIANT_COUNT) {
-        if (R.variant != VR_VARIANT_BASIC && R.variant != VR_VARIANT_LIGHT)
-            return fail(c, VR_ERR_UNSUPPORTED, "vr_render: ray bounds exist for BASIC and LIGHT only");
+        if (!kShader[R.variant].bounds) return fail(c, VR_ERR_UNSUPPORTED, "vr_render: ray bounds exist for BASIC and LIGHT only");
         if (R.surface) return fail(c, VR_ERR_UNSUPPORTED, "vr_render: ray bounds do not apply to surface output");
         if (R.variant == VR_VARIANT_LIGHT && c->shadows.div != 0)
             return fail(c, VR_ERR_UNSUPPORTED, "vr_render: ray bounds do not apply to LIGHT with shadows on");
@@ -194,8 +156,8 @@ int check_render_args(vr_ctx* c, RenderRequest& R, int* nvol, bool* off32)
         if (R.n_frames != 1) return fail(c, VR_ERR_INVALID_ARG, "vr_render: several frames per launch need their uniforms");
         if (!c->have_uniforms) return fail(c, VR_ERR_NOT_READY, "vr_render: vr_set_uniforms has not been called");
     }
-    int ntf;
-    variant_needs(R.variant, nvol, &ntf);
+    *nvol = kShader[R.variant].nvol;
+    const int ntf = kShader[R.variant].ntf;
     *off32 = true;
     for (int i = 0; i < *nvol; ++i) {
         if (!c->vols[i].vol.data) return fail(c, VR_ERR_NOT_READY, "vr_render: volume slot " + std::to_string(i) + " is empty");
@@ -226,206 +188,30 @@ void fill_launch_params(const vr_ctx* c, MarchParams& P, const vr_uniforms& u0, 
     P.iso = c->iso;  // (every frame of a batch: fill_batch copies P)
 }
 
-// What a launch could run, worked out once before the kernel choice (choose_flavour).
-struct Eligibility {
-    bool p2_ok;             // two steps ahead (16, 17) can run
-    unsigned p2_lds;        // ... with this much dynamic LDS (TF slot 0 and the three axis tables)
-    bool lut_ok;            // 18 can run
-    unsigned lut_lds;       // ... with this much (the slot tables of volume 0)
-    bool indexable;         // the skipping kernels can index volume 0's bricks (bricks_indexable): every skipping form needs it
-    bool can_skip;          // exact empty-space skipping (prepare_skip)
-    bool whole_frame;       // enough rays to fill the machine in one frame
-    bool empty;             // the share holds no tile: nothing is launched
-    unsigned chain_known;   // longest ray chain + 1 of the most recent launch of this scene shape whose sort has reported (0: none)
-};
-
-Eligibility eligibility(const vr_ctx* c, int requested, const RenderRequest& R)
+// What the kernel choice (vr_choice.h) reads of a launch and of the context.  requested: the flavour asked for -- only the default
+// choice looks the chain length up.
+ChoiceFacts choice_facts(const vr_ctx* c, const RenderRequest& R, int requested)
 {
-    Eligibility E = {};
-    // two steps ahead (16, 17; march_p2_kernel, vr_p2.h): lit / unlit shader and the three-volume composite (with its brick records:
-    // choose_flavour); TF slot 0 (one resolution for both tables) and the three axis tables in LDS; the bricked copy with 32-bit slots,
-    // rows and slabs of bricks below 2^24 slots; a volume of 4 GiB or more through a moving window of at least four z-slabs of bricks.
-    // Launches of several frames and launches in flight included.
-    const int sv = R.variant == VR_VARIANT_VOLUME_MASK ? 2 : 0;  // the volume whose density drives tf[0]'s opacity
-    E.p2_ok = (R.variant == VR_VARIANT_LIGHT || R.variant == VR_VARIANT_BASIC || R.variant == VR_VARIANT_VOLUME_MASK) && tf0_fits_lds(c) &&
-              c->layout_mode == 0 && c->vols[sv].bricked && c->vols[sv].bdens;
-    if (E.p2_ok) {
-        const DevVolume& v = c->vols[sv].vol;
-        const BrickedGrid g = bricked_grid(v);
-        const size_t slab = (size_t)g.nbx * g.nby * kVbN, window = R.variant == VR_VARIANT_BASIC ? 0x3fffffffull : 0x0fffffffull;
-        const size_t lds = (size_t)(c->tf[0].dev.res_o + 2) * 16 + ((size_t)v.nx + v.ny + v.nz + 3) * 8;
-        E.p2_ok = g.slots <= 0xFFFFFFFFull && slab < (1u << 24) && (c->p2_window ? c->p2_window / slab >= 3 : window / slab >= 4) && lds <= 160u * 1024u;
-        E.p2_lds = (unsigned)lds;
+    ChoiceFacts F = {};
+    F.variant = R.variant, F.rank = R.rank, F.world = R.world, F.n_frames = R.n_frames;
+    F.packed = R.packed, F.surface = R.surface, F.bounded = R.bounded;
+    for (int i = 0; i < VR_MAX_VOLUMES; ++i) {
+        const VolumeSlot& v = c->vols[i];
+        F.vols[i] = {v.vol.nx, v.vol.ny, v.vol.nz, v.bricked.p != nullptr, v.bdens.p != nullptr, v.bricks.p != nullptr};
     }
-    // 18: march_kernel with the slot tables of volume 0 in its workgroup's LDS (make_cell_lut): the shaders that sample ONE volume, the
-    // bricked copy with 32-bit slots
-    E.lut_ok = (R.variant == VR_VARIANT_LIGHT || R.variant == VR_VARIANT_BASIC || R.variant == VR_VARIANT_LIGHT_INSHADER) && c->layout_mode == 0 &&
-               c->vols[0].bricked && c->vols[0].bdens;
-    if (E.lut_ok) {
-        E.lut_lds = (unsigned)(((size_t)c->vols[0].vol.nx + c->vols[0].vol.ny + c->vols[0].vol.nz + 6) * 4);
-        E.lut_ok = bricked_grid(c->vols[0].vol).slots <= 0xFFFFFFFFull && E.lut_lds <= 32u * 1024u;
+    for (int i = 0; i < VR_MAX_TFS; ++i) {
+        const TfSlot& t = c->tf[i];
+        F.tf[i] = {t.dev.res_o, t.dev.res_c, t.zero_prefix, t.color_finite, t.opacity_finite};
     }
-    // exact empty-space skipping: only for the shaders whose opacity is the CT table value alone, only when a zero-opacity sample is
-    // provably the identity (finite colour table and light), and unless flavour 1 asks for the plain kernel (no rule of choose_flavour
-    // turns another flavour into 1 or 1 into another)
-    E.indexable = volume_bricks_indexable(c->vols[0].vol);
-    E.can_skip = (R.variant == VR_VARIANT_BASIC || R.variant == VR_VARIANT_LIGHT || R.variant == VR_VARIANT_THREE_FILES ||
-                  R.variant == VR_VARIANT_VOLUME_MASK || R.variant == VR_VARIANT_LIGHT_INSHADER) &&
-                 requested != 1 && c->vols[sv].bricks && c->tf[0].zero_prefix >= 0 && c->tf[0].color_finite;
-    for (int f = 0; f < R.n_frames; ++f) E.can_skip = E.can_skip && all_finite(R.batch_u ? R.batch_u[f].light_pos : c->u.light_pos, 12);
-    // the kernels index bricks with 24-bit multiplies and 32-bit byte offsets
-    E.can_skip = E.can_skip && volume_bricks_indexable(c->vols[sv].vol);
-    if (R.variant == VR_VARIANT_THREE_FILES) E.can_skip = E.can_skip && c->tf[1].color_finite && c->tf[1].opacity_finite;
-    if (R.variant == VR_VARIANT_VOLUME_MASK)  // mask and CT must share one grid so that one brick index serves both
-        E.can_skip = E.can_skip && c->vols[0].bricks && c->vols[0].vol.nx == c->vols[2].vol.nx && c->vols[0].vol.ny == c->vols[2].vol.ny &&
-                     c->vols[0].vol.nz == c->vols[2].vol.nz;
-    E.whole_frame = rays_per_lane(c, R.rank, R.world, 1) >= 4.5;
-    E.empty = tile_count(c, R.rank, R.world) == 0;
-    E.chain_known = requested == 0 ? c->order.last_chain(scene_key(c, R, false, false)) : 0;  // (the plain colour launch's key, always)
-    return E;
-}
-
-// The kernel form ("flavour") a launch runs: `fl` is the one asked for (vr_set_kernel_flavour, else VR_EXP_FLAVOUR), 0 = the default.
-int choose_flavour(vr_ctx* c, int fl, const RenderRequest& R, const Eligibility& E)
-{
-    // The one-lane families come in pairs: 1 asks for the form without skipping (the odd flavour + 1), everything else runs as the
-    // skipping one; nothing is measured.  The first row that applies decides (the isosurface's surface output keeps 21 / 22).
-    const struct {
-        bool applies;
-        int skipping;
-    } pairs[] = {
-        {R.bounded, 27},                                              // the unlit / lit shader between ray bounds
-        {R.surface && R.variant != VR_VARIANT_ISO, 25},               // the surface-position output of the unlit / lit shader
-        {is_projection(R.variant), 19},                               // the projections
-        {R.variant == VR_VARIANT_ISO, 21},                            // the isosurface
-        {R.variant == VR_VARIANT_LIGHT && c->shadows.div != 0, 23},    // the shadowed lit shader
-    };
-    for (const auto& pr : pairs)
-        if (pr.applies) return fl == 1 ? pr.skipping + 1 : pr.skipping;
-    const bool auto_choice = fl == 0;
-    const double rays = rays_per_lane(c, R.rank, R.world, c->frames_in_flight * R.n_frames);
-    const bool short_chains = E.chain_known != 0 && E.chain_known - 1 < 128;
-    if (auto_choice) {
-        // Default: pick the lanes per ray from what will be on the machine.  With many rays per hardware lane the machine is
-        // throughput-bound and one lane per ray does the least work; with few (a small frame, or one GPU's share of the
-        // tiles) the frame waits for its longest rays, whose chains of dependent samples the depth-parallel kernel cuts to a
-        // half or a quarter (vr_dp.h).  Two things refine the round-1 rule (thresholds measured on C3 at 1 / 2 / 4 / 8 ranks):
-        //  * frames in flight: when the caller keeps several frames in flight on different streams (it says so with
-        //    vr_hint_frames_in_flight; asking the events instead flushes the runtime's command batches and costs more than it
-        //    tells) the other launches fill the machine as well, so the rays per lane count once per frame in flight (a
-        //    rank's half of C3, two frames pipelined: 0.34 ms with one lane, 0.42 with two);
-        //  * how long the chains really are (E.chain_known).  Chains too short to matter -- under 128 samples, 0.2 ms (C2: 102) --
-        //    leave nothing for the depth-parallel kernels to cut (C2: 0.133 / 0.091 ms per frame with one lane, 0.153 / 0.123 with
-        //    two), unless the launch is too small to fill the machine at all.
-        // (two lanes per ray from 2 rays per lane on, four below: re-measured on the bricked layout -- a rank's quarter of C3
-        // (1.6 rays per lane), one frame at a time: 0.274 ms with two lanes, 0.203 with four; a rank's half (3.2): 0.362 / 0.377;
-        // a quarter with two launches in flight counts 3.2 and keeps two lanes: 0.190 / 0.217 per frame)
-        fl = (rays >= 4.5 || (short_chains && rays >= 1.2)) ? 6 : (rays >= 2.0 ? 11 : 10);
-    }
-    // what a form runs as where it cannot run: persistent wavefronts (12, 13; vr_pw.h) exist for launches of one frame
-    if ((fl == 12 || fl == 13) && R.n_frames != 1) fl = 6;
-    if ((fl == 16 || fl == 17) && !E.p2_ok) fl = R.n_frames != 1 ? 6 : (fl == 16 ? 13 : 12);
-    if (fl == 18 && !E.lut_ok) fl = 6;
-    if (fl == 16 && R.variant == VR_VARIANT_VOLUME_MASK) fl = 17;  // (the composite's form is the skipping one: its mask records)
-    // LDS tiles (15; vr_lt.h): the lit shader, launches of one frame
-    if (fl == 15 && (R.n_frames != 1 || R.variant != VR_VARIANT_LIGHT)) fl = 6;
-    // the illustrative shader's opacity reads the accumulated alpha: its steps cannot be sampled side by side
-    if (R.variant == VR_VARIANT_ILLUSTRATIVE && (fl == 7 || fl == 8 || fl == 10 || fl == 11)) fl = 6;
-    // the in-shader gradient variant (seven density fetches per sample) exists as the one-lane kernel only
-    if (R.variant == VR_VARIANT_LIGHT_INSHADER && fl != 1 && fl != 12 && fl != 13 && fl != 18) fl = 6;
-    if ((fl == 16 || fl == 17) && R.variant == VR_VARIANT_VOLUME_MASK && !E.can_skip)  // (no brick records: no on-demand mask fetch)
-        fl = R.n_frames != 1 ? 6 : 12;
-    if (!auto_choice) return fl;
-
-    // Default choice, second part -- THE PRIOR: what runs before anything has been measured.  Whole frames of the lit / unlit shader
-    // and of the composite, one launch at a time: the kernel with the corner loads two steps ahead (vr_p2.h) -- 17, or 16 where next to
-    // nothing can be skipped (noisy air under the default ramp 2.95 -> 1.97 ms; C3 0.65 -> 0.51; C4 0.72 -> 0.57) -- unless an earlier
-    // launch of this shape says its chains are short (C2, longest chain 102: a packet is too short for the pipeline's fill and a
-    // dequeue, 0.111 -> 0.161).  The same with launches in flight and several frames per launch since the approach loop (C3 0.417 / 0.382
-    // ms per frame against march_kernel's 0.464 / 0.445; C5 level); shares of a frame: the first part's choice.
-    const bool p2_variant = R.variant == VR_VARIANT_LIGHT || R.variant == VR_VARIANT_BASIC || (R.variant == VR_VARIANT_VOLUME_MASK && E.can_skip);
-    const bool nothing_to_skip = !E.can_skip || c->skip.active_fraction >= 0.9;  // (prepare_skip has measured the share of active bricks)
-    if (fl == 6 && E.whole_frame && E.p2_ok && p2_variant) {
-        if (nothing_to_skip && R.variant != VR_VARIANT_VOLUME_MASK) fl = 16;
-        else if (!short_chains) fl = 17;
-    }
-    // (a share without a tile launches nothing and takes no launch number: a trial that counted it would name the next launch twice)
-    if (!c->tuner.mode || E.empty) return fl;
-    // ... and THE MEASURED CHOICE (tune_pick): the eligible forms take turns on the caller's own frames, the fastest by the launches'
-    // own records stays.  Candidates: the prior; the two-steps-ahead kernel; the one-lane kernel; the depth-parallel kernel (launches
-    // that leave the machine part empty) or the persistent kernel without the pipeline (the longest chains).
-    int cand[6], n = 0;
-    auto add = [&](int f) {
-        for (int i = 0; i < n; ++i)
-            if (cand[i] == f) return;
-        if (n < 6) cand[n++] = f;
-    };
-    add(fl);
-    if (E.p2_ok && p2_variant) add((nothing_to_skip && R.variant != VR_VARIANT_VOLUME_MASK) || !E.can_skip ? 16 : 17);
-    add(6);
-    if (E.lut_ok && E.lut_lds <= 8u * 1024u) add(18);  // (the one-lane kernel with its slot arithmetic from LDS tables; larger tables cost it wavefronts per CU: C5 4.2 vs 3.4 ms)
-    const bool dp_variant = R.variant != VR_VARIANT_ILLUSTRATIVE && R.variant != VR_VARIANT_LIGHT_INSHADER;
-    if (!E.whole_frame && dp_variant) add(rays >= 2.0 ? 11 : 10);
-    else if (R.n_frames == 1 && (R.variant == VR_VARIANT_LIGHT || R.variant == VR_VARIANT_BASIC)) add(12);
-    const unsigned long long shape = 0x9E3779B97F4A7C15ull * (((unsigned long long)R.variant << 56) ^ ((unsigned long long)R.world << 48) ^ ((unsigned long long)R.rank << 40) ^
-                                                             ((unsigned long long)c->W << 24) ^ ((unsigned long long)c->H << 8) ^ (R.packed ? 0x80ull : 0ull) ^
-                                                             ((unsigned long long)R.n_frames << 4) ^ (unsigned long long)c->frames_in_flight) | 1ull;
-    const unsigned long long key = (shape ^ (c->brick_epoch * 0xD6E8FEB86659FD93ull) ^ (c->tf_epoch << 20) ^ ((unsigned long long)c->arith << 1) ^
-                                    ((unsigned long long)c->layout_mode << 2)) | 1ull;
-    const bool measurable = c->ring.h_span && c->ring.h_end && !c->event_timing;
-    return tune_pick(c->tuner, RingRecords{c->ring}, c->last.ring_head, c->frames_in_flight, key, shape, cand, n, E.chain_known, measurable);
-}
-
-// What each flavour launches -- the one place a flavour's number is decoded.
-struct KernelForm {
-    LaunchDesc::Family family;
-    int lanes;            // kDp: lanes per ray (vr_dp.h): 64 / 32 workgroups per tile
-    bool pipe;            // kDp / kPw: the next round's / step's corner loads software-pipelined
-    bool skip;            // the skipping flavour of a pair (17 of 16 / 17; 19, 21, 23, 25, 27 of the one-lane families): LaunchDesc::skip once
-                          // its records are in place
-    bool lut;             // kPlain: the slot tables of volume 0 in LDS
-    unsigned pw_threads;  // kPw / kP2: threads per workgroup
-    // what follows from the family
-    bool range_records() const { return family == LaunchDesc::kProj || family == LaunchDesc::kIso; }  // skips by prepare_proj's records
-    bool measured() const  // a candidate of the measured choice (the one-lane families never are)
-    {
-        return !(range_records() || family == LaunchDesc::kShadow || family == LaunchDesc::kSurf || family == LaunchDesc::kBound);
-    }
-};
-
-KernelForm kernel_form(int fl, int variant)
-{
-    // (march_p2_kernel: two corner buffers, 3 wavefronts per SIMD at most; with every ray sampling all the time two per SIMD are faster
-    // -- the corner data in flight is many times the L1 either way: noisy air 2.13 -> 2.04 ms.  The unlit shader's two buffers are 4-byte
-    // densities, 101 VGPRs: 4 wavefronts per SIMD -- C2 one frame at a time 0.121 -> 0.113 ms, thin table 0.255 -> 0.239, four frames per
-    // launch 0.070 -> 0.061: tools/experiments/s2h.sh.  Launches in flight: the same shape.  Two workgroups of 6 wavefronts do not share
-    // a CU -- the second one's wavefronts would have to go 1-1-2-2 over the SIMDs where the dispatcher deals 2-2-1-1: measured 0.75 ms
-    // per C3 frame, what one such workgroup per CU takes -- and two of 4 run at 8 wavefronts per CU: 0.63 against 0.54; three of 4, the
-    // same 12 wavefronts per CU, take 0.79 ms one frame at a time and 0.62 in flight against 0.55 / 0.51: profiles/r04_p2_launch_shapes.txt)
-    using D = LaunchDesc;
-    switch (fl) {
-    case 7: return {D::kDp, 4, false, false, false, 0u};
-    case 8: return {D::kDp, 2, false, false, false, 0u};
-    case 10: return {D::kDp, 4, true, false, false, 0u};
-    case 11: return {D::kDp, 2, true, false, false, 0u};
-    case 12: return {D::kPw, 0, false, false, false, 1024u};
-    case 13: return {D::kPw, 0, true, false, false, 1024u};
-    case 15: return {D::kLt, 0, false, false, false, 0u};
-    case 16: return {D::kP2, 0, false, false, false, 512u};
-    case 17: return {D::kP2, 0, false, true, false, variant == VR_VARIANT_BASIC ? 1024u : 768u};
-    case 18: return {D::kPlain, 0, false, false, true, 0u};
-    case 19:
-    case 20: return {D::kProj, 0, false, fl == 19, false, 0u};
-    case 21:
-    case 22: return {D::kIso, 0, false, fl == 21, false, 0u};
-    case 23:
-    case 24: return {D::kShadow, 0, false, fl == 23, false, 0u};
-    case 25:
-    case 26: return {D::kSurf, 0, false, fl == 25, false, 0u};
-    case 27:
-    case 28: return {D::kBound, 0, false, fl == 27, false, 0u};
-    default: return {D::kPlain, 0, false, false, false, 0u};  // 1, 6
-    }
+    F.layout_mode = c->layout_mode, F.p2_window = c->p2_window, F.n_cus = c->n_cus, F.W = c->W, F.H = c->H;
+    F.frames_in_flight = c->frames_in_flight;
+    F.shadows = c->shadows.div != 0;
+    F.lights_finite = lights_finite(R.batch_u ? R.batch_u : &c->u, R.n_frames);
+    F.active_fraction = c->skip.active_fraction;
+    F.tuner_mode = c->tuner.mode;
+    F.last_chain = requested == 0 ? c->order.last_chain(scene_key(c, R, false, false)) : 0;  // (the plain colour launch's key, always)
+    F.brick_epoch = c->brick_epoch, F.tf_epoch = c->tf_epoch, F.arith = c->arith;
+    return F;
 }
 
 // Claims the record slot of the next launch, *cb = order_seq % kInFlight.  (Record slot and order slot both derive from order_seq, which
@@ -597,19 +383,17 @@ int enqueue_render(vr_ctx* c, RenderRequest R)
         }
     // the kernel choice: what can run, the skipping state (the prior reads its share of active bricks), the flavour
     const int requested = c->flavour == 0 ? c->default_flavour : c->flavour;
-    Eligibility E = eligibility(c, requested, R);
-    if (R.surface && R.variant != VR_VARIANT_ISO) {
-        // The surface march skips by the distance field of BASIC / LIGHT under the weakest condition that is still exact: an inert
-        // brick's samples have opacity exactly 0, which leaves the accumulated alpha as it is whatever the colour table and the
-        // light hold -- neither is read.  So: the brick records, a zero prefix of the opacity table, the kernels' index range.
-        E.can_skip = requested != 1 && c->vols[0].bricks && c->tf[0].zero_prefix >= 0 && E.indexable;
-        E.chain_known = 0;
-    }
+    ChoiceFacts F = choice_facts(c, R, requested);
+    const Eligibility E = eligibility(F, requested);
     if (E.can_skip) {
         if (const int rc = prepare_skip(c, R.variant, s, P)) return rc;
         if (c->skip.pending) ++c->skip.unbounded_launches;
     }
-    const int fl = choose_flavour(c, requested, R, E);
+    F.active_fraction = c->skip.active_fraction;  // (prepare_skip may just have learnt it)
+    const Choice choice = choose_flavour(F, requested, E);
+    const int fl = !choice.tune ? choice.prior
+                                : tune_pick(c->tuner, RingRecords{c->ring}, c->last.ring_head, c->frames_in_flight, choice.key, choice.shape, choice.cand,
+                                            choice.n, E.chain_known, c->ring.h_span && c->ring.h_end && !c->event_timing);
     c->last.flavour = fl;
     const KernelForm form = kernel_form(fl, R.variant);
     c->last.unmeasured = !form.measured();
@@ -621,7 +405,7 @@ int enqueue_render(vr_ctx* c, RenderRequest R)
 
     if (c->layout_mode == 0) use_bricked_copies(c, P);
     if (form.lut && P.vol[0].bricked) P.vol[0].lut = 1;  // (march_kernel fills the tables; every fetch of volume 0 goes through them)
-    if (form.family == LaunchDesc::kBound) {  // the depth buffers, in the slots these shaders do not sample (vr_bound.h)
+    if (form.family == KernelForm::kBound) {  // the depth buffers, in the slots these shaders do not sample (vr_bound.h)
         P.vol[1].data = reinterpret_cast<const float4*>(c->d_near);
         P.vol[2].data = reinterpret_cast<const float4*>(c->d_far);
     }
@@ -646,14 +430,10 @@ int enqueue_render(vr_ctx* c, RenderRequest R)
         // the light volume it reads: built here when its key has none (inside vr_last_timing's total, outside its kernel time)
         if (shadowed)
             if (const int rc = prepare_shadow(c, s, P, shadow_k, skip, off32)) return rc;
-        // the LOGICAL blocks (records, launch order): one wavefront per workgroup (launch order at wavefront granularity) -- except
-        // for the depth-parallel kernels on large launches, where 4x the workgroups cost more at dispatch than the finer order gains
-        // (C2: 32 768 workgroups of a 0.12 ms frame).  See map_pixel / map_pixel_dp.
-        const int dp = form.family == LaunchDesc::kDp ? form.lanes : 0, wpb = dp && P.n_tiles * dp * 64 > 16384 ? 4 : 1;
-        const dim3 block((unsigned)(64 * wpb));
-        const dim3 grid((unsigned)(dp ? P.n_tiles * dp * 64 / wpb : (P.n_tiles + 7) / 8 * 8 * (64 / wpb)));
+        const LaunchShape shape = launch_shape(form, F, E, off32, P.vol[0].lut != 0);
+        const dim3 grid(shape.blocks);  // the LOGICAL blocks of a frame (records, launch order)
         if (R.n_frames > 1 && grid.x % 8u != 0) return fail(c, VR_ERR_INVALID_ARG, "vr_render: launch shape cannot carry several frames");
-        const bool pw = form.family == LaunchDesc::kPw || form.family == LaunchDesc::kP2;
+        const bool pw = shape.pw, ordered = shape.ordered;
         // the ring slots: record buffer, then the launch order and the sort waits (a launch order is kept per launch shape -- not per
         // flavour: the kernels that march one packet per wavefront -- 6, 12, 13, 16, 17 -- share the logical blocks, so an order sorted
         // behind one of them serves the others, and the measured choice tries them in turn on a live scene)
@@ -663,10 +443,9 @@ int enqueue_render(vr_ctx* c, RenderRequest R)
         if (const int rc = reserve_block_counts(c, s, cb, (size_t)grid.x * (size_t)R.n_frames, &slot_sort)) return rc;
         P.block_counts = c->slot[cb].block_counts;
         c->last.cnt_buf = cb;
-        const unsigned long long okey = ((unsigned long long)grid.x << 32) ^ ((unsigned long long)block.x << 20) ^
+        const unsigned long long okey = ((unsigned long long)grid.x << 32) ^ ((unsigned long long)(64 * shape.wpb) << 20) ^
                                         ((unsigned long long)(R.variant | (R.surface ? 0x10 : 0) | (R.bounded ? 0x20 : 0)) << 16) ^ ((unsigned long long)R.world << 8) ^
                                         (unsigned long long)R.rank ^ (R.packed ? 1ull << 63 : 0ull);
-        const bool ordered = grid.x <= (unsigned)kOrderMaxBlocks && grid.x % 8u == 0;
         if (const int rc = wait_for_order(c, s, ordered, okey, slot_sort, &P.order)) return rc;
 
         const int ring = KernelRing::slot(c->last.ring_head);
@@ -682,28 +461,21 @@ int enqueue_render(vr_ctx* c, RenderRequest R)
         L.off32 = off32;
         L.lanes = form.lanes;
         L.pipe = form.pipe;
-        L.lds_bytes = P.vol[0].lut ? E.lut_lds : 0u;
-        L.grid = dim3(grid.x * (unsigned)R.n_frames);
-        L.block = block;
+        L.ltf = shape.ltf;
+        L.p2_win = shape.p2_win;
+        L.lds_bytes = shape.lds_bytes;
+        L.grid = dim3(shape.grid);
+        L.block = dim3(shape.block);
         L.vrange = vrange;
         L.skip = skip;
         L.surface = R.surface;
-        if (pw) {
-            // persistent wavefronts: `grid` stays the number of LOGICAL blocks (records, launch order); the launch itself is one
-            // workgroup of form.pw_threads per CU (fewer when there are fewer packets), TF slot 0 in LDS when it fits
-            const bool p2 = form.family == LaunchDesc::kP2;
-            const unsigned per_wg = form.pw_threads / 64u, wgs = (grid.x * (unsigned)R.n_frames + per_wg - 1u) / per_wg;
-            L.ltf = tf0_fits_lds(c);
-            L.p2_win = p2 && (!off32 || c->p2_window != 0);
-            L.lds_bytes = p2 ? E.p2_lds : (L.ltf ? (unsigned)(c->tf[0].dev.res_o + 2) * 16u : 0u);
+        if (pw) {  // persistent wavefronts: the workgroups take the logical blocks from the slot's queue
             L.queue = PwQueue{c->d_pw_heads + (size_t)cb * 8 * 64, grid.x, c->p2_window};
-            L.grid = dim3(wgs < (unsigned)c->n_cus ? wgs : (unsigned)c->n_cus);
-            L.block = dim3(form.pw_threads);
             if (c->slot[cb].pw_heads_dirty) VR_HIP(c, hipMemsetAsync(L.queue.heads, 0, 8 * 64 * sizeof(unsigned), s));
             c->slot[cb].pw_heads_dirty = true;  // (until the sort that clears them behind this launch has really been enqueued)
         }
-        if (c->arith == VR_ARITH_FUSED) vrf::launch_march(L, s, B);
-        else vr::launch_march(L, s, B);
+        if (!(c->arith == VR_ARITH_FUSED ? vrf::launch_march(L, s, B) : vr::launch_march(L, s, B)))  // (never: tests/test_choice.py)
+            return fail(c, VR_ERR_INTERNAL, "vr_render: no kernel for flavour " + std::to_string(fl) + " of variant " + std::to_string(R.variant));
         VR_HIP(c, hipGetLastError());
         mark_reads(c, P);
         if (time_with_events) VR_HIP(c, hipEventRecord(c->ring.k1[ring], s));
@@ -908,15 +680,14 @@ int vr_skip_field(vr_ctx* c, int variant, uint8_t* dist, size_t capacity, int di
     if (!c) return VR_ERR_INVALID_ARG;
     if (variant < 0 || variant >= VR_VARIANT_COUNT) return fail(c, VR_ERR_INVALID_ARG, "vr_skip_field: bad variant");
     if (capacity > 0 && !dist) return fail(c, VR_ERR_INVALID_ARG, "vr_skip_field: dist is NULL");
-    int nvol, ntf;
-    variant_needs(variant, &nvol, &ntf);
+    const int nvol = kShader[variant].nvol, ntf = kShader[variant].ntf;
     for (int i = 0; i < nvol; ++i)
         if (!c->vols[i].vol.data) return fail(c, VR_ERR_NOT_READY, "vr_skip_field: volume slot " + std::to_string(i) + " is empty");
     for (int i = 0; i < ntf; ++i)
         if (!c->tf[i].dev.opacity || !c->tf[i].dev.color) return fail(c, VR_ERR_NOT_READY, "vr_skip_field: TF slot " + std::to_string(i) + " is empty");
     if (const int rc = drain(c)) return rc;
     (void)hipGetLastError();
-    const Eligibility E = eligibility(c, 0, render_request(c, variant, 0, 1, false, nullptr, nullptr));
+    const Eligibility E = eligibility(choice_facts(c, render_request(c, variant, 0, 1, false, nullptr, nullptr), 0), 0);
     if (!E.can_skip) return fail(c, VR_ERR_NOT_READY, "vr_skip_field: launches of this variant do not skip empty space now");
     MarchParams P;
     std::memset(&P, 0, sizeof P);

@@ -4,15 +4,6 @@
 
 namespace {
 
-// finite and of moderate size: products of a colour, a light term and a shading factor stay finite, so "x * 0 == 0"
-// holds for everything a provably-zero opacity is multiplied with
-bool all_finite(const float* v, int n)
-{
-    for (int i = 0; i < n; ++i)
-        if (!(v[i] - v[i] == 0.0f) || !(v[i] <= 1.0e15f && v[i] >= -1.0e15f)) return false;
-    return true;
-}
-
 // Before `s` rewrites generation b: every launch that read it must have finished, whatever its stream (launches on different
 // streams finish in any order).  A reader fewer than kInFlight launches old still owns its record slot's event: s waits for it on
 // the device, one wait per such slot.  An older one was waited for on the host by the claim_slot that reused its slot.

@@ -397,7 +397,7 @@ int vr_shadow_volume(vr_ctx* c, float* out, size_t capacity, int dims[3])
     MarchParams P;
     fill_launch_params(c, P, c->u, 0, 1, false);
     const int requested = c->flavour == 0 ? c->default_flavour : c->flavour;
-    const Eligibility E = eligibility(c, requested, render_request(c, VR_VARIANT_LIGHT, 0, 1, false, nullptr, nullptr));
+    const Eligibility E = eligibility(choice_facts(c, render_request(c, VR_VARIANT_LIGHT, 0, 1, false, nullptr, nullptr), requested), requested);
     if (E.can_skip)
         if (const int rc = prepare_skip(c, VR_VARIANT_LIGHT, c->stream, P)) return rc;
     if (c->layout_mode == 0) use_bricked_copies(c, P);

@@ -4,29 +4,9 @@
 
 namespace {
 
-// the bricked copy of a volume (DevVolume::bricked): storage bricks per axis, and their slots (voxels)
-struct BrickedGrid {
-    unsigned nbx, nby, nbz;
-    size_t slots;
-};
-BrickedGrid bricked_grid(const DevVolume& v)
-{
-    const unsigned nbx = ((unsigned)v.nx + kVbM) >> kVbS, nby = ((unsigned)v.ny + kVbM) >> kVbS, nbz = ((unsigned)v.nz + kVbM) >> kVbS;
-    return {nbx, nby, nbz, (size_t)nbx * nby * nbz * kVbN};
-}
-
-// empty-space bricks along an axis of n base cells
-int skip_bricks(int n) { return (n + kBrickCells - 1) >> kBrickShift; }
-
-// Can the skipping kernels index a grid of bnx x bny x bnz bricks?  brick_of (vr_kernels.h) and slice_record (vr_slice.h) compute
-// mul24(mul24(bz, bny) + by, bnx) + bx with SIGNED 24-bit multiplies, whose operands are sign-extended from bit 23: bz and bny are
-// bricks of a 16-bit axis, bz * bny + by < bny * bnz and bnx must stay below 2^23; brick_record addresses with the 32-bit byte
-// offset bid << 3.  A launch on a grid that fails this runs its form without skipping.
-bool bricks_indexable(int bnx, int bny, int bnz)
-{
-    return (long long)bny * bnz <= (1 << 23) && bnx < (1 << 23) && (long long)bnx * bny * bnz <= (1ll << 29);
-}
-bool volume_bricks_indexable(const DevVolume& v) { return bricks_indexable(skip_bricks(v.nx), skip_bricks(v.ny), skip_bricks(v.nz)); }
+// the grid helpers of vr_choice.h on a volume
+BrickedGrid bricked_grid(const DevVolume& v) { return vr::bricked_grid(v.nx, v.ny, v.nz); }
+bool volume_bricks_indexable(const DevVolume& v) { return vr::volume_bricks_indexable(v.nx, v.ny, v.nz); }
 
 // The parameters of a launch that no kernel form changes; the volumes as the vec4 voxels and their density plane (the bricked copies
 // replace them in use_bricked_copies).

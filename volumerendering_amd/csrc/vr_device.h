@@ -3,11 +3,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "vr_choice.h"  // kTile, the brick shifts, kOrderMaxBlocks; KernelForm::Family
 #include "vr_units.h"
 
 namespace vr {
 
-constexpr int kTile = 64;        // multi-GPU ownership granule (pixels)
 constexpr int kBlockEdge = 16;   // one 256-thread workgroup = 16x16 pixels = four 8x8 wave packets
 constexpr int kBlockRecord = 6;  // u64 words per block in MarchParams::block_counts
 constexpr int kBlocksPerTile = (kTile / kBlockEdge) * (kTile / kBlockEdge);
@@ -16,11 +16,7 @@ constexpr int kBlocksPerTile = (kTile / kBlockEdge) * (kTile / kBlockEdge);
 // 512^3, 16 MB for 1024^3: one byte per brick) and are faster on every configuration (C3 0.573 -> 0.562 ms one frame at a
 // time, 0.435 -> 0.423 batched; C2 0.119 -> 0.103 / 0.072 -> 0.065; C5 3.31 -> 3.28); 2-cell bricks fetch less still and
 // are slower again (the look-ups), and their index outgrows a launch at 1024^3.  -DVR_BRICK_SHIFT=3 rebuilds round 1's.
-#ifndef VR_BRICK_SHIFT
-#define VR_BRICK_SHIFT 2
-#endif
-constexpr int kBrickShift = VR_BRICK_SHIFT;
-constexpr int kBrickCells = 1 << kBrickShift;
+// (kBrickShift, kBrickCells: vr_choice.h)
 constexpr float kBrickInv = 1.0f / (float)kBrickCells;    // exact
 constexpr float kBrickHalf = 0.5f / (float)kBrickCells;   // half a cell in brick units (the -0.5 of the cell coordinate)
 #ifndef VR_DIST_MAX
@@ -37,14 +33,7 @@ struct SkipSummary {
     unsigned long long count;
     int box[6];
 };
-// Storage bricks of the bricked volume copy (DevVolume::bricked): 2^S voxels per axis, S = 2 (4 x 4 x 4 = 1 KiB of vec4 voxels)
-// by default; -DVR_VOX_BRICK_SHIFT=1 / 3 rebuilds with 2^3- / 8^3-voxel bricks for A/B (tools/run_r3l.sh).
-#ifndef VR_VOX_BRICK_SHIFT
-#define VR_VOX_BRICK_SHIFT 2
-#endif
-constexpr unsigned kVbS = VR_VOX_BRICK_SHIFT;          // log2 of the brick edge
-constexpr unsigned kVbM = (1u << kVbS) - 1u;           // mask of the in-brick coordinate
-constexpr unsigned kVbN = 1u << (3u * kVbS);           // voxels per brick
+// (the storage bricks of the bricked volume copy, kVbS / kVbM / kVbN: vr_choice.h)
 
 struct DevVolume {
     const float4* data;  // reference layout: x fastest, (k*ny + j)*nx + i   (VolumeFile.cpp:306)
@@ -226,19 +215,14 @@ struct PwQueue {
 // What enqueue_render decided about one march launch; handed to launch_march of the arithmetic mode's translation unit
 // (vr_launch.h: namespace vr = separately rounded multiply-adds, namespace vrf = fused).  Host only.
 struct LaunchDesc {
-    enum Family { kPlain, kDp, kPw, kP2, kLt, kProj, kIso, kShadow, kSurf, kBound };
     int variant;      // vr_variant
-    Family family;    // march_kernel, march_dp_kernel, march_pw_kernel (persistent wavefronts: grid = workgroups, the packets come
-                      // from `queue`), march_p2_kernel (the same, corner loads two steps ahead), march_lt_kernel (LDS tiles, lit shader),
-                      // the one-lane marches on vr_ray.h's prologue and shell:
-                      // march_proj_kernel (vr_proj.h: the intensity projections), march_iso_kernel (vr_iso.h: the isosurface),
-                      // march_shadow_kernel (vr_shadow.h: the lit shader with shadows; MarchParams::vol[1] = the light volume),
-                      // march_surf_kernel (vr_surf.h: the surface-position output of the unlit / lit shader; MarchParams::iso = the threshold),
-                      // march_bound_kernel (vr_bound.h: the unlit / lit shader between per-pixel ray bounds; MarchParams::vol[1].data /
-                      // vol[2].data = the near / far depth buffers, W*H floats each or nullptr)
+    KernelForm::Family family;  // which kernel (vr_choice.h: KernelForm::Family; kShader says which shaders have it).  What a family reads
+                      // beyond the batch: kPw / kP2 the packets from `queue` (grid = workgroups); kShadow MarchParams::vol[1] = the light
+                      // volume; kSurf MarchParams::iso = the threshold; kBound MarchParams::vol[1].data / vol[2].data = the near / far
+                      // depth buffers, W*H floats each or nullptr
     bool off32;       // every bound volume < 4 GiB: 32-bit byte offsets
-    int lanes;        // kDp: lanes per ray (2 / 4)
-    bool pipe;        // kDp / kPw: the next round's / step's corner loads software-pipelined
+    int lanes;        // KernelForm::lanes
+    bool pipe;        // KernelForm::pipe (dropped at the launch where the shader has no pipelined form: ShaderTraits::kDpPipe / kPwPipe)
     bool ltf;         // kPw: TF slot 0 in LDS (lds_bytes of dynamic LDS)
     bool p2_win;      // kP2: a bound volume of 4 GiB or more: the gather window moves (march_p2_kernel<.., WIN>)
     unsigned lds_bytes;

@@ -35,8 +35,10 @@
 namespace VR_KNS {
 using namespace vr;
 
-enum Variant : int { V_BASIC = 0, V_LIGHT = 1, V_VOLUME_MASK = 2, V_THREE_FILES = 3, V_MULTI_CTRT = 4, V_TF_CALIB = 5,
-                     V_ILLUSTRATIVE = 6, V_LIGHT_INSHADER = 7 };
+// march_kernel's shaders, by their vr_variant: a V indexes kShader (vr_choice.h)
+enum Variant : int { V_BASIC = VR_VARIANT_BASIC, V_LIGHT = VR_VARIANT_LIGHT, V_VOLUME_MASK = VR_VARIANT_VOLUME_MASK, V_THREE_FILES = VR_VARIANT_THREE_FILES,
+                     V_MULTI_CTRT = VR_VARIANT_MULTI_CTRT, V_TF_CALIB = VR_VARIANT_TF_CALIB, V_ILLUSTRATIVE = VR_VARIANT_ILLUSTRATIVE,
+                     V_LIGHT_INSHADER = VR_VARIANT_LIGHT_INSHADER };
 
 struct f3 {
     float x, y, z;
@@ -1699,7 +1701,6 @@ __global__ __launch_bounds__(64) void spin_kernel(unsigned long long ticks, unsi
 // modulo 8: position b of the order holds a block lb with lb % 8 == b % 8.  Workgroups are dispatched round-robin over the
 // 8 XCDs, so a block stays on the XCD its index maps to (what map_pixel relies on) and every XCD runs its own
 // blocks longest-processing-time-first.  Eight counting sorts over 128 key buckets each (n_blocks % 8 == 0).
-constexpr int kOrderMaxBlocks = 192 * 1024;  // launches with more blocks keep the index order (C5, one wavefront per block: 130 560)
 // It also reports how long the launch took: last workgroup end - first workgroup start of the records it reads (100 MHz
 // ticks, to host-visible memory; vr_kernel_times).  Timing events around every launch cost the frame's stream 11 us.
 // pw_heads: the queue heads of the persistent-wavefront launch whose records these are (vr_pw.h) -- cleared here, behind that

@@ -34,13 +34,13 @@
 #include "vr_slice.h"
 
 #include <type_traits>
+#include <utility>
 
 namespace VR_KNS {
 
-// the shaders with exact empty-space skipping (brick records), with a pipelined loop, with a two-steps-ahead kernel
-template <int V> constexpr bool kCanSkip = V == V_BASIC || V == V_LIGHT || V == V_THREE_FILES || V == V_VOLUME_MASK || V == V_LIGHT_INSHADER;
-template <int V> constexpr bool kCanPipe = V == V_BASIC || V == V_LIGHT;
-template <int V> constexpr bool kCanP2 = kCanPipe<V> || V == V_VOLUME_MASK;
+// which forms shader V has: kShader (vr_choice.h), the table the host's kernel choice reads -- there is no second list here
+template <int V> constexpr bool has(unsigned forms) { return kShader[V].has(forms); }
+template <int V> constexpr bool kCanSkip = has<V>(ShaderTraits::kSkip);
 
 // f(std::bool_constant<b>{}...): run-time flags as template arguments.  f is instantiated for every combination; it skips the ones
 // that have no kernel with `if constexpr`.
@@ -68,59 +68,95 @@ void launch_queued(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
     hipLaunchKernelGGL(K, L.grid, L.block, L.lds_bytes, s, B, L.queue);
 }
 
+// The launch helpers return whether a kernel was enqueued: false for a combination that kShader says does not exist.
+
 // march_kernel; launches that carry several frames (MarchBatch) exist for both loop forms: plain (0) and, skipping, runs (3)
 template <int V>
-void launch_plain(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
+bool launch_plain(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
 {
+    bool launched = false;
     with_flags([&](auto O, auto S, auto BT) {
-        if constexpr (!S || kCanSkip<V>)
+        if constexpr (has<V>(ShaderTraits::kMarch) && (!S || kCanSkip<V>)) {
             hipLaunchKernelGGL((march_kernel<V, O, S, (S ? 3 : 0), BT>), L.grid, L.block, L.lds_bytes, s, B);
+            launched = true;
+        }
     }, L.off32, kCanSkip<V> && B.frame[0].brick_dist, B.n_frames > 1);
+    return launched;
 }
 
-// march_dp_kernel, 4 or 2 lanes per ray (the pipelined form exists for the lit shader)
+// march_dp_kernel, 4 or 2 lanes per ray; without the pipelined form (ShaderTraits::kDpPipe) L.pipe is dropped
 template <int V>
-void launch_dp(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
+bool launch_dp(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
 {
+    bool launched = false;
     with_flags([&](auto O, auto S, auto K4, auto PIPE, auto BT) {
-        if constexpr ((!S || kCanSkip<V>) && (!PIPE || V == V_LIGHT))
+        if constexpr (has<V>(ShaderTraits::kDp) && (!S || kCanSkip<V>) && (!PIPE || has<V>(ShaderTraits::kDpPipe))) {
             hipLaunchKernelGGL((march_dp_kernel<V, O, S, (K4 ? 4 : 2), PIPE, BT>), L.grid, L.block, 0, s, B);
-    }, L.off32, kCanSkip<V> && B.frame[0].brick_dist, L.lanes == 4, V == V_LIGHT && L.pipe, B.n_frames > 1);
+            launched = true;
+        }
+    }, L.off32, kCanSkip<V> && B.frame[0].brick_dist, L.lanes == 4, has<V>(ShaderTraits::kDpPipe) && L.pipe, B.n_frames > 1);
+    return launched;
 }
 
-// persistent wavefronts (vr_pw.h); the loop form is march_kernel's default (runs through inert bricks when skipping)
+// persistent wavefronts (vr_pw.h); the loop form is march_kernel's default (runs through inert bricks when skipping); without the
+// pipelined form (ShaderTraits::kPwPipe) L.pipe is dropped
 template <int V>
-void launch_pw(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
+bool launch_pw(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
 {
+    bool launched = false;
     with_flags([&](auto O, auto S, auto T, auto PP) {
-        if constexpr ((!S || kCanSkip<V>) && (!PP || kCanPipe<V>)) launch_queued<march_pw_kernel<V, O, S, T, PP>>(L, s, B);
-    }, L.off32, kCanSkip<V> && B.frame[0].brick_dist, L.ltf, kCanPipe<V> && L.pipe);
+        if constexpr (has<V>(ShaderTraits::kPw) && (!S || kCanSkip<V>) && (!PP || has<V>(ShaderTraits::kPwPipe))) {
+            launch_queued<march_pw_kernel<V, O, S, T, PP>>(L, s, B);
+            launched = true;
+        }
+    }, L.off32, kCanSkip<V> && B.frame[0].brick_dist, L.ltf, has<V>(ShaderTraits::kPwPipe) && L.pipe);
+    return launched;
 }
 
-// two steps ahead (vr_p2.h; the host: TF slot 0 and the axis tables fit LDS, the bricked copy is in use).  The composite's form is the
-// skipping one (the host asks for it only with the brick records in place).
+// two steps ahead (vr_p2.h; the host: TF slot 0 and the axis tables fit LDS, the bricked copy is in use).  A shader without the form
+// that does not skip (ShaderTraits::kP2Plain: the composite) runs the skipping one: the host asks for it only with the brick records
+// in place.
 template <int V>
-void launch_p2(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
+bool launch_p2(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
 {
+    bool launched = false;
     with_flags([&](auto S, auto WN, auto BT) {
-        if constexpr (S || V != V_VOLUME_MASK) launch_queued<march_p2_kernel<V, S, WN, BT>>(L, s, B);
-    }, V == V_VOLUME_MASK || (B.frame[0].brick_dist && L.skip), L.p2_win, B.n_frames > 1);
+        if constexpr (has<V>(S ? ShaderTraits::kP2 : ShaderTraits::kP2Plain)) {
+            launch_queued<march_p2_kernel<V, S, WN, BT>>(L, s, B);
+            launched = true;
+        }
+    }, !has<V>(ShaderTraits::kP2Plain) || (B.frame[0].brick_dist && L.skip), L.p2_win, B.n_frames > 1);
+    return launched;
+}
+
+// LDS tiles (vr_lt.h): the lit shader's kernel
+template <int V>
+bool launch_lt(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
+{
+    if constexpr (has<V>(ShaderTraits::kLt)) {
+        static_assert(V == V_LIGHT, "march_lt_kernel is the lit shader");
+        with_flags([&](auto O, auto S) { hipLaunchKernelGGL((march_lt_kernel<O, S>), L.grid, L.block, 0, s, B); }, L.off32,
+                   B.frame[0].brick_dist != nullptr);
+        return true;
+    }
+    return false;
 }
 
 // The one-lane kernels of vr_proj.h, vr_iso.h, vr_shadow.h, vr_surf.h and vr_bound.h: skipping x addressing x frames per launch.
 // kernel(S, O, BT) returns the instantiation; args follow the batch.
 template <class K, class... A>
-void launch_one_lane(const LaunchDesc& L, hipStream_t s, const MarchBatch& B, K kernel, A... args)
+bool launch_one_lane(const LaunchDesc& L, hipStream_t s, const MarchBatch& B, K kernel, A... args)
 {
     with_flags([&](auto S, auto O, auto BT) { hipLaunchKernelGGL(kernel(S, O, BT), L.grid, L.block, 0, s, B, args...); }, L.skip, L.off32,
                B.n_frames > 1);
+    return true;
 }
 
 // the projections: one mode each
 template <int M>
-void launch_proj(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
+bool launch_proj(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
 {
-    launch_one_lane(L, s, B, [](auto S, auto O, auto BT) { return march_proj_kernel<M, O, S, BT>; }, L.vrange);
+    return launch_one_lane(L, s, B, [](auto S, auto O, auto BT) { return march_proj_kernel<M, O, S, BT>; }, L.vrange);
 }
 
 // the light volume of a shadowed launch (P: its parameters, vol[1] = the grid, whose storage is `out`); skip: by LIGHT's distance field
@@ -144,52 +180,45 @@ void launch_slice(const SliceParams& S, int reduce, bool nearest, bool off32, bo
     else launch(std::integral_constant<int, kProjAvg>{});
 }
 
-void launch_march(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
+// the families that exist per shader, for shader V
+template <int V>
+bool launch_variant(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
 {
     switch (L.family) {
-    case LaunchDesc::kShadow: launch_one_lane(L, s, B, [](auto S, auto O, auto BT) { return march_shadow_kernel<O, S, BT>; }); return;
-    case LaunchDesc::kSurf: launch_one_lane(L, s, B, [](auto S, auto O, auto BT) { return march_surf_kernel<O, S, BT>; }); return;
-    case LaunchDesc::kBound:  // (launches of one frame: BT is not an argument)
-        if (L.variant == VR_VARIANT_LIGHT) launch_one_lane(L, s, B, [](auto S, auto O, auto) { return march_bound_kernel<V_LIGHT, O, S>; });
-        else launch_one_lane(L, s, B, [](auto S, auto O, auto) { return march_bound_kernel<V_BASIC, O, S>; });
-        return;
-    case LaunchDesc::kIso:  // (surface output: the refined points)
-        if (L.surface) launch_one_lane(L, s, B, [](auto S, auto O, auto BT) { return iso_point_kernel<O, S, BT>; });
-        else launch_one_lane(L, s, B, [](auto S, auto O, auto BT) { return march_iso_kernel<O, S, BT>; });
-        return;
-    case LaunchDesc::kProj:
-        if (L.variant == VR_VARIANT_MIP) launch_proj<kProjMax>(L, s, B);
-        else if (L.variant == VR_VARIANT_MINIP) launch_proj<kProjMin>(L, s, B);
-        else launch_proj<kProjAvg>(L, s, B);
-        return;
-    case LaunchDesc::kLt:  // LDS tiles (vr_lt.h): lit shader
-        with_flags([&](auto O, auto S) { hipLaunchKernelGGL((march_lt_kernel<O, S>), L.grid, L.block, 0, s, B); },
-                   L.off32, B.frame[0].brick_dist != nullptr);
-        return;
-    default: break;  // the families that exist per shader variant
+    case KernelForm::kDp: return launch_dp<V>(L, s, B);
+    case KernelForm::kPw: return launch_pw<V>(L, s, B);
+    case KernelForm::kP2: return launch_p2<V>(L, s, B);
+    case KernelForm::kLt: return launch_lt<V>(L, s, B);
+    case KernelForm::kBound:  // (launches of one frame: BT is not an argument)
+        if constexpr (kShader[V].bounds)
+            return launch_one_lane(L, s, B, [](auto S, auto O, auto) { return march_bound_kernel<V, O, S>; });
+        return false;
+    default: return launch_plain<V>(L, s, B);
     }
-    auto launch = [&](auto v) {
-        constexpr int V = decltype(v)::value;
-        switch (L.family) {
-        case LaunchDesc::kDp:  // (no depth-parallel form of the illustrative and in-shader gradient shaders: enqueue_render never asks for one)
-            if constexpr (V != V_ILLUSTRATIVE && V != V_LIGHT_INSHADER) launch_dp<V>(L, s, B);
-            break;
-        case LaunchDesc::kPw: launch_pw<V>(L, s, B); break;
-        case LaunchDesc::kP2:
-            if constexpr (kCanP2<V>) launch_p2<V>(L, s, B);
-            break;
-        default: launch_plain<V>(L, s, B); break;
-        }
-    };
-    switch (L.variant) {
-    case VR_VARIANT_BASIC: launch(std::integral_constant<int, V_BASIC>{}); break;
-    case VR_VARIANT_LIGHT: launch(std::integral_constant<int, V_LIGHT>{}); break;
-    case VR_VARIANT_VOLUME_MASK: launch(std::integral_constant<int, V_VOLUME_MASK>{}); break;
-    case VR_VARIANT_THREE_FILES: launch(std::integral_constant<int, V_THREE_FILES>{}); break;
-    case VR_VARIANT_MULTI_CTRT: launch(std::integral_constant<int, V_MULTI_CTRT>{}); break;
-    case VR_VARIANT_ILLUSTRATIVE: launch(std::integral_constant<int, V_ILLUSTRATIVE>{}); break;
-    case VR_VARIANT_LIGHT_INSHADER: launch(std::integral_constant<int, V_LIGHT_INSHADER>{}); break;
-    default: launch(std::integral_constant<int, V_TF_CALIB>{}); break;
+}
+template <int... V>
+bool launch_variant_of(std::integer_sequence<int, V...>, const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
+{
+    bool launched = false;
+    (void)((L.variant == V && ((launched = launch_variant<V>(L, s, B)), true)) || ...);
+    return launched;
+}
+
+// Enqueues the kernel of L; false: there is none for this family of this shader, nothing was launched (enqueue_render fails the call).
+bool launch_march(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
+{
+    switch (L.family) {
+    case KernelForm::kShadow: return launch_one_lane(L, s, B, [](auto S, auto O, auto BT) { return march_shadow_kernel<O, S, BT>; });
+    case KernelForm::kSurf: return launch_one_lane(L, s, B, [](auto S, auto O, auto BT) { return march_surf_kernel<O, S, BT>; });
+    case KernelForm::kIso:  // (surface output: the refined points)
+        if (L.surface) return launch_one_lane(L, s, B, [](auto S, auto O, auto BT) { return iso_point_kernel<O, S, BT>; });
+        return launch_one_lane(L, s, B, [](auto S, auto O, auto BT) { return march_iso_kernel<O, S, BT>; });
+    case KernelForm::kProj:
+        if (L.variant == VR_VARIANT_MIP) return launch_proj<kProjMax>(L, s, B);
+        if (L.variant == VR_VARIANT_MINIP) return launch_proj<kProjMin>(L, s, B);
+        return launch_proj<kProjAvg>(L, s, B);
+    default:  // the families that exist per shader variant: by the variant's value
+        return launch_variant_of(std::make_integer_sequence<int, VR_VARIANT_COUNT>{}, L, s, B);
     }
 }
 
