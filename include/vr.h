@@ -1184,6 +1184,13 @@ int vr_last_kernel_flavour(vr_ctx* ctx);
  * Returns n, or a negative vr_status (VR_ERR_NOT_READY when such a launch would not skip empty space).             */
 int vr_skip_field(vr_ctx* ctx, int variant, uint8_t* dist, size_t capacity, int dims[3], int box[6], uint64_t* active);
 
+/* The hull of the active bricks of that field, which the skipping launches prune their rays with: lo[i] / hi[i] = the
+ * smallest / largest n_i . b over the active bricks b (brick coordinates), for the 13 directions n_i, in this order:
+ *   (1,0,0) (0,1,0) (0,0,1)  (1,1,0) (1,-1,0) (1,0,1) (1,0,-1) (0,1,1) (0,1,-1)  (1,1,1) (1,1,-1) (1,-1,1) (1,-1,-1)
+ * The first three pairs are vr_skip_field's box.  No active brick: lo[i] = INT_MAX, hi[i] = INT_MIN for every i.  Built
+ * synchronously like vr_skip_field, with its conditions and errors; drains the device.  Returns VR_OK or a negative vr_status. */
+int vr_skip_hull(vr_ctx* ctx, int variant, int lo[13], int hi[13]);
+
 /* 1 when the skipping kernels can index the bricks of an nx x ny x nz volume (THE BRICK-INDEX LIMIT at vr_set_kernel_flavour),
  * 0 when launches on such a volume run without skipping.  Needs no context and no device.                              */
 int vr_skip_indexable(uint16_t nx, uint16_t ny, uint16_t nz);

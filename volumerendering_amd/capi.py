@@ -59,7 +59,7 @@ ABI_SYMBOLS = [
     "vr_set_volume_layout", "vr_volume_layout", "vr_viewport", "vr_set_arithmetic", "vr_present_async", "vr_stream", "vr_hint_frames_in_flight",
     "vr_set_kernel_timing", "vr_present_tiles_async", "vr_kernel_choice",
     "vr_present_packed_async", "vr_unpack_tiles_bgra8_async",
-    "vr_tf_upload_opacity_async", "vr_tf_upload_color_async", "vr_skip_field", "vr_skip_indexable", "vr_unbounded_box_launches",
+    "vr_tf_upload_opacity_async", "vr_tf_upload_color_async", "vr_skip_field", "vr_skip_hull", "vr_skip_indexable", "vr_unbounded_box_launches",
     "vr_set_iso_value", "vr_set_shadows", "vr_shadow_volume",
     "vr_set_output", "vr_set_surface_threshold", "vr_surface_depth_async", "vr_pick",
     "vr_set_ray_bounds",
@@ -357,6 +357,7 @@ def load() -> C.CDLL:
     lib.vr_tf_upload_opacity_async.argtypes = [vp, i32, vp, u32, vp]
     lib.vr_tf_upload_color_async.argtypes = [vp, i32, vp, u32, vp]
     lib.vr_skip_field.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_int * 3), C.POINTER(C.c_int * 6), C.POINTER(C.c_uint64)]
+    lib.vr_skip_hull.argtypes = [vp, i32, C.POINTER(C.c_int * 13), C.POINTER(C.c_int * 13)]
     lib.vr_skip_indexable.argtypes = [u16, u16, u16]
     lib.vr_unbounded_box_launches.argtypes = [vp]
     lib.vr_unbounded_box_launches.restype = C.c_int64
@@ -536,6 +537,13 @@ class Context:
         out = np.zeros(n, dtype=np.uint8)
         self._chk(self.lib.vr_skip_field(self.h, variant, out.ctypes.data, n, C.byref(dims), C.byref(box), C.byref(active)))
         return out.reshape(dims[2], dims[1], dims[0]), tuple(int(x) for x in box), int(active.value)
+
+    def skip_hull(self, variant: int):
+        """(lo[13], hi[13]): the smallest / largest n . b over the active bricks of that field along the hull's 13 directions
+        (vr_skip_hull: built synchronously; INT_MAX / INT_MIN when no brick is active)."""
+        lo, hi = (C.c_int * 13)(), (C.c_int * 13)()
+        self._chk(self.lib.vr_skip_hull(self.h, variant, C.byref(lo), C.byref(hi)))
+        return tuple(int(x) for x in lo), tuple(int(x) for x in hi)
 
     @staticmethod
     def skip_indexable(nx: int, ny: int, nz: int) -> bool:

@@ -707,6 +707,19 @@ int vr_skip_field(vr_ctx* c, int variant, uint8_t* dist, size_t capacity, int di
     return (int)n;
 }
 
+int vr_skip_hull(vr_ctx* c, int variant, int lo[13], int hi[13])
+{
+    // (the field is built and its summary adopted as vr_skip_field does it; its errors carry that name)
+    const int n = vr_skip_field(c, variant, nullptr, 0, nullptr, nullptr, nullptr);
+    if (n < 0) return n;
+    static_assert(kHullDirs == 13, "include/vr.h documents 13 directions");
+    for (int d = 0; d < kHullDirs; ++d) {
+        if (lo) lo[d] = c->skip.hull_lo[d];
+        if (hi) hi[d] = c->skip.hull_hi[d];
+    }
+    return VR_OK;
+}
+
 int vr_skip_indexable(uint16_t nx, uint16_t ny, uint16_t nz)
 {
     return bricks_indexable(skip_bricks(nx), skip_bricks(ny), skip_bricks(nz)) ? 1 : 0;

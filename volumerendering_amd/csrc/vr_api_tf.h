@@ -86,7 +86,15 @@ int prepare_skip(vr_ctx* c, int variant, hipStream_t s, MarchParams& P)
     }
     F.adopt(bs);
     P.brick_dist = F.brick_dist;
-    for (int a = 0; a < 6; ++a) P.abox[a] = F.launch_box()[a];
+    const HullPlanes hull = F.launch_box();
+    for (int a = 0; a < kHullAxes; ++a) {
+        P.abox[a] = hull.lo[a];
+        P.abox[3 + a] = hull.hi[a];
+    }
+    for (int d = 0; d < kHullDiag; ++d) {
+        P.hull_lo[d] = hull.lo[kHullAxes + d];
+        P.hull_hi[d] = hull.hi[kHullAxes + d];
+    }
     return VR_OK;
 }
 

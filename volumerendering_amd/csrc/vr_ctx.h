@@ -199,7 +199,10 @@ struct SkipField {
     unsigned long long active = 0;
     long long unbounded_launches = 0;
     double active_fraction = 1.0;  // share of bricks that are not inert
-    float abox[6] = {-3.0e38f, -3.0e38f, -3.0e38f, 3.0e38f, 3.0e38f, 3.0e38f};  // uvw box around the active bricks (MarchParams::abox)
+    // min / max of n . b over the active bricks along the hull's 13 directions (vr_skip_hull; the first three are the box; INT_MAX /
+    // INT_MIN when there is none), and the plane pairs the launches get for them (MarchParams::hull)
+    int hull_lo[kHullDirs], hull_hi[kHullDirs];
+    HullPlanes hull = hull_unbounded();
     // generation b holds a field of bn_ bricks freshly built for k: it is the one in use, its count and box on their way
     void publish(int b, const FieldKey& k, const int bn_[3])
     {
@@ -223,25 +226,23 @@ struct SkipField {
         active = h.count;
         active_fraction = nb > 0 ? (double)h.count / (double)nb : 1.0;
         for (int a = 0; a < 6; ++a) box[a] = h.box[a];
-        for (int a = 0; a < 3; ++a) {
-            if (box[3 + a] < 0) {
-                // (no active brick: an inverted box.  steps_near_box reports a miss for it only where a step component is zero; every
-                // other ray counts all its steps as near and skips by the field, which says inert everywhere)
-                abox[a] = 3.0e38f;
-                abox[3 + a] = -3.0e38f;
-            } else {
-                abox[a] = (float)(((double)box[a] - 1.0 + (double)kBrickHalf) / (double)bs[a]);
-                abox[3 + a] = (float)(((double)box[3 + a] + 2.0 + (double)kBrickHalf) / (double)bs[a]);
+        if (h.count == 0) {  // (no active brick: every pair inverted, hull_inverted)
+            for (int d = 0; d < kHullDirs; ++d) {
+                hull_lo[d] = 0x7fffffff;
+                hull_hi[d] = -0x7fffffff - 1;
             }
+            hull = hull_inverted();
+        } else {
+            for (int d = 0; d < kHullDirs; ++d) {
+                hull_lo[d] = d < kHullAxes ? box[d] : h.hull_lo[d - kHullAxes];
+                hull_hi[d] = d < kHullAxes ? box[3 + d] : h.hull_hi[d - kHullAxes];
+            }
+            hull = hull_bounds(hull_lo, hull_hi, bs, kBrickHalf);
         }
         pending = false;
     }
-    // the box a launch gets: unbounded (the kernels only prune with it) while the count and box of a rebuild are on their way
-    const float* launch_box() const
-    {
-        static const float unbounded[6] = {-3.0e38f, -3.0e38f, -3.0e38f, 3.0e38f, 3.0e38f, 3.0e38f};
-        return pending ? unbounded : abox;
-    }
+    // the hull a launch gets: unbounded (the kernels only prune with it) while the count and planes of a rebuild are on their way
+    HullPlanes launch_box() const { return pending ? hull_unbounded() : hull; }
 };
 
 // The kernel-time ring (vr_kernel_times): launch number `head` (LastLaunch::ring_head) records itself in slot(head) -- with the events

@@ -5,6 +5,12 @@
 #include <stdint.h>
 #include "vr_choice.h"  // kTile, the brick shifts, kOrderMaxBlocks; KernelForm::Family
 #include "vr_units.h"
+// (the hull of the active bricks: plain C++ that the kernels and the host share; the device's reciprocal is v_rcp_f32)
+#define VR_HULL_FN __host__ __device__ __forceinline__
+#ifdef __HIP_DEVICE_COMPILE__
+#define VR_HULL_RCP(x) __builtin_amdgcn_rcpf(x)
+#endif
+#include "vr_hull.h"
 
 namespace vr {
 
@@ -28,10 +34,13 @@ static_assert(kDistMax >= 2 && kDistMax <= 128, "the distance-field builder (vr_
 
 // What a distance-field build reports to the host (pinned memory, written by its last workgroup): the active bricks and their box
 // (brick coordinates, inclusive; hi < 0 if none).  `gen` is written last: the values belong to build `gen` once it reads so.
+// hull_lo / hull_hi: min / max of n . b over the active bricks b for the ten diagonal directions of vr_hull.h (kHullDir[3 ..]); not
+// written when there is none.
 struct SkipSummary {
     unsigned long long gen;
     unsigned long long count;
     int box[6];
+    int hull_lo[kHullDirs - kHullAxes], hull_hi[kHullDirs - kHullAxes];
 };
 // (the storage bricks of the bricked volume copy, kVbS / kVbM / kVbN: vr_choice.h)
 
@@ -102,6 +111,7 @@ struct MarchParams {
                                       // distance k-1 is inert too (capped); rebuilt when the volume / opacity table change
     int skip_vol;            // which volume carries the density that drives the opacity (0, or 2 for VOLUME_MASK)
     float abox[6];           // uvw box (lo xyz, hi xyz) around the ACTIVE bricks of brick_dist, one brick of margin: outside it nothing is sampled
+                             // (the three axes of their hull, vr_hull.h; the ten diagonals: hull_lo / hull_hi at the end)
     int bnx, bny, bnz;       // bricks per axis
     float bsx, bsy, bsz;     // n / kBrickCells per axis of vol[skip_vol] (exact in f32)
     int tf_zero_prefix;      // largest Z with opacity[0..Z] == 0 exactly (-1: none); also the per-step vote of sample_and_blend
@@ -115,6 +125,9 @@ struct MarchParams {
     float iso;               // VR_VARIANT_ISO: the level (vr_set_iso_value) when the launch was enqueued (in the tail padding after
                              // batch_n: the size and every other offset of the struct are what they were without it).  Surface
                              // launches of the unlit / lit shader (vr_surf.h), which read no level: the alpha threshold
+    // The ten diagonal plane pairs of the active bricks' hull (vr_hull.h: lo <= g . p <= hi in brick units, margin included), which the
+    // skipping marches prune their rays with beside abox.  At the end: every other offset of a frame is what it was without them.
+    float hull_lo[kHullDiag], hull_hi[kHullDiag];
 };
 
 // One launch may carry up to kBatchMax frames of the same scene and shape (different uniforms, output and record buffers).
@@ -124,12 +137,13 @@ struct MarchParams {
 // g / n_frames -- so a workgroup keeps the XCD residue of its index within the frame, and the longest-first launch order
 // (MarchParams::order) holds across the whole launch: the long workgroups of EVERY frame start first.  (Frame after frame,
 // the last frame's long ray chains would start when the others' blocks have all been dispatched.)  Passed by value:
-// 4 x ~0.6 KB of the 4 KB kernarg segment.
+// 4 x ~0.7 KB of the 4 KB kernarg segment.
 constexpr int kBatchMax = 4;
 struct MarchBatch {
     MarchParams frame[kBatchMax];
     unsigned n_frames;
 };
+static_assert(sizeof(MarchBatch) + 256 <= 4096, "a launch's frames, its queue and the hidden arguments share the 4 KB kernarg segment");
 
 // Kernel argument block of a slice view (slice_kernel, vr_slice.h; vr_slice_desc of include/vr.h): passed by value.  A slice has
 // a geometry of its own -- a plane in texture space, any output size, any volume and TF slot -- and reads nothing of MarchParams.

@@ -1245,31 +1245,13 @@ __device__ __forceinline__ int steps_inside(f3 p, f3 step, float bx0, float by0,
 }
 
 constexpr int kApproachMax = 1024;            // identity steps one iteration of it may take
-// Steps [k0, k1] outside of which the ray's positions certainly lie outside the box [lo, hi] (uvw; the caller's box carries its own
-// margin of a whole brick, far above what the rounded additions of n_steps steps can drift -- 2^-23 per step -- and what this
-// quotient's evaluation in f32 can be off by: 0.1 % + 2 steps are added on top).  A ray that misses the box: k0 = INT_MAX, k1 = -1.
-// NaN anywhere -> no step is excluded.
-__device__ __forceinline__ void steps_near_box(f3 p, f3 s, const float* box, int n_steps, int& k0, int& k1)
+// Steps [k0, k1] outside of which the ray's positions certainly lie in no active brick: steps_near_hull (vr_hull.h) against the
+// launch's plane pairs.  `marching`: the lane has a ray; the ten diagonals are looked at only when the box has left the packet a ray
+// (a wave-uniform branch: the packets beside the box pay for the three axes alone).
+__device__ __forceinline__ void steps_near_hull(const MarchParams& P, f3 p, f3 s, bool marching, int n_steps, int& k0, int& k1)
 {
-    const float drift = (float)n_steps * 4.8e-7f;
-    float t0 = 0.0f, t1 = (float)n_steps;
-    bool miss = false;
-    const float pp[3] = {p.x, p.y, p.z}, ss[3] = {s.x, s.y, s.z};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float lo = box[a] - drift, hi = box[3 + a] + drift;
-        if (ss[a] == 0.0f) {
-            miss = miss || pp[a] < lo || pp[a] > hi;
-        } else {
-            const float inv = __builtin_amdgcn_rcpf(ss[a]);  // (1 ulp: the margins below are a thousand times that)
-            const float ta = (lo - pp[a]) * inv, tb = (hi - pp[a]) * inv;
-            t0 = fmaxf(t0, fminf(ta, tb));  // (fminf / fmaxf drop a NaN operand)
-            t1 = fminf(t1, fmaxf(ta, tb));
-        }
-    }
-    miss = miss || t0 > t1 + 4.0f;
-    k0 = miss ? 0x7fffffff : max((int)fminf(t0 * 0.999f, 2.0e9f) - 2, 0);
-    k1 = miss ? -1 : (int)fminf(t1 * 1.001f + 3.0f, 2.0e9f);
+    const float pp[3] = {p.x, p.y, p.z}, ss[3] = {s.x, s.y, s.z}, bs[3] = {P.bsx, P.bsy, P.bsz};
+    vr::steps_near_hull(pp, ss, bs, P.abox, P.abox + 3, P.hull_lo, P.hull_hi, n_steps, k0, k1, [&](bool open) { return vr_ballot(marching && open) != 0; });
 }
 
 // The whole march of one ray (ray set-up, per-pixel prologue, the loop): what a lane does for its pixel `slot`.  Shared by
@@ -1345,12 +1327,12 @@ __device__ __forceinline__ void march_packet(const MarchParams& P, const PixelSl
                     // THE APPROACH (march_p2_kernel's, vr_p2.h, with votes instead of a wave minimum: the lanes without a ray are
                     // switched off here): until a ray of the packet stands in an active brick, one byte per ray and the identity
                     // steps it allows -- the largest power of two every ray allows -- as plain rounded additions; rays outside the
-                    // box of the active bricks (abox) ask for nothing.  The packets that never meet an active brick end here; the
+                    // hull of the active bricks (MarchParams::hull) ask for nothing.  The packets that never meet an active brick end here; the
                     // world position follows only when a ray may still sample.  Every exit is wave-uniform.
                     const float vmax = fmaxf(fmaxf(fabsf(step.x) * P.bsx, fabsf(step.y) * P.bsy), fabsf(step.z) * P.bsz);
                     const float lc = 0.999f / vmax;
                     int k0, k1;
-                    steps_near_box(p, step, P.abox, P.steps_count, k0, k1);
+                    steps_near_hull(P, p, step, true, P.steps_count, k0, k1);  // (the lanes without a ray are switched off here)
                     int skipped = 0;
                     while (vr_ballot(i0 >= lim) == 0) {
                         const bool near = i0 >= k0 && i0 <= k1;
@@ -1837,15 +1819,18 @@ __global__ void brick_dist_x_kernel(unsigned char* __restrict__ dist, int bnx, i
 // Active-brick count and box of a field (brick coordinates), accumulated by the z pass's workgroups: lo as 0x7fffffff - lo and hi as
 // hi + 1 under atomicMax, so that all zeros is the empty state.  The last workgroup publishes it to pinned host memory, generation last,
 // and zeroes it again for the next build.
+// hlo / hhi: the same for n . b + kHullBias along the ten diagonal directions of the hull (vr_hull.h, kHullDir[3 ..]).
 struct SkipSumDev {
     unsigned count, done;
     unsigned lo[3], hi[3];
+    unsigned hlo[kHullDiag], hhi[kHullDiag];
 };
 
 // y and z passes (in -> out, never in place): a tile of kDistCols bricks along x by kDistRows along the pass's axis, with kDistHalo
 // bricks of halo on either side, staged in LDS row by row (every global read a 128-byte row along x); each output scans outwards
 // from its brick until the distance reaches the best value found.  Grid: (x tiles, axis tiles, `other` positions).  LAST (the z
-// pass): the tile's active bricks are counted and boxed -- wavefront, then workgroup in LDS, then one atomic per value.
+// pass): the tile's active bricks are counted and boxed -- wavefront, then workgroup in LDS, then one atomic per value -- and the ten
+// diagonals of their hull reduced the same way in a second round.
 template <bool LAST>
 __global__ void __launch_bounds__(256) brick_dist_axis_kernel(const unsigned char* __restrict__ in, unsigned char* __restrict__ out,
                                                                int bnx, int n_axis, size_t axis_stride, size_t other_stride,
@@ -1894,6 +1879,8 @@ __global__ void __launch_bounds__(256) brick_dist_axis_kernel(const unsigned cha
         }
     }
     if constexpr (LAST) {
+        const unsigned lane_cnt = cnt;  // this lane's own bricks, before the wavefront folds them
+        const int lane_zlo = lo[2], lane_zhi = hi[2];
         for (int off = 32; off > 0; off >>= 1) {
             cnt += __shfl_down(cnt, off, 64);
 #pragma unroll
@@ -1903,6 +1890,7 @@ __global__ void __launch_bounds__(256) brick_dist_axis_kernel(const unsigned cha
             }
         }
         __shared__ int red[4][7];
+        __shared__ int hred[4][2 * kHullDiag];
         __shared__ bool last;
         const int wv = t >> 6;
         if ((t & 63) == 0) {
@@ -1910,6 +1898,26 @@ __global__ void __launch_bounds__(256) brick_dist_axis_kernel(const unsigned cha
             for (int q = 0; q < 3; ++q) {
                 red[wv][1 + q] = lo[q];
                 red[wv][4 + q] = hi[q];
+            }
+        }
+        // The hull's diagonals, a second round: a lane's bricks share x and y (its column, the workgroup's `other` position), so the
+        // extremes of n . b over them lie at the lane's lowest and highest z, which the box has: nothing per brick, and one direction
+        // at a time through the wavefront (no more registers than the box took).
+        for (int d = 0; d < kHullDiag; ++d) {
+            const int nx = kHullDir[kHullAxes + d][0], ny = kHullDir[kHullAxes + d][1], nz = kHullDir[kHullAxes + d][2];
+            int dlo = 0x7fffffff, dhi = -1;
+            if (lane_cnt != 0) {
+                const int xy = nx * x + ny * (int)blockIdx.z + kHullBias;
+                dlo = xy + nz * (nz > 0 ? lane_zlo : lane_zhi);
+                dhi = xy + nz * (nz > 0 ? lane_zhi : lane_zlo);
+            }
+            for (int off = 32; off > 0; off >>= 1) {
+                dlo = min(dlo, __shfl_down(dlo, off, 64));
+                dhi = max(dhi, __shfl_down(dhi, off, 64));
+            }
+            if ((t & 63) == 0) {
+                hred[wv][d] = dlo;
+                hred[wv][kHullDiag + d] = dhi;
             }
         }
         __syncthreads();
@@ -1920,12 +1928,20 @@ __global__ void __launch_bounds__(256) brick_dist_axis_kernel(const unsigned cha
                     red[0][1 + q] = min(red[0][1 + q], red[v][1 + q]);
                     red[0][4 + q] = max(red[0][4 + q], red[v][4 + q]);
                 }
+                for (int d = 0; d < kHullDiag; ++d) {
+                    hred[0][d] = min(hred[0][d], hred[v][d]);
+                    hred[0][kHullDiag + d] = max(hred[0][kHullDiag + d], hred[v][kHullDiag + d]);
+                }
             }
             if (red[0][0] != 0) {
                 atomicAdd(&sum->count, (unsigned)red[0][0]);
                 for (int q = 0; q < 3; ++q) {
                     atomicMax(&sum->lo[q], 0x7fffffffu - (unsigned)red[0][1 + q]);
                     atomicMax(&sum->hi[q], (unsigned)(red[0][4 + q] + 1));
+                }
+                for (int d = 0; d < kHullDiag; ++d) {
+                    atomicMax(&sum->hlo[d], 0x7fffffffu - (unsigned)hred[0][d]);
+                    atomicMax(&sum->hhi[d], (unsigned)(hred[0][kHullDiag + d] + 1));
                 }
             }
             __threadfence();
@@ -1940,11 +1956,16 @@ __global__ void __launch_bounds__(256) brick_dist_axis_kernel(const unsigned cha
                 host->box[q] = (int)(0x7fffffffu - v->lo[q]);
                 host->box[3 + q] = (int)v->hi[q] - 1;
             }
+            for (int d = 0; d < kHullDiag; ++d) {  // (meaningless when the count is 0)
+                host->hull_lo[d] = (int)(0x7fffffffu - v->hlo[d]) - kHullBias;
+                host->hull_hi[d] = (int)v->hhi[d] - 1 - kHullBias;
+            }
             __threadfence_system();
             host->gen = gen;  // (after the values: the host reads the generation first)
             v->count = 0;
             v->done = 0;
             for (int q = 0; q < 3; ++q) v->lo[q] = v->hi[q] = 0;
+            for (int d = 0; d < kHullDiag; ++d) v->hlo[d] = v->hhi[d] = 0;
         }
     }
 }

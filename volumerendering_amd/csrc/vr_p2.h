@@ -18,10 +18,11 @@
 //     mask record, which rides along with the distance-field byte.
 //   * THE APPROACH: in front of the pipelined loop a packet walks its identity steps without asking for anything ahead -- one
 //     distance-field byte per ray and the wave's minimum of the steps they allow, as plain rounded additions -- until a ray stands in
-//     an active brick; rays outside the uvw box of the active bricks (MarchParams::abox, steps_near_box) ask for nothing at all, and
-//     behind that box the pipelined loop is left.  The packets that cross the volume without ever meeting an active brick (C3: 64 %
-//     of the packets that cross it, 22 % of the frame's wavefront time when their jumps were trips of the pipelined loop) end
-//     there: C3 one frame at a time 0.522 -> 0.476 ms.
+//     an active brick; rays outside the hull of the active bricks (13 plane pairs -- the uvw box MarchParams::abox and ten diagonals,
+//     MarchParams::hull_lo / hull_hi; steps_near_hull, vr_hull.h) ask for nothing at all, and behind that hull the pipelined loop is
+//     left.  The packets that cross the volume without ever meeting an active brick (C3: 64 % of the packets that cross it, 22 % of
+//     the frame's wavefront time when their jumps were trips of the pipelined loop) end there: C3 one frame at a time 0.522 -> 0.476
+//     ms.  The planes are read once per packet, in front of the loops: nothing of them lives in the pipelined loop.
 // Arithmetic, positions, blend order and counts are march_packet's (vr_kernels.h): bit-identical frames and records.
 #pragma once
 #include "vr_pw.h"
@@ -532,16 +533,17 @@ __global__ __launch_bounds__(V == V_BASIC ? kP2ThreadsUnlit : kP2Threads) void m
                 alive = alive && can_blend<V>(dst.w);
                 if constexpr (kLit) w = mk3(w.x + wstep.x, w.y + wstep.y, w.z + wstep.z);
             };
-            int k_last = 0x7fffffff;  // no step of the ray behind this one can lie in an active brick (steps_near_box)
+            int k_last = 0x7fffffff;  // no step of the ray behind this one can lie in an active brick (steps_near_hull)
             if constexpr (SKIP) {
                 // THE APPROACH: until a ray of the packet stands in an active brick nothing is requested ahead -- a byte per ray, the
                 // identity steps it allows (march_packet's run length, and one for the position itself), the wave's minimum of them
                 // as plain rounded additions.  A packet that never meets an active brick (C3: 7 775 of the 12 214 packets whose rays
                 // cross the box, 22 % of the frame's wavefront time when they went through the pipelined loop's trips) ends here.
-                // Rays outside the box of the active bricks (abox; steps_near_box) ask for nothing at all: before it they are safe up
-                // to it, behind it to the end.  The world position follows when a ray may still sample (it is only read by the shading).
+                // Rays outside the hull of the active bricks (MarchParams::hull; steps_near_hull) ask for nothing at all: before it they
+                // are safe up to it, behind it to the end.  The world position follows when a ray may still sample (it is only read by
+                // the shading).
                 int k0, k1;
-                steps_near_box(pA, step, P0.abox, steps_count, k0, k1);
+                steps_near_hull(P0, pA, step, alive, steps_count, k0, k1);
                 if constexpr (kExit) k_last = k1;
                 int skipped = 0;  // (wave-uniform) steps taken here
                 while (i < n_in_w && vr_ballot(alive) != 0) {
