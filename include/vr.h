@@ -1157,6 +1157,104 @@ int vr_outlines_counters(vr_ctx* ctx, uint64_t out[3]);
  * the emit and the copy back.  Zeros before the first, after one that failed, and for the phases a call did not reach. */
 int vr_outlines_timing(vr_ctx* ctx, float ms[4]);
 
+/* ---- connected components: the pieces a contour of a mask slot consists of ----------------------------------------------------------
+ * Labels the connected components of a contour -- or of its complement in a box -- on the device (csrc/vr_comp.h), so that specks can be
+ * removed, the largest piece kept, holes filled, lesions enumerated and islands coloured without the volume passing through the host.
+ * Everything is integer arithmetic; nothing is approximate, and every output is a function of the inputs alone, never of scheduling.
+ *   Set: with background = 0, S holds the voxels of the box whose component src_contour is != 0.0f (the membership rule of the other
+ *     mask tools: NaN is in, -0.0f is out); with background = 1, the voxels of the box for which that is NOT so.  Everything outside the
+ *     box is outside S in both modes and is never a neighbour: a path never leaves the box.
+ *   Components: the classes of S under the connectivity.  Two voxels are neighbours as in vr_segment_grow: VR_COMP_FACES if they share a
+ *     face, VR_COMP_ALL a face, an edge or a corner; VR_COMP_PLANE_FACES and VR_COMP_PLANE_ALL are the same within a slice: they also
+ *     require equal z.
+ *   Numbering: a voxel's index is z * ny * nx + y * nx + x; a component's `first` is its voxel with the smallest index.  Component c
+ *     (0-based in the table, label c + 1) is the one with the c-th smallest `first`: labels rise in raster order of the components'
+ *     first voxels.
+ *   Table: per component its voxels, the half-open bounding box, `first`, and `faces`: bit 0 .. 5 set if it has a voxel with
+ *     x == box_lo[0], x == box_hi[0] - 1, y == box_lo[1], y == box_hi[1] - 1, z == box_lo[2], z == box_hi[2] - 1.
+ *   Selection: a component PASSES if min_voxels <= voxels <= max_voxels and (faces & reject_faces) == 0.  With keep_largest = K != 0
+ *     only the K passing components with the most voxels are selected, ties going to the smaller label; with K = 0 every passing one.
+ *     min_voxels > max_voxels selects nothing and is not an error.  R is the union of the selected components.
+ *   Contour write (dst_slot >= 0): R is combined into component dst_contour of dst_slot over the voxels of the box by the rule of
+ *     vr_mask_morph (`combine`, VR_MORPH_REPLACE .. VR_MORPH_ANDNOT).  The other three components keep their bits, and so does every
+ *     voxel outside the box.  dst == src (slot and contour) is legal: S is packed before anything is written.
+ *   Label map (label_slot >= 0): for every voxel of the box, component label_channel of label_slot becomes (float)label inside S and
+ *     +0.0f outside S -- the labels of ALL components, not only the selected ones.  Everything else keeps its bits.  If a label map is
+ *     asked for and n_components > VR_COMP_MAX_LABEL (labels are stored as f32: exact up to there) the call returns VR_ERR_UNSUPPORTED
+ *     and nothing is written.
+ *   One slot per call: if both a contour and a label map are asked for they must lie in the same slot and in different components,
+ *     else VR_ERR_INVALID_ARG.  An empty destination slot is created zeroed with the source's dimensions; a slot of other dimensions is
+ *     VR_ERR_INVALID_ARG.  With neither, the call writes no slot and rebuilds nothing, like vr_mask_outlines.
+ *   Capacity: max_components == 0 with components == NULL: no table is wanted (with both destinations -1 as well: the counting call).
+ *     If 0 < max_components < n_components the table and every slot stay untouched, the result is filled all the same, the call returns
+ *     VR_ERR_INVALID_ARG and vr_last_error names the needed count.  A pointer without a capacity or a capacity without a pointer:
+ *     VR_ERR_INVALID_ARG.
+ *   Result: n_components, n_selected; voxels = |S|, selected_voxels = |R|; largest = the voxels of the biggest component (0 if none);
+ *     lo, hi = the half-open bounding box of R, zeros when R is empty.
+ *   Nodes: the work is done on maximal runs of set bits along x within one row of the box (csrc/vr_comp.h); more than 2^32 - 1 of them
+ *     in one call: VR_ERR_UNSUPPORTED.
+ *   Counters (vr_components_counters): out[0] = voxels of the box, out[1] = run nodes, out[2] = pairs (node, run that touches it in an
+ *     earlier row its connectivity names) examined.  All three are functions of the inputs.
+ * vr_set_kernel_flavour, vr_set_arithmetic and the volume layout play no part in the result: there is one kernel form. */
+#define VR_COMP_FACES        6    /* neighbours share a face                                     */
+#define VR_COMP_ALL         26    /* ... a face, an edge or a corner                             */
+#define VR_COMP_PLANE_FACES  4    /* as 6, within a slice only (dz == 0)                         */
+#define VR_COMP_PLANE_ALL    8    /* as 26, within a slice only                                  */
+#define VR_COMP_MAX_KEEP    64
+#define VR_COMP_MAX_LABEL   (1u << 24)   /* labels are stored as f32: exact up to here           */
+typedef struct vr_component {
+    uint64_t voxels;
+    int32_t  lo[3], hi[3];     /* half-open bounding box                                         */
+    int32_t  first[3];         /* its voxel with the smallest index z*ny*nx + y*nx + x           */
+    uint32_t faces;            /* bit 0..5: has a voxel with x == box_lo[0], x == box_hi[0]-1,
+                                  y == box_lo[1], y == box_hi[1]-1, z == box_lo[2], z == box_hi[2]-1 */
+} vr_component;
+typedef struct vr_components_desc {
+    int32_t  src_slot, src_contour;   /* the set: an uploaded slot, component 0..3               */
+    int32_t  background;              /* 0: S = voxels of the box IN the contour; 1: those NOT in */
+    int32_t  connectivity;
+    int32_t  box_lo[3], box_hi[3];    /* half open, 0 <= lo <= hi <= n                           */
+    uint64_t min_voxels, max_voxels;  /* selected iff min <= voxels <= max ...                   */
+    uint32_t reject_faces;            /* ... and (faces & reject_faces) == 0 ...                 */
+    uint32_t keep_largest;            /* ... and, if != 0, among the keep_largest biggest of those (0..VR_COMP_MAX_KEEP) */
+    int32_t  dst_slot, dst_contour, combine;   /* dst_slot -1: no contour is written; combine = VR_MORPH_REPLACE .. ANDNOT */
+    int32_t  label_slot, label_channel;        /* label_slot -1: no label map                    */
+    uint32_t max_components;          /* what `components` holds; 0 with NULL = no table wanted  */
+    vr_component* components;         /* host memory                                             */
+} vr_components_desc;
+typedef struct vr_components_result {
+    uint64_t n_components, n_selected;
+    uint64_t voxels, selected_voxels;  /* |S|, |R|                                               */
+    uint64_t largest;                  /* voxels of the biggest component, 0 if none             */
+    int32_t  lo[3], hi[3];             /* half-open bounding box of R, zeros when R is empty     */
+} vr_components_result;
+
+/* Fills *out for contour src_contour of the whole volume of src_slot: background = 0, VR_COMP_FACES, the box (0,0,0) .. (nx,ny,nz),
+ * min_voxels = 1, max_voxels = UINT64_MAX, reject_faces = 0, keep_largest = 0, both destinations -1 (their components 0, combine
+ * VR_MORPH_REPLACE) and no table.  Pure host arithmetic; VR_ERR_INVALID_ARG for a NULL pointer, a slot or a contour out of range,
+ * VR_ERR_NOT_READY for an empty slot. */
+int vr_components_whole(const vr_ctx* ctx, int src_slot, int src_contour, vr_components_desc* out);
+
+/* Does the work; `result` may be NULL.  Synchronous, on the ctx's own stream: it waits for everything in flight.  When it writes a slot
+ * it is a data-preparation call like vr_mask_morph: everything derived from that slot is rebuilt before it returns.  When it writes none
+ * it rebuilds nothing.  Either way it leaves what the reporting calls say about earlier launches and tools as it was.  An empty box
+ * or an empty set gives zero components and VR_OK (a contour or a label map that was asked for is still written over the box).
+ * Checked before anything is enqueued or touched.  VR_ERR_INVALID_ARG: a NULL ctx or descriptor; a slot or component out of range
+ * (dst_slot and label_slot may be -1); background not 0 or 1; an unknown connectivity or combine; keep_largest > VR_COMP_MAX_KEEP; bits
+ * of reject_faces above bit 5; a box that is not 0 <= lo <= hi <= n on every axis; a contour and a label map in different slots or in
+ * the same component; a destination slot whose dimensions differ from the source's; components NULL with a capacity, or given with
+ * none.  VR_ERR_NOT_READY: the source slot is empty.  VR_ERR_OOM: the working buffers could not be allocated. */
+int vr_mask_components(vr_ctx* ctx, const vr_components_desc* desc, vr_components_result* result);
+
+/* Counters of the last vr_mask_components that got as far as counting (as described above).  Zeros before the first. */
+int vr_components_counters(vr_ctx* ctx, uint64_t out[3]);
+
+/* Device time of the last vr_mask_components in milliseconds, from events on the ctx's stream: ms[0] the pack, ms[1] the runs, their
+ * scan, the merge and the flatten, ms[2] the numbering, the statistics, the selection, the writes and the copy back (the host's looks at
+ * the counts included), ms[3] the rebuild of what is derived from the written slot, 0 when no slot is written.  Zeros before the first
+ * call and after one that failed. */
+int vr_components_timing(vr_ctx* ctx, float ms[4]);
+
 /* Volume layout in HBM (A/B measurements; frames and counts are bit-identical in every mode).
  *   0  default: the march kernels gather from a BRICKED copy of every slot -- the vec4 voxels and a scalar f32 density plane
  *      (what fetches that consume .a alone read: BasicVolumeApp.wgsl:171, the density / dose fetches of the other shaders)

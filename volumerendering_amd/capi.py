@@ -46,6 +46,8 @@ DIST_OUTSIDE, DIST_INSIDE, DIST_SIGNED = range(3)                           # vr
 POLY_EVEN_ODD, POLY_UNION = 0, 1                                            # vr_polygons_desc.rule (include/vr.h)
 POLY_MAX_COORD, POLY_MAX_SPACING = 1 << 29, 1 << 20                         # of a point coordinate or origin value (magnitude), a spacing
 OUTLINE_SPLIT, OUTLINE_JOIN = 0, 1                                          # vr_outlines_desc.connect (include/vr.h)
+COMP_FACES, COMP_ALL, COMP_PLANE_FACES, COMP_PLANE_ALL = 6, 26, 4, 8              # vr_components_desc.connectivity (include/vr.h)
+COMP_MAX_KEEP, COMP_MAX_LABEL = 64, 1 << 24                                 # of keep_largest; of n_components with a label map
 DIST_MAX_SPACING, DIST_MAX_LIMIT, DIST_MAX_EXTENT = 1 << 20, 1 << 31, 1 << 30  # of a spacing, the limit, (hi - lo) * spacing per axis
 
 # every symbol include/vr.h declares (tests check that the library exports each of them)
@@ -70,6 +72,7 @@ ABI_SYMBOLS = [
     "vr_dist_whole", "vr_mask_distance", "vr_dist_counters", "vr_dist_timing",
     "vr_polygons_whole", "vr_mask_polygons", "vr_polygons_counters", "vr_polygons_timing",
     "vr_outlines_whole", "vr_mask_outlines", "vr_outlines_counters", "vr_outlines_timing",
+    "vr_components_whole", "vr_mask_components", "vr_components_counters", "vr_components_timing",
 ]
 
 
@@ -316,6 +319,51 @@ class OutlinesResult(C.Structure):
                 tuple(int(x) for x in self.area2))
 
 
+class Component(C.Structure):
+    """struct vr_component (include/vr.h): a component's voxels, half-open bounding box, first voxel (x, y, z) and the faces of the box
+    it touches."""
+    _fields_ = [("voxels", C.c_uint64), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("first", C.c_int32 * 3), ("faces", C.c_uint32)]
+
+    def as_tuple(self):
+        """(voxels, lo, hi, first, faces)"""
+        return (int(self.voxels), tuple(int(x) for x in self.lo), tuple(int(x) for x in self.hi), tuple(int(x) for x in self.first),
+                int(self.faces))
+
+
+class ComponentsDesc(C.Structure):
+    """struct vr_components_desc (include/vr.h): the set (slot, contour, background), the connectivity, the voxel box, the selection
+    (size window, rejected faces, keep_largest), the contour and label-map destinations, and the table's capacity and array (set by
+    Context.mask_components)."""
+    _fields_ = [
+        ("src_slot", C.c_int32), ("src_contour", C.c_int32), ("background", C.c_int32), ("connectivity", C.c_int32),
+        ("box_lo", C.c_int32 * 3), ("box_hi", C.c_int32 * 3), ("min_voxels", C.c_uint64), ("max_voxels", C.c_uint64),
+        ("reject_faces", C.c_uint32), ("keep_largest", C.c_uint32), ("dst_slot", C.c_int32), ("dst_contour", C.c_int32),
+        ("combine", C.c_int32), ("label_slot", C.c_int32), ("label_channel", C.c_int32), ("max_components", C.c_uint32),
+        ("components", C.c_void_p),
+    ]
+
+    def copy(self, **over) -> "ComponentsDesc":
+        """A copy with the given fields replaced (box_lo / box_hi from any sequence of three integers)."""
+        d = ComponentsDesc.from_buffer_copy(bytes(self))
+        for k, v in over.items():
+            if k in ("box_lo", "box_hi"):
+                v = (C.c_int32 * 3)(*[int(x) for x in v])
+            setattr(d, k, v)
+        return d
+
+
+class ComponentsResult(C.Structure):
+    """struct vr_components_result: the components and how many are selected, |S|, |R|, the biggest component's voxels and the half-open
+    bounding box of R (zeros when R is empty)."""
+    _fields_ = [("n_components", C.c_uint64), ("n_selected", C.c_uint64), ("voxels", C.c_uint64), ("selected_voxels", C.c_uint64),
+                ("largest", C.c_uint64), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3)]
+
+    def as_tuple(self):
+        """(n_components, n_selected, voxels, selected_voxels, largest, lo, hi)"""
+        return (int(self.n_components), int(self.n_selected), int(self.voxels), int(self.selected_voxels), int(self.largest),
+                tuple(int(x) for x in self.lo), tuple(int(x) for x in self.hi))
+
+
 class VrError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"vr error {code}: {msg}")
@@ -424,6 +472,10 @@ def load() -> C.CDLL:
     lib.vr_mask_outlines.argtypes = [vp, C.POINTER(OutlinesDesc), C.POINTER(OutlinesResult)]
     lib.vr_outlines_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
     lib.vr_outlines_timing.argtypes = [vp, C.POINTER(C.c_float * 4)]
+    lib.vr_components_whole.argtypes = [vp, i32, i32, C.POINTER(ComponentsDesc)]
+    lib.vr_mask_components.argtypes = [vp, C.POINTER(ComponentsDesc), C.POINTER(ComponentsResult)]
+    lib.vr_components_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
+    lib.vr_components_timing.argtypes = [vp, C.POINTER(C.c_float * 4)]
     lib.vr_present_async.argtypes = [vp, vp, vp, vp]
     lib.vr_present_tiles_async.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
     lib.vr_hint_frames_in_flight.argtypes = [vp, i32]
@@ -902,6 +954,35 @@ class Context:
     def outlines_timing(self):
         """(pack, corners + scan + link, doubling rounds, emit + copy back) of the last mask_outlines in ms of device time."""
         return self._tool_timing(self.lib.vr_outlines_timing)
+
+    def components_whole(self, src_slot: int, src_contour: int) -> ComponentsDesc:
+        """vr_components_whole: the descriptor of a labelling of contour src_contour over the whole volume (FACES, every component
+        selected, no destination, no table)."""
+        d = ComponentsDesc()
+        self._chk(self.lib.vr_components_whole(self.h, src_slot, src_contour, C.byref(d)))
+        return d
+
+    def mask_components(self, desc: ComponentsDesc) -> dict:
+        """vr_mask_components: the connected components of a contour (synchronous): the counting call, which writes nothing, then the
+        call that stores.  Returns {"result": ComponentsResult, "components": [(voxels, lo, hi, first, faces)]}.  The descriptor's own
+        capacity and array are ignored."""
+        out = ComponentsResult()
+        self._chk(self.lib.vr_mask_components(self.h, C.byref(desc.copy(dst_slot=-1, label_slot=-1, max_components=0, components=None)),
+                                              C.byref(out)))
+        n = int(out.n_components)
+        table = (Component * n)()
+        d = desc.copy(max_components=n, components=C.cast(table, C.c_void_p).value if n else None)
+        if n or desc.dst_slot >= 0 or desc.label_slot >= 0:
+            self._chk(self.lib.vr_mask_components(self.h, C.byref(d), C.byref(out)))  # (the table lives until here)
+        return {"result": out, "components": [q.as_tuple() for q in table]}
+
+    def components_counters(self):
+        """(voxels of the box, run nodes, pairs of a node and a touching run examined) of the last mask_components."""
+        return self._tool_counters(self.lib.vr_components_counters)
+
+    def components_timing(self):
+        """(pack, runs + scan + merge + flatten, numbering .. copy back, refresh) of the last mask_components in ms of device time."""
+        return self._tool_timing(self.lib.vr_components_timing)
 
     def set_volume_layout(self, mode: int):
         """0 bricked copy (default), 1 the reference's vec4 voxels only, 3 x-fastest voxels + density plane (2 was removed)."""

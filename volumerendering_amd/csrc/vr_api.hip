@@ -17,6 +17,8 @@
 #include "vr_raster.h"
 // Contour tracing (vr_mask_outlines): the inverse of the raster, exact integer work on the same bit-rows, compiled once as well
 #include "vr_outline.h"
+// Connected components (vr_mask_components): a union-find over the runs of the same bit-rows, compiled once as well
+#include "vr_comp.h"
 
 // the same dispatch over the kernels compiled with fused multiply-adds (vr_fused.hip)
 namespace vrf {
@@ -49,6 +51,7 @@ using namespace vr;
 #include "vr_api_dist.h"
 #include "vr_api_raster.h"
 #include "vr_api_outline.h"
+#include "vr_api_components.h"
 
 namespace {
 

@@ -442,6 +442,20 @@ struct OutlineState {
     ToolReport report;                   // phases: pack, corners + scan + link, doubling rounds, emit + copy back
 };
 
+// Connected components (vr_mask_components, vr_comp.h): the working buffers of the last call, grown on demand; what
+// vr_components_counters and vr_components_timing report.  Of vr_ctx::bit_row_scratch it takes two buffers: S and R.
+struct CompState {
+    DevBuf<unsigned> base;               // per word of the box: the runs that start in it, then the nodes before it
+    DevBuf<unsigned long long> sums;     // the scans' tile sums
+    DevBuf<unsigned> parent, root;       // per node: the union-find forest, then the roots before it; its root
+    DevBuf<unsigned> row, ab;            // ... its row of the box, its first and last x
+    DevBuf<vr_component> table;          // per component
+    DevBuf<unsigned> sel;                // ... it is selected
+    DevBuf<unsigned long long> pass;     // ... its voxels if it passes the filters (keep_largest: the host picks the winners from a copy)
+    WordsPair<CompWords> io;             // the totals, the pairs, the counts and bounding boxes
+    ToolReport report;                   // phases: pack, runs + scan + merge + flatten, numbering .. copy back, refresh_bricks
+};
+
 // What the reporting calls (vr_last_counters, vr_last_kernel_flavour, vr_last_timing, vr_kernel_times, vr_kernel_choice,
 // vr_download_tiles, vr_last_block_trace) read about the most recent march launch.  vr_pick copies it out and back as one value.
 struct LastLaunch {
@@ -536,13 +550,14 @@ struct vr_ctx {
     const float* d_near = nullptr;
     const float* d_far = nullptr;
     GrowState grow;  // region growing (vr_segment_grow)
-    // The bit-row scratch of the four mask tools below (vr_bitrows.h), grown to the most words a call has asked for.  Each call drains
+    // The bit-row scratch of the five mask tools below (vr_bitrows.h), grown to the most words a call has asked for.  Each call drains
     // the device, zeroes the buffers it takes before it reads them and is synchronous on return: no two uses are ever live.
     DevBuf<unsigned long long> bit_row_scratch;
     MorphState morph;  // mask morphology (vr_mask_morph)
     DistState dist;    // distance maps (vr_mask_distance)
     RasterState raster;  // polygon rasterisation (vr_mask_polygons)
     OutlineState outline;  // contour tracing (vr_mask_outlines)
+    CompState comp;  // connected components (vr_mask_components)
     std::string err;
 };
 
