@@ -1,7 +1,7 @@
-// order_probe.hip -- test-only: vr::order_blocks_kernel (csrc/vr_kernels.h) on records the test makes, launched exactly as finish_slot
+// order_probe.hip -- test-only: vr::order_blocks_kernel (csrc/vr_frame.h) on records the test makes, launched exactly as finish_slot
 // launches it behind a march launch -- one workgroup of 1024 threads -- with what it reports read back (tests/test_launch_records_gpu.py).
 // Built at test time with build.py's flags into tests/_build/.
-#include "vr_kernels.h"
+#include "vr_frame.h"
 
 #include <cstring>
 

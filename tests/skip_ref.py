@@ -46,7 +46,7 @@ def brick_max(plane):
 
 
 def brick_records(vol):
-    """Per brick of 4^3 cells (vr_kernels.h brick_max_kernel): the maxima of .a and of max(r, g, b) over the voxels
+    """Per brick of 4^3 cells (vr_prep.h brick_max_kernel): the maxima of .a and of max(r, g, b) over the voxels
     [4 b, min(4 b + 4, n - 1)] of each axis (finite volumes)."""
     return brick_max(vol[..., 3]), np.maximum(np.maximum(brick_max(vol[..., 0]), brick_max(vol[..., 1])), brick_max(vol[..., 2]))
 

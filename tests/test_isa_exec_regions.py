@@ -18,7 +18,7 @@ LIB = os.path.join(ROOT, "volumerendering_amd", "libvr_hip.so")
 def test_nothing_but_loads_between_the_exec_writes():
     assert os.path.exists(LIB), "libvr_hip.so is not built (python -c 'import __graft_entry__ as g; g.build()')"
     objs = cer.code_objects(LIB)
-    assert len(objs) >= 2  # separately rounded and fused multiply-adds: two translation units
+    assert len(objs) == 3  # the C ABI's unit, and the march kernels with separately rounded and with fused multiply-adds
     regions, bad = 0, []
     for o in objs:
         r, b = cer.check(cer.disassemble(o))

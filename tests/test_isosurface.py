@@ -19,6 +19,7 @@ from volumerendering_amd import capi
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import check_exec_regions as cer  # noqa: E402
+from march_units import march_units  # noqa: E402
 
 f32 = np.float32
 W, H = 40, 32
@@ -123,24 +124,9 @@ def test_abi_symbol_and_constant():
 
 @pytest.mark.skipif(not os.path.exists(cer.OBJDUMP), reason="llvm-objdump of the ROCm toolchain not found")
 def test_iso_kernels_in_both_units_without_scratch():
-    """Both translation units (separate and fused multiply-adds) carry march_iso_kernel instances -- skipping or not, 32- or
-    64-bit offsets, one frame or several -- and no instruction of theirs touches scratch."""
-    lib = os.path.join(ROOT, "volumerendering_amd", "libvr_hip.so")
-    objs = cer.code_objects(lib)
-    assert len(objs) >= 2
-    found = []
-    for o in objs:
-        kernel, names, scratch = None, set(), []
-        for line in cer.disassemble(o).split("\n"):
-            m = re.match(r"^[0-9a-f]+ <([^>]+)>:", line)
-            if m:
-                kernel = m.group(1) if "march_iso_kernel" in m.group(1) else None
-                if kernel:
-                    names.add(kernel)
-                continue
-            if kernel and "scratch_" in line:
-                scratch.append((kernel, line.strip()))
+    """Exactly two code objects, the march units of namespace vr (separate multiply-adds) and of namespace vrf (fused; march_units),
+    carry the 8 march_iso_kernel instances each -- skipping or not, 32- or 64-bit offsets, one frame or several -- and no instruction
+    of theirs touches scratch."""
+    for names, scratch, _ in march_units("march_iso_kernel"):
         assert len(names) == 8, sorted(names)
         assert not scratch, scratch[:5]
-        found.append(names)
-    assert any(n.startswith("_ZN2vr") for s in found for n in s) and any(n.startswith("_ZN3vrf") for s in found for n in s)

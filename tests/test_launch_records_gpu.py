@@ -36,7 +36,7 @@ def build_probe() -> str:
     os.makedirs(OUT, exist_ok=True)
     so = os.path.join(OUT, "liborder_probe.so")
     src = os.path.join(HERE, "order_probe", "order_probe.hip")
-    deps = [src] + [os.path.join(CSRC, f) for f in ("vr_kernels.h", "vr_device.h", "vr_units.h")]
+    deps = [src] + [os.path.join(CSRC, f) for f in ("vr_frame.h", "vr_shared.h", "vr_device.h", "vr_units.h")]
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
         tmp = so + f".{os.getpid()}.tmp"
         subprocess.run([build.HIPCC, *build.HIP_FLAGS, "-I", CSRC, "-o", tmp, src], check=True)

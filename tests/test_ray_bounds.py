@@ -22,6 +22,7 @@ from volumerendering_amd import capi
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import check_exec_regions as cer  # noqa: E402
+from march_units import march_units  # noqa: E402
 
 f32 = np.float32
 VARIANTS = [(ob.BASIC, "basic"), (ob.LIGHT, "light")]
@@ -188,33 +189,18 @@ def test_abi_symbol():
 
 @pytest.mark.skipif(not os.path.exists(cer.OBJDUMP), reason="llvm-objdump of the ROCm toolchain not found")
 def test_bound_kernels_in_both_units_without_scratch():
-    """Both translation units (separate and fused multiply-adds) carry the 8 march_bound_kernel instances -- BASIC (Li0) or LIGHT
-    (Li1), 32- or 64-bit offsets, skipping or not, launches of one frame --, no instruction of theirs touches scratch, and the
-    exec-region check of the two-steps-ahead kernel still passes on the library."""
-    lib = os.path.join(ROOT, "volumerendering_amd", "libvr_hip.so")
-    objs = cer.code_objects(lib)
-    assert len(objs) >= 2
-    found, regions, bad = [], 0, []
-    for o in objs:
-        text = cer.disassemble(o)
-        kernel, names, scratch = None, set(), []
-        for line in text.split("\n"):
-            m = re.match(r"^[0-9a-f]+ <([^>]+)>:", line)
-            if m:
-                kernel = m.group(1) if "march_bound_kernel" in m.group(1) else None
-                if kernel:
-                    names.add(kernel)
-                continue
-            if kernel and "scratch_" in line:
-                scratch.append((kernel, line.strip()))
+    """Exactly two code objects, the march units of namespace vr (separate multiply-adds) and of namespace vrf (fused; march_units),
+    carry the 8 march_bound_kernel instances each -- BASIC (Li0) or LIGHT (Li1), 32- or 64-bit offsets, skipping or not, launches of
+    one frame --, no instruction of theirs touches scratch, and the exec-region check of the two-steps-ahead kernel still passes on
+    the two units."""
+    regions, bad = 0, []
+    for names, scratch, text in march_units("march_bound_kernel"):
         want = {f"march_bound_kernelILi{v}ELb{o32}ELb{s}ELb0EE" for v in (0, 1) for o32 in (0, 1) for s in (0, 1)}
-        assert {re.search(r"march_bound_kernelI\w+?EE", n).group(0) for n in names} == want, sorted(names)
+        assert len(names) == 8 and {re.search(r"march_bound_kernelI\w+?EE", n).group(0) for n in names} == want, sorted(names)
         assert not scratch, scratch[:5]
-        found.append(names)
         r, b = cer.check(text)
         regions += r
         bad += b
-    assert any(n.startswith("_ZN2vr") for s in found for n in s) and any(n.startswith("_ZN3vrf") for s in found for n in s)
     assert regions >= 32 and not bad, (regions, bad[:5])
 
 

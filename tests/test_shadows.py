@@ -18,6 +18,7 @@ from volumerendering_amd import capi
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import check_exec_regions as cer  # noqa: E402
+from march_units import march_units  # noqa: E402
 
 f32 = np.float32
 W, H = 40, 32
@@ -113,26 +114,11 @@ def test_abi_symbols_without_a_new_variant():
 
 @pytest.mark.skipif(not os.path.exists(cer.OBJDUMP), reason="llvm-objdump of the ROCm toolchain not found")
 def test_shadow_kernels_in_both_units_without_scratch():
-    """Both translation units carry the 8 march_shadow_kernel instances (skipping or not, 32- or 64-bit offsets, one frame or several)
-    and the 4 shadow_build_kernel instances, and no instruction of theirs touches scratch."""
-    lib = os.path.join(ROOT, "volumerendering_amd", "libvr_hip.so")
-    objs = cer.code_objects(lib)
-    assert len(objs) >= 2
-    found = []
-    for o in objs:
-        kernel, march, build, scratch = None, set(), set(), []
-        for line in cer.disassemble(o).split("\n"):
-            m = re.match(r"^[0-9a-f]+ <([^>]+)>:", line)
-            if m:
-                name = m.group(1)
-                kernel = name if ("march_shadow_kernel" in name or "shadow_build_kernel" in name) else None
-                if kernel:
-                    (march if "march_shadow_kernel" in kernel else build).add(kernel)
-                continue
-            if kernel and "scratch_" in line:
-                scratch.append((kernel, line.strip()))
+    """Exactly two code objects, the march units of namespace vr and of namespace vrf (march_units), carry shadow kernels: each the 8
+    march_shadow_kernel instances (skipping or not, 32- or 64-bit offsets, one frame or several) and the 4 shadow_build_kernel
+    instances, and no instruction of theirs touches scratch."""
+    for names, scratch, _ in march_units("march_shadow_kernel", "shadow_build_kernel"):
+        march = {n for n in names if "march_shadow_kernel" in n}
         assert len(march) == 8, sorted(march)
-        assert len(build) == 4, sorted(build)
+        assert len(names - march) == 4, sorted(names - march)
         assert not scratch, scratch[:5]
-        found.append(march | build)
-    assert any(n.startswith("_ZN2vr") for s in found for n in s) and any(n.startswith("_ZN3vrf") for s in found for n in s)

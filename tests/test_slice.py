@@ -18,6 +18,7 @@ from volumerendering_amd import capi
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import check_exec_regions as cer  # noqa: E402
+from march_units import march_units, once_in_the_abi_unit  # noqa: E402
 
 f32 = np.float32
 
@@ -153,27 +154,13 @@ def test_abi_symbols_struct_and_null_context():
 
 @pytest.mark.skipif(not os.path.exists(cer.OBJDUMP), reason="llvm-objdump of the ROCm toolchain not found")
 def test_slice_kernels_in_both_units_without_scratch():
-    """Both translation units carry the 24 slice_kernel instances -- three reductions x two filters x 32- / 64-bit offsets x
-    skipping or not -- and no instruction of theirs touches scratch."""
-    lib = os.path.join(ROOT, "volumerendering_amd", "libvr_hip.so")
-    objs = cer.code_objects(lib)
-    assert len(objs) >= 2
-    found = []
-    for o in objs:
-        kernel, names, scratch = None, set(), []
-        for line in cer.disassemble(o).split("\n"):
-            m = re.match(r"^[0-9a-f]+ <([^>]+)>:", line)
-            if m:
-                kernel = m.group(1) if "slice_kernel" in m.group(1) else None
-                if kernel:
-                    names.add(kernel)
-                continue
-            if kernel and "scratch_" in line:
-                scratch.append((kernel, line.strip()))
+    """Exactly two code objects, the march units of namespace vr and of namespace vrf (march_units), carry the 24 slice_kernel
+    instances each -- three reductions x two filters x 32- / 64-bit offsets x skipping or not -- and no instruction of theirs touches
+    scratch.  slice_sum_kernel exists once, in the C ABI's unit, without scratch."""
+    for names, scratch, _ in march_units("slice_kernel"):
         assert len(names) == 24, sorted(names)
         assert not scratch, scratch[:5]
-        found.append(names)
-    assert any(n.startswith("_ZN2vr") for s in found for n in s) and any(n.startswith("_ZN3vrf") for s in found for n in s)
+    assert not once_in_the_abi_unit("slice_sum_kernel")[1]
 
 
 def test_bench_tool_help():

@@ -21,6 +21,7 @@ from volumerendering_amd import capi
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import check_exec_regions as cer  # noqa: E402
+from march_units import march_units, once_in_the_abi_unit  # noqa: E402
 
 f32 = np.float32
 W, H = 40, 32
@@ -180,27 +181,13 @@ def test_argument_validation_without_a_device():
 
 @pytest.mark.skipif(not os.path.exists(cer.OBJDUMP), reason="llvm-objdump of the ROCm toolchain not found")
 def test_surf_kernels_in_both_units_without_scratch():
-    """Both translation units (separate and fused multiply-adds) carry the 8 march_surf_kernel instances -- skipping or not, 32- or
-    64-bit offsets, one frame or several -- and the 8 of the isosurface's iso_point_kernel, and no instruction of theirs touches
-    scratch."""
-    lib = os.path.join(ROOT, "volumerendering_amd", "libvr_hip.so")
-    objs = cer.code_objects(lib)
-    assert len(objs) >= 2
-    found = []
-    for o in objs:
-        kernel, surf, point, scratch = None, set(), set(), []
-        for line in cer.disassemble(o).split("\n"):
-            m = re.match(r"^[0-9a-f]+ <([^>]+)>:", line)
-            if m:
-                name = m.group(1)
-                kernel = name if ("march_surf_kernel" in name or "iso_point_kernel" in name) else None
-                if kernel:
-                    (surf if "march_surf_kernel" in kernel else point).add(kernel)
-                continue
-            if kernel and "scratch_" in line:
-                scratch.append((kernel, line.strip()))
+    """Exactly two code objects, the march units of namespace vr (separate multiply-adds) and of namespace vrf (fused; march_units),
+    carry surface kernels: each the 8 march_surf_kernel instances -- skipping or not, 32- or 64-bit offsets, one frame or several --
+    and the 8 of the isosurface's iso_point_kernel, and no instruction of theirs touches scratch.  surface_depth_kernel exists once,
+    in the C ABI's unit, without scratch."""
+    for names, scratch, _ in march_units("march_surf_kernel", "iso_point_kernel"):
+        surf = {n for n in names if "march_surf_kernel" in n}
         assert len(surf) == 8, sorted(surf)
-        assert len(point) == 8, sorted(point)
+        assert len(names - surf) == 8, sorted(names - surf)
         assert not scratch, scratch[:5]
-        found.append(surf | point)
-    assert any(n.startswith("_ZN2vr") for s in found for n in s) and any(n.startswith("_ZN3vrf") for s in found for n in s)
+    assert not once_in_the_abi_unit("surface_depth_kernel")[1]

@@ -59,3 +59,24 @@ Disassembly of section .text:
     differ, missing, new = dcd.compare(a, renamed)
     assert differ == [] and missing == ["_ZN2vr14present_kernelEPK15HIP_vector_typeIfLj4EEPji"]
     assert new == ["_ZN2vr15present2_kernelEPK15HIP_vector_typeIfLj4EEPji"]
+
+    # A library is the union of its code objects: the same two functions in one listing, in two listings either way round, and in
+    # three with one that holds neither, are the same library; a change is found wherever the function lives.
+    head, march, present = a.split("\n\n0000")
+    one = [a]
+    two = [head + "\n\n0000" + march + "\n", head + "\n\n0000" + present]
+    other_two = [two[1], two[0]]
+    three = [head + "\n", two[1], two[0]]
+    assert sorted(dcd.union(two)[0]) == sorted(dcd.functions(a)) and dcd.union(two)[0] == dcd.functions(a)
+    for x in (one, two, other_two, three):
+        assert dcd.union(x)[1] == []
+        for y in (one, two, other_two, three):
+            assert dcd.compare(x, y) == ([], [], [])
+        assert dcd.compare(x, [changed]) == (["_ZN2vr12march_kernelILi0EEEvNS_10MarchBatchE"], [], [])
+        assert dcd.compare([renamed], x)[1:] == (["_ZN2vr15present2_kernelEPK15HIP_vector_typeIfLj4EEPji"],
+                                                 ["_ZN2vr14present_kernelEPK15HIP_vector_typeIfLj4EEPji"])
+    assert dcd.compare(two, [two[0]]) == ([], ["_ZN2vr14present_kernelEPK15HIP_vector_typeIfLj4EEPji"], [])
+    # one symbol in two code objects of a library: fine with one body (moved: other addresses), reported with two
+    assert dcd.union([a, moved]) == (dcd.functions(a), [])
+    assert dcd.union([a, changed])[1] == ["_ZN2vr12march_kernelILi0EEEvNS_10MarchBatchE"]
+    assert dcd.union([two[0], two[1], changed])[1] == ["_ZN2vr12march_kernelILi0EEEvNS_10MarchBatchE"]

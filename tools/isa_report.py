@@ -3,8 +3,9 @@
 waits -- the loads and the s_waitcnt vmcnt values, so that a change that makes the compiler drain the software pipeline
 (`vmcnt(0)` inside the pipelined loop of march_p2_kernel) is seen without a GPU.
 
-    hipcc <flags of build.py> --cuda-device-only -S -o /tmp/vr_api.s volumerendering_amd/csrc/vr_api.hip
-    python tools/isa_report.py /tmp/vr_api.s march_p2_kernelILi1ELb1E
+    hipcc <flags of build.py> --cuda-device-only -S -o /tmp/vr_march.s volumerendering_amd/csrc/vr_march.hip
+    python tools/isa_report.py /tmp/vr_march.s march_p2_kernelILi1ELb1E
+(vr_march.hip: the march kernels with separately rounded multiply-adds; vr_fused.hip the fused ones, vr_api.hip everything else)
 """
 import re
 import sys

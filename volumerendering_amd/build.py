@@ -3,6 +3,7 @@
 from __future__ import annotations
 
 import os
+import re
 import shutil
 import subprocess
 
@@ -33,24 +34,40 @@ def _sources(d: str, exts: tuple[str, ...]) -> list[str]:
     return sorted(out)
 
 
+# libvr_hip.so's translation units: the C ABI with the auxiliary and voxel-tool kernels, and the march kernels once per arithmetic mode
+HIP_UNITS = ("vr_api", "vr_march", "vr_fused")
+
+
+def include_closure(src: str, flags: list[str]) -> list[str]:
+    """src and every file it reaches through #include outside the system directories, as the compiler resolves them under
+    `flags` (the host pass's preprocessor alone: no code is generated, and none can be forgotten)."""
+    out = subprocess.run([HIPCC, *flags, "--cuda-host-only", "-E", "-MM", src], check=True, stdout=subprocess.PIPE, text=True).stdout
+    rule = out.replace("\\\n", " ").split(": ", 1)[1]  # (a make rule `object: files`, a space in a name escaped)
+    return [os.path.normpath(p.replace("\\ ", " ")) for p in re.split(r"(?<!\\)\s+", rule.strip())]
+
+
+def stale_units(objs: dict[str, str], closures: dict[str, list[str]], stamp: str, want: str) -> list[str]:
+    """The units to compile: all of them where the flags stamp is not `want`, else each whose object is missing or older than a
+    file of its own closure."""
+    if not os.path.exists(stamp) or open(stamp).read() != want:
+        return list(objs)
+    return [u for u in objs if _newer(objs[u], closures[u])]
+
+
 def build_hip(force: bool = False) -> str:
-    """Two translation units, compiled side by side: vr_api.hip (C ABI + kernels with separately rounded multiply-adds)
-    and vr_fused.hip (the march kernels once more with fused multiply-adds), linked into one libvr_hip.so."""
+    """Three translation units, compiled side by side: vr_api.hip (the C ABI and every kernel that exists once), vr_march.hip
+    (the march kernels with separately rounded multiply-adds) and vr_fused.hip (the march kernels once more with fused
+    multiply-adds), linked into one libvr_hip.so.  An edit recompiles the units whose include closure holds the edited file."""
     target = os.path.join(HERE, "libvr_hip.so")
-    hdrs = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")]  # (every header: none can be forgotten)
-    hdrs.append(os.path.join(os.path.dirname(HERE), "include", "vr.h"))
     flags = [f for f in HIP_FLAGS if f != "-shared"] + os.environ.get("VR_EXTRA_HIPCC_FLAGS", "").split()
     # the flags the objects were compiled with: a change (VR_EXTRA_HIPCC_FLAGS) rebuilds them
     stamp = os.path.join(CSRC, ".build_flags")
     want = " ".join(flags)
-    if not os.path.exists(stamp) or open(stamp).read() != want:
-        force = True
-    objs, procs = [], []
-    for name in ("vr_api", "vr_fused"):
-        src, obj = os.path.join(CSRC, name + ".hip"), os.path.join(CSRC, name + ".o")
-        objs.append(obj)
-        if force or _newer(obj, hdrs + [src]):
-            procs.append((name, subprocess.Popen([HIPCC, *flags, "-c", "-o", obj, src])))
+    srcs = {u: os.path.join(CSRC, u + ".hip") for u in HIP_UNITS}
+    objd = {u: os.path.join(CSRC, u + ".o") for u in HIP_UNITS}
+    objs = list(objd.values())
+    stale = list(HIP_UNITS) if force else stale_units(objd, {u: include_closure(srcs[u], flags) for u in HIP_UNITS}, stamp, want)
+    procs = [(u, subprocess.Popen([HIPCC, *flags, "-c", "-o", objd[u], srcs[u]])) for u in stale]
     for name, pr in procs:
         if pr.wait() != 0:
             raise subprocess.CalledProcessError(pr.returncode, f"hipcc {name}.hip")

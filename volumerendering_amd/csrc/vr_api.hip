@@ -1,9 +1,16 @@
 // vr_api.hip -- implementation of the C ABI declared in include/vr.h on top of the gfx950 kernels: one translation unit, the host code
 // by concern in vr_ctx.h and vr_api_*.h; here the context's life (create, resize, destroy), its settings and its streams.
+// The march kernels are not in this unit: vr_march.hip and vr_fused.hip compile them, one per arithmetic mode, and the host code
+// reaches them through launch_march, launch_shadow_build and launch_slice (vr_device.h).  What is compiled here, once, are the
+// kernels that no arithmetic mode touches: the auxiliary kernels and the voxel tools.
 // No CPU fallback exists behind this ABI (and nothing under oracle/ is referenced): without a usable HIP
 // device vr_create fails with VR_ERR_HIP.
 #include "../../include/vr.h"
-#include "vr_launch.h"
+#include "vr_device.h"
+// Auxiliary kernels: a volume's preparation and brick records, the skip-field build, a frame around its launch
+#include "vr_prep.h"
+#include "vr_skipfield.h"
+#include "vr_frame.h"
 #include "vr_units.h"  // what the voxel tools below share
 // Histograms (vr_histogram_async): nothing to fuse, so this kernel exists once, here
 #include "vr_hist.h"
@@ -19,13 +26,6 @@
 #include "vr_outline.h"
 // Connected components (vr_mask_components): a union-find over the runs of the same bit-rows, compiled once as well
 #include "vr_comp.h"
-
-// the same dispatch over the kernels compiled with fused multiply-adds (vr_fused.hip)
-namespace vrf {
-bool launch_march(const vr::LaunchDesc& L, hipStream_t s, const vr::MarchBatch& B);
-void launch_shadow_build(const vr::MarchParams& P, float* out, float sigma, bool skip, bool off32, hipStream_t s);
-void launch_slice(const vr::SliceParams& S, int reduce, bool nearest, bool off32, bool skip, unsigned tiles, hipStream_t s);
-}
 
 #include <algorithm>
 #include <cmath>

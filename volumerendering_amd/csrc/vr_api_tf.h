@@ -24,7 +24,7 @@ void mark_reads(vr_ctx* c, const MarchParams& P)
 }
 
 // The distance field for `k` (records of bn bricks) into generation `slot` on `s`: the active bricks, the x, y and z passes
-// (vr_kernels.h), the count and box of build `gen` into h_sum[slot].  F.tmp holds at least bn[0] * bn[1] * bn[2] bytes.
+// (vr_skipfield.h), the count and box of build `gen` into h_sum[slot].  F.tmp holds at least bn[0] * bn[1] * bn[2] bytes.
 int build_field(vr_ctx* c, hipStream_t s, const FieldKey& k, const int bn[3], int slot, unsigned long long gen)
 {
     SkipField& F = c->skip;

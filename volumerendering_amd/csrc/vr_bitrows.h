@@ -8,7 +8,8 @@
 // -0.0f is out), the count and the box of the packed bits come from the popcount and the first / last bit of the words.
 #pragma once
 #include "../../include/vr.h"
-#include "vr_kernels.h"
+#include "vr_device.h"  // DevVolume
+#include "vr_shared.h"  // vr_ballot
 #include "vr_units.h"
 
 namespace vr {

@@ -1,5 +1,5 @@
 // vr_ctx.h -- the context behind the C ABI (struct vr_ctx), the owners of its HIP resources, its error reporting.
-// Part of vr_api.hip's translation unit: included there once, behind vr_launch.h and `using namespace vr`.
+// Part of vr_api.hip's translation unit: included there once, behind the kernel headers and `using namespace vr`.
 #pragma once
 
 // ---- owners: move-only, released by their destructors (vr_destroy drains the device, then deletes the context) ---------------------

@@ -30,7 +30,7 @@ constexpr float kBrickHalf = 0.5f / (float)kBrickCells;   // half a cell in bric
 #endif
 constexpr int kDistMax = VR_DIST_MAX;  // cap of the brick distance field
 // (the builder's x pass sees 128 bricks to either side of a wavefront's 64, and its y / z tiles take 2 x (kDistMax - 1) rows of halo)
-static_assert(kDistMax >= 2 && kDistMax <= 128, "the distance-field builder (vr_kernels.h) is exact for caps up to 128");
+static_assert(kDistMax >= 2 && kDistMax <= 128, "the distance-field builder (vr_skipfield.h) is exact for caps up to 128");
 
 // What a distance-field build reports to the host (pinned memory, written by its last workgroup): the active bricks and their box
 // (brick coordinates, inclusive; hi < 0 if none).  `gen` is written last: the values belong to build `gen` once it reads so.
@@ -252,3 +252,20 @@ struct LaunchDesc {
 };
 
 }  // namespace vr
+
+// The entry points of a march unit (vr_launch.h defines them): all the C ABI's unit sees of the march kernels.  One text for both
+// arithmetic modes -- vr:: in vr_march.hip, vrf:: in vr_fused.hip; the host picks by the context's mode (vr_set_arithmetic).
+//   launch_march         enqueues the kernel of L; false: there is none for this family of this shader, nothing was launched
+//   launch_shadow_build  the light volume of a shadowed launch (P: its parameters, vol[1] = the grid, whose storage is `out`)
+//   launch_slice         a slice view: reduction x filter x addressing x skipping, `tiles` workgroups of one wavefront
+#define VR_MARCH_ENTRY_POINTS                                                                                                          \
+    bool launch_march(const vr::LaunchDesc& L, hipStream_t s, const vr::MarchBatch& B);                                                \
+    void launch_shadow_build(const vr::MarchParams& P, float* out, float sigma, bool skip, bool off32, hipStream_t s);                 \
+    void launch_slice(const vr::SliceParams& S, int reduce, bool nearest, bool off32, bool skip, unsigned tiles, hipStream_t s);
+namespace vr {
+VR_MARCH_ENTRY_POINTS
+}
+namespace vrf {
+VR_MARCH_ENTRY_POINTS
+}
+#undef VR_MARCH_ENTRY_POINTS

@@ -37,6 +37,8 @@
 // Write (grow_write_kernel): component `contour` of the mask voxels with one 4-byte vector store per voxel (the other three components
 // are never read or written), only in bricks with R != 0 unless zeros must be stored; |R| and its box from popcounts of the R words.
 #pragma once
+#include "vr_device.h"  // the argument blocks, BoxUnits
+#include "vr_shared.h"  // vr_ballot
 
 namespace vr {
 

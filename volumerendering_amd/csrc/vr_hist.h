@@ -17,7 +17,7 @@
 // (a) Combining: per row, the lanes that hold the bin of the wavefront's first contributing lane are counted with one ballot and
 //     that lane adds their number; the other contributing lanes add one each.  A wave-uniform unit costs one atomic instead of 64.
 // (b) Exact settling (channel 3, no mask, a unit wholly inside the box): the unit's range record (min .a, max .a) of
-//     brick_range_kernel (vr_proj.h) is read first.  If it is not the flagged (NaN, NaN) record and i(min) == i(max), the unit's 64
+//     brick_range_kernel (vr_prep.h) is read first.  If it is not the flagged (NaN, NaN) record and i(min) == i(max), the unit's 64
 //     voxels are added to that bin -- or to `dropped` -- and nothing is loaded.  This is exact:
 //       - for a fixed finite scale s, v -> fl(v * s) is monotone (non-decreasing for s >= 0, non-increasing for s <= 0: rounding is
 //         monotone), and t -> (int)t is non-decreasing on the finite floats and the infinities a product can overflow to; so
@@ -31,6 +31,8 @@
 // Masks: the mask voxel is loaded first, and the value only where a requested row needs it.  An unmasked channel-3 launch reads the
 // 4-byte density plane when the layout has one (HistParams::val / val_stride address either).
 #pragma once
+#include "vr_device.h"  // the argument blocks, BoxUnits
+#include "vr_shared.h"  // vr_ballot
 
 namespace vr {
 

@@ -6,7 +6,7 @@
 // order, packed tiles, the (frame, packet) items of batched launches).  Included by vr_launch.h once per arithmetic mode.
 //
 // Exact skipping (SKIP, flavour 21): a step whose base cell lies in a brick (brick_of) with record max < iso loads nothing.  The
-// records are the projections' (brick_range_kernel, vr_proj.h): (min .a, max .a) over the voxels the brick's cells can touch, and
+// records are the projections' (brick_range_kernel, vr_prep.h): (min .a, max .a) over the voxels the brick's cells can touch, and
 // vr_proj.h's header shows that a trilinear sample never exceeds the largest of its corners, in either arithmetic mode -- so such a
 // step's density is < iso and it cannot be the hit.  The comparison is strict (a sample equal to the level is a hit), and a flagged
 // (NaN, NaN) record fails it: never skipped.

@@ -1,7 +1,8 @@
 // vr_kernels.h -- hand-written HIP kernels for gfx950 (MI355X / CDNA4): the front-to-back compositing loop
 // of the reference's WGSL fragment shaders, one ray per lane, one 8x8 pixel packet per 64-wide wavefront
-// (march_kernel; vr_dp.h holds the two / four lanes per ray form), plus the
-// auxiliary kernels (brick records and distance field, counters, present, tile unpack, data preparation).
+// (march_kernel; vr_dp.h holds the two / four lanes per ray form).  March code only: the auxiliary kernels (data preparation and
+// brick records vr_prep.h, the skip-field build vr_skipfield.h, counters, launch order, present and tile unpack vr_frame.h) belong
+// to the C ABI's translation unit, and nothing here or behind vr_launch.h includes them.
 //
 // What each piece replaces (paths below the reference root):
 //   setup_ray()      rayCoords.wgsl:19-34 + vertex stage BasicVolumeApp.wgsl:44-57 + rasteriser, proxy box
@@ -11,7 +12,6 @@
 //   march_kernel<V>  fs_main of BasicVolumeApp.wgsl:113-188, BasicVolLightApp.wgsl:151-237,
 //                    VolumeMaskApp.wgsl:128-217, ThreeFilesApp.wgsl:170-272, MultiCTRTApp.wgsl:163-259,
 //                    TFCalibrationApp.wgsl:114-197, MutliCTRTIllustrative.wgsl:227-313
-//   present_kernel   output merge PipelineBuilder.cpp:142-147 over fullscreen.wgsl:33-41 white, BGRA8Unorm
 //
 // Arithmetic contract (DESIGN.md "Normative arithmetic"): IEEE f32, no FMA contraction (-ffp-contract=off),
 // correctly rounded divide and sqrt (hipcc default for HIP), dot = (x*x' + y*y') + z*z',
@@ -21,15 +21,14 @@
 // addition, one step at a time, because start + i*step is not bit-equal to the reference's accumulation.
 #pragma once
 #include "vr_device.h"
+#include "vr_shared.h"  // vr_ballot, wave_lds_fence, mat4_mul_point: what the other unit's kernels use as well
 
 // The kernels are compiled once per arithmetic mode, each in a translation unit and a namespace of its own:
-//   VR_KNS = vr,  VR_FUSED = 0   a * b + c rounds the product and the sum separately (the default normative arithmetic)
+//   VR_KNS = vr,  VR_FUSED = 0   a * b + c rounds the product and the sum separately (the default normative arithmetic; vr_march.hip)
 //   VR_KNS = vrf, VR_FUSED = 1   the per-sample expressions of that shape are single fused multiply-adds (vr_fused.hip)
+// The unit defines both before it includes vr_launch.h.
 #ifndef VR_KNS
-#define VR_KNS vr
-#endif
-#ifndef VR_FUSED
-#define VR_FUSED 0
+#error "the march headers are compiled by vr_march.hip and vr_fused.hip, which name the namespace and the arithmetic mode"
 #endif
 
 namespace VR_KNS {
@@ -95,9 +94,7 @@ __device__ __forceinline__ f3 normalize3s(f3 a)
     float inv = inv_sqrt_exact(dot3s(a, a));
     return mk3(a.x * inv, a.y * inv, a.z * inv);
 }
-// The wavefront's lane mask of a condition.  (HIP's __ballot takes an int: the condition becomes 0 / 1 in a register and is
-// compared again -- v_cndmask + v_cmp and a scalar wait on the vector compare -- where the builtin takes the condition's own mask.)
-__device__ __forceinline__ unsigned long long vr_ballot(bool x) { return __builtin_amdgcn_ballot_w64(x); }
+// (vr_ballot, the wavefront's lane mask of a condition: vr_shared.h)
 __device__ __forceinline__ float max0(float x) { return (x > 0.0f) ? x : 0.0f; }
 __device__ __forceinline__ float lerpf(float a, float b, float t) { return mad(b - a, t, a); }
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
@@ -111,12 +108,7 @@ __device__ __forceinline__ void texel_pair(float x0, int n, int& i0, int& i1)
     i1 = min(max(t + 1, 0), n - 1);
 }
 
-// column-major mat4 * (x,y,z,1), summed left to right
-__device__ __forceinline__ void mat4_mul_point(const float* m, float x, float y, float z, float w, float out[4])
-{
-#pragma unroll
-    for (int r = 0; r < 4; ++r) out[r] = ((m[0 + r] * x + m[4 + r] * y) + m[8 + r] * z) + m[12 + r] * w;
-}
+// (mat4_mul_point, column-major mat4 * (x,y,z,1) summed left to right: vr_shared.h)
 
 // ------------------------------------------------------------------------------------------------ jitter
 // BasicVolumeApp.wgsl:107-110.  sin() is evaluated in f64 (quadrant reduction + Taylor) so that the value is
@@ -1532,587 +1524,5 @@ __global__ __launch_bounds__(256, 1) void march_kernel(const MarchBatch B)
 
     store_block_counts(P, blends, covered, fetched, t_start);
 }
-
-#if !VR_FUSED  // auxiliary kernels (no multiply-adds of the per-sample kind): compiled once, in namespace vr
-// One wavefront per brick of c = kBrickCells cells: maximum of .a over the voxels [c b, min(c b + c, n-1)]^3 (NaN if any
-// voxel is NaN or infinite).
-__global__ __launch_bounds__(64) void brick_max_kernel(const float4* __restrict__ vol, int nx, int ny, int nz, int bnx,
-                                                       int bny, float2* __restrict__ out)
-{
-    const int b = blockIdx.x;
-    const int bx = b % bnx, by = (b / bnx) % bny, bz = b / (bnx * bny);
-    const int x0 = bx << kBrickShift, y0 = by << kBrickShift, z0 = bz << kBrickShift;
-    const int ex = min(kBrickCells + 1, nx - x0), ey = min(kBrickCells + 1, ny - y0), ez = min(kBrickCells + 1, nz - z0);
-    float m = -INFINITY, mc = -INFINITY;
-    bool has_nan = false, has_nan_c = false;
-    for (int t = threadIdx.x; t < ex * ey * ez; t += 64) {
-        int lx = t % ex, ly = (t / ex) % ey, lz = t / (ex * ey);
-        float4 v = vol[((size_t)(z0 + lz) * ny + (y0 + ly)) * nx + (x0 + lx)];
-        // NaN or +-inf: samples next to such a voxel interpolate to NaN (inf * 0, inf - inf) whatever the others hold, and a
-        // NaN density has a NaN opacity: the brick must stay active (a -inf would otherwise just lose the maximum)
-        if (!(v.w - v.w == 0.0f)) has_nan = true;
-        else if (v.w > m) m = v.w;
-        if (v.x != v.x || v.y != v.y || v.z != v.z) has_nan_c = true;
-        else mc = fmaxf(mc, fmaxf(v.x, fmaxf(v.y, v.z)));
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        m = fmaxf(m, __shfl_down(m, off, 64));
-        mc = fmaxf(mc, __shfl_down(mc, off, 64));
-        // (every lane takes part in every shuffle: behind a short-circuiting `||` a lane that has already seen a NaN would
-        // sit the shuffle out, and the lane reading from it would get nothing -- the flag of a NaN found by any lane but
-        // lane 0 was lost that way until round 2, and a brick holding nothing else but that voxel was skipped)
-        const int other = __shfl_down((int)has_nan, off, 64), other_c = __shfl_down((int)has_nan_c, off, 64);
-        has_nan = has_nan || other != 0;
-        has_nan_c = has_nan_c || other_c != 0;
-    }
-    if (threadIdx.x == 0) out[b] = make_float2(has_nan ? NAN : m, has_nan_c ? NAN : mc);
-}
-
-// ------------------------------------------------------------------------------------------------ aux kernels
-__device__ __forceinline__ unsigned unorm8(float v)
-{
-    if (!(v > 0.0f)) v = 0.0f;
-    if (v > 1.0f) v = 1.0f;
-    return (unsigned)floorf(v * 255.0f + 0.5f);
-}
-
-// Output merge over the white background, BGRA8Unorm (PipelineBuilder.cpp:142-147, fullscreen.wgsl:33-41).
-__global__ void present_kernel(const float4* __restrict__ frag, uint32_t* __restrict__ bgra, int n)
-{
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float4 s = frag[i];
-    float a = s.w;
-    float r = s.x * a + 1.0f * (1.0f - a);
-    float g = s.y * a + 1.0f * (1.0f - a);
-    float b = s.z * a + 1.0f * (1.0f - a);
-    float oa = s.w * a + 1.0f * (1.0f - a);
-    bgra[i] = unorm8(b) | (unorm8(g) << 8) | (unorm8(r) << 16) | (unorm8(oa) << 24);
-}
-
-// present_kernel reading the frame THROUGH the tile permutation: the root of the multi-GPU gather presents straight from the
-// gathered, tile-major segments (gathered[r][n][64*64]), no assembled float frame in between (16 B read + 4 B written per
-// pixel instead of an un-permute pass of 16 + 16 and a present pass of 16 + 4).  Same arithmetic as present_kernel.
-__global__ void present_tiles_kernel(const float4* __restrict__ gathered, uint32_t* __restrict__ bgra, int W, int H, int tiles_x,
-                                     int world, int tiles_per_rank_max)
-{
-    int x = blockIdx.x * blockDim.x + threadIdx.x;
-    int y = blockIdx.y * blockDim.y + threadIdx.y;
-    if (x >= W || y >= H) return;
-    int t = (y / kTile) * tiles_x + (x / kTile);
-    int r = t % world, n = t / world;
-    size_t src = ((size_t)r * tiles_per_rank_max + n) * (kTile * kTile) + (y % kTile) * kTile + (x % kTile);
-    float4 s = gathered[src];
-    float a = s.w;
-    float rr = s.x * a + 1.0f * (1.0f - a);
-    float g = s.y * a + 1.0f * (1.0f - a);
-    float b = s.z * a + 1.0f * (1.0f - a);
-    float oa = s.w * a + 1.0f * (1.0f - a);
-    bgra[(size_t)y * W + x] = unorm8(b) | (unorm8(g) << 8) | (unorm8(rr) << 16) | (unorm8(oa) << 24);
-}
-
-// Root side of the image-tile gather: gathered[r][n][64*64] -> frame[y*W+x]
-__global__ void unpack_tiles_kernel(const float4* __restrict__ gathered, float4* __restrict__ frame, int W, int H,
-                                    int tiles_x, int world, int tiles_per_rank_max)
-{
-    int x = blockIdx.x * blockDim.x + threadIdx.x;
-    int y = blockIdx.y * blockDim.y + threadIdx.y;
-    if (x >= W || y >= H) return;
-    int t = (y / kTile) * tiles_x + (x / kTile);
-    int r = t % world, n = t / world;
-    size_t src = ((size_t)r * tiles_per_rank_max + n) * (kTile * kTile) + (y % kTile) * kTile + (x % kTile);
-    frame[(size_t)y * W + x] = gathered[src];
-}
-
-// ... and the same un-permute for tiles that were presented where they were rendered (4 B per pixel: the multi-GPU loop gathers
-// BGRA8 tiles instead of float tiles when only the presented frame is wanted)
-__global__ void unpack_tiles_u32_kernel(const uint32_t* __restrict__ gathered, uint32_t* __restrict__ frame, int W, int H, int tiles_x,
-                                        int world, int tiles_per_rank_max)
-{
-    int x = blockIdx.x * blockDim.x + threadIdx.x;
-    int y = blockIdx.y * blockDim.y + threadIdx.y;
-    if (x >= W || y >= H) return;
-    int t = (y / kTile) * tiles_x + (x / kTile);
-    int r = t % world, n = t / world;
-    size_t src = ((size_t)r * tiles_per_rank_max + n) * (kTile * kTile) + (y % kTile) * kTile + (x % kTile);
-    frame[(size_t)y * W + x] = gathered[src];
-}
-
-// One block: adds the per-block counts of the last march launch up (out[0..2]).
-__global__ __launch_bounds__(256) void sum_block_counts_kernel(const unsigned long long* __restrict__ in, int n_blocks,
-                                                               unsigned long long* __restrict__ out)
-{
-    __shared__ unsigned long long part[4][3];
-    unsigned long long a = 0, b = 0, f = 0;
-    for (int i = threadIdx.x; i < n_blocks; i += 256) {
-        a += in[(size_t)i * kBlockRecord];
-        b += in[(size_t)i * kBlockRecord + 1];
-        f += in[(size_t)i * kBlockRecord + 2];
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        a += __shfl_down(a, off, 64);
-        b += __shfl_down(b, off, 64);
-        f += __shfl_down(f, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        part[threadIdx.x >> 6][0] = a;
-        part[threadIdx.x >> 6][1] = b;
-        part[threadIdx.x >> 6][2] = f;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) out[threadIdx.x] = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
-}
-
-// One wavefront that stays busy for `ticks` of the 100 MHz clock (bounded): vr_stream()'s probe for streams that really
-// run side by side (HIP maps streams onto a few hardware queues; two streams on one queue serialise).
-__global__ __launch_bounds__(64) void spin_kernel(unsigned long long ticks, unsigned* __restrict__ sink)
-{
-    const unsigned long long t0 = wall_clock64();
-    unsigned n = 0;
-    while (wall_clock64() - t0 < ticks && n < 4000000u) {
-        __builtin_amdgcn_s_sleep(8);
-        ++n;
-    }
-    if (sink && threadIdx.x == 0 && n == 0xFFFFFFFFu) *sink = n;  // (never true: keeps the loop observable)
-}
-
-// One workgroup: order[] = the logical blocks of the launch whose records are `in`, sorted by the longest per-ray sample
-// chain of the block (record word 5, bits 40..), longest first, SEPARATELY within each residue class of the block index
-// modulo 8: position b of the order holds a block lb with lb % 8 == b % 8.  Workgroups are dispatched round-robin over the
-// 8 XCDs, so a block stays on the XCD its index maps to (what map_pixel relies on) and every XCD runs its own
-// blocks longest-processing-time-first.  Eight counting sorts over 128 key buckets each (n_blocks % 8 == 0).
-// It also reports how long the launch took: last workgroup end - first workgroup start of the records it reads (100 MHz
-// ticks, to host-visible memory; vr_kernel_times).  Timing events around every launch cost the frame's stream 11 us.
-// pw_heads: the queue heads of the persistent-wavefront launch whose records these are (vr_pw.h) -- cleared here, behind that
-// launch, for the next launch that uses the slot.
-__global__ __launch_bounds__(1024) void order_blocks_kernel(const unsigned long long* __restrict__ in, int n_blocks,
-                                                            unsigned* __restrict__ order, unsigned* __restrict__ longest_chain,
-                                                            unsigned long long* __restrict__ span_ticks,
-                                                            unsigned* __restrict__ pw_heads,
-                                                            unsigned long long* __restrict__ end_tick = nullptr)
-{
-    if (pw_heads != nullptr && threadIdx.x < 8) pw_heads[threadIdx.x * 64] = 0u;
-    __shared__ unsigned hist[1024];  // [class 0..7][bucket 0..127]
-    __shared__ unsigned base[1024];
-    __shared__ unsigned chain_max;
-    __shared__ unsigned long long t_first, t_last;
-    const int t = threadIdx.x;
-    hist[t] = 0;
-    if (t == 0) {
-        chain_max = 0;
-        t_first = ~0ull;
-        t_last = 0ull;
-    }
-    unsigned my_chain = 0;
-    unsigned long long my_first = ~0ull, my_last = 0ull;
-    __syncthreads();
-    // every record is read ONCE (a launch that recycles the record buffer under this kernel can then only change the
-    // order, never make it something other than a permutation); bucket 0 = the longest chains (32 steps per bucket)
-    unsigned short bk[kOrderMaxBlocks / 1024];  // (private memory: the loops are not unrolled)
-    for (int k = 0; k * 1024 < n_blocks; ++k) {
-        const int b = t + k * 1024;
-        if (b < n_blocks) {
-            const unsigned long long crit = in[(size_t)b * kBlockRecord + 5] >> 40;
-            const unsigned long long b0 = in[(size_t)b * kBlockRecord + 3], b1 = in[(size_t)b * kBlockRecord + 4];
-            my_first = b0 < my_first ? b0 : my_first;
-            my_last = b1 > my_last ? b1 : my_last;
-            my_chain = crit > my_chain ? (unsigned)crit : my_chain;
-            const unsigned q = (unsigned)(crit >> 5);
-            bk[k] = (unsigned short)(((unsigned)b & 7u) * 128u + (127u - (q > 127u ? 127u : q)));
-            atomicAdd(&hist[bk[k]], 1u);
-        }
-    }
-    __syncthreads();
-    {   // exclusive prefix sum inside each class: classes are 128 consecutive entries = two wavefronts
-        const unsigned mine = hist[t];
-        unsigned incl = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const unsigned up = (unsigned)__shfl_up((int)incl, off, 64);
-            if ((t & 63) >= off) incl += up;
-        }
-        __shared__ unsigned wave_total[16];
-        if ((t & 63) == 63) wave_total[t >> 6] = incl;
-        __syncthreads();
-        const unsigned before = ((t >> 6) & 1) ? wave_total[(t >> 6) - 1] : 0u;  // the class's first wavefront
-        base[t] = before + incl - mine;
-    }
-    __syncthreads();
-    // the launch's longest ray chain + 1 (0 = not written yet), to host-visible memory: the host's choice of lanes per ray for
-    // a later launch of the same shape reads it without synchronising (vr_api.hip, enqueue_render)
-    if (longest_chain) {
-        atomicMax(&chain_max, my_chain);
-        __syncthreads();
-        if (t == 0) *longest_chain = chain_max + 1u;
-    }
-    if (span_ticks) {
-        // (a launch of several frames: the first frame's records stand for all of them -- the frames' workgroups are
-        // interleaved, so its first start and last end are the launch's to within a few workgroup times)
-        atomicMin(&t_first, my_first);
-        atomicMax(&t_last, my_last);
-        __syncthreads();
-        if (t == 0) {
-            if (end_tick) *end_tick = t_last | 1ull;  // (the last workgroup's end on the device clock; before the span: the host reads the span first)
-            __threadfence_system();
-            *span_ticks = t_last >= t_first ? t_last - t_first + 1ull : 1ull;  // (0 = not written yet)
-        }
-    }
-    // scatter with one cursor per (class, bucket): the i-th block of class x goes to position 8 * i + x
-    for (int k = 0; k * 1024 < n_blocks; ++k) {
-        const int b = t + k * 1024;
-        if (b < n_blocks) order[8u * atomicAdd(&base[bk[k]], 1u) + ((unsigned)b & 7u)] = (unsigned)b;
-    }
-}
-
-// ---- brick distance field (rebuilt when the volume or the opacity table changes) --------------------------------
-// first: 0 for active bricks, 255 for inert ones
-__global__ void brick_active_kernel(const float2* __restrict__ rec, unsigned char* __restrict__ dist, int n, int use_rgb,
-                                    int zero_prefix, int res_o)
-{
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float2 r = rec[i];
-    bool inert;
-    if (use_rgb && !(r.y <= 0.0f)) inert = false;
-    else if (r.x <= 0.0f) inert = zero_prefix >= 0;
-    else inert = floorf(r.x * (float)res_o - 0.5f) + 2.0f <= (float)zero_prefix;
-    dist[i] = inert ? 255 : 0;
-}
-// Then the capped Chebyshev distance, separably: the L-infinity distance to the nearest active brick is
-// d(p) = min_bz max(|dz|, min_by max(|dy|, min_bx |dx|)), so three 1-D passes -- x, y, z -- each h(i) = min_j max(|i - j|, f(j)),
-// capped at kDistMax (no |i - j| >= kDistMax can matter) give min(distance, kDistMax) exactly, kDistMax where nothing is active.
-constexpr int kDistHalo = kDistMax - 1;  // bricks on either side of a pass's tile that can lower a value below the cap
-constexpr int kDistCols = 128;           // y / z passes: bricks along x per tile (128-byte rows)
-constexpr int kDistRows = 64;            // ... and outputs along the pass's axis per tile
-
-// x pass, in place: the input is 0 (active) or 255, the nearest active brick on either side of a brick a bit scan.  One wavefront per
-// 64 bricks of a row, the activity of the 64 + 2 x 128 bricks around them as five ballots (the bytes it overwrites stay zero exactly
-// where they were: the other wavefronts' ballots are unaffected).
-__global__ void brick_dist_x_kernel(unsigned char* __restrict__ dist, int bnx, int rows)
-{
-    const int lane = (int)(threadIdx.x & 63u);
-    const long long segs = (bnx + 63) >> 6, w = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    if (w >= segs * rows) return;  // (wave-uniform)
-    const int x0 = (int)(w % segs) * 64;
-    unsigned char* line = dist + (size_t)(w / segs) * (size_t)bnx;
-    unsigned long long m[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const int x = x0 - 128 + 64 * k + lane;
-        m[k] = vr_ballot(x >= 0 && x < bnx && line[x] == 0);
-    }
-    const unsigned long long le = m[2] & ((2ull << lane) - 1ull), ri = m[2] & ~((1ull << lane) - 1ull);  // (bits <= lane, >= lane)
-    int d = kDistMax;
-    if (le) d = lane - (63 - __clzll((long long)le));
-    else if (m[1]) d = lane + 64 - (63 - __clzll((long long)m[1]));
-    else if (m[0]) d = lane + 128 - (63 - __clzll((long long)m[0]));
-    int e = kDistMax;
-    if (ri) e = __ffsll((long long)ri) - 1 - lane;
-    else if (m[3]) e = 64 + __ffsll((long long)m[3]) - 1 - lane;
-    else if (m[4]) e = 128 + __ffsll((long long)m[4]) - 1 - lane;
-    d = min(min(d, e), kDistMax);
-    if (x0 + lane < bnx) line[x0 + lane] = (unsigned char)d;
-}
-
-// Active-brick count and box of a field (brick coordinates), accumulated by the z pass's workgroups: lo as 0x7fffffff - lo and hi as
-// hi + 1 under atomicMax, so that all zeros is the empty state.  The last workgroup publishes it to pinned host memory, generation last,
-// and zeroes it again for the next build.
-// hlo / hhi: the same for n . b + kHullBias along the ten diagonal directions of the hull (vr_hull.h, kHullDir[3 ..]).
-struct SkipSumDev {
-    unsigned count, done;
-    unsigned lo[3], hi[3];
-    unsigned hlo[kHullDiag], hhi[kHullDiag];
-};
-
-// y and z passes (in -> out, never in place): a tile of kDistCols bricks along x by kDistRows along the pass's axis, with kDistHalo
-// bricks of halo on either side, staged in LDS row by row (every global read a 128-byte row along x); each output scans outwards
-// from its brick until the distance reaches the best value found.  Grid: (x tiles, axis tiles, `other` positions).  LAST (the z
-// pass): the tile's active bricks are counted and boxed -- wavefront, then workgroup in LDS, then one atomic per value -- and the ten
-// diagonals of their hull reduced the same way in a second round.
-template <bool LAST>
-__global__ void __launch_bounds__(256) brick_dist_axis_kernel(const unsigned char* __restrict__ in, unsigned char* __restrict__ out,
-                                                               int bnx, int n_axis, size_t axis_stride, size_t other_stride,
-                                                               SkipSumDev* __restrict__ sum, SkipSummary* __restrict__ host,
-                                                               unsigned long long gen)
-{
-    constexpr int kTileRows = kDistRows + 2 * kDistHalo;
-    __shared__ unsigned char tile[kTileRows][kDistCols];
-    const int t = (int)threadIdx.x;
-    const int x0 = (int)blockIdx.x * kDistCols, a0 = (int)blockIdx.y * kDistRows;
-    const size_t base = (size_t)blockIdx.z * other_stride;
-    for (int idx = t; idx < kTileRows * kDistCols; idx += 256) {
-        const int r = idx / kDistCols, cx = idx % kDistCols, x = x0 + cx, a = a0 - kDistHalo + r;
-        tile[r][cx] = (x < bnx && a >= 0 && a < n_axis) ? in[base + (size_t)a * axis_stride + (size_t)x] : (unsigned char)kDistMax;
-    }
-    __syncthreads();
-    // no output of a column lies below the column's minimum over the tile: a column that holds it stops there (most columns of the y
-    // pass through planes without an active brick are kDistMax throughout and scan nothing)
-    __shared__ unsigned char col_min[kDistCols];
-    if (t < kDistCols) {
-        int m = kDistMax;
-        for (int r = 0; r < kTileRows; ++r) m = min(m, (int)tile[r][t]);
-        col_min[t] = (unsigned char)m;
-    }
-    __syncthreads();
-    const int cx = t % kDistCols, x = x0 + cx, floor_c = col_min[cx];
-    unsigned cnt = 0;
-    int lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {-1, -1, -1};
-    for (int i = t / kDistCols; i < kDistRows; i += 256 / kDistCols) {
-        const int a = a0 + i;
-        if (x >= bnx || a >= n_axis) continue;
-        const int R = i + kDistHalo, reach = max(a, n_axis - 1 - a);
-        int best = tile[R][cx];
-        for (int k = 1; k < best && best > floor_c && k <= reach; ++k) best = min(best, max(k, (int)min(tile[R - k][cx], tile[R + k][cx])));
-        out[base + (size_t)a * axis_stride + (size_t)x] = (unsigned char)best;
-        if constexpr (LAST) {
-            if (best == 0) {
-                const int p[3] = {x, (int)blockIdx.z, a};  // (the z pass: axis z, `other` y)
-                ++cnt;
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    lo[q] = min(lo[q], p[q]);
-                    hi[q] = max(hi[q], p[q]);
-                }
-            }
-        }
-    }
-    if constexpr (LAST) {
-        const unsigned lane_cnt = cnt;  // this lane's own bricks, before the wavefront folds them
-        const int lane_zlo = lo[2], lane_zhi = hi[2];
-        for (int off = 32; off > 0; off >>= 1) {
-            cnt += __shfl_down(cnt, off, 64);
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                lo[q] = min(lo[q], __shfl_down(lo[q], off, 64));
-                hi[q] = max(hi[q], __shfl_down(hi[q], off, 64));
-            }
-        }
-        __shared__ int red[4][7];
-        __shared__ int hred[4][2 * kHullDiag];
-        __shared__ bool last;
-        const int wv = t >> 6;
-        if ((t & 63) == 0) {
-            red[wv][0] = (int)cnt;
-            for (int q = 0; q < 3; ++q) {
-                red[wv][1 + q] = lo[q];
-                red[wv][4 + q] = hi[q];
-            }
-        }
-        // The hull's diagonals, a second round: a lane's bricks share x and y (its column, the workgroup's `other` position), so the
-        // extremes of n . b over them lie at the lane's lowest and highest z, which the box has: nothing per brick, and one direction
-        // at a time through the wavefront (no more registers than the box took).
-        for (int d = 0; d < kHullDiag; ++d) {
-            const int nx = kHullDir[kHullAxes + d][0], ny = kHullDir[kHullAxes + d][1], nz = kHullDir[kHullAxes + d][2];
-            int dlo = 0x7fffffff, dhi = -1;
-            if (lane_cnt != 0) {
-                const int xy = nx * x + ny * (int)blockIdx.z + kHullBias;
-                dlo = xy + nz * (nz > 0 ? lane_zlo : lane_zhi);
-                dhi = xy + nz * (nz > 0 ? lane_zhi : lane_zlo);
-            }
-            for (int off = 32; off > 0; off >>= 1) {
-                dlo = min(dlo, __shfl_down(dlo, off, 64));
-                dhi = max(dhi, __shfl_down(dhi, off, 64));
-            }
-            if ((t & 63) == 0) {
-                hred[wv][d] = dlo;
-                hred[wv][kHullDiag + d] = dhi;
-            }
-        }
-        __syncthreads();
-        if (t == 0) {
-            for (int v = 1; v < 4; ++v) {
-                red[0][0] += red[v][0];
-                for (int q = 0; q < 3; ++q) {
-                    red[0][1 + q] = min(red[0][1 + q], red[v][1 + q]);
-                    red[0][4 + q] = max(red[0][4 + q], red[v][4 + q]);
-                }
-                for (int d = 0; d < kHullDiag; ++d) {
-                    hred[0][d] = min(hred[0][d], hred[v][d]);
-                    hred[0][kHullDiag + d] = max(hred[0][kHullDiag + d], hred[v][kHullDiag + d]);
-                }
-            }
-            if (red[0][0] != 0) {
-                atomicAdd(&sum->count, (unsigned)red[0][0]);
-                for (int q = 0; q < 3; ++q) {
-                    atomicMax(&sum->lo[q], 0x7fffffffu - (unsigned)red[0][1 + q]);
-                    atomicMax(&sum->hi[q], (unsigned)(red[0][4 + q] + 1));
-                }
-                for (int d = 0; d < kHullDiag; ++d) {
-                    atomicMax(&sum->hlo[d], 0x7fffffffu - (unsigned)hred[0][d]);
-                    atomicMax(&sum->hhi[d], (unsigned)(hred[0][kHullDiag + d] + 1));
-                }
-            }
-            __threadfence();
-            last = atomicAdd(&sum->done, 1u) == gridDim.x * gridDim.y * gridDim.z - 1u;
-        }
-        __syncthreads();
-        if (last && t == 0) {
-            __threadfence();
-            volatile SkipSumDev* v = sum;
-            host->count = v->count;
-            for (int q = 0; q < 3; ++q) {
-                host->box[q] = (int)(0x7fffffffu - v->lo[q]);
-                host->box[3 + q] = (int)v->hi[q] - 1;
-            }
-            for (int d = 0; d < kHullDiag; ++d) {  // (meaningless when the count is 0)
-                host->hull_lo[d] = (int)(0x7fffffffu - v->hlo[d]) - kHullBias;
-                host->hull_hi[d] = (int)v->hhi[d] - 1 - kHullBias;
-            }
-            __threadfence_system();
-            host->gen = gen;  // (after the values: the host reads the generation first)
-            v->count = 0;
-            v->done = 0;
-            for (int q = 0; q < 3; ++q) v->lo[q] = v->hi[q] = 0;
-            for (int d = 0; d < kHullDiag; ++d) v->hlo[d] = v->hhi[d] = 0;
-        }
-    }
-}
-
-// VOLUME_MASK looks at two volumes on one grid: record = (max density of the CT, max(r,g,b) of the mask)
-__global__ void merge_bricks_kernel(const float2* __restrict__ density_vol, const float2* __restrict__ mask_vol,
-                                    float2* __restrict__ out, int n)
-{
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = make_float2(density_vol[i].x, mask_vol[i].y);
-}
-
-// ---- bricked copy of a volume (DevVolume::bricked; rebuilt with the brick records after every upload or in-place change) -----
-// One thread per slot of the bricked arrays: slot s = brick * 64 + (lz * 16 + ly * 4 + lx) for the default 4 x 4 x 4 bricks;
-// voxels beyond the volume's faces (the last brick of an axis whose size is not a multiple of the brick edge) are zero and
-// never addressed.
-__global__ void rebrick_kernel(const float4* __restrict__ lin, float4* __restrict__ bvol, float* __restrict__ bdens, int nx, int ny,
-                               int nz, unsigned nbx, unsigned nby, size_t n_slots)
-{
-    size_t s = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (; s < n_slots; s += stride) {
-        const unsigned l = (unsigned)(s & (kVbN - 1u));
-        const size_t b = s >> (3u * kVbS);
-        const unsigned bx = (unsigned)(b % nbx), by = (unsigned)((b / nbx) % nby), bz = (unsigned)(b / ((size_t)nbx * nby));
-        const int x = (int)((bx << kVbS) + (l & kVbM)), y = (int)((by << kVbS) + ((l >> kVbS) & kVbM)), z = (int)((bz << kVbS) + (l >> (2u * kVbS)));
-        float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (x < nx && y < ny && z < nz) v = lin[((size_t)z * ny + y) * nx + x];
-        bvol[s] = v;
-        bdens[s] = v.w;
-    }
-}
-
-// ---- density plane / derived-gradient check (run with the brick records after every upload or in-place change) -------
-__global__ void extract_density_kernel(const float4* __restrict__ vol, float* __restrict__ dens, size_t n)
-{
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (; i < n; i += stride) dens[i] = vol[i].w;
-}
-// *mismatch != 0 afterwards unless EVERY voxel's .rgb has exactly the bits PreComputeGradient(false) computes from the
-// .a plane ((-(p - m)) * 0.5 per axis, neighbours outside the grid = 0; NaNs never match).
-__device__ __forceinline__ float grad_cd(float p, float m) { return (-(p - m)) * 0.5f; }
-__global__ void verify_gradient_kernel(const float4* __restrict__ vol, const float* __restrict__ dens, int nx, int ny, int nz,
-                                       unsigned* __restrict__ mismatch)
-{
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    const int y = blockIdx.y, z = blockIdx.z;
-    bool bad = false;
-    if (x < nx) {
-        const size_t c = ((size_t)z * ny + y) * nx + x;
-        const size_t sy = (size_t)nx, sz = (size_t)nx * ny;
-        const float mx = x > 0 ? dens[c - 1] : 0.0f, px = x + 1 < nx ? dens[c + 1] : 0.0f;
-        const float my = y > 0 ? dens[c - sy] : 0.0f, py = y + 1 < ny ? dens[c + sy] : 0.0f;
-        const float mz = z > 0 ? dens[c - sz] : 0.0f, pz = z + 1 < nz ? dens[c + sz] : 0.0f;
-        const float4 v = vol[c];
-        bad = __float_as_uint(v.x) != __float_as_uint(grad_cd(px, mx)) || __float_as_uint(v.y) != __float_as_uint(grad_cd(py, my)) ||
-              __float_as_uint(v.z) != __float_as_uint(grad_cd(pz, mz)) || v.x != v.x || v.y != v.y || v.z != v.z;
-    }
-    if (vr_ballot(bad) != 0 && (threadIdx.x & 63) == 0) atomicOr(mismatch, 1u);
-}
-
-// ------------------------------------------------------------------------------------------------ data preparation
-//  the reference's single-threaded CPU passes over the voxels, as HBM-bound streaming kernels.
-
-template <typename T>
-__global__ void broadcast_raw_kernel(const T* __restrict__ raw, float4* __restrict__ vol, size_t n)
-{
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (; i < n; i += stride) {
-        float v = (float)raw[i];
-        vol[i] = make_float4(v, v, v, v);
-    }
-}
-
-// out[0] = max over voxels of component `comp` (as f32 bits; values are >= 0 in every use: raw data, magnitudes)
-__global__ void max_component_kernel(const float4* __restrict__ vol, size_t n, int comp, unsigned* __restrict__ out)
-{
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    float m = 0.0f;
-    for (; i < n; i += stride) {
-        float4 v = vol[i];
-        float c = comp == 0 ? v.x : (comp == 1 ? v.y : (comp == 2 ? v.z : v.w));
-        if (m < c) m = c;  // std::max_element semantics of GetMaxNumber: NaNs never win
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_down(m, off, 64));
-    if ((threadIdx.x & 63) == 0) atomicMax(out, __float_as_uint(m));  // non-negative floats order like their bits
-}
-
-__global__ void normalize_kernel(float4* __restrict__ vol, size_t n, int value)
-{
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    const float d = (float)value;
-    for (; i < n; i += stride) {
-        float4 v = vol[i];
-        v.w = v.w / d;
-        vol[i] = v;
-    }
-}
-
-// One thread per voxel, x fastest (coalesced); the density is read from the untouched .w lanes, so the pass can
-// run in place.  max_mag (f32 bits) accumulates the largest |gradient| when requested.
-__global__ void gradient_kernel(float4* __restrict__ vol, int nx, int ny, int nz, int want_max, unsigned* __restrict__ max_mag)
-{
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    const int y = blockIdx.y, z = blockIdx.z;
-    float mag = 0.0f;
-    if (x < nx) {
-        const size_t row = ((size_t)z * ny + y) * nx;
-        const size_t c = row + x;
-        const size_t sy = (size_t)nx, sz = (size_t)nx * ny;
-        float mx = x > 0 ? vol[c - 1].w : 0.0f, px = x + 1 < nx ? vol[c + 1].w : 0.0f;
-        float my = y > 0 ? vol[c - sy].w : 0.0f, py = y + 1 < ny ? vol[c + sy].w : 0.0f;
-        float mz = z > 0 ? vol[c - sz].w : 0.0f, pz = z + 1 < nz ? vol[c + sz].w : 0.0f;
-        float tx = (-(px - mx)) * 0.5f, ty = (-(py - my)) * 0.5f, tz = (-(pz - mz)) * 0.5f;
-        if (want_max) mag = sqrtf((tx * tx + ty * ty) + tz * tz);
-        float* o = reinterpret_cast<float*>(vol + c);
-        o[0] = tx;
-        o[1] = ty;
-        o[2] = tz;
-    }
-    if (want_max) {
-        if (!(mag > 0.0f)) mag = 0.0f;  // `if (mag > maxGradMag)`: NaN never wins
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) mag = fmaxf(mag, __shfl_down(mag, off, 64));
-        if ((threadIdx.x & 63) == 0 && mag > 0.0f) atomicMax(max_mag, __float_as_uint(mag));
-    }
-}
-
-__global__ void scale_gradient_kernel(float4* __restrict__ vol, size_t n, const unsigned* __restrict__ max_mag)
-{
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    const float d = __uint_as_float(*max_mag);
-    for (; i < n; i += stride) {
-        float4 v = vol[i];
-        v.x = v.x / d;
-        v.y = v.y / d;
-        v.z = v.z / d;
-        vol[i] = v;
-    }
-}
-
-#endif  // !VR_FUSED
 
 }  // namespace VR_KNS

@@ -1,7 +1,8 @@
 // vr_launch.h -- picks the instantiation of the march kernels for one launch (variant x addressing x skipping x loop
-// form x lanes per ray).  Included once per arithmetic mode: by vr_api.hip (namespace vr, separately rounded
-// multiply-adds) and by vr_fused.hip (namespace vrf, fused multiply-adds); enqueue_render calls the one the context's
-// arithmetic mode selects (vr_set_arithmetic).
+// form x lanes per ray).  Included once per arithmetic mode: by vr_march.hip (namespace vr, separately rounded
+// multiply-adds) and by vr_fused.hip (namespace vrf, fused multiply-adds), each a translation unit that holds nothing else.  The C
+// ABI's unit (vr_api.hip) sees the three entry points that vr_device.h declares -- launch_march, launch_shadow_build, launch_slice
+// -- and calls the ones of the context's arithmetic mode (vr_set_arithmetic).
 #pragma once
 // march_p2_kernel: the several-frames form also for a launch of ONE frame.  It reads a frame's parameters where it uses them, through
 // a wave-uniform index, and keeps fewer of them in registers: no scratch reload in the pipelined loop, which the one-frame form of the
@@ -221,5 +222,9 @@ bool launch_march(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
         return launch_variant_of(std::make_integer_sequence<int, VR_VARIANT_COUNT>{}, L, s, B);
     }
 }
+
+// The three definitions above are the ones vr_device.h declares: with another signature a definition would be a second overload,
+// and the name's address ambiguous.
+static_assert(sizeof(&launch_march) + sizeof(&launch_shadow_build) + sizeof(&launch_slice) > 0);
 
 }  // namespace VR_KNS

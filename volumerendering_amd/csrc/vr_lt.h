@@ -40,14 +40,7 @@ __device__ __forceinline__ unsigned wave_pk_min_u16(unsigned v)
     return v;
 }
 
-// Orders a wavefront's LDS writes before its following LDS reads of the SAME wave-private region (and the reads of one
-// tile before the next tile load overwrites them).  A wavefront's LDS instructions execute in issue order, so no s_barrier
-// is needed; this only stops the compiler from moving memory operations across it.
-__device__ __forceinline__ void wave_lds_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
+// (wave_lds_fence, which orders a wavefront's LDS writes before its reads of the same wave-private region: vr_shared.h)
 
 constexpr int kLtCap = 480;   // float4 voxels per tile: 7.5 KiB of LDS per wavefront (one wavefront per workgroup, 20 per CU)
 constexpr int kLtSteps = 4;   // steps a tile is planned for

@@ -128,75 +128,4 @@ __global__ __launch_bounds__(64) void march_proj_kernel(const MarchBatch B, cons
     march_shell<BATCH>(B, [&](const MarchParams& P, auto&... a) { proj_packet<MODE, OFF32, SKIP>(P, vrange, a...); });
 }
 
-#if !VR_FUSED  // auxiliary kernels: compiled once, in namespace vr
-// |v| above this (or NaN / inf) flags a range: b - a of two such values may overflow, and the lerp bound above needs it finite
-constexpr float kProjRangeMag = 4.2535296e37f;  // 2^125
-
-// One wavefront per brick of c = kBrickCells cells: (min, max) of .a over the voxels [c b, min(c b + c, n-1)]^3 -- the footprint of
-// brick_max_kernel -- or (NaN, NaN) if any of them is NaN, infinite or above kProjRangeMag in magnitude.
-__global__ __launch_bounds__(64) void brick_range_kernel(const float4* __restrict__ vol, int nx, int ny, int nz, int bnx, int bny,
-                                                         float2* __restrict__ out)
-{
-    const int b = blockIdx.x;
-    const int bx = b % bnx, by = (b / bnx) % bny, bz = b / (bnx * bny);
-    const int x0 = bx << kBrickShift, y0 = by << kBrickShift, z0 = bz << kBrickShift;
-    const int ex = min(kBrickCells + 1, nx - x0), ey = min(kBrickCells + 1, ny - y0), ez = min(kBrickCells + 1, nz - z0);
-    float lo = INFINITY, hi = -INFINITY;
-    int bad = 0;
-    for (int t = threadIdx.x; t < ex * ey * ez; t += 64) {
-        const int lx = t % ex, ly = (t / ex) % ey, lz = t / (ex * ey);
-        const float a = vol[((size_t)(z0 + lz) * ny + (y0 + ly)) * nx + (x0 + lx)].w;
-        if (!(fabsf(a) <= kProjRangeMag)) bad = 1;  // (NaN fails the comparison)
-        else {
-            lo = fminf(lo, a);
-            hi = fmaxf(hi, a);
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {  // (every lane takes part in every shuffle)
-        lo = fminf(lo, __shfl_down(lo, off, 64));
-        hi = fmaxf(hi, __shfl_down(hi, off, 64));
-        bad |= __shfl_down(bad, off, 64);
-    }
-    if (threadIdx.x == 0) out[b] = bad ? make_float2(NAN, NAN) : make_float2(lo, hi);
-}
-
-// One workgroup: (min, max) over the n brick records into *out, (NaN, NaN) if any record is flagged.
-__global__ __launch_bounds__(1024) void range_reduce_kernel(const float2* __restrict__ rec, int n, float2* __restrict__ out)
-{
-    __shared__ float s_lo[16], s_hi[16];
-    __shared__ int s_bad[16];
-    float lo = INFINITY, hi = -INFINITY;
-    int bad = 0;
-    for (int i = threadIdx.x; i < n; i += 1024) {
-        const float2 r = rec[i];
-        if (r.x != r.x || r.y != r.y) bad = 1;
-        else {
-            lo = fminf(lo, r.x);
-            hi = fmaxf(hi, r.y);
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        lo = fminf(lo, __shfl_down(lo, off, 64));
-        hi = fmaxf(hi, __shfl_down(hi, off, 64));
-        bad |= __shfl_down(bad, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s_lo[threadIdx.x >> 6] = lo;
-        s_hi[threadIdx.x >> 6] = hi;
-        s_bad[threadIdx.x >> 6] = bad;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 16; ++w) {
-            lo = fminf(lo, s_lo[w]);
-            hi = fmaxf(hi, s_hi[w]);
-            bad |= s_bad[w];
-        }
-        *out = bad ? make_float2(NAN, NAN) : make_float2(lo, hi);
-    }
-}
-#endif
-
 }  // namespace VR_KNS

@@ -23,7 +23,7 @@
 // skipped.  |R_k| and the boxes from the R_k words.
 #pragma once
 #include "vr_bitrows.h"
-#include "vr_lt.h"  // wave_lds_fence
+#include "vr_shared.h"  // wave_lds_fence
 
 namespace vr {
 

@@ -13,7 +13,7 @@
 // monotone), so a component beyond the face its dn points away from never returns; a NaN component stays NaN.
 //
 // Exact skipping (SKIP) by the sliced slot's range records -- (min .a, max .a) over the (c+1)^3 voxels a brick of c^3 base cells can
-// touch, (NaN, NaN) when flagged (brick_range_kernel, vr_proj.h) -- with vr_proj.h's rules and early exit, whose header proves that a
+// touch, (NaN, NaN) when flagged (brick_range_kernel, vr_prep.h) -- with vr_proj.h's rules and early exit, whose header proves that a
 // brick's range bounds every trilinear sample whose base cell lies in it.
 // NEAREST reads the record of the same brick, the brick of p's BASE cell t = clamp(floor(p * n - 0.5), 0, n - 1) per axis, and that
 // brick bounds the voxel i = clamp(floor(p * n), 0, n - 1) it addresses, because i is t or t + 1 and brick b = t >> 2 covers the voxels
@@ -29,7 +29,7 @@
 // So the voxel's value lies in [rec.x, rec.y], and a flagged record (NaN voxel, infinity) is never skipped.
 //
 // Counters: every wavefront stores its three sums (counted samples, pixels with n > 0, samples loaded) with plain stores;
-// slice_sum_kernel adds them up when vr_slice_counters asks.
+// slice_sum_kernel (vr_frame.h) adds them up when vr_slice_counters asks.
 #pragma once
 
 namespace VR_KNS {
@@ -82,7 +82,7 @@ __device__ __forceinline__ float slice_value(const Fetch1& q, float fx, float fy
     else return interp_a(q, fx, fy, fz);
 }
 
-// present_kernel's arithmetic (vr_kernels.h) on one fragment
+// present_kernel's arithmetic (vr_frame.h) on one fragment
 __device__ __forceinline__ unsigned slice_unorm8(float v)
 {
     if (!(v > 0.0f)) v = 0.0f;
@@ -185,36 +185,5 @@ __global__ __launch_bounds__(64) void slice_kernel(const SliceParams S)
         o[2] = cf;
     }
 }
-
-#if !VR_FUSED  // auxiliary kernel: compiled once, in namespace vr
-// One workgroup: adds the n wavefront records of a slice launch up (out[0..2]).
-__global__ __launch_bounds__(1024) void slice_sum_kernel(const unsigned long long* __restrict__ in, unsigned n, unsigned long long* __restrict__ out)
-{
-    __shared__ unsigned long long part[16][3];
-    unsigned long long a = 0, b = 0, f = 0;
-    for (unsigned i = threadIdx.x; i < n; i += 1024u) {
-        a += in[(size_t)i * 3];
-        b += in[(size_t)i * 3 + 1];
-        f += in[(size_t)i * 3 + 2];
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        a += __shfl_down(a, off, 64);
-        b += __shfl_down(b, off, 64);
-        f += __shfl_down(f, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        part[threadIdx.x >> 6][0] = a;
-        part[threadIdx.x >> 6][1] = b;
-        part[threadIdx.x >> 6][2] = f;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        unsigned long long s = 0;
-        for (int w = 0; w < 16; ++w) s += part[w][threadIdx.x];
-        out[threadIdx.x] = s;
-    }
-}
-#endif
 
 }  // namespace VR_KNS

@@ -17,7 +17,7 @@
 // The loop issues the corner loads of the next step before it waits for this step's opacity texels, and looks each distance-field
 // byte up two steps ahead, so that waiting for a byte never waits for the corners still in flight (loads complete in order).
 //
-// surface_depth_kernel (vr_surface_depth_async): one lane per pixel, the depth a rasteriser drawing at q would write.
+// (The depth a rasteriser drawing at q would write, vr_surface_depth_async: surface_depth_kernel, vr_frame.h.)
 #pragma once
 
 namespace VR_KNS {
@@ -122,28 +122,5 @@ __global__ __launch_bounds__(64) void march_surf_kernel(const MarchBatch B)
 {
     march_shell<BATCH>(B, [](auto&... a) { surf_packet<OFF32, SKIP>(a...); });
 }
-
-#if !VR_FUSED
-// Depth of a surface frame (vr_surface_depth_async): .w > tau false -> 1.0f; else q -> world (the inverse of setup_ray's
-// world-to-uvw map) -> eye -> clip with the ray set-up's matrix product (separately rounded), depth = clip.z / clip.w.
-struct DepthParams {
-    float view[16], proj[16];
-    float tau;
-};
-__global__ __launch_bounds__(256) void surface_depth_kernel(const float4* __restrict__ surf, float* __restrict__ depth, int n, const DepthParams D)
-{
-    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (i >= n) return;
-    const float4 s = surf[i];
-    float z = 1.0f;
-    if (s.w > D.tau) {
-        float e[4], c[4];
-        mat4_mul_point(D.view, s.x - 0.5f, s.y - 0.5f, (0.5f - s.z) * 0.5f, 1.0f, e);
-        mat4_mul_point(D.proj, e[0], e[1], e[2], e[3], c);
-        z = c[2] / c[3];
-    }
-    depth[i] = z;
-}
-#endif
 
 }  // namespace VR_KNS
