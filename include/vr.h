@@ -1181,7 +1181,8 @@ int vr_outlines_timing(vr_ctx* ctx, float ms[4]);
  *   Label map (label_slot >= 0): for every voxel of the box, component label_channel of label_slot becomes (float)label inside S and
  *     +0.0f outside S -- the labels of ALL components, not only the selected ones.  Everything else keeps its bits.  If a label map is
  *     asked for and n_components > VR_COMP_MAX_LABEL (labels are stored as f32: exact up to there) the call returns VR_ERR_UNSUPPORTED
- *     and nothing is written.
+ *     and nothing is written: neither the label map nor the contour nor the table, and an empty destination slot stays empty.  The
+ *     result is filled all the same, as for a table that is too small, and vr_last_error names n_components.
  *   One slot per call: if both a contour and a label map are asked for they must lie in the same slot and in different components,
  *     else VR_ERR_INVALID_ARG.  An empty destination slot is created zeroed with the source's dimensions; a slot of other dimensions is
  *     VR_ERR_INVALID_ARG.  With neither, the call writes no slot and rebuilds nothing, like vr_mask_outlines.

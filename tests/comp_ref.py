@@ -93,6 +93,31 @@ def table(labels, n, box_lo):
     return out
 
 
+def table_arrays(labels, n, box_lo):
+    """table() as five arrays, for masks with a million components: (voxels int64[n], lo int64[n, 3], hi int64[n, 3], first int64[n, 3],
+    faces int64[n]), the triples (x, y, z).  No loop over components: the set voxels are sorted by label, stably, so each component's
+    voxels stand together in raster order, its first in front, and every column is one reduction over those segments."""
+    shape = labels.shape
+    if n == 0:
+        return np.zeros(0, np.int64), np.zeros((0, 3), np.int64), np.zeros((0, 3), np.int64), np.zeros((0, 3), np.int64), np.zeros(0, np.int64)
+    flat = np.flatnonzero(labels)
+    c = labels.ravel()[flat] - 1
+    order = np.argsort(c, kind="stable")
+    voxels = np.bincount(c, minlength=n).astype(np.int64)
+    assert voxels.min() > 0
+    starts = np.concatenate(([0], np.cumsum(voxels)[:-1]))
+    zyx = np.unravel_index(flat[order], shape)
+    lo, hi, first = np.zeros((n, 3), np.int64), np.zeros((n, 3), np.int64), np.zeros((n, 3), np.int64)
+    faces = np.zeros(n, np.int64)
+    for a, (v, m) in enumerate(zip(zyx[::-1], shape[::-1])):
+        v = v.astype(np.int64)
+        lo[:, a] = np.minimum.reduceat(v, starts) + box_lo[a]
+        hi[:, a] = np.maximum.reduceat(v, starts) + 1 + box_lo[a]
+        first[:, a] = v[starts] + box_lo[a]
+        faces |= np.bitwise_or.reduceat(np.where(v == 0, 1 << (2 * a), 0) | np.where(v == m - 1, 2 << (2 * a), 0), starts)
+    return voxels, lo, hi, first, faces
+
+
 def select(tab, min_voxels=1, max_voxels=U64_MAX, reject_faces=0, keep_largest=0):
     """The 0-based numbers of the selected components, ascending."""
     ok = [i for i, t in enumerate(tab) if min_voxels <= t[0] <= max_voxels and not (t[4] & reject_faces)]

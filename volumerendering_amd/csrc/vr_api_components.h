@@ -77,7 +77,8 @@ void comp_winners(const std::vector<unsigned long long>& pass, unsigned keep, Co
 
 // The call itself, every argument checked and the device drained.  dst: the written slot's voxels, nullptr when no slot is written;
 // `fresh`: they were allocated and zeroed by this call.  Records report.ev[0 .. 3] before it returns VR_OK, or VR_ERR_INVALID_ARG for a
-// table that is too small (*counted = true: the result is filled).
+// table that is too small, or VR_ERR_UNSUPPORTED for a label map of more than VR_COMP_MAX_LABEL components (*counted = true: the result
+// is filled, nothing is written).
 int run_components(vr_ctx* c, const vr_components_desc& d, float4* dst, bool fresh, vr_components_result* result, bool* counted)
 {
     CompState& K = c->comp;
@@ -154,8 +155,6 @@ int run_components(vr_ctx* c, const vr_components_desc& d, float4* dst, bool fre
     VR_HIP(c, hipStreamSynchronize(s));
     const unsigned long long ncomp = hw.components;
     K.report.counters[0] = box, K.report.counters[1] = nodes, K.report.counters[2] = hw.pairs;
-    if (want_labels && ncomp > VR_COMP_MAX_LABEL)
-        return fail(c, VR_ERR_UNSUPPORTED, "vr_mask_components: a label map of " + std::to_string(ncomp) + " components (labels are f32: at most 2^24)");
 
     // the statistics, the selection
     if (ncomp != 0) {
@@ -196,6 +195,10 @@ int run_components(vr_ctx* c, const vr_components_desc& d, float4* dst, bool fre
         VR_HIP(c, hipEventRecord(K.report.ev[3], s));
         return fail(c, VR_ERR_INVALID_ARG, "vr_mask_components: the mask has " + std::to_string(ncomp) + " components, the table holds " +
                                                std::to_string(d.max_components));
+    }
+    if (want_labels && ncomp > VR_COMP_MAX_LABEL) {
+        VR_HIP(c, hipEventRecord(K.report.ev[3], s));
+        return fail(c, VR_ERR_UNSUPPORTED, "vr_mask_components: a label map of " + std::to_string(ncomp) + " components (labels are f32: at most 2^24)");
     }
 
     // the writes, the copy back
