@@ -1256,6 +1256,101 @@ int vr_components_counters(vr_ctx* ctx, uint64_t out[3]);
  * call and after one that failed. */
 int vr_components_timing(vr_ctx* ctx, float ms[4]);
 
+/* ---- resampling: the values of one volume slot on the grid of another --------------------------------------------------------
+ * vr_volume_resample writes selected components of a destination slot, over a voxel box, with values sampled from a source slot at
+ * positions an affine map gives -- a dose grid brought onto the CT's, a second series or a registered prior onto the current study's
+ * grid, a structure onto the dose grid -- on the device (csrc/vr_resample.h).  Every tool that takes a second slot "of the same
+ * dimensions" (the mask rows of vr_histogram, the probe of vr_mask_distance, ...) works on the result.
+ *   Position.  Destination voxel (i, j, k) of the box lies at the SOURCE TEXTURE COORDINATE, per component,
+ *       p = ((origin + (float)i * di) + (float)j * dj) + (float)k * dk
+ *     VR_ARITH_SEPARATE: every product and every sum is rounded.  VR_ARITH_FUSED: the three multiply-adds are fused,
+ *     p = fma((float)k, dk, fma((float)j, dj, fma((float)i, di, origin))).  vr_set_arithmetic selects the mode, as for the samples.
+ *   Inside.  A voxel is INSIDE iff 0 <= p <= 1 on all three components (a NaN component is outside): the slice views' test.
+ *   Stored value, per selected component c (bit c of `channels`):
+ *     inside, VR_RESAMPLE_LINEAR   textureSample(src, linear, p).c: the clamp-to-edge texel pairs of p * n - 0.5 and seven lerps
+ *                                  (x, then y, then z), a + (b - a) * t each, in the arithmetic mode -- what the shaders sample
+ *     inside, VR_RESAMPLE_NEAREST  component c of voxel clamp((int)floor(p * n), 0, n - 1) per axis, its bits unchanged
+ *     outside                      outside[c]
+ *   What keeps its bits: the components that are not selected, and every voxel outside the box.  The destination is never read.
+ *   The uniforms, tables and viewport play no part.
+ * Destination slot: an empty dst_slot is created with the dimensions dst_n, every component +0.0f; a filled one must have exactly
+ * dst_n.  The call gathers, so src_slot == dst_slot is VR_ERR_INVALID_ARG.
+ * Result: inside / outside count the voxels of the box; lo / hi are the half-open bounding box of the inside voxels (destination
+ * voxel coordinates), all zero when there are none.
+ * Gradients: where .rgb of the source holds gradients, an affine map does not rotate them -- the components are interpolated as the
+ * scalars they are stored as.  Resample component 3 alone (channels = 8), then vr_volume_precompute_gradient on the destination.
+ * Kernel forms: vr_set_kernel_flavour(1) runs the plain form -- every voxel of the box is positioned and tested, every inside voxel
+ * loads the corners of its vec4 voxels.  Every other flavour runs the default form: a wavefront (64 voxels along x) whose voxels are
+ * all outside stores `outside` without an address; with channels == 8 the corners are read from the density plane, and, LINEAR,
+ * a wavefront whose inside voxels all lie in bricks of ONE value -- by the source's per-brick range records of .a, built on the
+ * call's stream when the source changed since they were built -- stores that value without a load (a brick of zeros of either
+ * sign gives +0.0f, as the lerps do; csrc/vr_resample.h has the argument).  The destination, the result and out[0] are bit-identical
+ * across the forms and the volume layouts.
+ *   Counters (vr_resample_counters), out[1] + out[2] == out[0] always: out[0] = voxels of the box; out[1] = voxels for which source
+ *   voxels were loaded; out[2] = voxels stored without a load (plain form: exactly the outside voxels). */
+#define VR_RESAMPLE_LINEAR 0
+#define VR_RESAMPLE_NEAREST 1
+typedef struct vr_resample_desc {
+    int32_t src_slot, dst_slot;    /* two different slots                                                                      */
+    uint32_t channels;             /* 1 .. 15; bit c: component c of dst is written from component c of src                    */
+    int32_t filter;                /* VR_RESAMPLE_LINEAR / VR_RESAMPLE_NEAREST                                                 */
+    int32_t dst_n[3];              /* nx, ny, nz of the destination grid, 1 .. 65535                                           */
+    float origin[3], di[3], dj[3], dk[3];
+    float outside[4];              /* per component: stored where p is not inside the source                                   */
+    int32_t box_lo[3], box_hi[3];  /* destination voxel box, half open                                                         */
+} vr_resample_desc;
+typedef struct vr_resample_result {
+    uint64_t inside, outside;
+    int32_t lo[3], hi[3];
+} vr_resample_result;
+/* A voxel grid in patient space: n voxels per axis, `origin` the centre of voxel (0,0,0), `spacing` the pitch per axis, one unit. */
+typedef struct vr_grid {
+    int32_t n[3];
+    double origin[3];
+    double spacing[3];
+} vr_grid;
+
+/* Fills *out for the identity: dst_n = the dimensions (nx, ny, nz) of src_slot, origin = (0.5f / (float)nx, 0.5f / (float)ny,
+ * 0.5f / (float)nz), di = (1.0f / (float)nx, 0, 0), dj = (0, 1.0f / (float)ny, 0), dk = (0, 0, 1.0f / (float)nz) -- voxel centres,
+ * vr_slice_orthogonal's expressions --, channels = 15, outside = 0, the whole box.  Where every dimension is a power of two the
+ * positions are exact and the descriptor reproduces finite source values bit for bit with either filter; elsewhere LINEAR differs
+ * from the source in the last bits.  Pure host arithmetic; VR_ERR_INVALID_ARG for a NULL pointer, a slot out of range, equal slots
+ * or an unknown filter, VR_ERR_NOT_READY for an empty source slot. */
+int vr_resample_identity(const vr_ctx* ctx, int src_slot, int dst_slot, int filter, vr_resample_desc* out);
+
+/* Fills dst_n, origin, di, dj, dk and the whole box of *out -- and nothing else of it -- for destination grid `dst` sampled from
+ * source grid `src`; dst_to_src is a row-major 3 x 4 affine map (M | t) from destination patient coordinates to source patient
+ * coordinates, NULL = the identity.  Pure host arithmetic in double, IEEE operations in exactly this order, for a = 0, 1, 2 (row a of
+ * the map is m = dst_to_src + 4 a; the identity has m[a] = 1.0 and zeros elsewhere):
+ *     s_a       = 1.0 / (src->spacing[a] * (double)src->n[a])
+ *     v_a       = ((((m[0] * dst->origin[0]) + (m[1] * dst->origin[1])) + (m[2] * dst->origin[2])) + m[3]) - src->origin[a]
+ *     origin[a] = (float)((v_a * s_a) + (0.5 / (double)src->n[a]))
+ *     di[a]     = (float)((m[0] * dst->spacing[0]) * s_a)
+ *     dj[a]     = (float)((m[1] * dst->spacing[1]) * s_a)
+ *     dk[a]     = (float)((m[2] * dst->spacing[2]) * s_a)
+ * -- origin = A (M o_dst + t - o_src) + 0.5 / n_src, di = A M e_x spacing_dst[0], ... with A = diag(1 / (spacing_src[a] n_src[a])),
+ * each of the twelve numbers rounded to float once.  Needs no context.  VR_ERR_INVALID_ARG: a NULL src, dst or out; an n outside
+ * 1 .. 65535; a spacing that is not finite and > 0; a matrix entry that is not finite. */
+int vr_resample_between(const vr_grid* src, const vr_grid* dst, const double dst_to_src[12], vr_resample_desc* out);
+
+/* Does the work; `result` may be NULL.  A data-preparation call like vr_mask_morph: it waits for everything in flight, runs on the
+ * ctx's own stream, rebuilds everything derived from the destination slot as an upload does, and is synchronous on return.  It leaves
+ * what the reporting calls say about earlier launches and tools as it was.  An empty box is valid and writes nothing (an empty
+ * destination slot is still created).  Everything is checked before anything is enqueued or a slot is touched.
+ * VR_ERR_INVALID_ARG: a NULL ctx or descriptor; a slot out of range; src_slot == dst_slot; channels 0 or above 15; an unknown
+ * filter; a dst_n outside 1 .. 65535 (or more than 2^32 voxels in all, as for an upload); a filled destination of other dimensions;
+ * a box that is not 0 <= lo <= hi <= dst_n on every axis.  No value of origin, di, dj, dk or outside is an error.
+ * VR_ERR_NOT_READY: the source slot is empty.  VR_ERR_OOM: the destination or the working buffers could not be allocated. */
+int vr_volume_resample(vr_ctx* ctx, const vr_resample_desc* desc, vr_resample_result* result);
+
+/* Counters of the last vr_volume_resample that got as far as counting (as described above).  Zeros before the first. */
+int vr_resample_counters(vr_ctx* ctx, uint64_t out[3]);
+
+/* Device time of the last vr_volume_resample in milliseconds, from events on the ctx's stream: ms[0] the preparation (the source's
+ * range records, where they had to be built), ms[1] the resample kernel, ms[2] the result words, ms[3] the rebuild of what is derived
+ * from the destination slot.  Zeros before the first call and after one that failed. */
+int vr_resample_timing(vr_ctx* ctx, float ms[4]);
+
 /* Volume layout in HBM (A/B measurements; frames and counts are bit-identical in every mode).
  *   0  default: the march kernels gather from a BRICKED copy of every slot -- the vec4 voxels and a scalar f32 density plane
  *      (what fetches that consume .a alone read: BasicVolumeApp.wgsl:171, the density / dose fetches of the other shaders)

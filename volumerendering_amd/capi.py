@@ -48,6 +48,7 @@ POLY_MAX_COORD, POLY_MAX_SPACING = 1 << 29, 1 << 20                         # of
 OUTLINE_SPLIT, OUTLINE_JOIN = 0, 1                                          # vr_outlines_desc.connect (include/vr.h)
 COMP_FACES, COMP_ALL, COMP_PLANE_FACES, COMP_PLANE_ALL = 6, 26, 4, 8              # vr_components_desc.connectivity (include/vr.h)
 COMP_MAX_KEEP, COMP_MAX_LABEL = 64, 1 << 24                                 # of keep_largest; of n_components with a label map
+RESAMPLE_LINEAR, RESAMPLE_NEAREST = 0, 1                                    # vr_resample_desc.filter (include/vr.h)
 DIST_MAX_SPACING, DIST_MAX_LIMIT, DIST_MAX_EXTENT = 1 << 20, 1 << 31, 1 << 30  # of a spacing, the limit, (hi - lo) * spacing per axis
 
 # every symbol include/vr.h declares (tests check that the library exports each of them)
@@ -73,6 +74,7 @@ ABI_SYMBOLS = [
     "vr_polygons_whole", "vr_mask_polygons", "vr_polygons_counters", "vr_polygons_timing",
     "vr_outlines_whole", "vr_mask_outlines", "vr_outlines_counters", "vr_outlines_timing",
     "vr_components_whole", "vr_mask_components", "vr_components_counters", "vr_components_timing",
+    "vr_resample_identity", "vr_resample_between", "vr_volume_resample", "vr_resample_counters", "vr_resample_timing",
 ]
 
 
@@ -364,6 +366,49 @@ class ComponentsResult(C.Structure):
                 tuple(int(x) for x in self.lo), tuple(int(x) for x in self.hi))
 
 
+class ResampleDesc(C.Structure):
+    """struct vr_resample_desc (include/vr.h): the source and destination slots, the components written, the filter, the destination
+    grid, the affine map of its voxels into the source's texture space, the values stored outside the source and the voxel box."""
+    _fields_ = [
+        ("src_slot", C.c_int32), ("dst_slot", C.c_int32), ("channels", C.c_uint32), ("filter", C.c_int32), ("dst_n", C.c_int32 * 3),
+        ("origin", C.c_float * 3), ("di", C.c_float * 3), ("dj", C.c_float * 3), ("dk", C.c_float * 3), ("outside", C.c_float * 4),
+        ("box_lo", C.c_int32 * 3), ("box_hi", C.c_int32 * 3),
+    ]
+
+    def copy(self, **over) -> "ResampleDesc":
+        """A copy with the given fields replaced (dst_n / box_lo / box_hi from any sequence of three integers, origin / di / dj / dk
+        from three floats, outside from four)."""
+        d = ResampleDesc.from_buffer_copy(bytes(self))
+        for k, v in over.items():
+            if k in ("dst_n", "box_lo", "box_hi"):
+                v = (C.c_int32 * 3)(*[int(x) for x in v])
+            if k in ("origin", "di", "dj", "dk"):
+                v = (C.c_float * 3)(*[float(x) for x in v])
+            if k == "outside":
+                v = (C.c_float * 4)(*[float(x) for x in v])
+            setattr(d, k, v)
+        return d
+
+
+class ResampleResult(C.Structure):
+    """struct vr_resample_result: the inside and outside voxels of the box, the half-open bounding box of the inside ones (zeros
+    when there are none)."""
+    _fields_ = [("inside", C.c_uint64), ("outside", C.c_uint64), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3)]
+
+    def as_tuple(self):
+        return int(self.inside), int(self.outside), tuple(int(x) for x in self.lo), tuple(int(x) for x in self.hi)
+
+
+class Grid(C.Structure):
+    """struct vr_grid: n voxels per axis, the centre of voxel (0, 0, 0) and the pitch per axis in patient space, one unit."""
+    _fields_ = [("n", C.c_int32 * 3), ("origin", C.c_double * 3), ("spacing", C.c_double * 3)]
+
+    @classmethod
+    def of(cls, n, origin, spacing) -> "Grid":
+        return cls((C.c_int32 * 3)(*[int(x) for x in n]), (C.c_double * 3)(*[float(x) for x in origin]),
+                   (C.c_double * 3)(*[float(x) for x in spacing]))
+
+
 class VrError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"vr error {code}: {msg}")
@@ -476,6 +521,11 @@ def load() -> C.CDLL:
     lib.vr_mask_components.argtypes = [vp, C.POINTER(ComponentsDesc), C.POINTER(ComponentsResult)]
     lib.vr_components_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
     lib.vr_components_timing.argtypes = [vp, C.POINTER(C.c_float * 4)]
+    lib.vr_resample_identity.argtypes = [vp, i32, i32, i32, C.POINTER(ResampleDesc)]
+    lib.vr_resample_between.argtypes = [C.POINTER(Grid), C.POINTER(Grid), C.POINTER(C.c_double * 12), C.POINTER(ResampleDesc)]
+    lib.vr_volume_resample.argtypes = [vp, C.POINTER(ResampleDesc), C.POINTER(ResampleResult)]
+    lib.vr_resample_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
+    lib.vr_resample_timing.argtypes = [vp, C.POINTER(C.c_float * 4)]
     lib.vr_present_async.argtypes = [vp, vp, vp, vp]
     lib.vr_present_tiles_async.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
     lib.vr_hint_frames_in_flight.argtypes = [vp, i32]
@@ -984,6 +1034,31 @@ class Context:
         """(pack, runs + scan + merge + flatten, numbering .. copy back, refresh) of the last mask_components in ms of device time."""
         return self._tool_timing(self.lib.vr_components_timing)
 
+    def resample_identity(self, src_slot: int, dst_slot: int, filter: int = RESAMPLE_LINEAR) -> ResampleDesc:
+        """vr_resample_identity: the descriptor that puts voxel centres on voxel centres of src_slot's own grid (all four components,
+        outside = 0, the whole box)."""
+        d = ResampleDesc()
+        self._chk(self.lib.vr_resample_identity(self.h, src_slot, dst_slot, filter, C.byref(d)))
+        return d
+
+    def resample_between(self, src: Grid, dst: Grid, dst_to_src=None, **over) -> ResampleDesc:
+        """vr_resample_between: the grid fields of a descriptor for `dst` sampled from `src` (resample_between below); needs no device."""
+        return resample_between(src, dst, dst_to_src, **over)
+
+    def volume_resample(self, desc: ResampleDesc) -> ResampleResult:
+        """vr_volume_resample: writes components of the destination slot with values sampled from the source slot (synchronous)."""
+        out = ResampleResult()
+        self._chk(self.lib.vr_volume_resample(self.h, C.byref(desc), C.byref(out)))
+        return out
+
+    def resample_counters(self):
+        """(voxels of the box, voxels whose source voxels were loaded, voxels stored without a load) of the last volume_resample."""
+        return self._tool_counters(self.lib.vr_resample_counters)
+
+    def resample_timing(self):
+        """(range records, kernel, result words, refresh) of the last volume_resample in ms of device time (vr_resample_timing)."""
+        return self._tool_timing(self.lib.vr_resample_timing)
+
     def set_volume_layout(self, mode: int):
         """0 bricked copy (default), 1 the reference's vec4 voxels only, 3 x-fastest voxels + density plane (2 was removed)."""
         self._chk(self.lib.vr_set_volume_layout(self.h, mode))
@@ -1031,3 +1106,15 @@ def dist_whole(ctx: "Context", src_slot: int, src_contour: int, dst_slot: int, d
     d = DistDesc()
     ctx._chk(ctx.lib.vr_dist_whole(ctx.h, src_slot, src_contour, dst_slot, dst_channel, mode, C.byref(d)))
     return d
+
+
+def resample_between(src: Grid, dst: Grid, dst_to_src=None, **over) -> ResampleDesc:
+    """vr_resample_between: dst_n, origin, di, dj, dk and the whole box of a descriptor for destination grid `dst` sampled from source
+    grid `src`; dst_to_src: twelve numbers, the row-major 3 x 4 map from destination to source patient coordinates (None = identity).
+    The other fields are zero unless given in `over` (as ResampleDesc.copy takes them).  Host arithmetic: needs no context."""
+    d = ResampleDesc()
+    m = None if dst_to_src is None else (C.c_double * 12)(*[float(x) for x in np.asarray(dst_to_src, np.float64).ravel()])
+    rc = load().vr_resample_between(C.byref(src), C.byref(dst), None if m is None else C.byref(m), C.byref(d))
+    if rc != VR_OK:
+        raise VrError(rc, "vr_resample_between: a grid size outside 1 .. 65535, a spacing that is not finite and > 0, or a matrix entry that is not finite")
+    return d.copy(**over)

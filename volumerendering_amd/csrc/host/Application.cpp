@@ -213,6 +213,35 @@ int Application::DistanceMm(int srcSlot, int srcContour, int dstSlot, int dstCha
     return DistanceMap(d, out);
 }
 
+int Application::ResampleOnto(const VolumeFileDcm& src, int srcSlot, const VolumeFileDcm& grid, int dstSlot, uint32_t channels, int filter,
+                              const float outside[4], vr_resample_result* out, const double dstToSrc[12])
+{
+    if (!p_Ctx) return VR_ERR_NOT_READY;
+    if (!outside) return VR_ERR_INVALID_ARG;
+    auto gridOf = [](const VolumeFileDcm& f) {
+        const DicomVolumeParams p = f.GetVolumeParams();
+        const auto [x, y, z] = f.GetSize();
+        vr_grid g;
+        g.n[0] = (int32_t)x, g.n[1] = (int32_t)y, g.n[2] = (int32_t)z;
+        for (int a = 0; a < 3; ++a) g.origin[a] = p.ImagePositionPatient[a];
+        g.spacing[0] = p.PixelSpacing[0], g.spacing[1] = p.PixelSpacing[1], g.spacing[2] = p.SliceThickness;
+        return g;
+    };
+    const vr_grid gs = gridOf(src), gd = gridOf(grid);
+    vr_resample_desc d;
+    int rc = vr_resample_identity(p_Ctx, srcSlot, dstSlot, filter, &d);  // (the slots, the filter, and the size srcSlot holds)
+    if (rc != VR_OK) return rc;
+    for (int a = 0; a < 3; ++a)
+        if (d.dst_n[a] != gs.n[a]) return VR_ERR_INVALID_ARG;
+    rc = vr_resample_between(&gs, &gd, dstToSrc, &d);
+    if (rc != VR_OK) return rc;
+    d.channels = channels;
+    for (int k = 0; k < 4; ++k) d.outside[k] = outside[k];
+    rc = vr_volume_resample(p_Ctx, &d, out);
+    if (rc != VR_OK) m_Error = vr_last_error(p_Ctx);
+    return rc;
+}
+
 int Application::RasterPolygons(const vr_polygons_desc& desc, vr_polygons_result* out)
 {
     if (!p_Ctx) return VR_ERR_NOT_READY;

@@ -86,6 +86,17 @@ public:
     // is not positive, or a volume longer than 2^30 micrometres on some axis.
     int DistanceMm(int srcSlot, int srcContour, int dstSlot, int dstChannel, int mode, float limitMm, const VolumeFileDcm& grid,
                    vr_dist_result* out);
+    // Volume srcSlot, which holds `src`, resampled onto the voxel grid of `grid` into volume dstSlot (vr_resample_between +
+    // vr_volume_resample of include/vr.h): a dose onto the CT's grid, a second series onto the first's, a structure onto the dose grid.
+    // Both grids in patient millimetres from GetVolumeParams() and GetSize(): ImagePositionPatient is the centre of voxel (0, 0, 0),
+    // PixelSpacing x / y and SliceThickness the pitch -- the convention of Create3DMask and ContoursToMask.  channels: bit c =
+    // component c is written; filter = VR_RESAMPLE_LINEAR / VR_RESAMPLE_NEAREST; outside[4] is stored where a voxel of `grid` lies
+    // outside `src`.  dstToSrc: a row-major 3 x 4 map from `grid`'s patient coordinates to `src`'s (a rigid registration's result),
+    // nullptr = the identity: one frame of reference.  An empty dstSlot is created on `grid`'s size.  `out` may be nullptr.
+    // VR_ERR_INVALID_ARG when srcSlot does not hold a volume of `src`'s size or a filled dstSlot is not of `grid`'s size, and for a
+    // spacing that is not positive.
+    int ResampleOnto(const VolumeFileDcm& src, int srcSlot, const VolumeFileDcm& grid, int dstSlot, uint32_t channels, int filter,
+                     const float outside[4], vr_resample_result* out, const double dstToSrc[12] = nullptr);
     // Closed planar polygons rasterised into contours of a mask volume on the device (vr_mask_polygons of include/vr.h): a descriptor
     // passed through.  `out` may be nullptr.
     int RasterPolygons(const vr_polygons_desc& desc, vr_polygons_result* out);

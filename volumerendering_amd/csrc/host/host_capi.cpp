@@ -480,6 +480,18 @@ int vrh_app_distance_mm(void* a, int src_slot, int src_contour, int dst_slot, in
     if (!vh || !vh->dcm) return VR_ERR_INVALID_ARG;
     VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->DistanceMm(src_slot, src_contour, dst_slot, dst_channel, mode, limit_mm, *vh->dcm, out); })
 }
+// Application::ResampleOnto (vr_volume_resample of the application's context); src, grid: volumes read by DicomReader; dst_to_src: twelve
+// doubles or nullptr
+int vrh_app_resample(void* a, void* src, int src_slot, void* grid, int dst_slot, uint32_t channels, int filter, const float outside[4],
+                     const double* dst_to_src, vr_resample_result* out)
+{
+    auto* sh = static_cast<VolumeHandle*>(src);
+    auto* gh = static_cast<VolumeHandle*>(grid);
+    if (!sh || !sh->dcm || !gh || !gh->dcm || !outside) return VR_ERR_INVALID_ARG;
+    VRH_TRY(VR_ERR_HIP, {
+        return static_cast<Application*>(a)->ResampleOnto(*sh->dcm, src_slot, *gh->dcm, dst_slot, channels, filter, outside, out, dst_to_src);
+    })
+}
 int vrh_app_set_surface_threshold(void* a, float tau) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->SetSurfaceThreshold(tau); }) }
 void vrh_app_set_prepare_on_device(void* a, int on) { static_cast<Application*>(a)->m_PrepareOnDevice = on != 0; }
 int vrh_app_update(void* a) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->OnUpdate(); }) }

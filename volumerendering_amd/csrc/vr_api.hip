@@ -1,7 +1,7 @@
 // vr_api.hip -- implementation of the C ABI declared in include/vr.h on top of the gfx950 kernels: one translation unit, the host code
 // by concern in vr_ctx.h and vr_api_*.h; here the context's life (create, resize, destroy), its settings and its streams.
 // The march kernels are not in this unit: vr_march.hip and vr_fused.hip compile them, one per arithmetic mode, and the host code
-// reaches them through launch_march, launch_shadow_build and launch_slice (vr_device.h).  What is compiled here, once, are the
+// reaches them through launch_march, launch_shadow_build, launch_slice and launch_resample (vr_device.h).  What is compiled here, once, are the
 // kernels that no arithmetic mode touches: the auxiliary kernels and the voxel tools.
 // No CPU fallback exists behind this ABI (and nothing under oracle/ is referenced): without a usable HIP
 // device vr_create fails with VR_ERR_HIP.
@@ -52,6 +52,7 @@ using namespace vr;
 #include "vr_api_raster.h"
 #include "vr_api_outline.h"
 #include "vr_api_components.h"
+#include "vr_api_resample.h"
 
 namespace {
 

@@ -1,5 +1,5 @@
 // vr_api_tools.h -- what the voxel tools (the histograms of vr_api_views.h, vr_api_segment.h, vr_api_morph.h, vr_api_dist.h,
-// vr_api_raster.h) share on the host: the rules for a slot, a component, a box and a second slot, a walk's units (vr_units.h) or word
+// vr_api_raster.h, vr_api_resample.h) share on the host: the rules for a slot, a component, a box and a second slot, a walk's units (vr_units.h) or word
 // rows (vr_bitrows.h) and its grid, the shell and the report of a call into a mask slot.
 #pragma once
 
@@ -106,18 +106,17 @@ int tool_timing(vr_ctx* c, State vr_ctx::*tool, float ms[4], const char* who)
     return VR_OK;
 }
 
-// The shell of a data-preparation call into mask slot `dst_slot`, its descriptor checked.  An empty slot gets the dimensions of slot
-// `dims_of_slot`, zeroed; run(float4* dst, bool fresh) is the tool, on the context's stream, and records report.ev[0 .. 3].
+// The shell of a data-preparation call into slot `dst_slot`, its descriptor checked.  An empty slot is created with the dimensions
+// dims = (nx, ny, nz), zeroed; run(float4* dst, bool fresh) is the tool, on the context's stream, and records report.ev[0 .. 3].
 template <typename Run>
-int mask_tool_call(vr_ctx* c, const char* who, int dims_of_slot, int dst_slot, ToolReport& report, Run run)
+int mask_tool_call(vr_ctx* c, const char* who, const int dims[3], int dst_slot, ToolReport& report, Run run)
 {
     if (const int rc = drain(c)) return rc;  // asynchronous renders on the caller's streams may still read the destination slot
     (void)hipGetLastError();
     for (Event& e : report.ev)  // (first use)
         if (!e) VR_HIP(c, e.create());
     VolumeSlot& D = c->vols[dst_slot];
-    const DevVolume& v = c->vols[dims_of_slot].vol;
-    const uint16_t nx = (uint16_t)v.nx, ny = (uint16_t)v.ny, nz = (uint16_t)v.nz;
+    const uint16_t nx = (uint16_t)dims[0], ny = (uint16_t)dims[1], nz = (uint16_t)dims[2];
     const bool fresh = !D.vol.data;
     if (fresh) {  // every component +0.0f
         const size_t n = (size_t)nx * ny * nz;
@@ -142,6 +141,15 @@ int mask_tool_call(vr_ctx* c, const char* who, int dims_of_slot, int dst_slot, T
     for (int i = 0; i < 4; ++i)
         if (hipEventElapsedTime(&report.ms[i], report.ev[i], report.ev[i + 1]) != hipSuccess) report.ms[i] = 0.0f;
     return VR_OK;
+}
+
+// ... an empty slot taking the dimensions of slot `dims_of_slot`: a mask on its volume's grid
+template <typename Run>
+int mask_tool_call(vr_ctx* c, const char* who, int dims_of_slot, int dst_slot, ToolReport& report, Run run)
+{
+    const DevVolume& v = c->vols[dims_of_slot].vol;
+    const int n[3] = {v.nx, v.ny, v.nz};
+    return mask_tool_call(c, who, n, dst_slot, report, run);
 }
 
 }  // namespace

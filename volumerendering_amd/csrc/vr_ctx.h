@@ -456,6 +456,12 @@ struct CompState {
     ToolReport report;                   // phases: pack, runs + scan + merge + flatten, numbering .. copy back, refresh_bricks
 };
 
+// Resampling (vr_volume_resample, vr_resample.h): what vr_resample_counters and vr_resample_timing report.
+struct ResampleState {
+    WordsPair<ResampleWords> io;         // the inside count, its bounding box, the loaded voxels
+    ToolReport report;                   // phases: the source's range records, the kernel, the result words, refresh_bricks
+};
+
 // What the reporting calls (vr_last_counters, vr_last_kernel_flavour, vr_last_timing, vr_kernel_times, vr_kernel_choice,
 // vr_download_tiles, vr_last_block_trace) read about the most recent march launch.  vr_pick copies it out and back as one value.
 struct LastLaunch {
@@ -558,6 +564,7 @@ struct vr_ctx {
     RasterState raster;  // polygon rasterisation (vr_mask_polygons)
     OutlineState outline;  // contour tracing (vr_mask_outlines)
     CompState comp;  // connected components (vr_mask_components)
+    ResampleState resample;  // resampling onto another grid (vr_volume_resample)
     std::string err;
 };
 

@@ -163,6 +163,29 @@ struct SliceParams {
     unsigned long long* counts;  // [workgroups][3]: counted samples, pixels with a sample, samples loaded
 };
 
+// The device words of one resample (vr_resample.h): what the host sets before the kernel and reads behind it.
+struct ResampleWords {
+    CountBox inside;            // the inside voxels of the box and their bounding box (starts as CountBox::empty())
+    unsigned long long loaded;  // voxels for which source voxels were loaded
+};
+
+// Kernel argument block of a resample (resample_kernel, vr_resample.h; vr_resample_desc of include/vr.h): passed by value.  Like a
+// slice it has a geometry of its own and reads nothing of MarchParams.
+struct ResampleParams {
+    DevVolume src;           // the source slot, in the layout in use
+    float4* dst;             // the destination's x-fastest vec4 voxels
+    int n[3];                // nx, ny, nz of the destination grid
+    int lo[3], hi[3];        // the destination voxel box, half open
+    unsigned ux;             // 64-voxel units per row of the box: ceil((hi[0] - lo[0]) / 64)
+    unsigned long long units;  // ux * rows * slices of the box: unit u is 64 voxels along x of row u / ux
+    float origin[3], di[3], dj[3], dk[3];
+    float outside[4];
+    unsigned channels;       // bit c: component c is written
+    const float2* bricks;    // exact settling: the source's range records (vr_proj.h), bnx x bny x ... bricks; nullptr = off
+    int bnx, bny;
+    ResampleWords* w;
+};
+
 // Kernel argument block of a histogram (hist_kernel, vr_hist.h; vr_hist_desc of include/vr.h): passed by value.
 struct HistParams {
     const float* val;        // the value of voxel idx is val[idx * val_stride]: the channel of the x-fastest vec4 voxels (stride 4),
@@ -251,6 +274,10 @@ struct LaunchDesc {
     bool surface;          // kIso: the refined point instead of the shaded fragment (iso_point_kernel, vr_iso.h)
 };
 
+// The forms of resample_kernel (vr_resample.h): the plain one (vr_set_kernel_flavour(1)); the default one; the default one of a launch
+// that writes component 3 alone, which reads the density plane and settles wavefronts by the range records where it has them.
+enum ResampleForm : int { kResamplePlain = 0, kResampleDefault = 1, kResampleDensity = 2 };
+
 }  // namespace vr
 
 // The entry points of a march unit (vr_launch.h defines them): all the C ABI's unit sees of the march kernels.  One text for both
@@ -258,10 +285,12 @@ struct LaunchDesc {
 //   launch_march         enqueues the kernel of L; false: there is none for this family of this shader, nothing was launched
 //   launch_shadow_build  the light volume of a shadowed launch (P: its parameters, vol[1] = the grid, whose storage is `out`)
 //   launch_slice         a slice view: reduction x filter x addressing x skipping, `tiles` workgroups of one wavefront
+//   launch_resample      a resample: filter x addressing x form (vr_resample.h: kResamplePlain ..), `blocks` persistent workgroups
 #define VR_MARCH_ENTRY_POINTS                                                                                                          \
     bool launch_march(const vr::LaunchDesc& L, hipStream_t s, const vr::MarchBatch& B);                                                \
     void launch_shadow_build(const vr::MarchParams& P, float* out, float sigma, bool skip, bool off32, hipStream_t s);                 \
-    void launch_slice(const vr::SliceParams& S, int reduce, bool nearest, bool off32, bool skip, unsigned tiles, hipStream_t s);
+    void launch_slice(const vr::SliceParams& S, int reduce, bool nearest, bool off32, bool skip, unsigned tiles, hipStream_t s);         \
+    void launch_resample(const vr::ResampleParams& R, bool nearest, bool off32, int form, unsigned blocks, hipStream_t s);
 namespace vr {
 VR_MARCH_ENTRY_POINTS
 }

@@ -1,8 +1,8 @@
 // vr_launch.h -- picks the instantiation of the march kernels for one launch (variant x addressing x skipping x loop
 // form x lanes per ray).  Included once per arithmetic mode: by vr_march.hip (namespace vr, separately rounded
 // multiply-adds) and by vr_fused.hip (namespace vrf, fused multiply-adds), each a translation unit that holds nothing else.  The C
-// ABI's unit (vr_api.hip) sees the three entry points that vr_device.h declares -- launch_march, launch_shadow_build, launch_slice
-// -- and calls the ones of the context's arithmetic mode (vr_set_arithmetic).
+// ABI's unit (vr_api.hip) sees the four entry points that vr_device.h declares -- launch_march, launch_shadow_build, launch_slice,
+// launch_resample -- and calls the ones of the context's arithmetic mode (vr_set_arithmetic).
 #pragma once
 // march_p2_kernel: the several-frames form also for a launch of ONE frame.  It reads a frame's parameters where it uses them, through
 // a wave-uniform index, and keeps fewer of them in registers: no scratch reload in the pipelined loop, which the one-frame form of the
@@ -33,6 +33,8 @@
 #include "vr_bound.h"
 // Slice views of any volume slot (vr_slice_async): a kernel with a parameter struct of its own, outside launch_march
 #include "vr_slice.h"
+// A volume slot resampled onto another grid (vr_volume_resample): a kernel with a parameter struct of its own as well
+#include "vr_resample.h"
 
 #include <type_traits>
 #include <utility>
@@ -181,6 +183,18 @@ void launch_slice(const SliceParams& S, int reduce, bool nearest, bool off32, bo
     else launch(std::integral_constant<int, kProjAvg>{});
 }
 
+// a resample (vr_resample.h): filter x addressing x form; `blocks` persistent workgroups of four wavefronts
+void launch_resample(const ResampleParams& R, bool nearest, bool off32, int form, unsigned blocks, hipStream_t s)
+{
+    auto launch = [&](auto f) {
+        constexpr int F = decltype(f)::value;
+        with_flags([&](auto N, auto O) { hipLaunchKernelGGL((resample_kernel<N, O, F>), dim3(blocks), dim3(256), 0, s, R); }, nearest, off32);
+    };
+    if (form == kResamplePlain) launch(std::integral_constant<int, kResamplePlain>{});
+    else if (form == kResampleDensity) launch(std::integral_constant<int, kResampleDensity>{});
+    else launch(std::integral_constant<int, kResampleDefault>{});
+}
+
 // the families that exist per shader, for shader V
 template <int V>
 bool launch_variant(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
@@ -223,8 +237,8 @@ bool launch_march(const LaunchDesc& L, hipStream_t s, const MarchBatch& B)
     }
 }
 
-// The three definitions above are the ones vr_device.h declares: with another signature a definition would be a second overload,
+// The four definitions above are the ones vr_device.h declares: with another signature a definition would be a second overload,
 // and the name's address ambiguous.
-static_assert(sizeof(&launch_march) + sizeof(&launch_shadow_build) + sizeof(&launch_slice) > 0);
+static_assert(sizeof(&launch_march) + sizeof(&launch_shadow_build) + sizeof(&launch_slice) + sizeof(&launch_resample) > 0);
 
 }  // namespace VR_KNS

@@ -74,6 +74,7 @@ def load() -> C.CDLL:
         "vrh_app_mask_to_contours": (vp, [vp, i32, i32, i32, vp, C.POINTER(C.c_int)]),
         "vrh_app_distance_map": (i32, [vp, C.POINTER(capi.DistDesc), C.POINTER(capi.DistResult)]),
         "vrh_app_distance_mm": (i32, [vp, i32, i32, i32, i32, i32, f32, vp, C.POINTER(capi.DistResult)]),
+        "vrh_app_resample": (i32, [vp, vp, i32, vp, i32, u32, i32, C.POINTER(C.c_float * 4), C.POINTER(C.c_double * 12), C.POINTER(capi.ResampleResult)]),
         "vrh_app_slice": (i32, [vp, C.POINTER(capi.SliceDesc), vp]),
         "vrh_app_slice_through_pick": (C.c_longlong, [vp, C.POINTER(capi.PickResult), i32, i32, vp, C.c_size_t, C.POINTER(u32), C.POINTER(u32)]), "vrh_app_set_surface_threshold": (i32, [vp, f32]), "vrh_app_update": (i32, [vp]), "vrh_app_render": (i32, [vp]),
         "vrh_app_resize": (i32, [vp, u32, u32]), "vrh_app_read_frame": (i32, [vp, vp, vp, C.POINTER(u64)]),
@@ -592,6 +593,19 @@ class Application:
         limit_mm = where the map saturates (0: nowhere)."""
         out = capi.DistResult()
         self._chk(self.lib.vrh_app_distance_mm(self.h, src_slot, src_contour, dst_slot, dst_channel, mode, limit_mm, grid.h, C.byref(out)))
+        return out
+
+    def resample_onto(self, src: "VolumeFile", src_slot: int, grid: "VolumeFile", dst_slot: int, channels: int = 15,
+                      filter: int = capi.RESAMPLE_LINEAR, outside=(0.0, 0.0, 0.0, 0.0), dst_to_src=None) -> capi.ResampleResult:
+        """Application::ResampleOnto: volume src_slot, which holds `src`, resampled onto the voxel grid of `grid` into volume dst_slot
+        (both read from DICOM: ImagePositionPatient, PixelSpacing, SliceThickness, in millimetres).  channels: bit c = component c is
+        written; outside: the four values stored where `grid` lies outside `src`; dst_to_src: twelve numbers, a row-major 3 x 4 map
+        from `grid`'s patient coordinates to `src`'s (None = one frame of reference)."""
+        out = capi.ResampleResult()
+        o = (C.c_float * 4)(*[float(x) for x in outside])
+        m = None if dst_to_src is None else (C.c_double * 12)(*[float(x) for x in np.asarray(dst_to_src, np.float64).ravel()])
+        self._chk(self.lib.vrh_app_resample(self.h, src.h, src_slot, grid.h, dst_slot, channels, filter, C.byref(o),
+                                            None if m is None else C.byref(m), C.byref(out)))
         return out
 
     def set_surface_threshold(self, tau: float):
