@@ -1351,6 +1351,80 @@ int vr_resample_counters(vr_ctx* ctx, uint64_t out[3]);
  * from the destination slot.  Zeros before the first call and after one that failed. */
 int vr_resample_timing(vr_ctx* ctx, float ms[4]);
 
+/* ---- surface extraction: the surface {value >= level} of a component as an indexed triangle mesh -----------------------------------
+ * The 3-D counterpart of vr_mask_outlines: the surface of a structure, or the surface VR_VARIANT_ISO renders, as a triangle mesh a
+ * caller can save, print, measure or hand to a rasteriser -- extracted on the device (csrc/vr_mesh.h) by MARCHING TETRAHEDRA on the Kuhn
+ * (Freudenthal) split of every cell, without the volume passing through the host.  The 16-case rule has no ambiguous case, and the mesh
+ * is watertight and combinatorially manifold by construction.  The combinatorics are integer work; a position is two f32 subtractions and
+ * one IEEE division.  Every output is a function of the inputs alone, never of scheduling.  The call reads a slot and writes none.
+ *   Lattice and cells: lattice point (i, j, k) is the centre of voxel (i, j, k).  With cap = 0 the points are those of the box,
+ *     lo <= p < hi, and the cells are the unit cubes with origin o, lo <= o < hi - 1 on every axis: a box thinner than 2 on an axis has
+ *     no cells.  With cap = 1 the lattice grows by one layer of VIRTUAL points on every side, lo - 1 <= p <= hi, and the cell origins are
+ *     lo - 1 <= o < hi.
+ *   Inside: a real point is inside if value >= level (VR_VARIANT_ISO's rule: equal is in; NaN compares false, so NaN is out).  A
+ *     virtual point is outside.  `level` must be finite.
+ *   Tetrahedra: cell o is split into six tetrahedra, one per permutation (a, b, c) of the axes, in lexicographic order xyz, xzy, yxz,
+ *     yzx, zxy, zyx: q0 = o, q1 = q0 + e_a, q2 = q1 + e_b, q3 = q2 + e_c = o + (1,1,1).  Every tetrahedron edge is a lattice edge
+ *     (p, p + d) with d in {0,1}^3 \ {0}; its direction code is m = d.x + 2 d.y + 4 d.z (1 .. 7).
+ *   Vertices: one per lattice edge whose two ends differ in "inside" and which belongs to some cell.  Its key is (the raster index of p in
+ *     the (extended) lattice, x fastest, then y, then z; then m); vertices are numbered 0 .. V - 1 in ascending key order.  With a = p and
+ *     b = p + d: t = (level - v_a) / (v_b - v_a) in f32 (two subtractions, one division); !(t >= 0) -> t = 0 (NaN too), t > 1 -> t = 1;
+ *     a virtual -> t = 1, b virtual -> t = 0 (the vertex sits on the real end).  The coordinate on an axis is (float)p + t where d is 1 on
+ *     that axis, (float)p otherwise: voxel-index units, three f32 per vertex.
+ *   Triangles: cells in the raster order of their origins (cap = 0: lo <= o < hi - 1; cap = 1: lo - 1 <= o < hi; x fastest -- the CELL
+ *     lattice, one layer shorter per axis than the point lattice), within a cell tetrahedra 0 .. 5.  With v_ij the vertex on edge q_i q_j:
+ *     one point alone (q_i inside or outside alone, the others j < k < l): (v_ij, v_ik, v_il); two and two (inside i < j, outside k < l):
+ *     (v_ik, v_il, v_jl) then (v_ik, v_jl, v_jk).  The last two indices of a case's triangles are swapped where needed so that
+ *     (p1 - p0) x (p2 - p0) points from the inside points toward the outside points for vertices strictly inside their edges: seen from
+ *     outside, triangles are counter-clockwise.  The swap is a function of (tetrahedron, case) alone.  Indices are uint32.
+ *   A cell whose 8 corners agree yields nothing.  With cap = 1 the mesh is closed for every input; with cap = 0 it is open exactly where
+ *     the surface meets the box.  Values equal to the level, or non-finite ones, can give zero-area triangles; they stay in the mesh.
+ *   Capacity: max_vertices == max_triangles == 0 is the counting call: VR_OK, the result filled.  If either buffer is too small both
+ *     arrays are left untouched, the result is filled all the same, the call returns VR_ERR_INVALID_ARG and vr_last_error names both
+ *     needed counts.  More than 2^31 - 1 vertices or triangles in one call: VR_ERR_UNSUPPORTED.
+ *   Result: n_vertices, n_triangles = what the surface needs; inside = the real points of the box that are inside; cells = the cells
+ *     that emit at least one triangle and lo / hi the half-open box of their origins (zeros if none).
+ *   Counters (vr_mesh_counters): out[0] = points of the box, out[1] = voxels loaded by the classification, out[2] = voxels settled from
+ *     a range record, out[3] = cells that emit.
+ * Kernel forms: for channel 3 the classification settles a voxel from its 4 x 4 x 4 brick's (min, max) record where that decides the
+ * test exactly (csrc/vr_mesh.h has the proof); channels 0 .. 2 have no records and every voxel is loaded, and vr_set_kernel_flavour(1)
+ * forces that plain form for channel 3 too.  Everything but the counters is identical across the forms and the volume layouts. */
+typedef struct vr_mesh_desc {
+    int32_t  src_slot, channel;        /* component 0 .. 3 of an uploaded slot                                   */
+    float    level;                    /* finite                                                                 */
+    int32_t  cap;                      /* 0 / 1: one layer of virtual outside points around the box              */
+    int32_t  box_lo[3], box_hi[3];     /* voxel box, half open                                                   */
+    uint32_t max_vertices, max_triangles; /* what the two arrays hold                                            */
+    float*    vertices;                /* host memory, 3 per vertex; NULL iff max_vertices == 0                  */
+    uint32_t* triangles;               /* host memory, 3 per triangle; NULL iff max_triangles == 0               */
+} vr_mesh_desc;
+typedef struct vr_mesh_result {
+    uint32_t n_vertices, n_triangles;  /* what the surface needs, whether or not it was stored                   */
+    uint64_t inside;                   /* real points of the box that are inside                                 */
+    uint64_t cells;                    /* cells that emit at least one triangle                                  */
+    int32_t  lo[3], hi[3];             /* half-open box of those cells' origins, zeros if none                   */
+} vr_mesh_result;
+
+/* Fills *out for the whole volume of src_slot: channel 3, level 0.5, cap 0, the box (0,0,0) .. (nx,ny,nz) and no buffers.  Pure host
+ * arithmetic; VR_ERR_INVALID_ARG for a NULL pointer or a slot out of range, VR_ERR_NOT_READY for an empty slot. */
+int vr_mesh_whole(const vr_ctx* ctx, int src_slot, vr_mesh_desc* out);
+
+/* Does the work; `result` may be NULL.  A synchronous data call on the ctx's own stream: it waits for everything in flight, writes no
+ * slot and leaves what the reporting calls say about earlier launches and tools as it was.  An empty box or a surface that does not
+ * meet it gives an empty mesh and VR_OK.
+ * Checked before anything is enqueued.  VR_ERR_INVALID_ARG: a NULL ctx or descriptor; a slot or channel out of range; a level that is
+ * not finite; a cap other than 0 / 1; a box that is not 0 <= lo <= hi <= n on every axis; vertices or triangles NULL with a capacity, or
+ * given with none.  VR_ERR_NOT_READY: the slot is empty.  VR_ERR_OOM: the working buffers could not be allocated. */
+int vr_volume_mesh(vr_ctx* ctx, const vr_mesh_desc* desc, vr_mesh_result* result);
+
+/* Counters of the last vr_volume_mesh that got as far as counting (as described above).  Zeros before the first. */
+int vr_mesh_counters(vr_ctx* ctx, uint64_t out[4]);
+
+/* Device time of the last vr_volume_mesh in milliseconds, from events on the ctx's stream: ms[0] the classification into bit-rows,
+ * ms[1] the counts and their scans (the host's look at the totals included), ms[2] the vertex emit, ms[3] the triangle emit and the copy
+ * back.  Zeros before the first, after one that failed, and for the phases a call did not reach. */
+int vr_mesh_timing(vr_ctx* ctx, float ms[4]);
+
 /* Volume layout in HBM (A/B measurements; frames and counts are bit-identical in every mode).
  *   0  default: the march kernels gather from a BRICKED copy of every slot -- the vec4 voxels and a scalar f32 density plane
  *      (what fetches that consume .a alone read: BasicVolumeApp.wgsl:171, the density / dose fetches of the other shaders)

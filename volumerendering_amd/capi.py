@@ -75,6 +75,7 @@ ABI_SYMBOLS = [
     "vr_outlines_whole", "vr_mask_outlines", "vr_outlines_counters", "vr_outlines_timing",
     "vr_components_whole", "vr_mask_components", "vr_components_counters", "vr_components_timing",
     "vr_resample_identity", "vr_resample_between", "vr_volume_resample", "vr_resample_counters", "vr_resample_timing",
+    "vr_mesh_whole", "vr_volume_mesh", "vr_mesh_counters", "vr_mesh_timing",
 ]
 
 
@@ -321,6 +322,37 @@ class OutlinesResult(C.Structure):
                 tuple(int(x) for x in self.area2))
 
 
+class MeshDesc(C.Structure):
+    """struct vr_mesh_desc (include/vr.h): the source slot and its component, the level, the cap, the voxel box, and the capacities and
+    arrays of the output (set by Context.volume_mesh)."""
+    _fields_ = [
+        ("src_slot", C.c_int32), ("channel", C.c_int32), ("level", C.c_float), ("cap", C.c_int32),
+        ("box_lo", C.c_int32 * 3), ("box_hi", C.c_int32 * 3),
+        ("max_vertices", C.c_uint32), ("max_triangles", C.c_uint32), ("vertices", C.c_void_p), ("triangles", C.c_void_p),
+    ]
+
+    def copy(self, **over) -> "MeshDesc":
+        """A copy with the given fields replaced (box_lo / box_hi from any sequence of three integers)."""
+        d = MeshDesc.from_buffer_copy(bytes(self))
+        for k, v in over.items():
+            if k in ("box_lo", "box_hi"):
+                v = (C.c_int32 * 3)(*[int(x) for x in v])
+            setattr(d, k, v)
+        return d
+
+
+class MeshResult(C.Structure):
+    """struct vr_mesh_result: the vertices and triangles the surface needs, the inside points of the box, the cells that emit and the
+    half-open box of their origins (zeros when there are none)."""
+    _fields_ = [("n_vertices", C.c_uint32), ("n_triangles", C.c_uint32), ("inside", C.c_uint64), ("cells", C.c_uint64),
+                ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3)]
+
+    def as_tuple(self):
+        """(n_vertices, n_triangles, inside, cells, lo, hi)"""
+        return (int(self.n_vertices), int(self.n_triangles), int(self.inside), int(self.cells), tuple(int(x) for x in self.lo),
+                tuple(int(x) for x in self.hi))
+
+
 class Component(C.Structure):
     """struct vr_component (include/vr.h): a component's voxels, half-open bounding box, first voxel (x, y, z) and the faces of the box
     it touches."""
@@ -526,6 +558,10 @@ def load() -> C.CDLL:
     lib.vr_volume_resample.argtypes = [vp, C.POINTER(ResampleDesc), C.POINTER(ResampleResult)]
     lib.vr_resample_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
     lib.vr_resample_timing.argtypes = [vp, C.POINTER(C.c_float * 4)]
+    lib.vr_mesh_whole.argtypes = [vp, i32, C.POINTER(MeshDesc)]
+    lib.vr_volume_mesh.argtypes = [vp, C.POINTER(MeshDesc), C.POINTER(MeshResult)]
+    lib.vr_mesh_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 4)]
+    lib.vr_mesh_timing.argtypes = [vp, C.POINTER(C.c_float * 4)]
     lib.vr_present_async.argtypes = [vp, vp, vp, vp]
     lib.vr_present_tiles_async.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
     lib.vr_hint_frames_in_flight.argtypes = [vp, i32]
@@ -1058,6 +1094,35 @@ class Context:
     def resample_timing(self):
         """(range records, kernel, result words, refresh) of the last volume_resample in ms of device time (vr_resample_timing)."""
         return self._tool_timing(self.lib.vr_resample_timing)
+
+    def mesh_whole(self, src_slot: int) -> MeshDesc:
+        """vr_mesh_whole: the descriptor of an extraction over the whole volume (channel 3, level 0.5, no cap, no buffers)."""
+        d = MeshDesc()
+        self._chk(self.lib.vr_mesh_whole(self.h, src_slot, C.byref(d)))
+        return d
+
+    def volume_mesh(self, desc: MeshDesc):
+        """vr_volume_mesh: the surface {value >= level} of a component inside a box as an indexed triangle mesh (synchronous): the
+        counting call, then the call that stores.  Returns (vertices float32 (V, 3) in voxel-index units, triangles uint32 (T, 3),
+        MeshResult).  The descriptor's own capacities and arrays are ignored."""
+        out = MeshResult()
+        self._chk(self.lib.vr_volume_mesh(self.h, C.byref(desc.copy(max_vertices=0, max_triangles=0, vertices=None, triangles=None)), C.byref(out)))
+        verts = np.zeros((int(out.n_vertices), 3), np.float32)
+        tris = np.zeros((int(out.n_triangles), 3), np.uint32)
+        if out.n_vertices:
+            d = desc.copy(max_vertices=len(verts), max_triangles=len(tris), vertices=verts.ctypes.data, triangles=tris.ctypes.data)
+            self._chk(self.lib.vr_volume_mesh(self.h, C.byref(d), C.byref(out)))  # (verts and tris live until here)
+        return verts, tris, out
+
+    def mesh_counters(self):
+        """(points of the box, voxels loaded, voxels settled from a range record, cells that emit) of the last volume_mesh."""
+        out = (C.c_uint64 * 4)()
+        self._chk(self.lib.vr_mesh_counters(self.h, C.byref(out)))
+        return tuple(int(x) for x in out)
+
+    def mesh_timing(self):
+        """(classify / pack, counts + scans, vertex emit, triangle emit + copy back) of the last volume_mesh in ms of device time."""
+        return self._tool_timing(self.lib.vr_mesh_timing)
 
     def set_volume_layout(self, mode: int):
         """0 bricked copy (default), 1 the reference's vec4 voxels only, 3 x-fastest voxels + density plane (2 was removed)."""

@@ -368,6 +368,46 @@ int Application::MaskToContours(int srcSlot, int contours, int connect, const Vo
     return VR_OK;
 }
 
+int Application::ExtractSurface(int slot, int channel, float level, int cap, SurfaceMesh& out, const double spacing[3])
+{
+    if (!p_Ctx) return VR_ERR_NOT_READY;
+    const double unit[3] = {1.0, 1.0, 1.0};
+    const double* const sp = spacing ? spacing : unit;
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(sp[a]) || !(sp[a] > 0.0)) return VR_ERR_INVALID_ARG;
+    vr_mesh_desc d;
+    int rc = vr_mesh_whole(p_Ctx, slot, &d);
+    if (rc != VR_OK) return rc;
+    d.channel = channel;
+    d.level = level;
+    d.cap = cap;
+    out = SurfaceMesh{};
+    rc = vr_volume_mesh(p_Ctx, &d, &out.result);  // the counting call
+    std::vector<float> verts((size_t)out.result.n_vertices * 3);
+    out.triangles.assign((size_t)out.result.n_triangles * 3, 0u);
+    if (rc == VR_OK && out.result.n_vertices != 0) {
+        d.max_vertices = out.result.n_vertices;
+        d.max_triangles = out.result.n_triangles;
+        d.vertices = verts.data();
+        d.triangles = out.triangles.data();
+        rc = vr_volume_mesh(p_Ctx, &d, &out.result);
+    }
+    if (rc != VR_OK) {
+        m_Error = vr_last_error(p_Ctx);
+        return rc;
+    }
+    out.positions.resize(verts.size());
+    for (size_t i = 0; i < verts.size(); ++i) out.positions[i] = static_cast<double>(verts[i]) * sp[i % 3];
+    return VR_OK;
+}
+
+int Application::ExtractSurface(int slot, int channel, float level, int cap, const VolumeFileDcm& grid, SurfaceMesh& out)
+{
+    const DicomVolumeParams p = grid.GetVolumeParams();
+    const double spacing[3] = {p.PixelSpacing[0], p.PixelSpacing[1], p.SliceThickness};
+    return ExtractSurface(slot, channel, level, cap, out, spacing);
+}
+
 int Application::Pick(uint32_t x, uint32_t y, vr_pick_result* out)
 {
     if (!p_Ctx || !p_App) return VR_ERR_NOT_READY;

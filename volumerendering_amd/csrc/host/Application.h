@@ -11,6 +11,7 @@
 
 #include "Camera.h"
 #include "MiniApp.h"
+#include "SurfaceMesh.h"
 #include "dicom/StructureFileDcm.h"
 #include "dicom/VolumeFileDcm.h"
 #include "vr.h"
@@ -119,6 +120,13 @@ public:
     // (the layout StructureFileDcm holds), z = that of the polygon's slice, the inverse of ContourSliceNumber.  VR_ERR_INVALID_ARG for a
     // spacing that is not positive, a coordinate beyond 2^29 micrometres or a volume of another size than `grid`.
     int MaskToContours(int srcSlot, int contours, int connect, const VolumeFileDcm& grid, std::vector<std::vector<std::vector<float>>>& out);
+    // The surface {value >= level} of component `channel` of volume `slot` over the whole volume as a triangle mesh, extracted on the
+    // device (vr_volume_mesh of include/vr.h: marching tetrahedra; cap = 1 closes the mesh at the volume's faces): the counting call and
+    // the call that stores.  The positions are the voxel indices times `spacing` (x, y, z; nullptr = 1), multiplied in double on the
+    // host; with `grid` its PixelSpacing and SliceThickness in millimetres.  VR_ERR_INVALID_ARG for a spacing that is not finite and
+    // positive.
+    int ExtractSurface(int slot, int channel, float level, int cap, SurfaceMesh& out, const double spacing[3] = nullptr);
+    int ExtractSurface(int slot, int channel, float level, int cap, const VolumeFileDcm& grid, SurfaceMesh& out);
     // the accumulated opacity at which the unlit / lit scene's surface lies (vr_set_surface_threshold: finite, 0 <= tau < 1)
     int SetSurfaceThreshold(float tau);
 

@@ -467,6 +467,47 @@ void* vrh_app_mask_to_contours(void* a, int src_slot, int contours, int connect,
     if (rc) *rc = code;
     return made;
 }
+// Application::ExtractSurface (vr_volume_mesh of the application's context): a SurfaceMesh handle (vrh_mesh_free), nullptr with *rc set
+// on failure.  grid: a volume read by DicomReader whose PixelSpacing and SliceThickness scale the positions, or, with grid == nullptr,
+// spacing: three doubles or nullptr (unit spacing).
+void* vrh_app_extract_surface(void* a, int slot, int channel, float level, int cap, void* grid, const double* spacing, int* rc)
+{
+    auto* vh = static_cast<VolumeHandle*>(grid);
+    int code = VR_ERR_INVALID_ARG;
+    SurfaceMesh* made = nullptr;
+    if (!vh || vh->dcm) {
+        try {
+            made = new SurfaceMesh();
+            code = vh ? static_cast<Application*>(a)->ExtractSurface(slot, channel, level, cap, *vh->dcm, *made)
+                      : static_cast<Application*>(a)->ExtractSurface(slot, channel, level, cap, *made, spacing);
+        } catch (...) {
+            code = VR_ERR_HIP;
+        }
+        if (code != VR_OK) {
+            delete made;
+            made = nullptr;
+        }
+    }
+    if (rc) *rc = code;
+    return made;
+}
+void vrh_mesh_free(void* m) { delete static_cast<SurfaceMesh*>(m); }
+void vrh_mesh_counts(void* m, uint64_t* vertices, uint64_t* triangles, vr_mesh_result* result)
+{
+    const auto* s = static_cast<SurfaceMesh*>(m);
+    if (vertices) *vertices = s->VertexCount();
+    if (triangles) *triangles = s->TriangleCount();
+    if (result) *result = s->result;
+}
+// positions: 3 doubles per vertex, triangles: 3 uint32 per triangle (either may be nullptr)
+void vrh_mesh_copy(void* m, double* positions, uint32_t* triangles)
+{
+    const auto* s = static_cast<SurfaceMesh*>(m);
+    if (positions && !s->positions.empty()) std::memcpy(positions, s->positions.data(), s->positions.size() * sizeof(double));
+    if (triangles && !s->triangles.empty()) std::memcpy(triangles, s->triangles.data(), s->triangles.size() * sizeof(uint32_t));
+}
+int vrh_mesh_write_stl(void* m, const char* path) { VRH_TRY(0, { return path && static_cast<SurfaceMesh*>(m)->WriteStl(path) ? 1 : 0; }) }
+int vrh_mesh_write_ply(void* m, const char* path) { VRH_TRY(0, { return path && static_cast<SurfaceMesh*>(m)->WritePly(path) ? 1 : 0; }) }
 // Application::DistanceMap and Application::DistanceMm (vr_mask_distance of the application's context); grid: as vrh_app_margin_mm's
 int vrh_app_distance_map(void* a, const vr_dist_desc* desc, vr_dist_result* out)
 {

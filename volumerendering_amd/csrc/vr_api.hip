@@ -26,6 +26,8 @@
 #include "vr_outline.h"
 // Connected components (vr_mask_components): a union-find over the runs of the same bit-rows, compiled once as well
 #include "vr_comp.h"
+// Surface extraction (vr_volume_mesh): marching tetrahedra over bit-rows of the lattice; nothing to fuse, compiled once as well
+#include "vr_mesh.h"
 
 #include <algorithm>
 #include <cmath>
@@ -53,6 +55,7 @@ using namespace vr;
 #include "vr_api_outline.h"
 #include "vr_api_components.h"
 #include "vr_api_resample.h"
+#include "vr_api_mesh.h"
 
 namespace {
 

@@ -462,6 +462,18 @@ struct ResampleState {
     ToolReport report;                   // phases: the source's range records, the kernel, the result words, refresh_bricks
 };
 
+// Surface extraction (vr_volume_mesh, vr_mesh.h): the working buffers of the last call, grown on demand; what vr_mesh_counters and
+// vr_mesh_timing report.  Of vr_ctx::bit_row_scratch it takes one buffer: the lattice rows of the "inside" bits.
+struct MeshState {
+    DevBuf<unsigned long long> masks;    // per lattice word: the cells that emit, the seven crossing masks
+    DevBuf<unsigned> vbase, tbase;       // per lattice word: its vertices / triangles, then those before it
+    DevBuf<float> vertices;              // the output, three per vertex ...
+    DevBuf<unsigned> triangles;          // ... and three per triangle
+    WordsPair<MeshWords> io;             // the counters, the totals, the emitting cells' box
+    ToolReport report;                   // phases: pack, counts + scans, vertex emit, triangle emit + copy back (counters: the first three)
+    unsigned long long active_cells = 0; // vr_mesh_counters' fourth
+};
+
 // What the reporting calls (vr_last_counters, vr_last_kernel_flavour, vr_last_timing, vr_kernel_times, vr_kernel_choice,
 // vr_download_tiles, vr_last_block_trace) read about the most recent march launch.  vr_pick copies it out and back as one value.
 struct LastLaunch {
@@ -565,6 +577,7 @@ struct vr_ctx {
     OutlineState outline;  // contour tracing (vr_mask_outlines)
     CompState comp;  // connected components (vr_mask_components)
     ResampleState resample;  // resampling onto another grid (vr_volume_resample)
+    MeshState mesh;  // surface extraction (vr_volume_mesh)
     std::string err;
 };
 

@@ -72,6 +72,9 @@ def load() -> C.CDLL:
         "vrh_app_contours_to_mask": (i32, [vp, vp, C.POINTER(C.c_int * 4), vp, i32, i32, C.POINTER(capi.PolygonsResult)]),
         "vrh_app_mask_outlines": (i32, [vp, C.POINTER(capi.OutlinesDesc), C.POINTER(capi.OutlinesResult)]),
         "vrh_app_mask_to_contours": (vp, [vp, i32, i32, i32, vp, C.POINTER(C.c_int)]),
+        "vrh_app_extract_surface": (vp, [vp, i32, i32, f32, i32, vp, C.POINTER(C.c_double * 3), C.POINTER(C.c_int)]),
+        "vrh_mesh_free": (None, [vp]), "vrh_mesh_counts": (None, [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(capi.MeshResult)]),
+        "vrh_mesh_copy": (None, [vp, vp, vp]), "vrh_mesh_write_stl": (i32, [vp, C.c_char_p]), "vrh_mesh_write_ply": (i32, [vp, C.c_char_p]),
         "vrh_app_distance_map": (i32, [vp, C.POINTER(capi.DistDesc), C.POINTER(capi.DistResult)]),
         "vrh_app_distance_mm": (i32, [vp, i32, i32, i32, i32, i32, f32, vp, C.POINTER(capi.DistResult)]),
         "vrh_app_resample": (i32, [vp, vp, i32, vp, i32, u32, i32, C.POINTER(C.c_float * 4), C.POINTER(C.c_double * 12), C.POINTER(capi.ResampleResult)]),
@@ -88,6 +91,40 @@ def load() -> C.CDLL:
         fn.restype, fn.argtypes = res, args
     _lib = lib
     return lib
+
+
+class SurfaceMesh:
+    """med::SurfaceMesh (csrc/host/SurfaceMesh.h): what Application.extract_surface returns."""
+
+    def __init__(self, handle):
+        self.lib = load()
+        self.h = handle
+        nv, nt, self.result = C.c_uint64(0), C.c_uint64(0), capi.MeshResult()
+        self.lib.vrh_mesh_counts(self.h, C.byref(nv), C.byref(nt), C.byref(self.result))
+        self.positions = np.zeros((nv.value, 3), np.float64)
+        self.triangles = np.zeros((nt.value, 3), np.uint32)
+        self.lib.vrh_mesh_copy(self.h, self.positions.ctypes.data, self.triangles.ctypes.data)
+
+    def write_stl(self, path: str):
+        """SurfaceMesh::WriteStl: binary STL with facet normals from the triangles."""
+        if not self.lib.vrh_mesh_write_stl(self.h, str(path).encode()):
+            raise IOError(f"cannot write {path}")
+
+    def write_ply(self, path: str):
+        """SurfaceMesh::WritePly: binary little-endian PLY, indexed."""
+        if not self.lib.vrh_mesh_write_ply(self.h, str(path).encode()):
+            raise IOError(f"cannot write {path}")
+
+    def close(self):
+        if self.h:
+            self.lib.vrh_mesh_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class VolumeFile:
@@ -579,6 +616,16 @@ class Application:
         h = self.lib.vrh_app_mask_to_contours(self.h, src_slot, contours, connect, grid.h, C.byref(rc))
         self._chk(rc.value)
         return StructureFile(h)
+
+    def extract_surface(self, slot: int, channel: int = 3, level: float = 0.5, cap: int = 0, grid: "VolumeFile" = None, spacing=None) -> "SurfaceMesh":
+        """Application::ExtractSurface: the surface {value >= level} of component `channel` of volume `slot` over the whole volume as a
+        triangle mesh (vr_volume_mesh, include/vr.h); positions = voxel indices times the spacing -- `grid`'s PixelSpacing and
+        SliceThickness (a volume read from DICOM), else `spacing` (x, y, z), else 1 -- multiplied in float64 on the host."""
+        rc = C.c_int(0)
+        sp = (C.c_double * 3)(*[float(x) for x in spacing]) if spacing is not None else None
+        h = self.lib.vrh_app_extract_surface(self.h, slot, channel, level, cap, grid.h if grid is not None else None, sp, C.byref(rc))
+        self._chk(rc.value)
+        return SurfaceMesh(h)
 
     def distance_map(self, desc: capi.DistDesc) -> capi.DistResult:
         """Application::DistanceMap: vr_mask_distance (include/vr.h) on the application's context."""
