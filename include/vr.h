@@ -1154,7 +1154,9 @@ int vr_outlines_counters(vr_ctx* ctx, uint64_t out[3]);
 
 /* Device time of the last vr_mask_outlines in milliseconds, from events on the ctx's stream: ms[0] the pack of the contours, ms[1] the
  * corners, their scan and the links, ms[2] the doubling rounds (the host's looks at their outcome included), ms[3] the polygons' scans,
- * the emit and the copy back.  Zeros before the first, after one that failed, and for the phases a call did not reach. */
+ * the emit and the copy back.  A phase the call did not begin is 0: all four for an empty box, ms[2] and ms[3] when no contour has a
+ * corner.  A call that fails only because points or polygons is too small has done the counting call's work and reports its phases
+ * like one.  Zeros before the first call and after one that failed otherwise; a call refused for its arguments changes nothing. */
 int vr_outlines_timing(vr_ctx* ctx, float ms[4]);
 
 /* ---- connected components: the pieces a contour of a mask slot consists of ----------------------------------------------------------
@@ -1252,8 +1254,10 @@ int vr_components_counters(vr_ctx* ctx, uint64_t out[3]);
 
 /* Device time of the last vr_mask_components in milliseconds, from events on the ctx's stream: ms[0] the pack, ms[1] the runs, their
  * scan, the merge and the flatten, ms[2] the numbering, the statistics, the selection, the writes and the copy back (the host's looks at
- * the counts included), ms[3] the rebuild of what is derived from the written slot, 0 when no slot is written.  Zeros before the first
- * call and after one that failed. */
+ * the counts included), ms[3] the rebuild of what is derived from the written slot.  A call that writes no slot reports ms[0 .. 2] and
+ * ms[3] = 0, also when it fails only because `components` is too small.  A call that writes a slot reports all four, and zeros
+ * when it fails, a table that is too small included (the counters are that call's all the same).  Zeros before the first call and
+ * after one that failed otherwise; a call refused for its arguments changes nothing. */
 int vr_components_timing(vr_ctx* ctx, float ms[4]);
 
 /* ---- resampling: the values of one volume slot on the grid of another --------------------------------------------------------
@@ -1422,7 +1426,9 @@ int vr_mesh_counters(vr_ctx* ctx, uint64_t out[4]);
 
 /* Device time of the last vr_volume_mesh in milliseconds, from events on the ctx's stream: ms[0] the classification into bit-rows,
  * ms[1] the counts and their scans (the host's look at the totals included), ms[2] the vertex emit, ms[3] the triangle emit and the copy
- * back.  Zeros before the first, after one that failed, and for the phases a call did not reach. */
+ * back.  A phase the call did not begin is 0: all four for an empty box, ms[2] and ms[3] for the counting call and for a surface without
+ * a vertex.  A call that fails only because vertices or triangles is too small reports ms[0] and ms[1] like the counting call.  Zeros
+ * before the first call and after one that failed otherwise; a call refused for its arguments changes nothing. */
 int vr_mesh_timing(vr_ctx* ctx, float ms[4]);
 
 /* Volume layout in HBM (A/B measurements; frames and counts are bit-identical in every mode).

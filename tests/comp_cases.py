@@ -144,10 +144,10 @@ def corner_pair(shape=(2, 3, 130)):
 
 # ---- scale: the sizes at which the kernels take another path (tests/test_components.py checks each against its header) --------------
 
-SCAN_TILE = 1024                    # kScanTile (csrc/vr_outline.h): elements per workgroup of a scan
-SPINE_CHUNK = 256                   # tiles per round of scan_spine_kernel's loop (csrc/vr_outline.h): one chunk = 262 144 elements
+SCAN_TILE = 1024                    # kScanTile (csrc/vr_scan.h): elements per workgroup of a scan
+SPINE_CHUNK = 256                   # tiles per round of scan_spine_kernel's loop (csrc/vr_scan.h): one chunk = 262 144 elements
 TOOL_BLOCKS = 512                   # kToolBlocks (csrc/vr_api_tools.h)
-LANE_CAP = 4 * TOOL_BLOCKS * 256    # outline_blocks (csrc/vr_api_outline.h): lanes of a comp_* launch; beyond it the loops go round
+LANE_CAP = 4 * TOOL_BLOCKS * 256    # lane_blocks (csrc/vr_api_tools.h): lanes of a comp_* launch; beyond it the loops go round
 WORDS_PER_PASS = TOOL_BLOCKS * 4    # tool_blocks (csrc/vr_api_tools.h): words of the box per round of the pack and of the write
 AXIS = 65535                        # the longest axis of a volume
 

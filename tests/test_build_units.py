@@ -12,7 +12,8 @@ UNITS = ("vr_api", "vr_march", "vr_fused")
 # the march code, which the C ABI's unit must not reach ...
 MARCH_HEADERS = {"vr_kernels.h", "vr_dp.h", "vr_pw.h", "vr_p2.h", "vr_lt.h", "vr_ray.h", "vr_iso.h", "vr_shadow.h", "vr_bound.h", "vr_launch.h"}
 # ... and the tool kernel headers, which the march units must not reach (beside vr_ctx.h and every vr_api_*.h)
-TOOL_HEADERS = {"vr_hist.h", "vr_grow.h", "vr_bitrows.h", "vr_morph.h", "vr_dist.h", "vr_raster.h", "vr_outline.h", "vr_comp.h"}
+TOOL_HEADERS = {"vr_hist.h", "vr_grow.h", "vr_bitrows.h", "vr_morph.h", "vr_dist.h", "vr_raster.h", "vr_scan.h", "vr_outline.h", "vr_comp.h",
+                "vr_mesh.h"}
 
 
 @pytest.fixture(scope="module")

@@ -183,20 +183,21 @@ def test_scale_thresholds_are_the_headers():
         with open(os.path.join(ROOT, "volumerendering_amd", "csrc", name)) as f:
             return f.read()
 
-    outline, api_outline, api_tools = text("vr_outline.h"), text("vr_api_outline.h"), text("vr_api_tools.h")
-    assert int(re.search(r"constexpr int kScanTile = (\d+);", outline).group(1)) == cc.SCAN_TILE
-    spine = outline[outline.index("void scan_spine_kernel"):outline.index("void scan_apply_kernel")]
+    scan, api_tools = text("vr_scan.h"), text("vr_api_tools.h")
+    assert int(re.search(r"constexpr int kScanTile = (\d+);", scan).group(1)) == cc.SCAN_TILE
+    spine = scan[scan.index("void scan_spine_kernel"):scan.index("void scan_apply_kernel")]
     assert int(re.search(r"for \(unsigned long long b0 = 0; b0 < nb; b0 \+= (\d+)u\)", spine).group(1)) == cc.SPINE_CHUNK
     assert "__shared__ unsigned long long s[%d];" % cc.SPINE_CHUNK in spine
     assert int(re.search(r"constexpr unsigned kToolBlocks = (\d+);", api_tools).group(1)) == cc.TOOL_BLOCKS
-    m = re.search(r"unsigned outline_blocks\(unsigned long long n\) \{ return \(unsigned\)std::min<unsigned long long>\("
-                  r"\(n \+ 255ull\) / 256ull, (\d+)ull \* kToolBlocks\); \}", api_outline)
+    m = re.search(r"unsigned lane_blocks\(unsigned long long n\) \{ return \(unsigned\)std::min<unsigned long long>\("
+                  r"\(n \+ 255ull\) / 256ull, (\d+)ull \* kToolBlocks\); \}", api_tools)
     assert int(m.group(1)) * cc.TOOL_BLOCKS * 256 == cc.LANE_CAP == 524288
     m = re.search(r"unsigned tool_blocks\(unsigned long long n\) \{ return n < (\d+) \? 1u : \(n / (\d+) < kToolBlocks \? "
                   r"\(unsigned\)\(n / (\d+)\) : kToolBlocks\); \}", api_tools)
     assert {int(g) for g in m.groups()} == {4} and 4 * cc.TOOL_BLOCKS == cc.WORDS_PER_PASS == 2048
-    comp = text("vr_comp.h") + text("vr_api_components.h")
-    assert comp.count("dim3(256)") >= 14 and "dim3(outline_blocks(" in comp and "dim3(tool_blocks(bwords))" in comp
+    comp = text("vr_comp.h") + text("vr_api_components.h")  # (its pack and its scans are launched by vr_api_tools.h's tool_pack, tool_scan)
+    assert (comp + api_tools).count("dim3(256)") >= 14 and "dim3(lane_blocks(" in comp and "dim3(tool_blocks(bwords))" in comp
+    assert "tool_pack(" in comp and comp.count("tool_scan(") == 2 and "dim3(tool_blocks(b.box_words))" in api_tools
     assert cc.SCAN_TILE * cc.SPINE_CHUNK == 262144
 
 

@@ -35,12 +35,13 @@ def reference(d, src, before):
                          d.label_channel if d.label_slot >= 0 else None)
 
 
-def check(ctx, d, src, before=None, what=None):
+def check(ctx, d, src, before=None, what=None, want=None):
     """One Context.mask_components against the restatement: the table and the result element for element, the written slot bit for
     bit, the counters.  `src`: the source slot's voxels; `before`: the written slot's before the call (None: an empty slot, or none
-    written).  Returns (the restatement's dict, the downloaded written slot or None)."""
+    written); `want`: the restatement of this very call where a test has it already.  Returns (the restatement's dict, the downloaded
+    written slot or None)."""
     shape = src.shape[:3]
-    want = reference(d, src, before)
+    want = want or reference(d, src, before)
     got = ctx.mask_components(d)
     cnt = ctx.components_counters()
     assert got["result"].as_tuple() == want["result"], (what, got["result"].as_tuple(), want["result"])
@@ -289,3 +290,50 @@ def test_protocol_and_errors(ctx):
     assert want["result"][0] == 0 and not m2[..., 1].any() and not m2[..., 3].any()
     want, _ = check(ctx, good.copy(background=1, connectivity=4), np.zeros(shape + (4,), f32), m2)
     assert want["result"][0] == nz and want["table"][0][4] == 0b011111  # a full slice touches every face but the far z one
+
+
+def test_timing_and_counters_of_every_ending(ctx):
+    """What vr_components_timing and vr_components_counters report after each ending a small input reaches, on (5, 12, 30) voxels: a
+    call that writes no slot times three phases and leaves the fourth at exactly 0.0, with VR_OK or with a table too small; one that
+    writes a slot times all four, and with a table too small none; the counters are the call's own; an argument error leaves both as
+    they were."""
+    shape = (5, 12, 30)
+    nz, ny, nx = shape
+    src = cc.volume(cc.random_set(shape, 0.3, 61), 0, seed=62)
+    m = mc.arbitrary_bits(shape, seed=63)
+    ctx.volume_upload(0, src)
+    ctx.volume_upload(1, m)
+    ctx.volume_upload(2, np.zeros(shape + (4,), f32))
+    d = desc(shape)
+    part = desc(shape, ((2, 1, 1), (nx, ny - 2, 3)))
+    empty = desc(shape, ((3, 2, 1), (3, ny, nz)))
+    (n, cnt_d), (n2, cnt_part) = ((w["result"][0], w["counters"]) for w in (reference(x, src, None) for x in (d, part)))
+    assert n > 10 and 1 < n2 < n and cnt_part[0] < cnt_d[0]
+    table = (capi.Component * n)()
+
+    def ended(x, capacity, rc, began, counted, what):
+        got = ctx.lib.vr_mask_components(ctx.h, C.byref(x.copy(max_components=capacity, components=C.cast(table, C.c_void_p).value if capacity else None)),
+                                         C.byref(capi.ComponentsResult()))
+        ms, cnt = ctx.components_timing(), ctx.components_counters()
+        assert got == rc, (what, got)
+        assert all(t >= 0.0 for t in ms[:began]) and ms[began:] == (0.0,) * (4 - began), (what, ms)
+        assert began < 4 or ms[3] > 0.0, (what, ms)
+        assert cnt == counted, (what, cnt)
+
+    def argument_error(what):
+        before = ctx.components_timing(), ctx.components_counters()
+        assert ctx.lib.vr_mask_components(ctx.h, C.byref(d.copy(connectivity=5)), None) == capi.VR_ERR_INVALID_ARG
+        assert (ctx.components_timing(), ctx.components_counters()) == before, what
+
+    into = dict(dst_slot=1, dst_contour=1, label_slot=1, label_channel=3)
+    ended(d.copy(**into), n, capi.VR_OK, 4, cnt_d, "a slot written, exact capacity")
+    argument_error("after a call that wrote a slot")
+    ended(part, 0, capi.VR_OK, 3, cnt_part, "no slot, the counting call")
+    ended(d, n, capi.VR_OK, 3, cnt_d, "no slot, exact capacity")
+    ended(part, n2 - 1, capi.VR_ERR_INVALID_ARG, 3, cnt_part, "no slot, the table one short")
+    argument_error("after a table too small")
+    ended(empty, 0, capi.VR_OK, 3, (0, 0, 0), "no slot, empty box")
+    ended(d.copy(src_slot=2), 0, capi.VR_OK, 3, (cnt_d[0], 0, 0), "no slot, contour empty in the box")
+    ended(part.copy(**into), n2 - 1, capi.VR_ERR_INVALID_ARG, 0, cnt_part, "a slot written, the table one short")
+    argument_error("after a refused write")
+    ended(empty.copy(**into), 0, capi.VR_OK, 4, (0, 0, 0), "a slot written, empty box")

@@ -7,9 +7,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import comp_cases as cc
 import host_ref as hr
 import mesh_cases as mc
 import mesh_ref as mr
+import outline_ref as orf
+import test_components_gpu as tcg
+import test_outline_gpu as tog
 import vrtest as vt
 from volumerendering_amd import capi
 
@@ -233,14 +237,23 @@ def test_capacity(ctx):
     check(ctx, d, v, want=want)  # (the context is usable)
 
 
+def ended(ctx, began, what):
+    """vr_mesh_timing after a call that began `began` phases: those are timed, the later ones exactly 0.0."""
+    ms = ctx.mesh_timing()
+    assert all(t > 0.0 for t in ms[:began]) and ms[began:] == (0.0,) * (4 - began), (what, ms)
+
+
 def test_argument_errors_leave_the_context_usable(ctx):
+    """... and what vr_mesh_timing and vr_mesh_counters report after each ending a small input reaches: a phase the call never began
+    is exactly 0.0, the counters are the call's own, and an argument error leaves both as they were."""
     shape = (5, 12, 30)
     nz, ny, nx = shape
     v = mc.smooth_noise(shape, seed=31)
     ctx.volume_upload(0, mc.vec4(v, 3, seed=32))
     good = desc(shape, 0.0, 1)
-    check(ctx, good, v)
-    counters = ctx.mesh_counters()
+    _, _, res, _, _ = check(ctx, good, v)
+    ended(ctx, 4, "full call")
+    counters, timing = ctx.mesh_counters(), ctx.mesh_timing()
     verts = np.zeros((4, 3), f32)
     tris = np.zeros((4, 3), np.uint32)
     invalid = [dict(src_slot=-1), dict(src_slot=3), dict(channel=-1), dict(channel=4), dict(level=np.nan), dict(level=np.inf), dict(level=-np.inf),
@@ -255,6 +268,21 @@ def test_argument_errors_leave_the_context_usable(ctx):
     assert ctx.lib.vr_volume_mesh(None, C.byref(good), None) == capi.VR_ERR_INVALID_ARG
     assert ctx.lib.vr_mesh_counters(ctx.h, None) == capi.VR_ERR_INVALID_ARG
     assert ctx.lib.vr_mesh_timing(ctx.h, None) == capi.VR_ERR_INVALID_ARG
+    assert ctx.mesh_counters() == counters and ctx.mesh_timing() == timing
+    # the counting call and a buffer one element short end behind the counts; both report their own counters
+    part = desc(shape, 0.0, 1, box=((2, 1, 1), (nx, ny - 2, 3)))
+    n2, q2 = mr.extract(v, 0.0, 1, tuple(part.box_lo), tuple(part.box_hi))["result"][:2]
+    assert 0 < n2 < res.n_vertices
+    for d, caps, rc in ((part, (0, 0), capi.VR_OK), (good, (res.n_vertices - 1, res.n_triangles), capi.VR_ERR_INVALID_ARG),
+                        (part, (n2, q2 - 1), capi.VR_ERR_INVALID_ARG)):
+        assert raw(ctx, d, *caps)[0] == rc, caps
+        ended(ctx, 2, caps)
+        assert ctx.mesh_counters()[0] == (nx * ny * nz if d is good else (nx - 2) * (ny - 3) * 2), caps
+        before = ctx.mesh_counters(), ctx.mesh_timing()
+        assert raw(ctx, d.copy(cap=2), *caps)[0] == capi.VR_ERR_INVALID_ARG
+        assert (ctx.mesh_counters(), ctx.mesh_timing()) == before, caps
+    assert raw(ctx, good, res.n_vertices, res.n_triangles)[0] == capi.VR_OK  # exact capacity
+    ended(ctx, 4, "exact capacity")
     assert ctx.mesh_counters() == counters
     with capi.Context(W, H, 0) as empty:
         assert empty.lib.vr_volume_mesh(empty.h, C.byref(good), None) == capi.VR_ERR_NOT_READY
@@ -271,12 +299,18 @@ def test_argument_errors_leave_the_context_usable(ctx):
     for box, cap in ((((3, 2, 1), (3, 9, 3)), 1), (((0, 0, 2), (nx, ny, 2)), 0)):
         _, _, res, cnt, _ = check(ctx, desc(shape, 0.0, cap, box=box), v, box)
         assert res.as_tuple() == EMPTY and cnt == (0, 0, 0, 0)
+        ended(ctx, 0, box)
+        assert raw(ctx, good.copy(channel=4), 0, 0)[0] == capi.VR_ERR_INVALID_ARG
+        assert ctx.mesh_counters() == (0, 0, 0, 0) and ctx.mesh_timing() == (0.0,) * 4
     _, _, res, cnt, _ = check(ctx, desc(shape, 0.0, 0, box=((0, 3, 0), (nx, 4, nz))), v, "one row thick")
     assert res.as_tuple()[:2] == (0, 0) and res.inside > 0 and cnt[0] == nx * nz
     _, _, res, cnt, _ = check(ctx, desc(shape, 0.0, 1, box=((0, 3, 0), (nx, 4, nz))), v, "one row thick, capped")
     assert res.n_triangles > 0
     _, _, res, cnt, _ = check(ctx, desc(shape, 1e30, 1), v, "nothing inside")
     assert res.as_tuple() == EMPTY and cnt[0] == nx * ny * nz
+    ended(ctx, 2, "nothing inside")
+    assert raw(ctx, desc(shape, 1e30, 1), 4, 4)[0] == capi.VR_OK  # (no crossing edge: nothing to emit into the buffers either)
+    ended(ctx, 2, "nothing inside, with buffers")
 
 
 def test_side_effects():
@@ -316,6 +350,34 @@ def test_side_effects():
         c.render(variant)
         assert np.array_equal(vt.bits(c.download()[0]), vt.bits(frame))
         assert (c.counters(), c.last_kernel_flavour()) == earlier[:2]
+
+
+def test_one_scan_buffer_serves_three_tools(ctx):
+    """Contour tracing, connected components and surface extraction take the tile sums of their scans from one buffer of the context.
+    Two volumes, (60, 36, 4) voxels -- 2160 words of one voxel row each, three scan tiles, in every tool -- and (4, 6, 10); the tools
+    run in turn on the small and the large one, each behind each of the others, and every output equals its restatement: a scan that
+    read the tile sums another call left behind fails here."""
+    calls = {}
+    for slot, shape in enumerate(((60, 36, 4), (4, 6, 10))):
+        nz, ny, nx = shape
+        z, y, x = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+        ball = (f32(0.4) * max(shape) - np.sqrt((x - 0.5 * nx) ** 2 + (y - 0.45 * ny) ** 2 + (z - 0.5 * nz) ** 2)).astype(f32)
+        state = mc.vec4(ball, 3, seed=75 + slot)
+        state[..., 0] = cc.random_set(shape, 0.5, 71 + slot)
+        ctx.volume_upload(slot, state)
+        m = orf.members(state)
+        o, k, s = tog.desc(shape, src_slot=slot), tcg.desc(shape, src_slot=slot), desc(shape, 0.0, slot=slot)
+        wo, wk, ws = tog.reference(o, m), tcg.reference(k, state, None), mr.extract(ball, 0.0, 0, *whole(shape))
+        calls["o", slot] = lambda o=o, m=m, wo=wo: tog.check(ctx, o, m, want=wo)
+        calls["k", slot] = lambda k=k, state=state, wk=wk: tcg.check(ctx, k, state, want=wk)
+        calls["s", slot] = lambda s=s, ball=ball, ws=ws: check(ctx, s, ball, want=ws)
+        if slot == 0:  # (not vacuous: the scans over the words, the corners and the runs chain over several tiles; there is a surface)
+            assert nz * ny > 2 * 1024 and wo["result"][0] > 2 * 1024 and wk["counters"][1] > 2 * 1024 and ws["result"][0] > 100
+    order = "oksoskok"  # every tool behind each of the others
+    assert {a + b for a, b in zip(order, order[1:])} >= {"ok", "os", "ko", "ks", "so", "sk"}
+    for first in (1, 0):  # small, large, small, ..; then large, small, large, ..: every tool meets both sizes behind every other
+        for i, tool in enumerate(order):
+            calls[tool, (first + i) % 2]()
 
 
 SWEEP = mc.sweep(40)

@@ -312,6 +312,44 @@ def test_argument_errors_leave_the_context_usable(ctx):
     assert polys_ == [] and res.as_tuple() == EMPTY and cnt == (0, 0, 0)
 
 
+def test_timing_and_counters_of_every_ending(ctx):
+    """What vr_outlines_timing and vr_outlines_counters report after each ending a small input reaches, on (5, 12, 30) voxels with one
+    non-empty contour: a phase the call never began is exactly 0.0, one it began is timed; the counters are the call's own; an
+    argument error leaves both as they were."""
+    shape = (5, 12, 30)
+    nz, ny, nx = shape
+    m = oc.blobs(shape, seed=51)
+    m[1:] = False
+    ctx.volume_upload(0, oc.volume(m, seed=52))
+    d = desc(shape, CT, None, (488, 488))
+    part = desc(shape, CT, ((2, 1, 1), (nx, ny - 2, 3)), (488, 488))
+    (n, q), (n2, q2) = (reference(x, m)["result"][:2] for x in (d, part))
+    assert n > 8 and q > 1 and 0 < n2 < n
+
+    def ended(call, rc, began, counted, what):
+        got = call[0]
+        ms, cnt = ctx.outlines_timing(), ctx.outlines_counters()
+        assert got == rc, (what, got)
+        assert all(t > 0.0 for t in ms[:began]) and ms[began:] == (0.0,) * (4 - began), (what, ms)
+        assert cnt[:2] == counted and (cnt[2] > 0) == (counted != (0, 0)), (what, cnt)
+
+    def argument_error(what):
+        before = ctx.outlines_timing(), ctx.outlines_counters()
+        assert raw(ctx, d.copy(contours=16), n, q)[0] == capi.VR_ERR_INVALID_ARG
+        assert (ctx.outlines_timing(), ctx.outlines_counters()) == before, what
+
+    ended(raw(ctx, d, n, q), capi.VR_OK, 4, (n, q), "exact capacity")
+    argument_error("after a full call")
+    ended(raw(ctx, desc(shape, CT, ((3, 2, 1), (3, 9, 3)), (488, 488)), n, q), capi.VR_OK, 0, (0, 0), "empty box")
+    argument_error("after an empty box")
+    ended(raw(ctx, part, 0, 0), capi.VR_OK, 4, (n2, q2), "counting call")
+    ended(raw(ctx, d.copy(contours=0b0010), n, q), capi.VR_OK, 2, (0, 0), "contour empty in the box")
+    argument_error("after a call without a corner")
+    ended(raw(ctx, d, n - 1, q), capi.VR_ERR_INVALID_ARG, 4, (n, q), "one point short")
+    ended(raw(ctx, part, n2, q2 - 1), capi.VR_ERR_INVALID_ARG, 4, (n2, q2), "one polygon short")
+    argument_error("after a buffer too small")
+
+
 SWEEP = oc.sweep(40)
 
 

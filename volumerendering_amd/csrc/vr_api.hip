@@ -22,6 +22,8 @@
 #include "vr_dist.h"
 // Polygon rasterisation (vr_mask_polygons): exact integer work on the same bit-rows, compiled once as well
 #include "vr_raster.h"
+// The prefix scan of the three tools below (tool_scan, vr_api_tools.h): integer work, compiled once as well
+#include "vr_scan.h"
 // Contour tracing (vr_mask_outlines): the inverse of the raster, exact integer work on the same bit-rows, compiled once as well
 #include "vr_outline.h"
 // Connected components (vr_mask_components): a union-find over the runs of the same bit-rows, compiled once as well

@@ -1,8 +1,9 @@
-// vr_api_components.h -- connected components of a mask contour on the device (vr_mask_components; the kernels are vr_comp.h's): the
-// checks of a descriptor, the scan's three launches, the choice of keep_largest's winners and the call itself.  When it writes a slot it
-// is a data-preparation call like vr_mask_morph (mask_tool_call: drains, runs on the context's stream, ends with bind_voxels or
-// refresh_bricks, synchronous on return); when it writes none it is a data call like vr_mask_outlines and rebuilds nothing.  It looks at
-// device words between its phases (the node count, the component count, the passing sizes).  Part of vr_api.hip's translation unit.
+// vr_api_components.h -- connected components of a mask contour on the device (vr_mask_components; the kernels are vr_comp.h's, the
+// scan vr_scan.h's): the checks of a descriptor, the choice of keep_largest's winners and the call itself.  When it writes a slot it is
+// a data-preparation call like vr_mask_morph (mask_tool_call: drains, runs on the context's stream, ends with bind_voxels or
+// refresh_bricks, synchronous on return); when it writes none it is a data call like vr_mask_outlines (data_tool_call) and rebuilds
+// nothing.  It looks at device words between its phases (the node count, the component count, the passing sizes).  Part of
+// vr_api.hip's translation unit.
 #pragma once
 
 namespace {
@@ -49,19 +50,6 @@ int check_components(vr_ctx* c, const vr_components_desc* d)
     return m.data ? check_same_dims(c, w, "destination", m, "source", v) : VR_OK;
 }
 
-// out[i] = in[0] + .. + in[i - 1] for i < n (in == out is allowed), *d_total = the sum of all, on the stream; n > 0
-int comp_scan(vr_ctx* c, const unsigned* in, unsigned long long n, unsigned* out, unsigned long long* d_total)
-{
-    CompState& K = c->comp;
-    const unsigned long long nb = (n + kScanTile - 1) / kScanTile;
-    if (const int rc = grow(c, K.sums, (size_t)nb, true)) return rc;
-    hipLaunchKernelGGL(scan_sums_kernel, dim3((unsigned)nb), dim3(256), 0, c->stream, in, n, K.sums.p);
-    hipLaunchKernelGGL(scan_spine_kernel, dim3(1), dim3(256), 0, c->stream, K.sums.p, nb, d_total);
-    hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)nb), dim3(256), 0, c->stream, in, n, (const unsigned long long*)K.sums.p, out);
-    VR_HIP(c, hipGetLastError());
-    return VR_OK;
-}
-
 // keep_largest: the (at most) K passing components with the most voxels, ties to the smaller number; pass[i] = voxels, or 0
 void comp_winners(const std::vector<unsigned long long>& pass, unsigned keep, CompFilter* F)
 {
@@ -76,16 +64,15 @@ void comp_winners(const std::vector<unsigned long long>& pass, unsigned keep, Co
 }
 
 // The call itself, every argument checked and the device drained.  dst: the written slot's voxels, nullptr when no slot is written;
-// `fresh`: they were allocated and zeroed by this call.  Records report.ev[0 .. 3] before it returns VR_OK, or VR_ERR_INVALID_ARG for a
-// table that is too small, or VR_ERR_UNSUPPORTED for a label map of more than VR_COMP_MAX_LABEL components (*counted = true: the result
-// is filled, nothing is written).
-int run_components(vr_ctx* c, const vr_components_desc& d, float4* dst, bool fresh, vr_components_result* result, bool* counted)
+// `fresh`: they were allocated and zeroed by this call.  P takes its three phases; when a slot is written a fourth begins behind them
+// (the shell's: the slot's rebuild).  A table that is too small (VR_ERR_INVALID_ARG) and a label map of more than VR_COMP_MAX_LABEL
+// components (VR_ERR_UNSUPPORTED) fill the result and the counters and write nothing.
+int run_components(vr_ctx* c, const vr_components_desc& d, float4* dst, bool fresh, vr_components_result* result, Phases& P)
 {
     CompState& K = c->comp;
     hipStream_t s = c->stream;
     const DevVolume& v = c->vols[d.src_slot].vol;
     if (result) std::memset(result, 0, sizeof *result);
-    *counted = false;
     const bool want_contour = dst && d.dst_slot >= 0, want_labels = dst && d.label_slot >= 0;
 
     CompGrid G;
@@ -109,23 +96,22 @@ int run_components(vr_ctx* c, const vr_components_desc& d, float4* dst, bool fre
     hw.packed = hw.result = CountBox::empty();
 
     // pack
-    VR_HIP(c, hipEventRecord(K.report.ev[0], s));
+    VR_HIP(c, P.begin());
     VR_HIP(c, K.io.push(s));
     VR_HIP(c, hipMemsetAsync(S, 0, (want_contour ? 2 : 1) * nw * sizeof(unsigned long long), s));
-    if (bwords != 0) {
-        const BitPack P = {v.data, d.src_contour, G.b, S, &dw->packed};
-        hipLaunchKernelGGL(bit_pack_kernel, dim3(tool_blocks(bwords)), dim3(256), 0, s, P);
-        if (d.background) hipLaunchKernelGGL(comp_complement_kernel, dim3(outline_blocks(bwords)), dim3(256), 0, s, G.b, S);
+    if (const int rc = tool_pack(c, v.data, d.src_contour, G.b, S, &dw->packed)) return rc;
+    if (bwords != 0 && d.background) {
+        hipLaunchKernelGGL(comp_complement_kernel, dim3(lane_blocks(bwords)), dim3(256), 0, s, G.b, S);
         VR_HIP(c, hipGetLastError());
     }
-    VR_HIP(c, hipEventRecord(K.report.ev[1], s));
+    VR_HIP(c, P.begin());
 
     // the runs, their scan, the merge, the flatten
     unsigned long long nodes = 0;
     if (bwords != 0) {
-        hipLaunchKernelGGL(comp_starts_kernel, dim3(outline_blocks(bwords)), dim3(256), 0, s, G, K.base.p);
+        hipLaunchKernelGGL(comp_starts_kernel, dim3(lane_blocks(bwords)), dim3(256), 0, s, G, K.base.p);
         VR_HIP(c, hipGetLastError());
-        if (const int rc = comp_scan(c, K.base.p, bwords, K.base.p, &dw->nodes)) return rc;
+        if (const int rc = tool_scan(c, K.base.p, bwords, K.base.p, &dw->nodes)) return rc;
         VR_HIP(c, hipMemcpyAsync(&hw.nodes, &dw->nodes, sizeof hw.nodes, hipMemcpyDeviceToHost, s));
         VR_HIP(c, hipStreamSynchronize(s));
         nodes = hw.nodes;
@@ -133,23 +119,23 @@ int run_components(vr_ctx* c, const vr_components_desc& d, float4* dst, bool fre
     if (nodes > kCompNodesMax) return fail(c, VR_ERR_UNSUPPORTED, "vr_mask_components: more than 2^32 - 1 run nodes in one call (" + std::to_string(nodes) + ")");
     const unsigned n = (unsigned)nodes;
     CompNodes N = {K.base.p, n, nullptr, nullptr, nullptr, nullptr};
-    const unsigned nblocks = outline_blocks(n);
+    const unsigned nblocks = lane_blocks(n);
     if (n != 0) {
         for (DevBuf<unsigned>* b : {&K.parent, &K.root, &K.row, &K.ab})
             if (const int rc = grow(c, *b, n, true)) return rc;
         N.parent = K.parent.p, N.root = K.root.p, N.row = K.row.p, N.ab = K.ab.p;
-        hipLaunchKernelGGL(comp_runs_kernel, dim3(outline_blocks(bwords)), dim3(256), 0, s, G, N);
+        hipLaunchKernelGGL(comp_runs_kernel, dim3(lane_blocks(bwords)), dim3(256), 0, s, G, N);
         hipLaunchKernelGGL(comp_merge_kernel, dim3(nblocks), dim3(256), 0, s, G, N, dw);
         hipLaunchKernelGGL(comp_flatten_kernel, dim3(nblocks), dim3(256), 0, s, (const unsigned*)N.parent, n, N.root);
         VR_HIP(c, hipGetLastError());
     }
-    VR_HIP(c, hipEventRecord(K.report.ev[2], s));
+    VR_HIP(c, P.begin());
 
     // the numbering
     if (n != 0) {
         hipLaunchKernelGGL(comp_leaders_kernel, dim3(nblocks), dim3(256), 0, s, (const unsigned*)N.root, n, N.parent);
         VR_HIP(c, hipGetLastError());
-        if (const int rc = comp_scan(c, N.parent, n, N.parent, &dw->components)) return rc;
+        if (const int rc = tool_scan(c, N.parent, n, N.parent, &dw->components)) return rc;
     }
     VR_HIP(c, K.io.pull(s));
     VR_HIP(c, hipStreamSynchronize(s));
@@ -166,7 +152,7 @@ int run_components(vr_ctx* c, const vr_components_desc& d, float4* dst, bool fre
         F.by_winners = d.keep_largest != 0;
         if (F.by_winners)
             if (const int rc = grow(c, K.pass, (size_t)ncomp, true)) return rc;
-        const unsigned cblocks = outline_blocks(ncomp);
+        const unsigned cblocks = lane_blocks(ncomp);
         hipLaunchKernelGGL(comp_init_kernel, dim3(nblocks), dim3(256), 0, s, G, N, K.table.p);
         hipLaunchKernelGGL(comp_stats_kernel, dim3(nblocks), dim3(256), 0, s, G, N, K.table.p);
         hipLaunchKernelGGL(comp_pass_kernel, dim3(cblocks), dim3(256), 0, s, (const vr_component*)K.table.p, ncomp, F, K.sel.p, K.pass.p, dw);
@@ -190,16 +176,11 @@ int run_components(vr_ctx* c, const vr_components_desc& d, float4* dst, bool fre
         result->largest = hw.largest;
         copy_count_box(hw.result, &result->selected_voxels, result->lo, result->hi);
     }
-    *counted = true;
-    if (d.max_components != 0 && d.max_components < ncomp) {
-        VR_HIP(c, hipEventRecord(K.report.ev[3], s));
-        return fail(c, VR_ERR_INVALID_ARG, "vr_mask_components: the mask has " + std::to_string(ncomp) + " components, the table holds " +
-                                               std::to_string(d.max_components));
-    }
-    if (want_labels && ncomp > VR_COMP_MAX_LABEL) {
-        VR_HIP(c, hipEventRecord(K.report.ev[3], s));
+    if (d.max_components != 0 && d.max_components < ncomp)
+        return short_of_room(c, P, "vr_mask_components: the mask has " + std::to_string(ncomp) + " components, the table holds " +
+                                       std::to_string(d.max_components));
+    if (want_labels && ncomp > VR_COMP_MAX_LABEL)
         return fail(c, VR_ERR_UNSUPPORTED, "vr_mask_components: a label map of " + std::to_string(ncomp) + " components (labels are f32: at most 2^24)");
-    }
 
     // the writes, the copy back
     if (dst && bwords != 0) {
@@ -210,7 +191,8 @@ int run_components(vr_ctx* c, const vr_components_desc& d, float4* dst, bool fre
     }
     if (d.max_components != 0 && ncomp != 0)
         VR_HIP(c, hipMemcpyAsync(d.components, K.table.p, (size_t)ncomp * sizeof(vr_component), hipMemcpyDeviceToHost, s));
-    VR_HIP(c, hipEventRecord(K.report.ev[3], s));
+    if (!dst) return VR_OK;  // (the shell ends the third phase and waits for it)
+    VR_HIP(c, P.begin());
     VR_HIP(c, hipStreamSynchronize(s));
     return VR_OK;
 }
@@ -242,24 +224,10 @@ int vr_mask_components(vr_ctx* c, const vr_components_desc* desc, vr_components_
     if (const int rc = check_components(c, desc)) return rc;
     ToolReport& report = c->comp.report;
     const int written = comp_written_slot(*desc);
-    bool counted = false;
-    if (written >= 0)
-        return mask_tool_call(c, "vr_mask_components", desc->src_slot, written, report,
-                              [&](float4* dst, bool fresh) { return run_components(c, *desc, dst, fresh, result, &counted); });
-    if (const int rc = drain(c)) return rc;  // renders on the caller's streams may still be in flight; the bit-row scratch is taken
-    (void)hipGetLastError();
-    for (Event& e : report.ev)  // (first use)
-        if (!e) VR_HIP(c, e.create());
-    for (float& t : report.ms) t = 0.0f;
-    const int rc = run_components(c, *desc, nullptr, false, result, &counted);
-    if (rc != VR_OK && !counted) {
-        (void)hipStreamSynchronize(c->stream);
-        return rc;
-    }
-    VR_HIP(c, hipEventSynchronize(report.ev[3]));
-    for (int i = 0; i < 3; ++i)
-        if (hipEventElapsedTime(&report.ms[i], report.ev[i], report.ev[i + 1]) != hipSuccess) report.ms[i] = 0.0f;
-    return rc;
+    if (written < 0) return data_tool_call(c, report, [&](Phases& P) { return run_components(c, *desc, nullptr, false, result, P); });
+    Phases P = {report, c->stream};
+    return mask_tool_call(c, "vr_mask_components", desc->src_slot, written, report,
+                          [&](float4* dst, bool fresh) { return run_components(c, *desc, dst, fresh, result, P); });
 }
 
 int vr_components_counters(vr_ctx* c, uint64_t out[3]) { return tool_counters(c, &vr_ctx::comp, out, "vr_components_counters"); }

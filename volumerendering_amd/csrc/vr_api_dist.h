@@ -111,21 +111,15 @@ int run_dist(vr_ctx* c, const vr_dist_desc& d, float4* dst, vr_dist_result* resu
     P.a = words;
     P.probe = probe ? words + nw : nullptr;
     P.w = S.io.d;
-    const BitPack pack = {v.data, d.src_contour, W, words, &S.io.d.p->src};
     const unsigned blocks = tool_blocks(W.box_words);
 
     VR_HIP(c, hipEventRecord(S.report.ev[0], s));
     *S.io.h.p = DistWords{CountBox::empty(), CountBox::empty(), 0ull, 0ull, kDistNone, 0ull};
     VR_HIP(c, S.io.push(s));
     VR_HIP(c, hipMemsetAsync(words, 0, (probe ? 2 : 1) * nw * sizeof(unsigned long long), s));
-    if (W.box_words != 0) {
-        hipLaunchKernelGGL(bit_pack_kernel, dim3(blocks), dim3(256), 0, s, pack);
-        if (probe) {
-            const BitPack probe_pack = {c->vols[d.probe_slot].vol.data, d.probe_contour, W, words + nw, &S.io.d.p->probe};
-            hipLaunchKernelGGL(bit_pack_kernel, dim3(blocks), dim3(256), 0, s, probe_pack);
-        }
-        VR_HIP(c, hipGetLastError());
-    }
+    if (const int rc = tool_pack(c, v.data, d.src_contour, W, words, &S.io.d.p->src)) return rc;
+    if (probe)
+        if (const int rc = tool_pack(c, c->vols[d.probe_slot].vol.data, d.probe_contour, W, words + nw, &S.io.d.p->probe)) return rc;
     VR_HIP(c, S.io.pull(s));
     VR_HIP(c, hipStreamSynchronize(s));
     const CountBox packed = S.io.h.p->src;

@@ -1,7 +1,7 @@
-// vr_api_mesh.h -- surface extraction on the device (vr_volume_mesh; the kernels are vr_mesh.h's): the checks of a descriptor and the
-// call itself.  A data call that writes no slot, like vr_mask_outlines: it drains the device, runs on the context's stream, looks at
-// the device words between the counting and the emitting phases and is synchronous on return; no launch's bookkeeping and no other
-// tool's report is touched.  Part of vr_api.hip's translation unit.
+// vr_api_mesh.h -- surface extraction on the device (vr_volume_mesh; the kernels are vr_mesh.h's, the scan vr_scan.h's): the checks of
+// a descriptor and the call itself.  A data call that writes no slot, like vr_mask_outlines (data_tool_call, vr_api_tools.h): it drains
+// the device, runs on the context's stream, looks at the device words between the counting and the emitting phases and is synchronous
+// on return; no launch's bookkeeping and no other tool's report is touched.  Part of vr_api.hip's translation unit.
 #pragma once
 
 namespace {
@@ -23,9 +23,8 @@ int check_mesh(vr_ctx* c, const vr_mesh_desc* d)
     return check_box(c, w, d->box_lo, d->box_hi, c->vols[d->src_slot].vol);
 }
 
-// The call itself, every argument checked and the device drained.  Records report.ev[0 .. 3]; *recorded = how many of them.
-// *counted: the result and the counters are those of this call (it got as far as counting).
-int run_mesh(vr_ctx* c, const vr_mesh_desc& d, vr_mesh_result* result, int* recorded, bool* counted)
+// The call itself, every argument checked and the device drained; P takes its (at most four) phases.
+int run_mesh(vr_ctx* c, const vr_mesh_desc& d, vr_mesh_result* result, Phases& P)
 {
     MeshState& M = c->mesh;
     hipStream_t s = c->stream;
@@ -52,7 +51,6 @@ int run_mesh(vr_ctx* c, const vr_mesh_desc& d, vr_mesh_result* result, int* reco
     auto done = [&](const MeshWords& w) {
         M.report.counters[0] = w.stats[0], M.report.counters[1] = w.stats[1], M.report.counters[2] = w.stats[2];
         M.active_cells = w.cells.voxels;
-        *counted = true;
     };
     if (box == 0) return done(MeshWords{}), VR_OK;  // (no real point: nothing is inside)
 
@@ -70,7 +68,7 @@ int run_mesh(vr_ctx* c, const vr_mesh_desc& d, vr_mesh_result* result, int* reco
     unsigned long long* const bits = c->bit_row_scratch.p;
 
     // pack
-    VR_HIP(c, hipEventRecord(M.report.ev[(*recorded)++], s));
+    VR_HIP(c, P.begin());
     const bool plain = plain_form(c) || d.channel != 3;
     if (!plain) {  // exact settling by the slot's range records (of .a: channel 3)
         G.bnx = skip_bricks(v.nx);
@@ -81,15 +79,15 @@ int run_mesh(vr_ctx* c, const vr_mesh_desc& d, vr_mesh_result* result, int* reco
     if (plain) hipLaunchKernelGGL(mesh_pack_kernel<true>, dim3(tool_blocks(G.words)), dim3(256), 0, s, G, bits, dw);
     else hipLaunchKernelGGL(mesh_pack_kernel<false>, dim3(tool_blocks(G.words)), dim3(256), 0, s, G, bits, dw);
     VR_HIP(c, hipGetLastError());
-    VR_HIP(c, hipEventRecord(M.report.ev[(*recorded)++], s));
+    VR_HIP(c, P.begin());
 
     // the crossings and the cases of every word, their two scans (a lattice thinner than 2 points on an axis has no cells)
     if (cells) {
-        hipLaunchKernelGGL(mesh_count_kernel, dim3(outline_blocks(G.words)), dim3(256), 0, s, G, (const unsigned long long*)bits, M.masks.p, M.vbase.p,
+        hipLaunchKernelGGL(mesh_count_kernel, dim3(lane_blocks(G.words)), dim3(256), 0, s, G, (const unsigned long long*)bits, M.masks.p, M.vbase.p,
                            M.tbase.p, dw);
         VR_HIP(c, hipGetLastError());
-        if (const int rc = outline_scan(c, M.vbase.p, G.words, M.vbase.p, &dw->vertices)) return rc;
-        if (const int rc = outline_scan(c, M.tbase.p, G.words, M.tbase.p, &dw->triangles)) return rc;
+        if (const int rc = tool_scan(c, M.vbase.p, G.words, M.vbase.p, &dw->vertices)) return rc;
+        if (const int rc = tool_scan(c, M.tbase.p, G.words, M.tbase.p, &dw->triangles)) return rc;
     }
     VR_HIP(c, M.io.pull(s));
     VR_HIP(c, hipStreamSynchronize(s));
@@ -106,18 +104,18 @@ int run_mesh(vr_ctx* c, const vr_mesh_desc& d, vr_mesh_result* result, int* reco
     done(hw);
     if (d.max_vertices == 0 && d.max_triangles == 0) return VR_OK;  // the counting call
     if (d.max_vertices < nv || d.max_triangles < nt)
-        return fail(c, VR_ERR_INVALID_ARG, "vr_volume_mesh: the surface needs " + std::to_string(nv) + " vertices and " + std::to_string(nt) +
-                                               " triangles, the buffers hold " + std::to_string(d.max_vertices) + " and " + std::to_string(d.max_triangles));
+        return short_of_room(c, P, "vr_volume_mesh: the surface needs " + std::to_string(nv) + " vertices and " + std::to_string(nt) +
+                                        " triangles, the buffers hold " + std::to_string(d.max_vertices) + " and " + std::to_string(d.max_triangles));
     if (nv == 0) return VR_OK;  // (no crossing edge: no triangle either)
 
     // emit, copy back
     if (const int rc = grow(c, M.vertices, (size_t)nv * 3u, true)) return rc;
     if (const int rc = grow(c, M.triangles, (size_t)nt * 3u, true)) return rc;
-    VR_HIP(c, hipEventRecord(M.report.ev[(*recorded)++], s));
+    VR_HIP(c, P.begin());
     hipLaunchKernelGGL(mesh_vertex_kernel, dim3(tool_blocks(G.words)), dim3(256), 0, s, G, (const unsigned long long*)M.masks.p, (const unsigned*)M.vbase.p,
                        (unsigned)nv, M.vertices.p);
     VR_HIP(c, hipGetLastError());
-    VR_HIP(c, hipEventRecord(M.report.ev[(*recorded)++], s));
+    VR_HIP(c, P.begin());
     hipLaunchKernelGGL(mesh_triangle_kernel, dim3(tool_blocks(G.words)), dim3(256), 0, s, G, (const unsigned long long*)bits,
                        (const unsigned long long*)M.masks.p, (const unsigned*)M.vbase.p, (const unsigned*)M.tbase.p, (unsigned)nt, M.triangles.p);
     VR_HIP(c, hipGetLastError());
@@ -148,27 +146,7 @@ int vr_volume_mesh(vr_ctx* c, const vr_mesh_desc* desc, vr_mesh_result* result)
 {
     if (!c) return VR_ERR_INVALID_ARG;
     if (const int rc = check_mesh(c, desc)) return rc;
-    if (const int rc = drain(c)) return rc;  // renders on the caller's streams may still be in flight; the bit-row scratch is taken
-    (void)hipGetLastError();
-    ToolReport& report = c->mesh.report;
-    for (Event& e : report.ev)  // (first use)
-        if (!e) VR_HIP(c, e.create());
-    for (float& t : report.ms) t = 0.0f;
-    int recorded = 0;
-    bool counted = false;
-    const int rc = run_mesh(c, *desc, result, &recorded, &counted);
-    if (rc != VR_OK && !(rc == VR_ERR_INVALID_ARG && counted)) {  // (counted: the work was done and the buffers are too small)
-        (void)hipStreamSynchronize(c->stream);
-        return rc;
-    }
-    // the phases that ran: a call that ended early (an empty box, the counting call) leaves the later ones at zero
-    if (recorded > 0) {
-        VR_HIP(c, hipEventRecord(report.ev[recorded], c->stream));
-        VR_HIP(c, hipEventSynchronize(report.ev[recorded]));
-        for (int i = 0; i < recorded; ++i)
-            if (hipEventElapsedTime(&report.ms[i], report.ev[i], report.ev[i + 1]) != hipSuccess) report.ms[i] = 0.0f;
-    }
-    return rc;
+    return data_tool_call(c, c->mesh.report, [&](Phases& P) { return run_mesh(c, *desc, result, P); });
 }
 
 int vr_mesh_counters(vr_ctx* c, uint64_t out[4])

@@ -102,7 +102,6 @@ int run_morph(vr_ctx* c, const vr_morph_desc& d, float4* dst, bool fresh, vr_mor
     if (!M.h_rows) VR_HIP(c, M.h_rows.reserve((size_t)kMorphSide * kMorphSide, true));
     VR_HIP(c, M.io.first_use());
     P.w = M.io.d;
-    const BitPack pack = {v.data, d.src_contour, W, A, &M.io.d.p->src};
     const bool plain = plain_form(c);
     const bool morph = d.op != VR_MORPH_NONE;
     const int rad[3] = {morph ? d.element.radius[0] : 0, morph ? d.element.radius[1] : 0, morph ? d.element.radius[2] : 0};
@@ -124,10 +123,7 @@ int run_morph(vr_ctx* c, const vr_morph_desc& d, float4* dst, bool fresh, vr_mor
     *M.io.h.p = MorphWords{CountBox::empty(), CountBox::empty()};
     VR_HIP(c, M.io.push(s));
     VR_HIP(c, hipMemsetAsync(A, 0, nw * sizeof(unsigned long long), s));
-    if (W.box_words != 0) {
-        hipLaunchKernelGGL(bit_pack_kernel, dim3(blocks), dim3(256), 0, s, pack);
-        VR_HIP(c, hipGetLastError());
-    }
+    if (const int rc = tool_pack(c, v.data, d.src_contour, W, A, &M.io.d.p->src)) return rc;
     VR_HIP(c, M.io.pull(s));
     VR_HIP(c, hipStreamSynchronize(s));
     const MorphWords packed = *M.io.h.p;

@@ -1,7 +1,8 @@
-// vr_api_outline.h -- contour tracing on the device (vr_mask_outlines; the kernels are vr_outline.h's): the checks of a descriptor, the
-// scan's three launches and the call itself.  A data call that writes no slot: it drains the device, runs on the context's stream, looks
-// at a device word between its phases (the node count, the rounds' outcome, the polygon count) and is synchronous on return; nothing
-// derived from a slot is rebuilt and no launch's bookkeeping is touched.  Part of vr_api.hip's translation unit.
+// vr_api_outline.h -- contour tracing on the device (vr_mask_outlines; the kernels are vr_outline.h's, the scan vr_scan.h's): the checks
+// of a descriptor and the call itself.  A data call that writes no slot (data_tool_call, vr_api_tools.h): it drains the device, runs on
+// the context's stream, looks at a device word between its phases (the node count, the rounds' outcome, the polygon count) and is
+// synchronous on return; nothing derived from a slot is rebuilt and no launch's bookkeeping is touched.  Part of vr_api.hip's
+// translation unit.
 #pragma once
 
 namespace {
@@ -33,21 +34,6 @@ int check_outlines(vr_ctx* c, const vr_outlines_desc* d)
     return VR_OK;
 }
 
-// out[i] = in[0] + .. + in[i - 1] for i < n (in == out is allowed), *d_total = the sum of all, on the stream; n > 0
-int outline_scan(vr_ctx* c, const unsigned* in, unsigned long long n, unsigned* out, unsigned long long* d_total)
-{
-    OutlineState& O = c->outline;
-    const unsigned long long nb = (n + kScanTile - 1) / kScanTile;
-    if (const int rc = grow(c, O.sums, (size_t)nb, true)) return rc;
-    hipLaunchKernelGGL(scan_sums_kernel, dim3((unsigned)nb), dim3(256), 0, c->stream, in, n, O.sums.p);
-    hipLaunchKernelGGL(scan_spine_kernel, dim3(1), dim3(256), 0, c->stream, O.sums.p, nb, d_total);
-    hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)nb), dim3(256), 0, c->stream, in, n, (const unsigned long long*)O.sums.p, out);
-    VR_HIP(c, hipGetLastError());
-    return VR_OK;
-}
-
-unsigned outline_blocks(unsigned long long n) { return (unsigned)std::min<unsigned long long>((n + 255ull) / 256ull, 4ull * kToolBlocks); }
-
 // fills *result from the device words of a call (pulled and the stream synchronised)
 void outline_result(const OutlineWords& w, vr_outlines_result* result)
 {
@@ -61,8 +47,8 @@ void outline_result(const OutlineWords& w, vr_outlines_result* result)
     }
 }
 
-// The call itself, every argument checked and the device drained.  Records report.ev[0 .. 4]; *recorded = how many of them.
-int run_outlines(vr_ctx* c, const vr_outlines_desc& d, vr_outlines_result* result, int* recorded)
+// The call itself, every argument checked and the device drained; P takes its (at most four) phases.
+int run_outlines(vr_ctx* c, const vr_outlines_desc& d, vr_outlines_result* result, Phases& P)
 {
     OutlineState& O = c->outline;
     hipStream_t s = c->stream;
@@ -102,20 +88,17 @@ int run_outlines(vr_ctx* c, const vr_outlines_desc& d, vr_outlines_result* resul
     for (int k = 0; k < G.nc; ++k) G.bits[k] = c->bit_row_scratch.p + (size_t)k * nw;
 
     // pack
-    VR_HIP(c, hipEventRecord(O.report.ev[(*recorded)++], s));
+    VR_HIP(c, P.begin());
     VR_HIP(c, O.io.push(s));
     VR_HIP(c, hipMemsetAsync(c->bit_row_scratch.p, 0, (size_t)G.nc * nw * sizeof(unsigned long long), s));
-    for (int k = 0; k < G.nc; ++k) {
-        BitPack P = {v.data, G.kmap[k], G.b, c->bit_row_scratch.p + (size_t)k * nw, &dw->packed[k]};
-        hipLaunchKernelGGL(bit_pack_kernel, dim3(tool_blocks(G.b.box_words)), dim3(256), 0, s, P);
-    }
-    VR_HIP(c, hipGetLastError());
-    VR_HIP(c, hipEventRecord(O.report.ev[(*recorded)++], s));
+    for (int k = 0; k < G.nc; ++k)
+        if (const int rc = tool_pack(c, v.data, G.kmap[k], G.b, c->bit_row_scratch.p + (size_t)k * nw, &dw->packed[k])) return rc;
+    VR_HIP(c, P.begin());
 
     // corners, their scan, the links
-    hipLaunchKernelGGL(outline_corners_kernel, dim3(outline_blocks(G.vwords)), dim3(256), 0, s, G, O.masks.p, O.base.p);
+    hipLaunchKernelGGL(outline_corners_kernel, dim3(lane_blocks(G.vwords)), dim3(256), 0, s, G, O.masks.p, O.base.p);
     VR_HIP(c, hipGetLastError());
-    if (const int rc = outline_scan(c, O.base.p, G.vwords, O.base.p, &dw->nodes)) return rc;
+    if (const int rc = tool_scan(c, O.base.p, G.vwords, O.base.p, &dw->nodes)) return rc;
     VR_HIP(c, hipMemcpyAsync(&hw.nodes, &dw->nodes, sizeof hw.nodes, hipMemcpyDeviceToHost, s));
     VR_HIP(c, hipStreamSynchronize(s));
     const unsigned long long nodes = hw.nodes;
@@ -130,11 +113,11 @@ int run_outlines(vr_ctx* c, const vr_outlines_desc& d, vr_outlines_result* resul
     for (auto& b : O.st)
         if (const int rc = grow(c, b, n, true)) return rc;
     const OutlineNodes N = {O.masks.p, O.base.p, n, O.pred.p, O.pt.p, O.meta.p};
-    const unsigned blocks = outline_blocks(n);
+    const unsigned blocks = lane_blocks(n);
     VR_HIP(c, hipMemsetAsync(O.pred.p, 0, (size_t)n * sizeof(unsigned), s));
     hipLaunchKernelGGL(outline_link_kernel, dim3(blocks), dim3(256), 0, s, G, N, dw);
     VR_HIP(c, hipGetLastError());
-    VR_HIP(c, hipEventRecord(O.report.ev[(*recorded)++], s));
+    VR_HIP(c, P.begin());
 
     // leader and rank: one launch per round; the plain form runs every round a loop of all the nodes would need
     unsigned fixed = 0;
@@ -152,13 +135,13 @@ int run_outlines(vr_ctx* c, const vr_outlines_desc& d, vr_outlines_result* resul
         VR_HIP(c, hipStreamSynchronize(s));
         if (!hw.changed[r]) break;
     }
-    VR_HIP(c, hipEventRecord(O.report.ev[(*recorded)++], s));
+    VR_HIP(c, P.begin());
 
     // the polygons: leaders, their scan, the counts of each contour
     const uint4* const st = O.st[cur].p;
     hipLaunchKernelGGL(outline_leaders_kernel, dim3(blocks), dim3(256), 0, s, st, n, O.pidx.p);
     VR_HIP(c, hipGetLastError());
-    if (const int rc = outline_scan(c, O.pidx.p, n, O.pidx.p, &dw->polygons)) return rc;
+    if (const int rc = tool_scan(c, O.pidx.p, n, O.pidx.p, &dw->polygons)) return rc;
     hipLaunchKernelGGL(outline_totals_kernel, dim3(1), dim3(64), 0, s, G, (const unsigned*)O.base.p, (const unsigned*)O.pidx.p, dw);
     VR_HIP(c, hipGetLastError());
     VR_HIP(c, O.io.pull(s));
@@ -169,15 +152,15 @@ int run_outlines(vr_ctx* c, const vr_outlines_desc& d, vr_outlines_result* resul
     done(nodes, polygons, rounds);
     if (d.max_points == 0 && d.max_polygons == 0) return VR_OK;  // the counting call
     if (d.max_points < nodes || d.max_polygons < polygons)
-        return fail(c, VR_ERR_INVALID_ARG, "vr_mask_outlines: the mask needs " + std::to_string(nodes) + " points and " + std::to_string(polygons) +
-                                               " polygons, the buffers hold " + std::to_string(d.max_points) + " and " + std::to_string(d.max_polygons));
+        return short_of_room(c, P, "vr_mask_outlines: the mask needs " + std::to_string(nodes) + " points and " + std::to_string(polygons) +
+                                        " polygons, the buffers hold " + std::to_string(d.max_points) + " and " + std::to_string(d.max_polygons));
 
     // emit into the idle half of the rounds' buffers (16 bytes a node: 8 for its point, at most 4 for its share of a polygon), copy back
     int2* const points = reinterpret_cast<int2*>(O.st[cur ^ 1].p);
     vr_polygon* const polys = reinterpret_cast<vr_polygon*>(points + n);
     hipLaunchKernelGGL(outline_counts_kernel, dim3(blocks), dim3(256), 0, s, st, (const unsigned*)O.pred.p, (const unsigned*)O.pidx.p, n, O.pcount.p);
     VR_HIP(c, hipGetLastError());
-    if (const int rc = outline_scan(c, O.pcount.p, polygons, O.pcount.p, &dw->points)) return rc;
+    if (const int rc = tool_scan(c, O.pcount.p, polygons, O.pcount.p, &dw->points)) return rc;
     hipLaunchKernelGGL(outline_emit_kernel, dim3(blocks), dim3(256), 0, s, st, N, (const unsigned*)O.pidx.p, (const unsigned*)O.pcount.p, points, polys);
     VR_HIP(c, hipGetLastError());
     VR_HIP(c, hipMemcpyAsync(d.points, points, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost, s));
@@ -208,26 +191,7 @@ int vr_mask_outlines(vr_ctx* c, const vr_outlines_desc* desc, vr_outlines_result
 {
     if (!c) return VR_ERR_INVALID_ARG;
     if (const int rc = check_outlines(c, desc)) return rc;
-    if (const int rc = drain(c)) return rc;  // renders on the caller's streams may still be in flight; the bit-row scratch is taken
-    (void)hipGetLastError();
-    ToolReport& report = c->outline.report;
-    for (Event& e : report.ev)  // (first use)
-        if (!e) VR_HIP(c, e.create());
-    for (float& t : report.ms) t = 0.0f;
-    int recorded = 0;
-    const int rc = run_outlines(c, *desc, result, &recorded);
-    if (rc != VR_OK && !(rc == VR_ERR_INVALID_ARG && recorded == 4)) {  // (recorded == 4: the work was done and the buffers are too small)
-        (void)hipStreamSynchronize(c->stream);
-        return rc;
-    }
-    // the phases that ran: a call that ended early (an empty box, no corner) leaves the later ones at zero
-    if (recorded > 0) {
-        VR_HIP(c, hipEventRecord(report.ev[recorded], c->stream));
-        VR_HIP(c, hipEventSynchronize(report.ev[recorded]));
-        for (int i = 0; i < recorded; ++i)
-            if (hipEventElapsedTime(&report.ms[i], report.ev[i], report.ev[i + 1]) != hipSuccess) report.ms[i] = 0.0f;
-    }
-    return rc;
+    return data_tool_call(c, c->outline.report, [&](Phases& P) { return run_outlines(c, *desc, result, P); });
 }
 
 int vr_outlines_counters(vr_ctx* c, uint64_t out[3]) { return tool_counters(c, &vr_ctx::outline, out, "vr_outlines_counters"); }

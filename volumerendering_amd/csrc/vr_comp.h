@@ -5,7 +5,7 @@
 //
 // Set: S is packed by bit_pack_kernel (background: complemented under the box mask, comp_complement_kernel); it is zero outside the box.
 //
-// Nodes (comp_starts_kernel, the scan of vr_outline.h, comp_runs_kernel): a NODE is a maximal run of set bits along x in one row of the
+// Nodes (comp_starts_kernel, the scan of vr_scan.h, comp_runs_kernel): a NODE is a maximal run of set bits along x in one row of the
 // box; it may span words.  The runs that start in a word are w & ~((w << 1) | carry), carry = bit 63 of the word before it in the row.
 // The scan of the per-word start counts over the box's words, which bit_box_word numbers x-fastest, then y, then z, numbers the nodes in
 // the order of their first voxels: node order is `first`-voxel order and nothing is ever sorted.  The run that holds a set bit x is the
@@ -39,7 +39,7 @@
 // Bit counts are the compiler's builtins, not HIP's wrappers (vr_outline.h says why).
 #pragma once
 #include "vr_bitrows.h"
-#include "vr_outline.h"  // the scan kernels, bits_below
+#include "vr_outline.h"  // bits_below
 
 namespace vr {
 

@@ -379,7 +379,9 @@ struct VolumeSlot {
     BuiltOn proj_built;
 };
 
-// A mask tool's report on its last call: three counters, and its three phases and refresh_bricks timed between five events (vr_api_tools.h).
+// A voxel tool's report on its last call: three counters, and up to four phases (a mask tool's three and refresh_bricks) timed between
+// five events.  open_report and close_report (vr_api_tools.h) begin and end it; a data call that writes no slot marks its events through
+// Phases.
 struct ToolReport {
     Event ev[5];
     unsigned long long counters[3] = {0, 0, 0};
@@ -433,7 +435,6 @@ struct RasterState {
 struct OutlineState {
     DevBuf<ulonglong2> masks;            // per vertex word: the vertices with one corner, with two
     DevBuf<unsigned> base;               // per vertex word: its corners, then the corners before it
-    DevBuf<unsigned long long> sums;     // the scans' tile sums
     DevBuf<unsigned> pred, meta;         // per corner node: the node before it on its loop; its slice and contour
     DevBuf<int2> pt;                     // ... its point
     DevBuf<uint4> st[2];                 // ... (leader, rank, jump) of the doubling rounds, written in turn; the idle one takes the output
@@ -446,7 +447,6 @@ struct OutlineState {
 // vr_components_counters and vr_components_timing report.  Of vr_ctx::bit_row_scratch it takes two buffers: S and R.
 struct CompState {
     DevBuf<unsigned> base;               // per word of the box: the runs that start in it, then the nodes before it
-    DevBuf<unsigned long long> sums;     // the scans' tile sums
     DevBuf<unsigned> parent, root;       // per node: the union-find forest, then the roots before it; its root
     DevBuf<unsigned> row, ab;            // ... its row of the box, its first and last x
     DevBuf<vr_component> table;          // per component
@@ -571,6 +571,11 @@ struct vr_ctx {
     // The bit-row scratch of the five mask tools below (vr_bitrows.h), grown to the most words a call has asked for.  Each call drains
     // the device, zeroes the buffers it takes before it reads them and is synchronous on return: no two uses are ever live.
     DevBuf<unsigned long long> bit_row_scratch;
+    // The tile sums of a prefix scan (tool_scan, vr_api_tools.h), grown to the most tiles a scan has had: contour tracing, connected
+    // components and surface extraction take it, one scan after the other.  Every one of them has drained the device before its first
+    // scan, and all scans run on the context's stream; a regrow frees the old buffer with hipFree, which waits for the scans already
+    // on the stream.  So no scan ever reads another's sums.
+    DevBuf<unsigned long long> scan_sums;
     MorphState morph;  // mask morphology (vr_mask_morph)
     DistState dist;    // distance maps (vr_mask_distance)
     RasterState raster;  // polygon rasterisation (vr_mask_polygons)

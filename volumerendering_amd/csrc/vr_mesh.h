@@ -27,7 +27,7 @@
 // corner's offset x + 2 y + 4 z; a shift by one bit with the carry of the next word for x) give the seven CROSSING MASKS
 // X_m = c_0 ^ c_m, masked to the edges (p, p + d) whose far end is a lattice point: bit i of X_m = the vertex of key (p, m).  The word's
 // vertices are the popcounts of the seven; its triangles one per tetrahedron with an odd number of inside corners and two per tetrahedron
-// with two, over the word's cells.  Two scans (scan_*_kernel, vr_outline.h) give every word its vertex base and triangle base in key
+// with two, over the word's cells.  Two scans (scan_*_kernel, vr_scan.h) give every word its vertex base and triangle base in key
 // order: nothing is sorted.  (Every lattice edge with both ends in a lattice of at least 2 points per axis belongs to some cell: the
 // cell p - s for an s in {0,1}^3 with s . d = 0 that keeps the cell inside; a thinner lattice has no cells and the host stops there.)
 //
