@@ -1431,6 +1431,87 @@ int vr_mesh_counters(vr_ctx* ctx, uint64_t out[4]);
  * before the first call and after one that failed otherwise; a call refused for its arguments changes nothing. */
 int vr_mesh_timing(vr_ctx* ctx, float ms[4]);
 
+/* ---- separable filters: the values of a channel smoothed or differentiated, without leaving the device ---------------------------------
+ * Every tool above reads a channel as it was uploaded; this one changes its values: up to three 1-D correlations with caller-given
+ * weights, along x, then y, then z, of one component of a volume slot, restricted to a box, written as f32 into one component of a volume
+ * slot -- on the device (csrc/vr_filter.h).  Smoothing before vr_volume_mesh, VR_VARIANT_ISO, vr_segment_grow or a threshold, and Gaussian
+ * derivatives for the lit shader's gradients, are filters of this kind (vr_filter_gaussian makes their weights).
+ *   Passes: the pass along axis a exists iff taps[a] != NULL, with radius r = radius[a] and weights w[0 .. 2r] = taps[a][0 .. 2r] (a NULL
+ *     taps[a] goes with radius[a] == 0; a given taps[a] with radius 0 is the one-tap pass out = w[0] * in).  It maps a field `in` to a
+ *     field `out`, every value f32:
+ *         acc = w[0] * in[i - r]                                     (one rounded product)
+ *         for t = 1 .. 2r:  acc = fmaf(w[t], in[i - r + t], acc)     (one fused multiply-add each, in this order)
+ *         out[i] = acc
+ *     Every tap after the first is an explicit fmaf: vr_set_arithmetic plays no part, and the result is the same in both modes.
+ *   Borders: an index i - r + t outside 0 .. n_a - 1 reads the clamped index under VR_FILTER_CLAMP (scipy.ndimage's mode="nearest") and
+ *     border_value under VR_FILTER_CONSTANT (mode="constant", cval) -- in every pass, for the source and for an intermediate field alike:
+ *     the meaning of correlate1d applied three times.  The faces are the VOLUME's, not the box's: the box only limits which voxels are
+ *     stored, and a pass reads real values outside it.
+ *   Source and destination: the first pass reads component src_channel of src_slot; the value after the last pass is stored in component
+ *     dst_channel of every voxel of the half-open box of dst_slot.  With no pass at all the stored value is the source value, its bits
+ *     unchanged.  The other three components of the destination keep their bits, and so does every voxel outside the box.  The result is
+ *     that of reading the whole source before anything is written: src_slot == dst_slot with src_channel == dst_channel is valid.  An
+ *     empty dst_slot is created with the source's nx, ny, nz and every component +0.0f; one of other dimensions is VR_ERR_INVALID_ARG.
+ *   Values: denormals are kept; NaN and +-inf travel as IEEE 754 says (an fmaf with a NaN gives a NaN, whose payload is not specified).
+ *     No value of a tap, of border_value or of a voxel is an error.
+ *   Result: stored = the voxels of the box; nonfinite = those whose stored value is NaN or +-inf; lo_value / hi_value = the least and the
+ *     greatest finite stored value under the order of the value bits that puts -0.0f below +0.0f (exact, independent of scheduling),
+ *     +0.0f both when there is none.
+ *   Counters (vr_filter_counters): out[0] = voxels of the box; out[1] = the values the passes computed, summed over the passes -- the pass
+ *     along axis a computes the box grown on every LATER axis that has a pass by that axis' radius and clipped to the volume; out[2] = the
+ *     number of passes.  An empty box gives zeros.
+ * Kernel forms: by default a pass loads every input value once per workgroup tile, plus the halo, into LDS and applies the taps from there;
+ * flavour 1 of vr_set_kernel_flavour reads the 2r + 1 inputs of every output straight from memory.  The destination, the result and all
+ * three counters are identical across the forms and the volume layouts. */
+#define VR_FILTER_MAX_RADIUS 32
+#define VR_FILTER_CLAMP    0   /* an index beyond a face reads the face's voxel (scipy mode="nearest") */
+#define VR_FILTER_CONSTANT 1   /* ... reads border_value (scipy mode="constant")                       */
+typedef struct vr_filter_desc {
+    int32_t src_slot, src_channel;     /* component 0 .. 3 of a filled slot                                        */
+    int32_t dst_slot, dst_channel;     /* may be the same slot, and the same channel                               */
+    int32_t radius[3];                 /* per axis x, y, z: 0 .. VR_FILTER_MAX_RADIUS; 0 where taps[a] is NULL     */
+    const float* taps[3];              /* host memory, 2 * radius[a] + 1 weights; NULL = no pass along that axis   */
+    int32_t border;  float border_value;
+    int32_t box_lo[3], box_hi[3];      /* voxel box of the OUTPUT, half open                                       */
+} vr_filter_desc;
+typedef struct vr_filter_result {
+    uint64_t stored, nonfinite;        /* voxels of the box; those whose stored value is NaN or +-inf              */
+    float    lo_value, hi_value;       /* least / greatest finite stored value; +0.0f both if there is none        */
+} vr_filter_result;
+
+/* Fills *out for the whole volume of src_slot: the given slots and channels, VR_FILTER_CLAMP, border_value 0, no taps (a copy until the
+ * caller sets some) and the box (0,0,0) .. (nx,ny,nz).  Pure host arithmetic; VR_ERR_INVALID_ARG for a NULL pointer or a slot or channel
+ * out of range, VR_ERR_NOT_READY for an empty source slot. */
+int vr_filter_whole(const vr_ctx* ctx, int src_slot, int src_channel, int dst_slot, int dst_channel, vr_filter_desc* out);
+
+/* The weights of a Gaussian (order 0) or of its first derivative (order 1) with standard deviation sigma in voxels, cut off at
+ * r = (int)(truncate * sigma + 0.5) -- scipy.ndimage.gaussian_filter1d's kernel.  Pure host arithmetic in double; needs no context.
+ *   phi[x] = exp(-0.5 * x * x / (sigma * sigma)) for x = 0 .. r;  S = phi[0] + 2 * (phi[1] + .. + phi[r]), summed in ascending x.
+ *   order 0: taps[r + x] = taps[r - x] = (float)(phi[x] / S).
+ *   order 1: taps[r + x] = (float)((x / (sigma * sigma)) * phi[x] / S), taps[r - x] = -taps[r + x], taps[r] = +0.0f: correlated with
+ *     increasing data they give a positive derivative (gaussian_filter1d(order=1)), in 1 / voxel.
+ * *radius = r whenever the arguments are valid.  VR_ERR_INVALID_ARG: radius is NULL; a sigma or truncate that is not finite and > 0; an
+ * order other than 0 or 1; r > VR_FILTER_MAX_RADIUS; and, with *radius set all the same, taps NULL or capacity < 2r + 1 -- the counting call. */
+int vr_filter_gaussian(double sigma, int order, double truncate, float* taps, int capacity, int* radius);
+
+/* Does the work; `result` may be NULL.  A data-preparation call exactly like vr_mask_distance: it waits for everything in flight, runs on
+ * the ctx's own stream, rebuilds what is derived from the destination slot's voxels as an upload does and is synchronous on return.  The
+ * weights are copied before it returns.  What the reporting calls say about the last march, slice, histogram or other tool stays as it
+ * was.  An empty box writes nothing and is VR_OK.
+ * Checked before anything is enqueued or a slot is touched.  VR_ERR_INVALID_ARG: a NULL ctx or descriptor; a slot or channel out of range;
+ * a radius outside 0 .. VR_FILTER_MAX_RADIUS, or a nonzero radius with NULL taps; an unknown border; a destination slot of other
+ * dimensions; a box that is not 0 <= lo <= hi <= n on every axis.  VR_ERR_NOT_READY: the source slot is empty.  VR_ERR_OOM: the working
+ * buffers -- two f32 fields, of the first and of the second pass' region -- could not be allocated.  A failed call changes no slot. */
+int vr_volume_filter(vr_ctx* ctx, const vr_filter_desc* desc, vr_filter_result* result);
+
+/* Counters of the last vr_volume_filter (as described above).  Zeros before the first. */
+int vr_filter_counters(vr_ctx* ctx, uint64_t out[3]);
+
+/* Device time of the last vr_volume_filter in milliseconds, from events on the ctx's stream: ms[0] the first pass that runs, ms[1] the
+ * remaining passes, ms[2] the write into the destination and the result words, ms[3] the rebuild of what is derived from the destination
+ * slot.  Zeros before the first and after one that failed. */
+int vr_filter_timing(vr_ctx* ctx, float ms[4]);
+
 /* Volume layout in HBM (A/B measurements; frames and counts are bit-identical in every mode).
  *   0  default: the march kernels gather from a BRICKED copy of every slot -- the vec4 voxels and a scalar f32 density plane
  *      (what fetches that consume .a alone read: BasicVolumeApp.wgsl:171, the density / dose fetches of the other shaders)

@@ -49,6 +49,8 @@ OUTLINE_SPLIT, OUTLINE_JOIN = 0, 1                                          # vr
 COMP_FACES, COMP_ALL, COMP_PLANE_FACES, COMP_PLANE_ALL = 6, 26, 4, 8              # vr_components_desc.connectivity (include/vr.h)
 COMP_MAX_KEEP, COMP_MAX_LABEL = 64, 1 << 24                                 # of keep_largest; of n_components with a label map
 RESAMPLE_LINEAR, RESAMPLE_NEAREST = 0, 1                                    # vr_resample_desc.filter (include/vr.h)
+FILTER_MAX_RADIUS = 32                                                      # of vr_filter_desc.radius (include/vr.h)
+FILTER_CLAMP, FILTER_CONSTANT = 0, 1                                        # vr_filter_desc.border
 DIST_MAX_SPACING, DIST_MAX_LIMIT, DIST_MAX_EXTENT = 1 << 20, 1 << 31, 1 << 30  # of a spacing, the limit, (hi - lo) * spacing per axis
 
 # every symbol include/vr.h declares (tests check that the library exports each of them)
@@ -76,6 +78,7 @@ ABI_SYMBOLS = [
     "vr_components_whole", "vr_mask_components", "vr_components_counters", "vr_components_timing",
     "vr_resample_identity", "vr_resample_between", "vr_volume_resample", "vr_resample_counters", "vr_resample_timing",
     "vr_mesh_whole", "vr_volume_mesh", "vr_mesh_counters", "vr_mesh_timing",
+    "vr_filter_whole", "vr_filter_gaussian", "vr_volume_filter", "vr_filter_counters", "vr_filter_timing",
 ]
 
 
@@ -353,6 +356,38 @@ class MeshResult(C.Structure):
                 tuple(int(x) for x in self.hi))
 
 
+class FilterDesc(C.Structure):
+    """struct vr_filter_desc (include/vr.h): the source and destination slots and channels, per axis the radius and the weights (set by
+    Context.volume_filter from its `taps`), the border rule and value, and the voxel box of the output."""
+    _fields_ = [
+        ("src_slot", C.c_int32), ("src_channel", C.c_int32), ("dst_slot", C.c_int32), ("dst_channel", C.c_int32),
+        ("radius", C.c_int32 * 3), ("taps", C.c_void_p * 3), ("border", C.c_int32), ("border_value", C.c_float),
+        ("box_lo", C.c_int32 * 3), ("box_hi", C.c_int32 * 3),
+    ]
+
+    def copy(self, **over) -> "FilterDesc":
+        """A copy with the given fields replaced (radius / box_lo / box_hi from any sequence of three integers, taps from three
+        addresses or None)."""
+        d = FilterDesc.from_buffer_copy(bytes(self))
+        for k, v in over.items():
+            if k in ("radius", "box_lo", "box_hi"):
+                v = (C.c_int32 * 3)(*[int(x) for x in v])
+            if k == "taps":
+                v = (C.c_void_p * 3)(*v)
+            setattr(d, k, v)
+        return d
+
+
+class FilterResult(C.Structure):
+    """struct vr_filter_result: the voxels of the box, those stored as NaN or +-inf, the least and greatest finite stored value."""
+    _fields_ = [("stored", C.c_uint64), ("nonfinite", C.c_uint64), ("lo_value", C.c_float), ("hi_value", C.c_float)]
+
+    def as_tuple(self):
+        """(stored, nonfinite, the bits of lo_value, the bits of hi_value)"""
+        lo, hi = np.array([self.lo_value, self.hi_value], np.float32).view(np.uint32)
+        return int(self.stored), int(self.nonfinite), int(lo), int(hi)
+
+
 class Component(C.Structure):
     """struct vr_component (include/vr.h): a component's voxels, half-open bounding box, first voxel (x, y, z) and the faces of the box
     it touches."""
@@ -562,6 +597,11 @@ def load() -> C.CDLL:
     lib.vr_volume_mesh.argtypes = [vp, C.POINTER(MeshDesc), C.POINTER(MeshResult)]
     lib.vr_mesh_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 4)]
     lib.vr_mesh_timing.argtypes = [vp, C.POINTER(C.c_float * 4)]
+    lib.vr_filter_whole.argtypes = [vp, i32, i32, i32, i32, C.POINTER(FilterDesc)]
+    lib.vr_filter_gaussian.argtypes = [C.c_double, i32, C.c_double, fp, i32, C.POINTER(C.c_int)]
+    lib.vr_volume_filter.argtypes = [vp, C.POINTER(FilterDesc), C.POINTER(FilterResult)]
+    lib.vr_filter_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
+    lib.vr_filter_timing.argtypes = [vp, C.POINTER(C.c_float * 4)]
     lib.vr_present_async.argtypes = [vp, vp, vp, vp]
     lib.vr_present_tiles_async.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
     lib.vr_hint_frames_in_flight.argtypes = [vp, i32]
@@ -1124,6 +1164,33 @@ class Context:
         """(classify / pack, counts + scans, vertex emit, triangle emit + copy back) of the last volume_mesh in ms of device time."""
         return self._tool_timing(self.lib.vr_mesh_timing)
 
+    def filter_whole(self, src_slot: int, src_channel: int, dst_slot: int, dst_channel: int) -> FilterDesc:
+        """vr_filter_whole: the descriptor of a filter of component src_channel of volume src_slot over its whole volume into component
+        dst_channel of volume dst_slot: CLAMP, border_value 0, no pass (edit with copy; volume_filter takes the weights)."""
+        d = FilterDesc()
+        self._chk(self.lib.vr_filter_whole(self.h, src_slot, src_channel, dst_slot, dst_channel, C.byref(d)))
+        return d
+
+    def volume_filter(self, desc: FilterDesc, taps=(None, None, None)) -> FilterResult:
+        """vr_volume_filter: up to three 1-D correlations along x, y, z of a component into a component (synchronous).  taps: per axis
+        an odd number of float32 weights (filter_gaussian's, say) or None for no pass along it; they set the descriptor's radius and
+        taps fields, whose own values are ignored."""
+        arrays = [None if t is None else np.ascontiguousarray(t, dtype=np.float32).ravel() for t in taps]
+        if len(arrays) != 3 or any(a is not None and a.size % 2 == 0 for a in arrays):
+            raise ValueError("taps: three entries, each None or an odd number of weights")
+        d = desc.copy(radius=[0 if a is None else a.size // 2 for a in arrays], taps=[None if a is None else a.ctypes.data for a in arrays])
+        out = FilterResult()
+        self._chk(self.lib.vr_volume_filter(self.h, C.byref(d), C.byref(out)))  # (arrays live until here)
+        return out
+
+    def filter_counters(self):
+        """(voxels of the box, values the passes computed, passes) of the last volume_filter."""
+        return self._tool_counters(self.lib.vr_filter_counters)
+
+    def filter_timing(self):
+        """(first pass, remaining passes, write + result words, refresh) of the last volume_filter in ms of device time."""
+        return self._tool_timing(self.lib.vr_filter_timing)
+
     def set_volume_layout(self, mode: int):
         """0 bricked copy (default), 1 the reference's vec4 voxels only, 3 x-fastest voxels + density plane (2 was removed)."""
         self._chk(self.lib.vr_set_volume_layout(self.h, mode))
@@ -1171,6 +1238,21 @@ def dist_whole(ctx: "Context", src_slot: int, src_contour: int, dst_slot: int, d
     d = DistDesc()
     ctx._chk(ctx.lib.vr_dist_whole(ctx.h, src_slot, src_contour, dst_slot, dst_channel, mode, C.byref(d)))
     return d
+
+
+def filter_gaussian(sigma: float, order: int = 0, truncate: float = 4.0) -> np.ndarray:
+    """vr_filter_gaussian: the 2 r + 1 float32 weights of a Gaussian of standard deviation `sigma` voxels (order 0) or of its first
+    derivative (order 1), r = int(truncate * sigma + 0.5): the counting call, then the call that stores.  Host arithmetic: needs no
+    context and no device."""
+    lib, r = load(), C.c_int(-1)
+    lib.vr_filter_gaussian(float(sigma), int(order), float(truncate), None, 0, C.byref(r))
+    if r.value < 0:
+        raise VrError(VR_ERR_INVALID_ARG, f"vr_filter_gaussian: sigma {sigma}, order {order}, truncate {truncate} (radius at most {FILTER_MAX_RADIUS})")
+    taps = np.zeros(2 * r.value + 1, np.float32)
+    rc = lib.vr_filter_gaussian(float(sigma), int(order), float(truncate), taps.ctypes.data_as(C.POINTER(C.c_float)), taps.size, C.byref(r))
+    if rc != VR_OK:
+        raise VrError(rc, "vr_filter_gaussian")
+    return taps
 
 
 def resample_between(src: Grid, dst: Grid, dst_to_src=None, **over) -> ResampleDesc:

@@ -408,6 +408,89 @@ int Application::ExtractSurface(int slot, int channel, float level, int cap, con
     return ExtractSurface(slot, channel, level, cap, out, spacing);
 }
 
+namespace {
+
+// The Gaussian weights of Smooth and GradientOfGaussian per axis and order ([order][axis]; truncate 4) and their radii: VR_OK, or
+// VR_ERR_INVALID_ARG for a sigma that is negative or not finite, a spacing that is not finite and positive or a radius beyond the
+// maximum.  An axis whose radius is 0 has no weights.
+struct GaussianTaps {
+    float w[2][3][2 * VR_FILTER_MAX_RADIUS + 1];
+    int radius[3];
+};
+int gaussianTaps(double sigmaMm, const double spacing[3], GaussianTaps& g)
+{
+    if (!std::isfinite(sigmaMm) || sigmaMm < 0.0) return VR_ERR_INVALID_ARG;
+    for (int a = 0; a < 3; ++a) {
+        const double sp = spacing ? spacing[a] : 1.0;
+        if (!std::isfinite(sp) || !(sp > 0.0)) return VR_ERR_INVALID_ARG;
+        const double sigma = sigmaMm / sp;
+        g.radius[a] = 0;
+        if (!(4.0 * sigma + 0.5 >= 1.0)) continue;  // (radius 0, sigma 0 included: no pass)
+        for (int order = 0; order < 2; ++order)
+            if (const int rc = vr_filter_gaussian(sigma, order, 4.0, g.w[order][a], 2 * VR_FILTER_MAX_RADIUS + 1, &g.radius[a])) return rc;
+    }
+    return VR_OK;
+}
+
+}  // namespace
+
+int Application::Smooth(int srcSlot, int srcChannel, int dstSlot, int dstChannel, double sigmaMm, const double spacing[3], vr_filter_result* out)
+{
+    if (!p_Ctx) return VR_ERR_NOT_READY;
+    GaussianTaps g;
+    int rc = gaussianTaps(sigmaMm, spacing, g);
+    if (rc != VR_OK) return rc;
+    vr_filter_desc d;
+    rc = vr_filter_whole(p_Ctx, srcSlot, srcChannel, dstSlot, dstChannel, &d);
+    if (rc != VR_OK) return rc;
+    for (int a = 0; a < 3; ++a) {
+        d.radius[a] = g.radius[a];
+        d.taps[a] = g.radius[a] != 0 ? g.w[0][a] : nullptr;
+    }
+    rc = vr_volume_filter(p_Ctx, &d, out);
+    if (rc != VR_OK) m_Error = vr_last_error(p_Ctx);
+    return rc;
+}
+
+int Application::Smooth(int srcSlot, int srcChannel, int dstSlot, int dstChannel, double sigmaMm, const VolumeFileDcm& grid, vr_filter_result* out)
+{
+    const DicomVolumeParams p = grid.GetVolumeParams();
+    const double spacing[3] = {p.PixelSpacing[0], p.PixelSpacing[1], p.SliceThickness};
+    return Smooth(srcSlot, srcChannel, dstSlot, dstChannel, sigmaMm, spacing, out);
+}
+
+int Application::GradientOfGaussian(int slot, double sigmaMm, const double spacing[3])
+{
+    if (!p_Ctx) return VR_ERR_NOT_READY;
+    GaussianTaps g;
+    int rc = gaussianTaps(sigmaMm, spacing, g);
+    if (rc != VR_OK) return rc;
+    for (int a = 0; a < 3; ++a)
+        if (g.radius[a] == 0) return VR_ERR_INVALID_ARG;
+    for (int k = 0; k < 3; ++k) {  // component k: the derivative along axis k of the smoothed component 3
+        vr_filter_desc d;
+        rc = vr_filter_whole(p_Ctx, slot, 3, slot, k, &d);
+        if (rc != VR_OK) return rc;
+        for (int a = 0; a < 3; ++a) {
+            d.radius[a] = g.radius[a];
+            d.taps[a] = g.w[a == k ? 1 : 0][a];
+        }
+        rc = vr_volume_filter(p_Ctx, &d, nullptr);
+        if (rc != VR_OK) {
+            m_Error = vr_last_error(p_Ctx);
+            return rc;
+        }
+    }
+    return VR_OK;
+}
+
+int Application::GradientOfGaussian(int slot, double sigmaMm, const VolumeFileDcm& grid)
+{
+    const DicomVolumeParams p = grid.GetVolumeParams();
+    const double spacing[3] = {p.PixelSpacing[0], p.PixelSpacing[1], p.SliceThickness};
+    return GradientOfGaussian(slot, sigmaMm, spacing);
+}
+
 int Application::Pick(uint32_t x, uint32_t y, vr_pick_result* out)
 {
     if (!p_Ctx || !p_App) return VR_ERR_NOT_READY;

@@ -127,6 +127,21 @@ public:
     // positive.
     int ExtractSurface(int slot, int channel, float level, int cap, SurfaceMesh& out, const double spacing[3] = nullptr);
     int ExtractSurface(int slot, int channel, float level, int cap, const VolumeFileDcm& grid, SurfaceMesh& out);
+    // Component srcChannel of volume srcSlot smoothed by a Gaussian of sigmaMm millimetres over the whole volume into component dstChannel
+    // of volume dstSlot, on the device (vr_filter_gaussian + vr_volume_filter of include/vr.h; VR_FILTER_CLAMP): per axis sigma in voxels =
+    // sigmaMm / spacing[a] (x, y, z in millimetres; nullptr = 1), truncate 4; with `grid` its PixelSpacing and SliceThickness.  An axis
+    // whose radius comes out 0 gets no pass; sigmaMm == 0 copies.  Source and destination may coincide.  `out` may be nullptr.
+    // VR_ERR_INVALID_ARG for a sigma that is negative or not finite, a spacing that is not finite and positive, or a radius beyond
+    // VR_FILTER_MAX_RADIUS voxels on some axis.
+    int Smooth(int srcSlot, int srcChannel, int dstSlot, int dstChannel, double sigmaMm, const double spacing[3] = nullptr,
+               vr_filter_result* out = nullptr);
+    int Smooth(int srcSlot, int srcChannel, int dstSlot, int dstChannel, double sigmaMm, const VolumeFileDcm& grid, vr_filter_result* out = nullptr);
+    // Gaussian derivatives of component 3 of volume `slot` into its components 0, 1, 2: three vr_volume_filter calls, each the first
+    // derivative (order 1) along its own axis and the Gaussian (order 0) along the other two, sigma and spacing as Smooth takes them.  The values are
+    // derivatives per VOXEL, unscaled: the caller normalises them (and divides by the spacing for a gradient in 1 / mm).  Component 3 is
+    // left alone.  VR_ERR_INVALID_ARG as Smooth, and where the radius comes out 0 on some axis (a derivative needs neighbours).
+    int GradientOfGaussian(int slot, double sigmaMm, const double spacing[3] = nullptr);
+    int GradientOfGaussian(int slot, double sigmaMm, const VolumeFileDcm& grid);
     // the accumulated opacity at which the unlit / lit scene's surface lies (vr_set_surface_threshold: finite, 0 <= tau < 1)
     int SetSurfaceThreshold(float tau);
 

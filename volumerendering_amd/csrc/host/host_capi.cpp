@@ -533,6 +533,27 @@ int vrh_app_resample(void* a, void* src, int src_slot, void* grid, int dst_slot,
         return static_cast<Application*>(a)->ResampleOnto(*sh->dcm, src_slot, *gh->dcm, dst_slot, channels, filter, outside, out, dst_to_src);
     })
 }
+// Application::Smooth and Application::GradientOfGaussian (vr_volume_filter of the application's context).  grid: a volume read by
+// DicomReader whose PixelSpacing and SliceThickness are the spacing, or, with grid == nullptr, spacing: three doubles or nullptr (1 mm)
+int vrh_app_smooth(void* a, int src_slot, int src_channel, int dst_slot, int dst_channel, double sigma_mm, void* grid, const double* spacing,
+                   vr_filter_result* out)
+{
+    auto* vh = static_cast<VolumeHandle*>(grid);
+    if (vh && !vh->dcm) return VR_ERR_INVALID_ARG;
+    VRH_TRY(VR_ERR_HIP, {
+        return vh ? static_cast<Application*>(a)->Smooth(src_slot, src_channel, dst_slot, dst_channel, sigma_mm, *vh->dcm, out)
+                  : static_cast<Application*>(a)->Smooth(src_slot, src_channel, dst_slot, dst_channel, sigma_mm, spacing, out);
+    })
+}
+int vrh_app_gradient_of_gaussian(void* a, int slot, double sigma_mm, void* grid, const double* spacing)
+{
+    auto* vh = static_cast<VolumeHandle*>(grid);
+    if (vh && !vh->dcm) return VR_ERR_INVALID_ARG;
+    VRH_TRY(VR_ERR_HIP, {
+        return vh ? static_cast<Application*>(a)->GradientOfGaussian(slot, sigma_mm, *vh->dcm)
+                  : static_cast<Application*>(a)->GradientOfGaussian(slot, sigma_mm, spacing);
+    })
+}
 int vrh_app_set_surface_threshold(void* a, float tau) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->SetSurfaceThreshold(tau); }) }
 void vrh_app_set_prepare_on_device(void* a, int on) { static_cast<Application*>(a)->m_PrepareOnDevice = on != 0; }
 int vrh_app_update(void* a) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->OnUpdate(); }) }

@@ -30,6 +30,8 @@
 #include "vr_comp.h"
 // Surface extraction (vr_volume_mesh): marching tetrahedra over bit-rows of the lattice; nothing to fuse, compiled once as well
 #include "vr_mesh.h"
+// Separable filters (vr_volume_filter): every tap an explicit fmaf whatever the arithmetic mode, compiled once as well
+#include "vr_filter.h"
 
 #include <algorithm>
 #include <cmath>
@@ -58,6 +60,7 @@ using namespace vr;
 #include "vr_api_components.h"
 #include "vr_api_resample.h"
 #include "vr_api_mesh.h"
+#include "vr_api_filter.h"
 
 namespace {
 

@@ -474,6 +474,14 @@ struct MeshState {
     unsigned long long active_cells = 0; // vr_mesh_counters' fourth
 };
 
+// Separable filters (vr_volume_filter, vr_filter.h): the working buffers of the last call, grown on demand; what vr_filter_counters and
+// vr_filter_timing report.
+struct FilterState {
+    DevBuf<float> field[2];              // the fields the passes write in turn: the first pass' region, the second pass' region
+    WordsPair<FilterWords> io;           // the non-finite count, the least and greatest finite value
+    ToolReport report;                   // phases: the first pass, the remaining passes, write + result words, refresh_bricks
+};
+
 // What the reporting calls (vr_last_counters, vr_last_kernel_flavour, vr_last_timing, vr_kernel_times, vr_kernel_choice,
 // vr_download_tiles, vr_last_block_trace) read about the most recent march launch.  vr_pick copies it out and back as one value.
 struct LastLaunch {
@@ -583,6 +591,7 @@ struct vr_ctx {
     CompState comp;  // connected components (vr_mask_components)
     ResampleState resample;  // resampling onto another grid (vr_volume_resample)
     MeshState mesh;  // surface extraction (vr_volume_mesh)
+    FilterState filter;  // separable filters of a channel (vr_volume_filter)
     std::string err;
 };
 

@@ -78,6 +78,8 @@ def load() -> C.CDLL:
         "vrh_app_distance_map": (i32, [vp, C.POINTER(capi.DistDesc), C.POINTER(capi.DistResult)]),
         "vrh_app_distance_mm": (i32, [vp, i32, i32, i32, i32, i32, f32, vp, C.POINTER(capi.DistResult)]),
         "vrh_app_resample": (i32, [vp, vp, i32, vp, i32, u32, i32, C.POINTER(C.c_float * 4), C.POINTER(C.c_double * 12), C.POINTER(capi.ResampleResult)]),
+        "vrh_app_smooth": (i32, [vp, i32, i32, i32, i32, f64, vp, C.POINTER(C.c_double * 3), C.POINTER(capi.FilterResult)]),
+        "vrh_app_gradient_of_gaussian": (i32, [vp, i32, f64, vp, C.POINTER(C.c_double * 3)]),
         "vrh_app_slice": (i32, [vp, C.POINTER(capi.SliceDesc), vp]),
         "vrh_app_slice_through_pick": (C.c_longlong, [vp, C.POINTER(capi.PickResult), i32, i32, vp, C.c_size_t, C.POINTER(u32), C.POINTER(u32)]), "vrh_app_set_surface_threshold": (i32, [vp, f32]), "vrh_app_update": (i32, [vp]), "vrh_app_render": (i32, [vp]),
         "vrh_app_resize": (i32, [vp, u32, u32]), "vrh_app_read_frame": (i32, [vp, vp, vp, C.POINTER(u64)]),
@@ -654,6 +656,24 @@ class Application:
         self._chk(self.lib.vrh_app_resample(self.h, src.h, src_slot, grid.h, dst_slot, channels, filter, C.byref(o),
                                             None if m is None else C.byref(m), C.byref(out)))
         return out
+
+    def smooth(self, src_slot: int, src_channel: int, dst_slot: int, dst_channel: int, sigma_mm: float, grid: "VolumeFile" = None,
+               spacing=None) -> capi.FilterResult:
+        """Application::Smooth: component src_channel of volume src_slot smoothed by a Gaussian of sigma_mm millimetres (truncate 4) over
+        the whole volume into component dst_channel of volume dst_slot (vr_volume_filter, include/vr.h).  The voxel spacing is `grid`'s
+        PixelSpacing and SliceThickness (a volume read from DICOM), else `spacing` (x, y, z in mm), else 1; an axis whose radius comes out
+        0 gets no pass and sigma_mm == 0 copies."""
+        out = capi.FilterResult()
+        sp = (C.c_double * 3)(*[float(x) for x in spacing]) if spacing is not None else None
+        self._chk(self.lib.vrh_app_smooth(self.h, src_slot, src_channel, dst_slot, dst_channel, sigma_mm, grid.h if grid is not None else None,
+                                          sp, C.byref(out)))
+        return out
+
+    def gradient_of_gaussian(self, slot: int, sigma_mm: float, grid: "VolumeFile" = None, spacing=None):
+        """Application::GradientOfGaussian: the Gaussian derivatives of component 3 of volume `slot` along x, y, z into its components
+        0, 1, 2 (three vr_volume_filter calls; spacing as smooth takes it).  Derivatives per voxel, unscaled: the caller normalises."""
+        sp = (C.c_double * 3)(*[float(x) for x in spacing]) if spacing is not None else None
+        self._chk(self.lib.vrh_app_gradient_of_gaussian(self.h, slot, sigma_mm, grid.h if grid is not None else None, sp))
 
     def set_surface_threshold(self, tau: float):
         """Application::SetSurfaceThreshold: the accumulated opacity at which the surface of an unlit / lit scene lies."""
