@@ -1512,6 +1512,73 @@ int vr_filter_counters(vr_ctx* ctx, uint64_t out[3]);
  * slot.  Zeros before the first and after one that failed. */
 int vr_filter_timing(vr_ctx* ctx, float ms[4]);
 
+/* ---- rank filters: the median, the minimum or the maximum over a box window of a channel, without leaving the device --------------------
+ * The non-linear neighbourhood filters, which no separable filter expresses: the median (the edge-preserving denoise before
+ * vr_segment_grow, vr_volume_mesh, VR_VARIANT_ISO or a threshold) and grey erosion and dilation (the minimum and the maximum of a value
+ * field such as a dose, a distance map or a CT, as opposed to the mask morphology of vr_mask_morph) -- on the device (csrc/vr_rank.h).
+ *   Window: the window of output voxel (x, y, z) holds N = (2 rx + 1)(2 ry + 1)(2 rz + 1) values: component src_channel of src_slot at
+ *     (x + dx, y + dy, z + dz) for |dx| <= rx, |dy| <= ry, |dz| <= rz.  An index beyond a face of the volume reads the clamped index under
+ *     VR_FILTER_CLAMP (scipy.ndimage's mode="nearest") and the bits of border_value under VR_FILTER_CONSTANT (mode="constant", cval).  The
+ *     faces are the VOLUME's, not the box's: the box only limits which voxels are stored.
+ *   Order: the N bit patterns are ordered as unsigned keys -- a pattern with the sign bit set maps to its complement, any other gets the
+ *     sign bit set -- which gives  negative NaNs < -inf < .. < -0.0f < +0.0f < .. < +inf < positive NaNs,  NaNs among themselves by
+ *     payload: a total order on all 2^32 patterns.  The stored value is the pattern at position k of the ascending order, its bits
+ *     unchanged: a NaN keeps its payload, a denormal stays a denormal, and with N = 1 the call is a copy.  k = rank, or N / 2 for
+ *     VR_RANK_MEDIAN, or N - 1 for VR_RANK_MAX.  For windows without NaN this is scipy.ndimage.rank_filter's value (where a window holds
+ *     both -0.0f and +0.0f, one of scipy's two equal values).  Nothing is computed: vr_set_arithmetic plays no part.
+ *   Source and destination: as for vr_volume_filter.  The other three components of the destination keep their bits, and so does every
+ *     voxel outside the box.  The result is that of reading the whole source before anything is written: src_slot == dst_slot with
+ *     src_channel == dst_channel is valid.  An empty dst_slot is created with the source's nx, ny, nz and every component +0.0f; one of
+ *     other dimensions is VR_ERR_INVALID_ARG.
+ *   Result: stored, nonfinite, lo_value and hi_value as in vr_filter_result; changed = the voxels of the box whose stored bits differ from
+ *     the bits of src_channel of src_slot at the same voxel before the call: how much a median altered.  All five are exact and
+ *     independent of scheduling.
+ *   Counters (vr_rank_counters): out[0] = voxels of the box; out[1] = voxels of the box grown by the radii and clipped to the volume, the
+ *     inputs a call must read; out[2] = the resolved rank k.  An empty box gives zeros.
+ * Kernel forms: by default every input is loaded once per workgroup tile, plus the halo, into LDS as keys and selected from there -- by
+ * three 1-D running minima or maxima for k = 0 and k = N - 1, by a network in registers for the 3 x 3 x 3 median, by a radix descent
+ * otherwise; flavour 1 of vr_set_kernel_flavour reads the N inputs of every output straight from memory into one radix descent.  The
+ * destination, the result and all three counters are identical across the forms and the volume layouts. */
+#define VR_RANK_MAX_RADIUS 3          /* windows up to 7 x 7 x 7 = 343 values */
+#define VR_RANK_MIN      0            /* rank 0: grey erosion by the box        */
+#define VR_RANK_MEDIAN (-1)           /* resolves to N / 2                      */
+#define VR_RANK_MAX    (-2)           /* resolves to N - 1: grey dilation       */
+typedef struct vr_rank_desc {
+    int32_t src_slot, src_channel;     /* component 0 .. 3 of a filled slot                                        */
+    int32_t dst_slot, dst_channel;     /* may be the same slot, and the same channel                               */
+    int32_t radius[3];                 /* per axis x, y, z: 0 .. VR_RANK_MAX_RADIUS; N = the product of 2 r + 1    */
+    int32_t rank;                      /* 0 .. N - 1, or VR_RANK_MEDIAN / VR_RANK_MAX                              */
+    int32_t border;  float border_value;   /* VR_FILTER_CLAMP / VR_FILTER_CONSTANT, as vr_volume_filter            */
+    int32_t box_lo[3], box_hi[3];      /* voxel box of the OUTPUT, half open                                       */
+} vr_rank_desc;
+typedef struct vr_rank_result {
+    uint64_t stored, nonfinite;        /* voxels of the box; those whose stored value is NaN or +-inf              */
+    uint64_t changed;                  /* those whose stored bits differ from the source's at the same voxel       */
+    float    lo_value, hi_value;       /* least / greatest finite stored value; +0.0f both if there is none        */
+} vr_rank_result;
+
+/* Fills *out for the whole volume of src_slot: the given slots and channels, radii 0, VR_RANK_MEDIAN, VR_FILTER_CLAMP, border_value 0 (a
+ * copy until the caller sets a radius) and the box (0,0,0) .. (nx,ny,nz).  Pure host arithmetic; VR_ERR_INVALID_ARG for a NULL pointer or a
+ * slot or channel out of range, VR_ERR_NOT_READY for an empty source slot. */
+int vr_rank_whole(const vr_ctx* ctx, int src_slot, int src_channel, int dst_slot, int dst_channel, vr_rank_desc* out);
+
+/* Does the work; `result` may be NULL.  A data-preparation call exactly like vr_volume_filter: it waits for everything in flight, runs on
+ * the ctx's own stream, rebuilds what is derived from the destination slot's voxels as an upload does and is synchronous on return.  What
+ * the reporting calls say about the last march, slice, histogram or other tool stays as it was.  An empty box writes nothing and is VR_OK.
+ * Checked before anything is enqueued or a slot is touched.  VR_ERR_INVALID_ARG: a NULL ctx or descriptor; a slot or channel out of range;
+ * a radius outside 0 .. VR_RANK_MAX_RADIUS; a rank outside 0 .. N - 1 that is neither VR_RANK_MEDIAN nor VR_RANK_MAX; an unknown border; a
+ * destination slot of other dimensions; a box that is not 0 <= lo <= hi <= n on every axis.  VR_ERR_NOT_READY: the source slot is empty.
+ * VR_ERR_OOM: the working field -- one word per voxel of the box -- could not be allocated.  A failed call changes no slot and no counter. */
+int vr_volume_rank(vr_ctx* ctx, const vr_rank_desc* desc, vr_rank_result* result);
+
+/* Counters of the last vr_volume_rank (as described above).  Zeros before the first. */
+int vr_rank_counters(vr_ctx* ctx, uint64_t out[3]);
+
+/* Device time of the last vr_volume_rank in milliseconds, from events on the ctx's stream: ms[0] the selection kernel, ms[1] any further
+ * ones (0: every form selects in one kernel), ms[2] the write into the destination and the result words, ms[3] the rebuild of what is
+ * derived from the destination slot.  Zeros before the first and after one that failed. */
+int vr_rank_timing(vr_ctx* ctx, float ms[4]);
+
 /* Volume layout in HBM (A/B measurements; frames and counts are bit-identical in every mode).
  *   0  default: the march kernels gather from a BRICKED copy of every slot -- the vec4 voxels and a scalar f32 density plane
  *      (what fetches that consume .a alone read: BasicVolumeApp.wgsl:171, the density / dose fetches of the other shaders)

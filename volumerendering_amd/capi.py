@@ -51,6 +51,8 @@ COMP_MAX_KEEP, COMP_MAX_LABEL = 64, 1 << 24                                 # of
 RESAMPLE_LINEAR, RESAMPLE_NEAREST = 0, 1                                    # vr_resample_desc.filter (include/vr.h)
 FILTER_MAX_RADIUS = 32                                                      # of vr_filter_desc.radius (include/vr.h)
 FILTER_CLAMP, FILTER_CONSTANT = 0, 1                                        # vr_filter_desc.border
+RANK_MAX_RADIUS = 3                                                         # of vr_rank_desc.radius (include/vr.h)
+RANK_MIN, RANK_MEDIAN, RANK_MAX = 0, -1, -2                                 # vr_rank_desc.rank: 0 .. N - 1, or N / 2, or N - 1
 DIST_MAX_SPACING, DIST_MAX_LIMIT, DIST_MAX_EXTENT = 1 << 20, 1 << 31, 1 << 30  # of a spacing, the limit, (hi - lo) * spacing per axis
 
 # every symbol include/vr.h declares (tests check that the library exports each of them)
@@ -79,6 +81,7 @@ ABI_SYMBOLS = [
     "vr_resample_identity", "vr_resample_between", "vr_volume_resample", "vr_resample_counters", "vr_resample_timing",
     "vr_mesh_whole", "vr_volume_mesh", "vr_mesh_counters", "vr_mesh_timing",
     "vr_filter_whole", "vr_filter_gaussian", "vr_volume_filter", "vr_filter_counters", "vr_filter_timing",
+    "vr_rank_whole", "vr_volume_rank", "vr_rank_counters", "vr_rank_timing",
 ]
 
 
@@ -388,6 +391,36 @@ class FilterResult(C.Structure):
         return int(self.stored), int(self.nonfinite), int(lo), int(hi)
 
 
+class RankDesc(C.Structure):
+    """struct vr_rank_desc (include/vr.h): the source and destination slots and channels, the radius per axis, the rank (0 .. N - 1 or
+    RANK_MEDIAN / RANK_MAX), the border rule and value, and the voxel box of the output."""
+    _fields_ = [
+        ("src_slot", C.c_int32), ("src_channel", C.c_int32), ("dst_slot", C.c_int32), ("dst_channel", C.c_int32),
+        ("radius", C.c_int32 * 3), ("rank", C.c_int32), ("border", C.c_int32), ("border_value", C.c_float),
+        ("box_lo", C.c_int32 * 3), ("box_hi", C.c_int32 * 3),
+    ]
+
+    def copy(self, **over) -> "RankDesc":
+        """A copy with the given fields replaced (radius / box_lo / box_hi from any sequence of three integers)."""
+        d = RankDesc.from_buffer_copy(bytes(self))
+        for k, v in over.items():
+            if k in ("radius", "box_lo", "box_hi"):
+                v = (C.c_int32 * 3)(*[int(x) for x in v])
+            setattr(d, k, v)
+        return d
+
+
+class RankResult(C.Structure):
+    """struct vr_rank_result: the voxels of the box, those stored as NaN or +-inf, those whose stored bits differ from the source's at
+    the same voxel, the least and greatest finite stored value."""
+    _fields_ = [("stored", C.c_uint64), ("nonfinite", C.c_uint64), ("changed", C.c_uint64), ("lo_value", C.c_float), ("hi_value", C.c_float)]
+
+    def as_tuple(self):
+        """(stored, nonfinite, changed, the bits of lo_value, the bits of hi_value)"""
+        lo, hi = np.array([self.lo_value, self.hi_value], np.float32).view(np.uint32)
+        return int(self.stored), int(self.nonfinite), int(self.changed), int(lo), int(hi)
+
+
 class Component(C.Structure):
     """struct vr_component (include/vr.h): a component's voxels, half-open bounding box, first voxel (x, y, z) and the faces of the box
     it touches."""
@@ -602,6 +635,10 @@ def load() -> C.CDLL:
     lib.vr_volume_filter.argtypes = [vp, C.POINTER(FilterDesc), C.POINTER(FilterResult)]
     lib.vr_filter_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
     lib.vr_filter_timing.argtypes = [vp, C.POINTER(C.c_float * 4)]
+    lib.vr_rank_whole.argtypes = [vp, i32, i32, i32, i32, C.POINTER(RankDesc)]
+    lib.vr_volume_rank.argtypes = [vp, C.POINTER(RankDesc), C.POINTER(RankResult)]
+    lib.vr_rank_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
+    lib.vr_rank_timing.argtypes = [vp, C.POINTER(C.c_float * 4)]
     lib.vr_present_async.argtypes = [vp, vp, vp, vp]
     lib.vr_present_tiles_async.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
     lib.vr_hint_frames_in_flight.argtypes = [vp, i32]
@@ -1190,6 +1227,28 @@ class Context:
     def filter_timing(self):
         """(first pass, remaining passes, write + result words, refresh) of the last volume_filter in ms of device time."""
         return self._tool_timing(self.lib.vr_filter_timing)
+
+    def rank_whole(self, src_slot: int, src_channel: int, dst_slot: int, dst_channel: int) -> RankDesc:
+        """vr_rank_whole: the descriptor of a rank filter of component src_channel of volume src_slot over its whole volume into
+        component dst_channel of volume dst_slot: radii 0, RANK_MEDIAN, CLAMP, border_value 0 (edit with copy)."""
+        d = RankDesc()
+        self._chk(self.lib.vr_rank_whole(self.h, src_slot, src_channel, dst_slot, dst_channel, C.byref(d)))
+        return d
+
+    def volume_rank(self, desc: RankDesc) -> RankResult:
+        """vr_volume_rank: the value at position `rank` of the ascending order of the (2 rx + 1)(2 ry + 1)(2 rz + 1) values around every
+        voxel of the box -- median, minimum, maximum -- of a component into a component (synchronous)."""
+        out = RankResult()
+        self._chk(self.lib.vr_volume_rank(self.h, C.byref(desc), C.byref(out)))
+        return out
+
+    def rank_counters(self):
+        """(voxels of the box, voxels of the box grown by the radii and clipped to the volume, the resolved rank) of the last volume_rank."""
+        return self._tool_counters(self.lib.vr_rank_counters)
+
+    def rank_timing(self):
+        """(the selection kernel, further ones: 0, write + result words, refresh) of the last volume_rank in ms of device time."""
+        return self._tool_timing(self.lib.vr_rank_timing)
 
     def set_volume_layout(self, mode: int):
         """0 bricked copy (default), 1 the reference's vec4 voxels only, 3 x-fastest voxels + density plane (2 was removed)."""

@@ -491,6 +491,47 @@ int Application::GradientOfGaussian(int slot, double sigmaMm, const VolumeFileDc
     return GradientOfGaussian(slot, sigmaMm, spacing);
 }
 
+int Application::RankFilter(int srcSlot, int srcChannel, int dstSlot, int dstChannel, double radiusMm, int rank, const double spacing[3],
+                            vr_rank_result* out)
+{
+    if (!p_Ctx) return VR_ERR_NOT_READY;
+    if (!std::isfinite(radiusMm) || radiusMm < 0.0) return VR_ERR_INVALID_ARG;
+    int radius[3];
+    for (int a = 0; a < 3; ++a) {
+        const double sp = spacing ? spacing[a] : 1.0;
+        if (!std::isfinite(sp) || !(sp > 0.0)) return VR_ERR_INVALID_ARG;
+        const double reach = radiusMm / sp + 0.5;
+        if (!(reach < (double)(VR_RANK_MAX_RADIUS + 1))) return VR_ERR_INVALID_ARG;
+        radius[a] = (int)reach;
+    }
+    vr_rank_desc d;
+    int rc = vr_rank_whole(p_Ctx, srcSlot, srcChannel, dstSlot, dstChannel, &d);
+    if (rc != VR_OK) return rc;
+    for (int a = 0; a < 3; ++a) d.radius[a] = radius[a];
+    d.rank = rank;
+    rc = vr_volume_rank(p_Ctx, &d, out);
+    if (rc != VR_OK) m_Error = vr_last_error(p_Ctx);
+    return rc;
+}
+
+int Application::RankFilter(int srcSlot, int srcChannel, int dstSlot, int dstChannel, double radiusMm, int rank, const VolumeFileDcm& grid,
+                            vr_rank_result* out)
+{
+    const DicomVolumeParams p = grid.GetVolumeParams();
+    const double spacing[3] = {p.PixelSpacing[0], p.PixelSpacing[1], p.SliceThickness};
+    return RankFilter(srcSlot, srcChannel, dstSlot, dstChannel, radiusMm, rank, spacing, out);
+}
+
+int Application::Median(int srcSlot, int srcChannel, int dstSlot, int dstChannel, double radiusMm, const double spacing[3], vr_rank_result* out)
+{
+    return RankFilter(srcSlot, srcChannel, dstSlot, dstChannel, radiusMm, VR_RANK_MEDIAN, spacing, out);
+}
+
+int Application::Median(int srcSlot, int srcChannel, int dstSlot, int dstChannel, double radiusMm, const VolumeFileDcm& grid, vr_rank_result* out)
+{
+    return RankFilter(srcSlot, srcChannel, dstSlot, dstChannel, radiusMm, VR_RANK_MEDIAN, grid, out);
+}
+
 int Application::Pick(uint32_t x, uint32_t y, vr_pick_result* out)
 {
     if (!p_Ctx || !p_App) return VR_ERR_NOT_READY;

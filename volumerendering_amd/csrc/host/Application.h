@@ -142,6 +142,19 @@ public:
     // left alone.  VR_ERR_INVALID_ARG as Smooth, and where the radius comes out 0 on some axis (a derivative needs neighbours).
     int GradientOfGaussian(int slot, double sigmaMm, const double spacing[3] = nullptr);
     int GradientOfGaussian(int slot, double sigmaMm, const VolumeFileDcm& grid);
+    // The value at position `rank` (0 .. N - 1, VR_RANK_MEDIAN or VR_RANK_MAX) of the ascending order of the values in a box window of
+    // radiusMm millimetres around every voxel of component srcChannel of volume srcSlot, over the whole volume into component dstChannel
+    // of volume dstSlot, on the device (vr_volume_rank of include/vr.h; VR_FILTER_CLAMP): per axis the radius in voxels is
+    // (int)(radiusMm / spacing[a] + 0.5) (x, y, z in millimetres; nullptr = 1); with `grid` its PixelSpacing and SliceThickness.  Source
+    // and destination may coincide.  `out` may be nullptr.  VR_ERR_INVALID_ARG for a radiusMm that is negative or not finite, a spacing
+    // that is not finite and positive, or a radius beyond VR_RANK_MAX_RADIUS voxels on some axis.  Median: the same with VR_RANK_MEDIAN.
+    int RankFilter(int srcSlot, int srcChannel, int dstSlot, int dstChannel, double radiusMm, int rank, const double spacing[3] = nullptr,
+                   vr_rank_result* out = nullptr);
+    int RankFilter(int srcSlot, int srcChannel, int dstSlot, int dstChannel, double radiusMm, int rank, const VolumeFileDcm& grid,
+                   vr_rank_result* out = nullptr);
+    int Median(int srcSlot, int srcChannel, int dstSlot, int dstChannel, double radiusMm, const double spacing[3] = nullptr,
+               vr_rank_result* out = nullptr);
+    int Median(int srcSlot, int srcChannel, int dstSlot, int dstChannel, double radiusMm, const VolumeFileDcm& grid, vr_rank_result* out = nullptr);
     // the accumulated opacity at which the unlit / lit scene's surface lies (vr_set_surface_threshold: finite, 0 <= tau < 1)
     int SetSurfaceThreshold(float tau);
 

@@ -554,6 +554,22 @@ int vrh_app_gradient_of_gaussian(void* a, int slot, double sigma_mm, void* grid,
                   : static_cast<Application*>(a)->GradientOfGaussian(slot, sigma_mm, spacing);
     })
 }
+// Application::RankFilter (vr_volume_rank of the application's context; rank = VR_RANK_MEDIAN is Application::Median).  grid and spacing
+// as vrh_app_smooth takes them
+int vrh_app_rank(void* a, int src_slot, int src_channel, int dst_slot, int dst_channel, double radius_mm, int rank, void* grid,
+                 const double* spacing, vr_rank_result* out)
+{
+    auto* vh = static_cast<VolumeHandle*>(grid);
+    if (vh && !vh->dcm) return VR_ERR_INVALID_ARG;
+    VRH_TRY(VR_ERR_HIP, {
+        auto* app = static_cast<Application*>(a);
+        if (rank == VR_RANK_MEDIAN)
+            return vh ? app->Median(src_slot, src_channel, dst_slot, dst_channel, radius_mm, *vh->dcm, out)
+                      : app->Median(src_slot, src_channel, dst_slot, dst_channel, radius_mm, spacing, out);
+        return vh ? app->RankFilter(src_slot, src_channel, dst_slot, dst_channel, radius_mm, rank, *vh->dcm, out)
+                  : app->RankFilter(src_slot, src_channel, dst_slot, dst_channel, radius_mm, rank, spacing, out);
+    })
+}
 int vrh_app_set_surface_threshold(void* a, float tau) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->SetSurfaceThreshold(tau); }) }
 void vrh_app_set_prepare_on_device(void* a, int on) { static_cast<Application*>(a)->m_PrepareOnDevice = on != 0; }
 int vrh_app_update(void* a) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->OnUpdate(); }) }

@@ -32,6 +32,8 @@
 #include "vr_mesh.h"
 // Separable filters (vr_volume_filter): every tap an explicit fmaf whatever the arithmetic mode, compiled once as well
 #include "vr_filter.h"
+// Rank filters (vr_volume_rank): keys compared as unsigned integers, nothing computed and nothing to fuse, compiled once as well
+#include "vr_rank.h"
 
 #include <algorithm>
 #include <cmath>
@@ -61,6 +63,7 @@ using namespace vr;
 #include "vr_api_resample.h"
 #include "vr_api_mesh.h"
 #include "vr_api_filter.h"
+#include "vr_api_rank.h"
 
 namespace {
 

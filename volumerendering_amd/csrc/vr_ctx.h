@@ -482,6 +482,14 @@ struct FilterState {
     ToolReport report;                   // phases: the first pass, the remaining passes, write + result words, refresh_bricks
 };
 
+// Rank filters (vr_volume_rank, vr_rank.h): the working field of the last call, grown on demand; what vr_rank_counters and
+// vr_rank_timing report.
+struct RankState {
+    DevBuf<unsigned> field;              // the selected bit pattern of every voxel of the box
+    WordsPair<RankWords> io;             // the non-finite and changed counts, the least and greatest finite value
+    ToolReport report;                   // phases: the selection kernel, further ones (none), write + result words, refresh_bricks
+};
+
 // What the reporting calls (vr_last_counters, vr_last_kernel_flavour, vr_last_timing, vr_kernel_times, vr_kernel_choice,
 // vr_download_tiles, vr_last_block_trace) read about the most recent march launch.  vr_pick copies it out and back as one value.
 struct LastLaunch {
@@ -592,6 +600,7 @@ struct vr_ctx {
     ResampleState resample;  // resampling onto another grid (vr_volume_resample)
     MeshState mesh;  // surface extraction (vr_volume_mesh)
     FilterState filter;  // separable filters of a channel (vr_volume_filter)
+    RankState rank;  // rank filters of a channel (vr_volume_rank)
     std::string err;
 };
 

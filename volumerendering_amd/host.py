@@ -80,6 +80,7 @@ def load() -> C.CDLL:
         "vrh_app_resample": (i32, [vp, vp, i32, vp, i32, u32, i32, C.POINTER(C.c_float * 4), C.POINTER(C.c_double * 12), C.POINTER(capi.ResampleResult)]),
         "vrh_app_smooth": (i32, [vp, i32, i32, i32, i32, f64, vp, C.POINTER(C.c_double * 3), C.POINTER(capi.FilterResult)]),
         "vrh_app_gradient_of_gaussian": (i32, [vp, i32, f64, vp, C.POINTER(C.c_double * 3)]),
+        "vrh_app_rank": (i32, [vp, i32, i32, i32, i32, f64, i32, vp, C.POINTER(C.c_double * 3), C.POINTER(capi.RankResult)]),
         "vrh_app_slice": (i32, [vp, C.POINTER(capi.SliceDesc), vp]),
         "vrh_app_slice_through_pick": (C.c_longlong, [vp, C.POINTER(capi.PickResult), i32, i32, vp, C.c_size_t, C.POINTER(u32), C.POINTER(u32)]), "vrh_app_set_surface_threshold": (i32, [vp, f32]), "vrh_app_update": (i32, [vp]), "vrh_app_render": (i32, [vp]),
         "vrh_app_resize": (i32, [vp, u32, u32]), "vrh_app_read_frame": (i32, [vp, vp, vp, C.POINTER(u64)]),
@@ -674,6 +675,23 @@ class Application:
         0, 1, 2 (three vr_volume_filter calls; spacing as smooth takes it).  Derivatives per voxel, unscaled: the caller normalises."""
         sp = (C.c_double * 3)(*[float(x) for x in spacing]) if spacing is not None else None
         self._chk(self.lib.vrh_app_gradient_of_gaussian(self.h, slot, sigma_mm, grid.h if grid is not None else None, sp))
+
+    def rank_filter(self, src_slot: int, src_channel: int, dst_slot: int, dst_channel: int, radius_mm: float, rank: int,
+                    grid: "VolumeFile" = None, spacing=None) -> capi.RankResult:
+        """Application::RankFilter: the value at position `rank` (0 .. N - 1, capi.RANK_MEDIAN or capi.RANK_MAX) of the ascending order
+        of the values in a box window of radius_mm millimetres around every voxel of component src_channel of volume src_slot, over the
+        whole volume into component dst_channel of volume dst_slot (vr_volume_rank, include/vr.h).  Per axis the radius in voxels is
+        int(radius_mm / spacing + 0.5); the spacing as smooth takes it."""
+        out = capi.RankResult()
+        sp = (C.c_double * 3)(*[float(x) for x in spacing]) if spacing is not None else None
+        self._chk(self.lib.vrh_app_rank(self.h, src_slot, src_channel, dst_slot, dst_channel, radius_mm, rank,
+                                        grid.h if grid is not None else None, sp, C.byref(out)))
+        return out
+
+    def median(self, src_slot: int, src_channel: int, dst_slot: int, dst_channel: int, radius_mm: float, grid: "VolumeFile" = None,
+               spacing=None) -> capi.RankResult:
+        """Application::Median: rank_filter with capi.RANK_MEDIAN."""
+        return self.rank_filter(src_slot, src_channel, dst_slot, dst_channel, radius_mm, capi.RANK_MEDIAN, grid, spacing)
 
     def set_surface_threshold(self, tau: float):
         """Application::SetSurfaceThreshold: the accumulated opacity at which the surface of an unlit / lit scene lies."""
