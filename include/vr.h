@@ -1579,6 +1579,102 @@ int vr_rank_counters(vr_ctx* ctx, uint64_t out[3]);
  * derived from the destination slot.  Zeros before the first and after one that failed. */
 int vr_rank_timing(vr_ctx* ctx, float ms[4]);
 
+/* ---- the gamma index: comparing two dose channels, without leaving the device -------------------------------------------------------------
+ * The gamma index of Low et al. (Med. Phys. 25, 1998): for every voxel of the reference dose the minimum, over nearby points of the
+ * evaluated dose, of dose difference and distance combined -- a plan against a recalculation, a measurement or yesterday's plan -- on the
+ * device (csrc/vr_gamma.h).  vr_volume_resample puts two doses on one grid before; vr_histogram and the slice views consume the result.
+ * Every f32 operation is named; vr_set_arithmetic plays no part (every fused step is an explicit fmaf, every other step stays unfused).
+ *   Operands: R = component ref_channel of ref_slot, E = component eval_channel of eval_slot; both slots filled and of equal dimensions
+ *     (nx, ny, nz).  Output voxels are those of the half-open box.
+ *   Spacing and distances: spacing[3] (x, y, z) in an integer unit of the caller's choice (micrometres, say), each 1 .. 2^20 as in
+ *     vr_dist_desc; dta (distance to agreement) and reach (how far the search goes) in the same unit, each 1 .. 2^24; sub = candidate
+ *     positions per voxel step and axis, 1 .. VR_GAMMA_MAX_SUB.  reach / spacing[a] (integer division) must be <= VR_GAMMA_MAX_RADIUS
+ *     on every axis, else VR_ERR_INVALID_ARG.
+ *   Candidates of an output voxel p: integer sub-step offsets o = (i, j, k) with
+ *     D2n(o) = (i spacing[0])^2 + (j spacing[1])^2 + (k spacing[2])^2 <= (reach sub)^2, both exact in uint64_t.  Per axis
+ *     o_a = sub m_a + f_a with floor division, 0 <= f_a < sub; the base voxel is b = p + m.  The candidate EXISTS iff 0 <= b_a and
+ *     b_a + (f_a > 0 ? 1 : 0) <= n_a - 1 on every axis.  The faces are the VOLUME's, not the box's, and there is no border mode: a
+ *     position outside the volume is not a candidate.
+ *   Value at a candidate: t_a = (float)f_a / (float)sub (one rounded division); lerp(u, v, t) = fmaf(t, v - u, u) with v - u one rounded
+ *     subtraction; E is interpolated along x between the corner pairs of b, then along y, then along z.  An axis with f_a == 0 takes its
+ *     lower value as it is -- no arithmetic, the upper neighbour is not read.  The result is e; with sub = 1 it is E at b.
+ *   Tolerance: r = R(p).  VR_GAMMA_GLOBAL: T = dose_tolerance (3 % of the prescription, say: the caller's number).  VR_GAMMA_LOCAL:
+ *     T = dose_tolerance * r, one rounded product (dose_tolerance a fraction such as 0.03f).  invT = 1.0f / T, the IEEE division.
+ *   Skipped voxels: p is skipped if !(r >= cutoff) (a NaN r is skipped), if T is not finite or not > 0, or if roi_slot != -1 and
+ *     component roi_contour of roi_slot at p is not in the contour (vr_mask_distance's rule: != 0.0f, NaN is in, -0.0f is out).  A
+ *     skipped voxel stores the bits of skip_value, whatever they are.
+ *   Gamma: kc = (float)(1.0 / ((double)dta * dta * sub * sub)), computed on the host.  Per candidate c = (float)D2n * kc (the uint64_t ->
+ *     f32 conversion rounded to nearest, then one product), d = (e - r) * invT (one rounded subtraction, one product),
+ *     g2 = fmaf(d, d, c).  G2 = the least g2 over the existing admitted candidates, a NaN g2 ignored; if every g2 is NaN, G2 is the NaN
+ *     0x7FC00000.  The stored value is the correctly rounded f32 square root of G2.  The voxel PASSES iff G2 <= 1.0f.
+ *   Why the order of candidates cannot matter: g2 is +0 or positive, never -0 (d * d >= +0 and c >= +0, and a sum of those is never
+ *     -0), so the minimum is one bit pattern whatever the order.
+ *   Why the search may be cut short exactly: rounding is monotone and d * d >= 0, so g2 = round(d * d + c) >= round(c) = c always.  A
+ *     candidate whose c is not below the running minimum therefore cannot lower it and may be left out; with the candidates in
+ *     ascending c, everything after the first such candidate may.
+ *   Source and destination: the stored values go into component dst_channel of the box's voxels of dst_slot; the other three components
+ *     and every voxel outside the box keep their bits.  The result is that of reading both doses and the ROI before anything is
+ *     written: the destination may be either dose's slot and channel.  An empty dst_slot is created with the reference's dimensions and
+ *     every component +0.0f; one of other dimensions is VR_ERR_INVALID_ARG.
+ *   Result: stored = voxels of the box; evaluated = those not skipped; passed = evaluated voxels with G2 <= 1; nonfinite = evaluated
+ *     voxels whose stored value is NaN or +inf; hi_value = the greatest finite stored value among evaluated voxels, +0.0f if there is
+ *     none.  All exact and independent of scheduling.
+ *   Counters (vr_gamma_counters): out[0] = voxels of the box; out[1] = evaluated voxels; out[2] = K, the number of admitted offsets.  An
+ *     empty box gives zeros.
+ * Kernel forms: the host builds the table of admitted offsets, ascending D2n with ties by (k, j, i), each with its c.  By default a
+ * workgroup stages E for a tile of outputs plus the halo in LDS and walks the table until no lane of a wavefront has a c below its
+ * running minimum; flavour 1 of vr_set_kernel_flavour visits every admitted candidate of every voxel from memory, with no cut.  The
+ * destination, the result and all three counters are identical across the forms and the volume layouts. */
+#define VR_GAMMA_MAX_SUB    4
+#define VR_GAMMA_MAX_RADIUS 8
+#define VR_GAMMA_GLOBAL 0
+#define VR_GAMMA_LOCAL  1
+typedef struct vr_gamma_desc {
+    int32_t  ref_slot, ref_channel;     /* R: component 0 .. 3 of a filled slot                                     */
+    int32_t  eval_slot, eval_channel;   /* E: the same, of a slot of equal dimensions                               */
+    int32_t  dst_slot, dst_channel;     /* where gamma goes; may be either dose's slot and channel                  */
+    int32_t  roi_slot, roi_contour;     /* voxels outside this contour are skipped; roi_slot = -1: none             */
+    uint32_t spacing[3];                /* x, y, z: 1 .. 2^20 each                                                  */
+    uint32_t dta, reach;                /* same unit: 1 .. 2^24 each; reach / spacing[a] <= VR_GAMMA_MAX_RADIUS     */
+    int32_t  sub;                       /* candidate positions per voxel step and axis: 1 .. VR_GAMMA_MAX_SUB       */
+    int32_t  mode;                      /* VR_GAMMA_GLOBAL / VR_GAMMA_LOCAL                                         */
+    float    dose_tolerance;            /* T (global), or the fraction of r (local)                                 */
+    float    cutoff;                    /* voxels with !(r >= cutoff) are skipped; -inf: none                       */
+    float    skip_value;                /* what a skipped voxel stores, bit for bit                                 */
+    int32_t  box_lo[3], box_hi[3];      /* voxel box of the OUTPUT, half open                                       */
+} vr_gamma_desc;
+typedef struct vr_gamma_result {
+    uint64_t stored, evaluated;         /* voxels of the box; those not skipped                                     */
+    uint64_t passed, nonfinite;         /* evaluated voxels with G2 <= 1; those whose stored value is NaN or +inf   */
+    float    hi_value;                  /* greatest finite stored value among evaluated voxels; +0.0f if none       */
+    uint32_t reserved;                  /* 0                                                                        */
+} vr_gamma_result;
+
+/* Fills *out for the whole volume of ref_slot: the given slots and channels, unit spacing, dta = reach = 1, sub 1, VR_GAMMA_GLOBAL,
+ * dose_tolerance 1.0f, cutoff -inf, no ROI (roi_slot -1), skip_value the NaN 0x7FC00000 and the box (0,0,0) .. (nx,ny,nz).  Pure host
+ * arithmetic; VR_ERR_INVALID_ARG for a NULL pointer or a slot or channel out of range, VR_ERR_NOT_READY for an empty reference slot. */
+int vr_gamma_whole(const vr_ctx* ctx, int ref_slot, int ref_channel, int eval_slot, int eval_channel, int dst_slot, int dst_channel,
+                   vr_gamma_desc* out);
+
+/* Does the work; `result` may be NULL.  A data-preparation call exactly like vr_volume_filter: it waits for everything in flight, runs on
+ * the ctx's own stream, rebuilds what is derived from the destination slot's voxels as an upload does and is synchronous on return.  What
+ * the reporting calls say about the last march, slice, histogram or other tool stays as it was.  An empty box writes nothing and is VR_OK.
+ * Checked before anything is enqueued or a slot is touched.  VR_ERR_INVALID_ARG: a NULL ctx or descriptor; a slot (the ROI's: other than
+ * -1), channel or contour out of range; a spacing outside 1 .. 2^20; dta or reach outside 1 .. 2^24; sub outside 1 .. VR_GAMMA_MAX_SUB;
+ * reach / spacing[a] above VR_GAMMA_MAX_RADIUS; an unknown mode; an evaluated, ROI or destination slot of other dimensions than the
+ * reference's; a box that is not 0 <= lo <= hi <= n on every axis.  VR_ERR_NOT_READY: the reference, evaluated or ROI slot is empty.
+ * VR_ERR_OOM: the working field -- two words per voxel of the box -- or the offset table could not be allocated.  A failed call changes no
+ * slot and no counter. */
+int vr_volume_gamma(vr_ctx* ctx, const vr_gamma_desc* desc, vr_gamma_result* result);
+
+/* Counters of the last vr_volume_gamma (as described above).  Zeros before the first. */
+int vr_gamma_counters(vr_ctx* ctx, uint64_t out[3]);
+
+/* Device time of the last vr_volume_gamma in milliseconds, from events on the ctx's stream: ms[0] the gamma kernel, ms[1] any further
+ * ones (0: every form searches in one kernel), ms[2] the write into the destination and the result words, ms[3] the rebuild of what is
+ * derived from the destination slot.  Zeros before the first and after one that failed. */
+int vr_gamma_timing(vr_ctx* ctx, float ms[4]);
+
 /* Volume layout in HBM (A/B measurements; frames and counts are bit-identical in every mode).
  *   0  default: the march kernels gather from a BRICKED copy of every slot -- the vec4 voxels and a scalar f32 density plane
  *      (what fetches that consume .a alone read: BasicVolumeApp.wgsl:171, the density / dose fetches of the other shaders)

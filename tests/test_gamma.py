@@ -1,0 +1,212 @@
+"""CPU side of the gamma index (vr_volume_gamma; include/vr.h): the constants and struct layouts against the header, the entry points
+through the binding with no device, and the restatement the GPU tests compare against (gamma_ref.py): pinned bit for bit to an
+independent float64 brute-force gamma where every f32 step but the square root is exact, compared with it on random doses, its exact
+cut against the full search, and the order and size of its offset table."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import gamma_ref as gr
+from volumerendering_amd import capi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+f32, u32 = np.float32, np.uint32
+
+
+# ---- the binding (these fail where the header, the binding or the library lack the feature) ------------------------------------------
+
+def test_constants_and_struct_layouts_match_header(tmp_path):
+    fields_d = ["ref_slot", "ref_channel", "eval_slot", "eval_channel", "dst_slot", "dst_channel", "roi_slot", "roi_contour", "spacing", "dta",
+                "reach", "sub", "mode", "dose_tolerance", "cutoff", "skip_value", "box_lo", "box_hi"]
+    fields_r = ["stored", "evaluated", "passed", "nonfinite", "hi_value", "reserved"]
+    args = ["sizeof(vr_gamma_desc)"] + [f"offsetof(vr_gamma_desc, {f})" for f in fields_d]
+    args += ["sizeof(vr_gamma_result)"] + [f"offsetof(vr_gamma_result, {f})" for f in fields_r]
+    args += [f"(size_t)(100 + {c})" for c in ("VR_GAMMA_MAX_SUB", "VR_GAMMA_MAX_RADIUS", "VR_GAMMA_GLOBAL", "VR_GAMMA_LOCAL")]
+    src = tmp_path / "sz.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "vr.h"\nint main(){' +
+                   "".join(f'printf("%zu ", {a});' for a in args) + "return 0;}\n")
+    exe = tmp_path / "sz"
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    out = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    D, R = capi.GammaDesc, capi.GammaResult
+    want = [C.sizeof(D)] + [getattr(D, f).offset for f in fields_d] + [C.sizeof(R)] + [getattr(R, f).offset for f in fields_r]
+    want += [100 + c for c in (capi.GAMMA_MAX_SUB, capi.GAMMA_MAX_RADIUS, capi.GAMMA_GLOBAL, capi.GAMMA_LOCAL)]
+    assert out == want
+    assert (C.sizeof(D), C.sizeof(R)) == (96, 40)
+    assert (gr.MAX_SUB, gr.MAX_RADIUS, gr.GLOBAL, gr.LOCAL) == (capi.GAMMA_MAX_SUB, capi.GAMMA_MAX_RADIUS, capi.GAMMA_GLOBAL, capi.GAMMA_LOCAL) == (4, 8, 0, 1)
+    assert (gr.MAX_SPACING, gr.MAX_REACH, gr.QNAN) == (1 << 20, 1 << 24, 0x7FC00000)
+
+
+def test_entry_points_without_a_device():
+    """Every entry point refuses a NULL context (or a NULL output) with VR_ERR_INVALID_ARG; the symbols are exported."""
+    lib = capi.load()
+    d = capi.GammaDesc()
+    assert lib.vr_gamma_whole(None, 0, 3, 1, 3, 2, 0, C.byref(d)) == capi.VR_ERR_INVALID_ARG
+    assert lib.vr_volume_gamma(None, C.byref(d), None) == capi.VR_ERR_INVALID_ARG
+    assert lib.vr_gamma_counters(None, None) == capi.VR_ERR_INVALID_ARG and lib.vr_gamma_timing(None, None) == capi.VR_ERR_INVALID_ARG
+    for name in ("vr_gamma_whole", "vr_volume_gamma", "vr_gamma_counters", "vr_gamma_timing"):
+        assert name in capi.ABI_SYMBOLS and hasattr(lib, name)
+    from volumerendering_amd import host
+    assert hasattr(host.load(), "vrh_app_gamma")
+
+
+def test_gamma_desc_copy_and_result_tuple():
+    d = capi.GammaDesc()
+    e = d.copy(ref_slot=2, ref_channel=1, eval_slot=1, eval_channel=3, dst_slot=0, dst_channel=2, roi_slot=-1, roi_contour=3,
+               spacing=(1000, 1000, 3000), dta=3000, reach=6000, sub=2, mode=capi.GAMMA_LOCAL, dose_tolerance=0.03, cutoff=-2.5,
+               skip_bits=0x7FA00001, box_lo=(1, 2, 3), box_hi=(4, 5, 6))
+    assert (e.ref_slot, e.ref_channel, e.eval_slot, e.eval_channel, e.dst_slot, e.dst_channel, e.roi_slot, e.roi_contour) == (2, 1, 1, 3, 0, 2, -1, 3)
+    assert (list(e.spacing), e.dta, e.reach, e.sub, e.mode, e.dose_tolerance, e.cutoff) == ([1000, 1000, 3000], 3000, 6000, 2, 1, f32(0.03), -2.5)
+    assert bytes(e)[capi.GammaDesc.skip_value.offset:][:4] == (0x7FA00001).to_bytes(4, "little")  # (a signalling NaN keeps its bits)
+    assert list(e.box_lo) == [1, 2, 3] and list(e.box_hi) == [4, 5, 6] and bytes(e.copy()) == bytes(e)
+    r = capi.GammaResult(9, 7, 5, 1, 2.0, 0)
+    assert r.as_tuple() == (9, 7, 5, 1, 0x40000000)
+
+
+def test_the_descriptor_ranges_of_the_restatement():
+    """What needs no device: the ranges of spacing, dta, reach and sub, and reach / spacing <= 8 on every axis."""
+    ok = dict(spacing=(1000, 1000, 3000), dta=3000, reach=6000, sub=1)
+    assert gr.valid(**ok) and gr.radii(ok["spacing"], ok["reach"]) == (6, 6, 2)
+    bad = [dict(spacing=(0, 1000, 3000)), dict(spacing=(1000, (1 << 20) + 1, 3000)), dict(dta=0), dict(dta=(1 << 24) + 1), dict(reach=0),
+           dict(reach=(1 << 24) + 1), dict(sub=0), dict(sub=5), dict(reach=9000), dict(spacing=(1000, 1000, 666))]
+    for over in bad:
+        assert not gr.valid(**{**ok, **over}), over
+    assert gr.valid(**{**ok, "reach": 8999, "sub": 4}) and gr.valid((1 << 20,) * 3, 1 << 24, (1 << 23) + (1 << 20) - 1, 4)
+
+
+# ---- the restatement against an independent float64 gamma ------------------------------------------------------------------------------
+
+def gamma64(R, E, spacing, dta, reach, sub, T):
+    """The textbook definition in float64, written apart from the restatement: gamma(p) = min over the positions q = p + o / sub inside
+    the volume with |q - p| <= reach of sqrt(|q - p|^2 / dta^2 + (E(q) - R(p))^2 / T^2), E(q) the trilinear interpolant as a sum of eight
+    weighted corners.  Returns (nz, ny, nx) float64."""
+    R, E = np.asarray(R, np.float64), np.asarray(E, np.float64)
+    nz, ny, nx = R.shape
+    out = np.full(R.shape, np.inf)
+    top = [int(reach * sub // s) for s in spacing]
+    z, y, x = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
+    for k in range(-top[2], top[2] + 1):
+        for j in range(-top[1], top[1] + 1):
+            for i in range(-top[0], top[0] + 1):
+                mm = np.array([i * spacing[0], j * spacing[1], k * spacing[2]], np.float64) / sub
+                dist2 = float((mm * mm).sum())
+                if dist2 > float(reach) ** 2:
+                    continue
+                q = [x + i / sub, y + j / sub, z + k / sub]
+                inside = (q[0] >= 0) & (q[0] <= nx - 1) & (q[1] >= 0) & (q[1] <= ny - 1) & (q[2] >= 0) & (q[2] <= nz - 1)
+                fl = [np.floor(v).astype(int) for v in q]
+                w = [v - f for v, f in zip(q, fl)]
+                e = np.zeros(R.shape)
+                for cz in (0, 1):
+                    for cy in (0, 1):
+                        for cx in (0, 1):
+                            weight = (w[0] if cx else 1 - w[0]) * (w[1] if cy else 1 - w[1]) * (w[2] if cz else 1 - w[2])
+                            corner = E[np.clip(fl[2] + cz, 0, nz - 1), np.clip(fl[1] + cy, 0, ny - 1), np.clip(fl[0] + cx, 0, nx - 1)]
+                            e += np.where(weight != 0, weight * corner, 0.0)
+                g2 = dist2 / float(dta) ** 2 + ((e - R) / T) ** 2
+                out = np.where(inside & (g2 < out), g2, out)
+    return np.sqrt(out)
+
+
+def vec4(field):
+    v = np.zeros(field.shape + (4,), f32)
+    v[..., 3] = field
+    return v
+
+
+@pytest.mark.parametrize("sub", [1, 2])
+def test_dyadic_pin(sub):
+    """The stored bits equal float32(sqrt64(gamma64^2)): a condition, not a tolerance.  Every f32 step of the restatement but the square
+    root is exact on these inputs.  Doses are multiples of 1/4 in [0, 4).  t is 0 or 1/2, so a lerp fmaf(t, v - u, u) gives a multiple
+    of 1/8 after x, 1/16 after y, 1/32 after z, all below 4: at most 7 significant bits.  T = 0.125, so invT = 8 and d = (e - r) * 8 is a
+    multiple of 1/4 below 32 in magnitude.  dta = 2048 and sub = 1 or 2 make kc = 2^-22 / sub^2 a power of two; with spacing (1024,
+    1024, 3072) D2n = 2^20 (i^2 + j^2 + 9 k^2), an integer of few bits times a power of two, so (float)D2n and c = (i^2 + j^2 + 9 k^2) /
+    (4 sub^2) are exact.  d * d is a multiple of 1/16 below 1024 and c a multiple of 1/16 below 5: g2 = fmaf(d, d, c) has at most 15
+    significant bits and is exact.  float64 computes the same rationals exactly, weights included (products of halves), so both minima
+    are the same number; the f32 square root is correctly rounded, and rounding the correctly rounded float64 square root to f32 is the
+    same single rounding (53 >= 2 * 24 + 2)."""
+    rng = np.random.default_rng(5 + sub)
+    shape = (4, 5, 6)
+    R = (rng.integers(0, 16, shape) / 4.0).astype(f32)
+    E = (rng.integers(0, 16, shape) / 4.0).astype(f32)
+    spacing, dta, reach, T = (1024, 1024, 3072), 2048, 4096, 0.125
+    out, res, cnt = gr.gamma(vec4(R), vec4(E), None, 3, 3, 0, spacing, dta, reach, sub, gr.GLOBAL, T)
+    want = gamma64(R, E, spacing, dta, reach, sub, T).astype(f32)
+    assert np.array_equal(out[..., 0].view(u32), want.view(u32))
+    assert res[:2] == (R.size, R.size) and res[2] == int((want <= 1).sum()) and res[3] == 0 and res[4] == int(want.view(u32).max())
+    assert cnt == (R.size, R.size, len(gr.table(spacing, dta, reach, sub)[2]))
+
+
+NON_DYADIC_MEASURED = 2.0885098178657913e-06  # the largest |restatement - float64| of the case below, in gamma units, as measured
+
+
+def test_non_dyadic_against_float64():
+    """sub 3, random doses, 3 % / 3 mm at 1 x 1 x 3 mm with a reach of 4.5 mm on an 11 x 9 x 7 volume: the restatement (f32, the
+    header's order of operations) against the float64 textbook gamma.  Largest deviation measured on the CPU: 2.0885098e-06 in gamma
+    units, where gamma reaches 1.7915 (a few units in the last place of an f32 near 1: the dose term d * d is rounded at d up to 1.8
+    and the interpolation at doses of 50).  The bound is that value times two: only the restatement is sanity-checked here, not the
+    product."""
+    rng = np.random.default_rng(17)
+    shape = (7, 9, 11)
+    R = (50.0 + 10.0 * rng.normal(0.0, 1.0, shape)).astype(f32)
+    E = (R * f32(1.02) + rng.normal(0.0, 1.5, shape)).astype(f32)
+    spacing, dta, reach, T = (1000, 1000, 3000), 3000, 4500, 1.8
+    out, res, _ = gr.gamma(vec4(R), vec4(E), None, 3, 3, 0, spacing, dta, reach, 3, gr.GLOBAL, T)
+    want = gamma64(R, E, spacing, dta, reach, 3, float(f32(T)))
+    dev = float(np.abs(out[..., 0].astype(np.float64) - want).max())
+    print("largest deviation", dev, "largest gamma", float(want.max()))
+    assert res[1] == R.size and res[3] == 0
+    assert dev <= 2 * NON_DYADIC_MEASURED
+
+
+@pytest.mark.parametrize("sub,reach", [(1, 6000), (3, 3000)])
+def test_the_cut_is_exact(sub, reach):
+    """The restatement with the header's cut (a candidate whose c is not below the running minimum is left out; chunk=1 applies it entry
+    by entry) and without it store the same bits, and the cut visits far fewer candidates.  3 mm with a reach of 6 mm at sub 1 and of
+    3 mm at sub 3, at 1 x 1 x 3 mm on an 11 x 9 x 7 volume."""
+    rng = np.random.default_rng(23)
+    shape = (7, 9, 11)
+    R = (50.0 + 10.0 * rng.normal(0.0, 1.0, shape)).astype(f32)
+    E = (R * f32(1.02) + rng.normal(0.0, 1.0, shape)).astype(f32)
+    args = (R, E, None, (1000, 1000, 3000), 3000, reach, sub, gr.GLOBAL, 1.5, -np.inf, (0, 0, 0), (11, 9, 7))
+    full, _, n_full, K, _ = gr.field(*args)
+    cut, skipped, n_cut, _, asked = gr.field(*args, cut=True, chunk=1)
+    coarse, _, n_coarse, _, _ = gr.field(*args, cut=True, chunk=64)
+    assert not skipped.any() and 1 <= asked.min() and asked.max() <= K and n_cut <= int(asked.sum())  # (asked counts absent candidates too)
+    assert np.array_equal(full.view(u32), cut.view(u32)) and np.array_equal(full.view(u32), coarse.view(u32))
+    print("candidates visited: cut", n_cut, "coarse cut", n_coarse, "full", n_full, "K", K)
+    assert n_cut < n_coarse <= n_full and 4 * n_cut < n_full
+    a = gr.gamma(vec4(R), vec4(E), None, 3, 3, 1, *args[3:7], tol=1.5)
+    b = gr.gamma(vec4(R), vec4(E), None, 3, 3, 1, *args[3:7], tol=1.5, cut=True, chunk=1)
+    assert np.array_equal(a[0].view(u32), b[0].view(u32)) and a[1:] == b[1:]
+
+
+def brute_table(spacing, reach, sub):
+    """The admitted offsets by integer arithmetic alone, as (D2n, k, j, i) tuples, sorted."""
+    lim = (reach * sub) ** 2
+    top = [reach * sub // s for s in spacing]
+    rows = []
+    for k in range(-top[2], top[2] + 1):
+        for j in range(-top[1], top[1] + 1):
+            for i in range(-top[0], top[0] + 1):
+                d2 = (i * spacing[0]) ** 2 + (j * spacing[1]) ** 2 + (k * spacing[2]) ** 2
+                if d2 <= lim:
+                    rows.append((d2, k, j, i))
+    return sorted(rows)
+
+
+@pytest.mark.parametrize("spacing,dta,reach,sub,K", [((1000, 1000, 3000), 3000, 6000, 1, 293), ((977, 977, 2500), 2000, 3000, 2, 389),
+                                                    ((1000, 2000, 1000), 1000, 1000, 4, 125)])
+def test_offset_table_order_and_size(spacing, dta, reach, sub, K):
+    """Ascending D2n, ties by (k, j, i); K by integer arithmetic alone; entry 0 is the offset (0, 0, 0); c ascends with D2n."""
+    o, d2, c = gr.table(spacing, dta, reach, sub)
+    rows = brute_table(spacing, reach, sub)
+    assert len(rows) == len(c) == K
+    assert [(int(d), int(k), int(j), int(i)) for d, (i, j, k) in zip(d2, o)] == rows
+    assert tuple(o[0]) == (0, 0, 0) and c[0] == 0 and (np.diff(c) >= 0).all()
+    kc = f32(1.0 / (float(dta) ** 2 * sub * sub))
+    assert np.array_equal(c, np.array([f32(d) * kc for d in d2.tolist()], f32))
+    assert {tuple(v) for v in o.tolist()} == {tuple(-x for x in v) for v in o.tolist()}  # (the set is symmetric)

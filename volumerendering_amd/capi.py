@@ -53,6 +53,8 @@ FILTER_MAX_RADIUS = 32                                                      # of
 FILTER_CLAMP, FILTER_CONSTANT = 0, 1                                        # vr_filter_desc.border
 RANK_MAX_RADIUS = 3                                                         # of vr_rank_desc.radius (include/vr.h)
 RANK_MIN, RANK_MEDIAN, RANK_MAX = 0, -1, -2                                 # vr_rank_desc.rank: 0 .. N - 1, or N / 2, or N - 1
+GAMMA_MAX_SUB, GAMMA_MAX_RADIUS = 4, 8                                      # of vr_gamma_desc.sub, of reach / spacing (include/vr.h)
+GAMMA_GLOBAL, GAMMA_LOCAL = 0, 1                                            # vr_gamma_desc.mode
 DIST_MAX_SPACING, DIST_MAX_LIMIT, DIST_MAX_EXTENT = 1 << 20, 1 << 31, 1 << 30  # of a spacing, the limit, (hi - lo) * spacing per axis
 
 # every symbol include/vr.h declares (tests check that the library exports each of them)
@@ -82,6 +84,7 @@ ABI_SYMBOLS = [
     "vr_mesh_whole", "vr_volume_mesh", "vr_mesh_counters", "vr_mesh_timing",
     "vr_filter_whole", "vr_filter_gaussian", "vr_volume_filter", "vr_filter_counters", "vr_filter_timing",
     "vr_rank_whole", "vr_volume_rank", "vr_rank_counters", "vr_rank_timing",
+    "vr_gamma_whole", "vr_volume_gamma", "vr_gamma_counters", "vr_gamma_timing",
 ]
 
 
@@ -421,6 +424,46 @@ class RankResult(C.Structure):
         return int(self.stored), int(self.nonfinite), int(self.changed), int(lo), int(hi)
 
 
+class GammaDesc(C.Structure):
+    """struct vr_gamma_desc (include/vr.h): the reference, evaluated and destination slots and channels, the ROI (roi_slot -1: none),
+    the spacing, dta and reach in one integer unit, the sub-steps per voxel, the mode, the tolerance, the cutoff, what a skipped voxel
+    stores, and the voxel box of the output."""
+    _fields_ = [
+        ("ref_slot", C.c_int32), ("ref_channel", C.c_int32), ("eval_slot", C.c_int32), ("eval_channel", C.c_int32),
+        ("dst_slot", C.c_int32), ("dst_channel", C.c_int32), ("roi_slot", C.c_int32), ("roi_contour", C.c_int32),
+        ("spacing", C.c_uint32 * 3), ("dta", C.c_uint32), ("reach", C.c_uint32), ("sub", C.c_int32), ("mode", C.c_int32),
+        ("dose_tolerance", C.c_float), ("cutoff", C.c_float), ("skip_value", C.c_float),
+        ("box_lo", C.c_int32 * 3), ("box_hi", C.c_int32 * 3),
+    ]
+
+    def copy(self, **over) -> "GammaDesc":
+        """A copy with the given fields replaced (spacing / box_lo / box_hi from any sequence of three integers; skip_bits sets the
+        bits of skip_value, which a conversion through a Python float would not keep for a signalling NaN)."""
+        d = GammaDesc.from_buffer_copy(bytes(self))
+        for k, v in over.items():
+            if k == "skip_bits":
+                C.c_uint32.from_address(C.addressof(d) + GammaDesc.skip_value.offset).value = int(v)
+                continue
+            if k in ("box_lo", "box_hi"):
+                v = (C.c_int32 * 3)(*[int(x) for x in v])
+            elif k == "spacing":
+                v = (C.c_uint32 * 3)(*[int(x) for x in v])
+            setattr(d, k, v)
+        return d
+
+
+class GammaResult(C.Structure):
+    """struct vr_gamma_result: the voxels of the box, those evaluated, those that pass (G2 <= 1), those stored as NaN or +inf, the
+    greatest finite stored value of an evaluated voxel."""
+    _fields_ = [("stored", C.c_uint64), ("evaluated", C.c_uint64), ("passed", C.c_uint64), ("nonfinite", C.c_uint64),
+                ("hi_value", C.c_float), ("reserved", C.c_uint32)]
+
+    def as_tuple(self):
+        """(stored, evaluated, passed, nonfinite, the bits of hi_value)"""
+        hi = np.array([self.hi_value], np.float32).view(np.uint32)[0]
+        return int(self.stored), int(self.evaluated), int(self.passed), int(self.nonfinite), int(hi)
+
+
 class Component(C.Structure):
     """struct vr_component (include/vr.h): a component's voxels, half-open bounding box, first voxel (x, y, z) and the faces of the box
     it touches."""
@@ -639,6 +682,10 @@ def load() -> C.CDLL:
     lib.vr_volume_rank.argtypes = [vp, C.POINTER(RankDesc), C.POINTER(RankResult)]
     lib.vr_rank_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
     lib.vr_rank_timing.argtypes = [vp, C.POINTER(C.c_float * 4)]
+    lib.vr_gamma_whole.argtypes = [vp, i32, i32, i32, i32, i32, i32, C.POINTER(GammaDesc)]
+    lib.vr_volume_gamma.argtypes = [vp, C.POINTER(GammaDesc), C.POINTER(GammaResult)]
+    lib.vr_gamma_counters.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
+    lib.vr_gamma_timing.argtypes = [vp, C.POINTER(C.c_float * 4)]
     lib.vr_present_async.argtypes = [vp, vp, vp, vp]
     lib.vr_present_tiles_async.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp]
     lib.vr_hint_frames_in_flight.argtypes = [vp, i32]
@@ -1249,6 +1296,29 @@ class Context:
     def rank_timing(self):
         """(the selection kernel, further ones: 0, write + result words, refresh) of the last volume_rank in ms of device time."""
         return self._tool_timing(self.lib.vr_rank_timing)
+
+    def gamma_whole(self, ref_slot: int, ref_channel: int, eval_slot: int, eval_channel: int, dst_slot: int, dst_channel: int) -> GammaDesc:
+        """vr_gamma_whole: the descriptor of a gamma comparison of component eval_channel of volume eval_slot against component
+        ref_channel of volume ref_slot over the whole volume into component dst_channel of volume dst_slot: unit spacing,
+        dta = reach = 1, sub 1, GAMMA_GLOBAL, tolerance 1, no cutoff, no ROI, skipped voxels NaN (edit with copy)."""
+        d = GammaDesc()
+        self._chk(self.lib.vr_gamma_whole(self.h, ref_slot, ref_channel, eval_slot, eval_channel, dst_slot, dst_channel, C.byref(d)))
+        return d
+
+    def volume_gamma(self, desc: GammaDesc) -> GammaResult:
+        """vr_volume_gamma: for every voxel of the box the gamma index of the evaluated dose against the reference dose -- the least,
+        over the candidate positions within reach, of dose difference and distance combined -- into a component (synchronous)."""
+        out = GammaResult()
+        self._chk(self.lib.vr_volume_gamma(self.h, C.byref(desc), C.byref(out)))
+        return out
+
+    def gamma_counters(self):
+        """(voxels of the box, evaluated voxels, admitted offsets K) of the last volume_gamma."""
+        return self._tool_counters(self.lib.vr_gamma_counters)
+
+    def gamma_timing(self):
+        """(the search kernel, further ones: 0, write + result words, refresh) of the last volume_gamma in ms of device time."""
+        return self._tool_timing(self.lib.vr_gamma_timing)
 
     def set_volume_layout(self, mode: int):
         """0 bricked copy (default), 1 the reference's vec4 voxels only, 3 x-fastest voxels + density plane (2 was removed)."""

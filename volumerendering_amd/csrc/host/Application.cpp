@@ -532,6 +532,49 @@ int Application::Median(int srcSlot, int srcChannel, int dstSlot, int dstChannel
     return RankFilter(srcSlot, srcChannel, dstSlot, dstChannel, radiusMm, VR_RANK_MEDIAN, grid, out);
 }
 
+int Application::Gamma(int refSlot, int refChannel, int evalSlot, int evalChannel, int dstSlot, int dstChannel, float doseTolerance, double dtaMm,
+                       const double spacing[3], const GammaOptions& options, vr_gamma_result* out)
+{
+    if (!p_Ctx) return VR_ERR_NOT_READY;
+    // millimetres into whole micrometres; 0: not finite, not positive or beyond `most`
+    const auto um = [](double mm, long long most) -> uint32_t {
+        if (!std::isfinite(mm) || !(mm > 0.0) || mm * 1000.0 > (double)most) return 0u;
+        const long long v = std::llround(mm * 1000.0);
+        return v >= 1 && v <= most ? (uint32_t)v : 0u;
+    };
+    vr_gamma_desc d;
+    int rc = vr_gamma_whole(p_Ctx, refSlot, refChannel, evalSlot, evalChannel, dstSlot, dstChannel, &d);
+    if (rc != VR_OK) {
+        m_Error = "Application::Gamma: a slot or channel is out of range, or the reference slot is empty";
+        return rc;
+    }
+    for (int a = 0; a < 3; ++a) d.spacing[a] = um(spacing ? spacing[a] : 1.0, 1ll << 20);
+    d.dta = um(dtaMm, 1ll << 24);
+    d.reach = um(options.reachMm != 0.0 ? options.reachMm : 2.0 * dtaMm, 1ll << 24);
+    if (d.spacing[0] == 0u || d.spacing[1] == 0u || d.spacing[2] == 0u || d.dta == 0u || d.reach == 0u) {
+        m_Error = "Application::Gamma: dtaMm, the reach or a spacing is not finite and positive, or beyond vr_volume_gamma's range in micrometres";
+        return VR_ERR_INVALID_ARG;
+    }
+    d.sub = options.sub;
+    d.mode = options.mode;
+    d.dose_tolerance = doseTolerance;
+    d.cutoff = options.cutoff;
+    d.roi_slot = options.roiSlot;
+    d.roi_contour = options.roiContour;
+    d.skip_value = options.skipValue;
+    rc = vr_volume_gamma(p_Ctx, &d, out);
+    if (rc != VR_OK) m_Error = vr_last_error(p_Ctx);
+    return rc;
+}
+
+int Application::Gamma(int refSlot, int refChannel, int evalSlot, int evalChannel, int dstSlot, int dstChannel, float doseTolerance, double dtaMm,
+                       const VolumeFileDcm& grid, const GammaOptions& options, vr_gamma_result* out)
+{
+    const DicomVolumeParams p = grid.GetVolumeParams();
+    const double spacing[3] = {p.PixelSpacing[0], p.PixelSpacing[1], p.SliceThickness};
+    return Gamma(refSlot, refChannel, evalSlot, evalChannel, dstSlot, dstChannel, doseTolerance, dtaMm, spacing, options, out);
+}
+
 int Application::Pick(uint32_t x, uint32_t y, vr_pick_result* out)
 {
     if (!p_Ctx || !p_App) return VR_ERR_NOT_READY;

@@ -4,6 +4,7 @@
 // OnResize :299-323) without the window, the event queue and the ImGui layer.
 #pragma once
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <memory>
 #include <string>
@@ -17,6 +18,16 @@
 #include "vr.h"
 
 namespace med {
+
+// What Application::Gamma takes beyond the tolerance and the distance to agreement.
+struct GammaOptions {
+    double reachMm = 0.0;            // how far the search goes; 0: 2 * dtaMm
+    int sub = 1;                     // candidate positions per voxel step and axis, 1 .. VR_GAMMA_MAX_SUB
+    int mode = VR_GAMMA_GLOBAL;      // VR_GAMMA_LOCAL: doseTolerance is a fraction of the reference dose at the voxel
+    float cutoff = -HUGE_VALF;       // voxels whose reference dose is not >= cutoff are skipped
+    int roiSlot = -1, roiContour = 0;  // voxels outside this contour are skipped; roiSlot -1: none
+    float skipValue = NAN;           // what a skipped voxel stores
+};
 
 class Application {
 public:
@@ -155,6 +166,16 @@ public:
     int Median(int srcSlot, int srcChannel, int dstSlot, int dstChannel, double radiusMm, const double spacing[3] = nullptr,
                vr_rank_result* out = nullptr);
     int Median(int srcSlot, int srcChannel, int dstSlot, int dstChannel, double radiusMm, const VolumeFileDcm& grid, vr_rank_result* out = nullptr);
+    // The gamma index of component evalChannel of volume evalSlot against component refChannel of volume refSlot, over the whole volume
+    // into component dstChannel of volume dstSlot, on the device (vr_volume_gamma of include/vr.h).  doseTolerance is in the doses' own
+    // unit (3 % of the prescription, say: the library does not guess a normalisation dose), or a fraction under VR_GAMMA_LOCAL.
+    // Millimetres become whole micrometres by llround(mm * 1000.0): dtaMm, the reach and the spacing (x, y, z; nullptr = 1 mm; with
+    // `grid` its PixelSpacing and SliceThickness).  `out` may be nullptr.  VR_ERR_INVALID_ARG for a dtaMm, reach or spacing that is not
+    // finite and positive or leaves vr_volume_gamma's ranges, and whatever else vr_volume_gamma refuses.
+    int Gamma(int refSlot, int refChannel, int evalSlot, int evalChannel, int dstSlot, int dstChannel, float doseTolerance, double dtaMm,
+              const double spacing[3] = nullptr, const GammaOptions& options = GammaOptions(), vr_gamma_result* out = nullptr);
+    int Gamma(int refSlot, int refChannel, int evalSlot, int evalChannel, int dstSlot, int dstChannel, float doseTolerance, double dtaMm,
+              const VolumeFileDcm& grid, const GammaOptions& options = GammaOptions(), vr_gamma_result* out = nullptr);
     // the accumulated opacity at which the unlit / lit scene's surface lies (vr_set_surface_threshold: finite, 0 <= tau < 1)
     int SetSurfaceThreshold(float tau);
 

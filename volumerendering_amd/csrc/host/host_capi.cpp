@@ -570,6 +570,28 @@ int vrh_app_rank(void* a, int src_slot, int src_channel, int dst_slot, int dst_c
                   : app->RankFilter(src_slot, src_channel, dst_slot, dst_channel, radius_mm, rank, spacing, out);
     })
 }
+// Application::Gamma (vr_volume_gamma of the application's context).  grid and spacing as vrh_app_smooth takes them; reach_mm 0 = twice
+// dta_mm; skip_bits = the bits of what a skipped voxel stores
+int vrh_app_gamma(void* a, int ref_slot, int ref_channel, int eval_slot, int eval_channel, int dst_slot, int dst_channel, float dose_tolerance,
+                  double dta_mm, double reach_mm, int sub, int mode, float cutoff, int roi_slot, int roi_contour, uint32_t skip_bits, void* grid,
+                  const double* spacing, vr_gamma_result* out)
+{
+    auto* vh = static_cast<VolumeHandle*>(grid);
+    if (vh && !vh->dcm) return VR_ERR_INVALID_ARG;
+    VRH_TRY(VR_ERR_HIP, {
+        auto* app = static_cast<Application*>(a);
+        GammaOptions o;
+        o.reachMm = reach_mm;
+        o.sub = sub;
+        o.mode = mode;
+        o.cutoff = cutoff;
+        o.roiSlot = roi_slot;
+        o.roiContour = roi_contour;
+        std::memcpy(&o.skipValue, &skip_bits, sizeof skip_bits);
+        return vh ? app->Gamma(ref_slot, ref_channel, eval_slot, eval_channel, dst_slot, dst_channel, dose_tolerance, dta_mm, *vh->dcm, o, out)
+                  : app->Gamma(ref_slot, ref_channel, eval_slot, eval_channel, dst_slot, dst_channel, dose_tolerance, dta_mm, spacing, o, out);
+    })
+}
 int vrh_app_set_surface_threshold(void* a, float tau) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->SetSurfaceThreshold(tau); }) }
 void vrh_app_set_prepare_on_device(void* a, int on) { static_cast<Application*>(a)->m_PrepareOnDevice = on != 0; }
 int vrh_app_update(void* a) { VRH_TRY(VR_ERR_HIP, { return static_cast<Application*>(a)->OnUpdate(); }) }

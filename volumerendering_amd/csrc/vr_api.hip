@@ -34,6 +34,8 @@
 #include "vr_filter.h"
 // Rank filters (vr_volume_rank): keys compared as unsigned integers, nothing computed and nothing to fuse, compiled once as well
 #include "vr_rank.h"
+// The gamma index (vr_volume_gamma): every fused step an explicit fmaf whatever the arithmetic mode, compiled once as well
+#include "vr_gamma.h"
 
 #include <algorithm>
 #include <cmath>
@@ -64,6 +66,7 @@ using namespace vr;
 #include "vr_api_mesh.h"
 #include "vr_api_filter.h"
 #include "vr_api_rank.h"
+#include "vr_api_gamma.h"
 
 namespace {
 

@@ -490,6 +490,17 @@ struct RankState {
     ToolReport report;                   // phases: the selection kernel, further ones (none), write + result words, refresh_bricks
 };
 
+// The gamma index (vr_volume_gamma, vr_gamma.h): the offset table and the working field of the last call, grown on demand; what
+// vr_gamma_counters and vr_gamma_timing report.
+struct GammaState {
+    std::vector<GammaEntry> entries;     // the admitted offsets as the host built them (alive until the upload has completed) ...
+    DevBuf<GammaEntry> table;            // ... and on the device
+    DevBuf<uint2> field;                 // the bits to store and the flags of every voxel of the box
+    WordsPair<GammaWords> io;            // the evaluated, passed and non-finite counts, the greatest finite value
+    ToolReport report;                   // phases: the search kernel, further ones (none), write + result words, refresh_bricks
+    bool lds_raised = false;             // the default form's kernels may take their largest tile of dynamic LDS
+};
+
 // What the reporting calls (vr_last_counters, vr_last_kernel_flavour, vr_last_timing, vr_kernel_times, vr_kernel_choice,
 // vr_download_tiles, vr_last_block_trace) read about the most recent march launch.  vr_pick copies it out and back as one value.
 struct LastLaunch {
@@ -601,6 +612,7 @@ struct vr_ctx {
     MeshState mesh;  // surface extraction (vr_volume_mesh)
     FilterState filter;  // separable filters of a channel (vr_volume_filter)
     RankState rank;  // rank filters of a channel (vr_volume_rank)
+    GammaState gamma;  // the gamma index of two dose channels (vr_volume_gamma)
     std::string err;
 };
 

@@ -81,6 +81,7 @@ def load() -> C.CDLL:
         "vrh_app_smooth": (i32, [vp, i32, i32, i32, i32, f64, vp, C.POINTER(C.c_double * 3), C.POINTER(capi.FilterResult)]),
         "vrh_app_gradient_of_gaussian": (i32, [vp, i32, f64, vp, C.POINTER(C.c_double * 3)]),
         "vrh_app_rank": (i32, [vp, i32, i32, i32, i32, f64, i32, vp, C.POINTER(C.c_double * 3), C.POINTER(capi.RankResult)]),
+        "vrh_app_gamma": (i32, [vp, i32, i32, i32, i32, i32, i32, f32, f64, f64, i32, i32, f32, i32, i32, u32, vp, C.POINTER(C.c_double * 3), C.POINTER(capi.GammaResult)]),
         "vrh_app_slice": (i32, [vp, C.POINTER(capi.SliceDesc), vp]),
         "vrh_app_slice_through_pick": (C.c_longlong, [vp, C.POINTER(capi.PickResult), i32, i32, vp, C.c_size_t, C.POINTER(u32), C.POINTER(u32)]), "vrh_app_set_surface_threshold": (i32, [vp, f32]), "vrh_app_update": (i32, [vp]), "vrh_app_render": (i32, [vp]),
         "vrh_app_resize": (i32, [vp, u32, u32]), "vrh_app_read_frame": (i32, [vp, vp, vp, C.POINTER(u64)]),
@@ -692,6 +693,21 @@ class Application:
                spacing=None) -> capi.RankResult:
         """Application::Median: rank_filter with capi.RANK_MEDIAN."""
         return self.rank_filter(src_slot, src_channel, dst_slot, dst_channel, radius_mm, capi.RANK_MEDIAN, grid, spacing)
+
+    def gamma(self, ref_slot: int, ref_channel: int, eval_slot: int, eval_channel: int, dst_slot: int, dst_channel: int,
+              dose_tolerance: float, dta_mm: float, grid: "VolumeFile" = None, spacing=None, reach_mm: float = 0.0, sub: int = 1,
+              mode: int = capi.GAMMA_GLOBAL, cutoff: float = float("-inf"), roi_slot: int = -1, roi_contour: int = 0,
+              skip_bits: int = 0x7FC00000) -> capi.GammaResult:
+        """Application::Gamma: the gamma index of component eval_channel of volume eval_slot against component ref_channel of volume
+        ref_slot, over the whole volume into component dst_channel of volume dst_slot (vr_volume_gamma, include/vr.h).  dose_tolerance
+        in the doses' unit (a fraction with capi.GAMMA_LOCAL); dta_mm, reach_mm (0: twice dta_mm) and the spacing (as smooth takes it)
+        become whole micrometres."""
+        out = capi.GammaResult()
+        sp = (C.c_double * 3)(*[float(x) for x in spacing]) if spacing is not None else None
+        self._chk(self.lib.vrh_app_gamma(self.h, ref_slot, ref_channel, eval_slot, eval_channel, dst_slot, dst_channel, dose_tolerance, dta_mm,
+                                         reach_mm, sub, mode, cutoff, roi_slot, roi_contour, skip_bits, grid.h if grid is not None else None, sp,
+                                         C.byref(out)))
+        return out
 
     def set_surface_threshold(self, tau: float):
         """Application::SetSurfaceThreshold: the accumulated opacity at which the surface of an unlit / lit scene lies."""
