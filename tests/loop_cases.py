@@ -7,7 +7,9 @@ the tools' own tests notice an accumulator that is reset per pass, in at most th
 accumulator, the advanced index, a uniform trip count around a ballot -- is exercised in earnest only by the cases here.
 
 ROWS is the inventory: one row per loop that `for \\(.*\\+= ?(W|stride)` finds in the nine tool headers and in vr_comp.h, with what the
-loop carries and why a collective inside it is safe, both read from the code.  Harness only; the thresholds are comp_cases'."""
+loop carries and why a collective inside it is safe, both read from the code.  CHANNEL_ROWS, at the end, is the same for the ten loops
+of the channel tools (vr_filter.h, vr_rank.h, vr_gamma.h), all launched with lane_blocks.  Harness only; the thresholds are
+comp_cases'."""
 import numpy as np
 
 import raster_cases as rc
@@ -512,3 +514,51 @@ COMP_ROWS = [
     ("comp_expand_kernel", "lane", "nodes", MORE_NODES),
     ("comp_write_kernel", "tool", "box words", SCAN_BOXES + " (262 144 and 262 145 words: 128 passes, and one word of a 129th)"),
 ]
+
+
+# ---- the channel tools: filter, rank, gamma -------------------------------------------------------------------------------------------
+# Their kernels are all launched with lane_blocks: the default forms with one workgroup per TILE up to 4 x TOOL_BLOCKS = 2048 workgroups
+# (`u += gridDim.x` over the tiles), the plain forms and the writes with one lane per voxel of the box (`i += step`, step = 256 x
+# gridDim.x <= LANE_CAP).  What a later trip of a tile loop needs is the barrier at the loop's tail (the next tile overwrites the LDS the
+# last one read); what a write carries is its counts and its least and greatest key, folded once behind the loop.
+CHANNEL_HEADERS = ["vr_filter.h", "vr_rank.h", "vr_gamma.h"]
+CHANNEL_API = {"vr_filter.h": "vr_api_filter.h", "vr_rank.h": "vr_api_rank.h", "vr_gamma.h": "vr_api_gamma.h"}
+TILE_LOOP = r"for \(unsigned long long u = blockIdx\.x; u < \w+\.tiles; u \+= gridDim\.x\)"
+LANE_LOOP = r"for \(unsigned long long i = \(unsigned long long\)blockIdx\.x \* 256ull \+ threadIdx\.x; i < n; i \+= step\)"
+LANE_STEP = r"step = \(unsigned long long\)gridDim\.x \* 256ull"
+FILTER_ROUND = "test_filter_gpu.test_the_launch_loops_go_round"
+RANK_ROUND = "test_rank_gpu.test_the_launch_loops_go_round"
+GAMMA_ROUND = "test_gamma_gpu.test_the_launch_loops_go_round"
+# (header, kernel, rule, what n counts, the GPU test that takes the loop past its first trip)
+CHANNEL_ROWS = [
+    ("vr_filter.h", "filter_x_kernel", "tile", "tiles: runs of 256 outputs of a row x groups of 8 rows of the pass' region", FILTER_ROUND),
+    ("vr_filter.h", "filter_line_kernel", "tile", "tiles: 64 x by 64 outputs along the axis, for every line of the third axis", FILTER_ROUND),
+    ("vr_filter.h", "filter_plain_kernel", "lane", "voxels of the pass' region", FILTER_ROUND),
+    ("vr_filter.h", "filter_write_kernel", "lane", "box voxels", FILTER_ROUND),
+    ("vr_rank.h", "rank_tile_kernel", "tile", "tiles: 32 x 8 x 4 outputs of the box", RANK_ROUND),
+    ("vr_rank.h", "rank_plain_kernel", "lane", "box voxels", RANK_ROUND),
+    ("vr_rank.h", "rank_write_kernel", "lane", "box voxels", RANK_ROUND),
+    ("vr_gamma.h", "gamma_tile_kernel", "tile", "tiles: 32 x 8 x 4 outputs of the box", GAMMA_ROUND),
+    ("vr_gamma.h", "gamma_plain_kernel", "lane", "box voxels", GAMMA_ROUND),
+    ("vr_gamma.h", "gamma_write_kernel", "lane", "box voxels", GAMMA_ROUND),
+]
+
+# The filter's case: (nz, ny, nx) = (343, 343, 5) with r = 2 on every axis and the whole box.  x pass: 1 run x ceil(343 x 343 / 8)
+# groups of rows; y pass: 1 x ceil(343 / 64) x 343; z pass the same; all against 2048 workgroups.  Voxels against LANE_CAP lanes.
+FILTER_ROUND_SHAPE = (343, 343, 5)
+FILTER_ROUND_TILES = (14707, 2058, 2058)
+FILTER_ROUND_VOXELS = 588245
+FILTER_ROUND_TAIL = 50000  # the last voxels, x fastest: all beyond LANE_CAP, the write's second trip
+
+
+def filter_round_case(seed=73):
+    """(src, the same with the tail's channel 3 zeroed): noise in every component; in channel 3 of the last FILTER_ROUND_TAIL voxels the
+    source's greatest and least value by far and three NaN, each at least 8000 voxels (more than two slices) from the tail's start and
+    from the volume's end, so that what the passes make of them stays in the tail."""
+    src = np.random.default_rng(seed).normal(0.0, 1.0, FILTER_ROUND_SHAPE + (4,)).astype(f32)
+    n = FILTER_ROUND_VOXELS
+    for back, value in ((40000, 1000.0), (30000, -1000.0), (20000, np.nan), (15000, np.nan), (10000, np.nan)):
+        src[np.unravel_index(n - back, FILTER_ROUND_SHAPE) + (3,)] = f32(value)
+    zeroed = src.copy()
+    zeroed[..., 3] = np.where(np.arange(n) >= n - FILTER_ROUND_TAIL, f32(0.0), src[..., 3].reshape(-1)).reshape(FILTER_ROUND_SHAPE)
+    return src, zeroed

@@ -5,6 +5,8 @@ counters, in both kernel forms (flavour 0: LDS tiles; flavour 1: plain) and in t
 The default form's tile extents (csrc/vr_filter.h): the x pass takes runs of 256 outputs of a row; the y and z passes take 64 consecutive x
 by 64 outputs along the axis.  EDGE_SHAPES holds a volume one below, at and one above each of them."""
 import ctypes as C
+import os
+import re
 
 import numpy as np
 import pytest
@@ -12,6 +14,7 @@ import pytest
 import filter_ref as fr
 import host_ref as hr
 import index_edges_cases as ie
+import loop_cases as lc
 import oracle_binding as ob
 import resample_cases as rc
 import vrtest as vt
@@ -20,6 +23,8 @@ from volumerendering_amd import capi
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 W, H = 64, 48
+with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "volumerendering_amd", "csrc", "vr_filter.h")) as _f:
+    HEADER = _f.read()
 FORMS = [(0, 0), (1, 0), (0, 3), (1, 3)]  # (flavour, layout)
 SHAPES = [(6, 9, 70), (21, 37, 130), (5, 1, 70), (9, 6, 1)]  # (nz, ny, nx)
 EDGE_SHAPES = [(2, 3, 255), (2, 3, 256), (2, 3, 257), (3, 5, 63), (3, 5, 64), (3, 5, 65), (2, 63, 5), (2, 64, 5), (2, 65, 5), (63, 2, 5),
@@ -214,6 +219,25 @@ def test_rods(ctx, n):
     check(ctx, src, before, (G[2], G[2], G[2]), forms=FORMS[:3], what=n)
     far = tuple(max(0, v - 70) for v in n)
     check(ctx, src, before, (G[2], G[2], G[2]), 3, 1, capi.FILTER_CONSTANT, 4.0, (far, n), forms=FORMS[:2], what=(n, "far end"))
+
+
+def test_the_launch_loops_go_round(ctx):
+    """5 x 343 x 343 voxels with r = 2 on every axis: 14 707 tiles of the x pass, 2058 of the y pass and of the z pass for the 2048
+    workgroups the default form launches at the most, 588 245 voxels for the 524 288 lanes of the plain passes and of the write.  The
+    source's least and greatest value and its NaN lie in the last 50 000 voxels, which the write reaches on its second trip alone: the
+    result words come out of the fold across trips."""
+    src, zeroed = lc.filter_round_case()
+    shape = src.shape[:3]
+    nx, ny, nz = rc.n_of(shape)
+    run, rows, t = (int(re.search(r"constexpr int %s = (\d+);" % k, HEADER).group(1)) for k in ("kFilterRun", "kFilterRows", "kFilterT"))
+    assert -(-nx // run) * -(-(ny * nz) // rows) == lc.FILTER_ROUND_TILES[0] > lc.TOOL_BLOCKS * 4
+    assert -(-nx // 64) * -(-ny // t) * nz == lc.FILTER_ROUND_TILES[1] > lc.TOOL_BLOCKS * 4
+    assert -(-nx // 64) * -(-nz // t) * ny == lc.FILTER_ROUND_TILES[2] > lc.TOOL_BLOCKS * 4
+    assert nx * ny * nz == lc.FILTER_ROUND_VOXELS > lc.LANE_CAP
+    taps = (G[2], G[2], G[2])
+    _, res, cnt = check(ctx, src, rc.arbitrary_bits(shape, 74), taps, forms=FORMS[:2], what="round again")
+    other = fr.filter(zeroed, None, 3, 0, taps)[1]
+    assert res[1] > 0 and other[1] == 0 and res[2] != other[2] and res[3] != other[3] and cnt == (nx * ny * nz, 3 * nx * ny * nz, 3)
 
 
 def test_a_slot_of_four_gib():

@@ -1,7 +1,8 @@
 """CPU side of the gamma index (vr_volume_gamma; include/vr.h): the constants and struct layouts against the header, the entry points
 through the binding with no device, and the restatement the GPU tests compare against (gamma_ref.py): pinned bit for bit to an
 independent float64 brute-force gamma where every f32 step but the square root is exact, compared with it on random doses, its exact
-cut against the full search, and the order and size of its offset table."""
+cut against the full search, the order and size of its offset table, and the conditions that the cases of gamma_cases.py must meet
+for the GPU tests over them to test what they claim."""
 import ctypes as C
 import os
 import subprocess
@@ -9,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import gamma_cases as gc
 import gamma_ref as gr
 from volumerendering_amd import capi
 
@@ -210,3 +212,138 @@ def test_offset_table_order_and_size(spacing, dta, reach, sub, K):
     kc = f32(1.0 / (float(dta) ** 2 * sub * sub))
     assert np.array_equal(c, np.array([f32(d) * kc for d in d2.tolist()], f32))
     assert {tuple(v) for v in o.tolist()} == {tuple(-x for x in v) for v in o.tolist()}  # (the set is symmetric)
+
+
+# ---- the cases of tests/gamma_cases.py: each has the property the GPU test relies on ----------------------------------------------------
+
+def test_edge_tables_and_halos():
+    assert [len(gr.table(sub=sub, **p)[2]) for sub, p in gc.EDGE_RUNS] == [33, 257, 515]
+    assert [gc.halo(p["spacing"], p["reach"], sub) for sub, p in gc.EDGE_RUNS] == [(2, 2, 2), (3, 3, 3), (3, 3, 3)]
+    reach = []  # the furthest voxel an entry reads, base voxel or upper corner
+    for sub, p in gc.EDGE_RUNS:
+        m, f = gc.steps(sub=sub, **p)
+        reach.append((int(m.min()), int((m + (f > 0)).max())))
+    assert reach == [(-2, 2), (-2, 2), (-3, 3)]  # (sub 2 with a reach of whole voxels never reads the halo's third voxel)
+    assert sum(min(s) < 3 for s in gc.EDGE_SHAPES) == 10 and gc.TILE == (32, 8, 4)  # (in ten of the fourteen the halo of 3 is longer than an axis)
+    for a, t in enumerate(gc.TILE):  # one below, at and one above the tile on every axis; two tiles and a tail on all three
+        assert {t - 1, t, t + 1, 2 * t + 1} <= {s[2 - a] for s in gc.EDGE_SHAPES}
+    (x0, y0, z0), (x1, y1, z1) = gc.EDGE_BOX
+    assert x0 < 32 < x1 and y0 < 8 < y1 and z0 < 4 < z1 and (x1, y1, z1) < rc_n(gc.EDGE_SHAPES[-1])
+
+
+def rc_n(shape):
+    return shape[2], shape[1], shape[0]
+
+
+@pytest.mark.parametrize("shape", gc.EDGE_SHAPES, ids=lambda s: "x".join(str(v) for v in s[::-1]))
+def test_edge_shapes_separate_the_mutants(shape):
+    """Per shape and table: an evaluated voxel (every voxel: VR_GAMMA_GLOBAL, no ROI) lacks a candidate; gamma_cases.search is the
+    restatement; and its mutants store other bits in some voxel.  A position beyond a face read as the voxel at the opposite face
+    ("wrap") separates; read CLAMPED to the face it cannot, for any doses: the clamped position is itself an admitted sub-grid position
+    no further away on any axis, whose e is the same (a lerp between a value and itself is that value) and whose c is no larger, and
+    g2 is monotone in c -- asserted here as equality, so that nobody takes the NaN staging for what keeps clamped reads out.  The
+    halo one voxel short separates wherever an entry reads the halo's last voxel: at sub 1, and at sub 2 with a reach of 2.5 voxels."""
+    ref, ev = gc.edge_doses(shape)
+    R, E = ref[..., 3], ev[..., 3]
+    for sub, p in gc.EDGE_RUNS:
+        want = gr.gamma(ref, ev, None, 3, 3, 0, sub=sub, tol=gc.EDGE_TOL, **p)[0][..., 0].view(u32)
+        assert np.array_equal(gc.search(R, E, sub=sub, tol=gc.EDGE_TOL, **p), want), (shape, sub)
+        assert np.array_equal(gc.search(R, E, sub=sub, tol=gc.EDGE_TOL, beyond="clamp", **p), want), (shape, sub)
+        lacks = gc.missing(shape, sub=sub, **p)
+        wrapped = gc.search(R, E, sub=sub, tol=gc.EDGE_TOL, beyond="wrap", **p)
+        short = gc.search(R, E, sub=sub, tol=gc.EDGE_TOL, staged=gc.short_halo(p["spacing"], p["reach"], sub), **p)
+        if shape == (1, 1, 1):  # the degenerate launch: every entry but (0, 0, 0) is missing, and no read can go wrong
+            assert lacks.tolist() == [len(gr.table(sub=sub, **p)[2]) - 1]
+            assert np.array_equal(wrapped, want) and np.array_equal(short, want)
+            continue
+        assert lacks.max() > 0, (shape, sub)
+        assert (wrapped != want).any(), (shape, sub)
+        if sub == 2 and p is gc.EDGE:
+            assert np.array_equal(short, want)  # (nothing reads the third voxel: see test_edge_tables_and_halos)
+        else:
+            assert (short != want).any(), (shape, sub, p["reach"])
+
+
+@pytest.mark.parametrize("n", gc.RODS, ids=lambda n: "x".join(str(v) for v in n))
+def test_rods_pass_in_part(n):
+    ref, ev = gc.rod_doses(n)
+    _, res, cnt = gr.gamma(ref, ev, None, 3, 3, 0, sub=1, tol=gc.ROD_TOL, **gc.EDGE)
+    assert cnt == (n[0] * n[1] * n[2], n[0] * n[1] * n[2], 33) and 0 < res[2] < res[1]
+    lo, hi = gc.rod_far_box(n)
+    _, res, cnt = gr.gamma(ref, ev, None, 3, 3, 0, sub=2, tol=gc.ROD_TOL, lo=lo, hi=hi, **gc.EDGE)
+    assert cnt[2] == 257 and 0 < res[2] < res[1] == cnt[0] == int(np.prod([min(v, 70) for v in n]))
+
+
+def test_the_lone_asker_asks_alone():
+    """asked, from the restatement's exact cut: the whole table at the outlier of R and one entry at every other voxel; at the outlier
+    of E the first two entries (the second is the first with c > 0, and a neighbour agrees exactly); the same with the outlier in the
+    last partial tile of a box off the tile origin, whose lanes beside it lie beyond the box."""
+    cases = gc.lone_cases()
+    K = len(gr.table(sub=1, **gc.LONE)[2])
+    assert K == 293
+    for name in ("r", "r_box"):
+        ref, ev, at, box = cases[name]
+        asked, k, G2 = gc.asked_of(ref, ev, gc.LONE, 1, gc.LONE_TOL, box)
+        lo = box[0] if box else (0, 0, 0)
+        rel = (at[0] - lo[2], at[1] - lo[1], at[2] - lo[0])
+        assert k == K and asked[rel] == K and (np.delete(asked.reshape(-1), np.ravel_multi_index(rel, asked.shape)) == 1).all(), name
+        assert G2[rel] > 0x3F800000 and np.count_nonzero(G2) == 1, name
+    ext = [h - l for l, h in zip(*gc.LONE_BOX)]
+    rel = [gc.LONE_AT_BOX[2 - a] - gc.LONE_BOX[0][a] for a in range(3)]
+    assert [e % t for e, t in zip(ext, gc.TILE)] == [29, 6, 3] and all(r // t == (e - 1) // t for r, e, t in zip(rel, ext, gc.TILE))
+    assert [r % t for r, t in zip(rel, gc.TILE)] == [28, 5, 2]  # (the last lane, row and output of the box in its tile)
+    ref, ev, at, _ = cases["e"]
+    asked, k, G2 = gc.asked_of(ref, ev, gc.LONE, 1, gc.LONE_TOL)
+    c = gr.table(sub=1, **gc.LONE)[2]
+    assert asked[at] == 2 and c[1] > 0 and G2[at] == c.view(u32)[1] and np.count_nonzero(G2) == 1
+    assert (np.delete(asked.reshape(-1), np.ravel_multi_index(at, asked.shape)) == 1).all()
+    ref, ev, at, _ = cases["r"]  # sub 2, reach 3 mm
+    asked, k, G2 = gc.asked_of(ref, ev, gc.LONE_SUB2, 2, gc.LONE_TOL)
+    assert k == len(gr.table(sub=2, **gc.LONE_SUB2)[2]) > 100 and asked[at] == k and np.count_nonzero(asked != 1) == 1
+
+
+@pytest.mark.parametrize("sub", [1, 2])
+def test_ties_are_common_and_exact(sub):
+    ref, ev = gc.tie_doses()
+    assert set(np.unique(ref[..., 3])) == set(np.unique(ev[..., 3])) == {0.0, 1.0, 2.0, 3.0, 4.0, 5.0}
+    c = gr.table(sub=sub, **gc.TIES[sub])[2]
+    assert len(c) == {1: 123, 2: 925}[sub] and np.array_equal(c, np.rint(c)) and c.max() == {1: 9.0, 2: 36.0}[sub]
+    share, most, K = gc.tie_share(ref, ev, sub)
+    print("tie share", share, "most entries asked", most, "of", K)
+    assert share >= 0.5 and most < K
+    G2 = gr.field(ref[..., 3], ev[..., 3], None, sub=sub, mode=gr.GLOBAL, tol=gc.TIE_TOL, cutoff=-np.inf, lo=(0, 0, 0), hi=(65, 17, 9), **gc.TIES[sub])[0]
+    exact = G2 * f32(1 if sub == 1 else 16)  # (d = 2 (e - r) is an integer at sub 1 and a multiple of 1/4 at sub 2)
+    assert np.array_equal(exact, np.rint(exact)) and G2.max() < 128
+
+
+SWEEP = gc.sweep()
+
+
+def test_the_sweep_covers_what_it_claims():
+    assert len(SWEEP) == 40
+    count = lambda key, v: sum(c[key] == v for c in SWEEP)
+    assert all(count("sub", s) >= 5 for s in (1, 2, 3, 4))
+    assert all(count("roi", r) >= 4 for r in gc.ROI_KINDS)
+    assert all(count("dst", d) >= 5 for d in gc.DST_KINDS)
+    assert count("mode", gr.GLOBAL) >= 10 and count("mode", gr.LOCAL) >= 10
+    assert {c["flavour"] for c in SWEEP} == {0, 1} and {c["layout"] for c in SWEEP} == {0, 1, 3}
+    assert 8 <= sum(c["hostile"] for c in SWEEP) <= 20
+    lacking = partial = idle = 0
+    for c in SWEEP:
+        assert gr.valid(c["spacing"], c["dta"], c["reach"], c["sub"]) and max(gr.radii(c["spacing"], c["reach"])) <= 8
+        voxels = int(np.prod([h - l for l, h in zip(c["lo"], c["hi"])]))
+        assert voxels * c["K"] <= gc.MAX_CELLS and c["K"] == len(gr.table(c["spacing"], c["dta"], c["reach"], c["sub"])[2])
+        assert (voxels == 0) == (c["box"] == "empty")
+        (sr, se, sd), (cr, ce, cd), roi, vols = gc.sweep_volumes(c)
+        assert len({sr, se, sd, roi[0]} - {-1}) <= 3 and all(0 <= s <= 2 for s in vols) and (sd in vols) == (c["dst"] != "fresh")
+        assert {"none": roi[0] == -1, "eval": roi[0] == se and roi[1] != ce, "dst": roi == (sd, cd), "third": roi[0] not in (-1, sr, se, sd)}[c["roi"]]
+        _, res, _ = gr.gamma(vols[sr], vols[se], vols.get(sd), cr, ce, cd, c["spacing"], c["dta"], c["reach"], c["sub"], c["mode"], c["tol"],
+                             c["cutoff"], c["skip_bits"], None if roi[0] < 0 else vols[roi[0]], roi[1], c["lo"], c["hi"])
+        G2, skipped, _, _, _ = gr.field(vols[sr][..., cr], vols[se][..., ce], None if roi[0] < 0 else vols[roi[0]][..., roi[1]], c["spacing"],
+                                        c["dta"], c["reach"], c["sub"], c["mode"], c["tol"], c["cutoff"], c["lo"], c["hi"]) if voxels else (None, np.zeros(0, bool), 0, 0, 0)
+        lacks = gc.missing(c["shape"], c["spacing"], c["dta"], c["reach"], c["sub"], c["lo"], c["hi"]) if voxels else np.zeros(0, int)
+        lacking += bool(((lacks > 0) & ~skipped).any())
+        partial += 0 < res[2] < res[1]
+        idle += res[1] == 0
+    print("lacking", lacking, "partial", partial, "idle", idle)
+    assert lacking >= 15 and partial >= 10 and idle <= 4

@@ -3,13 +3,18 @@ slot, the result struct, all three counters and the untouched dose slots, BIT FO
 (flavour 0: LDS tiles and the exact cut; flavour 1: plain, every candidate) and in the volume layouts 0, 1 and 3.
 
 The default form's tile (csrc/vr_gamma.h) is 32 outputs along x, 8 along y and 4 along z; the volumes of 37 x 21 x 13 voxels hold two
-tiles and a tail along x, three along y and four along z."""
+tiles and a tail along x, three along y and four along z.  The cases of gamma_cases.py go to the tile's, the index range's and the
+cut's edges."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import gamma_cases as gc
 import gamma_ref as gr
+import host_ref as hr
+import index_edges_cases as ie
+import oracle_binding as ob
 import resample_cases as rc
 import vrtest as vt
 from volumerendering_amd import capi
@@ -21,16 +26,10 @@ FORMS = [(0, 0), (1, 0), (0, 1), (1, 1), (0, 3), (1, 3)]  # (flavour, layout)
 SHAPE = (13, 21, 37)  # (nz, ny, nx)
 S = (1000, 1000, 3000)  # 1 x 1 x 3 mm in micrometres
 GLOBAL, LOCAL, QNAN = capi.GAMMA_GLOBAL, capi.GAMMA_LOCAL, gr.QNAN
-PAYLOAD = 0x7FA12345  # a signalling NaN with a payload
+PAYLOAD = gc.PAYLOAD  # a signalling NaN with a payload
 
 
-def doses(shape, seed, shift=1.03, noise=0.4):
-    """Two dose volumes around 20 with every other component arbitrary: the evaluated one the reference scaled and perturbed."""
-    rng = np.random.default_rng(seed)
-    ref, ev = rc.volume(shape, seed), rc.volume(shape, seed + 1)
-    ref[..., 3] = (20.0 + 5.0 * rng.normal(0.0, 1.0, shape)).astype(f32)
-    ev[..., 3] = (ref[..., 3] * f32(shift) + rng.normal(0.0, noise, shape)).astype(f32)
-    return ref, ev
+doses = gc.doses
 
 
 def describe(ctx, slots, chans, p):
@@ -40,13 +39,15 @@ def describe(ctx, slots, chans, p):
 
 
 def check(ctx, ref, ev, before, spacing=S, dta=3000, reach=3000, sub=1, mode=GLOBAL, tol=0.6, cutoff=-np.inf, skip_bits=QNAN, roi=(-1, 0),
-          box=None, chans=(3, 3, 0), slots=(0, 1, 2), forms=FORMS[:2], what=None):
+          box=None, chans=(3, 3, 0), slots=(0, 1, 2), forms=FORMS[:2], what=None, extra=None):
     """One descriptor in every form against the restatement.  ref, ev: the voxels of slots[0] and slots[1] (one array when they are one
-    slot); before: the voxels of slots[2] before the call (ignored where it is a dose's slot).  roi: (slot, contour), the slot one of
-    the three.  Every slot is uploaded again for every form.  Returns the restatement's (volume, result, counters)."""
+    slot); before: the voxels of slots[2] before the call (ignored where it is a dose's slot; None: the slot is empty and the call
+    creates it -- one form only).  roi: (slot, contour), the slot one of the three or one of extra = {slot: voxels}.  Every slot is
+    uploaded again for every form.  Returns the restatement's (volume, result, counters)."""
     shape = ref.shape[:3]
     lo, hi = box if box else ((0, 0, 0), rc.n_of(shape))
-    vols = {slots[2]: before}
+    vols = dict(extra or {})
+    vols[slots[2]] = before
     vols[slots[1]] = ev
     vols[slots[0]] = ref
     p = dict(spacing=spacing, dta=dta, reach=reach, sub=sub, mode=mode, tol=tol, cutoff=cutoff, skip_bits=skip_bits, roi=roi, lo=lo, hi=hi)
@@ -56,7 +57,8 @@ def check(ctx, ref, ev, before, spacing=S, dta=3000, reach=3000, sub=1, mode=GLO
         ctx.set_kernel_flavour(flavour)
         ctx.set_volume_layout(layout)
         for slot, v in vols.items():
-            ctx.volume_upload(slot, v)
+            if v is not None:
+                ctx.volume_upload(slot, v)
         res = ctx.volume_gamma(describe(ctx, slots, chans, p))
         cnt = ctx.gamma_counters()
         got = ctx.volume_download(slots[2], shape)
@@ -253,6 +255,177 @@ def test_the_launch_loops_go_round(ctx):
     ev[..., 3] = (ref[..., 3] + rng.normal(0.0, 1.0, shape)).astype(f32)
     _, res, cnt = check(ctx, ref, ev, np.zeros(shape + (4,), f32), spacing=(1000, 1000, 1000), dta=1000, reach=1000, tol=1.0, what="round again")
     assert cnt == (ref[..., 3].size, ref[..., 3].size, 7) and 0 < res[2] < res[1]
+
+
+# ---- the cases of tests/gamma_cases.py (tests/test_gamma.py shows on the CPU that each has the property it is here for) -----------------
+
+@pytest.mark.parametrize("shape", gc.EDGE_SHAPES, ids=lambda s: "x".join(str(v) for v in s[::-1]))
+def test_tile_edges(ctx, shape):
+    """One below, at and one above the tile's 32, 8 and 4 outputs, axes of one voxel, one voxel in all, and two tiles and a tail on
+    every axis at once; a reach of two voxels at sub 1 and 2 and of two and a half at sub 2, where the halo's third voxel is read: the
+    halo is longer than an axis in ten of the fourteen."""
+    ref, ev = gc.edge_doses(shape)
+    before = rc.arbitrary_bits(shape, 13)
+    last = shape == gc.EDGE_SHAPES[-1]
+    for sub, p in gc.EDGE_RUNS:
+        check(ctx, ref, ev, before, sub=sub, tol=gc.EDGE_TOL, forms=FORMS[:2] + (FORMS[4:5] if last else []), what=(shape, sub, p["reach"]), **p)
+    if last:
+        for sub, p in gc.EDGE_RUNS:
+            _, res, _ = check(ctx, ref, ev, before, sub=sub, mode=LOCAL, tol=0.03, box=gc.EDGE_BOX, chans=(3, 3, 1), what=(shape, sub, "box"), **p)
+            assert res[0] == res[1] == 5 * 4 * 4
+
+
+@pytest.mark.parametrize("n", gc.RODS, ids=lambda n: "x".join(str(v) for v in n))
+def test_rods(ctx, n):
+    """Axes of 65535 voxels: 2048 tiles along x, 8192 along y, 16384 along z (the tile loop goes round), a reach of two voxels."""
+    ref, ev = gc.rod_doses(n)
+    before = rc.arbitrary_bits(ref.shape[:3], 72)
+    _, res, _ = check(ctx, ref, ev, before, sub=1, tol=gc.ROD_TOL, forms=FORMS[:2] + FORMS[4:5], what=n, **gc.EDGE)
+    assert 0 < res[2] < res[1]
+    _, res, _ = check(ctx, ref, ev, before, sub=2, tol=gc.ROD_TOL, box=gc.rod_far_box(n), chans=(3, 3, 2), what=(n, "far end"), **gc.EDGE)
+    assert 0 < res[2] < res[1]
+
+
+def lone_gamma64(ref, ev, at, p, tol):
+    """gamma at voxel `at` (z, y, x) at sub 1, in float64 from the definition."""
+    o, d2, _ = gr.table(sub=1, **p)
+    z, y, x = at
+    best = np.inf
+    for (i, j, k), d in zip(o.tolist(), d2.tolist()):
+        q = (z + k, y + j, x + i)
+        if all(0 <= v < m for v, m in zip(q, ref.shape[:3])):
+            best = min(best, d / float(p["dta"]) ** 2 + ((float(ev[q + (3,)]) - float(ref[at + (3,)])) / float(f32(tol))) ** 2)
+    return float(np.sqrt(best))
+
+
+def test_a_lone_asker(ctx):
+    """One lane asks for all 293 entries, every other lane of the launch for entry 0 alone: the 63 beside it compute in step with it
+    and their minima of +0 do not move.  The other way round the outlier stops at entry 1.  With the outlier in the last partial tile of
+    a box off the tile origin the lanes beside it lie beyond the box."""
+    cases = gc.lone_cases()
+    zeros = np.zeros(gc.LONE_SHAPE + (4,), f32)
+    for name in ("r", "e", "r_box"):
+        ref, ev, at, box = cases[name]
+        want, res, cnt = check(ctx, ref, ev, zeros, tol=gc.LONE_TOL, box=box, what=name, **gc.LONE)
+        stored = vt.bits(want[..., 0])
+        assert np.count_nonzero(stored) == 1 and not vt.bits(want[..., 1:]).any() and cnt[2] == 293 and res[1] == res[0], name
+        if name == "e":
+            assert stored[at] == vt.bits(np.sqrt(gr.table(sub=1, **gc.LONE)[2][1:2]))[0] and res[2] == res[1]
+        else:
+            g = lone_gamma64(ref, ev, at, gc.LONE, gc.LONE_TOL)
+            assert abs(float(want[at + (0,)]) - g) <= 4e-7 * g and g > 100.0 and res[2] == res[1] - 1, (name, g)  # (a few roundings of 2^-24)
+    ref, ev, at, _ = cases["r"]
+    want, res, _ = check(ctx, ref, ev, zeros, tol=gc.LONE_TOL, sub=2, what="r, sub 2", **gc.LONE_SUB2)
+    assert np.count_nonzero(vt.bits(want[..., 0])) == 1 and want[at + (0,)] > 100.0
+
+
+@pytest.mark.parametrize("sub", [1, 2])
+def test_exact_ties(ctx, sub):
+    """Integer doses and integer c: in three voxels of four the running minimum equals the c of the entry that ends the search, bit
+    for bit (`c < best` is strict, and the lanes that finished keep computing with minima that must not move)."""
+    ref, ev = gc.tie_doses()
+    _, res, cnt = check(ctx, ref, ev, rc.arbitrary_bits(gc.TIE_SHAPE, 14), sub=sub, tol=gc.TIE_TOL, what=("ties", sub), **gc.TIES[sub])
+    assert cnt[2] == {1: 123, 2: 925}[sub] and 0 < res[2] < res[1] and res[3] == 0
+
+
+def test_the_roi_may_be_the_destination(ctx, pair, before):
+    """The ROI is the very contour the result overwrites (with NaN, in, and -0.0f, out); and the ROI lies in a third slot while the
+    result overwrites R."""
+    ref, ev = pair
+    rng = np.random.default_rng(15)
+    m = np.where(rng.random(SHAPE) < 0.5, f32(1.0), f32(0.0)).astype(f32)
+    m[rng.random(SHAPE) < 0.1] = f32(np.nan)
+    m[rng.random(SHAPE) < 0.1] = f32(-0.0)
+    mine = before.copy()
+    mine[..., 1] = m
+    _, res, _ = check(ctx, ref, ev, mine, reach=6000, roi=(2, 1), chans=(3, 3, 1), skip_bits=PAYLOAD, what="roi is dst")
+    assert res[1] == int(gr.member(m).sum()) and 0 < res[1] < res[0] and np.isnan(m).any() and (vt.bits(m) == 0x80000000).any()
+    _, res, _ = check(ctx, ref, ev, mine, sub=2, roi=(2, 1), chans=(3, 3, 1), skip_bits=0, what="roi is dst, sub 2")
+    third = rc.volume(SHAPE, 16)
+    third[..., 2] = m
+    _, res, _ = check(ctx, ref, ev, None, reach=6000, roi=(2, 2), chans=(3, 3, 3), slots=(0, 1, 0), skip_bits=PAYLOAD, extra={2: third}, what="third slot")
+    assert res[1] == int(gr.member(m).sum())
+
+
+def test_a_slot_of_four_gib():
+    """A slot of 512 x 512 x 1032 voxels, 4.03 GiB: R in channel 3, E in channel 2, gamma into channel 0 of the same slot, in a box of
+    five slabs across voxel index 2^28 (the start of slab z = 1024).  3 mm / 3 mm at 1 x 1 x 3 mm: 31 offsets, one slab along z, so the
+    box equals the restatement of the slabs z0 - 1 .. z1 + 1 alone; every slab near the box and every 16th slab of the rest against the
+    source."""
+    shape = (ie.A1[2], ie.A1[1], ie.A1[0])
+    z0, z1 = ie.LINE_Z - 2, ie.LINE_Z + 3
+    lo, hi = (100, 200, z0), (391, 263, z1)
+    band, ev = doses((z1 - z0 + 8, shape[1], shape[2]), 81)
+    band[..., 2] = ev[..., 3]
+    del ev
+    src = np.zeros(shape + (4,), f32)
+    src[z0 - 4:z1 + 4] = band
+    sub = src[z0 - 1:z1 + 1]
+    want, want_res, want_cnt = gr.gamma(sub, sub, sub, 3, 2, 0, S, 3000, 3000, tol=0.6, lo=(lo[0], lo[1], 1), hi=(hi[0], hi[1], 1 + z1 - z0))
+    assert want_cnt == (291 * 63 * 5, 291 * 63 * 5, 31) and 0 < want_res[2] < want_res[1] and gr.radii(S, 3000)[2] == 1
+    with capi.Context(W, H, 0) as c:
+        c.volume_upload(0, src)
+        for flavour in (0, 1):
+            c.set_kernel_flavour(flavour)
+            d = c.gamma_whole(0, 3, 0, 2, 0, 0).copy(spacing=S, dta=3000, reach=3000, dose_tolerance=0.6, box_lo=lo, box_hi=hi)
+            res = c.volume_gamma(d)
+            assert res.as_tuple() == want_res and c.gamma_counters() == want_cnt, flavour
+            got = c.volume_download(0, shape)
+            assert np.array_equal(vt.bits(got[z0:z1]), vt.bits(want[1:1 + z1 - z0])), flavour
+            for sl in (slice(z0 - 8, z0), slice(z1, shape[0]), slice(0, z0 - 8, 16)):
+                assert np.array_equal(vt.bits(got[sl]), vt.bits(src[sl])), (flavour, sl)
+            del got
+            if flavour == 0:
+                c.volume_upload(0, src)
+
+
+def test_everything_derived_is_fresh():
+    """After a gamma into channel 3 of a rendered slot the next vr_render equals the oracle's frame for the restatement's volume, and the
+    other tools' reports stay what they were."""
+    n = 24
+    shape = (n, n, n)
+    v = ob.normalize_data(hr.raw_to_vec4(hr.ct_phantom_raw(n)))
+    e = v.copy()
+    e[..., 3] = f32(1.0) - v[..., 3]
+    tf = (hr.default_opacity_tf(256), hr.default_color_tf(256))
+    step, count = hr.stepping_params(n, n, n)
+    u = hr.make_uniforms(W, H, steps_count=count, step_size=step)
+    p = dict(spacing=(1000, 1000, 1000), dta=2000, reach=2000)
+    want, want_res, want_cnt = gr.gamma(v, e, v, 3, 3, 3, tol=1.0, **p)
+    assert 0.0 <= v[..., 3].min() and v[..., 3].max() <= 1.0 and want[..., 3].max() <= 1.0 and want_res[3] == 0  # (|1 - 2 v| <= 1 at the voxel itself)
+    with capi.Context(W, H, 0) as c:
+        c.volume_upload(0, v)
+        c.volume_upload(1, e)
+        c.tf_upload(0, *tf)
+        c.set_uniforms(vt.to_capi_uniforms(u))
+        c.render(capi.BASIC)
+        before_frame = c.download()[0]
+        tools = lambda: (c.morph_counters(), c.dist_counters(), c.resample_counters(), c.mesh_counters(), c.grow_counters(), c.hist_counters(),
+                         c.filter_counters(), c.rank_counters())
+        seen = tools()
+        assert c.gamma_counters() == (0, 0, 0) and c.gamma_timing() == (0.0, 0.0, 0.0, 0.0)
+        res = c.volume_gamma(c.gamma_whole(0, 3, 1, 3, 0, 3).copy(dose_tolerance=1.0, **p))
+        assert res.as_tuple() == want_res and c.gamma_counters() == want_cnt
+        assert seen == tools()
+        c.render(capi.BASIC)
+        frame, _, samples = c.download()
+        assert np.array_equal(vt.bits(c.volume_download(0, shape)), vt.bits(want))
+    ref, n_ref, _ = ob.render(ob.BASIC, u, [want], [tf], W, H, nthreads=4)
+    assert samples == n_ref and n_ref > 0
+    assert np.array_equal(vt.bits(frame), vt.bits(ref)) and not np.array_equal(vt.bits(frame), vt.bits(before_frame))
+
+
+SWEEP = gc.sweep()
+
+
+@pytest.mark.parametrize("i", range(len(SWEEP)))
+def test_random_sweep(i):
+    case = SWEEP[i]
+    slots, chans, roi, vols = gc.sweep_volumes(case)
+    extra = {roi[0]: vols[roi[0]]} if roi[0] >= 0 and roi[0] not in slots else None
+    with capi.Context(W, H, 0) as c:
+        check(c, vols[slots[0]], vols[slots[1]], vols.get(slots[2]), case["spacing"], case["dta"], case["reach"], case["sub"], case["mode"], case["tol"],
+              case["cutoff"], case["skip_bits"], roi, (case["lo"], case["hi"]), chans, slots, [(case["flavour"], case["layout"])], case, extra)
 
 
 def test_timing_and_the_other_tools_reports(ctx, pair):

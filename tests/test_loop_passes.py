@@ -278,3 +278,69 @@ def test_the_rod_reference_counts():
         got = lc.banded_extract(v, lc.ROD_LEVEL, cap, lo, hi, mr.extract)
         assert got["result"][:4] == mr.counts(v, lc.ROD_LEVEL, cap, lo, hi) and got["result"][1] > 1000
         assert got["result"][5][2] == 65535 - 1 + cap and got["result"][4][2] == -cap
+
+
+# ---- the channel tools: vr_filter.h, vr_rank.h, vr_gamma.h -------------------------------------------------------------------------------
+
+def channel_loops(header):
+    """[(kernel, rule)] of every grid-stride loop of a channel tool's header, in order: a tile loop steps by gridDim.x, a lane loop by
+    `step`, which its kernel sets to 256 x gridDim.x."""
+    out, kernel, has_step = [], None, False
+    for line in text(header).splitlines():
+        m = re.search(r"__global__.* void (\w+)\(", line)
+        if m:
+            kernel, has_step = m.group(1), False
+        has_step = has_step or bool(re.search(lc.LANE_STEP, line))
+        if re.search(lc.TILE_LOOP, line):
+            out.append((kernel, "tile"))
+        elif re.search(lc.LANE_LOOP, line):
+            assert has_step, kernel
+            out.append((kernel, "lane"))
+        else:
+            assert not re.search(r"for \(.*\+= ?(gridDim|step|stride|W)\b", line), (kernel, line)  # (no grid-stride loop of another shape)
+    return out
+
+
+def test_every_loop_of_the_channel_tools_has_a_row():
+    found = [(h, k, rule) for h in lc.CHANNEL_HEADERS for k, rule in channel_loops(h)]
+    assert found == [(h, k, rule) for h, k, rule, _, _ in lc.CHANNEL_ROWS] and len(found) == 10
+    for header in lc.CHANNEL_HEADERS:  # one loop per kernel, and no kernel without one
+        kernels = re.findall(r"__global__.* void (\w+)\(", text(header))
+        assert kernels == [k for h, k, _ in found if h == header], header
+    for header, kernel, rule, counts, test in lc.CHANNEL_ROWS:
+        api = text(lc.CHANNEL_API[header])
+        launches = list(re.finditer(r"hipLaunchKernelGGL\(\(?" + kernel + r"\b(?:<[^>]*>)?\)?, (.*?), dim3\(256\)", api))
+        assert launches, kernel
+        for m in launches:
+            grid, at = m.group(1), m.start()
+            if "blocks" in grid and "lane_blocks(" not in grid:  # a grid computed on an earlier line
+                grid = re.findall(r"(?:const unsigned blocks = |const dim3 blocks\()(\w+\()", api[:at])[-1]
+            assert "lane_blocks(" in grid, (kernel, grid)
+        module, name = test.split(".")
+        with open(os.path.join(ROOT, "tests", module + ".py")) as f:
+            assert re.search(r"^def " + name + r"\(", f.read(), re.M), test
+        assert counts
+
+
+def test_the_filter_case_goes_round_in_every_loop():
+    """The tiles and voxels of tests/loop_cases.py's filter case from the tile constants of csrc/vr_filter.h and the launch rule, each
+    past the 2048 workgroups or the 524 288 lanes of one trip with a partial last trip; and the tail of the volume, which the write
+    reaches on its second trip alone, decides all three result words."""
+    import filter_ref as fr
+    src = text("vr_filter.h")
+    run, rows, t = (int(re.search(r"constexpr int %s = (\d+);" % k, src).group(1)) for k in ("kFilterRun", "kFilterRows", "kFilterT"))
+    nz, ny, nx = lc.FILTER_ROUND_SHAPE
+    tiles = (-(-nx // run) * -(-(ny * nz) // rows), -(-nx // 64) * -(-ny // t) * nz, -(-nx // 64) * -(-nz // t) * ny)
+    assert tiles == lc.FILTER_ROUND_TILES and nx * ny * nz == lc.FILTER_ROUND_VOXELS
+    for n in tiles:
+        assert lc.lane_blocks(256 * n) == 4 * lc.TOOL_BLOCKS < n and n % (4 * lc.TOOL_BLOCKS)
+    assert lc.passes("lane", lc.FILTER_ROUND_VOXELS)[:2] == (2, lc.FILTER_ROUND_VOXELS - lc.LANE_CAP)
+    assert lc.FILTER_ROUND_VOXELS - lc.FILTER_ROUND_TAIL >= lc.LANE_CAP
+    a, b = lc.filter_round_case()
+    w = np.random.default_rng(102).normal(0.0, 0.3, 5).astype(np.float32)  # (test_filter_gpu's G[2])
+    out, res, _ = fr.filter(a, None, 3, 0, (w, w, w))
+    _, other, _ = fr.filter(b, None, 3, 0, (w, w, w))
+    assert res[1] > 0 and other[1] == 0 and res[2] != other[2] and res[3] != other[3]
+    head = out[..., 0].reshape(-1)[:lc.LANE_CAP]  # the first trip's voxels hold neither a NaN nor the extremes
+    assert np.isfinite(head).all() and fr.key(head).min() > fr.key(np.array([res[2]], np.uint32).view(np.float32))[0]
+    assert fr.key(head).max() < fr.key(np.array([res[3]], np.uint32).view(np.float32))[0]
